@@ -1,16 +1,23 @@
 """bench.py — RRNet train-step throughput on MI355X (BASELINE.json metric: images/sec, train step).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
 Workload (BASELINE.json configs[1]): RRNet hourglass-104 (2 stacks), B=8 per GPU, 1024x1024
 synthetic VisDrone-shaped frames, fp32; one "step" = forward + focal/L1/stage-2 losses + backward
 + (RCCL gradient all-reduce when N>1) + fused Adam — nothing skipped.  Weak scaling: B=8 per GPU.
-Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line carrying
-`roofline` (dominant kernel = the implicit-GEMM forward convolution, MFMA-bound; per-launch
-durations measured live with HIP events on the launch stream) and `cpu_baseline` (the oracle's
-torch-CPU restatement of the same step, timed on this box's host cores on a bounded sample).
+Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs when
+--dump-outputs is given, and prints the headline line.  Every step, warm-up included, starts from
+the seeded initial parameters and optimizer state (restored outside the clock), so the same
+arguments give the same computation in every run.  --full adds everything else to that line:
+`roofline` and `kernels` (dominant kernel = the implicit-GEMM forward convolution, MFMA-bound;
+per-launch durations measured live with HIP events on the launch stream, inside the timed steps),
+the secondary workloads (`config5`, `config4`, `config2_f16x3`), the host-fed variant
+(`input_residency_host`) and `cpu_baseline` (the oracle's torch-CPU restatement of the same step,
+timed on this box's host cores on a bounded sample); the --no-* options switch parts of it off.
 """
 import argparse
 import json
@@ -38,6 +45,10 @@ def parse():
     ap.add_argument("--batch", type=int, default=8, help="images per GPU (BASELINE config: 8)")
     ap.add_argument("--size", type=int, default=1024, help="frame height = width (BASELINE config: 1024)")
     ap.add_argument("--backbone", default="hourglass", choices=["hourglass", "hourglass_tiny"])
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step computed (model "
+                    "logits and losses; large arrays as a fixed, seeded sample) as DIR/<name>.npy, float32, <= 64 MB in all")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline: kernel timing and "
+                    "roofline, secondary workloads, host-fed variant, CPU baseline (each can be switched off by its --no-* option)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the config-5 / config-4 secondary workloads")
     ap.add_argument("--extra-frames", type=int, default=10000, help="frames of the config-5 pass (BASELINE: 10k frames)")
@@ -46,7 +57,7 @@ def parse():
     ap.add_argument("--time-every", type=int, default=4, help="HIP-event pair around every n-th launch of the dominant kernel")
     ap.add_argument("--math", default="f32", choices=["f32", "f16x3"], help="cfg.Model.conv_math of the timed train step (f16x3: "
                     "split-operand kernels on the large layers; the default line stays on the fp32 matrix instruction)")
-    ap.add_argument("--detail", action="store_true", help="print a per-layer-shape conv time table to stderr")
+    ap.add_argument("--detail", action="store_true", help="print a per-layer-shape conv time table to stderr (--full)")
     ap.add_argument("--no-host-fed", action="store_true", help="skip the host-fed variant of the headline (pinned host pool -> "
                     "copy stream -> device slots; reported as the extra key `input_residency_host`)")
     return ap.parse_args()
@@ -255,6 +266,33 @@ def host_fed_steps(op, cfg, a, step_no):
                    "built on the device from the copied annotations inside the timed region"}
 
 
+DUMP_BYTES = 60 << 20              # --dump-outputs: all arrays together stay under 64 MB
+DUMP_MAX_ELEMS = 1 << 20           # a larger output is written as a fixed, seeded sample of this many elements
+def dump_outputs(path, outs, losses):
+    """--dump-outputs: what the last timed step handed its caller, as <path>/<name>.npy in float32 — RRNet's per-stack
+    heat-map / size / offset logits and the five losses.  An array of more elements than the per-array cap is written as
+    <name>_sample.npy: the elements (flattened in logical order) at sorted distinct positions drawn by a generator seeded
+    with the array's index, so that the same arguments give the same positions.
+    The step's RoIs, their scores and classes and the stage-2 regression over them are not written: stage 1 keeps the top
+    1500 of 655 360 class-pixel scores per image, tied at the cut within the logits' rounding, so which RoIs are kept (and
+    in which order among equal scores) changes with the rounding of the float atomics from run to run.  What is computed
+    from them, the stage-2 loss, is written and agrees to rounding."""
+    import numpy as np
+    hms, whs, offs = outs[:3]
+    arrays = [("hm_%d" % i, t) for i, t in enumerate(hms)] + [("wh_%d" % i, t) for i, t in enumerate(whs)] + \
+             [("offset_%d" % i, t) for i, t in enumerate(offs)] + \
+             list(zip(("loss", "hm_loss", "wh_loss", "offset_loss", "s2_reg_loss"), losses))
+    cap = min(DUMP_MAX_ELEMS, DUMP_BYTES // 4 // len(arrays))
+    os.makedirs(path, exist_ok=True)
+    for i, (name, t) in enumerate(arrays):
+        t = t.detach().float()
+        if t.numel() > cap:
+            pos = np.sort(np.random.default_rng(i).choice(t.numel(), cap, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(pos).to(t.device)]
+            name += "_sample"
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+
+
 def self_launch(n):
     """`python bench.py --gpus N ...` without launcher variables -> run N ranks under torch.distributed.run as a child
     process with the same arguments; returns its exit code.  Nothing here imports or initialises the GPU runtime."""
@@ -326,12 +364,37 @@ def main():
         # the criterion converts annos xywh -> xyxy IN PLACE (as the reference does): hand it a copy
         return (b[0], b[1].clone()) + tuple(b[2:])
 
+    # Every step starts from the seeded initial state: parameters, BatchNorm buffers, Adam moments and step count, learning
+    # rate.  A step's float atomics (split-K convolutions, weight gradients) leave rounding-sized differences between runs,
+    # which the ill-conditioned deep gradients and Adam's near-sign first updates magnify; steps chained from one another
+    # would compute from different parameters in every run.  Restored outside the clock, so each step costs what a
+    # training step costs.
+    opt = op.optimizer
+    flat0 = opt.fp.flat.clone()
+    bufs = [b for b in op.model.buffers()]
+    bufs0 = [b.clone() for b in bufs]
+    sched0, lrs0 = op.lr_sch.state_dict(), [g["lr"] for g in opt.param_groups]
+
+    def restore():
+        with torch.no_grad():
+            opt.fp.flat.copy_(flat0)
+            for b, b0 in zip(bufs, bufs0):
+                b.copy_(b0)
+            opt.exp_avg.zero_()
+            opt.exp_avg_sq.zero_()
+        opt.step_count = 0
+        op.lr_sch.load_state_dict(sched0)
+        for g, lr in zip(opt.param_groups, lrs0):
+            g["lr"] = lr
+        opt.fp.refresh_wt()           # the flipped-filter cache follows the restored parameters (as after an Adam step)
+
     step_no = 0
     for _ in range(a.warmup):
+        restore()
         op.train_step(step_no, fresh(batches[step_no % len(batches)]))
         step_no += 1
     timer = None
-    if not a.no_kernel_timing:
+    if a.full and not a.no_kernel_timing:
         # HIP events around every launch of the dominant kernel (the roofline leg); --detail times all conv kernels
         timer = ops.KernelTimer(None if a.detail else {"conv_fprop<BN=128,vec4>" + ("+f16x3" if a.math == "f16x3" else "")},
                                 every=1 if a.detail else a.time_every)
@@ -341,20 +404,29 @@ def main():
     dptrace.reset()
     ops.SYNC_WAIT_S = 0.0
     host_s = 0.0
-    t0 = time.perf_counter()
-    last = None
+    elapsed = 0.0
+    outs = last = None
     for _ in range(a.steps):
+        restore()
+        batch = fresh(batches[step_no % len(batches)])
+        torch.cuda.synchronize()
         h0 = time.perf_counter()
-        last = op.train_step(step_no, fresh(batches[step_no % len(batches)]))[1]
+        outs, last = op.train_step(step_no, batch)
         host_s += time.perf_counter() - h0
+        torch.cuda.synchronize()
+        elapsed += time.perf_counter() - h0
+        if not a.dump_outputs:
+            outs = None
         step_no += 1
     sync_all()
-    elapsed = time.perf_counter() - t0
     # a timing on non-finite numbers is not a timing (NaN arithmetic draws less power: every kernel runs faster)
     finite = bool(all(torch.isfinite(v.detach()).all() for v in last)) and bool(torch.isfinite(op.optimizer.fp.grad).all()) \
         and bool(torch.isfinite(op.optimizer.fp.flat).all())
     if not finite:
         raise RuntimeError("bench.py: non-finite losses / gradients / parameters after the timed steps")
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, outs, last)
+    outs = None
     # the loss tensors hold the last step's autograd graph, whose nodes keep what they attached to their ctx by hand (shared
     # fan-in buffers, bf16 images, parameter references): 20 GiB that counted into the extras' allocator peaks (round 5)
     last = None
@@ -446,14 +518,14 @@ def main():
                               dist.get_backend()
         if a.backbone == "hourglass" and a.size == 1024:
             out["step_mfma_frac"] = round(out["value"] / world * ALGO_TFLOP_PER_IMAGE / (2500.0 / 3.0 if a.math == "f16x3" else FP32_MFMA_PEAK_TFLOPS), 4)
-        if world == 1 and not a.no_extras:
+        if world == 1 and a.full and not a.no_extras:
             del op, batches
             import gc
             gc.collect()
             torch.cuda.empty_cache()
             op = batches = None
             out.update(extras(a))
-        if world == 1 and not a.no_host_fed and a.math == "f32":
+        if world == 1 and a.full and not a.no_host_fed and a.math == "f32":
             # the reference's hand-over: host batches, one PCIe crossing per step (rrnet_amd/datasets/synthetic.py:
             # HostFedDronesDET: pinned pool, copy stream one batch ahead, event-ordered).  Run LAST among the GPU workloads, on an
             # operator of its own when the headline's was released for the extras: measured in this process, the f16x3 step that
@@ -472,7 +544,7 @@ def main():
             except Exception as e:
                 out["input_residency_host"] = {"value": None, "error": repr(e)}
             del op
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(cfg.seed)
             except Exception as e:                                   # the baseline must never sink the GPU number

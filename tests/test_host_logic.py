@@ -215,3 +215,42 @@ def test_bench_self_launches_child_ranks_when_no_launcher_started_it():
     assert "starting 2 ranks" in r.stderr and "torch.distributed.run" in r.stderr, r.stderr[-1500:]
     assert r.stderr.count("no GPU visible") >= 2, r.stderr[-1500:]            # both child ranks ran bench.py's own check
     assert '{"metric"' not in r.stdout
+
+
+def test_bench_dump_outputs_writes_float32_arrays_and_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: the last timed step's heat-map / size / offset logits and losses as <name>.npy in float32,
+    arrays above the per-array cap as <name>_sample.npy at the same positions on every call, all files together under 64 MB
+    (outputs shaped as the 1024x1024, B=8 step hands them out; host tensors stand in for device ones).  The RoI outputs,
+    whose number and order depend on near-tied scores, are not written: a step keeping other RoIs writes the same files."""
+    import os
+    import sys
+    import numpy as np
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    g = torch.Generator().manual_seed(0)
+    n_hm = 8 * 10 * 256 * 256             # heat-map values = their flat position (exact in float32)
+    hms = [torch.arange(n_hm, dtype=torch.float32).view(8, 10, 256, 256).to(memory_format=torch.channels_last) for _ in range(2)]
+    whs = [torch.randn(8, 2, 256, 256, generator=g) for _ in range(2)]
+    losses = tuple(torch.tensor(float(i)) for i in range(5))
+
+    def step_outputs(r):
+        rois = torch.cat([torch.randint(0, 8, (r, 1), generator=g).float(), torch.rand(r, 4, generator=g) * 1000], 1)
+        return (hms, whs, whs, torch.randn(r, 4, generator=g), rois, torch.rand(r, generator=g),
+                torch.randint(0, 10, (r,), generator=g))
+
+    outs = step_outputs(9000)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), outs, losses)
+    bench.dump_outputs(str(tmp_path / "c"), step_outputs(8999), losses)
+    names = sorted(os.listdir(str(tmp_path / "a")))
+    assert names == sorted(["hm_0_sample.npy", "hm_1_sample.npy", "wh_0.npy", "wh_1.npy", "offset_0.npy", "offset_1.npy", "loss.npy", "hm_loss.npy", "wh_loss.npy", "offset_loss.npy", "s2_reg_loss.npy"])
+    assert sum(os.path.getsize(str(tmp_path / "a" / n)) for n in names) <= 64 << 20
+    for n in names:
+        a, b, c = (np.load(str(tmp_path / d / n)) for d in "abc")
+        assert a.dtype == np.float32 and np.array_equal(a, b) and np.array_equal(a, c) and a.size > 0, n
+    hm = np.load(str(tmp_path / "a" / "hm_0_sample.npy"))
+    assert np.all(np.diff(hm) > 0) and hm[0] >= 0 and hm[-1] < n_hm   # distinct positions, sorted, in logical order
+    assert np.array_equal(np.load(str(tmp_path / "a" / "wh_1.npy")), whs[1].numpy())
+    assert np.load(str(tmp_path / "a" / "wh_loss.npy")) == 2.0

@@ -84,6 +84,30 @@ def main():
     path = os.path.join(ROOT, "tests", "golden", "softnms.npz")
     np.savez_compressed(path, **out)
     print("wrote", path, os.path.getsize(path), "bytes,", len(names), "cases")
+    trials(ref)
+
+
+def trials(ref):
+    """tests/golden/softnms_trials.npz: the 60 seeded random sets of
+    tests/test_oracle_softnms.py::test_against_compiled_reference_if_present under the three methods, with the
+    reference's kept indices and rows, so that the test needs no compiled reference at run time."""
+    rng = np.random.default_rng(7)
+    out = {}
+    for trial in range(60):
+        n = int(rng.choice([1, 2, 5, 64, 65, 150, 400]))
+        xy = rng.uniform(0, 500, (n, 2))
+        wh = rng.uniform(8, 120, (n, 2))
+        s = rng.uniform(0.01, 1, (n, 1))
+        b = np.concatenate([xy, xy + wh, s], 1).astype(np.float32)
+        out["t%d/in" % trial] = b
+        for method in (0, 1, 2):
+            work = b.copy()
+            keep = ref.cpu_soft_nms(work, np.float32(0.5), np.float32(0.7), np.float32(0.1), np.uint8(method))
+            out["t%d/m%d/keep" % (trial, method)] = np.array(keep, dtype=np.int64)
+            out["t%d/m%d/out" % (trial, method)] = work[:len(keep)].copy()
+    path = os.path.join(ROOT, "tests", "golden", "softnms_trials.npz")
+    np.savez_compressed(path, **out)
+    print("wrote", path, os.path.getsize(path), "bytes, 60 trials x 3 methods")
 
 
 if __name__ == "__main__":

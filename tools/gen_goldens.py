@@ -8,7 +8,7 @@ restatement of torchvision 0.3 (not installed here) and are flagged `tv_unpinned
 
   G2 decode.npz       RRNet.transform_bbox                       models/rrnet.py:93-138
   G3 losses.npz       focal_loss_for_hm / RegL1Loss (+grads)     modules/loss/*.py ; to_heatmap targets
-  G4 blocks.npz       ResidualBlock / ConvBNRelu / Hourglass     backbones/hourglass.py
+  G4 blocks_*.npz     ResidualBlock / ConvBNRelu / Hourglass     backbones/hourglass.py  (one file per block)
   G5 ctnet_tiny.npz   hourglass-tiny + 3 heads + CenterNetOperator.criterion (+grads)
   G6 stage2.npz       FasterRCNNDetector, generate_bbox(_target), criterion stage-2 branch
   G7 extnms.npz       RRNetOperator._ext_nms on a mixed-class set
@@ -168,7 +168,6 @@ def run_block(mod, x, train):
 
 def g4_blocks():
     rng = np.random.default_rng(4)
-    d = {}
     specs = {
         "res_id": (lambda: ResidualBlock(16, 16, 1), (2, 16, 12, 10)),
         "res_s2": (lambda: ResidualBlock(16, 24, 2), (2, 16, 12, 10)),
@@ -178,6 +177,7 @@ def g4_blocks():
         "hg_odd": (lambda: Hourglass(2, [8, 8, 12], [1, 1, 2]), (1, 8, 37, 41)),   # bilinear resize path
     }
     for name, (ctor, shape) in specs.items():
+        d = {}
         x = torch.from_numpy(rng.normal(0, 1, shape).astype(np.float32))
         for train in (True, False):
             mod = load_det(ctor(), seed=40)
@@ -188,7 +188,7 @@ def g4_blocks():
                 d[t + "/grad/" + k] = g
             for k, b in bufs.items():
                 d[t + "/buf/" + k] = b
-    save("blocks.npz", d)
+        save("blocks_%s.npz" % name, d)
 
 
 # ------------------------------------------------------------------ G5
