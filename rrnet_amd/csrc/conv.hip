@@ -34,8 +34,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 __device__ float rr_zero16[4] = {0.f, 0.f, 0.f, 0.f};
 
 constexpr int BM = 128;
-constexpr int BK = 32;
-constexpr int LDA = 36;  // [m][k] image row stride (floats): conflict-free ds_read_b128
+constexpr int BK = 32;   // K-step depth: 32 channels (conv_igemm_kernel's BKT), 32 pixels (conv_wgrad_kernel)
 
 struct ConvArgs {
     const float *src;  // fprop: X [N,H,W,C]      dgrad: dY [N,P,Q,K]
@@ -79,25 +78,25 @@ __device__ __forceinline__ int xcd_remap(int bid, int nb)
 }
 
 // MODE 0 = fprop, 1 = dgrad.  SCALAR: source/weight channel counts not multiples of 4.
-// BKT = K-step depth (32: 2 workgroups per CU by LDS; 16: 4 per CU).
-// PIPE: software-pipelined main loop (global loads two K-steps ahead, LDS fragments one 8-deep group
-// ahead, barrier placed between the third and fourth MFMA group) so that a wave's MFMA stream never
-// waits on a barrier or on LDS latency.
+// BKT = K-step depth: 32 channels.
+// PIPE: 0 plain double-buffered loop; 2 software-pipelined main loop with one LDS image per operand (global loads
+// two K-steps ahead, LDS fragments one 8-deep group ahead, two barriers inside the last MFMA group) so that a wave's
+// MFMA stream never waits on a barrier or on LDS latency.
 // BNS: the epilogue also emits the producer's BatchNorm-backward sums (ConvArgs::bs_y); a separate instantiation so
 // that the plain kernel keeps its register budget (three workgroups per CU).
 // POSM: position-major M tiles (ConvArgs::pos_major); like BNS a separate instantiation — folded into the plain kernel
 // the extra state cost 20 registers and the third workgroup per CU (457 -> 466 ms per train step).
 template <int BN, int MODE, bool SCALAR, int BKT, int PIPE, bool BNS = false, bool POSM = false>
-__global__ __launch_bounds__(256, PIPE == 3 ? 3 : 1) void conv_igemm_kernel(const ConvArgs a)
+__global__ __launch_bounds__(256, 1) void conv_igemm_kernel(const ConvArgs a)
 {
+    static_assert(BKT == 32 && (PIPE == 0 || PIPE == 2), "conv_igemm_kernel: K-step 32, PIPE 0 or 2");
     constexpr int WN = BN / 64 ? BN / 64 : 1;   // waves along N
     constexpr int WM = 4 / WN;                  // waves along M
     constexpr int TM = BM / (WM * 32);
     constexpr int TN = BN / (WN * 32);
     constexpr bool B_KN = (MODE == 1);          // dgrad reads W as [k][n]
-    // [m][k] image row stride: padded by 4 floats for conflict-free ds_read_b128; PIPE 3 (LDS-DMA staging) cannot pad
-    // (a wave's 64 x 16 B land contiguously) and XOR-swizzles the 16-byte chunks of a row with (row & 7) instead
-    constexpr int LDK = PIPE == 3 ? BKT : BKT + 4;
+    // [m][k] image row stride: padded by 4 floats for conflict-free ds_read_b128
+    constexpr int LDK = BKT + 4;
     constexpr int LDB = B_KN ? BN : LDK;
     constexpr int A_ELEMS = BM * LDK;
     constexpr int B_ELEMS = B_KN ? BKT * BN : BN * LDK;
@@ -111,7 +110,7 @@ __global__ __launch_bounds__(256, PIPE == 3 ? 3 : 1) void conv_igemm_kernel(cons
     constexpr int BJ = B_KN ? BJ_KN : BJ_NK;
 
     extern __shared__ __align__(16) float lds[];
-    constexpr int NBUF = PIPE >= 2 ? 1 : 2;   // PIPE 2 / 3: one LDS image per operand, three / four workgroups per CU
+    constexpr int NBUF = PIPE == 2 ? 1 : 2;   // PIPE 2: one LDS image per operand, three workgroups per CU
     float *As = lds;                    // [NBUF][A_ELEMS]
     float *Bs = lds + NBUF * A_ELEMS;   // [NBUF][B_ELEMS]
 
@@ -166,8 +165,7 @@ __global__ __launch_bounds__(256, PIPE == 3 ? 3 : 1) void conv_igemm_kernel(cons
     }
 
     // ---- per-thread A rows: destination pixel coordinates
-    // PIPE 3: lane (row, slot) fetches chunk slot ^ (row & 7), so that its DMA lands at the swizzled position
-    const int a_col = PIPE == 3 ? (((t % CPR) ^ ((t / CPR) & 7)) * 4) : (t % CPR) * 4;
+    const int a_col = (t % CPR) * 4;
     const int a_row = t / CPR;
     int a_n[AJ], a_h[AJ], a_w[AJ];
 #pragma unroll
@@ -411,7 +409,7 @@ __global__ __launch_bounds__(256, PIPE == 3 ? 3 : 1) void conv_igemm_kernel(cons
         __syncthreads();
     }
     } else {
-    static_assert(PIPE == 0 || (BKT == 32 && !SCALAR && (BN == 128 || BN == 64)),
+    static_assert(!SCALAR && (BN == 128 || BN == 64),
                   "pipelined loop: 4 groups of 8 per K-step, vector gather, 128x128 or 128x64 tile");
     // Each K-step = 4 groups x 4 sub-groups of 4 MFMAs.  Memory instructions are dealt out between the
     // sub-groups (never clustered): a VMEM / DS issue that would stall this wave's in-order stream then
@@ -421,16 +419,6 @@ __global__ __launch_bounds__(256, PIPE == 3 ? 3 : 1) void conv_igemm_kernel(cons
     auto read_frags = [&](int buf, int kk, f32x4 (&fa)[TM], f32x4 (&fb)[TN]) {
         const float *A = As + buf * A_ELEMS;
         const float *B = Bs + buf * B_ELEMS;
-        if constexpr (PIPE == 3) {
-            const int slot = ((kk * 2 + lh) ^ (lr & 7)) * 4;
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-                fa[i] = *reinterpret_cast<const f32x4 *>(A + ((wm * TM + i) * 32 + lr) * LDK + slot);
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-                fb[j] = *reinterpret_cast<const f32x4 *>(B + ((wn * TN + j) * 32 + lr) * LDK + slot);
-            return;
-        }
 #pragma unroll
         for (int i = 0; i < TM; ++i)
             fa[i] = *reinterpret_cast<const f32x4 *>(A + ((wm * TM + i) * 32 + lr) * LDK + kk * 8 + lh * 4);
@@ -511,57 +499,7 @@ __global__ __launch_bounds__(256, PIPE == 3 ? 3 : 1) void conv_igemm_kernel(cons
         if (!B_KN) *reinterpret_cast<f32x4 *>(Bs + buf * B_ELEMS + (a_row + RPP * j) * LDK + a_col) = rb[j];
         else *reinterpret_cast<f32x4 *>(Bs + buf * B_ELEMS + (t / TPR + KRPP * j) * LDB + (t % TPR) * 4) = rb[j];
     };
-    static_assert(PIPE == 0 || (AJ == 4 && (BJ == 4 || BJ == 2)), "piece schedule below: 4 + (4 | 2) float4 per thread");
-    if constexpr (PIPE == 3) {
-    // LDS-DMA staging (buffer_load_dwordx4 ... lds): no staging registers, no ds_write; one unpadded, XOR-swizzled LDS
-    // image.  Per K-step: after the last fragment reads of tile kc everybody waits (1), each wave fires its 8 DMA
-    // loads of tile kc+1 under group 3's MFMAs, waits for its own (vmcnt 0), everybody waits (2); the exposed part of
-    // the load latency is covered by the other workgroups of the CU.
-    // Opt-in (RR_CONV_PIPE=3), measured on MI355X: at three workgroups per CU it ties with PIPE 2 (137-139 TFLOP/s on
-    // the 256x256 layer); a fourth workgroup needs <= 128 registers per lane and spills 17 dwords whose
-    // scratch reloads put s_waitcnt vmcnt(0) between the DMA loads, so PIPE 2 stays the default.
-    static_assert(PIPE != 3 || !B_KN, "DMA staging: [n][k] weight image only (fprop / flipped-weight dgrad)");
-    typedef __attribute__((address_space(3))) void lds_void;
-    auto dma_a = [&](int j) {
-        const unsigned ok = (unsigned)p_cok & (unsigned)((a_mask[j] >> p_tlc) & 1ull) & (unsigned)p_live;
-        const unsigned off = ok ? (unsigned)(a_boff[j] + p_adelta) : 0x80000000u;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_src, (lds_void *)(As + (wave * 8 + RPP * j) * LDK), 16, off, 0, 0, 0);
-    };
-    auto dma_b = [&](int j) {
-        const unsigned ok = ((unsigned)b_ok[j] & (unsigned)p_wcok) & (unsigned)p_live;
-        const unsigned off = ok ? (unsigned)(b_boff[j] + p_wdelta) : 0x80000000u;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (lds_void *)(Bs + (wave * 8 + RPP * j) * LDK), 16, off, 0, 0, 0);
-    };
-    if (kc_lo < kc_hi) {
-        prep();
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { dma_a(j); dma_b(j); }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (kc_lo < kc_hi) read_frags(0, 0, fa0, fb0);
-    for (int kc = kc_lo; kc < kc_hi; ++kc) {
-        p_live = kc + 1 < kc_hi;
-        read_frags(0, 1, fa1, fb1);
-        sub(fa0, fb0, 0); sub(fa0, fb0, 1); sub(fa0, fb0, 2); sub(fa0, fb0, 3);
-        read_frags(0, 2, fa0, fb0);
-        sub(fa1, fb1, 0); sub(fa1, fb1, 1); sub(fa1, fb1, 2); sub(fa1, fb1, 3);
-        prep();
-        read_frags(0, 3, fa1, fb1);
-        sub(fa0, fb0, 0); sub(fa0, fb0, 1); sub(fa0, fb0, 2); sub(fa0, fb0, 3);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        dma_a(0); dma_a(1); dma_a(2); dma_a(3);
-        sub(fa1, fb1, 0);
-        dma_b(0); dma_b(1); dma_b(2); dma_b(3);
-        sub(fa1, fb1, 1); sub(fa1, fb1, 2); sub(fa1, fb1, 3);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        read_frags(0, 0, fa0, fb0);
-    }
-    } else {
+    static_assert(AJ == 4 && (BJ == 4 || BJ == 2), "piece schedule below: 4 + (4 | 2) float4 per thread");
     if (kc_lo < kc_hi) {
         prep();
 #pragma unroll
@@ -576,11 +514,13 @@ __global__ __launch_bounds__(256, PIPE == 3 ? 3 : 1) void conv_igemm_kernel(cons
     }
     __syncthreads();
     if (kc_lo < kc_hi) read_frags(0, 0, fa0, fb0);
-    if constexpr (PIPE == 2) {
     // Single LDS image, two barriers per K-step, both inside group 3: after the last fragment reads of tile kc
     // everybody waits (1), the registers holding tile kc+1 are written over it, everybody waits (2), then the
     // first fragments of kc+1 and the global loads of kc+2 go out — all under group 3's 16 MFMAs.  Half the LDS
     // of the double-buffered loop: a third workgroup fits on the CU and covers the barrier waits.
+    // The body is branch-free on purpose: past the end of the K range the loads turn into out-of-range buffer reads
+    // (zeros) that nobody consumes.  With `if (has_next)` arms hipcc's waitcnt pass loses track of which loads the
+    // ds_writes already retired and parks s_waitcnt vmcnt(1) between consecutive load pairs, serialising them.
     for (int kc = kc_lo; kc < kc_hi; ++kc) {
         p_live = kc + 2 < kc_hi;
         read_frags(0, 1, fa1, fb1);
@@ -605,49 +545,6 @@ __global__ __launch_bounds__(256, PIPE == 3 ? 3 : 1) void conv_igemm_kernel(cons
         sub(fa1, fb1, 2);
         load_b(0); load_b(1); load_b(2); load_b(3);
         sub(fa1, fb1, 3);
-    }
-    } else {
-    for (int kc = kc_lo; kc < kc_hi; ++kc) {
-        const int buf = (kc - kc_lo) & 1;
-        // The body is branch-free on purpose: past the end of the K range the loads turn into out-of-range
-        // buffer reads (zeros) and the stores / fragment reads touch an LDS buffer nobody consumes.  With
-        // `if (has_next)` arms hipcc's waitcnt pass loses track of which loads the ds_writes already retired
-        // and parks s_waitcnt vmcnt(1) between consecutive load pairs, serialising them.
-        p_live = kc + 2 < kc_hi;
-        // group 0 (fragment set 0); prefetch set 1 <- group 1's fragments
-        read_frags(buf, 1, fa1, fb1);
-        sub(fa0, fb0, 0); sub(fa0, fb0, 1); sub(fa0, fb0, 2); sub(fa0, fb0, 3);
-        // group 1 (set 1); prefetch set 0 <- group 2; stage the next K-step into the other LDS buffer
-        read_frags(buf, 2, fa0, fb0);
-        store_a(0, buf ^ 1); store_a(1, buf ^ 1);
-        sub(fa1, fb1, 0);
-        store_a(2, buf ^ 1); store_a(3, buf ^ 1);
-        sub(fa1, fb1, 1);
-        store_b(0, buf ^ 1); store_b(1, buf ^ 1);
-        sub(fa1, fb1, 2);
-        store_b(2, buf ^ 1); store_b(3, buf ^ 1);
-        sub(fa1, fb1, 3);
-        // group 2 (set 0); prefetch set 1 <- group 3; refill the registers two K-steps ahead
-        prep();
-        read_frags(buf, 3, fa1, fb1);
-        load_a(0); load_a(1);
-        sub(fa0, fb0, 0);
-        load_a(2); load_a(3);
-        sub(fa0, fb0, 1);
-        load_b(0); load_b(1);
-        sub(fa0, fb0, 2);
-        load_b(2); load_b(3);
-        sub(fa0, fb0, 3);
-        // the only barrier of the step: this wave's fragment reads of `buf` have landed and its share of
-        // the next tile is written (lgkmcnt(0)); the global loads just issued stay in flight across it
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        // group 3 (set 1) overlaps the first fragment reads of the next K-step
-        read_frags(buf ^ 1, 0, fa0, fb0);
-        sub(fa1, fb1, 0); sub(fa1, fb1, 1); sub(fa1, fb1, 2); sub(fa1, fb1, 3);
-    }
-    }
     }
     }
 
@@ -789,14 +686,15 @@ struct WgradArgs {
 
 // BMW x BN output tile (ko x c).  128x128: 2x2 waves of 64x64; 128x32 / 32x128: 4 waves of one 32x32;
 // 32x32: the 4 waves split the 32-deep K-step between them (their partial sums meet in the atomics).
-// PIPE: 0 plain double-buffered loop; 1 software-pipelined; 2 software-pipelined for Q % BK == 0, where the BK pixels
-// of a K-step lie in one output row: the row walk (n, p, q0) is wave-uniform and lives in SGPRs, the tensor offsets go
-// through the buffer instruction's scalar offset, and the per-lane work per load is one add, one compare, one select.
-// PIPE 3 = PIPE 2 with ONE LDS image per operand and two barriers inside the last MFMA group (three workgroups per CU,
+// PIPE: 0 plain double-buffered loop; 1 software-pipelined (two LDS images); 3 software-pipelined for Q % BK == 0,
+// where the BK pixels of a K-step lie in one output row: the row walk (n, p, q0) is wave-uniform and lives in SGPRs,
+// the tensor offsets go through the buffer instruction's scalar offset, and the per-lane work per load is one add, one
+// compare, one select; ONE LDS image per operand and two barriers inside the last MFMA group (three workgroups per CU,
 // like conv_igemm_kernel<PIPE 2>).
 template <int BMW, int BN, bool A_SCALAR, bool B_SCALAR, int PIPE>
 __global__ __launch_bounds__(256, PIPE == 3 ? 3 : 1) void conv_wgrad_kernel(const WgradArgs a)
 {
+    static_assert(PIPE == 0 || PIPE == 1 || PIPE == 3, "conv_wgrad_kernel: PIPE 0, 1 or 3");
     constexpr int TILES = (BMW / 32) * (BN / 32);
     constexpr int KS = TILES == 1 ? 4 : 1;                       // waves splitting K
     constexpr int WN = TILES == 16 ? 2 : (BN / 32 >= 4 ? 4 : 1);
@@ -912,7 +810,7 @@ __global__ __launch_bounds__(256, PIPE == 3 ? 3 : 1) void conv_wgrad_kernel(cons
 
     const int lr = lane & 31, lh = lane >> 5;
     constexpr bool WPIPE = PIPE != 0 && (BMW == 128 && BN == 128 && !A_SCALAR && !B_SCALAR);
-    constexpr bool ALIGNED = PIPE >= 2;
+    constexpr bool ALIGNED = PIPE == 3;       // uniform row walk
     if constexpr (!WPIPE) {
     load_tiles(kc_begin);
     store_tiles(0);
@@ -973,7 +871,7 @@ __global__ __launch_bounds__(256, PIPE == 3 ? 3 : 1) void conv_wgrad_kernel(cons
         return __builtin_amdgcn_make_buffer_rsrc(q, 0, __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000);
     };
     const __amdgpu_buffer_rsrc_t rs_dy = make_srd(a.dy, (long)a.M * a.K * 4);
-    // Uniform row walk (ALIGNED): the descriptor of x starts pad_w pixels BEFORE the tensor, so that the per-lane
+    // Uniform row walk: the descriptor of x starts pad_w pixels BEFORE the tensor, so that the per-lane
     // offset (lq*stride + s) * C is never negative.  A negative (wrapped) lane offset is out of range for the
     // hardware's bounds check even when the scalar offset brings the address back inside the tensor — the left-most
     // tap column then silently lost the pixel in front of every K-step that does not start a row (Q > 32).  Lanes
@@ -1181,22 +1079,15 @@ int launch(K kern, int blocks, size_t lds, hipStream_t stream, const A &args, co
     return RR_OK;
 }
 
-size_t igemm_lds(int bn, bool b_kn, int bk, int nbuf = 2)
+// conv_igemm_kernel's dynamic LDS: nbuf images of A [BM][BK + 4] and B [bn][BK + 4] / [BK][bn]
+size_t igemm_lds(int bn, bool b_kn, int nbuf)
 {
-    return sizeof(float) * nbuf * (BM * (bk + 4) + (b_kn ? bk * bn : bn * (bk + 4)));
+    return sizeof(float) * nbuf * (BM * (BK + 4) + (b_kn ? BK * bn : bn * (BK + 4)));
 }
-
-int conv_rows_kernel() { return 1; }
-
-int conv_pos_major() { return 1; }
-
-int wgrad_aligned() { return 1; }       // 0 generic row walk, 1 uniform row walk + one LDS image (default), 2 uniform + two images
 
 int mid_tiles() { return 48; }       // <= 48 tiles of 128x128 (the 16x16 level): 128x64 tiles; measured worse at 192 (32x32)
 
 int small_tiles() { return 16; }       // <= 16 tiles of 128x128 (the 8x8 level): 128x32 tiles give 4x the workgroups
-
-int conv_bk() { return 32; }
 
 // split-K factor for layers whose output has too few tiles to fill the chip
 int pick_ksplit(int blocks, int nk)
@@ -1251,52 +1142,31 @@ __global__ __launch_bounds__(256) void colstats_kernel(const float *y, long M, i
     }
 }
 
-int conv_pipe() { return 2; }       // 0 plain loop, 1 pipelined (two LDS images), 2 pipelined with one LDS image (default)
-
+// PIPE 2 (pipelined, one LDS image) where both tensors are below 2 GiB: it addresses them through 32-bit buffer offsets
 template <int MODE>
 int launch_igemm(ConvArgs &a, int bn, bool scalar, int blocks, int gy, int gz, hipStream_t stream, const char *name)
 {
-    const int bk = conv_bk();
-    const size_t lds = igemm_lds(bn, MODE == 1, bk);
-#define IG(BNv, SCv, BKv, PIPEv)                                                                                     \
-    launch(conv_igemm_kernel<BNv, MODE, SCv, BKv, PIPEv>, blocks,                                                    \
-           PIPEv == 3 ? sizeof(float) * (BM + bn) * bk : (PIPEv == 2 ? igemm_lds(bn, MODE == 1, bk, 1) : lds), stream, a, name, gy, gz)
+    const bool small = (long)a.N * a.SH * a.SW * a.SC * 4 < (1l << 31) && (long)a.wK * a.R * a.S * a.wC * 4 < (1l << 31);
+#define IG(BNv, SCv, PIPEv, ...)                                                                                       \
+    launch(conv_igemm_kernel<BNv, MODE, SCv, BK, PIPEv, ##__VA_ARGS__>, blocks, igemm_lds(bn, MODE == 1, PIPEv == 2 ? 1 : 2), \
+           stream, a, name, gy, gz)
     if constexpr (MODE == 0) {
-        if (a.pos_major) {           // host rule (fprop_impl): vector gather, both tensors below 2 GiB
-            if (bn == 128) return launch(conv_igemm_kernel<128, 0, false, 32, 2, false, true>, blocks, igemm_lds(bn, false, 32, 1), stream, a, name, gy, gz);
-            return launch(conv_igemm_kernel<64, 0, false, 32, 2, false, true>, blocks, igemm_lds(64, false, 32, 1), stream, a, name, gy, gz);
-        }
-        if (a.bs_y != nullptr) {     // producer's BatchNorm-backward sums in the epilogue: vector kernels, K-step 32
-            const bool small = (long)a.N * a.SH * a.SW * a.SC * 4 < (1l << 31) && (long)a.wK * a.R * a.S * a.wC * 4 < (1l << 31);
-            RR_CHECK_ARG(!scalar && bk == 32, "conv: BatchNorm-backward sums need the vector kernels (C %% 4 == 0, RR_CONV_BK=32)");
-            if (bn == 128)
-                return conv_pipe() >= 1 && small
-                           ? launch(conv_igemm_kernel<128, 0, false, 32, 2, true>, blocks, igemm_lds(bn, false, bk, 1), stream, a, name, gy, gz)
-                           : launch(conv_igemm_kernel<128, 0, false, 32, 0, true>, blocks, lds, stream, a, name, gy, gz);
-            if (bn == 64)
-                return conv_pipe() >= 1 && small
-                           ? launch(conv_igemm_kernel<64, 0, false, 32, 2, true>, blocks, igemm_lds(bn, false, bk, 1), stream, a, name, gy, gz)
-                           : launch(conv_igemm_kernel<64, 0, false, 32, 0, true>, blocks, lds, stream, a, name, gy, gz);
-            return launch(conv_igemm_kernel<32, 0, false, 32, 0, true>, blocks, lds, stream, a, name, gy, gz);
+        if (a.pos_major)             // host rule (fprop_impl): vector gather, both tensors below 2 GiB
+            return bn == 128 ? IG(128, false, 2, false, true) : IG(64, false, 2, false, true);
+        if (a.bs_y != nullptr) {     // producer's BatchNorm-backward sums in the epilogue: vector kernels
+            RR_CHECK_ARG(!scalar, "conv: BatchNorm-backward sums need the vector kernels (C %% 4 == 0)");
+            if (bn == 128) return small ? IG(128, false, 2, true) : IG(128, false, 0, true);
+            if (bn == 64) return small ? IG(64, false, 2, true) : IG(64, false, 0, true);
+            return IG(32, false, 0, true);
         }
     }
-    if (bk == 32) {
-        // the pipelined kernel addresses both tensors through 32-bit buffer offsets
-        const bool small = (long)a.N * a.SH * a.SW * a.SC * 4 < (1l << 31) && (long)a.wK * a.R * a.S * a.wC * 4 < (1l << 31);
-        if (bn == 128) {
-            if (scalar) return IG(128, true, 32, 0);
-            if constexpr (MODE == 0) {
-                if (conv_pipe() == 3 && small) return IG(128, false, 32, 3);
-            }
-            if (conv_pipe() >= 2 && small) return IG(128, false, 32, 2);
-            return conv_pipe() && small ? IG(128, false, 32, 1) : IG(128, false, 32, 0);
-        }
-        if (bn == 64)     // 4 waves along M, 32x64 each: 33..64-column layers and under-filled 384-column levels
-            return conv_pipe() >= 2 && small ? IG(64, false, 32, 2) : IG(64, false, 32, 0);
-        return scalar ? IG(32, true, 32, 0) : IG(32, false, 32, 0);
+    if (bn == 128) {
+        if (scalar) return IG(128, true, 0);
+        return small ? IG(128, false, 2) : IG(128, false, 0);
     }
-    if (bn == 128) return scalar ? IG(128, true, 16, 0) : IG(128, false, 16, 0);
-    return scalar ? IG(32, true, 16, 0) : IG(32, false, 16, 0);
+    if (bn == 64)     // 4 waves along M, 32x64 each: 33..64-column layers and under-filled 384-column levels
+        return small ? IG(64, false, 2) : IG(64, false, 0);
+    return scalar ? IG(32, true, 0) : IG(32, false, 0);
 #undef IG
 }
 
@@ -1334,23 +1204,22 @@ static int fprop_impl(const float *x, const float *w, const float *bias, float *
     // 1x1 to 49..64 channels (both 32-column tiles of the rows kernel in use) on very many rows without statistics — the
     // stage-2 head's conv1 at inference: the row-streaming kernel of csrc/headtail.hip (weights in registers, no per-tile
     // prologue)
-    if (conv_rows_kernel() && r == 1 && s == 1 && stride == 1 && pad_h == 0 && pad_w == 0 && (c == 128 || c == 256) && k > 48 && k <= 64
+    if (r == 1 && s == 1 && stride == 1 && pad_h == 0 && pad_w == 0 && (c == 128 || c == 256) && k > 48 && k <= 64
         && stat_slab == nullptr && bs == nullptr && !accumulate && M >= 64 * 1024 && M * c * 4 < (1l << 31))
         return rr_conv1x1_rows(x, w, bias, y, M, c, k, relu, stream);
     const bool scalar = (c % 4) != 0 || r * s > 64;   // the vector path keeps a 64-bit tap mask per row
-    const int bk = conv_bk();
-    int bn = k > 64 ? 128 : (k > 32 ? (!scalar && bk == 32 ? 64 : 128) : 32);
+    int bn = k > 64 ? 128 : (k > 32 ? (!scalar ? 64 : 128) : 32);
     if (bn == 128 && !scalar && rr_cdiv(M, BM) * rr_cdiv(k, 128) <= small_tiles()) bn = 32;   // tiny layers: 4x the tiles
-    else if (bn == 128 && !scalar && bk == 32 && rr_cdiv(M, BM) * rr_cdiv(k, 128) <= mid_tiles()) bn = 64;
+    else if (bn == 128 && !scalar && rr_cdiv(M, BM) * rr_cdiv(k, 128) <= mid_tiles()) bn = 64;
     int blocks = rr_cdiv(M, BM) * rr_cdiv(k, bn);
-    const int nk = scalar ? rr_cdiv(a.Kg, bk) : rr_cdiv(c, bk) * r * s;
+    const int nk = scalar ? rr_cdiv(a.Kg, BK) : rr_cdiv(c, BK) * r * s;
     int ks = (bias == nullptr && !relu && k % 4 == 0 && k <= 1024) ? pick_ksplit(blocks, nk) : 1;
     if (bs != nullptr && bs->relu_bias) ks = 1;      // the masked store needs the complete value in one workgroup
     // padded filter on a tiny map, many images (the stage-2 head on 3x3 RoI maps): one output pixel per M tile, padding
     // taps skipped (ConvArgs::pos_major).  Not with statistics in the epilogue (their slab is sized by ceil(M/128) tiles).
-    // The variant exists for the pipelined 128- and 64-column kernels (K-step 32, 32-bit buffer offsets).
-    if (conv_pos_major() && !scalar && stat_slab == nullptr && bs == nullptr && (pad_h > 0 || pad_w > 0) && r * s > 1
-        && a.DH * a.DW <= 16 && n >= 16 * BM && bk == 32 && bn >= 64 && conv_pipe() >= 2
+    // The variant exists for the pipelined 128- and 64-column kernels (32-bit buffer offsets).
+    if (!scalar && stat_slab == nullptr && bs == nullptr && (pad_h > 0 || pad_w > 0) && r * s > 1
+        && a.DH * a.DW <= 16 && n >= 16 * BM && bn >= 64
         && (long)n * h * wd * c * 4 < (1l << 31) && (long)k * r * s * c * 4 < (1l << 31)) {
         a.pos_major = 1;
         ks = 1;
@@ -1581,13 +1450,12 @@ extern "C" int rr_conv_dgrad(const float *dy, const float *w, float *dx, int n, 
     RR_CHECK_ARG(M < (1l << 31), "rr_conv_dgrad: tensor too large");
     a.M = (int)M; a.Kg = r * s * k; a.wK = k; a.wC = c;
     const bool scalar = (k % 4) != 0 || (c % 4) != 0 || r * s > 64 || stride > 2;
-    const int bk = conv_bk();
-    int bn = c > 64 ? 128 : (c > 32 ? (!scalar && bk == 32 ? 64 : 128) : 32);
+    int bn = c > 64 ? 128 : (c > 32 ? (!scalar ? 64 : 128) : 32);
     if (bn == 128 && !scalar && stride == 1 && rr_cdiv(M, BM) * rr_cdiv(c, 128) <= small_tiles()) bn = 32;
-    else if (bn == 128 && !scalar && bk == 32 && stride == 1 && rr_cdiv(M, BM) * rr_cdiv(c, 128) <= mid_tiles()) bn = 64;
+    else if (bn == 128 && !scalar && stride == 1 && rr_cdiv(M, BM) * rr_cdiv(c, 128) <= mid_tiles()) bn = 64;
     int blocks = rr_cdiv(M, BM) * rr_cdiv(c, bn);
     int gy = 1;
-    int nk = scalar ? rr_cdiv(a.Kg, bk) : rr_cdiv(k, bk) * r * s;
+    int nk = scalar ? rr_cdiv(a.Kg, BK) : rr_cdiv(k, BK) * r * s;
     if (stride == 2 && !scalar) {     // parity-decomposed: 4 classes of ceil(h/2) x ceil(w/2) pixels each
         a.parity = 1;
         gy = 4;
@@ -1610,7 +1478,7 @@ extern "C" int rr_conv_dgrad(const float *dy, const float *w, float *dx, int n, 
             gy = live;
         }
         blocks = rr_cdiv((long)n * ((h + 1) / 2) * ((wd + 1) / 2), BM) * rr_cdiv(c, bn);
-        nk = rr_cdiv(k, bk) * ((r + 1) / 2) * ((s + 1) / 2);
+        nk = rr_cdiv(k, BK) * ((r + 1) / 2) * ((s + 1) / 2);
     }
     int ks = a.parity ? 1 : pick_ksplit(blocks * gy, nk);
     if (ks > 1) {
@@ -1646,9 +1514,9 @@ extern "C" int rr_conv_wgrad(const float *x, const float *dy, float *dw, int n, 
     // round for any remainder.  Never fewer than 8 K-steps per split.
     // pipelined 128x128 variants: 32-bit buffer offsets, both tensors below 2 GiB
     const bool as = (k % 4) != 0, bs = (c % 4) != 0;
-    const bool pipe_ok = bmw == 128 && bn == 128 && !as && !bs && conv_pipe() && M * k * 4 < (1l << 31) &&
+    const bool pipe_ok = bmw == 128 && bn == 128 && !as && !bs && M * k * 4 < (1l << 31) &&
                          (long)n * h * wd * c * 4 < (1l << 31);
-    const int wmode = !pipe_ok ? 0 : (a.Q % BK == 0 && wgrad_aligned() ? (wgrad_aligned() == 2 ? 2 : 3) : 1);
+    const int wmode = !pipe_ok ? 0 : (a.Q % BK == 0 ? 3 : 1);   // PIPE of the 128x128 kernel, 0: generic tiles
     const int slots = wmode == 3 ? 768 : 512;       // resident workgroups: 256 CUs x 3 with one LDS image, else x 2
     int splits = tiles < slots ? slots / tiles : 1;
     if (splits > rr_cdiv(total_chunks, 8)) splits = rr_cdiv(total_chunks, 8);
@@ -1663,7 +1531,6 @@ extern "C" int rr_conv_wgrad(const float *x, const float *dy, float *dw, int n, 
         : (bs ? launch(conv_wgrad_kernel<BMv, BNv, false, true, 0>, blocks, lds, stream, a, "rr_conv_wgrad")     \
               : launch(conv_wgrad_kernel<BMv, BNv, false, false, 0>, blocks, lds, stream, a, "rr_conv_wgrad")))
     if (wmode == 3) return launch(conv_wgrad_kernel<128, 128, false, false, 3>, blocks, lds, stream, a, "rr_conv_wgrad");
-    if (wmode == 2) return launch(conv_wgrad_kernel<128, 128, false, false, 2>, blocks, lds, stream, a, "rr_conv_wgrad");
     if (wmode == 1) return launch(conv_wgrad_kernel<128, 128, false, false, 1>, blocks, lds, stream, a, "rr_conv_wgrad");
     if (bmw == 128) return bn == 128 ? WG(128, 128) : WG(128, 32);
     return bn == 128 ? WG(32, 128) : WG(32, 32);

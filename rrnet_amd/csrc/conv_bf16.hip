@@ -162,12 +162,11 @@ __device__ __forceinline__ float split_scale_inv(float sc) { return __builtin_bi
 // and the products hi*hi + (hi*mid + mid*hi) [+ hi*lo + mid*mid + lo*hi] are accumulated — 3 / 6 matrix instructions per
 // product tile instead of 1, 2^-16 / 2^-24 relative per product.  The small products go to their own accumulator (added to
 // the hi*hi one in the epilogue), so their rounding never touches the main sum.
-// WS (wave specialisation, 512 threads): waves 0-3 only read LDS and issue matrix instructions, waves 4-7 only fetch, split
-// and stage the next tile.  Each SIMD then holds one wave of each kind and overlaps them in hardware — with 3 / 6 matrix
-// instructions per product tile the loop is matrix-bound only if nothing else sits in the matrix waves' instruction stream.
+// WS: always false (the wave-specialised 512-thread loop is no longer part of the kernel).
 template <int BN, bool BNS, bool B16 = false, bool SO = false, int SP = 1, bool WS = false, bool F16 = false>
-__global__ __launch_bounds__(WS ? 512 : 256, (!WS && SP == 2) ? 2 : 1) void conv_igemm_bf16_kernel(const ConvArgs a)
+__global__ __launch_bounds__(256, SP == 2 ? 2 : 1) void conv_igemm_bf16_kernel(const ConvArgs a)
 {
+    static_assert(!WS, "conv_igemm_bf16_kernel: WS = false");
     typedef typename std::conditional<F16, f16x8, bf16x8>::type frag_t;
     // operand scales (F16): 2^(14 - floor(log2(max|tensor|))), exact powers of two; the product is undone in the epilogue
     float sc_a = 1.f, sc_b = 1.f, sc_ia = 1.f, sc_ib = 1.f;
@@ -195,8 +194,7 @@ __global__ __launch_bounds__(WS ? 512 : 256, (!WS && SP == 2) ? 2 : 1) void conv
     unsigned short *As = lds16;                      // [2][SP][A_ELEMS]
     unsigned short *Bs = lds16 + 2 * SP * A_ELEMS;   // [2][SP][B_ELEMS]
 
-    const int t = WS ? (threadIdx.x & 255) : threadIdx.x;     // index inside the thread's role group
-    const bool producer = WS && threadIdx.x >= 256;
+    const int t = threadIdx.x;
     const int lane = t & 63, wave = t >> 6;
     const int wm = wave / WN, wn = wave % WN;
     const int ntiles = (a.DC + BN - 1) / BN;
@@ -347,133 +345,6 @@ __global__ __launch_bounds__(WS ? 512 : 256, (!WS && SP == 2) ? 2 : 1) void conv
             }
     const int lr = lane & 31, lh = lane >> 5;
 
-    if constexpr (WS) {
-        // LDS stores / reads of this wave retired, then the barrier: no vmcnt wait (the producers' loads of tile kc + 2 stay in
-        // flight across it, __syncthreads() would drain them).  "memory": the compiler moves no LDS access across it.
-#define RR_WS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-        if (producer) {
-            // Two tiles in flight in registers (ra / rb and ra2 / rb2 alternate): a tile's loads are issued a whole K-step before
-            // its split + LDS store needs them.  The loads are inline assembly and the waits are counted BY HAND: hipcc's own wait
-            // insertion is conservative at a loop header (registers loaded before the back edge get vmcnt(0) at their first use,
-            // whatever was issued after them), which exposed a full memory latency in every second K-step of this loop.
-            // Every load's destination is an output of its asm statement and an in/out operand of the wait that retires it, so
-            // nothing the compiler schedules can read it in between.
-            typedef int i32x4 __attribute__((ext_vector_type(4)));
-            auto srd4 = [](const void *p, long bytes) {
-                const unsigned long long u = reinterpret_cast<unsigned long long>(p);
-                i32x4 r;
-                r[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)u);
-                r[1] = __builtin_amdgcn_readfirstlane((int)(unsigned)(u >> 32));
-                r[2] = __builtin_amdgcn_readfirstlane((int)bytes);
-                r[3] = 0x00020000;
-                return r;
-            };
-            const i32x4 q_src = srd4(a.src, (long)a.N * a.SH * a.SW * a.SC * 4);
-            const i32x4 q_w = B16 ? srd4(a.w16, (long)a.wK * RS * a.wC * 2 * SP) : srd4(a.w, (long)a.wK * RS * a.wC * 4);
-            constexpr int NLOADS = AJ + NBI * BJ;       // loads per tile and thread
-            static_assert(NLOADS == 8 || NLOADS == 6 || NLOADS == 10, "the wait count below is a literal");
-            auto fetch = [&](f32x4 (&ra)[AJ], f32x4 (&rb)[NBI][BJ]) {
-#pragma unroll
-                for (int j = 0; j < AJ; ++j) {
-                    const unsigned ok = (unsigned)p_cok & (unsigned)((a_mask[j] >> p_tlc) & 1ull) & (unsigned)p_live;
-                    const unsigned off = ok ? (unsigned)(a_boff[j] + p_adelta) : OOB;
-                    asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=v"(ra[j]) : "v"(off), "s"(q_src) : "memory");
-                }
-#pragma unroll
-                for (int j = 0; j < BJ; ++j) {
-                    const unsigned ok = (unsigned)b_ok[j] & (unsigned)p_wcok & (unsigned)p_live;
-#pragma unroll
-                    for (int sp = 0; sp < NBI; ++sp) {
-                        const unsigned off = ok ? (unsigned)(b_boff[j] + p_wdelta + sp * w16_image) : OOB;
-                        asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=v"(rb[sp][j]) : "v"(off), "s"(q_w) : "memory");
-                    }
-                }
-            };
-            // all but the newest NLOADS loads have landed: the tile in (ra, rb) is complete, the next one may still be in flight
-            auto landed = [&](f32x4 (&ra)[AJ], f32x4 (&rb)[NBI][BJ]) {
-                static_assert(AJ == 4, "operand list below");
-                if constexpr (NLOADS == 8) asm volatile("s_waitcnt vmcnt(8)" : "+v"(ra[0]), "+v"(ra[1]), "+v"(ra[2]), "+v"(ra[3]) :: "memory");
-                else if constexpr (NLOADS == 6) asm volatile("s_waitcnt vmcnt(6)" : "+v"(ra[0]), "+v"(ra[1]), "+v"(ra[2]), "+v"(ra[3]) :: "memory");
-                else asm volatile("s_waitcnt vmcnt(10)" : "+v"(ra[0]), "+v"(ra[1]), "+v"(ra[2]), "+v"(ra[3]) :: "memory");
-#pragma unroll
-                for (int sp = 0; sp < NBI; ++sp)
-#pragma unroll
-                    for (int j = 0; j < BJ; ++j) asm volatile("" : "+v"(rb[sp][j]) :: "memory");   // (ordered behind the wait: both volatile)
-            };
-            f32x4 ra2[AJ], rb2[NBI][BJ];
-            prep();
-            fetch(ra, rb);                          // tile 0
-            p_live = kc_lo + 1 < kc_hi;
-            prep();
-            fetch(ra2, rb2);                        // tile 1
-            landed(ra, rb);
-            store_from(ra, rb, 0);
-            p_live = kc_lo + 2 < kc_hi;
-            prep();
-            fetch(ra, rb);                          // tile 2
-            RR_WS_BARRIER();
-            for (int kc = kc_lo; kc < kc_hi; kc += 2) {
-                landed(ra2, rb2);
-                store_from(ra2, rb2, 1);            // tile kc + 1: the readers of tile kc - 1 passed the previous barrier
-                p_live = kc + 3 < kc_hi;
-                prep();
-                fetch(ra2, rb2);
-                RR_WS_BARRIER();
-                if (kc + 1 >= kc_hi) break;
-                landed(ra, rb);
-                store_from(ra, rb, 0);              // tile kc + 2
-                p_live = kc + 4 < kc_hi;
-                prep();
-                fetch(ra, rb);
-                RR_WS_BARRIER();
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the two tiles past the end (all-zero loads) before the registers are reused
-        } else {
-            // Matrix waves, rotated by half a K-step against the barrier: the fragments of a tile's second half and of the next
-            // tile's first half are fetched while the other half's matrix instructions run, so no LDS latency is exposed.
-            //   barrier #kc+1 sits between the two halves of tile kc: by then this wave holds ALL of tile kc in registers
-            //   (its buffer is free for tile kc + 2) and the producers have finished tile kc + 1.
-            frag_t f0a[SP][TM], f0b[SP][TN], f1a[SP][TM], f1b[SP][TN];
-            auto frags = [&](frag_t (&fa)[SP][TM], frag_t (&fb)[SP][TN], int buf, int kk) {
-                const unsigned short *A = As + buf * SP * A_ELEMS, *B = Bs + buf * SP * B_ELEMS;
-#pragma unroll
-                for (int sp = 0; sp < SP; ++sp) {
-#pragma unroll
-                    for (int i = 0; i < TM; ++i)
-                        fa[sp][i] = *reinterpret_cast<const frag_t *>(A + sp * A_ELEMS + ((wm * TM + i) * 32 + lr) * LDK + kk * 16 + lh * 8);
-#pragma unroll
-                    for (int j = 0; j < TN; ++j)
-                        fb[sp][j] = *reinterpret_cast<const frag_t *>(B + sp * B_ELEMS + ((wn * TN + j) * 32 + lr) * LDK + kk * 16 + lh * 8);
-                }
-            };
-            auto mma = [&](frag_t (&fa)[SP][TM], frag_t (&fb)[SP][TN]) {
-#define RR_MM(ACC, PA, PB)                                                                                          \
-    _Pragma("unroll") for (int i = 0; i < TM; ++i) _Pragma("unroll") for (int j = 0; j < TN; ++j)                      \
-        ACC[i][j] = mfma16(fa[PA][i], fb[PB][j], ACC[i][j]);
-                RR_MM(acc, 0, 0)
-                if constexpr (SP >= 2) { RR_MM(acl, 0, 1) RR_MM(acl, 1, 0) }
-                if constexpr (SP == 3) { RR_MM(acl, 1, 1) RR_MM(acl, 0, 2) RR_MM(acl, 2, 0) }
-#undef RR_MM
-            };
-            __builtin_amdgcn_s_setprio(1);
-            RR_WS_BARRIER();
-            frags(f0a, f0b, 0, 0);
-            for (int kc = kc_lo; kc < kc_hi; ++kc) {
-                const int buf = (kc - kc_lo) & 1;
-                frags(f1a, f1b, buf, 1);
-                __builtin_amdgcn_sched_barrier(0);
-                mma(f0a, f0b);
-                __builtin_amdgcn_sched_barrier(0);
-                RR_WS_BARRIER();
-                frags(f0a, f0b, buf ^ 1, 0);        // (after the last tile: a buffer of zeros, never used)
-                __builtin_amdgcn_sched_barrier(0);
-                mma(f1a, f1b);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            __builtin_amdgcn_s_setprio(0);
-        }
-#undef RR_WS_BARRIER
-    } else {
     if (kc_lo < kc_hi) {
         prep();
         load_all();
@@ -529,7 +400,6 @@ __global__ __launch_bounds__(WS ? 512 : 256, (!WS && SP == 2) ? 2 : 1) void conv
         }
         __syncthreads();
     }
-    }
     if constexpr (SP > 1) {
 #pragma unroll
         for (int i = 0; i < TM; ++i)
@@ -546,7 +416,6 @@ __global__ __launch_bounds__(WS ? 512 : 256, (!WS && SP == 2) ? 2 : 1) void conv
     const __amdgpu_buffer_rsrc_t bs_rs_y = make_srd(BNS ? a.bs_y : a.src, (long)a.M * a.DC * 4);
     const __amdgpu_buffer_rsrc_t bs_rs_z = make_srd(BNS && a.bs_z != nullptr ? a.bs_z : a.src, (long)a.M * a.DC * 4);
     const int mode_e = a.ksplit > 1 ? 2 : (a.accumulate ? 1 : 0);
-    if (!producer) {
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
         const int ncol = n0 + (wn * TN + j) * 32 + lr;
@@ -632,10 +501,9 @@ __global__ __launch_bounds__(WS ? 512 : 256, (!WS && SP == 2) ? 2 : 1) void conv
             }
         }
     }
-    }
     if (do_stats) {
         __syncthreads();
-        if (t < BN && n0 + t < a.DC && !producer) {
+        if (t < BN && n0 + t < a.DC) {
             double d1 = 0.0, d2 = 0.0;
 #pragma unroll
             for (int w = 0; w < WM; ++w) {

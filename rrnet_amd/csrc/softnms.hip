@@ -341,10 +341,6 @@ __device__ __forceinline__ void soft_nms_registers(float *b, const int stride, c
         int d = 0;                                 // wave total of the lanes' death counts (0..NB each): NB ballots, no shuffles
 #pragma unroll
         for (int q = 1; q <= NB; ++q) d += __popcll(__ballot(dead >= q));
-        if (T == 64) {
-            dead_total = d;
-            return r;
-        }
         // slot = [score key, ~position, deaths, tied | x1, y1, x2, y2]: two 16-byte halves.  Every wave's first half is
         // read unconditionally (W independent ds_read_b128: one LDS round trip), the winner's box in a second one.
         typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -634,7 +630,7 @@ __global__ __launch_bounds__(T) void soft_nms_kernel(float *boxes, const int *se
     __syncthreads();
     __shared__ int outn;
     if (threadIdx.x == 0) outn = n;
-    if (T > 64 && n <= SMALL_SEG) {
+    if (n <= SMALL_SEG) {
         // The launch is sized for the LONGEST possible segment (the caller's bound, e.g. K = 1500), the typical
         // (frame, class) segment holds ~150 boxes: those run on the first wave alone — same algorithm, wave
         // shuffles instead of block barriers in every one of its ~N steps (the barriers were most of the step).
@@ -751,8 +747,8 @@ static int soft_nms_launch(float *boxes, const int *seg_off, const int *seg_len,
         RR_CHECK_LAUNCH("rr_soft_nms_segments");
         return RR_OK;
     }
-    if (max_seg_boxes <= SMALL_SEG) LAUNCH(64, lds, cap, -1, ALL);
-    else if (in_lds && max_seg_boxes > MID_SEG) {
+    // (segments of up to 256 boxes never get here: the register kernels above take them)
+    if (in_lds && max_seg_boxes > MID_SEG) {
         // The caller's bound is the LONGEST possible segment (K = 1500 at inference: 37.5 KB of LDS per workgroup = four
         // segments per CU) while a typical (frame, class) segment holds ~150 boxes.  Two launches: the segments of up to
         // MID_SEG boxes with 12.8 KB of LDS each (all 1280 segments of a 128-frame batch are resident at once: the launch

@@ -47,9 +47,6 @@ class DCNv2(nn.Module):
                            self.deformable_groups, bf16=self.bf16)
 
 
-_PAD_OFFSET_CONV = True     # A/B switch
-
-
 class DCN(DCNv2):
     def __init__(self, in_channels, out_channels, kernel_size, stride, padding, dilation=1, deformable_groups=1):
         super().__init__(in_channels, out_channels, kernel_size, stride, padding, dilation, deformable_groups)
@@ -74,7 +71,7 @@ class DCN(DCNv2):
         com = self.conv_offset_mask
         k = com.weight.shape[0]
         kp = (k + 3) // 4 * 4
-        if kp != k and _PAD_OFFSET_CONV:
+        if kp != k:
             wp = torch.cat((com.weight, com.weight.new_zeros((kp - k,) + tuple(com.weight.shape[1:]))), 0)
             bp = torch.cat((com.bias, com.bias.new_zeros(kp - k))) if com.bias is not None else None
             out = RF.conv_weight(xa, wp, bp, com.stride[0], tuple(com.padding))[:, :k]

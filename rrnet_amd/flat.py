@@ -71,7 +71,7 @@ class FlatParams:
         self._offs = {id(p): o for p, o in zip(params, offs)}
         # flipped / transposed copies of the 4-D filters for the stride-1 data gradients (rr_conv_dgrad_s1*): one flat
         # buffer with the parameters' offsets, filled by ONE launch per optimizer step instead of one launch per layer
-        # inside backward (lazily allocated at the first data gradient; RR_WT_CACHE=0: per-layer launches as before)
+        # inside backward (lazily allocated at the first data gradient)
         self.wt_flat = None
         self.w16_flat = self.wt16_flat = None       # bf16 copies (plain / flipped) for the bf16-operand kernels, on demand
         self._wt_table = None

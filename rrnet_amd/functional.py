@@ -99,8 +99,8 @@ def _wgrad_async(fn, device, *tensors):
         torch.autograd.Variable._execution_engine.queue_callback(_end_of_backward)
 
 
-_SYNC_COALESCE = True   # joint SyncBN exchange of layers that share their input
-_G_INTO = True     # residual gradient added into the fan-in buffer by bn_bwd_apply itself
+_G_INTO = True     # residual gradient added into the fan-in buffer by bn_bwd_apply itself (False: a separate add; the other arm of
+                   # tests/test_conv_gpu.py::test_train_step_gradients_equal_with_and_without_fused_bn_sums)
 BN_FUSED_STATS = True    # single process: slab -> statistics -> coefficients in one launch
 
 
@@ -245,8 +245,6 @@ class _ConvBnAct(torch.autograd.Function):
         # inside this kernel (no separate g tensor, no add pass)
         g_into = res_acc.buf if (want_g and res_acc is not None and res_acc.buf is not None and ctx.needs_input_grad[4]
                                  and _G_INTO) else None
-        if g_into is not None:
-            res_acc.begin(dz.device)
         # conv16: when the data gradient (if one is wanted) and the weight gradient of this convolution both read dy's bf16
         # image, the fp32 dy is never written
         w_t0 = _grad_target(w)
@@ -258,8 +256,6 @@ class _ConvBnAct(torch.autograd.Function):
         dy, g = ops.bn_bwd_apply(dz, z, y, mean, invstd, gamma, sums, count, want_g,
                                  dg_t if fused_affine else None, db_t if fused_affine else None, cnt_dev, msc, msh,
                                  g_into=g_into, bf16_only=only16)
-        if g_into is not None:
-            res_acc.end(dz.device)
         dx = None
         if ctx.needs_input_grad[0]:
             dx = _input_grad(dy, wc, ctx.xshape, stride, pad, x_acc, in_link, x, w)
@@ -288,12 +284,9 @@ class _ConvBnAct(torch.autograd.Function):
                 res_acc.pending -= 1
                 if res_acc.buf is None:
                     res_acc.buf = g
-                    res_acc.end(dz.device)
                 else:
                     if g_into is None:
-                        res_acc.begin(dz.device)
                         res_acc.buf.add_(g)
-                        res_acc.end(dz.device)
                     dres = None
         return dx, ret_dw, ret_dg, ret_db, dres, None, None, None, None, None, None, None, None
 
@@ -343,12 +336,9 @@ def _input_grad(dy, wc, xshape, stride, pad, x_acc, in_link, x, w_param=None):
     x_acc.pending -= 1
     if x_acc.buf is not None:
         # another consumer of x already produced its gradient: add into it inside the dgrad epilogue
-        x_acc.begin(dy.device)
         ops.conv_dgrad(dy, wc, xshape, stride, pad, out=x_acc.buf, accumulate=True, bnsum=link, bnsum_z=x, wt=wt, wt16=wt16)
-        x_acc.end(dy.device)
         return None
     x_acc.buf = ops.conv_dgrad(dy, wc, xshape, stride, pad, bnsum=link, bnsum_z=x, wt=wt, wt16=wt16)
-    x_acc.end(dy.device)
     return x_acc.buf
 
 
@@ -517,7 +507,7 @@ class _ConvBnSyncMulti(torch.autograd.Function):
 
 def sync_coalescing(bn):
     """True when the joint SyncBN node applies: statistics exchanged across ranks, training, gradients on."""
-    return _SYNC_COALESCE and _is_sync(bn) and bn.training and torch.is_grad_enabled()
+    return _is_sync(bn) and bn.training and torch.is_grad_enabled()
 
 
 def conv_bn_act_multi(x, layers):
@@ -677,16 +667,11 @@ class _FanOut(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, n):
         ctx.n = n
-        ctx.acc = None                     # the shared GradAcc of the views (fanout_shared), for its stream events
         ctx.set_materialize_grads(False)   # a consumer that accumulated into a shared GradAcc hands back None
         return tuple(x.view_as(x) for _ in range(n))
 
     @staticmethod
     def backward(ctx, *grads):
-        if ctx.acc is not None:
-            dev = next((g.device for g in grads if g is not None), None)
-            if dev is not None:
-                ctx.acc.begin(dev)         # contributors that added into the buffer from other streams
         gs = [ops.to_nhwc(g) if g.dim() == 4 else g.contiguous() for g in grads if g is not None]
         if not gs:
             return None, None
@@ -724,30 +709,19 @@ def fanout(x, n):
     return outs
 
 
-_SHARED_ACC = True
-
 class GradAcc:
     """Fan-in target shared by the consumers of one fan-out: the first consumer to run its backward publishes its
     input gradient here, the others add into it (inside their dgrad epilogue) and hand autograd `None`, so the
     fan-out's backward finds one complete gradient and launches no sum kernel.  The views a fan-out returns carry
     the accumulator as `_rr_acc`; convolution nodes pick it up from their input, and a nested fan-out of such a view
-    (a residual block at the head of an hourglass branch) joins the same accumulator."""
+    (a residual block at the head of an hourglass branch) joins the same accumulator.  Every contributor writes the buffer
+    on the caller's stream, so its raw-pointer writes need no ordering beyond the stream's own."""
     __slots__ = ("buf", "pending", "link")
 
     def __init__(self):
         self.buf = None
         self.pending = 0        # registered contributors that have not run their backward yet
         self.link = None        # ops.BnLink of the fanned-out tensor when a conv -> bn layer produced it
-
-    # The buffer is written through raw pointers, which autograd's own stream hand-over never sees: every contributor
-    # brackets its write with begin / end.  All contributors run on the caller's stream today, so both are no-ops — the
-    # hourglass branch streams that needed events here were measured (0 to -12 %, DESIGN §13.2) and removed in round 6; the
-    # bracket stays as the one place where an ordering would have to go.
-    def begin(self, device):
-        pass
-
-    def end(self, device):
-        pass
 
 
 def fanout_shared(x, n):
@@ -756,14 +730,10 @@ def fanout_shared(x, n):
     if n == 1 or not x.requires_grad:
         return (x,) * n + (None,)
     outs = _FanOut.apply(x, n)
-    if not _SHARED_ACC:
-        return outs + (None,)
     acc = getattr(x, "_rr_acc", None)
     if acc is None:
         acc = GradAcc()
         acc.link = getattr(x, "_rr_bnlink", None)
-    if outs[0].grad_fn is not None:         # (None under torch.no_grad(): nothing will run a backward)
-        outs[0].grad_fn.acc = acc           # (the node object is the ctx its backward receives)
     amax = getattr(x, "_rr_amax", None)     # (split-operand kernels: the views ARE x — its remembered maximum travels with them)
     for o in outs:
         o._rr_acc = acc
@@ -979,12 +949,9 @@ def _acc_publish(acc, g):
     acc.pending.)"""
     if acc.buf is None:
         acc.buf = g
-        acc.end(g.device)
         return g
-    acc.begin(g.device)
     ops.amax_drop(acc.buf)
     acc.buf.add_(g)
-    acc.end(g.device)
     return None
 
 
@@ -1018,7 +985,7 @@ class _DCNv2(torch.autograd.Function):
             bf = bool(ctx.bf16 and DCN_BF16_BWD)
             # both kernels take dY's bf16 image by LDS-DMA: its producer's, or ONE conversion pass made here, before the fork
             # (behind the weight-gradient kernel, which holds every CU, the pass took 2.4 ms instead of 0.2)
-            img = ops.bf16_of(dy) if (bf and ops._DCN_DYB and not ops.is_phantom(dy)) else None
+            img = ops.bf16_of(dy) if (bf and not ops.is_phantom(dy)) else None
             if side is not None:
                 side.wait_stream(cur)
                 with torch.cuda.stream(side):
@@ -1034,9 +1001,7 @@ class _DCNv2(torch.autograd.Function):
                 # gradient there, the others add into it — here inside the kernel, whose scatter is float atomics anyway
                 x_acc.pending -= 1
                 if x_acc.buf is not None and ops.dcn_dgrad_accumulates(bf):
-                    x_acc.begin(dy.device)
                     _, doff, dmask = ops.dcn_dgrad(x, off, m, w, dy, stride, pad, dil, dg, bf16=bf, out=x_acc.buf)
-                    x_acc.end(dy.device)
                     dx = None
                 else:
                     dx, doff, dmask = ops.dcn_dgrad(x, off, m, w, dy, stride, pad, dil, dg, bf16=bf)
@@ -1134,7 +1099,7 @@ def _side_stream(device, tag="dcn"):
 
 DCN_BF16_BWD = True         # bf16 forward -> bf16-operand wgrad / dgrad (0: fp32 kernels)
 DCN_BWD_STREAMS = os.environ.get("RR_DCN_BWD_STREAMS", "1") != "0"   # wgrad and dgrad of the fused backward side by side
-DCN_FUSED_BWD = True   # 0: the reference's column-buffer structure (A/B switch)
+DCN_FUSED_BWD = True   # False: the reference's column-buffer structure (test_dcn_gpu.py::test_dcn_fused_backward_equals_column_path)
 DCN_BF16 = os.environ.get("RR_DCN_BF16", "0") == "1"   # BASELINE config 4: bf16 matrix operands in the DCN forward
 
 

@@ -96,7 +96,7 @@ _MID_TILES = 48
 
 def _igemm_name(kind, n_gemm, scalar, m_rows=1 << 30, stride=1):
     """Timer key = the HIP kernel instance that runs (tile width as picked in csrc/conv.hip: 128 columns, 64 for
-    33..64-column layers, 32 for narrow ones and for layers with at most RR_CONV_SMALL_TILES 128x128 tiles)."""
+    33..64-column layers, 32 for narrow ones and for layers with at most rr_conv_small_tiles() 128x128 tiles)."""
     bn = 128 if n_gemm > 64 or (scalar and n_gemm > 32) else (64 if n_gemm > 32 else 32)
     if bn == 128 and not scalar and (kind == "fprop" or stride == 1):
         tiles = -(-m_rows // 128) * -(-n_gemm // 128)
@@ -139,10 +139,6 @@ def f32_of(t):
     if not is_phantom(t):
         return t
     img = image_of(t)
-    if _PHANTOM_TRACE:
-        import traceback
-        key = (tuple(t.shape), traceback.format_stack(limit=4)[0].strip().split("\n")[0])
-        PHANTOM_WIDENED[key] = PHANTOM_WIDENED.get(key, 0) + 1
     out = torch.empty_like(img, dtype=torch.float32)
     assert out.stride() == img.stride()
     _C.check(_C.fn("rr_from_bf16")(_C.ptr(img), _C.ptr(out), img.numel(), _C.stream()), "rr_from_bf16")
@@ -248,8 +244,6 @@ def _bf16_ok(c, k, r, s, *tensors, pixels=None):
 
 
 _SPLIT_MIN_PIXELS = 2048    # N*P*Q below which a layer stays on the fp32 kernels
-_FUSED_AMAX_FWD = True    # bn_apply leaves max |out| for the next convolution
-_FUSED_AMAX_BWD = True    # bn_bwd_apply leaves max |dx| for the data / weight gradient
 _SPLIT_PRESPLIT_PIXELS = 65536   # from here on the filter is split once per launch
 
 
@@ -266,7 +260,6 @@ def split_filter(w, amax_word, pixels, flat=None):
     return out
 
 
-_SPLIT_PER_LAUNCH = True     # the filter split at every large launch into a fresh temporary (0: in-tile split)
 _SPLIT_MIN_CH = 64                                                         # narrower layers (either side) likewise
 _SPLIT_MIN_K = 1024               # C*R*S (reduction length) likewise
 
@@ -321,8 +314,6 @@ class _PhantomScope(threading.local):
 
 
 _PHANTOM = _PhantomScope()
-_PHANTOM_TRACE = False       # count, by shape and caller, the bf16-only tensors that had to be widened
-PHANTOM_WIDENED = {}
 _PHANTOM_ENABLED = os.environ.get("RR_BF16_ONLY_ACT", "1") != "0"      # 0: every activation keeps its fp32 tensor next to the image
 
 
@@ -347,12 +338,9 @@ def phantom_out_ok(c, pixels, device):
                 and c % 256 == 0 and pixels >= _CONV16_MIN_PIXELS)
 
 
-_PHANTOM_Y = True      # 0: pre-BN convolution outputs keep their fp32 tensor
-
-
 def phantom_y_ok(k, x, w, stride, pad):
     """conv -> bn layers inside the backbone (phantom_scope): may the convolution's pre-BN output exist as a bf16 image only?"""
-    if not (_PHANTOM_Y and x.is_cuda):
+    if not x.is_cuda:
         return False
     n, c, h, wd = x.shape
     r, s = w.shape[2], w.shape[3]
@@ -544,7 +532,7 @@ def conv_fprop(x, w, bias=None, stride=1, pad=(0, 0), relu=False, want_stats=Fal
     f = _C.fn(("rr_conv_fprop", "rr_conv_fprop_bf16", "rr_conv_fprop_f16x3")[bf])
     flops = 2.0 * n * p * q * k * (c * r * s if algo_kg is None else algo_kg)
     # w16: the filter already rounded to bf16 (optional); split operands: the two tensors' maxima
-    if bf == MATH_F16X3 and w_split is None and _SPLIT_PER_LAUNCH:
+    if bf == MATH_F16X3 and w_split is None:
         # a LOCAL that lives until the launch below has been enqueued: built inside the argument tuple the temporary was
         # released before the launch, the caching allocator handed its block to the next zero-filled scratch, and the
         # data gradients read a filter of zeros / garbage — non-finite gradients, and a step that ran 10 % FASTER
@@ -557,14 +545,11 @@ def conv_fprop(x, w, bias=None, stride=1, pad=(0, 0), relu=False, want_stats=Fal
     return (y, slab) if want_stats else y
 
 
-_STEM_PACK = True
-
-
 def conv_packable(x, w, stride):
     """A convolution on very few channels (the 7x7 stride-2 stem on an RGB image): its taps are packed into one row
     per output pixel and it runs as a 1x1 convolution on the vector kernels (conv_fprop_packed / conv_wgrad_packed)."""
     k, c, r, s = w.shape
-    return _STEM_PACK and c % 4 != 0 and 32 < r * s * c <= 512 and k >= 32 and not x.requires_grad
+    return c % 4 != 0 and 32 < r * s * c <= 512 and k >= 32 and not x.requires_grad
 
 
 def conv_fprop_packed(x, w, stride, pad, want_stats=False):
@@ -612,7 +597,7 @@ def stem_wgrad_s2d(x, dy, dw):
     return dw
 
 
-_DGRAD_VIA_FPROP = True
+_DGRAD_VIA_FPROP = True             # False: rr_conv_dgrad (tests/test_conv_gpu.py::test_conv_fprop_dgrad_wgrad checks both)
 _DGRAD_VIA_FPROP_MIN_PIXELS = 4096  # below: the dgrad kernel's split-K wins
 
 
@@ -637,12 +622,13 @@ class BnLink:
         self.consumers = 0
 
 
-_DGRAD_BNSUM = True
+_DGRAD_BNSUM = True     # False: rr_bn_bwd_reduce (test_conv_gpu.py::test_train_step_gradients_equal_with_and_without_fused_bn_sums)
 # measured at 8 x 256 x 256 x 256 (tools/bench_head_dgrad.py): K = 10: 0.23 ms against 0.40, K = 2: 0.22 against 0.39; K = 34 (the WH head: 144 filter
 # registers per lane, two waves per SIMD): 0.58 against 0.48 — that layer stays on the implicit-GEMM kernel
 _HEAD_DGRAD_MAX_K = 12
-_HEAD_DGRAD = True      # 0: the heads' narrow 1x1 data gradients on the implicit-GEMM kernel (round 3)
-_BF16_S2_DGRAD = True     # A/B: stride-2 data gradients stay on the fp32 kernel
+_HEAD_DGRAD = True      # False: the heads' narrow 1x1 data gradients on the implicit-GEMM kernel
+                        # (test_conv_gpu.py::test_head_1x1_dgrad_kernel_accumulate_and_legacy_path checks both)
+_BF16_S2_DGRAD = True   # False: stride-2 data gradients stay on the fp32 kernel (tests/kernel_audit.py reads it to mirror the dispatch)
 
 
 def _s2_parity_pads_ok(r, s, pad):
@@ -777,7 +763,7 @@ def conv_dgrad(dy, w, x_shape, stride=1, pad=(0, 0), out=None, accumulate=False,
         bf = _bf16_ok(k, c, r, s, dy, out, pixels=n * h * wd)
         sfx, tsfx = (("", ""), ("_bf16", "+bf16"), ("_f16x3", "+f16x3"))[bf]
         # wt16: the flipped filter already in bf16 (optional); split operands: the maxima of dy and of the filter
-        if bf == MATH_F16X3 and wt_split is None and _SPLIT_PER_LAUNCH:
+        if bf == MATH_F16X3 and wt_split is None:
             wt_split = split_filter(w, amax_of(w), n * h * wd, flat=wt)
         tail = _math_tail(bf, wt16, dy, w, wt_split)
         if (bnsum is not None and not bnsum.relu_bias and _DGRAD_BNSUM and bnsum.y is not None and c <= 1024 and out.numel() * 4 < (1 << 31)
@@ -992,7 +978,7 @@ def bn_apply(y, scale, shift, residual=None, relu=False, res_scale=None, res_shi
             b16_attach(out, out16)
         return out
     out = empty_nhwc(n, c, h, w, y.device)
-    if _mode() == MATH_F16X3 and y.is_cuda and n * h * w >= _SPLIT_MIN_PIXELS and _FUSED_AMAX_FWD:
+    if _mode() == MATH_F16X3 and y.is_cuda and n * h * w >= _SPLIT_MIN_PIXELS:
         # split-operand convolutions: the consumer's operand scale comes out of this pass (see amax_of)
         word = _ZEROS.take(1, y.device)
         _C.check(_C.fn("rr_bn_apply_amax")(_C.ptr(y), _C.ptr(scale), _C.ptr(shift), _C.ptr(residual), _C.ptr(res_scale),
@@ -1065,7 +1051,7 @@ def bn_bwd_apply(dz, z, y, mean, invstd, gamma, sums, count, want_g=False, dgamm
         g = g_into
     else:
         g = empty_nhwc(n, c, h, w, y.device) if want_g else None
-    if _mode() == MATH_F16X3 and y.is_cuda and n * h * w >= _SPLIT_MIN_PIXELS and _FUSED_AMAX_BWD:
+    if _mode() == MATH_F16X3 and y.is_cuda and n * h * w >= _SPLIT_MIN_PIXELS:
         # split-operand convolutions: dx is the operand of the data / weight gradient launched next — its maximum comes out
         # of this pass.  (dx is a fresh tensor that nothing adds into later: the remembered maximum cannot go stale.)
         word = _ZEROS.take(1, y.device)
@@ -1463,8 +1449,7 @@ def roi_align_bwd(dout, rois, feat_shape, out_size, spatial_scale=1.0, sampling_
 # ---------------------------------------------------------------------------------------------
 # DCNv2
 # ---------------------------------------------------------------------------------------------
-_DCN_WPACK = True
-_DCN_DYB = True      # bf16 data gradient stages dY from a bf16 copy made once per call
+_DCN_WPACK = True       # False: rr_dcn_dgrad_bf16_ws (test_dcn_gpu.py::test_dcn_bf16_dgrad_equals_fp32_dgrad_on_rounded_operands)
 
 
 def dcn_fwd(x, offset, mask, w, bias, stride, pad, dilation, dg, bf16=False):
@@ -1519,7 +1504,7 @@ def dcn_wgrad(x, offset, mask, dy, dw, stride, pad, dilation, dg, bf16=False, dy
     assert is_nhwc(x) and is_nhwc(offset) and is_nhwc(mask) and is_nhwc(dy) and is_nhwc(dw)
     n, c, h, wd = x.shape
     k, _, r, s = dw.shape
-    if bf16 and dy_img is not None and _DCN_DYB:
+    if bf16 and dy_img is not None:
         _C.check(_C.fn("rr_dcn_wgrad_bf16_img")(_C.ptr(x), _C.ptr(offset), _C.ptr(mask), _C.ptr(dy), _C.ptr(dy_img), _C.ptr(dw), n, h,
                                                 wd, c, k, r, s, stride, pad[0], pad[1], dilation, dg, _C.stream()),
                  "rr_dcn_wgrad_bf16_img")
@@ -1532,7 +1517,7 @@ def dcn_wgrad(x, offset, mask, dy, dw, stride, pad, dilation, dg, bf16=False, dy
 
 def dcn_dgrad_accumulates(bf16):
     """True when dcn_dgrad(..., out=buf) adds into buf inside the kernel (the LDS-DMA data gradient of the bf16 path)."""
-    return bool(bf16 and _DCN_DYB and _DCN_WPACK)
+    return bool(bf16 and _DCN_WPACK)
 
 
 def dcn_dgrad(x, offset, mask, w, dy, stride, pad, dilation, dg, bf16=False, out=None):
@@ -1549,10 +1534,10 @@ def dcn_dgrad(x, offset, mask, w, dy, stride, pad, dilation, dg, bf16=False, out
     doff = torch.empty_like(offset)
     dmask = torch.empty_like(mask)
     assert doff.stride() == offset.stride() and dmask.stride() == mask.stride()
-    img = b16_carry(dy) if (bf16 and _DCN_DYB) else None
+    img = b16_carry(dy) if bf16 else None
     if img is not None and getattr(dy, "_rr_b16")[1] not in (None, torch.cuda.current_stream(dy.device).cuda_stream):
         img = None
-    if bf16 and _DCN_DYB and _DCN_WPACK:
+    if bf16 and _DCN_WPACK:
         # both sweep operands by LDS-DMA: weights packed to bf16 inside the call; dY = its producer's bf16 image when there is
         # one (the heads' 1x1 data gradient), else rounded once into the workspace
         ws = torch.empty(_C.fn("rr_dcn_dgrad_ws_bytes")(dy.shape[0], dy.shape[2], dy.shape[3], c, k, r, s, int(img is not None)),
@@ -1568,7 +1553,7 @@ def dcn_dgrad(x, offset, mask, w, dy, stride, pad, dilation, dg, bf16=False, out
                                                 _C.ptr(doff), _C.ptr(dmask), n, h, wd, c, k, r, s, stride, pad[0], pad[1],
                                                 dilation, dg, _C.stream()), "rr_dcn_dgrad_bf16_img")
         return dx, doff, dmask
-    if bf16 and _DCN_DYB:
+    if bf16:
         # dY rounded to bf16 once per call (caller scratch): the sweep's eight re-reads of a block's dY tile stay in L2
         dyb = torch.empty(_C.fn("rr_dcn_dyb_bytes")(dy.shape[0], dy.shape[2], dy.shape[3], k), dtype=torch.uint8, device=x.device)
         _C.check(_C.fn("rr_dcn_dgrad_bf16_ws")(_C.ptr(x), _C.ptr(offset), _C.ptr(mask), _C.ptr(w), _C.ptr(dy), _C.ptr(dx),

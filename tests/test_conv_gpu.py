@@ -257,7 +257,7 @@ def test_dgrad_with_producer_bn_backward_sums(cfg):
 
 
 def test_train_step_gradients_equal_with_and_without_fused_bn_sums():
-    """A tiny hourglass train step with the fused producer sums (default) and with RR_DGRAD_BNSUM / RR_BN_G_INTO off:
+    """A tiny hourglass train step with the fused producer sums (default) and with ops._DGRAD_BNSUM / functional._G_INTO off:
     same losses, same flat gradient up to summation order; the fused path really ran (bn_bwd_reduce launches drop)."""
     from types import SimpleNamespace
     from rrnet_amd import functional as RF, ops

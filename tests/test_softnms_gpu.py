@@ -79,10 +79,10 @@ def test_batched_segments_vs_oracle(method, Nt, thr):
         assert np.array_equal(o[:, :5].view(np.uint32), w[:k, :5].view(np.uint32))
 
 
-def test_large_segment_global_workspace_path():
+def test_large_segment_register_kernel_512x18():
     from oracle import nms as onms
     rng = np.random.default_rng(5)
-    n = 6500                                         # > RR_SOFT_NMS_LDS_MAX
+    n = 6500                                         # > RR_SOFT_NMS_LDS_MAX: soft_nms_reg_kernel<512, 18>
     xy = rng.uniform(0, 1500, (n, 2))
     wh = rng.uniform(8, 120, (n, 2))
     b = np.concatenate([xy, xy + wh, rng.uniform(0.01, 1, (n, 1))], 1).astype(np.float32)

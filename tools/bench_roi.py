@@ -36,7 +36,6 @@ def main():
             torch.cuda.synchronize()
             res[name + "_ms"] = round(e0.elapsed_time(e1) / a.iters, 4)
     res["rois"] = int(rois.shape[0])
-    res["lds_kb"] = int(os.environ.get("RR_ROI_LDS_KB", "0"))
     print(json.dumps(res))
 
 
