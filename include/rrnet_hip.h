@@ -387,8 +387,10 @@ int rr_conv1x1_bn_res_relu_avgpool(const float *h, const float *w, const float *
 int rr_wh_shift_sum_fwd(const float *t, const float *bias_w, const float *bias_h, float *out, int n, int h,
                         int w, int k, int ct, hipStream_t stream);
 int rr_wh_shift_sum_bwd(const float *dout, float *dt, int n, int h, int w, int k, int ct, hipStream_t stream);
-int rr_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long n, float lr,
-                 float beta1, float beta2, float eps, int step, float grad_scale, hipStream_t stream);
+/* torch.optim.Adam's fp32 update: lr, betas in double; 1 - beta and the bias corrections 1 - beta^step are formed in
+ * double and rounded once (step counts from 1). */
+int rr_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long n, double lr,
+                 double beta1, double beta2, float eps, int step, float grad_scale, hipStream_t stream);
 
 /* ---- losses --------------------------------------------------------------------------- *
  * rr_focal_loss_fwd/bwd: clamp(sigmoid(x),1e-4,1-1e-4) + focal_loss_for_hm of

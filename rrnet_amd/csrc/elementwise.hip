@@ -718,16 +718,17 @@ __global__ __launch_bounds__(EW_THREADS) void wh_shift_sum_bwd_kernel(const floa
 
 // ---- fused Adam over the flat parameter buffer (torch.optim.Adam defaults, no weight decay,
 //      no amsgrad; operators/rrnet_operator.py:29) -------------------------------------------
-__global__ __launch_bounds__(EW_THREADS) void adam_kernel(f32x4 *p, const f32x4 *g, f32x4 *m, f32x4 *v, long n4, float lr,
-                                                          float b1, float b2, float eps, float bc1, float bc2_sqrt,
-                                                          float grad_scale)
+// b1, 1 - b1, b2, 1 - b2, step_size = lr / (1 - b1^t) and sqrt(1 - b2^t) come from the host, computed in double from
+// the double betas and rounded once, as torch.optim.Adam's fp32 update uses them (1.f - (float)0.999 is 1.3e-5 off 0.001)
+__global__ __launch_bounds__(EW_THREADS) void adam_kernel(f32x4 *p, const f32x4 *g, f32x4 *m, f32x4 *v, long n4,
+                                                          float step_size, float b1, float omb1, float b2, float omb2,
+                                                          float eps, float bc2_sqrt, float grad_scale)
 {
-    const float step_size = lr / bc1;
     for (long i = (long)blockIdx.x * EW_THREADS + threadIdx.x; i < n4; i += (long)gridDim.x * EW_THREADS) {
         const f32x4 gg = g[i] * grad_scale;
         f32x4 mm = m[i], vv = v[i], pp = p[i];
-        mm = mm * b1 + gg * (1.f - b1);
-        vv = vv * b2 + gg * gg * (1.f - b2);
+        mm = mm * b1 + gg * omb1;
+        vv = vv * b2 + gg * gg * omb2;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const float denom = sqrtf(vv[e]) / bc2_sqrt + eps;
@@ -1244,14 +1245,15 @@ extern "C" int rr_wh_shift_sum_bwd(const float *dout, float *dt, int n, int h, i
     return RR_OK;
 }
 
-extern "C" int rr_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long n, float lr,
-                            float beta1, float beta2, float eps, int step, float grad_scale, hipStream_t stream)
+extern "C" int rr_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long n, double lr,
+                            double beta1, double beta2, float eps, int step, float grad_scale, hipStream_t stream)
 {
     RR_CHECK_ARG(n % 4 == 0 && step >= 1, "rr_adam_step: n must be a multiple of 4 (pad the flat buffer), step >= 1");
-    const float bc1 = 1.f - powf(beta1, (float)step);
-    const float bc2 = 1.f - powf(beta2, (float)step);
+    const double bc1 = 1.0 - pow(beta1, (double)step);
+    const double bc2 = 1.0 - pow(beta2, (double)step);
     EW_LAUNCH(adam_kernel, n / 4, stream, (f32x4 *)param, (const f32x4 *)grad, (f32x4 *)exp_avg, (f32x4 *)exp_avg_sq, n / 4,
-              lr, beta1, beta2, eps, bc1, sqrtf(bc2), grad_scale);
+              (float)(lr / bc1), (float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), eps,
+              (float)sqrt(bc2), grad_scale);
     RR_CHECK_LAUNCH("rr_adam_step");
     return RR_OK;
 }

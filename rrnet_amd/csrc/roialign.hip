@@ -34,6 +34,15 @@ __device__ __forceinline__ Tap make_tap(float y, float x, int H, int W, long C)
     return t;
 }
 
+// Sample position start + p * bin + (i + 0.5) * bin / g with every operation rounded on its own, as the reference's
+// CPU definition evaluates it: an FMA-contracted start + p * bin moves samples by an ulp, which the backward's bilinear
+// weights turn into gradient errors of |dout| * ulp(position).
+__device__ __forceinline__ float sample_pos(float start, int p, float bin, int i, int g)
+{
+#pragma clang fp contract(off)
+    return start + (float)p * bin + ((float)i + 0.5f) * bin / (float)g;
+}
+
 template <bool BWD>
 __global__ __launch_bounds__(256) void roi_align_kernel(const float *feat, float *dfeat, const float *rois, float *out,
                                                         const float *dout, int H, int W, int C, int PH, int PW,
@@ -55,9 +64,9 @@ __global__ __launch_bounds__(256) void roi_align_kernel(const float *feat, float
             float acc = 0.f;
             const float go = BWD ? dout[((long)r * PH * PW + bin) * C + c] / count : 0.f;
             for (int iy = 0; iy < gh; ++iy) {
-                const float y = y1 + ph * bh + ((float)iy + 0.5f) * bh / (float)gh;
+                const float y = sample_pos(y1, ph, bh, iy, gh);
                 for (int ix = 0; ix < gw; ++ix) {
-                    const float x = x1 + pw * bw + ((float)ix + 0.5f) * bw / (float)gw;
+                    const float x = sample_pos(x1, pw, bw, ix, gw);
                     const Tap t = make_tap(y, x, H, W, C);
                     if (!t.ok) continue;
                     if (!BWD) {

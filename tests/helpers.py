@@ -105,3 +105,275 @@ ROI_PIN_CASES = np.array([
     [1, 5.5, 5.5, 17.0, 6.0],         # flat: height clamp, wide bins
     [0, 0.5, 0.5, 22.5, 18.5],        # many samples per bin (adaptive grid 8 x 6)
 ], np.float32)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Seeded host-side inputs for the fp64 kernel checks (tests/test_criterion_gpu.py, tests/test_roi_tail_gpu.py,
+# tests/test_train_gpu.py).  Each generator states what it promises; tests/test_host_logic.py checks the promises.
+# ------------------------------------------------------------------------------------------------------------------
+U32 = 2.0 ** -24                                     # unit roundoff of float32
+FOCAL_CLAMP_LOGIT = float(np.log(1e-4 / (1 - 1e-4)))  # sigmoid(x) == 1e-4 at x = -9.21024 (and 1 - 1e-4 at +9.21024)
+FOCAL_BAND = 5e-3                                    # no logit lies within this of +-FOCAL_CLAMP_LOGIT
+STAGE2_IOU_BAND = 1e-4                               # no fp64 IoU lies within this of 0.5
+
+
+def focal_inputs(shape, seed, with_pos=True):
+    """(logits, gt) float32 NCHW arrays of `shape` for the fused focal loss.  Logits ~ N(-2, 4^2) with +-30 and +-100
+    sprinkled in (saturated: the clamp passes no gradient); values inside the clamp band are moved out of it, where the
+    fp32 and the fp64 clamp masks may legitimately disagree.  gt mixes exact 1.0 peaks (only if `with_pos`), exact 0,
+    np.nextafter(1, 0) (a negative with weight (1-g)^4 ~ 1e-29) and Gaussian-like values in (0, 1)."""
+    rng = np.random.default_rng(seed)
+    n = int(np.prod(shape))
+    x = rng.normal(-2.0, 4.0, n)
+    sat = rng.random(n) < 0.02
+    x[sat] = rng.choice([-100.0, -30.0, 30.0, 100.0], int(sat.sum()))
+    x = x.astype(np.float32).astype(np.float64)
+    near = np.abs(np.abs(x) - abs(FOCAL_CLAMP_LOGIT)) < FOCAL_BAND
+    side = np.where(np.abs(x) < abs(FOCAL_CLAMP_LOGIT), -1.0, 1.0)
+    x[near] = np.sign(x[near]) * (abs(FOCAL_CLAMP_LOGIT) + side[near] * 4 * FOCAL_BAND)
+    u = rng.random(n)
+    gt = np.exp(-rng.exponential(1.5, n))                          # (0, 1]
+    gt = np.where(gt >= 1.0, 0.5, gt)
+    gt[u < 0.4] = 0.0
+    gt[(u >= 0.4) & (u < 0.45)] = np.nextafter(np.float32(1), np.float32(0))
+    if with_pos:
+        gt[(u >= 0.45) & (u < 0.5)] = 1.0
+        gt[0] = 1.0
+    return x.astype(np.float32).reshape(shape), gt.astype(np.float32).reshape(shape)
+
+
+def regl1_inputs(batch, height, width, seed, channels=2, slots=24, all_masked=False):
+    """(pred [B,C,H,W], mask [B,M,1], ind [B,M,1], target [B,M,C]) float32, M = the longest per-image slot list with
+    the shorter ones zero-padded (ind 0, mask 0), as collate_ctnet pads them.  Every image holds two valid slots on one
+    pixel and three on another (the backward's atomic scatter), valid slots with target == pred exactly (sign 0),
+    masked slots whose ind is a valid object's pixel or H*W-1.  `all_masked` zeroes the whole mask; slots=0 gives M=0."""
+    rng = np.random.default_rng(seed)
+    hw = height * width
+    pred = rng.normal(0.0, 2.0, (batch, channels, height, width)).astype(np.float32)
+    if slots == 0:
+        return (pred, np.zeros((batch, 0, 1), np.float32), np.zeros((batch, 0, 1), np.float32),
+                np.zeros((batch, 0, channels), np.float32))
+    counts = [slots] + [int(rng.integers(slots // 2, slots + 1)) for _ in range(batch - 1)]
+    mask = np.zeros((batch, slots, 1), np.float32)
+    ind = np.zeros((batch, slots, 1), np.float32)
+    target = np.zeros((batch, slots, channels), np.float32)
+    for b, cnt in enumerate(counts):
+        nvalid = cnt - 3
+        pix = rng.choice(hw, nvalid, replace=False)
+        pix[1] = pix[0]                                  # two objects on one pixel
+        pix[3] = pix[4] = pix[2]                         # three on another
+        ind[b, :nvalid, 0] = pix
+        mask[b, :nvalid, 0] = 1.0
+        ind[b, nvalid:cnt, 0] = [pix[5], pix[0], hw - 1]  # masked slots pointing at real pixels
+        flat = pred[b].reshape(channels, hw)
+        target[b, :cnt] = (rng.normal(0.0, 2.0, (cnt, channels))).astype(np.float32)
+        target[b, 6, :] = flat[:, int(ind[b, 6, 0])]      # pred == target on both channels
+        target[b, 7, 0] = flat[0, int(ind[b, 7, 0])]      # ... and on one channel
+        target[b, 1, 1] = flat[1, int(ind[b, 1, 0])]      # ... on a shared pixel
+    if all_masked:
+        mask[:] = 0.0
+    return pred, mask, ind, target
+
+
+def _iou64(a, b):
+    area_a = (a[:, 2] - a[:, 0]) * (a[:, 3] - a[:, 1])
+    area_b = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
+    lt = np.maximum(a[:, None, :2], b[None, :, :2])
+    rb = np.minimum(a[:, None, 2:], b[None, :, 2:])
+    wh = np.clip(rb - lt, 0, None)
+    inter = wh[..., 0] * wh[..., 1]
+    return inter / (area_a[:, None] + area_b[None, :] - inter)
+
+
+def stage2_iou_margins(rois, gt, scale):
+    """Per RoI: (distance of the nearest fp64 IoU to 0.5, gap between the best IoU and the best IoU of a gt box that
+    differs from the first maximising box, inf when none).  rois [R,5] feature coords, gt [B,G,>=4] xyxy."""
+    rois = np.asarray(rois, np.float64)
+    gt = np.asarray(gt, np.float64)
+    d05 = np.empty(len(rois))
+    gap = np.empty(len(rois))
+    for r, row in enumerate(rois):
+        g = gt[int(row[0]), :, :4]
+        iou = _iou64(row[None, 1:5] * scale, g)[0]
+        d05[r] = np.abs(iou - 0.5).min()
+        best = int(np.argmax(iou))
+        other = np.any(g != g[best], axis=1)
+        gap[r] = iou[best] - iou[other].max() if other.any() else np.inf
+    return d05, gap
+
+
+def stage2_inputs(seed, batch=8, per_image=300, n_gt=100, scale=4.0, img=512.0, nopos_image=3, allpos_image=5):
+    """(rois [R,5] feature coords, reg [R,4], gt [B,G,8] xyxy image coords) float32.  Rows of gt past each image's
+    object count are zero; gt rows 1 and 6, 7 repeat rows 0 and 5 exactly.  RoIs are jittered gt boxes and random boxes,
+    all of positive area inside the image, shuffled so that images interleave; image `nopos_image` has only RoIs far
+    smaller than any gt box (no positive), every RoI of `allpos_image` is positive.  No fp64 IoU lies within
+    STAGE2_IOU_BAND of 0.5, and a positive RoI's best IoU leads the best IoU of any differing gt box by more than the
+    band (fp32 and fp64 pick the same target)."""
+    rng = np.random.default_rng(seed)
+    gt = np.zeros((batch, n_gt, 8), np.float32)
+    for b in range(batch):
+        cnt = int(rng.integers(n_gt // 3, n_gt - 5))
+        wh = np.exp(rng.uniform(np.log(12), np.log(120), (cnt, 2)))
+        xy = rng.uniform(0, img - wh)
+        gt[b, :cnt, :4] = np.concatenate([xy, xy + wh], 1)
+        gt[b, :cnt, 4] = 1.0
+        gt[b, :cnt, 5] = rng.integers(1, 11, cnt)
+        gt[b, 1] = gt[b, 0]
+        gt[b, 6] = gt[b, 7] = gt[b, 5]
+
+    def draw(b, kind):
+        g = gt[b, :, :4].astype(np.float64)
+        live = np.flatnonzero(g[:, 2] > 0)
+        if kind == "tiny":
+            wh = rng.uniform(1.0, 3.0, 2)
+            xy = rng.uniform(0, img - wh)
+            return np.concatenate([xy, xy + wh])
+        if kind == "random":
+            wh = np.exp(rng.uniform(np.log(4), np.log(150), 2))
+            xy = rng.uniform(0, img - wh)
+            return np.concatenate([xy, xy + wh])
+        box = g[rng.choice(live)]
+        size = np.tile(box[2:] - box[:2], 2)
+        sigma = 0.03 if kind == "tight" else 0.15
+        out = box + rng.normal(0, sigma, 4) * size
+        out[:2] = np.clip(out[:2], 0, img - 2)
+        out[2:] = np.clip(np.maximum(out[2:], out[:2] + 1.0), 1, img)
+        return out
+
+    rows = []
+    for b in range(batch):
+        for _ in range(per_image):
+            kind = ("tiny" if b == nopos_image else "tight" if b == allpos_image
+                    else rng.choice(["jitter", "jitter", "random"]))
+            while True:
+                box = (draw(b, kind) / scale).astype(np.float32)
+                row = np.concatenate([[b], box]).astype(np.float32)
+                d05, gap = stage2_iou_margins(row[None], gt, scale)
+                best = stage2_best_iou(row, gt, scale)
+                if d05[0] <= STAGE2_IOU_BAND or (gap[0] <= STAGE2_IOU_BAND and best > 0.5):
+                    continue
+                if b == allpos_image and not best > 0.5:
+                    continue
+                break
+            rows.append(row)
+    rois = np.stack(rows)[rng.permutation(len(rows))]
+    reg = rng.normal(0.0, 1.0, (len(rois), 4)).astype(np.float32)
+    return rois, reg, gt
+
+
+def stage2_best_iou(row, gt, scale):
+    g = np.asarray(gt, np.float64)[int(row[0]), :, :4]
+    return float(_iou64(np.asarray(row, np.float64)[None, 1:5] * scale, g).max())
+
+
+# RoIAlign backward: a RoI set on which every sample position and bilinear weight is exact in float32.  RoI corners are
+# multiples of 1/8 (in feature-map units, i.e. after spatial_scale) and the bin sizes are dyadic with ceil(bin) a power
+# of two, so bin / samples, the positions, 1 - frac and the weight products carry few bits; samples per bin is a power
+# of two, so weight / count is exact too.  The sum over taps is then the only rounding, in any order, with or without
+# FMA contraction.
+ROI_DYADIC_BINS = (1.75, 3.5, 15.5, 31.5)             # adaptive grid: 2, 4, 16, 32 samples (32 takes the > 16 path)
+ROI_DYADIC_BIN_P = (0.4, 0.4, 0.15, 0.05)
+ROI_DYADIC_BINS_SR2 = (0.625, 1.75, 2.5, 3.5, 5.25, 15.5)
+
+
+def roi_dyadic_set(seed, out_size, sampling_ratio, spatial_scale, height, width, n=40, race=500):
+    """rois [K,5] float32 (input coordinates: feature units / spatial_scale) on images 0 and 1 of a batch of 3 (image 2
+    is never touched): n random dyadic RoIs, partly outside the map, two entirely outside it, and `race` identical RoIs
+    over one ~6x6 patch of image 1 (the backward's atomics race on its pixels)."""
+    rng = np.random.default_rng(seed)
+    ph, pw = out_size
+    rows = []
+    for _ in range(n):
+        if sampling_ratio > 0:
+            by, bx = rng.choice(ROI_DYADIC_BINS_SR2, 2)
+        else:
+            by, bx = rng.choice(ROI_DYADIC_BINS, 2, p=ROI_DYADIC_BIN_P)
+        y1 = rng.integers(-24, 8 * height) / 8.0
+        x1 = rng.integers(-24, 8 * width) / 8.0
+        rows.append([rng.integers(0, 2), x1, y1, x1 + pw * bx, y1 + ph * by])
+    rows.append([0, -40.0, -40.0, -40.0 + pw * 1.75, -40.0 + ph * 1.75])           # every sample < -1
+    rows.append([1, width + 2.0, 1.0, width + 2.0 + pw * 1.75, 1.0 + ph * 1.75])     # every sample > W
+    ry = max(b for b in (0.875, 1.0, 1.75, 2.0) if ph * b <= 6.25)
+    rx = max(b for b in (0.875, 1.0, 1.75, 2.0) if pw * b <= 6.25)
+    rows += [[1, 5.0, 3.0, 5.0 + pw * rx, 3.0 + ph * ry]] * race
+    rois = np.array(rows, np.float64)
+    rois[:, 1:] /= spatial_scale
+    return rois.astype(np.float32)
+
+
+# (out_size, sampling_ratio, spatial_scale, channels) of tests/test_roi_tail_gpu.py: every bin shape meets both sampling
+# modes, both scales and all three channel counts (6 is not a multiple of 4)
+ROI_DYADIC_CASES = [((3, 3), -1, 1.0, 256), ((3, 3), 2, 1.0, 12), ((3, 3), -1, 0.25, 6), ((3, 3), 2, 0.25, 256),
+                    ((7, 7), -1, 1.0, 12), ((7, 7), 2, 1.0, 6), ((7, 7), -1, 0.25, 256), ((7, 7), 2, 0.25, 12),
+                    ((2, 5), -1, 1.0, 6), ((2, 5), 2, 1.0, 256), ((2, 5), -1, 0.25, 12), ((2, 5), 2, 0.25, 6)]
+ROI_DYADIC_MAP = (3, 30, 36)                          # batch, height, width
+
+
+def roi_dyadic_case(size, sr, scale, ch):
+    """The dyadic RoI set of one ROI_DYADIC_CASES entry."""
+    _, h, w = ROI_DYADIC_MAP
+    return roi_dyadic_set(seed=100 * size[0] + 10 * size[1] + ch + (sr > 0), out_size=size, sampling_ratio=sr,
+                          spatial_scale=scale, height=h, width=w)
+
+
+def roi_sample_grid(roi, out_size, spatial_scale, sampling_ratio, dtype):
+    """oracle.ops.roi_align's sample positions of one RoI, evaluated in `dtype` (np.float32 reproduces the oracle's
+    rounding step by step) -> (ys [ph, gh], xs [pw, gw], gh * gw)."""
+    f = dtype
+    ph, pw = out_size
+    x1, y1, x2, y2 = (f(f(roi[i]) * f(spatial_scale)) for i in range(1, 5))
+    rw, rh = f(max(f(x2 - x1), f(1))), f(max(f(y2 - y1), f(1)))
+    bh, bw = f(rh / f(ph)), f(rw / f(pw))
+    gh = sampling_ratio if sampling_ratio > 0 else int(np.ceil(rh / ph))
+    gw = sampling_ratio if sampling_ratio > 0 else int(np.ceil(rw / pw))
+    ys = np.array([[f(y1 + f(i) * bh + f(f(iy) + f(0.5)) * bh / f(gh)) for iy in range(gh)] for i in range(ph)], dtype)
+    xs = np.array([[f(x1 + f(j) * bw + f(f(ix) + f(0.5)) * bw / f(gw)) for ix in range(gw)] for j in range(pw)], dtype)
+    return ys, xs, gh * gw
+
+
+def bilinear_weights64(y, x, height, width):
+    """oracle.ops._bilinear_weights in float64 arithmetic."""
+    if y < -1.0 or y > height or x < -1.0 or x > width:
+        return False, None, None
+    y, x = max(float(y), 0.0), max(float(x), 0.0)
+    y_low, x_low = int(y), int(x)
+    if y_low >= height - 1:
+        y_high = y_low = height - 1
+        y = float(y_low)
+    else:
+        y_high = y_low + 1
+    if x_low >= width - 1:
+        x_high = x_low = width - 1
+        x = float(x_low)
+    else:
+        x_high = x_low + 1
+    ly, lx = y - y_low, x - x_low
+    hy, hx = 1.0 - ly, 1.0 - lx
+    return True, (y_low * width + x_low, y_low * width + x_high, y_high * width + x_low, y_high * width + x_high), \
+        (hy * hx, hy * lx, ly * hx, ly * lx)
+
+
+def roi_tap_counts(rois, out_size, spatial_scale, sampling_ratio, batch, height, width):
+    """Number of nonzero bilinear taps (sample x corner, over all RoIs and bins) that land on each pixel
+    [batch, height, width]: the number of terms the RoIAlign backward adds into each gradient element."""
+    from oracle.ops import _bilinear_weights
+    uniq, mult = np.unique(np.asarray(rois, np.float32), axis=0, return_counts=True)
+    cnt = np.zeros(batch * height * width)
+    for roi, k in zip(uniq, mult):
+        ys, xs, _ = roi_sample_grid(roi, out_size, spatial_scale, sampling_ratio, np.float32)
+        base = int(roi[0]) * height * width
+        for y in ys.ravel():
+            for x in xs.ravel():
+                ok, idx, w = _bilinear_weights(y, x, height, width)
+                if ok:
+                    for q in range(4):
+                        if w[q] != 0:
+                            cnt[base + idx[q]] += k
+    return cnt.reshape(batch, height, width)
+
+
+def adam_grads(rng, scales, zero_frac=0.05):
+    """One step's synthetic gradient: per-element magnitude `scales` times N(0,1), with exact zeros."""
+    g = scales * rng.standard_normal(scales.shape)
+    g[rng.random(scales.shape) < zero_frac] = 0.0
+    return g.astype(np.float32)

@@ -118,3 +118,12 @@ def test_reference_scripts_run_their_imports_through_shims():
     env = dict(os.environ, PYTHONPATH=os.path.join(ROOT, "shims"))
     out = subprocess.check_output(["python", "-c", code], text=True, cwd="/tmp", env=env, timeout=300)
     assert out.strip().endswith("ok")
+
+
+def test_adam_step_takes_lr_and_betas_in_double():
+    """rr_adam_step forms 1 - beta and the bias corrections 1 - beta^step in double: lr and the betas cross the ABI as
+    doubles (a float 0.999 is 1.3e-8 above 0.999)."""
+    from ctypes import c_double, c_float, c_int, c_long, c_void_p
+    from rrnet_amd import _C
+    _, args = _C.header_signatures()["rr_adam_step"]
+    assert args == [c_void_p] * 4 + [c_long, c_double, c_double, c_double, c_float, c_int, c_float, c_void_p]

@@ -254,3 +254,88 @@ def test_bench_dump_outputs_writes_float32_arrays_and_a_fixed_sample(tmp_path):
     assert np.all(np.diff(hm) > 0) and hm[0] >= 0 and hm[-1] < n_hm   # distinct positions, sorted, in logical order
     assert np.array_equal(np.load(str(tmp_path / "a" / "wh_1.npy")), whs[1].numpy())
     assert np.load(str(tmp_path / "a" / "wh_loss.npy")) == 2.0
+
+
+# ---- promises of the seeded generators behind the fp64 kernel checks (tests/helpers.py) ----------------------------
+def test_focal_inputs_keep_out_of_the_clamp_band():
+    """No logit within FOCAL_BAND of +-logit(1e-4), where fp32 and fp64 clamp masks may disagree; saturated logits,
+    exact peaks, exact zeros and nextafter(1, 0) are all present; the N_pos == 0 variant has no peak."""
+    import numpy as np
+    from helpers import FOCAL_BAND, FOCAL_CLAMP_LOGIT, focal_inputs
+    assert abs(FOCAL_CLAMP_LOGIT + 9.21024) < 1e-5
+    for shape, pos in [((1, 1, 1, 1), True), ((3, 7, 37, 41), True), ((2, 10, 128, 128), True),
+                       ((8, 10, 256, 256), True), ((8, 10, 256, 256), False)]:
+        x, gt = focal_inputs(shape, seed=sum(shape) + 7 * pos, with_pos=pos)
+        assert x.shape == gt.shape == shape and x.dtype == gt.dtype == np.float32
+        d = np.abs(np.abs(x.astype(np.float64)) - abs(FOCAL_CLAMP_LOGIT))
+        assert d.min() >= FOCAL_BAND, (shape, d.min())
+        assert (gt == 1).any() == pos
+        if x.size > 1000:
+            for v in (-100, -30, 30, 100):
+                assert (x == v).any()
+            assert (gt == 0).any() and (gt == np.nextafter(np.float32(1), np.float32(0))).any()
+            assert ((gt > 0) & (gt < 0.99)).any()
+
+
+def test_regl1_inputs_hold_the_edge_cases():
+    import numpy as np
+    from helpers import regl1_inputs
+    pred, mask, ind, target = regl1_inputs(8, 64, 64, seed=31, slots=64)
+    hw = 64 * 64
+    assert mask.shape == ind.shape == (8, 64, 1) and target.shape == (8, 64, 2)
+    for b in range(8):
+        valid = ind[b, mask[b, :, 0] == 1, 0]
+        _, cnt = np.unique(valid, return_counts=True)
+        assert cnt.max() == 3 and (cnt == 2).any()
+        masked = ind[b, mask[b, :, 0] == 0, 0]
+        assert (masked == hw - 1).any() and np.isin(masked[masked != 0], valid).sum() >= 2
+        flat = pred[b].reshape(2, hw)
+        same = [(flat[:, int(ind[b, s, 0])] == target[b, s]).any() for s in range(64) if mask[b, s, 0] == 1]
+        assert sum(same) >= 3
+    assert regl1_inputs(8, 16, 24, seed=31, slots=0)[1].shape == (8, 0, 1)
+
+
+def test_stage2_inputs_keep_out_of_the_iou_band():
+    """No fp64 IoU within STAGE2_IOU_BAND of 0.5, no near-tie between differing gt boxes for a positive RoI, images
+    interleaved, one image without a positive and one with only positives, zero and duplicated gt rows present."""
+    import numpy as np
+    from helpers import STAGE2_IOU_BAND, stage2_best_iou, stage2_inputs, stage2_iou_margins
+    for scale in (4.0, 1.0):
+        rois, reg, gt = stage2_inputs(seed=int(scale) + 40, scale=scale)
+        assert rois.shape == (2400, 5) and reg.shape == (2400, 4) and gt.shape == (8, 100, 8)
+        d05, gap = stage2_iou_margins(rois, gt, scale)
+        best = np.array([stage2_best_iou(r, gt, scale) for r in rois])
+        assert d05.min() > STAGE2_IOU_BAND
+        assert gap[best > 0.5].min() > STAGE2_IOU_BAND
+        img = rois[:, 0].astype(int)
+        assert (np.diff(img) != 0).mean() > 0.5                         # interleaved
+        npos = np.array([(best[img == b] > 0.5).sum() for b in range(8)])
+        assert npos[3] == 0 and npos[5] == 300 and (npos > 0).sum() == 7
+        assert np.all(rois[:, 3] > rois[:, 1]) and np.all(rois[:, 4] > rois[:, 2])
+        for b in range(8):
+            assert np.all(gt[b, -5:] == 0) and np.array_equal(gt[b, 0], gt[b, 1]) and np.array_equal(gt[b, 5], gt[b, 7])
+
+
+def test_dyadic_roi_set_is_exact_in_fp32():
+    """Every sample position of the dyadic RoIAlign set, evaluated as oracle.ops.roi_align does in fp32, equals its
+    fp64 evaluation, and so do the bilinear weights of oracle.ops._bilinear_weights and weight / count."""
+    import numpy as np
+    from helpers import ROI_DYADIC_CASES, ROI_DYADIC_MAP, bilinear_weights64, roi_dyadic_case, roi_sample_grid
+    from oracle.ops import _bilinear_weights
+    _, H, W = ROI_DYADIC_MAP
+    for size, sr, scale, ch in ROI_DYADIC_CASES:
+        rois = np.unique(roi_dyadic_case(size, sr, scale, ch), axis=0)
+        for roi in rois:
+            y32, x32, cnt = roi_sample_grid(roi, size, scale, sr, np.float32)
+            y64, x64, cnt64 = roi_sample_grid(roi, size, scale, sr, np.float64)
+            assert cnt == cnt64 and cnt & (cnt - 1) == 0
+            assert np.array_equal(y32.astype(np.float64), y64) and np.array_equal(x32.astype(np.float64), x64)
+            for y in y32.ravel()[::3]:
+                for x in x32.ravel()[::3]:
+                    ok, idx, w = _bilinear_weights(y, x, H, W)
+                    ok64, idx64, w64 = bilinear_weights64(float(y), float(x), H, W)
+                    assert ok == ok64
+                    if ok:
+                        assert idx == idx64
+                        assert [float(v) for v in w] == list(w64)
+                        assert [float(np.float32(v / np.float32(cnt))) for v in w] == [v / cnt for v in w64]
