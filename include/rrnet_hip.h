@@ -484,6 +484,28 @@ int rr_ctnet_targets(const float *annos, const int *counts, int b, int m, int an
                      int scale_factor, int num_classes, float *hm, float *wh, float *ind, float *offset,
                      float *reg_mask, hipStream_t stream);
 
+/* ---- training input: device-side augmentation ------------------------------------------------- *
+ * rr_augment_frames: the pixel half of the training chain of configs/rrnet_config.py:40-49 without FillDuck, one gather
+ *   per output pixel: MultiScale (datasets/transforms/functional.py:72-82, PIL `Image.resize(..., BILINEAR)` for scale
+ *   factors >= 1), ToTensor (:32-38), MaskIgnore (:290-313), HorizontalFlip (:13-19), RandomCrop's padding and crop
+ *   (datasets/transforms/transforms.py:60-72, functional.py:104-111) and Normalize (functional.py:135-143).  Bit-exact
+ *   with that chain on the host.
+ *   src [src_bytes] uint8: one HWC RGB source WINDOW per image, back to back (only the rows and columns a crop reads).
+ *   params [b, RR_AUGMENT_PARAMS] int32 per image: source height, width; window origin y, x; window height, width;
+ *     scaled height, width = int(h*s), int(w*s); flip flag; crop origin y, x in the scaled, flipped, padded frame; byte
+ *     offset of the window in src (low, high word); first row of the vertical and of the horizontal tap table in taps;
+ *     one reserved word.
+ *   rects [*,4] int32 = y0, y1, x0, x1: ignore rectangles in scaled, pre-flip coordinates (half open);
+ *     rect_off [b+1] int32: image i owns rows [rect_off[i], rect_off[i+1]).  rects may be NULL when there is none.
+ *   taps [ntaps,3] int32 = first tap, k0, k1 per output coordinate: PIL's fixed-point coefficients (22 bits) of one
+ *     resize pass, source coordinates in the FULL frame.
+ *   mean, stdv [3] float.  out [b,out_h,out_w,3] float NHWC, 16-byte aligned.  Pixels right of / below the scaled
+ *   frame are padding: (0 - mean) / std. */
+#define RR_AUGMENT_PARAMS 16
+int rr_augment_frames(const unsigned char *src, long src_bytes, const int *params, const int *rects,
+                      const int *rect_off, const int *taps, int ntaps, const float *mean, const float *stdv,
+                      float *out, int b, int out_h, int out_w, hipStream_t stream);
+
 /* ---- inference post-process (config 5: decode -> re-regression -> Soft-NMS) ------------------ *
  * rr_refine_boxes: operators/rrnet_operator.py:188-209 `generate_bbox` (stage-2 boxes from the packed RoIs
  *   [r,5] = image,x1,y1,x2,y2 in feature coordinates, the regression [r,4], scores, classes), the score filter

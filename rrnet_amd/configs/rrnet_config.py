@@ -1,10 +1,12 @@
 """`Config` for RRNet with the keys and values of the reference's configs/rrnet_config.py:7-91, declared as one
-nested table.  The augmentation transforms of the reference's training pipeline (MultiScale, MaskIgnore, FillDuck,
-HorizontalFlip, RandomCrop) belong to the out-of-scope data layer; the pipelines here keep the two transforms that
-define the tensor contract of the hot path (Normalize, ToHeatmap)."""
+nested table.  `Train.transforms` is the reference's chain (configs/rrnet_config.py:40-49) without FillDuck, which needs
+road maps and cv2 and stays out of scope; `Val.transforms` is ToTensor -> Normalize.  The real-data loader reads the
+chain's parameters from these instances and lowers the pixel work to rr_augment_frames (rrnet_amd/datasets/augment.py);
+the crop size is the one given to RandomCrop, as in the reference."""
 from torch.utils.data import DistributedSampler
 
-from rrnet_amd.datasets.transforms import Compose, Normalize, ToHeatmap
+from rrnet_amd.datasets.transforms import (Compose, HorizontalFlip, MaskIgnore, MultiScale, Normalize, RandomCrop,
+                                            ToHeatmap, ToTensor)
 from rrnet_amd.utils.attrdict import AttrDict
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
@@ -26,13 +28,15 @@ Config = _tree({
         # Adam: only lr is used by the operator (momentum / weight_decay are carried but ignored, as in the reference)
         "lr": 2.5e-4, "momentum": 0.9, "weight_decay": 0.0001, "lr_milestones": [60000, 80000], "iter_num": 100000,
         "crop_size": (512, 512), "mean": IMAGENET_MEAN, "std": IMAGENET_STD, "scale_factor": STRIDE, "with_road": True,
-        "transforms": Compose([Normalize(IMAGENET_MEAN, IMAGENET_STD), ToHeatmap(scale_factor=STRIDE)]),
+        "transforms": Compose([MultiScale(scale=(1, 1.15, 1.25, 1.35, 1.5)), ToTensor(), MaskIgnore(IMAGENET_MEAN),
+                               HorizontalFlip(), RandomCrop((512, 512)), Normalize(IMAGENET_MEAN, IMAGENET_STD),
+                               ToHeatmap(scale_factor=STRIDE)]),
         "print_interval": 20, "checkpoint_interval": 5000,
     },
     "Val": {
         "model_path": './log/%s/ckp-89999.pth' % LOG_PREFIX, "is_eval": True, "auto_test": True, "batch_size": 1,
         "num_workers": 4, "sampler": DistributedSampler, "mean": IMAGENET_MEAN, "std": IMAGENET_STD,
-        "scales": [1, 1.1, 1.2, 1.3, 1.4, 1.5], "transforms": Compose([Normalize(IMAGENET_MEAN, IMAGENET_STD)]),
+        "scales": [1, 1.1, 1.2, 1.3, 1.4, 1.5], "transforms": Compose([ToTensor(), Normalize(IMAGENET_MEAN, IMAGENET_STD)]),
         "result_dir": './results/',
     },
     "Model": {"backbone": 'hourglass', "num_stacks": 2,

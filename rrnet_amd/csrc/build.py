@@ -22,6 +22,7 @@ PER_FILE = {
     "refine.hip": ["-ffp-contract=off"],
     "targets.hip": ["-ffp-contract=off"],
     "psroi.hip": ["-ffp-contract=off"],
+    "augment.hip": ["-ffp-contract=off"],
 }
 
 

@@ -1,4 +1,12 @@
-"""Data contract of the hot path.  The reference's dataset / augmentation code (datasets/, 875 LoC) is out of
-scope; what the losses consume — the target tensors of the CenterNet collate contract — is produced on
-the device by rr_ctnet_targets and used by the synthetic VisDrone-shaped generator in synthetic.py."""
+"""Data layer of the hot path.  Two sources feed the same `get_batch()` surface:
+  * real VisDrone-DET frames (drones_det.py, augment.py): the host decodes the JPEG and decides scale, flip and crop;
+    everything that touches pixels runs on the device in rr_augment_frames, the targets in rr_ctnet_targets.  The host
+    restatement of the reference's transforms (transforms/) is the CPU path and the checker of the kernel;
+  * the synthetic VisDrone-shaped generator (synthetic.py), which make_dataloader returns when `cfg.data_root` holds no
+    dataset.
+Out of scope: FillDuck (road maps, cv2) and ColorJitter (in neither model's config)."""
+from .augment import DeviceAugmentLoader, DeviceValLoader, HostAugmentLoader  # noqa: F401
+from .drones_det import DronesDET  # noqa: F401
 from .synthetic import SyntheticDronesDET, make_dataloader  # noqa: F401
+
+datasets = {'drones_det': DronesDET}

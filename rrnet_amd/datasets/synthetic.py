@@ -1,4 +1,4 @@
-"""Synthetic VisDrone-DET-shaped batches (there is no dataset in either repository).
+"""Synthetic VisDrone-DET-shaped batches (neither repository ships a dataset; real frames: augment.py).
 
 Recipe of SURVEY §8(d): seed 219 + rank; uint8-uniform frames normalised with the ImageNet
 mean/std of configs/rrnet_config.py:36-37; `boxes_per_image` annotations with log-uniform sizes in
@@ -154,10 +154,17 @@ _LOADERS = {}
 
 
 def make_dataloader(cfg, collate_fn='rrnet'):
-    """datasets/__init__.py make_dataloader surface: (training_loader, validation_loader).  Real
-    VisDrone loading / augmentation is out of scope; synthetic frames of the configured crop size.  The generated
+    """datasets/__init__.py make_dataloader surface: (training_loader, validation_loader).
+    Where `<cfg.data_root>/train/images` exists the loaders are the real ones (rrnet_amd.datasets.augment:
+    DeviceAugmentLoader over DronesDET, and DeviceValLoader when `<cfg.data_root>/val/images` exists too).
+    Otherwise: synthetic frames of the configured crop size and no validation loader.  The generated
     pool is cached per (batch, size, seed, rank): a second operator in the same process (bench.py's secondary
     workloads) reuses the resident batches."""
+    import os
+    data_root = getattr(cfg, "data_root", None)
+    if data_root and os.path.isdir(os.path.join(data_root, 'train', 'images')):
+        from .augment import make_real_dataloaders
+        return make_real_dataloaders(cfg, data_root)
     rank = getattr(cfg.Distributed, "rank", 0)
     h, w = cfg.Train.crop_size
     key = (cfg.Train.batch_size, h, w, cfg.seed, rank, cfg.Train.scale_factor, cfg.num_classes)

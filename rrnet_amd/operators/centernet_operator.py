@@ -174,7 +174,7 @@ class CenterNetOperator(BaseOperator):
         state_dict = torch.load(self.cfg.Val.model_path, map_location='cpu')
         self.model.module.load_state_dict(state_dict)
         if self.validation_loader is None:
-            raise RuntimeError("no validation data: the VisDrone loader is outside the accelerated path")
+            raise RuntimeError("no validation data: %s/val/images does not exist" % self.cfg.data_root)
         os.makedirs(self.cfg.Val.result_dir, exist_ok=True)
         with torch.no_grad():
             for data in self.validation_loader:

@@ -1382,6 +1382,31 @@ def ctnet_targets(annos, counts, img_h, img_w, scale_factor=4, num_classes=10):
     return hm, wh, ind, off, mask
 
 
+AUGMENT_PARAMS = 16        # RR_AUGMENT_PARAMS: int32 words of rr_augment_frames' per-image record
+
+
+def augment_frames(src, params, rects, rect_off, taps, mean, std, out_h, out_w):
+    """rr_augment_frames: packed uint8 source windows + per-image records -> the normalised network input, logical
+    [B,3,out_h,out_w] in NHWC memory.  src uint8 [bytes], params int32 [B,16], rects int32 [R,4] (None or empty: no
+    ignore region), rect_off int32 [B+1], taps int32 [T,3], mean / std float32 [3]; all on the device.  The records
+    are built (and checked against the window and table sizes) by rrnet_amd.datasets.augment.pack_batch."""
+    _C.require_cuda(src, params, rects, rect_off, taps, mean, std)
+    assert src.dtype == torch.uint8 and src.is_contiguous() and src.dim() == 1
+    assert params.dtype == torch.int32 and params.is_contiguous() and params.shape[1] == AUGMENT_PARAMS
+    assert rect_off.dtype == torch.int32 and rect_off.numel() == params.shape[0] + 1
+    assert taps.dtype == torch.int32 and taps.is_contiguous() and taps.shape[1] == 3
+    assert mean.dtype == torch.float32 and std.dtype == torch.float32 and mean.numel() == 3 and std.numel() == 3
+    if rects is not None and rects.numel() == 0:
+        rects = None
+    assert rects is None or (rects.dtype == torch.int32 and rects.is_contiguous() and rects.shape[1] == 4)
+    b = params.shape[0]
+    out = empty_nhwc(b, 3, out_h, out_w, src.device)
+    _C.check(_C.fn("rr_augment_frames")(_C.ptr(src), src.numel(), _C.ptr(params), _C.ptr(rects), _C.ptr(rect_off),
+                                        _C.ptr(taps), taps.shape[0], _C.ptr(mean), _C.ptr(std), _C.ptr(out), b, out_h,
+                                        out_w, _C.stream()), "rr_augment_frames")
+    return out
+
+
 def refine_boxes(rois, reg, scores, clses, seg_off, scale, score_thr):
     """generate_bbox + score filter + xywh->xyxy for every (frame, class) segment of the packed RoI list.
     -> boxes6 [R,6] (kept rows at the front of each segment's range), seg_len int32 [nseg]."""
