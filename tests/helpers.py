@@ -377,3 +377,54 @@ def adam_grads(rng, scales, zero_frac=0.05):
     g = scales * rng.standard_normal(scales.shape)
     g[rng.random(scales.shape) < zero_frac] = 0.0
     return g.astype(np.float32)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# SyncBN: training-mode BatchNorm over the CONCATENATION of per-rank shards, evaluated in float64 on the host
+# (tests/test_syncbn_gpu.py, tests/test_dp_gpu.py; tests/test_host_logic.py holds it against torch's own batch_norm).
+# ------------------------------------------------------------------------------------------------------------------
+def _chan64(t):
+    return torch.as_tensor(t).detach().cpu().double().view(1, -1, 1, 1)
+
+
+def syncbn_ref64(ys, gamma, beta, eps, momentum=0.1, running_mean=None, running_var=None, dzs=None, masks=None):
+    """ys: per-rank pre-BN tensors [n_i,C,H_i,W_i] (any float dtype, read as float64); gamma / beta [C].
+    -> dict of float64 tensors:
+      count (float: samples per channel over all shards), local_sums[i] = [sum y | sum y^2] of shard i ([2C]: what a rank
+      puts into the exchange buffer in front of its count), sums (their total), mean, var (biased), invstd, scale
+      (gamma * invstd), shift (beta - mean * scale), out[i] = y_i * scale + shift, and — given running_mean /
+      running_var — their momentum update with the unbiased variance var * count / (count - 1).
+    With dzs (per-rank gradients w.r.t. out[i]; masks[i], if given, multiplies dz_i: the ReLU mask):
+      d[i] (the masked gradient), local_bwd[i] = [sum d | sum d * xhat] of shard i ([2C]: dbeta and dgamma a rank
+      accumulates BEFORE the exchange), bwd_sums (their total = the full-batch dbeta | dgamma), and
+      dx[i] = gamma * invstd * (d_i - sum d / count - xhat_i * sum(d * xhat) / count)."""
+    ys = [torch.as_tensor(y).detach().cpu().double() for y in ys]
+    c = ys[0].shape[1]
+    g64, b64 = _chan64(gamma), _chan64(beta)
+    count = float(sum(y.numel() // c for y in ys))
+    local = [torch.cat([y.sum((0, 2, 3)), (y * y).sum((0, 2, 3))]) for y in ys]
+    sums = torch.stack(local).sum(0)
+    mean = sums[:c] / count
+    var = (sums[c:] / count - mean * mean).clamp(min=0.0)
+    # (the two-pass variance: the one-pass form above is what the kernels evaluate, in float64 both agree to ~1e-16 |y|^2)
+    var2 = sum(((y - mean.view(1, -1, 1, 1)) ** 2).sum((0, 2, 3)) for y in ys) / count
+    invstd = 1.0 / torch.sqrt(var2 + eps)
+    scale = g64.view(-1) * invstd
+    shift = b64.view(-1) - mean * scale
+    r = dict(count=count, local_sums=local, sums=sums, mean=mean, var=var2, var_one_pass=var, invstd=invstd, scale=scale,
+             shift=shift, out=[y * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1) for y in ys])
+    if running_mean is not None:
+        unbiased = var2 * count / (count - 1.0) if count > 1 else var2
+        r["running_mean"] = (1.0 - momentum) * torch.as_tensor(running_mean).detach().cpu().double() + momentum * mean
+        r["running_var"] = (1.0 - momentum) * torch.as_tensor(running_var).detach().cpu().double() + momentum * unbiased
+    if dzs is not None:
+        ds = [torch.as_tensor(dz).detach().cpu().double() for dz in dzs]
+        if masks is not None:
+            ds = [d * torch.as_tensor(m).detach().cpu().double() for d, m in zip(ds, masks)]
+        xh = [(y - mean.view(1, -1, 1, 1)) * invstd.view(1, -1, 1, 1) for y in ys]
+        lb = [torch.cat([d.sum((0, 2, 3)), (d * x).sum((0, 2, 3))]) for d, x in zip(ds, xh)]
+        bs = torch.stack(lb).sum(0)
+        sdy, sdx = (bs[:c] / count).view(1, -1, 1, 1), (bs[c:] / count).view(1, -1, 1, 1)
+        a = scale.view(1, -1, 1, 1)
+        r.update(d=ds, xhat=xh, local_bwd=lb, bwd_sums=bs, dx=[a * (d - sdy - x * sdx) for d, x in zip(ds, xh)])
+    return r

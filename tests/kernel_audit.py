@@ -140,8 +140,8 @@ def audit(tol=2e-5, tol_wgrad=2e-4, sample=False, ref_device="cpu"):
     rec = Record()
     rec.sampled = set()
     names = ("conv_fprop", "conv_dgrad", "conv_wgrad", "stem_wgrad_s2d", "conv_fprop_packed", "conv_wgrad_packed", "bn_apply", "bn_bwd_reduce", "bn_bwd_apply",
-             "sum_n", "upsample_add_fwd", "upsample_add_bwd", "bias_relu_bwd", "relu_fwd", "bn_finalize",
-             "bn_stats_finalize", "dcn_fwd", "dcn_dgrad", "dcn_wgrad")
+             "sum_n", "upsample_add_fwd", "upsample_add_bwd", "bias_relu_bwd", "relu_fwd", "bn_finalize", "bn_finalize_sync",
+             "bn_affine_grad", "bn_stats_finalize", "dcn_fwd", "dcn_dgrad", "dcn_wgrad")
     orig = {n: getattr(ops, n) for n in names}
 
     def big(flops):
@@ -427,14 +427,17 @@ def audit(tol=2e-5, tol_wgrad=2e-4, sample=False, ref_device="cpu"):
 
     def bn_bwd_apply(dz, z, y, mean, invstd, gamma, sums, count, want_g=False, dgamma=None, dbeta=None, count_dev=None,
                      mask_scale=None, mask_shift=None, g_into=None, bf16_only=False):
+        # (SyncBN: the kernel divides by the exchanged count in device memory, whatever the host argument says)
         sig = (tuple(y.shape), z is not None, mask_scale is not None, want_g, g_into is not None, bool(bf16_only), ops.is_phantom(z),
-               ops.is_phantom(y))
-        todo = ("bn_bwd_apply",) + sig not in rec.seen and count_dev is None
+               ops.is_phantom(y)) + (("count-dev",) if count_dev is not None else ())
+        todo = ("bn_bwd_apply",) + sig not in rec.seen
         gbase = g_into.clone() if (g_into is not None and todo) else None
         out = orig["bn_bwd_apply"](dz, z, y, mean, invstd, gamma, sums, count, want_g, dgamma, dbeta, count_dev,
                                    mask_scale, mask_shift, g_into, bf16_only)
         z, y = _dat(z), _dat(y)
         if todo:
+            if count_dev is not None:
+                count = float(count_dev)          # one device read per new signature
             ns = _img_sample(y.shape[0]) if big_elems(y) else list(range(y.shape[0]))
             if big_elems(y):
                 rec.sampled.add(("bn_bwd_apply",) + sig)
@@ -548,18 +551,49 @@ def audit(tol=2e-5, tol_wgrad=2e-4, sample=False, ref_device="cpu"):
     def bn_finalize(sums, count, gamma, beta, running_mean, running_var, momentum, eps, count_dev=None,
                     num_batches_tracked=None):
         sig = (gamma.numel(), float(count), count_dev is not None)
-        check = ("bn_finalize",) + sig not in rec.seen and count_dev is None
+        check = ("bn_finalize",) + sig not in rec.seen
         if check:
             rm0, rv0, nb0 = _c64(running_mean), _c64(running_var), None if num_batches_tracked is None else int(num_batches_tracked)
         got = orig["bn_finalize"](sums, count, gamma, beta, running_mean, running_var, momentum, eps, count_dev,
                                   num_batches_tracked)
         if check:
+            if count_dev is not None:
+                count = float(count_dev[0])       # the exchanged count: one device read per new signature
             ref = _finalize_ref(sums.detach().to(REF["dev"]).double(), count, gamma, beta, rm0, rv0, momentum, eps)
             e = _finalize_err(got, ref, running_mean, running_var)
             if nb0 is not None and int(num_batches_tracked) != nb0 + 1:
                 e = float("inf")
             rec.note("bn_finalize", sig, e, 1e-5)        # fp32 outputs of fp64 arithmetic: a few ulp
         return got
+
+    def bn_finalize_sync(sums, count_slot, gamma, beta, running_mean, running_var, momentum, eps, num_batches_tracked=None):
+        """SyncBN: the finalize that reads the exchanged count from the buffer and hands it back in storage of its own."""
+        sig = (gamma.numel(),)
+        check = ("bn_finalize_sync",) + sig not in rec.seen
+        if check:
+            rm0, rv0, nb0 = _c64(running_mean), _c64(running_var), None if num_batches_tracked is None else int(num_batches_tracked)
+        got = orig["bn_finalize_sync"](sums, count_slot, gamma, beta, running_mean, running_var, momentum, eps, num_batches_tracked)
+        if check:
+            count = float(count_slot[0])          # one device read per new signature
+            ref = _finalize_ref(sums.detach().to(REF["dev"]).double(), count, gamma, beta, rm0, rv0, momentum, eps)
+            e = _finalize_err(got[:4], ref, running_mean, running_var)
+            if float(got[4]) != count or (nb0 is not None and int(num_batches_tracked) != nb0 + 1):
+                e = float("inf")
+            rec.note("bn_finalize_sync", sig, e, 1e-5)   # fp32 outputs of fp64 arithmetic: a few ulp
+        return got
+
+    def bn_affine_grad(sums, dgamma, dbeta):
+        """SyncBN: dbeta += sums[:c], dgamma += sums[c:2c] from the LOCAL backward sums."""
+        c = dgamma.numel()
+        sig = (c,)
+        check = ("bn_affine_grad",) + sig not in rec.seen
+        if check:
+            g0, b0 = _c64(dgamma), _c64(dbeta)
+        out = orig["bn_affine_grad"](sums, dgamma, dbeta)
+        if check:
+            s64 = sums.detach().to(REF["dev"]).double()
+            rec.note("bn_affine_grad", sig, max(_rel(dbeta, b0 + s64[:c]), _rel(dgamma, g0 + s64[c:2 * c])), tol)
+        return out
 
     def bn_stats_finalize(slab, count, gamma, beta, running_mean, running_var, momentum, eps, num_batches_tracked=None):
         c = gamma.numel()
@@ -754,7 +788,8 @@ def audit(tol=2e-5, tol_wgrad=2e-4, sample=False, ref_device="cpu"):
 
     patched = dict(conv_fprop=conv_fprop, conv_dgrad=conv_dgrad, conv_wgrad=conv_wgrad, stem_wgrad_s2d=stem_wgrad_s2d,
                    conv_fprop_packed=conv_fprop_packed, conv_wgrad_packed=conv_wgrad_packed,
-                   bn_finalize=bn_finalize, bn_stats_finalize=bn_stats_finalize, bn_apply=bn_apply,
+                   bn_finalize=bn_finalize, bn_finalize_sync=bn_finalize_sync, bn_affine_grad=bn_affine_grad,
+                   bn_stats_finalize=bn_stats_finalize, bn_apply=bn_apply,
                    bn_bwd_reduce=bn_bwd_reduce, bn_bwd_apply=bn_bwd_apply, sum_n=sum_n, upsample_add_fwd=upsample_add_fwd,
                    upsample_add_bwd=upsample_add_bwd, bias_relu_bwd=bias_relu_bwd, relu_fwd=relu_fwd,
                    dcn_fwd=dcn_fwd, dcn_dgrad=dcn_dgrad, dcn_wgrad=dcn_wgrad)

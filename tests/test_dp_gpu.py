@@ -182,6 +182,203 @@ def test_two_rank_collective_sequences_are_identical(tmp_path):
     assert t[0]["wsum"] == t[1]["wsum"] and t[0]["whash"] == t[1]["whash"]
 
 
+# ---- SyncBN nodes on RAGGED shards against the fp64 oracle ------------------------------------------------------------
+SYNC_SHARDS = {"cbr_res": (1, 3), "cbr": (1, 3), "block": (1, 3), "head": (37, 5)}      # rows of rank 0, rank 1
+SYNC_SHAPES = {"cbr_res": (64, 16, 16), "cbr": (64, 16, 16), "block": (32, 16, 16), "head": (256, 3, 3)}
+SYNC_PROJ = {"cbr_res": (64, 16, 16), "cbr": (64, 16, 16), "block": (64, 8, 8), "head": (4,)}
+
+
+def _sync_modules():
+    """conv -> SyncBN -> ReLU with a residual (mask from z) and without (mask recomputed), a stride-2 channel-changing
+    residual block (conv1 and the projection share the joint node) and the stage-2 head; seeded weights, running
+    statistics away from (0, 1)."""
+    import torch.nn as nn
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from helpers import det_fill
+    from rrnet_amd.backbones.hourglass import ResidualBlock
+    from rrnet_amd.detectors.fasterrcnn_detector import FasterRCNNDetector
+
+    class Cases(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.conv_a, self.bn_a = nn.Conv2d(64, 64, 3, padding=1, bias=False), nn.BatchNorm2d(64)
+            self.conv_b, self.bn_b = nn.Conv2d(64, 64, 3, padding=1, bias=False), nn.BatchNorm2d(64)
+            self.block = ResidualBlock(32, 64, stride=2)
+            self.head = FasterRCNNDetector()
+
+    m = Cases()
+    sd = det_fill({k: tuple(v.shape) for k, v in m.state_dict().items()}, 33)
+    for k in sd:
+        if k.endswith("running_mean"):
+            sd[k] = torch.linspace(-1.0, 1.0, sd[k].numel())
+        elif k.endswith("running_var"):
+            sd[k] = torch.linspace(0.5, 2.0, sd[k].numel())
+    m.load_state_dict(sd)
+    return m, sd
+
+
+def _sync_data():
+    """Full-batch inputs, the residual of the first case and the fixed cotangents `proj` (loss = sum(out * proj): linear in
+    the output, so the parameter gradients of the ranks add up to the full-batch gradient)."""
+    rng = np.random.default_rng(77)
+    d = {}
+    for name, (r0, r1) in SYNC_SHARDS.items():
+        n = r0 + r1
+        d["x/" + name] = torch.from_numpy(rng.normal(0.2, 1.0, (n,) + SYNC_SHAPES[name]).astype(np.float32))
+        d["proj/" + name] = torch.from_numpy(rng.normal(0.0, 1.0, (n,) + SYNC_PROJ[name]).astype(np.float32))
+    d["res/cbr_res"] = torch.from_numpy(rng.normal(0.0, 1.0, (4,) + SYNC_SHAPES["cbr_res"]).astype(np.float32))
+    return d
+
+
+def _sync_oracle(sd, data, dtype):
+    """oracle/model.py in train mode on the CONCATENATED batch, on the host -> {name: float64 array}."""
+    import torch.nn.functional as F
+    from oracle import model as om
+    stat = ("running_mean", "running_var", "num_batches_tracked")
+    P = om.Params({k: (v.clone() if k.endswith(stat[2]) else v.to(dtype).clone().requires_grad_(not k.endswith(stat)))
+                   for k, v in sd.items()}, training=True)
+    x = {k: v.to(dtype).clone().requires_grad_() for k, v in data.items() if not k.startswith("proj/")}
+    out = {"cbr_res": F.relu(om.bn(P, "bn_a", om.conv(P, "conv_a", x["x/cbr_res"], 1, 1)) + x["res/cbr_res"]),
+           "cbr": F.relu(om.bn(P, "bn_b", om.conv(P, "conv_b", x["x/cbr"], 1, 1))),
+           "block": om.residual_block(P, "block", x["x/block"], stride=2),
+           "head": om.stage2_head(P, x["x/head"], p="head")}
+    sum((out[k] * data["proj/" + k].to(dtype)).sum() for k in out).backward()
+    r = {"out/" + k: v for k, v in out.items()}
+    r.update({"d" + k: v.grad for k, v in x.items()})
+    for k, v in P.sd.items():
+        r[("buf/" if k.endswith(stat) else "grad/") + k] = v if k.endswith(stat) else v.grad
+    return {k: v.detach().double().numpy() for k, v in r.items()}
+
+
+def _sync_worker(rank, world, port, outdir):
+    import datetime
+    import json
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    torch.cuda.set_device(0)
+    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=90))
+    try:
+        model, _ = _sync_modules()
+        from kernel_audit import audit
+        from rrnet_amd import dptrace, functional as RF
+        from rrnet_amd.flat import FlatParams
+        CL = torch.channels_last
+        model = torch.nn.SyncBatchNorm.convert_sync_batchnorm(model.cuda().to(memory_format=CL)).train()
+        fp = FlatParams(model)
+        fp.broadcast(0)
+        fp.zero_grad()
+        data = _sync_data()
+        dptrace.ENABLED = True
+        dptrace.reset()
+        res = {}
+
+        def rows(key, name):
+            r0 = SYNC_SHARDS[name][0]
+            t = data[key][:r0] if rank == 0 else data[key][r0:]
+            return t.cuda().contiguous(memory_format=CL) if t.dim() == 4 else t.cuda()
+
+        with audit() as rec:
+            for name in SYNC_SHARDS:
+                x = rows("x/" + name, name).requires_grad_()
+                extra = None
+                if name == "cbr_res":
+                    extra = rows("res/cbr_res", name).requires_grad_()
+                    out = RF.conv_bn_act(x, model.conv_a, model.bn_a, relu=True, residual=extra)
+                elif name == "cbr":
+                    out = RF.conv_bn_act(x, model.conv_b, model.bn_b, relu=True)
+                elif name == "block":
+                    out = model.block(x)
+                else:
+                    out = model.head(x)
+                (out * rows("proj/" + name, name)).sum().backward()
+                res["out/" + name] = out
+                res["dx/" + name] = x.grad
+                if extra is not None:
+                    res["dres/" + name] = extra.grad
+        fp.all_reduce_grads()                      # fp.grad now holds the SUM over ranks
+        torch.cuda.synchronize()
+        for k, p in model.named_parameters():
+            res["grad/" + k] = p._rr_grad
+        for k, b in model.named_buffers():
+            res["buf/" + k] = b
+        np.savez(os.path.join(outdir, "sync%d.npz" % rank), **{k: v.detach().double().cpu().contiguous().numpy() for k, v in res.items()})
+        with open(os.path.join(outdir, "sync%d.json" % rank), "w") as f:
+            json.dump({"bad": [[repr(k), e] for k, e in rec.bad], "seen": [[repr(k), e] for k, e in rec.seen.items()],
+                       "notes": [e[3] for e in dptrace.EVENTS if e[0] == "default"]}, f)
+    finally:
+        dist.destroy_process_group()
+
+
+def test_two_rank_syncbn_nodes_on_ragged_shards_match_the_fp64_oracle(tmp_path):
+    """Two real ranks (gloo, one GPU), fp32 kernels, DIFFERENT numbers of rows per rank: functional._ConvBnAct under SyncBN
+    (ReLU mask from the saved output / recomputed), functional._ConvBnSyncMulti (a stride-2 projection block: two layers,
+    two sample counts in one exchange) and the stage-2 head on 37 + 5 RoIs, against oracle/model.py in float64 on the
+    concatenated batch.  Per case: each rank's output rows and input gradient, the rank-summed dw / dgamma / dbeta (the
+    loss is linear in the output), running_mean / running_var / num_batches_tracked — against float64 and equal on both
+    ranks.  Bound: 4x the error of the oracle's own float32 evaluation on the host (floor 2 u max|ref|), printed per
+    quantity.  The workers run under the kernel audit, which must have seen (and passed) the device-count calls.
+    Both workers end under time limits: the process group's collectives, and a deadline on the join."""
+    import json
+    import time
+    from helpers import U32
+    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
+    t0 = time.time()
+    ctx = mp.spawn(_sync_worker, nprocs=2, args=(2, port, str(tmp_path)), join=False)
+    deadline = t0 + 240.0
+    try:
+        while not ctx.join(timeout=5.0):
+            if time.time() > deadline:
+                raise AssertionError("the two ranks did not finish within 240 s")
+    finally:
+        for p in ctx.processes:
+            if p.is_alive():
+                p.terminate()
+        for p in ctx.processes:
+            p.join(10.0)
+    print("two ragged ranks, four cases under the kernel audit: %.1f s" % (time.time() - t0))
+    _, sd = _sync_modules()
+    data = _sync_data()
+    ref, r32 = _sync_oracle(sd, data, torch.float64), _sync_oracle(sd, data, torch.float32)
+    got = [np.load(str(tmp_path / ("sync%d.npz" % r))) for r in range(2)]
+    meta = [json.load(open(str(tmp_path / ("sync%d.json" % r)))) for r in range(2)]
+    worst = []
+
+    def check(key, g, rf, r3):
+        tol = max(4.0 * float(np.abs(r3 - rf).max()), 2.0 * U32 * float(np.abs(rf).max()))
+        err = float(np.abs(g - rf).max())
+        print("%-46s |HIP - fp64| %.3e   bound %.3e (fp32 host %.3e, max|ref| %.3e)" % (key, err, tol, float(np.abs(r3 - rf).max()), float(np.abs(rf).max())))
+        if not err <= tol:
+            worst.append((key, err, tol))
+
+    for key in sorted(ref):
+        kind, name = key.split("/", 1)
+        if kind in ("out", "dx", "dres"):
+            r0 = SYNC_SHARDS[name][0]
+            for r in range(2):
+                sl = slice(0, r0) if r == 0 else slice(r0, None)
+                assert got[r][key].shape == ref[key][sl].shape, (key, r)
+                check("%s rank %d" % (key, r), got[r][key], ref[key][sl], r32[key][sl])
+        elif kind == "grad":
+            assert np.array_equal(got[0][key], got[1][key]), key          # both ranks hold the same sum
+            check(key + " (sum over ranks)", got[0][key], ref[key], r32[key])
+        else:
+            assert np.array_equal(got[0][key], got[1][key]), key          # statistics identical on both ranks
+            if name.endswith("num_batches_tracked"):
+                assert int(got[0][key]) == int(ref[key]) == 1, key
+            else:
+                check(key, got[0][key], ref[key], r32[key])
+    for m in meta:
+        assert m["bad"] == [], m["bad"]
+        kinds = [k for k, _ in m["seen"]]
+        assert any(k.startswith("('bn_bwd_apply'") and "'count-dev'" in k for k in kinds), kinds
+        assert any(k.startswith("('bn_finalize_sync'") for k in kinds) and any(k.startswith("('bn_affine_grad'") for k in kinds)
+        # the projection block took the joint node: one exchange per direction for conv1 + skip
+        assert m["notes"].count("syncbn_fwd x2") == 1 and m["notes"].count("syncbn_bwd x2") == 1, m["notes"]
+    print("audited signatures with a device count: %s" % sorted(k for k, _ in meta[0]["seen"] if "count-dev" in k or "sync" in k or "affine" in k))
+    assert not worst, worst
+
+
 def _run_bench(extra_env, launcher, port):
     import json
     import subprocess

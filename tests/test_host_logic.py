@@ -339,3 +339,69 @@ def test_dyadic_roi_set_is_exact_in_fp32():
                         assert idx == idx64
                         assert [float(v) for v in w] == list(w64)
                         assert [float(np.float32(v / np.float32(cnt))) for v in w] == [v / cnt for v in w64]
+
+
+def _syncbn_shards(seed, shapes, c):
+    import numpy as np
+    import torch
+    rng = np.random.default_rng(seed)
+    ys = [torch.from_numpy(rng.normal(0.4, 1.3, (n, c, h, w))) for n, h, w in shapes]
+    dzs = [torch.from_numpy(rng.normal(0.0, 1.0, tuple(y.shape))) for y in ys]
+    masks = [torch.from_numpy((rng.random(tuple(y.shape)) < 0.6).astype(np.float64)) for y in ys]
+    gamma = torch.from_numpy(rng.normal(1.0, 0.3, c))
+    beta = torch.from_numpy(rng.normal(0.0, 0.5, c))
+    rm0 = torch.from_numpy(rng.normal(0.0, 1.0, c))
+    rv0 = torch.from_numpy(rng.uniform(0.5, 2.0, c))
+    return ys, dzs, masks, gamma, beta, rm0, rv0
+
+
+def test_syncbn_reference_equals_torch_batch_norm_on_the_concatenated_shards():
+    """helpers.syncbn_ref64 (the float64 reference of tests/test_syncbn_gpu.py) against torch.nn.functional.batch_norm in
+    double + autograd on the concatenation of ragged shards: outputs, dx, dgamma, dbeta and the running statistics, with
+    and without a mask on the incoming gradient, at momentum 0.1 and 0.37, down to a global count of 2.  Both are float64
+    evaluations of the same formulas: they agree to 1e-12 of each quantity's scale."""
+    import torch
+    import torch.nn.functional as F
+    from helpers import syncbn_ref64
+    for seed, shapes, c, mom in ((0, [(5, 3, 3), (131, 3, 3)], 8, 0.1), (1, [(1, 4, 6), (2, 4, 6), (4, 4, 6)], 5, 0.37),
+                                 (2, [(1, 1, 1), (1, 1, 1)], 4, 0.1)):
+        ys, dzs, masks, gamma, beta, rm0, rv0 = _syncbn_shards(seed, shapes, c)
+        for use_mask in (False, True):
+            r = syncbn_ref64(ys, gamma, beta, 1e-5, mom, rm0, rv0, dzs, masks if use_mask else None)
+            x = torch.cat(ys).clone().requires_grad_()
+            g, b = gamma.clone().requires_grad_(), beta.clone().requires_grad_()
+            rm, rv = rm0.clone(), rv0.clone()
+            out = F.batch_norm(x, rm, rv, g, b, True, mom, 1e-5)
+            cot = torch.cat(dzs) * (torch.cat(masks) if use_mask else 1.0)
+            out.backward(cot)
+            n = [y.shape[0] for y in ys]
+
+            def close(a, ref):
+                assert float((a - ref).abs().max()) <= 1e-12 * max(float(ref.abs().max()), 1.0), (seed, use_mask)
+            close(torch.cat(r["out"]), out.detach())
+            close(torch.cat(r["dx"]), x.grad)
+            close(r["bwd_sums"][:c], b.grad)
+            close(r["bwd_sums"][c:], g.grad)
+            close(r["running_mean"], rm)
+            close(r["running_var"], rv)
+            close(r["var_one_pass"], r["var"])
+            assert r["count"] == sum(k * h * w for k, h, w in shapes) and [t.shape[0] for t in r["dx"]] == n
+
+
+def test_syncbn_reference_local_sums_add_up_to_the_global_sums():
+    """What each virtual rank contributes to the two exchanges — [sum y | sum y^2] forward, [sum d | sum d * xhat] backward —
+    adds up to the sums over the concatenated batch; a rank's backward sums are its own dbeta | dgamma."""
+    import torch
+    from helpers import syncbn_ref64
+    ys, dzs, masks, gamma, beta, rm0, rv0 = _syncbn_shards(3, [(2, 5, 7), (3, 5, 7), (1, 5, 7)], 12)
+    r = syncbn_ref64(ys, gamma, beta, 1e-5, 0.1, rm0, rv0, dzs, masks)
+    y, d = torch.cat(ys), torch.cat(dzs) * torch.cat(masks)
+    xh = (y - r["mean"].view(1, -1, 1, 1)) * r["invstd"].view(1, -1, 1, 1)
+    for got, ref in ((torch.stack(r["local_sums"]).sum(0), torch.cat([y.sum((0, 2, 3)), (y * y).sum((0, 2, 3))])),
+                     (torch.stack(r["local_bwd"]).sum(0), torch.cat([d.sum((0, 2, 3)), (d * xh).sum((0, 2, 3))]))):
+        assert float((got - ref).abs().max()) <= 1e-12 * float(ref.abs().max())
+    assert torch.equal(r["sums"], torch.stack(r["local_sums"]).sum(0))
+    assert torch.equal(r["bwd_sums"], torch.stack(r["local_bwd"]).sum(0))
+    for i in range(3):          # a shard's own sums: not a share of the total
+        di, xi = dzs[i] * masks[i], xh[sum(t.shape[0] for t in ys[:i]):][:ys[i].shape[0]]
+        assert float((r["local_bwd"][i][12:] - (di * xi).sum((0, 2, 3))).abs().max()) <= 1e-12 * float(di.abs().sum())
