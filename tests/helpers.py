@@ -428,3 +428,375 @@ def syncbn_ref64(ys, gamma, beta, eps, momentum=0.1, running_mean=None, running_
         a = scale.view(1, -1, 1, 1)
         r.update(d=ds, xhat=xh, local_bwd=lb, bwd_sums=bs, dx=[a * (d - sdy - x * sdx) for d, x in zip(ds, xh)])
     return r
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# fp32 convolutions against float64 (tests/test_conv_fp64_gpu.py; tests/test_host_logic.py checks the promises made here).
+# The yardstick for "what a correct fp32 kernel may err by" is a MODEL written from the definition of the operation: the
+# products of one output, rounded to float32 and added one after the other in float32 (seq32_error).  A correct kernel's
+# chains are never longer than that one (the matrix instruction adds 2 products per step, tiles split the reduction,
+# split-K shortens it further), so its error should not exceed the model's by more than a small factor, CONV_MARGIN.
+# ------------------------------------------------------------------------------------------------------------------
+CONV_SAMPLES = 4096          # sampled outputs per tensor (seeded)
+CONV_MARGIN_CAP = 8          # a case that needs more than this is a finding, not a reason to raise the margin
+CONV_MARGIN = 8              # = the cap: the grid has not been measured on an MI355X yet.  Rule for lowering it: the largest ratio
+                             # tests/test_conv_fp64_gpu.py prints, rounded up to a power of two, not below 2 (CPU float32 conv2d: 1.8)
+
+
+def conv_ref64(x, w, bias, stride, pad, relu, gy=None):
+    """F.conv2d on the CPU in float64 (+ autograd) -> (y, dx, dw) float64 tensors; dx = dw = None without gy.
+    x [N,C,H,W], w [K,C,R,S], bias [K] | None, pad (pad_h, pad_w), gy [N,K,P,Q]: the gradient w.r.t. the (post-ReLU)
+    output.  With relu the gradient mask comes from the float64 y."""
+    import torch.nn.functional as F
+    x64 = torch.as_tensor(x).detach().cpu().double().clone().requires_grad_(gy is not None)
+    w64 = torch.as_tensor(w).detach().cpu().double().clone().requires_grad_(gy is not None)
+    b64 = None if bias is None else torch.as_tensor(bias).detach().cpu().double()
+    y = F.conv2d(x64, w64, b64, stride=stride, padding=tuple(pad))
+    if relu:
+        y = F.relu(y)
+    if gy is None:
+        return y.detach(), None, None
+    y.backward(torch.as_tensor(gy).detach().cpu().double())
+    return y.detach(), x64.grad, w64.grad
+
+
+def conv_bias_clear_of_zero(y_nobias, bias, band=1e-3, step=2.5e-3):
+    """bias [K] float32 moved, channel by channel and in steps of `step`, until no element of y_nobias[:, k] + bias[k] lies
+    within `band` of 0 (y_nobias: float64 [N,K,P,Q], the convolution without bias) -> float32 array."""
+    y = np.asarray(y_nobias, np.float64)
+    b = np.asarray(bias, np.float32).copy()
+    for k in range(len(b)):
+        col = y[:, k].ravel()
+        for _ in range(1000):
+            if np.abs(col + np.float64(b[k])).min() > 2 * band:
+                break
+            b[k] = np.float32(b[k] + step)
+        else:
+            raise AssertionError("no bias found for channel %d" % k)
+    return b
+
+
+def conv_sample_positions(shape, seed, count=CONV_SAMPLES, keep=None):
+    """`count` seeded positions of a tensor of `shape` -> tuple of index arrays (with repeats where the tensor is small).
+    keep: boolean array of `shape`; only positions where it is True are drawn."""
+    rng = np.random.default_rng(seed)
+    if keep is None:
+        flat = rng.integers(0, int(np.prod(shape)), count)
+    else:
+        flat = rng.choice(np.flatnonzero(np.asarray(keep).ravel()), count)
+    return np.unravel_index(flat, shape)
+
+
+def _np64(t):
+    return t.detach().cpu().double().numpy() if torch.is_tensor(t) else np.asarray(t, np.float64)
+
+
+def conv_terms(kind, idx, x, w, gy, stride, pad, bias=None, base=None, chunk=1 << 23):
+    """The products that make up the sampled outputs `idx` of one convolution pass, gathered from the (zero-padded)
+    operands: yields float64 arrays [s, n] that together cover idx in order (chunks of about `chunk` elements).
+      kind "fprop": idx = (n, k, p, q) into y;  terms x[n, c, p*st-ph+r, q*st-pw+s] * w[k, c, r, s] over (c, r, s), then bias[k]
+      kind "dgrad": idx = (n, c, h, w) into dx; terms gy[n, k, p, q] * w[k, c, r, s] over (k, r, s) with p*st-ph+r == h, after base[idx]
+      kind "wgrad": idx = (k, c, r, s) into dw; terms gy[n, k, p, q] * x[n, c, p*st-ph+r, q*st-pw+s] over (n, p, q), after base[idx]
+    Taps in the padding appear as exact zeros (adding one changes no float32 sum).  The output size of "wgrad" is gy's (an
+    output larger than the symmetric one = more padding at the far edge).  base: the tensor an accumulating call adds into."""
+    st, (ph, pw) = stride, pad
+    x, w = (None if x is None else _np64(x)), (w if w is None or isinstance(w, tuple) else _np64(w))     # wgrad: w or (R, S)
+    gy = None if gy is None else _np64(gy)
+    nidx = len(idx[0])
+    if kind == "fprop":
+        n_all, c_all, h, wd = x.shape
+        r, s = w.shape[2:]
+        p_all, q_all = (h + 2 * ph - r) // st + 1, (wd + 2 * pw - s) // st + 1
+        xp = np.pad(x, ((0, 0), (0, 0), (ph, ph), (pw, pw))) if (ph or pw) else x
+        per = c_all * r * s + 1
+    elif kind == "dgrad":
+        k_all, p_all, q_all = gy.shape[1:]
+        r, s = w.shape[2:]
+        per = k_all * r * s + 1
+    else:
+        n_all, c_all, h, wd = x.shape
+        _, k_all, p_all, q_all = gy.shape
+        r, s = w if isinstance(w, tuple) else w.shape[2:]
+        far_h = max(0, (p_all - 1) * st + r - (h + ph))
+        far_w = max(0, (q_all - 1) * st + s - (wd + pw))
+        xp = np.pad(x, ((0, 0), (0, 0), (ph, far_h), (pw, far_w)))
+        per = n_all * p_all * q_all + 1
+    step = max(1, chunk // per)
+    base = None if base is None else _np64(base)
+    N = None
+    for lo in range(0, nidx, step):
+        i0, i1, i2, i3 = (np.asarray(a[lo:lo + step]) for a in idx)
+        m = len(i0)
+        if kind == "fprop":
+            rows = i2[:, N] * st + np.arange(r)
+            cols = i3[:, N] * st + np.arange(s)
+            patch = xp[i0[:, N, N, N], np.arange(c_all)[N, :, N, N], rows[:, N, :, N], cols[:, N, N, :]]
+            t = (patch * w[i1]).reshape(m, -1)
+            tail = np.zeros(m) if bias is None else _np64(bias)[i1]
+            yield np.concatenate([t, tail[:, N]], 1)
+        elif kind == "dgrad":
+            pn = i2[:, N] + ph - np.arange(r)
+            qn = i3[:, N] + pw - np.arange(s)
+            vh = (pn % st == 0) & (pn // st >= 0) & (pn // st < p_all)
+            vw = (qn % st == 0) & (qn // st >= 0) & (qn // st < q_all)
+            pi, qi = np.clip(pn // st, 0, p_all - 1), np.clip(qn // st, 0, q_all - 1)
+            patch = gy[i0[:, N, N, N], np.arange(k_all)[N, :, N, N], pi[:, N, :, N], qi[:, N, N, :]]
+            patch = np.where(vh[:, N, :, N] & vw[:, N, N, :], patch, 0.0)
+            t = (patch * w[:, i1].transpose(1, 0, 2, 3)).reshape(m, -1)
+            head = np.zeros(m) if base is None else base[i0, i1, i2, i3]
+            yield np.concatenate([head[:, N], t], 1)
+        else:
+            rows = i2[:, N] + st * np.arange(p_all)
+            cols = i3[:, N] + st * np.arange(q_all)
+            patch = xp[np.arange(n_all)[N, :, N, N], i1[:, N, N, N], rows[:, N, :, N], cols[:, N, N, :]]
+            t = (patch * gy[:, i0].transpose(1, 0, 2, 3)).reshape(m, -1)
+            head = np.zeros(m) if base is None else base[i0, i1, i2, i3]
+            yield np.concatenate([head[:, N], t], 1)
+
+
+def _seq32(terms):
+    terms = np.asarray(terms, np.float64)
+    ref = terms.sum(1)
+    seq = np.cumsum(terms.astype(np.float32), axis=1, dtype=np.float32)[:, -1].astype(np.float64)
+    return ref, seq
+
+
+def seq32_error(terms):
+    """terms [S, n] float64: the products of S outputs.  -> (max-abs, RMS) over the S outputs of the error, against the
+    float64 sum, of a chained float32 sum of the float32-rounded products in plain loop order."""
+    ref, seq = _seq32(terms)
+    err = seq - ref
+    return float(np.abs(err).max()), float(np.sqrt(np.mean(err * err)))
+
+
+def conv_yardstick(chunks, relu=False, head=None):
+    """seq32_error over the chunks conv_terms yields -> (ref [S] float64 sums, max_seq, rms_seq).  relu: both the chained
+    sum and the float64 sum pass through max(., 0) first (an output the ReLU zeroes carries no error).  head [S]: a second
+    triple follows, for the same terms with their first column (an accumulating call's starting value) replaced by head."""
+    out = [([], []), ([], [])]
+    lo = 0
+    for t in chunks:
+        for slot in range(1 if head is None else 2):
+            if slot == 1:
+                t = np.array(t, np.float64)
+                t[:, 0] = np.asarray(head, np.float64)[lo:lo + len(t)]
+            ref, seq = _seq32(t)
+            if relu:
+                ref, seq = np.maximum(ref, 0.0), np.maximum(seq, 0.0)
+            out[slot][0].append(ref)
+            out[slot][1].append(seq - ref)
+        lo += len(t)
+    res = []
+    for refs, errs in out[:1 if head is None else 2]:
+        ref, err = np.concatenate(refs), np.concatenate(errs)
+        res += [ref, float(np.abs(err).max()), float(np.sqrt(np.mean(err * err)))]
+    return tuple(res)
+
+
+def conv_error_ratios(got_s, ref_s, max_seq, rms_seq, got_all=None, ref_all=None):
+    """-> (max-abs error at the samples / max_seq, RMS error at the samples / rms_seq, RMS error over the whole tensor /
+    rms_seq or None).  A zero yardstick (exact operands) asks for a zero error: the ratio is then 0 or inf."""
+    def ratio(e, bound):
+        return 0.0 if e == 0.0 else (float("inf") if bound == 0.0 else e / bound)
+    es = np.asarray(got_s, np.float64) - np.asarray(ref_s, np.float64)
+    out = [ratio(float(np.abs(es).max()), max_seq), ratio(float(np.sqrt(np.mean(es * es))), rms_seq), None]
+    if got_all is not None:
+        ea = np.asarray(got_all, np.float64) - np.asarray(ref_all, np.float64)
+        out[2] = ratio(float(np.sqrt(np.mean(ea * ea))), rms_seq)
+    return tuple(out)
+
+
+def conv_accepts(ratios, margin=None):
+    """The acceptance rule: every ratio of conv_error_ratios is finite and <= margin."""
+    margin = CONV_MARGIN if margin is None else margin
+    return all(r is None or (np.isfinite(r) and r <= margin) for r in ratios)
+
+
+def round_sig_bits(a, bits):
+    """float64 array rounded (to nearest) to `bits` significant bits."""
+    m, e = np.frexp(np.asarray(a, np.float64))
+    return np.ldexp(np.round(m * 2.0 ** bits) / 2.0 ** bits, e)
+
+
+def conv_tap_counts(size, out, r, stride, pad):
+    """1-D closed forms of an all-ones convolution: (taps of each output position that fall inside the input [out],
+    (output, tap) pairs that reach each input position [size], outputs whose tap t falls inside the input [r])."""
+    pos = np.arange(out)[:, None] * stride - pad + np.arange(r)[None, :]
+    inside = (pos >= 0) & (pos < size)
+    reach = np.zeros(size, np.int64)
+    np.add.at(reach, pos[inside], 1)
+    return inside.sum(1), reach, inside.sum(0)
+
+
+# ---- which host route a shape takes: a restatement of the dispatch rules of rrnet_amd/csrc/conv.hip ----
+_BM, _BK = 128, 32                                  # conv.hip:36-37
+_SMALL_TILES, _MID_TILES = 16, 48                   # small_tiles() / mid_tiles(), conv.hip:1088-1090
+
+
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+def pick_ksplit_mirror(blocks, nk):
+    """pick_ksplit (conv.hip:1093-1114) in float32 arithmetic, the 0.95 hysteresis included (RR_CONV_SPLITK unset)."""
+    f = np.float32
+    if blocks >= 256 or nk < 16:
+        return 1
+    best, best_t = 1, f(0)
+    ks = 1
+    while ks <= 8 and ks <= nk // 8:
+        n = (blocks * ks + 255) // 256
+        per = f(f(f((nk + ks - 1) // ks) + f(3)) + (f(1) if ks > 1 else f(0)))
+        t = f(f(f(n // 2) * f(f(f(2) * per) / f(0.87))) + f(f(n % 2) * f(per / f(0.75))))
+        if best_t == 0 or t < f(best_t * f(0.95)):
+            best, best_t = ks, t
+        ks += 1
+    return best
+
+
+def _fprop_route(n, c, h, w, k, r, s, stride, ph, pw, bias, relu, want_stats):
+    p, q = (h + 2 * ph - r) // stride + 1, (w + 2 * pw - s) // stride + 1
+    m = n * p * q
+    if (r == 1 and s == 1 and stride == 1 and ph == 0 and pw == 0 and c in (128, 256) and 48 < k <= 64 and not want_stats
+            and m >= 64 * 1024 and m * c * 4 < (1 << 31)):
+        return {"rows"}
+    scalar = c % 4 != 0 or r * s > 64
+    bn = 128 if k > 64 else ((64 if not scalar else 128) if k > 32 else 32)
+    if bn == 128 and not scalar and _cdiv(m, _BM) * _cdiv(k, 128) <= _SMALL_TILES:
+        bn = 32
+    elif bn == 128 and not scalar and _cdiv(m, _BM) * _cdiv(k, 128) <= _MID_TILES:
+        bn = 64
+    blocks = _cdiv(m, _BM) * _cdiv(k, bn)
+    nk = _cdiv(r * s * c, _BK) if scalar else _cdiv(c, _BK) * r * s
+    ks = pick_ksplit_mirror(blocks, nk) if (not bias and not relu and k % 4 == 0 and k <= 1024) else 1
+    labels = {"bn%d" % bn}
+    if scalar:
+        labels.add("scalar")
+    if (not scalar and not want_stats and (ph > 0 or pw > 0) and r * s > 1 and p * q <= 16 and n >= 16 * _BM and bn >= 64
+            and n * h * w * c * 4 < (1 << 31) and k * r * s * c * 4 < (1 << 31)):
+        labels.add("pos_major")
+        ks = 1
+    if ks > 1:
+        labels.add("ksplit>1+stats" if want_stats else "ksplit>1")
+    return labels
+
+
+def conv_routes(n, c, h, w, k, r, s, stride, pad, bias, relu, want_stats, out_h=0, out_w=0):
+    """The host route of each pass of one convolution: {"fprop", "dgrad", "wgrad", "dgrad_via_fprop"} -> set of labels.
+    A pure-Python mirror of the C rules in rrnet_amd/csrc/conv.hip (line numbers of the commit this was written against):
+      fprop  fprop_impl, lines 1189-1259 (rows: 1207-1209, scalar / tile width: 1210-1214, split-K: 1215-1217 with
+             pick_ksplit 1093-1114, pos_major: 1221-1227) and launch_igemm 1146-1171:
+             rows | bn128 / bn64 / bn32, scalar, pos_major, ksplit>1 (no statistics) / ksplit>1+stats (zero-fill + colstats_kernel)
+      dgrad  rr_conv_dgrad, lines 1437-1489: bn*, scalar, parity4 (stride 2, all four classes have taps),
+             parity_live<4 (classes without taps get no workgroups), ksplit>1
+      wgrad  rr_conv_wgrad, lines 1491-1538: pipe3 / pipe1 (the pipelined 128x128 kernels), 128x128 / 128x32 / 32x128 /
+             32x32 (the generic tiles), a_scalar (k % 4 != 0), b_scalar (c % 4 != 0), splits>1; out_h / out_w as there
+      dgrad_via_fprop  rr_conv_dgrad_s1 (1351-1360) = the fprop rules on (dy, flipped filter); empty where ops.conv_dgrad
+             cannot take that route (stride > 1, channel counts not multiples of 4, more than 64 taps)."""
+    ph, pw = pad
+    routes = {"fprop": _fprop_route(n, c, h, w, k, r, s, stride, ph, pw, bias, relu, want_stats)}
+    p, q = (h + 2 * ph - r) // stride + 1, (w + 2 * pw - s) // stride + 1
+    # ---- rr_conv_dgrad
+    m = n * h * w
+    scalar = k % 4 != 0 or c % 4 != 0 or r * s > 64 or stride > 2
+    bn = 128 if c > 64 else ((64 if not scalar else 128) if c > 32 else 32)
+    if bn == 128 and not scalar and stride == 1 and _cdiv(m, _BM) * _cdiv(c, 128) <= _SMALL_TILES:
+        bn = 32
+    elif bn == 128 and not scalar and stride == 1 and _cdiv(m, _BM) * _cdiv(c, 128) <= _MID_TILES:
+        bn = 64
+    blocks, gy = _cdiv(m, _BM) * _cdiv(c, bn), 1
+    nk = _cdiv(r * s * k, _BK) if scalar else _cdiv(k, _BK) * r * s
+    d = {"bn%d" % bn}
+    if scalar:
+        d.add("scalar")
+    parity = stride == 2 and not scalar
+    if parity:
+        taps = []
+        for cl in range(4):
+            r0, s0 = ((cl >> 1) + ph) & 1, ((cl & 1) + pw) & 1
+            taps.append(((r - r0 + 1) // 2 if r0 < r else 0) * ((s - s0 + 1) // 2 if s0 < s else 0))
+        taps.sort(reverse=True)
+        live = 4
+        while live > 1 and taps[live - 1] == 0:
+            live -= 1
+        gy = live
+        d.add("parity4" if live == 4 else "parity_live<4")
+        blocks = _cdiv(n * ((h + 1) // 2) * ((w + 1) // 2), _BM) * _cdiv(c, bn)
+        nk = _cdiv(k, _BK) * ((r + 1) // 2) * ((s + 1) // 2)
+    if not parity and pick_ksplit_mirror(blocks * gy, nk) > 1:
+        d.add("ksplit>1")
+    routes["dgrad"] = d
+    # ---- rr_conv_wgrad
+    pp, qq = (out_h if out_h > 0 else p), (out_w if out_w > 0 else q)
+    mw = n * pp * qq
+    bmw, bnw = (128 if k > 32 else 32), (128 if c > 32 else 32)
+    tiles = _cdiv(k, bmw) * _cdiv(c, bnw) * r * s
+    chunks = _cdiv(mw, _BK)
+    a_s, b_s = k % 4 != 0, c % 4 != 0
+    pipe_ok = (bmw == 128 and bnw == 128 and not a_s and not b_s and mw * k * 4 < (1 << 31) and n * h * w * c * 4 < (1 << 31))
+    wmode = 0 if not pipe_ok else (3 if qq % _BK == 0 else 1)
+    slots = 768 if wmode == 3 else 512
+    splits = slots // tiles if tiles < slots else 1
+    splits = max(1, min(splits, _cdiv(chunks, 8)))
+    splits = _cdiv(chunks, _cdiv(chunks, splits))
+    g = {"pipe3"} if wmode == 3 else ({"pipe1"} if wmode == 1 else {"%dx%d" % (bmw, bnw)})
+    if a_s:
+        g.add("a_scalar")
+    if b_s:
+        g.add("b_scalar")
+    if splits > 1:
+        g.add("splits>1")
+    routes["wgrad"] = g
+    via = set()
+    if stride == 1 and k % 4 == 0 and c % 4 == 0 and r * s <= 64 and ph < r and pw < s:
+        via = _fprop_route(n, k, p, q, c, r, s, 1, r - 1 - ph, s - 1 - pw, False, False, False)
+    routes["dgrad_via_fprop"] = via
+    return routes
+
+
+CONV_ROUTE_LABELS = {
+    "fprop": {"rows", "pos_major", "bn128", "bn64", "bn32", "scalar", "ksplit>1", "ksplit>1+stats"},
+    "dgrad": {"scalar", "parity4", "parity_live<4", "bn128", "bn64", "bn32", "ksplit>1"},
+    "wgrad": {"pipe3", "pipe1", "128x128", "128x32", "32x128", "32x32", "a_scalar", "b_scalar", "splits>1"},
+}
+
+# (N, C, H, W, K, R, S, stride, pad_h, pad_w, bias, relu, want_stats values, passes: f = fprop, d = dgrad, w = wgrad)
+CONV64_GRID = [
+    (1, 256, 16, 16, 256, 3, 3, 1, 1, 1, False, False, (False, True), "fdw"),     # fprop bn32 split-K (+ stats); dgrad split-K
+    (1, 384, 32, 32, 384, 3, 3, 1, 1, 1, False, False, (False, True), "fdw"),     # bn64 mid tiles, split-K
+    (2, 256, 64, 64, 256, 3, 3, 1, 1, 1, False, False, (False, True), "fdw"),     # bn128 pipelined, split-K (128 tiles); wgrad pipe3
+    (1, 256, 66, 70, 256, 3, 3, 1, 1, 1, False, False, (False, True), "fdw"),     # ragged M tile; wgrad pipe1
+    (1, 64, 128, 128, 256, 3, 3, 1, 1, 1, False, False, (False, True), "fdw"),    # bn128 with a full first wave: NO split, fused statistics
+    (1, 64, 9, 13, 128, 3, 3, 1, 1, 1, False, False, (False, True), "fdw"),       # ragged M and N, small
+    (2, 128, 15, 17, 256, 1, 1, 2, 0, 0, False, False, (False, True), "fdw"),     # dgrad parity_live<4
+    (2, 16, 7, 9, 24, 3, 3, 2, 1, 1, False, False, (False, True), "fdw"),         # dgrad parity4, odd H and W; wgrad 32x32
+    (1, 30, 11, 9, 50, 3, 3, 1, 1, 1, False, False, (False, True), "fdw"),        # c % 4 != 0: scalar fprop; wgrad 128x32 b_scalar
+    (1, 40, 9, 11, 18, 3, 3, 1, 1, 1, False, False, (False, True), "fdw"),        # k % 4 != 0: scalar dgrad; wgrad 32x128 a_scalar
+    (1, 34, 9, 7, 38, 3, 3, 1, 1, 1, False, False, (False, True), "fdw"),         # both: wgrad's generic 128x128 tile, a_ and b_scalar
+    (1, 6, 10, 10, 10, 3, 3, 3, 1, 1, False, False, (False, True), "fdw"),        # stride 3: scalar dgrad
+    (2, 3, 30, 34, 128, 7, 7, 2, 3, 3, False, False, (False, True), "fdw"),       # stem: 49 taps on 3 channels (scalar gather)
+    (1, 256, 20, 12, 1, 17, 1, 1, 8, 0, True, False, (False, True), "fdw"),       # HCov, bias
+    (1, 256, 10, 10, 256, 3, 3, 1, 1, 1, True, True, (False, True), "fdw"),       # bias + ReLU keep split-K off
+    (2048, 64, 3, 3, 64, 3, 3, 1, 1, 1, False, False, (False, True), "fdw"),      # pos_major (without statistics)
+    # the row-streaming 1x1 kernel (M = 65536, no statistics).  Forward only: that route exists in the forward pass alone,
+    # the gradients of this shape take the bn64 / pipelined routes the cases above hold, and a sampled weight-gradient
+    # yardstick here is 4096 chains of 65536 products
+    (1, 256, 256, 256, 64, 1, 1, 1, 0, 0, False, False, (False,), "f"),
+]
+# the weight gradient with the out_h / out_w override (one more output row and column than symmetric padding gives)
+CONV64_ASYM_WGRAD = (1, 64, 12, 12, 64, 3, 3, 1, 1, 1, 13, 13)
+
+
+def conv_grid_routes():
+    """{pass: set of labels} over CONV64_GRID (every want_stats value a case runs with) and CONV64_ASYM_WGRAD."""
+    seen = {"fprop": set(), "dgrad": set(), "wgrad": set()}
+    for cfg in CONV64_GRID:
+        n, c, h, w, k, r, s, st, ph, pw, bias, relu, stats, passes = cfg
+        for ws in stats:
+            rt = conv_routes(n, c, h, w, k, r, s, st, (ph, pw), bias, relu, ws)
+            for key, ch in (("fprop", "f"), ("dgrad", "d"), ("wgrad", "w")):
+                if ch in passes:
+                    seen[key] |= rt[key]
+    n, c, h, w, k, r, s, st, ph, pw, oh, ow = CONV64_ASYM_WGRAD
+    seen["wgrad"] |= conv_routes(n, c, h, w, k, r, s, st, (ph, pw), False, False, False, oh, ow)["wgrad"]
+    return seen

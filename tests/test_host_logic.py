@@ -405,3 +405,123 @@ def test_syncbn_reference_local_sums_add_up_to_the_global_sums():
     for i in range(3):          # a shard's own sums: not a share of the total
         di, xi = dzs[i] * masks[i], xh[sum(t.shape[0] for t in ys[:i]):][:ys[i].shape[0]]
         assert float((r["local_bwd"][i][12:] - (di * xi).sum((0, 2, 3))).abs().max()) <= 1e-12 * float(di.abs().sum())
+
+
+# ---- the float64 convolution checks (tests/test_conv_fp64_gpu.py): reference, yardstick, acceptance rule, route labels ----
+def test_conv_ref64_equals_a_hand_written_float64_loop():
+    """helpers.conv_ref64 (F.conv2d in float64 + autograd) against plain loops on one tiny strided, asymmetric-filter,
+    biased, ReLU'd shape: y, dx, dw; and helpers.conv_terms' gathered products add up to the same three tensors."""
+    import numpy as np
+    import torch
+    from helpers import conv_ref64, conv_terms
+    rng = np.random.default_rng(5)
+    n, c, h, w, k, r, s, st, ph, pw = 2, 3, 6, 7, 4, 3, 2, 2, 1, 1
+    x, wt, b = rng.standard_normal((n, c, h, w)), rng.standard_normal((k, c, r, s)), rng.standard_normal(k)
+    p, q = (h + 2 * ph - r) // st + 1, (w + 2 * pw - s) // st + 1
+    gy = rng.standard_normal((n, k, p, q))
+    y = np.zeros((n, k, p, q))
+    dx, dw = np.zeros_like(x), np.zeros_like(wt)
+    for pas in (0, 1):                       # pass 0: y; pass 1: the gradients through the ReLU mask of y
+        for i in range(n):
+            for ko in range(k):
+                for a in range(p):
+                    for bq in range(q):
+                        acc = b[ko]
+                        for ci in range(c):
+                            for rr in range(r):
+                                for ss in range(s):
+                                    ih, iw = a * st - ph + rr, bq * st - pw + ss
+                                    if 0 <= ih < h and 0 <= iw < w:
+                                        if pas == 0:
+                                            acc += x[i, ci, ih, iw] * wt[ko, ci, rr, ss]
+                                        elif y[i, ko, a, bq] > 0:
+                                            dx[i, ci, ih, iw] += gy[i, ko, a, bq] * wt[ko, ci, rr, ss]
+                                            dw[ko, ci, rr, ss] += gy[i, ko, a, bq] * x[i, ci, ih, iw]
+                        if pas == 0:
+                            y[i, ko, a, bq] = max(acc, 0.0)
+    yr, dxr, dwr = conv_ref64(torch.from_numpy(x), torch.from_numpy(wt), torch.from_numpy(b), st, (ph, pw), True, torch.from_numpy(gy))
+    assert yr.dtype == dxr.dtype == dwr.dtype == torch.float64
+    for got, ref in ((yr, y), (dxr, dx), (dwr, dw)):
+        assert np.abs(got.numpy() - ref).max() <= 1e-13 * np.abs(ref).max()
+    gm = gy * (y > 0)
+    for kind, ref, args in (("fprop", y, dict(bias=b)), ("dgrad", dx, {}), ("wgrad", dw, {})):
+        idx = np.unravel_index(np.arange(ref.size), ref.shape)
+        tot = np.concatenate([t.sum(1) for t in conv_terms(kind, idx, x, wt, gm, st, (ph, pw), chunk=200, **args)])
+        tot = np.maximum(tot, 0.0) if kind == "fprop" else tot
+        assert np.abs(tot - ref.ravel()).max() <= 1e-13 * np.abs(ref).max(), kind
+    # an accumulating call's starting value is one more term
+    base = rng.standard_normal(dw.shape)
+    idx = np.unravel_index(np.arange(dw.size), dw.shape)
+    tot = np.concatenate([t.sum(1) for t in conv_terms("wgrad", idx, x, (r, s), gm, st, (ph, pw), base=base)])
+    assert np.abs(tot - (dw + base).ravel()).max() <= 1e-13 * np.abs(dw).max()
+
+
+def test_conv_acceptance_rule_sees_what_a_loose_float32_comparison_cannot():
+    """The rule of tests/test_conv_fp64_gpu.py (error at the sampled outputs <= margin x the error of a chained float32 sum of
+    the same products: helpers.seq32_error / conv_error_ratios / conv_accepts) at its cap, margin = 8, at reduction lengths
+    2304 and 288: it REJECTS a host-simulated kernel that rounds one operand to 11 significant bits, one that rounds both
+    to fp16, and one that loses the last 4 products (scaled to 1e-4 of the output) — each otherwise summed exactly — and
+    ACCEPTS a float32 pairwise sum."""
+    import numpy as np
+    from helpers import CONV_MARGIN_CAP, CONV_SAMPLES, conv_accepts, conv_error_ratios, round_sig_bits, seq32_error
+    for kg in (2304, 288):
+        rng = np.random.default_rng(kg)
+        a = rng.standard_normal((CONV_SAMPLES, kg)).astype(np.float32).astype(np.float64)
+        b = (rng.standard_normal((CONV_SAMPLES, kg)) / np.sqrt(kg)).astype(np.float32).astype(np.float64)
+        tail_scale = 1e-4 * np.sqrt(kg) / 2.0                        # rms of 4 products = 2/sqrt(kg): 1e-4 of the unit output
+        a_tail = a.copy()
+        a_tail[:, -4:] *= np.float32(tail_scale)
+
+        def verdict(got, terms):
+            ref = terms.sum(1)
+            max_seq, rms_seq = seq32_error(terms)
+            assert 0 < rms_seq < max_seq < 1e-5
+            return conv_accepts(conv_error_ratios(got, ref, max_seq, rms_seq, got, ref), CONV_MARGIN_CAP), np.abs(got - ref).max()
+        terms = a * b
+        for name, got in (("one operand at 11 bits", (a * round_sig_bits(b, 11)).sum(1)),
+                          ("both operands fp16", (a.astype(np.float16).astype(np.float64) * b.astype(np.float16).astype(np.float64)).sum(1))):
+            ok, err = verdict(got, terms)
+            assert not ok, (kg, name, err)
+        terms_t = a_tail * b
+        ok, err = verdict(np.sum(terms_t[:, :-4].astype(np.float32), axis=1, dtype=np.float32).astype(np.float64), terms_t)
+        assert not ok, (kg, "lost K tail", err)
+        for t in (terms, terms_t):
+            ok, _ = verdict(np.sum(t.astype(np.float32), axis=1, dtype=np.float32).astype(np.float64), t)
+            assert ok, (kg, "float32 pairwise sum")
+    # a zero yardstick (exact operands) asks for a zero error
+    assert conv_accepts(conv_error_ratios(np.ones(4), np.ones(4), 0.0, 0.0)) and not conv_accepts(conv_error_ratios(np.ones(4) + 1e-7, np.ones(4), 0.0, 0.0))
+
+
+def test_conv_route_mirror_and_grid_coverage():
+    """helpers.conv_routes restates the host dispatch of rrnet_amd/csrc/conv.hip: its split-K rule equals the library's own
+    pick_ksplit wherever asked, the tile thresholds equal the library's, and the grid of tests/test_conv_fp64_gpu.py reaches
+    every route label at least once — and the combinations the grid was laid out for."""
+    import ctypes
+    from helpers import CONV64_GRID, CONV_ROUTE_LABELS, _MID_TILES, _SMALL_TILES, conv_grid_routes, conv_routes, pick_ksplit_mirror
+    from rrnet_amd import _C, ops
+    L = _C.lib()
+    pick = getattr(L, "_Z19rr_conv_pick_ksplitii")                  # int rr_conv_pick_ksplit(int, int): C++ linkage
+    pick.restype, pick.argtypes = ctypes.c_int, [ctypes.c_int, ctypes.c_int]
+    bad = [(b, nk) for b in range(1, 260) for nk in list(range(1, 160)) + [288, 432, 1000] if pick(b, nk) != pick_ksplit_mirror(b, nk)]
+    assert not bad, bad[:8]
+    for name, want in (("_Z19rr_conv_small_tilesv", _SMALL_TILES), ("_Z17rr_conv_mid_tilesv", _MID_TILES)):
+        f = getattr(L, name)
+        f.restype, f.argtypes = ctypes.c_int, []
+        assert f() == want
+    assert (ops._SMALL_TILES, ops._MID_TILES) == (_SMALL_TILES, _MID_TILES)
+    seen = conv_grid_routes()
+    missing = {p: sorted(CONV_ROUTE_LABELS[p] - seen[p]) for p in seen if CONV_ROUTE_LABELS[p] - seen[p]}
+    assert not missing, "route labels no grid shape reaches: %s" % missing
+
+    def route(i, ws=False):
+        n, c, h, w, k, r, s, st, ph, pw, bias, relu = CONV64_GRID[i][:12]
+        return conv_routes(n, c, h, w, k, r, s, st, (ph, pw), bias, relu, ws)
+    combos = [(rt["fprop"], rt["dgrad"], rt["wgrad"]) for i in range(len(CONV64_GRID)) for rt in (route(i, False), route(i, True))]
+    for pas, want in ((0, {"bn128"}), (0, {"bn128", "ksplit>1+stats"}), (0, {"bn64", "ksplit>1+stats"}), (0, {"bn32", "ksplit>1+stats"}),
+                      (0, {"bn128", "scalar"}), (0, {"bn32", "scalar"}), (0, {"bn64", "pos_major"}), (0, {"rows"}),
+                      (1, {"bn128", "parity_live<4"}), (1, {"bn32", "parity4"}), (1, {"bn32", "ksplit>1"}), (1, {"bn128", "scalar"}),
+                      (2, {"128x32", "a_scalar", "b_scalar"}), (2, {"32x128", "a_scalar"}), (2, {"32x32"}),
+                      (2, {"128x128", "a_scalar", "b_scalar"}), (2, {"pipe3", "splits>1"}), (2, {"pipe1"})):
+        assert any(cmb[pas] == want for cmb in combos), (pas, want)
+    # bias / ReLU keep split-K off on a shape that would otherwise split
+    assert route(14)["fprop"] == {"bn32"} and CONV64_GRID[14][10:12] == (True, True)
