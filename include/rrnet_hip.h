@@ -485,8 +485,8 @@ int rr_ctnet_targets(const float *annos, const int *counts, int b, int m, int an
                      float *reg_mask, hipStream_t stream);
 
 /* ---- training input: device-side augmentation ------------------------------------------------- *
- * rr_augment_frames: the pixel half of the training chain of configs/rrnet_config.py:40-49 without FillDuck, one gather
- *   per output pixel: MultiScale (datasets/transforms/functional.py:72-82, PIL `Image.resize(..., BILINEAR)` for scale
+ * rr_augment_frames: the pixel half of the training chain of configs/rrnet_config.py:40-49 for frames FillDuck does not
+ *   paste into (those go through rr_augment_frames_pasted below), one gather per output pixel: MultiScale (datasets/transforms/functional.py:72-82, PIL `Image.resize(..., BILINEAR)` for scale
  *   factors >= 1), ToTensor (:32-38), MaskIgnore (:290-313), HorizontalFlip (:13-19), RandomCrop's padding and crop
  *   (datasets/transforms/transforms.py:60-72, functional.py:104-111) and Normalize (functional.py:135-143).  Bit-exact
  *   with that chain on the host.
@@ -505,6 +505,31 @@ int rr_ctnet_targets(const float *annos, const int *counts, int b, int m, int an
 int rr_augment_frames(const unsigned char *src, long src_bytes, const int *params, const int *rects,
                       const int *rect_off, const int *taps, int ntaps, const float *mean, const float *stdv,
                       float *out, int b, int out_h, int out_w, hipStream_t stream);
+
+/* rr_augment_frames_pasted: the same chain WITH FillDuck between MaskIgnore and HorizontalFlip (datasets/transforms/
+ *   transforms.py:173-179, functional.py:356-523: crop an object, F.interpolate(mode='bilinear', align_corners=True),
+ *   slice-assign it elsewhere in the frame, :438-452 and :486-501).  The host decides every paste (datasets/transforms/
+ *   functional.py fill_duck_decide here); the device does the pixels in three stages: `canvas` (the scaled, masked,
+ *   un-flipped frame as fp32 = (float)v / 255.0f; the float32 mean inside ignore rectangles), `paste` (one workgroup per
+ *   frame walks its list in order; all reads of a paste come before its writes, later pastes see earlier ones) and
+ *   `finish` (crop, 0 padding, un-flip, (x - mean) / std).  Pixels no paste wrote are bit-identical to rr_augment_frames;
+ *   a pasted pixel is l0*(m0*a + m1*b) + l1*(m0*c + m1*d) with torch's source indices and weights (r = rheight*(float)oy,
+ *   y0 = (int)r, l1 = r - y0, l0 = 1 - l1; likewise x), within float32 rounding of torch's value.
+ *   src, params, rects, rect_off, taps, mean, stdv, out, b, out_h, out_w: as rr_augment_frames, except that a frame
+ *     with pastes ships a window that covers every source pixel (the whole frame).
+ *   pastes [*, RR_PASTE_WORDS] int32 = source rectangle y, x, h, w; destination y, x; object h, w (all inside the scaled
+ *     frame); the float32 bit patterns of rheight = (h-1)/(object h-1) and rwidth (0 for a 1-pixel object axis); two
+ *     reserved words.  paste_off [b+1] int32: frame i owns rows [paste_off[i], paste_off[i+1]).
+ *   canvas [b, canvas_stride, 3] float, 16-byte aligned, canvas_stride (pixels, a multiple of 4) >= every frame's
+ *     scaled height * width; scratch [b, scratch_stride, 3] float, scratch_stride (pixels) >= every object's h * w.  A
+ *     frame or object that does not fit is skipped, never written out of bounds.
+ *   stages: mask of 1 (canvas), 2 (paste), 4 (finish); 7 is the whole chain (the others exist to time one stage). */
+#define RR_PASTE_WORDS 12
+int rr_augment_frames_pasted(const unsigned char *src, long src_bytes, const int *params, const int *rects,
+                             const int *rect_off, const int *taps, int ntaps, const int *pastes, const int *paste_off,
+                             const float *mean, const float *stdv, float *canvas, long canvas_stride, float *scratch,
+                             long scratch_stride, float *out, int b, int out_h, int out_w, int stages,
+                             hipStream_t stream);
 
 /* ---- inference post-process (config 5: decode -> re-regression -> Soft-NMS) ------------------ *
  * rr_refine_boxes: operators/rrnet_operator.py:188-209 `generate_bbox` (stage-2 boxes from the packed RoIs

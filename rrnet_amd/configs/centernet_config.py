@@ -1,5 +1,6 @@
 """`Config` for CenterNet with the keys and values of the reference's configs/centernet_config.py:6-99 (BASELINE
-configs[0] plumbing).  As in rrnet_config.py the transform chains are the reference's without FillDuck."""
+configs[0] plumbing).  As in rrnet_config.py the transform chains are the reference's without FillDuck (see
+rrnet_fillduck_config.py for the full chain)."""
 from torch.utils.data import DistributedSampler
 
 from rrnet_amd.configs.rrnet_config import IMAGENET_MEAN, IMAGENET_STD, STRIDE, _tree

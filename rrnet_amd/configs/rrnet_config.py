@@ -1,6 +1,6 @@
 """`Config` for RRNet with the keys and values of the reference's configs/rrnet_config.py:7-91, declared as one
-nested table.  `Train.transforms` is the reference's chain (configs/rrnet_config.py:40-49) without FillDuck, which needs
-road maps and cv2 and stays out of scope; `Val.transforms` is ToTensor -> Normalize.  The real-data loader reads the
+nested table.  `Train.transforms` is the reference's chain (configs/rrnet_config.py:40-49) without FillDuck (the full
+chain, for datasets with road maps, is rrnet_fillduck_config.py); `Val.transforms` is ToTensor -> Normalize.  The real-data loader reads the
 chain's parameters from these instances and lowers the pixel work to rr_augment_frames (rrnet_amd/datasets/augment.py);
 the crop size is the one given to RandomCrop, as in the reference."""
 from torch.utils.data import DistributedSampler

@@ -1,7 +1,7 @@
 // rr_augment_frames: the pixel half of the training chain of configs/rrnet_config.py:40-49 (MultiScale -> ToTensor ->
-// MaskIgnore -> HorizontalFlip -> RandomCrop -> Normalize, FillDuck excluded) as ONE gather per output pixel.  The host
-// decodes the JPEG and decides (scale, flip, crop origin); this kernel reads the uint8 source window and writes the
-// normalised fp32 NHWC network input.  Bit-exact with the host chain:
+// MaskIgnore -> HorizontalFlip -> RandomCrop -> Normalize; frames FillDuck pastes into go through augment_paste.hip) as ONE
+// gather per output pixel.  The host decodes the JPEG and decides (scale, flip, crop origin); this kernel reads the uint8
+// source window and writes the normalised fp32 NHWC network input.  Bit-exact with the host chain:
 //   * PIL's 8-bit bilinear resize is two separable fixed-point passes (Resample.c): horizontal first, rounded to uint8,
 //     then vertical; an up-scale has at most two taps per output coordinate.  The per-axis tables (first tap, k0, k1)
 //     come from the host (datasets/transforms/functional.py pil_bilinear_taps), so the kernel does integer work only.

@@ -23,6 +23,7 @@ PER_FILE = {
     "targets.hip": ["-ffp-contract=off"],
     "psroi.hip": ["-ffp-contract=off"],
     "augment.hip": ["-ffp-contract=off"],
+    "augment_paste.hip": ["-ffp-contract=off"],
 }
 
 

@@ -1,14 +1,17 @@
 """Loaders that feed real VisDrone frames to the hot path with the `get_batch()` surface of datasets/dataloader.py:27-37.
 
 The host decodes the JPEG and DECIDES; the device produces the pixels.  Per sample the sampler draws (scale, flip, crop
-origin) from a generator keyed by (seed, rank, epoch, index), runs RandomCrop's decision logic on the annotations alone
-and emits the final annotation rows, the record rr_augment_frames needs and the source window the crop reads.
-DeviceAugmentLoader ships the windows through pinned memory, one batch ahead on a copy stream (the event hand-over of
-HostFedDronesDET), and runs rr_augment_frames + rr_ctnet_targets on the compute stream.  HostAugmentLoader runs the
-reference's chain on the host for the SAME decisions: it is what the device path is checked against, bit for bit.
+origin) from a generator keyed by (seed, rank, epoch, index), runs FillDuck's and RandomCrop's decision logic on the
+annotations (and the road map) alone and emits the final annotation rows, the record rr_augment_frames needs, the paste
+plan and the source window the crop reads.  DeviceAugmentLoader ships the windows through pinned memory, one batch ahead
+on a copy stream (the event hand-over of HostFedDronesDET), and runs rr_augment_frames (rr_augment_frames_pasted for a
+batch with pastes, whose pasted samples ship their whole frame) + rr_ctnet_targets on the compute stream.
+HostAugmentLoader runs the reference's chain on the host for the SAME decisions: it is what the device path is checked
+against, bit for bit except for pasted pixels (functional.apply_paste_plan states their bound).
 
 Deviations from the reference chain (configs/rrnet_config.py:40-49), see DESIGN.md "Data layer":
-  * FillDuck and ColorJitter are not part of it;
+  * ColorJitter is not part of it;
+  * FillDuck's draws come from a generator keyed per sample and attempt, not from the global torch generator;
   * where every box is larger than the crop the reference rescales the frame with F.interpolate
     (transforms.py:81-90); here the sampler redraws the MultiScale factor (and flip and origin) and counts it
     (`redraws`); a draw that keeps no box at all is redrawn too;
@@ -20,19 +23,22 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from .transforms import (Compose, HorizontalFlip, MaskIgnore, MultiScale, Normalize, RandomCrop, ToHeatmap, ToTensor)
+from .transforms import (Compose, FillDuck, HorizontalFlip, MaskIgnore, MultiScale, Normalize, RandomCrop, ToHeatmap,
+                         ToTensor)
 from .transforms import functional as F
 
 MAX_THREADS = 16
 MIN_SCALE = 1.0
 P_WORDS = 16          # ops.AUGMENT_PARAMS
+T_WORDS = F.PASTE_WORDS   # ops.PASTE_WORDS
+FILL_DUCK_TAG = 0x46443031   # "FD01": keeps FillDuck's generator apart from the scale / flip / crop draws
 
 
 def chain_params(transforms):
     """Reads the parameters of the lowered chain out of a Compose of transform instances.  Anything the kernel does not
     implement is an error, not a silent difference."""
     p = dict(scales=(1,), flip_p=0.0, crop=None, keep_iou=0.5, mean=None, std=None, ignore_idx=None, ignore_mean=None,
-             scale_factor=4, cls_num=10)
+             scale_factor=4, cls_num=10, fill_duck=None)
     seen = []
     for t in (transforms.transforms if isinstance(transforms, Compose) else transforms):
         seen.append(type(t))
@@ -42,6 +48,8 @@ def chain_params(transforms):
             pass
         elif isinstance(t, MaskIgnore):
             p["ignore_idx"], p["ignore_mean"] = t.ignore_idx, tuple(t.mean)
+        elif isinstance(t, FillDuck):
+            p["fill_duck"] = dict(cls_list=tuple(int(c) for c in t.cls_list.view(-1).tolist()), factor=float(t.factor))
         elif isinstance(t, HorizontalFlip):
             p["flip_p"] = t.p
         elif isinstance(t, RandomCrop):
@@ -52,10 +60,16 @@ def chain_params(transforms):
             p["scale_factor"], p["cls_num"] = t.scale_factor, t.cls_num
         else:
             raise NotImplementedError("transform %s is not lowered to rr_augment_frames" % type(t).__name__)
-    order = [c for c in (MultiScale, ToTensor, MaskIgnore, HorizontalFlip, RandomCrop, Normalize, ToHeatmap) if c in seen]
+    order = [c for c in (MultiScale, ToTensor, MaskIgnore, FillDuck, HorizontalFlip, RandomCrop, Normalize, ToHeatmap)
+             if c in seen]
     if [c for c in seen] != order:
-        raise NotImplementedError("the lowered chain is MultiScale, ToTensor, MaskIgnore, HorizontalFlip, RandomCrop, "
-                                  "Normalize, ToHeatmap in this order; got %s" % [c.__name__ for c in seen])
+        raise NotImplementedError("the lowered chain is MultiScale, ToTensor, MaskIgnore, FillDuck, HorizontalFlip, "
+                                  "RandomCrop, Normalize, ToHeatmap in this order; got %s" % [c.__name__ for c in seen])
+    if FillDuck in seen:
+        k = seen.index(FillDuck)
+        if seen[k - 1:k] != [MaskIgnore] or seen[k + 1:k + 2] != [HorizontalFlip] or k == 0:
+            raise NotImplementedError("FillDuck is lowered only between MaskIgnore and HorizontalFlip; got %s"
+                                      % [c.__name__ for c in seen])
     if p["mean"] is None:
         raise NotImplementedError("the lowered chain needs Normalize")
     if p["ignore_mean"] is not None and tuple(p["ignore_mean"]) != tuple(p["mean"]):
@@ -116,11 +130,22 @@ class _Rand:
 
 class Decision:
     """What the sampler decided for one sample."""
-    __slots__ = ("index", "scale", "flip", "dst_h", "dst_w", "crop_y0", "crop_x0", "annos", "rects", "redraws")
+    __slots__ = ("index", "scale", "flip", "dst_h", "dst_w", "crop_y0", "crop_x0", "annos", "rects", "redraws", "plan")
 
     def key(self):
+        plan = plan_of(self)
         return (self.index, self.scale, self.flip, self.dst_h, self.dst_w, self.crop_y0, self.crop_x0, self.redraws,
-                self.annos.numpy().tobytes(), self.rects.tobytes())
+                self.annos.numpy().tobytes(), self.rects.tobytes(), plan.key() if plan is not None else None)
+
+
+def plan_of(d):
+    """The decision's FillDuck plan, or None (a chain without FillDuck, no road map, or a hand-built Decision)."""
+    return getattr(d, "plan", None)
+
+
+def n_pastes(d):
+    plan = plan_of(d)
+    return 0 if plan is None else len(plan.pastes)
 
 
 class AugmentSampler:
@@ -142,14 +167,19 @@ class AugmentSampler:
             perm = np.concatenate([perm, perm[:pad]])
         return perm[self.rank::self.world_size]
 
-    def sample(self, annotations, src_h, src_w, epoch, index):
-        """annotations: the image's int64 [n,8] rows (not modified) -> Decision."""
+    def sample(self, annotations, src_h, src_w, epoch, index, roadmap=None):
+        """annotations: the image's int64 [n,8] rows (not modified); roadmap: uint8 [src_h,src_w] or None -> Decision.
+        With FillDuck in the chain and a road map, every draw attempt resizes and masks the map, plans the pastes
+        (functional.fill_duck_decide, from a generator of its own keyed by the attempt, so that the scale, flip and
+        crop draws are those of the chain without FillDuck) and appends the pasted boxes before the flip and the crop
+        decision: they steer RandomCrop as in the reference."""
         rng = np.random.default_rng([self.seed, self.rank, int(epoch), int(index)])
         rand = _Rand(rng)
         p = self.p
         d = Decision()
-        d.index, d.redraws = int(index), 0
-        for _ in range(50):
+        d.index, d.redraws, d.plan = int(index), 0, None
+        duck = p.get("fill_duck") if roadmap is not None else None
+        for attempt in range(50):
             d.scale = p["scales"][int(rng.integers(0, len(p["scales"])))]
             d.flip = bool(rng.random() <= p["flip_p"]) if p["flip_p"] > 0 else False
             d.dst_h, d.dst_w = F.scaled_size(src_h, src_w, d.scale)
@@ -160,6 +190,15 @@ class AugmentSampler:
                 t = t[~(t[:, 5] == p["ignore_idx"]), :]
             else:
                 d.rects = np.zeros((0, 4), np.int32)
+            if duck is not None:
+                road = torch.from_numpy(F.nearest_resize(roadmap, d.dst_h, d.dst_w)).float() / 255
+                for y0, y1, x0, x1 in d.rects.tolist():                     # functional.py:308-309
+                    road[y0:y1, x0:x1] = 0
+                fd_rng = np.random.default_rng([self.seed, self.rank, int(epoch), int(index), attempt, FILL_DUCK_TAG])
+                d.plan = F.fill_duck_decide(t, road, duck["cls_list"], duck["factor"], d.dst_h, d.dst_w,
+                                            F.GeneratorRand(fd_rng))
+                if d.plan.new_annos.size(0):
+                    t = torch.cat((t, d.plan.new_annos))
             if d.flip:
                 F.flip_annos(t, d.dst_w)
             if self.crop is None:
@@ -216,14 +255,36 @@ def pack_batch(items, src_out=None):
     return src[:max(total, 3)], params, rects, rect_off
 
 
+def pack_pastes(decisions):
+    """[Decision] -> (pastes int32 [K,12], paste_off int32 [B+1], largest scaled frame in pixels, largest object in
+    pixels).  Every rectangle is checked against its frame here, before anything is launched."""
+    tabs, off = [], np.zeros(len(decisions) + 1, np.int32)
+    for i, d in enumerate(decisions):
+        tab = plan_of(d).pastes if n_pastes(d) else np.zeros((0, T_WORDS), np.int32)
+        sy, sx, sh, sw, dy, dx, oh, ow = (tab[:, k].astype(np.int64) for k in range(8))
+        ok = ((sy >= 0) & (sx >= 0) & (sh > 0) & (sw > 0) & (sy + sh <= d.dst_h) & (sx + sw <= d.dst_w) &
+              (dy >= 0) & (dx >= 0) & (oh > 0) & (ow > 0) & (dy + oh <= d.dst_h) & (dx + ow <= d.dst_w))
+        if not ok.all():
+            raise RuntimeError("paste plan of image index %d leaves its %dx%d frame" % (d.index, d.dst_w, d.dst_h))
+        tabs.append(tab)
+        off[i + 1] = off[i] + len(tab)
+    pastes = np.concatenate(tabs, 0).astype(np.int32).reshape(-1, T_WORDS)
+    canvas = max(d.dst_h * d.dst_w for d in decisions)
+    scratch = int((pastes[:, 6].astype(np.int64) * pastes[:, 7]).max()) if len(pastes) else 1
+    return pastes, off, canvas, scratch
+
+
 def host_chain(image, annotations, d, params, out_h, out_w):
     """The reference chain on the host for decision `d`: PIL image + int64 annotations -> float32 [3,out_h,out_w].
-    (resize -> to_tensor -> mask_ignore -> flip -> pad/crop -> normalize; the annotations of the batch are d.annos.)"""
+    (resize -> to_tensor -> mask_ignore -> the decision's pastes -> flip -> pad/crop -> normalize; the annotations of
+    the batch are d.annos.)"""
     a = annotations.copy()
     img, a = F.resize((image, a), d.scale)[:2]
     img, t = F.img_to_tensor(img), F.annos_to_tensor(a)
     if params["ignore_idx"] is not None:
         img, t = F.mask_ignore((img, t), params["ignore_mean"], params["ignore_idx"])
+    if plan_of(d) is not None:
+        F.apply_paste_plan(img, d.plan)
     if d.flip:
         img = F.flip_img(img)
     h, w = img.shape[-2:]
@@ -279,8 +340,12 @@ class _AugmentLoader:
         return res
 
     def _decide(self, epoch, index):
-        image, annotations, name = self.dataset.load(index)
-        d = self.sampler.sample(annotations, image.size[1], image.size[0], epoch, index)
+        loaded = self.dataset.load(index)
+        image, annotations, name = loaded[:3]
+        roadmap = loaded[3] if len(loaded) > 3 else None
+        if roadmap is not None and roadmap.shape != (image.size[1], image.size[0]):
+            raise ValueError("road map of %s is %s, the image %s" % (name, roadmap.shape[::-1], image.size))
+        d = self.sampler.sample(annotations, image.size[1], image.size[0], epoch, index, roadmap)
         return image, annotations, name, d
 
     def close(self):
@@ -309,7 +374,12 @@ class DeviceAugmentLoader(_AugmentLoader):
     """Decode and decide on the threads; windows, records and annotations go through two pinned staging slots to two
     device slots, one batch ahead on a copy stream; get_batch() makes the compute stream wait for the batch's copy event,
     runs rr_augment_frames and rr_ctnet_targets there and starts the next batch's copy, which may overwrite the other
-    slot only after the work that read it has been enqueued (the copy stream waits for the compute stream)."""
+    slot only after the work that read it has been enqueued (the copy stream waits for the compute stream).
+
+    With FillDuck in the chain and road maps in the dataset, a sample whose plan has pastes ships its whole source frame
+    and its paste table, and a batch with such a sample runs rr_augment_frames_pasted (its unpasted samples still ship
+    windows; their pixels are bit-identical on either kernel).  Staging, device slots, the canvas and the scratch are
+    sized once, from the largest frame of the dataset at the largest scale."""
 
     def __init__(self, dataset, params, batch_size, **kw):
         super().__init__(dataset, params, batch_size, **kw)
@@ -320,7 +390,24 @@ class DeviceAugmentLoader(_AugmentLoader):
         r_cap = max(b * max(int((a[:, 5] == 0).sum()) for a in dataset.annotations), 1)
         # a crop of h x w reads at most h+1 rows and w+1 columns of the source at scale factors >= 1
         self.src_cap = b * (self.out_h + 2) * (self.out_w + 2) * 3
-        self.meta_words = b * P_WORDS + (b + 1) + 4 * r_cap + b
+        self.pasting = params.get("fill_duck") is not None and bool(getattr(dataset, "with_road_map", False))
+        self.k_cap, self.canvas_pix, self.work = 0, 0, None
+        if self.pasting:
+            from PIL import Image
+            from rrnet_amd import ops
+            sizes = set()
+            for k in range(len(dataset)):
+                with Image.open(dataset.image_path(k)) as im:
+                    sizes.add(im.size)
+            smax = max(params["scales"])
+            self.src_cap = max(self.src_cap, b * max(w * h for w, h in sizes) * 3)
+            self.canvas_pix = max(F.scaled_size(h, w, smax)[0] * F.scaled_size(h, w, smax)[1] for w, h in sizes)
+            # total_n = max(int(factor * road pixels), 5) pastes per frame (functional.py:408)
+            self.k_cap = b * max(int(params["fill_duck"]["factor"] * self.canvas_pix) + 1, 5)
+            self.m_cap += 2 * (self.k_cap // b)             # a pair paste adds two rows
+            # an object that does not fit its frame aborts the plan, so no object is larger than the largest frame
+            self.work = ops.paste_workspace(b, self.canvas_pix, self.canvas_pix, self.device)
+        self.meta_words = b * P_WORDS + (b + 1) + 4 * r_cap + b + (b + 1) + T_WORDS * self.k_cap
         self.r_cap = r_cap
         self.pinned = [(torch.empty(self.src_cap, dtype=torch.uint8).pin_memory(),
                         torch.empty(self.meta_words, dtype=torch.int32).pin_memory(),
@@ -336,6 +423,8 @@ class DeviceAugmentLoader(_AugmentLoader):
         image, annotations, name, d = self._decide(epoch, index)
         src_w, src_h = image.size
         win = source_window(d, src_h, src_w, self.out_h, self.out_w, self.taps)
+        if n_pastes(d):                                    # a paste may read any pixel of the frame
+            win = (0, 0, src_h, src_w) + win[4:]
         y0, x0, wh, ww = win[:4]
         pix = np.asarray(image.crop((x0, y0, x0 + ww, y0 + wh)), dtype=np.uint8)
         return d, (src_h, src_w, win, pix), name
@@ -359,6 +448,16 @@ class DeviceAugmentLoader(_AugmentLoader):
         meta[o1:o2] = rect_off
         meta[o2:o2 + rects.size] = rects.reshape(-1)
         meta[o3:o3 + b] = [int(r[0].annos.size(0)) for r in res]
+        npaste = 0
+        if self.pasting:
+            pastes, paste_off, canvas, scratch = pack_pastes([r[0] for r in res])
+            npaste = len(pastes)
+            if npaste > self.k_cap or canvas > self.canvas_pix or scratch > self.canvas_pix:
+                raise RuntimeError("paste plans exceed the staging slot or the canvas")
+            o4 = o3 + b
+            o5 = o4 + b + 1
+            meta[o4:o5] = paste_off
+            meta[o5:o5 + pastes.size] = pastes.reshape(-1)
         annos = p_annos[:b * m * 8].view(b, m, 8)
         annos.zero_()
         for k, r in enumerate(res):
@@ -374,7 +473,7 @@ class DeviceAugmentLoader(_AugmentLoader):
             ev = torch.cuda.Event()
             ev.record(self.copy_stream)
         self.events[slot] = ev
-        self.info[slot] = (int(src.size), m, int(rects.shape[0]), taps, [r[2] for r in res])
+        self.info[slot] = (int(src.size), m, int(rects.shape[0]), taps, [r[2] for r in res], npaste)
 
     def get_batch(self):
         from rrnet_amd import ops
@@ -384,14 +483,21 @@ class DeviceAugmentLoader(_AugmentLoader):
         cur = torch.cuda.current_stream(self.device)
         cur.wait_event(self.events[slot])
         d_src, d_meta, d_annos = self.slots[slot]
-        nbytes, m, nrect, taps, names = self.info[slot]
+        nbytes, m, nrect, taps, names, npaste = self.info[slot]
         b = self.bs
         o1 = b * P_WORDS
         o2 = o1 + b + 1
         o3 = o2 + 4 * self.r_cap
-        imgs = ops.augment_frames(d_src[:nbytes], d_meta[:o1].view(b, P_WORDS),
-                                  d_meta[o2:o2 + 4 * nrect].view(nrect, 4) if nrect else None, d_meta[o1:o2], taps,
-                                  self.mean, self.std, self.out_h, self.out_w)
+        rects = d_meta[o2:o2 + 4 * nrect].view(nrect, 4) if nrect else None
+        if npaste:
+            o4 = o3 + b
+            o5 = o4 + b + 1
+            imgs = ops.augment_frames_pasted(d_src[:nbytes], d_meta[:o1].view(b, P_WORDS), rects, d_meta[o1:o2], taps,
+                                             d_meta[o5:o5 + T_WORDS * npaste].view(npaste, T_WORDS), d_meta[o4:o5],
+                                             self.mean, self.std, self.out_h, self.out_w, work=self.work)
+        else:
+            imgs = ops.augment_frames(d_src[:nbytes], d_meta[:o1].view(b, P_WORDS), rects, d_meta[o1:o2], taps,
+                                      self.mean, self.std, self.out_h, self.out_w)
         annos = d_annos[:b * m * 8].view(b, m, 8).clone()      # the criterion converts them to xyxy in place
         hm, wh, ind, off, mask = ops.ctnet_targets(annos, d_meta[o3:o3 + b], self.out_h, self.out_w,
                                                    self.p["scale_factor"], self.p["cls_num"])
@@ -455,7 +561,9 @@ def make_real_dataloaders(cfg, data_root):
     from .drones_det import DronesDET
     rank, world = getattr(cfg.Distributed, "rank", 0), max(int(getattr(cfg.Distributed, "world_size", 1)), 1)
     taps = TapCache()
-    train = DeviceAugmentLoader(DronesDET(data_root, cfg.Train.transforms, 'train'), chain_params(cfg.Train.transforms),
+    params = chain_params(cfg.Train.transforms)
+    road = bool(getattr(cfg.Train, "with_road", False)) if params["fill_duck"] is not None else False
+    train = DeviceAugmentLoader(DronesDET(data_root, cfg.Train.transforms, 'train', with_road_map=road), params,
                                 cfg.Train.batch_size, seed=cfg.seed, rank=rank, world_size=world,
                                 num_workers=cfg.Train.num_workers, taps=taps)
     val = None

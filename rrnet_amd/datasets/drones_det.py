@@ -8,7 +8,10 @@ Differences from the reference, all on purpose:
     (transforms.py:96: torch.randint(0, 0, ...)); `dropped` lists their names (other splits keep every image);
   * file names are sorted, so that an index means the same image on every rank and machine (os.listdir order is not
     defined);
-  * there is no road map (FillDuck, its only consumer, is out of scope): a sample is (image, annotations)."""
+  * with_road_map=True reads `<root>/<split>/roadmap/<name>.jpg` with PIL and keeps its blue channel (the reference
+    takes channel 0 of cv2's BGR decode, drones_det.py:44-50; the two JPEG decoders may differ by a grey level, which a
+    0/255 road mask does not notice); a missing file gives None, which FillDuck hands through.  A sample is then
+    (image, annotations, road map); without the flag it is (image, annotations) as before."""
 import os
 
 import numpy as np
@@ -33,8 +36,8 @@ def parse_annotations(path):
 
 class DronesDET(torch.utils.data.Dataset):
     def __init__(self, root_dir, transforms=None, split='train', with_road_map=False):
-        if with_road_map:
-            raise NotImplementedError("DronesDET: road maps (FillDuck) are not part of this data layer")
+        self.with_road_map = bool(with_road_map)
+        self.roadmap_dir = os.path.join(root_dir, split, 'roadmap')
         self.images_dir = os.path.join(root_dir, split, 'images')
         self.annotations_dir = os.path.join(root_dir, split, 'annotations')
         self.transforms = transforms
@@ -53,14 +56,25 @@ class DronesDET(torch.utils.data.Dataset):
     def image_path(self, item):
         return os.path.join(self.images_dir, self.mdf[item] + '.jpg')
 
-    def load(self, item):
-        """-> (PIL RGB image, a fresh copy of the int64 annotations, name); the transforms write into the copy."""
+    def load_roadmap(self, item):
+        """-> uint8 [H,W] (the blue channel of the road-map JPEG) or None where the file is missing."""
         from PIL import Image
-        return Image.open(self.image_path(item)).convert("RGB"), self.annotations[item].copy(), self.mdf[item]
+        path = os.path.join(self.roadmap_dir, self.mdf[item] + '.jpg')
+        if not os.path.isfile(path):
+            return None
+        return np.ascontiguousarray(np.asarray(Image.open(path).convert("RGB"), dtype=np.uint8)[:, :, 2])
+
+    def load(self, item):
+        """-> (PIL RGB image, a fresh copy of the int64 annotations, name[, road map when with_road_map]); the
+        transforms write into the copy."""
+        from PIL import Image
+        out = Image.open(self.image_path(item)).convert("RGB"), self.annotations[item].copy(), self.mdf[item]
+        return out + (self.load_roadmap(item),) if self.with_road_map else out
 
     def __getitem__(self, item):
-        image, annotation, name = self.load(item)
-        sample = (image, annotation)
+        loaded = self.load(item)
+        image, annotation, name = loaded[:3]
+        sample = (image, annotation) + tuple(loaded[3:])
         if self.transforms:
             sample = self.transforms(sample)
         return tuple(sample) + (name,)

@@ -1,11 +1,13 @@
 """Transform classes of the reference's datasets/transforms/transforms.py: the training chain of
-configs/rrnet_config.py:40-49 without FillDuck (MultiScale, ToTensor, MaskIgnore, HorizontalFlip, RandomCrop,
-Normalize, ToHeatmap), with the reference's constructor and call signatures, on host tensors.  A sample is the tuple
-(image, annotations[, ...]); elements past the second are handed through.  ToTensor drops the road map: its only
-consumer, FillDuck, is out of scope.
+configs/rrnet_config.py:40-49 (MultiScale, ToTensor, MaskIgnore, FillDuck, HorizontalFlip, RandomCrop, Normalize,
+ToHeatmap), with the reference's constructor and call signatures, on host tensors.  A sample is the tuple
+(image, annotations[, road map, ...]); the road map (uint8 [H,W] or None, third element when the dataset loads one) is
+resized by MultiScale, made a tensor by ToTensor, masked by MaskIgnore and consumed by FillDuck.  Two-element samples
+pass through every class as before.
 
 These classes are the host path.  DeviceAugmentLoader (rrnet_amd/datasets/augment.py) reads the chain's parameters
-from the instances in `cfg.Train.transforms` and lowers everything that touches pixels to rr_augment_frames."""
+from the instances in `cfg.Train.transforms` and lowers everything that touches pixels to rr_augment_frames and
+rr_augment_frames_pasted."""
 import random
 
 import numpy as np
@@ -66,10 +68,12 @@ class MultiScale:
 
 
 class ToTensor:
-    """transforms.py:27-29: PIL image -> float32 [3,H,W] in [0,1], annotations -> float32 tensor."""
+    """transforms.py:27-29: PIL image -> float32 [3,H,W] in [0,1], annotations -> float32 tensor, road map (when the
+    sample carries one) -> float32 [H,W] / 255 or None."""
 
     def __call__(self, data):
-        return F.img_to_tensor(data[0]), F.annos_to_tensor(data[1])
+        out = F.img_to_tensor(data[0]), F.annos_to_tensor(data[1])
+        return out + (F.roadmap_to_tensor(data[2]),) if len(data) > 2 else out
 
 
 class MaskIgnore:
@@ -82,6 +86,21 @@ class MaskIgnore:
     def __call__(self, data):
         assert isinstance(data[0], torch.Tensor) and isinstance(data[1], torch.Tensor)
         return F.mask_ignore(data, self.mean, self.ignore_idx)
+
+
+class FillDuck:
+    """transforms.py:173-179, the paper's adaptive resampling: copies objects of `cls_list`, rescales them by a depth
+    heuristic and pastes them onto road pixels.  (img, annos, road map) -> (img, annos); without a road map (None, or
+    a two-element sample) the data comes back unchanged, as in the reference, whose `except` swallows the failure."""
+
+    def __init__(self, cls_list=(1, 2, 3, 7, 8, 10), factor=0.00005):
+        self.cls_list = torch.tensor(cls_list).unsqueeze(0)
+        self.factor = factor
+
+    def __call__(self, data):
+        if len(data) < 3 or data[2] is None:
+            return data[0], data[1]
+        return F.fill_duck(data[:3], self.cls_list, self.factor)
 
 
 class HorizontalFlip:

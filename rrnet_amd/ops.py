@@ -1407,6 +1407,57 @@ def augment_frames(src, params, rects, rect_off, taps, mean, std, out_h, out_w):
     return out
 
 
+PASTE_WORDS = 12           # RR_PASTE_WORDS: int32 words of one row of a paste table
+
+
+def paste_workspace(b, canvas_pix, scratch_pix, device):
+    """(canvas [b, canvas_pix rounded up to 4, 3], scratch [b, scratch_pix, 3]) for augment_frames_pasted."""
+    return (torch.empty((b, (max(int(canvas_pix), 1) + 3) // 4 * 4, 3), dtype=torch.float32, device=device),
+            torch.empty((b, max(int(scratch_pix), 1), 3), dtype=torch.float32, device=device))
+
+
+def augment_frames_pasted(src, params, rects, rect_off, taps, pastes, paste_off, mean, std, out_h, out_w,
+                          canvas_pix=None, scratch_pix=None, stages=7, work=None):
+    """rr_augment_frames_pasted: rr_augment_frames with FillDuck's ordered pastes between the ignore step and the flip.
+    Arguments as augment_frames, plus pastes int32 [K,12] (None or empty: none) and paste_off int32 [B+1]; a frame with
+    pastes ships its whole source frame as its window.  canvas_pix / scratch_pix: the largest scaled frame (dst_h*dst_w)
+    and the largest pasted object (out_h*out_w) of the batch in pixels; left None they are read back from the device
+    records (a synchronisation the loader avoids by passing them).  The canvas and the scratch come from the caching
+    allocator, which hands the same blocks back batch after batch.  `stages` / `work` (a paste_workspace kept between
+    calls) exist for timing one stage.  -> [B,3,out_h,out_w] in NHWC memory."""
+    _C.require_cuda(src, params, rects, rect_off, taps, pastes, paste_off, mean, std)
+    assert src.dtype == torch.uint8 and src.is_contiguous() and src.dim() == 1
+    assert params.dtype == torch.int32 and params.is_contiguous() and params.shape[1] == AUGMENT_PARAMS
+    b = params.shape[0]
+    assert rect_off.dtype == torch.int32 and rect_off.numel() == b + 1
+    assert paste_off.dtype == torch.int32 and paste_off.numel() == b + 1 and paste_off.is_contiguous()
+    assert taps.dtype == torch.int32 and taps.is_contiguous() and taps.shape[1] == 3
+    assert mean.dtype == torch.float32 and std.dtype == torch.float32 and mean.numel() == 3 and std.numel() == 3
+    if rects is not None and rects.numel() == 0:
+        rects = None
+    assert rects is None or (rects.dtype == torch.int32 and rects.is_contiguous() and rects.shape[1] == 4)
+    if pastes is None or pastes.numel() == 0:
+        pastes = torch.zeros((1, PASTE_WORDS), dtype=torch.int32, device=src.device)
+    assert pastes.dtype == torch.int32 and pastes.is_contiguous() and pastes.shape[1] == PASTE_WORDS
+    if work is None and canvas_pix is None:
+        host = params.cpu()
+        canvas_pix = int((host[:, 6].long() * host[:, 7].long()).max())
+    if work is None and scratch_pix is None:
+        host = pastes.cpu()
+        scratch_pix = int((host[:, 6].long() * host[:, 7].long()).max())
+    canvas, scratch = work if work is not None else paste_workspace(b, canvas_pix, scratch_pix, src.device)
+    canvas_pix, scratch_pix = canvas.shape[1], scratch.shape[1]
+    assert canvas.shape == (b, canvas_pix, 3) and scratch.shape == (b, scratch_pix, 3) and canvas_pix % 4 == 0
+    assert canvas.dtype == scratch.dtype == torch.float32 and canvas.is_contiguous() and scratch.is_contiguous()
+    out = empty_nhwc(b, 3, out_h, out_w, src.device)
+    _C.check(_C.fn("rr_augment_frames_pasted")(_C.ptr(src), src.numel(), _C.ptr(params), _C.ptr(rects), _C.ptr(rect_off),
+                                               _C.ptr(taps), taps.shape[0], _C.ptr(pastes), _C.ptr(paste_off),
+                                               _C.ptr(mean), _C.ptr(std), _C.ptr(canvas), canvas_pix, _C.ptr(scratch),
+                                               scratch_pix, _C.ptr(out), b, out_h, out_w, int(stages), _C.stream()),
+             "rr_augment_frames_pasted")
+    return out
+
+
 def refine_boxes(rois, reg, scores, clses, seg_off, scale, score_thr):
     """generate_bbox + score filter + xywh->xyxy for every (frame, class) segment of the packed RoI list.
     -> boxes6 [R,6] (kept rows at the front of each segment's range), seg_len int32 [nseg]."""

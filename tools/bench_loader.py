@@ -8,7 +8,12 @@ regions from a seeded generator) and reports, per crop size (512x512 and 1024x10
 Loader rates are medians over --runs timed windows of --batches batches each, after a warm-up window; each window ends
 in a device synchronise.  One JSON line on stdout; --out writes the same object to a file.
 
-  python tools/bench_loader.py [--images 48] [--batches 12] [--runs 3] [--threads 16] [--out profiles/loader.json]"""
+--fill-duck measures the full chain instead: every image gets a generated road map (a road band across the lower
+half), the chain holds FillDuck, and the kernel entry is rr_augment_frames_pasted with the time of each of its three
+stages (canvas, paste, finish) and of the whole call.
+
+  python tools/bench_loader.py [--images 48] [--batches 12] [--runs 3] [--threads 16] [--out profiles/loader.json]
+  python tools/bench_loader.py --fill-duck --crops 1024 --out profiles/loader_fillduck.json"""
 import argparse
 import json
 import os
@@ -46,11 +51,25 @@ def write_dataset(root, n, size=(1360, 765), seed=219):
             f.write("".join(",".join(str(v) for v in r) + "\n" for r in rows))
 
 
-def chain(crop):
-    from rrnet_amd.datasets.transforms import (Compose, HorizontalFlip, MaskIgnore, MultiScale, Normalize, RandomCrop,
-                                               ToHeatmap, ToTensor)
-    return Compose([MultiScale(scale=(1, 1.15, 1.25, 1.35, 1.5)), ToTensor(), MaskIgnore(MEAN), HorizontalFlip(),
-                    RandomCrop((crop, crop)), Normalize(MEAN, STD), ToHeatmap(scale_factor=4)])
+def write_roadmaps(root, n, size=(1360, 765)):
+    """A road band across the lower half of every frame."""
+    from PIL import Image
+    w, h = size
+    os.makedirs(os.path.join(root, "train", "roadmap"))
+    road = np.zeros((h, w, 3), np.uint8)
+    road[h // 2:] = 255
+    for i in range(n):
+        Image.fromarray(road).save(os.path.join(root, "train", "roadmap", "%06d.jpg" % i), quality=90)
+
+
+def chain(crop, fill_duck=False):
+    from rrnet_amd.datasets.transforms import (Compose, FillDuck, HorizontalFlip, MaskIgnore, MultiScale, Normalize,
+                                               RandomCrop, ToHeatmap, ToTensor)
+    ts = [MultiScale(scale=(1, 1.15, 1.25, 1.35, 1.5)), ToTensor(), MaskIgnore(MEAN), HorizontalFlip(),
+          RandomCrop((crop, crop)), Normalize(MEAN, STD), ToHeatmap(scale_factor=4)]
+    if fill_duck:
+        ts.insert(3, FillDuck())
+    return Compose(ts)
 
 
 def loader_rate(loader, batch, batches, runs):
@@ -104,6 +123,62 @@ def kernel_time(ds, params, batch, crop, reps):
             "bytes_read_windows": int(src.size), "write_GBps": out_bytes / med / 1e6}
 
 
+def _timed(fn, reps):
+    import torch
+    ms = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    return {"ms_median": statistics.median(ms), "ms_min": min(ms), "ms_max": max(ms)}
+
+
+def pasted_kernel_time(ds, params, batch, crop, reps):
+    """One batch of whole frames and their paste plans resident on the device; rr_augment_frames_pasted stage by stage
+    (the canvas stage restores what the paste stage changes, so each timed paste starts from the same canvas)."""
+    import torch
+    from rrnet_amd import ops
+    from rrnet_amd.datasets import augment as A
+    taps = A.TapCache()
+    sampler = A.AugmentSampler(params, seed=219)
+    items, ds_ = [], []
+    for i in range(batch):
+        image, annos, _, road = ds.load(i % len(ds))
+        d = sampler.sample(annos, image.size[1], image.size[0], 0, i, road)
+        win = A.source_window(d, image.size[1], image.size[0], crop, crop, taps)
+        if A.n_pastes(d):
+            win = (0, 0, image.size[1], image.size[0]) + win[4:]
+        y0, x0, wh, ww = win[:4]
+        items.append((d, image.size[1], image.size[0], win, np.asarray(image.crop((x0, y0, x0 + ww, y0 + wh)), dtype=np.uint8)))
+        ds_.append(d)
+    src, prm, rects, rect_off = A.pack_batch(items)
+    pastes, paste_off, canvas_pix, scratch_pix = A.pack_pastes(ds_)
+    dev = torch.device("cuda", 0)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    work = ops.paste_workspace(batch, canvas_pix, scratch_pix, dev)
+    args = (t(src.copy()), t(prm), t(rects) if len(rects) else None, t(rect_off), taps.device(dev),
+            t(pastes) if len(pastes) else None, t(paste_off), torch.tensor(MEAN, device=dev),
+            torch.tensor(STD, device=dev), crop, crop)
+    run = lambda stages: ops.augment_frames_pasted(*args, stages=stages, work=work)
+    for _ in range(5):
+        run(7)
+    torch.cuda.synchronize()
+    out = {"pastes": int(len(pastes)), "pastes_per_frame": np.diff(paste_off).tolist(),
+           "depth": [d.plan.depth if d.plan is not None else 0 for d in ds_],
+           "canvas_pixels_per_frame": int(canvas_pix), "largest_object_pixels": int(scratch_pix),
+           "bytes_read_frames": int(src.size), "all": _timed(lambda: run(7), reps), "canvas": _timed(lambda: run(1), reps)}
+    ms = []
+    for _ in range(reps):
+        run(1)
+        ms.append(_timed(lambda: run(2), 1)["ms_median"])
+    out["paste"] = {"ms_median": statistics.median(ms), "ms_min": min(ms), "ms_max": max(ms)}
+    out["finish"] = _timed(lambda: run(4), reps)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=48)
@@ -114,6 +189,7 @@ def main():
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--crops", type=int, nargs="+", default=[512, 1024])
     ap.add_argument("--out", default=None)
+    ap.add_argument("--fill-duck", action="store_true", help="the full chain with FillDuck on generated road maps")
     a = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -121,14 +197,16 @@ def main():
     from rrnet_amd.datasets import augment as A
     from rrnet_amd.datasets.drones_det import DronesDET
     res = {"tool": "bench_loader", "frame": [1360, 765], "images": a.images, "batch": a.batch, "threads": a.threads,
-           "batches_per_window": a.batches, "windows": a.runs, "crops": {}}
+           "batches_per_window": a.batches, "windows": a.runs, "fill_duck": a.fill_duck, "crops": {}}
     with tempfile.TemporaryDirectory() as root:
         t0 = time.perf_counter()
         write_dataset(root, a.images)
+        if a.fill_duck:
+            write_roadmaps(root, a.images)
         res["dataset_write_s"] = time.perf_counter() - t0
         for crop in a.crops:
-            tr = chain(crop)
-            ds = DronesDET(root, tr, "train")
+            tr = chain(crop, a.fill_duck)
+            ds = DronesDET(root, tr, "train", with_road_map=a.fill_duck)
             p = A.chain_params(tr)
             entry = {}
             for name, cls in (("host_loader", A.HostAugmentLoader), ("device_loader", A.DeviceAugmentLoader)):
@@ -139,7 +217,10 @@ def main():
                     loader.close()
                 entry[name] = {"images_per_s_median": statistics.median(rates), "images_per_s": rates,
                                "redraws": loader.redraws}
-            entry["rr_augment_frames"] = kernel_time(ds, p, a.batch, crop, a.reps)
+            if a.fill_duck:
+                entry["rr_augment_frames_pasted"] = pasted_kernel_time(ds, p, a.batch, crop, a.reps)
+            else:
+                entry["rr_augment_frames"] = kernel_time(ds, p, a.batch, crop, a.reps)
             res["crops"]["%dx%d" % (crop, crop)] = entry
     line = json.dumps(res)
     print(line)
