@@ -550,6 +550,38 @@ int rr_finalize_frames(const float *boxes6, const int *seg_off, const int *n_out
  * 278: the torch.sort calls around _ext_nms in the multi-scale evaluation); n <= 16384, out6 != rows6. */
 int rr_sort_rows_by_score(const float *rows6, int n, float *out6, hipStream_t stream);
 
+/* ---- evaluation: VisDrone AP / AR on the device ------------------------------------------------ *
+ * rr_eval_match: utils/metrics/metrics.py:51-131 (`get_tp` with its `bbox_iou` calls) for f frames in one launch, one
+ *   workgroup per frame.
+ *   dets [f,dmax,6] = x,y,w,h,score,cls rows already in evaluation order (score descending) and cut to max_det_num,
+ *   det_len [f]; gts [f,gmax,6] = the first six columns of the VisDrone rows (cls == 0: ignored region), gt_len [f];
+ *   thresholds [t] (the host's own tensor values, t <= RR_EVAL_MAX_THRESHOLDS).  Lengths are clamped to dmax / gmax.
+ *   1. with an ignored region in the frame, a ground truth leaves unless every inter/area(gt) over the ignored regions
+ *      is < 0.5 (0.5 leaves; zero area gives 0/0 = NaN and leaves);  2. a detection leaves by the same rule on
+ *      inter/area(det);  3. target_count [f,cls_num-1] = ground truths left per class 1..cls_num-1; counted [f,dmax] = 1
+ *      for a detection that stayed, has a class in 1..cls_num-1 and meets a ground truth of that class in its frame
+ *      (detections of a class the frame does not hold are dropped, not false positives: the reference's rule);
+ *   4. greedy matching per class in row order, independently per threshold: the detection takes the ground truth of
+ *      largest IoU among those of its class with iou - thr >= 0 not yet taken at that threshold, ties to the lowest
+ *      ground-truth index; flag_bits [f,dmax] bit t = true positive at threshold t (0 for rows not counted).
+ *   IoU in fp32 in bbox_iou's operation order (:10-49), correctly rounded division, no fused multiply-add: the flags
+ *   equal the host's.  gmax <= RR_EVAL_MAX_GT (the frame's ground truth lives in LDS), cls_num <= RR_EVAL_MAX_CLASSES.
+ * rr_eval_ap: utils/metrics/metrics.py:133-174 (`calculate_ap_rc`).  flag_bits [nrows]: the counted detections' words
+ *   class by class, each class sorted by confidence descending; seg_off [c+1] its row offsets; target_count,
+ *   in_img_count [c] summed over the frames.  Per (class, threshold): cumulative true positives, prec = cum/(i+1), rec =
+ *   cum/max(count,1) as fp32 quotients, the precision envelope (reverse running maximum, trailing sentinel 0), the sum of
+ *   (rec_i - rec_{i-1}) * env_i where recall rises (fp32 terms, summed in double) and the largest recall; then the
+ *   in_img_count weighting.  ap [t], rc [1]; classes with target_count 0 are skipped, no class at all gives NaN.
+ *   work: 2*c*t floats of device scratch. */
+#define RR_EVAL_MAX_GT 2048
+#define RR_EVAL_MAX_THRESHOLDS 16
+#define RR_EVAL_MAX_CLASSES 64
+int rr_eval_match(const float *dets, const int *det_len, const float *gts, const int *gt_len, const float *thresholds,
+                  int f, int dmax, int gmax, int t, int cls_num, int *flag_bits, unsigned char *counted,
+                  int *target_count, hipStream_t stream);
+int rr_eval_ap(const int *flag_bits, long nrows, const int *seg_off, const int *target_count, const int *in_img_count,
+               int c, int t, float *work, float *ap, float *rc, hipStream_t stream);
+
 /* ---- RoIAlign --------------------------------------------------------------------------- *
  * torchvision.ops.roi_align(feat, rois, (ph,pw)) at models/rrnet.py:51 (spatial_scale 1,
  * sampling_ratio -1, legacy coordinates).  feat NHWC [b,h,w,c]; out NHWC [r,ph,pw,c]. */

@@ -1492,6 +1492,57 @@ def sort_rows_by_score(rows6):
     return out
 
 
+EVAL_MAX_GT = 2048            # RR_EVAL_MAX_GT: ground truths of one frame that rr_eval_match keeps in LDS
+EVAL_MAX_THRESHOLDS = 16      # RR_EVAL_MAX_THRESHOLDS
+
+
+def eval_match(dets, det_len, gts, gt_len, thresholds, cls_num=11):
+    """rr_eval_match: `get_tp` of utils/metrics/metrics.py for F frames in one launch.  dets float32 [F,Dmax,6] =
+    x,y,w,h,score,cls in evaluation order, det_len int32 [F]; gts float32 [F,Gmax,6] (cls 0 = ignored region), gt_len
+    int32 [F]; thresholds float32 [T] (the host's tensor, moved to the device, not recomputed); all on the device.
+    -> flag_bits int32 [F,Dmax] (bit t: true positive at threshold t), counted uint8 [F,Dmax], target_count int32
+    [F,cls_num-1]."""
+    assert dets.dim() == 3 and dets.shape[2] == 6 and gts.dim() == 3 and gts.shape[2] == 6
+    f, dmax, gmax, t = dets.shape[0], dets.shape[1], gts.shape[1], thresholds.numel()
+    if gmax > EVAL_MAX_GT:
+        raise ValueError("eval_match: at most %d ground truths per frame (Gmax), got %d" % (EVAL_MAX_GT, gmax))
+    if not 1 <= t <= EVAL_MAX_THRESHOLDS:
+        raise ValueError("eval_match: 1..%d thresholds, got %d" % (EVAL_MAX_THRESHOLDS, t))
+    _C.require_cuda(dets, det_len, gts, gt_len, thresholds)
+    assert dets.dtype == torch.float32 and dets.is_contiguous() and gts.dtype == torch.float32 and gts.is_contiguous()
+    assert gts.shape[0] == f and det_len.numel() == f and gt_len.numel() == f
+    assert det_len.dtype == torch.int32 and gt_len.dtype == torch.int32 and det_len.is_contiguous() and gt_len.is_contiguous()
+    assert thresholds.dtype == torch.float32 and thresholds.is_contiguous()
+    dev = dets.device
+    flag_bits = torch.empty((f, dmax), dtype=torch.int32, device=dev)
+    counted = torch.empty((f, dmax), dtype=torch.uint8, device=dev)
+    target_count = torch.empty((f, cls_num - 1), dtype=torch.int32, device=dev)
+    _C.check(_C.fn("rr_eval_match")(_C.ptr(dets), _C.ptr(det_len), _C.ptr(gts), _C.ptr(gt_len), _C.ptr(thresholds), f,
+                                    dmax, gmax, t, int(cls_num), _C.ptr(flag_bits), _C.ptr(counted),
+                                    _C.ptr(target_count), _C.stream()), "rr_eval_match")
+    return flag_bits, counted, target_count
+
+
+def eval_ap(flag_bits, seg_off, target_count, in_img_count, t):
+    """rr_eval_ap: `calculate_ap_rc`.  flag_bits int32 [N]: the counted detections' words class by class, each class
+    sorted by confidence descending; seg_off int32 [C+1]; target_count, in_img_count int32 [C] summed over the frames.
+    -> ap float32 [t], rc float32 [] on the device."""
+    _C.require_cuda(flag_bits, seg_off, target_count, in_img_count)
+    c = target_count.numel()
+    assert flag_bits.dtype == torch.int32 and flag_bits.is_contiguous() and flag_bits.dim() == 1
+    assert seg_off.dtype == torch.int32 and seg_off.is_contiguous() and seg_off.numel() == c + 1
+    assert target_count.dtype == torch.int32 and in_img_count.dtype == torch.int32 and in_img_count.numel() == c
+    assert target_count.is_contiguous() and in_img_count.is_contiguous()
+    dev = flag_bits.device
+    work = torch.empty(2 * c * int(t), dtype=torch.float32, device=dev)
+    ap = torch.empty(int(t), dtype=torch.float32, device=dev)
+    rc = torch.empty((), dtype=torch.float32, device=dev)
+    _C.check(_C.fn("rr_eval_ap")(_C.ptr(flag_bits), flag_bits.numel(), _C.ptr(seg_off), _C.ptr(target_count),
+                                 _C.ptr(in_img_count), c, int(t), _C.ptr(work), _C.ptr(ap), _C.ptr(rc), _C.stream()),
+             "rr_eval_ap")
+    return ap, rc
+
+
 def roi_spatial_order(rois, frame_off):
     """Per-frame spatial processing order of the packed RoI list (frame_off int32 [B+1], device) -> int32 [R]."""
     r = rois.shape[0]
