@@ -550,6 +550,30 @@ int rr_finalize_frames(const float *boxes6, const int *seg_off, const int *n_out
  * 278: the torch.sort calls around _ext_nms in the multi-scale evaluation); n <= 16384, out6 != rows6. */
 int rr_sort_rows_by_score(const float *rows6, int n, float *out6, hipStream_t stream);
 
+/* ---- detection on raw frames: the multi-scale evaluation body (operators/rrnet_operator.py:256-279), batched ---- *
+ * rr_prepare_frames: frames [n,h,w,3] uint8 RGB -> ToTensor -> Normalize(mean, stdv [3]) -> F.interpolate(bilinear,
+ *   align_corners=True) to oh x ow, out [n,oh,ow,3] float NHWC.  Bit-identical to rr_resize_bilinear_ac on the host-
+ *   normalised frame ((u8 / 255 - mean) / std in float32).
+ * rr_merge_scales: one scale's stage-2 inputs (rois [r,5], reg [r,4], scores, clses [r] as the model returns them;
+ *   frame_off [nframes+1] = row range of every frame) -> rows (x, y, w, h, score, cls+1) of `generate_bbox` (scale =
+ *   the model's stride, 4), kept when !filter or score > score_thr, x,y,w,h divided by div (IEEE), appended in row
+ *   order to frame f's block of merged [nframes,k,6] at count[f]; count [nframes] int32 is advanced on the device.
+ *   The caller zeroes count and fills merged's class column with a value outside the class range before the first
+ *   scale; one launch per scale, in the order of the concatenation.  k <= RR_DETECT_MAX_ROWS.
+ * rr_sort_frames_by_score: per frame, the first count[f] rows of rows6 [nframes,k,6] by score descending, ties in row
+ *   order (rr_sort_rows_by_score's keys and network, one workgroup per frame).  out_off NULL: out6 [nframes,k,6],
+ *   out_rows = nframes*k, rows behind count[f] are written as padding (class -1).  out_off [nframes+1] (exclusive
+ *   prefix of count): out6 [out_rows,6] packed, frame f at row out_off[f].  xyxy != 0 writes x2 = x + w, y2 = y + h
+ *   (the step in front of Soft-NMS, :222-223).  out6 != rows6. */
+#define RR_DETECT_MAX_ROWS 16384
+int rr_prepare_frames(const unsigned char *frames, const float *mean, const float *stdv, float *out, int n, int h,
+                      int w, int oh, int ow, hipStream_t stream);
+int rr_merge_scales(const float *rois, const float *reg, const float *scores, const float *clses,
+                    const int *frame_off, int nframes, int r, float scale, float div, int filter, float score_thr,
+                    float *merged, int *count, int k, hipStream_t stream);
+int rr_sort_frames_by_score(const float *rows6, const int *count, const int *out_off, int nframes, int k, int xyxy,
+                            float *out6, long out_rows, hipStream_t stream);
+
 /* ---- evaluation: VisDrone AP / AR on the device ------------------------------------------------ *
  * rr_eval_match: utils/metrics/metrics.py:51-131 (`get_tp` with its `bbox_iou` calls) for f frames in one launch, one
  *   workgroup per frame.

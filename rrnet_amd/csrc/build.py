@@ -25,6 +25,7 @@ PER_FILE = {
     "augment.hip": ["-ffp-contract=off"],
     "augment_paste.hip": ["-ffp-contract=off"],
     "evalmatch.hip": ["-ffp-contract=off"],
+    "detect.hip": ["-ffp-contract=off"],
 }
 
 

@@ -1,0 +1,249 @@
+// Batched multi-scale detection on raw frames for gfx950: what surrounds the model in the multi-scale evaluation body
+// (operators/rrnet_operator.py:256-279), for B equal-size frames per launch.
+//   rr_prepare_frames        uint8 RGB frames -> ToTensor -> Normalize -> F.interpolate(scale_factor, bilinear,
+//                            align_corners=True) in ONE gather (:262-263), NHWC fp32 network input
+//   rr_merge_scales          generate_bbox (:188-209) + `score > 0.01` (:266-267) + `pred_bbox[:, :4] / scale` (:268) of one
+//                            scale, appended per frame to the cross-scale concatenation (:271)
+//   rr_sort_frames_by_score  `torch.sort(pred_bbox[:, 4], descending=True)` (:272) per frame: the batched
+//                            rr_sort_rows_by_score
+// Built with -ffp-contract=off like refine.hip: every step of the box arithmetic is its own fp32 rounding and the division by
+// the scale is an IEEE division (the reference divides on the CPU).  The interpolation in rr_prepare_frames has to give the
+// bits of rr_resize_bilinear_ac: its fused steps are written as explicit fmas (prep_taps / prep_bilinear below).
+#include "common.h"
+#include "rrnet_hip.h"
+
+#define DET_THREADS 256
+#define DET_SORT_THREADS 1024
+#define DET_MAX_ROWS 16384          // rows of one frame the LDS sort holds (RR_DETECT_MAX_ROWS)
+
+namespace {
+
+// Source coordinates and the four-tap blend of resize_bilinear_ac_kernel (elementwise.hip).  That file is compiled with the
+// compiler's default contraction, and what the compiler makes of `ly = sy*h - y0` and of
+// `hy * (hx*v00 + lx*v01) + ly * (hx*v10 + lx*v11)` there is spelled out here with explicit fmas (this file is built with
+// -ffp-contract=off, so nothing else fuses): the fraction is one fma of the un-rounded product, each row blend fuses its
+// second product onto the rounded first one, and the two row terms are rounded separately before their sum.
+// tests/test_detect_gpu.py holds the two kernels to the same bits.
+// h / w: output row / column; H, W: source size; sy / sx: (H-1)/(OH-1), (W-1)/(OW-1) or 0.
+struct PrepTaps { int y0, y1, x0, x1; float ly, lx, hy, hx; };
+
+__device__ __forceinline__ PrepTaps prep_taps(float sy, float sx, int h, int w, int H, int W)
+{
+    PrepTaps t;
+    const float fh = (float)h, fw = (float)w;
+    const float fy = sy * fh, fx = sx * fw;
+    t.y0 = (int)fy, t.x0 = (int)fx;
+    t.y1 = t.y0 + (t.y0 < H - 1 ? 1 : 0), t.x1 = t.x0 + (t.x0 < W - 1 ? 1 : 0);
+    t.ly = __builtin_fmaf(sy, fh, -(float)t.y0), t.lx = __builtin_fmaf(sx, fw, -(float)t.x0);
+    t.hy = 1.f - t.ly, t.hx = 1.f - t.lx;
+    return t;
+}
+
+__device__ __forceinline__ float prep_bilinear(const PrepTaps &t, float v00, float v01, float v10, float v11)
+{
+    const float r0 = __builtin_fmaf(t.lx, v01, t.hx * v00);
+    const float r1 = __builtin_fmaf(t.lx, v11, t.hx * v10);
+    return t.hy * r0 + t.ly * r1;
+}
+
+// One thread per output pixel (three channels = 12 contiguous bytes of the NHWC output).
+__global__ __launch_bounds__(DET_THREADS) void prepare_frames_kernel(const uint8_t *__restrict__ src, const float *__restrict__ mean,
+                                                                     const float *__restrict__ stdv, float *__restrict__ out, int N,
+                                                                     int H, int W, int OH, int OW)
+{
+    __shared__ float lut[256 * 3];                       // lut[v*3 + c], as augment_frames_kernel builds it
+    for (int i = threadIdx.x; i < 256 * 3; i += DET_THREADS) {
+        const int v = i / 3, c = i - v * 3;
+        const float x = (float)v / 255.0f;               // ToTensor: uint8.float().div(255)
+        lut[i] = (x - mean[c]) / stdv[c];                // Normalize: sub, div
+    }
+    __syncthreads();
+    const long total = (long)N * OH * OW;
+    const float sy = OH > 1 ? (float)(H - 1) / (float)(OH - 1) : 0.f;
+    const float sx = OW > 1 ? (float)(W - 1) / (float)(OW - 1) : 0.f;
+    for (long p = (long)blockIdx.x * DET_THREADS + threadIdx.x; p < total; p += (long)gridDim.x * DET_THREADS) {
+        long q = p;
+        const int w = (int)(q % OW); q /= OW;
+        const int h = (int)(q % OH);
+        const int n = (int)(q / OH);
+        const PrepTaps t = prep_taps(sy, sx, h, w, H, W);
+        // (int)(sy*h) <= H-1 and (int)(sx*w) <= W-1 up to one rounding of the product: clamp what addresses memory
+        const int y0 = min(max(t.y0, 0), H - 1), y1 = min(max(t.y1, 0), H - 1);
+        const int x0 = min(max(t.x0, 0), W - 1), x1 = min(max(t.x1, 0), W - 1);
+        const uint8_t *b = src + (long)n * H * W * 3;
+        const uint8_t *p00 = b + ((long)y0 * W + x0) * 3, *p01 = b + ((long)y0 * W + x1) * 3;
+        const uint8_t *p10 = b + ((long)y1 * W + x0) * 3, *p11 = b + ((long)y1 * W + x1) * 3;
+        float *o = out + p * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            o[c] = prep_bilinear(t, lut[p00[c] * 3 + c], lut[p01[c] * 3 + c], lut[p10[c] * 3 + c], lut[p11[c] * 3 + c]);
+    }
+}
+
+// One workgroup per frame: rows [frame_off[f], frame_off[f+1]) of one scale's packed stage-2 inputs -> generate_bbox rows
+// (x, y, w, h, score, cls+1), optional `score > thr`, x,y,w,h / div -> appended, order preserved, at merged[f][count[f]...].
+// Launches of successive scales are ordered by the stream, so count[f] needs no atomics.
+__global__ __launch_bounds__(DET_THREADS) void merge_scales_kernel(const float *rois, const float *reg, const float *scores,
+                                                                   const float *clses, const int *frame_off, int R, float scale,
+                                                                   float div, int filter, float thr, float *merged, int *count,
+                                                                   int K)
+{
+    __shared__ int wave_cnt[DET_THREADS / 64];
+    __shared__ int run;
+    const int f = blockIdx.x;
+    const int r0 = min(max(frame_off[f], 0), R);
+    const int n = min(max(frame_off[f + 1] - r0, 0), R - r0);
+    const int base0 = min(max(count[f], 0), K);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (threadIdx.x == 0) run = 0;
+    __syncthreads();
+    float *dst = merged + (long)f * K * 6;
+    for (int base = 0; base < n; base += DET_THREADS) {
+        const int i = base + threadIdx.x;
+        bool keep = false;
+        float o0 = 0.f, o1 = 0.f, o2 = 0.f, o3 = 0.f, sc = 0.f, cl = 0.f;
+        if (i < n) {
+            const long r = r0 + i;
+            const float *q = rois + r * 5;
+            const float *g = reg + r * 4;
+            // generate_bbox, as refine_boxes_kernel: xyxy * scale -> xywh -> w,h += 1 -> centre / size update -> xywh
+            const float x = q[1] * scale, y = q[2] * scale;
+            const float w = (q[3] * scale - x) + 1.0f, h = (q[4] * scale - y) + 1.0f;
+            const float cx = (g[0] * w + x) + w / 2.0f;
+            const float cy = (g[1] * h + y) + h / 2.0f;
+            const float ow = expf(g[2]) * w, oh = expf(g[3]) * h;
+            o0 = (cx - ow / 2.0f) / div;                 // pred_bbox[:, :4] / scale on the host: IEEE division
+            o1 = (cy - oh / 2.0f) / div;
+            o2 = ow / div;
+            o3 = oh / div;
+            sc = scores[r];
+            cl = clses[r] + 1.0f;
+            keep = !filter || sc > thr;
+        }
+        const unsigned long long m = __ballot(keep);
+        if (lane == 0) wave_cnt[wave] = __popcll(m);
+        __syncthreads();
+        int pos = base0 + run + __popcll(m & ((1ull << lane) - 1ull));
+        for (int wv = 0; wv < wave; ++wv) pos += wave_cnt[wv];
+        if (keep && pos < K) {
+            float *o = dst + (long)pos * 6;
+            o[0] = o0; o[1] = o1; o[2] = o2; o[3] = o3; o[4] = sc; o[5] = cl;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) run += wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) count[f] = min(base0 + run, K);
+}
+
+// One workgroup per frame: the first count[f] rows of rows[f] ordered by score descending, equal scores in input order — the
+// keys and the network of sort_rows_kernel (refine.hip).  The network runs over the frame's own power of two.
+//   out_off == NULL: out is [B,K,6]; the sorted rows lead frame f's block, rows behind them get class -1 (padding).
+//   out_off != NULL: out is packed ([out_rows,6]); frame f's rows start at row out_off[f] (exclusive prefix of count).
+//   xyxy: write (x, y, x + w, y + h, ...) — the xywh -> xyxy step in front of soft_nms (rrnet_operator.py:222-223).
+__global__ __launch_bounds__(DET_SORT_THREADS) void sort_frames_kernel(const float *rows, const int *count, const int *out_off, int K,
+                                                                       int KPmax, int xyxy, float *out, long out_rows)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    unsigned long long *keys = reinterpret_cast<unsigned long long *>(smem);
+    const int f = blockIdx.x;
+    const int n = min(max(count[f], 0), K);
+    int KP = 2;
+    while (KP < n) KP <<= 1;
+    if (KP > KPmax) KP = KPmax;                          // K <= KPmax by the launcher: never taken, keeps LDS indices bounded
+    const float *src = rows + (long)f * K * 6;
+    for (int i = threadIdx.x; i < KP; i += DET_SORT_THREADS) {
+        unsigned long long key = 0ull;
+        if (i < n) {
+            const unsigned int sc = __float_as_uint(src[(long)i * 6 + 4]);
+            const unsigned int ord = (sc & 0x80000000u) ? ~sc : (sc | 0x80000000u);
+            key = ((unsigned long long)ord << 32) | (unsigned long long)(0xffffffffu - (unsigned int)i);
+        }
+        keys[i] = key;
+    }
+    __syncthreads();
+    for (int k2 = 2; k2 <= KP; k2 <<= 1) {
+        for (int j = k2 >> 1; j > 0; j >>= 1) {
+            for (int t = threadIdx.x; t < KP / 2; t += DET_SORT_THREADS) {
+                const int lo = ((t / j) * 2 * j) + (t % j);
+                const int hi = lo + j;
+                const bool desc = ((lo & k2) == 0);
+                const unsigned long long a = keys[lo], b = keys[hi];
+                if ((a < b) == desc) { keys[lo] = b; keys[hi] = a; }
+            }
+            __syncthreads();
+        }
+    }
+    const long start = out_off ? min(max((long)out_off[f], 0l), out_rows) : (long)f * K;
+    const int nw = (int)min((long)n, out_rows - start);  // == n whenever out_off is the prefix of count
+    float *dst = out + start * 6;
+    for (int k = threadIdx.x; k < nw; k += DET_SORT_THREADS) {
+        int pos = (int)(0xffffffffu - (unsigned int)(keys[k] & 0xffffffffull));
+        pos = min(max(pos, 0), n - 1);
+        const float *r = src + (long)pos * 6;
+        float *o = dst + (long)k * 6;
+        o[0] = r[0]; o[1] = r[1];
+        o[2] = xyxy ? r[0] + r[2] : r[2];
+        o[3] = xyxy ? r[1] + r[3] : r[3];
+        o[4] = r[4]; o[5] = r[5];
+    }
+    if (!out_off) {
+        for (int k = n + threadIdx.x; k < K; k += DET_SORT_THREADS) {
+            float *o = dst + (long)k * 6;
+            o[0] = 0.f; o[1] = 0.f; o[2] = 0.f; o[3] = 0.f; o[4] = 0.f; o[5] = -1.0f;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int rr_prepare_frames(const unsigned char *frames, const float *mean, const float *stdv, float *out, int n, int h,
+                                 int w, int oh, int ow, hipStream_t stream)
+{
+    RR_CHECK_ARG(n > 0 && h > 0 && w > 0 && oh > 0 && ow > 0, "rr_prepare_frames: bad dims");
+    RR_CHECK_ARG(frames && mean && stdv && out, "rr_prepare_frames: null pointer");
+    const long total = (long)n * oh * ow;
+    long blocks = (total + DET_THREADS - 1) / DET_THREADS;
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(prepare_frames_kernel, dim3((unsigned)blocks), dim3(DET_THREADS), 0, stream, frames, mean, stdv, out, n, h,
+                       w, oh, ow);
+    RR_CHECK_LAUNCH("rr_prepare_frames");
+    return RR_OK;
+}
+
+extern "C" int rr_merge_scales(const float *rois, const float *reg, const float *scores, const float *clses,
+                               const int *frame_off, int nframes, int r, float scale, float div, int filter, float score_thr,
+                               float *merged, int *count, int k, hipStream_t stream)
+{
+    RR_CHECK_ARG(nframes >= 0 && r >= 0, "rr_merge_scales: negative size");
+    RR_CHECK_ARG(k > 0 && k <= DET_MAX_ROWS, "rr_merge_scales: %d rows per frame (limit %d)", k, DET_MAX_ROWS);
+    RR_CHECK_ARG(div > 0.0f, "rr_merge_scales: scale %g", (double)div);
+    if (nframes == 0) return RR_OK;
+    RR_CHECK_ARG(frame_off && merged && count, "rr_merge_scales: null pointer");
+    RR_CHECK_ARG(r == 0 || (rois && reg && scores && clses), "rr_merge_scales: null pointer");
+    hipLaunchKernelGGL(merge_scales_kernel, dim3(nframes), dim3(DET_THREADS), 0, stream, rois, reg, scores, clses, frame_off, r,
+                       scale, div, filter, score_thr, merged, count, k);
+    RR_CHECK_LAUNCH("rr_merge_scales");
+    return RR_OK;
+}
+
+extern "C" int rr_sort_frames_by_score(const float *rows6, const int *count, const int *out_off, int nframes, int k, int xyxy,
+                                       float *out6, long out_rows, hipStream_t stream)
+{
+    RR_CHECK_ARG(nframes >= 0, "rr_sort_frames_by_score: negative frame count");
+    RR_CHECK_ARG(k > 0 && k <= DET_MAX_ROWS, "rr_sort_frames_by_score: %d rows per frame (limit %d)", k, DET_MAX_ROWS);
+    if (nframes == 0) return RR_OK;
+    RR_CHECK_ARG(rows6 && count && out6 && rows6 != out6, "rr_sort_frames_by_score: null or aliased pointer");
+    RR_CHECK_ARG(out_off ? out_rows >= 0 : out_rows == (long)nframes * k, "rr_sort_frames_by_score: out6 holds %ld rows", out_rows);
+    int kp = 2;
+    while (kp < k) kp <<= 1;
+    const size_t lds = (size_t)kp * 8;
+    if (lds > 48 * 1024)
+        RR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(sort_frames_kernel),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
+                     "rr_sort_frames_by_score");
+    hipLaunchKernelGGL(sort_frames_kernel, dim3(nframes), dim3(DET_SORT_THREADS), lds, stream, rows6, count, out_off, k, kp, xyxy,
+                       out6, out_rows);
+    RR_CHECK_LAUNCH("rr_sort_frames_by_score");
+    return RR_OK;
+}

@@ -5,9 +5,11 @@
     transforms (transforms/) is the CPU path and the checker of the kernels;
   * the synthetic VisDrone-shaped generator (synthetic.py), which make_dataloader returns when `cfg.data_root` holds no
     dataset.
+Inference on raw frames has its own feeder (frames.py): decode, group by size, upload uint8.
 Out of scope: ColorJitter (in neither model's config)."""
 from .augment import DeviceAugmentLoader, DeviceValLoader, HostAugmentLoader  # noqa: F401
 from .drones_det import DronesDET  # noqa: F401
+from .frames import FrameFolder, SizeBucketedFrames, plan_buckets  # noqa: F401
 from .synthetic import SyntheticDronesDET, make_dataloader  # noqa: F401
 
 datasets = {'drones_det': DronesDET}

@@ -10,7 +10,10 @@ count that sizes the head's tensors, and the final box count).
 Ordering note: decode emits rows score-descending, grouping / hard NMS are stable, so inside every
 (frame, class) segment the stage-2 boxes already are in the order the reference's global
 `torch.sort(score, descending=True)` + `pred_bbox[:, 5] == cls` selection hands to `soft_nms`
-(ties: torch.sort leaves them unspecified; here they keep decode order)."""
+(ties: torch.sort leaves them unspecified; here they keep decode order).
+
+`detect_frames` / `Detector` are the entry point from raw frames: the multi-scale evaluation body
+(operators/rrnet_operator.py:256-279) for a batch of equal-size uint8 frames."""
 import os
 
 import torch
@@ -50,3 +53,111 @@ def refine_frames(hm, wh, offset, feat, head_detector, k=1500, num_classes=10, s
     if int(err.item()) != 0:
         raise ZeroDivisionError("float division")
     return out6[:int(fo[-1])], frame_off
+
+
+def _frame_ranges(bxyxy, b):
+    """Row range of every frame in the model's packed RoI list (column 0 = frame index, ascending) -> int32 [b+1]."""
+    ids = torch.arange(b + 1, dtype=torch.float32, device=bxyxy.device)
+    return torch.searchsorted(bxyxy[:, 0].contiguous(), ids).to(torch.int32)
+
+
+def _vec3(v, device):
+    if torch.is_tensor(v):
+        return v.to(device=device, dtype=torch.float32).contiguous()
+    return torch.tensor([float(x) for x in v], dtype=torch.float32, device=device)
+
+
+@torch.no_grad()
+def detect_frames(model, frames_u8, scales, mean, std, *, nms, k=1500, score_thr=0.01, scale_factor=4, num_classes=10,
+                  timer=None):
+    """Multi-scale detection (operators/rrnet_operator.py:256-279) on B equal-size frames.
+    frames_u8 uint8 [B,H,W,3] on the device (RGB as PIL decodes it), model = RRNet in eval mode, scales = the list of
+    cfg.Val.scales, mean / std = Normalize's, nms = `not cfg.Val.auto_test`.
+    -> boxes [n,6] = x,y,w,h,score,cls+1 (frames back to back, each score-descending), frame_off int32 [B+1]; both on
+    the device.  Per frame: every scale's generate_bbox rows (filtered by `score > score_thr` when nms), divided by the
+    scale, concatenated in scale order, stably sorted by score; with nms, per-class gaussian Soft-NMS (sigma 0.5, Nt 0.7,
+    threshold 0.1) and a second stable sort.  Host reads: the model's RoI count per scale and the final counts.
+    Raises ValueError when len(scales)*k exceeds the LDS sort's 16384 rows, ZeroDivisionError where soft_nms would.
+    timer (optional): called as timer(stage) with 'prepare' / 'model' / 'post' after the launches of each stage."""
+    if not torch.is_tensor(frames_u8) or frames_u8.dtype != torch.uint8:
+        raise TypeError("detect_frames: frames must be a uint8 tensor [B,H,W,3], got %s"
+                        % (frames_u8.dtype if torch.is_tensor(frames_u8) else type(frames_u8).__name__))
+    if frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
+        raise ValueError("detect_frames: frames must be [B,H,W,3], got %s" % (tuple(frames_u8.shape),))
+    scales = list(scales)
+    rows_per_frame = len(scales) * int(k)
+    if rows_per_frame > ops.DETECT_MAX_ROWS or rows_per_frame <= 0:
+        raise ValueError("detect_frames: %d scales x %d boxes = %d rows per frame (limit %d)"
+                         % (len(scales), k, rows_per_frame, ops.DETECT_MAX_ROWS))
+    from rrnet_amd import _C
+    _C.require_cuda(frames_u8)
+    tick = timer if timer is not None else (lambda stage: None)
+    dev = frames_u8.device
+    frames_u8 = frames_u8.contiguous()
+    b = frames_u8.shape[0]
+    mean, std = _vec3(mean, dev), _vec3(std, dev)
+    merged, count = ops.merge_buffers(b, rows_per_frame, dev)
+    for s in scales:
+        x = ops.prepare_frames(frames_u8, mean, std, s)
+        tick('prepare')
+        _, _, _, reg, bxyxy, scores, clses = model(x, k=k)
+        tick('model')
+        ops.merge_scales(bxyxy, reg, scores, clses.float(), _frame_ranges(bxyxy, b), s, merged, count,
+                         scale=scale_factor, score_thr=score_thr if nms else None)
+        tick('post')
+    out = finish_frames(merged, count, nms, num_classes)
+    tick('post')
+    return out
+
+
+@torch.no_grad()
+def finish_frames(merged, count, nms, num_classes=10):
+    """The cross-scale tail of detect_frames on the merged rows (ops.merge_buffers / ops.merge_scales): merged [B,K,6]
+    xywh rows, count int32 [B] -> (boxes [n,6], frame_off int32 [B+1]).  First stable sort by score; with nms the
+    per-class Soft-NMS of `_ext_nms` and the second sort.  One host read (final counts, error flag)."""
+    b, rows_per_frame, _ = merged.shape
+    if not nms:
+        frame_off = ops.seg_prefix(count)
+        out6 = ops.sort_frames_by_score(merged, count, out_off=frame_off)
+        fo = frame_off.cpu()                                        # the one sync: final counts
+        return out6[:int(fo[-1])], frame_off
+    ordered = ops.sort_frames_by_score(merged, count, xyxy=True)    # padding rows (class -1) are dropped by the grouping
+    grouped, seg_off, seg_len = ops.group_by_class(ordered, num_classes, cls_base=1)
+    rows = grouped.view(-1, 6)
+    n_out, err = soft_nms_segments(rows, seg_off, rows_per_frame, sigma=0.5, Nt=0.7, threshold=0.1, method=2,
+                                   seg_len=seg_len, check=False)
+    out6, frame_off = ops.finalize_frames(rows, seg_off, n_out, b, num_classes, rows_per_frame)
+    frame_off = frame_off.contiguous()
+    fo = frame_off.cpu()                                            # the one sync: final counts (+ error flag)
+    if int(err.item()) != 0:
+        raise ZeroDivisionError("float division")
+    return out6[:int(fo[-1])], frame_off
+
+
+class Detector:
+    """RRNet from a reference-format checkpoint, ready for `detect`: builds RRNet(cfg) (stage-1 NMS as
+    cfg.Model.nms_type_for_stage1 / nms_per_class_for_stage1 say, bf16 as cfg.Model.bf16 says), loads the state dict
+    (checkpoint=None keeps the initial weights) and sets eval mode."""
+
+    def __init__(self, cfg, checkpoint=None, device=None):
+        from rrnet_amd.datasets.augment import chain_params
+        from rrnet_amd.models.rrnet import RRNet
+        self.cfg = cfg
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        model = RRNet(cfg)
+        if checkpoint is not None:
+            sd = torch.load(checkpoint, map_location='cpu') if isinstance(checkpoint, (str, os.PathLike)) else checkpoint
+            sd = {(key[7:] if key.startswith('module.') else key): v for key, v in sd.items()}
+            model.load_state_dict(sd)
+        self.model = model.to(self.device).to(memory_format=torch.channels_last).eval()
+        p = chain_params(cfg.Val.transforms)
+        self.mean, self.std = p["mean"], p["std"]
+        self.scale_factor = int(cfg.Train.scale_factor)
+        self.num_classes = int(cfg.num_classes)
+
+    def detect(self, frames_u8, scales=None, nms=None, k=1500, timer=None):
+        """frames uint8 [B,H,W,3] on the device -> (boxes [n,6], frame_off int32 [B+1]) as detect_frames."""
+        scales = self.cfg.Val.scales if scales is None else scales
+        nms = (not self.cfg.Val.auto_test) if nms is None else bool(nms)
+        return detect_frames(self.model, frames_u8, scales, self.mean, self.std, nms=nms, k=k,
+                             scale_factor=self.scale_factor, num_classes=self.num_classes, timer=timer)

@@ -1492,6 +1492,71 @@ def sort_rows_by_score(rows6):
     return out
 
 
+DETECT_MAX_ROWS = 16384       # RR_DETECT_MAX_ROWS: merged rows of one frame the LDS sort holds
+
+
+def prepare_frames(frames_u8, mean, std, scale_factor):
+    """rr_prepare_frames: frames uint8 [B,H,W,3] (RGB) -> ToTensor -> Normalize -> F.interpolate(scale_factor, bilinear,
+    align_corners=True) -> logical [B,3,floor(H*s),floor(W*s)] float32 in NHWC memory.  mean / std float32 [3] on the
+    device.  Same bits as resize_bilinear_ac on the host-normalised frame."""
+    import math
+    _C.require_cuda(frames_u8, mean, std)
+    assert frames_u8.dtype == torch.uint8 and frames_u8.is_contiguous() and frames_u8.dim() == 4 and frames_u8.shape[3] == 3
+    assert mean.dtype == torch.float32 and std.dtype == torch.float32 and mean.numel() == 3 and std.numel() == 3
+    assert mean.is_contiguous() and std.is_contiguous()
+    b, h, w, _ = frames_u8.shape
+    oh, ow = int(math.floor(h * scale_factor)), int(math.floor(w * scale_factor))
+    out = empty_nhwc(b, 3, oh, ow, frames_u8.device)
+    _C.check(_C.fn("rr_prepare_frames")(_C.ptr(frames_u8), _C.ptr(mean), _C.ptr(std), _C.ptr(out), b, h, w, oh, ow,
+                                        _C.stream()), "rr_prepare_frames")
+    return out
+
+
+def merge_buffers(nframes, k, device):
+    """(merged [nframes,k,6] with every class -1, count int32 [nframes] zeros): the state rr_merge_scales appends to."""
+    if not 0 < k <= DETECT_MAX_ROWS:
+        raise ValueError("merge_buffers: %d rows per frame (limit %d)" % (k, DETECT_MAX_ROWS))
+    merged = torch.full((nframes, k, 6), -1.0, dtype=torch.float32, device=device)
+    return merged, torch.zeros(nframes, dtype=torch.int32, device=device)
+
+
+def merge_scales(rois, reg, scores, clses, frame_off, div, merged, count, scale=4, score_thr=None):
+    """rr_merge_scales: one scale's stage-2 inputs (rois [R,5], reg [R,4], scores / clses [R]; frame_off int32 [B+1] row
+    ranges) -> generate_bbox rows (x,y,w,h,score,cls+1), kept when score_thr is None or score > score_thr, x,y,w,h / div
+    (IEEE), appended to merged [B,K,6] at count [B] (both updated in place, see merge_buffers)."""
+    _C.require_cuda(rois, reg, scores, clses, frame_off, merged, count)
+    r = rois.shape[0]
+    b, k, six = merged.shape
+    assert six == 6 and merged.dtype == torch.float32 and merged.is_contiguous() and 0 < k <= DETECT_MAX_ROWS
+    assert count.dtype == torch.int32 and count.numel() == b and count.is_contiguous()
+    assert frame_off.dtype == torch.int32 and frame_off.numel() == b + 1 and frame_off.is_contiguous()
+    assert rois.dtype == torch.float32 and rois.is_contiguous() and tuple(rois.shape) == (r, 5)
+    assert reg.dtype == torch.float32 and tuple(reg.shape) == (r, 4)
+    assert scores.dtype == torch.float32 and scores.is_contiguous() and scores.numel() == r
+    assert clses.dtype == torch.float32 and clses.is_contiguous() and clses.numel() == r
+    _C.check(_C.fn("rr_merge_scales")(_C.ptr(rois), _C.ptr(reg.contiguous()), _C.ptr(scores), _C.ptr(clses),
+                                      _C.ptr(frame_off), b, r, float(scale), float(div), int(score_thr is not None),
+                                      float(score_thr if score_thr is not None else 0.0), _C.ptr(merged), _C.ptr(count), k,
+                                      _C.stream()), "rr_merge_scales")
+
+
+def sort_frames_by_score(rows6, count, out_off=None, xyxy=False):
+    """rr_sort_frames_by_score: rows6 [B,K,6], count int32 [B] -> every frame's first count[f] rows by score descending
+    (ties keep row order).  out_off None: [B,K,6], padding (class -1) behind the sorted rows.  out_off int32 [B+1]
+    (ops.seg_prefix(count)): packed [B*K,6] with frame f at row out_off[f].  xyxy: columns 2,3 become x+w, y+h."""
+    _C.require_cuda(rows6, count, out_off)
+    b, k, six = rows6.shape
+    if k > DETECT_MAX_ROWS:
+        raise ValueError("sort_frames_by_score: %d rows per frame (limit %d)" % (k, DETECT_MAX_ROWS))
+    assert six == 6 and rows6.dtype == torch.float32 and rows6.is_contiguous()
+    assert count.dtype == torch.int32 and count.numel() == b and count.is_contiguous()
+    assert out_off is None or (out_off.dtype == torch.int32 and out_off.numel() == b + 1 and out_off.is_contiguous())
+    out = torch.empty((b * k, 6) if out_off is not None else (b, k, 6), dtype=torch.float32, device=rows6.device)
+    _C.check(_C.fn("rr_sort_frames_by_score")(_C.ptr(rows6), _C.ptr(count), _C.ptr(out_off), b, k, int(bool(xyxy)),
+                                              _C.ptr(out), b * k, _C.stream()), "rr_sort_frames_by_score")
+    return out
+
+
 EVAL_MAX_GT = 2048            # RR_EVAL_MAX_GT: ground truths of one frame that rr_eval_match keeps in LDS
 EVAL_MAX_THRESHOLDS = 16      # RR_EVAL_MAX_THRESHOLDS
 

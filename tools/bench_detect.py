@@ -1,0 +1,201 @@
+"""Frames per second of multi-scale detection from raw frames to result files: the per-frame path (DeviceValLoader ->
+RRNetOperator.evaluate_images -> save_result) against detect_frames at several batch sizes, same process, same frames.
+
+Workload: RRNet with the hourglass-104 backbone and RANDOM weights, generated 1360x765 frames (VisDrone's common size),
+cfg.Val.scales, the config's auto_test (True: every box of every scale is kept and written).  Random weights keep all 1500
+boxes per scale whatever the filter: the worst case for the cross-scale tail and the writer; a trained model with --nms
+keeps far fewer.
+
+Every configuration runs 1 + --windows windows of --window-frames frames over a pool of --frames frames; the first window
+warms up (all scales' shapes), frames/s is the median of the others.  A window is timed with the host clock from the first
+decode to the last result file and ends in a device synchronise.  Device time per stage (prepare / model / post-process)
+comes from HIP events recorded between the stages of detect_frames; writer time is host time inside write_results /
+save_result.  One JSON line on stdout; --out writes the object to a file.
+
+  python tools/bench_detect.py [--frames 32] [--window-frames 8] [--windows 3] [--batches 1,2,4] [--modes f32,bf16]
+                               [--nms] [--out profiles/detect.json]"""
+import argparse
+import copy
+import json
+import os
+import statistics
+import sys
+import tempfile
+import time
+import types
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+FRAME_H, FRAME_W = 765, 1360
+
+
+class GeneratedFrames:
+    """DronesDET's load surface over seeded uint8 frames held as PIL images (decode cost: the uint8 copy only)."""
+
+    def __init__(self, n, seed=219):
+        from PIL import Image
+        rng = np.random.default_rng(seed)
+        self.images = []
+        for _ in range(n):
+            coarse = rng.integers(0, 256, (FRAME_H // 16 + 1, FRAME_W // 16 + 1, 3), dtype=np.uint8)
+            img = np.kron(coarse, np.ones((16, 16, 1), np.uint8))[:FRAME_H, :FRAME_W]      # blocks, not white noise
+            img = (img.astype(np.int16) + rng.integers(-8, 9, img.shape, dtype=np.int16)).clip(0, 255).astype(np.uint8)
+            self.images.append(Image.fromarray(img))
+        self.mdf = ["frame%04d" % i for i in range(n)]
+        self.annos = np.asarray([[10, 10, 50, 50, 1, 1, 0, 0]], np.int64)
+
+    def __len__(self):
+        return len(self.images)
+
+    def load(self, i):
+        return self.images[i].copy(), self.annos.copy(), self.mdf[i]
+
+
+class Window:
+    """A view of `count` frames of the pool starting at `start` (wrapping)."""
+
+    def __init__(self, pool, start, count):
+        self.pool, self.idx = pool, [(start + i) % len(pool) for i in range(count)]
+        self.mdf = [pool.mdf[i] for i in self.idx]
+
+    def __len__(self):
+        return len(self.idx)
+
+    def load(self, i):
+        return self.pool.load(self.idx[i])
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=32)
+    ap.add_argument("--window-frames", type=int, default=8)
+    ap.add_argument("--windows", type=int, default=3)
+    ap.add_argument("--batches", default="1,2,4")
+    ap.add_argument("--modes", default="f32,bf16")
+    ap.add_argument("--nms", action="store_true", help="auto_test=False: score filter and Soft-NMS (default: the config's raw mode)")
+    ap.add_argument("--backbone", default=None, help="override cfg.Model.backbone (rehearsals)")
+    ap.add_argument("--out")
+    args = ap.parse_args(argv)
+    assert args.windows >= 3, "frames/s is the median of at least 3 windows"
+
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("tools/bench_detect.py measures on the GPU; there is nothing to measure without one")
+    from rrnet_amd.configs.rrnet_config import Config
+    from rrnet_amd.datasets.augment import DeviceValLoader, chain_params
+    from rrnet_amd.datasets.frames import SizeBucketedFrames
+    from rrnet_amd.inference import Detector
+    from rrnet_amd.operators.rrnet_operator import RRNetOperator
+
+    pool = GeneratedFrames(args.frames)
+    out_dir = tempfile.mkdtemp(prefix="bench_detect_")
+    result = {"metric": "frames/sec, raw frame -> result file (multi-scale RRNet detection)", "unit": "frames/sec",
+              "higher_is_better": True, "data": "generated %dx%d frames, pool of %d" % (FRAME_W, FRAME_H, args.frames),
+              "weights": "random: all 1500 boxes of every scale survive, the worst case for the tail and the writer",
+              "windows": args.windows, "window_frames": args.window_frames, "modes": {}}
+
+    for mode in args.modes.split(","):
+        cfg = copy.deepcopy(Config)
+        if args.backbone:
+            cfg.Model.backbone = args.backbone
+        if mode == "bf16":
+            cfg.Model.bf16 = True
+        if args.nms:
+            cfg.Val.auto_test = False
+        nms = not cfg.Val.auto_test
+        torch.manual_seed(219)
+        det = Detector(cfg)
+        params = chain_params(cfg.Val.transforms)
+        ns = types.SimpleNamespace(cfg=cfg, model=det.model)
+        ns.generate_bbox = types.MethodType(RRNetOperator.generate_bbox, ns)
+        ns._ext_nms, ns._ext_nms_device = RRNetOperator._ext_nms, RRNetOperator._ext_nms_device
+        entry = {"scales": list(cfg.Val.scales), "nms": nms, "backbone": cfg.Model.backbone}
+
+        def per_frame_window(w):
+            """The parent's path: one frame at a time, D2H per frame, save_result's per-row loop."""
+            writer, boxes = 0.0, 0
+            t0 = time.perf_counter()
+            with torch.no_grad():
+                for imgs, _, names in DeviceValLoader(Window(pool, w * args.window_frames, args.window_frames), params,
+                                                      num_workers=8):
+                    pred = RRNetOperator.evaluate_images(ns, imgs)
+                    t1 = time.perf_counter()
+                    RRNetOperator.save_result(os.path.join(out_dir, names[0] + ".txt"), pred)
+                    writer += time.perf_counter() - t1
+                    boxes += pred.shape[0]
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0, writer, boxes, None
+
+        def batched_window(w, batch):
+            writer, boxes = 0.0, 0
+            marks = []
+
+            def timer(stage):
+                ev = torch.cuda.Event(enable_timing=True)
+                ev.record()
+                marks.append((stage, ev))
+
+            t0 = time.perf_counter()
+            for frames_u8, names in SizeBucketedFrames(Window(pool, w * args.window_frames, args.window_frames), batch,
+                                                       num_workers=8):
+                timer("start")
+                pred, frame_off = det.detect(frames_u8, nms=nms, timer=timer)
+                rows, off = pred.cpu().numpy(), frame_off.cpu().tolist()
+                t1 = time.perf_counter()
+                for i, name in enumerate(names):
+                    RRNetOperator.write_results(os.path.join(out_dir, name + ".txt"), rows[off[i]:off[i + 1]])
+                writer += time.perf_counter() - t1
+                boxes += rows.shape[0]
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            stages = {"prepare": 0.0, "model": 0.0, "post": 0.0}
+            for (_, a), (stage, b) in zip(marks, marks[1:]):
+                if stage != "start":
+                    stages[stage] += a.elapsed_time(b)
+            return dt, writer, boxes, stages
+
+        def run(name, fn):
+            torch.cuda.reset_peak_memory_stats()
+            rows = []
+            for w in range(args.windows + 1):
+                dt, writer, boxes, stages = fn(w)
+                print("  %s %s window %d: %.2f s" % (mode, name, w, dt), file=sys.stderr, flush=True)
+                if w > 0:                                                   # window 0 warms up
+                    rows.append((args.window_frames / dt, writer, boxes, stages))
+            fps = [r[0] for r in rows]
+            rec = {"frames_per_sec": round(statistics.median(fps), 3), "frames_per_sec_windows": [round(v, 3) for v in fps],
+                   "writer_ms_per_frame": round(1e3 * statistics.median(r[1] for r in rows) / args.window_frames, 3),
+                   "boxes_per_frame": rows[0][2] / args.window_frames,
+                   "allocator_peak_gib": round(torch.cuda.max_memory_allocated() / 2 ** 30, 3)}
+            if rows[0][3] is not None:
+                rec["device_ms_per_frame"] = {k: round(statistics.median(r[3][k] for r in rows) / args.window_frames, 3)
+                                              for k in rows[0][3]}
+            return rec
+
+        entry["per_frame"] = run("per-frame", per_frame_window)
+        for b in [int(v) for v in args.batches.split(",")]:
+            try:
+                entry["batch_%d" % b] = run("batch %d" % b, lambda w, b=b: batched_window(w, b))
+            except torch.cuda.OutOfMemoryError as e:
+                entry["batch_%d" % b] = {"error": "out of memory: %s" % str(e).split("\n")[0]}
+                torch.cuda.empty_cache()
+        result["modes"][mode] = entry
+        del det, ns
+        torch.cuda.empty_cache()
+
+    best = max((v["frames_per_sec"], k) for k, v in result["modes"][args.modes.split(",")[0]].items()
+               if isinstance(v, dict) and "frames_per_sec" in v)
+    result["value"], result["value_of"] = best[0], "%s %s" % (args.modes.split(",")[0], best[1])
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(json.dumps(result, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()
