@@ -407,29 +407,15 @@ def phantom_f32(shape, device, image):
 
 
 def wgrad_16bit_shape(c, k, r, s):
-    """Layer shapes whose weight gradient leaves the fp32 kernel when a 16-bit arithmetic is on (conv_wgrad's dispatch; the
-    kernel audit mirrors it)."""
+    """Layer shapes whose weight gradient leaves the fp32 kernel when a 16-bit arithmetic is on (conv_wgrad and the kernel audit ask).  Narrow filter
+    banks stay on its 32-filter tiles — except 3x3 banks of 16..32 filters, the DCN offset / mask convolution's 28: 1.20 ms fp32 against 0.54 ms bf16."""
     return c > 32 and (k > 32 or (k >= 16 and r * s >= 9))
 
 
-def dgrad16_takes(dy_shape, w_shape, x_shape, stride, pad, relu_bias_link=False):
-    """True when conv_dgrad(dy, w, x_shape, ...) will go to rr_conv16_dgrad_s1 (mirrors the dispatch there)."""
-    n, c, h, wd = x_shape
-    k, _, r, s = w_shape
-    if stride == 2:
-        return bool(_s2_parity_pads_ok(r, s, pad) and _CONV16 and _mode() == MATH_BF16 and _BF16_S2_DGRAD and k % 64 == 0 and c % 128 == 0
-                    and r * s <= 16 and n * h * wd // 4 >= _CONV16_MIN_PIXELS
-                    and max(n * h * wd * c, dy_shape[0] * dy_shape[1] * dy_shape[2] * dy_shape[3]) * 2 < (1 << 31))
-    return bool(stride == 1 and pad[0] < r and pad[1] < s and not relu_bias_link and _CONV16 and _mode() == MATH_BF16
-                and n * h * wd >= _CONV16_MIN_PIXELS and _C.fn("rr_conv16_supported")(k, c, r, s, 1)
-                and max(n * h * wd * c, dy_shape[0] * dy_shape[1] * dy_shape[2] * dy_shape[3]) * 2 < (1 << 31))
-
-
 def wgrad16_takes(x_shape, dy_shape, w_shape, stride):
-    """True when conv_wgrad(x, dy, dw, stride, ...) will go to rr_conv16_wgrad."""
+    """True when conv_wgrad(x, dy, dw, stride, ...) goes to rr_conv16_wgrad (the explicit_out form never does)."""
     k, c, r, s = w_shape
-    npix = dy_shape[0] * dy_shape[2] * dy_shape[3]
-    xn = x_shape[0] * x_shape[1] * x_shape[2] * x_shape[3]
+    npix, xn = dy_shape[0] * dy_shape[2] * dy_shape[3], x_shape[0] * x_shape[1] * x_shape[2] * x_shape[3]
     return bool(_CONV16 and _mode() == MATH_BF16 and npix >= _CONV16_MIN_PIXELS and _C.fn("rr_conv16_wgrad_supported")(c, k, r, s, stride)
                 and max(xn, npix * k) * 2 < (1 << 31))
 
@@ -628,7 +614,8 @@ _DGRAD_BNSUM = True     # False: rr_bn_bwd_reduce (test_conv_gpu.py::test_train_
 _HEAD_DGRAD_MAX_K = 12
 _HEAD_DGRAD = True      # False: the heads' narrow 1x1 data gradients on the implicit-GEMM kernel
                         # (test_conv_gpu.py::test_head_1x1_dgrad_kernel_accumulate_and_legacy_path checks both)
-_BF16_S2_DGRAD = True   # False: stride-2 data gradients stay on the fp32 kernel (tests/kernel_audit.py reads it to mirror the dispatch)
+_BF16_S2_DGRAD = True   # False: stride-2 data gradients stay on the fp32 kernel
+_DGRAD_DY16 = ("conv16_s1", "conv16_s2")      # the routes (dgrad_route) that read dy as a bf16 image; every other one reads fp32 memory
 
 
 def _s2_parity_pads_ok(r, s, pad):
@@ -644,13 +631,167 @@ def _s2_parity_pads_ok(r, s, pad):
     return True
 
 
+def dgrad_route(dy_shape, w_shape, x_shape, stride, pad, link=None, link_b16=False, have_z=False, device=True):
+    """The ONE place where the data-gradient kernel is chosen: conv_dgrad launches what this names; dgrad16_takes and the kernel
+    audit ask it.  Shapes and facts in, nothing allocated, no tensor touched; the thread's arithmetic and the module flags are read
+    at call time.  link: the producer link the launch may serve — None, "bn", "relu_bias" (conv + bias + ReLU) or "mask_only" (a
+    bare ReLU); link_b16: the link's y, or the z handed in, is a bf16 image only; have_z: the mask source the link needs is there.
+    -> (route, arithmetic MATH_*); each route's launcher (_dgrad_*, below) names its entry point."""
+    n, c, h, wd = x_shape
+    k, _, r, s = w_shape
+    npx, dx_elems, dy_elems = n * h * wd, n * h * wd * c, dy_shape[0] * dy_shape[1] * dy_shape[2] * dy_shape[3]
+    if link == "bn" and link_b16:
+        link = None         # no fp32 y / z for the epilogue to read: the producer runs its own reduce pass (rr_bn_bwd_reduce_b16)
+    relu_bias = link in ("relu_bias", "mask_only")
+    inside, fits32 = pad[0] < r and pad[1] < s, dx_elems * 4 < (1 << 31)
+    # csrc/conv16.hip (bf16 mode): both operands as bf16 tensors below 2 GiB, maps of at least _CONV16_MIN_PIXELS output pixels
+    conv16 = _CONV16 and _mode() == MATH_BF16 and device and max(dy_elems, dx_elems) * 2 < (1 << 31)
+    s1_16 = bool(stride == 1 and inside and conv16 and npx >= _CONV16_MIN_PIXELS and _C.fn("rr_conv16_supported")(k, c, r, s, 1))
+
+    def math(kk, pixels):           # the arithmetic of a csrc/conv_bf16.hip launch on a dy of kk channels
+        return _bf16_ok(kk, c, r, s, pixels=pixels) if max(dy_elems // k * kk, dx_elems) * 4 < (1 << 31) else 0
+    if (relu_bias and _DGRAD_BNSUM and stride == 1 and c % 4 == 0 and have_z and fits32 and r * s <= 64 and inside
+            and dy_shape[2] * dy_shape[3] >= _DGRAD_VIA_FPROP_MIN_PIXELS and npx % 128 == 0):      # whole 128-row tiles only (fprop_impl in csrc/conv.hip)
+        if link == "mask_only" and s1_16:
+            return "relumask", MATH_BF16
+        if r == 1 and s == 1 and k <= _HEAD_DGRAD_MAX_K and 1024 % c == 0 and _HEAD_DGRAD and device:
+            return "head", MATH_F32           # an fp32 element-wise pass in every arithmetic
+        return "relubias", math((k + 3) // 4 * 4, npx)       # (a 10- / 2-channel dy is zero-padded to 12 / 4)
+    if s1_16 and not relu_bias:
+        return "conv16_s1", MATH_BF16
+    if stride == 1 and k % 4 == 0 and c % 4 == 0 and r * s <= 64 and inside and _DGRAD_VIA_FPROP:
+        # 16-bit operands: the forward kernel at every size — its split-K covers the small maps, and the dgrad kernel is fp32-only
+        bf = math(k, npx)
+        if bf or dy_shape[2] * dy_shape[3] >= _DGRAD_VIA_FPROP_MIN_PIXELS:
+            return ("fprop_bnsum" if link == "bn" and _DGRAD_BNSUM and c <= 1024 and fits32 and have_z else "fprop"), bf
+    if stride == 2 and _BF16_S2_DGRAD and _s2_parity_pads_ok(r, s, pad):
+        if conv16 and k % 64 == 0 and c % 128 == 0 and r * s <= 16 and npx // 4 >= _CONV16_MIN_PIXELS:
+            return "conv16_s2", MATH_BF16
+        bf = math(k, npx // 4)
+        if bf:
+            return "parity_s2", bf
+    return "dgrad", MATH_F32
+
+
+def dgrad16_takes(dy_shape, w_shape, x_shape, stride, pad, relu_bias_link=False):
+    """True when conv_dgrad(dy, w, x_shape, ...) reads dy's bf16 image only (functional: the fp32 dy need not be written)."""
+    return dgrad_route(dy_shape, w_shape, x_shape, stride, pad, "relu_bias" if relu_bias_link else None)[0] in _DGRAD_DY16
+
+
+def link_facts(bnsum, bnsum_z, x_shape):
+    """A BnLink and the z that came with it -> (link, link_b16, have_z) as dgrad_route takes them."""
+    if bnsum is None or not (bnsum.relu_bias or (bnsum.y is not None and tuple(bnsum.y.shape) == tuple(x_shape))):
+        return None, False, False
+    z_ok = bnsum_z is not None and (is_phantom(bnsum_z) or is_nhwc(bnsum_z)) and tuple(bnsum_z.shape) == tuple(x_shape)
+    if bnsum.relu_bias:
+        return "mask_only" if bnsum.mask_only else "relu_bias", is_phantom(bnsum_z), z_ok
+    return "bn", is_phantom(bnsum.y) or is_phantom(bnsum_z), not bnsum.use_z or z_ok
+
+
+def _flipped_filter(w, wt, wt16, want16):
+    """-> (wt, wt16): the flipped / transposed filter (one tiny transpose per layer and step) and, with want16, its bf16 copy —
+    unless the caller brought them (FlatParams.wt_view / w16_views)."""
+    if wt is None and not (want16 and wt16 is not None):
+        wt = torch.empty(w.numel(), dtype=torch.float32, device=w.device)
+        _C.check(_C.fn("rr_weight_flip_transpose")(_C.ptr(w), _C.ptr(wt), *w.shape, _C.stream()), "rr_weight_flip_transpose")
+    if want16 and wt16 is None:
+        wt16 = torch.empty(wt.numel(), dtype=torch.bfloat16, device=w.device)
+        _C.check(_C.fn("rr_to_bf16")(_C.ptr(wt), _C.ptr(wt16), wt.numel(), _C.stream()), "rr_to_bf16")
+    return wt, wt16
+
+
+# The launchers, one per route or family.  geo = (n, h, wd, c, k, r, s, pad_h, pad_w, accumulate): the argument run the entry
+# points share; geo[:7] + (stride,) is the timer's detail.  link: the BnLink the launch serves (None: none).
+def _dgrad_conv16_s1(dy, w, out, geo, flops, wt, wt16, link=None, z=None):
+    """conv16_s1 / relumask (csrc/conv16.hip): the forward kernel on dY's bf16 image and the flipped filter's bf16 copy; for a bare
+    ReLU producer (link) with its mask in the epilogue.  (The producer's BatchNorm-backward sums are NOT carried by this kernel: the
+    producer runs its reduce pass.  An epilogue that did — round 5 — lost: with one workgroup per CU its image reads are in the open,
+    config-4 step 111.8-113.3 ms against 108.9-110.8 ms; removed in round 6, the numbers live in DESIGN §13.1.)"""
+    dy16 = bf16_of(dy)
+    wt16 = _flipped_filter(w, wt, wt16, True)[1]
+    if link is None:
+        _C.check(_timed("conv16_dgrad_s1", flops,
+                        lambda: _C.fn("rr_conv16_dgrad_s1")(_C.ptr(dy16), _C.ptr(wt16), _C.ptr(out), None, *geo, _C.stream()), geo[:7] + (1,),
+                        2.0 * (dy.numel() + w.numel()) + 4.0 * out.numel() * (2 if geo[9] else 1)), "rr_conv16_dgrad_s1")
+        return
+    _C.check(_timed("conv16_dgrad_s1+relumask", flops,
+                    lambda: _C.fn("rr_conv16_dgrad_s1_relumask")(_C.ptr(dy16), _C.ptr(wt16), _C.ptr(out), *geo, _C.ptr(z), _C.stream()),
+                    geo[:7] + (1,)), "rr_conv16_dgrad_s1_relumask")
+    link.sums, link.dz = _ZEROS.take(2, dy.device), out          # (sums: the "done" marker _ReLU.backward looks for)
+
+
+def _dgrad_relubias(dy, w, out, geo, flops, bf, link, z, wt, head):
+    """relubias / head: producer = conv + bias + ReLU: masked gradient + bias column sums in this launch's epilogue.  head: a head's narrow
+    1x1 layer (K = 10 / 2 / 34 of 36) is not a GEMM worth a matrix kernel — one HBM-bound pass of the same contract; under conv16 the bf16
+    image of dx comes out of it too.  Else a 10- or 2-channel dy is zero-padded to a multiple of 4 for the vector kernel (25 MB at 8x256x256)."""
+    n, h, wd, c, k, r, s = geo[:7]
+    link.sums, link.dz = _ZEROS.take(2 * c, dy.device), out
+    if head:
+        want16 = _CONV16 and _mode() == MATH_BF16 and c % 256 == 0 and n * h * wd >= _CONV16_MIN_PIXELS
+        out16 = torch.empty_like(out, dtype=torch.bfloat16) if want16 else None
+        _C.check(_C.fn("rr_head_dgrad_relubias")(_C.ptr(dy), _C.ptr(w), _C.ptr(out), _C.ptr(out16), _C.ptr(z), _C.ptr(link.sums),
+                                                 n * h * wd, c, k, geo[9], _C.stream()), "rr_head_dgrad_relubias")
+        if want16:
+            b16_attach(out, out16)
+        return
+    kp = (k + 3) // 4 * 4
+    if kp != k:
+        dyp, wp, wt = empty_nhwc(dy.shape[0], kp, dy.shape[2], dy.shape[3], dy.device), zeros_nhwc(kp, c, r, s, dy.device), None
+        _C.check(_C.fn("rr_pad_channels")(_C.ptr(dy), _C.ptr(dyp), dy.shape[0] * dy.shape[2] * dy.shape[3], k, kp, _C.stream()), "rr_pad_channels")
+        wp[:k] = w
+        dy, w = dyp, wp
+    wt = _flipped_filter(w, wt, None, False)[0]
+    slab = torch.empty(_C.fn("rr_conv_stat_slab_bytes")(n, h, wd, c) // 8, dtype=torch.float64, device=dy.device)
+    tail = (_C.ptr(amax_of(dy)), _C.ptr(amax_of(w)), _C.stream()) if bf == MATH_F16X3 else (_C.stream(),)
+    f = _C.fn("rr_conv_dgrad_s1_relubias" + ("", "_bf16", "_f16x3")[bf])
+    _C.check(_timed(_igemm_name("fprop", c, False, n * h * wd) + "+relubias" + ("", "+bf16", "+f16x3")[bf], flops,
+                    lambda: f(_C.ptr(dy), _C.ptr(wt), _C.ptr(out), n, h, wd, c, kp, *geo[5:], _C.ptr(z), _C.ptr(slab), _C.ptr(link.sums), *tail),
+                    geo[:7] + (1,)), "rr_conv_dgrad_s1_relubias")
+
+
+def _dgrad_fprop(dy, w, out, geo, flops, bf, wt, wt16, wt_split, link=None, z=None):
+    """fprop / fprop_bnsum: the forward kernel on dy with the flipped / transposed filter — the same HIP kernel instance as a forward
+    convolution, timed under its name; with a link the producer's BatchNorm-backward sums come out of its epilogue."""
+    n, h, wd, c = geo[:4]
+    wt = _flipped_filter(w, wt, None, False)[0]
+    sfx = ("_bnsum" if link is not None else "") + ("", "_bf16", "_f16x3")[bf]
+    name = _igemm_name("fprop", c, False, n * h * wd) + sfx.replace("_", "+")
+    if bf == MATH_F16X3 and wt_split is None:
+        wt_split = split_filter(w, amax_of(w), n * h * wd, flat=wt)
+    tail = _math_tail(bf, wt16, dy, w, wt_split)
+    if link is not None:
+        slab = torch.empty(_C.fn("rr_conv_stat_slab_bytes")(n, h, wd, c) // 8, dtype=torch.float64, device=dy.device)
+        link.sums, link.dz = _ZEROS.take(2 * c, dy.device), out
+        tail = (_C.ptr(link.y), _C.ptr(z if link.use_z else None), _C.ptr(link.mean), _C.ptr(link.invstd), _C.ptr(link.msc), _C.ptr(link.msh),
+                _C.ptr(slab), _C.ptr(link.sums)) + tail
+    f = _C.fn("rr_conv_dgrad_s1" + sfx)
+    _C.check(_timed(name, flops, lambda: f(_C.ptr(dy), _C.ptr(wt), _C.ptr(out), *geo, *tail), geo[:7] + (1,),
+                    4.0 * (dy.numel() + out.numel() * ((2 if geo[9] else 1) + (link is not None)) + w.numel())), "rr_conv_dgrad_s1" + sfx)
+
+
+def _dgrad_s2(dy, w, out, geo, flops, bf, conv16):
+    """conv16_s2 / parity_s2: a forward-kernel launch per output parity class on its sub-filter, packed inside the call, on dY's bf16 image / on dy."""
+    src = bf16_of(dy) if conv16 else dy
+    wsub = torch.empty(w.numel(), dtype=torch.bfloat16 if conv16 else torch.float32, device=dy.device)
+    f = _C.fn("rr_conv16_dgrad_s2" if conv16 else ("rr_conv_dgrad_s2_f16x3" if bf == MATH_F16X3 else "rr_conv_dgrad_s2_bf16"))
+    tail = (_C.ptr(amax_of(dy)), _C.ptr(amax_of(w)), _C.stream()) if bf == MATH_F16X3 else (_C.stream(),)
+    _C.check(_timed("conv16_dgrad_s2" if conv16 else "conv_dgrad_s2" + ("", "+bf16", "+f16x3")[bf], flops,
+                    lambda: f(_C.ptr(src), _C.ptr(w), _C.ptr(out), *geo, _C.ptr(wsub), *tail), geo[:7] + (2,)), "rr_conv_dgrad_s2")
+
+
+def _dgrad_fp32(dy, w, out, geo, flops, stride):
+    n, h, wd, c, k = geo[:5]
+    _C.check(_timed(_igemm_name("dgrad", c, (k % 4 != 0) or (c % 4 != 0), n * h * wd, stride), flops,
+                    lambda: _C.fn("rr_conv_dgrad")(_C.ptr(dy), _C.ptr(w), _C.ptr(out), *geo[:7], stride, *geo[7:], _C.stream()),
+                    geo[:7] + (stride,)), "rr_conv_dgrad")
+
+
 def conv_dgrad(dy, w, x_shape, stride=1, pad=(0, 0), out=None, accumulate=False, bnsum=None, bnsum_z=None, wt=None, wt16=None,
                wt_split=None):
-    """dy [N,K,P,Q], w [K,C,R,S] -> dx [N,C,H,W]; with `out` and accumulate adds into it.
+    """dy [N,K,P,Q], w [K,C,R,S] -> dx [N,C,H,W]; with `out` and accumulate adds into it.  The kernel is dgrad_route's choice.
     wt: the flipped / transposed filter (rr_weight_flip_transpose of w) when the caller keeps one (FlatParams.wt_view).
-    bnsum (BnLink of the layer that produced the convolution's input): when the launch can carry them, the producer's
-    BatchNorm-backward sums are computed in the epilogue and left in bnsum.sums / bnsum.dz.  bnsum_z: the
-    convolution's input itself (= the producer's output), needed when bnsum.use_z."""
+    bnsum (BnLink of the layer that produced the convolution's input): when the launch can carry them, the producer's BatchNorm-backward
+    sums are computed in the epilogue and left in bnsum.sums / bnsum.dz.  bnsum_z: the convolution's input itself, needed when bnsum.use_z."""
     _C.require_cuda(dy, w)
     assert (is_nhwc(dy) or is_phantom(dy)) and is_nhwc(w)     # (phantom: a bf16-only gradient, see phantom_f32)
     n, c, h, wd = x_shape
@@ -662,160 +803,24 @@ def conv_dgrad(dy, w, x_shape, stride=1, pad=(0, 0), out=None, accumulate=False,
     else:
         amax_drop(out)                # an existing tensor rewritten / added into through its pointer
     assert is_nhwc(out)
-    if bnsum is not None and not bnsum.relu_bias and bnsum.y is not None and is_phantom(bnsum.y):
-        bnsum = None                  # the producer's pre-BN output exists only as a bf16 image: it runs its own reduce pass
-    if bnsum is not None and bnsum_z is not None and is_phantom(bnsum_z):
-        # the producer's output exists only as a bf16 image: the fp32-reading epilogues cannot take their mask from it — a ReLU /
-        # bias producer gets the widened copy, a BatchNorm producer runs its own reduce pass (rr_bn_bwd_reduce_b16)
-        if bnsum.relu_bias:
-            bnsum_z = f32_of(bnsum_z)
-        else:
-            bnsum = None
-    s2_16 = (stride == 2 and _s2_parity_pads_ok(r, s, pad) and _CONV16 and _mode() == MATH_BF16 and _BF16_S2_DGRAD and dy.is_cuda
-             and k % 64 == 0 and c % 128 == 0 and r * s <= 16 and n * h * wd // 4 >= _CONV16_MIN_PIXELS)
-    if is_phantom(dy) and not s2_16 and not (stride == 1 and pad[0] < r and pad[1] < s and conv16_ok(k, c, r, s, 1, n * h * wd, dy, out)
-                                             and not (bnsum is not None and bnsum.relu_bias)):
-        dy = f32_of(dy)
-    if (bnsum is not None and bnsum.relu_bias and _DGRAD_BNSUM and stride == 1 and c % 4 == 0
-            and bnsum_z is not None and is_nhwc(bnsum_z) and bnsum_z.shape == out.shape and out.numel() * 4 < (1 << 31)
-            and r * s <= 64 and pad[0] < r and pad[1] < s and dy.shape[2] * dy.shape[3] >= _DGRAD_VIA_FPROP_MIN_PIXELS
-            and (n * h * wd) % 128 == 0):      # whole 128-row tiles only (see fprop_impl in csrc/conv.hip)
-        if bnsum.mask_only and pad[0] < r and pad[1] < s and conv16_ok(k, c, r, s, 1, n * h * wd, dy, out) and not is_phantom(bnsum_z):
-            # the producer is a bare ReLU (its mask is all that is wanted): conv16's data gradient with the mask in its epilogue
-            dy16 = bf16_of(dy)
-            if wt16 is None:
-                if wt is None:
-                    wt = torch.empty(k * c * r * s, dtype=torch.float32, device=dy.device)
-                    _C.check(_C.fn("rr_weight_flip_transpose")(_C.ptr(w), _C.ptr(wt), k, c, r, s, _C.stream()), "rr_weight_flip_transpose")
-                wt16 = torch.empty(wt.numel(), dtype=torch.bfloat16, device=dy.device)
-                _C.check(_C.fn("rr_to_bf16")(_C.ptr(wt), _C.ptr(wt16), wt.numel(), _C.stream()), "rr_to_bf16")
-            flops_m = 2.0 * dy.shape[0] * dy.shape[2] * dy.shape[3] * k * c * r * s
-            _C.check(_timed("conv16_dgrad_s1+relumask", flops_m,
-                            lambda: _C.fn("rr_conv16_dgrad_s1_relumask")(_C.ptr(dy16), _C.ptr(wt16), _C.ptr(out), n, h, wd, c, k, r, s, pad[0],
-                                                                         pad[1], int(accumulate), _C.ptr(bnsum_z), _C.stream()),
-                            (n, h, wd, c, k, r, s, stride)), "rr_conv16_dgrad_s1_relumask")
-            bnsum.sums, bnsum.dz = _ZEROS.take(2, dy.device), out          # (sums: the "done" marker _ReLU.backward looks for)
-            return out
-        if r == 1 and s == 1 and k <= _HEAD_DGRAD_MAX_K and 1024 % c == 0 and _HEAD_DGRAD and dy.is_cuda:
-            # a head's narrow 1x1 layer (K = 10 / 2 / 34 of 36): not a GEMM worth a matrix kernel — one HBM-bound pass
-            # (rr_head_dgrad_relubias), no channel padding; under conv16 the bf16 image of dx comes out of the same pass
-            sums = _ZEROS.take(2 * c, dy.device)
-            want16 = _CONV16 and _mode() == MATH_BF16 and c % 256 == 0 and n * h * wd >= _CONV16_MIN_PIXELS
-            out16 = torch.empty_like(out, dtype=torch.bfloat16) if want16 else None
-            _C.check(_C.fn("rr_head_dgrad_relubias")(_C.ptr(dy), _C.ptr(w), _C.ptr(out), _C.ptr(out16), _C.ptr(bnsum_z), _C.ptr(sums),
-                                                     n * h * wd, c, k, int(accumulate), _C.stream()), "rr_head_dgrad_relubias")
-            if want16:
-                b16_attach(out, out16)
-            bnsum.sums, bnsum.dz = sums, out
-            return out
-        # producer = conv + bias + ReLU: masked gradient + bias column sums in this launch's epilogue.  A 10- or
-        # 2-channel dy (hm / offset heads) is zero-padded to a multiple of 4 for the vector kernel (25 MB at 8x256x256)
-        kp = (k + 3) // 4 * 4
-        dyp, wp = dy, w
-        if kp != k:
-            dyp = empty_nhwc(dy.shape[0], kp, dy.shape[2], dy.shape[3], dy.device)
-            _C.check(_C.fn("rr_pad_channels")(_C.ptr(dy), _C.ptr(dyp), dy.shape[0] * dy.shape[2] * dy.shape[3], k, kp, _C.stream()),
-                     "rr_pad_channels")
-            wp = zeros_nhwc(kp, c, r, s, dy.device)
-            wp[:k] = w
-        if wt is None or kp != k:
-            wt = torch.empty(kp * c * r * s, dtype=torch.float32, device=dy.device)
-            _C.check(_C.fn("rr_weight_flip_transpose")(_C.ptr(wp), _C.ptr(wt), kp, c, r, s, _C.stream()), "rr_weight_flip_transpose")
-        slab = torch.empty(_C.fn("rr_conv_stat_slab_bytes")(n, h, wd, c) // 8, dtype=torch.float64, device=dy.device)
-        sums = _ZEROS.take(2 * c, dy.device)
-        flops_m = 2.0 * dy.shape[0] * dy.shape[2] * dy.shape[3] * k * c * r * s
-        bf = _bf16_ok(kp, c, r, s, dyp, out, pixels=n * h * wd)
-        fr = _C.fn("rr_conv_dgrad_s1_relubias" + ("", "_bf16", "_f16x3")[bf])
-        rtail = (_C.ptr(amax_of(dyp)), _C.ptr(amax_of(wp)), _C.stream()) if bf == MATH_F16X3 else (_C.stream(),)
-        _C.check(_timed(_igemm_name("fprop", c, False, n * h * wd) + "+relubias" + ("", "+bf16", "+f16x3")[bf], flops_m,
-                        lambda: fr(_C.ptr(dyp), _C.ptr(wt), _C.ptr(out), n, h, wd, c, kp, r, s, pad[0], pad[1], int(accumulate),
-                                   _C.ptr(bnsum_z), _C.ptr(slab), _C.ptr(sums), *rtail), (n, h, wd, c, k, r, s, stride)),
-                 "rr_conv_dgrad_s1_relubias")
-        bnsum.sums, bnsum.dz = sums, out
-        return out
+    link, link_b16, have_z = link_facts(bnsum, bnsum_z, x_shape)
+    if link_b16 and link != "bn":
+        bnsum_z = f32_of(bnsum_z)     # a ReLU / bias producer whose output is a bf16 image only: its mask is read from the widened copy
+    route, bf = dgrad_route(tuple(dy.shape), tuple(w.shape), x_shape, stride, pad, link, link_b16, have_z, dy.is_cuda)
+    if is_phantom(dy) and route not in _DGRAD_DY16:
+        dy = f32_of(dy)               # (relumask included: it rounds the widened copy again — exact, but two passes too many)
+    geo = (n, h, wd, c, k, r, s, pad[0], pad[1], int(accumulate))
     flops = 2.0 * dy.shape[0] * dy.shape[2] * dy.shape[3] * k * c * r * s
-    if (stride == 1 and pad[0] < r and pad[1] < s and conv16_ok(k, c, r, s, 1, n * h * wd, dy, out)
-            and not (bnsum is not None and bnsum.relu_bias)):
-        # csrc/conv16.hip: the forward kernel on dY's bf16 image and the flipped filter's bf16 copy.  (The producer's
-        # BatchNorm-backward sums are NOT carried by this kernel: `bnsum` stays untouched and the producer runs its reduce pass.
-        # An epilogue that did — round 5 — lost: with one workgroup per CU its image reads are in the open, config-4 step
-        # 111.8-113.3 ms against 108.9-110.8 ms; removed in round 6, the numbers live in DESIGN §13.1.)
-        dy16 = bf16_of(dy)
-        if wt16 is None:
-            if wt is None:
-                wt = torch.empty(k * c * r * s, dtype=torch.float32, device=dy.device)
-                _C.check(_C.fn("rr_weight_flip_transpose")(_C.ptr(w), _C.ptr(wt), k, c, r, s, _C.stream()), "rr_weight_flip_transpose")
-            wt16 = torch.empty(wt.numel(), dtype=torch.bfloat16, device=dy.device)
-            _C.check(_C.fn("rr_to_bf16")(_C.ptr(wt), _C.ptr(wt16), wt.numel(), _C.stream()), "rr_to_bf16")
-        _C.check(_timed("conv16_dgrad_s1", flops,
-                        lambda: _C.fn("rr_conv16_dgrad_s1")(_C.ptr(dy16), _C.ptr(wt16), _C.ptr(out), None, n, h, wd, c, k, r, s, pad[0], pad[1],
-                                                            int(accumulate), _C.stream()), (n, h, wd, c, k, r, s, stride),
-                        2.0 * (dy.numel() + w.numel()) + 4.0 * out.numel() * (2 if accumulate else 1)), "rr_conv16_dgrad_s1")
-        return out
-    # (bf16 operands: the forward kernel at every size — its split-K covers the small maps, and the dgrad kernel is fp32-only)
-    if (stride == 1 and k % 4 == 0 and c % 4 == 0 and r * s <= 64 and pad[0] < r and pad[1] < s and _DGRAD_VIA_FPROP
-            and (dy.shape[2] * dy.shape[3] >= _DGRAD_VIA_FPROP_MIN_PIXELS or _bf16_ok(k, c, r, s, dy, out, pixels=n * h * wd))):
-        # the forward kernel on dy with the flipped / transposed filter (one tiny transpose per layer and step)
-        if wt is None:
-            wt = torch.empty(k * c * r * s, dtype=torch.float32, device=dy.device)
-            _C.check(_C.fn("rr_weight_flip_transpose")(_C.ptr(w), _C.ptr(wt), k, c, r, s, _C.stream()),
-                     "rr_weight_flip_transpose")
-        bf = _bf16_ok(k, c, r, s, dy, out, pixels=n * h * wd)
-        sfx, tsfx = (("", ""), ("_bf16", "+bf16"), ("_f16x3", "+f16x3"))[bf]
-        # wt16: the flipped filter already in bf16 (optional); split operands: the maxima of dy and of the filter
-        if bf == MATH_F16X3 and wt_split is None:
-            wt_split = split_filter(w, amax_of(w), n * h * wd, flat=wt)
-        tail = _math_tail(bf, wt16, dy, w, wt_split)
-        if (bnsum is not None and not bnsum.relu_bias and _DGRAD_BNSUM and bnsum.y is not None and c <= 1024 and out.numel() * 4 < (1 << 31)
-                and tuple(bnsum.y.shape) == tuple(out.shape)
-                and (not bnsum.use_z or (bnsum_z is not None and is_nhwc(bnsum_z) and bnsum_z.shape == out.shape))):
-            zt = bnsum_z if bnsum.use_z else None
-            nb = _C.fn("rr_conv_stat_slab_bytes")(n, h, wd, c)
-            slab = torch.empty(nb // 8, dtype=torch.float64, device=dy.device)
-            sums = _ZEROS.take(2 * c, dy.device)
-            fb = _C.fn("rr_conv_dgrad_s1_bnsum" + sfx)
-            _C.check(_timed(_igemm_name("fprop", c, False, n * h * wd) + "+bnsum" + tsfx, flops,
-                            lambda: fb(_C.ptr(dy), _C.ptr(wt), _C.ptr(out), n, h, wd, c, k, r, s, pad[0], pad[1],
-                                       int(accumulate), _C.ptr(bnsum.y), _C.ptr(zt), _C.ptr(bnsum.mean),
-                                       _C.ptr(bnsum.invstd), _C.ptr(bnsum.msc), _C.ptr(bnsum.msh), _C.ptr(slab),
-                                       _C.ptr(sums), *tail), (n, h, wd, c, k, r, s, stride),
-                            4.0 * (dy.numel() + out.numel() * (3 if accumulate else 2) + w.numel())),
-                     "rr_conv_dgrad_s1_bnsum")
-            bnsum.sums, bnsum.dz = sums, out
-            return out
-        f1 = _C.fn("rr_conv_dgrad_s1" + sfx)
-        # same HIP kernel instance as a forward convolution: timed under its name
-        _C.check(_timed(_igemm_name("fprop", c, False, n * h * wd) + tsfx, flops,
-                        lambda: f1(_C.ptr(dy), _C.ptr(wt), _C.ptr(out), n, h, wd, c, k, r, s, pad[0], pad[1],
-                                   int(accumulate), *tail), (n, h, wd, c, k, r, s, stride),
-                        4.0 * (dy.numel() + out.numel() * (2 if accumulate else 1) + w.numel())), "rr_conv_dgrad_s1")
-        return out
-    if (stride == 2 and _s2_parity_pads_ok(r, s, pad) and _CONV16 and _mode() == MATH_BF16 and _BF16_S2_DGRAD and dy.is_cuda
-            and k % 64 == 0 and c % 128 == 0 and r * s <= 16 and n * h * wd // 4 >= _CONV16_MIN_PIXELS
-            and max(dy.numel(), out.numel()) * 2 < (1 << 31)):
-        # csrc/conv16.hip: the four parity-class launches on dY's bf16 image and bf16 sub-filters packed inside the call
-        dy16 = bf16_of(dy)
-        wsub16 = torch.empty(k * c * r * s, dtype=torch.bfloat16, device=dy.device)
-        _C.check(_timed("conv16_dgrad_s2", flops,
-                        lambda: _C.fn("rr_conv16_dgrad_s2")(_C.ptr(dy16), _C.ptr(w), _C.ptr(out), n, h, wd, c, k, r, s, pad[0], pad[1],
-                                                            int(accumulate), _C.ptr(wsub16), _C.stream()), (n, h, wd, c, k, r, s, stride)),
-                 "rr_conv16_dgrad_s2")
-        return out
-    if (stride == 2 and _s2_parity_pads_ok(r, s, pad) and _bf16_ok(k, c, r, s, dy, out, pixels=n * h * wd // 4)
-            and _BF16_S2_DGRAD):
-        # bf16 operands: one launch of the forward kernel per output parity class on its packed sub-filter
-        wsub = torch.empty(k * c * r * s, dtype=torch.float32, device=dy.device)
-        sx = _bf16_ok(k, c, r, s, dy, out, pixels=n * h * wd // 4) == MATH_F16X3
-        f2 = _C.fn("rr_conv_dgrad_s2_f16x3" if sx else "rr_conv_dgrad_s2_bf16")
-        stail = (_C.ptr(amax_of(dy)), _C.ptr(amax_of(w)), _C.stream()) if sx else (_C.stream(),)
-        _C.check(_timed("conv_dgrad_s2" + ("+f16x3" if sx else "+bf16"), flops,
-                        lambda: f2(_C.ptr(dy), _C.ptr(w), _C.ptr(out), n, h, wd, c, k, r, s, pad[0], pad[1], int(accumulate),
-                                   _C.ptr(wsub), *stail), (n, h, wd, c, k, r, s, stride)), "rr_conv_dgrad_s2_bf16")
-        return out
-    f = _C.fn("rr_conv_dgrad")
-    _C.check(_timed(_igemm_name("dgrad", c, (k % 4 != 0) or (c % 4 != 0), n * h * wd, stride), flops,
-                    lambda: f(_C.ptr(dy), _C.ptr(w), _C.ptr(out), n, h, wd, c, k, r, s, stride, pad[0], pad[1],
-                              int(accumulate), _C.stream()), (n, h, wd, c, k, r, s, stride)), "rr_conv_dgrad")
+    if route in ("conv16_s1", "relumask"):
+        _dgrad_conv16_s1(dy, w, out, geo, flops, wt, wt16, *((bnsum, bnsum_z) if route == "relumask" else ()))
+    elif route in ("relubias", "head"):
+        _dgrad_relubias(dy, w, out, geo, flops, bf, bnsum, bnsum_z, wt, route == "head")
+    elif route in ("fprop", "fprop_bnsum"):
+        _dgrad_fprop(dy, w, out, geo, flops, bf, wt, wt16, wt_split, *((bnsum, bnsum_z) if route == "fprop_bnsum" else ()))
+    elif route in ("conv16_s2", "parity_s2"):
+        _dgrad_s2(dy, w, out, geo, flops, bf, route == "conv16_s2")
+    else:
+        _dgrad_fp32(dy, w, out, geo, flops, stride)
     return out
 
 
@@ -828,24 +833,18 @@ def conv_wgrad(x, dy, dw, stride=1, pad=(0, 0), explicit_out=False, algo_c=None)
     k, c2, r, s = dw.shape
     assert c == c2 and dy.shape[1] == k
     flops = 2.0 * dy.shape[0] * dy.shape[2] * dy.shape[3] * k * (c * r * s if algo_c is None else algo_c)
-    npix = dy.shape[0] * dy.shape[2] * dy.shape[3]
-    if (_CONV16 and _mode() == MATH_BF16 and not explicit_out and npix >= _CONV16_MIN_PIXELS and x.is_cuda
-            and _C.fn("rr_conv16_wgrad_supported")(c, k, r, s, stride) and max(x.numel(), dy.numel()) * 2 < (1 << 31)):
+    if wgrad16_takes(x.shape, dy.shape, dw.shape, stride) and not explicit_out:
         x16, dy16 = bf16_of(x), bf16_of(dy)
-        _C.check(_timed("conv16_wgrad", flops,
-                        lambda: _C.fn("rr_conv16_wgrad")(_C.ptr(x16), _C.ptr(dy16), _C.ptr(dw), n, h, wd, c, k, r, s, stride, pad[0], pad[1],
-                                                         _C.stream()), (n, h, wd, c, k, r, s, stride)), "rr_conv16_wgrad")
+        _C.check(_timed("conv16_wgrad", flops, lambda: _C.fn("rr_conv16_wgrad")(_C.ptr(x16), _C.ptr(dy16), _C.ptr(dw), n, h, wd, c, k, r, s, stride,
+                                                                                 pad[0], pad[1], _C.stream()), (n, h, wd, c, k, r, s, stride)), "rr_conv16_wgrad")
         return dw
     x, dy = f32_of(x), f32_of(dy)            # (bf16-only operands in front of a layer the conv16 weight gradient does not take)
-    # (narrow filter banks stay on the fp32 kernel's 32-filter tiles — except 3x3 banks of 16..32 filters, the DCN offset / mask
-    #  convolution's 28: measured 1.20 ms fp32 against 0.54 ms on the bf16 kernel's 128-wide tile at the config-4 layer)
-    bf = _bf16_ok(c, k, r, s, x, dy, pixels=npix) if wgrad_16bit_shape(c, k, r, s) else 0
+    bf = _bf16_ok(c, k, r, s, x, dy, pixels=dy.shape[0] * dy.shape[2] * dy.shape[3]) if wgrad_16bit_shape(c, k, r, s) else 0
     f = _C.fn(("rr_conv_wgrad", "rr_conv_wgrad_bf16", "rr_conv_wgrad_f16x3")[bf])
     wtail = (_C.ptr(amax_of(x)), _C.ptr(amax_of(dy)), _C.stream()) if bf == MATH_F16X3 else (_C.stream(),)
     _C.check(_timed("conv_wgrad<BN=%d>%s" % (128 if c > 32 else 32, ("", "+bf16", "+f16x3")[bf]), flops,
                     lambda: f(_C.ptr(x), _C.ptr(dy), _C.ptr(dw), n, h, wd, c, k, r, s, stride, pad[0], pad[1],
-                              dy.shape[2] if explicit_out else 0, dy.shape[3] if explicit_out else 0,
-                              *wtail), (n, h, wd, c, k, r, s, stride)), "rr_conv_wgrad")
+                              *((dy.shape[2], dy.shape[3]) if explicit_out else (0, 0)), *wtail), (n, h, wd, c, k, r, s, stride)), "rr_conv_wgrad")
     return dw
 
 

@@ -252,6 +252,9 @@ def audit(tol=2e-5, tol_wgrad=2e-4, sample=False, ref_device="cpu"):
     def conv_dgrad(dy, w, x_shape, stride=1, pad=(0, 0), out=None, accumulate=False, bnsum=None, bnsum_z=None, wt=None, wt16=None,
                    wt_split=None):
         base = out.clone() if (out is not None and accumulate) else None
+        # operands rounded to bf16: exactly when the route the dispatch itself picks for this call computes in that arithmetic
+        qq = ops.dgrad_route(tuple(dy.shape), tuple(w.shape), tuple(x_shape), stride, pad, *ops.link_facts(bnsum, bnsum_z, x_shape),
+                             dy.is_cuda)[1] == ops.MATH_BF16
         res = orig["conv_dgrad"](dy, w, x_shape, stride, pad, out, accumulate, bnsum, bnsum_z, wt, wt16, wt_split)   # the cached flipped filters
         dy, bnsum_z = _dat(dy), _dat(bnsum_z)
         relu_mask = None          # conv + bias + ReLU producer: this launch stored the masked gradient
@@ -291,11 +294,6 @@ def audit(tol=2e-5, tol_wgrad=2e-4, sample=False, ref_device="cpu"):
         sig = (tuple(dy.shape), tuple(w.shape), tuple(x_shape), stride, tuple(pad), bool(accumulate)) + \
               (("relu-masked",) if relu_mask is not None else ())
         flops = 2.0 * dy.numel() * w.shape[1] * w.shape[2] * w.shape[3]
-        # bf16 operands: stride-1 layers (the forward kernel on the flipped filter); a 10- / 2-channel dy was zero-padded to 12 / 4
-        qq = (stride == 1 or (stride == 2 and ops._BF16_S2_DGRAD)) and pad[0] < w.shape[2] and pad[1] < w.shape[3] and \
-            ops._bf16_ok(w.shape[0] if relu_mask is None else (w.shape[0] + 3) // 4 * 4, w.shape[1], w.shape[2], w.shape[3], dy, res)
-        if relu_mask is not None and w.shape[2] == 1 and w.shape[3] == 1 and w.shape[0] <= ops._HEAD_DGRAD_MAX_K and ops._HEAD_DGRAD:
-            qq = 0            # rr_head_dgrad_relubias: an fp32 element-wise pass in every arithmetic, operands not rounded
         if qq:
             sig = sig + ("bf16",)
         if ("dgrad",) + sig not in rec.seen and big(flops):

@@ -525,3 +525,37 @@ def test_conv_route_mirror_and_grid_coverage():
         assert any(cmb[pas] == want for cmb in combos), (pas, want)
     # bias / ReLU keep split-K off on a shape that would otherwise split
     assert route(14)["fprop"] == {"bn32"} and CONV64_GRID[14][10:12] == (True, True)
+
+
+# ---- the data-gradient selector (ops.dgrad_route) against the recorded launches (tests/golden/conv_bwd_routes.json) -----------
+def test_dgrad_route_names_the_kernel_each_recorded_call_launched(golden_dir):
+    """For every conv_dgrad case of tests/conv_route_cases.py, ops.dgrad_route — asked with shapes and the link's facts only, the
+    device asserted, no tensor in sight — names the route whose entry point is the last launch of that case's record, taken on an
+    MI355X from the dispatch that preceded it; its arithmetic is the one the entry point's suffix says; ops.dgrad16_takes agrees."""
+    import json
+    import os
+    from conv_route_cases import cases, configured, dy_shape
+    from rrnet_amd import ops
+    with open(os.path.join(golden_dir, "conv_bwd_routes.json")) as fh:
+        golden = json.load(fh)
+    entry_route = {"rr_conv16_dgrad_s1_relumask": ("relumask", 1), "rr_head_dgrad_relubias": ("head", 0), "rr_conv16_dgrad_s1": ("conv16_s1", 1),
+                   "rr_conv16_dgrad_s2": ("conv16_s2", 1), "rr_conv_dgrad_s2_bf16": ("parity_s2", 1), "rr_conv_dgrad_s2_f16x3": ("parity_s2", 2),
+                   "rr_conv_dgrad": ("dgrad", 0)}
+    for stem, label in (("rr_conv_dgrad_s1_relubias", "relubias"), ("rr_conv_dgrad_s1_bnsum", "fprop_bnsum"), ("rr_conv_dgrad_s1", "fprop")):
+        for math, sfx in enumerate(("", "_bf16", "_f16x3")):
+            entry_route[stem + sfx] = (label, math)
+    seen = set()
+    for case in cases():
+        if case["op"] != "dgrad":
+            continue
+        want = entry_route[golden[case["id"]][-1][1]]
+        n, c, h, w = case["x"]
+        shapes = (dy_shape(case), (case["k"], c) + tuple(case["f"]), tuple(case["x"]), case["stride"], tuple(case["pad"]))
+        link = {"bn_z": "bn"}.get(case["link"], case["link"])
+        with configured(ops, case):
+            got = ops.dgrad_route(*shapes, link, bool({"y", "z"} & set(case["b16"])), link is not None, True)
+            takes = ops.dgrad16_takes(*shapes, relu_bias_link=link in ("relu_bias", "mask_only"))
+        assert got == want, (case["id"], got, want)
+        assert takes == (want[0] in ("conv16_s1", "conv16_s2")), case["id"]
+        seen.add(want[0])
+    assert seen == {"relumask", "head", "relubias", "conv16_s1", "fprop_bnsum", "fprop", "conv16_s2", "parity_s2", "dgrad"}
