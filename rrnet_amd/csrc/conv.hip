@@ -65,6 +65,7 @@ struct ConvArgs {
     int parity_order;  // dgrad, stride 2: 4 x 2 bits, parity class handled by blockIdx.y = 0..3 (most taps first)
     int parity;        // dgrad, stride 2: blockIdx.y = output parity class (h%2, w%2); only the taps that
                        // can reach that class are visited (1/2/2/4 of a 3x3) instead of masking 3/4 of the MFMAs
+    int dst32;         // destination below 2 GiB (launch_igemm): the epilogue addresses it with 32-bit buffer offsets
     int pos_major;     // fprop on tiny maps (the stage-2 head's 3x3 convolution on 3x3 RoI maps, fasterrcnn_detector.py:18
                        // -> Bottleneck.conv2): an M tile = ONE output pixel of 128 consecutive images, so the taps that
                        // fall into the padding are the same for every row of the tile and are skipped, not masked
@@ -86,8 +87,10 @@ __device__ __forceinline__ int xcd_remap(int bid, int nb)
 // that the plain kernel keeps its register budget (three workgroups per CU).
 // POSM: position-major M tiles (ConvArgs::pos_major); like BNS a separate instantiation — folded into the plain kernel
 // the extra state cost 20 registers and the third workgroup per CU (457 -> 466 ms per train step).
+// The pipelined instantiations are compiled FOR three workgroups per CU (168 registers): left to itself the allocator
+// follows the epilogue's appetite (220 with the accumulators in AGPRs), not the K loop's.
 template <int BN, int MODE, bool SCALAR, int BKT, int PIPE, bool BNS = false, bool POSM = false>
-__global__ __launch_bounds__(256, 1) void conv_igemm_kernel(const ConvArgs a)
+__global__ __launch_bounds__(256, PIPE == 2 ? 3 : 1) void conv_igemm_kernel(const ConvArgs a)
 {
     static_assert(BKT == 32 && (PIPE == 0 || PIPE == 2), "conv_igemm_kernel: K-step 32, PIPE 0 or 2");
     constexpr int WN = BN / 64 ? BN / 64 : 1;   // waves along N
@@ -562,15 +565,129 @@ __global__ __launch_bounds__(256, 1) void conv_igemm_kernel(const ConvArgs a)
     };
     const __amdgpu_buffer_rsrc_t bs_rs_y = bs_srd(BNS ? a.bs_y : a.src, (long)a.M * a.DC * 4);
     const __amdgpu_buffer_rsrc_t bs_rs_z = bs_srd(BNS && a.bs_z != nullptr ? a.bs_z : a.src, (long)a.M * a.DC * 4);
-    const int mode_e = a.ksplit > 1 ? 2 : (a.accumulate ? 1 : 0);   // wave-uniform: hoisted out of the store loops
+    // the destination through a buffer descriptor (dst32: below 2 GiB, set by launch_igemm): 32-bit byte offsets, and a lane
+    // whose row or column lies outside the tensor gets an out-of-range offset, so the buffer unit drops its store / atomic
+    // and answers its load with 0 — no exec-mask branch per element, hence nothing between consecutive stores
+    const __amdgpu_buffer_rsrc_t rs_dst = bs_srd(a.dst, a.dst32 ? (long)a.M * a.DC * 4 : 0);
+    constexpr unsigned OOBD = 0xFFFFFFF0u;
+    const int mode_e = a.ksplit > 1 ? 2 : (a.accumulate ? 1 : 0);   // wave-uniform: one branch around the whole epilogue
+    auto put_stats = [&](int j, float s1, float s2) {
+        double d1 = (double)s1, d2 = (double)s2;
+        d1 += __shfl_xor(d1, 32, 64);
+        d2 += __shfl_xor(d2, 32, 64);
+        if (lh == 0) {
+            const int cl = (wn * TN + j) * 32 + lr;
+            sred[(wm * BN + cl) * 2 + 0] = d1;
+            sred[(wm * BN + cl) * 2 + 1] = d2;
+        }
+    };
+    // One 32x32 accumulator tile at the byte offsets off[0..15] (OOBD: the element is outside the tensor).  mode is a
+    // literal at every call: 0 store, 1 add to the destination (its 16 loads go out first), 2 split-K float atomics.
+    auto put_tile = [&](const f32x16 &c, const unsigned (&off)[16], float bv, float &s1, float &s2, int mode)
+                        __attribute__((always_inline)) {
+        const bool relu = MODE == 0 && a.relu;
+        float v[16], old[16];
+        if (mode == 1) {
 #pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int ncol = n0 + (wn * TN + j) * 32 + lr;
-        const bool n_ok = ncol < a.DC;
-        const float bv = (MODE == 0 && a.bias != nullptr && n_ok) ? a.bias[ncol] : 0.f;
-        float s1 = 0.f, s2 = 0.f;
-        float bs_m = 0.f, bs_i = 0.f, bs_sc = 0.f, bs_sh = 0.f;
-        if constexpr (bnsum) {
+            for (int e = 0; e < 16; ++e)
+                old[e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_dst, off[e], 0, 0));
+        }
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            v[e] = c[e] + bv;
+            v[e] = (relu & !(v[e] > 0.f)) ? 0.f : v[e];
+        }
+        if (mode == 2) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e)      // partial sums of the K slices meet in a zeroed / running dst
+                __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(v[e], rs_dst, off[e], 0, 0);
+            return;
+        }
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            if (mode == 1) v[e] += old[e];
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v[e]), rs_dst, off[e], 0, 0);
+        }
+        if (MODE == 0) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {    // a dropped element adds +0 to both chains: s1, s2 never hold -0
+#pragma clang fp contract(off)                // the square is rounded before it is added, as it always was: slabs keep their bits
+                const float vm = off[e] != OOBD ? v[e] : 0.f;
+                s1 += vm;
+                s2 += vm * vm;
+            }
+        }
+    };
+    auto put_tiles = [&](int mode) __attribute__((always_inline)) {
+        if constexpr (MODE == 0) {
+            // consecutive rows of a tile are DC floats apart (position-major: one image apart)
+            const int rstride = POSM ? a.DH * a.DW * a.DC * 4 : a.DC * 4;
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+                const int ncol = n0 + (wn * TN + j) * 32 + lr;
+                const bool n_ok = ncol < a.DC;
+                const float bv = (a.bias != nullptr && n_ok) ? a.bias[ncol] : 0.f;
+                float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+                for (int i = 0; i < TM; ++i) {
+                    const int mrow = m0 + (wm * TM + i) * 32 + 4 * lh;        // first row of this lane half
+                    const int lim = n_ok ? Mloc - mrow : 0;                  // its rows below lim exist
+                    const unsigned base = (unsigned)(((POSM ? mrow * (a.DH * a.DW) + pm_pix : mrow) * a.DC + ncol) * 4);
+                    unsigned off[16];
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) {
+                        const int row = (e & 3) + 8 * (e >> 2);
+                        off[e] = row < lim ? base + (unsigned)(row * rstride) : OOBD;
+                    }
+                    put_tile(acc[i][j], off, bv, s1, s2, mode);
+                    __builtin_amdgcn_sched_barrier(0);      // one tile's offsets and values live at a time
+                }
+                if (do_stats) put_stats(j, s1, s2);
+            }
+        } else {
+            // data gradient: no statistics, so the row tiles go outside and the pixel of every row (parity classes: two
+            // divisions) is worked out once for all column tiles
+#pragma unroll
+            for (int i = 0; i < TM; ++i) {
+                unsigned roff[16];
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const int m = m0 + (wm * TM + i) * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
+                    int pix = m;
+                    if (a.parity) {
+                        const int hw = Hc * Wc;
+                        const int n = m / hw, rem = m - n * hw;
+                        const int h = rem / Wc;
+                        pix = (n * a.DH + (h * 2 + ph)) * a.DW + ((rem - h * Wc) * 2 + pw);
+                    }
+                    roff[e] = m < Mloc ? (unsigned)(pix * a.DC * 4) : OOBD;
+                }
+#pragma unroll
+                for (int j = 0; j < TN; ++j) {
+                    const int ncol = n0 + (wn * TN + j) * 32 + lr;
+                    const bool n_ok = ncol < a.DC;
+                    unsigned off[16];
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) off[e] = (n_ok & (roff[e] != OOBD)) ? roff[e] + (unsigned)(ncol * 4) : OOBD;
+                    float s1 = 0.f, s2 = 0.f;
+                    put_tile(acc[i][j], off, 0.f, s1, s2, mode);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+        }
+    };
+    // BNS: the producer's pre-BN output (and, for layers with a residual, its post-activation output) is fetched for a
+    // half-tile of 8 rows before the first dependent use, and with accum the destination's running values with them.  One
+    // per-lane byte offset (row of this lane half, its column), the row inside the tile goes through the buffer
+    // instruction's scalar offset: no 64-bit address per access, and columns past the end read 0 / drop their store.
+    // (The host sends only whole tiles here: the range check does not cover the scalar offset.)
+    auto put_tiles_bns = [&](bool accum) __attribute__((always_inline)) {
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            const int ncol = n0 + (wn * TN + j) * 32 + lr;
+            const bool n_ok = ncol < a.DC;
+            float s1 = 0.f, s2 = 0.f;
+            float bs_m = 0.f, bs_i = 0.f, bs_sc = 0.f, bs_sh = 0.f;
             if (n_ok && !a.bs_relu_bias) {
                 bs_m = a.bs_mean[ncol]; bs_i = a.bs_invstd[ncol];
                 if (a.bs_z == nullptr) {
@@ -578,82 +695,91 @@ __global__ __launch_bounds__(256, 1) void conv_igemm_kernel(const ConvArgs a)
                     else bs_sh = 1.f;          // a layer without ReLU: every element counts
                 }
             }
-        }
 #pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            if constexpr (bnsum) {
-                // Two half-tiles of 8 rows: the producer's pre-BN output (and, for layers with a residual, its
-                // post-activation output) is fetched for a half-tile before the first dependent use.  One per-lane
-                // byte offset (row of this lane half, its column), the row inside the tile goes through the buffer
-                // instruction's scalar offset: no 64-bit address per load, and rows past the end of the tensor read 0.
+            for (int i = 0; i < TM; ++i) {
                 const bool use_z = a.bs_z != nullptr;
-                const unsigned voff = n_ok ? (unsigned)(((m0 + (wm * TM + i) * 32 + 4 * lh) * a.DC + ncol) * 4) : 0xFFFFFFF0u;
+                const unsigned voff = n_ok ? (unsigned)(((m0 + (wm * TM + i) * 32 + 4 * lh) * a.DC + ncol) * 4) : OOBD;
 #pragma unroll
                 for (int hh = 0; hh < 2; ++hh) {
-                    float yv[8], zv[8];
+                    float yv[8], zv[8], old[8];
 #pragma unroll
                     for (int q = 0; q < 8; ++q) {
                         const int e = hh * 8 + q;
                         const int soff = __builtin_amdgcn_readfirstlane(((e & 3) + 8 * (e >> 2)) * a.DC * 4);
                         yv[q] = a.bs_relu_bias ? 0.f : __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(bs_rs_y, voff, soff, 0));
                         zv[q] = use_z ? __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(bs_rs_z, voff, soff, 0)) : 0.f;
+                        if (accum) old[q] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_dst, voff, soff, 0));
                     }
 #pragma unroll
                     for (int q = 0; q < 8; ++q) {
+#pragma clang fp contract(off)                        // every product of the chains is rounded on its own, as it always was
                         const int e = hh * 8 + q;
-                        const int m = m0 + (wm * TM + i) * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
-                        if (m < Mloc && n_ok) {
-                            float *p = a.dst + (long)m * a.DC + ncol;
-                            float v = acc[i][j][e];
-                            if (mode_e == 1) v += *p;
-                            const bool on = use_z ? zv[q] > 0.f : rr_bn_affine(yv[q], bs_sc, bs_sh) > 0.f;
-                            const float d = on ? v : 0.f;
-                            *p = a.bs_relu_bias ? d : v;
-                            s1 += d;
-                            s2 += d * ((yv[q] - bs_m) * bs_i);
-                        }
+                        const int soff = __builtin_amdgcn_readfirstlane(((e & 3) + 8 * (e >> 2)) * a.DC * 4);
+                        float v = acc[i][j][e];
+                        if (accum) v += old[q];
+                        const bool on = use_z ? zv[q] > 0.f : rr_bn_affine(yv[q], bs_sc, bs_sh) > 0.f;
+                        const float d = on ? v : 0.f;
+                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, a.bs_relu_bias ? d : v), rs_dst, voff, soff, 0);
+                        s1 += d;
+                        s2 += d * ((yv[q] - bs_m) * bs_i);
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                continue;
             }
+            if (do_stats) put_stats(j, s1, s2);
+        }
+    };
+    // destinations of 2 GiB and more: 64-bit addresses and a branch per element
+    auto put_tiles_wide = [&]() {
 #pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int row = (e & 3) + 8 * (e >> 2) + 4 * lh;
-                const int m = m0 + (wm * TM + i) * 32 + row;
-                float v = acc[i][j][e] + bv;
-                if (MODE == 0 && a.relu) v = v > 0.f ? v : 0.f;
-                if (m < Mloc && n_ok) {
-                    long pix = m;
-                    if constexpr (POSM) pix = (long)m * (a.DH * a.DW) + pm_pix;
-                    if (MODE == 1 && a.parity) {
-                        const int hw = Hc * Wc;
-                        const int n = m / hw, rem = m - n * hw;
-                        const int h = rem / Wc;
-                        pix = ((long)n * a.DH + (h * 2 + ph)) * a.DW + ((rem - h * Wc) * 2 + pw);
-                    }
-                    float *p = a.dst + pix * a.DC + ncol;
-                    if (mode_e == 2) {
-                        unsafeAtomicAdd(p, v);        // partial sums of the K slices meet in a zeroed / running dst
-                    } else {
-                        if (mode_e == 1) v += *p;
-                        *p = v;
-                        s1 += v;
-                        s2 += v * v;
+        for (int j = 0; j < TN; ++j) {
+            const int ncol = n0 + (wn * TN + j) * 32 + lr;
+            const bool n_ok = ncol < a.DC;
+            const float bv = (MODE == 0 && a.bias != nullptr && n_ok) ? a.bias[ncol] : 0.f;
+            float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+            for (int i = 0; i < TM; ++i) {
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const int row = (e & 3) + 8 * (e >> 2) + 4 * lh;
+                    const int m = m0 + (wm * TM + i) * 32 + row;
+                    float v = acc[i][j][e] + bv;
+                    if (MODE == 0 && a.relu) v = v > 0.f ? v : 0.f;
+                    if (m < Mloc && n_ok) {
+                        long pix = m;
+                        if constexpr (POSM) pix = (long)m * (a.DH * a.DW) + pm_pix;
+                        if (MODE == 1 && a.parity) {
+                            const int hw = Hc * Wc;
+                            const int n = m / hw, rem = m - n * hw;
+                            const int h = rem / Wc;
+                            pix = ((long)n * a.DH + (h * 2 + ph)) * a.DW + ((rem - h * Wc) * 2 + pw);
+                        }
+                        float *p = a.dst + pix * a.DC + ncol;
+                        if (mode_e == 2) {
+                            unsafeAtomicAdd(p, v);        // partial sums of the K slices meet in a zeroed / running dst
+                        } else {
+                            if (mode_e == 1) v += *p;
+                            *p = v;
+                            s1 += v;
+                            s2 += v * v;
+                        }
                     }
                 }
             }
+            if (do_stats) put_stats(j, s1, s2);
         }
-        if (do_stats) {
-            double d1 = (double)s1, d2 = (double)s2;
-            d1 += __shfl_xor(d1, 32, 64);
-            d2 += __shfl_xor(d2, 32, 64);
-            if (lh == 0) {
-                const int cl = (wn * TN + j) * 32 + lr;
-                sred[(wm * BN + cl) * 2 + 0] = d1;
-                sred[(wm * BN + cl) * 2 + 1] = d2;
-            }
-        }
+    };
+    if constexpr (bnsum) {
+        if (mode_e == 1) put_tiles_bns(true);
+        else put_tiles_bns(false);
+    } else if (!a.dst32) {
+        put_tiles_wide();
+    } else if (mode_e == 0) {
+        put_tiles(0);
+    } else if (mode_e == 1) {
+        put_tiles(1);
+    } else {
+        put_tiles(2);
     }
     if (do_stats) {
         __syncthreads();
@@ -1147,6 +1273,7 @@ template <int MODE>
 int launch_igemm(ConvArgs &a, int bn, bool scalar, int blocks, int gy, int gz, hipStream_t stream, const char *name)
 {
     const bool small = (long)a.N * a.SH * a.SW * a.SC * 4 < (1l << 31) && (long)a.wK * a.R * a.S * a.wC * 4 < (1l << 31);
+    a.dst32 = (long)a.M * a.DC * 4 < (1l << 31);
 #define IG(BNv, SCv, PIPEv, ...)                                                                                       \
     launch(conv_igemm_kernel<BNv, MODE, SCv, BK, PIPEv, ##__VA_ARGS__>, blocks, igemm_lds(bn, MODE == 1, PIPEv == 2 ? 1 : 2), \
            stream, a, name, gy, gz)
@@ -1236,8 +1363,10 @@ static int fprop_impl(const float *x, const float *w, const float *bias, float *
     // which the hardware's range check does not cover: in a partial last tile it would read up to 11 rows past the end of
     // the tensor.  Fused sums therefore only for M % 128 == 0 (every size the training configurations produce); other
     // sizes take the separate reduce pass below, and the masked-store mode — which has no such fallback — is refused.
-    const bool tiles_full = M % BM == 0;
-    RR_CHECK_ARG(bs == nullptr || !bs->relu_bias || tiles_full, "rr_conv_dgrad_s1_relubias: N*H*W = %ld must be a multiple of 128", M);
+    // The same epilogue reaches the destination and the producer's tensors through 32-bit offsets: below 2 GiB only.
+    const bool tiles_full = M % BM == 0 && M * k * 4 < (1l << 31);
+    RR_CHECK_ARG(bs == nullptr || !bs->relu_bias || tiles_full,
+                 "rr_conv_dgrad_s1_relubias: N*H*W = %ld must be a multiple of 128 and dx smaller than 2 GiB", M);
     if (bs != nullptr && ks == 1 && tiles_full) {      // sums in the epilogue; with split-K the complete values exist only afterwards
         a.stat_slab = bs->slab;
         a.bs_y = bs->y; a.bs_z = bs->z; a.bs_mean = bs->mean; a.bs_invstd = bs->invstd; a.bs_msc = bs->msc; a.bs_msh = bs->msh;
