@@ -564,7 +564,17 @@ int rr_sort_rows_by_score(const float *rows6, int n, float *out6, hipStream_t st
  *   order (rr_sort_rows_by_score's keys and network, one workgroup per frame).  out_off NULL: out6 [nframes,k,6],
  *   out_rows = nframes*k, rows behind count[f] are written as padding (class -1).  out_off [nframes+1] (exclusive
  *   prefix of count): out6 [out_rows,6] packed, frame f at row out_off[f].  xyxy != 0 writes x2 = x + w, y2 = y + h
- *   (the step in front of Soft-NMS, :222-223).  out6 != rows6. */
+ *   (the step in front of Soft-NMS, :222-223).  out6 != rows6.
+ * CenterNet's evaluation body (operators/centernet_operator.py:262-285: every scale once flipped, once plain):
+ * rr_prepare_frames_pair: rr_prepare_frames into out [2n,oh,ow,3]: images 0..n-1 are what rr_prepare_frames writes,
+ *   images n..2n-1 the same pixels mirrored in x, out[n+i][y][ow-1-x] = out[i][y][x] — the reference resizes first and
+ *   flips afterwards (:268-272), so the mirrored image carries the bits of the plain one.
+ * rr_merge_ctnet: rows6 [(pair ? 2 : 1)*nframes, k_in, 6] = CenterNet rows (x,y,w,h,score,cls+1) as rr_decode_topk
+ *   (box_mode 1) writes them.  Per frame f, appended in order at count[f] as rr_merge_scales does: with pair the rows of
+ *   image nframes+f (the flipped one) with x <- (img_w - x) - w (`flip_annos`, two fp32 subtractions; img_w = ow), then
+ *   the rows of image f.  A row is kept iff score > score_thr (`transform_bbox` always filters; NaN leaves); x,y,w,h
+ *   are each divided by div (IEEE) after the flip; w, h are not clamped.  Rows beyond k are dropped, count[f] <= k.
+ *   k <= RR_DETECT_MAX_ROWS; count[f] is clamped to [0,k] before it addresses anything. */
 #define RR_DETECT_MAX_ROWS 16384
 int rr_prepare_frames(const unsigned char *frames, const float *mean, const float *stdv, float *out, int n, int h,
                       int w, int oh, int ow, hipStream_t stream);
@@ -573,6 +583,10 @@ int rr_merge_scales(const float *rois, const float *reg, const float *scores, co
                     float *merged, int *count, int k, hipStream_t stream);
 int rr_sort_frames_by_score(const float *rows6, const int *count, const int *out_off, int nframes, int k, int xyxy,
                             float *out6, long out_rows, hipStream_t stream);
+int rr_prepare_frames_pair(const unsigned char *frames, const float *mean, const float *stdv, float *out, int n, int h,
+                           int w, int oh, int ow, hipStream_t stream);
+int rr_merge_ctnet(const float *rows6, int nframes, int k_in, int pair, float img_w, float div, float score_thr,
+                   float *merged, int *count, int k, hipStream_t stream);
 
 /* ---- evaluation: VisDrone AP / AR on the device ------------------------------------------------ *
  * rr_eval_match: utils/metrics/metrics.py:51-131 (`get_tp` with its `bbox_iou` calls) for f frames in one launch, one

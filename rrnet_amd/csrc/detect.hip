@@ -80,6 +80,99 @@ __global__ __launch_bounds__(DET_THREADS) void prepare_frames_kernel(const uint8
     }
 }
 
+// prepare_frames_kernel with a second, x-mirrored copy of every image behind the N plain ones: the flip of CenterNet's
+// test-time augmentation (operators/centernet_operator.py:268-272), which the reference applies AFTER the resize.  Each
+// pixel is therefore computed once, at its plain position, and stored twice: out[n][h][w] and out[N+n][h][OW-1-w].  The
+// lanes of a wave hold consecutive w, so the mirrored stores of a wave cover the same contiguous 64 * 12 bytes of a row as
+// its plain ones, in descending lane order: whole cache lines either way, no staging in LDS.
+__global__ __launch_bounds__(DET_THREADS) void prepare_frames_pair_kernel(const uint8_t *__restrict__ src,
+                                                                          const float *__restrict__ mean,
+                                                                          const float *__restrict__ stdv, float *__restrict__ out,
+                                                                          int N, int H, int W, int OH, int OW)
+{
+    __shared__ float lut[256 * 3];                       // as prepare_frames_kernel
+    for (int i = threadIdx.x; i < 256 * 3; i += DET_THREADS) {
+        const int v = i / 3, c = i - v * 3;
+        const float x = (float)v / 255.0f;
+        lut[i] = (x - mean[c]) / stdv[c];
+    }
+    __syncthreads();
+    const long total = (long)N * OH * OW;
+    const float sy = OH > 1 ? (float)(H - 1) / (float)(OH - 1) : 0.f;
+    const float sx = OW > 1 ? (float)(W - 1) / (float)(OW - 1) : 0.f;
+    for (long p = (long)blockIdx.x * DET_THREADS + threadIdx.x; p < total; p += (long)gridDim.x * DET_THREADS) {
+        long q = p;
+        const int w = (int)(q % OW); q /= OW;
+        const int h = (int)(q % OH);
+        const int n = (int)(q / OH);
+        const PrepTaps t = prep_taps(sy, sx, h, w, H, W);
+        const int y0 = min(max(t.y0, 0), H - 1), y1 = min(max(t.y1, 0), H - 1);
+        const int x0 = min(max(t.x0, 0), W - 1), x1 = min(max(t.x1, 0), W - 1);
+        const uint8_t *b = src + (long)n * H * W * 3;
+        const uint8_t *p00 = b + ((long)y0 * W + x0) * 3, *p01 = b + ((long)y0 * W + x1) * 3;
+        const uint8_t *p10 = b + ((long)y1 * W + x0) * 3, *p11 = b + ((long)y1 * W + x1) * 3;
+        float *o = out + p * 3;
+        float *m = out + ((((long)N + n) * OH + h) * OW + (OW - 1 - w)) * 3;      // 0 <= OW-1-w < OW, N+n < 2N
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float v = prep_bilinear(t, lut[p00[c] * 3 + c], lut[p01[c] * 3 + c], lut[p10[c] * 3 + c], lut[p11[c] * 3 + c]);
+            o[c] = v;
+            m[c] = v;
+        }
+    }
+}
+
+// One workgroup per frame: CenterNet rows (x, y, w, h, score, cls+1) of one scale, k_in per image as rr_decode_topk
+// (box_mode 1) writes them, -> `score > thr` (transform_bbox, :177) -> for the flipped image x = (img_w - x) - w
+// (flip_annos) -> x,y,w,h / div -> appended at merged[f][count[f]...], the flipped image's rows (image nframes + f) in
+// front of the plain one's (image f): the reference's concatenation order (:266-285).  Compaction as merge_scales_kernel.
+__global__ __launch_bounds__(DET_THREADS) void merge_ctnet_kernel(const float *rows, int nframes, int k_in, int pair, float img_w,
+                                                                  float div, float thr, float *merged, int *count, int K)
+{
+    __shared__ int wave_cnt[DET_THREADS / 64];
+    __shared__ int run;
+    const int f = blockIdx.x;
+    const int base0 = min(max(count[f], 0), K);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (threadIdx.x == 0) run = 0;
+    __syncthreads();
+    float *dst = merged + (long)f * K * 6;
+    for (int half = pair ? 1 : 0; half >= 0; --half) {   // 1: the flipped image, 0: the plain one
+        const float *src = rows + ((long)half * nframes + f) * k_in * 6;
+        for (int base = 0; base < k_in; base += DET_THREADS) {
+            const int i = base + threadIdx.x;
+            bool keep = false;
+            float o0 = 0.f, o1 = 0.f, o2 = 0.f, o3 = 0.f, sc = 0.f, cl = 0.f;
+            if (i < k_in) {
+                const float *q = src + (long)i * 6;
+                float x = q[0];
+                const float y = q[1], w = q[2], h = q[3];
+                sc = q[4];
+                cl = q[5];
+                if (half) x = (img_w - x) - w;           // flip_annos on the undivided row: two fp32 subtractions
+                o0 = x / div;                            // pred[:, :4] / scale on the host: IEEE division
+                o1 = y / div;
+                o2 = w / div;                            // not clamped: negative sizes pass, as in the reference
+                o3 = h / div;
+                keep = sc > thr;                         // NaN leaves
+            }
+            const unsigned long long m = __ballot(keep);
+            if (lane == 0) wave_cnt[wave] = __popcll(m);
+            __syncthreads();
+            int pos = base0 + run + __popcll(m & ((1ull << lane) - 1ull));
+            for (int wv = 0; wv < wave; ++wv) pos += wave_cnt[wv];
+            if (keep && pos < K) {
+                float *o = dst + (long)pos * 6;
+                o[0] = o0; o[1] = o1; o[2] = o2; o[3] = o3; o[4] = sc; o[5] = cl;
+            }
+            __syncthreads();
+            if (threadIdx.x == 0) run += wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+            __syncthreads();
+        }
+    }
+    if (threadIdx.x == 0) count[f] = min(base0 + run, K);
+}
+
 // One workgroup per frame: rows [frame_off[f], frame_off[f+1]) of one scale's packed stage-2 inputs -> generate_bbox rows
 // (x, y, w, h, score, cls+1), optional `score > thr`, x,y,w,h / div -> appended, order preserved, at merged[f][count[f]...].
 // Launches of successive scales are ordered by the stream, so count[f] needs no atomics.
@@ -208,6 +301,36 @@ extern "C" int rr_prepare_frames(const unsigned char *frames, const float *mean,
     hipLaunchKernelGGL(prepare_frames_kernel, dim3((unsigned)blocks), dim3(DET_THREADS), 0, stream, frames, mean, stdv, out, n, h,
                        w, oh, ow);
     RR_CHECK_LAUNCH("rr_prepare_frames");
+    return RR_OK;
+}
+
+extern "C" int rr_prepare_frames_pair(const unsigned char *frames, const float *mean, const float *stdv, float *out, int n,
+                                      int h, int w, int oh, int ow, hipStream_t stream)
+{
+    RR_CHECK_ARG(n > 0 && h > 0 && w > 0 && oh > 0 && ow > 0, "rr_prepare_frames_pair: bad dims");
+    RR_CHECK_ARG(frames && mean && stdv && out, "rr_prepare_frames_pair: null pointer");
+    const long total = (long)n * oh * ow;
+    long blocks = (total + DET_THREADS - 1) / DET_THREADS;
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(prepare_frames_pair_kernel, dim3((unsigned)blocks), dim3(DET_THREADS), 0, stream, frames, mean, stdv, out,
+                       n, h, w, oh, ow);
+    RR_CHECK_LAUNCH("rr_prepare_frames_pair");
+    return RR_OK;
+}
+
+extern "C" int rr_merge_ctnet(const float *rows6, int nframes, int k_in, int pair, float img_w, float div, float score_thr,
+                              float *merged, int *count, int k, hipStream_t stream)
+{
+    RR_CHECK_ARG(nframes >= 0 && k_in >= 0, "rr_merge_ctnet: negative size");
+    RR_CHECK_ARG(pair == 0 || pair == 1, "rr_merge_ctnet: pair %d", pair);
+    RR_CHECK_ARG(k > 0 && k <= DET_MAX_ROWS, "rr_merge_ctnet: %d rows per frame (limit %d)", k, DET_MAX_ROWS);
+    RR_CHECK_ARG(div > 0.0f, "rr_merge_ctnet: scale %g", (double)div);
+    if (nframes == 0) return RR_OK;
+    RR_CHECK_ARG(merged && count, "rr_merge_ctnet: null pointer");
+    RR_CHECK_ARG(k_in == 0 || rows6, "rr_merge_ctnet: null pointer");
+    hipLaunchKernelGGL(merge_ctnet_kernel, dim3(nframes), dim3(DET_THREADS), 0, stream, rows6, nframes, k_in, pair, img_w, div,
+                       score_thr, merged, count, k);
+    RR_CHECK_LAUNCH("rr_merge_ctnet");
     return RR_OK;
 }
 

@@ -13,7 +13,9 @@ Ordering note: decode emits rows score-descending, grouping / hard NMS are stabl
 (ties: torch.sort leaves them unspecified; here they keep decode order).
 
 `detect_frames` / `Detector` are the entry point from raw frames: the multi-scale evaluation body
-(operators/rrnet_operator.py:256-279) for a batch of equal-size uint8 frames."""
+(operators/rrnet_operator.py:256-279) for a batch of equal-size uint8 frames.  `detect_frames_centernet` /
+`CenterNetFrameDetector` are the same for CenterNet (operators/centernet_operator.py:262-285: every scale once flipped
+and once plain, both in one model pass)."""
 import os
 
 import torch
@@ -161,3 +163,103 @@ class Detector:
         nms = (not self.cfg.Val.auto_test) if nms is None else bool(nms)
         return detect_frames(self.model, frames_u8, scales, self.mean, self.std, nms=nms, k=k,
                              scale_factor=self.scale_factor, num_classes=self.num_classes, timer=timer)
+
+
+@torch.no_grad()
+def detect_frames_centernet(model, frames_u8, scales, mean, std, *, nms, flip=True, k=250, score_thr=0.01, scale_factor=4,
+                            num_classes=10, timer=None):
+    """CenterNet's multi-scale flip evaluation (operators/centernet_operator.py:262-285) on B equal-size frames.
+    frames_u8 uint8 [B,H,W,3] on the device, model = CenterNet in eval mode (fp32: CenterNet has no bf16 scope), scales =
+    cfg.Val.scales, mean / std = Normalize's, nms = `not cfg.Val.auto_test`, flip=False drops the flipped passes.
+    Per scale: one prepare (plain images 0..B-1, mirrored B..2B-1), ONE model pass on the 2B images, one decode of the last
+    stack's maps (k rows per image, box_mode 1), one merge.  A frame's rows are concatenated as the reference does: scale
+    by scale, flipped before plain, each filtered by `score > score_thr`, the flipped rows un-mirrored, x,y,w,h / scale.
+    -> (boxes [n,6], frame_off int32 [B+1]) on the device, frames back to back.
+      nms=False: x,y,w,h,score,cls+1, each frame stably sorted by score.
+      nms=True: `_ext_nms` (:222-236) after that sort: per-class gaussian Soft-NMS (sigma 0.5, Nt 0.7, threshold 0.1).
+        As in the reference the rows stay x1,y1,x2,y2,score,cls+1 (x2 = x + w) in class-ascending order; no second sort.
+    Host reads: none per scale; at the end the final counts (with nms also the packed row count and the error flag).
+    Raises ValueError when len(scales) * (2 if flip else 1) * k exceeds the LDS sort's 16384 rows, ZeroDivisionError where
+    soft_nms would.  timer as in detect_frames."""
+    if not torch.is_tensor(frames_u8) or frames_u8.dtype != torch.uint8:
+        raise TypeError("detect_frames_centernet: frames must be a uint8 tensor [B,H,W,3], got %s"
+                        % (frames_u8.dtype if torch.is_tensor(frames_u8) else type(frames_u8).__name__))
+    if frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
+        raise ValueError("detect_frames_centernet: frames must be [B,H,W,3], got %s" % (tuple(frames_u8.shape),))
+    scales = list(scales)
+    halves = 2 if flip else 1
+    rows_per_frame = len(scales) * halves * int(k)
+    if rows_per_frame > ops.DETECT_MAX_ROWS or rows_per_frame <= 0:
+        raise ValueError("detect_frames_centernet: %d scales x %d images x %d boxes = %d rows per frame (limit %d)"
+                         % (len(scales), halves, k, rows_per_frame, ops.DETECT_MAX_ROWS))
+    from rrnet_amd import _C
+    _C.require_cuda(frames_u8)
+    tick = timer if timer is not None else (lambda stage: None)
+    dev = frames_u8.device
+    frames_u8 = frames_u8.contiguous()
+    b = frames_u8.shape[0]
+    mean, std = _vec3(mean, dev), _vec3(std, dev)
+    merged, count = ops.merge_buffers(b, rows_per_frame, dev)
+    for s in scales:
+        x = (ops.prepare_frames_pair if flip else ops.prepare_frames)(frames_u8, mean, std, s)
+        tick('prepare')
+        hms, whs, regs = model(x)
+        tick('model')
+        rows = ops.decode_topk(ops.to_nhwc(hms[-1]), ops.to_nhwc(whs[-1]), ops.to_nhwc(regs[-1]), int(k), is_logits=True,
+                               box_mode=1, scale=float(scale_factor))
+        ops.merge_ctnet(rows, b, x.shape[3], s, merged, count, pair=flip, score_thr=score_thr)
+        tick('post')
+    out = finish_frames_centernet(merged, count, nms, num_classes)
+    tick('post')
+    return out
+
+
+@torch.no_grad()
+def finish_frames_centernet(merged, count, nms, num_classes=10):
+    """The cross-scale tail of detect_frames_centernet on the merged rows: merged [B,K,6] xywh rows, count int32 [B] ->
+    (boxes [n,6], frame_off int32 [B+1]).  Without nms finish_frames' stable sort; with nms `_ext_nms`
+    (operators/centernet_operator.py:222-236) behind that sort: per class ascending the gaussian Soft-NMS on x1,y1,x2,y2
+    rows, concatenated — the rows stay xyxy and are not sorted again, as in the reference."""
+    if not nms:
+        return finish_frames(merged, count, False, num_classes)
+    rows_per_frame = merged.shape[1]
+    ordered = ops.sort_frames_by_score(merged, count, xyxy=True)    # x2 = x + w as the kernel forms it; padding is dropped below
+    grouped, seg_off, seg_len = ops.group_by_class(ordered, num_classes, cls_base=1)
+    rows = grouped.view(-1, 6)
+    n_out, err = soft_nms_segments(rows, seg_off, rows_per_frame, sigma=0.5, Nt=0.7, threshold=0.1, method=2,
+                                   seg_len=seg_len, check=False)
+    _, _, _, out6, out_off = ops.pack_segments(rows, seg_off, n_out, num_classes, want_rois=False, want_rows=True,
+                                               want_offsets=True)   # its host read: the packed row count
+    frame_off = out_off[::num_classes].contiguous()
+    if int(err.item()) != 0:
+        raise ZeroDivisionError("float division")
+    return out6, frame_off
+
+
+class CenterNetFrameDetector:
+    """CenterNet from a reference-format checkpoint, ready for `detect`: the counterpart of Detector.  Builds CenterNet(cfg),
+    loads the state dict (with or without `module.` prefixes; checkpoint=None keeps the initial weights), sets eval mode
+    and channels-last; mean / std come from cfg.Val.transforms.  fp32 only."""
+
+    def __init__(self, cfg, checkpoint=None, device=None):
+        from rrnet_amd.datasets.augment import chain_params
+        from rrnet_amd.models.centernet import CenterNet
+        self.cfg = cfg
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        model = CenterNet(cfg)
+        if checkpoint is not None:
+            sd = torch.load(checkpoint, map_location='cpu') if isinstance(checkpoint, (str, os.PathLike)) else checkpoint
+            sd = {(key[7:] if key.startswith('module.') else key): v for key, v in sd.items()}
+            model.load_state_dict(sd)
+        self.model = model.to(self.device).to(memory_format=torch.channels_last).eval()
+        p = chain_params(cfg.Val.transforms)
+        self.mean, self.std = p["mean"], p["std"]
+        self.scale_factor = int(cfg.Train.scale_factor)
+        self.num_classes = int(cfg.num_classes)
+
+    def detect(self, frames_u8, scales=None, nms=None, flip=True, k=250, timer=None):
+        """frames uint8 [B,H,W,3] on the device -> (boxes [n,6], frame_off int32 [B+1]) as detect_frames_centernet."""
+        scales = self.cfg.Val.scales if scales is None else scales
+        nms = (not self.cfg.Val.auto_test) if nms is None else bool(nms)
+        return detect_frames_centernet(self.model, frames_u8, scales, self.mean, self.std, nms=nms, flip=flip, k=k,
+                                       scale_factor=self.scale_factor, num_classes=self.num_classes, timer=timer)

@@ -1539,6 +1539,36 @@ def merge_scales(rois, reg, scores, clses, frame_off, div, merged, count, scale=
                                       _C.stream()), "rr_merge_scales")
 
 
+def prepare_frames_pair(frames_u8, mean, std, scale_factor):
+    """rr_prepare_frames_pair: prepare_frames into logical [2B,3,oh,ow] (NHWC memory): images 0..B-1 are prepare_frames'
+    output, images B..2B-1 the same pixels mirrored in x (`flip_img` after the resize: the bits of the plain image)."""
+    import math
+    _C.require_cuda(frames_u8, mean, std)
+    assert frames_u8.dtype == torch.uint8 and frames_u8.is_contiguous() and frames_u8.dim() == 4 and frames_u8.shape[3] == 3
+    assert mean.dtype == torch.float32 and std.dtype == torch.float32 and mean.numel() == 3 and std.numel() == 3
+    assert mean.is_contiguous() and std.is_contiguous()
+    b, h, w, _ = frames_u8.shape
+    oh, ow = int(math.floor(h * scale_factor)), int(math.floor(w * scale_factor))
+    out = empty_nhwc(2 * b, 3, oh, ow, frames_u8.device)
+    _C.check(_C.fn("rr_prepare_frames_pair")(_C.ptr(frames_u8), _C.ptr(mean), _C.ptr(std), _C.ptr(out), b, h, w, oh, ow,
+                                             _C.stream()), "rr_prepare_frames_pair")
+    return out
+
+
+def merge_ctnet(rows, nframes, img_w, div, merged, count, pair=True, score_thr=0.01):
+    """rr_merge_ctnet: one scale's CenterNet rows [(2 if pair else 1)*nframes, k_in, 6] (decode_topk, box_mode=1) -> per
+    frame the flipped image's rows (image nframes+f, x <- (img_w - x) - w) then the plain image's, kept when score >
+    score_thr, x,y,w,h / div (IEEE), appended to merged [nframes,K,6] at count [nframes] (in place, see merge_buffers)."""
+    _C.require_cuda(rows, merged, count)
+    b, k, six = merged.shape
+    assert b == nframes and six == 6 and merged.dtype == torch.float32 and merged.is_contiguous() and 0 < k <= DETECT_MAX_ROWS
+    assert count.dtype == torch.int32 and count.numel() == b and count.is_contiguous()
+    assert rows.dtype == torch.float32 and rows.is_contiguous() and rows.dim() == 3 and rows.shape[2] == 6
+    assert rows.shape[0] == (2 if pair else 1) * nframes
+    _C.check(_C.fn("rr_merge_ctnet")(_C.ptr(rows), nframes, rows.shape[1], int(bool(pair)), float(img_w), float(div),
+                                     float(score_thr), _C.ptr(merged), _C.ptr(count), k, _C.stream()), "rr_merge_ctnet")
+
+
 def sort_frames_by_score(rows6, count, out_off=None, xyxy=False):
     """rr_sort_frames_by_score: rows6 [B,K,6], count int32 [B] -> every frame's first count[f] rows by score descending
     (ties keep row order).  out_off None: [B,K,6], padding (class -1) behind the sorted rows.  out_off int32 [B+1]

@@ -12,8 +12,13 @@ decode to the last result file and ends in a device synchronise.  Device time pe
 comes from HIP events recorded between the stages of detect_frames; writer time is host time inside write_results /
 save_result.  One JSON line on stdout; --out writes the object to a file.
 
+--centernet measures the other detector the same way: hourglass-104 CenterNet (centernet_config: six scales, each run
+flipped and plain, auto_test=True), the per-frame path DeviceValLoader -> CenterNetOperator.evaluate_images -> save_result
+against detect_frames_centernet; fp32 only (CenterNet has no bf16 scope).  Random weights keep all 250 boxes of each of the
+twelve passes: 3000 rows per frame.
+
   python tools/bench_detect.py [--frames 32] [--window-frames 8] [--windows 3] [--batches 1,2,4] [--modes f32,bf16]
-                               [--nms] [--out profiles/detect.json]"""
+                               [--nms] [--centernet] [--out profiles/detect.json]"""
 import argparse
 import copy
 import json
@@ -76,6 +81,7 @@ def main(argv=None):
     ap.add_argument("--batches", default="1,2,4")
     ap.add_argument("--modes", default="f32,bf16")
     ap.add_argument("--nms", action="store_true", help="auto_test=False: score filter and Soft-NMS (default: the config's raw mode)")
+    ap.add_argument("--centernet", action="store_true", help="CenterNet (centernet_config) instead of RRNet; fp32 only")
     ap.add_argument("--backbone", default=None, help="override cfg.Model.backbone (rehearsals)")
     ap.add_argument("--out")
     args = ap.parse_args(argv)
@@ -84,17 +90,25 @@ def main(argv=None):
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("tools/bench_detect.py measures on the GPU; there is nothing to measure without one")
-    from rrnet_amd.configs.rrnet_config import Config
     from rrnet_amd.datasets.augment import DeviceValLoader, chain_params
     from rrnet_amd.datasets.frames import SizeBucketedFrames
-    from rrnet_amd.inference import Detector
-    from rrnet_amd.operators.rrnet_operator import RRNetOperator
+    if args.centernet:
+        from rrnet_amd.configs.centernet_config import Config
+        from rrnet_amd.inference import CenterNetFrameDetector as Detector
+        from rrnet_amd.operators.centernet_operator import CenterNetOperator as Operator
+        args.modes = "f32"
+    else:
+        from rrnet_amd.configs.rrnet_config import Config
+        from rrnet_amd.inference import Detector
+        from rrnet_amd.operators.rrnet_operator import RRNetOperator as Operator
 
     pool = GeneratedFrames(args.frames)
     out_dir = tempfile.mkdtemp(prefix="bench_detect_")
-    result = {"metric": "frames/sec, raw frame -> result file (multi-scale RRNet detection)", "unit": "frames/sec",
+    result = {"metric": "frames/sec, raw frame -> result file (multi-scale %s detection)"
+                        % ("CenterNet flip" if args.centernet else "RRNet"), "unit": "frames/sec",
               "higher_is_better": True, "data": "generated %dx%d frames, pool of %d" % (FRAME_W, FRAME_H, args.frames),
-              "weights": "random: all 1500 boxes of every scale survive, the worst case for the tail and the writer",
+              "weights": "random: all %s boxes of every %s survive, the worst case for the tail and the writer"
+                         % (("250", "pass (two per scale)") if args.centernet else ("1500", "scale")),
               "windows": args.windows, "window_frames": args.window_frames, "modes": {}}
 
     for mode in args.modes.split(","):
@@ -110,8 +124,12 @@ def main(argv=None):
         det = Detector(cfg)
         params = chain_params(cfg.Val.transforms)
         ns = types.SimpleNamespace(cfg=cfg, model=det.model)
-        ns.generate_bbox = types.MethodType(RRNetOperator.generate_bbox, ns)
-        ns._ext_nms, ns._ext_nms_device = RRNetOperator._ext_nms, RRNetOperator._ext_nms_device
+        if args.centernet:
+            ns.transform_bbox = types.MethodType(Operator.transform_bbox, ns)
+            ns._ext_nms = Operator._ext_nms
+        else:
+            ns.generate_bbox = types.MethodType(Operator.generate_bbox, ns)
+            ns._ext_nms, ns._ext_nms_device = Operator._ext_nms, Operator._ext_nms_device
         entry = {"scales": list(cfg.Val.scales), "nms": nms, "backbone": cfg.Model.backbone}
 
         def per_frame_window(w):
@@ -121,9 +139,9 @@ def main(argv=None):
             with torch.no_grad():
                 for imgs, _, names in DeviceValLoader(Window(pool, w * args.window_frames, args.window_frames), params,
                                                       num_workers=8):
-                    pred = RRNetOperator.evaluate_images(ns, imgs)
+                    pred = Operator.evaluate_images(ns, imgs)
                     t1 = time.perf_counter()
-                    RRNetOperator.save_result(os.path.join(out_dir, names[0] + ".txt"), pred)
+                    Operator.save_result(os.path.join(out_dir, names[0] + ".txt"), pred)
                     writer += time.perf_counter() - t1
                     boxes += pred.shape[0]
             torch.cuda.synchronize()
@@ -146,7 +164,7 @@ def main(argv=None):
                 rows, off = pred.cpu().numpy(), frame_off.cpu().tolist()
                 t1 = time.perf_counter()
                 for i, name in enumerate(names):
-                    RRNetOperator.write_results(os.path.join(out_dir, name + ".txt"), rows[off[i]:off[i + 1]])
+                    Operator.write_results(os.path.join(out_dir, name + ".txt"), rows[off[i]:off[i + 1]])
                 writer += time.perf_counter() - t1
                 boxes += rows.shape[0]
             torch.cuda.synchronize()
