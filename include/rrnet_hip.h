@@ -391,6 +391,15 @@ int rr_wh_shift_sum_bwd(const float *dout, float *dt, int n, int h, int w, int k
  * double and rounded once (step counts from 1). */
 int rr_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long n, double lr,
                  double beta1, double beta2, float eps, int step, float grad_scale, hipStream_t stream);
+/* Copy and fingerprint of a training-state buffer in one pass (full-state checkpoints, rrnet_amd/checkpoint.py).
+ * src: n fp32 words; dst: n words, or NULL = digest only; chunk: elements per digest record, positive and a multiple of
+ * 4; digest: ceil(n / chunk) records of three 64-bit words, written, not accumulated.  With u_j the bit pattern
+ * (unsigned 32-bit) of element c*chunk + j, the record of chunk c is
+ *   d0 = sum u_j mod 2^64,   d1 = sum (j+1) * u_j mod 2^64,   d2 = #{ j : (u_j & 0x7f800000) == 0x7f800000 } (NaN, +-Inf).
+ * Integer sums: the digest is the same for every grid and wave layout; d1 makes it sensitive to position.
+ * dst receives the bits of src unchanged (copied as integers: NaN payloads, -0.0, denormals); words of dst beyond n
+ * are not written.  src and dst must be 16-byte aligned.  n >= 0; n == 0 launches nothing and succeeds. */
+int rr_state_snapshot(const float *src, float *dst, long n, long chunk, unsigned long long *digest, hipStream_t stream);
 
 /* ---- losses --------------------------------------------------------------------------- *
  * rr_focal_loss_fwd/bwd: clamp(sigmoid(x),1e-4,1-1e-4) + focal_loss_for_hm of

@@ -348,6 +348,20 @@ class _AugmentLoader:
         d = self.sampler.sample(annotations, image.size[1], image.size[0], epoch, index, roadmap)
         return image, annotations, name, d
 
+    def position(self):
+        """Batches handed out so far."""
+        return self.i
+
+    def seek(self, n):
+        """The next get_batch() returns what a fresh loader returns as its n-th batch: every sample is a function of
+        (seed, rank, epoch, index), so dropping the work queued for other positions is all there is to do.  Jobs already
+        running finish on their threads and their results are discarded."""
+        for fs in self.futures.values():
+            for f in fs:
+                f.cancel()
+        self.futures = {}
+        self.i = int(n)
+
     def close(self):
         self.pool.shutdown(wait=True, cancel_futures=True)
 
@@ -503,6 +517,12 @@ class DeviceAugmentLoader(_AugmentLoader):
                                                    self.p["scale_factor"], self.p["cls_num"])
         self._prefetch(i + 1)
         return imgs, annos, hm, wh, ind, off, mask, names
+
+    def seek(self, n):
+        """As _AugmentLoader.seek, and the device prefetch is redone for batch n: _prefetch waits for the copy that last
+        read the pinned slot and orders the new copy behind the kernels that last read the device slot."""
+        super().seek(n)
+        self._prefetch(self.i)
 
 
 class DeviceValLoader:

@@ -80,6 +80,14 @@ class SyntheticDronesDET:
         self.i += 1
         return (b[0], b[1].clone()) + tuple(b[2:])
 
+    def position(self):
+        """Batches handed out so far."""
+        return self.i
+
+    def seek(self, n):
+        """The next get_batch() returns what a fresh loader returns as its n-th batch."""
+        self.i = int(n)
+
     def __len__(self):
         return len(self.pool)
 
@@ -145,6 +153,16 @@ class HostFedDronesDET:
         batch = (imgs, annos.clone(), hm, wh, ind, off, mask, self.host[i % len(self.host)][3])
         self._prefetch(i + 1)
         return batch
+
+    def position(self):
+        """Batches handed out so far."""
+        return self.i
+
+    def seek(self, n):
+        """The next get_batch() returns what a fresh loader returns as its n-th batch: the copy of batch n is started into
+        its slot, ordered behind the copy in flight (same copy stream) and behind the step that last read that slot."""
+        self.i = int(n)
+        self._prefetch(self.i)
 
     def __len__(self):
         return len(self.host)

@@ -72,3 +72,33 @@ class BaseOperator(object):
         """Same file format as the reference: state_dict of the bare module, reference key names."""
         sd = {k: v.detach().cpu().contiguous() for k, v in models.state_dict().items()}
         torch.save(sd, os.path.join(path, 'ckp-{}.pth'.format(step)))
+
+    # ---- full-state checkpoints (rrnet_amd/checkpoint.py; opt-in through cfg.Train.full_state / cfg.Train.resume) ----
+    _state_writer = None
+
+    def save_state(self, step, log_dir=None):
+        """Enqueue a copy of the whole training state after step `step` and return; `state-{step}.pth` appears in
+        `log_dir` (default: where save_ckp writes) once the writer's thread is done.  Needs `self.optimizer` (FlatAdam)."""
+        from rrnet_amd.checkpoint import StateWriter
+        if self._state_writer is None:
+            log_dir = log_dir or os.path.join('./log', self.cfg.log_prefix)
+            self._state_writer = StateWriter(self.model.module, self.optimizer, log_dir, self.lr_sch,
+                                             getattr(self, "training_loader", None),
+                                             keep=getattr(self.cfg.Train, "keep_states", 2))
+        self._state_writer.save_state(step)
+
+    def load_state(self, path):
+        """Load a state file into the live model, optimizer, scheduler and training loader -> the step to continue at."""
+        from rrnet_amd.checkpoint import load_state
+        return load_state(path, self.model.module, self.optimizer, self.lr_sch, getattr(self, "training_loader", None))
+
+    def resume_state(self, where, log_dir):
+        """cfg.Train.resume ('auto' or a path) -> the step training_process starts at."""
+        from rrnet_amd.checkpoint import resume
+        return resume(where, log_dir, self.model.module, self.optimizer, self.lr_sch, getattr(self, "training_loader", None))
+
+    def close_state(self):
+        """Wait for the state file in flight, stop the writer's thread (re-raises what it raised)."""
+        writer, self._state_writer = self._state_writer, None
+        if writer is not None:
+            writer.close()

@@ -96,7 +96,13 @@ class RRNetOperator(BaseOperator):
         self.model.train()
         totals = np.zeros(5)
         log_dir = os.path.join('./log', self.cfg.log_prefix)
-        for step in range(self.cfg.Train.iter_num):
+        # builder-defined, opt-in (the config modules do not carry the keys): cfg.Train.full_state = True writes a full
+        # training state beside every checkpoint; cfg.Train.resume = 'auto' | <path> continues from one.  The running sums
+        # of the print interval are not part of a state: the first report after a resume averages over fewer steps
+        full_state = bool(getattr(self.cfg.Train, "full_state", False))
+        resume = getattr(self.cfg.Train, "resume", None)
+        start_step = self.resume_state(resume, log_dir) if resume else 0
+        for step in range(start_step, self.cfg.Train.iter_num):
             batch = self.training_loader.get_batch()
             outs, losses = self.train_step(step, batch)
             totals += np.array([float(l.detach()) for l in losses])
@@ -113,6 +119,9 @@ class RRNetOperator(BaseOperator):
                 if step % ci == ci - 1 or step == self.cfg.Train.iter_num - 1:
                     os.makedirs(log_dir, exist_ok=True)
                     self.save_ckp(self.model.module, step, log_dir)
+                    if full_state:
+                        self.save_state(step, log_dir)
+        self.close_state()
 
     def generate_bbox(self, outs, batch_idx=0):
         """rrnet_operator.py:188-209 -> (stage-1 boxes [n,6] xywh cls=0, stage-2 boxes [n,6] xywh cls+1)."""

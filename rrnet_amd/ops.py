@@ -1210,6 +1210,30 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, gra
                                    _C.stream()), "rr_adam_step")
 
 
+def state_snapshot(src, dst=None, chunk=65536, n=None, out=None):
+    """rr_state_snapshot on the current stream: copies the fp32 words of `src` into `dst` (None: no copy) as bits and
+    returns the digest, int64 [ceil(n / chunk), 3] holding the uint64 records (d0, d1, d2) of include/rrnet_hip.h.
+    `n` defaults to src.numel(); `out`: a preallocated digest tensor of that shape (a checkpoint writer keeps one)."""
+    _C.require_cuda(src, dst)
+    if src.dtype != torch.float32 or not src.is_contiguous() or src.dim() != 1:
+        raise _C.RRNetHipError("state_snapshot: src must be a flat contiguous float32 tensor")
+    n = src.numel() if n is None else int(n)
+    if n > src.numel():
+        raise _C.RRNetHipError("state_snapshot: n = %d exceeds src (%d words)" % (n, src.numel()))
+    if dst is not None and (dst.dtype != torch.float32 or not dst.is_contiguous() or dst.numel() < n):
+        raise _C.RRNetHipError("state_snapshot: dst must be a contiguous float32 tensor of at least n words")
+    chunk = int(chunk)
+    nchunks = (n + chunk - 1) // chunk if n > 0 and chunk > 0 else 0
+    if out is not None:
+        if out.dtype != torch.int64 or not out.is_contiguous() or tuple(out.shape) != (nchunks, 3) or out.device != src.device:
+            raise _C.RRNetHipError("state_snapshot: out must be a contiguous int64 [%d, 3] tensor on %s" % (nchunks, src.device))
+    digest = out if out is not None and nchunks else \
+        torch.empty((max(nchunks, 1), 3), dtype=torch.int64, device=src.device)        # never a NULL pointer, also for n == 0
+    _C.check(_C.fn("rr_state_snapshot")(_C.ptr(src), _C.ptr(dst), n, chunk, _C.ptr(digest), _C.stream()),
+             "rr_state_snapshot")
+    return digest[:nchunks]
+
+
 # ---------------------------------------------------------------------------------------------
 # losses
 # ---------------------------------------------------------------------------------------------

@@ -1,0 +1,98 @@
+"""Train RRNet or CenterNet on one GPU: the counterpart of tools/detect.py.
+
+  python tools/train.py --config rrnet_config|rrnet_fillduck_config|centernet_config [--data-root D] [--iters N]
+                        [--batch B] [--crop H W] [--backbone NAME] [--bf16] [--full-state] [--resume auto|PATH]
+                        [--checkpoint-interval N] [--print-interval N] [--keep-states N]
+
+A single process: it sets the config keys and calls the operator's training_process().  Without a dataset under
+--data-root the synthetic loader feeds the loop.  `ckp-{step}.pth` (weights, the reference's format) goes to
+./log/<log_prefix>/ every --checkpoint-interval steps; --full-state writes `state-{step}.pth` beside each of them
+(parameters, Adam moments, scheduler, BatchNorm buffers, step, loader position; rrnet_amd/checkpoint.py) and
+--resume continues from one: `auto` takes the newest state of the log directory that loads and verifies."""
+import argparse
+import copy
+import importlib
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+CONFIGS = ("rrnet_config", "rrnet_fillduck_config", "centernet_config")
+
+
+def load_config(name):
+    if name not in CONFIGS:
+        raise SystemExit("unknown config %r (one of %s)" % (name, ", ".join(CONFIGS)))
+    return copy.deepcopy(importlib.import_module("rrnet_amd.configs." + name).Config)
+
+
+def parse(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--config", default="rrnet_config")
+    ap.add_argument("--data-root")
+    ap.add_argument("--iters", type=int)
+    ap.add_argument("--batch", type=int)
+    ap.add_argument("--crop", type=int, nargs=2, metavar=("H", "W"))
+    ap.add_argument("--backbone")
+    ap.add_argument("--bf16", action="store_true")
+    ap.add_argument("--full-state", action="store_true")
+    ap.add_argument("--resume", metavar="auto|PATH")
+    ap.add_argument("--checkpoint-interval", type=int)
+    ap.add_argument("--print-interval", type=int)
+    ap.add_argument("--keep-states", type=int)
+    return ap.parse_args(argv)
+
+
+def configure(args):
+    """The config the arguments describe (a deep copy of the named module's Config)."""
+    cfg = load_config(args.config)
+    if args.bf16 and args.config.startswith("centernet"):
+        raise SystemExit("--bf16: CenterNet runs in fp32 only (the model has no bf16 scope)")
+    if args.data_root is not None:
+        cfg.data_root = args.data_root
+    if args.iters is not None:
+        cfg.Train.iter_num = args.iters
+    if args.batch is not None:
+        cfg.Train.batch_size = args.batch
+    if args.crop is not None:
+        from rrnet_amd.datasets.transforms import RandomCrop
+        cfg.Train.crop_size = tuple(args.crop)
+        chain = cfg.Train.transforms.transforms
+        for i, t in enumerate(chain):               # the real-data loader takes the crop from the chain, as the reference does
+            if isinstance(t, RandomCrop):
+                chain[i] = RandomCrop(tuple(args.crop))
+    if args.backbone is not None:
+        cfg.Model.backbone = args.backbone
+    if args.bf16:
+        cfg.Model.bf16 = True
+    if args.checkpoint_interval is not None:
+        cfg.Train.checkpoint_interval = args.checkpoint_interval
+    if args.print_interval is not None:
+        cfg.Train.print_interval = args.print_interval
+    if args.keep_states is not None:
+        cfg.Train.keep_states = args.keep_states
+    if args.full_state:
+        cfg.Train.full_state = True
+    if args.resume is not None:
+        cfg.Train.resume = args.resume
+    cfg.Distributed.gpu_id, cfg.Distributed.rank, cfg.Distributed.world_size = 0, 0, 1
+    return cfg
+
+
+def main(argv=None):
+    args = parse(argv)
+    cfg = configure(args)
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("tools/train.py needs the GPU (there is no CPU path)")
+    torch.cuda.set_device(0)
+    if args.config.startswith("centernet"):
+        from rrnet_amd.operators.centernet_operator import CenterNetOperator as Operator
+    else:
+        from rrnet_amd.operators.rrnet_operator import RRNetOperator as Operator
+    Operator(cfg).training_process()
+
+
+if __name__ == "__main__":
+    main()
