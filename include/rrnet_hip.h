@@ -278,6 +278,7 @@ int rr_conv_dgrad_s2_bf16(const float *dy, const float *w, float *dx, int n, int
  * mean/invstd (saved for backward), scale/shift (for rr_bn_apply), running stats updated with
  * `momentum` and the unbiased variance, num_batches_tracked (optional int64 counter) incremented.
  * rr_bn_apply: out = relu?(y*scale+shift [+ res | + res*res_scale+res_shift]).
+ *   Its ReLU hands a NaN on (v <= 0 ? 0 : v), as ATen's does: a poisoned statistic stays visible in the activation.
  * rr_bn_bwd_reduce: sums[2][c] = per-channel sum(dy), sum(dy*xhat), dy = dz*(z>0) if z; with z NULL and
  *   mask_scale/mask_shift given the ReLU mask is recomputed as (y*scale+shift > 0) — layers without a
  *   residual input need not re-read their output.  sums_zeroed != 0: the caller hands in zeroed sums (the host

@@ -142,6 +142,8 @@ __global__ void bn_eval_coeffs_kernel(const float *gamma, const float *beta, con
 }
 
 // out = relu?( y*scale+shift  [+ res | + res*res_scale+res_shift] )
+// The ReLU keeps what does not compare (`v <= 0 ? 0 : v`): a NaN in y, in the statistics or in the residual stays a NaN in the
+// activation and in its bf16 image, as ATen's relu leaves it; `v > 0 ? v : 0` turned a poisoned channel into zeros.
 // AMAX: also max |out| -> *amax as a bit pattern (one atomicMax per wave) — the next convolution's operand scale when it
 // runs on the split-operand kernels (rr_conv_*_f16x3), saved a pass of rr_absmax_bits over the tensor
 template <bool AMAX>
@@ -168,7 +170,7 @@ __global__ __launch_bounds__(EW_THREADS) void bn_apply_kernel(const f32x4 *y, co
         }
         if (relu) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
+            for (int e = 0; e < 4; ++e) v[e] = v[e] <= 0.f ? 0.f : v[e];
         }
         if (out) out[i] = v;
         if (out16) out16[i] = to_bf16x4(v);      // the bf16 image the next convolution reads (csrc/conv16.hip)
@@ -408,7 +410,7 @@ __global__ __launch_bounds__(EW_THREADS) void relu_fwd_kernel(const f32x4 *x, f3
     for (long i = (long)blockIdx.x * EW_THREADS + threadIdx.x; i < n4; i += (long)gridDim.x * EW_THREADS) {
         f32x4 v = x[i];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
+        for (int e = 0; e < 4; ++e) v[e] = v[e] <= 0.f ? 0.f : v[e];      // (a NaN stays a NaN: see bn_apply_kernel)
         out[i] = v;
     }
 }

@@ -401,7 +401,9 @@ def phantom_f32(shape, device, image):
     stub = _PHANTOM_STUB.get(device)
     if stub is None:
         stub = _PHANTOM_STUB[device] = torch.full((2,), float("nan"), dtype=torch.float32, device=device)
-    t = stub[1:].expand(shape)                            # (element 1 of 2: is_phantom's signature)
+    # (a 0-dim view of element 1 of 2: expanding the 1-element slice stub[1:] kept stride 1 on a last dimension of size 1, so a
+    # handle of width 1 failed is_phantom's all-zero-strides test and its consumer read the stub as if it were the data)
+    t = stub[1].expand(shape)
     t._rr_b16 = (t._version, torch.cuda.current_stream(device).cuda_stream if device.type == "cuda" else None, image)
     return t
 

@@ -800,3 +800,106 @@ def conv_grid_routes():
     n, c, h, w, k, r, s, st, ph, pw, oh, ow = CONV64_ASYM_WGRAD
     seen["wgrad"] |= conv_routes(n, c, h, w, k, r, s, st, (ph, pw), False, False, False, oh, ow)["wgrad"]
     return seen
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# BatchNorm forward / ReLU-mask agreement (tests/test_bn_forward_gpu.py; tests/test_bn_mask_host.py checks the builder).
+# ------------------------------------------------------------------------------------------------------------------
+def bf16_exact(a):
+    """float32 array -> the same values rounded to bfloat16 (nearest even), as float32."""
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(torch.bfloat16).float().numpy()
+
+
+def bf16_half_ulp(v):
+    """Half a bfloat16 ulp at magnitude v (float64 array, normal range): the most a round-to-nearest conversion of a value of
+    that magnitude can move it.  bfloat16 keeps 8 significant bits, its ulp at v is 2^(floor(log2 v) - 7)."""
+    v = np.maximum(np.abs(np.asarray(v, dtype=np.float64)), 2.0 ** -126)
+    return 2.0 ** (np.floor(np.log2(v)) - 8.0)
+
+
+def bn_mask_edge_inputs(seed, c, pixels, bf16=False):
+    """Inputs that sit ON the ReLU edge of y * sc + sh: per channel sc ~ N(1, 0.3), sh ~ N(0, 0.5) (float32), y0 = fl32(-sh / sc),
+    every element y0 stepped by k in [-3, 3] float32 ulps.  The exact value y * sc + sh is then a few ulps of sh: a 48-bit product
+    plus a 24-bit addend of like exponent, representable in float64, so `exact` below IS exact and `mask = exact > 0` leaves no
+    element out.  A mul + add that rounds the product first (fl(fl(y * sc) + sh)) gets the sign wrong on a few per cent of such a
+    set (muladd32_mask; measured 6.4 % at seed 7, c 64, pixels 4096); one explicit fma never does.
+    bf16: y holds bfloat16 values (y0 rounded to bfloat16, steps of bfloat16 ulps) so that it can live as a bf16 image only; sh is
+    then re-centred to fl32(-y0 * sc), which puts the k = 0 elements on the rounding residue of that product (the others lie
+    2^-8 |sh| away from the edge).
+    -> dict: y, dz [pixels, c] float32 (dz: magnitude in [0.5, 1.5], random sign), sc, sh [c] float32, exact [pixels, c]
+    float64, mask [pixels, c] bool."""
+    rng = np.random.default_rng(seed)
+    sc = rng.normal(1.0, 0.3, c).astype(np.float32)
+    sh = rng.normal(0.0, 0.5, c).astype(np.float32)
+    sc[np.abs(sc) < 0.05] = 0.05                       # (a scale next to zero would send y0 towards overflow)
+    sh[sh == 0.0] = 0.25
+    y0 = (-sh.astype(np.float64) / sc.astype(np.float64)).astype(np.float32)
+    ulp = 1
+    if bf16:
+        y0 = bf16_exact(y0)
+        sh = (-(y0.astype(np.float64) * sc.astype(np.float64))).astype(np.float32)
+        ulp = 1 << 16
+    k = rng.integers(-3, 4, (pixels, c))
+    bits = np.broadcast_to(y0.view(np.int32)[None, :], (pixels, c)).astype(np.int64)
+    bits = bits + k * ulp * np.sign(y0).astype(np.int64)[None, :]       # the integer view moves the MAGNITUDE: k ulps of value
+    y = bits.astype(np.int32).view(np.float32)
+    if bf16:
+        assert np.array_equal(bf16_exact(y), y)
+    dz = (rng.uniform(0.5, 1.5, (pixels, c)) * rng.choice([-1.0, 1.0], (pixels, c))).astype(np.float32)
+    exact = y.astype(np.float64) * sc.astype(np.float64)[None, :] + sh.astype(np.float64)[None, :]
+    return dict(y=y, dz=dz, sc=sc, sh=sh, exact=exact, mask=exact > 0.0, k=k)
+
+
+def muladd32_mask(y, sc, sh):
+    """The sign a float32 multiply followed by a float32 add gives (the product rounded on its own): what a kernel that lost its
+    explicit fma and was compiled without contraction would compute."""
+    return ((y * sc[None, :]).astype(np.float32) + sh[None, :]).astype(np.float32) > 0.0
+
+
+def nhwc_from_rows(a, n=1):
+    """[pixels, c] array -> torch tensor of logical shape [n, c, 1, pixels / n] over the same NHWC memory."""
+    t = torch.from_numpy(np.ascontiguousarray(a))
+    p, c = t.shape
+    return t.view(n, 1, p // n, c).permute(0, 3, 1, 2)
+
+
+def bn_apply_ref64(y, scale, shift, residual=None, relu=False):
+    """relu?(y * scale + shift [+ residual]) in float64 on [pixels, c] arrays, and the sum of the magnitudes the float32 bound is
+    taken of: |y * scale| + |shift| + |residual|."""
+    ys = y.astype(np.float64) * scale.astype(np.float64)[None, :]
+    v = ys + shift.astype(np.float64)[None, :]
+    mag = np.abs(ys) + np.abs(shift.astype(np.float64))[None, :]
+    if residual is not None:
+        v = v + residual.astype(np.float64)
+        mag = mag + np.abs(residual.astype(np.float64))
+    return (np.maximum(v, 0.0) if relu else v), mag
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# hourglass up path (tests/test_fanin_upsample_gpu.py)
+# ------------------------------------------------------------------------------------------------------------------
+def upsample_add_ref64(up1, low):
+    """up1 + F.interpolate(F.interpolate(low, scale_factor=2), size=up1's, mode="bilinear", align_corners=True) in float64
+    (NCHW tensors), as backbones/hourglass.py's up path composes it."""
+    import torch.nn.functional as F
+    up = F.interpolate(low.double(), scale_factor=2)
+    return up1.double() + F.interpolate(up, size=tuple(up1.shape[2:]), mode="bilinear", align_corners=True)
+
+
+def bf16_crafted_vector(seed=5, normals=1000):
+    """float32 values on which a float32 -> bfloat16 conversion can go wrong (bit patterns noted; 0x7f in the low half word below
+    the tie, 0x80 00 the tie, 0x80 01 above it): ties with an even and an odd kept mantissa, one float32 ulp either side of each,
+    +-0, +-Inf, NaN, the largest finite float32 (rounds to Inf), the largest value that stays finite, and random normals.
+    float32 subnormals are left out.  The length is a multiple of 4."""
+    pat = [0x3f808000, 0x3f818000,              # ties: kept mantissa even (rounds down), odd (rounds up)
+           0x3f807fff, 0x3f808001, 0x3f817fff, 0x3f818001,
+           0xbf808000, 0xbf818000, 0xbf807fff, 0xbf818001,
+           0x00000000, 0x80000000, 0x7f800000, 0xff800000, 0x7fc00000, 0xffc00000, 0x7f800001,
+           0x7f7fffff, 0xff7fffff, 0x7f7f7fff, 0x7f7f8000,      # max finite -> Inf; just below the last tie stays finite; the tie -> Inf
+           0x00800000, 0x80800000, 0x3f800000, 0x3f7fffff, 0x3fffffff, 0x477fe000]
+    v = np.array(pat, dtype=np.uint32).view(np.float32)
+    r = np.random.default_rng(seed).normal(0.0, 1.0, normals).astype(np.float32)
+    out = np.concatenate([v, r, r * np.float32(1e-20), r * np.float32(1e20)])
+    keep = (np.abs(out) >= np.float32(2.0 ** -126)) | (out == 0) | ~np.isfinite(out)
+    out = out[keep]
+    return np.ascontiguousarray(out[:len(out) // 4 * 4])

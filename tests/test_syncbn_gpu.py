@@ -246,6 +246,13 @@ BWD_FORMS = {
     "b16-image-inputs-c128": dict(mode=BF16, shards=[(1, 64, 64), (2, 64, 64)], c=128, phantom=True,
                                   entry=lambda px: "rr_bn_bwd_apply_b16"),
     "b16-image-only-dx": dict(mode=BF16, shards=[(2, 9, 11), (5, 9, 11)], c=20, only16=True, entry=lambda px: "rr_bn_bwd_apply_b16"),
+    # C / 4 = 96 does not divide the 256-thread workgroup.  64 pixels: 24 workgroups, a grid stride of 6144 quads = 64 x 96; 75 pixels:
+    # 29 workgroups, 7424 quads, no multiple of 96 — in the bf16-image launches (the kernel that keeps a quad's constants in
+    # registers when the stride allows) the two shards take one loop each
+    "plain-c384": dict(mode=F32, shards=[(1, 8, 8), (3, 5, 5)], c=384, entry=lambda px: "rr_bn_bwd_apply"),
+    "b16-image-inputs-c384": dict(mode=BF16, shards=[(1, 8, 8), (3, 5, 5)], c=384, phantom=True, entry=lambda px: "rr_bn_bwd_apply_b16"),
+    # C = 1024, the launchers' upper limit: rr_bn_bwd_reduce_b16 runs ONE pixel lane per pass
+    "b16-image-inputs-c1024": dict(mode=BF16, shards=[(1, 5, 7), (3, 5, 7)], c=1024, phantom=True, entry=lambda px: "rr_bn_bwd_apply_b16"),
 }
 APPLY_ENTRIES = ("rr_bn_bwd_apply", "rr_bn_bwd_apply_gacc", "rr_bn_bwd_apply_amax", "rr_bn_bwd_apply_b16")
 
