@@ -125,6 +125,17 @@ int rr_conv_dgrad_s1_relubias(const float *dy, const float *wt, float *dx, int n
                               double *sums, hipStream_t stream);
 int rr_conv_wgrad(const float *x, const float *dy, float *dw, int n, int h, int wd, int c, int k,
                   int r, int s, int stride, int pad_h, int pad_w, int out_h, int out_w, hipStream_t stream);
+/* Introspection, for tests: HOW a forward-kernel convolution (rr_conv_fprop*, rr_conv_dgrad_s1*, a parity class of
+ * rr_conv_dgrad_s2_*) would launch, as the one host plan of csrc/conv_plan.h decides it.  Launches nothing, needs no device.
+ * math: 0 fp32, 1 bf16, 2 f16x3.  out_h / out_w > 0: the output grid given explicitly (pads are leading pads).  flags: 1 bias,
+ * 2 relu, 4 statistics wanted, 8 accumulate, 16 strided parity-class destination, (link << 8): 1 a BatchNorm producer (_bnsum),
+ * 2 a conv + bias + ReLU producer (_relubias).  plan[RR_CONV_PLAN_INTS] = {row-streaming shortcut (the other fields are 0 then),
+ * scalar gather, tile width, workgroups per K slice, split-K factor, position-major, one column tile per XCD, the link's sums
+ * fused in the epilogue, pass afterwards (0 none, 1 rr_bn_reduce_slab, 2 rr_bn_bwd_reduce, 3 column statistics), destination
+ * zero-filled, statistics slab zero-filled}.  A call the arithmetic refuses returns an error (rr_last_error says why). */
+#define RR_CONV_PLAN_INTS 11
+int rr_conv_fprop_plan(int math, int n, int h, int wd, int c, int k, int r, int s, int stride, int pad_h, int pad_w,
+                       int out_h, int out_w, int flags, int *plan);
 
 /* ---- bf16-operand convolutions (BASELINE config 4, "bf16"; csrc/conv_bf16.hip) ------------------------------------- *
  * The reference is fp32-only (backbones/hourglass.py:12-61,127-199 -> nn.Conv2d), so this precision is builder-defined

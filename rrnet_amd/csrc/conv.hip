@@ -20,8 +20,7 @@
 // 128-B lines from L2, and block ids are remapped so that an XCD owns a contiguous tile range.
 //
 // Roofline: MFMA-bound (fp32 matrix peak 157.3 TFLOP/s); algorithmic FLOPs = 2*M*N*Kg.
-#include "common.h"
-#include "rrnet_hip.h"
+#include "conv_launch.h"
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
 namespace {
@@ -1194,49 +1193,10 @@ const float *zero_page()
     return p[dev];
 }
 
-template <typename K, typename A>
-int launch(K kern, int blocks, size_t lds, hipStream_t stream, const A &args, const char *name, int grid_y = 1,
-           int grid_z = 1)
-{
-    if (lds > 48 * 1024)
-        hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kern, dim3(blocks, grid_y, grid_z), dim3(256), lds, stream, args);
-    RR_CHECK_LAUNCH(name);
-    return RR_OK;
-}
-
 // conv_igemm_kernel's dynamic LDS: nbuf images of A [BM][BK + 4] and B [bn][BK + 4] / [BK][bn]
 size_t igemm_lds(int bn, bool b_kn, int nbuf)
 {
     return sizeof(float) * nbuf * (BM * (BK + 4) + (b_kn ? BK * bn : bn * (BK + 4)));
-}
-
-int mid_tiles() { return 48; }       // <= 48 tiles of 128x128 (the 16x16 level): 128x64 tiles; measured worse at 192 (32x32)
-
-int small_tiles() { return 16; }       // <= 16 tiles of 128x128 (the 8x8 level): 128x32 tiles give 4x the workgroups
-
-// split-K factor for layers whose output has too few tiles to fill the chip
-int pick_ksplit(int blocks, int nk)
-{
-    static int enabled = -1;
-    if (enabled < 0) {
-        const char *e = getenv("RR_CONV_SPLITK");
-        enabled = (e && atoi(e) == 0) ? 0 : 1;
-    }
-    if (!enabled || blocks >= 256 || nk < 16) return 1;   // a full first wave of tiles: splitting costs more than it balances
-    // Occupancy model: 256 CUs, two workgroups resident per CU.  A pair shares the MFMA pipes at ~0.87 of peak, a
-    // lone workgroup reaches ~0.75 (nobody fills its issue gaps); every workgroup pays ~3 K-steps of prologue +
-    // epilogue.  The busiest CU holds ceil(total / 256) workgroups; pick the split with the shortest makespan.
-    int best = 1;
-    float best_t = 0.f;
-    for (int ks = 1; ks <= 8 && ks <= nk / 8; ++ks) {
-        const int total = blocks * ks;
-        const int n = (total + 255) / 256;
-        const float per = (float)((nk + ks - 1) / ks) + 3.0f + (ks > 1 ? 1.0f : 0.0f);   // + atomic epilogue
-        const float t = (float)(n / 2) * (2.0f * per / 0.87f) + (float)(n % 2) * (per / 0.75f);
-        if (best_t == 0.f || t < best_t * 0.95f) { best = ks; best_t = t; }
-    }
-    return best;
 }
 
 // column sums / sums of squares of y -> slab row 0 (the other rows are zeroed by the caller); used when
@@ -1275,8 +1235,8 @@ int launch_igemm(ConvArgs &a, int bn, bool scalar, int blocks, int gy, int gz, h
     const bool small = (long)a.N * a.SH * a.SW * a.SC * 4 < (1l << 31) && (long)a.wK * a.R * a.S * a.wC * 4 < (1l << 31);
     a.dst32 = (long)a.M * a.DC * 4 < (1l << 31);
 #define IG(BNv, SCv, PIPEv, ...)                                                                                       \
-    launch(conv_igemm_kernel<BNv, MODE, SCv, BK, PIPEv, ##__VA_ARGS__>, blocks, igemm_lds(bn, MODE == 1, PIPEv == 2 ? 1 : 2), \
-           stream, a, name, gy, gz)
+    rr_launch(conv_igemm_kernel<BNv, MODE, SCv, BK, PIPEv, ##__VA_ARGS__>, dim3(blocks, gy, gz),                       \
+              igemm_lds(bn, MODE == 1, PIPEv == 2 ? 1 : 2), stream, a, name)
     if constexpr (MODE == 0) {
         if (a.pos_major)             // host rule (fprop_impl): vector gather, both tensors below 2 GiB
             return bn == 128 ? IG(128, false, 2, false, true) : IG(64, false, 2, false, true);
@@ -1305,93 +1265,43 @@ extern "C" size_t rr_conv_stat_slab_bytes(int n, int p, int q, int k)
     return (size_t)((M + BM - 1) / BM) * 2 * k * sizeof(double);
 }
 
-// BatchNorm-backward sums of the producer of the tensor a stride-1 data gradient writes (see ConvArgs::bs_y)
-struct BnSumArgs {
-    const float *y, *z, *mean, *invstd, *msc, *msh;
-    double *slab;      // [ceil(M/128)][2][C] scratch
-    double *sums;      // [2][C], zeroed by the caller
-    int relu_bias;     // producer = conv + bias + ReLU: masked store, sums[0..C) = bias gradient
-};
+int rr_conv_colstats(const float *y, long M, int C, double *slab, hipStream_t stream, const char *name)
+{
+    const int lanes = 256 / (C / 4);
+    int sblocks = rr_cdiv(M, (long)lanes * 8);
+    if (sblocks > 256) sblocks = 256;
+    hipLaunchKernelGGL(colstats_kernel, dim3(sblocks), dim3(256), 0, stream, y, M, C, slab);
+    RR_CHECK_LAUNCH(name);
+    return RR_OK;
+}
 
-static int fprop_impl(const float *x, const float *w, const float *bias, float *y, double *stat_slab,
+// name: the public entry point that was called.  How the call launches is rr_plan::fprop_plan's decision (conv_plan.h).
+static int fprop_impl(const char *name, const float *x, const float *w, const float *bias, float *y, double *stat_slab,
                       int n, int h, int wd, int c, int k, int r, int s, int stride, int pad_h,
                       int pad_w, int relu, int accumulate, hipStream_t stream, const BnSumArgs *bs = nullptr)
 {
-    RR_CHECK_ARG(n > 0 && h > 0 && wd > 0 && c > 0 && k > 0 && r > 0 && s > 0 && stride > 0, "rr_conv_fprop: bad dims");
+    const rr_plan::FpropPlan pl = rr_plan::fprop_plan(rr_plan::MATH_F32, {n, h, wd, c, k, r, s, stride, pad_h, pad_w, 0, 0},
+                                                      {bias != nullptr, relu != 0, stat_slab != nullptr, rr_conv_link(bs), accumulate != 0, false});
+    RR_CHECK_ARG(pl.refuse == nullptr, "%s: %s", name, pl.refuse);
+    if (pl.rows) return rr_conv1x1_rows(x, w, bias, y, pl.M, c, k, relu, stream);
     ConvArgs a{};
     a.src = x; a.w = w; a.dst = y; a.bias = bias; a.stat_slab = stat_slab;
     a.N = n; a.SH = h; a.SW = wd; a.SC = c;
-    a.DH = (h + 2 * pad_h - r) / stride + 1; a.DW = (wd + 2 * pad_w - s) / stride + 1; a.DC = k;
-    RR_CHECK_ARG(a.DH > 0 && a.DW > 0, "rr_conv_fprop: empty output");
+    a.DH = pl.dh; a.DW = pl.dw; a.DC = k;
     a.R = r; a.S = s; a.stride = stride; a.pad_h = pad_h; a.pad_w = pad_w;
-    a.relu = relu; a.accumulate = accumulate; a.ksplit = 1; a.zero = zero_page();
-    const long M = (long)n * a.DH * a.DW;
-    RR_CHECK_ARG(M < (1l << 31) && (long)n * h * wd * c < (1l << 40), "rr_conv_fprop: tensor too large");
-    a.M = (int)M; a.Kg = r * s * c; a.wK = k; a.wC = c;
-    // 1x1 to 49..64 channels (both 32-column tiles of the rows kernel in use) on very many rows without statistics — the
-    // stage-2 head's conv1 at inference: the row-streaming kernel of csrc/headtail.hip (weights in registers, no per-tile
-    // prologue)
-    if (r == 1 && s == 1 && stride == 1 && pad_h == 0 && pad_w == 0 && (c == 128 || c == 256) && k > 48 && k <= 64
-        && stat_slab == nullptr && bs == nullptr && !accumulate && M >= 64 * 1024 && M * c * 4 < (1l << 31))
-        return rr_conv1x1_rows(x, w, bias, y, M, c, k, relu, stream);
-    const bool scalar = (c % 4) != 0 || r * s > 64;   // the vector path keeps a 64-bit tap mask per row
-    int bn = k > 64 ? 128 : (k > 32 ? (!scalar ? 64 : 128) : 32);
-    if (bn == 128 && !scalar && rr_cdiv(M, BM) * rr_cdiv(k, 128) <= small_tiles()) bn = 32;   // tiny layers: 4x the tiles
-    else if (bn == 128 && !scalar && rr_cdiv(M, BM) * rr_cdiv(k, 128) <= mid_tiles()) bn = 64;
-    int blocks = rr_cdiv(M, BM) * rr_cdiv(k, bn);
-    const int nk = scalar ? rr_cdiv(a.Kg, BK) : rr_cdiv(c, BK) * r * s;
-    int ks = (bias == nullptr && !relu && k % 4 == 0 && k <= 1024) ? pick_ksplit(blocks, nk) : 1;
-    if (bs != nullptr && bs->relu_bias) ks = 1;      // the masked store needs the complete value in one workgroup
-    // padded filter on a tiny map, many images (the stage-2 head on 3x3 RoI maps): one output pixel per M tile, padding
-    // taps skipped (ConvArgs::pos_major).  Not with statistics in the epilogue (their slab is sized by ceil(M/128) tiles).
-    // The variant exists for the pipelined 128- and 64-column kernels (32-bit buffer offsets).
-    if (!scalar && stat_slab == nullptr && bs == nullptr && (pad_h > 0 || pad_w > 0) && r * s > 1
-        && a.DH * a.DW <= 16 && n >= 16 * BM && bn >= 64
-        && (long)n * h * wd * c * 4 < (1l << 31) && (long)k * r * s * c * 4 < (1l << 31)) {
-        a.pos_major = 1;
-        ks = 1;
-        blocks = a.DH * a.DW * rr_cdiv(n, BM) * rr_cdiv(k, bn);
-    }
-    if (ks > 1) {
-        a.ksplit = ks;
-        // the split-K destination and (filled by colstats_kernel after the launch) the statistics slab: one zero-fill launch
-        const bool zslab = stat_slab != nullptr && bs == nullptr;
-        RR_CHECK_HIP(rr_zero2(accumulate ? nullptr : y, accumulate ? 0 : sizeof(float) * (size_t)M * k, zslab ? stat_slab : nullptr,
-                              zslab ? rr_conv_stat_slab_bytes(n, a.DH, a.DW, k) : 0, stream), "rr_conv_fprop");
-    }
-    // The epilogue reads the producer's tensors through buffer descriptors with the row inside the tile in the SCALAR offset,
-    // which the hardware's range check does not cover: in a partial last tile it would read up to 11 rows past the end of
-    // the tensor.  Fused sums therefore only for M % 128 == 0 (every size the training configurations produce); other
-    // sizes take the separate reduce pass below, and the masked-store mode — which has no such fallback — is refused.
-    // The same epilogue reaches the destination and the producer's tensors through 32-bit offsets: below 2 GiB only.
-    const bool tiles_full = M % BM == 0 && M * k * 4 < (1l << 31);
-    RR_CHECK_ARG(bs == nullptr || !bs->relu_bias || tiles_full,
-                 "rr_conv_dgrad_s1_relubias: N*H*W = %ld must be a multiple of 128 and dx smaller than 2 GiB", M);
-    if (bs != nullptr && ks == 1 && tiles_full) {      // sums in the epilogue; with split-K the complete values exist only afterwards
-        a.stat_slab = bs->slab;
-        a.bs_y = bs->y; a.bs_z = bs->z; a.bs_mean = bs->mean; a.bs_invstd = bs->invstd; a.bs_msc = bs->msc; a.bs_msh = bs->msh;
-        a.bs_relu_bias = bs->relu_bias;
-    }
-    int rc = launch_igemm<0>(a, bn, scalar, blocks, 1, ks, stream, "rr_conv_fprop");
-    if (rc == RR_OK && bs != nullptr) {
-        if (ks == 1 && tiles_full) return rr_bn_reduce_slab(bs->slab, (int)rr_cdiv(M, BM), k, bs->sums, stream);
-        return rr_bn_bwd_reduce(y, bs->z, bs->y, bs->mean, bs->invstd, bs->msc, bs->msh, bs->sums, M, k, 1, stream);
-    }
-    if (rc == RR_OK && ks > 1 && stat_slab != nullptr) {
-        const int lanes = 256 / (k / 4);
-        int sblocks = rr_cdiv(M, (long)lanes * 8);
-        if (sblocks > 256) sblocks = 256;
-        hipLaunchKernelGGL(colstats_kernel, dim3(sblocks), dim3(256), 0, stream, y, M, k, stat_slab);
-        RR_CHECK_LAUNCH("rr_conv_fprop(stats)");
-    }
-    return rc;
+    a.relu = relu; a.accumulate = accumulate; a.ksplit = pl.ks; a.pos_major = pl.pos_major; a.zero = zero_page();
+    a.M = (int)pl.M; a.Kg = r * s * c; a.wK = k; a.wC = c;
+    if (pl.fused) bs->into(a);
+    if (int rc = rr_conv_before_launch(pl, n, k, y, stat_slab, stream, name)) return rc;
+    if (int rc = launch_igemm<0>(a, pl.bn, pl.scalar, pl.blocks, 1, pl.ks, stream, name)) return rc;
+    return rr_conv_after_launch(pl, bs, k, y, stat_slab, stream, name);
 }
 
 extern "C" int rr_conv_fprop(const float *x, const float *w, const float *bias, float *y, double *stat_slab,
                              int n, int h, int wd, int c, int k, int r, int s, int stride, int pad_h,
                              int pad_w, int relu, hipStream_t stream)
 {
-    return fprop_impl(x, w, bias, y, stat_slab, n, h, wd, c, k, r, s, stride, pad_h, pad_w, relu, 0, stream);
+    return fprop_impl("rr_conv_fprop", x, w, bias, y, stat_slab, n, h, wd, c, k, r, s, stride, pad_h, pad_w, relu, 0, stream);
 }
 
 // wt[c][R-1-r][S-1-s][k] = w[k][r][s][c]: 32x32 tiles of the (k, c) plane through LDS, one tap per grid.z
@@ -1477,15 +1387,19 @@ extern "C" int rr_weight_flip_transpose_batch_bf16(const float *flat, float *wt_
     return RR_OK;
 }
 
+// the stride-1 data gradients: rr_dgrad_s1_geom's checks and flip (conv_launch.h), then the forward kernel on (dy, wt)
+static int dgrad_s1(const char *name, bool producer_ok, const float *dy, const float *wt, float *dx, int n, int h, int wd, int c, int k,
+                    int r, int s, int pad_h, int pad_w, int accumulate, hipStream_t stream, const BnSumArgs *bs = nullptr)
+{
+    DgradS1Geom g;
+    if (int rc = rr_dgrad_s1_geom(name, h, wd, r, s, pad_h, pad_w, producer_ok, &g)) return rc;
+    return fprop_impl(name, dy, wt, nullptr, dx, nullptr, n, g.p, g.q, k, c, r, s, 1, g.pad_h, g.pad_w, 0, accumulate, stream, bs);
+}
+
 extern "C" int rr_conv_dgrad_s1(const float *dy, const float *wt, float *dx, int n, int h, int wd, int c, int k,
                                 int r, int s, int pad_h, int pad_w, int accumulate, hipStream_t stream)
 {
-    RR_CHECK_ARG(pad_h < r && pad_w < s && pad_h >= 0 && pad_w >= 0, "rr_conv_dgrad_s1: pad must be in [0, kernel)");
-    const int p = h + 2 * pad_h - r + 1, q = wd + 2 * pad_w - s + 1;
-    RR_CHECK_ARG(p > 0 && q > 0, "rr_conv_dgrad_s1: empty dy");
-    // a stride-1 data gradient IS a forward convolution of dy with the flipped, transposed filter
-    return fprop_impl(dy, wt, nullptr, dx, nullptr, n, p, q, k, c, r, s, 1, r - 1 - pad_h, s - 1 - pad_w, 0, accumulate,
-                      stream);
+    return dgrad_s1("rr_conv_dgrad_s1", true, dy, wt, dx, n, h, wd, c, k, r, s, pad_h, pad_w, accumulate, stream);
 }
 
 // out[m][k], m = (n,p,q), k = (r*S + s)*C + c for k < R*S*C and 0 up to KP: the taps of a small-channel convolution laid
@@ -1538,29 +1452,16 @@ extern "C" int rr_conv_dgrad_s1_bnsum(const float *dy, const float *wt, float *d
                                       const float *prod_mask_scale, const float *prod_mask_shift, double *slab,
                                       double *sums, hipStream_t stream)
 {
-    RR_CHECK_ARG(pad_h < r && pad_w < s && pad_h >= 0 && pad_w >= 0, "rr_conv_dgrad_s1_bnsum: pad must be in [0, kernel)");
-    RR_CHECK_ARG(prod_y && prod_mean && prod_invstd && slab && sums && (!prod_mask_scale == !prod_mask_shift),
-                 "rr_conv_dgrad_s1_bnsum: the producer's y / mean / invstd and the two buffers are required");
-    RR_CHECK_ARG(c % 4 == 0 && c <= 1024, "rr_conv_dgrad_s1_bnsum: C=%d must be a multiple of 4 and <= 1024", c);
-    const int p = h + 2 * pad_h - r + 1, q = wd + 2 * pad_w - s + 1;
-    RR_CHECK_ARG(p > 0 && q > 0, "rr_conv_dgrad_s1_bnsum: empty dy");
     const BnSumArgs bs{prod_y, prod_z, prod_mean, prod_invstd, prod_mask_scale, prod_mask_shift, slab, sums, 0};
-    return fprop_impl(dy, wt, nullptr, dx, nullptr, n, p, q, k, c, r, s, 1, r - 1 - pad_h, s - 1 - pad_w, 0, accumulate,
-                      stream, &bs);
+    return dgrad_s1("rr_conv_dgrad_s1_bnsum", bs.bn_ok(c), dy, wt, dx, n, h, wd, c, k, r, s, pad_h, pad_w, accumulate, stream, &bs);
 }
 
 extern "C" int rr_conv_dgrad_s1_relubias(const float *dy, const float *wt, float *dx, int n, int h, int wd, int c, int k,
                                          int r, int s, int pad_h, int pad_w, int accumulate, const float *prod_z, double *slab,
                                          double *sums, hipStream_t stream)
 {
-    RR_CHECK_ARG(pad_h < r && pad_w < s && pad_h >= 0 && pad_w >= 0, "rr_conv_dgrad_s1_relubias: pad must be in [0, kernel)");
-    RR_CHECK_ARG(prod_z && slab && sums, "rr_conv_dgrad_s1_relubias: the producer's output and the two buffers are required");
-    RR_CHECK_ARG(c % 4 == 0 && k % 4 == 0 && c <= 1024, "rr_conv_dgrad_s1_relubias: C=%d, K=%d must be multiples of 4", c, k);
-    const int p = h + 2 * pad_h - r + 1, q = wd + 2 * pad_w - s + 1;
-    RR_CHECK_ARG(p > 0 && q > 0, "rr_conv_dgrad_s1_relubias: empty dy");
     const BnSumArgs bs{prod_z, prod_z, nullptr, nullptr, nullptr, nullptr, slab, sums, 1};
-    return fprop_impl(dy, wt, nullptr, dx, nullptr, n, p, q, k, c, r, s, 1, r - 1 - pad_h, s - 1 - pad_w, 0, accumulate, stream,
-                      &bs);
+    return dgrad_s1("rr_conv_dgrad_s1_relubias", bs.relu_bias_ok(c, k), dy, wt, dx, n, h, wd, c, k, r, s, pad_h, pad_w, accumulate, stream, &bs);
 }
 
 extern "C" int rr_conv_dgrad(const float *dy, const float *w, float *dx, int n, int h, int wd, int c, int k,
@@ -1580,28 +1481,26 @@ extern "C" int rr_conv_dgrad(const float *dy, const float *w, float *dx, int n, 
     a.M = (int)M; a.Kg = r * s * k; a.wK = k; a.wC = c;
     const bool scalar = (k % 4) != 0 || (c % 4) != 0 || r * s > 64 || stride > 2;
     int bn = c > 64 ? 128 : (c > 32 ? (!scalar ? 64 : 128) : 32);
-    if (bn == 128 && !scalar && stride == 1 && rr_cdiv(M, BM) * rr_cdiv(c, 128) <= small_tiles()) bn = 32;
-    else if (bn == 128 && !scalar && stride == 1 && rr_cdiv(M, BM) * rr_cdiv(c, 128) <= mid_tiles()) bn = 64;
+    if (bn == 128 && !scalar && stride == 1 && rr_cdiv(M, BM) * rr_cdiv(c, 128) <= rr_plan::small_tiles()) bn = 32;
+    else if (bn == 128 && !scalar && stride == 1 && rr_cdiv(M, BM) * rr_cdiv(c, 128) <= rr_plan::mid_tiles()) bn = 64;
     int blocks = rr_cdiv(M, BM) * rr_cdiv(c, bn);
     int gy = 1;
     int nk = scalar ? rr_cdiv(a.Kg, BK) : rr_cdiv(k, BK) * r * s;
     if (stride == 2 && !scalar) {     // parity-decomposed: 4 classes of ceil(h/2) x ceil(w/2) pixels each
         a.parity = 1;
         gy = 4;
-        int taps[4], ord[4] = {0, 1, 2, 3};
-        for (int cl = 0; cl < 4; ++cl) {
-            const int r0 = ((cl >> 1) + pad_h) & 1, s0 = ((cl & 1) + pad_w) & 1;
-            taps[cl] = (r0 < r ? (r - r0 + 1) / 2 : 0) * (s0 < s ? (s - s0 + 1) / 2 : 0);
-        }
+        rr_plan::ParityClass cls[4];
+        rr_plan::parity_classes(h, wd, r, s, pad_h, pad_w, cls);
+        int ord[4] = {0, 1, 2, 3};
         for (int i = 0; i < 4; ++i)
             for (int j = i + 1; j < 4; ++j)
-                if (taps[ord[j]] > taps[ord[i]]) { const int t = ord[i]; ord[i] = ord[j]; ord[j] = t; }
+                if (cls[ord[j]].taps() > cls[ord[i]].taps()) { const int t = ord[i]; ord[i] = ord[j]; ord[j] = t; }
         a.parity_order = ord[0] | (ord[1] << 2) | (ord[2] << 4) | (ord[3] << 6);
         // classes without any tap (1x1 stride 2: three of four) produce zeros: one memset instead of workgroups
         // that run an empty K loop and store zeros element by element
         // (when accumulating they add nothing: no workgroups at all)
         int live = 4;
-        while (live > 1 && taps[ord[live - 1]] == 0) --live;
+        while (live > 1 && cls[ord[live - 1]].taps() == 0) --live;
         if (live < 4) {
             if (!accumulate) RR_CHECK_HIP(rr_zero2(dx, sizeof(float) * (size_t)M * c, nullptr, 0, stream), "rr_conv_dgrad");
             gy = live;
@@ -1609,7 +1508,7 @@ extern "C" int rr_conv_dgrad(const float *dy, const float *w, float *dx, int n, 
         blocks = rr_cdiv((long)n * ((h + 1) / 2) * ((wd + 1) / 2), BM) * rr_cdiv(c, bn);
         nk = rr_cdiv(k, BK) * ((r + 1) / 2) * ((s + 1) / 2);
     }
-    int ks = a.parity ? 1 : pick_ksplit(blocks * gy, nk);
+    int ks = a.parity ? 1 : rr_plan::pick_ksplit(blocks * gy, nk);
     if (ks > 1) {
         a.ksplit = ks;
         if (!accumulate) RR_CHECK_HIP(rr_zero2(dx, sizeof(float) * (size_t)M * c, nullptr, 0, stream), "rr_conv_dgrad");
@@ -1638,35 +1537,42 @@ extern "C" int rr_conv_wgrad(const float *x, const float *dy, float *dw, int n, 
     a.mt = rr_cdiv(k, bmw); a.nt = rr_cdiv(c, bn);
     const int tiles = a.mt * a.nt * r * s;
     const int total_chunks = rr_cdiv(M, BK);
-    // Split the pixel (K) dimension so that tiles*splits fills the 512 resident-workgroup slots
-    // (256 CUs x 2) exactly once: equal-length workgroups in more than one round pay a whole extra
-    // round for any remainder.  Never fewer than 8 K-steps per split.
     // pipelined 128x128 variants: 32-bit buffer offsets, both tensors below 2 GiB
     const bool as = (k % 4) != 0, bs = (c % 4) != 0;
     const bool pipe_ok = bmw == 128 && bn == 128 && !as && !bs && M * k * 4 < (1l << 31) &&
                          (long)n * h * wd * c * 4 < (1l << 31);
     const int wmode = !pipe_ok ? 0 : (a.Q % BK == 0 ? 3 : 1);   // PIPE of the 128x128 kernel, 0: generic tiles
     const int slots = wmode == 3 ? 768 : 512;       // resident workgroups: 256 CUs x 3 with one LDS image, else x 2
-    int splits = tiles < slots ? slots / tiles : 1;
-    if (splits > rr_cdiv(total_chunks, 8)) splits = rr_cdiv(total_chunks, 8);
-    if (splits < 1) splits = 1;
-    a.chunks_per_split = rr_cdiv(total_chunks, splits);
-    splits = rr_cdiv(total_chunks, a.chunks_per_split);
-    const int blocks = tiles * splits;
+    const int blocks = tiles * rr_plan::pixel_splits(tiles, total_chunks, slots, 8, &a.chunks_per_split);
     const size_t lds = sizeof(float) * (wmode == 3 ? 1 : 2) * (BK * bmw + BK * bn);
 #define WG(BMv, BNv)                                                                                                  \
-    (as ? (bs ? launch(conv_wgrad_kernel<BMv, BNv, true, true, 0>, blocks, lds, stream, a, "rr_conv_wgrad")      \
-              : launch(conv_wgrad_kernel<BMv, BNv, true, false, 0>, blocks, lds, stream, a, "rr_conv_wgrad"))    \
-        : (bs ? launch(conv_wgrad_kernel<BMv, BNv, false, true, 0>, blocks, lds, stream, a, "rr_conv_wgrad")     \
-              : launch(conv_wgrad_kernel<BMv, BNv, false, false, 0>, blocks, lds, stream, a, "rr_conv_wgrad")))
-    if (wmode == 3) return launch(conv_wgrad_kernel<128, 128, false, false, 3>, blocks, lds, stream, a, "rr_conv_wgrad");
-    if (wmode == 1) return launch(conv_wgrad_kernel<128, 128, false, false, 1>, blocks, lds, stream, a, "rr_conv_wgrad");
+    (as ? (bs ? rr_launch(conv_wgrad_kernel<BMv, BNv, true, true, 0>, dim3(blocks), lds, stream, a, "rr_conv_wgrad")      \
+              : rr_launch(conv_wgrad_kernel<BMv, BNv, true, false, 0>, dim3(blocks), lds, stream, a, "rr_conv_wgrad"))    \
+        : (bs ? rr_launch(conv_wgrad_kernel<BMv, BNv, false, true, 0>, dim3(blocks), lds, stream, a, "rr_conv_wgrad")     \
+              : rr_launch(conv_wgrad_kernel<BMv, BNv, false, false, 0>, dim3(blocks), lds, stream, a, "rr_conv_wgrad")))
+    if (wmode == 3) return rr_launch(conv_wgrad_kernel<128, 128, false, false, 3>, dim3(blocks), lds, stream, a, "rr_conv_wgrad");
+    if (wmode == 1) return rr_launch(conv_wgrad_kernel<128, 128, false, false, 1>, dim3(blocks), lds, stream, a, "rr_conv_wgrad");
     if (bmw == 128) return bn == 128 ? WG(128, 128) : WG(128, 32);
     return bn == 128 ? WG(32, 128) : WG(32, 32);
 #undef WG
 }
 
-// shared with csrc/conv_bf16.hip: one occupancy model / tile policy for both precisions
-int rr_conv_pick_ksplit(int blocks, int nk) { return pick_ksplit(blocks, nk); }
-int rr_conv_small_tiles() { return small_tiles(); }
-int rr_conv_mid_tiles() { return mid_tiles(); }
+// the policy of conv_plan.h as the library was built with it, for tests/test_host_logic.py (C++ linkage, called by mangled name)
+int rr_conv_pick_ksplit(int blocks, int nk) { return rr_plan::pick_ksplit(blocks, nk); }
+int rr_conv_small_tiles() { return rr_plan::small_tiles(); }
+int rr_conv_mid_tiles() { return rr_plan::mid_tiles(); }
+
+extern "C" int rr_conv_fprop_plan(int math, int n, int h, int wd, int c, int k, int r, int s, int stride, int pad_h, int pad_w,
+                                  int out_h, int out_w, int flags, int *plan)
+{
+    RR_CHECK_ARG(math >= rr_plan::MATH_F32 && math <= rr_plan::MATH_F16X3 && ((flags >> 8) & 3) <= rr_plan::LINK_RELU_BIAS && plan != nullptr,
+                 "rr_conv_fprop_plan: bad arguments");
+    const rr_plan::FpropPlan pl = rr_plan::fprop_plan(math, {n, h, wd, c, k, r, s, stride, pad_h, pad_w, out_h, out_w},
+                                                      {(flags & 1) != 0, (flags & 2) != 0, (flags & 4) != 0, (flags >> 8) & 3, (flags & 8) != 0,
+                                                       (flags & 16) != 0});
+    RR_CHECK_ARG(pl.refuse == nullptr, "rr_conv_fprop_plan: %s", pl.refuse);
+    const int out[RR_CONV_PLAN_INTS] = {pl.rows, pl.scalar, pl.bn, pl.blocks, pl.ks, pl.pos_major, pl.xcd_n, pl.fused, pl.after, pl.zero_dst,
+                                        pl.zero_slab};
+    for (int i = 0; i < RR_CONV_PLAN_INTS; ++i) plan[i] = out[i];
+    return RR_OK;
+}

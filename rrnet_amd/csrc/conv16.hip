@@ -33,8 +33,7 @@
 // + 537 MB fp32 out = 0.81 GB for 618.5 GFLOP: MFMA-bound, ridge at 8 TB/s 0.10 ms, matrix peak 0.25 ms).
 //
 // wgrad (conv16_wgrad_kernel): see below.
-#include "common.h"
-#include "rrnet_hip.h"
+#include "conv_launch.h"
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
 namespace {
@@ -344,33 +343,6 @@ __global__ __launch_bounds__(512, 1) void conv16_igemm_kernel(const Args a)
 // higher).  On random operands the chip does not hold 2.4 GHz under sustained matrix load: the practical ceiling of this tile is
 // ~1.3 PFLOP/s, the kept kernel sits at ~0.8 of it, and what separates the two is the DMA traffic, not the loop structure.)
 
-// Stride-2 data gradient as four stride-1 correlations, one per output parity class (ph, pw) = (h % 2, w % 2), each with the
-// sub-filter of the taps that reach the class (a 3x3 visits 1 / 2 / 2 / 4 taps instead of masking three quarters of a dilated
-// filter) — csrc/conv_bf16.hip's decomposition; here the sub-filters are packed, flipped and transposed straight to bf16
-// ([c][i'][j'][k], i' = Rc-1-i), class blocks in the order (0,0), (0,1), (1,0), (1,1).
-__global__ __launch_bounds__(256) void parity_pack_bf16_kernel(const float *w, unsigned short *wsub, int K, int C, int R, int S, int pad_h,
-                                                               int pad_w, long total)
-{
-    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
-        const int k = (int)(idx % K);
-        long rest = idx / K;
-        const int tap = (int)(rest % (R * S));
-        const int c = (int)(rest / (R * S));
-        const int r = tap / S, s = tap - r * S;
-        const int ph = (r - pad_h) & 1, pw = (s - pad_w) & 1;
-        const int r0 = (ph + pad_h) & 1, s0 = (pw + pad_w) & 1;
-        const int Rc = (R - r0 + 1) / 2, Sc = (S - s0 + 1) / 2;
-        long base = 0;
-        for (int cl = 0; cl < ph * 2 + pw; ++cl) {
-            const int q0 = ((cl >> 1) + pad_h) & 1, t0 = ((cl & 1) + pad_w) & 1;
-            base += (long)C * (q0 < R ? (R - q0 + 1) / 2 : 0) * (t0 < S ? (S - t0 + 1) / 2 : 0) * K;
-        }
-        const int ii = Rc - 1 - (r - r0) / 2, jj = Sc - 1 - (s - s0) / 2;
-        const __bf16 v = (__bf16)w[((long)k * R * S + tap) * C + c];
-        wsub[base + (((long)c * Rc + ii) * Sc + jj) * K + k] = __builtin_bit_cast(unsigned short, v);
-    }
-}
-
 int check_shape(const char *name, int n, int h, int wd, int c, int k, int r, int s, int stride, int pad_h, int pad_w)
 {
     RR_CHECK_ARG(n > 0 && h > 0 && wd > 0 && c > 0 && k > 0 && r > 0 && s > 0 && pad_h >= 0 && pad_w >= 0, "%s: bad dims", name);
@@ -584,40 +556,34 @@ int rr_conv16_fprop(const unsigned short *x, const unsigned short *w, const floa
     return launch_igemm(a, stream, "rr_conv16_fprop");
 }
 
+// dx[n,h,w,c] = sum_{tap,ko} dy[n, h + pad' - ..., ko] * wt[c][tap'][ko]: the forward kernel on dY with the flipped / transposed
+// filter (rr_weight_flip_transpose_batch_bf16), leading pad R-1-pad (rr_dgrad_s1_geom, conv_launch.h)
+static int dgrad16_s1(const char *name, bool ptrs_ok, const unsigned short *dy, const unsigned short *wt, float *dx, unsigned short *dx16,
+                      const float *mask_z, int n, int h, int wd, int c, int k, int r, int s, int pad_h, int pad_w, int accumulate, hipStream_t stream)
+{
+    if (int rc = check_shape(name, n, h, wd, k, c, r, s, 1, pad_h, pad_w)) return rc;
+    DgradS1Geom g;
+    if (int rc = rr_dgrad_s1_geom(name, h, wd, r, s, pad_h, pad_w, dy && wt && ptrs_ok, &g)) return rc;
+    Args a{};
+    a.src = dy; a.flt = wt; a.dst = dx; a.dst16 = dx16; a.mask_z = mask_z;
+    a.N = n; a.SH = g.p; a.SW = g.q; a.SC = k; a.DC = c; a.R = r; a.S = s; a.stride = 1; a.pad_h = g.pad_h; a.pad_w = g.pad_w;
+    a.DH = h; a.DW = wd; a.M = n * h * wd;
+    a.accumulate = accumulate;
+    return launch_igemm(a, stream, name);
+}
+
 int rr_conv16_dgrad_s1(const unsigned short *dy, const unsigned short *wt, float *dx, unsigned short *dx16, int n, int h, int wd, int c, int k,
                        int r, int s, int pad_h, int pad_w, int accumulate, hipStream_t stream)
 {
-    // dx[n,h,w,c] = sum_{tap,ko} dy[n, h + pad' - ..., ko] * wt[c][tap'][ko]: the forward kernel on dY with the flipped / transposed
-    // filter (rr_weight_flip_transpose_batch_bf16), leading pad R-1-pad
-    if (int rc = check_shape("rr_conv16_dgrad_s1", n, h, wd, k, c, r, s, 1, pad_h, pad_w)) return rc;
-    RR_CHECK_ARG(pad_h < r && pad_w < s && dy && wt && (dx || dx16), "rr_conv16_dgrad_s1: bad arguments");
-    Args a{};
-    a.src = dy; a.flt = wt; a.dst = dx; a.dst16 = dx16;
-    a.N = n; a.SH = h + 2 * pad_h - r + 1; a.SW = wd + 2 * pad_w - s + 1; a.SC = k; a.DC = c; a.R = r; a.S = s; a.stride = 1;
-    a.pad_h = r - 1 - pad_h; a.pad_w = s - 1 - pad_w;
-    a.DH = h; a.DW = wd;
-    RR_CHECK_ARG(a.SH > 0 && a.SW > 0, "rr_conv16_dgrad_s1: empty dy");
-    a.M = n * h * wd;
-    a.accumulate = accumulate;
-    return launch_igemm(a, stream, "rr_conv16_dgrad_s1");
+    return dgrad16_s1("rr_conv16_dgrad_s1", dx || dx16, dy, wt, dx, dx16, nullptr, n, h, wd, c, k, r, s, pad_h, pad_w, accumulate, stream);
 }
 
+// rr_conv16_dgrad_s1 whose epilogue applies the backward of the ReLU that produced the convolution's input: what is stored is
+// (dx [+ what dx held]) * (relu_out > 0) — the LAST contributor of a fan-in does this on the complete sum (functional._ReLU)
 int rr_conv16_dgrad_s1_relumask(const unsigned short *dy, const unsigned short *wt, float *dx, int n, int h, int wd, int c, int k,
                                 int r, int s, int pad_h, int pad_w, int accumulate, const float *relu_out, hipStream_t stream)
 {
-    // rr_conv16_dgrad_s1 whose epilogue applies the backward of the ReLU that produced the convolution's input: what is stored is
-    // (dx [+ what dx held]) * (relu_out > 0) — the LAST contributor of a fan-in does this on the complete sum (functional._ReLU)
-    if (int rc = check_shape("rr_conv16_dgrad_s1_relumask", n, h, wd, k, c, r, s, 1, pad_h, pad_w)) return rc;
-    RR_CHECK_ARG(pad_h < r && pad_w < s && dy && wt && dx && relu_out, "rr_conv16_dgrad_s1_relumask: bad arguments");
-    Args a{};
-    a.src = dy; a.flt = wt; a.dst = dx; a.mask_z = relu_out;
-    a.N = n; a.SH = h + 2 * pad_h - r + 1; a.SW = wd + 2 * pad_w - s + 1; a.SC = k; a.DC = c; a.R = r; a.S = s; a.stride = 1;
-    a.pad_h = r - 1 - pad_h; a.pad_w = s - 1 - pad_w;
-    a.DH = h; a.DW = wd;
-    RR_CHECK_ARG(a.SH > 0 && a.SW > 0, "rr_conv16_dgrad_s1_relumask: empty dy");
-    a.M = n * h * wd;
-    a.accumulate = accumulate;
-    return launch_igemm(a, stream, "rr_conv16_dgrad_s1_relumask");
+    return dgrad16_s1("rr_conv16_dgrad_s1_relumask", dx && relu_out, dy, wt, dx, nullptr, relu_out, n, h, wd, c, k, r, s, pad_h, pad_w, accumulate, stream);
 }
 
 int rr_conv16_dgrad_s2(const unsigned short *dy, const float *w, float *dx, int n, int h, int wd, int c, int k, int r, int s,
@@ -627,40 +593,24 @@ int rr_conv16_dgrad_s2(const unsigned short *dy, const float *w, float *dx, int 
     RR_CHECK_ARG(k % BK == 0 && c % 128 == 0 && r * s <= 16, "rr_conv16_dgrad_s2: unsupported shape c=%d k=%d %dx%d", c, k, r, s);
     const int p = (h + 2 * pad_h - r) / 2 + 1, q = (wd + 2 * pad_w - s) / 2 + 1;
     RR_CHECK_ARG(p > 0 && q > 0 && (long)n * p * q * k * 2 < (1l << 31), "rr_conv16_dgrad_s2: empty or oversized dy");
-    const long total = (long)k * c * r * s;
-    hipLaunchKernelGGL(parity_pack_bf16_kernel, dim3((int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256)), dim3(256), 0, stream,
-                       w, wsub, k, c, r, s, pad_h, pad_w, total);
-    RR_CHECK_LAUNCH("rr_conv16_dgrad_s2(pack)");
-    int Rc[4], Sc[4], lead_h[4], lead_w[4];
-    bool any_empty = false;
-    for (int cl = 0; cl < 4; ++cl) {
-        const int ph = cl >> 1, pw = cl & 1;
-        const int r0 = (ph + pad_h) & 1, s0 = (pw + pad_w) & 1;
-        Rc[cl] = r0 < r ? (r - r0 + 1) / 2 : 0;
-        Sc[cl] = s0 < s ? (s - s0 + 1) / 2 : 0;
-        lead_h[cl] = (Rc[cl] - 1) - (ph + pad_h - r0) / 2;
-        lead_w[cl] = (Sc[cl] - 1) - (pw + pad_w - s0) / 2;
-        const int Hc = (h - ph + 1) / 2, Wc = (wd - pw + 1) / 2;
-        if (Hc > 0 && Wc > 0 && Rc[cl] * Sc[cl] == 0) any_empty = true;
-        RR_CHECK_ARG(Rc[cl] * Sc[cl] == 0 || (lead_h[cl] >= 0 && lead_w[cl] >= 0), "rr_conv16_dgrad_s2: unsupported padding %d,%d", pad_h, pad_w);
-    }
+    // csrc/conv_bf16.hip's decomposition (rr_plan::parity_classes: a stride-1 correlation per output parity class with the
+    // sub-filter of the taps that reach it); here the sub-filters are packed straight to bf16
+    if (int rc = rr_parity_pack(w, wsub, k, c, r, s, pad_h, pad_w, stream, "rr_conv16_dgrad_s2")) return rc;
+    rr_plan::ParityClass cls[4];
+    const bool any_empty = rr_plan::parity_classes(h, wd, r, s, pad_h, pad_w, cls);
+    for (const rr_plan::ParityClass &pc : cls)
+        RR_CHECK_ARG(pc.taps() == 0 || (pc.lead_h >= 0 && pc.lead_w >= 0), "rr_conv16_dgrad_s2: unsupported padding %d,%d", pad_h, pad_w);
     if (any_empty && !accumulate) RR_CHECK_HIP(hipMemsetAsync(dx, 0, sizeof(float) * (size_t)n * h * wd * c, stream), "rr_conv16_dgrad_s2");
-    long base = 0;
-    for (int cl = 0; cl < 4; ++cl) {
-        const int ph = cl >> 1, pw = cl & 1;
-        const int Hc = (h - ph + 1) / 2, Wc = (wd - pw + 1) / 2;
-        const long blk = (long)c * Rc[cl] * Sc[cl] * k;
-        if (blk > 0 && Hc > 0 && Wc > 0) {
-            Args a{};
-            a.src = dy; a.flt = wsub + base; a.dst = dx;
-            a.N = n; a.SH = p; a.SW = q; a.SC = k; a.DC = c; a.R = Rc[cl]; a.S = Sc[cl]; a.stride = 1;
-            a.pad_h = lead_h[cl]; a.pad_w = lead_w[cl];
-            a.DH = Hc; a.DW = Wc; a.M = n * Hc * Wc;
-            a.accumulate = accumulate;
-            a.OH = h; a.OW = wd; a.osh = 2; a.osw = 2; a.oh0 = ph; a.ow0 = pw;
-            if (int rc = launch_igemm(a, stream, "rr_conv16_dgrad_s2")) return rc;
-        }
-        base += blk;
+    for (const rr_plan::ParityClass &pc : cls) {
+        if (pc.taps() == 0 || pc.Hc <= 0 || pc.Wc <= 0) continue;
+        Args a{};
+        a.src = dy; a.flt = wsub + (long)pc.taps_before * c * k; a.dst = dx;
+        a.N = n; a.SH = p; a.SW = q; a.SC = k; a.DC = c; a.R = pc.Rc; a.S = pc.Sc; a.stride = 1;
+        a.pad_h = pc.lead_h; a.pad_w = pc.lead_w;
+        a.DH = pc.Hc; a.DW = pc.Wc; a.M = n * pc.Hc * pc.Wc;
+        a.accumulate = accumulate;
+        a.OH = h; a.OW = wd; a.osh = 2; a.osw = 2; a.oh0 = pc.ph; a.ow0 = pc.pw;
+        if (int rc = launch_igemm(a, stream, "rr_conv16_dgrad_s2")) return rc;
     }
     return RR_OK;
 }
@@ -689,11 +639,7 @@ int rr_conv16_wgrad(const unsigned short *x, const unsigned short *dy, float *dw
     const int tiles = a.kt * a.nt * r * s;
     const int total_steps = rr_cdiv(a.M, 32);
     // pixel splits: fill the 256 CUs (one 512-thread workgroup each) about twice, never fewer than 32 K-steps per split
-    int splits = tiles < 512 ? 512 / tiles : 1;
-    if (splits > rr_cdiv(total_steps, 32)) splits = rr_cdiv(total_steps, 32);
-    if (splits < 1) splits = 1;
-    a.steps_per_split = rr_cdiv(total_steps, splits);
-    splits = rr_cdiv(total_steps, a.steps_per_split);
+    const int splits = rr_plan::pixel_splits(tiles, total_steps, 512, 32, &a.steps_per_split);
     const size_t ldsb = 4 * (size_t)(8 * 2048 + (nt_w / 32) * 2048);
     if (nt_w == 256) {
         RR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(conv16_wgrad_kernel<256>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb), "rr_conv16_wgrad");

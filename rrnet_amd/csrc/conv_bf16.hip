@@ -25,14 +25,9 @@
 //          through the hardware transpose ds_read_b64_tr_b16.
 // Roofline: MFMA bf16 (2.5 PFLOP/s dense) for the FLOPs, HBM for the fp32 operands: at 256 -> 256 3x3 on 8 x 256 x 256
 // the layer moves 1.07 GB for 618.5 GFLOP (ridge at 8 TB/s: 0.13 ms; MFMA at peak: 0.25 ms).
-#include "common.h"
-#include "rrnet_hip.h"
+#include "conv_launch.h"
 #include <type_traits>
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
-
-int rr_conv_pick_ksplit(int blocks, int nk);      // csrc/conv.hip: the occupancy model shared with the fp32 kernels
-int rr_conv_small_tiles();
-int rr_conv_mid_tiles();
 
 namespace {
 
@@ -517,39 +512,6 @@ __global__ __launch_bounds__(256, SP == 2 ? 2 : 1) void conv_igemm_bf16_kernel(c
     }
 }
 
-// column sums / sums of squares of y -> slab row 0 (split-K keeps the statistics out of the conv epilogue)
-__global__ __launch_bounds__(256) void colstats_bf16_kernel(const float *y, long M, int C, double *slab)
-{
-    __shared__ double red[2][256 * 4];
-    const int C4 = C / 4, lanes = 256 / C4;
-    const int t = threadIdx.x, cq = t % C4, pl = t / C4;
-    double s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
-    if (pl < lanes)
-        for (long p = (long)blockIdx.x * lanes + pl; p < M; p += (long)gridDim.x * lanes) {
-            const f32x4 v = *reinterpret_cast<const f32x4 *>(y + p * C + cq * 4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { s1[e] += (double)v[e]; s2[e] += (double)v[e] * (double)v[e]; }
-        }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { red[0][t * 4 + e] = s1[e]; red[1][t * 4 + e] = s2[e]; }
-    __syncthreads();
-    for (int c = t; c < C; c += 256) {
-        double a1 = 0.0, a2 = 0.0;
-        for (int l = 0; l < lanes; ++l) {
-            a1 += red[0][(l * C4 + c / 4) * 4 + (c & 3)];
-            a2 += red[1][(l * C4 + c / 4) * 4 + (c & 3)];
-        }
-        unsafeAtomicAdd(slab + c, a1);
-        unsafeAtomicAdd(slab + C + c, a2);
-    }
-}
-
-struct BnSumArgs {
-    const float *y, *z, *mean, *invstd, *msc, *msh;
-    double *slab, *sums;
-    int relu_bias;
-};
-
 struct OutMap { int DH, DW, OH, OW, osh, osw, oh0, ow0; };   // explicit logical output grid + strided destination
 
 // filter [K][R][S][C] fp32 -> its two fp16 parts, scaled by the power of two the convolution kernel derives from the same word:
@@ -568,110 +530,69 @@ __global__ __launch_bounds__(256) void weight_split_f16_kernel(const f32x4 *w, c
 
 size_t igemm_lds(int bn, int sp = 1) { return sizeof(unsigned short) * 2 * (size_t)sp * (BM + bn) * LDK; }
 
-template <typename K>
-int launch(K kern, int blocks, int gz, size_t lds, hipStream_t stream, const ConvArgs &args, const char *name, int threads = 256)
-{
-    if (lds > 48 * 1024)
-        RR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), name);
-    hipLaunchKernelGGL(kern, dim3(blocks, 1, gz), dim3(threads), lds, stream, args);
-    RR_CHECK_LAUNCH(name);
-    return RR_OK;
-}
+// The arithmetic of a call.  split 0: bf16, filter16 = the filter already rounded to bf16, or null.  split 1: f16x3, the two
+// operands' maxima, filter16 = the filter's two fp16 images (rr_weight_split_f16), or null.
+struct Math16 {
+    int split;
+    const unsigned short *filter16;
+    const unsigned *amax_src, *amax_w;
+};
 
-int fprop_impl(const float *x, const float *w, const float *bias, float *y, double *stat_slab, int n, int h, int wd, int c,
-               int k, int r, int s, int stride, int pad_h, int pad_w, int relu, int accumulate, hipStream_t stream,
-               const BnSumArgs *bs = nullptr, const OutMap *om = nullptr, const unsigned short *w16 = nullptr,
-               int split = 0, const unsigned *amax_src = nullptr, const unsigned *amax_w = nullptr,
-               const unsigned short *w_split = nullptr)
+// name: the public entry point that was called.  How the call launches is rr_plan::fprop_plan's decision (conv_plan.h).
+int fprop_impl(const char *name, const Math16 &mt, const float *x, const float *w, const float *bias, float *y, double *stat_slab, int n, int h,
+               int wd, int c, int k, int r, int s, int stride, int pad_h, int pad_w, int relu, int accumulate, hipStream_t stream,
+               const BnSumArgs *bs = nullptr, const OutMap *om = nullptr)
 {
-    RR_CHECK_ARG(n > 0 && h > 0 && wd > 0 && c > 0 && k > 0 && r > 0 && s > 0 && stride > 0, "rr_conv_fprop_bf16: bad dims");
-    RR_CHECK_ARG(c % 4 == 0 && r * s <= 64, "rr_conv_fprop_bf16: C=%d must be a multiple of 4 and R*S <= 64 (fp32 path for the rest)", c);
+    RR_CHECK_ARG(!mt.split || (mt.amax_src && mt.amax_w), "%s: the operands' maxima are required", name);
+    const rr_plan::FpropPlan pl = rr_plan::fprop_plan(mt.split ? rr_plan::MATH_F16X3 : rr_plan::MATH_BF16,
+                                                      {n, h, wd, c, k, r, s, stride, pad_h, pad_w, om ? om->DH : 0, om ? om->DW : 0},
+                                                      {bias != nullptr, relu != 0, stat_slab != nullptr, rr_conv_link(bs), accumulate != 0, om != nullptr});
+    RR_CHECK_ARG(pl.refuse == nullptr, "%s: %s", name, pl.refuse);
     ConvArgs a{};
     a.src = x; a.w = w; a.dst = y; a.bias = bias; a.stat_slab = stat_slab;
-    a.w16 = (w16 != nullptr && c % 8 == 0) ? w16 : nullptr;       // 16-byte loads of 8 channels
-    RR_CHECK_ARG(w != nullptr || a.w16 != nullptr, "rr_conv_fprop_bf16: no filter");
+    a.w16 = (!mt.split && mt.filter16 != nullptr && c % 8 == 0) ? mt.filter16 : nullptr;       // 16-byte loads of 8 channels
+    RR_CHECK_ARG(w != nullptr || a.w16 != nullptr, "%s: no filter", name);
     a.N = n; a.SH = h; a.SW = wd; a.SC = c;
-    a.DH = (h + 2 * pad_h - r) / stride + 1; a.DW = (wd + 2 * pad_w - s) / stride + 1; a.DC = k;
+    a.DH = pl.dh; a.DW = pl.dw; a.DC = k;
     if (om != nullptr) {        // pads are LEADING pads; taps past the far edge are masked by the gather
-        a.DH = om->DH; a.DW = om->DW; a.OH = om->OH; a.OW = om->OW; a.osh = om->osh; a.osw = om->osw; a.oh0 = om->oh0; a.ow0 = om->ow0;
+        a.OH = om->OH; a.OW = om->OW; a.osh = om->osh; a.osw = om->osw; a.oh0 = om->oh0; a.ow0 = om->ow0;
     }
-    RR_CHECK_ARG(a.DH > 0 && a.DW > 0, "rr_conv_fprop_bf16: empty output");
     a.R = r; a.S = s; a.stride = stride; a.pad_h = pad_h; a.pad_w = pad_w;
-    a.relu = relu; a.accumulate = accumulate; a.ksplit = 1;
-    const long M = (long)n * a.DH * a.DW;
-    RR_CHECK_ARG(M < (1l << 31) && (long)n * h * wd * c * 4 < (1l << 31) && (long)k * r * s * c * 4 < (1l << 31) && M * k * 4 < (1l << 31),
-                 "rr_conv_fprop_bf16: tensors must stay below 2 GiB (32-bit buffer offsets)");
-    RR_CHECK_ARG(om == nullptr || (bs == nullptr && stat_slab == nullptr), "rr_conv_fprop_bf16: strided destination without fused sums");
-    a.M = (int)M; a.wK = k; a.wC = c;
-    int bn = k > 64 ? 128 : (k > 32 ? 64 : 32);
-    if (bn == 128 && rr_cdiv(M, BM) * rr_cdiv(k, 128) <= rr_conv_small_tiles()) bn = 32;
-    else if (bn == 128 && rr_cdiv(M, BM) * rr_cdiv(k, 128) <= rr_conv_mid_tiles()) bn = 64;
-    const int blocks = rr_cdiv(M, BM) * rr_cdiv(k, bn);
-    {
-        const int nt = rr_cdiv(k, bn), mt = rr_cdiv(M, BM);
-        a.xcd_n = (nt > 1 && 8 % nt == 0 && mt % (8 / nt) == 0) ? 1 : 0;
-    }
-    const int nk = rr_cdiv(c, BK) * r * s;
-    int ks = (bias == nullptr && !relu && k % 4 == 0 && k <= 1024) ? rr_conv_pick_ksplit(blocks, nk) : 1;
-    if (bs != nullptr && bs->relu_bias) ks = 1;
-    if (om != nullptr) ks = 1;       // (the zero fill of a split-K destination would wipe the other parity classes)
-    if (ks > 1) {
-        a.ksplit = ks;
-        // the split-K destination and (filled by colstats_bf16_kernel after the launch) the statistics slab: one zero-fill launch
-        const bool zslab = stat_slab != nullptr && bs == nullptr;
-        RR_CHECK_HIP(rr_zero2(accumulate ? nullptr : y, accumulate ? 0 : sizeof(float) * (size_t)M * k, zslab ? stat_slab : nullptr,
-                              zslab ? rr_conv_stat_slab_bytes(n, a.DH, a.DW, k) : 0, stream), "rr_conv_fprop_bf16");
-    }
-    const bool tiles_full = M % BM == 0;
-    RR_CHECK_ARG(bs == nullptr || !bs->relu_bias || tiles_full, "rr_conv_dgrad_s1_relubias_bf16: N*H*W = %ld must be a multiple of 128", M);
-    const bool fused = bs != nullptr && ks == 1 && tiles_full;
-    if (fused) {
-        a.stat_slab = bs->slab;
-        a.bs_y = bs->y; a.bs_z = bs->z; a.bs_mean = bs->mean; a.bs_invstd = bs->invstd; a.bs_msc = bs->msc; a.bs_msh = bs->msh;
-        a.bs_relu_bias = bs->relu_bias;
-    }
+    a.relu = relu; a.accumulate = accumulate; a.ksplit = pl.ks; a.xcd_n = pl.xcd_n;
+    a.M = (int)pl.M; a.wK = k; a.wC = c;
+    const int bn = pl.bn, blocks = pl.blocks, ks = pl.ks;
+    const bool fused = pl.fused;
+    if (fused) bs->into(a);
+    if (int rc = rr_conv_before_launch(pl, n, k, y, stat_slab, stream, name)) return rc;
     int rc;
-    const char *name = "rr_conv_fprop_bf16";
 #define RR_IG(BNv, BNSv, SOv)                                                                                      \
-    (a.w16 ? launch(conv_igemm_bf16_kernel<BNv, BNSv, true, SOv>, blocks, ks, igemm_lds(BNv), stream, a, name)           \
-           : launch(conv_igemm_bf16_kernel<BNv, BNSv, false, SOv>, blocks, ks, igemm_lds(BNv), stream, a, name))
+    (a.w16 ? rr_launch(conv_igemm_bf16_kernel<BNv, BNSv, true, SOv>, dim3(blocks, 1, ks), igemm_lds(BNv), stream, a, name)           \
+           : rr_launch(conv_igemm_bf16_kernel<BNv, BNSv, false, SOv>, dim3(blocks, 1, ks), igemm_lds(BNv), stream, a, name))
     // split operands (rr_conv_*_f16x3): two fp16 parts per operand, three matrix instructions per product tile
-#define RR_SX(BNv, BNSv, SOv) launch(conv_igemm_bf16_kernel<BNv, BNSv, false, SOv, 2, false, true>, blocks, ks, igemm_lds(BNv, 2), stream, a, name)
-    if (split) {
+#define RR_SX(BNv, BNSv, SOv) rr_launch(conv_igemm_bf16_kernel<BNv, BNSv, false, SOv, 2, false, true>, dim3(blocks, 1, ks), igemm_lds(BNv, 2), stream, a, name)
+    // the instance of launcher L for (fused sums | strided destination | plain) x tile width
+#define RR_PICK(L) (fused ? RR_PICK_BN(L, true, false) : a.osh ? RR_PICK_BN(L, false, true) : RR_PICK_BN(L, false, false))
+#define RR_PICK_BN(L, BNSv, SOv) (bn == 128 ? L(128, BNSv, SOv) : bn == 64 ? L(64, BNSv, SOv) : L(32, BNSv, SOv))
+    if (mt.split) {
         // (A wave-specialised 512-thread form of this kernel — round 4 — measured 2.84 ms against 2.27 ms for two 256-thread
         // workgroups per CU at 256 -> 256 3x3 on 8 x 256 x 256: a SIMD does not overlap one wave's matrix instructions with another
         // wave's vector instructions (tools/coissue_probe.hip).  Its launch arm was removed in round 6.)
-        a.w16 = nullptr;
-        a.amax_src = amax_src; a.amax_w = amax_w;
-        name = "rr_conv_fprop_f16x3";
-        if (w_split != nullptr && c % 8 == 0 && bn == 128) {
+        a.amax_src = mt.amax_src; a.amax_w = mt.amax_w;
+        if (mt.filter16 != nullptr && c % 8 == 0 && bn == 128) {
             // the filter's two fp16 images, made by rr_weight_split_f16 (once per optimizer step, outside the backward pass): the B16 instantiation
-            a.w16 = w_split;
-#define RR_SB(BNSv, SOv) launch(conv_igemm_bf16_kernel<128, BNSv, true, SOv, 2, false, true>, blocks, ks, igemm_lds(128, 2), stream, a, name)
+            a.w16 = mt.filter16;
+#define RR_SB(BNSv, SOv) rr_launch(conv_igemm_bf16_kernel<128, BNSv, true, SOv, 2, false, true>, dim3(blocks, 1, ks), igemm_lds(128, 2), stream, a, name)
             rc = fused ? RR_SB(true, false) : (a.osh ? RR_SB(false, true) : RR_SB(false, false));
 #undef RR_SB
         } else
-        if (fused) rc = bn == 128 ? RR_SX(128, true, false) : bn == 64 ? RR_SX(64, true, false) : RR_SX(32, true, false);
-        else if (a.osh) rc = bn == 128 ? RR_SX(128, false, true) : bn == 64 ? RR_SX(64, false, true) : RR_SX(32, false, true);
-        else rc = bn == 128 ? RR_SX(128, false, false) : bn == 64 ? RR_SX(64, false, false) : RR_SX(32, false, false);
+            rc = RR_PICK(RR_SX);
     } else
-    if (fused) rc = bn == 128 ? RR_IG(128, true, false) : bn == 64 ? RR_IG(64, true, false) : RR_IG(32, true, false);
-    else if (a.osh) rc = bn == 128 ? RR_IG(128, false, true) : bn == 64 ? RR_IG(64, false, true) : RR_IG(32, false, true);
-    else rc = bn == 128 ? RR_IG(128, false, false) : bn == 64 ? RR_IG(64, false, false) : RR_IG(32, false, false);
+        rc = RR_PICK(RR_IG);
 #undef RR_IG
 #undef RR_SX
-    if (rc == RR_OK && bs != nullptr) {
-        if (fused) return rr_bn_reduce_slab(bs->slab, (int)rr_cdiv(M, BM), k, bs->sums, stream);
-        return rr_bn_bwd_reduce(y, bs->z, bs->y, bs->mean, bs->invstd, bs->msc, bs->msh, bs->sums, M, k, 1, stream);
-    }
-    if (rc == RR_OK && ks > 1 && stat_slab != nullptr) {
-        const int lanes = 256 / (k / 4);
-        int sblocks = rr_cdiv(M, (long)lanes * 8);
-        if (sblocks > 256) sblocks = 256;
-        hipLaunchKernelGGL(colstats_bf16_kernel, dim3(sblocks), dim3(256), 0, stream, y, M, k, stat_slab);
-        RR_CHECK_LAUNCH("rr_conv_fprop_bf16(stats)");
-    }
-    return rc;
+#undef RR_PICK
+#undef RR_PICK_BN
+    return rc == RR_OK ? rr_conv_after_launch(pl, bs, k, y, stat_slab, stream, name) : rc;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -912,18 +833,23 @@ extern "C" int rr_conv_fprop_bf16(const float *x, const float *w, const float *b
                                   int n, int h, int wd, int c, int k, int r, int s, int stride, int pad_h,
                                   int pad_w, int relu, const unsigned short *w_bf16, hipStream_t stream)
 {
-    return fprop_impl(x, w, bias, y, stat_slab, n, h, wd, c, k, r, s, stride, pad_h, pad_w, relu, 0, stream, nullptr, nullptr, w_bf16);
+    return fprop_impl("rr_conv_fprop_bf16", {0, w_bf16}, x, w, bias, y, stat_slab, n, h, wd, c, k, r, s, stride, pad_h, pad_w, relu, 0, stream);
+}
+
+// the stride-1 data gradients: rr_dgrad_s1_geom's checks and flip (conv_launch.h), then the forward kernel on (dy, wt)
+static int dgrad_s1(const char *name, const Math16 &mt, bool producer_ok, const float *dy, const float *wt, float *dx, int n, int h, int wd,
+                    int c, int k, int r, int s, int pad_h, int pad_w, int accumulate, hipStream_t stream, const BnSumArgs *bs = nullptr)
+{
+    DgradS1Geom g;
+    if (int rc = rr_dgrad_s1_geom(name, h, wd, r, s, pad_h, pad_w, producer_ok, &g)) return rc;
+    return fprop_impl(name, mt, dy, wt, nullptr, dx, nullptr, n, g.p, g.q, k, c, r, s, 1, g.pad_h, g.pad_w, 0, accumulate, stream, bs);
 }
 
 extern "C" int rr_conv_dgrad_s1_bf16(const float *dy, const float *wt, float *dx, int n, int h, int wd, int c, int k,
                                      int r, int s, int pad_h, int pad_w, int accumulate, const unsigned short *wt_bf16,
                                      hipStream_t stream)
 {
-    RR_CHECK_ARG(pad_h < r && pad_w < s && pad_h >= 0 && pad_w >= 0, "rr_conv_dgrad_s1_bf16: pad must be in [0, kernel)");
-    const int p = h + 2 * pad_h - r + 1, q = wd + 2 * pad_w - s + 1;
-    RR_CHECK_ARG(p > 0 && q > 0, "rr_conv_dgrad_s1_bf16: empty dy");
-    return fprop_impl(dy, wt, nullptr, dx, nullptr, n, p, q, k, c, r, s, 1, r - 1 - pad_h, s - 1 - pad_w, 0, accumulate, stream,
-                      nullptr, nullptr, wt_bf16);
+    return dgrad_s1("rr_conv_dgrad_s1_bf16", {0, wt_bf16}, true, dy, wt, dx, n, h, wd, c, k, r, s, pad_h, pad_w, accumulate, stream);
 }
 
 extern "C" int rr_conv_dgrad_s1_bnsum_bf16(const float *dy, const float *wt, float *dx, int n, int h, int wd, int c, int k,
@@ -932,98 +858,46 @@ extern "C" int rr_conv_dgrad_s1_bnsum_bf16(const float *dy, const float *wt, flo
                                            const float *prod_mask_scale, const float *prod_mask_shift, double *slab,
                                            double *sums, const unsigned short *wt_bf16, hipStream_t stream)
 {
-    RR_CHECK_ARG(pad_h < r && pad_w < s && pad_h >= 0 && pad_w >= 0, "rr_conv_dgrad_s1_bnsum_bf16: pad must be in [0, kernel)");
-    RR_CHECK_ARG(prod_y && prod_mean && prod_invstd && slab && sums && (!prod_mask_scale == !prod_mask_shift),
-                 "rr_conv_dgrad_s1_bnsum_bf16: the producer's y / mean / invstd and the two buffers are required");
-    RR_CHECK_ARG(c % 4 == 0 && c <= 1024, "rr_conv_dgrad_s1_bnsum_bf16: C=%d must be a multiple of 4 and <= 1024", c);
-    const int p = h + 2 * pad_h - r + 1, q = wd + 2 * pad_w - s + 1;
-    RR_CHECK_ARG(p > 0 && q > 0, "rr_conv_dgrad_s1_bnsum_bf16: empty dy");
     const BnSumArgs bs{prod_y, prod_z, prod_mean, prod_invstd, prod_mask_scale, prod_mask_shift, slab, sums, 0};
-    return fprop_impl(dy, wt, nullptr, dx, nullptr, n, p, q, k, c, r, s, 1, r - 1 - pad_h, s - 1 - pad_w, 0, accumulate, stream, &bs,
-                      nullptr, wt_bf16);
+    return dgrad_s1("rr_conv_dgrad_s1_bnsum_bf16", {0, wt_bf16}, bs.bn_ok(c), dy, wt, dx, n, h, wd, c, k, r, s, pad_h, pad_w, accumulate,
+                    stream, &bs);
 }
 
 extern "C" int rr_conv_dgrad_s1_relubias_bf16(const float *dy, const float *wt, float *dx, int n, int h, int wd, int c, int k,
                                               int r, int s, int pad_h, int pad_w, int accumulate, const float *prod_z,
                                               double *slab, double *sums, hipStream_t stream)
 {
-    RR_CHECK_ARG(pad_h < r && pad_w < s && pad_h >= 0 && pad_w >= 0, "rr_conv_dgrad_s1_relubias_bf16: pad must be in [0, kernel)");
-    RR_CHECK_ARG(prod_z && slab && sums, "rr_conv_dgrad_s1_relubias_bf16: the producer's output and the two buffers are required");
-    RR_CHECK_ARG(c % 4 == 0 && k % 4 == 0 && c <= 1024, "rr_conv_dgrad_s1_relubias_bf16: C=%d, K=%d must be multiples of 4", c, k);
-    const int p = h + 2 * pad_h - r + 1, q = wd + 2 * pad_w - s + 1;
-    RR_CHECK_ARG(p > 0 && q > 0, "rr_conv_dgrad_s1_relubias_bf16: empty dy");
     const BnSumArgs bs{prod_z, prod_z, nullptr, nullptr, nullptr, nullptr, slab, sums, 1};
-    return fprop_impl(dy, wt, nullptr, dx, nullptr, n, p, q, k, c, r, s, 1, r - 1 - pad_h, s - 1 - pad_w, 0, accumulate, stream, &bs);
+    return dgrad_s1("rr_conv_dgrad_s1_relubias_bf16", {0, nullptr}, bs.relu_bias_ok(c, k), dy, wt, dx, n, h, wd, c, k, r, s, pad_h, pad_w,
+                    accumulate, stream, &bs);
 }
 
 // Stride-2 data gradient on the forward kernel: dx[n, 2a+ph, 2b+pw, c] = sum over the taps r = r0 + 2i, s = s0 + 2j that
 // reach output parity class (ph, pw) (r0 = (ph + pad_h) & 1) of dY[n, a + (ph+pad_h-r0)/2 - i, ..., k] * w[k][r][s][c] — per
-// class a stride-1 correlation of dY with a sub-filter of ceil / floor (R/2) x (S/2) taps, written to every second pixel.
-// The four sub-filters are packed, flipped and transposed ([c][i'][j'][k], i' = Rc-1-i), into caller scratch of
-// k*r*s*c floats by one kernel; a 3x3 visits 1 / 2 / 2 / 4 taps instead of masking three quarters of a dilated filter.
-__global__ __launch_bounds__(256) void weight_parity_pack_kernel(const float *w, float *wsub, int K, int C, int R, int S,
-                                                                 int pad_h, int pad_w, long total)
+// class a stride-1 correlation of dY with a sub-filter of ceil / floor (R/2) x (S/2) taps, written to every second pixel
+// (rr_plan::parity_classes).  The four sub-filters are packed into caller scratch of k*r*s*c floats by one kernel
+// (rr_parity_pack); a 3x3 visits 1 / 2 / 2 / 4 taps instead of masking three quarters of a dilated filter.
+static int dgrad_s2_impl(const char *name, const Math16 &mt, const float *dy, const float *w, float *dx, int n, int h, int wd, int c, int k,
+                         int r, int s, int pad_h, int pad_w, int accumulate, float *wsub, hipStream_t stream)
 {
-    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
-        const int k = (int)(idx % K);
-        long rest = idx / K;
-        const int tap = (int)(rest % (R * S));
-        const int c = (int)(rest / (R * S));
-        const int r = tap / S, s = tap - r * S;
-        const int ph = (r - pad_h) & 1, pw = (s - pad_w) & 1;
-        const int r0 = (ph + pad_h) & 1, s0 = (pw + pad_w) & 1;
-        const int Rc = (R - r0 + 1) / 2, Sc = (S - s0 + 1) / 2;
-        // class blocks in the order (0,0), (0,1), (1,0), (1,1); block size C * Rc * Sc * K
-        long base = 0;
-        for (int cl = 0; cl < ph * 2 + pw; ++cl) {
-            const int q0 = ((cl >> 1) + pad_h) & 1, t0 = ((cl & 1) + pad_w) & 1;
-            base += (long)C * (q0 < R ? (R - q0 + 1) / 2 : 0) * (t0 < S ? (S - t0 + 1) / 2 : 0) * K;
-        }
-        const int ii = Rc - 1 - (r - r0) / 2, jj = Sc - 1 - (s - s0) / 2;
-        wsub[base + (((long)c * Rc + ii) * Sc + jj) * K + k] = w[((long)k * R * S + tap) * C + c];
-    }
-}
-
-static int dgrad_s2_impl(const float *dy, const float *w, float *dx, int n, int h, int wd, int c, int k, int r, int s, int pad_h,
-                         int pad_w, int accumulate, float *wsub, hipStream_t stream, int split, const unsigned *amax_dy,
-                         const unsigned *amax_w)
-{
-    RR_CHECK_ARG(n > 0 && h > 0 && wd > 0 && c > 0 && k > 0 && r > 0 && s > 0, "rr_conv_dgrad_s2_bf16: bad dims");
-    RR_CHECK_ARG(c % 4 == 0 && k % 4 == 0 && r * s <= 64 && pad_h >= 0 && pad_w >= 0 && wsub != nullptr,
-                 "rr_conv_dgrad_s2_bf16: C, K multiples of 4, R*S <= 64, scratch of k*r*s*c floats required");
+    RR_CHECK_ARG(n > 0 && h > 0 && wd > 0 && c > 0 && k > 0 && r > 0 && s > 0, "%s: bad dims", name);
+    RR_CHECK_ARG(c % 4 == 0 && k % 4 == 0 && r * s <= 64 && pad_h >= 0 && pad_w >= 0 && wsub != nullptr && (!mt.split || (mt.amax_src && mt.amax_w)),
+                 "%s: C, K multiples of 4, R*S <= 64, scratch of k*r*s*c floats (and, split operands, the two maxima) required", name);
     const int p = (h + 2 * pad_h - r) / 2 + 1, q = (wd + 2 * pad_w - s) / 2 + 1;
-    RR_CHECK_ARG(p > 0 && q > 0, "rr_conv_dgrad_s2_bf16: empty dy");
-    const long total = (long)k * c * r * s;
-    hipLaunchKernelGGL(weight_parity_pack_kernel, dim3((int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256)), dim3(256), 0,
-                       stream, w, wsub, k, c, r, s, pad_h, pad_w, total);
-    RR_CHECK_LAUNCH("rr_conv_dgrad_s2_bf16(pack)");
-    int Rc[4], Sc[4], lead_h[4], lead_w[4];
-    bool any_empty = false;
-    for (int cl = 0; cl < 4; ++cl) {
-        const int ph = cl >> 1, pw = cl & 1;
-        const int r0 = (ph + pad_h) & 1, s0 = (pw + pad_w) & 1;
-        Rc[cl] = r0 < r ? (r - r0 + 1) / 2 : 0;
-        Sc[cl] = s0 < s ? (s - s0 + 1) / 2 : 0;
-        lead_h[cl] = (Rc[cl] - 1) - (ph + pad_h - r0) / 2;
-        lead_w[cl] = (Sc[cl] - 1) - (pw + pad_w - s0) / 2;
-        const int Hc = (h - ph + 1) / 2, Wc = (wd - pw + 1) / 2;
-        if (Hc > 0 && Wc > 0 && Rc[cl] * Sc[cl] == 0) any_empty = true;
-        RR_CHECK_ARG(Rc[cl] * Sc[cl] == 0 || (lead_h[cl] >= 0 && lead_w[cl] >= 0), "rr_conv_dgrad_s2_bf16: unsupported padding %d,%d", pad_h, pad_w);
-    }
+    RR_CHECK_ARG(p > 0 && q > 0, "%s: empty dy", name);
+    if (int rc = rr_parity_pack(w, wsub, k, c, r, s, pad_h, pad_w, stream, name)) return rc;
+    rr_plan::ParityClass cls[4];
+    const bool any_empty = rr_plan::parity_classes(h, wd, r, s, pad_h, pad_w, cls);
+    for (const rr_plan::ParityClass &pc : cls)
+        RR_CHECK_ARG(pc.taps() == 0 || (pc.lead_h >= 0 && pc.lead_w >= 0), "%s: unsupported padding %d,%d", name, pad_h, pad_w);
     // parity classes no tap reaches (a 1x1 stride 2: three of four) are zero
-    if (any_empty && !accumulate) RR_CHECK_HIP(hipMemsetAsync(dx, 0, sizeof(float) * (size_t)n * h * wd * c, stream), "rr_conv_dgrad_s2_bf16");
-    long base = 0;
-    for (int cl = 0; cl < 4; ++cl) {
-        const int ph = cl >> 1, pw = cl & 1;
-        const int Hc = (h - ph + 1) / 2, Wc = (wd - pw + 1) / 2;
-        const long blk = (long)c * Rc[cl] * Sc[cl] * k;
-        if (blk > 0 && Hc > 0 && Wc > 0) {
-            const OutMap om{Hc, Wc, h, wd, 2, 2, ph, pw};
-            const int rc = fprop_impl(dy, wsub + base, nullptr, dx, nullptr, n, p, q, k, c, Rc[cl], Sc[cl], 1, lead_h[cl], lead_w[cl], 0,
-                                      accumulate, stream, nullptr, &om, nullptr, split, amax_dy, amax_w);
-            if (rc != RR_OK) return rc;
-        }
-        base += blk;
+    if (any_empty && !accumulate) RR_CHECK_HIP(hipMemsetAsync(dx, 0, sizeof(float) * (size_t)n * h * wd * c, stream), name);
+    for (const rr_plan::ParityClass &pc : cls) {
+        if (pc.taps() == 0 || pc.Hc <= 0 || pc.Wc <= 0) continue;
+        const OutMap om{pc.Hc, pc.Wc, h, wd, 2, 2, pc.ph, pc.pw};
+        if (int rc = fprop_impl(name, mt, dy, wsub + (long)pc.taps_before * c * k, nullptr, dx, nullptr, n, p, q, k, c, pc.Rc, pc.Sc, 1, pc.lead_h,
+                                pc.lead_w, 0, accumulate, stream, nullptr, &om))
+            return rc;
     }
     return RR_OK;
 }
@@ -1031,7 +905,7 @@ static int dgrad_s2_impl(const float *dy, const float *w, float *dx, int n, int 
 extern "C" int rr_conv_dgrad_s2_bf16(const float *dy, const float *w, float *dx, int n, int h, int wd, int c, int k,
                                      int r, int s, int pad_h, int pad_w, int accumulate, float *wsub, hipStream_t stream)
 {
-    return dgrad_s2_impl(dy, w, dx, n, h, wd, c, k, r, s, pad_h, pad_w, accumulate, wsub, stream, 0, nullptr, nullptr);
+    return dgrad_s2_impl("rr_conv_dgrad_s2_bf16", {0, nullptr}, dy, w, dx, n, h, wd, c, k, r, s, pad_h, pad_w, accumulate, wsub, stream);
 }
 
 static int wgrad_impl(const float *x, const float *dy, float *dw, int n, int h, int wd, int c, int k, int r, int s, int stride,
@@ -1056,22 +930,10 @@ static int wgrad_impl(const float *x, const float *dy, float *dw, int n, int h, 
     const int total_chunks = rr_cdiv(M, BK);
     // pixel splits: fill the resident-workgroup slots (256 CUs x 4; x 2 for the split kernel's 68 KB of LDS) once, never fewer
     // than 16 K-steps per split
-    const int slots = split ? 512 : 1024;
-    int splits = tiles < slots ? slots / tiles : 1;
-    if (splits > rr_cdiv(total_chunks, 16)) splits = rr_cdiv(total_chunks, 16);
-    if (splits < 1) splits = 1;
-    a.chunks_per_split = rr_cdiv(total_chunks, splits);
-    splits = rr_cdiv(total_chunks, a.chunks_per_split);
+    const int splits = rr_plan::pixel_splits(tiles, total_chunks, split ? 512 : 1024, 16, &a.chunks_per_split);
     const size_t lds = sizeof(unsigned short) * 4 * 4 * (32 * 32 + 32) * (split ? 2 : 1);  // 2 operands x 2 buffers x (parts) x 4 blocks of 32 x 32 (+ pad)
-    if (split) {
-        auto kern = conv_wgrad_bf16_kernel<2, true>;
-        RR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "rr_conv_wgrad_f16x3");
-        hipLaunchKernelGGL(kern, dim3(tiles * splits), dim3(256), lds, stream, a);
-    } else {
-        hipLaunchKernelGGL((conv_wgrad_bf16_kernel<1, false>), dim3(tiles * splits), dim3(256), lds, stream, a);
-    }
-    RR_CHECK_LAUNCH("rr_conv_wgrad_bf16");
-    return RR_OK;
+    return split ? rr_launch(conv_wgrad_bf16_kernel<2, true>, dim3(tiles * splits), lds, stream, a, "rr_conv_wgrad_f16x3")
+                 : rr_launch(conv_wgrad_bf16_kernel<1, false>, dim3(tiles * splits), lds, stream, a, "rr_conv_wgrad_bf16");
 }
 
 extern "C" int rr_conv_wgrad_bf16(const float *x, const float *dy, float *dw, int n, int h, int wd, int c, int k,
@@ -1103,21 +965,15 @@ extern "C" int rr_conv_fprop_f16x3(const float *x, const float *w, const float *
                                    int pad_w, int relu, const unsigned *amax_x, const unsigned *amax_w,
                                    const unsigned short *w_split, hipStream_t stream)
 {
-    RR_CHECK_ARG(amax_x && amax_w, "rr_conv_fprop_f16x3: the operands' maxima are required");
-    return fprop_impl(x, w, bias, y, stat_slab, n, h, wd, c, k, r, s, stride, pad_h, pad_w, relu, 0, stream, nullptr, nullptr, nullptr,
-                      1, amax_x, amax_w, w_split);
+    return fprop_impl("rr_conv_fprop_f16x3", {1, w_split, amax_x, amax_w}, x, w, bias, y, stat_slab, n, h, wd, c, k, r, s, stride, pad_h, pad_w,
+                      relu, 0, stream);
 }
 
 extern "C" int rr_conv_dgrad_s1_f16x3(const float *dy, const float *wt, float *dx, int n, int h, int wd, int c, int k,
                                       int r, int s, int pad_h, int pad_w, int accumulate, const unsigned *amax_dy,
                                       const unsigned *amax_w, const unsigned short *wt_split, hipStream_t stream)
 {
-    RR_CHECK_ARG(pad_h < r && pad_w < s && pad_h >= 0 && pad_w >= 0, "rr_conv_dgrad_s1_f16x3: pad must be in [0, kernel)");
-    RR_CHECK_ARG(amax_dy && amax_w, "rr_conv_dgrad_s1_f16x3: the operands' maxima are required");
-    const int p = h + 2 * pad_h - r + 1, q = wd + 2 * pad_w - s + 1;
-    RR_CHECK_ARG(p > 0 && q > 0, "rr_conv_dgrad_s1_f16x3: empty dy");
-    return fprop_impl(dy, wt, nullptr, dx, nullptr, n, p, q, k, c, r, s, 1, r - 1 - pad_h, s - 1 - pad_w, 0, accumulate, stream,
-                      nullptr, nullptr, nullptr, 1, amax_dy, amax_w, wt_split);
+    return dgrad_s1("rr_conv_dgrad_s1_f16x3", {1, wt_split, amax_dy, amax_w}, true, dy, wt, dx, n, h, wd, c, k, r, s, pad_h, pad_w, accumulate, stream);
 }
 
 extern "C" int rr_conv_dgrad_s1_bnsum_f16x3(const float *dy, const float *wt, float *dx, int n, int h, int wd, int c, int k,
@@ -1127,15 +983,9 @@ extern "C" int rr_conv_dgrad_s1_bnsum_f16x3(const float *dy, const float *wt, fl
                                             double *sums, const unsigned *amax_dy, const unsigned *amax_w,
                                             const unsigned short *wt_split, hipStream_t stream)
 {
-    RR_CHECK_ARG(pad_h < r && pad_w < s && pad_h >= 0 && pad_w >= 0, "rr_conv_dgrad_s1_bnsum_f16x3: pad must be in [0, kernel)");
-    RR_CHECK_ARG(prod_y && prod_mean && prod_invstd && slab && sums && (!prod_mask_scale == !prod_mask_shift) && amax_dy && amax_w,
-                 "rr_conv_dgrad_s1_bnsum_f16x3: the producer's y / mean / invstd, the two buffers and the maxima are required");
-    RR_CHECK_ARG(c % 4 == 0 && c <= 1024, "rr_conv_dgrad_s1_bnsum_f16x3: C=%d must be a multiple of 4 and <= 1024", c);
-    const int p = h + 2 * pad_h - r + 1, q = wd + 2 * pad_w - s + 1;
-    RR_CHECK_ARG(p > 0 && q > 0, "rr_conv_dgrad_s1_bnsum_f16x3: empty dy");
     const BnSumArgs bs{prod_y, prod_z, prod_mean, prod_invstd, prod_mask_scale, prod_mask_shift, slab, sums, 0};
-    return fprop_impl(dy, wt, nullptr, dx, nullptr, n, p, q, k, c, r, s, 1, r - 1 - pad_h, s - 1 - pad_w, 0, accumulate, stream, &bs,
-                      nullptr, nullptr, 1, amax_dy, amax_w, wt_split);
+    return dgrad_s1("rr_conv_dgrad_s1_bnsum_f16x3", {1, wt_split, amax_dy, amax_w}, bs.bn_ok(c), dy, wt, dx, n, h, wd, c, k, r, s, pad_h, pad_w,
+                    accumulate, stream, &bs);
 }
 
 extern "C" int rr_conv_dgrad_s1_relubias_f16x3(const float *dy, const float *wt, float *dx, int n, int h, int wd, int c, int k,
@@ -1143,22 +993,17 @@ extern "C" int rr_conv_dgrad_s1_relubias_f16x3(const float *dy, const float *wt,
                                                double *slab, double *sums, const unsigned *amax_dy, const unsigned *amax_w,
                                                hipStream_t stream)
 {
-    RR_CHECK_ARG(pad_h < r && pad_w < s && pad_h >= 0 && pad_w >= 0, "rr_conv_dgrad_s1_relubias_f16x3: pad must be in [0, kernel)");
-    RR_CHECK_ARG(prod_z && slab && sums && amax_dy && amax_w, "rr_conv_dgrad_s1_relubias_f16x3: the producer's output, the two buffers and the maxima are required");
-    RR_CHECK_ARG(c % 4 == 0 && k % 4 == 0 && c <= 1024, "rr_conv_dgrad_s1_relubias_f16x3: C=%d, K=%d must be multiples of 4", c, k);
-    const int p = h + 2 * pad_h - r + 1, q = wd + 2 * pad_w - s + 1;
-    RR_CHECK_ARG(p > 0 && q > 0, "rr_conv_dgrad_s1_relubias_f16x3: empty dy");
     const BnSumArgs bs{prod_z, prod_z, nullptr, nullptr, nullptr, nullptr, slab, sums, 1};
-    return fprop_impl(dy, wt, nullptr, dx, nullptr, n, p, q, k, c, r, s, 1, r - 1 - pad_h, s - 1 - pad_w, 0, accumulate, stream, &bs,
-                      nullptr, nullptr, 1, amax_dy, amax_w);
+    return dgrad_s1("rr_conv_dgrad_s1_relubias_f16x3", {1, nullptr, amax_dy, amax_w}, bs.relu_bias_ok(c, k), dy, wt, dx, n, h, wd, c, k, r, s,
+                    pad_h, pad_w, accumulate, stream, &bs);
 }
 
 extern "C" int rr_conv_dgrad_s2_f16x3(const float *dy, const float *w, float *dx, int n, int h, int wd, int c, int k,
                                       int r, int s, int pad_h, int pad_w, int accumulate, float *wsub, const unsigned *amax_dy,
                                       const unsigned *amax_w, hipStream_t stream)
 {
-    RR_CHECK_ARG(amax_dy && amax_w, "rr_conv_dgrad_s2_f16x3: the operands' maxima are required");
-    return dgrad_s2_impl(dy, w, dx, n, h, wd, c, k, r, s, pad_h, pad_w, accumulate, wsub, stream, 1, amax_dy, amax_w);
+    return dgrad_s2_impl("rr_conv_dgrad_s2_f16x3", {1, nullptr, amax_dy, amax_w}, dy, w, dx, n, h, wd, c, k, r, s, pad_h, pad_w, accumulate, wsub,
+                         stream);
 }
 
 extern "C" int rr_conv_wgrad_f16x3(const float *x, const float *dy, float *dw, int n, int h, int wd, int c, int k,

@@ -17,6 +17,7 @@
 // Layouts: x NHWC; offset NHWC [N,P,Q,2*dg*R*S] (per group: interleaved (dh,dw) per tap, as the
 // reference's channel order); mask NHWC [N,P,Q,dg*R*S]; weight OHWI.
 #include "common.h"
+#include "conv_plan.h"
 #include "rrnet_hip.h"
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
@@ -2446,11 +2447,7 @@ static int dcn_wgrad_plain(const float *x, const float *offset, const float *mas
     b.mt = rr_cdiv(k, 128); b.nt = rr_cdiv(c, 128);
     const int tiles = b.mt * b.nt * r * s;
     const int total_chunks = rr_cdiv(b.a.M, BK);
-    int splits = tiles < 512 ? 512 / tiles : 1;
-    if (splits > rr_cdiv(total_chunks, 8)) splits = rr_cdiv(total_chunks, 8);
-    if (splits < 1) splits = 1;
-    b.chunks_per_split = rr_cdiv(total_chunks, splits);
-    splits = rr_cdiv(total_chunks, b.chunks_per_split);
+    const int splits = rr_plan::pixel_splits(tiles, total_chunks, 512, 8, &b.chunks_per_split);
     const size_t lds = sizeof(float) * 2 * (BK * 128 + BK * 128);
     hipFuncSetAttribute(reinterpret_cast<const void *>(dcn_wgrad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(dcn_wgrad_kernel, dim3(tiles * splits), dim3(256), lds, stream, b);

@@ -464,14 +464,15 @@ def amax_of(t):
 AMAX_CHECKED = [0]       # remembered maxima verified under RR_AMAX_CHECK=1 (the audit asserts that the check really ran)
 
 
-def _math_tail(mode, filter16, src, flt, filter_split):
-    """The trailing arguments of a forward-kernel launch under the three arithmetics: fp32 (stream), bf16 (the filter's cached
-    bf16 copy or NULL, stream), f16x3 (the two operands' maxima, the filter's ready-made fp16 split or NULL, stream)."""
-    if mode == MATH_F16X3:
-        return (_C.ptr(amax_of(src)), _C.ptr(amax_of(flt)), _C.ptr(filter_split), _C.stream())
-    if mode == MATH_BF16:
-        return (_C.ptr(filter16), _C.stream())
-    return (_C.stream(),)
+def _math_call(mode, a, b, filter16=None, filter_split=None, takes_filter=False):
+    """-> (entry-point suffix, timer tag, trailing arguments) of a convolution entry point under arithmetic `mode`: fp32 ("", "", stream),
+    bf16 ("_bf16", "+bf16", stream), f16x3 ("_f16x3", "+f16x3", the maxima of the operands a and b, stream).  takes_filter (rr_conv_fprop*,
+    rr_conv_dgrad_s1{,_bnsum}*; not _relubias, _s2, wgrad): in front of the stream the filter's cached bf16 copy / fp16 split, or NULL."""
+    sfx = ("", "_bf16", "_f16x3")[mode]
+    tail = (_C.ptr(amax_of(a)), _C.ptr(amax_of(b))) if mode == MATH_F16X3 else ()
+    if takes_filter and mode != MATH_F32:
+        tail += (_C.ptr(filter_split if mode == MATH_F16X3 else filter16),)
+    return sfx, sfx.replace("_", "+"), tail + (_C.stream(),)
 
 
 def conv_fprop(x, w, bias=None, stride=1, pad=(0, 0), relu=False, want_stats=False, algo_kg=None, w16=None, w_split=None,
@@ -517,7 +518,6 @@ def conv_fprop(x, w, bias=None, stride=1, pad=(0, 0), relu=False, want_stats=Fal
         nbytes = _C.fn("rr_conv_stat_slab_bytes")(n, p, q, k)
         slab = torch.empty(nbytes // 8, dtype=torch.float64, device=x.device)
     bf = _bf16_ok(c, 4 if _mode() != MATH_F16X3 else k, r, s, x, w, y, pixels=n * p * q)
-    f = _C.fn(("rr_conv_fprop", "rr_conv_fprop_bf16", "rr_conv_fprop_f16x3")[bf])
     flops = 2.0 * n * p * q * k * (c * r * s if algo_kg is None else algo_kg)
     # w16: the filter already rounded to bf16 (optional); split operands: the two tensors' maxima
     if bf == MATH_F16X3 and w_split is None:
@@ -525,8 +525,9 @@ def conv_fprop(x, w, bias=None, stride=1, pad=(0, 0), relu=False, want_stats=Fal
         # released before the launch, the caching allocator handed its block to the next zero-filled scratch, and the
         # data gradients read a filter of zeros / garbage — non-finite gradients, and a step that ran 10 % FASTER
         w_split = split_filter(w, amax_of(w), n * p * q)
-    tail = _math_tail(bf, w16, x, w, w_split)
-    _C.check(_timed(_igemm_name("fprop", k, c % 4 != 0, n * p * q) + ("", "+bf16", "+f16x3")[bf], flops,
+    sfx, tag, tail = _math_call(bf, x, w, w16, w_split, takes_filter=True)
+    f = _C.fn("rr_conv_fprop" + sfx)
+    _C.check(_timed(_igemm_name("fprop", k, c % 4 != 0, n * p * q) + tag, flops,
                     lambda: f(_C.ptr(x), _C.ptr(w), _C.ptr(bias), _C.ptr(y), _C.ptr(slab), n, h, wd, c, k, r, s,
                               stride, pad[0], pad[1], int(relu), *tail),
                     (n, h, wd, c, k, r, s, stride), 4.0 * (x.numel() + y.numel() + w.numel())), "rr_conv_fprop")
@@ -744,9 +745,9 @@ def _dgrad_relubias(dy, w, out, geo, flops, bf, link, z, wt, head):
         dy, w = dyp, wp
     wt = _flipped_filter(w, wt, None, False)[0]
     slab = torch.empty(_C.fn("rr_conv_stat_slab_bytes")(n, h, wd, c) // 8, dtype=torch.float64, device=dy.device)
-    tail = (_C.ptr(amax_of(dy)), _C.ptr(amax_of(w)), _C.stream()) if bf == MATH_F16X3 else (_C.stream(),)
-    f = _C.fn("rr_conv_dgrad_s1_relubias" + ("", "_bf16", "_f16x3")[bf])
-    _C.check(_timed(_igemm_name("fprop", c, False, n * h * wd) + "+relubias" + ("", "+bf16", "+f16x3")[bf], flops,
+    sfx, tag, tail = _math_call(bf, dy, w)
+    f = _C.fn("rr_conv_dgrad_s1_relubias" + sfx)
+    _C.check(_timed(_igemm_name("fprop", c, False, n * h * wd) + "+relubias" + tag, flops,
                     lambda: f(_C.ptr(dy), _C.ptr(wt), _C.ptr(out), n, h, wd, c, kp, *geo[5:], _C.ptr(z), _C.ptr(slab), _C.ptr(link.sums), *tail),
                     geo[:7] + (1,)), "rr_conv_dgrad_s1_relubias")
 
@@ -756,11 +757,11 @@ def _dgrad_fprop(dy, w, out, geo, flops, bf, wt, wt16, wt_split, link=None, z=No
     convolution, timed under its name; with a link the producer's BatchNorm-backward sums come out of its epilogue."""
     n, h, wd, c = geo[:4]
     wt = _flipped_filter(w, wt, None, False)[0]
-    sfx = ("_bnsum" if link is not None else "") + ("", "_bf16", "_f16x3")[bf]
-    name = _igemm_name("fprop", c, False, n * h * wd) + sfx.replace("_", "+")
     if bf == MATH_F16X3 and wt_split is None:
         wt_split = split_filter(w, amax_of(w), n * h * wd, flat=wt)
-    tail = _math_tail(bf, wt16, dy, w, wt_split)
+    sfx, tag, tail = _math_call(bf, dy, w, wt16, wt_split, takes_filter=True)
+    sfx = ("_bnsum" if link is not None else "") + sfx
+    name = _igemm_name("fprop", c, False, n * h * wd) + ("+bnsum" if link is not None else "") + tag
     if link is not None:
         slab = torch.empty(_C.fn("rr_conv_stat_slab_bytes")(n, h, wd, c) // 8, dtype=torch.float64, device=dy.device)
         link.sums, link.dz = _ZEROS.take(2 * c, dy.device), out
@@ -775,9 +776,9 @@ def _dgrad_s2(dy, w, out, geo, flops, bf, conv16):
     """conv16_s2 / parity_s2: a forward-kernel launch per output parity class on its sub-filter, packed inside the call, on dY's bf16 image / on dy."""
     src = bf16_of(dy) if conv16 else dy
     wsub = torch.empty(w.numel(), dtype=torch.bfloat16 if conv16 else torch.float32, device=dy.device)
-    f = _C.fn("rr_conv16_dgrad_s2" if conv16 else ("rr_conv_dgrad_s2_f16x3" if bf == MATH_F16X3 else "rr_conv_dgrad_s2_bf16"))
-    tail = (_C.ptr(amax_of(dy)), _C.ptr(amax_of(w)), _C.stream()) if bf == MATH_F16X3 else (_C.stream(),)
-    _C.check(_timed("conv16_dgrad_s2" if conv16 else "conv_dgrad_s2" + ("", "+bf16", "+f16x3")[bf], flops,
+    sfx, tag, tail = _math_call(bf, dy, w)             # (bf is never MATH_F32 here, and MATH_BF16 under conv16: dgrad_route)
+    f = _C.fn("rr_conv16_dgrad_s2" if conv16 else "rr_conv_dgrad_s2" + sfx)
+    _C.check(_timed("conv16_dgrad_s2" if conv16 else "conv_dgrad_s2" + tag, flops,
                     lambda: f(_C.ptr(src), _C.ptr(w), _C.ptr(out), *geo, _C.ptr(wsub), *tail), geo[:7] + (2,)), "rr_conv_dgrad_s2")
 
 
@@ -842,9 +843,9 @@ def conv_wgrad(x, dy, dw, stride=1, pad=(0, 0), explicit_out=False, algo_c=None)
         return dw
     x, dy = f32_of(x), f32_of(dy)            # (bf16-only operands in front of a layer the conv16 weight gradient does not take)
     bf = _bf16_ok(c, k, r, s, x, dy, pixels=dy.shape[0] * dy.shape[2] * dy.shape[3]) if wgrad_16bit_shape(c, k, r, s) else 0
-    f = _C.fn(("rr_conv_wgrad", "rr_conv_wgrad_bf16", "rr_conv_wgrad_f16x3")[bf])
-    wtail = (_C.ptr(amax_of(x)), _C.ptr(amax_of(dy)), _C.stream()) if bf == MATH_F16X3 else (_C.stream(),)
-    _C.check(_timed("conv_wgrad<BN=%d>%s" % (128 if c > 32 else 32, ("", "+bf16", "+f16x3")[bf]), flops,
+    sfx, tag, wtail = _math_call(bf, x, dy)
+    f = _C.fn("rr_conv_wgrad" + sfx)
+    _C.check(_timed("conv_wgrad<BN=%d>%s" % (128 if c > 32 else 32, tag), flops,
                     lambda: f(_C.ptr(x), _C.ptr(dy), _C.ptr(dw), n, h, wd, c, k, r, s, stride, pad[0], pad[1],
                               *((dy.shape[2], dy.shape[3]) if explicit_out else (0, 0)), *wtail), (n, h, wd, c, k, r, s, stride)), "rr_conv_wgrad")
     return dw

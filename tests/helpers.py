@@ -628,9 +628,14 @@ def conv_tap_counts(size, out, r, stride, pad):
     return inside.sum(1), reach, inside.sum(0)
 
 
-# ---- which host route a shape takes: a restatement of the dispatch rules of rrnet_amd/csrc/conv.hip ----
-_BM, _BK = 128, 32                                  # conv.hip:36-37
-_SMALL_TILES, _MID_TILES = 16, 48                   # small_tiles() / mid_tiles(), conv.hip:1088-1090
+# ---- which host route a shape takes: a restatement of the dispatch rules of rrnet_amd/csrc/conv_plan.h, conv.hip ----
+# Written from the host code as it stood BEFORE conv_plan.h existed (the two fprop_impl of conv.hip and conv_bf16.hip), and
+# kept by hand: tests/test_host_logic.py holds the library's plan (rr_conv_fprop_plan) against it field by field.
+_BM, _BK = 128, 32                                  # rr_plan::BM, rr_plan::BK
+_SMALL_TILES, _MID_TILES = 16, 48                   # rr_plan::small_tiles() / mid_tiles()
+MATH_F32, MATH_BF16, MATH_F16X3 = 0, 1, 2           # the arithmetic argument of rr_conv_fprop_plan
+# the fields rr_conv_fprop_plan writes, in its order (include/rrnet_hip.h); after: 0 none, 1 rr_bn_reduce_slab, 2 rr_bn_bwd_reduce, 3 column statistics
+CONV_PLAN_FIELDS = ("rows", "scalar", "bn", "blocks", "ks", "pos_major", "xcd_n", "fused", "after", "zero_dst", "zero_slab")
 
 
 def _cdiv(a, b):
@@ -638,7 +643,7 @@ def _cdiv(a, b):
 
 
 def pick_ksplit_mirror(blocks, nk):
-    """pick_ksplit (conv.hip:1093-1114) in float32 arithmetic, the 0.95 hysteresis included (RR_CONV_SPLITK unset)."""
+    """rr_plan::pick_ksplit in float32 arithmetic, the 0.95 hysteresis included (RR_CONV_SPLITK unset)."""
     f = np.float32
     if blocks >= 256 or nk < 16:
         return 1
@@ -654,13 +659,30 @@ def pick_ksplit_mirror(blocks, nk):
     return best
 
 
-def _fprop_route(n, c, h, w, k, r, s, stride, ph, pw, bias, relu, want_stats):
-    p, q = (h + 2 * ph - r) // stride + 1, (w + 2 * pw - s) // stride + 1
+def _fprop_route(n, c, h, w, k, r, s, stride, ph, pw, bias, relu, want_stats, math=MATH_F32, strided=False, link=None,
+                 accumulate=False, out_hw=None):
+    """rr_plan::fprop_plan restated -> {"labels": set, every name of CONV_PLAN_FIELDS: int}, or None where the arithmetic `math`
+    refuses the call.  link: None | "bn" | "relu_bias" (whose backward sums the launch carries); strided: the destination is one
+    parity class of a larger map, its grid given by out_hw (16-bit kernels only).  Needs h + 2*ph >= r and w + 2*pw >= s (the
+    library divides like C, towards zero)."""
+    b16, two_gib = math != MATH_F32, 1 << 31
+    if b16 and (c % 4 != 0 or r * s > 64):
+        return None                                  # the 16-bit kernels have no scalar gather: refused, not rerouted
+    if strided and not b16:
+        return None
+    p, q = out_hw or ((h + 2 * ph - r) // stride + 1, (w + 2 * pw - s) // stride + 1)
     m = n * p * q
-    if (r == 1 and s == 1 and stride == 1 and ph == 0 and pw == 0 and c in (128, 256) and 48 < k <= 64 and not want_stats
-            and m >= 64 * 1024 and m * c * 4 < (1 << 31)):
-        return {"rows"}
-    scalar = c % 4 != 0 or r * s > 64
+    if p <= 0 or q <= 0 or m >= two_gib:
+        return None
+    if b16 and (n * h * w * c * 4 >= two_gib or k * r * s * c * 4 >= two_gib or m * k * 4 >= two_gib or (strided and (link or want_stats))):
+        return None
+    if not b16 and n * h * w * c >= 1 << 40:
+        return None
+    plan = dict.fromkeys(CONV_PLAN_FIELDS, 0)
+    if (not b16 and r == 1 and s == 1 and stride == 1 and ph == 0 and pw == 0 and c in (128, 256) and 48 < k <= 64 and not want_stats
+            and link is None and not accumulate and m >= 64 * 1024 and m * c * 4 < two_gib):
+        return dict(plan, rows=1, labels={"rows"})
+    scalar = not b16 and (c % 4 != 0 or r * s > 64)
     bn = 128 if k > 64 else ((64 if not scalar else 128) if k > 32 else 32)
     if bn == 128 and not scalar and _cdiv(m, _BM) * _cdiv(k, 128) <= _SMALL_TILES:
         bn = 32
@@ -669,32 +691,45 @@ def _fprop_route(n, c, h, w, k, r, s, stride, ph, pw, bias, relu, want_stats):
     blocks = _cdiv(m, _BM) * _cdiv(k, bn)
     nk = _cdiv(r * s * c, _BK) if scalar else _cdiv(c, _BK) * r * s
     ks = pick_ksplit_mirror(blocks, nk) if (not bias and not relu and k % 4 == 0 and k <= 1024) else 1
+    if link == "relu_bias" or strided:
+        ks = 1
     labels = {"bn%d" % bn}
     if scalar:
         labels.add("scalar")
-    if (not scalar and not want_stats and (ph > 0 or pw > 0) and r * s > 1 and p * q <= 16 and n >= 16 * _BM and bn >= 64
-            and n * h * w * c * 4 < (1 << 31) and k * r * s * c * 4 < (1 << 31)):
+    if b16:
+        nt, mt = _cdiv(k, bn), _cdiv(m, _BM)
+        plan["xcd_n"] = int(nt > 1 and 8 % nt == 0 and mt % (8 // nt) == 0)
+    elif (not scalar and not want_stats and link is None and (ph > 0 or pw > 0) and r * s > 1 and p * q <= 16 and n >= 16 * _BM and bn >= 64
+            and n * h * w * c * 4 < two_gib and k * r * s * c * 4 < two_gib):
         labels.add("pos_major")
-        ks = 1
+        ks, blocks = 1, p * q * _cdiv(n, _BM) * _cdiv(k, bn)
     if ks > 1:
         labels.add("ksplit>1+stats" if want_stats else "ksplit>1")
-    return labels
+    tiles_full = m % _BM == 0 and m * k * 4 < two_gib
+    if link == "relu_bias" and not tiles_full:
+        return None                                  # the masked store has no fallback pass
+    fused = link is not None and ks == 1 and tiles_full
+    colstats = ks > 1 and want_stats and link is None
+    plan.update(scalar=int(scalar), bn=bn, blocks=blocks, ks=ks, pos_major=int("pos_major" in labels), fused=int(fused),
+                after=((1 if fused else 2) if link is not None else (3 if colstats else 0)),
+                zero_dst=int(ks > 1 and not accumulate), zero_slab=int(colstats), labels=labels)
+    return plan
 
 
 def conv_routes(n, c, h, w, k, r, s, stride, pad, bias, relu, want_stats, out_h=0, out_w=0):
     """The host route of each pass of one convolution: {"fprop", "dgrad", "wgrad", "dgrad_via_fprop"} -> set of labels.
-    A pure-Python mirror of the C rules in rrnet_amd/csrc/conv.hip (line numbers of the commit this was written against):
-      fprop  fprop_impl, lines 1189-1259 (rows: 1207-1209, scalar / tile width: 1210-1214, split-K: 1215-1217 with
-             pick_ksplit 1093-1114, pos_major: 1221-1227) and launch_igemm 1146-1171:
+    A pure-Python mirror of the C rules in rrnet_amd/csrc (the fp32 arithmetic):
+      fprop  rr_plan::fprop_plan (conv_plan.h: the rows shortcut, scalar / tile width with small_tiles / mid_tiles, split-K
+             with pick_ksplit, pos_major) and launch_igemm (conv.hip):
              rows | bn128 / bn64 / bn32, scalar, pos_major, ksplit>1 (no statistics) / ksplit>1+stats (zero-fill + colstats_kernel)
-      dgrad  rr_conv_dgrad, lines 1437-1489: bn*, scalar, parity4 (stride 2, all four classes have taps),
-             parity_live<4 (classes without taps get no workgroups), ksplit>1
-      wgrad  rr_conv_wgrad, lines 1491-1538: pipe3 / pipe1 (the pipelined 128x128 kernels), 128x128 / 128x32 / 32x128 /
-             32x32 (the generic tiles), a_scalar (k % 4 != 0), b_scalar (c % 4 != 0), splits>1; out_h / out_w as there
-      dgrad_via_fprop  rr_conv_dgrad_s1 (1351-1360) = the fprop rules on (dy, flipped filter); empty where ops.conv_dgrad
-             cannot take that route (stride > 1, channel counts not multiples of 4, more than 64 taps)."""
+      dgrad  rr_conv_dgrad (conv.hip) with rr_plan::parity_classes: bn*, scalar, parity4 (stride 2, all four classes have
+             taps), parity_live<4 (classes without taps get no workgroups), ksplit>1
+      wgrad  rr_conv_wgrad (conv.hip) with rr_plan::pixel_splits: pipe3 / pipe1 (the pipelined 128x128 kernels), 128x128 /
+             128x32 / 32x128 / 32x32 (the generic tiles), a_scalar (k % 4 != 0), b_scalar (c % 4 != 0), splits>1; out_h / out_w as there
+      dgrad_via_fprop  rr_conv_dgrad_s1 (conv.hip: dgrad_s1, rr_dgrad_s1_geom) = the fprop rules on (dy, flipped filter); empty
+             where ops.conv_dgrad cannot take that route (stride > 1, channel counts not multiples of 4, more than 64 taps)."""
     ph, pw = pad
-    routes = {"fprop": _fprop_route(n, c, h, w, k, r, s, stride, ph, pw, bias, relu, want_stats)}
+    routes = {"fprop": _fprop_route(n, c, h, w, k, r, s, stride, ph, pw, bias, relu, want_stats)["labels"]}
     p, q = (h + 2 * ph - r) // stride + 1, (w + 2 * pw - s) // stride + 1
     # ---- rr_conv_dgrad
     m = n * h * w
@@ -749,7 +784,7 @@ def conv_routes(n, c, h, w, k, r, s, stride, pad, bias, relu, want_stats, out_h=
     routes["wgrad"] = g
     via = set()
     if stride == 1 and k % 4 == 0 and c % 4 == 0 and r * s <= 64 and ph < r and pw < s:
-        via = _fprop_route(n, k, p, q, c, r, s, 1, r - 1 - ph, s - 1 - pw, False, False, False)
+        via = _fprop_route(n, k, p, q, c, r, s, 1, r - 1 - ph, s - 1 - pw, False, False, False)["labels"]
     routes["dgrad_via_fprop"] = via
     return routes
 

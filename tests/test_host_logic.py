@@ -527,6 +527,101 @@ def test_conv_route_mirror_and_grid_coverage():
     assert route(14)["fprop"] == {"bn32"} and CONV64_GRID[14][10:12] == (True, True)
 
 
+def _plan_cases():
+    """-> [(source, (n, c, h, w, k, r, s, stride, ph, pw), dict(bias, relu, want_stats, link, strided, out_hw))]: what
+    test_library_plan_equals_the_mirror asks the library and the mirror about, in every arithmetic."""
+    import numpy as np
+    from conv_route_cases import cases
+    from helpers import CONV64_GRID
+    plain = dict(bias=False, relu=False, want_stats=False, link=None, strided=False, out_hw=None)
+    out = []
+
+    def add(src, geo, **kw):
+        out.append((src, geo, dict(plain, **kw)))
+
+    def via_forward(src, n, c, h, w, k, r, s, stride, ph, pw, link=None):
+        """the forward-kernel launches of the data gradient of this convolution: stride 1 on (dy, flipped filter); stride 2 one
+        per output parity class on its sub-filter, into a strided destination (the rule of ops._s2_parity_pads_ok restated)"""
+        p, q = (h + 2 * ph - r) // stride + 1, (w + 2 * pw - s) // stride + 1
+        if stride == 1 and ph < r and pw < s:
+            add(src + "/via", (n, k, p, q, c, r, s, 1, r - 1 - ph, s - 1 - pw), link=link)
+        if stride == 2:
+            for cl in range(4):
+                (a, b), (r0, s0) = (cl >> 1, cl & 1), (((cl >> 1) + ph) & 1, ((cl & 1) + pw) & 1)
+                rc, sc = ((r - r0 + 1) // 2 if r0 < r else 0), ((s - s0 + 1) // 2 if s0 < s else 0)
+                lead = (rc - 1 - (a + ph - r0) // 2, sc - 1 - (b + pw - s0) // 2)
+                grid = ((h - a + 1) // 2, (w - b + 1) // 2)
+                if rc * sc > 0 and min(lead) >= 0 and min(grid) > 0:
+                    add(src + "/class%d" % cl, (n, k, p, q, c, rc, sc, 1) + lead, strided=True, out_hw=grid)
+
+    for i, (n, c, h, w, k, r, s, st, ph, pw, bias, relu, stats, _) in enumerate(CONV64_GRID):
+        for ws in stats:
+            add("grid%d" % i, (n, c, h, w, k, r, s, st, ph, pw), bias=bias, relu=relu, want_stats=ws)
+        via_forward("grid%d" % i, n, c, h, w, k, r, s, st, ph, pw)
+    for case in cases():
+        (n, c, h, w), k, (r, s), st, (ph, pw) = case["x"], case["k"], case["f"], case["stride"], case["pad"]
+        if h + 2 * ph < r or case["mode"] != "f32" or case.get("accumulate"):
+            continue                                                    # (the record's arithmetics and accumulate repeat the geometry)
+        add(case["id"], (n, c, h, w, k, r, s, st, ph, pw))
+        if case["op"] == "dgrad":
+            link = {"bn_z": "bn", "mask_only": "relu_bias"}.get(case["link"], case["link"])
+            via_forward(case["id"], n, c, h, w, (k + 3) // 4 * 4 if link == "relu_bias" else k, r, s, st, ph, pw, link)
+    # relu_bias is refused unless N*P*Q is a multiple of 128, which random maps seldom are: drawn with 0.2 so that, with the
+    # 4 / 15 of the channel counts the 16-bit kernels refuse, fewer than half of the draws are refused in any arithmetic
+    rng = np.random.default_rng(219)
+    chans = (3, 6, 10, 24, 34, 36, 48, 64, 128, 160, 256, 384, 512, 1024, 2048)
+    for i in range(2400):
+        r, s = ((1, 1), (3, 3), (7, 7), (17, 1))[rng.integers(4)]
+        geo = (int(rng.integers(1, 17)), chans[rng.integers(15)], int(rng.integers(1, 161)), int(rng.integers(1, 161)), chans[rng.integers(15)],
+               r, s, int(rng.integers(1, 4)), int(rng.integers(0, 4)), int(rng.integers(0, 4)))
+        add("random%d" % i, geo, bias=bool(rng.integers(2)), relu=bool(rng.integers(2)), want_stats=bool(rng.integers(2)),
+            link=(None, "bn", "relu_bias")[rng.choice(3, p=(0.6, 0.2, 0.2))])
+    return out
+
+
+def test_library_plan_equals_the_mirror():
+    """rr_conv_fprop_plan — the plan of rrnet_amd/csrc/conv_plan.h that both fprop_impl launch from — equals helpers._fprop_route,
+    the Python restatement of the host code that preceded it, field by field and in each arithmetic: over the grid of
+    tests/test_conv_fp64_gpu.py, the forward-kernel launches of its data gradients, the geometries of tests/conv_route_cases.py
+    and 2400 seeded random geometries; what an arithmetic refuses, the mirror refuses.  Of the random draws at most half are
+    refused per arithmetic, and together the cases reach every route label and every pass around a launch."""
+    import ctypes
+    from helpers import CONV_PLAN_FIELDS, CONV_ROUTE_LABELS, MATH_BF16, MATH_F16X3, MATH_F32, _fprop_route
+    from rrnet_amd import _C
+    plan_fn = _C.fn("rr_conv_fprop_plan")
+    buf = (ctypes.c_int * len(CONV_PLAN_FIELDS))()
+    link_code = {None: 0, "bn": 1, "relu_bias": 2}
+    cases = _plan_cases()
+    n_random = sum(src.startswith("random") for src, _, _ in cases)
+    assert n_random >= 2000
+    for math in (MATH_F32, MATH_BF16, MATH_F16X3):
+        labels, reached, refused, first3 = set(), set(), 0, set()
+        for src, (n, c, h, w, k, r, s, st, ph, pw), f in cases:
+            valid = h + 2 * ph >= r and w + 2 * pw >= s                        # (below that the mirror's floor division is not C's)
+            want = _fprop_route(n, c, h, w, k, r, s, st, ph, pw, f["bias"], f["relu"], f["want_stats"], math, f["strided"], f["link"],
+                                False, f["out_hw"]) if valid else None
+            if want is None:
+                refused += src.startswith("random")
+            if not valid:
+                continue
+            flags = f["bias"] | f["relu"] << 1 | f["want_stats"] << 2 | f["strided"] << 4 | link_code[f["link"]] << 8
+            rc = plan_fn(math, n, h, w, c, k, r, s, st, ph, pw, *(f["out_hw"] or (0, 0)), flags, buf)
+            assert (rc != 0) == (want is None), (src, math, rc, want, _C.lib().rr_last_error())
+            if want is None:
+                continue
+            got = dict(zip(CONV_PLAN_FIELDS, buf))
+            assert got == {name: want[name] for name in CONV_PLAN_FIELDS}, (src, math, got, want)
+            labels |= want["labels"]
+            if src in ("grid0", "grid1", "grid2"):
+                first3 |= want["labels"]
+            reached |= {name for name in ("xcd_n", "fused", "zero_dst", "zero_slab") if got[name]} | {"after%d" % got["after"]}
+        assert refused <= n_random // 2, (math, refused, n_random)
+        sixteen = {"bn128", "bn64", "bn32", "ksplit>1", "ksplit>1+stats"}
+        assert labels == (CONV_ROUTE_LABELS["fprop"] if math == MATH_F32 else sixteen), (math, sorted(labels))
+        assert first3 >= sixteen, (math, sorted(first3))
+        assert reached == {"fused", "zero_dst", "zero_slab", "after0", "after1", "after2", "after3"} | ({"xcd_n"} if math else set()), (math, sorted(reached))
+
+
 # ---- the data-gradient selector (ops.dgrad_route) against the recorded launches (tests/golden/conv_bwd_routes.json) -----------
 def test_dgrad_route_names_the_kernel_each_recorded_call_launched(golden_dir):
     """For every conv_dgrad case of tests/conv_route_cases.py, ops.dgrad_route — asked with shapes and the link's facts only, the
