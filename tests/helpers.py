@@ -838,6 +838,234 @@ def conv_grid_routes():
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# The bf16 and f16x3 convolutions of csrc/conv_bf16.hip against float64 (tests/test_conv_lowp_fp64_gpu.py; the promises made
+# here are checked by tests/test_host_logic.py).  The contract defines each operand's IMAGE — bf16: the value rounded to nearest
+# even; f16x3: hi + lo, two fp16 values after the power-of-two scale of the tensor's maximum (oracle/split.py) — and which products
+# of image parts a term consists of.  The reference multiplies those images in float64; the yardstick chains the same products (all
+# exact in float32) in float32.  Only fp32 accumulation separates a correct kernel from that reference, so conv_accepts is unchanged.
+# ------------------------------------------------------------------------------------------------------------------
+CONV16_MARGIN = 2            # by the rule of CONV_MARGIN: the largest ratio of profiles/conv_lowp_fp64_ratios.txt (an MI355X run of
+                             # tests/test_conv_lowp_fp64_gpu.py) is 1.32 — bf16, weight gradient under the dynamic-range input; f16x3 stays
+                             # below 0.35 — rounded up to a power of two, not below 2
+LOWP_PAIRS = {MATH_BF16: ((0, 0),), MATH_F16X3: ((0, 0), (0, 1), (1, 0))}     # (part of the first operand, part of the second) per term
+LOWP_NAMES = {MATH_BF16: "bf16", MATH_F16X3: "f16x3"}
+
+
+def _np32(t):
+    return t.detach().cpu().float().numpy() if torch.is_tensor(t) else np.asarray(t, np.float32)
+
+
+def lowp_image(math, t, bits=None):
+    """The image of operand t (float32 tensor / array) under arithmetic `math` -> (parts: tuple of float64 arrays, scale float64);
+    t is modelled as sum(parts) / scale.  bf16: one part, scale 1.  f16x3: (hi, lo) of oracle.split.split under the scale of
+    oracle.split.scale_of(bits), bits = the bit pattern of max|t| unless given (the word the entry point is handed)."""
+    a = _np32(t)
+    if math == MATH_BF16:
+        return (bf16_exact(a).astype(np.float64),), np.float64(1.0)
+    from oracle import split as osp
+    sc = osp.scale_of(osp.absmax_bits(a) if bits is None else bits)
+    hi, lo = osp.split(a, sc)
+    return (hi.astype(np.float64), lo.astype(np.float64)), np.float64(sc)
+
+
+def _t64(a):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64))
+
+
+def lowp_fprop_ref64(math, xi, wi, bias, stride, pad, relu):
+    """y float64 from the images xi, wi (lowp_image): the terms of LOWP_PAIRS, each conv_ref64, over the two scales; + bias, ReLU.
+    f16x3: exactly oracle.split.conv2d."""
+    (xp, sx), (wp, sw) = xi, wi
+    y = None
+    for i, j in LOWP_PAIRS[math]:
+        t = conv_ref64(_t64(xp[i]), _t64(wp[j]), None, stride, pad, False)[0]
+        y = t if y is None else y + t
+    y = y / (sx * sw)
+    if bias is not None:
+        y = y + torch.as_tensor(bias).detach().cpu().double().view(1, -1, 1, 1)
+    return torch.relu(y) if relu else y
+
+
+def lowp_grads_ref64(math, xi, wi, gi, stride, pad, far=(0, 0), pairs=None):
+    """(dx, dw) float64 from the images of x, w and gy: dx = sum over LOWP_PAIRS of dgrad(gy part, w part) / (s_gy s_w),
+    dw = sum of wgrad(x part, gy part) / (s_x s_gy), each through conv_ref64's autograd.  far: rows / columns of zero padding
+    added to x at the far edge (the weight gradient's out_h / out_w override)."""
+    import torch.nn.functional as F
+    (xp, sx), (wp, sw), (gp, sg) = xi, wi, gi
+    if pairs is None:                                      # one backward serves dgrad(gy_g, w_b) and wgrad(x_a, gy_g)
+        pairs, calls = LOWP_PAIRS[math], ([(0, 0, 0)] if math == MATH_BF16 else [(0, 0, 0), (1, 1, 0), (0, 0, 1)])
+    else:
+        calls = [(a, b, g) for a in range(len(xp)) for b in range(len(wp)) for g in range(len(gp))]
+    dx = dw = 0.0
+    done_dx, done_dw = set(), set()
+    for a, b, g in calls:
+        if ((g, b) not in pairs or (g, b) in done_dx) and ((a, g) not in pairs or (a, g) in done_dw):
+            continue
+        x64 = _t64(xp[a])
+        if far != (0, 0):
+            x64 = F.pad(x64, (0, far[1], 0, far[0]))
+        _, tdx, tdw = conv_ref64(x64, _t64(wp[b]), None, stride, pad, False, _t64(gp[g]))
+        if (g, b) in pairs and (g, b) not in done_dx:
+            dx, _ = dx + tdx, done_dx.add((g, b))
+        if (a, g) in pairs and (a, g) not in done_dw:
+            dw, _ = dw + tdw, done_dw.add((a, g))
+    assert done_dx == set(pairs) and done_dw == set(pairs)
+    if far != (0, 0):
+        dx = dx[:, :, :dx.shape[2] - far[0], :dx.shape[3] - far[1]]
+    return dx / (sg * sw), dw / (sx * sg)
+
+
+def lowp_terms(math, kind, idx, first, second, stride, pad, rs=None, bias=None, base=None, pairs=None):
+    """conv_terms over the image products: the chunks hold, side by side, the products of every pair of LOWP_PAIRS (a term of f16x3
+    is three separate products), over the two scales; bias / base appear once.  first, second: the images in the order of the
+    products — fprop (x, w), dgrad (gy, w), wgrad (x, gy; rs = (R, S))."""
+    (ap, sa), (bp, sb) = first, second
+    div = sa * sb
+    gens = []
+    for n_, (i, j) in enumerate(LOWP_PAIRS[math] if pairs is None else pairs):
+        extra = {}
+        if n_ == 0 and bias is not None:
+            extra["bias"] = _np64(bias) * div
+        if n_ == 0 and base is not None:
+            extra["base"] = _np64(base) * div
+        if kind == "fprop":
+            gens.append(conv_terms(kind, idx, ap[i], bp[j], None, stride, pad, **extra))
+        elif kind == "dgrad":
+            gens.append(conv_terms(kind, idx, None, bp[j], ap[i], stride, pad, **extra))
+        else:
+            gens.append(conv_terms(kind, idx, ap[i], tuple(rs), bp[j], stride, pad, **extra))
+    for chunks in zip(*gens):
+        yield np.concatenate(chunks, 1) / div
+
+
+def _parity_launches(h, w, r, s, ph, pw):
+    """rr_plan::parity_classes restated -> ([(class, Rc, Sc, lead_h, lead_w, Hc, Wc)] of the classes that launch, any_empty)."""
+    out, any_empty = [], False
+    for cl in range(4):
+        a, b = cl >> 1, cl & 1
+        r0, s0 = (a + ph) & 1, (b + pw) & 1
+        rc, sc = ((r - r0 + 1) // 2 if r0 < r else 0), ((s - s0 + 1) // 2 if s0 < s else 0)
+        hc, wc = (h - a + 1) // 2, (w - b + 1) // 2
+        if hc > 0 and wc > 0 and rc * sc == 0:
+            any_empty = True
+        if rc * sc > 0 and hc > 0 and wc > 0:
+            out.append((cl, rc, sc, rc - 1 - (a + ph - r0) // 2, sc - 1 - (b + pw - s0) // 2, hc, wc))
+    return out, any_empty
+
+
+def conv16_fprop_labels(math, n, c, h, w, k, r, s, stride, ph, pw, bias, relu, want_stats):
+    """(labels, plan) of one rr_conv_fprop_bf16 / _f16x3 call: _fprop_route's, and what the kernel does differently at this shape."""
+    plan = _fprop_route(n, c, h, w, k, r, s, stride, ph, pw, bias, relu, want_stats, math)
+    lab, bn = set(plan["labels"]), plan["bn"]
+    p, q = (h + 2 * ph - r) // stride + 1, (w + 2 * pw - s) // stride + 1
+    lab.add("xcd_n" if plan["xcd_n"] else ("xcd_off,tiles>1" if _cdiv(k, bn) > 1 else "one column tile"))
+    lab |= {name for name, on in (("ragged M", n * p * q % _BM), ("ragged filter tile", k % bn), ("partial K-step", c % _BK),
+                                  ("C%8: image refused", c % 8), ("bias+relu", bias and relu), ("stride 2", stride == 2),
+                                  ("fused stats", want_stats and plan["ks"] == 1)) if on}
+    if c % 8 == 0 and (math == MATH_BF16 or bn == 128):
+        lab.add("image@bn%d" % bn)                   # the ready-made filter image (bf16 w_bf16 / f16x3 w_split) is read
+    return lab, plan
+
+
+def conv16_dgrad_labels(math, n, c, h, w, k, r, s, stride, ph, pw, link=None):
+    """Labels of the data gradient of this convolution on the 16-bit kernels: stride 1 one forward launch on (dy, flipped filter)
+    ("s1 ..."), stride 2 one strided launch per live parity class ("s2 ...")."""
+    p, q = (h + 2 * ph - r) // stride + 1, (w + 2 * pw - s) // stride + 1
+    if stride == 1:
+        plan = _fprop_route(n, k, p, q, c, r, s, 1, r - 1 - ph, s - 1 - pw, False, False, False, math, link=link)
+        if link is None:
+            return {"s1 " + name for name in plan["labels"]}
+        how = "fused" if plan["fused"] else "reduce pass"
+        return {"link %s bn%d %s" % (link, plan["bn"], how)}
+    launches, any_empty = _parity_launches(h, w, r, s, ph, pw)
+    lab = {"s2 any_empty"} if any_empty else set()
+    for _, rc, sc, lh, lw, hc, wc in launches:
+        plan = _fprop_route(n, k, p, q, c, rc, sc, 1, lh, lw, False, False, False, math, strided=True, out_hw=(hc, wc))
+        lab.add("s2 bn%d" % plan["bn"])
+    return lab
+
+
+def conv16_wgrad_labels(math, n, c, h, w, k, r, s, stride, ph, pw, out_hw=None):
+    """wgrad_impl of csrc/conv_bf16.hip restated (rr_plan::pixel_splits over 1024 workgroup slots, 512 for the split kernel,
+    never fewer than 16 K-steps per split) -> labels."""
+    p, q = out_hw or ((h + 2 * ph - r) // stride + 1, (w + 2 * pw - s) // stride + 1)
+    m = n * p * q
+    tiles, chunks, slots = _cdiv(k, 128) * _cdiv(c, 128) * r * s, _cdiv(m, _BK), (512 if math == MATH_F16X3 else 1024)
+    splits = max(1, min(slots // tiles if tiles < slots else 1, _cdiv(chunks, 16)))
+    splits = _cdiv(chunks, _cdiv(chunks, splits))
+    lab = {"splits>1" if splits > 1 else "one split"}
+    lab |= {name for name, on in (("ragged K tile", k % 128), ("ragged C tile", c % 128), ("M%32", m % _BK), ("stride 2", stride == 2),
+                                  ("out override", out_hw is not None)) if on}
+    return {"wgrad " + name for name in lab}
+
+
+# (N, C, H, W, K, R, S, stride, pad_h, pad_w, bias, relu, want_stats values, passes) as CONV64_GRID; every case at the smallest
+# size that still takes its route (test_conv16_grid_reaches_every_route names the route of each from the mirror)
+CONV16_GRID = [
+    (1, 128, 16, 16, 128, 3, 3, 1, 1, 1, False, False, (False, True), "fdw"),    # bn32, split-K 4, xcd_n; statistics in the colstats pass
+    (1, 64, 9, 13, 128, 3, 3, 1, 1, 1, False, False, (False, True), "fdw"),      # bn32, ragged M, split-K 2, xcd_n off on 4 column tiles
+    (1, 64, 24, 24, 64, 3, 3, 1, 1, 1, False, False, (False, True), "fdw"),      # bn64, split-K 2
+    (1, 128, 32, 32, 384, 3, 3, 1, 1, 1, False, False, (False, True), "fdw"),    # bn64 by the mid-tile rule, 6 column tiles, split-K 4
+    (1, 64, 64, 64, 256, 3, 3, 1, 1, 1, False, False, (False, True), "fdw"),     # bn128, xcd_n, split-K 2; the f16x3 filter image
+    (1, 32, 80, 80, 132, 3, 3, 1, 1, 1, False, False, (False, True), "fdw"),     # bn128, ragged filter tile, no split: fused statistics
+    (2, 48, 8, 8, 24, 3, 3, 1, 1, 1, False, False, (False, True), "fdw"),        # partial K-step, C % 8 == 0
+    (1, 44, 12, 12, 40, 3, 3, 1, 1, 1, False, False, (False, True), "fdw"),      # partial K-step, C % 8 != 0: the filter image is refused
+    (1, 256, 20, 12, 1, 17, 1, 1, 8, 0, True, False, (False, True), "f"),        # HCov with bias: bn32, one live column (K % 4 != 0: forward only)
+    (1, 256, 10, 10, 256, 3, 3, 1, 1, 1, True, True, (False, True), "fdw"),      # bias + ReLU keep split-K off
+    (2, 64, 15, 17, 128, 3, 3, 2, 1, 1, False, False, (False, True), "fdw"),     # stride-2 forward on an odd map; dgrad bn64 strided
+    (1, 160, 64, 64, 32, 3, 3, 1, 1, 1, False, False, (), "d"),                  # stride-1 dgrad at bn128 without split-K: the accumulate epilogue
+    (2, 256, 79, 81, 16, 3, 3, 2, 1, 1, False, False, (), "dw"),                # stride-2 dgrad: four classes of different sizes, bn128 strided
+    (2, 64, 15, 17, 32, 3, 3, 2, 1, 1, False, False, (), "d"),                   # ... bn64 strided
+    (1, 32, 9, 7, 16, 3, 3, 2, 1, 1, False, False, (), "dw"),                    # ... bn32 strided
+    (2, 128, 15, 17, 64, 1, 1, 2, 0, 0, False, False, (), "d"),                  # ... 1x1: three empty classes (memset; accumulate must not clear dx)
+    (1, 64, 12, 12, 64, 3, 3, 2, 0, 0, False, False, (), "d"),                   # ... no padding
+]
+CONV16_ASYM_WGRAD = (1, 64, 12, 12, 64, 3, 3, 1, 1, 1, 13, 13)                    # the out_h / out_w override, as CONV64_ASYM_WGRAD
+# stride-1 data gradients that carry their producer's backward sums: (dx shape (n, c, h, w), k of dy, link, mask source) at 3x3 pad 1.
+# mask source of a "bn" link: "affine" (y * scale + shift > 0, recomputed), "z" (the producer's output), None (no ReLU)
+CONV16_LINKS = [
+    ((2, 64, 16, 16), 32, "bn", "affine"),          # LINK_BN fused at bn64
+    ((2, 256, 16, 16), 32, "bn", "z"),              # LINK_BN fused at bn32
+    ((2, 64, 16, 16), 64, "relu_bias", "z"),        # LINK_RELU_BIAS at bn64 (the plan keeps split-K off)
+    ((1, 32, 16, 16), 64, "relu_bias", "z"),        # LINK_RELU_BIAS at bn32
+    ((2, 64, 16, 16), 64, "bn", None),              # split-K: not fused, the sums come from the reduce pass behind the launch
+]
+_COMMON16 = {"bn128", "bn64", "bn32", "ksplit>1", "ksplit>1+stats", "xcd_n", "xcd_off,tiles>1", "ragged M", "ragged filter tile",
+             "partial K-step", "C%8: image refused", "image@bn128", "bias+relu", "stride 2", "fused stats",
+             "s1 bn128", "s1 bn64", "s1 bn32", "s1 ksplit>1", "s2 bn128", "s2 bn64", "s2 bn32", "s2 any_empty",
+             "link bn bn64 fused", "link bn bn32 fused", "link relu_bias bn64 fused", "link relu_bias bn32 fused", "link bn bn64 reduce pass",
+             "wgrad splits>1", "wgrad one split", "wgrad ragged K tile", "wgrad ragged C tile", "wgrad M%32", "wgrad stride 2",
+             "wgrad out override"}
+CONV16_ROUTE_LABELS = {MATH_BF16: _COMMON16 | {"image@bn64", "image@bn32"}, MATH_F16X3: set(_COMMON16)}
+
+
+def conv16_case_labels(math, cfg, want_stats=False):
+    """{"fprop" | "dgrad" | "wgrad": labels} of the passes one CONV16_GRID case runs."""
+    geo, (bias, relu, _, passes) = cfg[:10], cfg[10:]
+    out = {}
+    if "f" in passes:
+        out["fprop"] = conv16_fprop_labels(math, *geo, bias, relu, want_stats)[0]
+    if "d" in passes:
+        out["dgrad"] = conv16_dgrad_labels(math, *geo)
+    if "w" in passes:
+        out["wgrad"] = conv16_wgrad_labels(math, *geo)
+    return out
+
+
+def conv16_grid_labels(math):
+    """Every label CONV16_GRID, CONV16_LINKS and CONV16_ASYM_WGRAD reach under arithmetic `math`."""
+    seen = set()
+    for cfg in CONV16_GRID:
+        for ws in cfg[12] or (False,):
+            for lab in conv16_case_labels(math, cfg, ws).values():
+                seen |= lab
+    for (n, c, h, w), k, link, _ in CONV16_LINKS:
+        seen |= conv16_dgrad_labels(math, n, c, h, w, k, 3, 3, 1, 1, 1, link=link)
+    seen |= conv16_wgrad_labels(math, *CONV16_ASYM_WGRAD[:10], out_hw=CONV16_ASYM_WGRAD[10:])
+    return seen
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # BatchNorm forward / ReLU-mask agreement (tests/test_bn_forward_gpu.py; tests/test_bn_mask_host.py checks the builder).
 # ------------------------------------------------------------------------------------------------------------------
 def bf16_exact(a):

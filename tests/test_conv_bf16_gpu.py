@@ -9,7 +9,15 @@ contract is stated against our own fp32 kernels: a bf16 entry point rounds both 
 (a product of two bf16 values is exact in fp32).  Bound: 2e-5 of the output scale (max |ref|) — fp32 re-association over
 <= 4608 terms (fprop / dgrad) or <= 16 k pixels per split (wgrad); it is NOT a bf16-sized bound: an operand that was
 left unrounded, or rounded twice, or a dropped K-step shows up at >= 1e-3.  The fp32 kernels themselves are pinned
-against torch / the reference goldens in tests/test_conv_gpu.py and tests/test_model_gpu.py."""
+against torch / the reference goldens in tests/test_conv_gpu.py and tests/test_model_gpu.py.
+
+Which kernels run: under the default RR_CONV16=1, rrnet_amd.ops sends a launch of 8192 or more output pixels whose channel
+counts csrc/conv16.hip supports (ops.conv16_ok / dgrad_route / wgrad16_takes) to THAT file, not to the one this file is
+named after.  Of SHAPES that is n2c256h64w64k256, n1c256h96w96k256 (bias + ReLU) and n2c128h128w128k256 stride 2 — the
+forward pass and the data gradient, and the weight gradient where rr_conv16_wgrad_supported says so; conv16.hip has its
+own float64 test in tests/test_conv16_gpu.py.  The other sixteen shapes run csrc/conv_bf16.hip on the route ops picks.
+HIP against HIP either way: tests/test_conv_lowp_fp64_gpu.py pins csrc/conv_bf16.hip to float64 directly, on every route of
+the launch plan and in both of its arithmetics."""
 import numpy as np
 import pytest
 import torch

@@ -43,22 +43,28 @@ def math_switch():
 
 @pytest.mark.parametrize("cfg", SHAPES, ids=lambda c: "n%dc%dh%dw%dk%dr%ds%d_s%d" % c[:8])
 def test_split_kernels_equal_fp32_kernels(cfg, math_switch):
+    """ops' layer policy (_SPLIT_MIN_PIXELS / _SPLIT_MIN_K / _SPLIT_MIN_CH) keeps all but the four largest of SHAPES on the fp32
+    kernels, which would compare csrc/conv.hip with itself: the thresholds are zeroed here, and the arithmetic that will run is
+    asserted — f16x3 for every shape the split kernels take at all (C and K multiples of 4, at most 64 taps)."""
     from rrnet_amd import ops
     n, c, h, w, k, r, s, stride, ph, pw, use_bias, relu = cfg
     x = ops.to_nhwc(_mk((n, c, h, w), 1).cuda())
     wt = ops.to_nhwc((_mk((k, c, r, s), 2) * (1.0 / np.sqrt(c * r * s))).cuda())
     b = _mk((k,), 3).cuda() if use_bias else None
-    math_switch(ops.MATH_F16X3)
-    y, slab = ops.conv_fprop(x, wt, b, stride, (ph, pw), relu, want_stats=True)
-    math_switch(ops.MATH_F32)
-    y_ref, slab_ref = ops.conv_fprop(x, wt, b, stride, (ph, pw), relu, want_stats=True)
-    _close(y, y_ref, "fprop")
-    _close(slab.view(-1, 2, k).sum(0), slab_ref.view(-1, 2, k).sum(0), "fprop statistics", 2e-5)
-    p, q = y.shape[2], y.shape[3]
-    gy = ops.to_nhwc((_mk((n, k, p, q), 4) * 1e-4).cuda())          # gradient-sized values: the scale does the work
-    saved = ops._DGRAD_VIA_FPROP_MIN_PIXELS
-    ops._DGRAD_VIA_FPROP_MIN_PIXELS = 0
+    takes = ops.MATH_F16X3 if (c % 4 == 0 and k % 4 == 0 and r * s <= 64) else ops.MATH_F32
+    p, q = ops.out_hw(h, w, r, s, stride, ph, pw)
+    saved = (ops._SPLIT_PRESPLIT_PIXELS, ops._SPLIT_MIN_PIXELS, ops._SPLIT_MIN_K, ops._SPLIT_MIN_CH, ops._DGRAD_VIA_FPROP_MIN_PIXELS)
+    ops._SPLIT_PRESPLIT_PIXELS = ops._SPLIT_MIN_PIXELS = ops._SPLIT_MIN_K = ops._SPLIT_MIN_CH = ops._DGRAD_VIA_FPROP_MIN_PIXELS = 0
     try:
+        math_switch(ops.MATH_F16X3)
+        assert ops._bf16_ok(c, k, r, s, pixels=n * p * q) == takes                                   # forward pass, weight gradient
+        assert ops.dgrad_route((n, k, p, q), (k, c, r, s), (n, c, h, w), stride, (ph, pw))[1] == takes
+        y, slab = ops.conv_fprop(x, wt, b, stride, (ph, pw), relu, want_stats=True)
+        math_switch(ops.MATH_F32)
+        y_ref, slab_ref = ops.conv_fprop(x, wt, b, stride, (ph, pw), relu, want_stats=True)
+        _close(y, y_ref, "fprop")
+        _close(slab.view(-1, 2, k).sum(0), slab_ref.view(-1, 2, k).sum(0), "fprop statistics", 2e-5)
+        gy = ops.to_nhwc((_mk((n, k, p, q), 4) * 1e-4).cuda())          # gradient-sized values: the scale does the work
         if k % 4 == 0:
             math_switch(ops.MATH_F16X3)
             dx = ops.conv_dgrad(gy, wt, (n, c, h, w), stride, (ph, pw))
@@ -69,16 +75,17 @@ def test_split_kernels_equal_fp32_kernels(cfg, math_switch):
             dx_ref = ops.conv_dgrad(gy, wt, (n, c, h, w), stride, (ph, pw))
             _close(dx, dx_ref, "dgrad")
             _close(acc, dx_ref + base, "dgrad (accumulate)")
+        if c > 32 and k > 32 and k % 4 == 0:
+            dw = torch.zeros((k, r, s, c), device="cuda").permute(0, 3, 1, 2)
+            dw_ref = torch.zeros((k, r, s, c), device="cuda").permute(0, 3, 1, 2)
+            math_switch(ops.MATH_F16X3)
+            assert ops.wgrad_16bit_shape(c, k, r, s)
+            ops.conv_wgrad(x, gy, dw, stride, (ph, pw))
+            math_switch(ops.MATH_F32)
+            ops.conv_wgrad(x, gy, dw_ref, stride, (ph, pw))
+            _close(dw, dw_ref, "wgrad", 1e-5)          # (pixel-split partial sums meet in float atomics on both sides)
     finally:
-        ops._DGRAD_VIA_FPROP_MIN_PIXELS = saved
-    if c > 32 and k > 32 and k % 4 == 0:
-        dw = torch.zeros((k, r, s, c), device="cuda").permute(0, 3, 1, 2)
-        dw_ref = torch.zeros((k, r, s, c), device="cuda").permute(0, 3, 1, 2)
-        math_switch(ops.MATH_F16X3)
-        ops.conv_wgrad(x, gy, dw, stride, (ph, pw))
-        math_switch(ops.MATH_F32)
-        ops.conv_wgrad(x, gy, dw_ref, stride, (ph, pw))
-        _close(dw, dw_ref, "wgrad", 1e-5)          # (pixel-split partial sums meet in float atomics on both sides)
+        ops._SPLIT_PRESPLIT_PIXELS, ops._SPLIT_MIN_PIXELS, ops._SPLIT_MIN_K, ops._SPLIT_MIN_CH, ops._DGRAD_VIA_FPROP_MIN_PIXELS = saved
 
 
 def _fp64_conv(x, w, pad):

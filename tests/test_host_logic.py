@@ -654,3 +654,176 @@ def test_dgrad_route_names_the_kernel_each_recorded_call_launched(golden_dir):
         assert takes == (want[0] in ("conv16_s1", "conv16_s2")), case["id"]
         seen.add(want[0])
     assert seen == {"relumask", "head", "relubias", "conv16_s1", "fprop_bnsum", "fprop", "conv16_s2", "parity_s2", "dgrad"}
+
+
+# ---- the bf16 / f16x3 convolution checks (tests/test_conv_lowp_fp64_gpu.py): routes, references, acceptance rule ------------------
+def test_conv16_grid_reaches_every_route():
+    """helpers.CONV16_GRID, CONV16_LINKS and CONV16_ASYM_WGRAD reach every label of helpers.CONV16_ROUTE_LABELS in both 16-bit
+    arithmetics.  The labels come from helpers._fprop_route, and for every forward-kernel launch of the grid — forward pass,
+    stride-1 data gradient with and without a link, each parity class of a stride-2 one — the library's own plan
+    (rr_conv_fprop_plan) equals that mirror field by field; the combinations the grid was laid out for are there."""
+    import ctypes
+    from helpers import (CONV16_GRID, CONV16_LINKS, CONV16_ROUTE_LABELS, CONV_PLAN_FIELDS, MATH_BF16, MATH_F16X3, _fprop_route, _parity_launches,
+                         conv16_case_labels, conv16_grid_labels)
+    from rrnet_amd import _C
+    plan_fn = _C.fn("rr_conv_fprop_plan")
+    buf = (ctypes.c_int * len(CONV_PLAN_FIELDS))()
+    link_code = {None: 0, "bn": 1, "relu_bias": 2}
+
+    def same_plan(math, geo, bias=False, relu=False, ws=False, strided=False, link=None, out_hw=None):
+        n, c, h, w, k, r, s, st, ph, pw = geo
+        want = _fprop_route(n, c, h, w, k, r, s, st, ph, pw, bias, relu, ws, math, strided, link, False, out_hw)
+        flags = bias | relu << 1 | ws << 2 | strided << 4 | link_code[link] << 8
+        assert plan_fn(math, n, h, w, c, k, r, s, st, ph, pw, *(out_hw or (0, 0)), flags, buf) == 0 and want is not None, (math, geo)
+        assert dict(zip(CONV_PLAN_FIELDS, buf)) == {name: want[name] for name in CONV_PLAN_FIELDS}, (math, geo, list(buf), want)
+        return want
+    for math in (MATH_BF16, MATH_F16X3):
+        seen = conv16_grid_labels(math)
+        missing = sorted(CONV16_ROUTE_LABELS[math] - seen)
+        assert not missing, "math %d: route labels no case reaches: %s" % (math, missing)
+        combos = []
+        for cfg in CONV16_GRID:
+            n, c, h, w, k, r, s, st, ph, pw, bias, relu, stats, passes = cfg
+            p, q = (h + 2 * ph - r) // st + 1, (w + 2 * pw - s) // st + 1
+            for ws in stats:
+                same_plan(math, cfg[:10], bias, relu, ws)
+                combos.append(conv16_case_labels(math, cfg, ws)["fprop"])
+            if "d" in passes and st == 1:
+                same_plan(math, (n, k, p, q, c, r, s, 1, r - 1 - ph, s - 1 - pw))
+            if "d" in passes and st == 2:
+                sizes = set()
+                for _, rc, sc, lh, lw, hc, wc in _parity_launches(h, w, r, s, ph, pw)[0]:
+                    pl = same_plan(math, (n, k, p, q, c, rc, sc, 1, lh, lw), strided=True, out_hw=(hc, wc))
+                    assert pl["ks"] == 1 and not pl["zero_dst"]
+                    sizes.add((hc, wc))
+                if (n, c, h, w, k) == (2, 256, 79, 81, 16):
+                    assert len(sizes) == 4                                   # four classes of four different sizes
+        for (n, c, h, w), k, link, _ in CONV16_LINKS:
+            pl = same_plan(math, (n, k, h, w, c, 3, 3, 1, 1, 1), link=link)
+            assert n * h * w % 128 == 0 and (pl["after"] == 2) == (pl["ks"] > 1)
+        for want in ({"bn32", "ksplit>1+stats", "xcd_n"}, {"bn32", "ragged M", "xcd_off,tiles>1"}, {"bn64", "xcd_off,tiles>1", "ksplit>1"},
+                     {"bn128", "xcd_n", "ksplit>1+stats"}, {"bn128", "ragged filter tile", "fused stats"}, {"partial K-step", "C%8: image refused"},
+                     {"bn32", "bias+relu", "fused stats"}, {"stride 2", "ragged M"}):
+            assert any(want <= cmb for cmb in combos), (math, want)
+        # bias / ReLU keep split-K off on a shape that would otherwise split
+        assert not any("bias+relu" in cmb and ("ksplit>1" in cmb or "ksplit>1+stats" in cmb) for cmb in combos)
+        assert _fprop_route(1, 256, 10, 10, 256, 3, 3, 1, 1, 1, False, False, False, math)["ks"] > 1
+
+
+def test_lowp_references_are_what_they_claim():
+    """helpers.lowp_image / lowp_fprop_ref64 / lowp_grads_ref64 / lowp_terms on one small strided shape with bias and one stride-1
+    shape: the f16x3 forward reference IS oracle.split.conv2d; the f16x3 gradient references equal conv_ref64 on hi + lo up to the
+    dropped lo*lo term, bounded by the same convolution of |lo| with |lo|; the bf16 references equal conv_ref64 on operands
+    rounded by torch; the gathered products add up to the references; the scale follows the word it is given."""
+    import numpy as np
+    import torch
+    from oracle import split as osp
+    from helpers import (LOWP_PAIRS, MATH_BF16, MATH_F16X3, conv_ref64, lowp_fprop_ref64, lowp_grads_ref64, lowp_image, lowp_terms)
+    for n, c, h, w, k, r, s, st, ph, pw in ((2, 8, 7, 9, 12, 3, 3, 2, 1, 1), (1, 12, 6, 5, 8, 3, 2, 1, 1, 0)):
+        rng = np.random.default_rng(h)
+        p, q = (h + 2 * ph - r) // st + 1, (w + 2 * pw - s) // st + 1
+        x = torch.from_numpy((rng.standard_normal((n, c, h, w)) * 3e-3).astype(np.float32))
+        wt = torch.from_numpy((rng.standard_normal((k, c, r, s)) * 0.05).astype(np.float32))
+        gy = torch.from_numpy((rng.standard_normal((n, k, p, q)) * 40.0).astype(np.float32))
+        b = torch.from_numpy(rng.standard_normal(k).astype(np.float32) * 1e-4)
+        base = rng.standard_normal((k, c, r, s)) * 1e-2
+        for math in (MATH_BF16, MATH_F16X3):
+            xi, wi, gi = (lowp_image(math, t) for t in (x, wt, gy))
+            y = lowp_fprop_ref64(math, xi, wi, b, st, (ph, pw), False)
+            dx, dw = lowp_grads_ref64(math, xi, wi, gi, st, (ph, pw))
+            if math == MATH_BF16:
+                rd = lambda t: t.to(torch.bfloat16).float()
+                y0, dx0, dw0 = conv_ref64(rd(x), rd(wt), b, st, (ph, pw), False, rd(gy))
+                for got, ref in ((y, y0), (dx, dx0), (dw, dw0)):
+                    assert float((got - ref).abs().max()) <= 1e-14 * float(ref.abs().max())
+            else:
+                y0 = osp.conv2d(x.numpy(), wt.numpy(), st, (ph, pw)) + b.double().numpy()[None, :, None, None]
+                assert np.abs(y.numpy() - y0).max() <= 1e-14 * np.abs(y0).max()
+                for (parts, sc), t in ((xi, x), (wi, wt), (gi, gy)):
+                    assert float(sc) == float(osp.scale_of(osp.absmax_bits(t.numpy()))) and 2.0 ** 14 <= np.abs(parts[0]).max() <= 2.0 ** 15
+                    assert np.abs((parts[0] + parts[1]) / sc - t.double().numpy()).max() <= 2.0 ** -21 * float(t.abs().max())
+                full = lambda im: torch.from_numpy((im[0][0] + im[0][1]) / im[1])
+                lo = lambda im: torch.from_numpy(np.abs(im[0][1]) / im[1])
+                _, dx1, dw1 = conv_ref64(full(xi), full(wi), None, st, (ph, pw), False, full(gi))
+                _, bx, bw = conv_ref64(lo(xi), lo(wi), None, st, (ph, pw), False, lo(gi))          # sum |lo| |lo|: the dropped term at most
+                assert bool(((dx - dx1).abs() <= bx * (1 + 1e-9) + 1e-14 * dx1.abs().max()).all()) and 0 < float(bx.max()) < 1e-5 * float(dx1.abs().max())
+                assert bool(((dw - dw1).abs() <= bw * (1 + 1e-9) + 1e-14 * dw1.abs().max()).all()) and 0 < float(bw.max()) < 1e-5 * float(dw1.abs().max())
+                # ... and the dropped term is exactly what is missing
+                ddx, ddw = lowp_grads_ref64(math, xi, wi, gi, st, (ph, pw), pairs=((1, 1),))
+                assert float((dx + ddx - dx1).abs().max()) <= 1e-14 * float(dx1.abs().max())
+                assert float((dw + ddw - dw1).abs().max()) <= 1e-14 * float(dw1.abs().max())
+                # the scale is the given word's: a tensor whose maximum is infinite keeps no finite value
+                parts, sc = lowp_image(math, x, bits=0x7f800000)
+                assert float(sc) == 2.0 ** -114 and not parts[0].any() and not parts[1].any()
+            for kind, ref, a, bb, kw in (("fprop", y, xi, wi, dict(bias=b)), ("dgrad", dx, gi, wi, {}), ("wgrad", dw + torch.from_numpy(base), xi, gi, dict(rs=(r, s), base=base))):
+                idx = np.unravel_index(np.arange(ref.numel()), tuple(ref.shape))
+                chunks = list(lowp_terms(math, kind, idx, a, bb, st, (ph, pw), **kw))
+                per = {"fprop": c * r * s, "dgrad": k * r * s, "wgrad": n * p * q}[kind] + 1
+                assert all(t.shape[1] == per * len(LOWP_PAIRS[math]) for t in chunks)
+                tot = np.concatenate([t.sum(1) for t in chunks])
+                assert np.abs(tot - ref.numpy().ravel()).max() <= 1e-13 * float(ref.abs().max()), (math, kind)
+                if kind == "dgrad":                                     # (no bias, no base:) every product is exact in float32
+                    assert all(np.array_equal(t.astype(np.float32).astype(np.float64), t) for t in chunks)
+
+
+def test_lowp_acceptance_rule_rejects_modelled_kernel_faults():
+    """On three helpers.CONV16_GRID shapes the rule of tests/test_conv_lowp_fp64_gpu.py (conv_accepts at CONV_MARGIN_CAP, against the
+    chained-float32 yardstick of the image products) ACCEPTS a faithful numpy model — the image products added in float32, pairwise
+    — and REJECTS a model of each of these faults, everything else summed exactly in float64: f16x3 without the hi*lo term; a bf16
+    operand left unrounded; one rounded twice (to 12 significant bits, then to bf16: the values next to a tie move); the last
+    K-step of 32 channels — where C % 32 != 0, the partial one — skipped; two 32-column tiles swapped; one parity class of a
+    stride-2 data gradient left at the value the accumulating call found there."""
+    import numpy as np
+    import torch
+    from helpers import (CONV16_GRID, CONV_MARGIN_CAP, MATH_BF16, MATH_F16X3, bf16_exact, conv_accepts, conv_error_ratios, conv_sample_positions,
+                         conv_yardstick, lowp_fprop_ref64, lowp_grads_ref64, lowp_image, lowp_terms, round_sig_bits)
+    ran = {}
+    for gi_ in (1, 6, 13):
+        n, c, h, w, k, r, s, st, ph, pw = CONV16_GRID[gi_][:10]
+        rng = np.random.default_rng(90 + gi_)
+        p, q = (h + 2 * ph - r) // st + 1, (w + 2 * pw - s) // st + 1
+        x = rng.standard_normal((n, c, h, w)).astype(np.float32)
+        wt = (rng.standard_normal((k, c, r, s)) / np.sqrt(c * r * s)).astype(np.float32)
+        gy = rng.standard_normal((n, k, p, q)).astype(np.float32)
+        base = rng.standard_normal((n, c, h, w)).astype(np.float32)
+        for math in (MATH_BF16, MATH_F16X3):
+            xi, wi, gim = (lowp_image(math, t) for t in (x, wt, gy))
+            y = lowp_fprop_ref64(math, xi, wi, None, st, (ph, pw), False).numpy()
+            idx = conv_sample_positions(y.shape, 3)
+            terms = np.concatenate(list(lowp_terms(math, "fprop", idx, xi, wi, st, (ph, pw))))
+            ref_s, max_seq, rms_seq = conv_yardstick([terms])
+            assert 0 < rms_seq < max_seq and np.abs(ref_s - y[idx]).max() <= 1e-12 * np.abs(y).max()
+
+            def verdict(name, got_s, got_all=None, want=False, ref_all=y, ref_at=ref_s, yard=(max_seq, rms_seq)):
+                ok = conv_accepts(conv_error_ratios(got_s, ref_at, *yard, got_all, None if got_all is None else ref_all), CONV_MARGIN_CAP)
+                assert ok == want, (gi_, math, name, float(np.abs(got_s - ref_at).max()), yard)
+                ran[name] = ran.get(name, 0) + 1
+            verdict("faithful", np.sum(terms.astype(np.float32), axis=1, dtype=np.float32).astype(np.float64), want=True)
+            exact = lambda a, b, **kw: np.concatenate([t.sum(1) for t in lowp_terms(math, "fprop", idx, a, b, st, (ph, pw), **kw)])
+            if math == MATH_F16X3:
+                verdict("no hi*lo", exact(xi, wi, pairs=((0, 0), (1, 0))))
+            else:
+                raw = ((x.astype(np.float64),), np.float64(1.0))
+                twice = ((bf16_exact(round_sig_bits(x, 12).astype(np.float32)).astype(np.float64),), np.float64(1.0))
+                assert 0 < np.mean(twice[0][0] != xi[0][0]) < 0.2
+                verdict("unrounded operand", exact(raw, wi))
+                verdict("operand rounded twice", exact(twice, wi))
+            cut = (c - 1) // 32 * 32                                            # first channel of the last K-step
+            short = (tuple(np.where(np.arange(c)[None, :, None, None] < cut, part, 0.0) for part in xi[0]), xi[1])
+            if cut > 0:
+                verdict("last K-step skipped" + (" (partial)" if c % 32 else ""), exact(short, wi))
+            if k >= 64:
+                sw = y.copy()
+                sw[:, 0:32], sw[:, 32:64] = y[:, 32:64], y[:, 0:32]
+                verdict("column tiles swapped", sw[idx], sw)
+            if st == 2:
+                dx = lowp_grads_ref64(math, xi, wi, gim, st, (ph, pw))[0].numpy() + base.astype(np.float64)
+                didx = conv_sample_positions(dx.shape, 4)
+                dref, dmax, drms = conv_yardstick(lowp_terms(math, "dgrad", didx, gim, wi, st, (ph, pw), base=base))
+                stale = dx.copy()
+                stale[:, :, 1::2, 1::2] = base[:, :, 1::2, 1::2]
+                verdict("stale parity class", stale[didx], stale, ref_all=dx, ref_at=dref, yard=(dmax, drms))
+                verdict("faithful", dx[didx], dx, want=True, ref_all=dx, ref_at=dref, yard=(dmax, drms))
+    assert set(ran) == {"faithful", "no hi*lo", "unrounded operand", "operand rounded twice", "last K-step skipped", "last K-step skipped (partial)",
+                        "column tiles swapped", "stale parity class"}, ran
+    assert all(v >= 2 for name, v in ran.items() if "partial" not in name and name != "last K-step skipped"), ran
