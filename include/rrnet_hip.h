@@ -757,6 +757,22 @@ int rr_dcn_wgrad_bf16(const float *x, const float *offset, const float *mask, co
                       int wd, int c, int k, int r, int s, int stride, int pad_h, int pad_w, int dilation,
                       int deformable_groups, hipStream_t stream);
 
+/* Introspection, for tests: HOW a deformable convolution would launch, as the host plans of csrc/dcn_plan.h decide it.  Launches
+ * nothing, needs no device.  pass: 0 forward, 1 weight gradient, 2 data gradient.  margin: the window margin asked for
+ * (RR_DCN_WINDOW), < 0: the library's.  flags, what the entry points of a pass differ by: 1 a workspace for packed weights
+ * (_packed), 2 a buffer for dY's bf16 image (_ws, _img, _packed), 4 that image is complete (_img, _packed with dy_bf16),
+ * 8 accumulate.  out[0..7] = {window kernel (0: L2-gather), margin, window height, window width, pixel blocks down / across an
+ * image, workgroups, dynamic LDS bytes}; out[8..] by pass —
+ *   forward: window tile width, L2-gather tile width, weights packed in front and fed by LDS-DMA;
+ *   weight gradient: dY by LDS-DMA, 256-filter tiles, workgroups per pixel split, pixel splits, input window by LDS-DMA, and for
+ *     the L2-gather kernel 128-filter tiles, 128-channel tiles, K-steps per split;
+ *   data gradient: dx zero-filled in front, the sweep reads dY's bf16 image, a pass in front writes that image, both sweep
+ *     operands by LDS-DMA (weights packed in front), byte offset of the window-pixel offset table;
+ * the rest 0.  n_out >= RR_DCN_PLAN_INTS.  A call the pass refuses returns an error (rr_last_error says why). */
+#define RR_DCN_PLAN_INTS 16
+int rr_dcn_plan(int pass, int bf16, int n, int h, int wd, int c, int k, int r, int s, int stride, int pad_h, int pad_w,
+                int dilation, int deformable_groups, int margin, int flags, int *out, int n_out);
+
 /* DCN module glue (ext/dcn/dcn_v2.py:117-121): om NHWC [m, 3*third] -> offset [m, 2*third] (first two thirds,
  * unchanged = cat(o1, o2)) and mask [m, third] = sigmoid(last third); backward: dom from doffset, dmask and mask. */
 int rr_dcn_split_fwd(const float *om, long m, int third, float *offset, float *mask, hipStream_t stream);

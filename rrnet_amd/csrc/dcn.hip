@@ -10,22 +10,23 @@
 //     workgroup owns an 8x16 block of output pixels and stages the input block it can reach in LDS once per 32-channel
 //     chunk; templates over the operand precision (bf16 on v_mfma_f32_32x32x16_bf16, fp32 on v_mfma_f32_32x32x2_f32);
 //     d input is pre-summed in a fixed-point LDS image before it goes out as global atomics;
-//   * L2-gather kernels (dcn_fprop_kernel, dcn_fprop_bf16_kernel, dcn_wgrad_kernel, dcn_dgrad_kernel): the same GEMMs
+//   * L2-gather kernels (dcn_fprop_kernel for both operand precisions, dcn_wgrad_kernel, dcn_dgrad_kernel): the same GEMMs
 //     with the corners fetched from global memory per K-step — every other layer shape, and RR_DCN_WINDOW=0;
 //   * column path (dcn_im2col_kernel / dcn_col2im_kernel): the reference's structure ([M, R*S*C] columns materialised,
 //     GEMMs on the conv kernels), kept as the A/B reference of the fused backward and for the layouts it does not take.
 // Layouts: x NHWC; offset NHWC [N,P,Q,2*dg*R*S] (per group: interleaved (dh,dw) per tap, as the
 // reference's channel order); mask NHWC [N,P,Q,dg*R*S]; weight OHWI.
 #include "common.h"
-#include "conv_plan.h"
+#include "dcn_plan.h"
 #include "rrnet_hip.h"
+#include <type_traits>
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-constexpr int BM = 128, BK = 32, LDK = 36;
+constexpr int BM = rr_plan::BM, BK = rr_plan::BK, LDK = rr_plan::DCN_LDK;      // (the plan sizes the LDS from the same constants)
 
 struct DcnArgs {
     const float *x, *offset, *mask, *w, *bias;
@@ -63,15 +64,41 @@ __device__ __forceinline__ Tap4 make_tap(const DcnArgs &a, int n, int p, int q, 
     return t;
 }
 
-template <int BN>
+// ---- bf16 operands (BASELINE config 4) -------------------------------------------------------------------------------
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+constexpr int LDKH = rr_plan::DCN_LDKH;
+
+// float -> bf16, round to nearest even, on the hardware converter (v_cvt_pk_bf16_f32: two values per instruction).  The
+// integer emulation this replaces (add 0x7fff + lsb, shift: four VALU operations per value) was a third of the VALU work of
+// every staging thread — 192 of ≈330 operations per thread and K-step in the forward.
+typedef __bf16 bf16x4v __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ unsigned short f2bf(float f)
+{
+    return __builtin_bit_cast(unsigned short, (__bf16)f);
+}
+__device__ __forceinline__ u16x4 f2bf4(f32x4 v)
+{
+    return __builtin_bit_cast(u16x4, __builtin_convertvector(v, bf16x4v));
+}
+
+// The L2-gather forward.  F32: fp32 operands on v_mfma_f32_32x32x2_f32, LDS tiles [row][k] of 36 floats per row.  Otherwise the
+// blended samples and the weights are rounded to bf16 (round-to-nearest-even) on their way into LDS and multiplied on
+// v_mfma_f32_32x32x16_bf16 (fp32 accumulation): 8 MFMAs per 32-channel K-step instead of 64, which moves the bound from the
+// matrix pipe to the four-corner gather; LDS tiles are [row][k] with 40 bf16 per row (16-byte aligned rows, one ds_read_b128 =
+// the 8 k values a lane feeds to one MFMA).
+template <int BN, bool F32>
 __global__ __launch_bounds__(256) void dcn_fprop_kernel(const DcnArgs a)
 {
     constexpr int WN = BN / 64 ? BN / 64 : 1, WM = 4 / WN;
     constexpr int TM = BM / (WM * 32), TN = BN / (WN * 32);
-    constexpr int A_ELEMS = BM * LDK, B_ELEMS = BN * LDK;
+    using elem = std::conditional_t<F32, float, unsigned short>;      // what an LDS tile holds
+    constexpr int LD = F32 ? LDK : LDKH;                              // its row pitch in elements
+    constexpr int A_ELEMS = BM * LD, B_ELEMS = BN * LD;
     constexpr int AJ = BM / 32, BJ = BN / 32;
-    extern __shared__ __align__(16) float lds[];
-    float *As = lds, *Bs = lds + 2 * A_ELEMS;
+    extern __shared__ __align__(16) unsigned char smem[];
+    elem *As = reinterpret_cast<elem *>(smem), *Bs = As + 2 * A_ELEMS;
 
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wm = wave / WN, wn = wave % WN;
     const int ntiles = (a.K + BN - 1) / BN;
@@ -100,7 +127,6 @@ __global__ __launch_bounds__(256) void dcn_fprop_kernel(const DcnArgs a)
 
     f32x4 rv[AJ][4], rb[BJ];
     float rw[AJ][4];
-    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
 
     // the sample geometry of a (row, tap) pair is shared by the channel chunks of the tap (K-steps run tap outer,
     // chunk inner): recomputed only when the tap or the deformable group changes — a wave-uniform branch
@@ -145,14 +171,18 @@ __global__ __launch_bounds__(256) void dcn_fprop_kernel(const DcnArgs a)
         }
     };
     auto commit = [&](int buf) {      // blend the four corners and stage both tiles
-        float *A = As + buf * A_ELEMS, *B = Bs + buf * B_ELEMS;
+        elem *A = As + buf * A_ELEMS, *B = Bs + buf * B_ELEMS;
 #pragma unroll
         for (int j = 0; j < AJ; ++j) {
             const f32x4 v = rv[j][0] * rw[j][0] + rv[j][1] * rw[j][1] + rv[j][2] * rw[j][2] + rv[j][3] * rw[j][3];
-            *reinterpret_cast<f32x4 *>(A + (a_row + 32 * j) * LDK + a_col) = v;
+            if constexpr (F32) *reinterpret_cast<f32x4 *>(A + (a_row + 32 * j) * LD + a_col) = v;
+            else *reinterpret_cast<u16x4 *>(A + (a_row + 32 * j) * LD + a_col) = f2bf4(v);
         }
 #pragma unroll
-        for (int j = 0; j < BJ; ++j) *reinterpret_cast<f32x4 *>(B + (a_row + 32 * j) * LDK + a_col) = rb[j];
+        for (int j = 0; j < BJ; ++j) {
+            if constexpr (F32) *reinterpret_cast<f32x4 *>(B + (a_row + 32 * j) * LD + a_col) = rb[j];
+            else *reinterpret_cast<u16x4 *>(B + (a_row + 32 * j) * LD + a_col) = f2bf4(rb[j]);
+        }
     };
 
     f32x16 acc[TM][TN];
@@ -170,187 +200,42 @@ __global__ __launch_bounds__(256) void dcn_fprop_kernel(const DcnArgs a)
     for (int kc = 0; kc < nk; ++kc) {
         const int buf = kc & 1;
         if (kc + 1 < nk) issue(kc + 1);
-        const float *A = As + buf * A_ELEMS, *B = Bs + buf * B_ELEMS;
+        const elem *A = As + buf * A_ELEMS, *B = Bs + buf * B_ELEMS;
+        if constexpr (F32) {
 #pragma unroll
-        for (int kk = 0; kk < BK / 8; ++kk) {
-            f32x4 fa[TM], fb[TN];
+            for (int kk = 0; kk < BK / 8; ++kk) {
+                f32x4 fa[TM], fb[TN];
 #pragma unroll
-            for (int i = 0; i < TM; ++i)
-                fa[i] = *reinterpret_cast<const f32x4 *>(A + ((wm * TM + i) * 32 + lr) * LDK + kk * 8 + lh * 4);
+                for (int i = 0; i < TM; ++i)
+                    fa[i] = *reinterpret_cast<const f32x4 *>(A + ((wm * TM + i) * 32 + lr) * LD + kk * 8 + lh * 4);
 #pragma unroll
-            for (int j = 0; j < TN; ++j)
-                fb[j] = *reinterpret_cast<const f32x4 *>(B + ((wn * TN + j) * 32 + lr) * LDK + kk * 8 + lh * 4);
+                for (int j = 0; j < TN; ++j)
+                    fb[j] = *reinterpret_cast<const f32x4 *>(B + ((wn * TN + j) * 32 + lr) * LD + kk * 8 + lh * 4);
 #pragma unroll
-            for (int e = 0; e < 4; ++e)
+                for (int e = 0; e < 4; ++e)
+#pragma unroll
+                    for (int i = 0; i < TM; ++i)
+#pragma unroll
+                        for (int j = 0; j < TN; ++j)
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i][e], fb[j][e], acc[i][j], 0, 0, 0);
+            }
+        } else {
+#pragma unroll
+            for (int kk = 0; kk < BK / 16; ++kk) {
+                // both operands use the same (lane half, element) -> k map, so the MFMA's own k ordering is immaterial
+                bf16x8 fa[TM], fb[TN];
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+                    fa[i] = *reinterpret_cast<const bf16x8 *>(A + ((wm * TM + i) * 32 + lr) * LD + kk * 16 + lh * 8);
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+                    fb[j] = *reinterpret_cast<const bf16x8 *>(B + ((wn * TN + j) * 32 + lr) * LD + kk * 16 + lh * 8);
 #pragma unroll
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
                     for (int j = 0; j < TN; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i][e], fb[j][e], acc[i][j], 0, 0, 0);
-        }
-        if (kc + 1 < nk) commit(buf ^ 1);
-        __syncthreads();
-    }
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int ko = n0 + (wn * TN + j) * 32 + lr;
-        if (ko >= a.K) continue;
-        const float bv = a.bias ? a.bias[ko] : 0.f;
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int m = m0 + (wm * TM + i) * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
-                if (m < a.M) a.y[(long)m * a.K + ko] = acc[i][j][e] + bv;
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
             }
-    }
-}
-
-// ---- bf16-operand forward (BASELINE config 4) --------------------------------------------------------------------
-// Same gather-GEMM; the blended samples and the weights are rounded to bf16 (round-to-nearest-even) on their way into
-// LDS and multiplied on v_mfma_f32_32x32x16_bf16 (fp32 accumulation): 8 MFMAs per 32-channel K-step instead of 64,
-// which moves the bound from the matrix pipe to the four-corner gather.  LDS tiles are [row][k] with 40 bf16 per
-// row (16-byte aligned rows, one ds_read_b128 = the 8 k values a lane feeds to one MFMA).
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-constexpr int LDKH = BK + 8;
-
-// float -> bf16, round to nearest even, on the hardware converter (v_cvt_pk_bf16_f32: two values per instruction).  The
-// integer emulation this replaces (add 0x7fff + lsb, shift: four VALU operations per value) was a third of the VALU work of
-// every staging thread — 192 of ≈330 operations per thread and K-step in the forward.
-typedef __bf16 bf16x4v __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ unsigned short f2bf(float f)
-{
-    return __builtin_bit_cast(unsigned short, (__bf16)f);
-}
-__device__ __forceinline__ u16x4 f2bf4(f32x4 v)
-{
-    return __builtin_bit_cast(u16x4, __builtin_convertvector(v, bf16x4v));
-}
-
-template <int BN>
-__global__ __launch_bounds__(256) void dcn_fprop_bf16_kernel(const DcnArgs a)
-{
-    constexpr int WN = BN / 64 ? BN / 64 : 1, WM = 4 / WN;
-    constexpr int TM = BM / (WM * 32), TN = BN / (WN * 32);
-    constexpr int A_ELEMS = BM * LDKH, B_ELEMS = BN * LDKH;      // in bf16 elements
-    constexpr int AJ = BM / 32, BJ = BN / 32;
-    extern __shared__ __align__(16) unsigned short ldsh[];
-    unsigned short *As = ldsh, *Bs = ldsh + 2 * A_ELEMS;
-
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wm = wave / WN, wn = wave % WN;
-    const int ntiles = (a.K + BN - 1) / BN;
-    const int n_tile = blockIdx.x % ntiles, m_tile = blockIdx.x / ntiles;
-    const int m0 = m_tile * BM, n0 = n_tile * BN;
-    const int RS = a.R * a.S;
-    const int cpt = (a.C + BK - 1) / BK;
-    const int nk = RS * cpt;
-    const int cpg = a.C / a.dg;
-    const int a_col = (t & 7) * 4, a_row = t >> 3;
-
-    int rn[AJ], rp[AJ], rq[AJ];
-#pragma unroll
-    for (int j = 0; j < AJ; ++j) {
-        const int m = m0 + a_row + 32 * j;
-        if (m < a.M) {
-            const int pq = a.P * a.Q;
-            rn[j] = m / pq;
-            const int rem = m - rn[j] * pq;
-            rp[j] = rem / a.Q;
-            rq[j] = rem - rp[j] * a.Q;
-        } else {
-            rn[j] = -1; rp[j] = 0; rq[j] = 0;
-        }
-    }
-    f32x4 rv[AJ][4], rb[BJ];
-    float rw[AJ][4];
-    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-
-    // the sample geometry of a (row, tap) pair is shared by the channel chunks of the tap (K-steps run tap outer,
-    // chunk inner): recomputed only when the tap or the deformable group changes — a wave-uniform branch
-    Tap4 tc[AJ];
-    int tc_tap = -1, tc_g = -1;
-    auto issue = [&](int kc) {
-        const int tap = kc / cpt, cch = kc - tap * cpt;
-        const int i = tap / a.S, jx = tap - i * a.S;
-        const int c0 = cch * BK;
-        const int g = c0 / cpg;
-        const bool c_ok = c0 + a_col < a.C;
-        if (tap != tc_tap || g != tc_g) {
-            tc_tap = tap; tc_g = g;
-#pragma unroll
-            for (int j = 0; j < AJ; ++j) {
-                if (rn[j] >= 0) {
-                    const long m = (long)m0 + a_row + 32 * j;
-                    const float *po = a.offset + m * (2 * a.dg * RS) + g * 2 * RS + 2 * tap;
-                    const float mk = a.mask[m * (a.dg * RS) + g * RS + tap];
-                    tc[j] = make_tap(a, rn[j], rp[j], rq[j], i, jx, po[0], po[1], mk);
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { tc[j].o[e] = -1; tc[j].w[e] = 0.f; }
-                }
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < AJ; ++j) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float *src = (tc[j].o[e] >= 0 && c_ok) ? a.x + tc[j].o[e] + c0 + a_col : a.zero;
-                rv[j][e] = *reinterpret_cast<const f32x4 *>(src);
-                rw[j][e] = tc[j].w[e];
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < BJ; ++j) {
-            const int ko = n0 + a_row + 32 * j;
-            const bool ok = ko < a.K && c0 + a_col < a.C;
-            const float *src = ok ? a.w + ((long)ko * RS + tap) * a.C + c0 + a_col : a.zero;
-            rb[j] = *reinterpret_cast<const f32x4 *>(src);
-        }
-    };
-    auto commit = [&](int buf) {
-        unsigned short *A = As + buf * A_ELEMS, *B = Bs + buf * B_ELEMS;
-#pragma unroll
-        for (int j = 0; j < AJ; ++j) {
-            const f32x4 v = rv[j][0] * rw[j][0] + rv[j][1] * rw[j][1] + rv[j][2] * rw[j][2] + rv[j][3] * rw[j][3];
-            *reinterpret_cast<u16x4 *>(A + (a_row + 32 * j) * LDKH + a_col) = f2bf4(v);
-        }
-#pragma unroll
-        for (int j = 0; j < BJ; ++j) *reinterpret_cast<u16x4 *>(B + (a_row + 32 * j) * LDKH + a_col) = f2bf4(rb[j]);
-    };
-
-    f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-    const int lr = lane & 31, lh = lane >> 5;
-
-    issue(0);
-    commit(0);
-    __syncthreads();
-    for (int kc = 0; kc < nk; ++kc) {
-        const int buf = kc & 1;
-        if (kc + 1 < nk) issue(kc + 1);
-        const unsigned short *A = As + buf * A_ELEMS, *B = Bs + buf * B_ELEMS;
-#pragma unroll
-        for (int kk = 0; kk < BK / 16; ++kk) {
-            // both operands use the same (lane half, element) -> k map, so the MFMA's own k ordering is immaterial
-            bf16x8 fa[TM], fb[TN];
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-                fa[i] = *reinterpret_cast<const bf16x8 *>(A + ((wm * TM + i) * 32 + lr) * LDKH + kk * 16 + lh * 8);
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-                fb[j] = *reinterpret_cast<const bf16x8 *>(B + ((wn * TN + j) * 32 + lr) * LDKH + kk * 16 + lh * 8);
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
         }
         if (kc + 1 < nk) commit(buf ^ 1);
         __syncthreads();
@@ -371,7 +256,7 @@ __global__ __launch_bounds__(256) void dcn_fprop_bf16_kernel(const DcnArgs a)
 }
 
 // ---- forward with an LDS-staged input window (round 2; bf16 or fp32 operands) -------------------------------------------------
-// The gather was the bound of dcn_fprop_bf16_kernel: every (pixel, tap) fetched its four corner rows from global
+// The gather was the bound of the bf16 dcn_fprop_kernel: every (pixel, tap) fetched its four corner rows from global
 // memory, 19.4 GB per call through the fabric for a 0.54 GB input (each input row is wanted ~36 times, minutes apart in
 // L2 terms).  Here a workgroup owns a 2-D block of TH x TW = 8 x 16 output pixels, and for every 32-channel chunk the
 // input window that block can reach — the block, the filter's extent and a margin of RW pixels for the offsets — is
@@ -379,8 +264,8 @@ __global__ __launch_bounds__(256) void dcn_fprop_bf16_kernel(const DcnArgs a)
 // the chunk gather their corners from LDS.  Corners that fall outside the window (|offset| beyond the margin) are
 // fetched from global memory by the lanes concerned.  The sample geometry (4 corner indices + 4 mask-weighted bilinear
 // weights per pixel and tap) is computed once per workgroup into LDS tables.  K-steps run chunk outer / tap inner.
-// stride 1 only (the window of a strided layer is not compact); other layers take dcn_fprop_bf16_kernel.
-constexpr int WIN_TH = 8, WIN_TW = 16;
+// stride 1 only (the window of a strided layer is not compact); other layers take dcn_fprop_kernel.
+constexpr int WIN_TH = rr_plan::DCN_TH, WIN_TW = rr_plan::DCN_TW;
 
 struct DcnWinArgs {
     DcnArgs a;
@@ -2234,21 +2119,17 @@ __global__ __launch_bounds__(512) void dcn_wgrad_win_kernel(const DcnWinWgradArg
 
 __device__ float rr_dcn_zero16[4] = {0.f, 0.f, 0.f, 0.f};
 
-int fill_args(DcnArgs &a, const float *x, const float *offset, const float *mask, const float *w, int n, int h, int wd,
-              int c, int k, int r, int s, int stride, int pad_h, int pad_w, int dil, int dg)
+using rr_plan::DcnGeom;
+
+// d: rr_plan::dcn_dims(g), or the plan of the pass — what it refuses (the dimensions, or the pass this shape) is the call's error
+int fill_args(DcnArgs &a, const float *x, const float *offset, const float *mask, const float *w, const DcnGeom &g,
+              const rr_plan::DcnPlanHead &d)
 {
-    RR_CHECK_ARG(n > 0 && h > 0 && wd > 0 && c > 0 && k > 0 && r > 0 && s > 0 && stride > 0 && dil > 0 && dg > 0, "rr_dcn: bad dims");
-    RR_CHECK_ARG(c % 4 == 0 && c % dg == 0, "rr_dcn: C=%d must be a multiple of 4 and of deformable_groups=%d", c, dg);
-    RR_CHECK_ARG(dg == 1 || (c / dg) % BK == 0, "rr_dcn: channels per deformable group (%d) must be a multiple of 32", c / dg);
+    RR_CHECK_ARG(d.refuse == nullptr, d.refuse, d.a0, d.a1);
     a.x = x; a.offset = offset; a.mask = mask; a.w = w;
-    a.N = n; a.H = h; a.W = wd; a.C = c; a.K = k; a.R = r; a.S = s;
-    a.P = (h + 2 * pad_h - (dil * (r - 1) + 1)) / stride + 1;
-    a.Q = (wd + 2 * pad_w - (dil * (s - 1) + 1)) / stride + 1;
-    RR_CHECK_ARG(a.P > 0 && a.Q > 0, "rr_dcn: empty output");
-    a.stride = stride; a.pad_h = pad_h; a.pad_w = pad_w; a.dil = dil; a.dg = dg;
-    const long M = (long)n * a.P * a.Q;
-    RR_CHECK_ARG(M < (1l << 31), "rr_dcn: too many output pixels");
-    a.M = (int)M;
+    a.N = g.n; a.H = g.h; a.W = g.w; a.C = g.c; a.K = g.k; a.R = g.r; a.S = g.s;
+    a.P = d.P; a.Q = d.Q; a.M = d.M;
+    a.stride = g.stride; a.pad_h = g.pad_h; a.pad_w = g.pad_w; a.dil = g.dil; a.dg = g.dg;
     static float *zp[64] = {};
     int dev = 0;
     hipGetDevice(&dev);
@@ -2260,6 +2141,7 @@ int fill_args(DcnArgs &a, const float *x, const float *offset, const float *mask
 
 }  // namespace
 
+// ---- host side.  How a call launches is rr_plan::dcn_*_plan's decision (dcn_plan.h); the code below carries it out.
 static int dcn_win_margin()
 {
     static int v = -2;
@@ -2270,7 +2152,27 @@ static int dcn_win_margin()
     return v;
 }
 
-// LDS-window forward for either operand precision; -1 when the layer does not qualify.
+// Raise the kernel's dynamic LDS limit, launch, check.  The limit is raised for what asks for more than 48 KB; the kernels that
+// stay below (the bf16 and the 32-column L2-gather forward) launch without that runtime call.
+template <class Args>
+static int dcn_launch(void (*kernel)(Args), int grid, int threads, int lds, hipStream_t stream, const char *name, const Args &args)
+{
+    if (lds > 48 * 1024)
+        RR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds), name);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds, stream, args);
+    RR_CHECK_LAUNCH(name);
+    return RR_OK;
+}
+
+static DcnWinArgs dcn_win_args(const DcnArgs &a, const rr_plan::DcnPlanHead &pl)
+{
+    DcnWinArgs wa{};
+    wa.a = a;
+    wa.RW = pl.margin; wa.WH = pl.WH; wa.WW = pl.WW;
+    wa.tiles_y = pl.tiles_y; wa.tiles_x = pl.tiles_x;
+    return wa;
+}
+
 // wpk[((tap * C/32 + cch) * K + ko) * 32 + cl] = bf16(w[(ko * RS + tap) * C + cch * 32 + cl]): one thread = 4 values
 __global__ __launch_bounds__(256) void dcn_pack_weights_kernel(const float *w, unsigned short *wpk, int K, int C, int RS)
 {
@@ -2286,89 +2188,50 @@ __global__ __launch_bounds__(256) void dcn_pack_weights_kernel(const float *w, u
     }
 }
 
-static int dcn_fwd_win(const DcnArgs &a, int n, int k, int r, int s, int stride, int dilation, int c, int h, int wd, int bf16,
-                       hipStream_t stream, const char *name, unsigned short *wpk = nullptr)
+static void dcn_pack_weights(const float *w, unsigned short *wpk, const DcnGeom &g, hipStream_t stream)
 {
-    const int rw = dcn_win_margin();
-    if (!(rw > 0 && stride == 1 && k > 32 && c % BK == 0 && (long)h * wd < (1l << 30))) return -1;
-    // the input block a pixel tile can reach is staged once per channel chunk
-    DcnWinArgs wa{};
-    wa.a = a;
-    wa.tiles_y = rr_cdiv(a.P, WIN_TH);
-    wa.tiles_x = rr_cdiv(a.Q, WIN_TW);
-    const int wbn = (k % 256 == 0 || k > 384) ? 256 : 128;
-    size_t lds = 0;
-    bool fits = false;
-    for (int m = rw; m >= 1 && !fits; --m) {          // the largest margin <= the requested one that fits
-        wa.RW = m;
-        wa.WH = WIN_TH + (r - 1) * dilation + 2 * m + 1;
-        wa.WW = WIN_TW + (s - 1) * dilation + 2 * m + 1;
-        const int npx = wa.WH * wa.WW;
-        lds = (size_t)npx * BK * 4 + (size_t)BM * r * s * 4 * 8 + sizeof(unsigned short) * 2 * (BM * LDKH + wbn * LDKH);
-        fits = npx <= 14 * 32 && lds <= 160 * 1024 - 512;
+    hipLaunchKernelGGL(dcn_pack_weights_kernel, dim3(rr_cdiv((long)g.k * g.r * g.s * g.c / 4, 256)), dim3(256), 0, stream, w, wpk, g.k, g.c,
+                       g.r * g.s);
+}
+
+// wpk: the caller's workspace for the weights packed to bf16 (rr_dcn_wpack_bytes), or null
+static int dcn_fwd_impl(const char *name, const float *x, const float *offset, const float *mask, const float *w, const float *bias,
+                        float *y, const DcnGeom &g, bool bf16, unsigned short *wpk, hipStream_t stream)
+{
+    const rr_plan::DcnFwdPlan pl = rr_plan::dcn_fwd_plan(g, bf16, wpk ? rr_plan::DCN_HAS_WPACK : 0, dcn_win_margin());
+    DcnArgs a{};
+    const int rc = fill_args(a, x, offset, mask, w, g, pl);
+    if (rc != RR_OK) return rc;
+    a.bias = bias; a.y = y;
+    if (!pl.window) {
+        const auto kernel = pl.bn == 128 ? (bf16 ? dcn_fprop_kernel<128, false> : dcn_fprop_kernel<128, true>)
+                                         : (bf16 ? dcn_fprop_kernel<32, false> : dcn_fprop_kernel<32, true>);
+        return dcn_launch(kernel, pl.grid, 256, pl.lds, stream, name, a);
     }
-    if (!fits) return -1;
-    const int blocks = n * wa.tiles_y * wa.tiles_x * rr_cdiv(k, wbn);
-#define RR_WIN_LAUNCH(BNV, F32V)                                                                                          \
-    do {                                                                                                                  \
-        hipFuncSetAttribute(reinterpret_cast<const void *>(dcn_fprop_win_kernel<BNV, F32V>),                              \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                        \
-        hipLaunchKernelGGL((dcn_fprop_win_kernel<BNV, F32V>), dim3(blocks), dim3(512), lds, stream, wa);                  \
-    } while (0)
-    wa.wpk = nullptr;
-    if (wbn == 256 && bf16 && wpk != nullptr) {      // B tile by LDS-DMA from the weights packed to bf16 once per call
-        hipLaunchKernelGGL(dcn_pack_weights_kernel, dim3(rr_cdiv((long)k * r * s * c / 4, 256)), dim3(256), 0, stream, a.w, wpk, k, c,
-                           r * s);
+    DcnWinArgs wa = dcn_win_args(a, pl);
+    if (pl.pack) {      // B tile by LDS-DMA from the weights packed to bf16 once per call
+        dcn_pack_weights(w, wpk, g, stream);
         wa.wpk = wpk;
     }
-    if (wbn == 256) { if (bf16) RR_WIN_LAUNCH(256, false); else RR_WIN_LAUNCH(256, true); }
-    else { if (bf16) RR_WIN_LAUNCH(128, false); else RR_WIN_LAUNCH(128, true); }
-#undef RR_WIN_LAUNCH
-    RR_CHECK_LAUNCH(name);
-    return RR_OK;
+    const auto kernel = pl.wbn == 256 ? (bf16 ? dcn_fprop_win_kernel<256, false> : dcn_fprop_win_kernel<256, true>)
+                                      : (bf16 ? dcn_fprop_win_kernel<128, false> : dcn_fprop_win_kernel<128, true>);
+    return dcn_launch(kernel, pl.grid, 512, pl.lds, stream, name, wa);
 }
+
+#define RR_DCN_GEOM {n, h, wd, c, k, r, s, stride, pad_h, pad_w, dilation, deformable_groups}
 
 extern "C" int rr_dcn_fwd(const float *x, const float *offset, const float *mask, const float *w, const float *bias,
                           float *y, int n, int h, int wd, int c, int k, int r, int s, int stride, int pad_h, int pad_w,
                           int dilation, int deformable_groups, hipStream_t stream)
 {
-    DcnArgs a{};
-    const int rc = fill_args(a, x, offset, mask, w, n, h, wd, c, k, r, s, stride, pad_h, pad_w, dilation, deformable_groups);
-    if (rc != RR_OK) return rc;
-    a.bias = bias; a.y = y;
-    const int wrc = dcn_fwd_win(a, n, k, r, s, stride, dilation, c, h, wd, 0, stream, "rr_dcn_fwd");
-    if (wrc != -1) return wrc;
-    const int bn = k > 32 ? 128 : 32;
-    const int blocks = rr_cdiv(a.M, BM) * rr_cdiv(k, bn);
-    const size_t lds = sizeof(float) * 2 * (BM * LDK + bn * LDK);
-    if (bn == 128) {
-        hipFuncSetAttribute(reinterpret_cast<const void *>(dcn_fprop_kernel<128>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(dcn_fprop_kernel<128>, dim3(blocks), dim3(256), lds, stream, a);
-    } else {
-        hipLaunchKernelGGL(dcn_fprop_kernel<32>, dim3(blocks), dim3(256), lds, stream, a);
-    }
-    RR_CHECK_LAUNCH("rr_dcn_fwd");
-    return RR_OK;
+    return dcn_fwd_impl("rr_dcn_fwd", x, offset, mask, w, bias, y, RR_DCN_GEOM, false, nullptr, stream);
 }
-
 
 extern "C" int rr_dcn_fwd_bf16(const float *x, const float *offset, const float *mask, const float *w, const float *bias,
                                float *y, int n, int h, int wd, int c, int k, int r, int s, int stride, int pad_h, int pad_w,
                                int dilation, int deformable_groups, hipStream_t stream)
 {
-    DcnArgs a{};
-    const int rc = fill_args(a, x, offset, mask, w, n, h, wd, c, k, r, s, stride, pad_h, pad_w, dilation, deformable_groups);
-    if (rc != RR_OK) return rc;
-    a.bias = bias; a.y = y;
-    const int bn = k > 32 ? 128 : 32;
-    const int wrc = dcn_fwd_win(a, n, k, r, s, stride, dilation, c, h, wd, 1, stream, "rr_dcn_fwd_bf16");
-    if (wrc != -1) return wrc;
-    const int blocks = rr_cdiv(a.M, BM) * rr_cdiv(k, bn);
-    const size_t lds = sizeof(unsigned short) * 2 * (BM * LDKH + bn * LDKH);
-    if (bn == 128) hipLaunchKernelGGL(dcn_fprop_bf16_kernel<128>, dim3(blocks), dim3(256), lds, stream, a);
-    else hipLaunchKernelGGL(dcn_fprop_bf16_kernel<32>, dim3(blocks), dim3(256), lds, stream, a);
-    RR_CHECK_LAUNCH("rr_dcn_fwd_bf16");
-    return RR_OK;
+    return dcn_fwd_impl("rr_dcn_fwd_bf16", x, offset, mask, w, bias, y, RR_DCN_GEOM, true, nullptr, stream);
 }
 
 extern "C" size_t rr_dcn_wpack_bytes(int c, int k, int r, int s)
@@ -2381,14 +2244,7 @@ extern "C" int rr_dcn_fwd_bf16_packed(const float *x, const float *offset, const
                                       int pad_w, int dilation, int deformable_groups, void *wpack, hipStream_t stream)
 {
     RR_CHECK_ARG(wpack != nullptr, "rr_dcn_fwd_bf16_packed: wpack (rr_dcn_wpack_bytes) is required");
-    DcnArgs a{};
-    const int rc = fill_args(a, x, offset, mask, w, n, h, wd, c, k, r, s, stride, pad_h, pad_w, dilation, deformable_groups);
-    if (rc != RR_OK) return rc;
-    a.bias = bias; a.y = y;
-    const int wrc = dcn_fwd_win(a, n, k, r, s, stride, dilation, c, h, wd, 1, stream, "rr_dcn_fwd_bf16_packed",
-                                (c % 32 == 0 && (long)k * r * s * c * 2 < (1l << 31)) ? static_cast<unsigned short *>(wpack) : nullptr);
-    if (wrc != -1) return wrc;
-    return rr_dcn_fwd_bf16(x, offset, mask, w, bias, y, n, h, wd, c, k, r, s, stride, pad_h, pad_w, dilation, deformable_groups, stream);
+    return dcn_fwd_impl("rr_dcn_fwd_bf16_packed", x, offset, mask, w, bias, y, RR_DCN_GEOM, true, static_cast<unsigned short *>(wpack), stream);
 }
 
 extern "C" size_t rr_dcn_col_bytes(int n, int h, int wd, int c, int r, int s, int stride, int pad_h, int pad_w, int dilation)
@@ -2404,7 +2260,8 @@ extern "C" int rr_dcn_im2col(const float *x, const float *offset, const float *m
                              hipStream_t stream)
 {
     DcnArgs a{};
-    const int rc = fill_args(a, x, offset, mask, nullptr, n, h, wd, c, 1, r, s, stride, pad_h, pad_w, dilation, deformable_groups);
+    const DcnGeom g{n, h, wd, c, 1, r, s, stride, pad_h, pad_w, dilation, deformable_groups};
+    const int rc = fill_args(a, x, offset, mask, nullptr, g, rr_plan::dcn_dims(g));
     if (rc != RR_OK) return rc;
     const long total = (long)a.M * r * s * (c / 4);
     long blocks = (total + 255) / 256;
@@ -2420,7 +2277,8 @@ extern "C" int rr_dcn_col2im(const float *x, const float *offset, const float *m
                              int pad_h, int pad_w, int dilation, int deformable_groups, hipStream_t stream)
 {
     DcnArgs a{};
-    const int rc = fill_args(a, x, offset, mask, nullptr, n, h, wd, c, 1, r, s, stride, pad_h, pad_w, dilation, deformable_groups);
+    const DcnGeom g{n, h, wd, c, 1, r, s, stride, pad_h, pad_w, dilation, deformable_groups};
+    const int rc = fill_args(a, x, offset, mask, nullptr, g, rr_plan::dcn_dims(g));
     if (rc != RR_OK) return rc;
     hipMemsetAsync(dx, 0, sizeof(float) * (size_t)n * h * wd * c, stream);
     const long items = (long)a.M * r * s * deformable_groups;
@@ -2432,122 +2290,35 @@ extern "C" int rr_dcn_col2im(const float *x, const float *offset, const float *m
 }
 
 // Fused backward, part 1: weight gradient.  dw [K][R][S][C] += dY^T x deformed columns (float atomics; pre-zeroed or
-// holding the running gradient).  Requires K % 4 == 0 and one deformable group per 128-channel tile.
-static int dcn_wgrad_plain(const float *x, const float *offset, const float *mask, const float *dy, float *dw, int n, int h,
-                           int wd, int c, int k, int r, int s, int stride, int pad_h, int pad_w, int dilation,
-                           int deformable_groups, hipStream_t stream)
+// holding the running gradient).  dyb: dY's bf16 image, complete on the stream, or null.
+static int dcn_wgrad_impl(const float *x, const float *offset, const float *mask, const float *dy, float *dw, const DcnGeom &g,
+                          bool bf16, const unsigned short *dyb, hipStream_t stream)
 {
-    DcnBwdArgs b{};
-    const int rc = fill_args(b.a, x, offset, mask, nullptr, n, h, wd, c, k, r, s, stride, pad_h, pad_w, dilation, deformable_groups);
+    const rr_plan::DcnWgradPlan pl =
+        rr_plan::dcn_wgrad_plan(g, bf16, dyb ? rr_plan::DCN_HAS_DYB | rr_plan::DCN_DYB_READY : 0, dcn_win_margin());
+    DcnArgs a{};
+    const int rc = fill_args(a, x, offset, mask, nullptr, g, pl);
     if (rc != RR_OK) return rc;
-    RR_CHECK_ARG(k % 4 == 0, "rr_dcn_wgrad: K=%d must be a multiple of 4", k);
-    RR_CHECK_ARG(deformable_groups == 1 || (c / deformable_groups) % 128 == 0,
-                 "rr_dcn_wgrad: channels per deformable group (%d) must be a multiple of 128", c / deformable_groups);
-    b.dy = dy; b.dw = dw;
-    b.mt = rr_cdiv(k, 128); b.nt = rr_cdiv(c, 128);
-    const int tiles = b.mt * b.nt * r * s;
-    const int total_chunks = rr_cdiv(b.a.M, BK);
-    const int splits = rr_plan::pixel_splits(tiles, total_chunks, 512, 8, &b.chunks_per_split);
-    const size_t lds = sizeof(float) * 2 * (BK * 128 + BK * 128);
-    hipFuncSetAttribute(reinterpret_cast<const void *>(dcn_wgrad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(dcn_wgrad_kernel, dim3(tiles * splits), dim3(256), lds, stream, b);
-    RR_CHECK_LAUNCH("rr_dcn_wgrad");
-    return RR_OK;
-}
-
-// Window kernel for either operand precision; returns -1 when the layer does not qualify (caller takes dcn_wgrad_kernel).
-// LDS footprint of the window kernels for a margin of m pixels (0: the window does not fit with any margin >= 1)
-static size_t dcn_wgrad_win_lds(int r, int s, int dilation, int m)
-{
-    const int npx = (WIN_TH + (r - 1) * dilation + 2 * m + 1) * (WIN_TW + (s - 1) * dilation + 2 * m + 1);
-    return sizeof(float) * (size_t)(npx * 32 + BM * r * s * 4) + sizeof(unsigned short) * (size_t)((256 + r * s * 32) * 72);
-}
-
-static size_t dcn_dgrad_win_lds(int r, int s, int dilation, int m)
-{
-    const int npx = (WIN_TH + (r - 1) * dilation + 2 * m + 1) * (WIN_TW + (s - 1) * dilation + 2 * m + 1);
-    // operand area: one image of the sweep (dY 128 x LDKH + weights taps x 32 x LDKH), and for the DMA sweep image 0 + the
-    // third dY image (128 x 32 + taps x 32 x 32 + 128 x 32) — the larger of the two
-    const size_t opa = std::max((size_t)(BM * LDKH + r * s * 32 * LDKH), (size_t)(2 * BM * 32 + r * s * 32 * 32));
-    return sizeof(float) * (size_t)(((npx * 33 + 3) & ~3) + BM * r * s * 7 + npx * 32) + sizeof(unsigned short) * opa;
-}
-
-static bool dcn_win_fits(bool dgrad, int r, int s, int dilation)
-{
-    return (dgrad ? dcn_dgrad_win_lds(r, s, dilation, 1) : dcn_wgrad_win_lds(r, s, dilation, 1)) <= 160 * 1024 - 512;
-}
-
-static int dcn_wgrad_win(const float *x, const float *offset, const float *mask, const float *dy, float *dw, int n, int h,
-                         int wd, int c, int k, int r, int s, int stride, int pad_h, int pad_w, int dilation,
-                         int deformable_groups, int bf16, hipStream_t stream, const unsigned short *dyb = nullptr)
-{
-    const int rw = dcn_win_margin();
-    if (rw > 0 && stride == 1 && r * s == 9 && c % 32 == 0 && k % 4 == 0 && h < 32768 && wd < 32768 &&
-        (deformable_groups == 1 || (c / deformable_groups) % 32 == 0)) {
-        DcnWinWgradArgs wb{};
-        const int rc = fill_args(wb.w.a, x, offset, mask, nullptr, n, h, wd, c, k, r, s, stride, pad_h, pad_w, dilation, deformable_groups);
-        if (rc != RR_OK) return rc;
-        wb.w.tiles_y = rr_cdiv(wb.w.a.P, WIN_TH);
-        wb.w.tiles_x = rr_cdiv(wb.w.a.Q, WIN_TW);
-        wb.dy = dy; wb.dw = dw;
-        size_t ldsw = 0;
-        constexpr bool dydma_on = true;
-        const bool dydma = dydma_on && bf16 && dyb != nullptr && k % 32 == 0 && (long)wb.w.a.M * k * 2 < (1l << 31) &&
-                           (long)n * h * wd * c * 4 < (1l << 31);
-        for (int m = rw; m >= 1; --m) {
-            wb.w.RW = m;
-            wb.w.WH = WIN_TH + (r - 1) * dilation + 2 * m + 1;
-            wb.w.WW = WIN_TW + (s - 1) * dilation + 2 * m + 1;
-            ldsw = dcn_wgrad_win_lds(r, s, dilation, m);
-            // the dY ring: 8 waves x 6 KB instead of the 256 x 72 image; the samples unpadded
-            if (dydma) ldsw = ldsw - sizeof(unsigned short) * (size_t)((256 + r * s * 32) * 72) + sizeof(unsigned short) * (size_t)(8 * 6 * 512 + r * s * 64 * 32);
-            if (ldsw <= 160 * 1024 - 512) break;
-        }
-        if (ldsw <= 160 * 1024 - 512) {
-            const int ntiles = n * wb.w.tiles_y * wb.w.tiles_x;
-            wb.ktiles = rr_cdiv(k, 256);
-            const int per_split = (c / 32) * wb.ktiles;
-            int splits = rr_cdiv(256, per_split);          // one workgroup per CU (the window leaves room for one)
-            if (splits > 8) splits = splits / 8 * 8;
-            if (splits > ntiles) splits = ntiles;
-            wb.splits = splits;
-            wb.dma_window = (long)n * h * wd * c * 4 < (1l << 31);
-            wb.dyb = dyb;
-            if (dydma) {
-                RR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(dcn_wgrad_win_kernel<9, false, true>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw), "rr_dcn_wgrad");
-                hipLaunchKernelGGL((dcn_wgrad_win_kernel<9, false, true>), dim3(splits * per_split), dim3(512), ldsw, stream, wb);
-            } else if (bf16) {
-                hipFuncSetAttribute(reinterpret_cast<const void *>(dcn_wgrad_win_kernel<9, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw);
-                hipLaunchKernelGGL((dcn_wgrad_win_kernel<9, false>), dim3(splits * per_split), dim3(512), ldsw, stream, wb);
-            } else {
-                hipFuncSetAttribute(reinterpret_cast<const void *>(dcn_wgrad_win_kernel<9, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw);
-                hipLaunchKernelGGL((dcn_wgrad_win_kernel<9, true>), dim3(splits * per_split), dim3(512), ldsw, stream, wb);
-            }
-            RR_CHECK_LAUNCH("rr_dcn_wgrad");
-            return RR_OK;
-        }
+    if (!pl.window) {
+        DcnBwdArgs b{};
+        b.a = a; b.dy = dy; b.dw = dw;
+        b.mt = pl.mt; b.nt = pl.nt; b.chunks_per_split = pl.chunks_per_split;
+        return dcn_launch(dcn_wgrad_kernel, pl.grid, 256, pl.lds, stream, "rr_dcn_wgrad", b);
     }
-    return -1;
+    DcnWinWgradArgs wb{};
+    wb.w = dcn_win_args(a, pl);
+    wb.dy = dy; wb.dw = dw; wb.dyb = dyb;
+    wb.splits = pl.splits; wb.ktiles = pl.ktiles; wb.dma_window = pl.dma_window;
+    const auto kernel = pl.dy_dma ? dcn_wgrad_win_kernel<9, false, true> : bf16 ? dcn_wgrad_win_kernel<9, false> : dcn_wgrad_win_kernel<9, true>;
+    return dcn_launch(kernel, pl.grid, 512, pl.lds, stream, "rr_dcn_wgrad", wb);
 }
 
-static int dcn_wgrad_plain(const float *x, const float *offset, const float *mask, const float *dy, float *dw, int n, int h,
-                           int wd, int c, int k, int r, int s, int stride, int pad_h, int pad_w, int dilation,
-                           int deformable_groups, hipStream_t stream);
-
-// 1 when rr_dcn_wgrad / rr_dcn_dgrad take this layer (the host layer runs the column path otherwise): K % 4 == 0 and
-// the deformable groups either span whole 128-channel tiles (L2-gather kernels) or the window kernels apply (3x3,
-// stride 1, C % 32 == 0, groups of a multiple of 32 channels).
+// 1 when rr_dcn_wgrad / rr_dcn_dgrad take this layer (the host layer runs the column path otherwise): both backward plans accept
+// the shape (the map's size is not what they refuse a layer for: asked for the smallest map the filter fits)
 extern "C" int rr_dcn_fused_bwd_supported_dil(int c, int k, int r, int s, int stride, int dilation, int deformable_groups)
 {
-    if (c <= 0 || k <= 0 || deformable_groups <= 0 || c % deformable_groups != 0 || k % 4 != 0 || c % 4 != 0 || dilation <= 0)
-        return 0;
-    const int cpg = c / deformable_groups;
-    if (deformable_groups == 1 || cpg % 128 == 0) return 1;     // the L2-gather kernels take these whatever the window does
-    // smaller groups exist on the window kernels only: BOTH of them must fit their LDS windows with a margin >= 1
-    // (a 3x3 filter with dilation >= 3 does not: rr_dcn_dgrad would drop to the L2-gather kernel and refuse the groups)
-    return dcn_win_margin() > 0 && stride == 1 && r * s == 9 && c % 32 == 0 && cpg % 32 == 0 &&
-           dcn_win_fits(false, r, s, dilation) && dcn_win_fits(true, r, s, dilation);
+    const DcnGeom g{1, dilation * (r - 1) + 1, dilation * (s - 1) + 1, c, k, r, s, stride, 0, 0, dilation, deformable_groups};
+    return !rr_plan::dcn_wgrad_plan(g, false, 0, dcn_win_margin()).refuse && !rr_plan::dcn_dgrad_plan(g, false, 0, dcn_win_margin()).refuse;
 }
 
 extern "C" int rr_dcn_fused_bwd_supported(int c, int k, int r, int s, int stride, int deformable_groups)
@@ -2555,13 +2326,18 @@ extern "C" int rr_dcn_fused_bwd_supported(int c, int k, int r, int s, int stride
     return rr_dcn_fused_bwd_supported_dil(c, k, r, s, stride, 1, deformable_groups);
 }
 
+extern "C" int rr_dcn_wgrad(const float *x, const float *offset, const float *mask, const float *dy, float *dw, int n, int h,
+                            int wd, int c, int k, int r, int s, int stride, int pad_h, int pad_w, int dilation,
+                            int deformable_groups, hipStream_t stream)
+{
+    return dcn_wgrad_impl(x, offset, mask, dy, dw, RR_DCN_GEOM, false, nullptr, stream);
+}
+
 extern "C" int rr_dcn_wgrad_bf16(const float *x, const float *offset, const float *mask, const float *dy, float *dw, int n, int h,
                                  int wd, int c, int k, int r, int s, int stride, int pad_h, int pad_w, int dilation,
                                  int deformable_groups, hipStream_t stream)
 {
-    const int rc = dcn_wgrad_win(x, offset, mask, dy, dw, n, h, wd, c, k, r, s, stride, pad_h, pad_w, dilation, deformable_groups, 1, stream);
-    if (rc != -1) return rc;
-    return dcn_wgrad_plain(x, offset, mask, dy, dw, n, h, wd, c, k, r, s, stride, pad_h, pad_w, dilation, deformable_groups, stream);
+    return dcn_wgrad_impl(x, offset, mask, dy, dw, RR_DCN_GEOM, true, nullptr, stream);
 }
 
 // rr_dcn_wgrad_bf16 with dY's bf16 image (its producer's, or one rr_to_bf16 pass shared with the data gradient): the dY
@@ -2571,18 +2347,7 @@ extern "C" int rr_dcn_wgrad_bf16_img(const float *x, const float *offset, const 
                                      int stride, int pad_h, int pad_w, int dilation, int deformable_groups, hipStream_t stream)
 {
     RR_CHECK_ARG(dy_bf16 != nullptr, "rr_dcn_wgrad_bf16_img: the bf16 image of dy is required");
-    const int rc = dcn_wgrad_win(x, offset, mask, dy, dw, n, h, wd, c, k, r, s, stride, pad_h, pad_w, dilation, deformable_groups, 1, stream, dy_bf16);
-    if (rc != -1) return rc;
-    return dcn_wgrad_plain(x, offset, mask, dy, dw, n, h, wd, c, k, r, s, stride, pad_h, pad_w, dilation, deformable_groups, stream);
-}
-
-extern "C" int rr_dcn_wgrad(const float *x, const float *offset, const float *mask, const float *dy, float *dw, int n, int h,
-                            int wd, int c, int k, int r, int s, int stride, int pad_h, int pad_w, int dilation,
-                            int deformable_groups, hipStream_t stream)
-{
-    const int rc = dcn_wgrad_win(x, offset, mask, dy, dw, n, h, wd, c, k, r, s, stride, pad_h, pad_w, dilation, deformable_groups, 0, stream);
-    if (rc != -1) return rc;
-    return dcn_wgrad_plain(x, offset, mask, dy, dw, n, h, wd, c, k, r, s, stride, pad_h, pad_w, dilation, deformable_groups, stream);
+    return dcn_wgrad_impl(x, offset, mask, dy, dw, RR_DCN_GEOM, true, dy_bf16, stream);
 }
 
 // Fused backward, part 2: dx (zeroed here, then float atomics on the bilinear corners), doffset, dmask (plain stores).
@@ -2592,92 +2357,46 @@ __global__ __launch_bounds__(256) void dcn_to_bf16_kernel(const f32x4 *src, u16x
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) dst[i] = f2bf4(src[i]);
 }
 
-static int dcn_dgrad_impl(const float *x, const float *offset, const float *mask, const float *w, const float *dy,
-                          float *dx, float *doffset, float *dmask, int n, int h, int wd, int c, int k, int r, int s,
-                          int stride, int pad_h, int pad_w, int dilation, int deformable_groups, int bf16, hipStream_t stream,
-                          unsigned short *dyb = nullptr, bool dyb_ready = false, unsigned short *wpk = nullptr, bool accumulate = false)
+// dyb: a buffer for dY's bf16 image (rr_dcn_dyb_bytes), which dyb_ready says dY's producer has filled; wpk: a workspace for the
+// packed weights; accumulate: dx holds another consumer's gradient and is added to
+static int dcn_dgrad_impl(const float *x, const float *offset, const float *mask, const float *w, const float *dy, float *dx,
+                          float *doffset, float *dmask, const DcnGeom &g, bool bf16, hipStream_t stream, unsigned short *dyb = nullptr,
+                          bool dyb_ready = false, unsigned short *wpk = nullptr, bool accumulate = false)
 {
+    using namespace rr_plan;
+    const DcnDgradPlan pl = dcn_dgrad_plan(g, bf16, (dyb ? DCN_HAS_DYB : 0) | (dyb_ready ? DCN_DYB_READY : 0) | (wpk ? DCN_HAS_WPACK : 0) |
+                                                        (accumulate ? DCN_ACCUMULATE : 0), dcn_win_margin());
     DcnBwdArgs b{};
-    const int rc = fill_args(b.a, x, offset, mask, w, n, h, wd, c, k, r, s, stride, pad_h, pad_w, dilation, deformable_groups);
+    const int rc = fill_args(b.a, x, offset, mask, w, g, pl);
     if (rc != RR_OK) return rc;
-    RR_CHECK_ARG(k % 4 == 0, "rr_dcn_dgrad: K=%d must be a multiple of 4", k);
-    RR_CHECK_ARG((long)n * h * wd < (1l << 31), "rr_dcn_dgrad: input too large");
     b.dy = dy; b.dx = dx; b.doffset = doffset; b.dmask = dmask;
-    if (!accumulate) hipMemsetAsync(dx, 0, sizeof(float) * (size_t)n * h * wd * c, stream);     // (every kernel below ADDS into dx with float atomics)
-    const int rw = dcn_win_margin();
-    if (rw > 0 && stride == 1 && c % 32 == 0 && h < 32768 && wd < 32768 &&
-        (deformable_groups == 1 || (c / deformable_groups) % 32 == 0)) {
-        DcnWinBwdArgs wb{};
-        wb.w.a = b.a;
-        wb.w.tiles_y = rr_cdiv(b.a.P, WIN_TH);
-        wb.w.tiles_x = rr_cdiv(b.a.Q, WIN_TW);
-        wb.dy = dy; wb.dx = dx; wb.doffset = doffset; wb.dmask = dmask;
-        wb.dyb = nullptr;
-        // two windows live in LDS here (d input in fixed point, input values): the margin is the largest <= the
-        // requested one that fits (2 pixels for a 3x3 filter with dilation 1)
-        size_t ldsw = 0;
-        for (int m = rw; m >= 1; --m) {
-            wb.w.RW = m;
-            wb.w.WH = WIN_TH + (r - 1) * dilation + 2 * m + 1;
-            wb.w.WW = WIN_TW + (s - 1) * dilation + 2 * m + 1;
-            ldsw = dcn_dgrad_win_lds(r, s, dilation, m);
-            if (ldsw <= 160 * 1024 - 512) break;
-        }
-        if (r * s == 9 && ldsw <= 160 * 1024 - 512) {
-            const dim3 grid(n * wb.w.tiles_y * wb.w.tiles_x);
-            if (bf16) {
-                if (dyb != nullptr && dyb_ready) {
-                    wb.dyb = dyb;                 // the caller's bf16 image of dY (written by dY's producer): nothing to convert
-                } else if (dyb != nullptr && k % 4 == 0) {
-                    const long n4 = (long)b.a.M * k / 4;
-                    long cb = (n4 + 255) / 256;
-                    if (cb > 256 * 32) cb = 256 * 32;
-                    hipLaunchKernelGGL(dcn_to_bf16_kernel, dim3((int)cb), dim3(256), 0, stream, reinterpret_cast<const f32x4 *>(dy),
-                                       reinterpret_cast<u16x4 *>(dyb), n4);
-                    wb.dyb = dyb;
-                }
-                constexpr bool dma_on = true;
-                if (dma_on && wb.dyb != nullptr && wpk != nullptr && k % 32 == 0 && (long)b.a.M * k * 2 < (1l << 31) &&
-                    (long)n * h * wd * c * 4 < (1l << 31) && wb.w.WH * wb.w.WW <= 368 &&
-                    ldsw + (size_t)wb.w.WH * wb.w.WW * 4 + 16 <= 160 * 1024 - 512 &&
-                    (size_t)wb.w.WH * wb.w.WW * 33 * 4 >= (size_t)(BM * 32 + 2 * r * s * 32 * 32) * 2) {     // the ring's share of the d-input window
-                    // both sweep operands by LDS-DMA: the weights packed to bf16 (the forward's layout) once per call
-                    hipLaunchKernelGGL(dcn_pack_weights_kernel, dim3(rr_cdiv((long)k * r * s * c / 4, 256)), dim3(256), 0, stream, w, wpk, k, c,
-                                       r * s);
-                    wb.wpk = wpk;
-                    wb.goff_at = (int)ldsw;
-                    const size_t ldsd = ldsw + (((size_t)wb.w.WH * wb.w.WW * 4 + 15) & ~(size_t)15);
-                    RR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(dcn_dgrad_win_kernel<9, false, true>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsd), "rr_dcn_dgrad");
-                    hipLaunchKernelGGL((dcn_dgrad_win_kernel<9, false, true>), grid, dim3(512), ldsd, stream, wb);
-                    RR_CHECK_LAUNCH("rr_dcn_dgrad");
-                    return RR_OK;
-                }
-                hipFuncSetAttribute(reinterpret_cast<const void *>(dcn_dgrad_win_kernel<9, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw);
-                hipLaunchKernelGGL((dcn_dgrad_win_kernel<9, false>), grid, dim3(512), ldsw, stream, wb);
-            } else {
-                hipFuncSetAttribute(reinterpret_cast<const void *>(dcn_dgrad_win_kernel<9, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw);
-                hipLaunchKernelGGL((dcn_dgrad_win_kernel<9, true>), grid, dim3(512), ldsw, stream, wb);
-            }
-            RR_CHECK_LAUNCH("rr_dcn_dgrad");
-            return RR_OK;
-        }
+    if (pl.zero_dx) hipMemsetAsync(dx, 0, sizeof(float) * (size_t)g.n * g.h * g.w * g.c, stream);     // (every kernel below ADDS into dx with float atomics)
+    if (!pl.window) return dcn_launch(dcn_dgrad_kernel, pl.grid, 256, pl.lds, stream, "rr_dcn_dgrad", b);
+    DcnWinBwdArgs wb{};
+    wb.w = dcn_win_args(b.a, pl);
+    wb.dy = dy; wb.dx = dx; wb.doffset = doffset; wb.dmask = dmask;
+    if (pl.convert_dy) {
+        const long n4 = (long)pl.M * g.k / 4;
+        long cb = (n4 + 255) / 256;
+        if (cb > 256 * 32) cb = 256 * 32;
+        hipLaunchKernelGGL(dcn_to_bf16_kernel, dim3((int)cb), dim3(256), 0, stream, reinterpret_cast<const f32x4 *>(dy),
+                           reinterpret_cast<u16x4 *>(dyb), n4);
     }
-    RR_CHECK_ARG(deformable_groups == 1 || (c / deformable_groups) % 128 == 0,
-                 "rr_dcn_dgrad: channels per deformable group (%d) must be a multiple of 128 on the L2-gather kernel", c / deformable_groups);
-    const size_t lds = sizeof(float) * (2 * (BM * LDK + BK * 128) + BM * 8 + BM * 4 + BM * 3);
-    hipFuncSetAttribute(reinterpret_cast<const void *>(dcn_dgrad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(dcn_dgrad_kernel, dim3(rr_cdiv(b.a.M, BM)), dim3(256), lds, stream, b);
-    RR_CHECK_LAUNCH("rr_dcn_dgrad");
-    return RR_OK;
+    if (pl.dy_image) wb.dyb = dyb;
+    if (pl.dma_sweep) {       // the weights packed to bf16 (the forward's layout) once per call
+        dcn_pack_weights(w, wpk, g, stream);
+        wb.wpk = wpk;
+        wb.goff_at = pl.goff_at;
+    }
+    const auto kernel = pl.dma_sweep ? dcn_dgrad_win_kernel<9, false, true> : bf16 ? dcn_dgrad_win_kernel<9, false> : dcn_dgrad_win_kernel<9, true>;
+    return dcn_launch(kernel, pl.grid, 512, pl.lds, stream, "rr_dcn_dgrad", wb);
 }
 
 extern "C" int rr_dcn_dgrad(const float *x, const float *offset, const float *mask, const float *w, const float *dy,
                             float *dx, float *doffset, float *dmask, int n, int h, int wd, int c, int k, int r, int s,
                             int stride, int pad_h, int pad_w, int dilation, int deformable_groups, hipStream_t stream)
 {
-    return dcn_dgrad_impl(x, offset, mask, w, dy, dx, doffset, dmask, n, h, wd, c, k, r, s, stride, pad_h, pad_w, dilation,
-                          deformable_groups, 0, stream);
+    return dcn_dgrad_impl(x, offset, mask, w, dy, dx, doffset, dmask, RR_DCN_GEOM, false, stream);
 }
 
 // The same gradients with bf16 matrix operands (dY and W rounded to bf16 for the column-gradient GEMM, fp32 accumulation,
@@ -2686,8 +2405,7 @@ extern "C" int rr_dcn_dgrad_bf16(const float *x, const float *offset, const floa
                                  float *dx, float *doffset, float *dmask, int n, int h, int wd, int c, int k, int r, int s,
                                  int stride, int pad_h, int pad_w, int dilation, int deformable_groups, hipStream_t stream)
 {
-    return dcn_dgrad_impl(x, offset, mask, w, dy, dx, doffset, dmask, n, h, wd, c, k, r, s, stride, pad_h, pad_w, dilation,
-                          deformable_groups, 1, stream);
+    return dcn_dgrad_impl(x, offset, mask, w, dy, dx, doffset, dmask, RR_DCN_GEOM, true, stream);
 }
 
 extern "C" size_t rr_dcn_dyb_bytes(int n, int p, int q, int k)
@@ -2700,8 +2418,7 @@ extern "C" int rr_dcn_dgrad_bf16_ws(const float *x, const float *offset, const f
                                     int stride, int pad_h, int pad_w, int dilation, int deformable_groups, void *dyb,
                                     hipStream_t stream)
 {
-    return dcn_dgrad_impl(x, offset, mask, w, dy, dx, doffset, dmask, n, h, wd, c, k, r, s, stride, pad_h, pad_w, dilation,
-                          deformable_groups, 1, stream, static_cast<unsigned short *>(dyb));
+    return dcn_dgrad_impl(x, offset, mask, w, dy, dx, doffset, dmask, RR_DCN_GEOM, true, stream, static_cast<unsigned short *>(dyb));
 }
 
 // dy_bf16: dY's bf16 image as its producer left it (same element order as dy; csrc/conv16.hip's contract) — no conversion pass
@@ -2711,8 +2428,7 @@ extern "C" int rr_dcn_dgrad_bf16_img(const float *x, const float *offset, const 
                                      int deformable_groups, hipStream_t stream)
 {
     RR_CHECK_ARG(dy_bf16 != nullptr, "rr_dcn_dgrad_bf16_img: the bf16 image of dy is required");
-    return dcn_dgrad_impl(x, offset, mask, w, dy, dx, doffset, dmask, n, h, wd, c, k, r, s, stride, pad_h, pad_w, dilation,
-                          deformable_groups, 1, stream, const_cast<unsigned short *>(dy_bf16), true);
+    return dcn_dgrad_impl(x, offset, mask, w, dy, dx, doffset, dmask, RR_DCN_GEOM, true, stream, const_cast<unsigned short *>(dy_bf16), true);
 }
 
 // Workspace of rr_dcn_dgrad_bf16_packed: the weights packed to bf16, then (when the caller has no bf16 image of dY) dY in bf16
@@ -2732,9 +2448,37 @@ extern "C" int rr_dcn_dgrad_bf16_packed(const float *x, const float *offset, con
     const size_t wbytes = ((size_t)c * k * r * s * sizeof(unsigned short) + 255) & ~(size_t)255;
     unsigned short *dyb = dy_bf16 ? const_cast<unsigned short *>(dy_bf16)
                                   : reinterpret_cast<unsigned short *>(static_cast<unsigned char *>(ws) + wbytes);
-    return dcn_dgrad_impl(x, offset, mask, w, dy, dx, doffset, dmask, n, h, wd, c, k, r, s, stride, pad_h, pad_w, dilation,
-                          deformable_groups, 1, stream, dyb, dy_bf16 != nullptr, wpk, accumulate != 0);
+    return dcn_dgrad_impl(x, offset, mask, w, dy, dx, doffset, dmask, RR_DCN_GEOM, true, stream, dyb, dy_bf16 != nullptr, wpk, accumulate != 0);
 }
+
+// the plans of dcn_plan.h as the entry points above ask them, for tests/test_host_logic.py
+extern "C" int rr_dcn_plan(int pass, int bf16, int n, int h, int wd, int c, int k, int r, int s, int stride, int pad_h, int pad_w,
+                           int dilation, int deformable_groups, int margin, int flags, int *out, int n_out)
+{
+    using namespace rr_plan;
+    RR_CHECK_ARG(pass >= DCN_FWD && pass <= DCN_DGRAD && (flags & ~15) == 0 && out != nullptr && n_out >= RR_DCN_PLAN_INTS,
+                 "rr_dcn_plan: bad arguments");
+    const DcnGeom g RR_DCN_GEOM;
+    if (margin < 0) margin = dcn_win_margin();
+    DcnPlanHead hd;
+    int own[8] = {};
+    if (pass == DCN_FWD) {
+        const DcnFwdPlan p = dcn_fwd_plan(g, bf16 != 0, flags, margin);
+        hd = p; own[0] = p.wbn; own[1] = p.bn; own[2] = p.pack;
+    } else if (pass == DCN_WGRAD) {
+        const DcnWgradPlan p = dcn_wgrad_plan(g, bf16 != 0, flags, margin);
+        hd = p; own[0] = p.dy_dma; own[1] = p.ktiles; own[2] = p.per_split; own[3] = p.splits; own[4] = p.dma_window; own[5] = p.mt;
+        own[6] = p.nt; own[7] = p.chunks_per_split;
+    } else {
+        const DcnDgradPlan p = dcn_dgrad_plan(g, bf16 != 0, flags, margin);
+        hd = p; own[0] = p.zero_dx; own[1] = p.dy_image; own[2] = p.convert_dy; own[3] = p.dma_sweep; own[4] = p.goff_at;
+    }
+    RR_CHECK_ARG(hd.refuse == nullptr, hd.refuse, hd.a0, hd.a1);
+    const int head[8] = {hd.window, hd.margin, hd.WH, hd.WW, hd.tiles_y, hd.tiles_x, hd.grid, hd.lds};
+    for (int i = 0; i < 8; ++i) { out[i] = head[i]; out[8 + i] = own[i]; }
+    return RR_OK;
+}
+#undef RR_DCN_GEOM
 
 extern "C" int rr_dcn_split_fwd(const float *om, long m, int third, float *offset, float *mask, hipStream_t stream)
 {

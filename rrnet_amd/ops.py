@@ -1808,9 +1808,8 @@ def dcn_dgrad(x, offset, mask, w, dy, stride, pad, dilation, dg, bf16=False, out
                                                _C.ptr(doff), _C.ptr(dmask), n, h, wd, c, k, r, s, stride, pad[0], pad[1],
                                                dilation, dg, _C.ptr(dyb), _C.stream()), "rr_dcn_dgrad_bf16_ws")
         return dx, doff, dmask
-    name = "rr_dcn_dgrad_bf16" if bf16 else "rr_dcn_dgrad"
-    _C.check(_C.fn(name)(_C.ptr(x), _C.ptr(offset), _C.ptr(mask), _C.ptr(w), _C.ptr(dy), _C.ptr(dx), _C.ptr(doff),
-                         _C.ptr(dmask), n, h, wd, c, k, r, s, stride, pad[0], pad[1], dilation, dg, _C.stream()), name)
+    _C.check(_C.fn("rr_dcn_dgrad")(_C.ptr(x), _C.ptr(offset), _C.ptr(mask), _C.ptr(w), _C.ptr(dy), _C.ptr(dx), _C.ptr(doff),
+                                   _C.ptr(dmask), n, h, wd, c, k, r, s, stride, pad[0], pad[1], dilation, dg, _C.stream()), "rr_dcn_dgrad")
     return dx, doff, dmask
 
 

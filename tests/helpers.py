@@ -837,6 +837,147 @@ def conv_grid_routes():
     return seen
 
 
+# ---- how a deformable convolution launches: a restatement of the host code of rrnet_amd/csrc/dcn.hip -------------------------------
+# Written from dcn.hip as it stood BEFORE csrc/dcn_plan.h existed — fill_args, dcn_fwd_win and the two rr_dcn_fwd* tails,
+# dcn_wgrad_win / dcn_wgrad_plain, dcn_dgrad_impl, function by function — and kept by hand: tests/test_host_logic.py holds the
+# library's plans (rr_dcn_plan) against it field by field.
+DCN_FWD, DCN_WGRAD, DCN_DGRAD = 0, 1, 2                                    # the pass argument of rr_dcn_plan
+DCN_HAS_WPACK, DCN_HAS_DYB, DCN_DYB_READY, DCN_ACCUMULATE = 1, 2, 4, 8     # its flags
+_DCN_HEAD = ("window", "margin", "WH", "WW", "tiles_y", "tiles_x", "grid", "lds")
+DCN_PLAN_FIELDS = {DCN_FWD: _DCN_HEAD + ("wbn", "bn", "pack"),
+                   DCN_WGRAD: _DCN_HEAD + ("dy_dma", "ktiles", "per_split", "splits", "dma_window", "mt", "nt", "chunks_per_split"),
+                   DCN_DGRAD: _DCN_HEAD + ("zero_dx", "dy_image", "convert_dy", "dma_sweep", "goff_at")}
+DCN_PLAN_INTS = 16                                                          # RR_DCN_PLAN_INTS: 8 shared + up to 8 of the pass
+# what each entry point of a pass hands its plan: (bf16, flags)
+DCN_ENTRY_FLAGS = {
+    DCN_FWD: {"rr_dcn_fwd": (0, 0), "rr_dcn_fwd_bf16": (1, 0), "rr_dcn_fwd_bf16_packed": (1, DCN_HAS_WPACK)},
+    DCN_WGRAD: {"rr_dcn_wgrad": (0, 0), "rr_dcn_wgrad_bf16": (1, 0), "rr_dcn_wgrad_bf16_img": (1, DCN_HAS_DYB | DCN_DYB_READY)},
+    DCN_DGRAD: {"rr_dcn_dgrad": (0, 0), "rr_dcn_dgrad_bf16": (1, 0), "rr_dcn_dgrad_bf16_ws": (1, DCN_HAS_DYB),
+                "rr_dcn_dgrad_bf16_img": (1, DCN_HAS_DYB | DCN_DYB_READY),
+                "rr_dcn_dgrad_bf16_packed": (1, DCN_HAS_WPACK | DCN_HAS_DYB),
+                "rr_dcn_dgrad_bf16_packed+img": (1, DCN_HAS_WPACK | DCN_HAS_DYB | DCN_DYB_READY),
+                "rr_dcn_dgrad_bf16_packed+acc": (1, DCN_HAS_WPACK | DCN_HAS_DYB | DCN_ACCUMULATE),
+                "rr_dcn_dgrad_bf16_packed+img+acc": (1, DCN_HAS_WPACK | DCN_HAS_DYB | DCN_DYB_READY | DCN_ACCUMULATE)},
+}
+DCN_ROUTE_LABELS = {      # per pass: (fp32 operands, bf16 operands)
+    DCN_FWD: ({"window256", "window256:k>384", "window128", "gather128", "gather32", "margin_shrunk"},
+              {"window256+packed", "window256+packed:k>384", "window128", "gather128", "gather32", "margin_shrunk"}),
+    DCN_WGRAD: ({"window_f32", "gather", "refused"}, {"window_bf16", "window_dy_dma", "gather", "refused"}),
+    DCN_DGRAD: ({"window_f32", "gather", "refused"}, {"window_bf16_convert", "window_bf16_image", "window_dma", "gather", "refused"}),
+}
+
+
+def _c_div(a, b):
+    """a / b as C divides ints (towards zero), b > 0."""
+    return a // b if a >= 0 else -((-a) // b)
+
+
+def dcn_plan_mirror(pas, bf16, geo, margin, flags=0):
+    """What the entry points of dcn.hip did with geo = (n, c, h, w, k, r, s, stride, pad_h, pad_w, dilation, groups) at window margin
+    `margin` (RR_DCN_WINDOW) -> {every name of DCN_PLAN_FIELDS[pas]: int, "labels": set}, or None where the call was refused."""
+    n, c, h, w, k, r, s, stride, ph, pw, dil, dg = geo
+    two_gib, budget = 1 << 31, 160 * 1024 - 512
+    # fill_args
+    if min(n, h, w, c, k, r, s, stride, dil, dg) <= 0 or c % 4 or c % dg or (dg != 1 and (c // dg) % 32):
+        return None
+    p, q = _c_div(h + 2 * ph - (dil * (r - 1) + 1), stride) + 1, _c_div(w + 2 * pw - (dil * (s - 1) + 1), stride) + 1
+    m_out = n * p * q
+    if p <= 0 or q <= 0 or m_out >= two_gib:
+        return None
+    plan = dict.fromkeys(DCN_PLAN_FIELDS[pas], 0)
+    labels = set()
+    cpg = c // dg
+    wpack, dyb, ready = bool(flags & DCN_HAS_WPACK), bool(flags & DCN_HAS_DYB), bool(flags & DCN_DYB_READY)
+
+    def window(rw):
+        return 8 + (r - 1) * dil + 2 * rw + 1, 16 + (s - 1) * dil + 2 * rw + 1
+
+    def take_window(rw, lds):
+        wh, ww = window(rw)
+        plan.update(window=1, margin=rw, WH=wh, WW=ww, tiles_y=_cdiv(p, 8), tiles_x=_cdiv(q, 16), lds=lds)
+
+    if pas == DCN_FWD:
+        wbn, bn = (256 if (k % 256 == 0 or k > 384) else 128), (128 if k > 32 else 32)
+        plan.update(wbn=wbn, bn=bn)
+        if margin > 0 and stride == 1 and k > 32 and c % 32 == 0 and h * w < (1 << 30):            # dcn_fwd_win
+            for rw in range(margin, 0, -1):
+                wh, ww = window(rw)
+                lds = wh * ww * 32 * 4 + 128 * r * s * 4 * 8 + 2 * 2 * (128 * 40 + wbn * 40)
+                if wh * ww <= 14 * 32 and lds <= budget:
+                    take_window(rw, lds)
+                    plan["grid"] = n * plan["tiles_y"] * plan["tiles_x"] * _cdiv(k, wbn)
+                    # rr_dcn_fwd_bf16_packed hands the workspace on only under these limits; the window launch packs at 256 columns
+                    plan["pack"] = int(wbn == 256 and bool(bf16) and wpack and c % 32 == 0 and k * r * s * c * 2 < two_gib)
+                    labels.add(("window%d" % wbn) + ("+packed" if plan["pack"] else "") + (":k>384" if wbn == 256 and k % 256 else ""))
+                    if rw < margin:
+                        labels.add("margin_shrunk")
+                    return dict(plan, labels=labels)
+        plan["grid"] = _cdiv(m_out, 128) * _cdiv(k, bn)                                               # the tails of rr_dcn_fwd / _bf16
+        plan["lds"] = 2 * 2 * (128 * 40 + bn * 40) if bf16 else 4 * 2 * (128 * 36 + bn * 36)
+        return dict(plan, labels={"gather%d" % bn})
+
+    if pas == DCN_WGRAD:
+        if (margin > 0 and stride == 1 and r * s == 9 and c % 32 == 0 and k % 4 == 0 and h < 32768 and w < 32768
+                and (dg == 1 or cpg % 32 == 0)):                                                      # dcn_wgrad_win
+            dydma = bool(bf16) and dyb and k % 32 == 0 and m_out * k * 2 < two_gib and n * h * w * c * 4 < two_gib
+            for rw in range(margin, 0, -1):
+                wh, ww = window(rw)
+                lds = 4 * (wh * ww * 32 + 128 * r * s * 4) + 2 * ((256 + r * s * 32) * 72)
+                if dydma:
+                    lds = lds - 2 * ((256 + r * s * 32) * 72) + 2 * (8 * 6 * 512 + r * s * 64 * 32)
+                if lds <= budget:
+                    take_window(rw, lds)
+                    ntiles = n * plan["tiles_y"] * plan["tiles_x"]
+                    ktiles = _cdiv(k, 256)
+                    per_split = (c // 32) * ktiles
+                    splits = _cdiv(256, per_split)
+                    if splits > 8:
+                        splits = splits // 8 * 8
+                    splits = min(splits, ntiles)
+                    plan.update(dy_dma=int(dydma), ktiles=ktiles, per_split=per_split, splits=splits, grid=splits * per_split,
+                                dma_window=int(n * h * w * c * 4 < two_gib))
+                    return dict(plan, labels={"window_dy_dma" if dydma else ("window_bf16" if bf16 else "window_f32")})
+        if k % 4 or (dg != 1 and cpg % 128):                                                          # dcn_wgrad_plain
+            return None
+        mt, nt = _cdiv(k, 128), _cdiv(c, 128)
+        tiles, chunks = mt * nt * r * s, _cdiv(m_out, 32)
+        splits = 512 // tiles if tiles < 512 else 1
+        splits = max(1, min(splits, _cdiv(chunks, 8)))
+        per = _cdiv(chunks, splits)
+        splits = _cdiv(chunks, per)
+        plan.update(mt=mt, nt=nt, splits=splits, chunks_per_split=per, grid=tiles * splits, lds=4 * 2 * (32 * 128 + 32 * 128))
+        return dict(plan, labels={"gather"})
+
+    # dcn_dgrad_impl
+    if k % 4 or n * h * w >= two_gib:
+        return None
+    plan["zero_dx"] = int(not flags & DCN_ACCUMULATE)
+    if margin > 0 and stride == 1 and c % 32 == 0 and h < 32768 and w < 32768 and (dg == 1 or cpg % 32 == 0):
+        for rw in range(margin, 0, -1):
+            wh, ww = window(rw)
+            npx = wh * ww
+            opa = max(128 * 40 + r * s * 32 * 40, 2 * 128 * 32 + r * s * 32 * 32)
+            lds = 4 * (((npx * 33 + 3) & ~3) + 128 * r * s * 7 + npx * 32) + 2 * opa
+            if lds <= budget:
+                break
+        if r * s == 9 and lds <= budget:
+            take_window(rw, lds)
+            plan["grid"] = n * plan["tiles_y"] * plan["tiles_x"]
+            if not bf16:
+                return dict(plan, labels={"window_f32"})
+            plan["dy_image"] = int(dyb)                        # (k % 4 == 0 here: what is not ready is converted)
+            plan["convert_dy"] = int(dyb and not ready)
+            if (dyb and wpack and k % 32 == 0 and m_out * k * 2 < two_gib and n * h * w * c * 4 < two_gib and npx <= 368
+                    and lds + npx * 4 + 16 <= budget and npx * 33 * 4 >= (128 * 32 + 2 * r * s * 32 * 32) * 2):
+                plan.update(dma_sweep=1, goff_at=lds, lds=lds + ((npx * 4 + 15) & ~15))
+                return dict(plan, labels={"window_dma"})
+            return dict(plan, labels={"window_bf16_image" if (dyb and ready) else ("window_bf16_convert" if dyb else "window_bf16_fp32dy")})
+    if dg != 1 and cpg % 128:
+        return None
+    plan.update(grid=_cdiv(m_out, 128), lds=4 * (2 * (128 * 36 + 32 * 128) + 128 * 8 + 128 * 4 + 128 * 3))
+    return dict(plan, labels={"gather"})
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # The bf16 and f16x3 convolutions of csrc/conv_bf16.hip against float64 (tests/test_conv_lowp_fp64_gpu.py; the promises made
 # here are checked by tests/test_host_logic.py).  The contract defines each operand's IMAGE — bf16: the value rounded to nearest

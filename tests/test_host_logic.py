@@ -827,3 +827,173 @@ def test_lowp_acceptance_rule_rejects_modelled_kernel_faults():
     assert set(ran) == {"faithful", "no hi*lo", "unrounded operand", "operand rounded twice", "last K-step skipped", "last K-step skipped (partial)",
                         "column tiles swapped", "stale parity class"}, ran
     assert all(v >= 2 for name, v in ran.items() if "partial" not in name and name != "last K-step skipped"), ran
+
+
+# ---- the launch plans of the deformable convolutions (csrc/dcn_plan.h) ------------------------------------------------------------
+_DCN_BENCH_LAYER = (8, 256, 256, 256, 256, 3, 3, 1, 1, 1, 1, 1)             # bench.py's config4 head layer
+
+
+def _dcn_geo(cfg):
+    """(N, C, H, W, K, ksize, stride, pad, dil, dg) of tests/test_dcn_gpu.py -> the geometry dcn_plan_mirror takes."""
+    n, c, h, w, k, ks, stride, pad, dil, dg = cfg
+    return (n, c, h, w, k, ks, ks, stride, pad, pad, dil, dg)
+
+
+def _dcn_gpu_test_shapes():
+    """test_dcn_gpu.CASES and the shapes of its other parametrised tests -> ([geometry of every CASES entry], [(test, geometry)])."""
+    import test_dcn_gpu as t
+
+    def params(fn):
+        return [m.args[1] for m in fn.pytestmark if m.name == "parametrize"][0]
+    others = [("bf16_dgrad", (n, c, h, w, k, 3, 3, 1, 1, 1, 1, dg)) for n, c, h, w, k, dg in params(t.test_dcn_bf16_dgrad_equals_fp32_dgrad_on_rounded_operands)]
+    others += [("bf16_wgrad", (n, c, h, w, k, 3, 3, 1, 1, 1, 1, dg)) for n, c, h, w, k, dg, _ in params(t.test_dcn_bf16_wgrad_equals_gemm_of_rounded_operands)]
+    others.append(("column_path", (2, 256, 24, 40, 256, 3, 3, 1, 1, 1, 1, 1)))
+    return [_dcn_geo(cfg) for cfg in t.CASES], others
+
+
+def _dcn_plan_of_library(pas, bf16, geo, margin, flags):
+    """rr_dcn_plan -> {field: int} or None where the library refuses (a refusal must come with a reason)."""
+    import ctypes
+    from helpers import DCN_PLAN_FIELDS, DCN_PLAN_INTS
+    from rrnet_amd import _C
+    buf = (ctypes.c_int * DCN_PLAN_INTS)(*([-7] * DCN_PLAN_INTS))
+    n, c, h, w, k, r, s, stride, ph, pw, dil, dg = geo
+    rc = _C.fn("rr_dcn_plan")(pas, bf16, n, h, w, c, k, r, s, stride, ph, pw, dil, dg, margin, flags, buf, DCN_PLAN_INTS)
+    if rc != 0:
+        assert _C.lib().rr_last_error().decode().startswith("rr_dcn"), (geo, _C.lib().rr_last_error())
+        return None
+    names = DCN_PLAN_FIELDS[pas]
+    own = names[8:]
+    assert all(v == 0 for v in buf[8 + len(own):]), (pas, list(buf))
+    return dict(zip(names, list(buf[:8]) + list(buf[8:8 + len(own)])))
+
+
+def test_dcn_library_plans_equal_the_mirror():
+    """rr_dcn_plan — the three plans of rrnet_amd/csrc/dcn_plan.h that every rr_dcn_* entry point launches from — equals
+    helpers.dcn_plan_mirror, the Python restatement of the host code that preceded the header, field by field: for every entry of
+    test_dcn_gpu.CASES, the shapes of its other parametrised tests, bench.py's config-4 layer, shapes at the 2 GiB / 2^30 / 32768
+    limits and 2400 seeded random shapes (dilation 1-4; 3x3, 5x5 and 1x1 filters; stride 1 and 2; 1, 2 and 4 groups), in both
+    precisions, with every flag combination an entry point can produce and at margins 0, 1, 2 and 3.  What the library refuses, the
+    mirror refuses; fewer than half of the random draws are refused in any pass."""
+    import numpy as np
+    from helpers import DCN_DGRAD, DCN_ENTRY_FLAGS, DCN_FWD, DCN_PLAN_FIELDS, DCN_WGRAD, dcn_plan_mirror
+    cases_geo, others = _dcn_gpu_test_shapes()
+    shapes = [("case", g) for g in cases_geo] + others + [("bench", _DCN_BENCH_LAYER)]
+    shapes += [("limit", g) for g in (
+        (8, 64, 2048, 2048, 64, 3, 3, 1, 1, 1, 1, 1),          # x above 2 GiB: no window DMA, no dY DMA, no DMA sweep
+        (1, 32, 32768, 16, 64, 3, 3, 1, 1, 1, 1, 1),           # h == 32768: the backward windows step aside
+        (1, 32, 16, 32768, 64, 3, 3, 1, 1, 1, 1, 2),
+        (1, 32, 40000, 30000, 64, 3, 3, 1, 1, 1, 1, 1),        # h * w >= 2^30: the forward window steps aside
+        (2, 32, 40000, 30000, 64, 3, 3, 1, 1, 1, 1, 1),        # too many output pixels
+        (4, 4, 30000, 20000, 64, 3, 3, 1, 1, 1, 1, 1),         # n * h * w >= 2^31: the data gradient refuses
+        (1, 2048, 8, 16, 65536, 3, 3, 1, 1, 1, 1, 1),          # packed weights of 2 GiB and more
+        (16, 32, 1024, 1024, 128, 3, 3, 1, 1, 1, 1, 1),        # dY's bf16 image of 2 GiB and more
+        (1, 64, 2, 2, 64, 5, 5, 2, 0, 0, 1, 1),                # the filter does not fit (C divides towards zero)
+        (1, 30, 9, 9, 64, 3, 3, 1, 1, 1, 1, 1), (1, 64, 9, 9, 64, 3, 3, 1, 1, 1, 1, 4), (1, 96, 9, 9, 30, 3, 3, 1, 1, 1, 1, 3))]
+    rng = np.random.default_rng(355)
+    chans, filts = (8, 16, 32, 64, 96, 128, 160, 256, 384, 512), (4, 12, 30, 32, 36, 64, 96, 132, 256, 260, 388, 512)
+    for i in range(2400):
+        ks = (3, 3, 3, 5, 1)[rng.integers(5)]
+        shapes.append(("random%d" % i, (int(rng.integers(1, 5)), chans[rng.integers(10)], int(rng.integers(1, 71)), int(rng.integers(1, 71)),
+                                        filts[rng.integers(12)], ks, ks, int(rng.integers(1, 3)), int(rng.integers(0, 4)), int(rng.integers(0, 4)),
+                                        int(rng.integers(1, 5)), (1, 1, 2, 4)[rng.integers(4)])))
+    n_random = sum(src.startswith("random") for src, _ in shapes)
+    assert n_random >= 2000
+    seen = {pas: set() for pas in (DCN_FWD, DCN_WGRAD, DCN_DGRAD)}
+    refused_at_3 = dict.fromkeys(seen, 0)
+    for src, geo in shapes:
+        for pas in seen:
+            for margin in (0, 1, 2, 3):
+                for bf16 in (0, 1):
+                    for flags in sorted({f for _, f in DCN_ENTRY_FLAGS[pas].values()}):
+                        want = dcn_plan_mirror(pas, bf16, geo, margin, flags)
+                        got = _dcn_plan_of_library(pas, bf16, geo, margin, flags)
+                        if want is None or got is None:
+                            assert want is None and got is None, (src, geo, pas, bf16, margin, flags, got, want)
+                            continue
+                        assert got == {name: want[name] for name in DCN_PLAN_FIELDS[pas]}, (src, geo, pas, bf16, margin, flags, got, want)
+                        seen[pas] |= want["labels"]
+            refused_at_3[pas] += src.startswith("random") and dcn_plan_mirror(pas, 0, geo, 3, 0) is None
+    assert all(v < n_random // 2 for v in refused_at_3.values()), (refused_at_3, n_random)
+    assert refused_at_3[DCN_FWD] < refused_at_3[DCN_WGRAD] <= refused_at_3[DCN_DGRAD]        # the forward refuses dimensions only
+    assert seen[DCN_FWD] == {"window256", "window256+packed", "window256:k>384", "window256+packed:k>384", "window128", "gather128", "gather32",
+                             "margin_shrunk"}
+    assert seen[DCN_WGRAD] == {"window_f32", "window_bf16", "window_dy_dma", "gather"}
+    assert seen[DCN_DGRAD] == {"window_f32", "window_bf16_fp32dy", "window_bf16_convert", "window_bf16_image", "window_dma", "gather"}
+    # margin < 0 asks with the library's own margin (RR_DCN_WINDOW, 3 when unset)
+    import os
+    own = int(os.environ.get("RR_DCN_WINDOW", "3"))
+    assert _dcn_plan_of_library(DCN_DGRAD, 1, _DCN_BENCH_LAYER, -1, 7) == _dcn_plan_of_library(DCN_DGRAD, 1, _DCN_BENCH_LAYER, own, 7)
+
+
+def test_dcn_fused_bwd_supported_answers_as_recorded(golden_dir):
+    """rr_dcn_fused_bwd_supported_dil — now "both backward plans of csrc/dcn_plan.h accept the shape" — answers exactly as the
+    predicate it replaced did: tests/golden/dcn_bwd_supported.json holds that predicate's answers over 3360 layer shapes, recorded
+    from the library of the commit before the header.  The same answers follow from the mirror's two backward plans."""
+    import json
+    import os
+    import pytest
+    from helpers import DCN_DGRAD, DCN_WGRAD, dcn_plan_mirror
+    from rrnet_amd import _C
+    if int(os.environ.get("RR_DCN_WINDOW", "3")) != 3:
+        pytest.skip("the answers were recorded with the default window margin")
+    with open(os.path.join(golden_dir, "dcn_bwd_supported.json")) as fh:
+        doc = json.load(fh)
+    ax = doc["axes"]
+    assert doc["order"] == ["c", "k", "filter", "stride", "dilation", "groups"]
+    fn = _C.fn("rr_dcn_fused_bwd_supported_dil")
+    got, mirrored = [], []
+    for c in ax["c"]:
+        for k in ax["k"]:
+            for f in ax["filter"]:
+                for st in ax["stride"]:
+                    for d in ax["dilation"]:
+                        for g in ax["groups"]:
+                            got.append(str(int(fn(c, k, f, f, st, d, g))))
+                            geo = (1, c, d * (f - 1) + 1, d * (f - 1) + 1, k, f, f, st, 0, 0, d, g)
+                            mirrored.append(str(int(all(dcn_plan_mirror(pas, 0, geo, 3) is not None for pas in (DCN_WGRAD, DCN_DGRAD)))))
+    assert len(got) == 3360 == len(doc["answers"])
+    assert "".join(got) == doc["answers"]
+    assert "".join(mirrored) == doc["answers"]
+    assert 0 < doc["answers"].count("1") < 3360
+    assert _C.fn("rr_dcn_fused_bwd_supported")(64, 64, 3, 3, 1, 2) == fn(64, 64, 3, 3, 1, 1, 2) == 1
+
+
+def test_dcn_gpu_shapes_reach_every_route():
+    """Every route label the three plans can produce (helpers.DCN_ROUTE_LABELS, per operand precision) is reached by a call
+    tests/test_dcn_gpu.py makes, with the flags that call's entry point hands its plan: CASES through functional.dcn_v2_conv in
+    fp32 and in bf16 (forward packed; backward with dY's bf16 image, the data gradient packed — only where both backward plans
+    accept the layer, the column path runs otherwise and the refusing plan counts as `refused`), and the shapes of the tests that
+    call ops.dcn_dgrad / ops.dcn_wgrad directly.  The plans are the library's (equal to the mirror, as checked above)."""
+    from helpers import (DCN_DGRAD, DCN_DYB_READY, DCN_FWD, DCN_HAS_DYB, DCN_HAS_WPACK, DCN_ROUTE_LABELS, DCN_WGRAD, dcn_plan_mirror)
+    cases_geo, others = _dcn_gpu_test_shapes()
+    seen = {(pas, bf): set() for pas in (DCN_FWD, DCN_WGRAD, DCN_DGRAD) for bf in (0, 1)}
+
+    def call(pas, bf16, geo, flags):
+        want = dcn_plan_mirror(pas, bf16, geo, 3, flags)
+        assert (want is None) == (_dcn_plan_of_library(pas, bf16, geo, 3, flags) is None)
+        return want
+    img = DCN_HAS_DYB | DCN_DYB_READY
+    for geo in cases_geo:
+        for bf in (0, 1):
+            seen[DCN_FWD, bf] |= call(DCN_FWD, bf, geo, DCN_HAS_WPACK if bf else 0)["labels"]
+            plans = {DCN_WGRAD: call(DCN_WGRAD, bf, geo, img if bf else 0), DCN_DGRAD: call(DCN_DGRAD, bf, geo, (DCN_HAS_WPACK | img) if bf else 0)}
+            fused = all(call(pas, 0, geo, 0) is not None for pas in plans)            # ops.dcn_fused_bwd_supported
+            for pas, pl in plans.items():
+                if pl is None:
+                    seen[pas, bf].add("refused")
+                elif fused:
+                    seen[pas, bf] |= pl["labels"]
+    for test, geo in others:
+        if test == "bf16_dgrad":          # fp32, rr_dcn_dgrad_bf16_packed without an image, then rr_dcn_dgrad_bf16_ws
+            seen[DCN_DGRAD, 0] |= call(DCN_DGRAD, 0, geo, 0)["labels"]
+            seen[DCN_DGRAD, 1] |= call(DCN_DGRAD, 1, geo, DCN_HAS_WPACK | DCN_HAS_DYB)["labels"] | call(DCN_DGRAD, 1, geo, DCN_HAS_DYB)["labels"]
+        elif test == "bf16_wgrad":        # rr_dcn_wgrad_bf16, rr_dcn_wgrad_bf16_img, rr_dcn_wgrad
+            seen[DCN_WGRAD, 1] |= call(DCN_WGRAD, 1, geo, 0)["labels"] | call(DCN_WGRAD, 1, geo, img)["labels"]
+            seen[DCN_WGRAD, 0] |= call(DCN_WGRAD, 0, geo, 0)["labels"]
+        else:
+            for pas in (DCN_FWD, DCN_WGRAD, DCN_DGRAD):
+                seen[pas, 0] |= call(pas, 0, geo, 0)["labels"]
+    for (pas, bf), labels in seen.items():
+        missing = sorted(DCN_ROUTE_LABELS[pas][bf] - labels)
+        assert not missing, "pass %d, %s: route labels no shape of test_dcn_gpu.py reaches: %s" % (pas, ("fp32", "bf16")[bf], missing)
