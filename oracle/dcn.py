@@ -96,7 +96,14 @@ def dcn_columns(x, offset, mask, kh, kw, stride=1, padding=0, dilation=1, deform
 
 
 def _bf16_round(t):
-    return t.detach().to(torch.bfloat16).to(t.dtype)
+    t = t.detach()
+    if t.dtype == torch.float64:
+        # straight from the float64 value (nearest even on its bit pattern: 45 of the 52 fraction bits go; normal range): torch's
+        # conversion passes through float32 first, and that double rounding moves values next to a bf16 tie to the other side
+        b = t.contiguous().view(torch.int64)
+        b = (b + ((b >> 45) & 1) + ((1 << 44) - 1)) & ~((1 << 45) - 1)
+        return b.view(torch.float64)
+    return t.to(torch.bfloat16).to(t.dtype)
 
 
 class _ContractBf16(torch.autograd.Function):

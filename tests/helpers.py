@@ -1207,6 +1207,574 @@ def conv16_grid_labels(math):
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# The deformable convolutions of csrc/dcn.hip against float64 (tests/test_dcn_fp64_gpu.py; the promises made here are checked by
+# tests/test_host_logic.py).  Reference: oracle/dcn.py evaluated in float64 on the float32 inputs, the sample position formed by ONE
+# float32 addition as the kernels do (pos_fp32).  Yardstick: the same definition in float32 with every reduction chained in plain
+# loop order, minus the float64 result.  Acceptance: conv_accepts, margin DCN_MARGIN, plus two allowances restated from reference
+# quantities only — the fixed-point window of the data gradient (dcn_fixed_point_allowance) and bf16 column ties (dcn_tie_*).
+# ------------------------------------------------------------------------------------------------------------------
+DCN_MARGIN = 4                   # by the rule of CONV_MARGIN: the largest ratio of profiles/dcn_fp64_ratios.txt (an MI355X run of
+                                 # tests/test_dcn_fp64_gpu.py) is 2.07 — the 32-wide L2-gather forward, fp32, max-abs at the samples; every
+                                 # other tensor stays below 1.8 — rounded up to a power of two, not below 2
+DCN_TIE_BAND = 8 * U32           # a float32 blend errs by at most 7 roundings (taken up to 8) x 2^-24 x sum |w_e x_e| |mask|
+DCN_TIE_MAX = 10                 # outputs with more near-tie terms are left out (2^10 subsets are searched)
+DCN_TIE_LEFT_OUT = 0.01          # at most this share of a tensor may be left out
+DCN_TIE_CLEAN = 1.0 / 3.0        # at least this share of a tensor's sampled outputs has no near-tie term
+DCN_BLOCK = (8, 16)              # the output-pixel block of the window kernels
+DCN_FX_UNIT_LOG2 = -29           # one fixed-point unit <= bound * 2^-29 (dcn.hip: bound scaled into [2^29, 2^30))
+DCN_EDGE_CLASSES = ("gauss", "border", "exact", "beyond", "far", "pile", "operands")
+
+
+def bf16_rne64(a):
+    """float64 array -> the nearest bf16 value (ties to even) as float64, straight from the float64 bit pattern (normal range)."""
+    b = np.ascontiguousarray(a, np.float64).view(np.int64)
+    b = (b + ((b >> 45) & 1) + ((1 << 44) - 1)) & ~np.int64((1 << 45) - 1)
+    return b.view(np.float64)
+
+
+def dcn_out_hw(h, w, r, s, stride, ph, pw, dil):
+    return (h + 2 * ph - (dil * (r - 1) + 1)) // stride + 1, (w + 2 * pw - (dil * (s - 1) + 1)) // stride + 1
+
+
+def dcn_ref64(x, offset, mask, w, bias, stride, pad, dil, dg, gy=None, base_dx=None, bf16=False):
+    """oracle/dcn.py in float64 on the float32 inputs, pos_fp32=True -> {"out", "cols", and with gy: "dx", "doffset", "dmask", "dw",
+    "db"} as float64 numpy arrays.  bf16: the oracle's _ContractBf16 (columns, W and dY rounded to bf16 straight from float64).
+    base_dx: what an accumulating data gradient adds into."""
+    from oracle import dcn as odcn
+    ins = [None if t is None else torch.as_tensor(t).detach().cpu().double().clone().requires_grad_(gy is not None)
+           for t in (x, offset, mask, w, bias)]
+    k, _, r, s = ins[3].shape
+    with torch.no_grad():
+        cols = odcn.dcn_columns(ins[0], ins[1], ins[2], r, s, stride, pad, dil, dg, pos_fp32=True)
+    out = odcn.dcn_v2_conv(*ins, stride, pad, dil, dg, bf16=bf16, pos_fp32=True)
+    res = {"out": out.detach().numpy(), "cols": cols.numpy()}
+    if gy is not None:
+        out.backward(torch.as_tensor(gy).detach().cpu().double())
+        for name, t in zip(("dx", "doffset", "dmask", "dw", "db"), ins):
+            res[name] = None if t is None else t.grad.numpy()
+        if base_dx is not None:
+            res["dx"] = res["dx"] + _np64(base_dx)
+    return res
+
+
+def dcn_geometry(offset, h, w, r, s, stride, pad, dil, dg, dtype=np.float64, fault=None):
+    """The sampling geometry of every (n, group, tap, p, q): position = ONE float32 add of the integer grid position and the offset,
+    everything after it in `dtype`.  -> dict of arrays [n, dg, T, P, Q] (h, w, inside, lh, lw) and [4, n, dg, T, P, Q] per corner
+    e = 2 * (row + 1) + (col + 1): hy, wx (image coordinates), idx (clamped flat pixel), valid, wgt, dwh, dww (d wgt / d h, d w)."""
+    off = _np32(offset)
+    n, _, p, q = off.shape
+    t = r * s
+    off = off.reshape(n, dg, t, 2, p, q)
+    if fault == "swap_hw":
+        off = off[:, :, :, ::-1]
+    if fault == "group0":
+        off = np.broadcast_to(off[:, :1], off.shape)
+    ph, pw = (pad, pad) if isinstance(pad, int) else pad
+    ti, tj = np.divmod(np.arange(t), s)
+    bh = (np.arange(p)[None, :] * stride - ph + ti[:, None] * dil).astype(np.float32)
+    bw = (np.arange(q)[None, :] * stride - pw + tj[:, None] * dil).astype(np.float32)
+    hp = (bh[None, None, :, :, None] + off[:, :, :, 0]).astype(np.float32).astype(dtype)
+    wp = (bw[None, None, :, None, :] + off[:, :, :, 1]).astype(np.float32).astype(dtype)
+    if fault == "nonstrict":
+        inside = (hp >= -1) & (wp >= -1) & (hp <= h) & (wp <= w)
+    else:
+        inside = (hp > -1) & (wp > -1) & (hp < h) & (wp < w)
+    hf, wf = np.floor(hp), np.floor(wp)
+    lh, lw = hp - hf, wp - wf
+    one = dtype(1)
+    hh, hw = one - lh, one - lw
+    h0, w0 = np.clip(hf, -2, h + 1).astype(np.int64), np.clip(wf, -2, w + 1).astype(np.int64)
+    hy, wx = np.stack([h0, h0, h0 + 1, h0 + 1]), np.stack([w0, w0 + 1, w0, w0 + 1])
+    valid = inside[None] & (hy >= 0) & (hy <= h - 1) & (wx >= 0) & (wx <= w - 1)
+    return {"h": hp, "w": wp, "inside": inside, "lh": lh, "lw": lw, "hy": hy, "wx": wx, "valid": valid,
+            "idx": np.clip(hy, 0, h - 1) * w + np.clip(wx, 0, w - 1),
+            "wgt": np.stack([hh * hw, hh * lw, lh * hw, lh * lw]), "dwh": np.stack([-hw, -lw, hw, lw]),
+            "dww": np.stack([-hh, hh, -lh, lh]), "base_h": bh, "base_w": bw}
+
+
+def dcn_window(r, s, dil, margin):
+    """(WH, WW) of the LDS window at margin `margin` (dcn_plan_mirror's window())."""
+    return 8 + (r - 1) * dil + 2 * margin + 1, 16 + (s - 1) * dil + 2 * margin + 1
+
+
+def dcn_in_window(geo, r, s, pad, dil, margin):
+    """[4, n, dg, T, P, Q]: whether corner e lies in the LDS window of its output pixel's 8x16 block (stride 1; window pixel (0, 0)
+    is image pixel (y0 - pad_h - margin, x0 - pad_w - margin), as dcn.hip places it)."""
+    ph, pw = (pad, pad) if isinstance(pad, int) else pad
+    p, q = geo["inside"].shape[-2:]
+    wh, ww = dcn_window(r, s, dil, margin)
+    wy0 = (np.arange(p) // DCN_BLOCK[0] * DCN_BLOCK[0] - ph - margin)[:, None]
+    wx0 = (np.arange(q) // DCN_BLOCK[1] * DCN_BLOCK[1] - pw - margin)[None, :]
+    ly, lx = geo["hy"] - wy0, geo["wx"] - wx0
+    return (ly >= 0) & (ly < wh) & (lx >= 0) & (lx < ww)
+
+
+def _dcn_blocks(p, q):
+    by, bx = _cdiv(p, DCN_BLOCK[0]), _cdiv(q, DCN_BLOCK[1])
+    return by * bx, (np.arange(p)[:, None] // DCN_BLOCK[0]) * bx + np.arange(q)[None, :] // DCN_BLOCK[1]
+
+
+DCN_FAULTS = ("clamp", "nonstrict", "swap_hw", "group0", "beyond_margin", "tap_mask", "skip_chunk", "doffset_nomask",
+              "cols_unrounded", "round_before_mask", "dy_unrounded", "base_ignored", "fx_unit20")
+
+
+def dcn_model(x, offset, mask, w, bias, stride, pad, dil, dg, gy=None, base_dx=None, base_dw=None, dtype=np.float64, bf16=False,
+              fault=None, margin=3, dcol=None, blocks=False):
+    """The definition of the modulated deformable convolution and of its gradients written out in numpy, corner by corner, in `dtype`
+    (float64: equal to dcn_ref64, which tests/test_host_logic.py checks; float32: the float32 evaluation the modelled faults are
+    applied to).  fault: one of DCN_FAULTS.  dcol: a given column gradient [n, c, T, P, Q] (rr_dcn_col2im) instead of dY . W.
+    blocks: also "dx_blocks" [n, dg, blocks, H*W, cpg], d input summed per 8x16 output block.  -> dict of arrays."""
+    dt = dtype
+    xa, mk, wa = (_np32(t).astype(dt) for t in (x, mask, w))
+    n, c, h, wd = xa.shape
+    k, _, r, s = wa.shape
+    t, cpg = r * s, c // dg
+    geo = dcn_geometry(offset, h, wd, r, s, stride, pad, dil, dg, dt, fault)
+    p, q = geo["inside"].shape[-2:]
+    mk = mk.reshape(n, dg, t, p, q)
+    if fault == "tap_mask":
+        mk = mk.copy()
+        mk[:, :, t // 2] = 1
+    valid = geo["valid"]
+    if fault == "beyond_margin":
+        valid = valid & dcn_in_window(geo, r, s, pad, dil, margin)
+    read = np.broadcast_to(geo["inside"][None], valid.shape) if fault == "clamp" else valid
+    xg = xa.reshape(n, dg, cpg, h * wd)
+    xs = np.stack([np.take_along_axis(xg, geo["idx"][e].reshape(n, dg, 1, -1), axis=3).reshape(n, dg, cpg, t, p, q)
+                   * read[e][:, :, None].astype(dt) for e in range(4)])
+    wgt = geo["wgt"][:, :, :, None]
+    sample = (wgt * xs).sum(0, dtype=dt)
+    col = sample * mk[:, :, None]
+    rq = (lambda a: a) if not bf16 else (bf16_rne64 if dt == np.float64 else bf16_exact)
+    colq = col if fault == "cols_unrounded" else (rq(sample) * mk[:, :, None] if fault == "round_before_mask" and bf16 else rq(col))
+    w3 = rq(wa).reshape(k, c, t)
+    colf = colq.reshape(n, c, t, p, q)
+    live = slice(0, c - 32) if fault == "skip_chunk" else slice(None)            # the last 32-channel chunk never runs
+    out = np.einsum("nctpq,kct->nkpq", colf[:, live], w3[:, live], optimize=True)
+    if bias is not None:
+        out = out + _np32(bias).astype(dt).reshape(1, -1, 1, 1)
+    res = {"geo": geo, "xs": xs, "sample": sample, "col": col.reshape(n, c, t, p, q), "colq": colf, "w3": w3, "out": out, "mask": mk,
+           "absblend": (np.abs(wgt * xs).sum(0) * np.abs(mk[:, :, None])).reshape(n, c, t, p, q)}
+    if gy is None and dcol is None:
+        return res
+    if dcol is None:
+        ga = _np32(gy).astype(dt)
+        gq = ga if fault == "dy_unrounded" else rq(ga)
+        dcol = np.einsum("nkpq,kct->nctpq", gq, w3, optimize=True)
+        dw = np.einsum("nkpq,nctpq->kct", gq, colf, optimize=True)
+        if fault == "skip_chunk":
+            dcol[:, c - 32:] = 0
+            dw[:, c - 32:] = 0
+        if base_dw is not None and fault != "base_ignored":
+            dw = dw + _np32(base_dw).astype(dt).reshape(k, c, t)
+        res.update(gyq=gq, dw=dw.reshape(k, c, r, s), db=ga.sum((0, 2, 3)))
+    else:
+        dcol = np.asarray(dcol).astype(dt)
+    dcg = dcol.reshape(n, dg, cpg, t, p, q)
+    dsm = dcg * mk[:, :, None]
+    dsrc = dcg if fault == "doffset_nomask" else dsm
+    gh = (geo["dwh"][:, :, :, None] * xs).sum(0, dtype=dt)
+    gw = (geo["dww"][:, :, :, None] * xs).sum(0, dtype=dt)
+    res.update(dcol=dcol, dmask=(dcg * sample).sum(2, dtype=dt).reshape(n, dg * t, p, q),
+               doffset=np.stack([(dsrc * gh).sum(2, dtype=dt), (dsrc * gw).sum(2, dtype=dt)], 3).reshape(n, 2 * dg * t, p, q))
+    nb, blk = _dcn_blocks(p, q)
+    unit = None
+    if fault == "fx_unit20":
+        unit = _dcn_fx_units(geo, dcol, mk, h * wd, -20)[0]                       # [n, dg, cpg, nb]
+    part = np.zeros((n, dg, nb if blocks else 1, h * wd, cpg), dt)
+    bsel = np.broadcast_to(blk if blocks else np.zeros_like(blk), (t, p, q)).ravel()
+    for e in range(4):
+        ce = dsm * (geo["wgt"][e] * valid[e])[:, :, None].astype(dt)               # [n, dg, cpg, T, P, Q]
+        if unit is not None:
+            u = unit[:, :, :, blk][:, :, :, None]                                  # [n, dg, cpg, 1, P, Q]
+            ce = np.where(u > 0, np.round(ce / np.where(u > 0, u, 1)) * u, ce).astype(dt)
+        for i in range(n):
+            for g in range(dg):
+                np.add.at(part[i, g], (bsel, geo["idx"][e][i, g].ravel()), ce[i, g].reshape(cpg, -1).T)
+    dx = part.sum(2, dtype=dt).transpose(0, 1, 3, 2).reshape(n, c, h, wd)
+    if base_dx is not None and fault != "base_ignored":
+        dx = dx + _np32(base_dx).astype(dt)
+    res["dx"] = dx
+    if blocks:
+        res["dx_blocks"] = part
+    return res
+
+
+def _dcn_fx_units(geo, dcol, mk, npix, unit_log2=DCN_FX_UNIT_LOG2):
+    """The fixed-point contract of the window data gradient from reference quantities: per (n, group, 8x16 output block) the hit count
+    of every image pixel (valid corners of the block's samples that land on it) and its maximum, the block's largest |dcol| per
+    channel and largest |mask| -> (unit [n, dg, cpg, blocks] = maxhits * max|dcol| * max|mask| * 2^unit_log2, hits [n, dg, blocks, npix])."""
+    n, dg, t, p, q = geo["inside"].shape
+    c = dcol.shape[1]
+    nb, blk = _dcn_blocks(p, q)
+    hits = np.zeros((n, dg, nb, npix))
+    for e in range(4):
+        nn, gg, tt, pp, qq = np.nonzero(geo["valid"][e])
+        np.add.at(hits, (nn, gg, blk[pp, qq], geo["idx"][e][nn, gg, tt, pp, qq]), 1)
+    maxhits = np.maximum(hits.max(3), 1)
+    ad, am = np.abs(dcol).max(2), np.abs(mk).reshape(n, dg * t, p, q).max(1)
+    maxd, maxm = np.zeros((n, c, nb)), np.zeros((n, nb))
+    for b in range(nb):
+        maxd[:, :, b], maxm[:, b] = ad[:, :, blk == b].max(-1), am[:, blk == b].max(-1)
+    unit = maxhits[:, :, None] * maxd.reshape(n, dg, c // dg, nb) * maxm[:, None, None] * 2.0 ** unit_log2
+    return unit, hits
+
+
+def dcn_fixed_point_allowance(m64, base_dx=None):
+    """What the window data-gradient routes may add to a d-input element's error, from the float64 model m64 (dcn_model(..., blocks=
+    True)) alone: every contribution is rounded to nearest in its block's unit (half a unit each, hits x half a unit per block that
+    reaches the element) and each block's sum joins the element with one float32 add (2^-24 of the running magnitude, taken as the
+    sum of the blocks' |partial sums| and |base|).  -> (allowance [n, c, h, w], its fixed-point part alone)."""
+    geo, part = m64["geo"], m64["dx_blocks"]
+    n, dg, nb, npix, cpg = part.shape
+    unit, hits = _dcn_fx_units(geo, m64["dcol"], m64["mask"], npix)
+    fx = 0.5 * np.einsum("ngbx,ngcb->ngcx", hits, unit)
+    mag = np.abs(part).sum(2).transpose(0, 1, 3, 2)                                # [n, dg, cpg, npix]
+    shape = m64["dx"].shape
+    if base_dx is not None:
+        mag = mag + np.abs(_np64(base_dx)).reshape(mag.shape)
+    reach = (hits > 0).sum(2)[:, :, None]
+    return (fx + U32 * reach * mag).reshape(shape), fx.reshape(shape)
+
+
+def dcn_tie_info(m64):
+    """Near-tie columns of the float64 bf16 model m64: a float32 blend errs by at most DCN_TIE_BAND x sum |w_e x_e| |mask|, so a kernel's
+    column may round to the other bf16 neighbour where the float64 column lies within that band of the rounding boundary.
+    -> (near [n, c, T, P, Q] bool, alternative rounding - chosen rounding, float64)."""
+    col = m64["col"]
+    qv = bf16_rne64(col)
+    step = np.where(np.abs(col) > np.abs(qv), 1, -1).astype(np.int64) << 45
+    alt = np.where(qv == 0, qv, (qv.view(np.int64) + step).view(np.float64))
+    near = (qv != 0) & (np.abs(col - 0.5 * (qv + alt)) < DCN_TIE_BAND * m64["absblend"])
+    return near, alt - qv
+
+
+def dcn_tie_counts(kind, near, k):
+    """Near-tie terms per output of `kind`: "out" [n, k, P, Q] (the (c, tap) terms of a pixel), "dw" [k, c, T] (the (n, p, q) terms)."""
+    if kind == "out":
+        cnt = near.sum((1, 2))
+        return np.broadcast_to(cnt[:, None], (cnt.shape[0], k) + cnt.shape[1:])
+    cnt = near.sum((0, 3, 4))
+    return np.broadcast_to(cnt[None], (k,) + cnt.shape)
+
+
+def dcn_tie_deltas(kind, idx, near, alt_minus, other):
+    """delta_i = other operand x (alternative rounding - chosen rounding) of the near-tie terms of the sampled outputs idx, zero-padded
+    -> [S, DCN_TIE_MAX] (samples must hold at most DCN_TIE_MAX such terms).  other: w3 [k, c, T] for "out", dY's image [n, k, P, Q]
+    for "dw" (idx = (k, c, tap))."""
+    if kind == "out":
+        i0, i1, i2, i3 = idx
+        nr = near[i0, :, :, i2, i3].reshape(len(i0), -1)
+        dl = (alt_minus[i0, :, :, i2, i3] * other[i1]).reshape(len(i0), -1)
+    else:
+        i0, i1, i2 = idx
+        nr = near[:, i1, i2].transpose(1, 0, 2, 3).reshape(len(i0), -1)
+        dl = (alt_minus[:, i1, i2] * other[:, i0]).transpose(1, 0, 2, 3).reshape(len(i0), -1)
+    assert nr.sum(1).max() <= DCN_TIE_MAX
+    order = np.argsort(~nr, axis=1, kind="stable")[:, :DCN_TIE_MAX]
+    return np.take_along_axis(np.where(nr, dl, 0.0), order, 1)
+
+
+def dcn_tie_adjust(err, deltas):
+    """err [S] = got - ref; deltas [S, t] -> err - sum over the subset of deltas that leaves the smallest |.| (all 2^t are tried)."""
+    tmax = deltas.shape[1]
+    combos = ((np.arange(1 << tmax)[:, None] >> np.arange(tmax)) & 1).astype(np.float64)
+    cand = np.asarray(err, np.float64)[:, None] - deltas @ combos.T
+    return cand[np.arange(len(cand)), np.abs(cand).argmin(1)]
+
+
+def _chain32(terms):
+    return np.cumsum(np.asarray(terms).astype(np.float32), axis=1, dtype=np.float32)[:, -1].astype(np.float64)
+
+
+def dcn_chain_dcol(gy, w3):
+    """dcol [n, c, T, P, Q] = sum over k of dY x W chained in float32 in plain loop order (float32 array)."""
+    gy, w3 = np.asarray(gy, np.float64).astype(np.float32), np.asarray(w3, np.float64).astype(np.float32)
+    acc = np.zeros((gy.shape[0],) + w3.shape[1:] + gy.shape[2:], np.float32)
+    for k in range(w3.shape[0]):
+        acc += gy[:, k, None, None] * w3[k][None, :, :, None, None]
+    return acc
+
+
+def dcn_terms(kind, idx, y, chunk=1 << 24):
+    """The float32 terms of the sampled outputs idx of one tensor, in plain loop order: yields float64 arrays [s, terms] covering idx in
+    order.  y: the yardstick's operands — "col" [n, c, T, P, Q] (the float32 oracle's columns, or the bf16 images), "w3" [k, c, T],
+    "gy" [n, k, P, Q], "bias", "dcol" (dcn_chain_dcol), "m32" (dcn_model in float32: geometry, corner values, mask), "base_dx",
+    "base_dw".
+      "out"     idx (n, k, p, q): col x W over (c, tap), then bias
+      "dw"      idx (k, c, tap): base, then dY x col over (n, p, q)
+      "dmask"   idx (n, g T + tap, p, q): dcol x wgt_e x x_e over (c, corner)
+      "doffset" idx (n, g 2T + 2 tap + {0, 1}, p, q): dcol x mask x d wgt_e x x_e over (c, corner)
+      "dx"      idx (n, c, y, x): base, then dcol x mask x wgt_e over the (tap, p, q, corner) whose corner is that pixel"""
+    N = None
+    if kind == "out":
+        i0, i1, i2, i3 = idx
+        t = (y["col"][i0, :, :, i2, i3] * y["w3"][i1]).reshape(len(i0), -1)
+        tail = np.zeros(len(i0)) if y.get("bias") is None else _np64(y["bias"])[i1]
+        yield np.concatenate([t, tail[:, N]], 1)
+        return
+    if kind == "dw":
+        i0, i1, i2 = idx
+        t = (y["col"][:, i1, i2] * y["gy"][:, i0]).transpose(1, 0, 2, 3).reshape(len(i0), -1)
+        head = np.zeros(len(i0)) if y.get("base_dw") is None else _np64(y["base_dw"]).reshape(y["w3"].shape)[i0, i1, i2]
+        yield np.concatenate([head[:, N], t], 1)
+        return
+    m = y["m32"]
+    geo, xs, mk = m["geo"], m["xs"], m["mask"]
+    n, dg, cpg, t_all, p, q = xs.shape[1:]
+    dcg = y["dcol"].reshape(n, dg, cpg, t_all, p, q).astype(np.float64)
+    if kind in ("dmask", "doffset"):
+        i0, ch, i2, i3 = idx
+        if kind == "dmask":
+            g, tap = np.divmod(ch, t_all)
+            fac = geo["wgt"][:, i0, g, tap, i2, i3].astype(np.float64)                                  # [4, S]
+        else:
+            g, rest = np.divmod(ch, 2 * t_all)
+            tap, hw = np.divmod(rest, 2)
+            fac = np.where(hw == 0, geo["dwh"][:, i0, g, tap, i2, i3], geo["dww"][:, i0, g, tap, i2, i3]).astype(np.float64)
+            fac = fac * mk[i0, g, tap, i2, i3].astype(np.float64)
+        xv = xs[:, i0, g, :, tap, i2, i3].astype(np.float64)                                            # [S, 4, cpg]
+        yield (dcg[i0, g, :, tap, i2, i3][:, N] * fac.T[:, :, N] * xv).transpose(0, 2, 1).reshape(len(i0), -1)
+        return
+    # dx: per (n, group) the valid corners sorted by the pixel they land on
+    i0, i1, i2, i3 = idx
+    wd = m["wd"]
+    g, cl = np.divmod(i1, cpg)
+    pix = i2 * wd + i3
+    cw = (geo["wgt"] * geo["valid"]).astype(np.float64) * mk[N].astype(np.float64)                     # [4, n, dg, T, P, Q]
+    base = None if y.get("base_dx") is None else _np64(y["base_dx"])
+    lists = {}
+    for key in set(zip(i0.tolist(), g.tolist())):
+        tgt = np.where(geo["valid"][:, key[0], key[1]], geo["idx"][:, key[0], key[1]], -1).transpose(1, 2, 3, 0).ravel()
+        order = np.argsort(tgt, kind="stable")
+        lists[key] = (order, np.searchsorted(tgt[order], np.arange(m["npix"] + 1)))
+    step = max(1, chunk // max(1, 4 * t_all * p * q))
+    for lo in range(0, len(i0), step):
+        sl = slice(lo, lo + step)
+        rows, width = [], 1
+        for a, b, c_, px in zip(i0[sl], g[sl], cl[sl], pix[sl]):
+            order, start = lists[int(a), int(b)]
+            ent = order[start[px]:start[px + 1]]                                  # entries (tap, p, q, corner) flattened
+            e = ent % 4
+            tpq = ent // 4
+            rows.append(dcg[a, b, c_].ravel()[tpq] * cw[:, a, b].transpose(1, 2, 3, 0).ravel()[ent] if len(ent) else np.zeros(0))
+            width = max(width, len(ent))
+        out = np.zeros((len(rows), width + 1))
+        for j, row in enumerate(rows):
+            out[j, 1:1 + len(row)] = row
+        if base is not None:
+            out[:, 0] = base[i0[sl], i1[sl], i2[sl], i3[sl]]
+        yield out
+
+
+def dcn_yardstick(kind, idx, y, ref_s):
+    """The chained float32 evaluation of the sampled outputs minus the float64 reference at them -> (max-abs, RMS)."""
+    seq = np.concatenate([_chain32(t) for t in dcn_terms(kind, idx, y)])
+    err = seq - np.asarray(ref_s, np.float64)
+    return float(np.abs(err).max()), float(np.sqrt(np.mean(err * err)))
+
+
+def dcn_error_ratios(got, ref, idx, yard, allow=None, deltas=None, keep=None, slack=None):
+    """conv_error_ratios for one DCN tensor: got, ref whole tensors (float64 arrays), idx the sampled positions, yard = (max_seq,
+    rms_seq).  allow: per-element allowance subtracted from |error| (the fixed-point window); deltas [S, t]: the bf16 near-tie terms of
+    the samples (dcn_tie_adjust); keep / slack: whole-tensor mask of outputs that are not left out / their sum of |delta|.
+    -> (ratios, share): share = the largest part the allowance takes of a sample's bound margin x max_seq + allowance."""
+    err = np.asarray(got, np.float64) - np.asarray(ref, np.float64)
+    es = err[idx]
+    if deltas is not None:
+        es = dcn_tie_adjust(es, deltas)
+    share = 0.0
+    if allow is not None:
+        al = allow[idx]
+        share = float((al / (DCN_MARGIN * yard[0] + al + 1e-300)).max())
+        es = np.sign(es) * np.maximum(np.abs(es) - al, 0.0)
+        err = np.sign(err) * np.maximum(np.abs(err) - allow, 0.0)
+    if slack is not None:
+        err = np.sign(err) * np.maximum(np.abs(err) - slack, 0.0)
+    if keep is not None:
+        err = err[keep]
+    zero = np.zeros_like
+    return conv_error_ratios(es, zero(es), yard[0], yard[1], err, zero(err)), share
+
+
+# ---- edge inputs (seeded); tests/test_host_logic.py asserts from the float64 geometry that each holds what it claims ----
+def dcn_edge_inputs(cls, geo, seed, margin=3):
+    """Seeded float32 inputs (x, offset, mask, w, bias, gy) of edge class cls (DCN_EDGE_CLASSES) for geometry
+    geo = (n, c, h, w, k, r, s, stride, pad_h, pad_w, dilation, groups).  margin: the LDS window margin the plan reports ("beyond")."""
+    n, c, h, w, k, r, s, stride, ph, pw, dil, dg = geo
+    p, q = dcn_out_hw(h, w, r, s, stride, ph, pw, dil)
+    t = r * s
+    g = torch.Generator().manual_seed(seed)
+    rng = np.random.default_rng(seed)
+    x = torch.randn(n, c, h, w, generator=g)
+    off = (torch.randn(n, dg, t, 2, p, q, generator=g) * 1.5).numpy()
+    mask = torch.sigmoid(torch.randn(n, dg * t, p, q, generator=g))
+    wt = torch.randn(k, c, r, s, generator=g) / float(np.sqrt(c * t))
+    bias = torch.randn(k, generator=g)
+    gy = torch.randn(n, k, p, q, generator=g)
+    ti, tj = np.divmod(np.arange(t), s)
+    bh = np.broadcast_to((np.arange(p)[None, :] * stride - ph + ti[:, None] * dil)[None, None, :, :, None], (n, dg, t, p, q)).astype(np.float32)
+    bw = np.broadcast_to((np.arange(q)[None, :] * stride - pw + tj[:, None] * dil)[None, None, :, None, :], (n, dg, t, p, q)).astype(np.float32)
+    base = (bh, bw)
+    size = (h, w)
+
+    def place(axis, sel, target):
+        """offset such that float32(base + offset) == target where that is representable; elsewhere the sample keeps its offset."""
+        o = (np.asarray(target, np.float32) - base[axis]).astype(np.float32)
+        ok = sel & ((base[axis] + o).astype(np.float32) == np.asarray(target, np.float32))
+        off[:, :, :, axis][ok] = o[ok]
+        return ok
+
+    if cls == "border":
+        pp, qq = np.arange(p)[:, None], np.arange(q)[None, :]
+        for axis, first, last in ((0, pp == 0, pp == p - 1), (1, qq == 0, qq == q - 1)):
+            u = rng.uniform(0.1, 0.9, (n, dg, t, p, q)).astype(np.float32)
+            off[:, :, :, axis] = np.where(first, (u - 1) - base[axis], np.where(last, (size[axis] - 1 + u) - base[axis], off[:, :, :, axis]))
+    elif cls == "exact":
+        for axis in (0, 1):
+            kind = rng.integers(0, 10, (n, dg, t, p, q))                                  # 8, 9: the sample keeps its Gaussian offset
+            off[:, :, :, axis][kind == 0] = 0.0
+            place(axis, kind == 1, np.clip(base[axis] + rng.integers(-2, 3, kind.shape), 0, size[axis] - 1))
+            place(axis, kind == 2, np.float32(-1))
+            place(axis, kind == 3, np.float32(size[axis]))
+            place(axis, (kind == 4) | (kind == 5), np.nextafter(np.float32(-1), np.float32(0)))    # representable next to few grid positions
+            place(axis, (kind == 6) | (kind == 7), np.nextafter(np.float32(size[axis]), np.float32(0)))
+    elif cls == "beyond":
+        way = rng.integers(0, 8, (n, dg, t, p, q))                                       # 0..3: up, down, left, right; others stay
+        dist = rng.uniform(margin + 1, margin + 6, way.shape).astype(np.float32)
+        off[:, :, :, 0] = np.where(way == 0, -dist, np.where(way == 1, dist, off[:, :, :, 0]))
+        off[:, :, :, 1] = np.where(way == 2, -dist, np.where(way == 3, dist, off[:, :, :, 1]))
+    elif cls == "far":
+        pick = rng.integers(0, 240, (n, dg, t, p, q))                                    # 5 % of the samples: 12 of 240
+        vals = np.array([1e4, -1e4, 3e9, -3e9, 1e30, -1e30], np.float32)
+        for j in range(12):
+            off[:, :, :, j % 2][pick == j] = vals[j // 2]
+    elif cls == "pile":
+        off[:, :, :, 0] = np.float32(0.43 * h - 0.2) - bh
+        off[:, :, :, 1] = np.float32(0.57 * w - 0.4) - bw
+        mask = torch.rand(n, dg * t, p, q, generator=g) * 0.5 + 0.5
+        wt = (torch.rand(k, c, r, s, generator=g) + 0.5) / float(c * t)
+        gy = torch.rand(n, k, p, q, generator=g) + 0.5
+    elif cls == "operands":
+        mask = torch.randn(n, dg * t, p, q, generator=g) * 1.2
+        mask[torch.rand(mask.shape, generator=g) < 0.1] = 0.0
+        x = x * torch.exp2(torch.randint(-12, 13, (1, c, 1, 1), generator=g).float())
+        gy = gy * torch.exp2(torch.randint(-12, 13, (1, k, 1, 1), generator=g).float())
+    else:
+        assert cls == "gauss", cls
+    return x, torch.from_numpy(off.reshape(n, 2 * dg * t, p, q).astype(np.float32)), mask, wt, bias, gy
+
+
+# ---- the grid: the smallest shapes that still split.  name -> (n, c, h, w, k, r, s, stride, pad_h, pad_w, dilation, groups) ----
+DCN64_GRID = {
+    "k36":       (2, 32, 17, 20, 36, 3, 3, 1, 1, 1, 1, 1),      # ragged 8x16 blocks (3 x 2), a partial 32-filter slab: window kernels, no DMA
+    "k64":       (2, 64, 9, 17, 64, 3, 3, 1, 1, 1, 1, 1),       # 2 x 2 ragged blocks, two channel chunks: dY by DMA, the DMA sweep
+    "k12":       (1, 32, 9, 17, 12, 3, 3, 1, 1, 1, 1, 1),       # K <= 32: the 32-wide gather forward
+    "k256":      (1, 32, 9, 17, 256, 3, 3, 1, 1, 1, 1, 1),      # one 256-filter tile
+    "k260":      (1, 32, 9, 17, 260, 3, 3, 1, 1, 1, 1, 1),      # two 256-filter tiles in the weight gradient, 128-wide forward window
+    "k388":      (1, 32, 9, 17, 388, 3, 3, 1, 1, 1, 1, 1),      # K > 384: the 256-wide forward window with a ragged second tile
+    "stride2":   (2, 32, 17, 19, 36, 3, 3, 2, 1, 1, 1, 1),      # stride 2: the L2-gather kernels in every pass
+    "c8":        (1, 8, 9, 17, 36, 3, 3, 1, 1, 1, 1, 1),        # C % 32 != 0: gather kernels at stride 1
+    "dil2":      (1, 32, 12, 20, 64, 3, 3, 1, 2, 2, 2, 1),      # dilation 2: the window fits only with a smaller margin
+    "dil3g2":    (1, 256, 14, 14, 32, 3, 3, 1, 3, 3, 3, 2),     # dilation 3, two groups of 128: the gather data gradient
+    "5x5":       (1, 64, 11, 9, 64, 5, 5, 1, 2, 2, 1, 1),       # 5x5: forward on the window, gradients on the gather kernels
+    "g2":        (1, 64, 10, 18, 48, 3, 3, 1, 1, 1, 1, 2),      # two groups of 32 channels
+    "g4":        (1, 128, 9, 17, 32, 3, 3, 1, 1, 1, 1, 4),      # four groups of 32 channels
+    "edge":      (1, 32, 18, 24, 64, 3, 3, 1, 1, 1, 1, 1),      # 3 x 2 blocks; tall and wide enough that, from a block on one image border,
+                                                                # corners beyond the window margin still lie inside the image in all four directions
+}
+DCN64_EDGE_CASES = ("edge", "stride2")
+DCN64_BF16_PASSES = {"dil3g2": (DCN_DGRAD,)}  # 2304 terms per output leave fewer than a third of them without a near-tie column: the shape is
+                                              # there for its data gradient (no tie handling), its bf16 forward / weight gradient are not run        # one window route and one gather route per pass: every edge class runs on both
+
+
+def dcn64_entries(shape, margin=3):
+    """What tests/test_dcn_fp64_gpu.py calls for the grid shape named `shape`: [(pass, entry point of DCN_ENTRY_FLAGS, bf16, flags, labels
+    the plan mirror gives)]; entries whose plan refuses the shape are left out (the refusals have their own test)."""
+    out, geo = [], DCN64_GRID[shape]
+    for pas in (DCN_FWD, DCN_WGRAD, DCN_DGRAD):
+        for name, (bf, flags) in DCN_ENTRY_FLAGS[pas].items():
+            if bf and pas not in DCN64_BF16_PASSES.get(shape, (DCN_FWD, DCN_WGRAD, DCN_DGRAD)):
+                continue
+            plan = dcn_plan_mirror(pas, bf, geo, margin, flags)
+            if plan is not None:
+                out.append((pas, name, bf, flags, plan["labels"]))
+    return out
+
+
+class DcnCase:
+    """One (grid shape, edge class, operand precision): inputs, float64 reference, yardsticks and the acceptance rule of every tensor.
+    Built on the CPU only; check(tensor, got, ...) -> (ratios, allowance share, accepted)."""
+
+    def __init__(self, geo, cls, bf16, seed=0, margin=3, accumulate=False, samples=CONV_SAMPLES):
+        n, c, h, w, k, r, s, stride, ph, pw, dil, dg = geo
+        self.geo, self.cls, self.bf16, self.margin = geo, cls, bf16, margin
+        seed = seed + zlib.crc32(repr((geo, cls)).encode()) % 100000
+        self.inputs = x, off, mask, wt, bias, gy = dcn_edge_inputs(cls, geo, seed, margin)
+        gen = torch.Generator().manual_seed(seed + 1)
+        self.base_dw = torch.randn(k, c, r, s, generator=gen) * 0.1
+        self.base_dx = torch.randn(n, c, h, w, generator=gen) * float(gy.abs().mean()) if accumulate else None
+        args = (x, off, mask, wt, bias, stride, (ph, pw), dil, dg)
+        self.m64 = dcn_model(*args, gy=gy, base_dx=self.base_dx, base_dw=self.base_dw, bf16=bf16, blocks=True)
+        self.m32 = dcn_model(*args, gy=gy, dtype=np.float32)
+        self.m32["wd"], self.m32["npix"] = w, h * w
+        self.ref = dcn_ref64(*args, gy=gy, base_dx=self.base_dx, bf16=bf16)
+        self.ref["dw"] = (self.ref["dw"] + _np64(self.base_dw)).reshape(k, c, r * s)
+        if bf16:
+            ycol, yw, ygy = self.m64["colq"], self.m64["w3"], self.m64["gyq"]
+            self.near, self.alt_minus = dcn_tie_info(self.m64)
+        else:
+            from oracle import dcn as odcn
+            ycol = odcn.dcn_columns(x, off, mask, r, s, stride, (ph, pw), dil, dg, pos_fp32=True).numpy().astype(np.float64)
+            yw, ygy = _np64(wt).reshape(k, c, r * s), _np64(gy)
+        self.y = {"col": ycol, "w3": yw, "gy": ygy, "bias": bias, "dcol": dcn_chain_dcol(ygy, yw), "m32": self.m32,
+                  "base_dx": self.base_dx, "base_dw": self.base_dw}
+        self.samples, self._yard, self._tie = samples, {}, {}
+        self.allow, self.allow_fx = dcn_fixed_point_allowance(self.m64, self.base_dx)
+
+    def tie(self, tensor):
+        """bf16 "out" / "dw": (keep mask over the tensor, near-tie counts)."""
+        if tensor not in self._tie:
+            cnt = dcn_tie_counts(tensor, self.near, self.geo[4])
+            self._tie[tensor] = (cnt <= DCN_TIE_MAX, cnt)
+        return self._tie[tensor]
+
+    def yard(self, tensor):
+        if tensor not in self._yard:
+            ref = self.ref[tensor]
+            keep = self.tie(tensor)[0] if (self.bf16 and tensor in ("out", "dw")) else None
+            idx = conv_sample_positions(ref.shape, zlib.crc32(tensor.encode()) % 1000, self.samples, keep)
+            if tensor == "cols":
+                err = self.y["col"][idx] - ref[idx] if not self.bf16 else np.zeros(1)
+                yd = (float(np.abs(err).max()), float(np.sqrt(np.mean(err * err))))
+            else:
+                yd = dcn_yardstick(tensor, idx, self.y, ref[idx])
+            self._yard[tensor] = (idx, yd)
+        return self._yard[tensor]
+
+    def check(self, tensor, got, window=False, ties=True):
+        """got: the kernel's tensor in the reference's layout (dw as [k, c, T]).  window: a window data-gradient route (the fixed-point
+        allowance applies to dx).  ties: bf16 columns are rounded by the kernel (False where the test hands over rounded columns)."""
+        idx, yd = self.yard(tensor)
+        ref = self.ref[tensor]
+        kw = {}
+        if tensor == "dx" and window:
+            kw["allow"] = self.allow
+        if self.bf16 and ties and tensor in ("out", "dw"):
+            keep, _ = self.tie(tensor)
+            other = self.m64["w3"] if tensor == "out" else self.m64["gyq"]
+            kw["deltas"] = dcn_tie_deltas(tensor, idx, self.near, self.alt_minus, other)
+            ad = np.abs(self.alt_minus) * self.near
+            if tensor == "out":
+                kw["slack"] = np.einsum("nctpq,kct->nkpq", ad, np.abs(other), optimize=True)
+            else:
+                kw["slack"] = np.einsum("nkpq,nctpq->kct", np.abs(other), ad, optimize=True)
+            kw["keep"] = keep
+        ratios, share = dcn_error_ratios(_np64(got).reshape(ref.shape), ref, idx, yd, **kw)
+        return ratios, share, conv_accepts(ratios, DCN_MARGIN)
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # BatchNorm forward / ReLU-mask agreement (tests/test_bn_forward_gpu.py; tests/test_bn_mask_host.py checks the builder).
 # ------------------------------------------------------------------------------------------------------------------
 def bf16_exact(a):

@@ -997,3 +997,265 @@ def test_dcn_gpu_shapes_reach_every_route():
     for (pas, bf), labels in seen.items():
         missing = sorted(DCN_ROUTE_LABELS[pas][bf] - labels)
         assert not missing, "pass %d, %s: route labels no shape of test_dcn_gpu.py reaches: %s" % (pas, ("fp32", "bf16")[bf], missing)
+
+
+# ---- the float64 pin of the deformable convolutions (tests/test_dcn_fp64_gpu.py): what helpers promises, checked on the CPU --------
+_DCN64_HOST_SAMPLES = 1024          # the rule is the one the GPU test applies; fewer sampled outputs keep these tests quick
+
+
+def test_dcn64_grid_reaches_every_route_and_entry_point():
+    """helpers.DCN64_GRID through helpers.dcn64_entries — the calls tests/test_dcn_fp64_gpu.py makes — reaches every route label of
+    DCN_ROUTE_LABELS (refusals excepted: they have their own test) in both operand precisions and every entry point of
+    DCN_ENTRY_FLAGS, by the plan mirror and by the library's rr_dcn_plan alike; the shapes stay within the limits set for them."""
+    import helpers as H
+    seen = {(pas, bf): set() for pas in (H.DCN_FWD, H.DCN_WGRAD, H.DCN_DGRAD) for bf in (0, 1)}
+    entries, splits, ktiles = set(), set(), set()
+    for name, geo in H.DCN64_GRID.items():
+        n, c, h, w, k, r, s, stride, ph, pw, dil, dg = geo
+        assert n <= 2 and h <= 24 and w <= 24 and k in (12, 32, 36, 48, 64, 256, 260, 388), name
+        p, q = H.dcn_out_hw(h, w, r, s, stride, ph, pw, dil)
+        assert H._cdiv(p, 8) * H._cdiv(q, 16) >= 2 and (p % 8 or q % 16), name
+        for pas, entry, bf, flags, labels in H.dcn64_entries(name):
+            got = _dcn_plan_of_library(pas, bf, geo, 3, flags)
+            want = H.dcn_plan_mirror(pas, bf, geo, 3, flags)
+            assert got == {f: want[f] for f in H.DCN_PLAN_FIELDS[pas]}, (name, entry)
+            seen[pas, bf] |= labels
+            entries.add(entry)
+            if pas == H.DCN_WGRAD:
+                splits.add(want["splits"])
+                ktiles.add(want["ktiles"])
+    for (pas, bf), labels in seen.items():
+        missing = sorted(H.DCN_ROUTE_LABELS[pas][bf] - labels - {"refused"})
+        assert not missing, (pas, bf, missing)
+    assert "window_bf16_fp32dy" in seen[H.DCN_DGRAD, 1]                          # rr_dcn_dgrad_bf16: fp32 dY converted while staging
+    assert entries == {e for pas in H.DCN_ENTRY_FLAGS for e in H.DCN_ENTRY_FLAGS[pas]}
+    assert len([v for v in splits if v > 1]) >= 2 and 2 in ktiles
+    blocks = [H._cdiv(p_, 8) >= 2 and H._cdiv(q_, 16) >= 2 for p_, q_ in
+              (H.dcn_out_hw(g[2], g[3], g[5], g[6], g[7], g[8], g[9], g[10]) for g in (H.DCN64_GRID[nm] for nm in H.DCN64_EDGE_CASES))]
+    assert blocks[0]                                                             # the window edge case has at least 2 x 2 blocks
+    print("entry points compared with float64:", sorted(entries))
+    print("route labels compared with float64:", {k_: sorted(v) for k_, v in seen.items()})
+
+
+def test_dcn_ref64_is_what_it_claims():
+    """dcn_ref64: at zero offsets and unit mask it is float64 F.conv2d; on a tiny case it equals a plain Python loop over the definition
+    (values and all gradients); helpers.dcn_model in float64 equals it on grouped, strided and dilated shapes, bf16 included; and the
+    float64 bf16 image is round-to-nearest-even of the float64 value, not a double rounding through float32."""
+    import numpy as np
+    import torch.nn.functional as F
+    import helpers as H
+    from oracle import dcn as odcn
+    g = torch.Generator().manual_seed(1)
+    for stride, pad, dil in ((1, 1, 1), (2, 1, 1), (1, 2, 2)):
+        x, wt, b = torch.randn(2, 8, 9, 11, generator=g), torch.randn(12, 8, 3, 3, generator=g), torch.randn(12, generator=g)
+        p, q = H.dcn_out_hw(9, 11, 3, 3, stride, pad, pad, dil)
+        ref = H.dcn_ref64(x, torch.zeros(2, 18, p, q), torch.ones(2, 9, p, q), wt, b, stride, pad, dil, 1)
+        want = F.conv2d(x.double(), wt.double(), b.double(), stride=stride, padding=pad, dilation=dil).numpy()
+        assert np.abs(ref["out"] - want).max() <= 1e-13
+    # a plain loop over the definition: N=1, C=2, 4x5, K=2, 3x3, pad 1
+    n, c, h, w, k = 1, 2, 4, 5, 2
+    x, off, mask = torch.randn(n, c, h, w, generator=g), torch.randn(n, 18, h, w, generator=g) * 1.5, torch.rand(n, 9, h, w, generator=g)
+    wt, b, gy = torch.randn(k, c, 3, 3, generator=g), torch.randn(k, generator=g), torch.randn(n, k, h, w, generator=g)
+    ref = H.dcn_ref64(x, off, mask, wt, b, 1, 1, 1, 1, gy=gy)
+    X, O, M, W_, G = (t.double().numpy() for t in (x, off, mask, wt, gy))
+    out, dx, doff, dm, dw = np.zeros((n, k, h, w)), np.zeros(X.shape), np.zeros(O.shape), np.zeros(M.shape), np.zeros(W_.shape)
+    for pp in range(h):
+        for qq in range(w):
+            for tap in range(9):
+                i, j = divmod(tap, 3)
+                hp = float(np.float32(pp - 1 + i) + np.float32(O[0, 2 * tap, pp, qq]))
+                wp = float(np.float32(qq - 1 + j) + np.float32(O[0, 2 * tap + 1, pp, qq]))
+                if not (hp > -1 and wp > -1 and hp < h and wp < w):
+                    continue
+                h0, w0 = int(np.floor(hp)), int(np.floor(wp))
+                lh, lw = hp - h0, wp - w0
+                for hy, wx, wg, gh, gw in ((h0, w0, (1 - lh) * (1 - lw), -(1 - lw), -(1 - lh)), (h0, w0 + 1, (1 - lh) * lw, -lw, 1 - lh),
+                                           (h0 + 1, w0, lh * (1 - lw), 1 - lw, -lh), (h0 + 1, w0 + 1, lh * lw, lw, lh)):
+                    if not (0 <= hy <= h - 1 and 0 <= wx <= w - 1):
+                        continue
+                    for ch in range(c):
+                        for ko in range(k):
+                            gcol = G[0, ko, pp, qq] * W_[ko, ch, i, j]
+                            out[0, ko, pp, qq] += W_[ko, ch, i, j] * M[0, tap, pp, qq] * wg * X[0, ch, hy, wx]
+                            dw[ko, ch, i, j] += G[0, ko, pp, qq] * M[0, tap, pp, qq] * wg * X[0, ch, hy, wx]
+                            dx[0, ch, hy, wx] += gcol * M[0, tap, pp, qq] * wg
+                            dm[0, tap, pp, qq] += gcol * wg * X[0, ch, hy, wx]
+                            doff[0, 2 * tap, pp, qq] += gcol * M[0, tap, pp, qq] * gh * X[0, ch, hy, wx]
+                            doff[0, 2 * tap + 1, pp, qq] += gcol * M[0, tap, pp, qq] * gw * X[0, ch, hy, wx]
+    out += b.double().numpy().reshape(1, -1, 1, 1)
+    for name, a in (("out", out), ("dx", dx), ("doffset", doff), ("dmask", dm), ("dw", dw)):
+        assert np.abs(ref[name] - a).max() <= 1e-12 * max(1.0, np.abs(a).max()), name
+    assert np.abs(ref["db"] - G.sum((0, 2, 3))).max() <= 1e-12
+    # helpers.dcn_model (the corner-by-corner numpy model the yardstick, the allowances and the modelled faults use) in float64
+    for name, bf in (("g2", 0), ("stride2", 1), ("dil2", 1), ("k64", 0)):
+        geo = H.DCN64_GRID[name]
+        ins = H.dcn_edge_inputs("gauss", geo, 5)
+        args = ins[:5] + (geo[7], (geo[8], geo[9]), geo[10], geo[11])
+        ref = H.dcn_ref64(*args, gy=ins[5], bf16=bool(bf))
+        mod = H.dcn_model(*args, gy=ins[5], bf16=bool(bf))
+        for tensor in ("out", "dx", "doffset", "dmask", "dw", "db"):
+            assert np.abs(ref[tensor] - mod[tensor]).max() <= 1e-12 * max(1.0, np.abs(ref[tensor]).max()), (name, tensor)
+        assert np.abs(ref["cols"] - mod["col"]).max() <= 1e-13 * np.abs(ref["cols"]).max()
+    # the bf16 image of a float64 value: 1 + 2^-8 + 2^-30 lies ABOVE the tie between 1 and 1 + 2^-7; float32 rounds it onto the tie
+    v = 1.0 + 2.0 ** -8 + 2.0 ** -30
+    assert float(torch.tensor([v], dtype=torch.float64).float().bfloat16()) == 1.0           # the double rounding this must not be
+    assert float(odcn._bf16_round(torch.tensor([v], dtype=torch.float64))[0]) == 1.0 + 2.0 ** -7 == float(H.bf16_rne64(np.array([v]))[0])
+    assert float(H.bf16_rne64(np.array([1.0 + 2.0 ** -8]))[0]) == 1.0 and float(H.bf16_rne64(np.array([1.0 + 3 * 2.0 ** -8]))[0]) == 1.0 + 2.0 ** -6
+    a = np.random.default_rng(3).standard_normal(20000) * 10.0 ** np.random.default_rng(4).integers(-6, 7, 20000)
+    q = H.bf16_rne64(a)
+    assert (q == H.bf16_exact(q.astype(np.float32))).all()                                   # bf16 values
+    ulp = 2.0 * H.bf16_half_ulp(q)
+    assert (np.abs(a - q) <= np.minimum(np.abs(a - (q + ulp)), np.abs(a - (q - ulp)))).all() and (np.abs(a - q) <= 0.5 * ulp).all()
+    assert (odcn._bf16_round(torch.from_numpy(a)).numpy() == q).all()
+
+
+def test_dcn_edge_classes_hold_what_they_claim():
+    """Every seeded edge class of helpers.dcn_edge_inputs contains what it claims, counted from the float64 geometry, on both shapes
+    the GPU test runs them on (one window route, one gather route)."""
+    import numpy as np
+    import helpers as H
+    for name in H.DCN64_EDGE_CASES:
+        geo = H.DCN64_GRID[name]
+        n, c, h, w, k, r, s, stride, ph, pw, dil, dg = geo
+        plan = H.dcn_plan_mirror(H.DCN_DGRAD, 0, geo, 3, 0)
+        margin = plan["margin"] if plan["window"] else 3
+        res = {}
+        for cls in H.DCN_EDGE_CLASSES:
+            x, off, mask, wt, b, gy = H.dcn_edge_inputs(cls, geo, 11, margin)
+            g_ = H.dcn_geometry(off, h, w, r, s, stride, (ph, pw), dil, dg)
+            res[cls] = (g_, x, off, mask, gy)
+            assert torch.isfinite(off).all()
+        hw = {"h": h, "w": w}
+        g_ = res["gauss"][0]
+        assert 0.5 < g_["inside"].mean() < 1.0 and np.abs(res["gauss"][2].std().item() - 1.5) < 0.1
+        # border band: every sample of a border output pixel in (-1, 0) / (H - 1, H); partial footprints; both at the corners
+        g_ = res["border"][0]
+        p, q = g_["inside"].shape[-2:]
+        assert ((g_["h"][..., 0, :] > -1) & (g_["h"][..., 0, :] < 0)).all() and ((g_["h"][..., p - 1, :] > h - 1) & (g_["h"][..., p - 1, :] < h)).all()
+        assert ((g_["w"][..., 0] > -1) & (g_["w"][..., 0] < 0)).all() and ((g_["w"][..., q - 1] > w - 1) & (g_["w"][..., q - 1] < w)).all()
+        nvalid = g_["valid"].sum(0)
+        assert (nvalid[..., 0, 0] == 1).all() and (nvalid[..., p - 1, q - 1] == 1).all() and (nvalid[g_["inside"]] >= 1).all()
+        assert ((nvalid == 2) & g_["inside"]).sum() >= 2 * 9 * (p + q - 4) // 2
+        # exact positions: integers (offset 0 among them), exactly -1 and H / W, one float32 ulp inside each
+        g_, off = res["exact"][0], res["exact"][2]
+        counts = {}
+        for ax in ("h", "w"):
+            v, size = g_[ax], hw[ax]
+            counts[ax] = {"integer": int(((v == np.floor(v)) & (v >= 0) & (v <= size - 1)).sum()), "-1": int((v == -1).sum()),
+                          "size": int((v == size).sum()), "-1+ulp": int((v == np.nextafter(np.float32(-1), np.float32(0))).sum()),
+                          "size-ulp": int((v == np.nextafter(np.float32(size), np.float32(0))).sum())}
+            assert all(cnt >= 10 for cnt in counts[ax].values()), (name, counts)        # (one ulp inside is representable next to few grid positions)
+        assert int((off == 0).sum()) >= 100
+        assert (~g_["inside"] & ((g_["h"] == -1) | (g_["h"] == h) | (g_["w"] == -1) | (g_["w"] == w))).sum() >= 80
+        # beyond the margin: in each of the four directions, corners off the window that are inside the image (the direct global path)
+        # and corners outside it, from source pixels of blocks on the image border
+        g_, off = res["beyond"][0], res["beyond"][2].numpy().reshape(n, dg, r * s, 2, p, q)
+        inwin = H.dcn_in_window(g_, r, s, (ph, pw), dil, margin)
+        for ax, sign in ((0, -1), (0, 1), (1, -1), (1, 1)):
+            o = off[:, :, :, ax] * sign
+            sel = (o >= margin + 1) & (o <= margin + 6)
+            assert sel.sum() >= 0.08 * sel.size, (name, ax, sign)
+            if stride == 1:
+                assert (g_["valid"] & ~inwin & sel[None]).sum() >= 10 and (~g_["valid"] & ~inwin & sel[None]).sum() >= 10, (name, ax, sign)
+        # far away: a few percent of the samples at +-1e4, +-3e9, +-1e30, all outside; the neighbours keep their Gaussian offsets
+        g_, off = res["far"][0], res["far"][2].numpy()
+        for val in (1e4, 3e9, 1e30):
+            assert (off == np.float32(val)).sum() >= 5 and (off == np.float32(-val)).sum() >= 5
+        big = (np.abs(off) >= 1e4).reshape(n, dg, r * s, 2, p, q).any(3)
+        assert 0.02 <= big.mean() <= 0.08 and not g_["inside"][big].any() and (np.abs(off[np.abs(off) < 1e4]) < 10).all()
+        # pile-up: every sample on ONE fractional position
+        g_ = res["pile"][0]
+        assert len(np.unique(g_["idx"][0])) == 1 and g_["inside"].all() and (g_["lh"] > 0.05).all() and (g_["lw"] > 0.05).all()
+        assert np.ptp(g_["lh"]) < 1e-5 and np.ptp(g_["lw"]) < 1e-5
+        # operands: masks with exact zeros, negative values and values above 1; 2^+-12 dynamic range across channels
+        _, x, _, mask, gy = res["operands"]
+        assert (mask == 0).float().mean() > 0.05 and (mask < 0).float().mean() > 0.2 and (mask > 1).float().mean() > 0.05
+        for t in (x, gy):
+            rms = t.square().mean((0, 2, 3)).sqrt()
+            assert rms.max() / rms.min() >= 2.0 ** 20
+
+
+def test_dcn_tie_conditions_and_allowance_share():
+    """On the reference alone: in every bf16 grid case (and every edge class on the edge cases) at most 1 % of the outputs and of the dw
+    elements hold more than DCN_TIE_MAX near-tie terms (they are left out) and at least a third of each tensor's sampled outputs hold
+    none and take the plain rule; no float32-model column rounds differently from the float64 column outside the band.  The
+    fixed-point allowance of the window data gradient is the contract's WORST case (every one of an element's ~15 hits rounds half a
+    unit the same way, the unit sized for the block's ~50 hits on its busiest pixel): on Gaussian inputs it is below 2^-17 of the
+    tensor's maximum, but it is no small share of an element's bound at the cap margin — measured 0.38 to 0.59 (about as much as
+    8 x the chained float32 sum), asserted below 0.75; the flush part alone stays below a quarter of 8 x the yardstick (measured: 0.14 at most).  What keeps
+    the allowance honest is the modelled fault below: a unit of 2^-20 of the bound is refused."""
+    import numpy as np
+    import helpers as H
+    cases = [(nm, "gauss") for nm in H.DCN64_GRID] + [(nm, cls) for nm in H.DCN64_EDGE_CASES for cls in H.DCN_EDGE_CLASSES[1:]]
+    for name, cls in cases:
+        geo = H.DCN64_GRID[name]
+        cs = H.DcnCase(geo, cls, 1, samples=_DCN64_HOST_SAMPLES)
+        for tensor in ("out", "dw") if name not in H.DCN64_BF16_PASSES else ():    # (shapes whose bf16 forward / weight gradient do not run)
+            keep, cnt = cs.tie(tensor)
+            assert 1.0 - keep.mean() <= H.DCN_TIE_LEFT_OUT, (name, cls, tensor, 1.0 - keep.mean())
+            idx, _ = cs.yard(tensor)
+            assert keep[idx].all()
+            clean = float((cnt[idx] == 0).mean())
+            assert clean >= H.DCN_TIE_CLEAN, (name, cls, tensor, clean)
+        m32 = H.dcn_model(*cs.inputs[:5], geo[7], (geo[8], geo[9]), geo[10], geo[11], dtype=np.float32, bf16=True)
+        flipped = m32["colq"].astype(np.float64) != cs.m64["colq"]
+        assert not (flipped & ~cs.near).any(), (name, cls, int((flipped & ~cs.near).sum()))
+        assert cs.near.mean() < 0.01
+    for name in ("k64", "k36", "g2"):
+        cs = H.DcnCase(H.DCN64_GRID[name], "gauss", 0, samples=_DCN64_HOST_SAMPLES)
+        idx, yd = cs.yard("dx")
+        al, fx = cs.allow[idx], cs.allow_fx[idx]
+        share = al / (H.CONV_MARGIN_CAP * yd[0] + al)
+        assert share.max() < 0.75 and ((al - fx) / (H.CONV_MARGIN_CAP * yd[0])).max() < 0.25, (name, share.max())
+        assert al.max() < 2.0 ** -17 * np.abs(cs.ref["dx"]).max()
+
+
+_DCN_FAULT_CASES = {            # fault -> (grid shape, edge class, bf16, accumulate) where the rule must refuse it
+    "clamp": ("edge", "border", 0, False), "nonstrict": ("edge", "exact", 0, False), "swap_hw": ("k64", "gauss", 0, False),
+    "group0": ("g2", "gauss", 0, False), "beyond_margin": ("edge", "beyond", 0, False), "tap_mask": ("k64", "gauss", 0, False),
+    "skip_chunk": ("k64", "gauss", 0, False), "doffset_nomask": ("k64", "gauss", 0, False), "cols_unrounded": ("k64", "gauss", 1, False),
+    "round_before_mask": ("k64", "gauss", 1, False), "dy_unrounded": ("k64", "gauss", 1, False), "base_ignored": ("k64", "gauss", 1, True),
+    "fx_unit20": ("k64", "gauss", 0, False),
+}
+
+
+def test_dcn_modelled_faults_are_rejected():
+    """The acceptance rule of tests/test_dcn_fp64_gpu.py (conv_accepts at the cap margin, with the fixed-point allowance on d input and
+    the bf16 tie rule) refuses every modelled fault — applied on the CPU to the float32 evaluation — in the tensor the fault shows in,
+    and accepts the unmodified float32 evaluation in every grid case and edge class, in both precisions."""
+    import numpy as np
+    import helpers as H
+    assert set(_DCN_FAULT_CASES) == set(H.DCN_FAULTS)
+    shows = {"clamp": {"out", "dw", "dmask", "doffset"}, "nonstrict": {"doffset"}, "doffset_nomask": {"doffset"}, "fx_unit20": {"dx"},
+             "dy_unrounded": {"dw", "dx", "dmask", "doffset"}, "base_ignored": {"dw", "dx"}, "cols_unrounded": {"out", "dw"},
+             "round_before_mask": {"out", "dw"}}
+    tensors = ("out", "dw", "dmask", "doffset", "dx")
+
+    def run(cs, fault):
+        geo = cs.geo
+        m = H.dcn_model(*cs.inputs[:5], geo[7], (geo[8], geo[9]), geo[10], geo[11], gy=cs.inputs[5], base_dx=cs.base_dx, base_dw=cs.base_dw,
+                        dtype=np.float32, bf16=bool(cs.bf16), fault=fault, margin=cs.margin)
+        return {t: cs.check(t, m[t], window=True) for t in tensors}
+
+    built = {}
+    for fault, key in _DCN_FAULT_CASES.items():
+        if key not in built:
+            name, cls, bf, acc = key
+            built[key] = H.DcnCase(H.DCN64_GRID[name], cls, bf, accumulate=acc, samples=_DCN64_HOST_SAMPLES)
+            clean = run(built[key], None)
+            assert all(v[2] for v in clean.values()), (key, clean)
+        res = run(built[key], fault)
+        refused = {t for t, v in res.items() if not v[2]}
+        assert refused, (fault, res)
+        assert refused >= shows.get(fault, {"out"}), (fault, refused, res)
+    # the unmodified float32 evaluation passes everywhere
+    cases = [(nm, "gauss") for nm in H.DCN64_GRID] + [(nm, cls) for nm in H.DCN64_EDGE_CASES for cls in H.DCN_EDGE_CLASSES[1:]]
+    worst = 0.0
+    for name, cls in cases:
+        for bf in (0, 1):
+            key = (name, cls, bf, bool(bf))
+            cs = built.get(key) or H.DcnCase(H.DCN64_GRID[name], cls, bf, accumulate=bool(bf), samples=_DCN64_HOST_SAMPLES)
+            res = run(cs, None)
+            assert all(v[2] for v in res.values()), (name, cls, bf, res)
+            worst = max(worst, max(r for t, v in res.items() if t != "dx" for r in v[0]))
+    assert worst < H.CONV_MARGIN_CAP / 2, worst
