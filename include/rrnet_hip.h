@@ -136,6 +136,20 @@ int rr_conv_wgrad(const float *x, const float *dy, float *dw, int n, int h, int 
 #define RR_CONV_PLAN_INTS 11
 int rr_conv_fprop_plan(int math, int n, int h, int wd, int c, int k, int r, int s, int stride, int pad_h, int pad_w,
                        int out_h, int out_w, int flags, int *plan);
+/* The same for the gradient passes (dgrad_plan, dgrad_s2_plan, wgrad_plan of csrc/conv_plan.h).  pass: 0 rr_conv_dgrad (family 0),
+ * 1 a parity-class data gradient (stride 2; family 1 rr_conv_dgrad_s2_bf16, 2 rr_conv_dgrad_s2_f16x3, 3 rr_conv16_dgrad_s2),
+ * 2 a weight gradient (family 0 rr_conv_wgrad, 1 _bf16, 2 _f16x3, 3 rr_conv16_wgrad, which has no out_h / out_w).  out[], by pass —
+ *   0: scalar gather, tile width, grid.x (workgroups of a class), grid.y (classes that launch), parity-decomposed, class order
+ *      (2 bits per class, most taps first), split-K factor, dx zero-filled in front;
+ *   1: dy's height, width, dx zero-filled in front, number of launches, then per launch 10 values: the class (h % 2, w % 2),
+ *      sub-filter height and width, leading pads down and across, class image height and width, the sub-filter's offset in the
+ *      packed filter in units of C*K elements, workgroups (family 3; 0 where rr_conv_fprop_plan decides the launch);
+ *   2: dy's height, width, pixels, tile filters x channels, scalar dy loads, scalar x loads, pipeline mode (0 generic, 1, 3),
+ *      tiles along K and along C, tiles, pixel splits, K-steps per split, workgroups, dynamic LDS bytes;
+ * the rest 0.  n_out >= RR_CONV_GRAD_PLAN_INTS.  A call the pass refuses returns an error (rr_last_error says why). */
+#define RR_CONV_GRAD_PLAN_INTS 44
+int rr_conv_grad_plan(int pass, int family, int n, int h, int wd, int c, int k, int r, int s, int stride, int pad_h, int pad_w,
+                      int out_h, int out_w, int accumulate, int *out, int n_out);
 
 /* ---- bf16-operand convolutions (BASELINE config 4, "bf16"; csrc/conv_bf16.hip) ------------------------------------- *
  * The reference is fp32-only (backbones/hourglass.py:12-61,127-199 -> nn.Conv2d), so this precision is builder-defined

@@ -1235,7 +1235,7 @@ int launch_igemm(ConvArgs &a, int bn, bool scalar, int blocks, int gy, int gz, h
     const bool small = (long)a.N * a.SH * a.SW * a.SC * 4 < (1l << 31) && (long)a.wK * a.R * a.S * a.wC * 4 < (1l << 31);
     a.dst32 = (long)a.M * a.DC * 4 < (1l << 31);
 #define IG(BNv, SCv, PIPEv, ...)                                                                                       \
-    rr_launch(conv_igemm_kernel<BNv, MODE, SCv, BK, PIPEv, ##__VA_ARGS__>, dim3(blocks, gy, gz),                       \
+    rr_launch(conv_igemm_kernel<BNv, MODE, SCv, BK, PIPEv, ##__VA_ARGS__>, dim3(blocks, gy, gz), 256,                  \
               igemm_lds(bn, MODE == 1, PIPEv == 2 ? 1 : 2), stream, a, name)
     if constexpr (MODE == 0) {
         if (a.pos_major)             // host rule (fprop_impl): vector gather, both tensors below 2 GiB
@@ -1464,97 +1464,47 @@ extern "C" int rr_conv_dgrad_s1_relubias(const float *dy, const float *wt, float
     return dgrad_s1("rr_conv_dgrad_s1_relubias", bs.relu_bias_ok(c, k), dy, wt, dx, n, h, wd, c, k, r, s, pad_h, pad_w, accumulate, stream, &bs);
 }
 
+// How these two launch is rr_plan::dgrad_plan's and rr_plan::wgrad_plan's decision (conv_plan.h).
 extern "C" int rr_conv_dgrad(const float *dy, const float *w, float *dx, int n, int h, int wd, int c, int k,
                              int r, int s, int stride, int pad_h, int pad_w, int accumulate,
                              hipStream_t stream)
 {
-    RR_CHECK_ARG(n > 0 && h > 0 && wd > 0 && c > 0 && k > 0 && r > 0 && s > 0 && stride > 0, "rr_conv_dgrad: bad dims");
+    const rr_plan::DgradPlan pl = rr_plan::dgrad_plan({n, h, wd, c, k, r, s, stride, pad_h, pad_w, 0, 0}, accumulate != 0);
+    if (pl.refuse.why) return rr_refuse("rr_conv_dgrad", pl.refuse);
     ConvArgs a{};
     a.src = dy; a.w = w; a.dst = dx; a.bias = nullptr; a.stat_slab = nullptr;
     a.N = n;
     a.SH = (h + 2 * pad_h - r) / stride + 1; a.SW = (wd + 2 * pad_w - s) / stride + 1; a.SC = k;
     a.DH = h; a.DW = wd; a.DC = c;
     a.R = r; a.S = s; a.stride = stride; a.pad_h = pad_h; a.pad_w = pad_w;
-    a.relu = 0; a.accumulate = accumulate; a.ksplit = 1; a.zero = zero_page();
-    const long M = (long)n * h * wd;
-    RR_CHECK_ARG(M < (1l << 31), "rr_conv_dgrad: tensor too large");
-    a.M = (int)M; a.Kg = r * s * k; a.wK = k; a.wC = c;
-    const bool scalar = (k % 4) != 0 || (c % 4) != 0 || r * s > 64 || stride > 2;
-    int bn = c > 64 ? 128 : (c > 32 ? (!scalar ? 64 : 128) : 32);
-    if (bn == 128 && !scalar && stride == 1 && rr_cdiv(M, BM) * rr_cdiv(c, 128) <= rr_plan::small_tiles()) bn = 32;
-    else if (bn == 128 && !scalar && stride == 1 && rr_cdiv(M, BM) * rr_cdiv(c, 128) <= rr_plan::mid_tiles()) bn = 64;
-    int blocks = rr_cdiv(M, BM) * rr_cdiv(c, bn);
-    int gy = 1;
-    int nk = scalar ? rr_cdiv(a.Kg, BK) : rr_cdiv(k, BK) * r * s;
-    if (stride == 2 && !scalar) {     // parity-decomposed: 4 classes of ceil(h/2) x ceil(w/2) pixels each
-        a.parity = 1;
-        gy = 4;
-        rr_plan::ParityClass cls[4];
-        rr_plan::parity_classes(h, wd, r, s, pad_h, pad_w, cls);
-        int ord[4] = {0, 1, 2, 3};
-        for (int i = 0; i < 4; ++i)
-            for (int j = i + 1; j < 4; ++j)
-                if (cls[ord[j]].taps() > cls[ord[i]].taps()) { const int t = ord[i]; ord[i] = ord[j]; ord[j] = t; }
-        a.parity_order = ord[0] | (ord[1] << 2) | (ord[2] << 4) | (ord[3] << 6);
-        // classes without any tap (1x1 stride 2: three of four) produce zeros: one memset instead of workgroups
-        // that run an empty K loop and store zeros element by element
-        // (when accumulating they add nothing: no workgroups at all)
-        int live = 4;
-        while (live > 1 && cls[ord[live - 1]].taps() == 0) --live;
-        if (live < 4) {
-            if (!accumulate) RR_CHECK_HIP(rr_zero2(dx, sizeof(float) * (size_t)M * c, nullptr, 0, stream), "rr_conv_dgrad");
-            gy = live;
-        }
-        blocks = rr_cdiv((long)n * ((h + 1) / 2) * ((wd + 1) / 2), BM) * rr_cdiv(c, bn);
-        nk = rr_cdiv(k, BK) * ((r + 1) / 2) * ((s + 1) / 2);
-    }
-    int ks = a.parity ? 1 : rr_plan::pick_ksplit(blocks * gy, nk);
-    if (ks > 1) {
-        a.ksplit = ks;
-        if (!accumulate) RR_CHECK_HIP(rr_zero2(dx, sizeof(float) * (size_t)M * c, nullptr, 0, stream), "rr_conv_dgrad");
-    }
-    return launch_igemm<1>(a, bn, scalar, blocks, gy, ks, stream, "rr_conv_dgrad");
+    a.relu = 0; a.accumulate = accumulate; a.ksplit = pl.ks; a.zero = zero_page();
+    a.parity = pl.parity; a.parity_order = pl.parity_order;
+    a.M = (int)pl.M; a.Kg = r * s * k; a.wK = k; a.wC = c;
+    if (pl.zero_dst) RR_CHECK_HIP(rr_zero2(dx, sizeof(float) * (size_t)pl.M * c, nullptr, 0, stream), "rr_conv_dgrad");
+    return launch_igemm<1>(a, pl.bn, pl.scalar, pl.blocks, pl.gy, pl.ks, stream, "rr_conv_dgrad");
 }
 
 extern "C" int rr_conv_wgrad(const float *x, const float *dy, float *dw, int n, int h, int wd, int c, int k,
                              int r, int s, int stride, int pad_h, int pad_w, int out_h, int out_w,
                              hipStream_t stream)
 {
-    RR_CHECK_ARG(n > 0 && h > 0 && wd > 0 && c > 0 && k > 0 && r > 0 && s > 0 && stride > 0, "rr_conv_wgrad: bad dims");
+    const rr_plan::WgradPlan pl = rr_plan::wgrad_plan(rr_plan::MATH_F32, {n, h, wd, c, k, r, s, stride, pad_h, pad_w, out_h, out_w});
+    if (pl.refuse.why) return rr_refuse("rr_conv_wgrad", pl.refuse);
     WgradArgs a{};
     a.x = x; a.dy = dy; a.dw = dw; a.zero = zero_page();
     a.N = n; a.H = h; a.W = wd; a.C = c; a.K = k; a.R = r; a.S = s;
-    // out_h/out_w > 0 override the symmetric-padding output size (pad_h/pad_w are the LEADING pads; taps that
-    // fall past the far edge are masked), which is how asymmetric padding is expressed
-    a.P = out_h > 0 ? out_h : (h + 2 * pad_h - r) / stride + 1;
-    a.Q = out_w > 0 ? out_w : (wd + 2 * pad_w - s) / stride + 1;
+    a.P = pl.P; a.Q = pl.Q;
     a.stride = stride; a.pad_h = pad_h; a.pad_w = pad_w;
-    const long M = (long)n * a.P * a.Q;
-    RR_CHECK_ARG(M > 0 && M < (1l << 31), "rr_conv_wgrad: bad pixel count");
-    a.M = (int)M;
-    const int bmw = k > 32 ? 128 : 32;
-    const int bn = c > 32 ? 128 : 32;
-    a.mt = rr_cdiv(k, bmw); a.nt = rr_cdiv(c, bn);
-    const int tiles = a.mt * a.nt * r * s;
-    const int total_chunks = rr_cdiv(M, BK);
-    // pipelined 128x128 variants: 32-bit buffer offsets, both tensors below 2 GiB
-    const bool as = (k % 4) != 0, bs = (c % 4) != 0;
-    const bool pipe_ok = bmw == 128 && bn == 128 && !as && !bs && M * k * 4 < (1l << 31) &&
-                         (long)n * h * wd * c * 4 < (1l << 31);
-    const int wmode = !pipe_ok ? 0 : (a.Q % BK == 0 ? 3 : 1);   // PIPE of the 128x128 kernel, 0: generic tiles
-    const int slots = wmode == 3 ? 768 : 512;       // resident workgroups: 256 CUs x 3 with one LDS image, else x 2
-    const int blocks = tiles * rr_plan::pixel_splits(tiles, total_chunks, slots, 8, &a.chunks_per_split);
-    const size_t lds = sizeof(float) * (wmode == 3 ? 1 : 2) * (BK * bmw + BK * bn);
-#define WG(BMv, BNv)                                                                                                  \
-    (as ? (bs ? rr_launch(conv_wgrad_kernel<BMv, BNv, true, true, 0>, dim3(blocks), lds, stream, a, "rr_conv_wgrad")      \
-              : rr_launch(conv_wgrad_kernel<BMv, BNv, true, false, 0>, dim3(blocks), lds, stream, a, "rr_conv_wgrad"))    \
-        : (bs ? rr_launch(conv_wgrad_kernel<BMv, BNv, false, true, 0>, dim3(blocks), lds, stream, a, "rr_conv_wgrad")     \
-              : rr_launch(conv_wgrad_kernel<BMv, BNv, false, false, 0>, dim3(blocks), lds, stream, a, "rr_conv_wgrad")))
-    if (wmode == 3) return rr_launch(conv_wgrad_kernel<128, 128, false, false, 3>, dim3(blocks), lds, stream, a, "rr_conv_wgrad");
-    if (wmode == 1) return rr_launch(conv_wgrad_kernel<128, 128, false, false, 1>, dim3(blocks), lds, stream, a, "rr_conv_wgrad");
-    if (bmw == 128) return bn == 128 ? WG(128, 128) : WG(128, 32);
-    return bn == 128 ? WG(32, 128) : WG(32, 32);
+    a.M = (int)pl.M; a.mt = pl.mt; a.nt = pl.nt; a.chunks_per_split = pl.per_split;
+#define WG(BMv, BNv, ASv, BSv, PIPEv) rr_launch(conv_wgrad_kernel<BMv, BNv, ASv, BSv, PIPEv>, dim3(pl.grid), 256, pl.lds, stream, a, "rr_conv_wgrad")
+#define WG_AB(BMv, BNv) (pl.a_scalar ? (pl.b_scalar ? WG(BMv, BNv, true, true, 0) : WG(BMv, BNv, true, false, 0))         \
+                                     : (pl.b_scalar ? WG(BMv, BNv, false, true, 0) : WG(BMv, BNv, false, false, 0)))
+    if (pl.pipe == 3) return WG(128, 128, false, false, 3);
+    if (pl.pipe == 1) return WG(128, 128, false, false, 1);
+    if (pl.bm == 128) return pl.bn == 128 ? WG_AB(128, 128) : WG_AB(128, 32);
+    return pl.bn == 128 ? WG_AB(32, 128) : WG_AB(32, 32);
 #undef WG
+#undef WG_AB
 }
 
 // the policy of conv_plan.h as the library was built with it, for tests/test_host_logic.py (C++ linkage, called by mangled name)
@@ -1574,5 +1524,39 @@ extern "C" int rr_conv_fprop_plan(int math, int n, int h, int wd, int c, int k, 
     const int out[RR_CONV_PLAN_INTS] = {pl.rows, pl.scalar, pl.bn, pl.blocks, pl.ks, pl.pos_major, pl.xcd_n, pl.fused, pl.after, pl.zero_dst,
                                         pl.zero_slab};
     for (int i = 0; i < RR_CONV_PLAN_INTS; ++i) plan[i] = out[i];
+    return RR_OK;
+}
+
+// the gradient plans of conv_plan.h as the entry points of conv.hip, conv_bf16.hip and conv16.hip ask them
+extern "C" int rr_conv_grad_plan(int pass, int family, int n, int h, int wd, int c, int k, int r, int s, int stride, int pad_h, int pad_w,
+                                 int out_h, int out_w, int accumulate, int *out, int n_out)
+{
+    using namespace rr_plan;
+    const bool family_ok = pass == GRAD_DGRAD ? family == MATH_F32 : pass == GRAD_DGRAD_S2 ? (family >= MATH_BF16 && family <= FAM_CONV16)
+                                                                                          : (family >= MATH_F32 && family <= FAM_CONV16);
+    RR_CHECK_ARG(pass >= GRAD_DGRAD && pass <= GRAD_WGRAD && family_ok && out != nullptr && n_out >= RR_CONV_GRAD_PLAN_INTS,
+                 "rr_conv_grad_plan: bad arguments");
+    const ConvGeom g{n, h, wd, c, k, r, s, stride, pad_h, pad_w, out_h, out_w};
+    for (int i = 0; i < n_out; ++i) out[i] = 0;
+    if (pass == GRAD_DGRAD) {
+        const DgradPlan p = dgrad_plan(g, accumulate != 0);
+        if (p.refuse.why) return rr_refuse("rr_conv_grad_plan", p.refuse);
+        const int f[8] = {p.scalar, p.bn, p.blocks, p.gy, p.parity, p.parity_order, p.ks, p.zero_dst};
+        for (int i = 0; i < 8; ++i) out[i] = f[i];
+    } else if (pass == GRAD_DGRAD_S2) {
+        const DgradS2Plan p = dgrad_s2_plan(family, g, accumulate != 0);
+        if (p.refuse.why) return rr_refuse("rr_conv_grad_plan", p.refuse);
+        out[0] = p.p; out[1] = p.q; out[2] = p.zero_dst; out[3] = p.n_launch;
+        for (int i = 0; i < p.n_launch; ++i) {
+            const ParityClass &pc = p.cls[i];
+            const int f[10] = {pc.ph, pc.pw, pc.Rc, pc.Sc, pc.lead_h, pc.lead_w, pc.Hc, pc.Wc, pc.taps_before, p.blocks[i]};
+            for (int j = 0; j < 10; ++j) out[4 + 10 * i + j] = f[j];
+        }
+    } else {
+        const WgradPlan p = wgrad_plan(family, g);
+        if (p.refuse.why) return rr_refuse("rr_conv_grad_plan", p.refuse);
+        const int f[15] = {p.P, p.Q, (int)p.M, p.bm, p.bn, p.a_scalar, p.b_scalar, p.pipe, p.mt, p.nt, p.tiles, p.splits, p.per_split, p.grid, p.lds};
+        for (int i = 0; i < 15; ++i) out[i] = f[i];
+    }
     return RR_OK;
 }

@@ -353,19 +353,9 @@ int check_shape(const char *name, int n, int h, int wd, int c, int k, int r, int
 
 int launch_igemm(const Args &a, hipStream_t stream, const char *name)
 {
-    const int mt = rr_cdiv(a.M, TP);
-    if (a.DC % 256 == 0) {
-        const size_t ldsb = 2 * (size_t)(IMG + 256 * ROWB);
-        // (set on every launch: the attribute is per device, and a once-per-process flag would leave a second GPU without it)
-        RR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(conv16_igemm_kernel<256>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb), name);
-        hipLaunchKernelGGL(conv16_igemm_kernel<256>, dim3(mt * (a.DC / 256)), dim3(512), ldsb, stream, a);
-    } else {
-        const size_t ldsb = 128 * 1024;        // (two buffers need 96 KiB; the statistics epilogue's table 128)
-        RR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(conv16_igemm_kernel<128>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb), name);
-        hipLaunchKernelGGL(conv16_igemm_kernel<128>, dim3(mt * (a.DC / 128)), dim3(512), ldsb, stream, a);
-    }
-    RR_CHECK_LAUNCH(name);
-    return RR_OK;
+    const rr_plan::Conv16Tile t = rr_plan::conv16_tile(a.M, a.DC);      // (conv_plan.h)
+    return t.tch == 256 ? rr_launch(conv16_igemm_kernel<256>, dim3(t.grid), 512, t.lds, stream, a, name)
+                        : rr_launch(conv16_igemm_kernel<128>, dim3(t.grid), 512, t.lds, stream, a, name);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -533,10 +523,7 @@ __global__ __launch_bounds__(512, 1) void conv16_wgrad_kernel(const WArgs a)
 
 extern "C" {
 
-int rr_conv16_supported(int c, int k, int r, int s, int stride)
-{
-    return c % BK == 0 && k % 128 == 0 && r * s <= 16 && (stride == 1 || stride == 2);
-}
+int rr_conv16_supported(int c, int k, int r, int s, int stride) { return rr_plan::conv16_supported(c, k, r, s, stride); }
 
 size_t rr_conv16_stat_slab_bytes(int n, int p, int q, int k) { return sizeof(double) * 2 * (size_t)rr_cdiv((long)n * p * q, TP) * k; }
 
@@ -589,67 +576,39 @@ int rr_conv16_dgrad_s1_relumask(const unsigned short *dy, const unsigned short *
 int rr_conv16_dgrad_s2(const unsigned short *dy, const float *w, float *dx, int n, int h, int wd, int c, int k, int r, int s,
                        int pad_h, int pad_w, int accumulate, unsigned short *wsub, hipStream_t stream)
 {
-    RR_CHECK_ARG(n > 0 && h > 0 && wd > 0 && dy && w && dx && wsub && pad_h >= 0 && pad_w >= 0, "rr_conv16_dgrad_s2: bad arguments");
-    RR_CHECK_ARG(k % BK == 0 && c % 128 == 0 && r * s <= 16, "rr_conv16_dgrad_s2: unsupported shape c=%d k=%d %dx%d", c, k, r, s);
-    const int p = (h + 2 * pad_h - r) / 2 + 1, q = (wd + 2 * pad_w - s) / 2 + 1;
-    RR_CHECK_ARG(p > 0 && q > 0 && (long)n * p * q * k * 2 < (1l << 31), "rr_conv16_dgrad_s2: empty or oversized dy");
-    // csrc/conv_bf16.hip's decomposition (rr_plan::parity_classes: a stride-1 correlation per output parity class with the
+    // csrc/conv_bf16.hip's decomposition (rr_plan::dgrad_s2_plan: a stride-1 correlation per output parity class with the
     // sub-filter of the taps that reach it); here the sub-filters are packed straight to bf16
-    if (int rc = rr_parity_pack(w, wsub, k, c, r, s, pad_h, pad_w, stream, "rr_conv16_dgrad_s2")) return rc;
-    rr_plan::ParityClass cls[4];
-    const bool any_empty = rr_plan::parity_classes(h, wd, r, s, pad_h, pad_w, cls);
-    for (const rr_plan::ParityClass &pc : cls)
-        RR_CHECK_ARG(pc.taps() == 0 || (pc.lead_h >= 0 && pc.lead_w >= 0), "rr_conv16_dgrad_s2: unsupported padding %d,%d", pad_h, pad_w);
-    if (any_empty && !accumulate) RR_CHECK_HIP(hipMemsetAsync(dx, 0, sizeof(float) * (size_t)n * h * wd * c, stream), "rr_conv16_dgrad_s2");
-    for (const rr_plan::ParityClass &pc : cls) {
-        if (pc.taps() == 0 || pc.Hc <= 0 || pc.Wc <= 0) continue;
+    const char *name = "rr_conv16_dgrad_s2";
+    const rr_plan::ConvGeom g{n, h, wd, c, k, r, s, 2, pad_h, pad_w, 0, 0};
+    const rr_plan::DgradS2Plan pl = rr_plan::dgrad_s2_plan(rr_plan::FAM_CONV16, g, accumulate != 0, dy && w && dx && wsub);
+    if (pl.refuse.why) return rr_refuse(name, pl.refuse);
+    return rr_dgrad_s2_run(pl, g, w, wsub, dx, stream, name, [&](const rr_plan::ParityClass &pc) {
         Args a{};
         a.src = dy; a.flt = wsub + (long)pc.taps_before * c * k; a.dst = dx;
-        a.N = n; a.SH = p; a.SW = q; a.SC = k; a.DC = c; a.R = pc.Rc; a.S = pc.Sc; a.stride = 1;
+        a.N = n; a.SH = pl.p; a.SW = pl.q; a.SC = k; a.DC = c; a.R = pc.Rc; a.S = pc.Sc; a.stride = 1;
         a.pad_h = pc.lead_h; a.pad_w = pc.lead_w;
         a.DH = pc.Hc; a.DW = pc.Wc; a.M = n * pc.Hc * pc.Wc;
         a.accumulate = accumulate;
         a.OH = h; a.OW = wd; a.osh = 2; a.osw = 2; a.oh0 = pc.ph; a.ow0 = pc.pw;
-        if (int rc = launch_igemm(a, stream, "rr_conv16_dgrad_s2")) return rc;
-    }
-    return RR_OK;
+        return launch_igemm(a, stream, name);
+    });
 }
 
-int rr_conv16_wgrad_supported(int c, int k, int r, int s, int stride)
-{
-    return k % 128 == 0 && c % 128 == 0 && r * s <= 64 && (stride == 1 || stride == 2);     // (K % 256 == 128: the last 256-filter tile runs half empty)
-}
+int rr_conv16_wgrad_supported(int c, int k, int r, int s, int stride) { return rr_plan::conv16_wgrad_supported(c, k, r, s, stride); }
 
 int rr_conv16_wgrad(const unsigned short *x, const unsigned short *dy, float *dw, int n, int h, int wd, int c, int k,
                     int r, int s, int stride, int pad_h, int pad_w, hipStream_t stream)
 {
-    RR_CHECK_ARG(n > 0 && h > 0 && wd > 0 && x && dy && dw, "rr_conv16_wgrad: bad arguments");
-    RR_CHECK_ARG(rr_conv16_wgrad_supported(c, k, r, s, stride), "rr_conv16_wgrad: unsupported shape c=%d k=%d %dx%d stride %d", c, k, r, s, stride);
+    RR_CHECK_ARG(x && dy && dw, "rr_conv16_wgrad: bad arguments");
+    const rr_plan::WgradPlan pl = rr_plan::wgrad_plan(rr_plan::FAM_CONV16, {n, h, wd, c, k, r, s, stride, pad_h, pad_w, 0, 0});
+    if (pl.refuse.why) return rr_refuse("rr_conv16_wgrad", pl.refuse);
     WArgs a{};
     a.x = x; a.dy = dy; a.dw = dw;
     a.N = n; a.H = h; a.W = wd; a.C = c; a.K = k; a.R = r; a.S = s; a.stride = stride; a.pad_h = pad_h; a.pad_w = pad_w;
-    a.P = (h + 2 * pad_h - r) / stride + 1;
-    a.Q = (wd + 2 * pad_w - s) / stride + 1;
-    RR_CHECK_ARG(a.P > 0 && a.Q > 0, "rr_conv16_wgrad: empty output");
-    a.M = n * a.P * a.Q;
-    RR_CHECK_ARG((long)a.M * k * 2 < (1l << 31) && (long)n * h * wd * c * 2 < (1l << 31), "rr_conv16_wgrad: tensor beyond 2 GiB");
-    const int nt_w = c % 256 == 0 ? 256 : 128;
-    a.kt = rr_cdiv(k, 256);
-    a.nt = c / nt_w;
-    const int tiles = a.kt * a.nt * r * s;
-    const int total_steps = rr_cdiv(a.M, 32);
-    // pixel splits: fill the 256 CUs (one 512-thread workgroup each) about twice, never fewer than 32 K-steps per split
-    const int splits = rr_plan::pixel_splits(tiles, total_steps, 512, 32, &a.steps_per_split);
-    const size_t ldsb = 4 * (size_t)(8 * 2048 + (nt_w / 32) * 2048);
-    if (nt_w == 256) {
-        RR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(conv16_wgrad_kernel<256>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb), "rr_conv16_wgrad");
-        hipLaunchKernelGGL(conv16_wgrad_kernel<256>, dim3(tiles * splits), dim3(512), ldsb, stream, a);
-    } else {
-        RR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(conv16_wgrad_kernel<128>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb), "rr_conv16_wgrad");
-        hipLaunchKernelGGL(conv16_wgrad_kernel<128>, dim3(tiles * splits), dim3(512), ldsb, stream, a);
-    }
-    RR_CHECK_LAUNCH("rr_conv16_wgrad");
-    return RR_OK;
+    a.P = pl.P; a.Q = pl.Q; a.M = (int)pl.M;
+    a.kt = pl.mt; a.nt = pl.nt; a.steps_per_split = pl.per_split;
+    return pl.bn == 256 ? rr_launch(conv16_wgrad_kernel<256>, dim3(pl.grid), 512, pl.lds, stream, a, "rr_conv16_wgrad")
+                        : rr_launch(conv16_wgrad_kernel<128>, dim3(pl.grid), 512, pl.lds, stream, a, "rr_conv16_wgrad");
 }
 
 }  // extern "C"

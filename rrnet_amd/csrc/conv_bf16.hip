@@ -566,10 +566,10 @@ int fprop_impl(const char *name, const Math16 &mt, const float *x, const float *
     if (int rc = rr_conv_before_launch(pl, n, k, y, stat_slab, stream, name)) return rc;
     int rc;
 #define RR_IG(BNv, BNSv, SOv)                                                                                      \
-    (a.w16 ? rr_launch(conv_igemm_bf16_kernel<BNv, BNSv, true, SOv>, dim3(blocks, 1, ks), igemm_lds(BNv), stream, a, name)           \
-           : rr_launch(conv_igemm_bf16_kernel<BNv, BNSv, false, SOv>, dim3(blocks, 1, ks), igemm_lds(BNv), stream, a, name))
+    (a.w16 ? rr_launch(conv_igemm_bf16_kernel<BNv, BNSv, true, SOv>, dim3(blocks, 1, ks), 256, igemm_lds(BNv), stream, a, name)           \
+           : rr_launch(conv_igemm_bf16_kernel<BNv, BNSv, false, SOv>, dim3(blocks, 1, ks), 256, igemm_lds(BNv), stream, a, name))
     // split operands (rr_conv_*_f16x3): two fp16 parts per operand, three matrix instructions per product tile
-#define RR_SX(BNv, BNSv, SOv) rr_launch(conv_igemm_bf16_kernel<BNv, BNSv, false, SOv, 2, false, true>, dim3(blocks, 1, ks), igemm_lds(BNv, 2), stream, a, name)
+#define RR_SX(BNv, BNSv, SOv) rr_launch(conv_igemm_bf16_kernel<BNv, BNSv, false, SOv, 2, false, true>, dim3(blocks, 1, ks), 256, igemm_lds(BNv, 2), stream, a, name)
     // the instance of launcher L for (fused sums | strided destination | plain) x tile width
 #define RR_PICK(L) (fused ? RR_PICK_BN(L, true, false) : a.osh ? RR_PICK_BN(L, false, true) : RR_PICK_BN(L, false, false))
 #define RR_PICK_BN(L, BNSv, SOv) (bn == 128 ? L(128, BNSv, SOv) : bn == 64 ? L(64, BNSv, SOv) : L(32, BNSv, SOv))
@@ -581,7 +581,7 @@ int fprop_impl(const char *name, const Math16 &mt, const float *x, const float *
         if (mt.filter16 != nullptr && c % 8 == 0 && bn == 128) {
             // the filter's two fp16 images, made by rr_weight_split_f16 (once per optimizer step, outside the backward pass): the B16 instantiation
             a.w16 = mt.filter16;
-#define RR_SB(BNSv, SOv) rr_launch(conv_igemm_bf16_kernel<128, BNSv, true, SOv, 2, false, true>, dim3(blocks, 1, ks), igemm_lds(128, 2), stream, a, name)
+#define RR_SB(BNSv, SOv) rr_launch(conv_igemm_bf16_kernel<128, BNSv, true, SOv, 2, false, true>, dim3(blocks, 1, ks), 256, igemm_lds(128, 2), stream, a, name)
             rc = fused ? RR_SB(true, false) : (a.osh ? RR_SB(false, true) : RR_SB(false, false));
 #undef RR_SB
         } else
@@ -880,26 +880,15 @@ extern "C" int rr_conv_dgrad_s1_relubias_bf16(const float *dy, const float *wt, 
 static int dgrad_s2_impl(const char *name, const Math16 &mt, const float *dy, const float *w, float *dx, int n, int h, int wd, int c, int k,
                          int r, int s, int pad_h, int pad_w, int accumulate, float *wsub, hipStream_t stream)
 {
-    RR_CHECK_ARG(n > 0 && h > 0 && wd > 0 && c > 0 && k > 0 && r > 0 && s > 0, "%s: bad dims", name);
-    RR_CHECK_ARG(c % 4 == 0 && k % 4 == 0 && r * s <= 64 && pad_h >= 0 && pad_w >= 0 && wsub != nullptr && (!mt.split || (mt.amax_src && mt.amax_w)),
-                 "%s: C, K multiples of 4, R*S <= 64, scratch of k*r*s*c floats (and, split operands, the two maxima) required", name);
-    const int p = (h + 2 * pad_h - r) / 2 + 1, q = (wd + 2 * pad_w - s) / 2 + 1;
-    RR_CHECK_ARG(p > 0 && q > 0, "%s: empty dy", name);
-    if (int rc = rr_parity_pack(w, wsub, k, c, r, s, pad_h, pad_w, stream, name)) return rc;
-    rr_plan::ParityClass cls[4];
-    const bool any_empty = rr_plan::parity_classes(h, wd, r, s, pad_h, pad_w, cls);
-    for (const rr_plan::ParityClass &pc : cls)
-        RR_CHECK_ARG(pc.taps() == 0 || (pc.lead_h >= 0 && pc.lead_w >= 0), "%s: unsupported padding %d,%d", name, pad_h, pad_w);
-    // parity classes no tap reaches (a 1x1 stride 2: three of four) are zero
-    if (any_empty && !accumulate) RR_CHECK_HIP(hipMemsetAsync(dx, 0, sizeof(float) * (size_t)n * h * wd * c, stream), name);
-    for (const rr_plan::ParityClass &pc : cls) {
-        if (pc.taps() == 0 || pc.Hc <= 0 || pc.Wc <= 0) continue;
+    const rr_plan::ConvGeom g{n, h, wd, c, k, r, s, 2, pad_h, pad_w, 0, 0};
+    const rr_plan::DgradS2Plan pl = rr_plan::dgrad_s2_plan(mt.split ? rr_plan::MATH_F16X3 : rr_plan::MATH_BF16, g, accumulate != 0,
+                                                           wsub != nullptr && (!mt.split || (mt.amax_src && mt.amax_w)));
+    if (pl.refuse.why) return rr_refuse(name, pl.refuse);
+    return rr_dgrad_s2_run(pl, g, w, wsub, dx, stream, name, [&](const rr_plan::ParityClass &pc) {
         const OutMap om{pc.Hc, pc.Wc, h, wd, 2, 2, pc.ph, pc.pw};
-        if (int rc = fprop_impl(name, mt, dy, wsub + (long)pc.taps_before * c * k, nullptr, dx, nullptr, n, p, q, k, c, pc.Rc, pc.Sc, 1, pc.lead_h,
-                                pc.lead_w, 0, accumulate, stream, nullptr, &om))
-            return rc;
-    }
-    return RR_OK;
+        return fprop_impl(name, mt, dy, wsub + (long)pc.taps_before * c * k, nullptr, dx, nullptr, n, pl.p, pl.q, k, c, pc.Rc, pc.Sc, 1, pc.lead_h,
+                          pc.lead_w, 0, accumulate, stream, nullptr, &om);
+    });
 }
 
 extern "C" int rr_conv_dgrad_s2_bf16(const float *dy, const float *w, float *dx, int n, int h, int wd, int c, int k,
@@ -908,32 +897,23 @@ extern "C" int rr_conv_dgrad_s2_bf16(const float *dy, const float *w, float *dx,
     return dgrad_s2_impl("rr_conv_dgrad_s2_bf16", {0, nullptr}, dy, w, dx, n, h, wd, c, k, r, s, pad_h, pad_w, accumulate, wsub, stream);
 }
 
+// How it launches is rr_plan::wgrad_plan's decision (conv_plan.h); both arithmetics refuse under rr_conv_wgrad_bf16's name.
 static int wgrad_impl(const float *x, const float *dy, float *dw, int n, int h, int wd, int c, int k, int r, int s, int stride,
                       int pad_h, int pad_w, int out_h, int out_w, hipStream_t stream, int split, const unsigned *amax_x,
                       const unsigned *amax_dy)
 {
-    RR_CHECK_ARG(n > 0 && h > 0 && wd > 0 && c > 0 && k > 0 && r > 0 && s > 0 && stride > 0, "rr_conv_wgrad_bf16: bad dims");
-    RR_CHECK_ARG(c % 4 == 0 && k % 4 == 0, "rr_conv_wgrad_bf16: C=%d, K=%d must be multiples of 4 (fp32 path for the rest)", c, k);
+    const rr_plan::WgradPlan pl = rr_plan::wgrad_plan(split ? rr_plan::MATH_F16X3 : rr_plan::MATH_BF16,
+                                                      {n, h, wd, c, k, r, s, stride, pad_h, pad_w, out_h, out_w});
+    if (pl.refuse.why) return rr_refuse("rr_conv_wgrad_bf16", pl.refuse);
     WgradArgs a{};
     a.x = x; a.dy = dy; a.dw = dw;
     a.amax_x = amax_x; a.amax_dy = amax_dy;
     a.N = n; a.H = h; a.W = wd; a.C = c; a.K = k; a.R = r; a.S = s;
-    a.P = out_h > 0 ? out_h : (h + 2 * pad_h - r) / stride + 1;
-    a.Q = out_w > 0 ? out_w : (wd + 2 * pad_w - s) / stride + 1;
+    a.P = pl.P; a.Q = pl.Q;
     a.stride = stride; a.pad_h = pad_h; a.pad_w = pad_w;
-    const long M = (long)n * a.P * a.Q;
-    RR_CHECK_ARG(M > 0 && M < (1l << 31) && M * k * 4 < (1l << 31) && (long)n * h * wd * c * 4 < (1l << 31),
-                 "rr_conv_wgrad_bf16: tensors must stay below 2 GiB (32-bit buffer offsets)");
-    a.M = (int)M;
-    a.mt = rr_cdiv(k, 128); a.nt = rr_cdiv(c, 128);
-    const int tiles = a.mt * a.nt * r * s;
-    const int total_chunks = rr_cdiv(M, BK);
-    // pixel splits: fill the resident-workgroup slots (256 CUs x 4; x 2 for the split kernel's 68 KB of LDS) once, never fewer
-    // than 16 K-steps per split
-    const int splits = rr_plan::pixel_splits(tiles, total_chunks, split ? 512 : 1024, 16, &a.chunks_per_split);
-    const size_t lds = sizeof(unsigned short) * 4 * 4 * (32 * 32 + 32) * (split ? 2 : 1);  // 2 operands x 2 buffers x (parts) x 4 blocks of 32 x 32 (+ pad)
-    return split ? rr_launch(conv_wgrad_bf16_kernel<2, true>, dim3(tiles * splits), lds, stream, a, "rr_conv_wgrad_f16x3")
-                 : rr_launch(conv_wgrad_bf16_kernel<1, false>, dim3(tiles * splits), lds, stream, a, "rr_conv_wgrad_bf16");
+    a.M = (int)pl.M; a.mt = pl.mt; a.nt = pl.nt; a.chunks_per_split = pl.per_split;
+    return split ? rr_launch(conv_wgrad_bf16_kernel<2, true>, dim3(pl.grid), 256, pl.lds, stream, a, "rr_conv_wgrad_f16x3")
+                 : rr_launch(conv_wgrad_bf16_kernel<1, false>, dim3(pl.grid), 256, pl.lds, stream, a, "rr_conv_wgrad_bf16");
 }
 
 extern "C" int rr_conv_wgrad_bf16(const float *x, const float *dy, float *dw, int n, int h, int wd, int c, int k,

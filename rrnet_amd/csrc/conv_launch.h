@@ -1,5 +1,5 @@
 // What csrc/conv.hip, conv_bf16.hip and conv16.hip do around a launch in the same way: the work a plan (conv_plan.h) asks for in
-// front of and behind a forward-kernel launch, the geometry flip of the stride-1 data gradients, the sub-filter pack of the stride-2 ones.
+// front of and behind a forward-kernel launch, the geometry flip of the stride-1 data gradients, the sub-filter pack and class loop of the stride-2 ones.
 #pragma once
 #include "common.h"
 #include "conv_plan.h"
@@ -22,13 +22,22 @@ struct BnSumArgs {
 
 // One launch: above 48 KiB of dynamic LDS the kernel's limit is raised first (per device, so on every launch).
 template <typename K, typename A>
-inline int rr_launch(K kern, dim3 grid, size_t lds, hipStream_t stream, const A &args, const char *name)
+inline int rr_launch(K kern, dim3 grid, int threads, size_t lds, hipStream_t stream, const A &args, const char *name)
 {
     if (lds > 48 * 1024)
         RR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), name);
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, args);
+    hipLaunchKernelGGL(kern, grid, dim3(threads), lds, stream, args);
     RR_CHECK_LAUNCH(name);
     return RR_OK;
+}
+
+// a gradient plan's refusal as the error of entry point `name` (the plan's text follows the name)
+inline int rr_refuse(const char *name, const rr_plan::Refusal &r)
+{
+    char why[256];
+    snprintf(why, sizeof(why), r.why, r.a[0], r.a[1], r.a[2], r.a[3], r.a[4]);
+    rr_set_error("%s: %s", name, why);
+    return RR_ERR_ARG;
 }
 
 inline int rr_conv_link(const BnSumArgs *bs) { return bs == nullptr ? rr_plan::LINK_NONE : (bs->relu_bias ? rr_plan::LINK_RELU_BIAS : rr_plan::LINK_BN); }
@@ -104,5 +113,18 @@ inline int rr_parity_pack(const float *w, T *wsub, int k, int c, int r, int s, i
     hipLaunchKernelGGL(rr_parity_pack_kernel<T>, dim3((int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256)), dim3(256), 0, stream, w, wsub,
                        k, c, r, s, pad_h, pad_w, total);
     RR_CHECK_LAUNCH(name);
+    return RR_OK;
+}
+
+// A parity-class data gradient carried out (rr_plan::dgrad_s2_plan): the sub-filters packed, dx cleared where a class with
+// pixels has no tap, then launch_class(ParityClass) -> error code for every class that launches.
+template <typename T, typename F>
+inline int rr_dgrad_s2_run(const rr_plan::DgradS2Plan &pl, const rr_plan::ConvGeom &g, const float *w, T *wsub, float *dx, hipStream_t stream,
+                           const char *name, F launch_class)
+{
+    if (int rc = rr_parity_pack(w, wsub, g.k, g.c, g.r, g.s, g.pad_h, g.pad_w, stream, name)) return rc;
+    if (pl.zero_dst) RR_CHECK_HIP(hipMemsetAsync(dx, 0, sizeof(float) * (size_t)g.n * g.h * g.w * g.c, stream), name);
+    for (int i = 0; i < pl.n_launch; ++i)
+        if (int rc = launch_class(pl.cls[i])) return rc;
     return RR_OK;
 }

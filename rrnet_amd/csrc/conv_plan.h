@@ -1,14 +1,17 @@
-// The host launch plan of the implicit-GEMM convolutions, plain C++ with no HIP include (it compiles with a host compiler alone).
+// The host launch plans of the convolutions, plain C++ with no HIP include (it compiles with a host compiler alone).
 // HOW a "forward-kernel" convolution launches — tile width, split-K, zero fill, statistics fused or in a second pass, which
 // BatchNorm-backward sums ride in the epilogue — is decided in fprop_plan, for csrc/conv.hip (fp32) and csrc/conv_bf16.hip (16-bit)
 // alike; rr_conv_fprop_plan (include/rrnet_hip.h) shows it to the tests, whose Python mirror (tests/helpers.py) answers to it.
-// Next to it: the parity classes of a stride-2 data gradient and the pixel split of the weight gradients.
+// The gradients have the same arrangement: dgrad_plan (rr_conv_dgrad), dgrad_s2_plan (the parity-class data gradients of
+// conv_bf16.hip and conv16.hip) and wgrad_plan (the weight gradients of all three files) decide, the entry points carry out, and
+// rr_conv_grad_plan shows them.  Next to them: the tile rule and shape predicates of csrc/conv16.hip.
 #pragma once
 #include <stdlib.h>
 
 namespace rr_plan {
 
 enum { MATH_F32 = 0, MATH_BF16 = 1, MATH_F16X3 = 2 };                   // ops.MATH_*
+enum { FAM_CONV16 = 3 };                                                // a gradient plan's family: a MATH_*, or the 16-bit-activation kernels of csrc/conv16.hip
 enum { LINK_NONE = 0, LINK_BN = 1, LINK_RELU_BIAS = 2 };                // whose backward sums the epilogue carries (ConvArgs::bs_y)
 enum { AFTER_NONE = 0, AFTER_REDUCE_SLAB = 1, AFTER_BWD_REDUCE = 2, AFTER_COLSTATS = 3 };   // FpropPlan::after
 
@@ -171,6 +174,115 @@ inline bool parity_classes(int h, int w, int r, int s, int pad_h, int pad_w, Par
     return any_empty;
 }
 
+// ---- the gradient passes.  A plan's refusal: why, a printf format for a[] without the entry point's name (null: the call is taken)
+struct Refusal { const char *why; int a[5]; };
+enum { GRAD_DGRAD = 0, GRAD_DGRAD_S2 = 1, GRAD_WGRAD = 2 };              // the pass argument of rr_conv_grad_plan
+
+// ---- rr_conv_dgrad (fp32, any stride): the gather kernel of csrc/conv.hip, at stride 2 over the parity classes in one launch
+struct DgradPlan {
+    Refusal refuse;
+    long M;               // n * h * w
+    int scalar;           // scalar gather
+    int bn;               // tile width 128 / 64 / 32
+    int blocks, gy;       // grid.x: workgroups of one class (of the whole map without parity); grid.y: the classes that have taps
+    int parity;           // stride 2 on the vector kernels: parity-decomposed, 4 classes of ceil(h/2) x ceil(w/2) pixels each
+    int parity_order;     // the classes by falling tap count, two bits each (ConvArgs::parity_order)
+    int ks;               // split-K factor (grid.z)
+    int zero_dst;         // dx is zero-filled in front: a class without taps, or split-K, and the call does not accumulate
+};
+
+inline DgradPlan dgrad_plan(const ConvGeom &g, bool accumulate)
+{
+    DgradPlan p{};
+    const int n = g.n, h = g.h, w = g.w, c = g.c, k = g.k, r = g.r, s = g.s, stride = g.stride;
+    if (!(n > 0 && h > 0 && w > 0 && c > 0 && k > 0 && r > 0 && s > 0 && stride > 0)) { p.refuse = {"bad dims"}; return p; }
+    const long M = p.M = (long)n * h * w;
+    if (!(M < (1l << 31))) { p.refuse = {"tensor too large"}; return p; }
+    const bool scalar = (k % 4) != 0 || (c % 4) != 0 || r * s > 64 || stride > 2;
+    int bn = c > 64 ? 128 : (c > 32 ? (!scalar ? 64 : 128) : 32);
+    if (bn == 128 && !scalar && stride == 1 && cdiv(M, BM) * cdiv(c, 128) <= small_tiles()) bn = 32;
+    else if (bn == 128 && !scalar && stride == 1 && cdiv(M, BM) * cdiv(c, 128) <= mid_tiles()) bn = 64;
+    p.scalar = scalar; p.bn = bn; p.gy = 1;
+    p.blocks = cdiv(M, BM) * cdiv(c, bn);
+    int nk = scalar ? cdiv((long)r * s * k, BK) : cdiv(k, BK) * r * s;
+    if (stride == 2 && !scalar) {
+        p.parity = 1;
+        ParityClass cls[4];
+        parity_classes(h, w, r, s, g.pad_h, g.pad_w, cls);
+        int ord[4] = {0, 1, 2, 3};
+        for (int i = 0; i < 4; ++i)
+            for (int j = i + 1; j < 4; ++j)
+                if (cls[ord[j]].taps() > cls[ord[i]].taps()) { const int t = ord[i]; ord[i] = ord[j]; ord[j] = t; }
+        p.parity_order = ord[0] | (ord[1] << 2) | (ord[2] << 4) | (ord[3] << 6);
+        // classes without any tap (1x1 stride 2: three of four) produce zeros: one memset instead of workgroups
+        // that run an empty K loop and store zeros element by element
+        // (when accumulating they add nothing: no workgroups at all)
+        p.gy = 4;
+        while (p.gy > 1 && cls[ord[p.gy - 1]].taps() == 0) --p.gy;
+        p.blocks = cdiv((long)n * ((h + 1) / 2) * ((w + 1) / 2), BM) * cdiv(c, bn);
+        nk = cdiv(k, BK) * ((r + 1) / 2) * ((s + 1) / 2);
+    }
+    p.ks = p.parity ? 1 : pick_ksplit(p.blocks, nk);
+    p.zero_dst = ((p.parity && p.gy < 4) || p.ks > 1) && !accumulate;
+    return p;
+}
+
+// ---- csrc/conv16.hip: which shapes its kernels take, and the forward kernel's tile (fprop, stride-1 and parity-class data gradients)
+inline bool conv16_supported(int c, int k, int r, int s, int stride) { return c % 64 == 0 && k % 128 == 0 && r * s <= 16 && (stride == 1 || stride == 2); }
+inline bool conv16_wgrad_supported(int c, int k, int r, int s, int stride)
+{
+    return k % 128 == 0 && c % 128 == 0 && r * s <= 64 && (stride == 1 || stride == 2);     // (K % 256 == 128: the last 256-filter tile runs half empty)
+}
+struct Conv16Tile { int tch, grid, lds; };     // output channels per tile (256 pixels wide), workgroups, dynamic LDS bytes
+inline Conv16Tile conv16_tile(long M, int dc)
+{
+    if (dc % 256 == 0) return {256, cdiv(M, 256) * (dc / 256), 2 * (256 * 128 + 256 * 128)};   // 2 buffers x (pixel image + filter image, 128-byte rows)
+    return {128, cdiv(M, 256) * (dc / 128), 128 * 1024};                                         // (two buffers need 96 KiB; the statistics epilogue's table 128)
+}
+
+// ---- the parity-class data gradients rr_conv_dgrad_s2_bf16 / _f16x3 (family MATH_BF16 / MATH_F16X3) and rr_conv16_dgrad_s2
+// (FAM_CONV16): one forward-kernel launch per class that has taps and pixels, into a strided destination.  How each of them
+// launches is fprop_plan's decision (strided_dst) or conv16_tile's.
+struct DgradS2Plan {
+    Refusal refuse;
+    int p, q;             // dy's grid
+    int zero_dst;         // dx is zero-filled in front: a class with pixels has no tap, and the call does not accumulate
+    int n_launch;
+    ParityClass cls[4];   // the classes that launch, in their order
+    int blocks[4];        // FAM_CONV16: workgroups of the class's launch
+};
+
+// ptrs: the scratch (and the split operands' maxima) are there — their absence shares a refusal text with the shape
+inline DgradS2Plan dgrad_s2_plan(int family, const ConvGeom &g, bool accumulate, bool ptrs = true)
+{
+    DgradS2Plan p{};
+    const int n = g.n, h = g.h, w = g.w, c = g.c, k = g.k, r = g.r, s = g.s, pad_h = g.pad_h, pad_w = g.pad_w;
+#define RR_PLAN_REFUSE(cond, ...) do { if (cond) { p.refuse = {__VA_ARGS__}; return p; } } while (0)
+    if (family == FAM_CONV16) {
+        RR_PLAN_REFUSE(!(n > 0 && h > 0 && w > 0 && pad_h >= 0 && pad_w >= 0 && ptrs), "bad arguments");
+        RR_PLAN_REFUSE(!(k % 64 == 0 && c % 128 == 0 && r * s <= 16), "unsupported shape c=%d k=%d %dx%d", {c, k, r, s});
+    } else {
+        RR_PLAN_REFUSE(!(n > 0 && h > 0 && w > 0 && c > 0 && k > 0 && r > 0 && s > 0), "bad dims");
+        RR_PLAN_REFUSE(!(c % 4 == 0 && k % 4 == 0 && r * s <= 64 && pad_h >= 0 && pad_w >= 0 && ptrs),
+                       "C, K multiples of 4, R*S <= 64, scratch of k*r*s*c floats (and, split operands, the two maxima) required");
+    }
+    p.p = (h + 2 * pad_h - r) / 2 + 1; p.q = (w + 2 * pad_w - s) / 2 + 1;
+    if (family == FAM_CONV16) RR_PLAN_REFUSE(!(p.p > 0 && p.q > 0 && (long)n * p.p * p.q * k * 2 < (1l << 31)), "empty or oversized dy");
+    else RR_PLAN_REFUSE(!(p.p > 0 && p.q > 0), "empty dy");
+    ParityClass cls[4];
+    const bool any_empty = parity_classes(h, w, r, s, pad_h, pad_w, cls);
+    for (const ParityClass &pc : cls)
+        RR_PLAN_REFUSE(!(pc.taps() == 0 || (pc.lead_h >= 0 && pc.lead_w >= 0)), "unsupported padding %d,%d", {pad_h, pad_w});
+#undef RR_PLAN_REFUSE
+    p.zero_dst = any_empty && !accumulate;      // parity classes no tap reaches (a 1x1 stride 2: three of four) are zero
+    for (const ParityClass &pc : cls) {
+        if (pc.taps() == 0 || pc.Hc <= 0 || pc.Wc <= 0) continue;
+        if (family == FAM_CONV16) p.blocks[p.n_launch] = conv16_tile((long)n * pc.Hc * pc.Wc, c).grid;
+        p.cls[p.n_launch++] = pc;
+    }
+    return p;
+}
+
 // ---- weight gradients: split the pixel (K) dimension so that tiles * splits fills the `slots` resident workgroups exactly once (equal-length
 // workgroups in more than one round pay a whole extra round for any remainder), never fewer than `min_chunks` K-steps per split.  -> splits
 inline int pixel_splits(int tiles, int total_chunks, int slots, int min_chunks, int *per_split)
@@ -180,6 +292,75 @@ inline int pixel_splits(int tiles, int total_chunks, int slots, int min_chunks, 
     if (splits < 1) splits = 1;
     *per_split = cdiv(total_chunks, splits);
     return cdiv(total_chunks, *per_split);
+}
+
+// the slots and the fewest K-steps per split of each weight-gradient kernel
+struct WgradFill { int slots, min_chunks; };
+constexpr WgradFill WGRAD_F32_PIPE3 = {768, 8};      // resident workgroups: 256 CUs x 3 with one LDS image,
+constexpr WgradFill WGRAD_F32 = {512, 8};            // else x 2
+constexpr WgradFill WGRAD_BF16 = {1024, 16};         // 256 CUs x 4, never fewer than 16 K-steps per split;
+constexpr WgradFill WGRAD_F16X3 = {512, 16};         // x 2 for the split kernel's 68 KB of LDS
+constexpr WgradFill WGRAD_CONV16 = {512, 32};        // the 256 CUs (one 512-thread workgroup each) about twice, never fewer than 32 K-steps per split
+
+// rr_conv_wgrad (MATH_F32), rr_conv_wgrad_bf16 / _f16x3, rr_conv16_wgrad (FAM_CONV16, which has no out_h / out_w override)
+struct WgradPlan {
+    Refusal refuse;
+    int P, Q;             // dy's grid.  out_h / out_w > 0 override the symmetric-padding output size (pad_h / pad_w are the LEADING pads;
+                          // taps that fall past the far edge are masked), which is how asymmetric padding is expressed
+    long M;               // n * P * Q
+    int bm, bn;           // tile: filters x channels (fp32: 128|32 x 128|32, 16-bit: 128 x 128, conv16: 256 x 256|128)
+    int a_scalar, b_scalar, pipe;    // fp32: scalar loads of dy / x (K / C not multiples of 4); PIPE of the 128x128 kernel, 0: the generic tiles
+    int mt, nt, tiles;    // tiles along K and C; mt * nt * r * s
+    int splits, per_split, grid, lds;
+};
+
+inline WgradPlan wgrad_plan(int family, const ConvGeom &g)
+{
+    WgradPlan p{};
+    const int n = g.n, h = g.h, w = g.w, c = g.c, k = g.k, r = g.r, s = g.s, stride = g.stride;
+    const long G2 = 1l << 31;
+    const bool conv16 = family == FAM_CONV16;
+#define RR_PLAN_REFUSE(cond, ...) do { if (cond) { p.refuse = {__VA_ARGS__}; return p; } } while (0)
+    if (conv16) {
+        RR_PLAN_REFUSE(!(n > 0 && h > 0 && w > 0), "bad arguments");
+        RR_PLAN_REFUSE(!conv16_wgrad_supported(c, k, r, s, stride), "unsupported shape c=%d k=%d %dx%d stride %d", {c, k, r, s, stride});
+    } else {
+        RR_PLAN_REFUSE(!(n > 0 && h > 0 && w > 0 && c > 0 && k > 0 && r > 0 && s > 0 && stride > 0), "bad dims");
+        RR_PLAN_REFUSE(family != MATH_F32 && !(c % 4 == 0 && k % 4 == 0), "C=%d, K=%d must be multiples of 4 (fp32 path for the rest)", {c, k});
+    }
+    p.P = g.out_h > 0 && !conv16 ? g.out_h : (h + 2 * g.pad_h - r) / stride + 1;
+    p.Q = g.out_w > 0 && !conv16 ? g.out_w : (w + 2 * g.pad_w - s) / stride + 1;
+    const long M = p.M = (long)n * p.P * p.Q, x_elems = (long)n * h * w * c;
+    WgradFill fill;
+    if (conv16) {
+        RR_PLAN_REFUSE(!(p.P > 0 && p.Q > 0), "empty output");
+        RR_PLAN_REFUSE(!(M * k * 2 < G2 && x_elems * 2 < G2), "tensor beyond 2 GiB");
+        p.bm = 256; p.bn = c % 256 == 0 ? 256 : 128;
+        p.mt = cdiv(k, 256); p.nt = c / p.bn;
+        fill = WGRAD_CONV16;
+        p.lds = 4 * (8 * 2048 + (p.bn / 32) * 2048);       // 4 stages x (dY blocks + X blocks of [32 pixels][32 channels] bf16)
+    } else if (family != MATH_F32) {
+        RR_PLAN_REFUSE(!(M > 0 && M < G2 && M * k * 4 < G2 && x_elems * 4 < G2), "tensors must stay below 2 GiB (32-bit buffer offsets)");
+        p.bm = p.bn = 128;
+        p.mt = cdiv(k, 128); p.nt = cdiv(c, 128);
+        fill = family == MATH_F16X3 ? WGRAD_F16X3 : WGRAD_BF16;
+        p.lds = 2 * 4 * 4 * (32 * 32 + 32) * (family == MATH_F16X3 ? 2 : 1);  // 2 operands x 2 buffers x (parts) x 4 blocks of 32 x 32 (+ pad), 16-bit
+    } else {
+        RR_PLAN_REFUSE(!(M > 0 && M < G2), "bad pixel count");
+        p.bm = k > 32 ? 128 : 32; p.bn = c > 32 ? 128 : 32;
+        p.mt = cdiv(k, p.bm); p.nt = cdiv(c, p.bn);
+        p.a_scalar = (k % 4) != 0; p.b_scalar = (c % 4) != 0;
+        // pipelined 128x128 variants: 32-bit buffer offsets, both tensors below 2 GiB
+        const bool pipe_ok = p.bm == 128 && p.bn == 128 && !p.a_scalar && !p.b_scalar && M * k * 4 < G2 && x_elems * 4 < G2;
+        p.pipe = !pipe_ok ? 0 : (p.Q % BK == 0 ? 3 : 1);
+        fill = p.pipe == 3 ? WGRAD_F32_PIPE3 : WGRAD_F32;
+        p.lds = 4 * (p.pipe == 3 ? 1 : 2) * (BK * p.bm + BK * p.bn);
+    }
+#undef RR_PLAN_REFUSE
+    p.tiles = p.mt * p.nt * r * s;
+    p.splits = pixel_splits(p.tiles, cdiv(M, BK), fill.slots, fill.min_chunks, &p.per_split);     // (every kernel's K-step is 32 pixels)
+    p.grid = p.tiles * p.splits;
+    return p;
 }
 
 }  // namespace rr_plan

@@ -16,7 +16,7 @@
 //     GEMMs on the conv kernels), kept as the A/B reference of the fused backward and for the layouts it does not take.
 // Layouts: x NHWC; offset NHWC [N,P,Q,2*dg*R*S] (per group: interleaved (dh,dw) per tap, as the
 // reference's channel order); mask NHWC [N,P,Q,dg*R*S]; weight OHWI.
-#include "common.h"
+#include "conv_launch.h"      // rr_launch
 #include "dcn_plan.h"
 #include "rrnet_hip.h"
 #include <type_traits>
@@ -2152,18 +2152,6 @@ static int dcn_win_margin()
     return v;
 }
 
-// Raise the kernel's dynamic LDS limit, launch, check.  The limit is raised for what asks for more than 48 KB; the kernels that
-// stay below (the bf16 and the 32-column L2-gather forward) launch without that runtime call.
-template <class Args>
-static int dcn_launch(void (*kernel)(Args), int grid, int threads, int lds, hipStream_t stream, const char *name, const Args &args)
-{
-    if (lds > 48 * 1024)
-        RR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds), name);
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds, stream, args);
-    RR_CHECK_LAUNCH(name);
-    return RR_OK;
-}
-
 static DcnWinArgs dcn_win_args(const DcnArgs &a, const rr_plan::DcnPlanHead &pl)
 {
     DcnWinArgs wa{};
@@ -2206,7 +2194,7 @@ static int dcn_fwd_impl(const char *name, const float *x, const float *offset, c
     if (!pl.window) {
         const auto kernel = pl.bn == 128 ? (bf16 ? dcn_fprop_kernel<128, false> : dcn_fprop_kernel<128, true>)
                                          : (bf16 ? dcn_fprop_kernel<32, false> : dcn_fprop_kernel<32, true>);
-        return dcn_launch(kernel, pl.grid, 256, pl.lds, stream, name, a);
+        return rr_launch(kernel, dim3(pl.grid), 256, pl.lds, stream, a, name);
     }
     DcnWinArgs wa = dcn_win_args(a, pl);
     if (pl.pack) {      // B tile by LDS-DMA from the weights packed to bf16 once per call
@@ -2215,7 +2203,7 @@ static int dcn_fwd_impl(const char *name, const float *x, const float *offset, c
     }
     const auto kernel = pl.wbn == 256 ? (bf16 ? dcn_fprop_win_kernel<256, false> : dcn_fprop_win_kernel<256, true>)
                                       : (bf16 ? dcn_fprop_win_kernel<128, false> : dcn_fprop_win_kernel<128, true>);
-    return dcn_launch(kernel, pl.grid, 512, pl.lds, stream, name, wa);
+    return rr_launch(kernel, dim3(pl.grid), 512, pl.lds, stream, wa, name);
 }
 
 #define RR_DCN_GEOM {n, h, wd, c, k, r, s, stride, pad_h, pad_w, dilation, deformable_groups}
@@ -2303,14 +2291,14 @@ static int dcn_wgrad_impl(const float *x, const float *offset, const float *mask
         DcnBwdArgs b{};
         b.a = a; b.dy = dy; b.dw = dw;
         b.mt = pl.mt; b.nt = pl.nt; b.chunks_per_split = pl.chunks_per_split;
-        return dcn_launch(dcn_wgrad_kernel, pl.grid, 256, pl.lds, stream, "rr_dcn_wgrad", b);
+        return rr_launch(dcn_wgrad_kernel, dim3(pl.grid), 256, pl.lds, stream, b, "rr_dcn_wgrad");
     }
     DcnWinWgradArgs wb{};
     wb.w = dcn_win_args(a, pl);
     wb.dy = dy; wb.dw = dw; wb.dyb = dyb;
     wb.splits = pl.splits; wb.ktiles = pl.ktiles; wb.dma_window = pl.dma_window;
     const auto kernel = pl.dy_dma ? dcn_wgrad_win_kernel<9, false, true> : bf16 ? dcn_wgrad_win_kernel<9, false> : dcn_wgrad_win_kernel<9, true>;
-    return dcn_launch(kernel, pl.grid, 512, pl.lds, stream, "rr_dcn_wgrad", wb);
+    return rr_launch(kernel, dim3(pl.grid), 512, pl.lds, stream, wb, "rr_dcn_wgrad");
 }
 
 // 1 when rr_dcn_wgrad / rr_dcn_dgrad take this layer (the host layer runs the column path otherwise): both backward plans accept
@@ -2371,7 +2359,7 @@ static int dcn_dgrad_impl(const float *x, const float *offset, const float *mask
     if (rc != RR_OK) return rc;
     b.dy = dy; b.dx = dx; b.doffset = doffset; b.dmask = dmask;
     if (pl.zero_dx) hipMemsetAsync(dx, 0, sizeof(float) * (size_t)g.n * g.h * g.w * g.c, stream);     // (every kernel below ADDS into dx with float atomics)
-    if (!pl.window) return dcn_launch(dcn_dgrad_kernel, pl.grid, 256, pl.lds, stream, "rr_dcn_dgrad", b);
+    if (!pl.window) return rr_launch(dcn_dgrad_kernel, dim3(pl.grid), 256, pl.lds, stream, b, "rr_dcn_dgrad");
     DcnWinBwdArgs wb{};
     wb.w = dcn_win_args(b.a, pl);
     wb.dy = dy; wb.dx = dx; wb.doffset = doffset; wb.dmask = dmask;
@@ -2389,7 +2377,7 @@ static int dcn_dgrad_impl(const float *x, const float *offset, const float *mask
         wb.goff_at = pl.goff_at;
     }
     const auto kernel = pl.dma_sweep ? dcn_dgrad_win_kernel<9, false, true> : bf16 ? dcn_dgrad_win_kernel<9, false> : dcn_dgrad_win_kernel<9, true>;
-    return dcn_launch(kernel, pl.grid, 512, pl.lds, stream, "rr_dcn_dgrad", wb);
+    return rr_launch(kernel, dim3(pl.grid), 512, pl.lds, stream, wb, "rr_dcn_dgrad");
 }
 
 extern "C" int rr_dcn_dgrad(const float *x, const float *offset, const float *mask, const float *w, const float *dy,

@@ -731,7 +731,53 @@ def conv_routes(n, c, h, w, k, r, s, stride, pad, bias, relu, want_stats, out_h=
     ph, pw = pad
     routes = {"fprop": _fprop_route(n, c, h, w, k, r, s, stride, ph, pw, bias, relu, want_stats)["labels"]}
     p, q = (h + 2 * ph - r) // stride + 1, (w + 2 * pw - s) // stride + 1
-    # ---- rr_conv_dgrad
+    routes["dgrad"] = _dgrad_route(n, c, h, w, k, r, s, stride, ph, pw)["labels"]
+    routes["wgrad"] = _wgrad_route(n, c, h, w, k, r, s, stride, ph, pw, out_h, out_w)["labels"]
+    via = set()
+    if stride == 1 and k % 4 == 0 and c % 4 == 0 and r * s <= 64 and ph < r and pw < s:
+        via = _fprop_route(n, k, p, q, c, r, s, 1, r - 1 - ph, s - 1 - pw, False, False, False)["labels"]
+    routes["dgrad_via_fprop"] = via
+    return routes
+
+
+# ---- the gradient passes: restatements of the host code of rr_conv_dgrad / rr_conv_wgrad (conv.hip), dgrad_s2_impl / wgrad_impl
+# (conv_bf16.hip) and rr_conv16_dgrad_s2 / rr_conv16_wgrad / launch_igemm (conv16.hip) as they stood BEFORE the gradient plans of
+# conv_plan.h existed, kept by hand: tests/test_host_logic.py holds the library's plans (rr_conv_grad_plan) against them field by
+# field.  Each returns the plan's fields (and the labels the grid-coverage tests use), or None where the entry point refuses.
+GRAD_DGRAD, GRAD_DGRAD_S2, GRAD_WGRAD = 0, 1, 2     # the pass argument of rr_conv_grad_plan
+FAM_CONV16 = 3                                      # its family argument: a MATH_*, or the kernels of conv16.hip
+CONV_GRAD_PLAN_INTS = 44                            # RR_CONV_GRAD_PLAN_INTS
+CONV_GRAD_FIELDS = {                                # what rr_conv_grad_plan writes, in its order (include/rrnet_hip.h)
+    GRAD_DGRAD: ("scalar", "bn", "blocks", "gy", "parity", "parity_order", "ks", "zero_dst"),
+    GRAD_DGRAD_S2: ("p", "q", "zero_dst", "n_launch"),          # then 10 values per launch: dgrad_s2_mirror's "launches"
+    GRAD_WGRAD: ("P", "Q", "M", "bm", "bn", "a_scalar", "b_scalar", "pipe", "mt", "nt", "tiles", "splits", "per_split", "grid", "lds"),
+}
+
+
+def refused_call(entry, ints, null=()):
+    """Calls entry point `entry` of include/rrnet_hip.h the way tests/golden/conv_grad_refusals.json records a refused call: `ints`
+    are its non-pointer arguments in order; every pointer is a dummy host buffer, except those whose position among the pointer
+    arguments is in `null`; the stream is null.  -> (return code, rr_last_error).  For calls that are refused before any launch."""
+    import ctypes
+    from rrnet_amd import _C
+    f = _C.fn(entry)
+    dummy, values, args, nptr = ctypes.create_string_buffer(256), iter(ints), [], 0
+    for j, t in enumerate(f.argtypes):
+        if t is not ctypes.c_void_p:
+            args.append(next(values))
+        elif j == len(f.argtypes) - 1:
+            args.append(None)                                # hipStream_t
+        else:
+            args.append(None if nptr in null else ctypes.addressof(dummy))
+            nptr += 1
+    rc = f(*args)
+    return rc, _C.lib().rr_last_error().decode()
+
+
+def _dgrad_route(n, c, h, w, k, r, s, stride, ph, pw, accumulate=False):
+    """rr_conv_dgrad (conv.hip) with rr_plan::parity_classes restated -> {"labels": set, every name of CONV_GRAD_FIELDS[GRAD_DGRAD]}."""
+    if min(n, h, w, c, k, r, s, stride) <= 0 or n * h * w >= 1 << 31:
+        return None
     m = n * h * w
     scalar = k % 4 != 0 or c % 4 != 0 or r * s > 64 or stride > 2
     bn = 128 if c > 64 else ((64 if not scalar else 128) if c > 32 else 32)
@@ -745,35 +791,58 @@ def conv_routes(n, c, h, w, k, r, s, stride, pad, bias, relu, want_stats, out_h=
     if scalar:
         d.add("scalar")
     parity = stride == 2 and not scalar
+    order, live = 0, 4
     if parity:
         taps = []
         for cl in range(4):
             r0, s0 = ((cl >> 1) + ph) & 1, ((cl & 1) + pw) & 1
             taps.append(((r - r0 + 1) // 2 if r0 < r else 0) * ((s - s0 + 1) // 2 if s0 < s else 0))
-        taps.sort(reverse=True)
-        live = 4
+        ord_ = [0, 1, 2, 3]                          # the host's exchange sort: classes by falling tap count
+        for i in range(4):
+            for j in range(i + 1, 4):
+                if taps[ord_[j]] > taps[ord_[i]]:
+                    ord_[i], ord_[j] = ord_[j], ord_[i]
+        order = ord_[0] | ord_[1] << 2 | ord_[2] << 4 | ord_[3] << 6
+        taps = [taps[o] for o in ord_]
         while live > 1 and taps[live - 1] == 0:
             live -= 1
         gy = live
         d.add("parity4" if live == 4 else "parity_live<4")
         blocks = _cdiv(n * ((h + 1) // 2) * ((w + 1) // 2), _BM) * _cdiv(c, bn)
         nk = _cdiv(k, _BK) * ((r + 1) // 2) * ((s + 1) // 2)
-    if not parity and pick_ksplit_mirror(blocks * gy, nk) > 1:
+    ks = 1 if parity else pick_ksplit_mirror(blocks * gy, nk)
+    if ks > 1:
         d.add("ksplit>1")
-    routes["dgrad"] = d
-    # ---- rr_conv_wgrad
+    return dict(labels=d, scalar=int(scalar), bn=bn, blocks=blocks, gy=gy, parity=int(parity), parity_order=order, ks=ks,
+                zero_dst=int(((parity and live < 4) or ks > 1) and not accumulate))
+
+
+def _pixel_splits(tiles, chunks, slots, min_chunks):
+    """rr_plan::pixel_splits restated -> (splits, K-steps per split)."""
+    splits = slots // tiles if tiles < slots else 1
+    splits = max(1, min(splits, _cdiv(chunks, min_chunks)))
+    per = _cdiv(chunks, splits)
+    return _cdiv(chunks, per), per
+
+
+def _wgrad_route(n, c, h, w, k, r, s, stride, ph, pw, out_h=0, out_w=0):
+    """rr_conv_wgrad (conv.hip) restated -> {"labels": set, every name of CONV_GRAD_FIELDS[GRAD_WGRAD]}."""
+    if min(n, h, w, c, k, r, s, stride) <= 0:
+        return None
+    p, q = (h + 2 * ph - r) // stride + 1, (w + 2 * pw - s) // stride + 1
     pp, qq = (out_h if out_h > 0 else p), (out_w if out_w > 0 else q)
     mw = n * pp * qq
+    if not 0 < mw < 1 << 31:
+        return None
     bmw, bnw = (128 if k > 32 else 32), (128 if c > 32 else 32)
-    tiles = _cdiv(k, bmw) * _cdiv(c, bnw) * r * s
+    mt, nt = _cdiv(k, bmw), _cdiv(c, bnw)
+    tiles = mt * nt * r * s
     chunks = _cdiv(mw, _BK)
     a_s, b_s = k % 4 != 0, c % 4 != 0
     pipe_ok = (bmw == 128 and bnw == 128 and not a_s and not b_s and mw * k * 4 < (1 << 31) and n * h * w * c * 4 < (1 << 31))
     wmode = 0 if not pipe_ok else (3 if qq % _BK == 0 else 1)
     slots = 768 if wmode == 3 else 512
-    splits = slots // tiles if tiles < slots else 1
-    splits = max(1, min(splits, _cdiv(chunks, 8)))
-    splits = _cdiv(chunks, _cdiv(chunks, splits))
+    splits, per = _pixel_splits(tiles, chunks, slots, 8)
     g = {"pipe3"} if wmode == 3 else ({"pipe1"} if wmode == 1 else {"%dx%d" % (bmw, bnw)})
     if a_s:
         g.add("a_scalar")
@@ -781,12 +850,8 @@ def conv_routes(n, c, h, w, k, r, s, stride, pad, bias, relu, want_stats, out_h=
         g.add("b_scalar")
     if splits > 1:
         g.add("splits>1")
-    routes["wgrad"] = g
-    via = set()
-    if stride == 1 and k % 4 == 0 and c % 4 == 0 and r * s <= 64 and ph < r and pw < s:
-        via = _fprop_route(n, k, p, q, c, r, s, 1, r - 1 - ph, s - 1 - pw, False, False, False)["labels"]
-    routes["dgrad_via_fprop"] = via
-    return routes
+    return dict(labels=g, P=pp, Q=qq, M=mw, bm=bmw, bn=bnw, a_scalar=int(a_s), b_scalar=int(b_s), pipe=wmode, mt=mt, nt=nt, tiles=tiles,
+                splits=splits, per_split=per, grid=tiles * splits, lds=4 * (1 if wmode == 3 else 2) * (_BK * bmw + _BK * bnw))
 
 
 CONV_ROUTE_LABELS = {
@@ -1080,8 +1145,9 @@ def lowp_terms(math, kind, idx, first, second, stride, pad, rs=None, bias=None, 
 
 
 def _parity_launches(h, w, r, s, ph, pw):
-    """rr_plan::parity_classes restated -> ([(class, Rc, Sc, lead_h, lead_w, Hc, Wc)] of the classes that launch, any_empty)."""
-    out, any_empty = [], False
+    """rr_plan::parity_classes restated -> ([(class, Rc, Sc, lead_h, lead_w, Hc, Wc, taps of the classes before it)] of the classes
+    that launch, any_empty)."""
+    out, any_empty, before = [], False, 0
     for cl in range(4):
         a, b = cl >> 1, cl & 1
         r0, s0 = (a + ph) & 1, (b + pw) & 1
@@ -1090,8 +1156,48 @@ def _parity_launches(h, w, r, s, ph, pw):
         if hc > 0 and wc > 0 and rc * sc == 0:
             any_empty = True
         if rc * sc > 0 and hc > 0 and wc > 0:
-            out.append((cl, rc, sc, rc - 1 - (a + ph - r0) // 2, sc - 1 - (b + pw - s0) // 2, hc, wc))
+            out.append((cl, rc, sc, rc - 1 - (a + ph - r0) // 2, sc - 1 - (b + pw - s0) // 2, hc, wc, before))
+        before += rc * sc
     return out, any_empty
+
+
+def conv16hip_tile(m, dc):
+    """launch_igemm of csrc/conv16.hip restated -> (output channels per tile, workgroups, dynamic LDS bytes)."""
+    if dc % 256 == 0:
+        return 256, _cdiv(m, 256) * (dc // 256), 2 * (256 * 128 + 256 * 128)
+    return 128, _cdiv(m, 256) * (dc // 128), 128 * 1024
+
+
+def dgrad_s2_mirror(family, n, c, h, w, k, r, s, ph, pw, accumulate=False):
+    """dgrad_s2_impl (conv_bf16.hip: family MATH_BF16 / MATH_F16X3) and rr_conv16_dgrad_s2 (conv16.hip: FAM_CONV16) restated ->
+    {p, q, zero_dst, n_launch, "launches": [(ph, pw, Rc, Sc, lead_h, lead_w, Hc, Wc, taps before, workgroups)]}, or None where the
+    entry point refuses.  Workgroups: launch_igemm's of conv16.hip; 0 for the two arithmetics whose launches _fprop_route states.
+    Needs h + 2*ph >= r and w + 2*pw >= s (the library divides like C, towards zero)."""
+    if family == FAM_CONV16:
+        if min(n, h, w) <= 0 or ph < 0 or pw < 0 or k % 64 != 0 or c % 128 != 0 or r * s > 16:
+            return None
+    elif min(n, h, w, c, k, r, s) <= 0 or c % 4 != 0 or k % 4 != 0 or r * s > 64 or ph < 0 or pw < 0:
+        return None
+    p, q = (h + 2 * ph - r) // 2 + 1, (w + 2 * pw - s) // 2 + 1
+    if p <= 0 or q <= 0 or (family == FAM_CONV16 and n * p * q * k * 2 >= 1 << 31):
+        return None
+    if not _s2_pads_ok(r, s, ph, pw):
+        return None
+    launches, any_empty = _parity_launches(h, w, r, s, ph, pw)
+    rows = [(cl >> 1, cl & 1, rc, sc, lh, lw, hc, wc, before, conv16hip_tile(n * hc * wc, c)[1] if family == FAM_CONV16 else 0)
+            for cl, rc, sc, lh, lw, hc, wc, before in launches]
+    return dict(p=p, q=q, zero_dst=int(any_empty and not accumulate), n_launch=len(rows), launches=rows)
+
+
+def _s2_pads_ok(r, s, ph, pw):
+    """the refusal loop of the two stride-2 hosts: every class that has taps needs non-negative leading pads"""
+    for cl in range(4):
+        a, b = cl >> 1, cl & 1
+        r0, s0 = (a + ph) & 1, (b + pw) & 1
+        rc, sc = ((r - r0 + 1) // 2 if r0 < r else 0), ((s - s0 + 1) // 2 if s0 < s else 0)
+        if rc * sc > 0 and (rc - 1 - (a + ph - r0) // 2 < 0 or sc - 1 - (b + pw - s0) // 2 < 0):
+            return False
+    return True
 
 
 def conv16_fprop_labels(math, n, c, h, w, k, r, s, stride, ph, pw, bias, relu, want_stats):
@@ -1120,7 +1226,7 @@ def conv16_dgrad_labels(math, n, c, h, w, k, r, s, stride, ph, pw, link=None):
         return {"link %s bn%d %s" % (link, plan["bn"], how)}
     launches, any_empty = _parity_launches(h, w, r, s, ph, pw)
     lab = {"s2 any_empty"} if any_empty else set()
-    for _, rc, sc, lh, lw, hc, wc in launches:
+    for _, rc, sc, lh, lw, hc, wc, _ in launches:
         plan = _fprop_route(n, k, p, q, c, rc, sc, 1, lh, lw, False, False, False, math, strided=True, out_hw=(hc, wc))
         lab.add("s2 bn%d" % plan["bn"])
     return lab
@@ -1129,15 +1235,44 @@ def conv16_dgrad_labels(math, n, c, h, w, k, r, s, stride, ph, pw, link=None):
 def conv16_wgrad_labels(math, n, c, h, w, k, r, s, stride, ph, pw, out_hw=None):
     """wgrad_impl of csrc/conv_bf16.hip restated (rr_plan::pixel_splits over 1024 workgroup slots, 512 for the split kernel,
     never fewer than 16 K-steps per split) -> labels."""
+    return wgrad16_mirror(math, n, c, h, w, k, r, s, stride, ph, pw, out_hw)["labels"]
+
+
+def wgrad16_mirror(family, n, c, h, w, k, r, s, stride, ph, pw, out_hw=None):
+    """wgrad_impl of csrc/conv_bf16.hip (family MATH_BF16 / MATH_F16X3) and rr_conv16_wgrad of csrc/conv16.hip (FAM_CONV16, which
+    has no output override) restated -> {"labels": set, every name of CONV_GRAD_FIELDS[GRAD_WGRAD]}, or None where the entry point
+    refuses.  Needs h + 2*ph >= r and w + 2*pw >= s."""
+    two_gib = 1 << 31
+    if family == FAM_CONV16:
+        if min(n, h, w) <= 0 or k % 128 != 0 or c % 128 != 0 or r * s > 64 or stride not in (1, 2):
+            return None
+        p, q = (h + 2 * ph - r) // stride + 1, (w + 2 * pw - s) // stride + 1
+        m = n * p * q
+        if p <= 0 or q <= 0 or m * k * 2 >= two_gib or n * h * w * c * 2 >= two_gib:
+            return None
+        nt_w = 256 if c % 256 == 0 else 128
+        mt, nt = _cdiv(k, 256), c // nt_w
+        tiles = mt * nt * r * s
+        splits, per = _pixel_splits(tiles, _cdiv(m, 32), 512, 32)
+        lab = {"splits>1" if splits > 1 else "one split", "c tile %d" % nt_w}
+        return dict(labels={"wgrad " + name for name in lab}, P=p, Q=q, M=m, bm=256, bn=nt_w, a_scalar=0, b_scalar=0, pipe=0, mt=mt, nt=nt,
+                    tiles=tiles, splits=splits, per_split=per, grid=tiles * splits, lds=4 * (8 * 2048 + (nt_w // 32) * 2048))
+    if min(n, h, w, c, k, r, s, stride) <= 0 or c % 4 != 0 or k % 4 != 0:
+        return None
     p, q = out_hw or ((h + 2 * ph - r) // stride + 1, (w + 2 * pw - s) // stride + 1)
     m = n * p * q
-    tiles, chunks, slots = _cdiv(k, 128) * _cdiv(c, 128) * r * s, _cdiv(m, _BK), (512 if math == MATH_F16X3 else 1024)
+    if not 0 < m < two_gib or m * k * 4 >= two_gib or n * h * w * c * 4 >= two_gib:
+        return None
+    mt, nt = _cdiv(k, 128), _cdiv(c, 128)
+    tiles, chunks, slots = mt * nt * r * s, _cdiv(m, _BK), (512 if family == MATH_F16X3 else 1024)
     splits = max(1, min(slots // tiles if tiles < slots else 1, _cdiv(chunks, 16)))
-    splits = _cdiv(chunks, _cdiv(chunks, splits))
+    per = _cdiv(chunks, splits)
+    splits = _cdiv(chunks, per)
     lab = {"splits>1" if splits > 1 else "one split"}
     lab |= {name for name, on in (("ragged K tile", k % 128), ("ragged C tile", c % 128), ("M%32", m % _BK), ("stride 2", stride == 2),
                                   ("out override", out_hw is not None)) if on}
-    return {"wgrad " + name for name in lab}
+    return dict(labels={"wgrad " + name for name in lab}, P=p, Q=q, M=m, bm=128, bn=128, a_scalar=0, b_scalar=0, pipe=0, mt=mt, nt=nt,
+                tiles=tiles, splits=splits, per_split=per, grid=tiles * splits, lds=2 * 4 * 4 * (32 * 32 + 32) * (2 if family == MATH_F16X3 else 1))
 
 
 # (N, C, H, W, K, R, S, stride, pad_h, pad_w, bias, relu, want_stats values, passes) as CONV64_GRID; every case at the smallest

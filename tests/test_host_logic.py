@@ -569,14 +569,24 @@ def _plan_cases():
     # relu_bias is refused unless N*P*Q is a multiple of 128, which random maps seldom are: drawn with 0.2 so that, with the
     # 4 / 15 of the channel counts the 16-bit kernels refuse, fewer than half of the draws are refused in any arithmetic
     rng = np.random.default_rng(219)
-    chans = (3, 6, 10, 24, 34, 36, 48, 64, 128, 160, 256, 384, 512, 1024, 2048)
     for i in range(2400):
-        r, s = ((1, 1), (3, 3), (7, 7), (17, 1))[rng.integers(4)]
-        geo = (int(rng.integers(1, 17)), chans[rng.integers(15)], int(rng.integers(1, 161)), int(rng.integers(1, 161)), chans[rng.integers(15)],
-               r, s, int(rng.integers(1, 4)), int(rng.integers(0, 4)), int(rng.integers(0, 4)))
-        add("random%d" % i, geo, bias=bool(rng.integers(2)), relu=bool(rng.integers(2)), want_stats=bool(rng.integers(2)),
+        add("random%d" % i, _random_geometry(rng), bias=bool(rng.integers(2)), relu=bool(rng.integers(2)), want_stats=bool(rng.integers(2)),
             link=(None, "bn", "relu_bias")[rng.choice(3, p=(0.6, 0.2, 0.2))])
     return out
+
+
+_PLAN_CHANS = (3, 6, 10, 24, 34, 36, 48, 64, 128, 160, 256, 384, 512, 1024, 2048)
+_PLAN_FILTERS = ((1, 1), (3, 3), (7, 7), (17, 1))
+
+
+def _random_geometry(rng, chan_p=None, filter_p=None, stride_p=None, pad_hi=4):
+    """One (n, c, h, w, k, r, s, stride, ph, pw) of _plan_cases' generator.  Uniform by default; *_p: draw probabilities over
+    _PLAN_CHANS / _PLAN_FILTERS / strides 1..3, pad_hi: pads below this — for the families that refuse most uniform draws."""
+    def pick(count, p):
+        return int(rng.integers(count)) if p is None else int(rng.choice(count, p=p))
+    r, s = _PLAN_FILTERS[pick(4, filter_p)]
+    return (int(rng.integers(1, 17)), _PLAN_CHANS[pick(15, chan_p)], int(rng.integers(1, 161)), int(rng.integers(1, 161)), _PLAN_CHANS[pick(15, chan_p)],
+            r, s, 1 + pick(3, stride_p), int(rng.integers(0, pad_hi)), int(rng.integers(0, pad_hi)))
 
 
 def test_library_plan_equals_the_mirror():
@@ -620,6 +630,220 @@ def test_library_plan_equals_the_mirror():
         assert labels == (CONV_ROUTE_LABELS["fprop"] if math == MATH_F32 else sixteen), (math, sorted(labels))
         assert first3 >= sixteen, (math, sorted(first3))
         assert reached == {"fused", "zero_dst", "zero_slab", "after0", "after1", "after2", "after3"} | ({"xcd_n"} if math else set()), (math, sorted(reached))
+
+
+# ---- the gradient plans of conv_plan.h (rr_conv_grad_plan) against their mirrors ------------------------------------------------
+def _grad_plan_of_library(pas, family, geo, out_hw=(0, 0), accumulate=False):
+    """rr_conv_grad_plan -> the pass's fields under the mirrors' names, or None where the library refuses the call."""
+    import ctypes
+    from helpers import CONV_GRAD_FIELDS, CONV_GRAD_PLAN_INTS, GRAD_DGRAD_S2
+    from rrnet_amd import _C
+    n, c, h, w, k, r, s, st, ph, pw = geo
+    buf = (ctypes.c_int * CONV_GRAD_PLAN_INTS)()
+    if _C.fn("rr_conv_grad_plan")(pas, family, n, h, w, c, k, r, s, st, ph, pw, out_hw[0], out_hw[1], int(accumulate), buf, len(buf)) != 0:
+        return None
+    got = dict(zip(CONV_GRAD_FIELDS[pas], buf))
+    used = len(CONV_GRAD_FIELDS[pas])
+    if pas == GRAD_DGRAD_S2:
+        got["launches"] = [tuple(buf[4 + 10 * i:14 + 10 * i]) for i in range(got["n_launch"])]
+        used += 10 * got["n_launch"]
+    assert not any(buf[used:]), (pas, family, geo, list(buf))
+    return got
+
+
+def _grad_plan_of_mirror(pas, family, geo, out_hw=(0, 0), accumulate=False):
+    from helpers import FAM_CONV16, GRAD_DGRAD, GRAD_DGRAD_S2, MATH_F32, _dgrad_route, _wgrad_route, dgrad_s2_mirror, wgrad16_mirror
+    n, c, h, w, k, r, s, st, ph, pw = geo
+    if pas == GRAD_DGRAD:
+        return _dgrad_route(*geo, accumulate)
+    if pas == GRAD_DGRAD_S2:
+        return dgrad_s2_mirror(family, n, c, h, w, k, r, s, ph, pw, accumulate)
+    if family == MATH_F32:
+        return _wgrad_route(*geo, *out_hw)
+    return wgrad16_mirror(family, *geo, tuple(out_hw) if any(out_hw) and family != FAM_CONV16 else None)
+
+
+def _grad_plan_combos():
+    from helpers import FAM_CONV16, GRAD_DGRAD, GRAD_DGRAD_S2, GRAD_WGRAD, MATH_BF16, MATH_F16X3, MATH_F32
+    return [(GRAD_DGRAD, MATH_F32)] + [(GRAD_DGRAD_S2, f) for f in (MATH_BF16, MATH_F16X3, FAM_CONV16)] + \
+           [(GRAD_WGRAD, f) for f in (MATH_F32, MATH_BF16, MATH_F16X3, FAM_CONV16)]
+
+
+def _grad_draw_weights(pas, family):
+    """How _random_geometry draws for one pass and family.  Uniform draws are refused too often by the families with shape
+    conditions — 4 of the 15 channel counts are no multiple of 4, 9 no multiple of 128, conv16 takes strides 1 and 2 and at most 16
+    taps, and a parity-class gradient takes a 1x1 filter with pad 0 only, a 3x3 with pads below 2 — so those get 0.1 of the
+    refused channel counts, 0.1 of stride 3, few 1x1 / 7x7 / 17x1 filters and pads below 2: at most half of the draws refused."""
+    from helpers import FAM_CONV16, GRAD_DGRAD_S2, GRAD_WGRAD, MATH_F32
+    kw = {}
+    if family == FAM_CONV16:
+        kw["chan_p"] = [0.9 / 6 if ch % 128 == 0 else 0.1 / 9 for ch in _PLAN_CHANS]
+    elif family != MATH_F32:
+        kw["chan_p"] = [0.9 / 11 if ch % 4 == 0 else 0.1 / 4 for ch in _PLAN_CHANS]
+    if pas == GRAD_DGRAD_S2:
+        kw.update(filter_p=(0.1, 0.8, 0.05, 0.05) if family == FAM_CONV16 else (0.1, 0.5, 0.3, 0.1), pad_hi=2)
+    if pas == GRAD_WGRAD and family == FAM_CONV16:
+        kw["stride_p"] = (0.45, 0.45, 0.1)
+    return kw
+
+
+def test_library_gradient_plans_equal_their_mirrors():
+    """rr_conv_grad_plan — dgrad_plan, dgrad_s2_plan and wgrad_plan of rrnet_amd/csrc/conv_plan.h, which the gradient entry points
+    of conv.hip, conv_bf16.hip and conv16.hip launch from — equals the Python restatements of the host code that preceded them
+    (helpers._dgrad_route, dgrad_s2_mirror, _wgrad_route, wgrad16_mirror) field by field, for every pass and family: over
+    CONV64_GRID, CONV64_ASYM_WGRAD, CONV16_GRID, CONV16_ASYM_WGRAD, the geometries of tests/conv_route_cases.py and 2400 seeded
+    random geometries per pass and family, with and without accumulate.  What a family refuses, the mirror refuses; at most half of
+    the random draws are refused per pass and family; together the cases reach every value the plans can take."""
+    import numpy as np
+    from conv_route_cases import cases
+    from helpers import (CONV16_ASYM_WGRAD, CONV16_GRID, CONV64_ASYM_WGRAD, CONV64_GRID, CONV_ROUTE_LABELS, FAM_CONV16, GRAD_DGRAD, GRAD_DGRAD_S2,
+                         GRAD_WGRAD, MATH_F32)
+    fixed = [("grid64/%d" % i, cfg[:10], (0, 0)) for i, cfg in enumerate(CONV64_GRID)]
+    fixed += [("grid16/%d" % i, cfg[:10], (0, 0)) for i, cfg in enumerate(CONV16_GRID)]
+    fixed += [("asym64", CONV64_ASYM_WGRAD[:10], CONV64_ASYM_WGRAD[10:]), ("asym16", CONV16_ASYM_WGRAD[:10], CONV16_ASYM_WGRAD[10:])]
+    for case in cases():
+        (n, c, h, w), k, (r, s), st, (ph, pw) = case["x"], case["k"], case["f"], case["stride"], case["pad"]
+        if case["mode"] == "f32" and not case.get("accumulate"):
+            fixed.append((case["id"], (n, c, h, w, k, r, s, st, ph, pw), tuple(case.get("dy_hw") or (0, 0))))
+    for pas, family in _grad_plan_combos():
+        rng = np.random.default_rng(219)
+        draws = [("random%d" % i, _random_geometry(rng, **_grad_draw_weights(pas, family)), (0, 0)) for i in range(2400)]
+        seen, refused = [], 0
+        for src, geo, out_hw in fixed + draws:
+            n, c, h, w, k, r, s, st, ph, pw = geo
+            if pas == GRAD_DGRAD_S2 and st != 2 and not src.startswith("random"):
+                continue                                                    # (a random draw's stride is not looked at by this pass)
+            if pas != GRAD_WGRAD or family == FAM_CONV16:
+                out_hw = (0, 0)
+            valid = h + 2 * ph >= r and w + 2 * pw >= s                        # (below that the mirrors' floor division is not C's)
+            for acc in ((False,) if pas == GRAD_WGRAD else (False, True)):
+                want = _grad_plan_of_mirror(pas, family, geo, out_hw, acc) if valid else None
+                if want is None and not acc:
+                    refused += src.startswith("random")
+                if not valid:
+                    continue
+                got = _grad_plan_of_library(pas, family, geo, out_hw, acc)
+                assert (got is None) == (want is None), (src, pas, family, geo, got, want)
+                if want is not None:
+                    assert got == {name: want[name] for name in got}, (src, pas, family, geo, acc, got, want)
+                    seen.append(want)
+        assert refused <= 2400 // 2, (pas, family, refused)
+
+        def values(name):
+            return {pl[name] for pl in seen}
+        labels = set().union(*(pl.get("labels", set()) for pl in seen))
+        if pas == GRAD_DGRAD:
+            assert labels == CONV_ROUTE_LABELS["dgrad"], sorted(labels)
+            assert values("zero_dst") == {0, 1} and values("scalar") == {0, 1} and values("bn") == {128, 64, 32}
+            assert {pl["gy"] for pl in seen if pl["parity"]} == {1, 2, 4} and {pl["ks"] > 1 for pl in seen} == {False, True}
+            assert len({pl["parity_order"] for pl in seen if pl["parity"]}) > 2
+        elif pas == GRAD_DGRAD_S2:
+            assert values("zero_dst") == {0, 1} and values("n_launch") >= {1, 4}
+            if family == FAM_CONV16:
+                assert {row[9] > 0 for pl in seen for row in pl["launches"]} == {True}
+        else:
+            assert {pl["splits"] > 1 for pl in seen} == {False, True}
+            if family == MATH_F32:
+                assert labels == CONV_ROUTE_LABELS["wgrad"], sorted(labels)
+                assert {(pl["bm"], pl["bn"]) for pl in seen} == {(128, 128), (128, 32), (32, 128), (32, 32)}
+                assert values("pipe") == {0, 1, 3} and values("a_scalar") == {0, 1} and values("b_scalar") == {0, 1}
+            else:
+                assert {(pl["bm"], pl["bn"]) for pl in seen} == ({(256, 256), (256, 128)} if family == FAM_CONV16 else {(128, 128)})
+
+
+def test_refused_gradient_calls_say_what_they_said(golden_dir):
+    """tests/golden/conv_grad_refusals.json: the error text of refused gradient (and conv16 forward) calls — every refusal branch of
+    every entry point whose host code moved to the plans — recorded from the library before they existed.  Dummy non-null
+    pointers: a refused call returns before it touches a device."""
+    import json
+    import os
+    from helpers import refused_call
+    with open(os.path.join(golden_dir, "conv_grad_refusals.json")) as fh:
+        recorded = json.load(fh)
+    assert len(recorded) >= 36
+    for rec in recorded:
+        rc, text = refused_call(rec["entry"], rec["ints"], rec["null"])
+        assert rc != 0 and text == rec["text"], (rec, rc, text)
+
+
+def test_s2_parity_pads_rule_is_the_plans_padding_refusal():
+    """ops._s2_parity_pads_ok (which keeps a layer off rr_conv_dgrad_s2_* / rr_conv16_dgrad_s2) says no exactly where
+    dgrad_s2_plan refuses for its padding, for all r, s <= 7 and pads <= 3, in each of the three families."""
+    from helpers import FAM_CONV16, GRAD_DGRAD_S2, MATH_BF16, MATH_F16X3
+    from rrnet_amd import _C, ops
+    n_no = 0
+    for family in (MATH_BF16, MATH_F16X3, FAM_CONV16):
+        for r in range(1, 8):
+            for s in range(1, 8):
+                for ph in range(4):
+                    for pw in range(4):
+                        if family == FAM_CONV16 and r * s > 16:
+                            continue                                        # (refused for its shape before the padding is looked at)
+                        got = _grad_plan_of_library(GRAD_DGRAD_S2, family, (2, 128, 32, 32, 128, r, s, 2, ph, pw))
+                        assert (got is not None) == ops._s2_parity_pads_ok(r, s, (ph, pw)), (family, r, s, ph, pw)
+                        if got is None:
+                            n_no += 1
+                            assert _C.lib().rr_last_error().decode() == "rr_conv_grad_plan: unsupported padding %d,%d" % (ph, pw)
+    assert n_no > 100
+
+
+def test_conv_gpu_shapes_reach_every_gradient_plan_label():
+    """The shapes the GPU tests run — CONV64_GRID and CONV64_ASYM_WGRAD (tests/test_conv_fp64_gpu.py), CONV16_GRID and
+    CONV16_ASYM_WGRAD in both arithmetics (tests/test_conv_lowp_fp64_gpu.py), SHAPES of tests/test_conv16_gpu.py — reach every
+    label the gradient plans can name, per pass and family, as the library's own plans (rr_conv_grad_plan) name them."""
+    from helpers import (CONV16_ASYM_WGRAD, CONV16_GRID, CONV64_ASYM_WGRAD, CONV64_GRID, FAM_CONV16, GRAD_DGRAD, GRAD_DGRAD_S2, GRAD_WGRAD,
+                         MATH_BF16, MATH_F16X3, MATH_F32)
+    from rrnet_amd import _C
+    from test_conv16_gpu import SHAPES
+
+    def labels(pas, family, pl):
+        if pas == GRAD_DGRAD:
+            lab = {"bn%d" % pl["bn"]} | ({"scalar"} if pl["scalar"] else set()) | ({"ksplit>1"} if pl["ks"] > 1 else set())
+            lab |= {"zero fill" if pl["zero_dst"] else "no zero fill"}
+            return lab | ({"parity4" if pl["gy"] == 4 else "parity_live<4"} if pl["parity"] else set())
+        if pas == GRAD_DGRAD_S2:
+            lab = {"zero fill" if pl["zero_dst"] else "no zero fill", "4 launches" if pl["n_launch"] == 4 else "fewer launches"}
+            return lab | {"ragged classes"} if len({row[6:8] for row in pl["launches"]}) > 1 else lab
+        lab = {"splits>1" if pl["splits"] > 1 else "one split", "%dx%d" % (pl["bm"], pl["bn"])}
+        if family == MATH_F32:
+            lab = {"splits>1"} & lab | {"pipe%d" % pl["pipe"] if pl["pipe"] else "%dx%d" % (pl["bm"], pl["bn"])}
+            lab |= {name for name in ("a_scalar", "b_scalar") if pl[name]}
+        return lab
+    seen = {combo: set() for combo in _grad_plan_combos()}
+
+    def run(pas, family, geo, out_hw=(0, 0), accs=(False,)):
+        for acc in accs:
+            pl = _grad_plan_of_library(pas, family, geo, out_hw, acc)
+            assert pl is not None, (pas, family, geo, _C.lib().rr_last_error())
+            seen[pas, family] |= labels(pas, family, pl)
+    for cfg in CONV64_GRID:                                                      # test_conv_fp64_gpu.py: rr_conv_dgrad / rr_conv_wgrad
+        if "d" in cfg[13]:
+            run(GRAD_DGRAD, MATH_F32, cfg[:10], accs=(False, True))
+        if "w" in cfg[13]:
+            run(GRAD_WGRAD, MATH_F32, cfg[:10])
+    run(GRAD_WGRAD, MATH_F32, CONV64_ASYM_WGRAD[:10], CONV64_ASYM_WGRAD[10:])
+    for family in (MATH_BF16, MATH_F16X3):                                       # test_conv_lowp_fp64_gpu.py
+        for cfg in CONV16_GRID:
+            if "d" in cfg[13] and cfg[7] == 2:
+                run(GRAD_DGRAD_S2, family, cfg[:10], accs=(False, True))
+            if "w" in cfg[13]:
+                run(GRAD_WGRAD, family, cfg[:10])
+        run(GRAD_WGRAD, family, CONV16_ASYM_WGRAD[:10], CONV16_ASYM_WGRAD[10:])
+    for n, c, h, w, k, r, st in SHAPES:                                          # test_conv16_gpu.py, under its own conditions
+        geo = (n, c, h, w, k, r, r, st, r // 2, r // 2)
+        if st == 2 and k % 64 == 0 and c % 128 == 0:
+            run(GRAD_DGRAD_S2, FAM_CONV16, geo, accs=(False, True))
+        if k % 128 == 0 and c % 128 == 0 and r * r <= 64:
+            run(GRAD_WGRAD, FAM_CONV16, geo)
+    s2 = {"zero fill", "no zero fill", "4 launches", "fewer launches", "ragged classes"}
+    want = {(GRAD_DGRAD, MATH_F32): {"bn128", "bn64", "bn32", "scalar", "ksplit>1", "parity4", "parity_live<4", "zero fill", "no zero fill"},
+            (GRAD_WGRAD, MATH_F32): {"pipe3", "pipe1", "128x128", "128x32", "32x128", "32x32", "a_scalar", "b_scalar", "splits>1"},
+            (GRAD_WGRAD, MATH_BF16): {"128x128", "splits>1", "one split"}, (GRAD_WGRAD, MATH_F16X3): {"128x128", "splits>1", "one split"},
+            (GRAD_WGRAD, FAM_CONV16): {"256x256", "256x128", "splits>1", "one split"},
+            (GRAD_DGRAD_S2, MATH_BF16): s2, (GRAD_DGRAD_S2, MATH_F16X3): s2, (GRAD_DGRAD_S2, FAM_CONV16): s2}
+    missing = {combo: sorted(want[combo] - seen[combo]) for combo in want if want[combo] - seen[combo]}
+    assert not missing, "gradient-plan labels no GPU test shape reaches (pass, family): %s" % missing
+    assert all(seen[combo] <= want[combo] for combo in want), seen
 
 
 # ---- the data-gradient selector (ops.dgrad_route) against the recorded launches (tests/golden/conv_bwd_routes.json) -----------
@@ -692,7 +916,7 @@ def test_conv16_grid_reaches_every_route():
                 same_plan(math, (n, k, p, q, c, r, s, 1, r - 1 - ph, s - 1 - pw))
             if "d" in passes and st == 2:
                 sizes = set()
-                for _, rc, sc, lh, lw, hc, wc in _parity_launches(h, w, r, s, ph, pw)[0]:
+                for _, rc, sc, lh, lw, hc, wc, _ in _parity_launches(h, w, r, s, ph, pw)[0]:
                     pl = same_plan(math, (n, k, p, q, c, rc, sc, 1, lh, lw), strided=True, out_hw=(hc, wc))
                     assert pl["ks"] == 1 and not pl["zero_dst"]
                     sizes.add((hc, wc))
