@@ -52,6 +52,19 @@ int rr_soft_nms_segments(float *boxes, const int *seg_off, int nseg, int max_seg
 int rr_soft_nms_ragged(float *boxes, const int *seg_off, const int *seg_len, int nseg, int max_seg_boxes, int stride,
                        float sigma, float Nt, float threshold, int method, int *n_out, int *err_flag,
                        void *workspace, hipStream_t stream);
+/* Introspection, for tests: HOW a Soft-NMS call of nseg segments of up to max_seg_boxes boxes would launch, as the host plan
+ * of csrc/softnms_plan.h decides it.  Launches nothing, needs no device.  out[0..10] = {launches (0: an empty batch; 2: the
+ * two-launch split of the LDS loop), kernel (0 register-resident, 1 LDS loop), threads per workgroup (of the last launch),
+ * boxes per lane (register kernel; else 0), dynamic LDS bytes and row capacity of the last launch (LDS loop; else 0), that
+ * launch raises the function's dynamic-LDS limit first, threads and dynamic LDS bytes of the first launch of a split (else 0),
+ * the caller must bring a workspace, the kernel runs on it (the LDS loop's global-workspace form)}; out[11..16] = the
+ * per-segment constants of the kernels: {deaths of one step the register kernel renumbers from its list (more: the mask path),
+ * longest segment that runs <256, 1> inside a wider register launch, longest segment the LDS loop runs on one wave, longest
+ * segment of the split's first launch, RR_SOFT_NMS_LDS_MAX, longest segment of the register kernels (the mask's capacity)};
+ * the rest 0.  n_out >= RR_SOFT_NMS_PLAN_INTS.  A bound the entry points refuse (negative, >= 65536) returns an error; they
+ * also refuse stride < 5 and, where out[9] is set, a null workspace.  Scores and coordinates must be finite. */
+#define RR_SOFT_NMS_PLAN_INTS 18
+int rr_soft_nms_plan(int nseg, int max_seg_boxes, int *out, int n_out);
 
 
 /* ---- Convolutions (NHWC fp32, implicit GEMM on v_mfma_f32_32x32x2_f32) --------------- *

@@ -18,6 +18,7 @@
 // N*stride*4 bytes in + out per segment.
 #include "common.h"
 #include "rrnet_hip.h"
+#include "softnms_plan.h"
 
 namespace {
 
@@ -227,8 +228,10 @@ __device__ void soft_nms_segment(SegView v, const int n, const float sigma, cons
 // for the LDS-resident loop (0.94 / 1.58 on steps without deaths); the floor of the bare reduction + exchange chain is
 // 0.64 us (tools/softnms_floor.hip).  A third variant (one DPP prefix scan of the mask + an LDS hole table instead of the
 // popcount searches) was built, bit-exact, and measured no faster: removed.
-// Same arithmetic, same order of selection, same final rows: bit-exact with the LDS form and the reference
-// (tests/test_softnms_gpu.py runs every golden through both).  Latency-bound: tools/bench_softnms.py quotes its
+// Same arithmetic, same order of selection, same final rows: bit-exact with the LDS form and the reference.  Which form a call
+// takes is softnms_plan.h's decision; tests/test_softnms_routes_gpu.py runs every golden through both (alone: the register
+// kernel; inside a batch of more than 512 segments with a bound above 256: the LDS loop) and every route of the plan on inputs
+// that tests/test_softnms_routes_host.py proves to reach the list and mask renumbering and every compaction branch.  Latency-bound: tools/bench_softnms.py quotes its
 // us per outer step against the measured floor of the bare reduction + exchange chain.
 __device__ __forceinline__ unsigned sortable_key(float s)
 {
@@ -254,7 +257,7 @@ __device__ __forceinline__ unsigned dpp_max_u32(unsigned v)
 struct RegCand {            // a candidate for the next selection: key = (sortable score, ~position), the box itself
     unsigned ks, kp;
     float x1, y1, x2, y2;
-    unsigned tied;          // more than one candidate carries the maximal score (the position decided)
+    unsigned tied;          // more than one candidate carries the maximal score (the position decided); in: among the lane's own boxes
 };
 
 // wave-wide best candidate (highest score, then lowest position) -> every lane holds it
@@ -263,7 +266,8 @@ __device__ __forceinline__ RegCand wave_best(RegCand c)
     const unsigned ms = dpp_max_u32(c.ks);
     unsigned long long tie = __ballot(c.ks == ms);
     int src;
-    const unsigned tied = __popcll(tie) > 1;
+    // (two boxes of ONE lane may share the maximal score too: the lane offers the one at the lower position and says so)
+    const unsigned tied = __popcll(tie) > 1 || __ballot(c.ks == ms && c.tied != 0u) != 0ull;
     if (!tied) {
         src = __ffsll((long long)tie) - 1;
     } else {                                        // equal scores: the lowest position (largest ~position) wins
@@ -293,14 +297,14 @@ __device__ unsigned long long g_snms_stamp[8];
 #define SN_T(i)
 #define SN_FLUSH
 #endif
-constexpr int SMALL_SEG_REG = 256;          // one box per lane of four waves
+constexpr int SMALL_SEG_REG = rr_plan::SNMS_REG_SHORT;   // 256: one box per lane of four waves
 constexpr int REG_DEAD = 0x7fffffff;         // position of a box that is out of the game (dead, or a padding slot)
-constexpr int REG_MASK_WORDS = 288;          // 32-bit words of one dead-position mask: positions < 9216
+constexpr int REG_MASK_WORDS = rr_plan::SNMS_MASK_WORDS;   // 288 32-bit words of one dead-position mask: positions < 9216
 // Round 5: a death step usually kills a handful of boxes.  Their positions go to a short LDS LIST (REG_LIST entries, two buffers)
 // and the renumbering works on that list — O(deaths^2) broadcast reads — instead of popcount scans over the position mask, which
 // for a 9000-box segment walked up to 288 words per moved box (and per lane for the pre-selected next box): ~6 of the 8.4 us per
 // outer step.  Steps with more deaths than the list holds keep the mask path.
-constexpr int REG_LIST = 64;
+constexpr int REG_LIST = rr_plan::SNMS_REG_LIST;   // 64
 constexpr int REG_LDS_WORDS = 2 * 16 * 8 + 2 * REG_MASK_WORDS + 2 * REG_LIST + 4;
 
 // lds: [2][16] exchange slots of 8 words + [2][REG_MASK_WORDS] dead-position masks (zero on entry)
@@ -380,6 +384,7 @@ __device__ __forceinline__ void soft_nms_registers(float *b, const int stride, c
     auto lane_best = [&](int lo) -> RegCand {
         RegCand c;
         c.ks = 0u; c.kp = 0u; c.x1 = c.y1 = c.x2 = c.y2 = 0.f;
+        c.tied = 0u;                               // (selected on the final numbering: no renumbering can overturn the order)
 #pragma unroll
         for (int j = 0; j < NB; ++j) {
             if (pos[j] > lo && pos[j] < N) {
@@ -458,11 +463,15 @@ __device__ __forceinline__ void soft_nms_registers(float *b, const int stride, c
         SN_T(1);
         RegCand c;
         c.ks = 0u; c.kp = 0u; c.x1 = c.y1 = c.x2 = c.y2 = 0.f;
+        c.tied = 0u;
 #pragma unroll
         for (int j = 0; j < NB; ++j) {
             const int p = pos[j];
             if (p > i && p < N && !(deadbits & (1u << j))) {
                 const unsigned ks = key[j], kp = ~(unsigned)p;
+                // a second box of this lane with the lane's best score: the renumbering below may put either in front, and
+                // the other lanes cannot see it (NB > 1 only; a key is never 0 for a finite score)
+                if (NB > 1) c.tied = ks > c.ks ? 0u : (ks == c.ks ? 1u : c.tied);
                 if (ks > c.ks || (ks == c.ks && kp > c.kp)) {
                     c.ks = ks; c.kp = kp; c.x1 = x1[j]; c.y1 = y1[j]; c.x2 = x2[j]; c.y2 = y2[j];
                 }
@@ -592,8 +601,8 @@ __device__ __forceinline__ void soft_nms_registers(float *b, const int stride, c
     if (tid == 0) *out_n = N;
 }
 
-constexpr int SMALL_SEG = 192;   // segments up to this many boxes run on one wave
-constexpr int MID_SEG = 512;     // first launch of the two-launch split: LDS for this many boxes (12.8 KB)
+constexpr int SMALL_SEG = rr_plan::SNMS_ONE_WAVE;   // 192: segments up to this many boxes run on one wave
+constexpr int MID_SEG = rr_plan::SNMS_MID_SEG;      // 512: first launch of the two-launch split: LDS for this many boxes (12.8 KB)
 
 // LDS-resident: dynamic LDS = n_max * 25 bytes (rounded), boxes are loaded AoS->SoA and stored back.
 template <int T>
@@ -697,70 +706,66 @@ extern "C" size_t rr_soft_nms_workspace_bytes(int total_boxes, int max_seg_boxes
     return max_seg_boxes > RR_SOFT_NMS_LDS_MAX ? (size_t)total_boxes * 28 + 64 : 0;
 }
 
+// How a call launches is rr_plan::soft_nms_plan's decision (softnms_plan.h); the code below carries it out.
+template <int T>
+static void launch_lds_loop(const rr_plan::SoftNmsLdsLaunch &l, float *boxes, const int *seg_off, const int *seg_len, int nseg,
+                            int stride, float sigma, float Nt, float threshold, int method, int *n_out, int *err_flag, float *gws,
+                            hipStream_t stream)
+{
+    if (l.raise_lds_limit)
+        hipFuncSetAttribute(reinterpret_cast<const void *>(soft_nms_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, l.lds);
+    hipLaunchKernelGGL(soft_nms_kernel<T>, dim3(nseg), dim3(T), (size_t)l.lds, stream, boxes, seg_off, seg_len, stride, sigma, Nt,
+                       threshold, method, l.cap, n_out, err_flag, gws, l.lo, l.hi);
+}
+
 static int soft_nms_launch(float *boxes, const int *seg_off, const int *seg_len, int nseg, int max_seg_boxes,
                            int stride, float sigma, float Nt, float threshold, int method,
                            int *n_out, int *err_flag, void *workspace, hipStream_t stream)
 {
+    using namespace rr_plan;
     RR_CHECK_ARG(stride >= 5, "rr_soft_nms_segments: stride %d < 5", stride);
-    RR_CHECK_ARG(nseg >= 0 && max_seg_boxes >= 0, "rr_soft_nms_segments: negative size");
-    RR_CHECK_ARG(max_seg_boxes < 65536, "rr_soft_nms_segments: segment of %d boxes (limit 65535)", max_seg_boxes);
-    if (nseg == 0) return RR_OK;
+    const SoftNmsPlan p = soft_nms_plan(nseg, max_seg_boxes, workspace != nullptr);
+    RR_CHECK_ARG(p.refuse == nullptr, p.refuse, p.a0);
+    if (p.launches == 0) return RR_OK;         // an empty batch
     RR_CHECK_ARG(!(method == 2 && sigma == 0.0f), "rr_soft_nms_segments: sigma == 0 (reference raises ZeroDivisionError)");
-    const bool in_lds = max_seg_boxes <= RR_SOFT_NMS_LDS_MAX;
-    RR_CHECK_ARG(in_lds || workspace != nullptr, "rr_soft_nms_segments: workspace required for %d-box segments", max_seg_boxes);
-    const int cap = (max_seg_boxes + 3) & ~3;
-    const size_t lds = in_lds ? (size_t)cap * 25 + 16 : 0;
-    float *gws = in_lds ? nullptr : reinterpret_cast<float *>(workspace);
-#define LAUNCH(T, LDS, CAP, LO, HI)                                                                    \
-    do {                                                                                              \
-        if ((LDS) > 48 * 1024)                                                                        \
-            hipFuncSetAttribute(reinterpret_cast<const void *>(soft_nms_kernel<T>),                   \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS));              \
-        hipLaunchKernelGGL(soft_nms_kernel<T>, dim3(nseg), dim3(T), (LDS), stream, boxes, seg_off,    \
-                           seg_len, stride, sigma, Nt, threshold, method, (CAP), n_out, err_flag, gws, (LO), (HI)); \
-    } while (0)
-    constexpr int ALL = 0x7fffffff;
-    // Regime: a few segments (an image's classes at evaluation, rrnet_operator.py:246-284) are a latency problem — the
-    // register-resident kernel; a batch of more long segments than two per CU is a throughput problem, where the LDS loop's
-    // 256-thread workgroups (4 per CU) retire more segments per unit time (1280 x 1500 boxes: 5.5 against 6.0 ms)
-    const bool throughput_regime = nseg > 512 && max_seg_boxes > 256;
-    // (measured, one segment: 2500 boxes 4.97 against 5.57 ms for the LDS loop; at 5000 / 9000 boxes — six / nine boxes per
-    // lane of a 1024-thread workgroup, 128 registers per lane — the register kernel spills and loses, 15.7 against 14.2 and
-    // 52 against 38 ms: it takes segments of up to 3072 boxes)
-    // (round 5, with the list renumbering: one 9000-box segment 29 ms in registers — 18 boxes per lane of 512 threads, 256 registers,
-    // no scratch — against 38 ms for the LDS loop on its global workspace; a batch of such segments likewise: the LDS loop has no
-    // LDS for them and runs out of L2)
-    if (max_seg_boxes <= 9216 && (!throughput_regime || !in_lds)) {
-        // register-resident kernels: T x NB boxes per segment
+    if (p.kernel == SNMS_REGISTERS) {
 #define LAUNCH_REG(T, NB)                                                                                              \
         hipLaunchKernelGGL((soft_nms_reg_kernel<T, NB>), dim3(nseg), dim3(T), 0, stream, boxes, seg_off, seg_len, stride, sigma, \
                            Nt, threshold, method, n_out, err_flag)
-        // One wave alone on a SIMD issues a vector instruction every 4 cycles, two waves one every 2: the configurations put
-        // (at least) two waves on every SIMD of the CU wherever the segment is long enough to feed them
-        // (measured: 1024 x 2 for 1500 boxes, four waves per SIMD, is 30 % slower than 512 x 3: a 16-wave barrier and exchange)
-        if (max_seg_boxes <= 256) LAUNCH_REG(256, 1);
-        else if (max_seg_boxes <= 1536) LAUNCH_REG(512, 3);
-        else if (max_seg_boxes <= 3072) LAUNCH_REG(1024, 3);
-        else if (max_seg_boxes <= 6144) LAUNCH_REG(512, 12);
-        else LAUNCH_REG(512, 18);
+        if (p.T == 256 && p.NB == 1) LAUNCH_REG(256, 1);
+        else if (p.T == 512 && p.NB == 3) LAUNCH_REG(512, 3);
+        else if (p.T == 1024 && p.NB == 3) LAUNCH_REG(1024, 3);
+        else if (p.T == 512 && p.NB == 12) LAUNCH_REG(512, 12);
+        else if (p.T == 512 && p.NB == 18) LAUNCH_REG(512, 18);
+        else RR_CHECK_ARG(false, "rr_soft_nms_segments: no register kernel <%d, %d>", p.T, p.NB);
 #undef LAUNCH_REG
         RR_CHECK_LAUNCH("rr_soft_nms_segments");
         return RR_OK;
     }
-    // (segments of up to 256 boxes never get here: the register kernels above take them)
-    if (in_lds && max_seg_boxes > MID_SEG) {
-        // The caller's bound is the LONGEST possible segment (K = 1500 at inference: 37.5 KB of LDS per workgroup = four
-        // segments per CU) while a typical (frame, class) segment holds ~150 boxes.  Two launches: the segments of up to
-        // MID_SEG boxes with 12.8 KB of LDS each (all 1280 segments of a 128-frame batch are resident at once: the launch
-        // lasts as long as its longest segment instead of a round and a quarter), then the larger ones with the LDS
-        // they need (workgroups of the others return at once).
-        LAUNCH(256, (size_t)MID_SEG * 25 + 16, MID_SEG, -1, MID_SEG);
-        if (max_seg_boxes <= 2560) LAUNCH(256, lds, cap, MID_SEG, ALL);
-        else LAUNCH(1024, lds, cap, MID_SEG, ALL);
-    } else if (max_seg_boxes <= 2560) LAUNCH(256, lds, cap, -1, ALL);
-    else LAUNCH(1024, lds, cap, -1, ALL);
-#undef LAUNCH
+    float *gws = p.use_workspace ? reinterpret_cast<float *>(workspace) : nullptr;
+    for (int i = 0; i < p.launches; ++i) {
+        const SoftNmsLdsLaunch &l = p.lds_launch[i];
+        if (l.T == 256) launch_lds_loop<256>(l, boxes, seg_off, seg_len, nseg, stride, sigma, Nt, threshold, method, n_out, err_flag, gws, stream);
+        else launch_lds_loop<1024>(l, boxes, seg_off, seg_len, nseg, stride, sigma, Nt, threshold, method, n_out, err_flag, gws, stream);
+    }
     RR_CHECK_LAUNCH("rr_soft_nms_segments");
+    return RR_OK;
+}
+
+// the plan of softnms_plan.h as the entry points below ask it, with the kernels' per-segment constants, for the tests
+extern "C" int rr_soft_nms_plan(int nseg, int max_seg_boxes, int *out, int n_out)
+{
+    using namespace rr_plan;
+    RR_CHECK_ARG(out != nullptr && n_out >= RR_SOFT_NMS_PLAN_INTS, "rr_soft_nms_plan: bad arguments");
+    const SoftNmsPlan p = soft_nms_plan(nseg, max_seg_boxes, true);
+    RR_CHECK_ARG(p.refuse == nullptr, p.refuse, p.a0);
+    const SoftNmsLdsLaunch none{};
+    const bool loop = p.launches > 0 && p.kernel == SNMS_LDS_LOOP;
+    const SoftNmsLdsLaunch &last = loop ? p.lds_launch[p.launches - 1] : none, &first = p.launches == 2 ? p.lds_launch[0] : none;
+    const int v[RR_SOFT_NMS_PLAN_INTS] = {p.launches, p.kernel, p.T, p.NB, last.lds, last.cap, last.raise_lds_limit, first.T, first.lds,
+                                          !p.in_lds && p.launches > 0, p.use_workspace,
+                                          SNMS_REG_LIST, SNMS_REG_SHORT, SNMS_ONE_WAVE, SNMS_MID_SEG, SNMS_LDS_MAX, SNMS_MASK_BOXES, 0};
+    for (int i = 0; i < RR_SOFT_NMS_PLAN_INTS; ++i) out[i] = v[i];
     return RR_OK;
 }
 
