@@ -363,6 +363,8 @@ int rr_bn_apply(const float *y, const float *scale, const float *shift, const fl
 int rr_bn_apply_amax(const float *y, const float *scale, const float *shift, const float *res,
                      const float *res_scale, const float *res_shift, float *out, long total, int c, int relu,
                      unsigned *amax_out, hipStream_t stream);
+/* c % 4 == 0; up to 1024 channels one workgroup covers every channel of its pixels, wider layers (backbones/resnet.py:69, the
+ * 2048-channel stage) run in chunks of 1024 channels. */
 int rr_bn_bwd_reduce(const float *dz, const float *z, const float *y, const float *mean,
                      const float *invstd, const float *mask_scale, const float *mask_shift, double *sums,
                      long npix, int c, int sums_zeroed, hipStream_t stream);
@@ -667,6 +669,52 @@ int rr_eval_match(const float *dets, const int *det_len, const float *gts, const
                   int *target_count, hipStream_t stream);
 int rr_eval_ap(const int *flag_bits, long nrows, const int *seg_off, const int *target_count, const int *in_img_count,
                int c, int t, float *work, float *ap, float *rc, hipStream_t stream);
+
+/* ---- RetinaNet: stem pool, FPN upsample-add, anchor criterion, decode (retina.hip) ---------------- *
+ * rr_maxpool3x3s2_fwd / _bwd: nn.MaxPool2d(kernel_size=3, stride=2, padding=1) of backbones/resnet.py:65 on NHWC fp32.
+ *   x [n,h,w,c] -> y [n,oh,ow,c], oh = (h-1)/2+1, ow = (w-1)/2+1; idx (uint8, y's shape) = the winning tap ky*3+kx of the
+ *   window (input row 2*oy-1+ky, column 2*ox-1+kx).  Padding counts as -inf; the first maximum in row-major window order
+ *   wins; a NaN replaces the running maximum (ATen's rule).  The backward is a gather: dx [n,h,w,c] = the sum, in window
+ *   order, of dy over the at most 4 windows whose tap names the element.  No atomics.
+ * rr_bilinear_add_fwd / _bwd: modules/fpn.py:39-40, out = y + F.interpolate(x, size(y), 'bilinear', align_corners=False).
+ *   x NHWC [n,ih,iw,c], y and out NHWC [n,oh,ow,c], any sizes.  Source coordinate (dst + 0.5) * in/out - 0.5 (in/out as
+ *   one float quotient) clamped at 0, second tap clamped at in-1.  d y is dout itself; _bwd writes d x [n,ih,iw,c] as a
+ *   gather over the bounded range of output pixels that read the input pixel, weights recomputed.  No atomics.
+ * rr_retina_assign: operators/retinanet_operator.py:51-62,67,76-97.  annos [b,m,8] (x,y,w,h,.,cls,.,.; zero rows are
+ *   padding), anchors [a,4] xyxy.  Per (image, anchor): float32 IoU of utils/metrics/metrics.py:29-44 against every row
+ *   (x2 = x + w as the criterion's in-place add; union clamped at 1e-8; IEEE division), max_iou / argmax (lowest index on
+ *   ties), state int8 = 1 (IoU >= 0.5), 0 (IoU < 0.4), -1 (between), cls = the assigned class of a positive (0 otherwise),
+ *   target [b,a,4] = the regression target of a positive (0 otherwise): centres from the unclamped w/h, w/h clamped at 1,
+ *   log, divided by (0.1, 0.1, 0.2, 0.2).  npos [b] int32 = positives per image (zeroed inside, integer atomics).
+ *   Deviation: a class outside [1, num_classes] gives cls 0, i.e. no target bit (the reference indexes -1 or raises).
+ * rr_retina_loss_fwd / _bwd: modules/loss/functional.py:6-22 and retinanet_operator.py:64-72,99-113.  logits [b,a,c],
+ *   loc [b,a,4].  losses[0] = mean over images of sum over (state >= 0 anchors x classes) of the focal term (p =
+ *   clamp(sigmoid, 1e-7, 1-1e-7), alpha 0.75 on the target bit, 0.25 elsewhere, gamma 2) / max(1, npos); losses[1] =
+ *   mean over images of the smooth-L1 (knee 1/9) mean over npos*4 values, 0 for npos == 0.  Two stages: partial
+ *   [b, rr_retina_loss_blocks(a,c), 2] doubles written per workgroup, then one workgroup: bit-identical run to run.
+ *   _bwd: gout [2] (device) = the two upstream scalars; dlogits [b,a,c] and dloc [b,a,4] are written whole: zero for
+ *   ignored anchors, for non-positives in loc and where the probability clamp is active.  npos is clamped to [0,a].
+ * rr_retina_decode: retinanet_operator.py:179-213 for a batch.  Per image: sigmoid, max over classes (first maximum),
+ *   kept when prob > score_thr (NaN leaves), decoded against the anchors (std 0.1/0.2, exp); rows (x,y,w,h,prob,cls+1)
+ *   appended in anchor order to rows [b,a,6], count [b] int32 written on the device.  One workgroup per image. */
+int rr_maxpool3x3s2_fwd(const float *x, float *y, unsigned char *idx, int n, int h, int w, int c, hipStream_t stream);
+int rr_maxpool3x3s2_bwd(const float *dy, const unsigned char *idx, float *dx, int n, int h, int w, int c,
+                        hipStream_t stream);
+int rr_bilinear_add_fwd(const float *x, const float *y, float *out, int n, int ih, int iw, int oh, int ow, int c,
+                        hipStream_t stream);
+int rr_bilinear_add_bwd(const float *dout, float *dx, int n, int ih, int iw, int oh, int ow, int c, hipStream_t stream);
+int rr_retina_assign(const float *annos, const float *anchors, int b, int m, int a, int num_classes,
+                     signed char *state, int *argmax, float *max_iou, int *cls, float *target, int *npos,
+                     hipStream_t stream);
+int rr_retina_loss_blocks(int a, int c);
+int rr_retina_loss_fwd(const float *logits, const float *loc, const signed char *state, const int *cls,
+                       const float *target, const int *npos, int b, int a, int c, double *partial, float *losses,
+                       hipStream_t stream);
+int rr_retina_loss_bwd(const float *logits, const float *loc, const signed char *state, const int *cls,
+                       const float *target, const int *npos, const float *gout, int b, int a, int c, float *dlogits,
+                       float *dloc, hipStream_t stream);
+int rr_retina_decode(const float *logits, const float *loc, const float *anchors, int b, int a, int c, float score_thr,
+                     float *rows, int *count, hipStream_t stream);
 
 /* ---- RoIAlign --------------------------------------------------------------------------- *
  * torchvision.ops.roi_align(feat, rois, (ph,pw)) at models/rrnet.py:51 (spatial_scale 1,

@@ -26,6 +26,7 @@ PER_FILE = {
     "augment_paste.hip": ["-ffp-contract=off"],
     "evalmatch.hip": ["-ffp-contract=off"],
     "detect.hip": ["-ffp-contract=off"],
+    "retina.hip": ["-ffp-contract=off"],
 }
 
 

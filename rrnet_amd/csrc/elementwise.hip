@@ -281,6 +281,70 @@ __global__ __launch_bounds__(EW_THREADS) void bn_bwd_reduce_kernel(const float *
     }
 }
 
+// bn_bwd_reduce_kernel for layers wider than 4 * EW_THREADS channels (ResNet's 2048-channel stage; fp32 tensors only): blockIdx.y
+// names a chunk of up to 4 * EW_THREADS channels, inside which the thread layout, the 8-pixel fp32 partial sums and the double
+// reduction are those of the kernel above.
+__global__ __launch_bounds__(EW_THREADS) void bn_bwd_reduce_wide_kernel(const float *dz, const float *z, const float *y,
+                                                                        const float *mean, const float *invstd,
+                                                                        const float *mscale, const float *mshift,
+                                                                        double *sums, long npix, int C)
+{
+    __shared__ double red[2][EW_THREADS * 4];
+    const int cbase = blockIdx.y * (EW_THREADS * 4);
+    const int cw = min(EW_THREADS * 4, C - cbase);       // > 0 and a multiple of 4 (checked by the launcher)
+    const int C4 = cw / 4;
+    const int lanes = EW_THREADS / C4;
+    const int t = threadIdx.x;
+    const int cq = t % C4, pl = t / C4;
+    double d1[4] = {0.0, 0.0, 0.0, 0.0}, d2[4] = {0.0, 0.0, 0.0, 0.0};
+    if (pl < lanes) {
+        const int ch = cbase + cq * 4;
+        const f32x4 mu = *reinterpret_cast<const f32x4 *>(mean + ch);
+        const f32x4 is = *reinterpret_cast<const f32x4 *>(invstd + ch);
+        f32x4 msc = {0.f, 0.f, 0.f, 0.f}, msh = msc;
+        if (mscale) { msc = *reinterpret_cast<const f32x4 *>(mscale + ch); msh = *reinterpret_cast<const f32x4 *>(mshift + ch); }
+        const long step = (long)gridDim.x * lanes;
+        for (long p0 = (long)blockIdx.x * lanes + pl; p0 < npix; p0 += step * 8) {
+            f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const long p = p0 + u * step;
+                if (p < npix) {
+                    const long off = p * C + ch;
+                    f32x4 g = *reinterpret_cast<const f32x4 *>(dz + off);
+                    const f32x4 yy = *reinterpret_cast<const f32x4 *>(y + off);
+                    if (z) {
+                        const f32x4 zz = *reinterpret_cast<const f32x4 *>(z + off);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) g[e] = zz[e] > 0.f ? g[e] : 0.f;
+                    } else if (mscale) {
+                        const f32x4 zz = rr_bn_affine4(yy, msc, msh);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) g[e] = zz[e] > 0.f ? g[e] : 0.f;
+                    }
+                    const f32x4 xh = (yy - mu) * is;
+                    s1 += g;
+                    s2 += g * xh;
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { d1[e] += (double)s1[e]; d2[e] += (double)s2[e]; }
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { red[0][t * 4 + e] = d1[e]; red[1][t * 4 + e] = d2[e]; }
+    __syncthreads();
+    for (int c = t; c < cw; c += EW_THREADS) {
+        double a = 0.0, b = 0.0;
+        for (int l = 0; l < lanes; ++l) {
+            a += red[0][(l * C4 + c / 4) * 4 + (c & 3)];
+            b += red[1][(l * C4 + c / 4) * 4 + (c & 3)];
+        }
+        unsafeAtomicAdd(sums + cbase + c, a);
+        unsafeAtomicAdd(sums + C + cbase + c, b);
+    }
+}
+
 // dx = gamma*invstd*(dy - sum_dy/count - xhat*sum_dy_xhat/count); optional g_out = dy (the masked
 // gradient, for the residual branch); workgroup 0 also accumulates dgamma / dbeta.
 // AMAX: also max |dx| -> *amax (bit pattern): dx is the output gradient of the convolution in front of this BatchNorm, i.e.
@@ -1031,7 +1095,7 @@ extern "C" int rr_bn_bwd_reduce(const float *dz, const float *z, const float *y,
                                 const float *invstd, const float *mask_scale, const float *mask_shift, double *sums,
                                 long npix, int c, int sums_zeroed, hipStream_t stream)
 {
-    RR_CHECK_ARG(c % 4 == 0 && c <= 1024, "rr_bn_bwd_reduce: C=%d must be a multiple of 4 and <= 1024", c);
+    RR_CHECK_ARG(c > 0 && c % 4 == 0 && c <= 65535 * 1024 && npix >= 0, "rr_bn_bwd_reduce: C=%d must be a positive multiple of 4", c);
     if (!sums_zeroed) hipMemsetAsync(sums, 0, sizeof(double) * 2 * c, stream);
     const int c4 = c / 4;
     const int lanes = EW_THREADS / c4 > 0 ? EW_THREADS / c4 : 1;
@@ -1041,6 +1105,12 @@ extern "C" int rr_bn_bwd_reduce(const float *dz, const float *z, const float *y,
     const long cap = npix >= 400000 ? 1024 : (npix >= 16384 ? 512 : 256);
     if (blocks > cap) blocks = cap;
     if (blocks < 1) blocks = 1;
+    if (c > EW_THREADS * 4) {          // wider than one workgroup's channel quads: chunks of 4 * EW_THREADS channels on blockIdx.y
+        hipLaunchKernelGGL(bn_bwd_reduce_wide_kernel, dim3((int)blocks, rr_cdiv(c, EW_THREADS * 4)), dim3(EW_THREADS), 0, stream, dz, z, y,
+                           mean, invstd, mask_scale, mask_shift, sums, npix, c);
+        RR_CHECK_LAUNCH("rr_bn_bwd_reduce");
+        return RR_OK;
+    }
     hipLaunchKernelGGL(bn_bwd_reduce_kernel<false>, dim3((int)blocks), dim3(EW_THREADS), 0, stream, dz, z, y, mean, invstd, mask_scale,
                        mask_shift, sums, npix, c, (const unsigned short *)nullptr, (const unsigned short *)nullptr);
     RR_CHECK_LAUNCH("rr_bn_bwd_reduce");

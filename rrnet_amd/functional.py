@@ -815,6 +815,47 @@ def global_avg_pool(x):
     return _AvgPool.apply(x)
 
 
+class _MaxPool3x3S2(torch.autograd.Function):
+    """nn.MaxPool2d(kernel_size=3, stride=2, padding=1) (backbones/resnet.py:65); the backward gathers through the stored taps."""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = ops.to_nhwc(x)
+        y, idx = ops.maxpool3x3s2_fwd(x)
+        ctx.save_for_backward(idx)
+        ctx.shape = tuple(x.shape)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (idx,) = ctx.saved_tensors
+        return ops.maxpool3x3s2_bwd(ops.to_nhwc(dy), idx, ctx.shape)
+
+
+def max_pool3x3s2(x):
+    return _MaxPool3x3S2.apply(x)
+
+
+class _BilinearAdd(torch.autograd.Function):
+    """F.interpolate(x, size(y), mode='bilinear', align_corners=False) + y  (modules/fpn.py:39-40)."""
+
+    @staticmethod
+    def forward(ctx, x, y):
+        x, y = ops.to_nhwc(x), ops.to_nhwc(y)
+        ctx.x_shape = tuple(x.shape)
+        return ops.bilinear_add_fwd(x, y)
+
+    @staticmethod
+    def backward(ctx, dout):
+        dout = ops.to_nhwc(dout)
+        dx = ops.bilinear_add_bwd(dout, ctx.x_shape) if ctx.needs_input_grad[0] else None
+        return dx, dout
+
+
+def bilinear_add(x, y):
+    return _BilinearAdd.apply(x, y)
+
+
 class _RoIAlign(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feat, rois, out_size, spatial_scale, sampling_ratio):
@@ -864,6 +905,31 @@ class _FocalHM(torch.autograd.Function):
 
 def focal_loss_hm_from_logits(logits, gt):
     return _FocalHM.apply(logits, gt)
+
+
+class _RetinaCriterion(torch.autograd.Function):
+    """operators/retinanet_operator.py:47-113: anchor assignment, focal loss (modules/loss/functional.py:6-22) and smooth-L1 of a
+    whole batch -> the two scalars [cls_loss, loc_loss] as one tensor of 2."""
+
+    @staticmethod
+    def forward(ctx, loc, logits, annos, anchors, num_classes):
+        loc, logits = loc.contiguous().float(), logits.contiguous().float()
+        asg = ops.retina_assign(annos, anchors, num_classes)
+        ctx.asg = asg
+        ctx.save_for_backward(loc, logits)
+        return ops.retina_loss_fwd(logits, loc, asg)
+
+    @staticmethod
+    def backward(ctx, gout):
+        loc, logits = ctx.saved_tensors
+        dlogits, dloc = ops.retina_loss_bwd(logits, loc, ctx.asg, gout.contiguous().float())
+        return dloc, dlogits, None, None, None
+
+
+def retina_criterion(loc_preds, cls_preds, annos, anchors, num_classes):
+    """-> (cls_loss, loc_loss); annos [B,M,8] xywh rows as the collate pads them (not modified), anchors [A,4] xyxy."""
+    losses = _RetinaCriterion.apply(loc_preds, cls_preds, annos.detach(), anchors, int(num_classes))
+    return losses[0], losses[1]
 
 
 class _RegL1(torch.autograd.Function):

@@ -1862,6 +1862,122 @@ def dcn_psroi_bwd(dout, x, rois, trans, count, no_trans, spatial_scale, output_d
     return dx, dtrans
 
 
+# ---------------------------------------------------------------------------------------------
+# RetinaNet (csrc/retina.hip)
+# ---------------------------------------------------------------------------------------------
+def maxpool3x3s2_fwd(x):
+    """x NHWC [n,c,h,w] -> (y, idx): MaxPool2d(3, 2, 1) and the winning tap (uint8, 0..8) of every output element."""
+    _C.require_cuda(x)
+    assert is_nhwc(x) and x.dtype == torch.float32
+    n, c, h, w = x.shape
+    oh, ow = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    y = empty_nhwc(n, c, oh, ow, x.device)
+    idx = empty_nhwc(n, c, oh, ow, x.device, dtype=torch.uint8)
+    _C.check(_C.fn("rr_maxpool3x3s2_fwd")(_C.ptr(x), _C.ptr(y), _C.ptr(idx), n, h, w, c, _C.stream()), "rr_maxpool3x3s2_fwd")
+    return y, idx
+
+
+def maxpool3x3s2_bwd(dy, idx, x_shape):
+    n, c, h, w = x_shape
+    assert is_nhwc(dy) and is_nhwc(idx) and dy.shape == idx.shape and dy.dtype == torch.float32
+    assert tuple(dy.shape) == (n, c, (h - 1) // 2 + 1, (w - 1) // 2 + 1)
+    dx = empty_nhwc(n, c, h, w, dy.device)
+    _C.check(_C.fn("rr_maxpool3x3s2_bwd")(_C.ptr(dy), _C.ptr(idx), _C.ptr(dx), n, h, w, c, _C.stream()), "rr_maxpool3x3s2_bwd")
+    return dx
+
+
+def bilinear_add_fwd(x, y):
+    """y + F.interpolate(x, size(y), mode='bilinear', align_corners=False); both NHWC."""
+    _C.require_cuda(x, y)
+    assert is_nhwc(x) and is_nhwc(y) and x.shape[:2] == y.shape[:2] and x.dtype == y.dtype == torch.float32
+    n, c, ih, iw = x.shape
+    oh, ow = y.shape[2], y.shape[3]
+    out = empty_nhwc(n, c, oh, ow, x.device)
+    _C.check(_C.fn("rr_bilinear_add_fwd")(_C.ptr(x), _C.ptr(y), _C.ptr(out), n, ih, iw, oh, ow, c, _C.stream()),
+             "rr_bilinear_add_fwd")
+    return out
+
+
+def bilinear_add_bwd(dout, x_shape):
+    n, c, ih, iw = x_shape
+    assert is_nhwc(dout) and dout.shape[0] == n and dout.shape[1] == c and dout.dtype == torch.float32
+    dx = empty_nhwc(n, c, ih, iw, dout.device)
+    _C.check(_C.fn("rr_bilinear_add_bwd")(_C.ptr(dout), _C.ptr(dx), n, ih, iw, dout.shape[2], dout.shape[3], c, _C.stream()),
+             "rr_bilinear_add_bwd")
+    return dx
+
+
+def retina_assign(annos, anchors, num_classes):
+    """annos [B,M,8] xywh rows (zero rows = padding), anchors [A,4] xyxy ->
+    dict(state int8 [B,A], argmax int32, max_iou, cls int32, target [B,A,4], npos int32 [B])."""
+    _C.require_cuda(annos, anchors)
+    assert annos.dim() == 3 and annos.shape[2] == 8 and anchors.dim() == 2 and anchors.shape[1] == 4
+    annos = annos.contiguous().float()
+    anchors = anchors.contiguous().float()
+    b, m, a = annos.shape[0], annos.shape[1], anchors.shape[0]
+    if m == 0:                                  # an all-padding image list: one zero row wins nothing
+        annos, m = annos.new_zeros((b, 1, 8)), 1
+    dev = annos.device
+    out = {
+        "state": torch.empty((b, a), dtype=torch.int8, device=dev),
+        "argmax": torch.empty((b, a), dtype=torch.int32, device=dev),
+        "max_iou": torch.empty((b, a), dtype=torch.float32, device=dev),
+        "cls": torch.empty((b, a), dtype=torch.int32, device=dev),
+        "target": torch.empty((b, a, 4), dtype=torch.float32, device=dev),
+        "npos": torch.empty((b,), dtype=torch.int32, device=dev),
+    }
+    _C.check(_C.fn("rr_retina_assign")(_C.ptr(annos), _C.ptr(anchors), b, m, a, int(num_classes), _C.ptr(out["state"]),
+                                       _C.ptr(out["argmax"]), _C.ptr(out["max_iou"]), _C.ptr(out["cls"]),
+                                       _C.ptr(out["target"]), _C.ptr(out["npos"]), _C.stream()), "rr_retina_assign")
+    return out
+
+
+def _retina_loss_args(logits, loc, asg):
+    assert logits.dim() == 3 and loc.dim() == 3 and loc.shape[2] == 4 and logits.shape[:2] == loc.shape[:2]
+    assert logits.is_contiguous() and loc.is_contiguous() and logits.dtype == loc.dtype == torch.float32
+    b, a, c = logits.shape
+    assert tuple(asg["state"].shape) == (b, a) and tuple(asg["target"].shape) == (b, a, 4)
+    return b, a, c
+
+
+def retina_loss_fwd(logits, loc, asg):
+    """-> losses [2] = (classification, regression) of the criterion, bit-identical run to run."""
+    _C.require_cuda(logits, loc)
+    b, a, c = _retina_loss_args(logits, loc, asg)
+    nblk = _C.fn("rr_retina_loss_blocks")(a, c)
+    partial = torch.empty((b, nblk, 2), dtype=torch.float64, device=logits.device)
+    losses = torch.empty(2, dtype=torch.float32, device=logits.device)
+    _C.check(_C.fn("rr_retina_loss_fwd")(_C.ptr(logits), _C.ptr(loc), _C.ptr(asg["state"]), _C.ptr(asg["cls"]),
+                                         _C.ptr(asg["target"]), _C.ptr(asg["npos"]), b, a, c, _C.ptr(partial), _C.ptr(losses),
+                                         _C.stream()), "rr_retina_loss_fwd")
+    return losses
+
+
+def retina_loss_bwd(logits, loc, asg, gout):
+    """gout [2] (device) -> (d logits [B,A,C], d loc [B,A,4])."""
+    b, a, c = _retina_loss_args(logits, loc, asg)
+    assert gout.is_cuda and gout.numel() == 2 and gout.dtype == torch.float32 and gout.is_contiguous()
+    dlogits, dloc = torch.empty_like(logits), torch.empty_like(loc)
+    _C.check(_C.fn("rr_retina_loss_bwd")(_C.ptr(logits), _C.ptr(loc), _C.ptr(asg["state"]), _C.ptr(asg["cls"]),
+                                         _C.ptr(asg["target"]), _C.ptr(asg["npos"]), _C.ptr(gout), b, a, c, _C.ptr(dlogits),
+                                         _C.ptr(dloc), _C.stream()), "rr_retina_loss_bwd")
+    return dlogits, dloc
+
+
+def retina_decode(logits, loc, anchors, score_thr=0.1):
+    """logits [B,A,C], loc [B,A,4], anchors [A,4] -> (rows [B,A,6] = x,y,w,h,prob,cls+1 in anchor order, count int32 [B])."""
+    _C.require_cuda(logits, loc, anchors)
+    logits, loc, anchors = logits.contiguous().float(), loc.contiguous().float(), anchors.contiguous().float()
+    b, a, c = logits.shape
+    assert tuple(loc.shape) == (b, a, 4) and tuple(anchors.shape) == (a, 4)
+    rows = torch.zeros((b, a, 6), dtype=torch.float32, device=logits.device)
+    count = torch.zeros((b,), dtype=torch.int32, device=logits.device)
+    if a > 0:
+        _C.check(_C.fn("rr_retina_decode")(_C.ptr(logits), _C.ptr(loc), _C.ptr(anchors), b, a, c, float(score_thr),
+                                           _C.ptr(rows), _C.ptr(count), _C.stream()), "rr_retina_decode")
+    return rows, count
+
+
 class _OpsModule(types.ModuleType):
     """`ops.BF16` (read / assign) = this thread's arithmetic switch."""
 

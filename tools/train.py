@@ -1,6 +1,6 @@
-"""Train RRNet or CenterNet on one GPU: the counterpart of tools/detect.py.
+"""Train RRNet, CenterNet or RetinaNet on one GPU: the counterpart of tools/detect.py.
 
-  python tools/train.py --config rrnet_config|rrnet_fillduck_config|centernet_config [--data-root D] [--iters N]
+  python tools/train.py --config rrnet_config|rrnet_fillduck_config|centernet_config|retinanet_config [--data-root D] [--iters N]
                         [--batch B] [--crop H W] [--backbone NAME] [--bf16] [--full-state] [--resume auto|PATH]
                         [--checkpoint-interval N] [--print-interval N] [--keep-states N]
 
@@ -18,7 +18,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-CONFIGS = ("rrnet_config", "rrnet_fillduck_config", "centernet_config")
+CONFIGS = ("rrnet_config", "rrnet_fillduck_config", "centernet_config", "retinanet_config")
 
 
 def load_config(name):
@@ -49,6 +49,8 @@ def configure(args):
     cfg = load_config(args.config)
     if args.bf16 and args.config.startswith("centernet"):
         raise SystemExit("--bf16: CenterNet runs in fp32 only (the model has no bf16 scope)")
+    if args.bf16 and args.config.startswith("retinanet"):
+        raise SystemExit("--bf16: RetinaNet runs in fp32 only (the model has no bf16 scope)")
     if args.data_root is not None:
         cfg.data_root = args.data_root
     if args.iters is not None:
@@ -89,6 +91,8 @@ def main(argv=None):
     torch.cuda.set_device(0)
     if args.config.startswith("centernet"):
         from rrnet_amd.operators.centernet_operator import CenterNetOperator as Operator
+    elif args.config.startswith("retinanet"):
+        from rrnet_amd.operators.retinanet_operator import RetinaNetOperator as Operator
     else:
         from rrnet_amd.operators.rrnet_operator import RRNetOperator as Operator
     Operator(cfg).training_process()
