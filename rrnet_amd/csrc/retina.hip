@@ -546,12 +546,12 @@ __global__ __launch_bounds__(TPB) void retina_decode_kernel(const float *__restr
             int bi = 0;
             for (int c = 1; c < C; ++c) {
                 const float p = sigmoidf_(q[c]);
-                if (p > best) {                           // first maximum
+                if (p > best || p != p) {                 // first maximum; a NaN is the maximum wherever it stands (torch's max)
                     best = p;
                     bi = c;
                 }
             }
-            keep = best > thr;                            // NaN leaves
+            keep = best > thr;                            // a row with a NaN leaves
             if (keep) {
                 const rr_f32x4 bx = *reinterpret_cast<const rr_f32x4 *>(anchors + (long)a * 4);
                 const rr_f32x4 d = *reinterpret_cast<const rr_f32x4 *>(loc + ((long)b * A + a) * 4);

@@ -51,6 +51,120 @@ def criterion_batch(kind, num_classes=10):
     raise KeyError(kind)
 
 
+# The criterion's launch routes (tests/test_retina_gpu.py runs each against float64; tests/test_retina_host.py proves on the
+# host that each input sits on its route and that float64 can make every discrete decision of it on its own).
+# name: (kind, anchors, classes, seed of the predictions, saturated logits); anchors = an image size for `anchors_of`, a
+# number of synthetic anchors, or None where the kind brings its own.
+CRIT_ROUTE_CASES = {
+    # C % 4 == 0: the float4 loss kernels.  4 classes: the rows carry 3, 1, 0, 4, 4, 2, every lane of the one vector is hot
+    # somewhere; 8: class 8 is lane 3 of the second vector; 12: class 10 is in the third vector.  Row 3 (the 3x4 box) wins no
+    # anchor, so its class 7 is never hot: c12_swapped moves 7 and 10 to rows 0 and 1, which do win.
+    "c4": ("base", (64, 64), 4, 41, False),
+    "c8": ("base", (64, 64), 8, 42, False),
+    "c12": ("base", (64, 64), 12, 43, False),
+    "c12_swapped": ("swapped", (64, 64), 12, 44, False),
+    "c8_saturated": ("base", (64, 64), 8, 45, True),
+    # M against ANNO_CHUNK = 256: exactly one chunk, one row into the second, one row into the third
+    "many_256": (("many", 256, 3), (64, 64), 10, 46, False),
+    "many_257": (("many", 257, 6), (72, 56), 10, 47, False),
+    "many_513": (("many", 513, 2), (64, 64), 10, 48, False),
+    # IoU exactly 0.5 (positive), 0.75, 0.75, 0 and 2/5 (not below 0.4: ignored)
+    "exact_thresholds": ("exact", None, 10, 49, False),
+    # rr_retina_loss_blocks at both ends: 1 workgroup; the cap of 1024, where 1 048 700 elements make the stride loops of
+    # 262 144 threads wrap a fifth time for the last 124
+    "one_block_100": (("synthetic", 11), 100, 10, 50, False),
+    "one_anchor": (("synthetic", 12), 1, 10, 51, False),
+    "block_cap": (("synthetic", 21), 104870, 10, 52, False),
+}
+MANY_DUPLICATE = (3, 300)            # many_513: row 300 repeats row 3, class included
+EXACT_ANCHORS = [[0, 0, 4, 4], [10, 10, 14, 14], [20, 20, 24, 24], [30, 30, 34, 34], [40, 40, 45, 45]]
+EXACT_XYXY = [(0, 0, 4, 2), (40, 40, 45, 42), (10, 10, 13, 14), (20, 20, 24, 23)]
+EXACT_STATE, EXACT_ARGMAX = [1, 1, 1, 0, -1], [0, 2, 3, 0, 1]
+SWAPPED_CLASSES = [7, 10, 0, 3, 1, 2]
+
+
+def many_boxes(m, seed):
+    """-> [2, m, 8]: m boxes with corners uniform in (-4, 56) and sizes uniform in (3, 48), snapped to quarter pixels, classes
+    uniform in 1..10; from 301 rows on, row 300 repeats row 3.  The second image holds the same rows in reverse order, so a
+    tie across a chunk boundary is met from both sides."""
+    g = np.random.default_rng(seed)
+    xy = np.round(g.uniform(-4, 56, (m, 2)) * 4) / 4
+    wh = np.round(g.uniform(3, 48, (m, 2)) * 4) / 4
+    out = np.zeros((m, 8), dtype=np.float32)
+    out[:, 0:2], out[:, 2:4], out[:, 4] = xy, wh, 1.0
+    out[:, 5] = g.integers(1, 11, m)
+    if m > MANY_DUPLICATE[1]:
+        out[MANY_DUPLICATE[1]] = out[MANY_DUPLICATE[0]]
+    return np.stack([out, out[::-1].copy()])
+
+
+def synthetic_anchors(a, seed):
+    """a boxes (xyxy float32): centres uniform in a square of side 1024 (64 for fewer than 1000), sides 16, 64 or 128 times
+    uniform(0.7, 1.4)."""
+    g = np.random.default_rng(seed)
+    ctr = g.uniform(0, 1024 if a >= 1000 else 64, (a, 2))
+    half = 0.5 * g.choice([16.0, 64.0, 128.0], (a, 1)) * g.uniform(0.7, 1.4, (a, 2))
+    return np.concatenate([ctr - half, ctr + half], axis=1).astype(np.float32)
+
+
+def synthetic_batch(anchors, seed):
+    """-> [1, 7, 8]: seven boxes, box i being anchor (i * A) // 7 with its sides scaled by uniform(0.85, 1.2) and its centre
+    moved by up to 8 % of them, so that every box has anchors on either side of both thresholds."""
+    g = np.random.default_rng(seed + 1000)
+    a = anchors.shape[0]
+    src = anchors[[(i * a) // 7 for i in range(7)]].astype(np.float64)
+    wh = src[:, 2:4] - src[:, 0:2]
+    ctr = 0.5 * (src[:, 0:2] + src[:, 2:4]) + g.uniform(-0.08, 0.08, (7, 2)) * wh
+    wh = wh * g.uniform(0.85, 1.2, (7, 2))
+    boxes = np.round(np.concatenate([ctr - 0.5 * wh, ctr + 0.5 * wh], axis=1) * 4) / 4
+    return annos_of([tuple(r) for r in boxes], [1 + (3 * i) % 10 for i in range(7)])[None]
+
+
+def criterion_inputs(kind, where, num_classes=10):
+    """-> (annos [B,M,8] float32 numpy, anchors [A,4] float32 tensor) of a CRIT_CASES / CRIT_ROUTE_CASES entry."""
+    if kind == "swapped":
+        a = annos_of(GT_XYXY, SWAPPED_CLASSES, 7)
+        return np.stack([a, np.zeros_like(a), annos_of(GT_XYXY[::-1], SWAPPED_CLASSES[::-1], 7)]), anchors_of(where)
+    if kind == "exact":
+        return annos_of(EXACT_XYXY, [1, 2, 3, 4])[None], torch.tensor(EXACT_ANCHORS, dtype=torch.float32)
+    if isinstance(kind, tuple) and kind[0] == "many":
+        return many_boxes(kind[1], kind[2]), anchors_of(where)
+    if isinstance(kind, tuple) and kind[0] == "synthetic":
+        anchors = synthetic_anchors(where, kind[1])
+        return synthetic_batch(anchors, kind[1]), torch.from_numpy(anchors)
+    return criterion_batch(kind, num_classes), anchors_of(where)
+
+
+def loss_blocks(a, c):
+    """rr_retina_loss_blocks of the built library (a host function: no GPU)."""
+    from rrnet_amd import _C
+    return int(_C.fn("rr_retina_loss_blocks")(int(a), int(c)))
+
+
+def input_margins(annos, anchors, num_classes):
+    """What makes an input decidable by float64 alone -> dict: `agree` (the float32 and float64 restatements give the same
+    states, argmax and classes), `threshold` (smallest distance of a best IoU from 0.4 or 0.5), `gap` (smallest best minus
+    second-best IoU on a positive anchor, rows that repeat the winner's box exactly left out), `repeats` (rows whose box
+    equals an earlier row's, per image), `a64` (the float64 assignment)."""
+    a64 = assign(annos, anchors, num_classes, torch.float64)
+    a32 = assign(annos, anchors, num_classes, torch.float32)
+    agree = all(bool(torch.equal(a64[k], a32[k])) for k in ("state", "argmax", "cls", "npos"))
+    best = a64["max_iou"]
+    threshold = min(float((best - 0.4).abs().min()), float((best - 0.5).abs().min()))
+    gap, repeats = float("inf"), []
+    for i in range(annos.shape[0]):
+        rows = torch.from_numpy(np.ascontiguousarray(annos[i, :, :4]))
+        same = (rows[:, None, :] == rows[None, :, :]).all(dim=2)                # [M, M]
+        live = rows[:, 2:4].abs().sum(dim=1) > 0                                # padding rows repeat each other by design
+        repeats.append(int((torch.triu(same, 1) & live[:, None] & live[None, :]).any(dim=0).sum()))
+        pos = torch.nonzero(a64["state"][i] == 1)[:, 0]
+        if pos.numel():
+            iou = a64["iou"][i][:, pos].clone()
+            iou[same[a64["argmax"][i][pos]].T] = -1.0                           # the winner and its exact repeats
+            gap = min(gap, float((best[i][pos] - iou.max(dim=0).values).min()))
+    return {"agree": agree, "threshold": threshold, "gap": gap, "repeats": repeats, "a64": a64}
+
+
 def criterion_preds(b, a, c, seed, saturate=False):
     g = np.random.default_rng(seed)
     logits = (g.standard_normal((b, a, c)) * 2.0 - 2.0).astype(np.float32)
@@ -226,6 +340,9 @@ class _Block(nn.Module):
         return F.relu(self.bn3(self.conv3(x)) + skip)
 
 
+IDENTITY_DEPTHS = (2, 1, 1, 2)       # the smallest ResNet with identity blocks at its narrowest (256) and widest (2048) stage
+
+
 class _Backbone(nn.Module):
     def __init__(self, depths):
         super().__init__()
@@ -238,12 +355,16 @@ class _Backbone(nn.Module):
             setattr(self, "layer%d" % (i + 1), nn.Sequential(*blocks))
             cin = planes * 4
 
-    def forward(self, x):
+    def stages(self, x):
+        """-> (l1, l2, l3, l4), what the package's ResNet returns."""
         x = F.max_pool2d(F.relu(self.bn1(self.conv1(x))), 3, 2, 1)
         l1 = self.layer1(x)
         l2 = self.layer2(l1)
         l3 = self.layer3(l2)
-        return l2, l3, self.layer4(l3)
+        return l1, l2, l3, self.layer4(l3)
+
+    def forward(self, x):
+        return self.stages(x)[1:]
 
 
 class _Pyramid(nn.Module):

@@ -52,14 +52,14 @@ CRIT_CASES = {                      # kind, image size, classes, seed, saturated
     "one_class": ("base", (72, 56), 1, 25, False),
     "saturated": ("base", (64, 64), 10, 26, True),
 }
+CRIT_CASES.update(rc.CRIT_ROUTE_CASES)   # every launch route; tests/test_retina_host.py proves each input sits on its route
 W_CLS, W_LOC = 0.7, 1.3             # the two upstream scalars of the backward
 
 
 @functools.lru_cache(maxsize=None)
 def _crit_case(name):
     kind, size, classes, seed, sat = CRIT_CASES[name]
-    annos = rc.criterion_batch(kind, classes)
-    anchors = rc.anchors_of(size)
+    annos, anchors = rc.criterion_inputs(kind, size, classes)
     loc, logits = rc.criterion_preds(annos.shape[0], anchors.shape[0], classes, seed, saturate=sat)
     r64 = rc.criterion_with_grads(loc, logits, annos, anchors, classes, torch.float64, W_CLS, W_LOC)
     r32 = rc.criterion_with_grads(loc, logits, annos, anchors, classes, torch.float32, W_CLS, W_LOC)
@@ -89,13 +89,19 @@ def test_retina_criterion_vs_fp64(name):
     8.6e-7 (max 2.89); cls_loss 2.7e-6 / 5.0e-6 of 103.7 (tolerance 1.2e-5); loc_loss 4.3e-8 / 1.7e-8 of 0.732; d loc 1.2e-8
     / 1.2e-8 (max 6.0e-3); d logits for 1e-3 <= p <= 0.99 1.4e-8 / 1.6e-8 (max 0.066), for p > 0.99 8.5e-9 / 1.2e-8.  The
     closest case is one_class: cls_loss 6.0e-7 / 1.3e-6 of 13.4 against a tolerance of 2.4e-6.  saturated: the float32 upper
-    clamp 1 - 2^-23 is not float64's 1 - 1e-7, which moves the loss of 1747 by 18.2 in the restatement and the kernel alike."""
+    clamp 1 - 2^-23 is not float64's 1 - 1e-7, which moves the loss of 1747 by 18.2 in the restatement and the kernel alike.
+    The routes of rc.CRIT_ROUTE_CASES, cls_loss: c4 2.1e-6 / 1.7e-6 of 41.8; c8 6.4e-6 / 1.3e-6 of 86.8; c12 1.3e-5 / 2.0e-6 of
+    130; c12_swapped 1.2e-5 / 3.7e-6 of 128; c8_saturated 15.6 / 15.6 of 1490 (the clamp again); many_256 4.8e-8 / 1.9e-7 of
+    2.14 (tolerance 2.6e-7, the closest of the new cases); many_257 2.9e-7 / 5.5e-8; many_513 5.4e-8 / 5.4e-8 of 2.08;
+    exact_thresholds 2.6e-8 / 3.3e-8 of 0.776; one_block_100 1.4e-7 / 9.9e-8; one_anchor 3.6e-7 / 1.2e-7 of 3.60; block_cap
+    5.4e-6 / 2.2e-6 of 77.8 with 518 positives, its last 13 rows d logits 3.7e-11 / 3.6e-11 (max 3.0e-4) and d loc 1.1e-10 /
+    1.1e-10.  Every discrete result of every case is equal."""
     from rrnet_amd import functional as RF
     from rrnet_amd import ops
     annos, anchors, loc, logits, classes, r64, r32 = _crit_case(name)
     a64 = r64["asg"]
     print("\ncriterion %s: B=%d A=%d C=%d npos %s" % (name, logits.shape[0], logits.shape[1], classes, a64["npos"].tolist()))
-    if name.startswith("base"):
+    if CRIT_CASES[name][0] in ("base", "swapped"):
         assert int(a64["npos"][1]) == 0 and int(a64["npos"][0]) > 0        # one image without annotations
     an_d, ad = torch.from_numpy(annos).cuda(), anchors.cuda()
     before = an_d.clone()
@@ -105,6 +111,13 @@ def test_retina_criterion_vs_fp64(name):
     assert np.array_equal(asg["argmax"].cpu().numpy(), a64["argmax"].numpy())
     assert np.array_equal(asg["npos"].cpu().numpy(), a64["npos"].numpy())
     assert np.array_equal(asg["cls"].cpu().numpy(), a64["cls"].numpy())
+    if name == "exact_thresholds":                                         # 0.5 is positive, 2/5 is not below 0.4
+        assert asg["state"][0].tolist() == rc.EXACT_STATE and asg["argmax"][0].tolist() == rc.EXACT_ARGMAX
+    if name == "many_513":                                                 # rows 3 and 300 tie across a chunk boundary: 3 wins
+        first, twin = rc.MANY_DUPLICATE
+        got_arg, got_state = asg["argmax"].cpu(), asg["state"].cpu()
+        assert int(((got_arg[0] == first) & (got_state[0] == 1)).sum()) > 0 and not bool((got_arg[0] == twin).any())
+        assert int(((got_arg[1] == 512 - twin) & (got_state[1] == 1)).sum()) > 0 and not bool((got_arg[1] == 512 - first).any())
     if name == "bad_class":
         hit = (a64["argmax"] == 0) & (a64["state"] == 1)
         assert bool(hit.any()) and int(a64["cls"][hit].abs().max()) == 0    # positives of the bad box carry no class
@@ -124,7 +137,7 @@ def test_retina_criterion_vs_fp64(name):
     assert np.all(got_dl[r64["dloc"] == 0.0] == 0.0) and np.all(got_dg[r64["dlogits"] == 0.0] == 0.0)
     ignored = (a64["state"] == -1).numpy()
     assert np.all(got_dg[ignored] == 0.0) and np.all(got_dl[(a64["state"] != 1).numpy()] == 0.0)
-    if name == "saturated":
+    if CRIT_CASES[name][4]:
         sat = np.abs(logits) == 40.0
         assert sat.any() and np.all(got_dg[sat] == 0.0)                    # the clamp passes no gradient
     _judge("d loc", got_dl, r64["dloc"], r32["dloc"])
@@ -132,6 +145,12 @@ def test_retina_criterion_vs_fp64(name):
     for tag, sel in (("p<1e-3", p < 1e-3), ("1e-3<=p<=0.99", (p >= 1e-3) & (p <= 0.99)), ("p>0.99", p > 0.99)):
         if sel.any():
             _judge("d logits " + tag, got_dg[sel], r64["dlogits"][sel], r32["dlogits"][sel])
+    if name == "block_cap":
+        # the three bands above cover every element; the rows that only the fifth turn of the stride loop reaches, on their own
+        last = (4 * 1024 * 256) // classes
+        assert last < logits.shape[1] and np.count_nonzero(r64["dlogits"][:, last:]) and np.count_nonzero(r64["dloc"][:, last:])
+        _judge("d logits, last %d rows" % (logits.shape[1] - last), got_dg[:, last:], r64["dlogits"][:, last:], r32["dlogits"][:, last:])
+        _judge("d loc, last rows", got_dl[:, last:], r64["dloc"][:, last:], r32["dloc"][:, last:])
 
 
 # --------------------------------------------------------------------------------------------------------------------
@@ -203,7 +222,9 @@ def test_maxpool_propagates_nan():
 # --------------------------------------------------------------------------------------------------------------------
 # bilinear upsample-add
 # --------------------------------------------------------------------------------------------------------------------
-BILINEAR_CASES = [((1, 1), (1, 1)), ((3, 4), (5, 7)), ((4, 4), (8, 8)), ((5, 5), (9, 9)), ((4, 7), (7, 13))]
+BILINEAR_CASES = [((1, 1), (1, 1)), ((3, 4), (5, 7)), ((4, 4), (8, 8)), ((5, 5), (9, 9)), ((4, 7), (7, 13)),
+                  # one source pixel feeds everything; ratio above 4; shrinking; shrinking by a non-integer ratio; same size
+                  ((1, 1), (4, 5)), ((2, 3), (9, 10)), ((8, 9), (4, 3)), ((7, 13), (4, 7)), ((5, 5), (5, 5))]
 
 
 def _bilinear_ref(x, y, dout, dtype):
@@ -214,9 +235,21 @@ def _bilinear_ref(x, y, dout, dtype):
     return [t.detach().numpy().astype(np.float64) for t in (out, xt.grad, yt.grad)]
 
 
-@pytest.mark.parametrize("c", [256, 3])
+@pytest.mark.parametrize("c", [256, 3, 4, 6])
 @pytest.mark.parametrize("src,dst", BILINEAR_CASES)
 def test_bilinear_add_vs_fp64(src, dst, c):
+    """out and d x by the measured rule; d y is dout itself; at equal sizes out = y + x and d x = dout bit for bit; the
+    adjoint identity sum(dout (out - y)) = sum(x d x): both sides summed in float64 from the kernel's results must agree
+    within the sum of the two sides' bounds, each the measured rule's for that side (4x the float32 restatement's error of
+    that sum, floor 2 u |sum|); the float64 restatement's own two sides agree to 1e-12.  Each side's distance from float64
+    is printed, not asserted: one sum's float32 error is a single random number and can be small by chance (with C = 3,
+    (1,1) -> (4,5): kernel 1.3e-7 / 4.6e-7, float32 restatement 0.9e-7 / 1.1e-7; (2,3) -> (9,10): 1.9e-6 / 2.7e-6 against
+    1.8e-7 / 4.3e-7), while every element of out and d x is within its bound.
+    Measured (float32 restatement on the CPU / kernel on an MI355X, both against float64), C = 256: (2,3) -> (9,10) out 7.3e-7
+    / 5.5e-7, d x 2.8e-6 / 2.5e-6 (max 11.1), the two sides 2.7e-5 apart against a bound of 7.1e-5; (8,9) -> (4,3) out 3.0e-7
+    / 3.0e-7, d x 0 / 0 (every weight is 1/4), sides 8.0e-6 apart (bound 3.6e-5); (7,13) -> (4,7) out 1.8e-6 / 1.8e-6, d x 1.1e-6
+    / 1.1e-6, sides 1.0e-5 apart (bound 2.0e-4).  The two sides come closest to their bound at (5,5) -> (9,9), C = 256 (2.1e-5
+    of 2.6e-5) and at (1,1) -> (4,5), C = 3 (6.0e-7 of 8.0e-7)."""
     from rrnet_amd import functional as RF
     g = np.random.default_rng(31 * src[0] + dst[1] + c)
     n = 2
@@ -232,14 +265,26 @@ def test_bilinear_add_vs_fp64(src, dst, c):
     _judge("out", _np(out), r64[0], r32[0])
     _judge("d x", _np(xd.grad), r64[1], r32[1])
     assert np.array_equal(yd.grad.cpu().numpy(), dout)                          # d y is dout itself
+    if src == dst:
+        assert np.array_equal(out.detach().cpu().numpy().view(np.uint32), (y + x).view(np.uint32))
+        assert np.array_equal(xd.grad.cpu().numpy().view(np.uint32), dout.view(np.uint32))
+    x64, y64, d64 = (a.astype(np.float64) for a in (x, y, dout))
+    sides = [[float((d64 * (o - y64)).sum()), float((x64 * dx).sum())] for o, dx in ((_np(out), _np(xd.grad)), r64[:2], r32[:2])]
+    assert abs(sides[1][0] - sides[1][1]) <= 1e-12 * float(np.abs(d64 * (r64[0] - y64)).sum())
+    tol = sum(measured_tol(abs(s32 - s64), np.array([s64])) for s64, s32 in zip(sides[1], sides[2]))
+    gap = abs(sides[0][0] - sides[0][1])
+    print("  adjoint: sum(dout (out - y)) %.9g  sum(x dx) %.9g  differ by %.3g (float32 restatement %.3g), tol %.3g;  each side off "
+          "float64 by %.3g / %.3g (float32 restatement %.3g / %.3g)"
+          % (sides[0][0], sides[0][1], gap, abs(sides[2][0] - sides[2][1]), tol, abs(sides[0][0] - sides[1][0]),
+             abs(sides[0][1] - sides[1][1]), abs(sides[2][0] - sides[1][0]), abs(sides[2][1] - sides[1][1])))
+    assert gap <= tol, (gap, tol)
 
 
 # --------------------------------------------------------------------------------------------------------------------
 # decode
 # --------------------------------------------------------------------------------------------------------------------
-def _decode_inputs(a, c, seed, mode):
+def _decode_inputs(a, c, seed, mode, b=2, thr=0.1):
     g = np.random.default_rng(seed)
-    b = 2
     logits = (g.standard_normal((b, a, c)) * 2.0 - 2.5).astype(np.float32)
     if mode == "none":
         logits = (-5.0 - np.abs(logits)).astype(np.float32)
@@ -253,8 +298,24 @@ def _decode_inputs(a, c, seed, mode):
         for i in range(b):
             sel = np.nonzero(rows & (first[i] < c - 1))[0]
             logits[i, sel, c - 1] = top[i, sel]
+    if mode == "batch3":                                                        # some; the middle image nothing; the last everything
+        logits[0] -= np.float32(2.0)
+        logits[1] = (-5.0 - np.abs(logits[1])).astype(np.float32)
+        logits[2, :, c - 1] = 3.0
     p = 1.0 / (1.0 + np.exp(-logits.astype(np.float64)))
-    logits[np.abs(p - 0.1) < 1e-5] = -3.0                                       # nothing within 1e-5 of the threshold
+    logits[np.abs(p - thr) < 1e-5] = -3.0                                       # nothing within 1e-5 of the threshold
+    if mode == "special":
+        for i in range(b):
+            for kind, rows in SPECIAL_ROWS.items():
+                r = rows[i]
+                if kind == "nan_all":
+                    logits[i, r, :] = np.nan
+                elif kind == "nan_first":                                       # NaN in class 0, class 4 far above the threshold
+                    logits[i, r, 0], logits[i, r, 4] = np.nan, 6.0
+                elif kind == "nan_later":                                       # NaN in class 3, class 5 far above the threshold
+                    logits[i, r, 3], logits[i, r, 5] = np.nan, 6.0
+                elif kind == "inf":                                             # probability exactly 1, class 3
+                    logits[i, r, 2] = np.inf
     loc = (g.standard_normal((b, a, 4)) * 0.8).astype(np.float32)
     xy = g.uniform(0, 400, (a, 2))
     wh = g.uniform(4, 120, (a, 2))
@@ -262,28 +323,58 @@ def _decode_inputs(a, c, seed, mode):
     return logits, loc, anchors
 
 
-@pytest.mark.parametrize("a,mode", [(300, "none"), (1, "all"), (63, "mixed"), (64, "mixed"), (65, "mixed"), (1025, "mixed"),
-                                    (777, "all")])
-def test_retina_decode_vs_fp64(a, mode):
+# mode "special" (A = 300, C = 10): the rows of image 0 / image 1 that carry a NaN or an infinite logit; they sit in the first,
+# the second and the last wave of the first pass over 256 anchors and in the second pass, with kept rows on either side
+SPECIAL_ROWS = {"nan_all": (5, 255), "nan_first": (70, 256), "nan_later": (130, 299), "inf": (64, 257)}
+DECODE_CASES = [pytest.param(a, mode, 10, None, id="%d-%s" % (a, mode)) for a, mode in
+                [(300, "none"), (1, "all"), (63, "mixed"), (64, "mixed"), (65, "mixed"), (1025, "mixed"), (777, "all")]]
+DECODE_CASES += [pytest.param(a, "mixed", c, None, id="%d-mixed-c%d" % (a, c)) for c in (1, 4, 80) for a in (65, 1025)]
+DECODE_CASES += [pytest.param(1025, "mixed", 10, thr, id="1025-mixed-thr%g" % thr) for thr in (0.05, 0.5)]
+DECODE_CASES += [pytest.param(300, "batch3", 10, None, id="300-batch3"), pytest.param(300, "special", 10, None, id="300-special")]
+
+
+@pytest.mark.parametrize("a,mode,c,thr", DECODE_CASES)
+def test_retina_decode_vs_fp64(a, mode, c, thr):
+    """rr_retina_decode against rc.decode in float64: counts, classes (first maximum), kept rows in anchor order, nothing
+    behind the count.  C = 1 (the class loop does not run), 4, 10 and 80; the default threshold and 0.05 / 0.5 passed
+    explicitly; B = 3 with an image that keeps nothing between two that keep rows.  "special": a NaN probability is the row's
+    maximum wherever it stands (torch's max), so rows whose logits are all NaN, NaN in class 0, or NaN in class 3 beside a
+    class at 6.0 are dropped, and a +inf logit is kept with probability exactly 1; the rows around them pack as without them.
+    Measured (float32 restatement on the CPU / kernel on an MI355X, both against float64): special keeps 297 / 297 of 300,
+    probabilities 7.4e-8 / 7.4e-8, boxes 4.1e-5 / 4.1e-5 (max 412); C = 80, A = 1025 keeps every row, 8.2e-8 / 8.2e-8 and 4.4e-5
+    / 4.4e-5; C = 1 keeps 460 / 455 of 1025; threshold 0.5 keeps 688 / 664, 0.05 keeps 1024 / 1025; batch3 keeps 221, 0, 300.
+    Before the kernel took a NaN for the maximum, special kept 298 / 298: `p > best` skipped the NaN in class 3 and the row
+    stayed on the strength of its class at 6.0."""
     from rrnet_amd import ops
-    c = 10
-    logits, loc, anchors = _decode_inputs(a, c, 1000 + a, mode)
+    b = 3 if mode == "batch3" else 2
+    args = {} if thr is None else {"thr": thr}
+    thr_used = 0.1 if thr is None else thr
+    logits, loc, anchors = _decode_inputs(a, c, 1000 + a + (0 if c == 10 else 31 * c), mode, b=b, **args)
     p = 1.0 / (1.0 + np.exp(-logits.astype(np.float64)))
-    assert float(np.abs(p.max(axis=2) - 0.1).min()) > 1e-5
-    rows, count = ops.retina_decode(torch.from_numpy(logits).cuda(), torch.from_numpy(loc).cuda(),
-                                    torch.from_numpy(anchors).cuda())
+    top_p = p.max(axis=2)                                                       # NaN where a row holds one
+    assert float(np.abs(top_p[~np.isnan(top_p)] - thr_used).min()) > 1e-5
+    assert bool(np.isnan(top_p).any()) == (mode == "special")
+    dev = [torch.from_numpy(t).cuda() for t in (logits, loc, anchors)]
+    rows, count = ops.retina_decode(*dev) if thr is None else ops.retina_decode(*dev, thr)
     rows, count = rows.cpu().numpy(), count.cpu().numpy()
-    print("\ndecode A=%d %s: kept %s" % (a, mode, count.tolist()))
+    print("\ndecode A=%d %s C=%d threshold %g: kept %s" % (a, mode, c, thr_used, count.tolist()))
     ties = 0
     for i in range(logits.shape[0]):
-        r64, keep64 = rc.decode(logits[i], loc[i], anchors, torch.float64)
-        r32, _ = rc.decode(logits[i], loc[i], anchors, torch.float32)
+        r64, keep64 = rc.decode(logits[i], loc[i], anchors, torch.float64, **args)
+        r32, _ = rc.decode(logits[i], loc[i], anchors, torch.float32, **args)
         k = keep64.numel()
+        if mode == "special":
+            kept = keep64.tolist()
+            for kind, at in SPECIAL_ROWS.items():
+                assert (at[i] in kept) == (kind == "inf"), (kind, at[i])
+                assert min(abs(r - at[i]) for r in kept if r != at[i]) == 1      # a kept neighbour: the packing is at stake
         assert int(count[i]) == k
-        if mode == "none":
+        if mode == "none" or (mode == "batch3" and i == 1):
             assert k == 0
-        if mode == "all":
+        if mode == "all" or (mode == "batch3" and i == 2):
             assert k == a
+        if mode == "batch3" and i == 0:
+            assert 0 < k < a
         got = rows[i, :k]
         assert np.array_equal(got[:, 5], r64[:, 5].numpy())                     # class + 1, first maximum
         top = logits[i].max(axis=1, keepdims=True)
@@ -292,8 +383,11 @@ def test_retina_decode_vs_fp64(a, mode):
             # the kept anchors, in anchor order: every row's probability is the one of its anchor
             _judge("prob", got[:, 4], r64[:, 4].numpy(), r32[:, 4].numpy())
             _judge("boxes", got[:, :4], r64[:, :4].numpy(), r32[:, :4].numpy())
+        if mode == "special":
+            at = keep64.tolist().index(SPECIAL_ROWS["inf"][i])
+            assert got[at, 4] == 1.0 and got[at, 5] == 3.0
         assert not rows[i, k:].any()                                            # nothing behind the count
-    if mode == "mixed" and a >= 63:
+    if mode == "mixed" and a >= 63 and c > 2:
         assert ties > 0
 
 
@@ -305,6 +399,12 @@ CONV_SHAPES = {                      # n, c, h, w, k, r, s, stride, pad, bias
     "lateral_1x1_2048_256": (2, 2048, 3, 4, 256, 1, 1, 1, 0, True),
     "loc_3x3_256_36": (2, 256, 8, 10, 36, 3, 3, 1, 1, True),
     "cls_3x3_256_90": (2, 256, 8, 10, 90, 3, 3, 1, 1, True),
+    # the ResNet bottlenecks: stride-2 projections (on an odd map; at 2048 outputs), the stride-2 3x3, the 1x1 pair at 2048
+    "proj_1x1s2_256_512": (2, 256, 7, 9, 512, 1, 1, 2, 0, False),
+    "proj_1x1s2_1024_2048": (2, 1024, 6, 8, 2048, 1, 1, 2, 0, False),
+    "c2_3x3s2_512_512": (2, 512, 6, 8, 512, 3, 3, 2, 1, False),
+    "c3_1x1_512_2048": (2, 512, 3, 4, 2048, 1, 1, 1, 0, False),
+    "c1_1x1_2048_512": (2, 2048, 3, 4, 512, 1, 1, 1, 0, False),
 }
 
 

@@ -94,6 +94,126 @@ def test_retinanet_gradient_parity_vs_fp64():
     assert not bad, bad
 
 
+IDENTITY_SIZE = (64, 96)             # stage maps 16x24, 8x12, 4x6, 2x3
+
+
+def _identity_plain_run(state, imgs, ups, dtype, train):
+    """rc._Backbone((2, 1, 1, 2)) in `dtype` -> ([four stage outputs], {name: grad}); the backward (train mode only) is
+    driven by the fixed upstream gradient of every output."""
+    net = rc._Backbone(rc.IDENTITY_DEPTHS).to(dtype).train(train)
+    net.load_state_dict({k: v.to(dtype) if v.is_floating_point() else v for k, v in state.items()}, strict=True)
+    with torch.set_grad_enabled(train):
+        outs = net.stages(imgs.to(dtype))
+        if train:
+            sum((o * u.to(dtype)).sum() for o, u in zip(outs, ups)).backward()
+    grads = {k: p.grad.detach().double().numpy() for k, p in net.named_parameters()} if train else {}
+    return [o.detach().double().numpy() for o in outs], grads
+
+
+@functools.lru_cache(maxsize=1)
+def _identity_case():
+    """The model, its state (BatchNorm weights, biases and running statistics away from 1 / 0), the batch, one upstream
+    gradient per stage output, and the float64 / float32 restatements in train and eval mode."""
+    from rrnet_amd.backbones.resnet import Bottleneck, ResNet
+    torch.manual_seed(220)
+    model = ResNet(Bottleneck, list(rc.IDENTITY_DEPTHS))
+    g = torch.Generator().manual_seed(221)
+    with torch.no_grad():
+        for m in model.modules():
+            if isinstance(m, torch.nn.BatchNorm2d):
+                m.weight.copy_(0.5 + torch.rand(m.weight.shape, generator=g))
+                m.bias.copy_(0.2 * torch.randn(m.bias.shape, generator=g))
+                m.running_mean.copy_(0.2 * torch.randn(m.bias.shape, generator=g))
+                m.running_var.copy_(0.5 + torch.rand(m.bias.shape, generator=g))
+    state = {k: v.detach().clone() for k, v in model.state_dict().items()}
+    imgs = torch.randn((2, 3) + IDENTITY_SIZE, generator=g)
+    with torch.no_grad():
+        shapes = [tuple(o.shape) for o in rc._Backbone(rc.IDENTITY_DEPTHS).stages(imgs)]
+    ups = [torch.randn(s, generator=g) for s in shapes]
+    runs = {(train, dt): _identity_plain_run(state, imgs, ups, dt, train)
+            for train in (True, False) for dt in (torch.float64, torch.float32)}
+    return model, state, imgs, ups, shapes, runs
+
+
+def _identity_model():
+    model, state = _identity_case()[:2]
+    assert [len(getattr(model, "layer%d" % i)) for i in (1, 2, 3, 4)] == list(rc.IDENTITY_DEPTHS)
+    for stage, channels in ((model.layer1, 256), (model.layer4, 2048)):       # the identity residual comes from RF.fanout
+        assert stage[1].downsample is None and stage[1].conv3.out_channels == channels
+    model.load_state_dict(state, strict=True)                                 # a train-mode run moves the running statistics
+    return model.cuda().to(memory_format=torch.channels_last)
+
+
+def test_resnet_identity_blocks_train_vs_fp64():
+    """ResNet(Bottleneck, [2, 1, 1, 2]) in train mode, B = 2 at 64x96, against rc._Backbone in float64 with the same state:
+    the four stage outputs and, after a backward driven by one fixed random upstream gradient per output, every parameter
+    gradient.  The second blocks of stages 1 and 4 have no projection: their residual is the fan-out view itself, at 256
+    channels on the 16x24 map and at 2048 channels on the 2x3 map (past the 1024-channel limits of the BatchNorm launches).
+    The rule of test_retinanet_gradient_parity_vs_fp64: relative L2 per tensor, at most 4 x max(the float32 restatement's
+    error for that tensor, the median of its errors), the median taken over the four outputs for an output and over all
+    parameter gradients for a gradient.  The float32 restatement's gradient errors are near 1 % throughout: they are not
+    rounding but single ReLU decisions that fall the other way (1 of the 24 576 elements of l4 and 1 of 98 304 of l2 at the
+    outputs alone), each of which moves every gradient below it; the outputs, which a flipped decision barely moves, are
+    held to 1e-5.
+    Measured (float32 restatement on the CPU / kernels on an MI355X, both against float64): outputs l1..l4 1.06e-6 /
+    1.11e-6, 1.75e-6 / 1.85e-6, 2.68e-6 / 2.83e-6, 6.33e-6 / 6.86e-6; gradients median 1.27e-2, max 1.99e-2
+    (layer4.1.bn2.weight) / the kernels' the same to two digits on every tensor, largest error over its bound 0.25; the
+    kernels against the float32 restatement (printed, not asserted): median 1.7e-3, max 6.9e-3, so they share its large
+    flips and make a few small ones of their own."""
+    _model, _state, imgs, ups, shapes, runs = _identity_case()
+    r64, r32 = runs[(True, torch.float64)], runs[(True, torch.float32)]
+    model = _identity_model().train()
+    outs = model(imgs.cuda().contiguous(memory_format=torch.channels_last))
+    assert [tuple(o.shape) for o in outs] == shapes
+    sum((o * u.cuda().contiguous(memory_format=torch.channels_last)).sum() for o, u in zip(outs, ups)).backward()
+    torch.cuda.synchronize()
+    err32 = {k: rc.rel_l2(r32[1][k], r64[1][k]) for k in r64[1]}
+    floor = float(np.median(list(err32.values())))
+    out32 = [rc.rel_l2(a, b) for a, b in zip(r32[0], r64[0])]
+    out_floor = float(np.median(out32))
+    print("\nfloat32 restatement: gradient relative errors median %.3g max %.3g; outputs median %.3g"
+          % (floor, max(err32.values()), out_floor))
+    for i, o in enumerate(outs):
+        e = rc.rel_l2(o.detach().cpu().double().numpy(), r64[0][i])
+        print("  output l%d %s: kernel %.3g  fp32 %.3g" % (i + 1, shapes[i], e, out32[i]))
+        assert e <= 4 * max(out32[i], out_floor), (i, e, out32[i])
+    params = dict(model.named_parameters())
+    assert set(params) == set(r64[1])
+    bad, worst, to32 = [], 0.0, []
+    for k, p in params.items():
+        assert p.grad is not None, k
+        got = p.grad.detach().cpu().double().numpy()
+        e = rc.rel_l2(got, r64[1][k])
+        to32.append(rc.rel_l2(got, r32[1][k]))
+        worst = max(worst, e / (4 * max(err32[k], floor)))
+        if e > 4 * max(err32[k], floor):
+            bad.append((k, e, err32[k]))
+        print("  grad %-36s kernel %.3g  fp32 %.3g  kernel against the float32 restatement %.3g" % (k, e, err32[k], to32[-1]))
+    print("  worst kernel error / bound: %.3f; kernel against the float32 restatement (reported): median %.3g max %.3g"
+          % (worst, float(np.median(to32)), max(to32)))
+    assert not bad, bad
+
+
+def test_resnet_identity_blocks_eval_vs_fp64():
+    """The same model in eval mode (running statistics drawn away from 0 / 1): the four stage outputs, relative L2 at most
+    4 x max(the float32 restatement's error for that output, the median of its four errors).
+    Measured (float32 restatement on the CPU / kernels on an MI355X, both against float64): 3.3e-7 / 4.3e-7, 3.9e-7 / 5.5e-7,
+    4.8e-7 / 7.5e-7, 5.7e-7 / 1.14e-6 (bound 2.3e-6)."""
+    _model, _state, imgs, _ups, shapes, runs = _identity_case()
+    r64, r32 = runs[(False, torch.float64)], runs[(False, torch.float32)]
+    model = _identity_model().eval()
+    with torch.no_grad():
+        outs = model(imgs.cuda().contiguous(memory_format=torch.channels_last))
+    torch.cuda.synchronize()
+    err32 = [rc.rel_l2(a, b) for a, b in zip(r32[0], r64[0])]
+    floor = float(np.median(err32))
+    print()
+    for i, o in enumerate(outs):
+        e = rc.rel_l2(o.cpu().double().numpy(), r64[0][i])
+        print("  eval output l%d %s: kernel %.3g  fp32 %.3g (median %.3g)" % (i + 1, shapes[i], e, err32[i], floor))
+        assert tuple(o.shape) == shapes[i] and e <= 4 * max(err32[i], floor), (i, e, err32[i])
+
+
 def _operator():
     from rrnet_amd.operators.retinanet_operator import RetinaNetOperator
     cfg = rc.retina_cfg("resnet10", crop=SIZE)
