@@ -74,8 +74,7 @@ def _wgrad_async(fn, device, *tensors):
     side = _side_stream(device, "wgrad")
     side.wait_stream(cur)
     for t in tensors:                     # maxima reduced / bf16 images written on the current stream so far are complete for the side stream too
-        ops.amax_publish(t)
-        ops.b16_publish(t)
+        ops.side_publish(t)
     with torch.cuda.stream(side):
         _stress_delay()
         fn()
@@ -182,10 +181,9 @@ class _ConvBnAct(torch.autograd.Function):
             remask = relu and residual is None
             ctx.save_for_backward(x, wc, y, z if (relu and not remask) else None, mean, invstd, gamma, cnt_dev,
                                   scale if remask else None, shift if remask else None)
-            ctx.x_amax = ops.amax_carry(x)      # (split-operand kernels: the weight gradient reuses the forward's reduction)
-            ctx.x_b16 = ops.b16_carry(x)        # (conv16 kernels: the weight gradient reads the forward's bf16 image of x)
-            ctx.z_b16 = ops.b16_carry(z) if (relu and not remask) else None      # (a bf16-only z: its image is the mask's source)
-            ctx.y_b16 = ops.b16_carry(y) if ops.is_phantom(y) else None
+            # x: its maximum (split-operand kernels: the weight gradient reuses the forward's reduction) and its bf16 image (conv16
+            # kernels: the weight gradient reads it); a saved z: its image (bf16-only: the mask's source); a bf16-only y: its image
+            ctx.side = ops.side_carry(x, z if (relu and not remask) else None, y if ops.is_phantom(y) else None)
             if out_link is not None:
                 # what a consumer's data gradient needs to produce this layer's BatchNorm-backward sums in its epilogue
                 out_link.y, out_link.mean, out_link.invstd = y, mean, invstd
@@ -204,10 +202,7 @@ class _ConvBnAct(torch.autograd.Function):
     @staticmethod
     def _backward(ctx, dz):
         x, wc, y, z, mean, invstd, gamma, cnt_dev, msc, msh = ctx.saved_tensors
-        ops.amax_restore(x, getattr(ctx, "x_amax", None))
-        ops.b16_restore(x, getattr(ctx, "x_b16", None))
-        ops.b16_restore(z, getattr(ctx, "z_b16", None))
-        ops.b16_restore(y, getattr(ctx, "y_b16", None))
+        ops.side_restore(getattr(ctx, "side", None), x, z, y)
         stride, pad, relu, count, sync, has_res = ctx.cfg
         w, gamma_p, beta_p = ctx.params
         dz = ops.to_nhwc(dz)
@@ -317,7 +312,7 @@ def _wamax_attach(w_param, wc):
     if hit is None or hit[0] != key:
         hit = (key, ops.amax_of(wc))
         w_param._rr_wamax = hit
-    ops.amax_restore(wc, hit[1])
+    ops.amax_side.restore(wc, hit[1])
 
 
 def _input_grad(dy, wc, xshape, stride, pad, x_acc, in_link, x, w_param=None):
@@ -546,8 +541,7 @@ class _ConvBias(torch.autograd.Function):
         _wamax_attach(w, wc)
         y = ops.conv_fprop(x, wc, b, stride, pad, relu, w16=_w16_of(w)[0])
         ctx.save_for_backward(x, wc, y if relu else None)
-        ctx.x_amax = ops.amax_carry(x)
-        ctx.x_b16 = ops.b16_carry(x)
+        ctx.side = ops.side_carry(x)
         ctx.cfg = (stride, pad, relu)
         ctx.params = (w, b)
         ctx.xshape = tuple(x.shape)
@@ -561,8 +555,7 @@ class _ConvBias(torch.autograd.Function):
     @staticmethod
     def _backward(ctx, dy):
         x, wc, y = ctx.saved_tensors
-        ops.amax_restore(x, getattr(ctx, "x_amax", None))
-        ops.b16_restore(x, getattr(ctx, "x_b16", None))
+        ops.side_restore(getattr(ctx, "side", None), x)
         stride, pad, relu = ctx.cfg
         w, b = ctx.params
         dy = ops.to_nhwc(dy)
@@ -684,21 +677,14 @@ def _share_b16(x, views):
     """conv16 kernels: the fan-out views ARE x — its bf16 image (written by x's producer, or converted once here so that the
     n consumers do not convert n times) travels with them."""
     if ops.is_phantom(x):                  # a bf16-only tensor: its views must keep the image, whatever the mode
-        img = ops.image_of(x)
-        for o in views:
-            o._rr_b16 = (o._version, x._rr_b16[1], img)
+        ops.image_of(x)
+    elif ops.BF16 != ops.MATH_BF16 or not x.is_cuda or x.dim() != 4 or x.dtype != torch.float32:
         return
-    if ops.BF16 != ops.MATH_BF16 or not x.is_cuda or x.dim() != 4 or x.dtype != torch.float32:
-        return
-    hit = getattr(x, "_rr_b16", None)
-    if hit is None or hit[0] != x._version:
-        if not (ops._CONV16 and x.shape[1] % 128 == 0
-                and x.shape[0] * x.shape[2] * x.shape[3] >= ops._CONV16_MIN_PIXELS and ops.is_nhwc(x)):
+    elif ops.b16_carry(x) is None:
+        if not (ops.image_wanted(x.shape[1], x.shape[0] * x.shape[2] * x.shape[3], x.device) and ops.is_nhwc(x)):
             return
         ops.bf16_of(x)
-        hit = x._rr_b16
-    for o in views:
-        o._rr_b16 = (o._version, hit[1], hit[2])
+    ops.b16_side.share(x, views)
 
 
 def fanout(x, n):
@@ -734,11 +720,9 @@ def fanout_shared(x, n):
     if acc is None:
         acc = GradAcc()
         acc.link = getattr(x, "_rr_bnlink", None)
-    amax = getattr(x, "_rr_amax", None)     # (split-operand kernels: the views ARE x — its remembered maximum travels with them)
     for o in outs:
         o._rr_acc = acc
-        if amax is not None and amax[0] == x._version:
-            o._rr_amax = (o._version, amax[1], amax[2])
+    ops.amax_side.share(x, outs)            # (split-operand kernels: the views ARE x — its remembered maximum travels with them)
     _share_b16(x, outs)
     return outs + (acc,)
 

@@ -124,11 +124,11 @@ def is_phantom(t):
 
 
 def image_of(t):
-    hit = getattr(t, "_rr_b16", None)
-    if hit is None:
+    img = b16_side.carry(t)
+    if img is None:
         raise RuntimeError("a bf16-only tensor of shape %s reached a consumer without its bf16 image (a view / saved tensor whose "
-                           "producer did not hand the image on: ops.b16_carry / b16_restore)" % (tuple(t.shape),))
-    return hit[2]
+                           "producer did not hand the image on: ops.side_carry / side_restore)" % (tuple(t.shape),))
+    return img
 
 
 def f32_of(t):
@@ -264,48 +264,112 @@ _SPLIT_MIN_CH = 64                                                         # nar
 _SPLIT_MIN_K = 1024               # C*R*S (reduction length) likewise
 
 
-def amax_carry(t):
-    """The remembered maximum of t (or None), to be kept by an autograd node next to the tensor it saves: saved tensors
-    come back as new Python objects.  amax_restore() hands it to the unpacked tensor in backward."""
-    hit = getattr(t, "_rr_amax", None)
-    return hit[2] if (hit is not None and hit[0] == t._version) else None
-
-
-def amax_restore(t, word):
-    """Backward: the maximum computed in forward (complete long before: valid on every stream)."""
-    if word is not None and t is not None:
-        t._rr_amax = (t._version, None, word)
-
-
-def amax_publish(t):
-    """The caller has just ordered another stream behind the current one (wait_stream): a maximum remembered on t from the
-    current stream may be read there."""
-    hit = getattr(t, "_rr_amax", None) if t is not None else None
-    if hit is not None and hit[1] == torch.cuda.current_stream(t.device).cuda_stream:
-        t._rr_amax = (hit[0], None, hit[2])
-
-
 _AMAX_CHECK = os.environ.get("RR_AMAX_CHECK", "0") == "1"     # recompute every remembered maximum when it is used; raise on mismatch
+_CONV16 = os.environ.get("RR_CONV16", "1") != "0"               # 0: the round-4 kernels (fp32 tensors, converted inside every launch)
+_CONV16_MIN_PIXELS = 8192     # output pixels below which the 256-pixel tiles lose to the round-4 kernels (8 x 32 x 32 x 384: 351 vs 229 TFLOP/s; 16 x 16: 24 workgroups)
+
+
+# ---- sidecars: derived values that ride on tensor OBJECTS ------------------------------------------------------------------
+# Two kinds.  The maximum: the device word holding the bit pattern of max|t| that the f16x3 kernels scale their operands by
+# (amax_of).  The image: the bf16 copy of an fp32 tensor that csrc/conv16.hip reads both operands of a convolution as — under
+# cfg.Model.bf16 the producers of a convolution's operands (bn_apply, bn_bwd_apply) write it next to the fp32 tensor in the
+# same pass, an operand without one (a fan-in sum, the up-sample add, a head's masked gradient) is converted on first use
+# (bf16_of); for a bf16-only activation (phantom_f32) it is the only data there is.
+# One rule for both, and this section is the only code that knows how it is stored (a Python attribute holding
+# `(version | None, stream id | None, payload)`): the payload is valid for this version of the tensor (None: whatever the
+# version — a phantom handle, below), on the stream that made it (None: on every stream — published, restored, or not on the
+# GPU), and a kernel that writes the tensor through its raw pointer drops it.
+class _Sidecar:
+    def __init__(self, attr):
+        self.attr = attr
+
+    def _hit(self, t):
+        """The stored triple if it is valid for t's version, else None."""
+        hit = getattr(t, self.attr, None) if t is not None else None
+        return hit if (hit is not None and (hit[0] is None or hit[0] == t._version)) else None
+
+    def attach(self, t, payload, versioned=True):
+        """payload was made on the current stream.  versioned=False: a phantom handle — every such handle is a view of one stub
+        and shares its version counter, while its image is its value, written once and never updated in place: a version
+        test there protects nothing and could only lose data."""
+        setattr(t, self.attr, (t._version if versioned else None, torch.cuda.current_stream(t.device).cuda_stream if t.is_cuda else None, payload))
+
+    def now(self, t):
+        """For use by a kernel launched now: valid for this version and on the current stream (or None)."""
+        hit = self._hit(t)
+        if hit is None or (hit[1] is not None and hit[1] != torch.cuda.current_stream(t.device).cuda_stream):
+            return None
+        return hit[2]
+
+    def carry(self, t):
+        """Valid for this version, on whatever stream (or None) — for an autograd node to keep next to a tensor it saves: saved
+        tensors come back as new Python objects, restore() hands the payload to the unpacked one."""
+        hit = self._hit(t)
+        return hit[2] if hit is not None else None
+
+    def restore(self, t, payload, versioned=True):
+        """Backward: a payload made in the forward (complete long before: valid on every stream) onto the fresh object."""
+        if payload is not None and t is not None:
+            setattr(t, self.attr, (t._version if versioned else None, None, payload))
+
+    def publish(self, t):
+        """The caller has just ordered another stream behind the current one (wait_stream): a payload made on the current stream
+        may be read there."""
+        hit = getattr(t, self.attr, None) if t is not None else None
+        if hit is not None and hit[1] is not None and hit[1] == torch.cuda.current_stream(t.device).cuda_stream:
+            setattr(t, self.attr, (hit[0], None, hit[2]))
+
+    def share(self, t, views):
+        """views ARE t (view_as): what rides on t, as valid as it is there, travels with them."""
+        hit = self._hit(t)
+        if hit is not None:
+            for o in views:
+                setattr(o, self.attr, (None if hit[0] is None else o._version, hit[1], hit[2]))
+
+    def drop(self, t):
+        if t is not None and getattr(t, self.attr, None) is not None:
+            setattr(t, self.attr, None)
+
+
+amax_side, b16_side = _Sidecar("_rr_amax"), _Sidecar("_rr_b16")
+amax_carry, b16_carry = amax_side.carry, b16_side.carry
 
 
 def amax_drop(t):
     """`t` is about to be (or has just been) written through its raw pointer by a kernel — an accumulate-form data gradient,
     bn_bwd_apply's g_into, any `out=` argument: such writes never move `t._version`, so a maximum remembered on the tensor
     object would look valid and be stale (too low: the fp16 parts overflow; too high: bits are dropped silently)."""
-    if t is not None and getattr(t, "_rr_amax", None) is not None:
-        t._rr_amax = None
-    if t is not None and getattr(t, "_rr_b16", None) is not None:
-        t._rr_b16 = None                       # (the bf16 image is as stale as the maximum)
+    amax_side.drop(t)
+    b16_side.drop(t)                           # (the bf16 image is as stale as the maximum)
 
 
-# ---- bf16 images of fp32 tensors (csrc/conv16.hip reads both operands of a convolution as bf16 tensors) -----------------
-# Under cfg.Model.bf16 the producers of a convolution's operands (bn_apply, bn_bwd_apply) write a bf16 image next to the fp32
-# tensor in the same pass; it rides on the tensor OBJECT as `_rr_b16 = (version, stream id | None, image)`.  An operand
-# without one (a fan-in sum, the up-sample add, a head's masked gradient) is converted on first use (rr_to_bf16) and
-# remembered the same way.  Like the remembered maxima it must be dropped when a kernel rewrites the tensor through its
-# raw pointer (amax_drop does both), is valid on the stream that made it, and on every stream once published.
-_CONV16 = os.environ.get("RR_CONV16", "1") != "0"               # 0: the round-4 kernels (fp32 tensors, converted inside every launch)
-_CONV16_MIN_PIXELS = 8192     # output pixels below which the 256-pixel tiles lose to the round-4 kernels (8 x 32 x 32 x 384: 351 vs 229 TFLOP/s; 16 x 16: 24 workgroups)
+def side_carry(x, *image_only):
+    """What an autograd node keeps next to the tensors it saves: both kinds of x, the images of the rest (None entries allowed)."""
+    return (amax_side._hit(x),) + tuple(b16_side._hit(t) for t in (x,) + image_only)
+
+
+def side_restore(carried, x, *image_only):
+    """side_carry's result onto the unpacked tensors, in the same order (a phantom's image stays free of the version)."""
+    if carried is not None:
+        for side, t, hit in zip((amax_side, b16_side) + (b16_side,) * len(image_only), (x, x) + image_only, carried):
+            if hit is not None:
+                side.restore(t, hit[2], versioned=hit[0] is not None)
+
+
+def side_publish(t):
+    amax_side.publish(t)
+    b16_side.publish(t)
+
+
+def image_wanted(c, pixels, device, multiple=128):
+    """Does the producer of a c-channel tensor of this many pixels write its bf16 image in the same pass (its consumer is a conv16
+    kernel)?  Read at call time: the thread's arithmetic and the module switches."""
+    return bool(_CONV16 and _mode() == MATH_BF16 and device.type == "cuda" and c % multiple == 0 and pixels >= _CONV16_MIN_PIXELS)
+
+
+def amax_wanted(c, pixels, device):
+    """Does the producer publish max|t| out of the same pass (split-operand convolutions: the consumer's operand scale, see amax_of)?"""
+    return bool(_mode() == MATH_F16X3 and device.type == "cuda" and pixels >= _SPLIT_MIN_PIXELS)
 
 
 class _PhantomScope(threading.local):
@@ -334,8 +398,7 @@ class phantom_scope:
 
 def phantom_out_ok(c, pixels, device):
     # (no grad-mode test: inside an autograd Function's forward grad mode is always off)
-    return bool(_PHANTOM.on and _PHANTOM_ENABLED and _CONV16 and _mode() == MATH_BF16 and device.type == "cuda"
-                and c % 256 == 0 and pixels >= _CONV16_MIN_PIXELS)
+    return bool(_PHANTOM.on and _PHANTOM_ENABLED and image_wanted(c, pixels, device, 256))
 
 
 def phantom_y_ok(k, x, w, stride, pad):
@@ -348,42 +411,20 @@ def phantom_y_ok(k, x, w, stride, pad):
     return phantom_out_ok(k, n * p * q, x.device) and conv16_ok(c, k, r, s, stride, n * p * q, x)
 
 
-def b16_attach(t, image):
-    t._rr_b16 = (t._version, torch.cuda.current_stream(t.device).cuda_stream, image)
-
-
-def b16_carry(t):
-    """The bf16 image riding on t (or None) — for an autograd node to keep next to a tensor it saves (saved tensors come
-    back as new Python objects); b16_restore hands it to the unpacked tensor."""
-    hit = getattr(t, "_rr_b16", None)
-    return hit[2] if (hit is not None and hit[0] == t._version) else None
-
-
-def b16_restore(t, image):
-    if image is not None and t is not None:
-        t._rr_b16 = (t._version, None, image)          # made in the forward: complete on every stream by now
-
-
-def b16_publish(t):
-    hit = getattr(t, "_rr_b16", None) if t is not None else None
-    if hit is not None and hit[1] == torch.cuda.current_stream(t.device).cuda_stream:
-        t._rr_b16 = (hit[0], None, hit[2])
-
-
 def bf16_of(t):
-    """bf16 image of the fp32 NHWC tensor t (same logical shape, same memory order)."""
+    """bf16 image of the fp32 NHWC tensor t (same logical shape, same memory order), converted on the current stream and
+    remembered on the tensor object when none rides on it."""
     if is_phantom(t):
         return image_of(t)
-    sid = torch.cuda.current_stream(t.device).cuda_stream
-    hit = getattr(t, "_rr_b16", None)
-    if hit is not None and hit[0] == t._version and (hit[1] is None or hit[1] == sid):
-        return hit[2]
+    img = b16_side.now(t)
+    if img is not None:
+        return img
     assert t.dtype == torch.float32 and t.numel() % 4 == 0
     img = torch.empty_like(t, dtype=torch.bfloat16)
     assert img.stride() == t.stride()
     _C.check(_C.fn("rr_to_bf16")(_C.ptr(t), _C.ptr(img), t.numel(), _C.stream()), "rr_to_bf16")
     try:
-        t._rr_b16 = (t._version, sid, img)
+        b16_side.attach(t, img)
     except AttributeError:
         pass
     return img
@@ -404,7 +445,7 @@ def phantom_f32(shape, device, image):
     # (a 0-dim view of element 1 of 2: expanding the 1-element slice stub[1:] kept stride 1 on a last dimension of size 1, so a
     # handle of width 1 failed is_phantom's all-zero-strides test and its consumer read the stub as if it were the data)
     t = stub[1].expand(shape)
-    t._rr_b16 = (t._version, torch.cuda.current_stream(device).cuda_stream if device.type == "cuda" else None, image)
+    b16_side.attach(t, image, versioned=False)
     return t
 
 
@@ -441,21 +482,20 @@ def amax_of(t):
     current stream and remembered on the tensor object (same version, same stream): a gradient serves its data
     gradient and its weight gradient with one reduction.  RR_AMAX_CHECK=1 (tests): every remembered word is checked
     against a fresh reduction at the moment it is used."""
-    sid = torch.cuda.current_stream(t.device).cuda_stream
-    hit = getattr(t, "_rr_amax", None)
-    if hit is not None and hit[0] == t._version and (hit[1] == sid or hit[1] is None):
+    word = amax_side.now(t)
+    if word is not None:
         if _AMAX_CHECK:
             fresh = int(_absmax_word(t).view(torch.int32)[0].item())
-            kept = int(hit[2].view(torch.int32)[0].item())
+            kept = int(word.view(torch.int32)[0].item())
             if fresh != kept:
                 raise RuntimeError("ops.amax_of: stale remembered maximum on a tensor of shape %s: remembered bits 0x%08x, "
                                    "actual 0x%08x (a kernel wrote it through its raw pointer without ops.amax_drop)"
                                    % (tuple(t.shape), kept & 0xffffffff, fresh & 0xffffffff))
             AMAX_CHECKED[0] += 1
-        return hit[2]
+        return word
     word = _absmax_word(t)
     try:
-        t._rr_amax = (t._version, sid, word)
+        amax_side.attach(t, word)
     except AttributeError:
         pass
     return word
@@ -730,12 +770,12 @@ def _dgrad_relubias(dy, w, out, geo, flops, bf, link, z, wt, head):
     n, h, wd, c, k, r, s = geo[:7]
     link.sums, link.dz = _ZEROS.take(2 * c, dy.device), out
     if head:
-        want16 = _CONV16 and _mode() == MATH_BF16 and c % 256 == 0 and n * h * wd >= _CONV16_MIN_PIXELS
+        want16 = image_wanted(c, n * h * wd, dy.device, 256)
         out16 = torch.empty_like(out, dtype=torch.bfloat16) if want16 else None
         _C.check(_C.fn("rr_head_dgrad_relubias")(_C.ptr(dy), _C.ptr(w), _C.ptr(out), _C.ptr(out16), _C.ptr(z), _C.ptr(link.sums),
                                                  n * h * wd, c, k, geo[9], _C.stream()), "rr_head_dgrad_relubias")
         if want16:
-            b16_attach(out, out16)
+            b16_side.attach(out, out16)
         return
     kp = (k + 3) // 4 * 4
     if kp != k:
@@ -960,44 +1000,47 @@ def bn_eval_coeffs(gamma, beta, running_mean, running_var, eps):
     return scale, shift
 
 
+def _operand(t, phantom):
+    """-> (fp32 pointer, image pointer) of an operand the `_b16` entry points read in either form: one of the two is NULL."""
+    return (_C.ptr(None), _C.ptr(image_of(t))) if phantom else (_C.ptr(t), _C.ptr(None))
+
+
+def _produced(n, c, h, w, device, f32, image):
+    """-> (fp32 tensor | None, bf16 image | None) for a producer to write."""
+    return (empty_nhwc(n, c, h, w, device) if f32 else None, empty_nhwc(n, c, h, w, device, torch.bfloat16) if image else None)
+
+
+def _published(out, out16, word=None):
+    """What the producer returns: its fp32 tensor with the sidecars it wrote in the same pass — or, bf16-only, the phantom handle."""
+    if out is None:
+        return phantom_f32(tuple(out16.shape), out16.device, out16)
+    if out16 is not None:
+        b16_side.attach(out, out16)     # the bf16 image the consuming convolution (csrc/conv16.hip) reads
+    if word is not None:
+        amax_side.attach(out, word)     # split-operand convolutions: the consumer's operand scale (see amax_of)
+    return out
+
+
 def bn_apply(y, scale, shift, residual=None, relu=False, res_scale=None, res_shift=None, bf16_only=False):
     """bf16_only (conv16, ops.phantom_scope): the output is written as a bf16 image only and returned as a memory-less fp32
     handle (phantom_f32).  A bf16-only residual is read from its image."""
     res_ph, y_ph = is_phantom(residual), is_phantom(y)
     assert (is_nhwc(y) or y_ph) and (residual is None or ((is_nhwc(residual) or res_ph) and residual.shape == y.shape))
     n, c, h, w = y.shape
-    want16 = _CONV16 and _mode() == MATH_BF16 and y.is_cuda and c % 128 == 0 and n * h * w >= _CONV16_MIN_PIXELS
-    if (bf16_only or res_ph or y_ph) and y.is_cuda and c % 4 == 0:
-        out = None if bf16_only else empty_nhwc(n, c, h, w, y.device)
-        out16 = torch.empty((n, h, w, c), dtype=torch.bfloat16, device=y.device).permute(0, 3, 1, 2) if (bf16_only or want16) else None
-        _C.check(_C.fn("rr_bn_apply_b16")(_C.ptr(None if y_ph else y), _C.ptr(image_of(y) if y_ph else None), _C.ptr(scale), _C.ptr(shift),
-                                          _C.ptr(None if res_ph else residual), _C.ptr(image_of(residual) if res_ph else None),
+    mixed = bool((bf16_only or res_ph or y_ph) and y.is_cuda and c % 4 == 0)       # an operand or the output exists as an image only
+    only16 = mixed and bf16_only
+    out, out16 = _produced(n, c, h, w, y.device, not only16, only16 or image_wanted(c, n * h * w, y.device))
+    if mixed or out16 is not None:
+        _C.check(_C.fn("rr_bn_apply_b16")(*_operand(y, y_ph), _C.ptr(scale), _C.ptr(shift), *_operand(residual, res_ph),
                                           _C.ptr(res_scale), _C.ptr(res_shift), _C.ptr(out), _C.ptr(out16), y.numel(), c, int(relu),
                                           _C.stream()), "rr_bn_apply_b16")
-        if bf16_only:
-            return phantom_f32((n, c, h, w), y.device, out16)
-        if out16 is not None:
-            b16_attach(out, out16)
-        return out
-    out = empty_nhwc(n, c, h, w, y.device)
-    if _mode() == MATH_F16X3 and y.is_cuda and n * h * w >= _SPLIT_MIN_PIXELS:
-        # split-operand convolutions: the consumer's operand scale comes out of this pass (see amax_of)
+        return _published(out, out16)
+    head = (_C.ptr(y), _C.ptr(scale), _C.ptr(shift), _C.ptr(residual), _C.ptr(res_scale), _C.ptr(res_shift), _C.ptr(out), y.numel(), c, int(relu))
+    if amax_wanted(c, n * h * w, y.device):
         word = _ZEROS.take(1, y.device)
-        _C.check(_C.fn("rr_bn_apply_amax")(_C.ptr(y), _C.ptr(scale), _C.ptr(shift), _C.ptr(residual), _C.ptr(res_scale),
-                                           _C.ptr(res_shift), _C.ptr(out), y.numel(), c, int(relu), _C.ptr(word), _C.stream()),
-                 "rr_bn_apply_amax")
-        out._rr_amax = (out._version, torch.cuda.current_stream(y.device).cuda_stream, word)
-        return out
-    if want16:
-        # the bf16 image the consuming convolution (csrc/conv16.hip) reads, written in the same pass
-        out16 = torch.empty_like(out, dtype=torch.bfloat16)
-        _C.check(_C.fn("rr_bn_apply_b16")(_C.ptr(y), None, _C.ptr(scale), _C.ptr(shift), _C.ptr(residual), None, _C.ptr(res_scale),
-                                          _C.ptr(res_shift), _C.ptr(out), _C.ptr(out16), y.numel(), c, int(relu), _C.stream()),
-                 "rr_bn_apply_b16")
-        b16_attach(out, out16)
-        return out
-    _C.check(_C.fn("rr_bn_apply")(_C.ptr(y), _C.ptr(scale), _C.ptr(shift), _C.ptr(residual), _C.ptr(res_scale),
-                                  _C.ptr(res_shift), _C.ptr(out), y.numel(), c, int(relu), _C.stream()), "rr_bn_apply")
+        _C.check(_C.fn("rr_bn_apply_amax")(*head, _C.ptr(word), _C.stream()), "rr_bn_apply_amax")
+        return _published(out, None, word)
+    _C.check(_C.fn("rr_bn_apply")(*head, _C.stream()), "rr_bn_apply")
     return out
 
 
@@ -1006,10 +1049,9 @@ def bn_bwd_reduce(dz, z, y, mean, invstd, extra=0, mask_scale=None, mask_shift=N
     sums = _ZEROS.take(2 * c + extra, y.device)            # pre-zeroed pool slice: no memset launch per layer
     z_ph, y_ph = is_phantom(z), is_phantom(y)
     if z_ph or y_ph:                                        # the layer's output / pre-BN output exist only as bf16 images
-        _C.check(_C.fn("rr_bn_bwd_reduce_b16")(_C.ptr(dz), _C.ptr(None if z_ph else z), _C.ptr(image_of(z) if z_ph else None),
-                                               _C.ptr(None if y_ph else y), _C.ptr(image_of(y) if y_ph else None), _C.ptr(mean),
-                                               _C.ptr(invstd), _C.ptr(mask_scale), _C.ptr(mask_shift), _C.ptr(sums), n * h * w, c,
-                                               _C.stream()), "rr_bn_bwd_reduce_b16")
+        _C.check(_C.fn("rr_bn_bwd_reduce_b16")(_C.ptr(dz), *_operand(z, z_ph), *_operand(y, y_ph), _C.ptr(mean), _C.ptr(invstd),
+                                               _C.ptr(mask_scale), _C.ptr(mask_shift), _C.ptr(sums), n * h * w, c, _C.stream()),
+                 "rr_bn_bwd_reduce_b16")
         return sums
     _C.check(_C.fn("rr_bn_bwd_reduce")(_C.ptr(dz), _C.ptr(z), _C.ptr(y), _C.ptr(mean), _C.ptr(invstd),
                                        _C.ptr(mask_scale), _C.ptr(mask_shift), _C.ptr(sums),
@@ -1025,55 +1067,28 @@ def bn_bwd_apply(dz, z, y, mean, invstd, gamma, sums, count, want_g=False, dgamm
     n, c, h, w = y.shape
     z_ph, y_ph = is_phantom(z), is_phantom(y)
     only16 = bool(bf16_only and _CONV16 and _mode() == MATH_BF16 and y.is_cuda and c % 4 == 0)
-    if only16 or z_ph or y_ph:
-        if g_into is not None:
-            assert is_nhwc(g_into) and g_into.shape == y.shape
-            amax_drop(g_into)
-            g = g_into
-        else:
-            g = empty_nhwc(n, c, h, w, y.device) if want_g else None
-        want16 = only16 or (_CONV16 and _mode() == MATH_BF16 and c % 128 == 0 and n * h * w >= _CONV16_MIN_PIXELS)
-        dx = None if only16 else empty_nhwc(n, c, h, w, y.device)
-        dx16 = torch.empty((n, h, w, c), dtype=torch.bfloat16, device=y.device).permute(0, 3, 1, 2) if want16 else None
-        _C.check(_C.fn("rr_bn_bwd_apply_b16")(_C.ptr(dz), _C.ptr(None if z_ph else z), _C.ptr(image_of(z) if z_ph else None),
-                                              _C.ptr(None if y_ph else y), _C.ptr(image_of(y) if y_ph else None),
-                                              _C.ptr(mean), _C.ptr(invstd), _C.ptr(gamma), _C.ptr(mask_scale), _C.ptr(mask_shift),
-                                              _C.ptr(sums), float(count), _C.ptr(count_dev), _C.ptr(dx), _C.ptr(dx16), _C.ptr(g),
-                                              int(g_into is not None), _C.ptr(dgamma), _C.ptr(dbeta), y.numel(), c, _C.stream()),
-                 "rr_bn_bwd_apply_b16")
-        if only16:
-            return phantom_f32((n, c, h, w), y.device, dx16), g
-        if dx16 is not None:
-            b16_attach(dx, dx16)
-        return dx, g
-    dx = empty_nhwc(n, c, h, w, y.device)
     if g_into is not None:
         assert is_nhwc(g_into) and g_into.shape == y.shape
         amax_drop(g_into)             # added into through its pointer
         g = g_into
     else:
         g = empty_nhwc(n, c, h, w, y.device) if want_g else None
-    if _mode() == MATH_F16X3 and y.is_cuda and n * h * w >= _SPLIT_MIN_PIXELS:
+    dx, dx16 = _produced(n, c, h, w, y.device, not only16, only16 or image_wanted(c, n * h * w, y.device))
+    mid = (_C.ptr(mean), _C.ptr(invstd), _C.ptr(gamma), _C.ptr(mask_scale), _C.ptr(mask_shift), _C.ptr(sums), float(count), _C.ptr(count_dev))
+    if z_ph or y_ph or dx16 is not None:
+        _C.check(_C.fn("rr_bn_bwd_apply_b16")(_C.ptr(dz), *_operand(z, z_ph), *_operand(y, y_ph), *mid, _C.ptr(dx), _C.ptr(dx16), _C.ptr(g),
+                                              int(g_into is not None), _C.ptr(dgamma), _C.ptr(dbeta), y.numel(), c, _C.stream()),
+                 "rr_bn_bwd_apply_b16")
+        return _published(dx, dx16), g
+    if amax_wanted(c, n * h * w, y.device):
         # split-operand convolutions: dx is the operand of the data / weight gradient launched next — its maximum comes out
         # of this pass.  (dx is a fresh tensor that nothing adds into later: the remembered maximum cannot go stale.)
         word = _ZEROS.take(1, y.device)
-        _C.check(_C.fn("rr_bn_bwd_apply_amax")(_C.ptr(dz), _C.ptr(z), _C.ptr(y), _C.ptr(mean), _C.ptr(invstd), _C.ptr(gamma),
-                                               _C.ptr(mask_scale), _C.ptr(mask_shift), _C.ptr(sums), float(count), _C.ptr(count_dev),
-                                               _C.ptr(dx), _C.ptr(g), int(g_into is not None), _C.ptr(dgamma), _C.ptr(dbeta),
-                                               y.numel(), c, _C.ptr(word), _C.stream()), "rr_bn_bwd_apply_amax")
-        dx._rr_amax = (dx._version, torch.cuda.current_stream(y.device).cuda_stream, word)
-        return dx, g
-    if _CONV16 and _mode() == MATH_BF16 and y.is_cuda and c % 128 == 0 and n * h * w >= _CONV16_MIN_PIXELS:
-        dx16 = torch.empty_like(dx, dtype=torch.bfloat16)
-        _C.check(_C.fn("rr_bn_bwd_apply_b16")(_C.ptr(dz), _C.ptr(z), None, _C.ptr(y), None, _C.ptr(mean), _C.ptr(invstd), _C.ptr(gamma),
-                                              _C.ptr(mask_scale), _C.ptr(mask_shift), _C.ptr(sums), float(count), _C.ptr(count_dev),
-                                              _C.ptr(dx), _C.ptr(dx16), _C.ptr(g), int(g_into is not None), _C.ptr(dgamma), _C.ptr(dbeta),
-                                              y.numel(), c, _C.stream()), "rr_bn_bwd_apply_b16")
-        b16_attach(dx, dx16)
-        return dx, g
-    _C.check(_C.fn("rr_bn_bwd_apply_gacc" if g_into is not None else "rr_bn_bwd_apply")(_C.ptr(dz), _C.ptr(z), _C.ptr(y), _C.ptr(mean), _C.ptr(invstd), _C.ptr(gamma),
-                                      _C.ptr(mask_scale), _C.ptr(mask_shift), _C.ptr(sums), float(count), _C.ptr(count_dev), _C.ptr(dx), _C.ptr(g), _C.ptr(dgamma), _C.ptr(dbeta),
-                                      y.numel(), c, _C.stream()), "rr_bn_bwd_apply")
+        _C.check(_C.fn("rr_bn_bwd_apply_amax")(_C.ptr(dz), _C.ptr(z), _C.ptr(y), *mid, _C.ptr(dx), _C.ptr(g), int(g_into is not None),
+                                               _C.ptr(dgamma), _C.ptr(dbeta), y.numel(), c, _C.ptr(word), _C.stream()), "rr_bn_bwd_apply_amax")
+        return _published(dx, None, word), g
+    _C.check(_C.fn("rr_bn_bwd_apply_gacc" if g_into is not None else "rr_bn_bwd_apply")(
+        _C.ptr(dz), _C.ptr(z), _C.ptr(y), *mid, _C.ptr(dx), _C.ptr(g), _C.ptr(dgamma), _C.ptr(dbeta), y.numel(), c, _C.stream()), "rr_bn_bwd_apply")
     return dx, g
 
 
@@ -1115,17 +1130,10 @@ def upsample_add_fwd(up1, low, bf16_only=False):
     fast = (2 * low.shape[2] == h and 2 * low.shape[3] == w and c % 4 == 0 and up1.is_cuda)
     if fast and (bf16_only or is_phantom(up1) or is_phantom(low)):
         u_ph, l_ph = is_phantom(up1), is_phantom(low)
-        want16 = bf16_only or (_CONV16 and _mode() == MATH_BF16 and c % 128 == 0 and n * h * w >= _CONV16_MIN_PIXELS)
-        out = None if bf16_only else empty_nhwc(n, c, h, w, up1.device)
-        out16 = torch.empty((n, h, w, c), dtype=torch.bfloat16, device=up1.device).permute(0, 3, 1, 2) if want16 else None
-        _C.check(_C.fn("rr_upsample2x_add_b16")(_C.ptr(None if u_ph else up1), _C.ptr(image_of(up1) if u_ph else None),
-                                                _C.ptr(None if l_ph else low), _C.ptr(image_of(low) if l_ph else None),
-                                                _C.ptr(out), _C.ptr(out16), n, h, w, c, _C.stream()), "rr_upsample2x_add_b16")
-        if bf16_only:
-            return phantom_f32((n, c, h, w), up1.device, out16)
-        if out16 is not None:
-            b16_attach(out, out16)
-        return out
+        out, out16 = _produced(n, c, h, w, up1.device, not bf16_only, bf16_only or image_wanted(c, n * h * w, up1.device))
+        _C.check(_C.fn("rr_upsample2x_add_b16")(*_operand(up1, u_ph), *_operand(low, l_ph), _C.ptr(out), _C.ptr(out16), n, h, w, c,
+                                                _C.stream()), "rr_upsample2x_add_b16")
+        return _published(out, out16)
     up1, low = f32_of(up1), f32_of(low)
     out = empty_nhwc(n, c, h, w, up1.device)
     _C.check(_C.fn("rr_upsample_add_fwd")(_C.ptr(up1), _C.ptr(low), _C.ptr(out), n, h, w, low.shape[2], low.shape[3],
@@ -1782,9 +1790,7 @@ def dcn_dgrad(x, offset, mask, w, dy, stride, pad, dilation, dg, bf16=False, out
     doff = torch.empty_like(offset)
     dmask = torch.empty_like(mask)
     assert doff.stride() == offset.stride() and dmask.stride() == mask.stride()
-    img = b16_carry(dy) if bf16 else None
-    if img is not None and getattr(dy, "_rr_b16")[1] not in (None, torch.cuda.current_stream(dy.device).cuda_stream):
-        img = None
+    img = b16_side.now(dy) if bf16 else None
     if bf16 and _DCN_WPACK:
         # both sweep operands by LDS-DMA: weights packed to bf16 inside the call; dY = its producer's bf16 image when there is
         # one (the heads' 1x1 data gradient), else rounded once into the workspace

@@ -164,11 +164,11 @@ def test_bn_apply_vs_fp64(form, c, px, relu, res):
     tag = "%s C=%d pixels=%d relu=%d res=%d via %s" % (form, c, px, relu, res, entry)
     fig = _check_against(tag, None if only16 else _rows_of(out), None if img is None else _rows_of(img), ref, 3.0 * U32 * mag)
     if entry == "rr_bn_apply_amax":
-        word = out._rr_amax[2].view(torch.float32)[0]
+        word = ops.amax_carry(out).view(torch.float32)[0]
         assert float(word) == float(out.abs().max()), (float(word), float(out.abs().max()))
         fig.append("published max|out| %.6e" % float(word))
     else:
-        assert getattr(out, "_rr_amax", None) is None
+        assert ops.amax_carry(out) is None
     print(tag + ": " + ", ".join(fig))
 
 
@@ -245,7 +245,7 @@ def test_relu_edge_forward_is_the_rounded_exact_value(form):
         fig.append("image: %d differ from RNE of that" % bad)
         assert bad == 0
     if form == "amax":
-        assert float(out._rr_amax[2].view(torch.float32)[0]) == float(want.max())
+        assert float(ops.amax_carry(out).view(torch.float32)[0]) == float(want.max())
     print("relu edge forward / %s via %s: %s" % (form, cfg["entry"], ", ".join(fig)))
 
 

@@ -194,6 +194,105 @@ def test_bf16_only_handle_reads_as_nan_for_torch_native_consumers():
         raise AssertionError("a handle without its image link must raise")
 
 
+def _b16_image(n, c, h, w):
+    import torch
+    return torch.zeros((n, h, w, c), dtype=torch.bfloat16).permute(0, 3, 1, 2)
+
+
+def test_phantom_image_does_not_depend_on_the_shared_stub_version():
+    """Every bf16-only handle of a device views one stub and shares its version counter; its image is its value and is never
+    updated in place.  A write of the stub must not unlink the image of any live handle, nor of a restored view of one."""
+    import torch
+    from rrnet_amd import ops
+    dev = torch.device("cpu")
+    img_p, img_q = _b16_image(2, 8, 3, 4), _b16_image(1, 8, 5, 4)
+    p, q = ops.phantom_f32((2, 8, 3, 4), dev, img_p), ops.phantom_f32((1, 8, 5, 4), dev, img_q)
+    assert ops.b16_carry(p) is img_p and ops.b16_carry(q) is img_q
+    carried = ops.side_carry(p)
+    v = p.view_as(p)
+    ops.side_restore(carried, v)
+    ops._PHANTOM_STUB[dev].fill_(float("nan"))
+    assert ops.b16_carry(p) is img_p and ops.b16_carry(q) is img_q
+    assert ops.image_of(p) is img_p and ops.image_of(q) is img_q
+    assert ops.image_of(v) is img_p and ops.bf16_of(v) is img_p
+    v2 = p.view_as(p)
+    ops.side_restore(ops.side_carry(p), v2)
+    ops._PHANTOM_STUB[dev].fill_(float("nan"))
+    assert ops.image_of(v2) is img_p and ops.b16_side.now(v2) is img_p
+
+
+def test_sidecars_of_ordinary_tensors_go_stale_with_the_version_and_drop_together():
+    import torch
+    from rrnet_amd import ops
+    t, img, word = torch.zeros(1, 8, 2, 2), _b16_image(1, 8, 2, 2), torch.zeros(1, dtype=torch.float64)
+    ops.b16_side.attach(t, img)                 # (not on the GPU: no stream to be valid on)
+    ops.amax_side.attach(t, word)
+    assert ops.b16_carry(t) is img and ops.amax_carry(t) is word and ops.b16_side.now(t) is img and ops.amax_side.now(t) is word
+    a, b = torch.zeros(1, 8, 2, 2), torch.zeros(1, 8, 2, 2)
+    ops.side_restore(ops.side_carry(t, None, t), a, None, b)       # both kinds of the first tensor, the images of the rest
+    assert ops.amax_carry(a) is word and ops.b16_carry(a) is img and ops.amax_carry(b) is None and ops.b16_carry(b) is img
+    t.add_(1)
+    assert ops.b16_carry(t) is None and ops.amax_carry(t) is None and ops.b16_side.now(t) is None and ops.amax_side.now(t) is None
+    ops.b16_side.attach(t, img)
+    ops.amax_side.attach(t, word)
+    assert ops.b16_carry(t) is img and ops.amax_carry(t) is word
+    ops.amax_drop(t)                            # a raw-pointer write: both kinds
+    assert ops.b16_carry(t) is None and ops.amax_carry(t) is None
+    ops.amax_drop(None)
+
+
+def test_sidecars_are_shared_with_views_and_restored_for_use_now():
+    import torch
+    from rrnet_amd import ops
+    t, img, word = torch.zeros(1, 8, 2, 2), _b16_image(1, 8, 2, 2), torch.zeros(1, dtype=torch.float64)
+    ops.b16_side.attach(t, img)
+    ops.amax_side.attach(t, word)
+    a, b = t.view_as(t), t.view_as(t)
+    ops.b16_side.share(t, (a, b))
+    ops.amax_side.share(t, (a, b))
+    for o in (a, b):
+        assert ops.b16_carry(o) is img and ops.amax_carry(o) is word and ops.b16_side.now(o) is img
+    fresh = torch.zeros(1, 8, 2, 2)
+    ops.side_restore(ops.side_carry(t), fresh)
+    assert ops.b16_side.now(fresh) is img and ops.amax_side.now(fresh) is word
+    ops.side_restore(None, fresh)               # a node that carried nothing
+    ops.side_restore((None, None, None), fresh, None)
+    assert ops.b16_side.now(fresh) is img and ops.amax_side.now(fresh) is word
+    stale = torch.zeros(1, 8, 2, 2)
+    ops.b16_side.attach(stale, img)
+    stale.add_(1)
+    c = stale.view_as(stale)
+    ops.b16_side.share(stale, (c,))             # nothing valid rides on it: nothing travels
+    assert ops.b16_carry(c) is None
+
+
+def test_publication_truth_tables():
+    """ops.image_wanted / amax_wanted: the conditions bn_apply, bn_bwd_apply, upsample_add_fwd and the fan-out used to restate
+    (C % 128 == 0 and >= 8192 pixels under bf16 with the conv16 kernels on; >= 2048 pixels under f16x3; on the GPU only)."""
+    import torch
+    from rrnet_amd import ops
+    gpu, cpu = torch.device("cuda"), torch.device("cpu")
+    assert ops._CONV16_MIN_PIXELS == 8192 and ops._SPLIT_MIN_PIXELS == 2048
+    saved = ops._CONV16
+    try:
+        ops._CONV16 = True
+        with ops.bf16_scope(ops.MATH_BF16, force=True):
+            assert ops.image_wanted(128, 8192, gpu) and ops.image_wanted(384, 10000, gpu)
+            assert not ops.image_wanted(127, 8192, gpu) and not ops.image_wanted(128, 8191, gpu) and not ops.image_wanted(128, 8192, cpu)
+            assert ops.image_wanted(256, 8192, gpu, 256) and not ops.image_wanted(128, 8192, gpu, 256)
+            assert not ops.amax_wanted(128, 8192, gpu)
+            ops._CONV16 = False
+            assert not ops.image_wanted(128, 8192, gpu)
+            ops._CONV16 = True
+        with ops.bf16_scope(ops.MATH_F16X3, force=True):
+            assert ops.amax_wanted(12, 2048, gpu) and not ops.amax_wanted(12, 2047, gpu) and not ops.amax_wanted(12, 2048, cpu)
+            assert not ops.image_wanted(128, 8192, gpu)
+        with ops.bf16_scope(ops.MATH_F32, force=True):
+            assert not ops.image_wanted(128, 8192, gpu) and not ops.amax_wanted(12, 2048, gpu)
+    finally:
+        ops._CONV16 = saved
+
+
 def test_bench_self_launches_child_ranks_when_no_launcher_started_it():
     """VERDICT r5 missing #3 (reference: operators/distributed_wrapper.py:47-61 spawns its own workers): `python bench.py --gpus 2`
     without launcher variables must become the launcher — `torch.distributed.run` with two ranks as a CHILD process, decided

@@ -243,3 +243,28 @@ def test_side_stream_f16x3_model_equals_one_stream(tmp_path):
     _compare(one, side, "f16x3 model: side stream under stress vs one stream")
     for r in side[1]["repeat_vs_first"]:
         assert r["grad"][0] <= BOUND, r
+
+
+def test_sidecars_are_valid_on_their_stream_until_published():
+    """ops' sidecars (the bf16 image of bf16_of, the maximum of amax_of) ride on the tensor object: valid on the stream that made
+    them, and on every stream once published behind a wait_stream (what _wgrad_async does for the weight-gradient stream)."""
+    from rrnet_amd import ops
+    main, side = torch.cuda.current_stream(), torch.cuda.Stream()
+    for lookup in (ops.bf16_of, ops.amax_of):
+        t = ops.empty_nhwc(1, 8, 2, 2, "cuda").normal_()
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            first = lookup(t)
+            assert lookup(t) is first                    # remembered on the stream that made it
+        main.wait_stream(side)
+        second = lookup(t)
+        assert second is not first                       # ordered behind it, but nobody said so: not valid here
+        t = ops.empty_nhwc(1, 8, 2, 2, "cuda").normal_()
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            first = lookup(t)
+            main.wait_stream(side)
+            ops.side_publish(t)
+        assert lookup(t) is first
+        assert torch.equal(ops.bf16_of(t), t.to(torch.bfloat16))
+    torch.cuda.synchronize()

@@ -373,7 +373,7 @@ def test_bwd_apply_divides_by_the_device_count(form, mask):
                 assert g_a is None and g_b is None
             if name == "rr_bn_bwd_apply_amax":
                 for dx in (dxa, dxb):
-                    word = dx._rr_amax[2].view(torch.float32)[0]
+                    word = ops.amax_carry(dx).view(torch.float32)[0]
                     assert float(word) == float(dx.abs().max()), (float(word), float(dx.abs().max()))
                 fig.append("published max|dx| %.6e" % float(dxa.abs().max()))
             print("%s / %s, shard %d of %s (local count %d, global %d) via %s: %s" % (form, mask, i, shards, n_loc, n_glob, name, ", ".join(fig)))

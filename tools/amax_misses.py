@@ -19,12 +19,9 @@ torch.cuda.synchronize()
 orig = ops.amax_of
 cnt = collections.Counter()
 def spy(t):
-    hit = getattr(t, "_rr_amax", None)
-    sid = torch.cuda.current_stream(t.device).cuda_stream
-    miss = not (hit is not None and hit[0] == t._version and (hit[1] == sid or hit[1] is None))
-    if miss:
+    if ops.amax_side.now(t) is None:
         st = traceback.extract_stack(limit=6)
-        why = "none" if hit is None else ("version" if hit[0] != t._version else "stream")
+        why = "none / version" if ops.amax_carry(t) is None else "stream"
         cnt[(why, tuple(t.shape), " <- ".join("%s:%d" % (f.name, f.lineno) for f in st[:-1][-4:]))] += 1
     return orig(t)
 ops.amax_of = spy
