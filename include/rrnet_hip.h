@@ -520,6 +520,21 @@ int rr_nms_sorted(const float *boxes, int n, int stride, float thresh, int inclu
                   int *keep, int *num_out, hipStream_t stream);
 void _nms(int *keep_out, int *num_out, const float *boxes_host, int boxes_num, int boxes_dim,
           float nms_overlap_thresh, int device_id);
+/* rr_nms_frames: rr_nms_sorted for all frames of a batch, no host read in between.  rows6 = the packed, score-descending
+ *   x,y,w,h,score,cls rows of rr_sort_frames_by_score(out_off, xyxy = 0); frame f occupies rows frame_off[f] ..
+ *   frame_off[f+1] (int32 [nframes+1], device).  The kernel forms x2 = x + w, y2 = y + h in float32 itself.
+ *   keep[frame_off[f] + j] = the j-th kept row index, local to the frame and ascending: the indices rr_nms_sorted returns
+ *   for that frame alone; kept[f] their number.  rows6 and keep hold at least nframes * max_rows rows; max_rows <=
+ *   RR_DETECT_MAX_ROWS is checked on the host, a frame length outside [0, max_rows] or a first row outside that space is
+ *   clamped on the device.  workspace = rr_nms_frames_workspace_bytes(nframes, max_rows) bytes: one max_rows x
+ *   ceil(max_rows / 64) word suppression matrix per frame.
+ * rr_pack_frames: the kept rows back to back: out6[out_off[f] + j] = row keep[frame_off[f] + j] of frame f, j < kept[f];
+ *   out_off [nframes+1] = exclusive prefix of kept, written by the same launch; rows beyond out_rows are not written. */
+size_t rr_nms_frames_workspace_bytes(int nframes, int max_rows);
+int rr_nms_frames(const float *rows6, const int *frame_off, int nframes, int max_rows, float thresh, int inclusive,
+                  void *workspace, int *keep, int *kept, hipStream_t stream);
+int rr_pack_frames(const float *rows6, const int *frame_off, const int *keep, const int *kept, int nframes, int max_rows,
+                   float *out6, long out_rows, int *out_off, hipStream_t stream);
 int rr_pack_segments(const float *grouped, const int *seg_off, const int *n_out, int nseg, int segs_per_image,
                      int *out_off, float *rois, float *scores, float *clses, float *rows6, int phase,
                      hipStream_t stream);
@@ -715,6 +730,17 @@ int rr_retina_loss_bwd(const float *logits, const float *loc, const signed char 
                        float *dloc, hipStream_t stream);
 int rr_retina_decode(const float *logits, const float *loc, const float *anchors, int b, int a, int c, float score_thr,
                      float *rows, int *count, hipStream_t stream);
+/* rr_retina_decode_frames: rr_retina_decode with the anchors of an image spread over workgroups of RR_RETINA_DECODE_CHUNK
+ *   anchors.  rows [b,k,6], 0 < k <= a: the first min(count[f], k) rows of frame f are bit for bit the rows rr_retina_decode
+ *   writes for that image, in anchor order; count[f] is the true number of candidates also when it exceeds k; rows at and
+ *   beyond k are not written, rows between count[f] and k are left untouched.  Two launches ordered by the stream (per-chunk
+ *   counts and per-anchor probability / class into the workspace; then every workgroup sums the counts of the chunks in
+ *   front of it and writes its rows): no workgroup waits on another.  workspace =
+ *   rr_retina_decode_frames_workspace_bytes(b, a) bytes. */
+#define RR_RETINA_DECODE_CHUNK 256
+size_t rr_retina_decode_frames_workspace_bytes(int b, int a);
+int rr_retina_decode_frames(const float *logits, const float *loc, const float *anchors, int b, int a, int c,
+                            float score_thr, float *rows, int k, int *count, void *workspace, hipStream_t stream);
 
 /* ---- RoIAlign --------------------------------------------------------------------------- *
  * torchvision.ops.roi_align(feat, rois, (ph,pw)) at models/rrnet.py:51 (spatial_scale 1,

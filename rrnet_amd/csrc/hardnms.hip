@@ -135,6 +135,110 @@ __global__ __launch_bounds__(256) void nms_reduce_kernel(const unsigned long lon
     }
     if (threadIdx.x == 0) *num_out = k;
 }
+
+// ---- the same two phases for all frames of a batch (rr_nms_frames) ------------------------------------------------
+// rows are the packed, score-descending x,y,w,h,score,class rows of rr_sort_frames_by_score; frame f holds rows
+// frame_off[f] .. frame_off[f+1].  What comes from device memory is clamped before it addresses anything: a frame's
+// length to [0, max_rows], its first row to [0, nframes * max_rows - length] (rows6 and keep hold that many rows).
+struct FrameSpan { long start; int n; };
+
+__device__ __forceinline__ FrameSpan frame_span(const int *frame_off, int f, int nframes, int max_rows)
+{
+    const int lo = frame_off[f], hi = frame_off[f + 1];
+    FrameSpan s;
+    s.n = min(max(hi - lo, 0), max_rows);
+    s.start = min(max((long)lo, 0l), (long)nframes * max_rows - s.n);
+    return s;
+}
+
+// x, y, w, h -> x1, y1, x2, y2 with x2 = x + w, y2 = y + h: the float32 additions in front of the reference's nms()
+__device__ __forceinline__ void load_xyxy(const float *row, float *o)
+{
+    const float x = row[0], y = row[1];
+    o[0] = x; o[1] = y; o[2] = x + row[2]; o[3] = y + row[3];
+}
+
+// grid (column block, row block, frame); mask of frame f: max_rows x cbmax words at mask + f * max_rows * cbmax, rows at the
+// frame's own stride of ceil(n / 64) words.  Blocks past the frame's own length leave at once.
+__global__ __launch_bounds__(64) void nms_frames_mask_kernel(const float *rows6, const int *frame_off, int nframes, int max_rows,
+                                                             float thresh, int inclusive, unsigned long long *mask)
+{
+    const int f = blockIdx.z, row_blk = blockIdx.y, col_blk = blockIdx.x;
+    const FrameSpan s = frame_span(frame_off, f, nframes, max_rows);
+    const int n = s.n;
+    const int col_blocks = (n + 63) / 64;
+    if (row_blk >= col_blocks || col_blk >= col_blocks || col_blk < row_blk) return;
+    const float *boxes = rows6 + s.start * 6;
+    unsigned long long *fm = mask + (long)f * max_rows * ((max_rows + 63) / 64);
+    __shared__ float cb[64 * 4];
+    const int cj = col_blk * 64 + threadIdx.x;
+    if (cj < n) load_xyxy(boxes + (long)cj * 6, cb + threadIdx.x * 4);
+    __syncthreads();
+    const int i = row_blk * 64 + threadIdx.x;
+    if (i >= n) return;
+    float me[4];
+    load_xyxy(boxes + (long)i * 6, me);
+    const int ncol = n - col_blk * 64 < 64 ? n - col_blk * 64 : 64;
+    unsigned long long t = 0;
+    for (int j = (row_blk == col_blk ? threadIdx.x + 1 : 0); j < ncol; ++j) {
+        const float ovr = iou_plus1(me, cb + j * 4);
+        if (inclusive ? ovr >= thresh : ovr > thresh) t |= 1ull << j;
+    }
+    fm[(long)i * col_blocks + col_blk] = t;
+}
+
+// one workgroup per frame: nms_reduce_kernel on the frame's mask; keep[start + j] = j-th kept row, local to the frame
+__global__ __launch_bounds__(256) void nms_frames_reduce_kernel(const unsigned long long *mask, const int *frame_off, int nframes,
+                                                                int max_rows, int *keep, int *kept)
+{
+    extern __shared__ unsigned long long remv[];   // [ceil(max_rows / 64)]
+    const int f = blockIdx.x;
+    const FrameSpan s = frame_span(frame_off, f, nframes, max_rows);
+    const int n = s.n;
+    const int col_blocks = (n + 63) / 64;
+    const unsigned long long *fm = mask + (long)f * max_rows * ((max_rows + 63) / 64);
+    int *out = keep + s.start;
+    for (int j = threadIdx.x; j < col_blocks; j += 256) remv[j] = 0ull;
+    __syncthreads();
+    int k = 0;
+    for (int i = 0; i < n; ++i) {
+        if ((remv[i >> 6] >> (i & 63)) & 1ull) continue;       // uniform: every thread reads the same word
+        if (threadIdx.x == 0) out[k] = i;
+        ++k;
+        __syncthreads();                                        // all reads of remv[i >> 6] done before it changes
+        for (int j = (i >> 6) + threadIdx.x; j < col_blocks; j += 256) remv[j] |= fm[(long)i * col_blocks + j];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) kept[f] = k;
+}
+
+// grid (row block, frame): out6[out_off[f] + j] = frame f's row keep[j]; every workgroup sums kept[0..f) itself
+__global__ __launch_bounds__(NT) void pack_frames_kernel(const float *rows6, const int *frame_off, const int *keep, const int *kept,
+                                                         int nframes, int max_rows, float *out6, long out_rows, int *out_off)
+{
+    __shared__ int wsum[NT / 64];
+    const int f = blockIdx.y;
+    int part = 0;
+    for (int g = threadIdx.x; g < f; g += NT) part += min(max(kept[g], 0), frame_span(frame_off, g, nframes, max_rows).n);
+    part = wave_sum_i(part);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = part;
+    __syncthreads();
+    long before = 0;
+    for (int w = 0; w < NT / 64; ++w) before += wsum[w];
+    const FrameSpan s = frame_span(frame_off, f, nframes, max_rows);
+    const int nk = min(max(kept[f], 0), s.n);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        out_off[f] = (int)before;
+        if (f == nframes - 1) out_off[nframes] = (int)before + nk;
+    }
+    const int j = blockIdx.x * NT + threadIdx.x;
+    if (j >= nk || before + j >= out_rows) return;
+    const int r = min(max(keep[s.start + j], 0), s.n - 1);
+    const float *src = rows6 + (s.start + r) * 6;
+    float *dst = out6 + (before + j) * 6;
+#pragma unroll
+    for (int e = 0; e < 6; ++e) dst[e] = src[e];
+}
 }  // namespace
 
 extern "C" size_t rr_nms_workspace_bytes(int n)
@@ -162,6 +266,56 @@ extern "C" int rr_nms_sorted(const float *boxes, int n, int stride, float thresh
         hipFuncSetAttribute(reinterpret_cast<const void *>(nms_reduce_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(nms_reduce_kernel, dim3(1), dim3(256), lds, stream, mask, n, keep, num_out);
     RR_CHECK_LAUNCH("rr_nms_sorted(reduce)");
+    return RR_OK;
+}
+
+extern "C" size_t rr_nms_frames_workspace_bytes(int nframes, int max_rows)
+{
+    if (nframes <= 0 || max_rows <= 0) return 0;
+    return (size_t)nframes * rr_nms_workspace_bytes(max_rows);
+}
+
+extern "C" int rr_nms_frames(const float *rows6, const int *frame_off, int nframes, int max_rows, float thresh, int inclusive,
+                             void *workspace, int *keep, int *kept, hipStream_t stream)
+{
+    RR_CHECK_ARG(nframes >= 0 && nframes <= 65535, "rr_nms_frames: %d frames (limit 65535)", nframes);
+    RR_CHECK_ARG(max_rows >= 0 && max_rows <= RR_DETECT_MAX_ROWS, "rr_nms_frames: %d rows per frame (limit %d)", max_rows,
+                 RR_DETECT_MAX_ROWS);
+    RR_CHECK_ARG(inclusive == 0 || inclusive == 1, "rr_nms_frames: inclusive %d", inclusive);
+    if (nframes == 0) return RR_OK;
+    RR_CHECK_ARG(kept != nullptr, "rr_nms_frames: null pointer");
+    if (max_rows == 0) {
+        RR_CHECK_HIP(hipMemsetAsync(kept, 0, sizeof(int) * (size_t)nframes, stream), "rr_nms_frames");
+        return RR_OK;
+    }
+    RR_CHECK_ARG(rows6 && frame_off && keep, "rr_nms_frames: null pointer");
+    RR_CHECK_ARG(workspace != nullptr, "rr_nms_frames: workspace required (rr_nms_frames_workspace_bytes)");
+    const int cb = (max_rows + 63) / 64;
+    unsigned long long *mask = reinterpret_cast<unsigned long long *>(workspace);
+    hipLaunchKernelGGL(nms_frames_mask_kernel, dim3(cb, cb, nframes), dim3(64), 0, stream, rows6, frame_off, nframes, max_rows,
+                       thresh, inclusive, mask);
+    RR_CHECK_LAUNCH("rr_nms_frames(mask)");
+    hipLaunchKernelGGL(nms_frames_reduce_kernel, dim3(nframes), dim3(256), (size_t)cb * 8, stream, mask, frame_off, nframes,
+                       max_rows, keep, kept);
+    RR_CHECK_LAUNCH("rr_nms_frames(reduce)");
+    return RR_OK;
+}
+
+extern "C" int rr_pack_frames(const float *rows6, const int *frame_off, const int *keep, const int *kept, int nframes,
+                              int max_rows, float *out6, long out_rows, int *out_off, hipStream_t stream)
+{
+    RR_CHECK_ARG(nframes >= 0 && nframes <= 65535, "rr_pack_frames: %d frames (limit 65535)", nframes);
+    RR_CHECK_ARG(max_rows >= 0 && max_rows <= RR_DETECT_MAX_ROWS, "rr_pack_frames: %d rows per frame (limit %d)", max_rows,
+                 RR_DETECT_MAX_ROWS);
+    RR_CHECK_ARG(out_rows >= 0 && out_off != nullptr, "rr_pack_frames: out6 holds %ld rows", out_rows);
+    if (nframes == 0 || max_rows == 0) {
+        RR_CHECK_HIP(hipMemsetAsync(out_off, 0, sizeof(int) * ((size_t)nframes + 1), stream), "rr_pack_frames");
+        return RR_OK;
+    }
+    RR_CHECK_ARG(rows6 && frame_off && keep && kept && (out6 || out_rows == 0) && rows6 != out6, "rr_pack_frames: null or aliased pointer");
+    hipLaunchKernelGGL(pack_frames_kernel, dim3(rr_cdiv(max_rows, NT), nframes), dim3(NT), 0, stream, rows6, frame_off, keep, kept,
+                       nframes, max_rows, out6, out_rows, out_off);
+    RR_CHECK_LAUNCH("rr_pack_frames");
     return RR_OK;
 }
 

@@ -1,5 +1,5 @@
 // RetinaNet's own kernels for gfx950: the stem's max-pool, the FPN's bilinear upsample-add, the anchor criterion
-// (assignment + focal / smooth-L1 losses) and the box decode.
+// (assignment + focal / smooth-L1 losses) and the box decode (one workgroup per image, and chunked over many for frames).
 //
 // All of them are bandwidth-bound (no MFMA): one pass over their operands, float4 over channels / classes where the
 // innermost extent is a multiple of 4, wave-level reductions, no float atomics (the only atomics are the integer adds
@@ -581,6 +581,92 @@ __global__ __launch_bounds__(TPB) void retina_decode_kernel(const float *__restr
     if (threadIdx.x == 0) count[b] = run;
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// decode for many frames: an image's anchors spread over workgroups of RR_RETINA_DECODE_CHUNK anchors, rows appended in
+// anchor order across them.  Two launches ordered by the stream and nothing else: no workgroup waits on another.
+//   pass 1 (score): per anchor the probability and class + 1 of retina_decode_kernel (0 = row leaves) into the scratch,
+//                   per chunk the number of rows kept
+//   pass 2 (write): every workgroup sums the counts of the chunks in front of it, ranks its own rows by ballot + prefix
+//                   and decodes the ones that land below k; the last chunk's workgroup owns count[f]
+// ------------------------------------------------------------------------------------------------------------------
+constexpr int DCHUNK = RR_RETINA_DECODE_CHUNK;
+static_assert(DCHUNK == TPB, "one anchor per thread of a chunk's workgroup");
+
+struct ScoreCls { float prob; int cls; };
+
+__global__ __launch_bounds__(TPB) void retina_score_chunks_kernel(const float *__restrict__ logits, int A, int C, float thr,
+                                                                  ScoreCls *__restrict__ sc, int *__restrict__ chunk_cnt)
+{
+    __shared__ int wave_cnt[4];
+    const int b = blockIdx.y, chunk = blockIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int a = chunk * DCHUNK + threadIdx.x;
+    bool keep = false;
+    if (a < A) {
+        const float *q = logits + ((long)b * A + a) * C;
+        float best = sigmoidf_(q[0]);
+        int bi = 0;
+        for (int c = 1; c < C; ++c) {
+            const float p = sigmoidf_(q[c]);
+            if (p > best || p != p) {                     // as retina_decode_kernel: first maximum, a NaN is the maximum
+                best = p;
+                bi = c;
+            }
+        }
+        keep = best > thr;
+        ScoreCls r;
+        r.prob = best;
+        r.cls = keep ? bi + 1 : 0;
+        sc[(long)b * A + a] = r;
+    }
+    const unsigned long long m = __ballot(keep);
+    if (lane == 0) wave_cnt[wave] = __popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) chunk_cnt[(long)b * gridDim.x + chunk] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+}
+
+__global__ __launch_bounds__(TPB) void retina_write_chunks_kernel(const ScoreCls *__restrict__ sc, const int *__restrict__ chunk_cnt,
+                                                                  const float *__restrict__ loc, const float *__restrict__ anchors,
+                                                                  int A, float *__restrict__ rows, int K, int *__restrict__ count)
+{
+    __shared__ int wave_cnt[4];
+    __shared__ int wave_sum[4];
+    const int b = blockIdx.y, chunk = blockIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int *cnt = chunk_cnt + (long)b * gridDim.x;
+    int part = 0;
+    for (int i = threadIdx.x; i < chunk; i += TPB) part += min(max(cnt[i], 0), DCHUNK);   // a count is at most its chunk
+    part = wave_sum_i(part);
+    const int a = chunk * DCHUNK + threadIdx.x;
+    ScoreCls r;
+    r.prob = 0.f;
+    r.cls = 0;
+    if (a < A) r = sc[(long)b * A + a];
+    const bool keep = r.cls > 0;
+    const unsigned long long m = __ballot(keep);
+    if (lane == 0) {
+        wave_sum[wave] = part;
+        wave_cnt[wave] = __popcll(m);
+    }
+    __syncthreads();
+    const int base = wave_sum[0] + wave_sum[1] + wave_sum[2] + wave_sum[3];     // base <= chunk * DCHUNK <= A: no overflow
+    int pos = base + __popcll(m & ((1ull << lane) - 1ull));
+    for (int wv = 0; wv < wave; ++wv) pos += wave_cnt[wv];
+    if (keep && pos < K) {
+        const rr_f32x4 bx = *reinterpret_cast<const rr_f32x4 *>(anchors + (long)a * 4);
+        const rr_f32x4 d = *reinterpret_cast<const rr_f32x4 *>(loc + ((long)b * A + a) * 4);
+        const float w = bx[2] - bx[0], h = bx[3] - bx[1];
+        const float cx = bx[0] + 0.5f * w, cy = bx[1] + 0.5f * h;
+        const float pcx = cx + (d[0] * 0.1f) * w, pcy = cy + (d[1] * 0.1f) * h;
+        const float o2 = expf(d[2] * 0.2f) * w;
+        const float o3 = expf(d[3] * 0.2f) * h;
+        float *o = rows + ((long)b * K + pos) * 6;
+        o[0] = pcx - 0.5f * o2; o[1] = pcy - 0.5f * o3; o[2] = o2; o[3] = o3; o[4] = r.prob; o[5] = (float)r.cls;
+    }
+    if (chunk == (int)gridDim.x - 1 && threadIdx.x == 0)
+        count[b] = base + wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+}
+
 inline int blocks_of(long total) { return (int)((total + TPB - 1) / TPB); }
 constexpr long MAX_BLOCKS = 2147483647L;
 
@@ -725,5 +811,30 @@ extern "C" int rr_retina_decode(const float *logits, const float *loc, const flo
     RR_CHECK_ARG(b > 0 && a > 0 && c > 0, "rr_retina_decode: bad dims b=%d a=%d c=%d", b, a, c);
     hipLaunchKernelGGL(retina_decode_kernel, dim3(b), dim3(TPB), 0, stream, logits, loc, anchors, a, c, score_thr, rows, count);
     RR_CHECK_LAUNCH("rr_retina_decode");
+    return RR_OK;
+}
+
+extern "C" size_t rr_retina_decode_frames_workspace_bytes(int b, int a)
+{
+    if (b <= 0 || a <= 0) return 0;
+    const size_t chunks = ((size_t)a + DCHUNK - 1) / DCHUNK;
+    return (size_t)b * (size_t)a * sizeof(ScoreCls) + (size_t)b * chunks * sizeof(int);
+}
+
+extern "C" int rr_retina_decode_frames(const float *logits, const float *loc, const float *anchors, int b, int a, int c,
+                                       float score_thr, float *rows, int k, int *count, void *workspace, hipStream_t stream)
+{
+    RR_CHECK_ARG(logits && loc && anchors && rows && count && workspace, "rr_retina_decode_frames: null pointer");
+    RR_CHECK_ARG(b > 0 && b <= 65535 && a > 0 && a <= (1 << 30) && c > 0, "rr_retina_decode_frames: bad dims b=%d a=%d c=%d", b, a,
+                 c);
+    RR_CHECK_ARG(k > 0 && k <= a, "rr_retina_decode_frames: %d rows per frame for %d anchors", k, a);
+    const int chunks = rr_cdiv(a, DCHUNK);
+    ScoreCls *sc = reinterpret_cast<ScoreCls *>(workspace);                     // [b, a]
+    int *chunk_cnt = reinterpret_cast<int *>(sc + (size_t)b * (size_t)a);       // [b, chunks]
+    hipLaunchKernelGGL(retina_score_chunks_kernel, dim3(chunks, b), dim3(TPB), 0, stream, logits, a, c, score_thr, sc, chunk_cnt);
+    RR_CHECK_LAUNCH("rr_retina_decode_frames(score)");
+    hipLaunchKernelGGL(retina_write_chunks_kernel, dim3(chunks, b), dim3(TPB), 0, stream, sc, chunk_cnt, loc, anchors, a, rows, k,
+                       count);
+    RR_CHECK_LAUNCH("rr_retina_decode_frames(write)");
     return RR_OK;
 }

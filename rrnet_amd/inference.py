@@ -15,7 +15,8 @@ Ordering note: decode emits rows score-descending, grouping / hard NMS are stabl
 `detect_frames` / `Detector` are the entry point from raw frames: the multi-scale evaluation body
 (operators/rrnet_operator.py:256-279) for a batch of equal-size uint8 frames.  `detect_frames_centernet` /
 `CenterNetFrameDetector` are the same for CenterNet (operators/centernet_operator.py:262-285: every scale once flipped
-and once plain, both in one model pass)."""
+and once plain, both in one model pass).  `detect_frames_retinanet` / `RetinaNetFrameDetector` are RetinaNet's single-scale
+evaluation body (operators/retinanet_operator.py:243-255): decode, score sort, the reference's hard NMS."""
 import os
 
 import torch
@@ -263,3 +264,107 @@ class CenterNetFrameDetector:
         nms = (not self.cfg.Val.auto_test) if nms is None else bool(nms)
         return detect_frames_centernet(self.model, frames_u8, scales, self.mean, self.std, nms=nms, flip=flip, k=k,
                                        scale_factor=self.scale_factor, num_classes=self.num_classes, timer=timer)
+
+
+RETINA_MAX_CANDIDATES = ops.DETECT_MAX_ROWS     # candidates of one frame the batched score sort holds
+
+
+@torch.no_grad()
+def detect_frames_retinanet(model, frames_u8, mean, std, anchors, *, score_thr=0.1, nms_thresh=0.3, timer=None):
+    """RetinaNet's evaluation body (operators/retinanet_operator.py:243-255, with RetinaNetOperator's two deviations: the
+    kept indices select the rows, and every image of the batch is evaluated) on B equal-size frames.
+    frames_u8 uint8 [B,H,W,3] on the device, model = RetinaNet in eval mode (fp32), mean / std = Normalize's (the validation
+    chain is ToTensor, Normalize: no resize), anchors [A,4] xyxy on the device for this frame size.
+    One prepare at the frames' own size, one model pass, rr_retina_decode_frames (at most 16384 rows per frame), the stable
+    score sort, rr_nms_frames ("+1" IoU, suppression at IoU > nms_thresh) and the pack.
+    -> (boxes [n,6] = x,y,w,h,prob,cls+1, frames back to back, each score-descending; frame_off int32 [B+1]), both on the
+    device: per frame the rows RetinaNetOperator.evaluate_images returns.  Host reads: the candidate counts and the final
+    offsets.  Raises ValueError when a frame has more than 16384 candidates (evaluate_images' refusal), before the sort.
+    timer as in detect_frames."""
+    if not torch.is_tensor(frames_u8) or frames_u8.dtype != torch.uint8:
+        raise TypeError("detect_frames_retinanet: frames must be a uint8 tensor [B,H,W,3], got %s"
+                        % (frames_u8.dtype if torch.is_tensor(frames_u8) else type(frames_u8).__name__))
+    if frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
+        raise ValueError("detect_frames_retinanet: frames must be [B,H,W,3], got %s" % (tuple(frames_u8.shape),))
+    from rrnet_amd import _C
+    _C.require_cuda(frames_u8)
+    tick = timer if timer is not None else (lambda stage: None)
+    dev = frames_u8.device
+    frames_u8 = frames_u8.contiguous()
+    b = frames_u8.shape[0]
+    mean, std = _vec3(mean, dev), _vec3(std, dev)
+    x = ops.prepare_frames(frames_u8, mean, std, 1)
+    tick('prepare')
+    loc_pre, cls_pre = model(x)
+    tick('model')
+    a = cls_pre.shape[1]
+    if tuple(anchors.shape) != (a, 4):
+        raise ValueError("detect_frames_retinanet: %d predictions per frame against %s anchors" % (a, tuple(anchors.shape)))
+    limit = RETINA_MAX_CANDIDATES
+    rows, count = ops.retina_decode_frames(cls_pre, loc_pre, anchors, score_thr, k=min(a, limit))
+    counts = count.cpu()                                            # host read: the candidate counts
+    over = torch.nonzero(counts > limit)
+    if over.numel():
+        f = int(over[0, 0])
+        raise ValueError("detect_frames_retinanet: frame %d has %d candidates above the score threshold; the score sort "
+                         "accepts %d per frame" % (f, int(counts[f]), limit))
+    most = int(counts.max())
+    if most == 0:
+        tick('post')
+        return rows.new_zeros((0, 6)), torch.zeros(b + 1, dtype=torch.int32, device=dev)
+    cand_off = ops.seg_prefix(count)
+    ordered = ops.sort_frames_by_score(rows, count, out_off=cand_off)
+    keep, kept = ops.nms_frames(ordered, cand_off, most, nms_thresh)
+    out6, frame_off = ops.pack_frames(ordered, cand_off, keep, kept, most, out_rows=int(counts.sum()))
+    fo = frame_off.cpu()                                            # host read: the final offsets
+    tick('post')
+    return out6[:int(fo[-1])], frame_off
+
+
+class RetinaNetFrameDetector:
+    """RetinaNet from a reference-format checkpoint, ready for `detect`: the counterpart of CenterNetFrameDetector.  Builds
+    RetinaNet(cfg), loads the state dict (with or without `module.` prefixes; checkpoint=None keeps the initial weights),
+    sets eval mode and channels-last; mean / std come from cfg.Val.transforms; the anchors are Anchors(sizes=(16, 64, 128)),
+    cached per frame size on the device.  fp32 only."""
+
+    def __init__(self, cfg, checkpoint=None, device=None):
+        from rrnet_amd.datasets.augment import chain_params
+        from rrnet_amd.models.retinanet import RetinaNet
+        from rrnet_amd.modules.anchor import Anchors
+        self.cfg = cfg
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        model = RetinaNet(cfg)
+        if checkpoint is not None:
+            sd = torch.load(checkpoint, map_location='cpu') if isinstance(checkpoint, (str, os.PathLike)) else checkpoint
+            sd = {(key[7:] if key.startswith('module.') else key): v for key, v in sd.items()}
+            model.load_state_dict(sd)
+        self.model = model.to(self.device).to(memory_format=torch.channels_last).eval()
+        p = chain_params(cfg.Val.transforms)
+        self.mean, self.std = p["mean"], p["std"]
+        self.anchor_maker = Anchors(sizes=(16, 64, 128))
+        self._anchors = {}
+
+    def anchors(self, size):
+        key = (int(size[0]), int(size[1]))
+        hit = self._anchors.get(key)
+        if hit is None:
+            hit = self._anchors[key] = self.anchor_maker(key).to(self.device)
+        return hit
+
+    def detect(self, frames_u8, score_thr=0.1, nms_thresh=0.3, timer=None):
+        """frames uint8 [B,H,W,3] on the device -> (boxes [n,6], frame_off int32 [B+1]) as detect_frames_retinanet."""
+        return detect_frames_retinanet(self.model, frames_u8, self.mean, self.std, self.anchors(frames_u8.shape[1:3]),
+                                       score_thr=score_thr, nms_thresh=nms_thresh, timer=timer)
+
+    @torch.no_grad()
+    def threshold_for_rows(self, frames_u8, rows_per_frame):
+        """A score threshold for models whose scores mean nothing (random weights: every anchor sits near 0.5 and passes
+        0.1, which the score sort refuses): one model pass on these frames -> (threshold, candidates per frame at it), the
+        threshold being the smallest at which no frame keeps more than rows_per_frame anchors.  For smoke runs and the
+        benchmark, not part of the detection path."""
+        x = ops.prepare_frames(frames_u8.contiguous(), _vec3(self.mean, self.device), _vec3(self.std, self.device), 1)
+        _, cls_pre = self.model(x)
+        best = torch.sigmoid(cls_pre.float()).amax(dim=2)                       # [B,A]
+        rows_per_frame = min(int(rows_per_frame), best.shape[1] - 1)
+        thr = float(best.topk(rows_per_frame + 1, dim=1).values[:, -1].max())   # `prob > thr` keeps at most rows_per_frame
+        return thr, (best > thr).sum(dim=1).tolist()

@@ -2,7 +2,8 @@
 make_anchor / criterion / training_process / transform_bbox / save_result / evaluation_process surface; underneath: the
 HIP kernels of librrnet_hip.so (convolutions, max-pool, bilinear upsample-add), the anchor criterion as one autograd node
 over rr_retina_assign / rr_retina_loss_* (RF.retina_criterion), the fused flat Adam, rr_retina_decode, the score sort and
-rr_nms_sorted.  fp32, one process, one GPU.
+rr_nms_sorted.  fp32, one process, one GPU.  With cfg.Val.device_batch >= 1 the evaluation runs batched on raw frames
+(rrnet_amd.inference.detect_frames_retinanet).
 
 Deviations from the reference, all in the evaluation (:227-265):
   * the reference indexes `pred_bbox` with what `nms()` returns (:254-255) — `nms()` returns the kept ROWS, not indices, so
@@ -160,6 +161,38 @@ class RetinaNetOperator(BaseOperator):
                                         _C.ptr(num), _C.stream()), "rr_nms_sorted")
         return ordered[keep[:int(num.item())].long()]
 
+    @staticmethod
+    def write_results(result_dir, names, boxes, frame_off):
+        """The files save_result writes for the frames of one batch, byte for byte, from one host conversion: boxes [n,6]
+        and frame_off [B+1] as detect_frames_retinanet returns them (tensors or arrays), names the B file stems."""
+        rows = boxes.detach().cpu().numpy() if torch.is_tensor(boxes) else np.asarray(boxes)
+        rows = rows.astype(np.float32, copy=False).reshape(-1, 6)
+        rows = np.where(rows < 0, np.float32(0.), rows).tolist()     # torch.clamp(min=0.): -0.0 passes through
+        off = frame_off.tolist() if hasattr(frame_off, "tolist") else list(frame_off)
+        for i, name in enumerate(names):
+            with open(os.path.join(result_dir, name + '.txt'), 'w') as f:
+                f.write(''.join('%d,%d,%d,%d,%.4f,%d,-1,-1\n' % (int(r[0]), int(r[1]), int(r[2]), int(r[3]), r[4], int(r[5]))
+                                for r in rows[off[i]:off[i + 1]]))
+
+    def evaluate_batched(self, device_batch, result_dir=None):
+        """evaluation_process' loop over SizeBucketedFrames -> detect_frames_retinanet: equal-size raw frames `device_batch`
+        at a time, one D2H copy per batch."""
+        from rrnet_amd.datasets.augment import chain_params
+        from rrnet_amd.datasets.frames import SizeBucketedFrames
+        from rrnet_amd.inference import detect_frames_retinanet
+        cfg = self.cfg
+        result_dir = getattr(cfg.Val, "result_dir", './results/') if result_dir is None else result_dir
+        p = chain_params(cfg.Val.transforms)
+        model = getattr(self.model, "module", self.model)
+        frames = SizeBucketedFrames(self.validation_loader.dataset, device_batch, rank=getattr(cfg.Distributed, "rank", 0),
+                                    world_size=max(int(getattr(cfg.Distributed, "world_size", 1)), 1),
+                                    num_workers=cfg.Val.num_workers)
+        for frames_u8, names in frames:
+            anchors = self.make_anchor(frames_u8.shape[1:3])[0]
+            boxes, frame_off = detect_frames_retinanet(model, frames_u8, p["mean"], p["std"], anchors,
+                                                       score_thr=SCORE_THRESH, nms_thresh=NMS_THRESH)
+            self.write_results(result_dir, names, boxes, frame_off.cpu())
+
     def evaluation_process(self):
         self.model.eval()
         state_dict = torch.load(self.cfg.Val.model_path, map_location='cpu')
@@ -168,6 +201,14 @@ class RetinaNetOperator(BaseOperator):
             raise RuntimeError("no validation data: %s/val/images does not exist" % self.cfg.data_root)
         result_dir = getattr(self.cfg.Val, "result_dir", './results/')
         os.makedirs(result_dir, exist_ok=True)
+        # builder-defined, opt-in (the config modules do not carry the key): cfg.Val.device_batch = N >= 1 runs the batched
+        # path on raw frames; absent or 0 is the per-frame loop below
+        device_batch = int(getattr(self.cfg.Val, "device_batch", 0) or 0)
+        if device_batch >= 1:
+            with torch.no_grad():
+                self.evaluate_batched(device_batch, result_dir)
+            print('Done !!!')
+            return
         step = 0
         with torch.no_grad():
             for data in self.validation_loader:

@@ -1984,6 +1984,69 @@ def retina_decode(logits, loc, anchors, score_thr=0.1):
     return rows, count
 
 
+RETINA_DECODE_CHUNK = 256     # RR_RETINA_DECODE_CHUNK: anchors of one workgroup of rr_retina_decode_frames
+
+
+def retina_decode_frames(logits, loc, anchors, score_thr=0.1, k=None, rows=None):
+    """rr_retina_decode_frames: retina_decode with an image's anchors spread over workgroups.  logits [B,A,C], loc [B,A,4],
+    anchors [A,4] -> (rows [B,k,6], count int32 [B]); k defaults to A.  The first min(count[f], k) rows of a frame are
+    retina_decode's; count[f] is the true number of candidates also above k.  rows (optional): the buffer to write into —
+    what lies behind min(count[f], k) stays as it was (a fresh buffer is zero-filled)."""
+    _C.require_cuda(logits, loc, anchors, rows)
+    logits, loc, anchors = logits.contiguous().float(), loc.contiguous().float(), anchors.contiguous().float()
+    b, a, c = logits.shape
+    assert tuple(loc.shape) == (b, a, 4) and tuple(anchors.shape) == (a, 4)
+    k = a if k is None else int(k)
+    if rows is None:
+        rows = torch.zeros((b, k, 6), dtype=torch.float32, device=logits.device)
+    assert tuple(rows.shape) == (b, k, 6) and rows.dtype == torch.float32 and rows.is_contiguous()
+    count = torch.zeros((b,), dtype=torch.int32, device=logits.device)
+    if a > 0 and b > 0:
+        ws = torch.empty(_C.fn("rr_retina_decode_frames_workspace_bytes")(b, a), dtype=torch.uint8, device=logits.device)
+        _C.check(_C.fn("rr_retina_decode_frames")(_C.ptr(logits), _C.ptr(loc), _C.ptr(anchors), b, a, c, float(score_thr),
+                                                  _C.ptr(rows), k, _C.ptr(count), _C.ptr(ws), _C.stream()),
+                 "rr_retina_decode_frames")
+    return rows, count
+
+
+def nms_frames(rows6, frame_off, max_rows, thresh, inclusive=False):
+    """rr_nms_frames: the reference's hard NMS ("+1" IoU; suppression at IoU > thresh, with inclusive at IoU >= thresh) for
+    every frame of a batch.  rows6 [R,6] = packed score-descending x,y,w,h,score,cls rows (sort_frames_by_score with
+    out_off), frame_off int32 [B+1], max_rows >= the longest frame, R >= B * max_rows.
+    -> (keep int32 [R]: keep[frame_off[f] + j] = j-th kept row of frame f, local to the frame; kept int32 [B])."""
+    _C.require_cuda(rows6, frame_off)
+    assert rows6.dim() == 2 and rows6.shape[1] == 6 and rows6.dtype == torch.float32 and rows6.is_contiguous()
+    assert frame_off.dtype == torch.int32 and frame_off.dim() == 1 and frame_off.numel() >= 1 and frame_off.is_contiguous()
+    b, max_rows = frame_off.numel() - 1, int(max_rows)
+    if not 0 <= max_rows <= DETECT_MAX_ROWS:
+        raise ValueError("nms_frames: %d rows per frame (limit %d)" % (max_rows, DETECT_MAX_ROWS))
+    assert rows6.shape[0] >= b * max_rows
+    dev = rows6.device
+    keep = torch.empty(rows6.shape[0], dtype=torch.int32, device=dev)
+    kept = torch.zeros(b, dtype=torch.int32, device=dev)
+    ws = torch.empty(_C.fn("rr_nms_frames_workspace_bytes")(b, max_rows), dtype=torch.uint8, device=dev)
+    _C.check(_C.fn("rr_nms_frames")(_C.ptr(rows6), _C.ptr(frame_off), b, max_rows, float(thresh),
+                                    int(bool(inclusive)), _C.ptr(ws), _C.ptr(keep), _C.ptr(kept), _C.stream()), "rr_nms_frames")
+    return keep, kept
+
+
+def pack_frames(rows6, frame_off, keep, kept, max_rows, out_rows=None):
+    """rr_pack_frames: the rows nms_frames kept, frames back to back, each in its score order -> (out6 [out_rows,6], out_off
+    int32 [B+1] = exclusive prefix of kept).  out_rows defaults to rows6's row count; the caller slices by out_off[-1]."""
+    _C.require_cuda(rows6, frame_off, keep, kept)
+    b, max_rows = frame_off.numel() - 1, int(max_rows)
+    assert rows6.dim() == 2 and rows6.shape[1] == 6 and rows6.dtype == torch.float32 and rows6.is_contiguous()
+    assert keep.dtype == torch.int32 and keep.numel() == rows6.shape[0] and keep.is_contiguous()
+    assert kept.dtype == torch.int32 and kept.numel() == b and kept.is_contiguous()
+    assert frame_off.dtype == torch.int32 and frame_off.is_contiguous() and rows6.shape[0] >= b * max_rows
+    out_rows = rows6.shape[0] if out_rows is None else int(out_rows)
+    out6 = torch.empty((out_rows, 6), dtype=torch.float32, device=rows6.device)
+    out_off = torch.empty(b + 1, dtype=torch.int32, device=rows6.device)
+    _C.check(_C.fn("rr_pack_frames")(_C.ptr(rows6), _C.ptr(frame_off), _C.ptr(keep), _C.ptr(kept), b, max_rows, _C.ptr(out6),
+                                     out_rows, _C.ptr(out_off), _C.stream()), "rr_pack_frames")
+    return out6, out_off
+
+
 class _OpsModule(types.ModuleType):
     """`ops.BF16` (read / assign) = this thread's arithmetic switch."""
 

@@ -17,8 +17,14 @@ flipped and plain, auto_test=True), the per-frame path DeviceValLoader -> Center
 against detect_frames_centernet; fp32 only (CenterNet has no bf16 scope).  Random weights keep all 250 boxes of each of the
 twelve passes: 3000 rows per frame.
 
+--retinanet measures RetinaNet (retinanet_config: resnet50, one scale, hard NMS at 0.3; fp32 only): the per-frame path
+DeviceValLoader -> RetinaNetOperator.evaluate_images -> save_result against detect_frames_retinanet.  With random weights
+every anchor scores near 0.5 and passes the reference's 0.1, more candidates than the score sort holds: the tool picks, from
+one model pass on the first frames, the score threshold that leaves at most --rows candidates in any of them, uses it on
+both paths (the per-frame path reads the operator module's SCORE_THRESH) and records it with the counts.
+
   python tools/bench_detect.py [--frames 32] [--window-frames 8] [--windows 3] [--batches 1,2,4] [--modes f32,bf16]
-                               [--nms] [--centernet] [--out profiles/detect.json]"""
+                               [--nms] [--centernet | --retinanet [--rows 1000]] [--out profiles/detect.json]"""
 import argparse
 import copy
 import json
@@ -82,6 +88,8 @@ def main(argv=None):
     ap.add_argument("--modes", default="f32,bf16")
     ap.add_argument("--nms", action="store_true", help="auto_test=False: score filter and Soft-NMS (default: the config's raw mode)")
     ap.add_argument("--centernet", action="store_true", help="CenterNet (centernet_config) instead of RRNet; fp32 only")
+    ap.add_argument("--retinanet", action="store_true", help="RetinaNet (retinanet_config) instead of RRNet; fp32 only")
+    ap.add_argument("--rows", type=int, default=1000, help="--retinanet: candidates per frame the picked threshold leaves")
     ap.add_argument("--backbone", default=None, help="override cfg.Model.backbone (rehearsals)")
     ap.add_argument("--out")
     args = ap.parse_args(argv)
@@ -92,7 +100,14 @@ def main(argv=None):
         raise SystemExit("tools/bench_detect.py measures on the GPU; there is nothing to measure without one")
     from rrnet_amd.datasets.augment import DeviceValLoader, chain_params
     from rrnet_amd.datasets.frames import SizeBucketedFrames
-    if args.centernet:
+    assert not (args.centernet and args.retinanet), "--centernet or --retinanet, not both"
+    if args.retinanet:
+        from rrnet_amd.configs.retinanet_config import Config
+        from rrnet_amd.inference import RetinaNetFrameDetector as Detector
+        from rrnet_amd.operators import retinanet_operator as retina_mod
+        Operator = retina_mod.RetinaNetOperator
+        args.modes = "f32"
+    elif args.centernet:
         from rrnet_amd.configs.centernet_config import Config
         from rrnet_amd.inference import CenterNetFrameDetector as Detector
         from rrnet_amd.operators.centernet_operator import CenterNetOperator as Operator
@@ -104,10 +119,13 @@ def main(argv=None):
 
     pool = GeneratedFrames(args.frames)
     out_dir = tempfile.mkdtemp(prefix="bench_detect_")
-    result = {"metric": "frames/sec, raw frame -> result file (multi-scale %s detection)"
-                        % ("CenterNet flip" if args.centernet else "RRNet"), "unit": "frames/sec",
+    result = {"metric": "frames/sec, raw frame -> result file (%s detection)"
+                        % ("single-scale RetinaNet" if args.retinanet else "multi-scale CenterNet flip" if args.centernet
+                           else "multi-scale RRNet"), "unit": "frames/sec",
               "higher_is_better": True, "data": "generated %dx%d frames, pool of %d" % (FRAME_W, FRAME_H, args.frames),
-              "weights": "random: all %s boxes of every %s survive, the worst case for the tail and the writer"
+              "weights": "random: the score threshold is picked so that at most %d candidates of a frame survive" % args.rows
+                         if args.retinanet else
+                         "random: all %s boxes of every %s survive, the worst case for the tail and the writer"
                          % (("250", "pass (two per scale)") if args.centernet else ("1500", "scale")),
               "windows": args.windows, "window_frames": args.window_frames, "modes": {}}
 
@@ -117,20 +135,33 @@ def main(argv=None):
             cfg.Model.backbone = args.backbone
         if mode == "bf16":
             cfg.Model.bf16 = True
-        if args.nms:
+        if args.retinanet:
+            cfg.Train.pretrained = False
+        elif args.nms:
             cfg.Val.auto_test = False
-        nms = not cfg.Val.auto_test
+        nms = True if args.retinanet else not cfg.Val.auto_test
         torch.manual_seed(219)
         det = Detector(cfg)
         params = chain_params(cfg.Val.transforms)
         ns = types.SimpleNamespace(cfg=cfg, model=det.model)
-        if args.centernet:
+        if args.retinanet:
+            from rrnet_amd.modules.anchor import Anchors
+            ns.anchor_maker, ns._anchor_sets, ns._nms_rows = Anchors(sizes=(16, 64, 128)), {}, Operator._nms_rows
+            ns.make_anchor = types.MethodType(Operator.make_anchor, ns)
+            first = next(iter(SizeBucketedFrames(Window(pool, 0, max(int(v) for v in args.batches.split(","))), 64,
+                                                 num_workers=8)))[0]
+            score_thr, at_thr = det.threshold_for_rows(first, args.rows)
+            retina_mod.SCORE_THRESH = score_thr                          # what evaluate_images decodes with
+            del first
+        elif args.centernet:
             ns.transform_bbox = types.MethodType(Operator.transform_bbox, ns)
             ns._ext_nms = Operator._ext_nms
         else:
             ns.generate_bbox = types.MethodType(Operator.generate_bbox, ns)
             ns._ext_nms, ns._ext_nms_device = Operator._ext_nms, Operator._ext_nms_device
-        entry = {"scales": list(cfg.Val.scales), "nms": nms, "backbone": cfg.Model.backbone}
+        entry = {"scales": [1] if args.retinanet else list(cfg.Val.scales), "nms": nms, "backbone": cfg.Model.backbone}
+        if args.retinanet:
+            entry.update(score_thr=score_thr, candidates_at_threshold=at_thr, rows_asked=args.rows)
 
         def per_frame_window(w):
             """The parent's path: one frame at a time, D2H per frame, save_result's per-row loop."""
@@ -140,6 +171,7 @@ def main(argv=None):
                 for imgs, _, names in DeviceValLoader(Window(pool, w * args.window_frames, args.window_frames), params,
                                                       num_workers=8):
                     pred = Operator.evaluate_images(ns, imgs)
+                    pred = pred[0] if args.retinanet else pred           # RetinaNet returns one tensor per image
                     t1 = time.perf_counter()
                     Operator.save_result(os.path.join(out_dir, names[0] + ".txt"), pred)
                     writer += time.perf_counter() - t1
@@ -160,11 +192,17 @@ def main(argv=None):
             for frames_u8, names in SizeBucketedFrames(Window(pool, w * args.window_frames, args.window_frames), batch,
                                                        num_workers=8):
                 timer("start")
-                pred, frame_off = det.detect(frames_u8, nms=nms, timer=timer)
+                if args.retinanet:
+                    pred, frame_off = det.detect(frames_u8, score_thr=score_thr, timer=timer)
+                else:
+                    pred, frame_off = det.detect(frames_u8, nms=nms, timer=timer)
                 rows, off = pred.cpu().numpy(), frame_off.cpu().tolist()
                 t1 = time.perf_counter()
-                for i, name in enumerate(names):
-                    Operator.write_results(os.path.join(out_dir, name + ".txt"), rows[off[i]:off[i + 1]])
+                if args.retinanet:
+                    Operator.write_results(out_dir, names, rows, off)
+                else:
+                    for i, name in enumerate(names):
+                        Operator.write_results(os.path.join(out_dir, name + ".txt"), rows[off[i]:off[i + 1]])
                 writer += time.perf_counter() - t1
                 boxes += rows.shape[0]
             torch.cuda.synchronize()

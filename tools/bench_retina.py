@@ -1,11 +1,16 @@
 """Times RetinaNet's criterion and decode kernels against the same chains written in plain torch ops on the device.
 
-  python tools/bench_retina.py [--batch 2] [--size 512 512] [--boxes 100] [--classes 10] [--iters 50] [--out profiles/retina.json]
+  python tools/bench_retina.py [--batch 2] [--size 512 512] [--boxes 100] [--classes 10] [--iters 50] [--nms-frames 4]
+                               [--out profiles/retina.json]
 
 criterion: RF.retina_criterion forward + backward (rr_retina_assign, rr_retina_loss_fwd, rr_retina_loss_bwd) against the
 per-image loop of tensor operations the reference's operator runs (IoU table, max, masks, focal loss, smooth-L1, autograd).
 decode: rr_retina_decode for the batch against the per-image chain of tensor operations (sigmoid, max, mask, gather, exp,
-stack).  Times are medians of HIP-event intervals after a warm-up; the result is a report, nothing is asserted."""
+stack).  decode_frames: rr_retina_decode_frames (an image's anchors over many workgroups) beside rr_retina_decode (one
+workgroup per image) at the shape above and at B = 1 / 4 on the 192 888 anchors of a 1360x765 frame.  nms_frames:
+rr_nms_frames for B frames beside B calls of rr_nms_sorted (without the read of num_out that its callers add) at 1000 and
+8000 score-ordered rows per frame.  Times are medians of HIP-event intervals after a warm-up; the result is a report,
+nothing is asserted."""
 import argparse
 import json
 import os
@@ -69,6 +74,58 @@ def torch_decode(cls_preds, loc_preds, anchors):
     return out
 
 
+def clustered_rows(n, seed):
+    """n score-descending x,y,w,h,score,class rows: clusters of about four overlapping boxes on a quarter-pixel grid."""
+    g = np.random.default_rng(seed)
+    centres = g.uniform(0, 40.0 * np.sqrt(n), (max(n // 4, 1), 2))
+    rows = np.zeros((n, 6), dtype=np.float32)
+    rows[:, 0:2] = np.round((centres[g.integers(0, len(centres), n)] + g.uniform(-6, 6, (n, 2))) * 4) / 4
+    rows[:, 2:4] = np.round(g.uniform(12, 36, (n, 2)) * 4) / 4
+    rows[:, 4], rows[:, 5] = g.uniform(0.1, 1.0, n), g.integers(1, 11, n)
+    return rows[np.argsort(-rows[:, 4], kind="stable")]
+
+
+def bench_decode_frames(report, key, cls, loc, anchors, iters):
+    from rrnet_amd import ops
+    rows, count = ops.retina_decode(cls, loc, anchors)
+    rows_f, count_f = ops.retina_decode_frames(cls, loc, anchors)
+    n = count.tolist()
+    same = torch.equal(count, count_f) and all(torch.equal(rows[i, :k], rows_f[i, :k]) for i, k in enumerate(n))
+    one, _ = timed(lambda: ops.retina_decode(cls, loc, anchors), iters)
+    many, _ = timed(lambda: ops.retina_decode_frames(cls, loc, anchors), iters)
+    report[key] = {"batch": cls.size(0), "anchors": cls.size(1), "kept": n, "same_rows": bool(same), "decode_ms": one,
+                   "decode_frames_ms": many, "speedup": one / many}
+
+
+def bench_nms_frames(report, key, b, n, iters):
+    from rrnet_amd import _C, ops
+    dev = torch.device("cuda", 0)
+    frames = [torch.from_numpy(clustered_rows(n, 100 + i)).to(dev) for i in range(b)]
+    packed = torch.cat(frames)
+    off = torch.arange(b + 1, dtype=torch.int32, device=dev) * n
+    xyxy = [f.clone() for f in frames]
+    for t in xyxy:
+        t[:, 2:4] += t[:, 0:2]
+    ws = torch.empty(_C.fn("rr_nms_workspace_bytes")(n), dtype=torch.uint8, device=dev)
+    keep1 = torch.empty((b, n), dtype=torch.int32, device=dev)
+    num1 = torch.zeros(b, dtype=torch.int32, device=dev)
+    f_sorted = _C.fn("rr_nms_sorted")
+
+    def sequential():
+        for i in range(b):
+            _C.check(f_sorted(_C.ptr(xyxy[i]), n, 6, 0.3, 0, _C.ptr(ws), _C.ptr(keep1[i]), _C.ptr(num1[i:]), _C.stream()),
+                     "rr_nms_sorted")
+
+    sequential()
+    keep, kept = ops.nms_frames(packed, off, n, 0.3)
+    same = torch.equal(kept, num1) and all(torch.equal(keep[i * n:i * n + k], keep1[i, :k]) for i, k in enumerate(kept.tolist()))
+    seq, _ = timed(sequential, iters)
+    bat, _ = timed(lambda: ops.nms_frames(packed, off, n, 0.3), iters)
+    pack, _ = timed(lambda: ops.pack_frames(packed, off, keep, kept, n), iters)
+    report[key] = {"frames": b, "rows_per_frame": n, "kept": kept.tolist(), "same_indices": bool(same),
+                   "nms_sorted_calls_ms": seq, "nms_frames_ms": bat, "pack_frames_ms": pack, "speedup": seq / bat}
+
+
 def timed(fn, iters, warmup=10):
     for _ in range(warmup):
         fn()
@@ -91,6 +148,7 @@ def main(argv=None):
     ap.add_argument("--boxes", type=int, default=100)
     ap.add_argument("--classes", type=int, default=10)
     ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--nms-frames", type=int, default=4, help="frames of the rr_nms_frames comparison")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "retina.json"))
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
@@ -145,6 +203,15 @@ def main(argv=None):
         for name, fn in (("decode_hip_ms", lambda: ops.retina_decode(cd, ld, anchors)),
                          ("decode_torch_ms", lambda: torch_decode(cd, ld, anchors))):
             report[name], report[name.replace("_ms", "_min_ms")] = timed(fn, args.iters)
+        bench_decode_frames(report, "decode_frames", cd, ld, anchors, args.iters)
+        big = Anchors(sizes=(16, 64, 128))((765, 1360)).to(dev)                # a 1360x765 VisDrone frame: 192 888 anchors
+        for bb in (1, 4):
+            lg = (torch.randn((bb, big.size(0), c), generator=g) * 2.0 - 3.0).to(dev)
+            lo = (torch.randn((bb, big.size(0), 4), generator=g) * 0.5).to(dev)
+            bench_decode_frames(report, "decode_frames_1360x765_b%d" % bb, lg, lo, big, args.iters)
+            del lg, lo
+        for n in (1000, 8000):
+            bench_nms_frames(report, "nms_frames_%d_rows" % n, args.nms_frames, n, args.iters if n <= 1000 else 10)
     report["criterion_speedup"] = report["criterion_torch_ms"] / report["criterion_hip_ms"]
     report["decode_speedup"] = report["decode_torch_ms"] / report["decode_hip_ms"]
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -12,7 +12,18 @@ without either the config decides.  --random-weights runs without a checkpoint (
 
 --config centernet_config runs CenterNet through rrnet_amd.inference.detect_frames_centernet and writes the integer lines
 of CenterNetOperator.save_result.  Every scale is run flipped and plain in one model pass, as the reference's evaluation
-does (--no-flip: plain only).  CenterNet is fp32 only: --bf16 is refused with it."""
+does (--no-flip: plain only).  CenterNet is fp32 only: --bf16 is refused with it.
+
+--config retinanet_config runs RetinaNet through rrnet_amd.inference.detect_frames_retinanet (single scale: decode, score
+sort, hard NMS at 0.3) and writes the truncated integer lines of RetinaNetOperator.save_result:
+
+  python tools/detect.py --config retinanet_config --checkpoint ckp.pth --images DIR --out DIR [--backbone resnet50]
+                         [--batch 4] [--score-thr 0.1] [--random-weights]
+
+RetinaNet is fp32 only and its evaluation has one scale, no flip and always the NMS: --bf16, --flip / --no-flip, --scales and
+--nms / --raw are refused with it.  With --random-weights every anchor scores near 0.5, more candidates than the score sort
+holds; unless --score-thr is given the tool then picks, from the first batch, the threshold that keeps at most 1000
+anchors of a frame, and prints it."""
 import argparse
 import copy
 import importlib
@@ -23,7 +34,8 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-CONFIGS = ("rrnet_config", "rrnet_fillduck_config", "centernet_config")
+CONFIGS = ("rrnet_config", "rrnet_fillduck_config", "centernet_config", "retinanet_config")
+RANDOM_WEIGHT_ROWS = 1000            # retinanet_config --random-weights without --score-thr: anchors of a frame that stay
 
 
 def load_config(name):
@@ -44,13 +56,21 @@ def main(argv=None):
     mode.add_argument("--raw", action="store_true")
     mode.add_argument("--nms", action="store_true")
     ap.add_argument("--bf16", action="store_true")
-    ap.add_argument("--flip", dest="flip", action="store_true", default=True,
+    ap.add_argument("--flip", dest="flip", action="store_true", default=None,
                     help="CenterNet: every scale flipped and plain, as the reference evaluates (default)")
     ap.add_argument("--no-flip", dest="flip", action="store_false", help="CenterNet: the plain image only")
     ap.add_argument("--random-weights", action="store_true")
     ap.add_argument("--workers", type=int, default=8)
+    ap.add_argument("--backbone", help="RetinaNet: override cfg.Model.backbone (resnet10 / resnet50 / resnet101)")
+    ap.add_argument("--score-thr", type=float, help="RetinaNet: the candidate threshold (default 0.1)")
     args = ap.parse_args(argv)
     cfg = load_config(args.config)
+    retinanet = args.config.startswith("retinanet")
+    if not retinanet and (args.backbone is not None or args.score_thr is not None):
+        raise SystemExit("--backbone / --score-thr belong to --config retinanet_config")
+    if retinanet:
+        return main_retinanet(args, cfg)
+    args.flip = True if args.flip is None else args.flip
     if (args.checkpoint is None) == (not args.random_weights):
         raise SystemExit("give --checkpoint FILE or --random-weights (one of them)")
     centernet = args.config.startswith("centernet")
@@ -98,6 +118,51 @@ def main(argv=None):
     dt = time.perf_counter() - t0
     print("%d frames, %d boxes -> %s in %.2f s (%.2f frames/s, %s, %d scales, batch %d%s)"
           % (frames_done, boxes_done, args.out, dt, frames_done / dt, "nms" if nms else "raw", len(scales), args.batch,
+             ", random weights" if args.random_weights else ""))
+
+
+def main_retinanet(args, cfg):
+    if args.bf16:
+        raise SystemExit("--bf16: RetinaNet runs in fp32 only")
+    if args.flip is not None:
+        raise SystemExit("--flip / --no-flip: RetinaNet's evaluation has no flipped pass")
+    if args.nms or args.raw:
+        raise SystemExit("--nms / --raw: RetinaNet's evaluation always ends in its hard NMS at 0.3; there is no raw mode")
+    if args.scales:
+        raise SystemExit("--scales: RetinaNet's evaluation runs at the frames' own size only")
+    if (args.checkpoint is None) == (not args.random_weights):
+        raise SystemExit("give --checkpoint FILE or --random-weights (one of them)")
+    if args.backbone:
+        cfg.Model.backbone = args.backbone
+    cfg.Train.pretrained = False                          # the weights come from --checkpoint (or stay random)
+
+    import torch
+    from rrnet_amd import inference
+    from rrnet_amd.datasets.frames import FrameFolder, SizeBucketedFrames
+    from rrnet_amd.operators.retinanet_operator import RetinaNetOperator
+    if not torch.cuda.is_available():
+        raise SystemExit("tools/detect.py needs the GPU (there is no CPU path)")
+    folder = FrameFolder(args.images)
+    if len(folder) == 0:
+        raise SystemExit("no images in %s" % args.images)
+    os.makedirs(args.out, exist_ok=True)
+    torch.manual_seed(219)
+    detector = inference.RetinaNetFrameDetector(cfg, None if args.random_weights else args.checkpoint)
+    score_thr = 0.1 if args.score_thr is None else args.score_thr
+    pick = args.random_weights and args.score_thr is None
+    t0, frames_done, boxes_done = time.perf_counter(), 0, 0
+    for frames_u8, names in SizeBucketedFrames(folder, args.batch, num_workers=args.workers):
+        if pick:
+            score_thr, counts = detector.threshold_for_rows(frames_u8, RANDOM_WEIGHT_ROWS)
+            print("random weights: score threshold %.9g keeps %s anchors of the first batch's frames" % (score_thr, counts))
+            pick = False
+        boxes, frame_off = detector.detect(frames_u8, score_thr=score_thr)
+        RetinaNetOperator.write_results(args.out, names, boxes, frame_off.cpu())             # one copy per batch
+        frames_done += len(names)
+        boxes_done += boxes.shape[0]
+    dt = time.perf_counter() - t0
+    print("%d frames, %d boxes -> %s in %.2f s (%.2f frames/s, score > %g, batch %d%s)"
+          % (frames_done, boxes_done, args.out, dt, frames_done / dt, score_thr, args.batch,
              ", random weights" if args.random_weights else ""))
 
 
