@@ -596,6 +596,37 @@ int rr_augment_frames_pasted(const unsigned char *src, long src_bytes, const int
                              long scratch_stride, float *out, int b, int out_h, int out_w, int stages,
                              hipStream_t stream);
 
+/* ColorJitter in front of the chain (datasets/transforms/transforms.py:120-130, functional.py:159-174: PIL's
+ *   ImageEnhance.Brightness, Contrast, Color on the uint8 frame, before MultiScale).  Each stage is PIL's Image.blend,
+ *   float32  t = (float)d + alpha*(float)(v - d)  (a multiply, then an add), 0 at t <= 0, 255 at t >= 255, truncated
+ *   otherwise, with d = 0 (brightness), d = m, the rounded grey mean of the brightness-adjusted WHOLE frame (contrast),
+ *   d = L of the pixel itself (colour); L = (r*19595 + g*38470 + b*7471 + 0x8000) >> 16.  Bit-exact with PIL.
+ *   PRECONDITION of all three entries: every frame ships its whole source frame as its window (window origin 0, 0;
+ *   window height, width = source height, width), because m is a mean over the whole frame.
+ * rr_jitter_gray_mean: for every frame i, sums[i] = the integer sum of L over the frame after brightness factors[i,0]
+ *   (zeroed here on the stream, one 64-bit integer atomic per workgroup: the same words run to run) and
+ *   gray_mean[i] = (2*sums[i] + N) / (2*N), N the frame's pixels = int(mean + 0.5) as PIL forms it.
+ *   src, src_bytes, params: as rr_augment_frames.  factors [b,3] float = brightness, contrast, colour factor per frame.
+ *   sums [b] 64-bit words (workspace, 8-byte aligned), gray_mean [b] int32.  max_pixels >= every frame's height * width
+ *   (it sizes the grid; pixels beyond it would not be summed).  b <= 65535.
+ * rr_augment_frames_jitter, rr_augment_frames_pasted_jitter: rr_augment_frames and rr_augment_frames_pasted with the
+ *   jitter applied to each of the four source taps before PIL's fixed-point resize (exact, since the jitter precedes the
+ *   resize).  factors as above; gray_mean [b] int32 from rr_jitter_gray_mean (clamped to 0..255 where it is read).
+ *   Ignore rectangles and padding are what they were: the chain writes them after ToTensor.  Pasted objects read the
+ *   jittered canvas.  With factors (1, 1, 1) the results equal the unjittered entries bit for bit. */
+int rr_jitter_gray_mean(const unsigned char *src, long src_bytes, const int *params, const float *factors,
+                        unsigned long long *sums, int *gray_mean, int b, long max_pixels, hipStream_t stream);
+int rr_augment_frames_jitter(const unsigned char *src, long src_bytes, const int *params, const int *rects,
+                             const int *rect_off, const int *taps, int ntaps, const float *mean, const float *stdv,
+                             const float *factors, const int *gray_mean, float *out, int b, int out_h, int out_w,
+                             hipStream_t stream);
+int rr_augment_frames_pasted_jitter(const unsigned char *src, long src_bytes, const int *params, const int *rects,
+                                    const int *rect_off, const int *taps, int ntaps, const int *pastes,
+                                    const int *paste_off, const float *mean, const float *stdv, const float *factors,
+                                    const int *gray_mean, float *canvas, long canvas_stride, float *scratch,
+                                    long scratch_stride, float *out, int b, int out_h, int out_w, int stages,
+                                    hipStream_t stream);
+
 /* ---- inference post-process (config 5: decode -> re-regression -> Soft-NMS) ------------------ *
  * rr_refine_boxes: operators/rrnet_operator.py:188-209 `generate_bbox` (stage-2 boxes from the packed RoIs
  *   [r,5] = image,x1,y1,x2,y2 in feature coordinates, the regression [r,4], scores, classes), the score filter

@@ -10,8 +10,12 @@
 // Order per pixel (datasets/transforms/transforms.py:60-72, functional.py:290-313): crop -> padding (0, normalised; the
 // reference pads right/bottom after the flip and before Normalize) -> un-flip -> ignore rectangle (mean, normalised:
 // +0.0) -> bilinear sample.
+// rr_augment_frames_jitter is the same gather with ColorJitter (jitter.h) applied to each of the four source taps before
+// the resize: the jitter is the first transform of the chain, so the resize reads jittered uint8 pixels.  It is a second
+// instantiation of the same body; the unjittered kernel compiles to what it was without it.
 #include "common.h"
 #include "rrnet_hip.h"
+#include "jitter.h"
 
 #define AUG_THREADS 256
 #define AUG_PIX 4                 // pixels per thread: 12 floats = three 16-byte stores
@@ -24,10 +28,25 @@ enum { P_SRC_H, P_SRC_W, P_WIN_Y0, P_WIN_X0, P_WIN_H, P_WIN_W, P_DST_H, P_DST_W,
 __device__ __forceinline__ int aug_clip8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 __device__ __forceinline__ int aug_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
+// one jittered source tap
+__device__ __forceinline__ void aug_tap(const uint8_t *__restrict__ src, long a, float fb, float fc, float fs, int m, int *t)
+{
+    t[0] = src[a], t[1] = src[a + 1], t[2] = src[a + 2];
+    jit_pixel(t[0], t[1], t[2], fb, fc, fs, m);
+}
+
+// what the jittered instantiation takes on top: nothing in the unjittered one, whose arguments stay what they were
+template <bool JIT> struct AugJitter {};
+template <> struct AugJitter<true> {
+    const float *factors;          // [b,3] brightness, contrast, colour
+    const int *gray_mean;          // [b] rr_jitter_gray_mean
+};
+
+template <bool JIT>
 __global__ __launch_bounds__(AUG_THREADS) void augment_frames_kernel(
     const uint8_t *__restrict__ src, long src_bytes, const int *__restrict__ params, const int *__restrict__ rects,
     const int *__restrict__ rect_off, const int *__restrict__ taps, int ntaps, const float *__restrict__ mean,
-    const float *__restrict__ stdv, float *__restrict__ out, long npix, int OH, int OW)
+    const float *__restrict__ stdv, float *__restrict__ out, long npix, int OH, int OW, AugJitter<JIT> jit)
 {
     __shared__ float lut[256 * 3];                       // lut[v*3 + c]
     for (int i = threadIdx.x; i < 256 * 3; i += AUG_THREADS) {
@@ -79,11 +98,28 @@ __global__ __launch_bounds__(AUG_THREADS) void augment_frames_kernel(
                     a10 = a10 < 0 ? 0 : (a10 > last ? last : a10);
                     a11 = a11 < 0 ? 0 : (a11 > last ? last : a11);
                     int v[3];
+                    if constexpr (!JIT) {
 #pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        const int h0 = aug_clip8(((int)src[a00 + c] * kx0 + (int)src[a01 + c] * kx1 + (1 << (AUG_PREC - 1))) >> AUG_PREC);
-                        const int h1 = aug_clip8(((int)src[a10 + c] * kx0 + (int)src[a11 + c] * kx1 + (1 << (AUG_PREC - 1))) >> AUG_PREC);
-                        v[c] = aug_clip8((h0 * ky0 + h1 * ky1 + (1 << (AUG_PREC - 1))) >> AUG_PREC);
+                        for (int c = 0; c < 3; ++c) {
+                            const int h0 = aug_clip8(((int)src[a00 + c] * kx0 + (int)src[a01 + c] * kx1 + (1 << (AUG_PREC - 1))) >> AUG_PREC);
+                            const int h1 = aug_clip8(((int)src[a10 + c] * kx0 + (int)src[a11 + c] * kx1 + (1 << (AUG_PREC - 1))) >> AUG_PREC);
+                            v[c] = aug_clip8((h0 * ky0 + h1 * ky1 + (1 << (AUG_PREC - 1))) >> AUG_PREC);
+                        }
+                    } else {                             // the same resize on jittered taps
+                        const float *f = jit.factors + (long)b * 3;
+                        const float fb = f[0], fc = f[1], fs = f[2];
+                        const int gm = aug_clampi(jit.gray_mean[b], 0, 255);
+                        int t00[3], t01[3], t10[3], t11[3];
+                        aug_tap(src, a00, fb, fc, fs, gm, t00);
+                        aug_tap(src, a01, fb, fc, fs, gm, t01);
+                        aug_tap(src, a10, fb, fc, fs, gm, t10);
+                        aug_tap(src, a11, fb, fc, fs, gm, t11);
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) {
+                            const int h0 = aug_clip8((t00[c] * kx0 + t01[c] * kx1 + (1 << (AUG_PREC - 1))) >> AUG_PREC);
+                            const int h1 = aug_clip8((t10[c] * kx0 + t11[c] * kx1 + (1 << (AUG_PREC - 1))) >> AUG_PREC);
+                            v[c] = aug_clip8((h0 * ky0 + h1 * ky1 + (1 << (AUG_PREC - 1))) >> AUG_PREC);
+                        }
                     }
                     r0 = lut[v[0] * 3], r1 = lut[v[1] * 3 + 1], r2 = lut[v[2] * 3 + 2];
                 }
@@ -114,8 +150,27 @@ extern "C" int rr_augment_frames(const unsigned char *src, long src_bytes, const
     const long npix = (long)b * out_h * out_w;
     const long blocks = (npix + (long)AUG_THREADS * AUG_PIX - 1) / ((long)AUG_THREADS * AUG_PIX);
     RR_CHECK_ARG(blocks <= 0x7fffffffL, "rr_augment_frames: too many pixels");
-    hipLaunchKernelGGL(augment_frames_kernel, dim3((unsigned)blocks), dim3(AUG_THREADS), 0, stream, src, src_bytes, params,
-                       rects, rect_off, taps, ntaps, mean, stdv, out, npix, out_h, out_w);
+    hipLaunchKernelGGL(augment_frames_kernel<false>, dim3((unsigned)blocks), dim3(AUG_THREADS), 0, stream, src, src_bytes,
+                       params, rects, rect_off, taps, ntaps, mean, stdv, out, npix, out_h, out_w, AugJitter<false>{});
     RR_CHECK_LAUNCH("rr_augment_frames");
+    return RR_OK;
+}
+
+extern "C" int rr_augment_frames_jitter(const unsigned char *src, long src_bytes, const int *params, const int *rects,
+                                        const int *rect_off, const int *taps, int ntaps, const float *mean,
+                                        const float *stdv, const float *factors, const int *gray_mean, float *out, int b,
+                                        int out_h, int out_w, hipStream_t stream)
+{
+    RR_CHECK_ARG(b > 0 && out_h > 0 && out_w > 0 && src_bytes >= 3 && ntaps > 0, "rr_augment_frames_jitter: bad dims");
+    RR_CHECK_ARG(src && params && rect_off && taps && mean && stdv && factors && gray_mean && out,
+                 "rr_augment_frames_jitter: null pointer");
+    RR_CHECK_ARG((reinterpret_cast<size_t>(out) & 15) == 0, "rr_augment_frames_jitter: out must be 16-byte aligned");
+    const long npix = (long)b * out_h * out_w;
+    const long blocks = (npix + (long)AUG_THREADS * AUG_PIX - 1) / ((long)AUG_THREADS * AUG_PIX);
+    RR_CHECK_ARG(blocks <= 0x7fffffffL, "rr_augment_frames_jitter: too many pixels");
+    hipLaunchKernelGGL(augment_frames_kernel<true>, dim3((unsigned)blocks), dim3(AUG_THREADS), 0, stream, src, src_bytes,
+                       params, rects, rect_off, taps, ntaps, mean, stdv, out, npix, out_h, out_w,
+                       AugJitter<true>{factors, gray_mean});
+    RR_CHECK_LAUNCH("rr_augment_frames_jitter");
     return RR_OK;
 }

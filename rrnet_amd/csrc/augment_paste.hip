@@ -17,8 +17,12 @@
 // pixel is  l0*(m0*a + m1*b) + l1*(m0*c + m1*d)  with r = rheight*(float)oy, y0 = (int)r, l1 = r - y0, l0 = 1 - l1
 // (likewise along x): torch's source indices exactly, its value within float32 rounding of the blend.
 // Every address is clamped into the frame's canvas / scratch slab; a record that does not fit its slab is skipped.
+// rr_augment_frames_pasted_jitter: the canvas stage, the one place that reads src, applies ColorJitter (jitter.h) to each
+// source tap before the resize; pasted objects then read the jittered canvas, as the reference's order implies.  The
+// unjittered canvas kernel compiles to what it was without it.
 #include "common.h"
 #include "rrnet_hip.h"
+#include "jitter.h"
 
 #define AUG_THREADS 256
 #define AUG_PIX 4                 // pixels per thread: 12 floats = three 16-byte stores
@@ -39,10 +43,25 @@ __device__ __forceinline__ bool pst_frame_fits(const int *P, long canvas_stride)
     return P[P_DST_H] > 0 && P[P_DST_W] > 0 && (long)P[P_DST_H] * P[P_DST_W] <= canvas_stride;
 }
 
+// one jittered source tap
+__device__ __forceinline__ void pst_tap(const uint8_t *__restrict__ src, long a, float fb, float fc, float fs, int m, int *t)
+{
+    t[0] = src[a], t[1] = src[a + 1], t[2] = src[a + 2];
+    jit_pixel(t[0], t[1], t[2], fb, fc, fs, m);
+}
+
+// what the jittered instantiation takes on top: nothing in the unjittered one, whose arguments stay what they were
+template <bool JIT> struct PstJitter {};
+template <> struct PstJitter<true> {
+    const float *factors;          // [b,3] brightness, contrast, colour
+    const int *gray_mean;          // [b] rr_jitter_gray_mean
+};
+
+template <bool JIT>
 __global__ __launch_bounds__(AUG_THREADS) void paste_canvas_kernel(
     const uint8_t *__restrict__ src, long src_bytes, const int *__restrict__ params, const int *__restrict__ rects,
     const int *__restrict__ rect_off, const int *__restrict__ taps, int ntaps, const int *__restrict__ paste_off,
-    const float *__restrict__ mean, float *__restrict__ canvas, long canvas_stride, int OH, int OW)
+    const float *__restrict__ mean, float *__restrict__ canvas, long canvas_stride, int OH, int OW, PstJitter<JIT> jit)
 {
     const int b = blockIdx.y;
     const int *P = params + (long)b * RR_AUGMENT_PARAMS;
@@ -90,11 +109,28 @@ __global__ __launch_bounds__(AUG_THREADS) void paste_canvas_kernel(
                     a10 = a10 < 0 ? 0 : (a10 > last ? last : a10);
                     a11 = a11 < 0 ? 0 : (a11 > last ? last : a11);
                     float v[3];
+                    if constexpr (!JIT) {
 #pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        const int h0 = pst_clip8(((int)src[a00 + c] * kx0 + (int)src[a01 + c] * kx1 + (1 << (AUG_PREC - 1))) >> AUG_PREC);
-                        const int h1 = pst_clip8(((int)src[a10 + c] * kx0 + (int)src[a11 + c] * kx1 + (1 << (AUG_PREC - 1))) >> AUG_PREC);
-                        v[c] = (float)pst_clip8((h0 * ky0 + h1 * ky1 + (1 << (AUG_PREC - 1))) >> AUG_PREC) / 255.0f;
+                        for (int c = 0; c < 3; ++c) {
+                            const int h0 = pst_clip8(((int)src[a00 + c] * kx0 + (int)src[a01 + c] * kx1 + (1 << (AUG_PREC - 1))) >> AUG_PREC);
+                            const int h1 = pst_clip8(((int)src[a10 + c] * kx0 + (int)src[a11 + c] * kx1 + (1 << (AUG_PREC - 1))) >> AUG_PREC);
+                            v[c] = (float)pst_clip8((h0 * ky0 + h1 * ky1 + (1 << (AUG_PREC - 1))) >> AUG_PREC) / 255.0f;
+                        }
+                    } else {                                // the same resize on jittered taps
+                        const float *f = jit.factors + (long)b * 3;
+                        const float fb = f[0], fc = f[1], fs = f[2];
+                        const int gm = pst_clampi(jit.gray_mean[b], 0, 255);
+                        int t00[3], t01[3], t10[3], t11[3];
+                        pst_tap(src, a00, fb, fc, fs, gm, t00);
+                        pst_tap(src, a01, fb, fc, fs, gm, t01);
+                        pst_tap(src, a10, fb, fc, fs, gm, t10);
+                        pst_tap(src, a11, fb, fc, fs, gm, t11);
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) {
+                            const int h0 = pst_clip8((t00[c] * kx0 + t01[c] * kx1 + (1 << (AUG_PREC - 1))) >> AUG_PREC);
+                            const int h1 = pst_clip8((t10[c] * kx0 + t11[c] * kx1 + (1 << (AUG_PREC - 1))) >> AUG_PREC);
+                            v[c] = (float)pst_clip8((h0 * ky0 + h1 * ky1 + (1 << (AUG_PREC - 1))) >> AUG_PREC) / 255.0f;
+                        }
                     }
                     r0 = v[0], r1 = v[1], r2 = v[2];
                 }
@@ -207,11 +243,12 @@ __global__ __launch_bounds__(AUG_THREADS) void paste_finish_kernel(
     }
 }
 
-extern "C" int rr_augment_frames_pasted(const unsigned char *src, long src_bytes, const int *params, const int *rects,
-                                        const int *rect_off, const int *taps, int ntaps, const int *pastes,
-                                        const int *paste_off, const float *mean, const float *stdv, float *canvas,
-                                        long canvas_stride, float *scratch, long scratch_stride, float *out, int b,
-                                        int out_h, int out_w, int stages, hipStream_t stream)
+// both entry points: factors == nullptr is the unjittered chain
+static int augment_frames_pasted(const unsigned char *src, long src_bytes, const int *params, const int *rects,
+                                 const int *rect_off, const int *taps, int ntaps, const int *pastes, const int *paste_off,
+                                 const float *mean, const float *stdv, const float *factors, const int *gray_mean,
+                                 float *canvas, long canvas_stride, float *scratch, long scratch_stride, float *out, int b,
+                                 int out_h, int out_w, int stages, hipStream_t stream)
 {
     RR_CHECK_ARG(b > 0 && out_h > 0 && out_w > 0 && src_bytes >= 3 && ntaps > 0, "rr_augment_frames_pasted: bad dims");
     RR_CHECK_ARG(src && params && rect_off && taps && pastes && paste_off && mean && stdv && canvas && scratch && out,
@@ -225,9 +262,14 @@ extern "C" int rr_augment_frames_pasted(const unsigned char *src, long src_bytes
     if (stages & 1) {
         const long blocks = (canvas_stride + per_block - 1) / per_block;
         RR_CHECK_ARG(blocks <= 0x7fffffffL && b <= 65535, "rr_augment_frames_pasted: canvas too large");
-        hipLaunchKernelGGL(paste_canvas_kernel, dim3((unsigned)blocks, (unsigned)b), dim3(AUG_THREADS), 0, stream, src,
-                           src_bytes, params, rects, rect_off, taps, ntaps, paste_off, mean, canvas, canvas_stride, out_h,
-                           out_w);
+        if (factors)
+            hipLaunchKernelGGL(paste_canvas_kernel<true>, dim3((unsigned)blocks, (unsigned)b), dim3(AUG_THREADS), 0, stream,
+                               src, src_bytes, params, rects, rect_off, taps, ntaps, paste_off, mean, canvas, canvas_stride,
+                               out_h, out_w, PstJitter<true>{factors, gray_mean});
+        else
+            hipLaunchKernelGGL(paste_canvas_kernel<false>, dim3((unsigned)blocks, (unsigned)b), dim3(AUG_THREADS), 0, stream,
+                               src, src_bytes, params, rects, rect_off, taps, ntaps, paste_off, mean, canvas, canvas_stride,
+                               out_h, out_w, PstJitter<false>{});
         RR_CHECK_LAUNCH("rr_augment_frames_pasted (canvas)");
     }
     if (stages & 2) {
@@ -244,4 +286,27 @@ extern "C" int rr_augment_frames_pasted(const unsigned char *src, long src_bytes
         RR_CHECK_LAUNCH("rr_augment_frames_pasted (finish)");
     }
     return RR_OK;
+}
+
+extern "C" int rr_augment_frames_pasted(const unsigned char *src, long src_bytes, const int *params, const int *rects,
+                                        const int *rect_off, const int *taps, int ntaps, const int *pastes,
+                                        const int *paste_off, const float *mean, const float *stdv, float *canvas,
+                                        long canvas_stride, float *scratch, long scratch_stride, float *out, int b,
+                                        int out_h, int out_w, int stages, hipStream_t stream)
+{
+    return augment_frames_pasted(src, src_bytes, params, rects, rect_off, taps, ntaps, pastes, paste_off, mean, stdv, nullptr,
+                                 nullptr, canvas, canvas_stride, scratch, scratch_stride, out, b, out_h, out_w, stages, stream);
+}
+
+extern "C" int rr_augment_frames_pasted_jitter(const unsigned char *src, long src_bytes, const int *params,
+                                               const int *rects, const int *rect_off, const int *taps, int ntaps,
+                                               const int *pastes, const int *paste_off, const float *mean,
+                                               const float *stdv, const float *factors, const int *gray_mean,
+                                               float *canvas, long canvas_stride, float *scratch, long scratch_stride,
+                                               float *out, int b, int out_h, int out_w, int stages, hipStream_t stream)
+{
+    RR_CHECK_ARG(factors && gray_mean, "rr_augment_frames_pasted_jitter: null pointer");
+    return augment_frames_pasted(src, src_bytes, params, rects, rect_off, taps, ntaps, pastes, paste_off, mean, stdv, factors,
+                                 gray_mean, canvas, canvas_stride, scratch, scratch_stride, out, b, out_h, out_w, stages,
+                                 stream);
 }

@@ -24,6 +24,7 @@ PER_FILE = {
     "psroi.hip": ["-ffp-contract=off"],
     "augment.hip": ["-ffp-contract=off"],
     "augment_paste.hip": ["-ffp-contract=off"],
+    "jitter.hip": ["-ffp-contract=off"],
     "evalmatch.hip": ["-ffp-contract=off"],
     "detect.hip": ["-ffp-contract=off"],
     "retina.hip": ["-ffp-contract=off"],

@@ -5,12 +5,16 @@ origin) from a generator keyed by (seed, rank, epoch, index), runs FillDuck's an
 annotations (and the road map) alone and emits the final annotation rows, the record rr_augment_frames needs, the paste
 plan and the source window the crop reads.  DeviceAugmentLoader ships the windows through pinned memory, one batch ahead
 on a copy stream (the event hand-over of HostFedDronesDET), and runs rr_augment_frames (rr_augment_frames_pasted for a
-batch with pastes, whose pasted samples ship their whole frame) + rr_ctnet_targets on the compute stream.
+batch with pastes, whose pasted samples ship their whole frame) + rr_ctnet_targets on the compute stream.  With
+ColorJitter in front of the chain the sampler also draws the three factors, every sample ships its whole frame, and
+rr_jitter_gray_mean (the grey mean PIL's contrast step needs) runs in front of the _jitter variant of either kernel.
 HostAugmentLoader runs the reference's chain on the host for the SAME decisions: it is what the device path is checked
 against, bit for bit except for pasted pixels (functional.apply_paste_plan states their bound).
 
 Deviations from the reference chain (configs/rrnet_config.py:40-49), see DESIGN.md "Data layer":
-  * ColorJitter is not part of it;
+  * ColorJitter is lowered only as the first transform (in front of MultiScale, or of ToTensor without MultiScale):
+    anywhere else it would see other pixels, another grey mean and another order of rounding; its factors come from a
+    generator keyed per sample, not from Python's global `random`;
   * FillDuck's draws come from a generator keyed per sample and attempt, not from the global torch generator;
   * where every box is larger than the crop the reference rescales the frame with F.interpolate
     (transforms.py:81-90); here the sampler redraws the MultiScale factor (and flip and origin) and counts it
@@ -23,8 +27,8 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from .transforms import (Compose, FillDuck, HorizontalFlip, MaskIgnore, MultiScale, Normalize, RandomCrop, ToHeatmap,
-                         ToTensor)
+from .transforms import (ColorJitter, Compose, FillDuck, HorizontalFlip, MaskIgnore, MultiScale, Normalize, RandomCrop,
+                         ToHeatmap, ToTensor)
 from .transforms import functional as F
 
 MAX_THREADS = 16
@@ -32,15 +36,23 @@ MIN_SCALE = 1.0
 P_WORDS = 16          # ops.AUGMENT_PARAMS
 T_WORDS = F.PASTE_WORDS   # ops.PASTE_WORDS
 FILL_DUCK_TAG = 0x46443031   # "FD01": keeps FillDuck's generator apart from the scale / flip / crop draws
+JITTER_TAG = 0x434a3031      # "CJ01": likewise for ColorJitter's three factors
 
 
 def chain_params(transforms):
     """Reads the parameters of the lowered chain out of a Compose of transform instances.  Anything the kernel does not
     implement is an error, not a silent difference."""
     p = dict(scales=(1,), flip_p=0.0, crop=None, keep_iou=0.5, mean=None, std=None, ignore_idx=None, ignore_mean=None,
-             scale_factor=4, cls_num=10, fill_duck=None)
+             scale_factor=4, cls_num=10, fill_duck=None, jitter=None)
     seen = []
-    for t in (transforms.transforms if isinstance(transforms, Compose) else transforms):
+    for k, t in enumerate(transforms.transforms if isinstance(transforms, Compose) else transforms):
+        if isinstance(t, ColorJitter):
+            if k != 0:
+                raise NotImplementedError("ColorJitter is lowered only as the first transform of the chain: behind %s it "
+                                          "would need another grey mean and another order of rounding"
+                                          % (seen[-1].__name__ if seen else "another ColorJitter"))
+            p["jitter"] = (tuple(t.brightness), tuple(t.contrast), tuple(t.saturation))
+            continue
         seen.append(type(t))
         if isinstance(t, MultiScale):
             p["scales"] = tuple(t.scale)
@@ -130,17 +142,26 @@ class _Rand:
 
 class Decision:
     """What the sampler decided for one sample."""
-    __slots__ = ("index", "scale", "flip", "dst_h", "dst_w", "crop_y0", "crop_x0", "annos", "rects", "redraws", "plan")
+    __slots__ = ("index", "scale", "flip", "dst_h", "dst_w", "crop_y0", "crop_x0", "annos", "rects", "redraws", "plan",
+                 "jitter")
 
     def key(self):
         plan = plan_of(self)
         return (self.index, self.scale, self.flip, self.dst_h, self.dst_w, self.crop_y0, self.crop_x0, self.redraws,
-                self.annos.numpy().tobytes(), self.rects.tobytes(), plan.key() if plan is not None else None)
+                self.annos.numpy().tobytes(), self.rects.tobytes(), plan.key() if plan is not None else None,
+                jitter_of(self))
 
 
 def plan_of(d):
     """The decision's FillDuck plan, or None (a chain without FillDuck, no road map, or a hand-built Decision)."""
     return getattr(d, "plan", None)
+
+
+def jitter_of(d):
+    """The decision's ColorJitter factors (brightness, contrast, saturation; Python floats that hold float32 values, the
+    precision PIL's blend and the kernel both compute in), or None (a chain without ColorJitter, a hand-built
+    Decision)."""
+    return getattr(d, "jitter", None)
 
 
 def n_pastes(d):
@@ -177,7 +198,10 @@ class AugmentSampler:
         rand = _Rand(rng)
         p = self.p
         d = Decision()
-        d.index, d.redraws, d.plan = int(index), 0, None
+        d.index, d.redraws, d.plan, d.jitter = int(index), 0, None, None
+        if p.get("jitter") is not None:                     # a generator of its own: the other draws stay what they are
+            cj_rng = np.random.default_rng([self.seed, self.rank, int(epoch), int(index), JITTER_TAG])
+            d.jitter = tuple(float(np.float32(cj_rng.uniform(lo, hi))) for lo, hi in p["jitter"])
         duck = p.get("fill_duck") if roadmap is not None else None
         for attempt in range(50):
             d.scale = p["scales"][int(rng.integers(0, len(p["scales"])))]
@@ -246,6 +270,7 @@ def pack_batch(items, src_out=None):
     rects, off = [], 0
     for i, (d, src_h, src_w, win, pix) in enumerate(items):
         assert pix.dtype == np.uint8 and pix.shape == (win[2], win[3], 3)
+        check_jitter_window(d, src_h, src_w, win)
         src[off:off + pix.size] = pix.reshape(-1)
         params[i] = param_record(d, src_h, src_w, win, off)
         off += pix.size
@@ -253,6 +278,24 @@ def pack_batch(items, src_out=None):
         rect_off[i + 1] = rect_off[i] + len(d.rects)
     rects = np.concatenate(rects, 0).astype(np.int32).reshape(-1, 4)
     return src[:max(total, 3)], params, rects, rect_off
+
+
+def check_jitter_window(d, src_h, src_w, win):
+    """Contrast blends towards the grey mean of the WHOLE frame: a jittered sample ships it."""
+    if jitter_of(d) is not None and tuple(int(v) for v in win[:4]) != (0, 0, int(src_h), int(src_w)):
+        raise ValueError("image index %d is colour-jittered and ships the window %s of its %dx%d frame; the grey mean "
+                         "needs the whole frame" % (d.index, tuple(win[:4]), src_w, src_h))
+
+
+def pack_jitter(items):
+    """items as for pack_batch -> (factors float32 [B,3], the largest frame in pixels): what rr_jitter_gray_mean and the
+    _jitter kernels take on top of pack_batch's records.  A sample without factors gets (1, 1, 1), the identity."""
+    factors = np.ones((len(items), 3), np.float32)
+    for i, (d, src_h, src_w, win, _) in enumerate(items):
+        check_jitter_window(d, src_h, src_w, win)
+        if jitter_of(d) is not None:
+            factors[i] = jitter_of(d)
+    return factors, max(int(it[3][2]) * int(it[3][3]) for it in items)
 
 
 def pack_pastes(decisions):
@@ -276,9 +319,11 @@ def pack_pastes(decisions):
 
 def host_chain(image, annotations, d, params, out_h, out_w):
     """The reference chain on the host for decision `d`: PIL image + int64 annotations -> float32 [3,out_h,out_w].
-    (resize -> to_tensor -> mask_ignore -> the decision's pastes -> flip -> pad/crop -> normalize; the annotations of
-    the batch are d.annos.)"""
+    (the decision's colour jitter -> resize -> to_tensor -> mask_ignore -> the decision's pastes -> flip -> pad/crop ->
+    normalize; the annotations of the batch are d.annos.)"""
     a = annotations.copy()
+    if jitter_of(d) is not None:
+        image = F.color_jitter(image, *d.jitter)
     img, a = F.resize((image, a), d.scale)[:2]
     img, t = F.img_to_tensor(img), F.annos_to_tensor(a)
     if params["ignore_idx"] is not None:
@@ -393,7 +438,12 @@ class DeviceAugmentLoader(_AugmentLoader):
     With FillDuck in the chain and road maps in the dataset, a sample whose plan has pastes ships its whole source frame
     and its paste table, and a batch with such a sample runs rr_augment_frames_pasted (its unpasted samples still ship
     windows; their pixels are bit-identical on either kernel).  Staging, device slots, the canvas and the scratch are
-    sized once, from the largest frame of the dataset at the largest scale."""
+    sized once, from the largest frame of the dataset at the largest scale.
+
+    With ColorJitter in the chain EVERY sample ships its whole frame (the contrast step needs its grey mean) and its
+    three factors, which travel in the meta block; get_batch() runs rr_jitter_gray_mean and then the _jitter variant of
+    the kernel the batch would have taken.  The factors are a function of (seed, rank, epoch, index) like every other
+    draw, so seek() and resume need nothing more."""
 
     def __init__(self, dataset, params, batch_size, **kw):
         super().__init__(dataset, params, batch_size, **kw)
@@ -405,23 +455,28 @@ class DeviceAugmentLoader(_AugmentLoader):
         # a crop of h x w reads at most h+1 rows and w+1 columns of the source at scale factors >= 1
         self.src_cap = b * (self.out_h + 2) * (self.out_w + 2) * 3
         self.pasting = params.get("fill_duck") is not None and bool(getattr(dataset, "with_road_map", False))
-        self.k_cap, self.canvas_pix, self.work = 0, 0, None
-        if self.pasting:
+        self.jitter = params.get("jitter") is not None
+        self.k_cap, self.canvas_pix, self.work, self.jitter_work = 0, 0, None, None
+        if self.pasting or self.jitter:
             from PIL import Image
             from rrnet_amd import ops
             sizes = set()
             for k in range(len(dataset)):
                 with Image.open(dataset.image_path(k)) as im:
                     sizes.add(im.size)
-            smax = max(params["scales"])
             self.src_cap = max(self.src_cap, b * max(w * h for w, h in sizes) * 3)
+        if self.jitter:
+            self.jitter_work = ops.jitter_workspace(b, self.device)
+        if self.pasting:
+            smax = max(params["scales"])
             self.canvas_pix = max(F.scaled_size(h, w, smax)[0] * F.scaled_size(h, w, smax)[1] for w, h in sizes)
             # total_n = max(int(factor * road pixels), 5) pastes per frame (functional.py:408)
             self.k_cap = b * max(int(params["fill_duck"]["factor"] * self.canvas_pix) + 1, 5)
             self.m_cap += 2 * (self.k_cap // b)             # a pair paste adds two rows
             # an object that does not fit its frame aborts the plan, so no object is larger than the largest frame
             self.work = ops.paste_workspace(b, self.canvas_pix, self.canvas_pix, self.device)
-        self.meta_words = b * P_WORDS + (b + 1) + 4 * r_cap + b + (b + 1) + T_WORDS * self.k_cap
+        self.factors_at = b * P_WORDS + (b + 1) + 4 * r_cap + b + (b + 1) + T_WORDS * self.k_cap
+        self.meta_words = self.factors_at + 3 * b          # the factors' float32 bit patterns close the block
         self.r_cap = r_cap
         self.pinned = [(torch.empty(self.src_cap, dtype=torch.uint8).pin_memory(),
                         torch.empty(self.meta_words, dtype=torch.int32).pin_memory(),
@@ -437,7 +492,7 @@ class DeviceAugmentLoader(_AugmentLoader):
         image, annotations, name, d = self._decide(epoch, index)
         src_w, src_h = image.size
         win = source_window(d, src_h, src_w, self.out_h, self.out_w, self.taps)
-        if n_pastes(d):                                    # a paste may read any pixel of the frame
+        if n_pastes(d) or jitter_of(d) is not None:        # a paste may read any pixel; the grey mean is over all of them
             win = (0, 0, src_h, src_w) + win[4:]
         y0, x0, wh, ww = win[:4]
         pix = np.asarray(image.crop((x0, y0, x0 + ww, y0 + wh)), dtype=np.uint8)
@@ -450,7 +505,8 @@ class DeviceAugmentLoader(_AugmentLoader):
             self.events[slot].synchronize()            # the copy that last read this pinned slot has finished
         p_src, p_meta, p_annos = self.pinned[slot]
         b = self.bs
-        src, params, rects, rect_off = pack_batch([(r[0],) + r[1] for r in res], p_src.numpy())
+        items = [(r[0],) + r[1] for r in res]
+        src, params, rects, rect_off = pack_batch(items, p_src.numpy())
         if len(rects) > self.r_cap:
             raise RuntimeError("more ignore rectangles than the staging slot holds")
         m = max(int(r[0].annos.size(0)) for r in res)
@@ -472,6 +528,10 @@ class DeviceAugmentLoader(_AugmentLoader):
             o5 = o4 + b + 1
             meta[o4:o5] = paste_off
             meta[o5:o5 + pastes.size] = pastes.reshape(-1)
+        max_pixels = 0
+        if self.jitter:
+            factors, max_pixels = pack_jitter(items)
+            meta[self.factors_at:self.factors_at + 3 * b] = factors.reshape(-1).view(np.int32)
         annos = p_annos[:b * m * 8].view(b, m, 8)
         annos.zero_()
         for k, r in enumerate(res):
@@ -487,7 +547,7 @@ class DeviceAugmentLoader(_AugmentLoader):
             ev = torch.cuda.Event()
             ev.record(self.copy_stream)
         self.events[slot] = ev
-        self.info[slot] = (int(src.size), m, int(rects.shape[0]), taps, [r[2] for r in res], npaste)
+        self.info[slot] = (int(src.size), m, int(rects.shape[0]), taps, [r[2] for r in res], npaste, max_pixels)
 
     def get_batch(self):
         from rrnet_amd import ops
@@ -497,15 +557,27 @@ class DeviceAugmentLoader(_AugmentLoader):
         cur = torch.cuda.current_stream(self.device)
         cur.wait_event(self.events[slot])
         d_src, d_meta, d_annos = self.slots[slot]
-        nbytes, m, nrect, taps, names, npaste = self.info[slot]
+        nbytes, m, nrect, taps, names, npaste, max_pixels = self.info[slot]
         b = self.bs
         o1 = b * P_WORDS
         o2 = o1 + b + 1
         o3 = o2 + 4 * self.r_cap
         rects = d_meta[o2:o2 + 4 * nrect].view(nrect, 4) if nrect else None
-        if npaste:
-            o4 = o3 + b
-            o5 = o4 + b + 1
+        o4 = o3 + b
+        o5 = o4 + b + 1
+        if self.jitter:
+            prm = d_meta[:o1].view(b, P_WORDS)
+            factors = d_meta[self.factors_at:self.factors_at + 3 * b].view(torch.float32).view(b, 3)
+            gray, _ = ops.jitter_gray_mean(d_src[:nbytes], prm, factors, max_pixels, work=self.jitter_work)
+            if npaste:
+                imgs = ops.augment_frames_pasted_jitter(d_src[:nbytes], prm, rects, d_meta[o1:o2], taps,
+                                                        d_meta[o5:o5 + T_WORDS * npaste].view(npaste, T_WORDS),
+                                                        d_meta[o4:o5], factors, gray, self.mean, self.std, self.out_h,
+                                                        self.out_w, work=self.work)
+            else:
+                imgs = ops.augment_frames_jitter(d_src[:nbytes], prm, rects, d_meta[o1:o2], taps, factors, gray,
+                                                 self.mean, self.std, self.out_h, self.out_w)
+        elif npaste:
             imgs = ops.augment_frames_pasted(d_src[:nbytes], d_meta[:o1].view(b, P_WORDS), rects, d_meta[o1:o2], taps,
                                              d_meta[o5:o5 + T_WORDS * npaste].view(npaste, T_WORDS), d_meta[o4:o5],
                                              self.mean, self.std, self.out_h, self.out_w, work=self.work)

@@ -1,6 +1,7 @@
 """Transform classes of the reference's datasets/transforms/transforms.py: the training chain of
 configs/rrnet_config.py:40-49 (MultiScale, ToTensor, MaskIgnore, FillDuck, HorizontalFlip, RandomCrop, Normalize,
-ToHeatmap), with the reference's constructor and call signatures, on host tensors.  A sample is the tuple
+ToHeatmap) and ColorJitter (which no reference config uses), with the reference's constructor and call signatures, on
+host tensors.  A sample is the tuple
 (image, annotations[, road map, ...]); the road map (uint8 [H,W] or None, third element when the dataset loads one) is
 resized by MultiScale, made a tensor by ToTensor, masked by MaskIgnore and consumed by FillDuck.  Two-element samples
 pass through every class as before.
@@ -74,6 +75,22 @@ class ToTensor:
     def __call__(self, data):
         out = F.img_to_tensor(data[0]), F.annos_to_tensor(data[1])
         return out + (F.roadmap_to_tensor(data[2]),) if len(data) > 2 else out
+
+
+class ColorJitter:
+    """transforms.py:120-130: brightness, contrast and saturation factors drawn with random.uniform (in this order,
+    functional.py:168-170) from [max(1 - x, 0), 1 + x], applied to the PIL image by PIL's ImageEnhance."""
+
+    def __init__(self, brightness=0.5, contrast=0.5, saturation=0.5):
+        self.brightness = [max(1 - brightness, 0), 1 + brightness]
+        self.contrast = [max(1 - contrast, 0), 1 + contrast]
+        self.saturation = [max(1 - saturation, 0), 1 + saturation]
+
+    def __call__(self, data):
+        from PIL import Image
+        assert isinstance(data[0], Image.Image)
+        b, c, s = (random.uniform(*r) for r in (self.brightness, self.contrast, self.saturation))
+        return (F.color_jitter(data[0], b, c, s),) + tuple(data[1:])
 
 
 class MaskIgnore:

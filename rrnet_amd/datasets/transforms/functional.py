@@ -81,6 +81,16 @@ def resize(data, scale_factor):
     return (img, resize_annos(anno, scale_factor)) + rest
 
 
+def color_jitter(image, brightness, contrast, saturation):
+    """functional.py:159-174 with the three factors as arguments (the reference draws them here; ColorJitter.__call__
+    and the loader's sampler draw them): PIL's ImageEnhance.Brightness, Contrast and Color, in this order, on the uint8
+    PIL image.  rr_jitter_gray_mean and the jittered tap reads of rr_augment_frames_jitter equal it bit for bit."""
+    from PIL import ImageEnhance
+    im = ImageEnhance.Brightness(image).enhance(brightness)
+    im = ImageEnhance.Contrast(im).enhance(contrast)
+    return ImageEnhance.Color(im).enhance(saturation)
+
+
 def crop_tensor(data, crop_coor):
     """functional.py:104-111."""
     return data[:, int(crop_coor[1]):int(crop_coor[3]), int(crop_coor[0]):int(crop_coor[2])]

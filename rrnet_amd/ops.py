@@ -1419,11 +1419,23 @@ def ctnet_targets(annos, counts, img_h, img_w, scale_factor=4, num_classes=10):
 AUGMENT_PARAMS = 16        # RR_AUGMENT_PARAMS: int32 words of rr_augment_frames' per-image record
 
 
-def augment_frames(src, params, rects, rect_off, taps, mean, std, out_h, out_w):
+def _jitter_ptrs(jitter, b):
+    """jitter: None or (factors float32 [B,3], gray_mean int32 [B]) -> the two extra pointers of a _jitter entry."""
+    if jitter is None:
+        return ()
+    factors, gray_mean = jitter
+    _C.require_cuda(factors, gray_mean)
+    assert factors.dtype == torch.float32 and factors.is_contiguous() and factors.shape == (b, 3)
+    assert gray_mean.dtype == torch.int32 and gray_mean.is_contiguous() and gray_mean.numel() == b
+    return (_C.ptr(factors), _C.ptr(gray_mean))
+
+
+def augment_frames(src, params, rects, rect_off, taps, mean, std, out_h, out_w, jitter=None):
     """rr_augment_frames: packed uint8 source windows + per-image records -> the normalised network input, logical
     [B,3,out_h,out_w] in NHWC memory.  src uint8 [bytes], params int32 [B,16], rects int32 [R,4] (None or empty: no
     ignore region), rect_off int32 [B+1], taps int32 [T,3], mean / std float32 [3]; all on the device.  The records
-    are built (and checked against the window and table sizes) by rrnet_amd.datasets.augment.pack_batch."""
+    are built (and checked against the window and table sizes) by rrnet_amd.datasets.augment.pack_batch.  `jitter`
+    (factors, gray_mean) selects rr_augment_frames_jitter: see augment_frames_jitter."""
     _C.require_cuda(src, params, rects, rect_off, taps, mean, std)
     assert src.dtype == torch.uint8 and src.is_contiguous() and src.dim() == 1
     assert params.dtype == torch.int32 and params.is_contiguous() and params.shape[1] == AUGMENT_PARAMS
@@ -1435,9 +1447,10 @@ def augment_frames(src, params, rects, rect_off, taps, mean, std, out_h, out_w):
     assert rects is None or (rects.dtype == torch.int32 and rects.is_contiguous() and rects.shape[1] == 4)
     b = params.shape[0]
     out = empty_nhwc(b, 3, out_h, out_w, src.device)
-    _C.check(_C.fn("rr_augment_frames")(_C.ptr(src), src.numel(), _C.ptr(params), _C.ptr(rects), _C.ptr(rect_off),
-                                        _C.ptr(taps), taps.shape[0], _C.ptr(mean), _C.ptr(std), _C.ptr(out), b, out_h,
-                                        out_w, _C.stream()), "rr_augment_frames")
+    entry = _C.fn("rr_augment_frames_jitter") if jitter is not None else _C.fn("rr_augment_frames")
+    _C.check(entry(_C.ptr(src), src.numel(), _C.ptr(params), _C.ptr(rects), _C.ptr(rect_off), _C.ptr(taps), taps.shape[0],
+                   _C.ptr(mean), _C.ptr(std), *_jitter_ptrs(jitter, b), _C.ptr(out), b, out_h, out_w, _C.stream()),
+             "rr_augment_frames_jitter" if jitter is not None else "rr_augment_frames")
     return out
 
 
@@ -1451,14 +1464,15 @@ def paste_workspace(b, canvas_pix, scratch_pix, device):
 
 
 def augment_frames_pasted(src, params, rects, rect_off, taps, pastes, paste_off, mean, std, out_h, out_w,
-                          canvas_pix=None, scratch_pix=None, stages=7, work=None):
+                          canvas_pix=None, scratch_pix=None, stages=7, work=None, jitter=None):
     """rr_augment_frames_pasted: rr_augment_frames with FillDuck's ordered pastes between the ignore step and the flip.
     Arguments as augment_frames, plus pastes int32 [K,12] (None or empty: none) and paste_off int32 [B+1]; a frame with
     pastes ships its whole source frame as its window.  canvas_pix / scratch_pix: the largest scaled frame (dst_h*dst_w)
     and the largest pasted object (out_h*out_w) of the batch in pixels; left None they are read back from the device
     records (a synchronisation the loader avoids by passing them).  The canvas and the scratch come from the caching
     allocator, which hands the same blocks back batch after batch.  `stages` / `work` (a paste_workspace kept between
-    calls) exist for timing one stage.  -> [B,3,out_h,out_w] in NHWC memory."""
+    calls) exist for timing one stage.  `jitter` (factors, gray_mean) selects rr_augment_frames_pasted_jitter: see
+    augment_frames_pasted_jitter.  -> [B,3,out_h,out_w] in NHWC memory."""
     _C.require_cuda(src, params, rects, rect_off, taps, pastes, paste_off, mean, std)
     assert src.dtype == torch.uint8 and src.is_contiguous() and src.dim() == 1
     assert params.dtype == torch.int32 and params.is_contiguous() and params.shape[1] == AUGMENT_PARAMS
@@ -1484,12 +1498,53 @@ def augment_frames_pasted(src, params, rects, rect_off, taps, pastes, paste_off,
     assert canvas.shape == (b, canvas_pix, 3) and scratch.shape == (b, scratch_pix, 3) and canvas_pix % 4 == 0
     assert canvas.dtype == scratch.dtype == torch.float32 and canvas.is_contiguous() and scratch.is_contiguous()
     out = empty_nhwc(b, 3, out_h, out_w, src.device)
-    _C.check(_C.fn("rr_augment_frames_pasted")(_C.ptr(src), src.numel(), _C.ptr(params), _C.ptr(rects), _C.ptr(rect_off),
-                                               _C.ptr(taps), taps.shape[0], _C.ptr(pastes), _C.ptr(paste_off),
-                                               _C.ptr(mean), _C.ptr(std), _C.ptr(canvas), canvas_pix, _C.ptr(scratch),
-                                               scratch_pix, _C.ptr(out), b, out_h, out_w, int(stages), _C.stream()),
-             "rr_augment_frames_pasted")
+    entry = _C.fn("rr_augment_frames_pasted_jitter") if jitter is not None else _C.fn("rr_augment_frames_pasted")
+    _C.check(entry(_C.ptr(src), src.numel(), _C.ptr(params), _C.ptr(rects), _C.ptr(rect_off), _C.ptr(taps), taps.shape[0],
+                   _C.ptr(pastes), _C.ptr(paste_off), _C.ptr(mean), _C.ptr(std), *_jitter_ptrs(jitter, b), _C.ptr(canvas),
+                   canvas_pix, _C.ptr(scratch), scratch_pix, _C.ptr(out), b, out_h, out_w, int(stages), _C.stream()),
+             "rr_augment_frames_pasted_jitter" if jitter is not None else "rr_augment_frames_pasted")
     return out
+
+
+def jitter_workspace(b, device):
+    """(sums int64 [b], gray_mean int32 [b]) for jitter_gray_mean."""
+    return (torch.empty(b, dtype=torch.int64, device=device), torch.empty(b, dtype=torch.int32, device=device))
+
+
+def jitter_gray_mean(src, params, factors, max_pixels=None, work=None):
+    """rr_jitter_gray_mean: ColorJitter's one whole-frame quantity.  src, params as augment_frames, every frame shipped
+    WHOLE (rrnet_amd.datasets.augment.pack_batch / pack_jitter check that on the host records); factors float32 [B,3] =
+    brightness, contrast, saturation per frame.  max_pixels: the largest frame of the batch in pixels; left None it is
+    read back from the device records (a synchronisation the loader avoids by passing it).  -> (gray_mean int32 [B] =
+    int(mean(L) + 0.5) of each brightness-adjusted frame, sums int64 [B] = the integer sums of L)."""
+    _C.require_cuda(src, params, factors)
+    assert src.dtype == torch.uint8 and src.is_contiguous() and src.dim() == 1
+    assert params.dtype == torch.int32 and params.is_contiguous() and params.shape[1] == AUGMENT_PARAMS
+    b = params.shape[0]
+    assert factors.dtype == torch.float32 and factors.is_contiguous() and factors.shape == (b, 3)
+    if max_pixels is None:
+        host = params.cpu()
+        max_pixels = int((host[:, 4].long() * host[:, 5].long()).max())
+    sums, gray = work if work is not None else jitter_workspace(b, src.device)
+    assert sums.dtype == torch.int64 and gray.dtype == torch.int32 and sums.numel() == b and gray.numel() == b
+    _C.check(_C.fn("rr_jitter_gray_mean")(_C.ptr(src), src.numel(), _C.ptr(params), _C.ptr(factors), _C.ptr(sums),
+                                          _C.ptr(gray), b, int(max_pixels), _C.stream()), "rr_jitter_gray_mean")
+    return gray, sums
+
+
+def augment_frames_jitter(src, params, rects, rect_off, taps, factors, gray_mean, mean, std, out_h, out_w):
+    """rr_augment_frames_jitter: augment_frames with ColorJitter applied to the source taps.  factors float32 [B,3],
+    gray_mean int32 [B] from jitter_gray_mean on the same src / params / factors; every frame shipped whole."""
+    return augment_frames(src, params, rects, rect_off, taps, mean, std, out_h, out_w, jitter=(factors, gray_mean))
+
+
+def augment_frames_pasted_jitter(src, params, rects, rect_off, taps, pastes, paste_off, factors, gray_mean, mean, std,
+                                 out_h, out_w, **kw):
+    """rr_augment_frames_pasted_jitter: augment_frames_pasted on the colour-jittered frame (the canvas stage jitters the
+    source taps; pasted objects read the jittered canvas).  factors, gray_mean as augment_frames_jitter; everything
+    else, keywords included, as augment_frames_pasted."""
+    return augment_frames_pasted(src, params, rects, rect_off, taps, pastes, paste_off, mean, std, out_h, out_w,
+                                 jitter=(factors, gray_mean), **kw)
 
 
 def refine_boxes(rois, reg, scores, clses, seg_off, scale, score_thr):

@@ -12,8 +12,14 @@ in a device synchronise.  One JSON line on stdout; --out writes the same object 
 half), the chain holds FillDuck, and the kernel entry is rr_augment_frames_pasted with the time of each of its three
 stages (canvas, paste, finish) and of the whole call.
 
+--color-jitter measures the chain with ColorJitter(0.5, 0.5, 0.5) in front on the same generated data set: both loaders,
+rr_jitter_gray_mean, rr_augment_frames_jitter beside the unjittered kernel (on the windows the plain loader ships and on
+the whole frames the jittered one ships) and the bytes each ships per batch; written to profiles/loader_jitter.json
+unless --out names another file.
+
   python tools/bench_loader.py [--images 48] [--batches 12] [--runs 3] [--threads 16] [--out profiles/loader.json]
-  python tools/bench_loader.py --fill-duck --crops 1024 --out profiles/loader_fillduck.json"""
+  python tools/bench_loader.py --fill-duck --crops 1024 --out profiles/loader_fillduck.json
+  python tools/bench_loader.py --color-jitter"""
 import argparse
 import json
 import os
@@ -62,13 +68,15 @@ def write_roadmaps(root, n, size=(1360, 765)):
         Image.fromarray(road).save(os.path.join(root, "train", "roadmap", "%06d.jpg" % i), quality=90)
 
 
-def chain(crop, fill_duck=False):
-    from rrnet_amd.datasets.transforms import (Compose, FillDuck, HorizontalFlip, MaskIgnore, MultiScale, Normalize,
-                                               RandomCrop, ToHeatmap, ToTensor)
+def chain(crop, fill_duck=False, color_jitter=False):
+    from rrnet_amd.datasets.transforms import (ColorJitter, Compose, FillDuck, HorizontalFlip, MaskIgnore, MultiScale,
+                                               Normalize, RandomCrop, ToHeatmap, ToTensor)
     ts = [MultiScale(scale=(1, 1.15, 1.25, 1.35, 1.5)), ToTensor(), MaskIgnore(MEAN), HorizontalFlip(),
           RandomCrop((crop, crop)), Normalize(MEAN, STD), ToHeatmap(scale_factor=4)]
     if fill_duck:
         ts.insert(3, FillDuck())
+    if color_jitter:
+        ts.insert(0, ColorJitter(0.5, 0.5, 0.5))
     return Compose(ts)
 
 
@@ -136,6 +144,43 @@ def _timed(fn, reps):
     return {"ms_median": statistics.median(ms), "ms_min": min(ms), "ms_max": max(ms)}
 
 
+def jitter_kernel_time(ds, params, batch, crop, reps):
+    """One batch of whole frames and their factors resident on the device: rr_jitter_gray_mean, rr_augment_frames_jitter
+    and, on the same whole-frame records, the unjittered kernel (what the arithmetic per tap costs apart from what
+    reading whole frames costs; kernel_time has the unjittered kernel on windows)."""
+    import torch
+    from rrnet_amd import ops
+    from rrnet_amd.datasets import augment as A
+    taps = A.TapCache()
+    sampler = A.AugmentSampler(params, seed=219)
+    items = []
+    for i in range(batch):
+        image, annos, _ = ds.load(i % len(ds))
+        h, w = image.size[1], image.size[0]
+        d = sampler.sample(annos, h, w, 0, i)
+        win = (0, 0, h, w) + A.source_window(d, h, w, crop, crop, taps)[4:]
+        items.append((d, h, w, win, np.asarray(image, dtype=np.uint8)))
+    src, prm, rects, rect_off = A.pack_batch(items)
+    factors, max_pixels = A.pack_jitter(items)
+    dev = torch.device("cuda", 0)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    args = (t(src.copy()), t(prm), t(rects) if len(rects) else None, t(rect_off), taps.device(dev))
+    mean, std, fac = torch.tensor(MEAN, device=dev), torch.tensor(STD, device=dev), t(factors)
+    work = ops.jitter_workspace(batch, dev)
+    gray, _ = ops.jitter_gray_mean(args[0], args[1], fac, max_pixels, work=work)
+    runs = {"rr_jitter_gray_mean": lambda: ops.jitter_gray_mean(args[0], args[1], fac, max_pixels, work=work),
+            "rr_augment_frames_jitter": lambda: ops.augment_frames_jitter(*args, fac, gray, mean, std, crop, crop),
+            "rr_augment_frames_whole_frames": lambda: ops.augment_frames(*args, mean, std, crop, crop)}
+    out = {"factors": factors.tolist(), "gray_mean": gray.cpu().tolist(), "bytes_read_frames": int(src.size),
+           "bytes_written": batch * crop * crop * 3 * 4}
+    for name, fn in runs.items():
+        for _ in range(10):
+            fn()
+        torch.cuda.synchronize()
+        out[name] = _timed(fn, reps)
+    return out
+
+
 def pasted_kernel_time(ds, params, batch, crop, reps):
     """One batch of whole frames and their paste plans resident on the device; rr_augment_frames_pasted stage by stage
     (the canvas stage restores what the paste stage changes, so each timed paste starts from the same canvas)."""
@@ -190,7 +235,12 @@ def main():
     ap.add_argument("--crops", type=int, nargs="+", default=[512, 1024])
     ap.add_argument("--out", default=None)
     ap.add_argument("--fill-duck", action="store_true", help="the full chain with FillDuck on generated road maps")
+    ap.add_argument("--color-jitter", action="store_true", help="the chain with ColorJitter(0.5, 0.5, 0.5) in front")
     a = ap.parse_args()
+    if a.color_jitter and a.fill_duck:
+        raise SystemExit("--color-jitter and --fill-duck are measured one at a time")
+    if a.color_jitter and a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "loader_jitter.json")
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("bench_loader.py measures on the GPU; none is visible")
@@ -198,6 +248,8 @@ def main():
     from rrnet_amd.datasets.drones_det import DronesDET
     res = {"tool": "bench_loader", "frame": [1360, 765], "images": a.images, "batch": a.batch, "threads": a.threads,
            "batches_per_window": a.batches, "windows": a.runs, "fill_duck": a.fill_duck, "crops": {}}
+    if a.color_jitter:
+        res["color_jitter"] = [0.5, 0.5, 0.5]
     with tempfile.TemporaryDirectory() as root:
         t0 = time.perf_counter()
         write_dataset(root, a.images)
@@ -205,7 +257,7 @@ def main():
             write_roadmaps(root, a.images)
         res["dataset_write_s"] = time.perf_counter() - t0
         for crop in a.crops:
-            tr = chain(crop, a.fill_duck)
+            tr = chain(crop, a.fill_duck, a.color_jitter)
             ds = DronesDET(root, tr, "train", with_road_map=a.fill_duck)
             p = A.chain_params(tr)
             entry = {}
@@ -219,6 +271,11 @@ def main():
                                "redraws": loader.redraws}
             if a.fill_duck:
                 entry["rr_augment_frames_pasted"] = pasted_kernel_time(ds, p, a.batch, crop, a.reps)
+            elif a.color_jitter:
+                entry["rr_augment_frames"] = kernel_time(ds, dict(p, jitter=None), a.batch, crop, a.reps)
+                entry["jitter"] = jitter_kernel_time(ds, p, a.batch, crop, a.reps)
+                entry["h2d_bytes_per_batch"] = {"windows": entry["rr_augment_frames"]["bytes_read_windows"],
+                                                "whole_frames": entry["jitter"]["bytes_read_frames"]}
             else:
                 entry["rr_augment_frames"] = kernel_time(ds, p, a.batch, crop, a.reps)
             res["crops"]["%dx%d" % (crop, crop)] = entry

@@ -2,13 +2,15 @@
 
   python tools/train.py --config rrnet_config|rrnet_fillduck_config|centernet_config|retinanet_config [--data-root D] [--iters N]
                         [--batch B] [--crop H W] [--backbone NAME] [--bf16] [--full-state] [--resume auto|PATH]
-                        [--checkpoint-interval N] [--print-interval N] [--keep-states N]
+                        [--checkpoint-interval N] [--print-interval N] [--keep-states N] [--color-jitter B C S]
 
 A single process: it sets the config keys and calls the operator's training_process().  Without a dataset under
 --data-root the synthetic loader feeds the loop.  `ckp-{step}.pth` (weights, the reference's format) goes to
 ./log/<log_prefix>/ every --checkpoint-interval steps; --full-state writes `state-{step}.pth` beside each of them
 (parameters, Adam moments, scheduler, BatchNorm buffers, step, loader position; rrnet_amd/checkpoint.py) and
---resume continues from one: `auto` takes the newest state of the log directory that loads and verifies."""
+--resume continues from one: `auto` takes the newest state of the log directory that loads and verifies.
+--color-jitter B C S puts ColorJitter(B, C, S) in front of the config's training chain (the config modules carry none,
+as the reference's): brightness, contrast and saturation factors from [max(1 - x, 0), 1 + x], applied on the device."""
 import argparse
 import copy
 import importlib
@@ -41,6 +43,7 @@ def parse(argv=None):
     ap.add_argument("--checkpoint-interval", type=int)
     ap.add_argument("--print-interval", type=int)
     ap.add_argument("--keep-states", type=int)
+    ap.add_argument("--color-jitter", type=float, nargs=3, metavar=("B", "C", "S"))
     return ap.parse_args(argv)
 
 
@@ -64,6 +67,9 @@ def configure(args):
         for i, t in enumerate(chain):               # the real-data loader takes the crop from the chain, as the reference does
             if isinstance(t, RandomCrop):
                 chain[i] = RandomCrop(tuple(args.crop))
+    if args.color_jitter is not None:
+        from rrnet_amd.datasets.transforms import ColorJitter
+        cfg.Train.transforms.transforms.insert(0, ColorJitter(*args.color_jitter))
     if args.backbone is not None:
         cfg.Model.backbone = args.backbone
     if args.bf16:
