@@ -925,6 +925,31 @@ int rr_dcn_psroi_bwd(const float *dout, const float *x, const float *rois, const
                      int group_size, int pooled_size, int part_size, int sample_per_part, float trans_std,
                      int trans_channels, float *dx, float *dtrans, hipStream_t stream);
 
+/* ---- k-means (ext/kmeans/kmeans.py:13-36 `lloyd`, the anchor statistics of scripts/kmeans.py) ------------------- *
+ * rr_kmeans_steps enqueues `nsteps` Lloyd steps for r independent restarts over the same points x [n,m] float32, each
+ * with its own centres [r,k,m] float32 (updated in place).  One step, per restart whose flag is 0:
+ *   d[n,j] = sum_m (x[n,m] - c[j,m])^2, every difference, product and sum rounded to float32, m ascending, no FMA;
+ *   labels[n] = the lowest j of the minimum; sum[j,m] and count[j] over the members in double, through per-workgroup
+ *   partials added in a fixed order (no floating-point atomics: a run repeats bit for bit);
+ *   c'[j,m] = (float)(sum[j,m] / count[j]); where count[j] == 0 the centre STAYS (the reference writes NaN there and then
+ *   never returns); shift = sum_j sqrt(sum_m (c'[j,m] - c[j,m])^2) in double on the float32 values, j and m ascending;
+ *   iters += 1; inertia = sum_n d[n, labels[n]] in double (like the labels, against the centres before the update);
+ *   flags = 1 (done, converged) when shift^2 < tol, else 2 (done, not converged) when iters >= max_iter.
+ * A restart whose flag is set is skipped: labels [r,n], centres, counts [r,k], inertia [r], iters [r] stay as its last
+ * step left them.  The caller zeroes iters and flags before the first call and reads flags [r] whenever it likes; the
+ * result does not depend on how the steps are split over calls.  Limits: k <= RR_KMEANS_MAX_K, m <= RR_KMEANS_MAX_M,
+ * r <= RR_KMEANS_MAX_R, n >= 1 (n < k is legal); x 16-byte aligned.  The grid is rr_kmeans_blocks(n) workgroups of 256
+ * points per restart, capped at RR_KMEANS_MAX_BLOCKS (the loop strides); workspace = rr_kmeans_workspace_bytes bytes. */
+#define RR_KMEANS_MAX_K 64
+#define RR_KMEANS_MAX_M 4
+#define RR_KMEANS_MAX_R 64
+#define RR_KMEANS_MAX_BLOCKS 512
+int rr_kmeans_blocks(long n);
+size_t rr_kmeans_workspace_bytes(long n, int m, int k, int r);
+int rr_kmeans_steps(const float *x, long n, int m, int k, int r, float *centres, int *labels, int *counts,
+                    double *inertia, int *iters, int *flags, double tol, int max_iter, int nsteps, void *workspace,
+                    hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

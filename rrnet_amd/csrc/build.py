@@ -28,6 +28,7 @@ PER_FILE = {
     "evalmatch.hip": ["-ffp-contract=off"],
     "detect.hip": ["-ffp-contract=off"],
     "retina.hip": ["-ffp-contract=off"],
+    "kmeans.hip": ["-ffp-contract=off"],
 }
 
 

@@ -2102,6 +2102,55 @@ def pack_frames(rows6, frame_off, keep, kept, max_rows, out_rows=None):
     return out6, out_off
 
 
+KMEANS_MAX_K, KMEANS_MAX_M, KMEANS_MAX_R = 64, 4, 64      # RR_KMEANS_MAX_K / _M / _R
+
+
+def kmeans_lloyd(X, init, tol=1e-4, max_iter=10000, check_every=16):
+    """rr_kmeans_steps: Lloyd's algorithm for R restarts side by side.  X [N,M] float32, init [R,k,M] float32 (device) ->
+    (labels int32 [R,N], centres float32 [R,k,M], counts int32 [R,k], inertia float64 [R], iters int32 [R], converged bool
+    [R]).  Labels, counts and inertia refer to the centres before the last update, as the reference's labels do; an empty
+    cluster keeps its centre; a restart ends when shift^2 < tol (converged) or at max_iter.  `check_every` steps are
+    enqueued on the current stream between two reads of the R done flags; the result does not depend on it.  Shapes
+    outside 1 <= k <= 64, 1 <= M <= 4, 1 <= R <= 64, N >= 1 raise ValueError before anything is launched."""
+    if not (torch.is_tensor(X) and torch.is_tensor(init)):
+        raise ValueError("kmeans_lloyd: X and init must be tensors")
+    if X.dim() != 2 or init.dim() != 3:
+        raise ValueError("kmeans_lloyd: X must be [N,M] and init [R,k,M], got %s and %s" % (tuple(X.shape), tuple(init.shape)))
+    if X.dtype != torch.float32 or init.dtype != torch.float32:
+        raise ValueError("kmeans_lloyd: X and init must be float32, got %s and %s" % (X.dtype, init.dtype))
+    (n, m), (r, k, m2) = X.shape, init.shape
+    if m2 != m:
+        raise ValueError("kmeans_lloyd: init has %d columns, X has %d" % (m2, m))
+    if not (n >= 1 and 1 <= m <= KMEANS_MAX_M and 1 <= k <= KMEANS_MAX_K and 1 <= r <= KMEANS_MAX_R):
+        raise ValueError("kmeans_lloyd: N=%d M=%d k=%d R=%d outside N >= 1, 1 <= M <= %d, 1 <= k <= %d, 1 <= R <= %d"
+                         % (n, m, k, r, KMEANS_MAX_M, KMEANS_MAX_K, KMEANS_MAX_R))
+    max_iter, check_every = int(max_iter), int(check_every)
+    if max_iter < 1 or check_every < 1:
+        raise ValueError("kmeans_lloyd: max_iter=%d and check_every=%d must be at least 1" % (max_iter, check_every))
+    _C.require_cuda(X, init)
+    dev = X.device
+    X = X.contiguous()
+    if X.data_ptr() % 16:
+        X = X.clone()
+    centres = init.to(dev).clone(memory_format=torch.contiguous_format)
+    labels = torch.empty((r, n), dtype=torch.int32, device=dev)
+    counts = torch.zeros((r, k), dtype=torch.int32, device=dev)
+    inertia = torch.zeros((r,), dtype=torch.float64, device=dev)
+    iters = torch.zeros((r,), dtype=torch.int32, device=dev)
+    flags = torch.zeros((r,), dtype=torch.int32, device=dev)
+    ws = torch.empty(_C.fn("rr_kmeans_workspace_bytes")(n, m, k, r), dtype=torch.uint8, device=dev)
+    steps = _C.fn("rr_kmeans_steps")
+    left = max_iter
+    while left > 0:
+        ns = min(check_every, left)
+        _C.check(steps(_C.ptr(X), n, m, k, r, _C.ptr(centres), _C.ptr(labels), _C.ptr(counts), _C.ptr(inertia), _C.ptr(iters),
+                       _C.ptr(flags), float(tol), max_iter, ns, _C.ptr(ws), _C.stream()), "rr_kmeans_steps")
+        left -= ns
+        if bool(flags.cpu().numpy().all()):                  # the one host read per `check_every` steps
+            break
+    return labels, centres, counts, inertia, iters, flags == 1
+
+
 class _OpsModule(types.ModuleType):
     """`ops.BF16` (read / assign) = this thread's arithmetic switch."""
 
