@@ -683,6 +683,33 @@ int rr_prepare_frames_pair(const unsigned char *frames, const float *mean, const
                            int w, int oh, int ow, hipStream_t stream);
 int rr_merge_ctnet(const float *rows6, int nframes, int k_in, int pair, float img_w, float div, float score_thr,
                    float *merged, int *count, int k, hipStream_t stream);
+/* Tiled inference (no counterpart in the reference): equal-size overlapping tiles cut out of frames of any size, detected
+ * as a batch, and their rows brought back into per-frame blocks.
+ * rr_prepare_tiles: frames = one packed byte buffer; frame f is [H_f, W_f, 3] uint8 at byte frame_base[f] (any byte
+ *   address), frame_hw [nframes,2] = H_f, W_f.  tiles [ntiles,3] = frame, y0, x0: the th x tw window of that frame at
+ *   (y0, x0), which the caller has checked to lie inside it.  Tile t of out [ntiles,oh,ow,3] (float NHWC) equals, bit for
+ *   bit, what rr_prepare_frames writes for the host-cropped array frame[y0:y0+th, x0:x0+tw] at output size oh x ow: the taps
+ *   are the tile's (sy = (th-1)/(oh-1) or 0, likewise sx) and the "+1" tap stops at the tile's last row / column, not the
+ *   frame's.  The kernel clamps the frame index, the origin and every tap to the frame the table names.
+ * rr_merge_tiles: rows6 [T,k_in,6] = (x, y, w, h, score, cls) rows per tile in the model's input coordinates (oh x ow),
+ *   count_in [T]; tiles as above, sorted by frame, tile_off [nframes+1] = the tile range of every frame (built and
+ *   checked by the caller; column 0 of tiles is not read).  Per frame its tiles in table order, of each its first
+ *   min(max(count_in[t], 0), k_in) rows in row order; float32 throughout, every operation its own rounding:
+ *   margin test (only when margin > 0): a tile side is interior when it is not on the frame's border (left x0 > 0, top
+ *     y0 > 0, right x0 + tw < W_f, bottom y0 + th < H_f); the row leaves iff left is interior and x < margin, or top is
+ *     interior and y < margin, or right is interior and x + w > (float)ow - margin, or bottom is interior and
+ *     y + h > (float)oh - margin.  A NaN makes every comparison false: the row stays.
+ *   move: x <- x / div + (float)x0, y <- y / div + (float)y0, w <- w / div, h <- h / div (IEEE division); score and class
+ *     are unchanged.
+ *   append: the row goes to frame f's block of merged [nframes,k,6] at count[f] (the caller zeroes count); count[f] ends
+ *     as the true number of kept rows, also above k; rows at and beyond k are not written, rows between count[f] and k are
+ *     left as they were.  k <= RR_DETECT_MAX_ROWS.  One workgroup per frame, no atomics, no dependence on dispatch order. */
+int rr_prepare_tiles(const unsigned char *frames, const long long *frame_base, const int *frame_hw, int nframes,
+                     const int *tiles, int ntiles, int th, int tw, int oh, int ow, const float *mean, const float *stdv,
+                     float *out, hipStream_t stream);
+int rr_merge_tiles(const float *rows6, const int *count_in, const int *tiles, const int *tile_off, const int *frame_hw,
+                   int nframes, int k_in, int th, int tw, int oh, int ow, float div, float margin, float *merged,
+                   int *count, int k, hipStream_t stream);
 
 /* ---- evaluation: VisDrone AP / AR on the device ------------------------------------------------ *
  * rr_eval_match: utils/metrics/metrics.py:51-131 (`get_tp` with its `bbox_iou` calls) for f frames in one launch, one

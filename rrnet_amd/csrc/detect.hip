@@ -6,6 +6,9 @@
 //                            scale, appended per frame to the cross-scale concatenation (:271)
 //   rr_sort_frames_by_score  `torch.sort(pred_bbox[:, 4], descending=True)` (:272) per frame: the batched
 //                            rr_sort_rows_by_score
+//   rr_prepare_tiles         rr_prepare_frames for equal-size tiles cut out of frames of differing sizes (tiled inference:
+//   rr_merge_tiles           the builder's own feature, the reference has none), and the way back: per-tile rows -> margin
+//                            test -> frame coordinates -> per-frame blocks in table order
 // Built with -ffp-contract=off like refine.hip: every step of the box arithmetic is its own fp32 rounding and the division by
 // the scale is an IEEE division (the reference divides on the CPU).  The interpolation in rr_prepare_frames has to give the
 // bits of rr_resize_bilinear_ac: its fused steps are written as explicit fmas (prep_taps / prep_bilinear below).
@@ -120,6 +123,117 @@ __global__ __launch_bounds__(DET_THREADS) void prepare_frames_pair_kernel(const 
             m[c] = v;
         }
     }
+}
+
+// prepare_frames_kernel for T equal-size tiles cut out of F frames of differing sizes: tile n is the th x tw window of frame
+// tiles[n][0] at (tiles[n][1], tiles[n][2]), resized to OH x OW.  The taps are those of the TILE (prep_taps with H = TH,
+// W = TW), so the "+1" tap stops at the tile's last row / column and the output carries the bits prepare_frames_kernel
+// writes for the host-cropped window.  Frame f is [H_f, W_f, 3] bytes at src + frame_base[f], any byte address: byte loads,
+// 64-bit offsets.  The lanes of a wave hold consecutive output columns of one tile row, so their byte loads fall into one or
+// two source rows of at most 64 * 3 * sx bytes each — the same lines prepare_frames_kernel touches, found through one table
+// row per pixel (12 bytes that every lane of the wave shares: one L1 line).
+// The table is checked on the host; what it and frame_hw say is clamped again before it addresses memory.
+__global__ __launch_bounds__(DET_THREADS) void prepare_tiles_kernel(const uint8_t *__restrict__ src,
+                                                                    const long long *__restrict__ frame_base,
+                                                                    const int *__restrict__ frame_hw, int F,
+                                                                    const int *__restrict__ tiles, int T, int TH, int TW, int OH,
+                                                                    int OW, const float *__restrict__ mean,
+                                                                    const float *__restrict__ stdv, float *__restrict__ out)
+{
+    __shared__ float lut[256 * 3];                       // as prepare_frames_kernel
+    for (int i = threadIdx.x; i < 256 * 3; i += DET_THREADS) {
+        const int v = i / 3, c = i - v * 3;
+        const float x = (float)v / 255.0f;
+        lut[i] = (x - mean[c]) / stdv[c];
+    }
+    __syncthreads();
+    const long total = (long)T * OH * OW;
+    const float sy = OH > 1 ? (float)(TH - 1) / (float)(OH - 1) : 0.f;
+    const float sx = OW > 1 ? (float)(TW - 1) / (float)(OW - 1) : 0.f;
+    for (long p = (long)blockIdx.x * DET_THREADS + threadIdx.x; p < total; p += (long)gridDim.x * DET_THREADS) {
+        long q = p;
+        const int w = (int)(q % OW); q /= OW;
+        const int h = (int)(q % OH);
+        const int n = (int)(q / OH);                     // < T
+        const int f = min(max(tiles[n * 3], 0), F - 1);
+        const int H = max(frame_hw[f * 2], 1), W = max(frame_hw[f * 2 + 1], 1);
+        const int oy = tiles[n * 3 + 1], ox = tiles[n * 3 + 2];
+        const PrepTaps t = prep_taps(sy, sx, h, w, TH, TW);
+        // inside the tile as in prepare_frames_kernel, then inside the frame the table names
+        const int y0 = min(max(oy + min(max(t.y0, 0), TH - 1), 0), H - 1), y1 = min(max(oy + min(max(t.y1, 0), TH - 1), 0), H - 1);
+        const int x0 = min(max(ox + min(max(t.x0, 0), TW - 1), 0), W - 1), x1 = min(max(ox + min(max(t.x1, 0), TW - 1), 0), W - 1);
+        const uint8_t *b = src + frame_base[f];
+        const uint8_t *p00 = b + ((long)y0 * W + x0) * 3, *p01 = b + ((long)y0 * W + x1) * 3;
+        const uint8_t *p10 = b + ((long)y1 * W + x0) * 3, *p11 = b + ((long)y1 * W + x1) * 3;
+        float *o = out + p * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            o[c] = prep_bilinear(t, lut[p00[c] * 3 + c], lut[p01[c] * 3 + c], lut[p10[c] * 3 + c], lut[p11[c] * 3 + c]);
+    }
+}
+
+// One workgroup per frame: the rows (x, y, w, h, score, cls) of the frame's tiles [tile_off[f], tile_off[f+1]), tile by
+// tile in table order, the first min(max(count_in[t], 0), k_in) rows of each in row order -> margin test in the model's
+// input coordinates -> x / div + x0, y / div + y0, w / div, h / div -> appended at merged[f][count[f]...].  Compaction as
+// merge_scales_kernel.  count[f] ends as the true number of kept rows, also above K; rows at and beyond K are not written.
+// No workgroup reads what another writes: the result does not depend on the dispatch order.
+__global__ __launch_bounds__(DET_THREADS) void merge_tiles_kernel(const float *rows, const int *count_in, const int *tiles,
+                                                                  const int *tile_off, const int *frame_hw, int k_in, int TH,
+                                                                  int TW, float fow, float foh, float div, float margin,
+                                                                  float *merged, int *count, int K)
+{
+    __shared__ int wave_cnt[DET_THREADS / 64];
+    __shared__ int run;
+    const int f = blockIdx.x;
+    const int t0 = max(tile_off[f], 0), t1 = max(tile_off[f + 1], t0);     // the host built and checked the offsets
+    const int H = frame_hw[f * 2], W = frame_hw[f * 2 + 1];
+    const int base0 = max(count[f], 0);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bool test = margin > 0.0f;
+    if (threadIdx.x == 0) run = 0;
+    __syncthreads();
+    float *dst = merged + (long)f * K * 6;
+    for (int t = t0; t < t1; ++t) {
+        const int n = min(max(count_in[t], 0), k_in);
+        const int oy = tiles[t * 3 + 1], ox = tiles[t * 3 + 2];
+        const float fy = (float)oy, fx = (float)ox;
+        // a side is interior when it is not on the frame's border: only there has the tile cut what it shows
+        const bool left = test && ox > 0, top = test && oy > 0;
+        const bool right = test && ox + TW < W, bottom = test && oy + TH < H;
+        const float *src = rows + (long)t * k_in * 6;
+        for (int base = 0; base < n; base += DET_THREADS) {
+            const int i = base + threadIdx.x;
+            bool keep = false;
+            float o0 = 0.f, o1 = 0.f, o2 = 0.f, o3 = 0.f, sc = 0.f, cl = 0.f;
+            if (i < n) {
+                const float *q = src + (long)i * 6;
+                const float x = q[0], y = q[1], w = q[2], h = q[3];
+                sc = q[4];
+                cl = q[5];
+                // every comparison is false on a NaN: the row stays
+                const bool cut = (left && x < margin) || (top && y < margin) || (right && x + w > fow - margin) ||
+                                 (bottom && y + h > foh - margin);
+                keep = !cut;
+                o0 = x / div + fx;                       // IEEE division, then one addition: two roundings
+                o1 = y / div + fy;
+                o2 = w / div;
+                o3 = h / div;
+            }
+            const unsigned long long m = __ballot(keep);
+            if (lane == 0) wave_cnt[wave] = __popcll(m);
+            __syncthreads();
+            long pos = (long)base0 + run + __popcll(m & ((1ull << lane) - 1ull));
+            for (int wv = 0; wv < wave; ++wv) pos += wave_cnt[wv];
+            if (keep && pos < K) {
+                float *o = dst + pos * 6;
+                o[0] = o0; o[1] = o1; o[2] = o2; o[3] = o3; o[4] = sc; o[5] = cl;
+            }
+            __syncthreads();
+            if (threadIdx.x == 0) run += wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+            __syncthreads();
+        }
+    }
+    if (threadIdx.x == 0) count[f] = (int)min((long)base0 + run, 0x7fffffffl);
 }
 
 // One workgroup per frame: CenterNet rows (x, y, w, h, score, cls+1) of one scale, k_in per image as rr_decode_topk
@@ -315,6 +429,42 @@ extern "C" int rr_prepare_frames_pair(const unsigned char *frames, const float *
     hipLaunchKernelGGL(prepare_frames_pair_kernel, dim3((unsigned)blocks), dim3(DET_THREADS), 0, stream, frames, mean, stdv, out,
                        n, h, w, oh, ow);
     RR_CHECK_LAUNCH("rr_prepare_frames_pair");
+    return RR_OK;
+}
+
+extern "C" int rr_prepare_tiles(const unsigned char *frames, const long long *frame_base, const int *frame_hw, int nframes,
+                                const int *tiles, int ntiles, int th, int tw, int oh, int ow, const float *mean,
+                                const float *stdv, float *out, hipStream_t stream)
+{
+    RR_CHECK_ARG(nframes > 0 && ntiles >= 0, "rr_prepare_tiles: %d frames, %d tiles", nframes, ntiles);
+    RR_CHECK_ARG(th > 0 && tw > 0 && oh > 0 && ow > 0, "rr_prepare_tiles: tile %dx%d -> %dx%d", th, tw, oh, ow);
+    RR_CHECK_ARG(ntiles <= 0x7fffffff / 3, "rr_prepare_tiles: %d tiles", ntiles);
+    if (ntiles == 0) return RR_OK;
+    RR_CHECK_ARG(frames && frame_base && frame_hw && tiles && mean && stdv && out, "rr_prepare_tiles: null pointer");
+    const long total = (long)ntiles * oh * ow;
+    long blocks = (total + DET_THREADS - 1) / DET_THREADS;
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(prepare_tiles_kernel, dim3((unsigned)blocks), dim3(DET_THREADS), 0, stream, frames, frame_base, frame_hw,
+                       nframes, tiles, ntiles, th, tw, oh, ow, mean, stdv, out);
+    RR_CHECK_LAUNCH("rr_prepare_tiles");
+    return RR_OK;
+}
+
+extern "C" int rr_merge_tiles(const float *rows6, const int *count_in, const int *tiles, const int *tile_off,
+                              const int *frame_hw, int nframes, int k_in, int th, int tw, int oh, int ow, float div,
+                              float margin, float *merged, int *count, int k, hipStream_t stream)
+{
+    RR_CHECK_ARG(nframes >= 0 && nframes <= 65535 && k_in >= 0, "rr_merge_tiles: %d frames, %d rows per tile", nframes, k_in);
+    RR_CHECK_ARG(th > 0 && tw > 0 && oh > 0 && ow > 0, "rr_merge_tiles: tile %dx%d, input %dx%d", th, tw, oh, ow);
+    RR_CHECK_ARG(k > 0 && k <= DET_MAX_ROWS, "rr_merge_tiles: %d rows per frame (limit %d)", k, DET_MAX_ROWS);
+    RR_CHECK_ARG(div > 0.0f, "rr_merge_tiles: zoom %g", (double)div);
+    RR_CHECK_ARG(margin >= 0.0f, "rr_merge_tiles: margin %g", (double)margin);
+    if (nframes == 0) return RR_OK;
+    RR_CHECK_ARG(count_in && tiles && tile_off && frame_hw && merged && count, "rr_merge_tiles: null pointer");
+    RR_CHECK_ARG(k_in == 0 || rows6, "rr_merge_tiles: null pointer");
+    hipLaunchKernelGGL(merge_tiles_kernel, dim3(nframes), dim3(DET_THREADS), 0, stream, rows6, count_in, tiles, tile_off, frame_hw,
+                       k_in, th, tw, (float)ow, (float)oh, div, margin, merged, count, k);
+    RR_CHECK_LAUNCH("rr_merge_tiles");
     return RR_OK;
 }
 

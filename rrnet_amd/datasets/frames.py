@@ -3,7 +3,8 @@ equal size, upload uint8.  No transform runs on the host; ToTensor -> Normalize 
 
   FrameFolder         the *.jpg / *.png files of a directory, sorted by name, with DronesDET's `load` surface
   plan_buckets        the batching rule on a sequence of sizes (pure; what SizeBucketedFrames follows)
-  SizeBucketedFrames  iterator of (frames uint8 [b,H,W,3] on the device, names)"""
+  SizeBucketedFrames  iterator of (frames uint8 [b,H,W,3] on the device, names)
+  OrderedFrames       iterator of (list of uint8 [H_i,W_i,3] device tensors, names) in file order: for tiled detection"""
 import os
 from concurrent.futures import ThreadPoolExecutor
 
@@ -105,3 +106,32 @@ class SizeBucketedFrames:
                     yield self._emit(full)
         for rest in buckets.flush():
             yield self._emit(rest)
+
+
+class OrderedFrames(SizeBucketedFrames):
+    """Iterating yields ([uint8 [H_i,W_i,3] device tensors], [names]) with `batch` frames per step (the last step may be
+    shorter), in file order whatever the frames' sizes: the input of tiled detection, where tiles of one size make the batch.
+    Same dataset surface, rank split and threaded decode consumed in file order as SizeBucketedFrames."""
+
+    def _job(self, index):
+        loaded = self.dataset.load(index)
+        return np.array(loaded[0], dtype=np.uint8), loaded[2]       # a copy: PIL's buffer is read-only
+
+    def _emit(self, items):
+        return [torch.from_numpy(a).to(self.device, non_blocking=False) for a, _ in items], [n for _, n in items]
+
+    def __iter__(self):
+        with ThreadPoolExecutor(max_workers=self.workers) as pool:
+            ahead = max(2 * self.workers, self.batch)
+            futures = [pool.submit(self._job, i) for i in self.indices[:ahead]]
+            items = []
+            for k in range(len(self.indices)):
+                if k + ahead < len(self.indices):
+                    futures.append(pool.submit(self._job, self.indices[k + ahead]))
+                items.append(futures[k].result())
+                futures[k] = None
+                if len(items) == self.batch:
+                    yield self._emit(items)
+                    items = []
+        if items:
+            yield self._emit(items)

@@ -16,7 +16,9 @@ Ordering note: decode emits rows score-descending, grouping / hard NMS are stabl
 (operators/rrnet_operator.py:256-279) for a batch of equal-size uint8 frames.  `detect_frames_centernet` /
 `CenterNetFrameDetector` are the same for CenterNet (operators/centernet_operator.py:262-285: every scale once flipped
 and once plain, both in one model pass).  `detect_frames_retinanet` / `RetinaNetFrameDetector` are RetinaNet's single-scale
-evaluation body (operators/retinanet_operator.py:243-255): decode, score sort, the reference's hard NMS."""
+evaluation body (operators/retinanet_operator.py:243-255): decode, score sort, the reference's hard NMS.
+`plan_tiles` / `detect_tiled_retinanet` / `finish_tiles` are tiled inference for RetinaNet: overlapping tiles of the
+training size cut out of frames of any sizes, detected as one batch of equal-size images (no counterpart in the reference)."""
 import os
 
 import torch
@@ -321,6 +323,173 @@ def detect_frames_retinanet(model, frames_u8, mean, std, anchors, *, score_thr=0
     return out6[:int(fo[-1])], frame_off
 
 
+def _tile_hw(tile):
+    if isinstance(tile, (tuple, list)):
+        if len(tile) != 2:
+            raise ValueError("tile must be N or (H, W), got %r" % (tile,))
+        return int(tile[0]), int(tile[1])
+    return int(tile), int(tile)
+
+
+def plan_tiles(h, w, tile, overlap):
+    """Origins (y0, x0) of the overlapping tiles that cover an h x w frame, row-major (y outer).  tile = (th, tw) or N,
+    0 <= overlap < min(th, tw).  Along an axis of length L with tile size t the step is s = t - overlap; the origins are
+    0, s, 2s, ... while origin + t < L, then a last origin L - t (L == t: [0]).  Every tile has the full size and lies
+    inside the frame: nothing is padded and no edge tile is smaller, so t > L raises ValueError."""
+    th, tw = _tile_hw(tile)
+    h, w, overlap = int(h), int(w), int(overlap)
+    if th <= 0 or tw <= 0:
+        raise ValueError("plan_tiles: tile %dx%d" % (th, tw))
+    if not 0 <= overlap < min(th, tw):
+        raise ValueError("plan_tiles: overlap %d must be in [0, %d) for a %dx%d tile" % (overlap, min(th, tw), th, tw))
+    if th > h or tw > w:
+        raise ValueError("plan_tiles: a %dx%d frame is smaller than the %dx%d tile (tiles are neither padded nor shrunk)"
+                         % (h, w, th, tw))
+
+    def axis(length, t):
+        step, origins, o = t - overlap, [], 0
+        while o + t < length:
+            origins.append(o)
+            o += step
+        return origins + [length - t]
+
+    return [(y0, x0) for y0 in axis(h, th) for x0 in axis(w, tw)]
+
+
+TILE_MAX_ROWS = ops.DETECT_MAX_ROWS             # merged rows of one frame the batched score sort holds
+
+
+@torch.no_grad()
+def finish_tiles(rows, count_in, tiles, sizes, tile, in_size, zoom=1.0, margin=0.0, nms_thresh=0.3):
+    """What follows the model in detect_tiled_retinanet: rows [T,k,6] = every tile's candidates (x,y,w,h,prob,cls+1 in the
+    model's input coordinates, in_size = (oh, ow)) as rr_retina_decode_frames writes them, count_in int32 [T] its true
+    counts; tiles = T host rows (frame, y0, x0) sorted by frame, sizes = (H, W) of every frame, tile = (th, tw).
+    rr_merge_tiles (div = float32(zoom), margin as ops.merge_tiles explains it) brings the rows into per-frame blocks in
+    frame coordinates; then detect_frames_retinanet's tail: stable score sort, rr_nms_frames, rr_pack_frames.
+    -> (boxes [n,6], frame_off int32 [F+1]) on the device.  Host reads: the tile counts, the frame counts, the final
+    offsets.  Raises ValueError, before the sort, for a tile with more than k candidates and for a frame with more than
+    16384 merged rows."""
+    import numpy as np
+    t, k, _ = rows.shape
+    nframes = len(sizes)
+    dev = rows.device
+    table, tile_off = ops.check_tiles(tiles, sizes, tile)
+    if table.shape[0] != t:
+        raise ValueError("finish_tiles: %d tiles in the table, rows of %d" % (table.shape[0], t))
+    empty = (rows.new_zeros((0, 6)), torch.zeros(nframes + 1, dtype=torch.int32, device=dev))
+    if t == 0 or nframes == 0:
+        return empty
+    tile_counts = count_in.cpu().numpy().astype(np.int64)           # host read: the tile counts
+    over = np.nonzero(tile_counts > k)[0]
+    if over.size:
+        i = int(over[0])
+        raise ValueError("finish_tiles: tile %d (frame %d, origin y %d x %d) has %d candidates above the score threshold; a "
+                         "tile's buffer holds %d" % (i, table[i, 0], table[i, 1], table[i, 2], tile_counts[i], k))
+    bound = [int(np.clip(tile_counts[tile_off[f]:tile_off[f + 1]], 0, None).sum()) for f in range(nframes)]
+    if max(bound) == 0:
+        return empty
+    limit = TILE_MAX_ROWS
+
+    def refuse_over(per_frame):
+        for f, n in enumerate(per_frame):
+            if n > limit:
+                raise ValueError("finish_tiles: frame %d has %d merged rows from its %d tiles; the score sort accepts %d per "
+                                 "frame" % (f, n, int(tile_off[f + 1] - tile_off[f]), limit))
+
+    if not float(margin) > 0:
+        refuse_over(bound)                                          # nothing leaves: the sums are the merged counts
+    merged, count = ops.merge_buffers(nframes, min(max(bound), limit), dev)
+    ops.merge_tiles(rows, count_in, table, sizes, tile, in_size, np.float32(zoom), margin, merged, count)
+    counts = count.cpu()                                            # host read: the frame counts
+    refuse_over(counts.tolist())
+    most = int(counts.max())
+    if most == 0:
+        return empty
+    cand_off = ops.seg_prefix(count)
+    ordered = ops.sort_frames_by_score(merged, count, out_off=cand_off)
+    keep, kept = ops.nms_frames(ordered, cand_off, most, nms_thresh)
+    out6, frame_off = ops.pack_frames(ordered, cand_off, keep, kept, most, out_rows=int(counts.sum()))
+    fo = frame_off.cpu()                                            # host read: the final offsets
+    return out6[:int(fo[-1])], frame_off
+
+
+def _tiles_of(frames, tile, overlap):
+    """-> (sizes, host table [(frame, y0, x0), ...]) of plan_tiles over every frame, frames in order."""
+    sizes = ops._frame_sizes(frames)
+    table = []
+    for f, (h, w) in enumerate(sizes):
+        try:
+            table += [(f, y0, x0) for y0, x0 in plan_tiles(h, w, tile, overlap)]
+        except ValueError as e:
+            raise ValueError("frame %d: %s" % (f, e)) from None
+    return sizes, table
+
+
+def _check_tiled_frames(what, frames):
+    tensors = [frames] if torch.is_tensor(frames) else list(frames)
+    if not tensors:
+        raise ValueError("%s: no frames" % what)
+    for fr in tensors:
+        if not torch.is_tensor(fr) or fr.dtype != torch.uint8:
+            raise TypeError("%s: frames must be uint8 tensors ([B,H,W,3] or a list of [H,W,3]), got %s"
+                            % (what, fr.dtype if torch.is_tensor(fr) else type(fr).__name__))
+    return tensors
+
+
+@torch.no_grad()
+def detect_tiled_retinanet(model, frames, mean, std, anchors, *, tile, overlap, zoom=1.0, margin=0.0, tile_batch=8,
+                           score_thr=0.1, nms_thresh=0.3, timer=None):
+    """Tiled inference with RetinaNet (the builder's own feature; the reference has none): every frame is cut into
+    overlapping tiles of one size (plan_tiles), each tile is resized by `zoom` and detected on its own, the boxes are moved
+    back into the frame and the duplicates the overlap produces are suppressed by the NMS.
+    frames: a list of uint8 [H_i,W_i,3] device tensors of ANY sizes, or one uint8 [B,H,W,3] tensor — tiles of one size are
+    equal-size images whatever frame they come from, so nothing is padded and no batch is cut short.  tile = N or (th, tw),
+    anchors [A,4] for the model's input size (floor(th*zoom), floor(tw*zoom)).
+    One rr_prepare_tiles call; model passes over the tiles `tile_batch` at a time (a frame's tiles may straddle two passes);
+    rr_retina_decode_frames per pass into slices of one [T,k,6] buffer, k = min(A, 16384); finish_tiles.
+    margin (in input pixels, 0 = off): rows within `margin` of a tile side that is not on the frame's border leave — the
+    boxes that side has cut.  The neighbouring tile sees such an object whole only if `overlap` is larger than margin / zoom
+    plus the object's size: choose overlap accordingly.
+    -> (boxes [n,6] = x,y,w,h,prob,cls+1 in frame coordinates, frames back to back, each score-descending; frame_off int32
+    [F+1]) on the device, as detect_frames_retinanet.  Host reads: three (finish_tiles).  timer as in detect_frames."""
+    import math
+    tensors = _check_tiled_frames("detect_tiled_retinanet", frames)
+    from rrnet_amd import _C
+    _C.require_cuda(*tensors)
+    tick = timer if timer is not None else (lambda stage: None)
+    dev = tensors[0].device
+    th, tw = _tile_hw(tile)
+    tile_batch = int(tile_batch)
+    if tile_batch < 1:
+        raise ValueError("detect_tiled_retinanet: tile_batch %d" % tile_batch)
+    if not float(zoom) > 0 or not float(margin) >= 0:
+        raise ValueError("detect_tiled_retinanet: zoom %r, margin %r" % (zoom, margin))
+    sizes, table = _tiles_of(frames, (th, tw), overlap)
+    oh, ow = int(math.floor(th * zoom)), int(math.floor(tw * zoom))
+    mean, std = _vec3(mean, dev), _vec3(std, dev)
+    x = ops.prepare_tiles(frames, table, (th, tw), zoom, mean, std)
+    tick('prepare')
+    t = len(table)
+    rows = count_in = None
+    for i in range(0, t, tile_batch):
+        loc_pre, cls_pre = model(x[i:i + tile_batch])
+        tick('model')
+        if rows is None:
+            a = cls_pre.shape[1]
+            if tuple(anchors.shape) != (a, 4):
+                raise ValueError("detect_tiled_retinanet: %d predictions per %dx%d tile against %s anchors"
+                                 % (a, oh, ow, tuple(anchors.shape)))
+            k = min(a, TILE_MAX_ROWS)
+            rows = torch.zeros((t, k, 6), dtype=torch.float32, device=dev)
+            count_in = torch.zeros(t, dtype=torch.int32, device=dev)
+        _, c = ops.retina_decode_frames(cls_pre, loc_pre, anchors, score_thr, k=k, rows=rows[i:i + tile_batch])
+        count_in[i:i + c.numel()] = c
+        tick('post')
+    out = finish_tiles(rows, count_in, table, sizes, (th, tw), (oh, ow), zoom, margin, nms_thresh)
+    tick('post')
+    return out
+
+
 class RetinaNetFrameDetector:
     """RetinaNet from a reference-format checkpoint, ready for `detect`: the counterpart of CenterNetFrameDetector.  Builds
     RetinaNet(cfg), loads the state dict (with or without `module.` prefixes; checkpoint=None keeps the initial weights),
@@ -355,6 +524,30 @@ class RetinaNetFrameDetector:
         """frames uint8 [B,H,W,3] on the device -> (boxes [n,6], frame_off int32 [B+1]) as detect_frames_retinanet."""
         return detect_frames_retinanet(self.model, frames_u8, self.mean, self.std, self.anchors(frames_u8.shape[1:3]),
                                        score_thr=score_thr, nms_thresh=nms_thresh, timer=timer)
+
+    def detect_tiled(self, frames, tile, overlap, zoom=1.0, margin=0.0, tile_batch=8, score_thr=0.1, nms_thresh=0.3,
+                     timer=None):
+        """frames (a list of uint8 [H_i,W_i,3] device tensors or one [B,H,W,3]) -> (boxes [n,6], frame_off int32 [F+1]) as
+        detect_tiled_retinanet; the anchors are those of the model's input size floor(tile * zoom), cached as detect's."""
+        import math
+        th, tw = _tile_hw(tile)
+        anchors = self.anchors((int(math.floor(th * zoom)), int(math.floor(tw * zoom))))
+        return detect_tiled_retinanet(self.model, frames, self.mean, self.std, anchors, tile=(th, tw), overlap=overlap,
+                                      zoom=zoom, margin=margin, tile_batch=tile_batch, score_thr=score_thr,
+                                      nms_thresh=nms_thresh, timer=timer)
+
+    @torch.no_grad()
+    def threshold_for_tile_rows(self, frames, tile, overlap, zoom, rows_per_tile, tile_batch=8):
+        """threshold_for_rows for the tiled path: model passes over these frames' tiles -> (threshold, the largest number of
+        candidates a tile keeps at it).  Not part of the detection path."""
+        th, tw = _tile_hw(tile)
+        _, table = _tiles_of(frames, (th, tw), overlap)
+        x = ops.prepare_tiles(frames, table, (th, tw), zoom, _vec3(self.mean, self.device), _vec3(self.std, self.device))
+        best = torch.cat([torch.sigmoid(self.model(x[i:i + tile_batch])[1].float()).amax(dim=2)
+                          for i in range(0, len(table), int(tile_batch))])      # [T,A]
+        rows_per_tile = min(int(rows_per_tile), best.shape[1] - 1)
+        thr = float(best.topk(rows_per_tile + 1, dim=1).values[:, -1].max())
+        return thr, int((best > thr).sum(dim=1).max())
 
     @torch.no_grad()
     def threshold_for_rows(self, frames_u8, rows_per_frame):

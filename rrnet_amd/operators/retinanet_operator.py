@@ -3,7 +3,8 @@ make_anchor / criterion / training_process / transform_bbox / save_result / eval
 HIP kernels of librrnet_hip.so (convolutions, max-pool, bilinear upsample-add), the anchor criterion as one autograd node
 over rr_retina_assign / rr_retina_loss_* (RF.retina_criterion), the fused flat Adam, rr_retina_decode, the score sort and
 rr_nms_sorted.  fp32, one process, one GPU.  With cfg.Val.device_batch >= 1 the evaluation runs batched on raw frames
-(rrnet_amd.inference.detect_frames_retinanet).
+(rrnet_amd.inference.detect_frames_retinanet); with cfg.Val.tile set beside it, on overlapping tiles
+(rrnet_amd.inference.detect_tiled_retinanet).
 
 Deviations from the reference, all in the evaluation (:227-265):
   * the reference indexes `pred_bbox` with what `nms()` returns (:254-255) — `nms()` returns the kept ROWS, not indices, so
@@ -176,14 +177,37 @@ class RetinaNetOperator(BaseOperator):
 
     def evaluate_batched(self, device_batch, result_dir=None):
         """evaluation_process' loop over SizeBucketedFrames -> detect_frames_retinanet: equal-size raw frames `device_batch`
-        at a time, one D2H copy per batch."""
+        at a time, one D2H copy per batch.
+        Builder-defined, opt-in (the config modules do not carry the keys): with cfg.Val.tile = N or (H, W) the loop runs
+        over OrderedFrames -> detect_tiled_retinanet instead: `device_batch` frames of any sizes per step, cut into
+        overlapping tiles; cfg.Val.tile_overlap (default a quarter of the tile), tile_zoom (1.0) and tile_margin (0.0) are
+        optional beside it."""
+        import math
         from rrnet_amd.datasets.augment import chain_params
-        from rrnet_amd.datasets.frames import SizeBucketedFrames
+        from rrnet_amd.datasets.frames import OrderedFrames, SizeBucketedFrames
+        from rrnet_amd import inference
         from rrnet_amd.inference import detect_frames_retinanet
         cfg = self.cfg
         result_dir = getattr(cfg.Val, "result_dir", './results/') if result_dir is None else result_dir
         p = chain_params(cfg.Val.transforms)
         model = getattr(self.model, "module", self.model)
+        tile = getattr(cfg.Val, "tile", None)
+        if tile:
+            th, tw = inference._tile_hw(tile)
+            overlap = getattr(cfg.Val, "tile_overlap", None)
+            overlap = min(th, tw) // 4 if overlap is None else int(overlap)
+            zoom = float(getattr(cfg.Val, "tile_zoom", None) or 1.0)
+            margin = float(getattr(cfg.Val, "tile_margin", None) or 0.0)
+            anchors = self.make_anchor((int(math.floor(th * zoom)), int(math.floor(tw * zoom))))[0]
+            frames = OrderedFrames(self.validation_loader.dataset, device_batch, rank=getattr(cfg.Distributed, "rank", 0),
+                                   world_size=max(int(getattr(cfg.Distributed, "world_size", 1)), 1),
+                                   num_workers=cfg.Val.num_workers)
+            for frame_list, names in frames:
+                boxes, frame_off = inference.detect_tiled_retinanet(model, frame_list, p["mean"], p["std"], anchors,
+                                                                    tile=(th, tw), overlap=overlap, zoom=zoom, margin=margin,
+                                                                    score_thr=SCORE_THRESH, nms_thresh=NMS_THRESH)
+                self.write_results(result_dir, names, boxes, frame_off.cpu())
+            return
         frames = SizeBucketedFrames(self.validation_loader.dataset, device_batch, rank=getattr(cfg.Distributed, "rank", 0),
                                     world_size=max(int(getattr(cfg.Distributed, "world_size", 1)), 1),
                                     num_workers=cfg.Val.num_workers)

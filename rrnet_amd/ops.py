@@ -1659,6 +1659,121 @@ def merge_ctnet(rows, nframes, img_w, div, merged, count, pair=True, score_thr=0
                                      float(score_thr), _C.ptr(merged), _C.ptr(count), k, _C.stream()), "rr_merge_ctnet")
 
 
+def check_tiles(tiles, sizes, tile):
+    """The host's check of a tile table before it is uploaded.  tiles: T rows (frame, y0, x0); sizes: (H, W) of every frame;
+    tile = (th, tw).  Every tile must name a frame and lie inside it, and the rows must be sorted by frame (a frame's tiles
+    back to back, which is what rr_merge_tiles' ranges need).
+    -> (table int32 [T,3] numpy, tile_off int32 [F+1] numpy); ValueError naming the first offending row."""
+    import numpy as np
+    table = np.ascontiguousarray(np.asarray(tiles, dtype=np.int64).reshape(-1, 3))
+    th, tw = int(tile[0]), int(tile[1])
+    if th <= 0 or tw <= 0:
+        raise ValueError("tiles: tile %dx%d" % (th, tw))
+    nframes = len(sizes)
+    per_frame = [0] * nframes
+    last = 0
+    for t, (f, y0, x0) in enumerate(table.tolist()):
+        if not 0 <= f < nframes:
+            raise ValueError("tiles: row %d names frame %d of %d" % (t, f, nframes))
+        h, w = int(sizes[f][0]), int(sizes[f][1])
+        if y0 < 0 or x0 < 0 or y0 + th > h or x0 + tw > w:
+            raise ValueError("tiles: row %d: tile %dx%d at (%d, %d) leaves frame %d (%dx%d)" % (t, th, tw, y0, x0, f, h, w))
+        if f < last:
+            raise ValueError("tiles: row %d: frame %d after frame %d (rows must be sorted by frame)" % (t, f, last))
+        last = f
+        per_frame[f] += 1
+    tile_off = np.concatenate([[0], np.cumsum(per_frame)]).astype(np.int32)
+    return table.astype(np.int32), tile_off
+
+
+def _frame_sizes(frames):
+    if torch.is_tensor(frames):
+        if frames.dim() != 4 or frames.shape[3] != 3:
+            raise ValueError("tiles: frames must be [B,H,W,3] or a list of [H,W,3], got %s" % (tuple(frames.shape),))
+        return [(int(frames.shape[1]), int(frames.shape[2]))] * int(frames.shape[0])
+    sizes = []
+    for i, fr in enumerate(frames):
+        if not torch.is_tensor(fr) or fr.dim() != 3 or fr.shape[2] != 3:
+            raise ValueError("tiles: frame %d must be a [H,W,3] tensor" % i)
+        sizes.append((int(fr.shape[0]), int(fr.shape[1])))
+    return sizes
+
+
+def prepare_tiles(frames, tiles, tile, zoom, mean, std, out=None):
+    """rr_prepare_tiles: T equal-size tiles cut out of F frames of any sizes -> ToTensor -> Normalize -> bilinear resize
+    (align_corners=True) by `zoom`, one launch.  frames: a list of uint8 [H_i,W_i,3] device tensors (packed here into one
+    byte buffer) or one uint8 [B,H,W,3] tensor; tiles: T host rows (frame, y0, x0), checked by check_tiles; tile = (th, tw).
+    -> logical [T,3,floor(th*zoom),floor(tw*zoom)] float32 in NHWC memory; tile t carries the bits prepare_frames gives for
+    frames[f][y0:y0+th, x0:x0+tw] at that factor.  out (optional): the NHWC buffer to write into."""
+    import math
+    import numpy as np
+    sizes = _frame_sizes(frames)
+    if not sizes:
+        raise ValueError("prepare_tiles: no frames")
+    th, tw = int(tile[0]), int(tile[1])
+    table, _ = check_tiles(tiles, sizes, (th, tw))
+    if torch.is_tensor(frames):
+        packed = frames.contiguous()
+    else:
+        packed = torch.cat([fr.contiguous().view(-1) for fr in frames]) if len(frames) > 1 else frames[0].contiguous()
+    _C.require_cuda(packed, mean, std, out)
+    assert packed.dtype == torch.uint8
+    assert mean.dtype == torch.float32 and std.dtype == torch.float32 and mean.numel() == 3 and std.numel() == 3
+    assert mean.is_contiguous() and std.is_contiguous()
+    oh, ow = int(math.floor(th * zoom)), int(math.floor(tw * zoom))
+    if oh <= 0 or ow <= 0:
+        raise ValueError("prepare_tiles: tile %dx%d at zoom %g is empty" % (th, tw, zoom))
+    t = table.shape[0]
+    dev = packed.device
+    if out is None:
+        out = empty_nhwc(t, 3, oh, ow, dev)
+    assert tuple(out.shape) == (t, 3, oh, ow) and out.dtype == torch.float32 and (t == 0 or is_nhwc(out))
+    if t == 0:
+        return out
+    base = np.concatenate([[0], np.cumsum([h * w * 3 for h, w in sizes])[:-1]]).astype(np.int64)
+    frame_base = torch.from_numpy(base).to(dev)
+    frame_hw = torch.tensor(sizes, dtype=torch.int32).to(dev)
+    tiles_dev = torch.from_numpy(table).to(dev)
+    _C.check(_C.fn("rr_prepare_tiles")(_C.ptr(packed), _C.ptr(frame_base), _C.ptr(frame_hw), len(sizes), _C.ptr(tiles_dev), t,
+                                       th, tw, oh, ow, _C.ptr(mean), _C.ptr(std), _C.ptr(out), _C.stream()),
+             "rr_prepare_tiles")
+    return out
+
+
+def merge_tiles(rows, count_in, tiles, sizes, tile, in_size, div, margin, merged, count):
+    """rr_merge_tiles: per-tile rows [T,k_in,6] (x,y,w,h,score,cls in the model's input coordinates, in_size = (oh, ow)) and
+    count_in int32 [T] -> per frame, its tiles in table order and of each its first min(max(count_in[t], 0), k_in) rows:
+    the margin test (margin > 0: a row leaves when it comes within `margin` input pixels of a tile side that is not on the
+    frame's border — the box a tile edge has cut; the neighbouring tile sees it whole as long as the tiles' overlap exceeds
+    margin / div plus the object size), x / div + x0, y / div + y0, w / div, h / div (float32, IEEE), appended to merged
+    [F,K,6] at count [F] (in place, see merge_buffers).  count[f] ends as the true number of kept rows, also above K; rows
+    beyond K are not written.  tiles: T host rows (frame, y0, x0) sorted by frame, sizes: (H, W) per frame."""
+    import numpy as np
+    th, tw = int(tile[0]), int(tile[1])
+    table, tile_off = check_tiles(tiles, sizes, (th, tw))
+    _C.require_cuda(rows, count_in, merged, count)
+    f, k, six = merged.shape
+    t = table.shape[0]
+    assert f == len(sizes) and six == 6 and merged.dtype == torch.float32 and merged.is_contiguous() and 0 < k <= DETECT_MAX_ROWS
+    assert count.dtype == torch.int32 and count.numel() == f and count.is_contiguous()
+    assert rows.dtype == torch.float32 and rows.is_contiguous() and rows.dim() == 3 and rows.shape[0] == t and rows.shape[2] == 6
+    assert count_in.dtype == torch.int32 and count_in.numel() == t and count_in.is_contiguous()
+    div, margin = float(np.float32(div)), float(np.float32(margin))
+    if not div > 0 or not margin >= 0:
+        raise ValueError("merge_tiles: zoom %r, margin %r" % (div, margin))
+    if f == 0:
+        return
+    dev = merged.device
+    # an empty table still needs addresses the kernel may name
+    tiles_dev = torch.from_numpy(table if t else np.zeros((1, 3), np.int32)).to(dev)
+    off_dev = torch.from_numpy(tile_off).to(dev)
+    hw_dev = torch.tensor([(int(h), int(w)) for h, w in sizes], dtype=torch.int32).to(dev)
+    cin = count_in if t else torch.zeros(1, dtype=torch.int32, device=dev)
+    _C.check(_C.fn("rr_merge_tiles")(_C.ptr(rows), _C.ptr(cin), _C.ptr(tiles_dev), _C.ptr(off_dev), _C.ptr(hw_dev), f,
+                                     rows.shape[1], th, tw, int(in_size[0]), int(in_size[1]), div, margin, _C.ptr(merged),
+                                     _C.ptr(count), k, _C.stream()), "rr_merge_tiles")
+
+
 def sort_frames_by_score(rows6, count, out_off=None, xyxy=False):
     """rr_sort_frames_by_score: rows6 [B,K,6], count int32 [B] -> every frame's first count[f] rows by score descending
     (ties keep row order).  out_off None: [B,K,6], padding (class -1) behind the sorted rows.  out_off int32 [B+1]

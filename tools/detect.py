@@ -23,7 +23,18 @@ sort, hard NMS at 0.3) and writes the truncated integer lines of RetinaNetOperat
 RetinaNet is fp32 only and its evaluation has one scale, no flip and always the NMS: --bf16, --flip / --no-flip, --scales and
 --nms / --raw are refused with it.  With --random-weights every anchor scores near 0.5, more candidates than the score sort
 holds; unless --score-thr is given the tool then picks, from the first batch, the threshold that keeps at most 1000
-anchors of a frame, and prints it."""
+anchors of a frame, and prints it.
+
+--tile N (or H,W) with retinanet_config detects on overlapping tiles of that size instead of whole frames
+(rrnet_amd.inference.detect_tiled_retinanet): the model was trained on 512x512 crops, and tiles of one size batch whatever
+the frames' sizes are, so `--batch` frames are taken in file order and their tiles run --tile-batch at a time:
+
+  python tools/detect.py --config retinanet_config --checkpoint ckp.pth --images DIR --out DIR --tile 512
+                         [--tile-overlap 128] [--tile-zoom 1.5] [--tile-margin 4] [--tile-batch 8]
+
+--tile-overlap must exceed --tile-margin / --tile-zoom plus the size of the objects, or an object cut by both of two
+neighbouring tiles is lost.  A frame smaller than the tile is refused.  With --random-weights the threshold is picked on the
+first batch's tiles.  The other configs refuse --tile."""
 import argparse
 import copy
 import importlib
@@ -42,6 +53,33 @@ def load_config(name):
     if name not in CONFIGS:
         raise SystemExit("unknown config %r (one of %s)" % (name, ", ".join(CONFIGS)))
     return copy.deepcopy(importlib.import_module("rrnet_amd.configs." + name).Config)
+
+
+def parse_tile(args):
+    """--tile N | H,W with its companions -> dict(tile=(th, tw), overlap, zoom, margin, batch), or None without --tile."""
+    if args.tile is None:
+        return None
+    parts = args.tile.split(",")
+    try:
+        nums = [int(p) for p in parts]
+    except ValueError:
+        nums = []
+    if len(nums) not in (1, 2) or any(n <= 0 for n in nums):
+        raise SystemExit("--tile takes N or H,W (positive integers), got %r" % args.tile)
+    th, tw = (nums[0], nums[0]) if len(nums) == 1 else nums
+    overlap = min(th, tw) // 4 if args.tile_overlap is None else args.tile_overlap
+    if not 0 <= overlap < min(th, tw):
+        raise SystemExit("--tile-overlap %d must be at least 0 and smaller than the tile (%dx%d)" % (overlap, th, tw))
+    zoom = 1.0 if args.tile_zoom is None else args.tile_zoom
+    margin = 0.0 if args.tile_margin is None else args.tile_margin
+    batch = 8 if args.tile_batch is None else args.tile_batch
+    if not zoom > 0 or int(th * zoom) < 1 or int(tw * zoom) < 1:
+        raise SystemExit("--tile-zoom %g leaves no pixels of a %dx%d tile" % (zoom, th, tw))
+    if not margin >= 0:
+        raise SystemExit("--tile-margin %g must not be negative" % margin)
+    if batch < 1:
+        raise SystemExit("--tile-batch %d must be at least 1" % batch)
+    return dict(tile=(th, tw), overlap=overlap, zoom=zoom, margin=margin, batch=batch)
 
 
 def main(argv=None):
@@ -63,11 +101,23 @@ def main(argv=None):
     ap.add_argument("--workers", type=int, default=8)
     ap.add_argument("--backbone", help="RetinaNet: override cfg.Model.backbone (resnet10 / resnet50 / resnet101)")
     ap.add_argument("--score-thr", type=float, help="RetinaNet: the candidate threshold (default 0.1)")
+    ap.add_argument("--tile", help="RetinaNet: tiled inference on overlapping tiles of this size, N or H,W")
+    ap.add_argument("--tile-overlap", type=int, help="pixels two neighbouring tiles share (default: a quarter of the tile)")
+    ap.add_argument("--tile-zoom", type=float, help="resize every tile by this factor in front of the model (default 1)")
+    ap.add_argument("--tile-margin", type=float, help="drop boxes within this many input pixels of a cutting tile side (default 0)")
+    ap.add_argument("--tile-batch", type=int, help="tiles per model pass (default 8)")
     args = ap.parse_args(argv)
     cfg = load_config(args.config)
     retinanet = args.config.startswith("retinanet")
     if not retinanet and (args.backbone is not None or args.score_thr is not None):
         raise SystemExit("--backbone / --score-thr belong to --config retinanet_config")
+    tile_options = (args.tile_overlap, args.tile_zoom, args.tile_margin, args.tile_batch)
+    if not retinanet and (args.tile is not None or any(v is not None for v in tile_options)):
+        raise SystemExit("--tile: tiled inference is built for --config retinanet_config only (RRNet and CenterNet answer "
+                         "small objects with their scales)")
+    if args.tile is None and any(v is not None for v in tile_options):
+        raise SystemExit("--tile-overlap / --tile-zoom / --tile-margin / --tile-batch need --tile")
+    args.tile = parse_tile(args)
     if retinanet:
         return main_retinanet(args, cfg)
     args.flip = True if args.flip is None else args.flip
@@ -151,6 +201,31 @@ def main_retinanet(args, cfg):
     score_thr = 0.1 if args.score_thr is None else args.score_thr
     pick = args.random_weights and args.score_thr is None
     t0, frames_done, boxes_done = time.perf_counter(), 0, 0
+    if args.tile is not None:
+        from rrnet_amd.datasets.frames import OrderedFrames
+        tl = args.tile
+        for frames, names in OrderedFrames(folder, args.batch, num_workers=args.workers):
+            if pick:
+                per_frame = max(len(inference.plan_tiles(f.shape[0], f.shape[1], tl["tile"], tl["overlap"])) for f in frames)
+                # a frame's tiles share one sort; later frames may keep more than the first batch's: half the room is theirs
+                rows = min(RANDOM_WEIGHT_ROWS, inference.TILE_MAX_ROWS // (2 * per_frame))
+                score_thr, most = detector.threshold_for_tile_rows(frames, tl["tile"], tl["overlap"], tl["zoom"], rows,
+                                                                   tile_batch=tl["batch"])
+                print("random weights: score threshold %.9g keeps at most %d anchors of a tile of the first batch"
+                      % (score_thr, most))
+                pick = False
+            boxes, frame_off = detector.detect_tiled(frames, tl["tile"], tl["overlap"], zoom=tl["zoom"], margin=tl["margin"],
+                                                     tile_batch=tl["batch"], score_thr=score_thr)
+            RetinaNetOperator.write_results(args.out, names, boxes, frame_off.cpu())         # one copy per batch
+            frames_done += len(names)
+            boxes_done += boxes.shape[0]
+        dt = time.perf_counter() - t0
+        print("%d frames, %d boxes -> %s in %.2f s (%.2f frames/s, score > %g, %dx%d tiles, overlap %d, zoom %g, margin %g, "
+              "%d tiles per pass, batch %d%s)"
+              % (frames_done, boxes_done, args.out, dt, frames_done / dt, score_thr, tl["tile"][0], tl["tile"][1],
+                 tl["overlap"], tl["zoom"], tl["margin"], tl["batch"], args.batch,
+                 ", random weights" if args.random_weights else ""))
+        return
     for frames_u8, names in SizeBucketedFrames(folder, args.batch, num_workers=args.workers):
         if pick:
             score_thr, counts = detector.threshold_for_rows(frames_u8, RANDOM_WEIGHT_ROWS)
