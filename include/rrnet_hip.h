@@ -977,6 +977,38 @@ int rr_kmeans_steps(const float *x, long n, int m, int k, int r, float *centres,
                     double *inertia, int *iters, int *flags, double tol, int max_iter, int nsteps, void *workspace,
                     hipStream_t stream);
 
+/* ---- Weighted boxes fusion (Solovyev, Wang, Gabruseva 2021; the project's own feature, rrnet_amd/ensemble.py) ---- *
+ * rr_wbf_segments fuses each segment's rows into clusters.  rows6 = x1,y1,x2,y2,score,cls, finite, score > 0; segment s is
+ * rows seg_off[s] .. +n with n = seg_len[s], or seg_off[s+1]-seg_off[s] when seg_len is NULL.  Rows are taken in the order
+ * given (the caller sorts them score-descending); classes are not compared.  Clusters are numbered in creation order.  For
+ * every row r, in order:
+ *   IoU of a cluster's fused box F against r, in float32 with every operation rounded on its own (no FMA):
+ *     iw = min(F.x2, r.x2) - max(F.x1, r.x1), ih likewise; !(iw > 0 && ih > 0) -> 0; inter = iw*ih;
+ *     u = ((F.x2-F.x1)*(F.y2-F.y1) + (r.x2-r.x1)*(r.y2-r.y1)) - inter; IoU = u > 0 ? inter/u : 0.
+ *   The cluster of the largest IoU is chosen, the lowest index among equals.  r joins it iff a cluster exists and that IoU
+ *   is strictly greater than iou_thr: acc_k += (double)score*(double)coord_k, S += (double)score, cnt += 1,
+ *   mx = max(mx, score), F_k = (float)(acc_k / S).  Otherwise r opens a cluster: F = r's coordinates (bits unchanged),
+ *   acc_k = (double)score*(double)coord_k, S = (double)score, cnt = 1, mx = score, and the cluster takes r's cls.
+ * At the end cluster c goes to out6[seg_off[s]+c] = F, conf, cls; members[seg_off[s]+c] = cnt (members may be NULL);
+ * n_out[s] = clusters.  conf = (float)(base * min((double)cnt, weight_sum) / weight_sum), left to right in double, with
+ * base = S/cnt for conf_type 0 ("avg") and (double)mx for conf_type 1 ("max").  Rows of out6 at and beyond n_out[s] are not
+ * written; out6 may not alias rows6.  No atomics and no workgroup waits on another: a run repeats bit for bit.
+ * Segments of up to RR_WBF_MAX_SEG rows; a bound above RR_WBF_LDS_MAX needs `workspace` of rr_wbf_workspace_bytes bytes.
+ * max_seg_boxes sizes the kernel's LDS: a segment longer than the bound the caller gave is not fused, its n_out is 0.
+ * rr_wbf_plan shows what a call would launch (csrc/wbf_plan.h), for the tests: out[0] = launches (0 for an empty batch),
+ * out[1] = a workspace is needed, out[2..6] = {longest segment that runs on one wave, longest segment of a split's first
+ * launch, RR_WBF_LDS_MAX, RR_WBF_MAX_SEG, workgroups of the workspace launch}, out[7] = 0, then seven ints per launch i at
+ * out[8+7i]: {threads, dynamic LDS bytes, clusters the LDS holds, lo, hi (the launch takes segments of lo < n <= hi rows),
+ * running sums in the workspace, grid (0: one workgroup per segment)}; the rest 0.  n_out >= RR_WBF_PLAN_INTS. */
+#define RR_WBF_LDS_MAX 2048
+#define RR_WBF_MAX_SEG 8192
+#define RR_WBF_PLAN_INTS 32
+size_t rr_wbf_workspace_bytes(int nseg, int max_seg_boxes);
+int rr_wbf_plan(int nseg, int max_seg_boxes, int *out, int n_out);
+int rr_wbf_segments(const float *rows6, const int *seg_off, const int *seg_len, int nseg, int max_seg_boxes,
+                    float iou_thr, int conf_type, double weight_sum, float *out6, int *members, int *n_out,
+                    void *workspace, size_t workspace_bytes, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,7 @@ PER_FILE = {
     "detect.hip": ["-ffp-contract=off"],
     "retina.hip": ["-ffp-contract=off"],
     "kmeans.hip": ["-ffp-contract=off"],
+    "wbf.hip": ["-ffp-contract=off"],
 }
 
 

@@ -1365,6 +1365,46 @@ def hard_nms_segments(boxes6, seg_off, max_seg, thresh, seg_len=None):
     return n_out
 
 
+WBF_CONF_TYPES = {"avg": 0, "max": 1}
+
+
+def wbf_plan(nseg, max_seg):
+    """rr_wbf_plan -> list of RR_WBF_PLAN_INTS ints (include/rrnet_hip.h); a bound the kernel refuses raises RRNetHipError."""
+    import ctypes
+    buf = (ctypes.c_int * 32)()
+    _C.check(_C.fn("rr_wbf_plan")(int(nseg), int(max_seg), buf, 32), "rr_wbf_plan")
+    return list(buf)
+
+
+def wbf_segments(rows, seg_off, max_seg, iou_thr, conf_type, weight_sum, seg_len=None, out=None):
+    """rr_wbf_segments: weighted boxes fusion of score-sorted segments.  rows [R,6] float32 x1,y1,x2,y2,score,cls,
+    seg_off int32 [nseg+1] (seg_len int32 [nseg] where the offsets leave gaps) -> (out [R,6], members int32 [R],
+    n_out int32 [nseg]): segment s's clusters are out[seg_off[s] : seg_off[s]+n_out[s]], rows beyond are not written.
+    conf_type 0 / "avg" or 1 / "max".  `out`: a caller's [R,6] buffer to write into."""
+    _C.require_cuda(rows, seg_off, seg_len, out)
+    if rows.dtype != torch.float32 or rows.dim() != 2 or rows.shape[1] != 6 or not rows.is_contiguous():
+        raise ValueError("wbf_segments: rows must be contiguous float32 [R,6], got %s %s" % (rows.dtype, tuple(rows.shape)))
+    if seg_off.dtype != torch.int32 or (seg_len is not None and seg_len.dtype != torch.int32):
+        raise ValueError("wbf_segments: seg_off and seg_len must be int32")
+    conf_type = WBF_CONF_TYPES.get(conf_type, conf_type)
+    nseg = seg_off.numel() - 1
+    if seg_len is not None and seg_len.numel() != nseg:
+        raise ValueError("wbf_segments: seg_len has %d entries for %d segments" % (seg_len.numel(), nseg))
+    dev = rows.device
+    if out is None:
+        out = torch.empty_like(rows)
+    elif out.shape != rows.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.data_ptr() == rows.data_ptr():
+        raise ValueError("wbf_segments: out must be another contiguous float32 tensor of rows' shape")
+    members = torch.zeros(rows.shape[0], dtype=torch.int32, device=dev)
+    n_out = torch.zeros(max(nseg, 0), dtype=torch.int32, device=dev)
+    nbytes = _C.fn("rr_wbf_workspace_bytes")(nseg, int(max_seg))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    _C.check(_C.fn("rr_wbf_segments")(_C.ptr(rows), _C.ptr(seg_off), _C.ptr(seg_len), nseg, int(max_seg), float(iou_thr),
+                                      int(conf_type), float(weight_sum), _C.ptr(out), _C.ptr(members), _C.ptr(n_out),
+                                      _C.ptr(ws), nbytes, _C.stream()), "rr_wbf_segments")
+    return out, members, n_out
+
+
 def seg_prefix(n_out):
     """Exclusive prefix of per-segment counts -> int32 [nseg+1] (last entry = total)."""
     nseg = n_out.numel()
