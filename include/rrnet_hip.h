@@ -1009,6 +1009,69 @@ int rr_wbf_segments(const float *rows6, const int *seg_off, const int *seg_len, 
                     float iou_thr, int conf_type, double weight_sum, float *out6, int *members, int *n_out,
                     void *workspace, size_t workspace_bytes, hipStream_t stream);
 
+/* ---- VisDrone text files: parse and format (utils/metrics/metrics.py `_read` = pandas.read_csv(float_precision='high'); the
+ * writers operators/rrnet_operator.py, centernet_operator.py, retinanet_operator.py `write_results`, ensemble.format_rows) ---- *
+ * Both directions are exact in 64-bit integer arithmetic (csrc/textcodec.h, shared by the kernels and the *_host loops); what
+ * they cannot decide is FLAGGED and left to the host functions, never approximated.  No atomics, nothing depends on the
+ * dispatch order: a run repeats bit for bit.  Limits: a text buffer of at most 2^40 bytes, fewer than 2^31 lines / rows.
+ *
+ * PARSE.  `text` holds nfiles files back to back, file f = bytes [file_off[f], file_off[f+1]); the caller makes every
+ * non-empty file end in '\n'.  Any byte address works (byte loads only).  A line starts at byte 0 and behind every '\n'; a
+ * blank line (nothing, or only '\r', in front of its '\n') is skipped, as pandas skips it.
+ *   rr_text_line_counts: block_count[b] = lines that start in bytes [b, b+1) * RR_TEXT_BLOCK_BYTES, b < rr_text_line_blocks.
+ *   rr_text_lines: with block_off = the exclusive sum of block_count and nlines = its total, line_pos[l] = the start of line
+ *     l, ascending, and file_line_off[f] = the lines that start before file_off[f], f = 0..nfiles: file f holds lines
+ *     [file_line_off[f], file_line_off[f+1]).
+ *   rr_text_parse: rows[l, 0..ncol) = the first ncol fields of line l, line_flag[l] = 0, RR_TEXT_LINE_SURPLUS (the line has
+ *     exactly one surplus field and it is empty: the trailing comma of some annotation files) or RR_TEXT_LINE_FLAGGED.
+ *     A field is [+-]? digit* ('.' digit*)? with at least one digit, ended by ',' '\r' '\n' or the buffer's end; its value is
+ *     (double)D / 10^k, D the integer of all its digits and k the digits behind the point, ONE IEEE division.  Flagged:
+ *     D >= 2^53, k > 22, more than 17 digit characters (leading zeros count: pandas' parser reads 17 digits of a field and
+ *     drops the rest, so beyond them it is no longer float()), anything outside the grammar (exponents, blanks, nan, inf, an empty field), a zero written with a
+ *     minus sign (pandas answers 0 or -0.0 by the column's dtype), fewer than ncol fields, any other surplus, a '\r' that no
+ *     '\n' follows.  Fields of a flagged line that were not reached are 0.  pandas fixes the column count by the first line:
+ *     a file in which only some lines carry the surplus field belongs to the host as well (rrnet_amd/textio.py sees to it).
+ *
+ * FORMAT.  rows6 [nrows,6] float32 = x,y,w,h (layout 1, 2: the four values the writer is given), score, cls.  clamp 1 applies
+ * v < 0 ? 0 : v to all six in float32 (NaN and -0.0 pass, as np.where(rows < 0, 0, rows) lets them).  A row's bytes:
+ *   layout 0 (RRNet):     '%f,%f,%f,%f,%.4f,%d,-1,-1\n' % (x, y, w, h, score, int(cls))
+ *   layout 1 (CenterNet): a..d = int(rintf(.)) of the four, then '%d,%d,%d,%d,%.4f,%d,-1,-1\n' % (a, b, c-a, d-b, score, int(cls))
+ *   layout 2 (RetinaNet): '%d,%d,%d,%d,%.4f,%d,-1,-1\n' % (int(x), int(y), int(w), int(h), score, int(cls))
+ * with Python's meaning of % on the float32 value: '%f' rounds the exact binary value half to even (|v| = m*2^e, the digits are
+ * (m*10^6) >> -e in integers), a set sign bit prints '-' (also in front of 0.000000), infinity prints inf / -inf, NaN nan;
+ * int() truncates towards zero and -0.0 gives 0.  Flagged: a finite |v| >= 2^63 anywhere, NaN or infinity under %d, and in
+ * layout 1 a rounded corner at or beyond 2^62 (the difference of two must fit 64 bits).
+ *   rr_text_format_len: len[r] = the row's bytes (0 for a flagged row), row_flag[r] = 0 / 1.
+ *   rr_text_format: with byte_off [nrows+1] = the exclusive sum of len (int64), writes row r to out[byte_off[r] ..
+ *     byte_off[r+1]).  A row whose slot is not exactly its length, or leaves [0, out_bytes), is not written; nothing else of
+ *     `out` is touched.  The bytes of rows [a, b) are out[byte_off[a] .. byte_off[b]).
+ * A row is at most RR_TEXT_MAX_ROW bytes: four '%f' of 27 (sign, 19 digits of 2^63, point, 6 decimals), '%.4f' of 25, '%d' of
+ * 20, five commas and ",-1,-1\n" (static_assert in csrc/textio.hip against the layouts).
+ *
+ * rr_text_lines_host / rr_text_parse_host / rr_text_format_host run the same codec in plain loops on host pointers, so that
+ * the digit logic can be tested without a device: lines_host counts (*nlines) and, where line_pos is not NULL, writes the first
+ * max_lines positions; format_host fills len / row_flag where they are not NULL and writes the bytes where `out` is not NULL. */
+#define RR_TEXT_BLOCK_BYTES 4096
+#define RR_TEXT_MAX_ROW 165
+#define RR_TEXT_MAX_COLS 64
+#define RR_TEXT_LINE_FLAGGED 1
+#define RR_TEXT_LINE_SURPLUS 2
+int rr_text_line_blocks(long nbytes);
+int rr_text_line_counts(const unsigned char *text, long nbytes, int *block_count, hipStream_t stream);
+int rr_text_lines(const unsigned char *text, long nbytes, const long *file_off, int nfiles, const long *block_off,
+                  long nlines, long *line_pos, long *file_line_off, hipStream_t stream);
+int rr_text_parse(const unsigned char *text, long nbytes, const long *line_pos, long nlines, int ncol, double *rows,
+                  int *line_flag, hipStream_t stream);
+int rr_text_format_len(const float *rows6, long nrows, int layout, int clamp, int *len, int *row_flag, hipStream_t stream);
+int rr_text_format(const float *rows6, long nrows, int layout, int clamp, const long *byte_off, unsigned char *out,
+                   long out_bytes, hipStream_t stream);
+int rr_text_lines_host(const unsigned char *text, long nbytes, const long *file_off, int nfiles, long max_lines,
+                       long *line_pos, long *file_line_off, long *nlines);
+int rr_text_parse_host(const unsigned char *text, long nbytes, const long *line_pos, long nlines, int ncol, double *rows,
+                       int *line_flag);
+int rr_text_format_host(const float *rows6, long nrows, int layout, int clamp, int *len, int *row_flag,
+                        const long *byte_off, unsigned char *out, long out_bytes);
+
 #ifdef __cplusplus
 }
 #endif

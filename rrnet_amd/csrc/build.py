@@ -30,6 +30,7 @@ PER_FILE = {
     "retina.hip": ["-ffp-contract=off"],
     "kmeans.hip": ["-ffp-contract=off"],
     "wbf.hip": ["-ffp-contract=off"],
+    "textio.hip": ["-ffp-contract=off"],
 }
 
 

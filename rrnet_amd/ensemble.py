@@ -153,11 +153,30 @@ def result_names(dirs):
     return sorted(names)
 
 
-def read_result_dirs(dirs):
+def _text_route(text, device):
+    if text not in ("host", "device"):
+        raise ValueError("text=%r, expected 'host' or 'device'" % (text,))
+    if text == "device":
+        return torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    return None
+
+
+def read_result_dirs(dirs, text="host", device=None):
     """-> (names, sets, missing): sets[m][f] the rows of run m for names[f]; a file a run lacks counts as no detections of
-    that run, and `missing` counts such files."""
+    that run, and `missing` counts such files.  text="device" parses all files of all runs in one pass of
+    rrnet_amd.textio.read_files (files the codec flags, and missing or empty ones, still go through _read_or_empty)."""
     names = result_names(dirs)
     sets, missing = [], 0
+    dev = _text_route(text, device)
+    if dev is not None:
+        from rrnet_amd import textio
+        paths = [os.path.join(d, name + ".txt") for d in dirs for name in names]
+        arrays, _ = textio.read_files(paths, dev, host_read=_read_or_empty)
+        for m in range(len(dirs)):
+            run = arrays[m * len(names):(m + 1) * len(names)]
+            missing += sum(a is None for a in run)
+            sets.append([np.zeros((0, 8), np.float64) if a is None else a for a in run])
+        return names, sets, missing
     for d in dirs:
         run = []
         for name in names:
@@ -175,23 +194,38 @@ def format_rows(rows):
     return "".join((RESULT_FORMAT % (r[0], r[1], r[2], r[3], r[4], int(r[5]))) + "\n" for r in rows)
 
 
-def write_result_dir(out_dir, names, frames):
+def write_result_dir(out_dir, names, frames, text="host", device=None):
+    """One result file per frame.  text="device": the float32 rows are uploaded once, formatted by rr_text_format and written
+    in binary mode; the files are the same bytes."""
     os.makedirs(out_dir, exist_ok=True)
+    dev = _text_route(text, device)
+    if dev is not None:
+        from rrnet_amd import textio
+        frames = [np.asarray(rows) for rows in frames[:len(names)]]
+        if any(rows.dtype != np.float32 for rows in frames):
+            raise ValueError("write_result_dir: text='device' formats float32 rows")
+        frames = [rows.reshape(-1, 6) for rows in frames]
+        host = np.concatenate(frames, 0) if frames else np.zeros((0, 6), np.float32)
+        frame_off = np.cumsum([0] + [rows.shape[0] for rows in frames])
+        textio.write_frames([os.path.join(out_dir, name + ".txt") for name in names[:len(frames)]],
+                            torch.from_numpy(np.ascontiguousarray(host)).to(dev), frame_off, "rrnet", False)
+        return
     for name, rows in zip(names, frames):
         with open(os.path.join(out_dir, name + ".txt"), "w") as f:
             f.write(format_rows(rows))
 
 
-def fuse_result_dirs(dirs, out_dir, timing=None, **kw):
-    """Fuses the result folders `dirs` (one per run) into `out_dir`.  Returns the number of files that some run lacked."""
+def fuse_result_dirs(dirs, out_dir, timing=None, text="host", **kw):
+    """Fuses the result folders `dirs` (one per run) into `out_dir`.  Returns the number of files that some run lacked.
+    text="device" reads and writes the files through the device-side text codec (rrnet_amd/textio.py)."""
     t0 = time.perf_counter()
-    names, sets, missing = read_result_dirs(dirs)
+    names, sets, missing = read_result_dirs(dirs, text=text, device=kw.get("device"))
     if timing is not None:
         timing["read"] = timing.get("read", 0.0) + time.perf_counter() - t0
     print("%d files of %d runs, %d missing (counted as no detections)" % (len(names), len(dirs), missing))
     frames = fuse_rows(sets, frame_names=names, timing=timing, **kw) if names else []
     t0 = time.perf_counter()
-    write_result_dir(out_dir, names, frames)
+    write_result_dir(out_dir, names, frames, text=text, device=kw.get("device"))
     if timing is not None:
         timing["write"] = timing.get("write", 0.0) + time.perf_counter() - t0
     return missing

@@ -166,6 +166,14 @@ class CenterNetOperator(BaseOperator):
             f.write(''.join('%d,%d,%d,%d,%.4f,%d,-1,-1\n' % (int(r[0]), int(r[1]), int(r[2]) - int(r[0]), int(r[3]) - int(r[1]),
                                                              r[4], int(r[5])) for r in rows.tolist()))
 
+    @staticmethod
+    def write_results_device(file_path, rows):
+        """write_results from a device tensor [n,6]: the same file, formatted by rr_text_format (rrnet_amd/textio.py) and
+        written in binary mode; a row the codec flags sends the file through the host expression."""
+        from rrnet_amd import textio
+        rows = rows.detach().to(torch.float32).reshape(-1, 6)
+        textio.write_frames([file_path], rows, [0, rows.shape[0]], "centernet", True)
+
     def evaluate_images(self, imgs):
         """Body of evaluation_process (:262-285) for one image batch (bs=1): every scale twice (flipped, plain)."""
         boxes = []

@@ -175,6 +175,15 @@ class RetinaNetOperator(BaseOperator):
                 f.write(''.join('%d,%d,%d,%d,%.4f,%d,-1,-1\n' % (int(r[0]), int(r[1]), int(r[2]), int(r[3]), r[4], int(r[5]))
                                 for r in rows[off[i]:off[i + 1]]))
 
+    @staticmethod
+    def write_results_device(result_dir, names, boxes, frame_off):
+        """write_results from a device tensor: the same files, formatted by rr_text_format (rrnet_amd/textio.py) in one launch
+        sequence for the whole batch and written in binary mode; a frame with a row the codec flags goes through the host
+        expression."""
+        from rrnet_amd import textio
+        rows = boxes.detach().to(torch.float32).reshape(-1, 6)
+        textio.write_frames([os.path.join(result_dir, name + '.txt') for name in names], rows, frame_off, "retinanet", True)
+
     def evaluate_batched(self, device_batch, result_dir=None):
         """evaluation_process' loop over SizeBucketedFrames -> detect_frames_retinanet: equal-size raw frames `device_batch`
         at a time, one D2H copy per batch.

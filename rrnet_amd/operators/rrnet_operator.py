@@ -223,6 +223,14 @@ class RRNetOperator(BaseOperator):
         with open(file_path, 'w') as f:
             f.write(''.join('%f,%f,%f,%f,%.4f,%d,-1,-1\n' % (r[0], r[1], r[2], r[3], r[4], int(r[5])) for r in rows.tolist()))
 
+    @staticmethod
+    def write_results_device(file_path, rows):
+        """write_results from a device tensor [n,6]: the same file, formatted by rr_text_format (rrnet_amd/textio.py) and
+        written in binary mode; a row the codec flags sends the file through the host expression."""
+        from rrnet_amd import textio
+        rows = rows.detach().to(torch.float32).reshape(-1, 6)
+        textio.write_frames([file_path], rows, [0, rows.shape[0]], "rrnet", True)
+
     def evaluate_batched(self, device_batch, k=1500):
         """evaluation_process' loop over SizeBucketedFrames -> detect_frames: equal-size frames `device_batch` at a time,
         one D2H copy per batch."""

@@ -1405,6 +1405,127 @@ def wbf_segments(rows, seg_off, max_seg, iou_thr, conf_type, weight_sum, seg_len
     return out, members, n_out
 
 
+TEXT_LAYOUTS = {"rrnet": 0, "centernet": 1, "retinanet": 2}
+TEXT_LINE_FLAGGED, TEXT_LINE_SURPLUS = 1, 2
+TEXT_MAX_ROW = 165                                    # RR_TEXT_MAX_ROW
+
+
+def _exclusive_sum(counts):
+    off = torch.zeros(counts.numel() + 1, dtype=torch.int64, device=counts.device)
+    torch.cumsum(counts, 0, dtype=torch.int64, out=off[1:])
+    return off
+
+
+def text_lines(text, file_off):
+    """rr_text_line_counts + rr_text_lines: text uint8 [N] (files back to back, each non-empty one ending in '\\n'), file_off
+    int64 [F+1] -> (line_pos int64 [L], file_line_off int64 [F+1]).  One host sync to learn L."""
+    _C.require_cuda(text, file_off)
+    if text.dtype != torch.uint8 or text.dim() != 1 or file_off.dtype != torch.int64 or file_off.numel() < 1:
+        raise ValueError("text_lines: text must be uint8 [N] and file_off int64 [F+1]")
+    if not file_off.is_contiguous():
+        raise ValueError("text_lines: file_off must be contiguous")
+    n, dev = text.numel(), text.device
+    nblocks = _C.fn("rr_text_line_blocks")(n)
+    counts = torch.empty(nblocks, dtype=torch.int32, device=dev)
+    _C.check(_C.fn("rr_text_line_counts")(_C.ptr(text), n, _C.ptr(counts), _C.stream()), "rr_text_line_counts")
+    block_off = _exclusive_sum(counts)
+    nlines = int(block_off[-1].item())
+    line_pos = torch.empty(nlines, dtype=torch.int64, device=dev)
+    file_line_off = torch.empty(file_off.numel(), dtype=torch.int64, device=dev)
+    _C.check(_C.fn("rr_text_lines")(_C.ptr(text), n, _C.ptr(file_off), file_off.numel() - 1, _C.ptr(block_off), nlines,
+                                    _C.ptr(line_pos), _C.ptr(file_line_off), _C.stream()), "rr_text_lines")
+    return line_pos, file_line_off
+
+
+def text_parse(text, line_pos, ncol=8):
+    """rr_text_parse: -> (rows float64 [L,ncol], line_flag int32 [L]: 0, TEXT_LINE_SURPLUS or TEXT_LINE_FLAGGED)."""
+    _C.require_cuda(text, line_pos)
+    if text.dtype != torch.uint8 or line_pos.dtype != torch.int64 or not line_pos.is_contiguous():
+        raise ValueError("text_parse: text must be uint8 and line_pos contiguous int64")
+    nlines, dev = line_pos.numel(), text.device
+    rows = torch.empty((nlines, ncol), dtype=torch.float64, device=dev)
+    flags = torch.empty(nlines, dtype=torch.int32, device=dev)
+    _C.check(_C.fn("rr_text_parse")(_C.ptr(text), text.numel(), _C.ptr(line_pos), nlines, int(ncol), _C.ptr(rows),
+                                    _C.ptr(flags), _C.stream()), "rr_text_parse")
+    return rows, flags
+
+
+def _check_rows6(who, rows6):
+    if rows6.dtype != torch.float32 or rows6.dim() != 2 or rows6.shape[1] != 6 or not rows6.is_contiguous():
+        raise ValueError("%s: rows must be contiguous float32 [R,6], got %s %s" % (who, rows6.dtype, tuple(rows6.shape)))
+
+
+def text_format_len(rows6, layout, clamp):
+    """rr_text_format_len: -> (len int32 [R], row_flag int32 [R], byte_off int64 [R+1] = the exclusive sum of len)."""
+    _C.require_cuda(rows6)
+    _check_rows6("text_format_len", rows6)
+    r, dev = rows6.shape[0], rows6.device
+    length = torch.empty(r, dtype=torch.int32, device=dev)
+    flag = torch.empty(r, dtype=torch.int32, device=dev)
+    _C.check(_C.fn("rr_text_format_len")(_C.ptr(rows6), r, int(TEXT_LAYOUTS.get(layout, layout)), int(bool(clamp)),
+                                         _C.ptr(length), _C.ptr(flag), _C.stream()), "rr_text_format_len")
+    return length, flag, _exclusive_sum(length)
+
+
+def text_format(rows6, layout, clamp, byte_off, out):
+    """rr_text_format: writes row r to out[byte_off[r] : byte_off[r+1]] (uint8 device buffer) and returns out."""
+    _C.require_cuda(rows6, byte_off, out)
+    _check_rows6("text_format", rows6)
+    if byte_off.dtype != torch.int64 or byte_off.numel() != rows6.shape[0] + 1 or not byte_off.is_contiguous():
+        raise ValueError("text_format: byte_off must be contiguous int64 [R+1]")
+    if out.dtype != torch.uint8 or not out.is_contiguous():
+        raise ValueError("text_format: out must be a contiguous uint8 buffer")
+    _C.check(_C.fn("rr_text_format")(_C.ptr(rows6), rows6.shape[0], int(TEXT_LAYOUTS.get(layout, layout)), int(bool(clamp)),
+                                     _C.ptr(byte_off), _C.ptr(out), out.numel(), _C.stream()), "rr_text_format")
+    return out
+
+
+def _np_ptr(a):
+    return _C.c_void_p(a.ctypes.data) if a is not None else _C.c_void_p(0)
+
+
+def text_parse_host(text, file_off, ncol=8):
+    """The codec's host loops (rr_text_lines_host + rr_text_parse_host) on numpy buffers, no device: text uint8 [N], file_off
+    int64 [F+1] -> (rows float64 [L,ncol], line_flag int32 [L], line_pos int64 [L], file_line_off int64 [F+1])."""
+    import ctypes
+    import numpy as np
+    text = np.ascontiguousarray(text, np.uint8)
+    file_off = np.ascontiguousarray(file_off, np.int64)
+    nfiles = file_off.size - 1
+    file_line_off = np.zeros(nfiles + 1, np.int64)
+    nlines = ctypes.c_long(0)
+    f = _C.fn("rr_text_lines_host")
+    _C.check(f(_np_ptr(text), text.size, _np_ptr(file_off), nfiles, 0, _np_ptr(None), _np_ptr(file_line_off),
+               ctypes.byref(nlines)), "rr_text_lines_host")
+    line_pos = np.zeros(nlines.value, np.int64)
+    _C.check(f(_np_ptr(text), text.size, _np_ptr(file_off), nfiles, line_pos.size, _np_ptr(line_pos), _np_ptr(file_line_off),
+               ctypes.byref(nlines)), "rr_text_lines_host")
+    rows = np.zeros((line_pos.size, ncol), np.float64)
+    flags = np.zeros(line_pos.size, np.int32)
+    _C.check(_C.fn("rr_text_parse_host")(_np_ptr(text), text.size, _np_ptr(line_pos), line_pos.size, int(ncol), _np_ptr(rows),
+                                         _np_ptr(flags)), "rr_text_parse_host")
+    return rows, flags, line_pos, file_line_off
+
+
+def text_format_host(rows6, layout, clamp, pad=0, fill=0):
+    """The codec's host loop (rr_text_format_host) on a numpy [R,6] float32 array, no device -> (out uint8 [total + pad],
+    byte_off int64 [R+1], row_flag int32 [R]); `pad` bytes of `fill` follow the text (the tests look at them)."""
+    import numpy as np
+    rows6 = np.ascontiguousarray(rows6, np.float32).reshape(-1, 6)
+    layout = int(TEXT_LAYOUTS.get(layout, layout))
+    r = rows6.shape[0]
+    length, flag = np.zeros(r, np.int32), np.zeros(r, np.int32)
+    f = _C.fn("rr_text_format_host")
+    _C.check(f(_np_ptr(rows6), r, layout, int(bool(clamp)), _np_ptr(length), _np_ptr(flag), _np_ptr(None), _np_ptr(None), 0),
+             "rr_text_format_host")
+    byte_off = np.zeros(r + 1, np.int64)
+    np.cumsum(length, out=byte_off[1:])
+    out = np.full(int(byte_off[-1]) + pad, fill, np.uint8)
+    _C.check(f(_np_ptr(rows6), r, layout, int(bool(clamp)), _np_ptr(None), _np_ptr(None), _np_ptr(byte_off), _np_ptr(out),
+               int(byte_off[-1])), "rr_text_format_host")
+    return out, byte_off, flag
+
+
 def seg_prefix(n_out):
     """Exclusive prefix of per-segment counts -> int32 [nseg+1] (last entry = total)."""
     nseg = n_out.numel()

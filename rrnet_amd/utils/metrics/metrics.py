@@ -18,6 +18,7 @@ statement and `auto_evaluate_results` mixes tensors and arrays (:286-289) — re
 (xywh float32 array back); evaluate_results / auto_evaluate_results also RETURN (ap, rc) besides printing.
 Quirk kept: detections of a class are dropped (not counted as false positives) in images that hold no ground
 truth of that class (:112-113)."""
+import contextlib
 import glob
 import os
 import time
@@ -144,6 +145,36 @@ def _read(path):
     return np.array(pd.read_csv(path, header=None, float_precision='high'))
 
 
+_TEXT = ["host"]                 # how the device evaluators read their files; text_route() changes it for a block
+
+
+@contextlib.contextmanager
+def text_route(text):
+    """with text_route("device"): evaluate_results(..., device=dev) parses the files on the device as well (rrnet_amd.textio);
+    "host" is the default, pandas per file.  The evaluators' signatures stay the reference's plus `device`."""
+    if text not in ("host", "device"):
+        raise ValueError("text=%r, expected 'host' or 'device'" % (text,))
+    _TEXT.append(text)
+    try:
+        yield
+    finally:
+        _TEXT.pop()
+
+
+def _reader(pred_dir, target_dir, text, device):
+    """path -> rows for the result and annotation files of one evaluation.  text="host": _read itself.  text="device": every
+    file goes through rrnet_amd.textio.read_files once (one upload, the parse kernels, one download; files the codec flags
+    are read by _read), and the function looks the arrays up."""
+    if text == "host":
+        return _read
+    if text != "device":
+        raise ValueError("text=%r, expected 'host' or 'device'" % (text,))
+    from rrnet_amd import textio
+    paths = [os.path.join(d, "{}.txt".format(name)) for name in _names(pred_dir) for d in (pred_dir, target_dir)]
+    arrays, _ = textio.read_files(paths, device, host_read=_read)
+    return dict(zip(paths, arrays)).__getitem__
+
+
 def _names(pred_dir):
     return [os.path.splitext(os.path.basename(x))[0] for x in glob.glob(os.path.join(pred_dir, '*.txt'))]
 
@@ -166,7 +197,7 @@ def _report(ap, rc, st):
 
 def evaluate_results(pred_dir, target_dir, thresholds=THRESHOLDS, cls_num=11, max_det_num=500, device=None):
     if device is not None:
-        return _evaluate_results_device(pred_dir, target_dir, thresholds, cls_num, max_det_num, device)
+        return _evaluate_results_device(pred_dir, target_dir, thresholds, cls_num, max_det_num, device, text=_TEXT[-1])
     st = time.time()
     flags, confs, tc, ic = _fresh(cls_num, thresholds.size(0))
     for name in _names(pred_dir):
@@ -220,7 +251,7 @@ def auto_evaluate_results(pred_dir, target_dir, ctnet_min_threshold, softnms_min
                           cls_num=11, max_det_num=500, device=None):
     if device is not None:
         return _auto_evaluate_results_device(pred_dir, target_dir, ctnet_min_threshold, softnms_min_threshold,
-                                             thresholds, cls_num, max_det_num, device)
+                                             thresholds, cls_num, max_det_num, device, text=_TEXT[-1])
     st = time.time()
     names = _names(pred_dir)
     preds, targets = [], []
@@ -326,27 +357,29 @@ def evaluate_arrays(preds, targets, thresholds=THRESHOLDS, cls_num=11, max_det_n
     return ap, rc, {"flags": flags, "confs": confs, "target_count": tc, "in_img_count": ic}
 
 
-def _evaluate_results_device(pred_dir, target_dir, thresholds, cls_num, max_det_num, device):
+def _evaluate_results_device(pred_dir, target_dir, thresholds, cls_num, max_det_num, device, text="host"):
     st = time.time()
     preds, targets = [], []
+    read = _reader(pred_dir, target_dir, text, device)
     for name in _names(pred_dir):
-        pred = _snap(_read(os.path.join(pred_dir, "{}.txt".format(name))).astype(np.float64))
+        pred = _snap(read(os.path.join(pred_dir, "{}.txt".format(name))).astype(np.float64))
         preds.append(torch.from_numpy(pred).float()[:max_det_num, :6])
-        targets.append(torch.from_numpy(_read(os.path.join(target_dir, "{}.txt".format(name)))).float()[:max_det_num, :6])
+        targets.append(torch.from_numpy(read(os.path.join(target_dir, "{}.txt".format(name)))).float()[:max_det_num, :6])
     ap, rc, _ = _evaluate_device(preds, targets, thresholds, cls_num, torch.device(device))
     _report(ap, rc, st)
     return ap, rc
 
 
 def _auto_evaluate_results_device(pred_dir, target_dir, ctnet_min_threshold, softnms_min_threshold, thresholds, cls_num,
-                                  max_det_num, device):
+                                  max_det_num, device, text="host"):
     st = time.time()
     preds, targets = [], []
+    read = _reader(pred_dir, target_dir, text, device)
     for name in _names(pred_dir):
-        pred = _read(os.path.join(pred_dir, "{}.txt".format(name)))
+        pred = read(os.path.join(pred_dir, "{}.txt".format(name)))
         pred = torch.from_numpy(pred[pred[:, 4] > ctnet_min_threshold]).float()
         preds.append(pred[torch.sort(pred[:, 4], descending=True, stable=True)[1]])
-        targets.append(torch.from_numpy(_read(os.path.join(target_dir, "{}.txt".format(name)))).float()[:max_det_num, :6])
+        targets.append(torch.from_numpy(read(os.path.join(target_dir, "{}.txt".format(name)))).float()[:max_det_num, :6])
     kept = ext_nms_batch(preds, softnms_min_threshold)
     preds = []
     for pred in kept:
@@ -357,12 +390,13 @@ def _auto_evaluate_results_device(pred_dir, target_dir, ctnet_min_threshold, sof
     return ap, rc
 
 
-def _sweep_read(pred_dir, target_dir, ctnet_min_thresholds, max_det_num):
+def _sweep_read(pred_dir, target_dir, ctnet_min_thresholds, max_det_num, text="host", device=None):
     """Every file once -> score-sorted float32 detections, per (ctnet threshold, file) how many of them pass the score
     filter (a prefix: the filter compares the parsed float64 score as auto_evaluate_results does), cut annotations."""
     preds, targets, lens = [], [], []
+    read = _reader(pred_dir, target_dir, text, device)
     for name in _names(pred_dir):
-        raw = _read(os.path.join(pred_dir, "{}.txt".format(name)))
+        raw = read(os.path.join(pred_dir, "{}.txt".format(name)))
         order = torch.sort(torch.from_numpy(raw[:, 4]).float(), descending=True, stable=True)[1].numpy()
         raw = raw[order]
         row = []
@@ -374,7 +408,7 @@ def _sweep_read(pred_dir, target_dir, ctnet_min_thresholds, max_det_num):
             row.append(n)
         lens.append(row)
         preds.append(torch.from_numpy(raw).float()[:, :6])
-        targets.append(torch.from_numpy(_read(os.path.join(target_dir, "{}.txt".format(name)))).float()[:max_det_num, :6])
+        targets.append(torch.from_numpy(read(os.path.join(target_dir, "{}.txt".format(name)))).float()[:max_det_num, :6])
     return preds, targets, np.asarray(lens, np.int32).reshape(len(preds), len(ctnet_min_thresholds)).T
 
 
@@ -432,7 +466,7 @@ def sweep_evaluate_results(pred_dir, target_dir, ctnet_min_thresholds, softnms_m
                 out[i, j, :-1], out[i, j, -1] = ap.numpy(), float(rc)
         return out
     device = torch.device(device)
-    preds, targets, lens = _sweep_read(pred_dir, target_dir, ctnet_min_thresholds, max_det_num)
+    preds, targets, lens = _sweep_read(pred_dir, target_dir, ctnet_min_thresholds, max_det_num, text=_TEXT[-1], device=device)
     dets, _ = _pad(preds, device)
     gts, gt_len = _pad(targets, device)
     lens = torch.from_numpy(np.ascontiguousarray(lens)).to(device)

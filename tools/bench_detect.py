@@ -131,6 +131,8 @@ def main(argv=None):
 
     pool = GeneratedFrames(args.frames)
     out_dir = tempfile.mkdtemp(prefix="bench_detect_")
+    dev_dir = tempfile.mkdtemp(prefix="bench_detect_devtext_")           # the same files, written through rrnet_amd.textio
+    from rrnet_amd import textio
     result = {"metric": "frames/sec, raw frame -> result file (%s detection)"
                         % ("single-scale RetinaNet" if args.retinanet else "multi-scale CenterNet flip" if args.centernet
                            else "multi-scale RRNet"), "unit": "frames/sec",
@@ -192,7 +194,8 @@ def main(argv=None):
             return time.perf_counter() - t0, writer, boxes, None
 
         def batched_window(w, batch):
-            writer, boxes = 0.0, 0
+            writer, writer_dev, boxes = 0.0, 0.0, 0
+            layout = "retinanet" if args.retinanet else "centernet" if args.centernet else "rrnet"
             marks = []
 
             def timer(stage):
@@ -216,28 +219,34 @@ def main(argv=None):
                     for i, name in enumerate(names):
                         Operator.write_results(os.path.join(out_dir, name + ".txt"), rows[off[i]:off[i + 1]])
                 writer += time.perf_counter() - t1
+                t1 = time.perf_counter()                  # the same files once more through the device codec (textio)
+                textio.write_frames([os.path.join(dev_dir, name + ".txt") for name in names], pred, off, layout, True)
+                writer_dev += time.perf_counter() - t1
                 boxes += rows.shape[0]
             torch.cuda.synchronize()
-            dt = time.perf_counter() - t0
+            dt = time.perf_counter() - t0 - writer_dev    # the frames/s are those of the host writer, as before
             stages = {"prepare": 0.0, "model": 0.0, "post": 0.0}
             for (_, a), (stage, b) in zip(marks, marks[1:]):
                 if stage != "start":
                     stages[stage] += a.elapsed_time(b)
-            return dt, writer, boxes, stages
+            return dt, writer, boxes, stages, writer_dev
 
         def run(name, fn):
             torch.cuda.reset_peak_memory_stats()
             rows = []
             for w in range(args.windows + 1):
-                dt, writer, boxes, stages = fn(w)
+                r = fn(w)
+                dt, writer, boxes, stages = r[:4]
                 print("  %s %s window %d: %.2f s" % (mode, name, w, dt), file=sys.stderr, flush=True)
                 if w > 0:                                                   # window 0 warms up
-                    rows.append((args.window_frames / dt, writer, boxes, stages))
+                    rows.append((args.window_frames / dt, writer, boxes, stages, r[4] if len(r) > 4 else None))
             fps = [r[0] for r in rows]
             rec = {"frames_per_sec": round(statistics.median(fps), 3), "frames_per_sec_windows": [round(v, 3) for v in fps],
                    "writer_ms_per_frame": round(1e3 * statistics.median(r[1] for r in rows) / args.window_frames, 3),
                    "boxes_per_frame": rows[0][2] / args.window_frames,
                    "allocator_peak_gib": round(torch.cuda.max_memory_allocated() / 2 ** 30, 3)}
+            if rows[0][4] is not None:
+                rec["writer_device_ms_per_frame"] = round(1e3 * statistics.median(r[4] for r in rows) / args.window_frames, 3)
             if rows[0][3] is not None:
                 rec["device_ms_per_frame"] = {k: round(statistics.median(r[3][k] for r in rows) / args.window_frames, 3)
                                               for k in rows[0][3]}

@@ -71,6 +71,7 @@ def main():
     ap.add_argument("--dets", type=int, default=500)
     ap.add_argument("--annos", type=int, default=120)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--host-text", action="store_true", help="the device line parses the files on the host (pandas), as before")
     a = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -101,16 +102,21 @@ def main():
         print("host evaluate_results ...", file=sys.stderr, flush=True)
         host, res["host_evaluate_results_s"] = timed(M.evaluate_results, pd_dir, gt_dir)
         print("device evaluate_results ...", file=sys.stderr, flush=True)
-        got, total = timed(M.evaluate_results, pd_dir, gt_dir, device=dev)
+        text = "host" if a.host_text else "device"
+        res["text"] = text
+        with M.text_route(text):
+            timed(M.evaluate_results, pd_dir, gt_dir, device=dev)                        # warm-up of the text route
+            got, total = timed(M.evaluate_results, pd_dir, gt_dir, device=dev)
 
         max_det = 500                                           # the drivers' default max_det_num
 
         def parse():
             preds, targets = [], []
+            read = M._reader(pd_dir, gt_dir, text, dev)           # pandas per file, or one pass of rrnet_amd.textio
             for name in M._names(pd_dir):
-                pred = M._snap(M._read(os.path.join(pd_dir, name + ".txt")).astype(np.float64))
+                pred = M._snap(read(os.path.join(pd_dir, name + ".txt")).astype(np.float64))
                 preds.append(torch.from_numpy(pred).float()[:max_det, :6])
-                targets.append(torch.from_numpy(M._read(os.path.join(gt_dir, name + ".txt"))).float()[:max_det, :6])
+                targets.append(torch.from_numpy(read(os.path.join(gt_dir, name + ".txt"))).float()[:max_det, :6])
             return preds, targets
         (preds, targets), t_parse = timed(parse)
         (dets, det_len, gts, gt_len), t_up = timed(lambda: M._pad(preds, dev) + M._pad(targets, dev))
@@ -121,7 +127,8 @@ def main():
         print("host auto_evaluate_results pair ...", file=sys.stderr, flush=True)
         pair, res["host_auto_pair_s"] = timed(M.auto_evaluate_results, pd_dir, gt_dir, CTNET_MIN[0], SOFTNMS_MIN[0])
         print("device sweep ...", file=sys.stderr, flush=True)
-        sweep, t_sweep = timed(M.sweep_evaluate_results, pd_dir, gt_dir, CTNET_MIN, SOFTNMS_MIN, device=dev)
+        with M.text_route(text):
+            sweep, t_sweep = timed(M.sweep_evaluate_results, pd_dir, gt_dir, CTNET_MIN, SOFTNMS_MIN, device=dev)
         first = (torch.from_numpy(sweep[0, 0, :-1]), torch.tensor(sweep[0, 0, -1]))
         res["device_sweep"] = {"pairs": len(CTNET_MIN) * len(SOFTNMS_MIN), "total_s": t_sweep,
                                "per_pair_s": t_sweep / (len(CTNET_MIN) * len(SOFTNMS_MIN)),

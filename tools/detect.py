@@ -106,6 +106,8 @@ def main(argv=None):
     ap.add_argument("--tile-zoom", type=float, help="resize every tile by this factor in front of the model (default 1)")
     ap.add_argument("--tile-margin", type=float, help="drop boxes within this many input pixels of a cutting tile side (default 0)")
     ap.add_argument("--tile-batch", type=int, help="tiles per model pass (default 8)")
+    ap.add_argument("--host-text", action="store_true",
+                    help="format the result files on the host (write_results) instead of on the device (rrnet_amd/textio.py)")
     args = ap.parse_args(argv)
     cfg = load_config(args.config)
     retinanet = args.config.startswith("retinanet")
@@ -134,7 +136,7 @@ def main(argv=None):
     import torch
     from rrnet_amd import ops
     from rrnet_amd.datasets.frames import FrameFolder, SizeBucketedFrames
-    from rrnet_amd import inference
+    from rrnet_amd import inference, textio
     if centernet:
         from rrnet_amd.operators.centernet_operator import CenterNetOperator as Operator
         per_scale, what = (2 if args.flip else 1) * 250, "%d x 250" % (2 if args.flip else 1)
@@ -160,11 +162,15 @@ def main(argv=None):
     t0, frames_done, boxes_done = time.perf_counter(), 0, 0
     for frames_u8, names in SizeBucketedFrames(folder, args.batch, num_workers=args.workers):
         boxes, frame_off = detector.detect(frames_u8, scales=scales, nms=nms, **extra)
-        rows, off = boxes.cpu().numpy(), frame_off.cpu().tolist()             # one copy per batch
-        for i, name in enumerate(names):
-            Operator.write_results(os.path.join(args.out, name + ".txt"), rows[off[i]:off[i + 1]])
+        if args.host_text or not boxes.is_cuda:               # rows on the device are formatted there
+            rows, off = boxes.cpu().numpy(), frame_off.cpu().tolist()             # one copy per batch
+            for i, name in enumerate(names):
+                Operator.write_results(os.path.join(args.out, name + ".txt"), rows[off[i]:off[i + 1]])
+        else:                                                 # the batch's files in one launch sequence, the same bytes
+            textio.write_frames([os.path.join(args.out, name + ".txt") for name in names], boxes, frame_off,
+                                "centernet" if centernet else "rrnet", True)
         frames_done += len(names)
-        boxes_done += rows.shape[0]
+        boxes_done += boxes.shape[0]
     dt = time.perf_counter() - t0
     print("%d frames, %d boxes -> %s in %.2f s (%.2f frames/s, %s, %d scales, batch %d%s)"
           % (frames_done, boxes_done, args.out, dt, frames_done / dt, "nms" if nms else "raw", len(scales), args.batch,
@@ -199,6 +205,12 @@ def main_retinanet(args, cfg):
     torch.manual_seed(219)
     detector = inference.RetinaNetFrameDetector(cfg, None if args.random_weights else args.checkpoint)
     score_thr = 0.1 if args.score_thr is None else args.score_thr
+
+    def write(out, names, boxes, frame_off):                  # rows on the device are formatted there
+        if args.host_text or not boxes.is_cuda:
+            RetinaNetOperator.write_results(out, names, boxes, frame_off)
+        else:
+            RetinaNetOperator.write_results_device(out, names, boxes, frame_off)
     pick = args.random_weights and args.score_thr is None
     t0, frames_done, boxes_done = time.perf_counter(), 0, 0
     if args.tile is not None:
@@ -216,7 +228,7 @@ def main_retinanet(args, cfg):
                 pick = False
             boxes, frame_off = detector.detect_tiled(frames, tl["tile"], tl["overlap"], zoom=tl["zoom"], margin=tl["margin"],
                                                      tile_batch=tl["batch"], score_thr=score_thr)
-            RetinaNetOperator.write_results(args.out, names, boxes, frame_off.cpu())         # one copy per batch
+            write(args.out, names, boxes, frame_off.cpu())                                    # one copy per batch
             frames_done += len(names)
             boxes_done += boxes.shape[0]
         dt = time.perf_counter() - t0
@@ -232,7 +244,7 @@ def main_retinanet(args, cfg):
             print("random weights: score threshold %.9g keeps %s anchors of the first batch's frames" % (score_thr, counts))
             pick = False
         boxes, frame_off = detector.detect(frames_u8, score_thr=score_thr)
-        RetinaNetOperator.write_results(args.out, names, boxes, frame_off.cpu())             # one copy per batch
+        write(args.out, names, boxes, frame_off.cpu())                                        # one copy per batch
         frames_done += len(names)
         boxes_done += boxes.shape[0]
     dt = time.perf_counter() - t0

@@ -31,6 +31,8 @@ def parse_args(argv=None):
     ap.add_argument("--method", choices=("wbf", "soft-nms"), default="wbf")
     ap.add_argument("--targets", default=None, metavar="DIR", help="annotation folder: print the AP of the runs and the output")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--host-text", action="store_true",
+                    help="read and write the files on the host (pandas, formatted writes) instead of on the device")
     args = ap.parse_args(argv)
     if args.weights is not None:
         if len(args.weights) != len(args.runs):
@@ -53,16 +55,16 @@ def parse_args(argv=None):
     return args
 
 
-def soft_nms_dirs(dirs, out_dir, threshold, max_det):
+def soft_nms_dirs(dirs, out_dir, threshold, max_det, text="host"):
     """The baseline: per frame the concatenation of the runs through ext_nms_batch, score-descending, max_det rows."""
     from rrnet_amd import ensemble
     from rrnet_amd.utils.metrics.metrics import ext_nms_batch
-    names, sets, missing = ensemble.read_result_dirs(dirs)
+    names, sets, missing = ensemble.read_result_dirs(dirs, text=text)
     print("%d files of %d runs, %d missing (counted as no detections)" % (len(names), len(dirs), missing))
     cat = [np.concatenate([np.asarray(s[f])[:, :6] for s in sets], 0).astype(np.float32) for f in range(len(names))]
     kept = ext_nms_batch(cat, threshold) if names else []
     frames = [k[np.argsort(-k[:, 4], kind="stable")][:max_det] for k in kept]
-    ensemble.write_result_dir(out_dir, names, frames)
+    ensemble.write_result_dir(out_dir, names, frames, text=text)
     return missing
 
 
@@ -71,18 +73,20 @@ def main(argv=None):
     import torch
     from rrnet_amd import ensemble
     torch.cuda.set_device(args.device)
+    text = "host" if args.host_text else "device"
     if args.method == "wbf":
         ensemble.fuse_result_dirs(args.runs, args.out, weights=args.weights, iou_thr=args.iou, skip_score=args.skip_score,
-                                  conf_type=args.conf, max_det=args.max_det)
+                                  conf_type=args.conf, max_det=args.max_det, text=text)
     else:
-        soft_nms_dirs(args.runs, args.out, args.skip_score, args.max_det)
+        soft_nms_dirs(args.runs, args.out, args.skip_score, args.max_det, text=text)
     print("wrote %s" % args.out)
     if args.targets is not None:
-        from rrnet_amd.utils.metrics.metrics import evaluate_results
+        from rrnet_amd.utils.metrics.metrics import evaluate_results, text_route
         dev = torch.device("cuda", args.device)
         for d in list(args.runs) + [args.out]:
             print("== %s" % d)
-            evaluate_results(d, args.targets, max_det_num=args.max_det, device=dev)
+            with text_route(text):
+                evaluate_results(d, args.targets, max_det_num=args.max_det, device=dev)
     return 0
 
 
