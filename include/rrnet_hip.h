@@ -441,6 +441,54 @@ int rr_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg
  * dst receives the bits of src unchanged (copied as integers: NaN payloads, -0.0, denormals); words of dst beyond n
  * are not written.  src and dst must be 16-byte aligned.  n >= 0; n == 0 launches nothing and succeeds. */
 int rr_state_snapshot(const float *src, float *dst, long n, long chunk, unsigned long long *digest, hipStream_t stream);
+/* The guarded optimiser step (csrc/optim.hip): gradient-norm clipping, a skip on non-finite gradients and an
+ * exponential moving average (EMA) of the weights, decided and applied on the device; the host never reads `ctl` to run a
+ * step.  Three launches on one stream: rr_grad_norm, rr_guard_decide, rr_adam_step_guarded.
+ *
+ * rr_grad_norm: grad holds n fp32 words, n % 4 == 0, 16-byte aligned; n == 0 launches nothing.  The grid is
+ *   rr_grad_norm_blocks(n) workgroups of RR_GRAD_NORM_THREADS lanes, a function of n alone and capped: the host sizes
+ *   partial [blocks] (double) and bad [blocks] (int) from it.  Global lane t of T = blocks * RR_GRAD_NORM_THREADS visits the
+ *   16-byte vectors t, t + T, t + 2T, ... and adds the squares of their words, in index order, in double (a float squared
+ *   is exact in double); a word with (bits & 0x7f800000) == 0x7f800000 (NaN, +-Inf) is counted and adds 0, so the sum
+ *   stays finite.  Lanes are added by an xor butterfly over the wave (offsets 32, 16, ..., 1), the four waves in order.
+ *   partial[b] and bad[b] are written, not accumulated.  No atomics: a run repeats bit for bit.
+ * rr_guard_decide: one workgroup.  Lane t adds partial[t], partial[t + RR_GRAD_NORM_THREADS], ... in order, then the same
+ *   butterfly -> S; B = sum of bad.  blocks <= the cap of rr_grad_norm_blocks; blocks == 0 means S = 0, B = 0.  ctl holds
+ *   RR_GUARD_CTL_WORDS doubles (a fresh record: all 0 except beta1_pow = beta2_pow = 1):
+ *     0 applied     steps applied so far              10 step_size  lr / (1 - beta1_pow)
+ *     1 skipped     steps skipped so far              11 bc2_sqrt   sqrt(1 - beta2_pow)
+ *     2 clipped     steps clipped so far              12 ema_d      EMA decay of this step
+ *     3 beta1_pow   running product of beta1          13 ema_omd    1 - that decay
+ *     4 beta2_pow   running product of beta2          14, 15        zero
+ *     5 norm        this step's gradient norm         16 b1         (float)beta1
+ *     6 norm_max    largest finite norm seen          17 omb1       (float)(1 - beta1)
+ *     7 bad         non-finite words of this step     18 b2         (float)beta2
+ *     8 skip        0 or 1                            19 omb2       (float)(1 - beta2)
+ *     9 scale       factor applied to the gradient
+ *   Slots 9-13 and 16-19 hold values already rounded to float (the record was widened from 16 words for the four beta
+ *   floats that rr_adam_step_guarded needs).  All in double, every operation rounded on its own (no fused multiply-add):
+ *     norm = sqrt(S) * grad_scale, or +inf when B > 0;   skip = skip_nonfinite && (B > 0 || !isfinite(norm)).
+ *     skip: skipped += 1; bad, norm and skip are written; nothing else changes.
+ *     otherwise: coef = 1 when max_norm is +inf or norm is not finite, else min(1, max_norm / (norm + 1e-6))
+ *       (torch.nn.utils.clip_grad_norm_); clipped += (coef < 1); scale = (float)(grad_scale * coef); applied += 1;
+ *       beta1_pow *= beta1; beta2_pow *= beta2 (running products: a skipped step does not advance Adam's bias correction,
+ *       and a host restatement is exact); step_size = (float)(lr / (1 - beta1_pow)); bc2_sqrt = (float)sqrt(1 - beta2_pow);
+ *       d = ema_decay, or with ema_warmup min(ema_decay, (1 + applied) / (10 + applied)) with the new `applied`;
+ *       ema_d = (float)d; ema_omd = (float)(1 - d); norm_max = max(norm_max, norm) when norm is finite.
+ *   grad_scale finite and > 0; max_norm > 0 (+inf: no clipping); betas in [0, 1); ema_decay in [0, 1].
+ * rr_adam_step_guarded: every lane reads ctl with ordinary loads.  skip != 0: returns with param, exp_avg, exp_avg_sq and
+ *   ema untouched bit for bit.  Otherwise rr_adam_step's arithmetic with scale, step_size, bc2_sqrt and the four beta
+ *   floats from ctl, and with ema != NULL  ema = ema * ema_d + param_new * ema_omd  in the same pass.  n % 4 == 0, every
+ *   buffer 16-byte aligned. */
+#define RR_GUARD_CTL_WORDS 20
+#define RR_GRAD_NORM_THREADS 256
+int rr_grad_norm_blocks(long n);
+int rr_grad_norm(const float *grad, long n, double *partial, int *bad, hipStream_t stream);
+int rr_guard_decide(const double *partial, const int *bad, int blocks, double grad_scale, double max_norm,
+                    int skip_nonfinite, double lr, double beta1, double beta2, double ema_decay, int ema_warmup,
+                    double *ctl, hipStream_t stream);
+int rr_adam_step_guarded(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, float *ema,
+                         long n, float eps, const double *ctl, hipStream_t stream);
 
 /* ---- losses --------------------------------------------------------------------------- *
  * rr_focal_loss_fwd/bwd: clamp(sigmoid(x),1e-4,1-1e-4) + focal_loss_for_hm of

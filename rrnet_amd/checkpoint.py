@@ -5,6 +5,9 @@ The state: FlatParams.flat, FlatAdam.exp_avg / exp_avg_sq / step_count, the lear
 state_dict, every module buffer by name (BatchNorm running statistics; num_batches_tracked as int64), the step index,
 the training loader's position, and a fingerprint of the flat buffer's layout.  Random-number-generator states are not
 part of it: no kernel of the step consumes a random number, and the loaders draw from (seed, rank, epoch, index).
+With the guarded optimiser step on two optional entries join it: `ema`, the averaged weights, a fourth flat
+buffer handled like the other three, and `guard`, the step's control record; a file taken without them is unchanged, and
+extras_plan() says what a load does with each combination of file and live optimiser.
 
 Taking it (StateWriter.save_state, on the training stream): join the auxiliary streams, three rr_state_snapshot launches
 (copy + digest in one pass) into device staging buffers, the buffers packed into staging tensors, one event.  A copy
@@ -99,6 +102,42 @@ def compare_fingerprint(saved, live):
         raise StateError("flat buffer length differs: saved %d, live %d" % (saved["numel"], live["numel"]))
 
 
+def state_names(optimizer):
+    """The flat buffers a state of this optimiser holds, in digest order: FLAT_NAMES, and `ema` behind them when the
+    optimiser keeps averaged weights (FlatAdam(ema_decay=...)).  Without the option the list, and with it the file, is
+    the one of format 1 as it always was."""
+    return FLAT_NAMES + (("ema",) if getattr(optimizer, "ema", None) is not None else ())
+
+
+def guard_ctl_from_step_count(step_count, beta1, beta2):
+    """The guard's control record (float64, ops.GUARD_CTL_WORDS) for an optimiser that took `step_count` unguarded steps:
+    applied = step_count, the two running products by step_count host multiplications (what the device would have done
+    one step at a time), every other counter 0.  The per-step slots are rewritten by the next decide launch."""
+    from rrnet_amd import ops
+    ctl = ops.guard_ctl_fresh().numpy().copy()
+    b1p = b2p = 1.0
+    for _ in range(int(step_count)):
+        b1p *= float(beta1)
+        b2p *= float(beta2)
+    ctl[0], ctl[3], ctl[4] = float(int(step_count)), b1p, b2p
+    return ctl
+
+
+def extras_plan(sd, optimizer):
+    """What load_state does with the two optional entries of a state file, decided on the host from the file's keys and
+    the live optimiser's options -> (ema, guard):
+      ema:   'restore' (file has it, EMA on: verify its digest, copy it in), 'init' (file lacks it, EMA on: start the
+             average from the loaded weights, with a warning), 'ignore' (file has it, EMA off: a note), None;
+      guard: 'restore' (file has it, a guard is on), 'derive' (file lacks it, a guard is on: guard_ctl_from_step_count),
+             None (no guard on; an entry in the file is not needed)."""
+    has_ema, want_ema = "ema" in sd, getattr(optimizer, "ema", None) is not None
+    ema = ("restore" if has_ema else "init") if want_ema else ("ignore" if has_ema else None)
+    guard = None
+    if getattr(optimizer, "ctl", None) is not None:
+        guard = "restore" if "guard" in sd else "derive"
+    return ema, guard
+
+
 def _buffer_index(module):
     """Buffers grouped by dtype: {dtype name: [(buffer name, shape, offset into that dtype's packed tensor)]}, and the
     packed lengths."""
@@ -146,15 +185,21 @@ class StateWriter:
         self._staged = False
 
     def _sources(self):
-        return (self.fp.flat, self.opt.exp_avg, self.opt.exp_avg_sq)
+        src = (self.fp.flat, self.opt.exp_avg, self.opt.exp_avg_sq)
+        return src + ((self.opt.ema,) if len(self.names) > len(FLAT_NAMES) else ())
 
     def _allocate(self):
         n = self.fp.numel
         nchunks = (n + self.chunk - 1) // self.chunk
-        self.d_stage = [torch.empty(n, dtype=torch.float32, device=self.device) for _ in FLAT_NAMES]
-        self.d_digest = torch.empty((len(FLAT_NAMES), nchunks, 3), dtype=torch.int64, device=self.device)
-        self.h_stage = [torch.empty(n, dtype=torch.float32).pin_memory() for _ in FLAT_NAMES]
-        self.h_digest = torch.empty((len(FLAT_NAMES), nchunks, 3), dtype=torch.int64).pin_memory()
+        self.names = state_names(self.opt)                # the averaged weights are a fourth source when they exist
+        self.d_stage = [torch.empty(n, dtype=torch.float32, device=self.device) for _ in self.names]
+        self.d_digest = torch.empty((len(self.names), nchunks, 3), dtype=torch.int64, device=self.device)
+        self.h_stage = [torch.empty(n, dtype=torch.float32).pin_memory() for _ in self.names]
+        self.h_digest = torch.empty((len(self.names), nchunks, 3), dtype=torch.int64).pin_memory()
+        self.d_guard = self.h_guard = None                # the guard's control record, when a guard is on
+        if getattr(self.opt, "ctl", None) is not None:
+            self.d_guard = torch.empty_like(self.opt.ctl)
+            self.h_guard = torch.empty(self.opt.ctl.shape, dtype=torch.float64).pin_memory()
         self.buf_index, sizes = _buffer_index(self.module)
         self.d_bufs = {k: torch.empty(sz, dtype=getattr(torch, k), device=self.device) for k, sz in sizes.items()}
         self.h_bufs = {k: torch.empty(sz, dtype=getattr(torch, k)).pin_memory() for k, sz in sizes.items()}
@@ -183,6 +228,8 @@ class StateWriter:
         ops.join_aux_streams(self.device)                 # weight gradients / Adam's producers on their side streams
         for i, src in enumerate(self._sources()):
             ops.state_snapshot(src, self.d_stage[i], self.chunk, out=self.d_digest[i])
+        if self.d_guard is not None:
+            self.d_guard.copy_(self.opt.ctl)               # on the training stream, behind the step that wrote it
         bufs = dict(self.module.named_buffers())
         for k, rows in self.buf_index.items():            # one gather per dtype into its packed staging tensor
             torch.cat([bufs[name].detach().reshape(-1) for name, _, _ in rows], out=self.d_bufs[k])
@@ -199,6 +246,8 @@ class StateWriter:
             for h, d in zip(self.h_stage, self.d_stage):
                 h.copy_(d, non_blocking=True)
             self.h_digest.copy_(self.d_digest, non_blocking=True)
+            if self.d_guard is not None:
+                self.h_guard.copy_(self.d_guard, non_blocking=True)
             for k in self.d_bufs:
                 self.h_bufs[k].copy_(self.d_bufs[k], non_blocking=True)
             landed = torch.cuda.Event()
@@ -212,11 +261,13 @@ class StateWriter:
         bad = self.h_digest[:, :, 2].sum(dim=1).tolist()
         if any(bad):
             self.warnings.append("state of step %d not written: %s; the previous state file stays"
-                                 % (meta["step"], ", ".join("%s holds %d NaN/Inf" % (n, c) for n, c in zip(FLAT_NAMES, bad) if c)))
+                                 % (meta["step"], ", ".join("%s holds %d NaN/Inf" % (n, c) for n, c in zip(self.names, bad) if c)))
             return None
         obj = dict(meta)
-        for name, h in zip(FLAT_NAMES, self.h_stage):
+        for name, h in zip(self.names, self.h_stage):
             obj[name] = h
+        if self.h_guard is not None:
+            obj["guard"] = self.h_guard
         obj["digests"] = self.h_digest
         obj["buffers"] = dict(self.h_bufs)
         os.makedirs(self.log_dir, exist_ok=True)
@@ -271,8 +322,20 @@ def load_state(path, module, optimizer, lr_sch=None, loader=None):
     chunk = int(sd["chunk"])
     stored = sd["digests"]
     live = (fp.flat, optimizer.exp_avg, optimizer.exp_avg_sq)
+    names = FLAT_NAMES
+    ema_plan, guard_plan = extras_plan(sd, optimizer)
+    if ema_plan == "restore":       # a fourth flat buffer, checked and copied like the other three
+        live, names = live + (optimizer.ema,), names + ("ema",)
+        if stored.shape[0] < len(names):
+            raise StateError("%s: holds ema but no digest of it" % path)
+    if guard_plan == "restore":
+        g = sd["guard"]
+        if not torch.is_tensor(g) or g.dtype != torch.float64 or g.numel() != optimizer.ctl.numel():
+            raise StateError("%s: guard record has %s, the live one %d float64 words"
+                             % (path, "%d %s words" % (g.numel(), g.dtype) if torch.is_tensor(g) else type(g).__name__,
+                                optimizer.ctl.numel()))
     uploaded = []
-    for i, name in enumerate(FLAT_NAMES):
+    for i, name in enumerate(names):
         t = sd[name]
         if t.dtype != torch.float32 or t.numel() != fp.numel:
             raise StateError("%s: %s has %d %s words, the live buffer %d float32" % (path, name, t.numel(), t.dtype, fp.numel))
@@ -283,10 +346,21 @@ def load_state(path, module, optimizer, lr_sch=None, loader=None):
     for i, (dst, u) in enumerate(zip(live, uploaded)):
         dst.copy_(u)                                      # in place: the version counters move
         if not _same_digest(ops.state_snapshot(dst, None, chunk).cpu(), stored[i]):
-            raise StateError("%s: digest of the live %s differs after the copy" % (path, FLAT_NAMES[i]))
+            raise StateError("%s: digest of the live %s differs after the copy" % (path, names[i]))
     del uploaded
     fp.invalidate_wt()              # flipped-filter cache, bf16 filter copies, split-operand filter maxima
     optimizer.step_count = int(sd["step_count"])
+    if ema_plan == "init":
+        optimizer.ema.copy_(fp.flat)
+        print("warning: %s holds no averaged weights: the average starts from the loaded weights" % path, flush=True)
+    elif ema_plan == "ignore":
+        print("note: %s holds averaged weights; the optimiser keeps none (ema_decay is not set), they are not loaded" % path,
+              flush=True)
+    if guard_plan == "restore":
+        optimizer.ctl.copy_(sd["guard"].reshape(optimizer.ctl.shape))
+    elif guard_plan == "derive":    # a state taken without a guard: Adam's bias correction continues from its step count
+        b1, b2 = optimizer.param_groups[0]["betas"]
+        optimizer.ctl.copy_(torch.from_numpy(guard_ctl_from_step_count(optimizer.step_count, b1, b2)))
     optimizer.param_groups[0]["lr"] = float(sd["lr"])
     if lr_sch is not None and sd["lr_sch"] is not None:
         lr_sch.load_state_dict(sd["lr_sch"])

@@ -69,6 +69,7 @@ class FlatParams:
                 start, need = end, 0
         self._index_of = {id(p): i for i, p in enumerate(params)}
         self._offs = {id(p): o for p, o in zip(params, offs)}
+        self._names = {id(p): name for name, p in module.named_parameters()}
         # flipped / transposed copies of the 4-D filters for the stride-1 data gradients (rr_conv_dgrad_s1*): one flat
         # buffer with the parameters' offsets, filled by ONE launch per optimizer step instead of one launch per layer
         # inside backward (lazily allocated at the first data gradient)
@@ -167,6 +168,22 @@ class FlatParams:
             return None, None
         o = self._offs[id(p)]
         return self.w16_flat[o:o + p.numel()], self.wt16_flat[o:o + p.numel()]
+
+    def views_of(self, flat_like):
+        """{parameter name: view in the parameter's logical shape} of any buffer with this flat layout (the averaged
+        weights, a moment buffer): the slices and the OHWI -> [K,C,R,S] permutation that __init__ gives the parameters."""
+        if flat_like.dim() != 1 or flat_like.numel() != self.numel:
+            raise ValueError("views_of: expected a flat buffer of %d words, got %s" % (self.numel, tuple(flat_like.shape)))
+        views = {}
+        for p in self.params:
+            o, n = self._offs[id(p)], p.numel()
+            if p.dim() == 4:
+                k, c, r, s = p.shape
+                v = flat_like[o:o + n].view(k, r, s, c).permute(0, 3, 1, 2)
+            else:
+                v = flat_like[o:o + n].view(p.shape)
+            views[self._names[id(p)]] = v
+        return views
 
     def _begin_step(self):
         nb = len(self._bucket_range)
@@ -273,17 +290,65 @@ class FlatParams:
 class FlatAdam(torch.optim.Optimizer):
     """torch.optim.Adam semantics (defaults of operators/rrnet_operator.py:29: betas (0.9,0.999),
     eps 1e-8, no weight decay, no amsgrad) as one fused kernel over FlatParams, preceded by the
-    data-parallel gradient all-reduce.  Subclasses Optimizer so lr schedulers drive `param_groups`."""
+    data-parallel gradient all-reduce.  Subclasses Optimizer so lr schedulers drive `param_groups`.
 
-    def __init__(self, module_or_flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+    The guarded step is opt-in; with every option at its default step() launches rr_adam_step exactly as
+    before.  `max_grad_norm`: clip the gradient's global 2-norm (torch.nn.utils.clip_grad_norm_'s formula).
+    `skip_nonfinite`: a step whose gradient holds a NaN or an Inf changes nothing -- parameters, moments, averaged
+    weights and Adam's bias correction stay as they were.  `ema_decay`: keep an exponential moving average of the
+    weights in `self.ema` (a flat buffer, copied from the parameters here), updated inside the Adam kernel; `ema_warmup`
+    ramps the decay as min(ema_decay, (1 + t) / (10 + t)) over the applied steps t.  With any of them set, step() runs
+    rr_grad_norm, rr_guard_decide and rr_adam_step_guarded on the current stream and never reads the device: the
+    decision lives in `self.ctl` (include/rrnet_hip.h), which guard_stats() reads for the log line."""
+
+    def __init__(self, module_or_flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, skip_nonfinite=False,
+                 ema_decay=None, ema_warmup=True):
         self.fp = module_or_flat if isinstance(module_or_flat, FlatParams) else FlatParams(module_or_flat)
         super().__init__(self.fp.params, dict(lr=lr, betas=betas, eps=eps))
         self.exp_avg = torch.zeros_like(self.fp.flat)
         self.exp_avg_sq = torch.zeros_like(self.fp.flat)
         self.step_count = 0
+        if max_grad_norm is not None and not float(max_grad_norm) > 0:
+            raise ValueError("FlatAdam: max_grad_norm = %r must be positive" % (max_grad_norm,))
+        if ema_decay is not None and not 0.0 <= float(ema_decay) <= 1.0:
+            raise ValueError("FlatAdam: ema_decay = %r outside [0, 1]" % (ema_decay,))
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        self.guarded = self.max_grad_norm is not None or self.skip_nonfinite or self.ema_decay is not None
+        self.ema = self.ctl = self._partial = self._bad = None
+        if self.guarded:
+            dev = self.fp.flat.device
+            if dev.type != "cuda":
+                raise RuntimeError("FlatAdam: max_grad_norm / skip_nonfinite / ema_decay run on the device only, the "
+                                   "parameters are on %s" % dev)
+            blocks = ops.grad_norm_blocks(self.fp.numel)
+            self.ctl = ops.guard_ctl_fresh().to(dev)
+            self._partial = torch.empty(blocks, dtype=torch.float64, device=dev)
+            self._bad = torch.empty(blocks, dtype=torch.int32, device=dev)
+            if self.ema_decay is not None:
+                self.ema = self.fp.flat.clone()
 
     def zero_grad(self, set_to_none=False):
         self.fp.zero_grad()
+
+    def guard_stats(self):
+        """The control record of the guarded step as a dict (ops.GUARD_CTL_SLOTS -> float): ONE small device read, which
+        waits for the stream.  For the print interval; step() never calls it."""
+        if not self.guarded:
+            raise RuntimeError("FlatAdam.guard_stats: no guard option is set")
+        return dict(zip(ops.GUARD_CTL_SLOTS, self.ctl.tolist()))
+
+    def ema_state_dict(self, module):
+        """module.state_dict() with every trainable parameter replaced by its averaged value (a view of `self.ema` in the
+        parameter's logical shape).  Buffers -- BatchNorm running statistics and counters -- are the live module's: they
+        are themselves moving averages over the recent batches, and the activations they describe change with the
+        weights, so there is no better estimate to pair with the averaged weights short of a re-estimation pass."""
+        if self.ema is None:
+            raise RuntimeError("FlatAdam.ema_state_dict: ema_decay is not set")
+        views = self.fp.views_of(self.ema)
+        return {k: (views[k] if k in views else v).detach() for k, v in module.state_dict().items()}
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -292,7 +357,15 @@ class FlatAdam(torch.optim.Optimizer):
         scale = self.fp.all_reduce_grads()
         g = self.param_groups[0]
         self.step_count += 1
-        ops.adam_step(self.fp.flat, self.fp.grad, self.exp_avg, self.exp_avg_sq, g['lr'], g['betas'][0], g['betas'][1],
-                      g['eps'], self.step_count, scale)
+        if self.guarded:
+            ops.grad_norm(self.fp.grad, self._partial, self._bad)
+            ops.guard_decide(self._partial, self._bad, self.ctl, scale,
+                             float("inf") if self.max_grad_norm is None else self.max_grad_norm, self.skip_nonfinite, g['lr'],
+                             g['betas'][0], g['betas'][1], 0.0 if self.ema_decay is None else self.ema_decay,
+                             self.ema_decay is not None and self.ema_warmup)
+            ops.adam_step_guarded(self.fp.flat, self.fp.grad, self.exp_avg, self.exp_avg_sq, self.ema, g['eps'], self.ctl)
+        else:
+            ops.adam_step(self.fp.flat, self.fp.grad, self.exp_avg, self.exp_avg_sq, g['lr'], g['betas'][0], g['betas'][1],
+                          g['eps'], self.step_count, scale)
         self.fp.epoch += 1
         self.fp.refresh_wt()          # the update kernel wrote through raw pointers: refill the flipped-filter cache now

@@ -30,6 +30,29 @@ def broadcast_buffers(module, src=0):
     return len(bufs)
 
 
+def guard_options(cfg):
+    """FlatAdam's guard arguments from the opt-in keys cfg.Train.max_grad_norm / skip_nonfinite / ema_decay / ema_warmup
+    (builder-defined: the config modules do not carry them, as with full_state).  All absent: an empty dict."""
+    opts = {}
+    for key in ("max_grad_norm", "skip_nonfinite", "ema_decay", "ema_warmup"):
+        v = getattr(cfg.Train, key, None)
+        if v is not None:
+            opts[key] = v
+    return opts
+
+
+def make_lr_scheduler(cfg, optimizer):
+    """cfg.Train.warmup_iters > 0 (opt-in, with warmup_factor and warmup_method) puts the reference's warm-up in front of
+    the milestones (utils/warmup_lr.py); otherwise MultiStepLR as the reference's operators build it."""
+    warmup_iters = int(getattr(cfg.Train, "warmup_iters", 0) or 0)
+    if warmup_iters > 0:
+        from rrnet_amd.utils.warmup_lr import WarmupMultiStepLR
+        return WarmupMultiStepLR(optimizer, milestones=cfg.Train.lr_milestones, gamma=0.1,
+                                 warmup_factor=float(getattr(cfg.Train, "warmup_factor", 1.0 / 3)),
+                                 warmup_iters=warmup_iters, warmup_method=getattr(cfg.Train, "warmup_method", "linear"))
+    return torch.optim.lr_scheduler.MultiStepLR(optimizer, milestones=cfg.Train.lr_milestones, gamma=0.1)
+
+
 class RCCLDataParallel(nn.Module):
     """Keeps DDP's surface used by the reference (`self.model(x)`, `self.model.module`,
     state_dict of `.module`)."""
@@ -72,6 +95,24 @@ class BaseOperator(object):
         """Same file format as the reference: state_dict of the bare module, reference key names."""
         sd = {k: v.detach().cpu().contiguous() for k, v in models.state_dict().items()}
         torch.save(sd, os.path.join(path, 'ckp-{}.pth'.format(step)))
+
+    # ---- the guarded optimiser step (FlatAdam's max_grad_norm / skip_nonfinite / ema_decay; DESIGN §20) ----
+    def guard_report(self):
+        """What the print-interval line gains with a guard active (one small device read), else ''."""
+        opt = getattr(self, "optimizer", None)
+        if opt is None or not getattr(opt, "guarded", False):
+            return ""
+        s = opt.guard_stats()
+        return "  gnorm %.4g clipped %d skipped %d" % (s["norm"], s["clipped"], s["skipped"])
+
+    def save_ema_ckp(self, step, path):
+        """With averaged weights on: `ckp-ema-{step}.pth` beside `ckp-{step}.pth`, the same format (the module's keys), the
+        trainable parameters replaced by their averages (FlatAdam.ema_state_dict)."""
+        opt = getattr(self, "optimizer", None)
+        if opt is None or getattr(opt, "ema", None) is None:
+            return
+        sd = {k: v.detach().cpu().contiguous() for k, v in opt.ema_state_dict(self.model.module).items()}
+        torch.save(sd, os.path.join(path, 'ckp-ema-{}.pth'.format(step)))
 
     # ---- full-state checkpoints (rrnet_amd/checkpoint.py; opt-in through cfg.Train.full_state / cfg.Train.resume) ----
     _state_writer = None

@@ -18,7 +18,7 @@ from rrnet_amd.models.centernet import CenterNet
 from rrnet_amd.models.rrnet import RRNet
 from rrnet_amd.modules.loss.focalloss import FocalLossHM
 from rrnet_amd.modules.loss.regl1loss import RegL1Loss
-from .base_operator import BaseOperator
+from .base_operator import BaseOperator, guard_options, make_lr_scheduler
 from .rrnet_operator import RRNetOperator
 
 
@@ -39,8 +39,8 @@ class CenterNetOperator(BaseOperator):
         self.cfg = cfg
         model = CenterNet(cfg).cuda(cfg.Distributed.gpu_id).to(memory_format=torch.channels_last)
         flat = FlatParams(model)
-        self.optimizer = FlatAdam(flat, lr=cfg.Train.lr)
-        self.lr_sch = optim.lr_scheduler.MultiStepLR(self.optimizer, milestones=cfg.Train.lr_milestones, gamma=0.1)
+        self.optimizer = FlatAdam(flat, lr=cfg.Train.lr, **guard_options(cfg))
+        self.lr_sch = make_lr_scheduler(cfg, self.optimizer)
         self.training_loader, self.validation_loader = make_dataloader(cfg, collate_fn='ctnet')
         super(CenterNetOperator, self).__init__(cfg=self.cfg, model=model, lr_sch=self.lr_sch, flat=flat)
         self.focal_loss = FocalLossHM()
@@ -90,7 +90,8 @@ class CenterNetOperator(BaseOperator):
             if self.main_proc_flag:
                 if step % pi == pi - 1:
                     print("step %d  loss %.4f hm %.4f wh %.4f off %.4f  lr %.3g" %
-                          ((step,) + tuple(totals / pi) + (self.optimizer.param_groups[0]['lr'],)), flush=True)
+                          ((step,) + tuple(totals / pi) + (self.optimizer.param_groups[0]['lr'],)) + self.guard_report(),
+                          flush=True)
                     pred = self.transform_bbox(outs[0][1], outs[1][1], outs[2][1],
                                                scale_factor=self.cfg.Train.scale_factor)
                     self._ext_nms(pred)
@@ -99,6 +100,7 @@ class CenterNetOperator(BaseOperator):
                 if step % ci == ci - 1 or step == self.cfg.Train.iter_num - 1:
                     os.makedirs(log_dir, exist_ok=True)
                     self.save_ckp(self.model.module, step, log_dir)
+                    self.save_ema_ckp(step, log_dir)
                     if full_state:
                         self.save_state(step, log_dir)
         self.close_state()

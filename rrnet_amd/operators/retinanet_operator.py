@@ -26,7 +26,7 @@ from rrnet_amd.flat import FlatAdam, FlatParams
 from rrnet_amd.models.retinanet import RetinaNet
 from rrnet_amd.modules.anchor import Anchors
 from rrnet_amd.modules.loss.focalloss import FocalLoss
-from .base_operator import BaseOperator
+from .base_operator import BaseOperator, guard_options, make_lr_scheduler
 from .centernet_operator import _released
 
 NMS_THRESH = 0.3            # :254
@@ -46,8 +46,8 @@ class RetinaNetOperator(BaseOperator):
                                       "all-reduce a bucket after the first")
         model = RetinaNet(cfg).cuda(cfg.Distributed.gpu_id).to(memory_format=torch.channels_last)
         flat = FlatParams(model)
-        self.optimizer = FlatAdam(flat, lr=cfg.Train.lr)
-        self.lr_sch = optim.lr_scheduler.MultiStepLR(self.optimizer, milestones=cfg.Train.lr_milestones, gamma=0.1)
+        self.optimizer = FlatAdam(flat, lr=cfg.Train.lr, **guard_options(cfg))
+        self.lr_sch = make_lr_scheduler(cfg, self.optimizer)
         self.training_loader, self.validation_loader = make_dataloader(cfg, collate_fn='ctnet')
         super(RetinaNetOperator, self).__init__(cfg=self.cfg, model=model, lr_sch=self.lr_sch, flat=flat)
         self.anchor_maker = Anchors(sizes=(16, 64, 128))
@@ -107,12 +107,14 @@ class RetinaNetOperator(BaseOperator):
             if self.main_proc_flag:
                 if step % pi == pi - 1:
                     print("step %d  loss %.4f cls %.4f loc %.4f  lr %.3g" %
-                          ((step,) + tuple(totals / pi) + (self.optimizer.param_groups[0]['lr'],)), flush=True)
+                          ((step,) + tuple(totals / pi) + (self.optimizer.param_groups[0]['lr'],)) + self.guard_report(),
+                          flush=True)
                     totals[:] = 0
                 ci = self.cfg.Train.checkpoint_interval
                 if step % ci == ci - 1 or step == self.cfg.Train.iter_num - 1:
                     os.makedirs(log_dir, exist_ok=True)
                     self.save_ckp(self.model.module, step, log_dir)
+                    self.save_ema_ckp(step, log_dir)
                     if full_state:
                         self.save_state(step, log_dir)
         self.close_state()

@@ -23,7 +23,7 @@ from rrnet_amd.flat import FlatAdam, FlatParams
 from rrnet_amd.models.rrnet import RRNet
 from rrnet_amd.modules.loss.focalloss import FocalLossHM
 from rrnet_amd.modules.loss.regl1loss import RegL1Loss
-from .base_operator import BaseOperator
+from .base_operator import BaseOperator, guard_options, make_lr_scheduler
 
 
 
@@ -44,8 +44,8 @@ class RRNetOperator(BaseOperator):
         model = RRNet(cfg).cuda(cfg.Distributed.gpu_id).to(memory_format=torch.channels_last)
         model = nn.SyncBatchNorm.convert_sync_batchnorm(model)
         flat = FlatParams(model)
-        self.optimizer = FlatAdam(flat, lr=cfg.Train.lr)
-        self.lr_sch = optim.lr_scheduler.MultiStepLR(self.optimizer, milestones=cfg.Train.lr_milestones, gamma=0.1)
+        self.optimizer = FlatAdam(flat, lr=cfg.Train.lr, **guard_options(cfg))
+        self.lr_sch = make_lr_scheduler(cfg, self.optimizer)
         self.training_loader, self.validation_loader = make_dataloader(cfg, collate_fn='rrnet')
         super(RRNetOperator, self).__init__(cfg=self.cfg, model=model, lr_sch=self.lr_sch, flat=flat)
         self.hm_focal_loss = FocalLossHM()
@@ -111,7 +111,7 @@ class RRNetOperator(BaseOperator):
                 if step % pi == pi - 1:
                     lr = self.optimizer.param_groups[0]['lr']
                     print("step %d  loss %.4f hm %.4f wh %.4f off %.4f s2 %.4f  lr %.3g" %
-                          ((step,) + tuple(totals / pi) + (lr,)), flush=True)
+                          ((step,) + tuple(totals / pi) + (lr,)) + self.guard_report(), flush=True)
                     s1_pred_bbox, s2_pred_bbox = self.generate_bbox(outs, batch_idx=0)
                     s2_pred_bbox = self._ext_nms(s2_pred_bbox)
                     totals[:] = 0
@@ -119,6 +119,7 @@ class RRNetOperator(BaseOperator):
                 if step % ci == ci - 1 or step == self.cfg.Train.iter_num - 1:
                     os.makedirs(log_dir, exist_ok=True)
                     self.save_ckp(self.model.module, step, log_dir)
+                    self.save_ema_ckp(step, log_dir)
                     if full_state:
                         self.save_state(step, log_dir)
         self.close_state()

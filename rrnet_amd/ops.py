@@ -1221,6 +1221,85 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, gra
                                    _C.stream()), "rr_adam_step")
 
 
+GUARD_CTL_WORDS = 20                # RR_GUARD_CTL_WORDS of include/rrnet_hip.h
+GUARD_CTL_SLOTS = ("applied", "skipped", "clipped", "beta1_pow", "beta2_pow", "norm", "norm_max", "bad", "skip", "scale",
+                   "step_size", "bc2_sqrt", "ema_d", "ema_omd", "reserved0", "reserved1", "b1", "omb1", "b2", "omb2")
+
+
+def guard_ctl_fresh():
+    """A fresh control record of the guarded step as a host float64 tensor: all zero, the two running products 1."""
+    ctl = torch.zeros(GUARD_CTL_WORDS, dtype=torch.float64)
+    ctl[3] = ctl[4] = 1.0
+    return ctl
+
+
+def grad_norm_blocks(n):
+    """rr_grad_norm_blocks: the workgroups (= partial sums) of rr_grad_norm over n words; a function of n alone."""
+    return int(_C.fn("rr_grad_norm_blocks")(int(n)))
+
+
+def _flat_f32(what, name, t, n=None):
+    if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 1 or (n is not None and t.numel() != n):
+        raise _C.RRNetHipError("%s: %s must be a flat contiguous float32 tensor%s" % (what, name, "" if n is None else " of %d words" % n))
+
+
+def grad_norm(grad, partial=None, bad=None):
+    """rr_grad_norm on the current stream -> (partial float64 [blocks], bad int32 [blocks]): per workgroup the sum of
+    squares of the finite words of `grad` and the count of its NaN / Inf words.  `partial` / `bad`: preallocated outputs."""
+    _C.require_cuda(grad, partial, bad)
+    _flat_f32("grad_norm", "grad", grad)
+    n = grad.numel()
+    if n % 4:
+        raise _C.RRNetHipError("grad_norm: n = %d is not a multiple of 4 (pad the flat buffer)" % n)
+    blocks = grad_norm_blocks(n)
+    if partial is None:
+        partial = torch.empty(blocks, dtype=torch.float64, device=grad.device)
+    if bad is None:
+        bad = torch.empty(blocks, dtype=torch.int32, device=grad.device)
+    if partial.dtype != torch.float64 or not partial.is_contiguous() or partial.numel() != blocks or partial.device != grad.device:
+        raise _C.RRNetHipError("grad_norm: partial must be a contiguous float64 [%d] tensor on %s" % (blocks, grad.device))
+    if bad.dtype != torch.int32 or not bad.is_contiguous() or bad.numel() != blocks or bad.device != grad.device:
+        raise _C.RRNetHipError("grad_norm: bad must be a contiguous int32 [%d] tensor on %s" % (blocks, grad.device))
+    _C.check(_C.fn("rr_grad_norm")(_C.ptr(grad), n, _C.ptr(partial), _C.ptr(bad), _C.stream()), "rr_grad_norm")
+    return partial, bad
+
+
+def _check_ctl(what, ctl, device):
+    if ctl.dtype != torch.float64 or not ctl.is_contiguous() or ctl.numel() != GUARD_CTL_WORDS or ctl.device != device:
+        raise _C.RRNetHipError("%s: ctl must be a contiguous float64 [%d] tensor on %s" % (what, GUARD_CTL_WORDS, device))
+
+
+def guard_decide(partial, bad, ctl, grad_scale=1.0, max_norm=float("inf"), skip_nonfinite=False, lr=1e-3, beta1=0.9,
+                 beta2=0.999, ema_decay=0.0, ema_warmup=False):
+    """rr_guard_decide on the current stream: adds up what grad_norm left, decides skip / clip and advances the control
+    record `ctl` (float64 [GUARD_CTL_WORDS] on the device, layout in include/rrnet_hip.h) in place.  Nothing is read back."""
+    _C.require_cuda(partial, bad, ctl)
+    if partial.dtype != torch.float64 or not partial.is_contiguous() or bad.dtype != torch.int32 or not bad.is_contiguous() \
+            or partial.numel() != bad.numel():
+        raise _C.RRNetHipError("guard_decide: partial (float64) and bad (int32) must be contiguous and equally long")
+    _check_ctl("guard_decide", ctl, partial.device)
+    _C.check(_C.fn("rr_guard_decide")(_C.ptr(partial), _C.ptr(bad), partial.numel(), float(grad_scale), float(max_norm),
+                                      int(bool(skip_nonfinite)), float(lr), float(beta1), float(beta2), float(ema_decay),
+                                      int(bool(ema_warmup)), _C.ptr(ctl), _C.stream()), "rr_guard_decide")
+    return ctl
+
+
+def adam_step_guarded(param, grad, exp_avg, exp_avg_sq, ema, eps, ctl):
+    """rr_adam_step_guarded on the current stream: the fused Adam step with its constants read from `ctl`; does nothing when
+    ctl says skip; `ema` (None: no averaged weights) is updated in the same pass."""
+    _C.require_cuda(param, grad, exp_avg, exp_avg_sq, ema, ctl)
+    _flat_f32("adam_step_guarded", "param", param)
+    n = param.numel()
+    if n % 4:
+        raise _C.RRNetHipError("adam_step_guarded: n = %d is not a multiple of 4 (pad the flat buffer)" % n)
+    for name, t in (("grad", grad), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq), ("ema", ema)):
+        if t is not None:
+            _flat_f32("adam_step_guarded", name, t, n)
+    _check_ctl("adam_step_guarded", ctl, param.device)
+    _C.check(_C.fn("rr_adam_step_guarded")(_C.ptr(param), _C.ptr(grad), _C.ptr(exp_avg), _C.ptr(exp_avg_sq), _C.ptr(ema), n,
+                                           float(eps), _C.ptr(ctl), _C.stream()), "rr_adam_step_guarded")
+
+
 def state_snapshot(src, dst=None, chunk=65536, n=None, out=None):
     """rr_state_snapshot on the current stream: copies the fp32 words of `src` into `dst` (None: no copy) as bits and
     returns the digest, int64 [ceil(n / chunk), 3] holding the uint64 records (d0, d1, d2) of include/rrnet_hip.h.

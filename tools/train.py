@@ -3,6 +3,8 @@
   python tools/train.py --config rrnet_config|rrnet_fillduck_config|centernet_config|retinanet_config [--data-root D] [--iters N]
                         [--batch B] [--crop H W] [--backbone NAME] [--bf16] [--full-state] [--resume auto|PATH]
                         [--checkpoint-interval N] [--print-interval N] [--keep-states N] [--color-jitter B C S]
+                        [--clip-grad-norm X] [--skip-nonfinite] [--ema DECAY] [--no-ema-warmup] [--warmup ITERS]
+                        [--warmup-factor F]
 
 A single process: it sets the config keys and calls the operator's training_process().  Without a dataset under
 --data-root the synthetic loader feeds the loop.  `ckp-{step}.pth` (weights, the reference's format) goes to
@@ -10,7 +12,11 @@ A single process: it sets the config keys and calls the operator's training_proc
 (parameters, Adam moments, scheduler, BatchNorm buffers, step, loader position; rrnet_amd/checkpoint.py) and
 --resume continues from one: `auto` takes the newest state of the log directory that loads and verifies.
 --color-jitter B C S puts ColorJitter(B, C, S) in front of the config's training chain (the config modules carry none,
-as the reference's): brightness, contrast and saturation factors from [max(1 - x, 0), 1 + x], applied on the device."""
+as the reference's): brightness, contrast and saturation factors from [max(1 - x, 0), 1 + x], applied on the device.
+--clip-grad-norm X clips the gradient's global norm to X, --skip-nonfinite drops a step whose gradient holds a NaN or an Inf,
+--ema DECAY keeps averaged weights and writes `ckp-ema-{step}.pth` beside each checkpoint (--no-ema-warmup: the full decay
+from the first step); all three are decided on the device inside the optimiser step.  --warmup ITERS puts the
+reference's linear learning-rate warm-up (from --warmup-factor F, default 1/3, of the rate) in front of the milestones."""
 import argparse
 import copy
 import importlib
@@ -44,6 +50,12 @@ def parse(argv=None):
     ap.add_argument("--print-interval", type=int)
     ap.add_argument("--keep-states", type=int)
     ap.add_argument("--color-jitter", type=float, nargs=3, metavar=("B", "C", "S"))
+    ap.add_argument("--clip-grad-norm", type=float, metavar="X")
+    ap.add_argument("--skip-nonfinite", action="store_true")
+    ap.add_argument("--ema", type=float, metavar="DECAY")
+    ap.add_argument("--no-ema-warmup", action="store_true")
+    ap.add_argument("--warmup", type=int, metavar="ITERS")
+    ap.add_argument("--warmup-factor", type=float, metavar="F")
     return ap.parse_args(argv)
 
 
@@ -84,6 +96,26 @@ def configure(args):
         cfg.Train.full_state = True
     if args.resume is not None:
         cfg.Train.resume = args.resume
+    if args.clip_grad_norm is not None:
+        if not args.clip_grad_norm > 0:
+            raise SystemExit("--clip-grad-norm: %r is not a positive norm" % args.clip_grad_norm)
+        cfg.Train.max_grad_norm = args.clip_grad_norm
+    if args.skip_nonfinite:
+        cfg.Train.skip_nonfinite = True
+    if args.ema is not None:
+        if not 0.0 <= args.ema <= 1.0:
+            raise SystemExit("--ema: decay %r outside [0, 1]" % args.ema)
+        cfg.Train.ema_decay = args.ema
+    if args.no_ema_warmup:
+        if args.ema is None:
+            raise SystemExit("--no-ema-warmup needs --ema DECAY")
+        cfg.Train.ema_warmup = False
+    if args.warmup is not None:
+        cfg.Train.warmup_iters = args.warmup
+    if args.warmup_factor is not None:
+        if args.warmup is None:
+            raise SystemExit("--warmup-factor needs --warmup ITERS")
+        cfg.Train.warmup_factor = args.warmup_factor
     cfg.Distributed.gpu_id, cfg.Distributed.rank, cfg.Distributed.world_size = 0, 0, 1
     return cfg
 
