@@ -16,6 +16,7 @@
 #include "common.h"
 #include "rrnet_hip.h"
 #include "jitter.h"
+#include "rowkit.h"
 
 #define AUG_THREADS 256
 #define AUG_PIX 4                 // pixels per thread: 12 floats = three 16-byte stores
@@ -49,12 +50,7 @@ __global__ __launch_bounds__(AUG_THREADS) void augment_frames_kernel(
     const float *__restrict__ stdv, float *__restrict__ out, long npix, int OH, int OW, AugJitter<JIT> jit)
 {
     __shared__ float lut[256 * 3];                       // lut[v*3 + c]
-    for (int i = threadIdx.x; i < 256 * 3; i += AUG_THREADS) {
-        const int v = i / 3, c = i - v * 3;
-        const float x = (float)v / 255.0f;               // ToTensor: uint8.float().div(255)
-        lut[i] = (x - mean[c]) / stdv[c];                // Normalize: sub, div
-    }
-    __syncthreads();
+    rr_norm_lut_fill<AUG_THREADS>(lut, mean, stdv);
     const long p0 = ((long)blockIdx.x * AUG_THREADS + threadIdx.x) * AUG_PIX;
     if (p0 >= npix) return;
     const long per_img = (long)OH * OW;

@@ -17,20 +17,12 @@
 // operators/rrnet_operator.py:211-232) into batched launches.
 #include "common.h"
 #include "rrnet_hip.h"
+#include "rowkit.h"        // integer helpers only: this file is built with the default contraction
 
 namespace {
 
 constexpr int DT = 1024;  // threads per image
 
-__device__ __forceinline__ unsigned int f2ord(float f)
-{
-    const unsigned int u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ord2f(unsigned int o)
-{
-    return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
 __device__ __forceinline__ float score_of(float v, int is_logits) { return is_logits ? 1.0f / (1.0f + expf(-v)) : v; }
 
 // wave 0: find the bin (scanning from the top) where the running count reaches `need`.
@@ -150,7 +142,7 @@ __device__ unsigned int place_threshold(const float *x, long n, int K, int peak,
         __syncthreads();
         for (long j = tid; j < ns; j += blockDim.x) {
             const long i = by_line ? (j >> 5) * lstride + (j & 31) : j * stride;
-            const unsigned int o = f2ord(x[i]);
+            const unsigned int o = rr_f2ord(x[i]);
             if (pass == 0 || (o >> 21) == (prefix >> 21)) {
                 if (!peak || is_peak3x3(x, i, C, H, W, is_logits)) atomicAdd(&hist[(o >> shift) & 2047], 1);
             }
@@ -177,32 +169,21 @@ __device__ int finish_candidates(unsigned long long *keys, int m, unsigned int t
     for (int p = tid; p < m; p += DT) {
         const unsigned long long cand = keys[p];
         const long i = (long)(cand & 0xffffffffull);
-        const float sc = score_of(ord2f((unsigned int)(cand >> 32)), is_logits);
+        const float sc = score_of(rr_ord2f((unsigned int)(cand >> 32)), is_logits);
         const unsigned int ref = (unsigned int)((i % C) * HW + i / C);
-        keys[p] = ((unsigned long long)f2ord(sc) << 32) | (unsigned long long)(0xffffffffu - ref);
+        keys[p] = rr_score_key(sc, ref);
     }
     int mp = 2;
     while (mp < m) mp <<= 1;
     for (int p = m + tid; p < mp; p += DT) keys[p] = 0ull;
     __syncthreads();
-    for (int k2 = 2; k2 <= mp; k2 <<= 1) {
-        for (int j = k2 >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < mp / 2; t += DT) {
-                const int lo = ((t / j) * 2 * j) + (t % j);
-                const int hi2 = lo + j;
-                const bool desc = ((lo & k2) == 0);
-                const unsigned long long a = keys[lo], b = keys[hi2];
-                if ((a < b) == desc) { keys[lo] = b; keys[hi2] = a; }
-            }
-            __syncthreads();
-        }
-    }
+    rr_bitonic_sort<DT, true>(keys, mp);
     const unsigned int kth = (unsigned int)(keys[K - 1] >> 32);
     if (t0 != 0) {
-        const unsigned int edge = f2ord(score_of(ord2f(t0), is_logits));
+        const unsigned int edge = rr_f2ord(score_of(rr_ord2f(t0), is_logits));
         if (kth <= edge) return -1;           // an outsider could tie with the K-th score
     }
-    if (peak && kth <= f2ord(0.f)) return -1; // filtered-out elements rank as 0: they could tie / outrank
+    if (peak && kth <= rr_f2ord(0.f)) return -1; // filtered-out elements rank as 0: they could tie / outrank
     return m;
 }
 
@@ -217,7 +198,7 @@ __device__ int decode_fast_path(const float *x, long n, int is_logits, int peak,
     if (tid == 0) *cnt = 0;
     __syncthreads();
     for (long i = tid; i < n; i += DT) {
-        const unsigned int o = f2ord(x[i]);
+        const unsigned int o = rr_f2ord(x[i]);
         if (o >= t0 && (!peak || is_peak3x3(x, i, C, H, W, is_logits))) {
             const int p = atomicAdd(cnt, 1);
             if (p < DEC_CAP) keys[p] = ((unsigned long long)o << 32) | (unsigned long long)i;
@@ -287,7 +268,7 @@ __global__ __launch_bounds__(SCAN_T) void decode_scan_kernel(const float *hm, in
 #define RR_SCAN4(V, R)                                                                                              \
         {                                                                                                           \
             const long i0 = base + ((long)(R) * SCAN_T + threadIdx.x) * 4;                                          \
-            const unsigned int o0 = f2ord(V.x), o1 = f2ord(V.y), o2 = f2ord(V.z), o3 = f2ord(V.w);                  \
+            const unsigned int o0 = rr_f2ord(V.x), o1 = rr_f2ord(V.y), o2 = rr_f2ord(V.z), o3 = rr_f2ord(V.w);                  \
             if (o0 >= t0) scan_push(x, o0, i0, peak, is_logits, C, H, W, lcand, &lcnt, LCAP, f);                    \
             if (o1 >= t0) scan_push(x, o1, i0 + 1, peak, is_logits, C, H, W, lcand, &lcnt, LCAP, f);                \
             if (o2 >= t0) scan_push(x, o2, i0 + 2, peak, is_logits, C, H, W, lcand, &lcnt, LCAP, f);                \
@@ -299,7 +280,7 @@ __global__ __launch_bounds__(SCAN_T) void decode_scan_kernel(const float *hm, in
     } else {
         const long end = base + SCAN_T * SCAN_PER < n ? base + SCAN_T * SCAN_PER : n;
         for (long i = base + threadIdx.x; i < end; i += SCAN_T) {
-            const unsigned int o = f2ord(x[i]);
+            const unsigned int o = rr_f2ord(x[i]);
             if (o >= t0) scan_push(x, o, i, peak, is_logits, C, H, W, lcand, &lcnt, LCAP, f);
         }
     }
@@ -356,7 +337,7 @@ __global__ __launch_bounds__(DT) void decode_topk_kernel(const float *hm, int is
         for (int i = tid; i < 2048; i += DT) hist[i] = 0;
         __syncthreads();
         for (long i = tid; i < n; i += DT) {
-            const unsigned int o = f2ord(elem_score(x, i, is_logits, peak, C, H, W));
+            const unsigned int o = rr_f2ord(elem_score(x, i, is_logits, peak, C, H, W));
             unsigned int word, pref;
             if (pass < 3) {
                 word = o; pref = hi_pref;
@@ -381,37 +362,23 @@ __global__ __launch_bounds__(DT) void decode_topk_kernel(const float *hm, int is
     for (int i = K + tid; i < KP; i += DT) keys[i] = 0ull;
     __syncthreads();
     for (long i = tid; i < n; i += DT) {
-        const unsigned int o = f2ord(elem_score(x, i, is_logits, peak, C, H, W));
-        if (o < hi_pref) continue;
-        const unsigned int ref = (unsigned int)((i % C) * HW + i / C);
-        const unsigned long long key = ((unsigned long long)o << 32) | (unsigned long long)(0xffffffffu - ref);
+        const float sc = elem_score(x, i, is_logits, peak, C, H, W);
+        if (rr_f2ord(sc) < hi_pref) continue;
+        const unsigned long long key = rr_score_key(sc, (unsigned int)((i % C) * HW + i / C));
         if (key >= kth) {
             const int p = atomicAdd(&cnt_gt, 1);
             if (p < K) keys[p] = key;
         }
     }
     __syncthreads();
-
-    // ---- bitonic sort, descending
-    for (int k2 = 2; k2 <= KP; k2 <<= 1) {
-        for (int j = k2 >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < KP / 2; t += DT) {
-                const int lo = ((t / j) * 2 * j) + (t % j);
-                const int hi2 = lo + j;
-                const bool desc = ((lo & k2) == 0);
-                const unsigned long long a = keys[lo], b = keys[hi2];
-                if ((a < b) == desc) { keys[lo] = b; keys[hi2] = a; }
-            }
-            __syncthreads();
-        }
-    }
+    rr_bitonic_sort<DT, true>(keys, KP);          // descending
     }   // exact path
 
     // ---- gather + box assembly (models/rrnet.py:122-137)
     for (int k = tid; k < K; k += DT) {
         const unsigned long long key = keys[k];
-        const float score = ord2f((unsigned int)(key >> 32));
-        const unsigned int ref = 0xffffffffu - (unsigned int)(key & 0xffffffffu);
+        const float score = rr_ord2f((unsigned int)(key >> 32));
+        const unsigned int ref = rr_key_pos(key);
         const int cls = (int)(ref / HW);
         const long pix = ref % HW;
         const float xs0 = (float)(pix % W), ys0 = (float)(pix / W);
@@ -536,18 +503,7 @@ __global__ __launch_bounds__(256) void group_by_class_kernel(const float *boxes,
             keys[i] = key;
         }
         __syncthreads();
-        for (int k2 = 2; k2 <= KP; k2 <<= 1) {
-            for (int j = k2 >> 1; j > 0; j >>= 1) {
-                for (int t = threadIdx.x; t < KP / 2; t += 256) {
-                    const int lo = ((t / j) * 2 * j) + (t % j);
-                    const int hi2 = lo + j;
-                    const bool asc = ((lo & k2) == 0);
-                    const unsigned int a = keys[lo], c = keys[hi2];
-                    if ((a > c) == asc) { keys[lo] = c; keys[hi2] = a; }
-                }
-                __syncthreads();
-            }
-        }
+        rr_bitonic_sort<256, false>(keys, KP);
         const int nv = n_valid;
         for (int e = threadIdx.x; e < nv * 6; e += 256) {
             const int r = e / 6, col = e - r * 6;

@@ -12,8 +12,10 @@
 // Built with -ffp-contract=off like refine.hip: every step of the box arithmetic is its own fp32 rounding and the division by
 // the scale is an IEEE division (the reference divides on the CPU).  The interpolation in rr_prepare_frames has to give the
 // bits of rr_resize_bilinear_ac: its fused steps are written as explicit fmas (prep_taps / prep_bilinear below).
+// The compaction of the merge kernels, the sort and the normalisation table come from rowkit.h.
 #include "common.h"
 #include "rrnet_hip.h"
+#include "rowkit.h"
 
 #define DET_THREADS 256
 #define DET_SORT_THREADS 1024
@@ -49,90 +51,91 @@ __device__ __forceinline__ float prep_bilinear(const PrepTaps &t, float v00, flo
     return t.hy * r0 + t.ly * r1;
 }
 
-// One thread per output pixel (three channels = 12 contiguous bytes of the NHWC output).
-__global__ __launch_bounds__(DET_THREADS) void prepare_frames_kernel(const uint8_t *__restrict__ src, const float *__restrict__ mean,
-                                                                     const float *__restrict__ stdv, float *__restrict__ out, int N,
-                                                                     int H, int W, int OH, int OW)
+// Where the th x tw source window of output image n lies.
+//   PrepFrames: image n is the whole of frame n, N equal-size frames back to back (th x tw = the frame).
+//   PrepTiles:  image n is the window of frame tiles[n][0] at (tiles[n][1], tiles[n][2]); frame f is [H_f, W_f, 3] bytes at
+//               src + frame_base[f], any byte address: byte loads, 64-bit offsets.  The table is checked on the host.
+struct PrepFrames {
+    static constexpr bool from_table = false;
+    const uint8_t *src;
+};
+struct PrepTiles {
+    static constexpr bool from_table = true;
+    const uint8_t *src; const long long *frame_base; const int *frame_hw; int F; const int *tiles;
+};
+
+// The prepare body: N images of th x tw source pixels -> OH x OW, one thread per output pixel (three channels = 12
+// contiguous bytes of the NHWC output).  The taps are those of the WINDOW (prep_taps with H = th, W = tw), so for a tile the
+// "+1" tap stops at the tile's last row / column and the output carries the bits the whole-frame kernel writes for the
+// host-cropped window.  The lanes of a wave hold consecutive output columns of one row, so their byte loads fall into one
+// or two source rows of at most 64 * 3 * sx bytes each; a tile finds them through one table row per pixel (12 bytes that
+// every lane of the wave shares: one L1 line).
+// MIRROR: a second, x-mirrored copy of every image behind the N plain ones, the flip of CenterNet's test-time
+// augmentation (operators/centernet_operator.py:268-272), which the reference applies AFTER the resize.  Each pixel is
+// computed once, at its plain position, and stored twice: out[n][h][w] and out[N+n][h][OW-1-w].  The mirrored stores of a
+// wave cover the same contiguous 64 * 12 bytes of a row as its plain ones, in descending lane order: whole cache lines
+// either way, no staging in LDS.
+template <class Source, bool MIRROR>
+__device__ __forceinline__ void prepare_gather(const Source &from, const float *__restrict__ mean, const float *__restrict__ stdv,
+                                               float *__restrict__ out, int N, int th, int tw, int OH, int OW)
 {
     __shared__ float lut[256 * 3];                       // lut[v*3 + c], as augment_frames_kernel builds it
-    for (int i = threadIdx.x; i < 256 * 3; i += DET_THREADS) {
-        const int v = i / 3, c = i - v * 3;
-        const float x = (float)v / 255.0f;               // ToTensor: uint8.float().div(255)
-        lut[i] = (x - mean[c]) / stdv[c];                // Normalize: sub, div
-    }
-    __syncthreads();
+    rr_norm_lut_fill<DET_THREADS>(lut, mean, stdv);
     const long total = (long)N * OH * OW;
-    const float sy = OH > 1 ? (float)(H - 1) / (float)(OH - 1) : 0.f;
-    const float sx = OW > 1 ? (float)(W - 1) / (float)(OW - 1) : 0.f;
+    const float sy = OH > 1 ? (float)(th - 1) / (float)(OH - 1) : 0.f;
+    const float sx = OW > 1 ? (float)(tw - 1) / (float)(OW - 1) : 0.f;
     for (long p = (long)blockIdx.x * DET_THREADS + threadIdx.x; p < total; p += (long)gridDim.x * DET_THREADS) {
         long q = p;
         const int w = (int)(q % OW); q /= OW;
         const int h = (int)(q % OH);
-        const int n = (int)(q / OH);
-        const PrepTaps t = prep_taps(sy, sx, h, w, H, W);
-        // (int)(sy*h) <= H-1 and (int)(sx*w) <= W-1 up to one rounding of the product: clamp what addresses memory
-        const int y0 = min(max(t.y0, 0), H - 1), y1 = min(max(t.y1, 0), H - 1);
-        const int x0 = min(max(t.x0, 0), W - 1), x1 = min(max(t.x1, 0), W - 1);
-        const uint8_t *b = src + (long)n * H * W * 3;
+        const int n = (int)(q / OH);                     // < N
+        const PrepTaps t = prep_taps(sy, sx, h, w, th, tw);
+        // (int)(sy*h) <= th-1 and (int)(sx*w) <= tw-1 up to one rounding of the product: clamp what addresses memory
+        int y0 = min(max(t.y0, 0), th - 1), y1 = min(max(t.y1, 0), th - 1);
+        int x0 = min(max(t.x0, 0), tw - 1), x1 = min(max(t.x1, 0), tw - 1);
+        const uint8_t *b;
+        int W;
+        if constexpr (Source::from_table) {
+            // what the table and frame_hw say is clamped again, inside the frame they name, before it addresses memory
+            const int f = min(max(from.tiles[n * 3], 0), from.F - 1);
+            const int H = max(from.frame_hw[f * 2], 1);
+            W = max(from.frame_hw[f * 2 + 1], 1);
+            const int oy = from.tiles[n * 3 + 1], ox = from.tiles[n * 3 + 2];
+            y0 = min(max(oy + y0, 0), H - 1), y1 = min(max(oy + y1, 0), H - 1);
+            x0 = min(max(ox + x0, 0), W - 1), x1 = min(max(ox + x1, 0), W - 1);
+            b = from.src + from.frame_base[f];
+        } else {
+            W = tw;
+            b = from.src + (long)n * th * tw * 3;
+        }
         const uint8_t *p00 = b + ((long)y0 * W + x0) * 3, *p01 = b + ((long)y0 * W + x1) * 3;
         const uint8_t *p10 = b + ((long)y1 * W + x0) * 3, *p11 = b + ((long)y1 * W + x1) * 3;
         float *o = out + p * 3;
+        float *m = out + ((((long)N + n) * OH + h) * OW + (OW - 1 - w)) * 3;      // MIRROR only; 0 <= OW-1-w < OW, N+n < 2N
 #pragma unroll
-        for (int c = 0; c < 3; ++c)
-            o[c] = prep_bilinear(t, lut[p00[c] * 3 + c], lut[p01[c] * 3 + c], lut[p10[c] * 3 + c], lut[p11[c] * 3 + c]);
+        for (int c = 0; c < 3; ++c) {
+            const float v = prep_bilinear(t, lut[p00[c] * 3 + c], lut[p01[c] * 3 + c], lut[p10[c] * 3 + c], lut[p11[c] * 3 + c]);
+            o[c] = v;
+            if constexpr (MIRROR) m[c] = v;
+        }
     }
 }
 
-// prepare_frames_kernel with a second, x-mirrored copy of every image behind the N plain ones: the flip of CenterNet's
-// test-time augmentation (operators/centernet_operator.py:268-272), which the reference applies AFTER the resize.  Each
-// pixel is therefore computed once, at its plain position, and stored twice: out[n][h][w] and out[N+n][h][OW-1-w].  The
-// lanes of a wave hold consecutive w, so the mirrored stores of a wave cover the same contiguous 64 * 12 bytes of a row as
-// its plain ones, in descending lane order: whole cache lines either way, no staging in LDS.
+__global__ __launch_bounds__(DET_THREADS) void prepare_frames_kernel(const uint8_t *__restrict__ src, const float *__restrict__ mean,
+                                                                     const float *__restrict__ stdv, float *__restrict__ out, int N,
+                                                                     int H, int W, int OH, int OW)
+{
+    prepare_gather<PrepFrames, false>(PrepFrames{src}, mean, stdv, out, N, H, W, OH, OW);
+}
+
 __global__ __launch_bounds__(DET_THREADS) void prepare_frames_pair_kernel(const uint8_t *__restrict__ src,
                                                                           const float *__restrict__ mean,
                                                                           const float *__restrict__ stdv, float *__restrict__ out,
                                                                           int N, int H, int W, int OH, int OW)
 {
-    __shared__ float lut[256 * 3];                       // as prepare_frames_kernel
-    for (int i = threadIdx.x; i < 256 * 3; i += DET_THREADS) {
-        const int v = i / 3, c = i - v * 3;
-        const float x = (float)v / 255.0f;
-        lut[i] = (x - mean[c]) / stdv[c];
-    }
-    __syncthreads();
-    const long total = (long)N * OH * OW;
-    const float sy = OH > 1 ? (float)(H - 1) / (float)(OH - 1) : 0.f;
-    const float sx = OW > 1 ? (float)(W - 1) / (float)(OW - 1) : 0.f;
-    for (long p = (long)blockIdx.x * DET_THREADS + threadIdx.x; p < total; p += (long)gridDim.x * DET_THREADS) {
-        long q = p;
-        const int w = (int)(q % OW); q /= OW;
-        const int h = (int)(q % OH);
-        const int n = (int)(q / OH);
-        const PrepTaps t = prep_taps(sy, sx, h, w, H, W);
-        const int y0 = min(max(t.y0, 0), H - 1), y1 = min(max(t.y1, 0), H - 1);
-        const int x0 = min(max(t.x0, 0), W - 1), x1 = min(max(t.x1, 0), W - 1);
-        const uint8_t *b = src + (long)n * H * W * 3;
-        const uint8_t *p00 = b + ((long)y0 * W + x0) * 3, *p01 = b + ((long)y0 * W + x1) * 3;
-        const uint8_t *p10 = b + ((long)y1 * W + x0) * 3, *p11 = b + ((long)y1 * W + x1) * 3;
-        float *o = out + p * 3;
-        float *m = out + ((((long)N + n) * OH + h) * OW + (OW - 1 - w)) * 3;      // 0 <= OW-1-w < OW, N+n < 2N
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float v = prep_bilinear(t, lut[p00[c] * 3 + c], lut[p01[c] * 3 + c], lut[p10[c] * 3 + c], lut[p11[c] * 3 + c]);
-            o[c] = v;
-            m[c] = v;
-        }
-    }
+    prepare_gather<PrepFrames, true>(PrepFrames{src}, mean, stdv, out, N, H, W, OH, OW);
 }
 
-// prepare_frames_kernel for T equal-size tiles cut out of F frames of differing sizes: tile n is the th x tw window of frame
-// tiles[n][0] at (tiles[n][1], tiles[n][2]), resized to OH x OW.  The taps are those of the TILE (prep_taps with H = TH,
-// W = TW), so the "+1" tap stops at the tile's last row / column and the output carries the bits prepare_frames_kernel
-// writes for the host-cropped window.  Frame f is [H_f, W_f, 3] bytes at src + frame_base[f], any byte address: byte loads,
-// 64-bit offsets.  The lanes of a wave hold consecutive output columns of one tile row, so their byte loads fall into one or
-// two source rows of at most 64 * 3 * sx bytes each — the same lines prepare_frames_kernel touches, found through one table
-// row per pixel (12 bytes that every lane of the wave shares: one L1 line).
-// The table is checked on the host; what it and frame_hw say is clamped again before it addresses memory.
 __global__ __launch_bounds__(DET_THREADS) void prepare_tiles_kernel(const uint8_t *__restrict__ src,
                                                                     const long long *__restrict__ frame_base,
                                                                     const int *__restrict__ frame_hw, int F,
@@ -140,58 +143,30 @@ __global__ __launch_bounds__(DET_THREADS) void prepare_tiles_kernel(const uint8_
                                                                     int OW, const float *__restrict__ mean,
                                                                     const float *__restrict__ stdv, float *__restrict__ out)
 {
-    __shared__ float lut[256 * 3];                       // as prepare_frames_kernel
-    for (int i = threadIdx.x; i < 256 * 3; i += DET_THREADS) {
-        const int v = i / 3, c = i - v * 3;
-        const float x = (float)v / 255.0f;
-        lut[i] = (x - mean[c]) / stdv[c];
-    }
-    __syncthreads();
-    const long total = (long)T * OH * OW;
-    const float sy = OH > 1 ? (float)(TH - 1) / (float)(OH - 1) : 0.f;
-    const float sx = OW > 1 ? (float)(TW - 1) / (float)(OW - 1) : 0.f;
-    for (long p = (long)blockIdx.x * DET_THREADS + threadIdx.x; p < total; p += (long)gridDim.x * DET_THREADS) {
-        long q = p;
-        const int w = (int)(q % OW); q /= OW;
-        const int h = (int)(q % OH);
-        const int n = (int)(q / OH);                     // < T
-        const int f = min(max(tiles[n * 3], 0), F - 1);
-        const int H = max(frame_hw[f * 2], 1), W = max(frame_hw[f * 2 + 1], 1);
-        const int oy = tiles[n * 3 + 1], ox = tiles[n * 3 + 2];
-        const PrepTaps t = prep_taps(sy, sx, h, w, TH, TW);
-        // inside the tile as in prepare_frames_kernel, then inside the frame the table names
-        const int y0 = min(max(oy + min(max(t.y0, 0), TH - 1), 0), H - 1), y1 = min(max(oy + min(max(t.y1, 0), TH - 1), 0), H - 1);
-        const int x0 = min(max(ox + min(max(t.x0, 0), TW - 1), 0), W - 1), x1 = min(max(ox + min(max(t.x1, 0), TW - 1), 0), W - 1);
-        const uint8_t *b = src + frame_base[f];
-        const uint8_t *p00 = b + ((long)y0 * W + x0) * 3, *p01 = b + ((long)y0 * W + x1) * 3;
-        const uint8_t *p10 = b + ((long)y1 * W + x0) * 3, *p11 = b + ((long)y1 * W + x1) * 3;
-        float *o = out + p * 3;
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-            o[c] = prep_bilinear(t, lut[p00[c] * 3 + c], lut[p01[c] * 3 + c], lut[p10[c] * 3 + c], lut[p11[c] * 3 + c]);
-    }
+    prepare_gather<PrepTiles, false>(PrepTiles{src, frame_base, frame_hw, F, tiles}, mean, stdv, out, T, TH, TW, OH, OW);
 }
 
-// One workgroup per frame: the rows (x, y, w, h, score, cls) of the frame's tiles [tile_off[f], tile_off[f+1]), tile by
-// tile in table order, the first min(max(count_in[t], 0), k_in) rows of each in row order -> margin test in the model's
-// input coordinates -> x / div + x0, y / div + y0, w / div, h / div -> appended at merged[f][count[f]...].  Compaction as
-// merge_scales_kernel.  count[f] ends as the true number of kept rows, also above K; rows at and beyond K are not written.
-// No workgroup reads what another writes: the result does not depend on the dispatch order.
+// The three merge kernels below append rows in order at merged[f][count[f]...], one workgroup per frame: each pass of
+// DET_THREADS rows is ranked by rr_block_rank, the rows kept so far are counted in a register.  Launches are ordered by the
+// stream and no workgroup reads what another writes, so count[f] needs no atomics and the result does not depend on the
+// dispatch order.
+
+// Rows (x, y, w, h, score, cls) of the frame's tiles [tile_off[f], tile_off[f+1]), tile by tile in table order, the first
+// min(max(count_in[t], 0), k_in) rows of each in row order -> margin test in the model's input coordinates ->
+// x / div + x0, y / div + y0, w / div, h / div.  count[f] ends as the true number of kept rows, also above K (so the base is
+// not clamped and the position is 64-bit); rows at and beyond K are not written.
 __global__ __launch_bounds__(DET_THREADS) void merge_tiles_kernel(const float *rows, const int *count_in, const int *tiles,
                                                                   const int *tile_off, const int *frame_hw, int k_in, int TH,
                                                                   int TW, float fow, float foh, float div, float margin,
                                                                   float *merged, int *count, int K)
 {
     __shared__ int wave_cnt[DET_THREADS / 64];
-    __shared__ int run;
     const int f = blockIdx.x;
     const int t0 = max(tile_off[f], 0), t1 = max(tile_off[f + 1], t0);     // the host built and checked the offsets
     const int H = frame_hw[f * 2], W = frame_hw[f * 2 + 1];
     const int base0 = max(count[f], 0);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const bool test = margin > 0.0f;
-    if (threadIdx.x == 0) run = 0;
-    __syncthreads();
+    int run = 0;
     float *dst = merged + (long)f * K * 6;
     for (int t = t0; t < t1; ++t) {
         const int n = min(max(count_in[t], 0), k_in);
@@ -219,37 +194,27 @@ __global__ __launch_bounds__(DET_THREADS) void merge_tiles_kernel(const float *r
                 o2 = w / div;
                 o3 = h / div;
             }
-            const unsigned long long m = __ballot(keep);
-            if (lane == 0) wave_cnt[wave] = __popcll(m);
-            __syncthreads();
-            long pos = (long)base0 + run + __popcll(m & ((1ull << lane) - 1ull));
-            for (int wv = 0; wv < wave; ++wv) pos += wave_cnt[wv];
-            if (keep && pos < K) {
-                float *o = dst + pos * 6;
-                o[0] = o0; o[1] = o1; o[2] = o2; o[3] = o3; o[4] = sc; o[5] = cl;
-            }
-            __syncthreads();
-            if (threadIdx.x == 0) run += wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+            int total;
+            const long pos = (long)base0 + run + rr_block_rank<DET_THREADS / 64>(keep, wave_cnt, total);
+            if (keep && pos < K) rr_store_row6(dst + pos * 6, o0, o1, o2, o3, sc, cl);
+            run += total;
             __syncthreads();
         }
     }
     if (threadIdx.x == 0) count[f] = (int)min((long)base0 + run, 0x7fffffffl);
 }
 
-// One workgroup per frame: CenterNet rows (x, y, w, h, score, cls+1) of one scale, k_in per image as rr_decode_topk
-// (box_mode 1) writes them, -> `score > thr` (transform_bbox, :177) -> for the flipped image x = (img_w - x) - w
-// (flip_annos) -> x,y,w,h / div -> appended at merged[f][count[f]...], the flipped image's rows (image nframes + f) in
-// front of the plain one's (image f): the reference's concatenation order (:266-285).  Compaction as merge_scales_kernel.
+// CenterNet rows (x, y, w, h, score, cls+1) of one scale, k_in per image as rr_decode_topk (box_mode 1) writes them, ->
+// `score > thr` (transform_bbox, :177) -> for the flipped image x = (img_w - x) - w (flip_annos) -> x,y,w,h / div, the
+// flipped image's rows (image nframes + f) in front of the plain one's (image f): the reference's concatenation order
+// (:266-285).
 __global__ __launch_bounds__(DET_THREADS) void merge_ctnet_kernel(const float *rows, int nframes, int k_in, int pair, float img_w,
                                                                   float div, float thr, float *merged, int *count, int K)
 {
     __shared__ int wave_cnt[DET_THREADS / 64];
-    __shared__ int run;
     const int f = blockIdx.x;
     const int base0 = min(max(count[f], 0), K);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) run = 0;
-    __syncthreads();
+    int run = 0;
     float *dst = merged + (long)f * K * 6;
     for (int half = pair ? 1 : 0; half >= 0; --half) {   // 1: the flipped image, 0: the plain one
         const float *src = rows + ((long)half * nframes + f) * k_in * 6;
@@ -270,40 +235,29 @@ __global__ __launch_bounds__(DET_THREADS) void merge_ctnet_kernel(const float *r
                 o3 = h / div;
                 keep = sc > thr;                         // NaN leaves
             }
-            const unsigned long long m = __ballot(keep);
-            if (lane == 0) wave_cnt[wave] = __popcll(m);
-            __syncthreads();
-            int pos = base0 + run + __popcll(m & ((1ull << lane) - 1ull));
-            for (int wv = 0; wv < wave; ++wv) pos += wave_cnt[wv];
-            if (keep && pos < K) {
-                float *o = dst + (long)pos * 6;
-                o[0] = o0; o[1] = o1; o[2] = o2; o[3] = o3; o[4] = sc; o[5] = cl;
-            }
-            __syncthreads();
-            if (threadIdx.x == 0) run += wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+            int total;
+            const int pos = base0 + run + rr_block_rank<DET_THREADS / 64>(keep, wave_cnt, total);
+            if (keep && pos < K) rr_store_row6(dst + (long)pos * 6, o0, o1, o2, o3, sc, cl);
+            run += total;
             __syncthreads();
         }
     }
     if (threadIdx.x == 0) count[f] = min(base0 + run, K);
 }
 
-// One workgroup per frame: rows [frame_off[f], frame_off[f+1]) of one scale's packed stage-2 inputs -> generate_bbox rows
-// (x, y, w, h, score, cls+1), optional `score > thr`, x,y,w,h / div -> appended, order preserved, at merged[f][count[f]...].
-// Launches of successive scales are ordered by the stream, so count[f] needs no atomics.
+// Rows [frame_off[f], frame_off[f+1]) of one scale's packed stage-2 inputs -> generate_bbox rows
+// (x, y, w, h, score, cls+1), optional `score > thr`, x,y,w,h / div.
 __global__ __launch_bounds__(DET_THREADS) void merge_scales_kernel(const float *rois, const float *reg, const float *scores,
                                                                    const float *clses, const int *frame_off, int R, float scale,
                                                                    float div, int filter, float thr, float *merged, int *count,
                                                                    int K)
 {
     __shared__ int wave_cnt[DET_THREADS / 64];
-    __shared__ int run;
     const int f = blockIdx.x;
     const int r0 = min(max(frame_off[f], 0), R);
     const int n = min(max(frame_off[f + 1] - r0, 0), R - r0);
     const int base0 = min(max(count[f], 0), K);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) run = 0;
-    __syncthreads();
+    int run = 0;
     float *dst = merged + (long)f * K * 6;
     for (int base = 0; base < n; base += DET_THREADS) {
         const int i = base + threadIdx.x;
@@ -311,33 +265,20 @@ __global__ __launch_bounds__(DET_THREADS) void merge_scales_kernel(const float *
         float o0 = 0.f, o1 = 0.f, o2 = 0.f, o3 = 0.f, sc = 0.f, cl = 0.f;
         if (i < n) {
             const long r = r0 + i;
-            const float *q = rois + r * 5;
-            const float *g = reg + r * 4;
-            // generate_bbox, as refine_boxes_kernel: xyxy * scale -> xywh -> w,h += 1 -> centre / size update -> xywh
-            const float x = q[1] * scale, y = q[2] * scale;
-            const float w = (q[3] * scale - x) + 1.0f, h = (q[4] * scale - y) + 1.0f;
-            const float cx = (g[0] * w + x) + w / 2.0f;
-            const float cy = (g[1] * h + y) + h / 2.0f;
-            const float ow = expf(g[2]) * w, oh = expf(g[3]) * h;
-            o0 = (cx - ow / 2.0f) / div;                 // pred_bbox[:, :4] / scale on the host: IEEE division
-            o1 = (cy - oh / 2.0f) / div;
-            o2 = ow / div;
-            o3 = oh / div;
+            float x, y, w, h;
+            rr_generate_bbox(rois + r * 5, reg + r * 4, scale, x, y, w, h);
+            o0 = x / div;                                // pred_bbox[:, :4] / scale on the host: IEEE division
+            o1 = y / div;
+            o2 = w / div;
+            o3 = h / div;
             sc = scores[r];
             cl = clses[r] + 1.0f;
             keep = !filter || sc > thr;
         }
-        const unsigned long long m = __ballot(keep);
-        if (lane == 0) wave_cnt[wave] = __popcll(m);
-        __syncthreads();
-        int pos = base0 + run + __popcll(m & ((1ull << lane) - 1ull));
-        for (int wv = 0; wv < wave; ++wv) pos += wave_cnt[wv];
-        if (keep && pos < K) {
-            float *o = dst + (long)pos * 6;
-            o[0] = o0; o[1] = o1; o[2] = o2; o[3] = o3; o[4] = sc; o[5] = cl;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) run += wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+        int total;
+        const int pos = base0 + run + rr_block_rank<DET_THREADS / 64>(keep, wave_cnt, total);
+        if (keep && pos < K) rr_store_row6(dst + (long)pos * 6, o0, o1, o2, o3, sc, cl);
+        run += total;
         __syncthreads();
     }
     if (threadIdx.x == 0) count[f] = min(base0 + run, K);
@@ -359,47 +300,27 @@ __global__ __launch_bounds__(DET_SORT_THREADS) void sort_frames_kernel(const flo
     while (KP < n) KP <<= 1;
     if (KP > KPmax) KP = KPmax;                          // K <= KPmax by the launcher: never taken, keeps LDS indices bounded
     const float *src = rows + (long)f * K * 6;
-    for (int i = threadIdx.x; i < KP; i += DET_SORT_THREADS) {
-        unsigned long long key = 0ull;
-        if (i < n) {
-            const unsigned int sc = __float_as_uint(src[(long)i * 6 + 4]);
-            const unsigned int ord = (sc & 0x80000000u) ? ~sc : (sc | 0x80000000u);
-            key = ((unsigned long long)ord << 32) | (unsigned long long)(0xffffffffu - (unsigned int)i);
-        }
-        keys[i] = key;
-    }
-    __syncthreads();
-    for (int k2 = 2; k2 <= KP; k2 <<= 1) {
-        for (int j = k2 >> 1; j > 0; j >>= 1) {
-            for (int t = threadIdx.x; t < KP / 2; t += DET_SORT_THREADS) {
-                const int lo = ((t / j) * 2 * j) + (t % j);
-                const int hi = lo + j;
-                const bool desc = ((lo & k2) == 0);
-                const unsigned long long a = keys[lo], b = keys[hi];
-                if ((a < b) == desc) { keys[lo] = b; keys[hi] = a; }
-            }
-            __syncthreads();
-        }
-    }
+    rr_sort_rows6_keys<DET_SORT_THREADS>(src, n, keys, KP);
     const long start = out_off ? min(max((long)out_off[f], 0l), out_rows) : (long)f * K;
     const int nw = (int)min((long)n, out_rows - start);  // == n whenever out_off is the prefix of count
     float *dst = out + start * 6;
     for (int k = threadIdx.x; k < nw; k += DET_SORT_THREADS) {
-        int pos = (int)(0xffffffffu - (unsigned int)(keys[k] & 0xffffffffull));
-        pos = min(max(pos, 0), n - 1);
+        const int pos = min(max((int)rr_key_pos(keys[k]), 0), n - 1);
         const float *r = src + (long)pos * 6;
-        float *o = dst + (long)k * 6;
-        o[0] = r[0]; o[1] = r[1];
-        o[2] = xyxy ? r[0] + r[2] : r[2];
-        o[3] = xyxy ? r[1] + r[3] : r[3];
-        o[4] = r[4]; o[5] = r[5];
+        rr_store_row6(dst + (long)k * 6, r[0], r[1], xyxy ? r[0] + r[2] : r[2], xyxy ? r[1] + r[3] : r[3], r[4], r[5]);
     }
     if (!out_off) {
-        for (int k = n + threadIdx.x; k < K; k += DET_SORT_THREADS) {
-            float *o = dst + (long)k * 6;
-            o[0] = 0.f; o[1] = 0.f; o[2] = 0.f; o[3] = 0.f; o[4] = 0.f; o[5] = -1.0f;
-        }
+        for (int k = n + threadIdx.x; k < K; k += DET_SORT_THREADS) rr_store_row6(dst + (long)k * 6, 0.f, 0.f, 0.f, 0.f, 0.f, -1.0f);
     }
+}
+
+// the grid of the three prepare launchers: one thread per output pixel, capped (the kernel strides)
+inline dim3 prepare_grid(int images, int oh, int ow)
+{
+    const long total = (long)images * oh * ow;
+    long blocks = (total + DET_THREADS - 1) / DET_THREADS;
+    if (blocks > 8192) blocks = 8192;
+    return dim3((unsigned)blocks);
 }
 
 }  // namespace
@@ -409,10 +330,7 @@ extern "C" int rr_prepare_frames(const unsigned char *frames, const float *mean,
 {
     RR_CHECK_ARG(n > 0 && h > 0 && w > 0 && oh > 0 && ow > 0, "rr_prepare_frames: bad dims");
     RR_CHECK_ARG(frames && mean && stdv && out, "rr_prepare_frames: null pointer");
-    const long total = (long)n * oh * ow;
-    long blocks = (total + DET_THREADS - 1) / DET_THREADS;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(prepare_frames_kernel, dim3((unsigned)blocks), dim3(DET_THREADS), 0, stream, frames, mean, stdv, out, n, h,
+    hipLaunchKernelGGL(prepare_frames_kernel, prepare_grid(n, oh, ow), dim3(DET_THREADS), 0, stream, frames, mean, stdv, out, n, h,
                        w, oh, ow);
     RR_CHECK_LAUNCH("rr_prepare_frames");
     return RR_OK;
@@ -423,10 +341,7 @@ extern "C" int rr_prepare_frames_pair(const unsigned char *frames, const float *
 {
     RR_CHECK_ARG(n > 0 && h > 0 && w > 0 && oh > 0 && ow > 0, "rr_prepare_frames_pair: bad dims");
     RR_CHECK_ARG(frames && mean && stdv && out, "rr_prepare_frames_pair: null pointer");
-    const long total = (long)n * oh * ow;
-    long blocks = (total + DET_THREADS - 1) / DET_THREADS;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(prepare_frames_pair_kernel, dim3((unsigned)blocks), dim3(DET_THREADS), 0, stream, frames, mean, stdv, out,
+    hipLaunchKernelGGL(prepare_frames_pair_kernel, prepare_grid(n, oh, ow), dim3(DET_THREADS), 0, stream, frames, mean, stdv, out,
                        n, h, w, oh, ow);
     RR_CHECK_LAUNCH("rr_prepare_frames_pair");
     return RR_OK;
@@ -441,11 +356,8 @@ extern "C" int rr_prepare_tiles(const unsigned char *frames, const long long *fr
     RR_CHECK_ARG(ntiles <= 0x7fffffff / 3, "rr_prepare_tiles: %d tiles", ntiles);
     if (ntiles == 0) return RR_OK;
     RR_CHECK_ARG(frames && frame_base && frame_hw && tiles && mean && stdv && out, "rr_prepare_tiles: null pointer");
-    const long total = (long)ntiles * oh * ow;
-    long blocks = (total + DET_THREADS - 1) / DET_THREADS;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(prepare_tiles_kernel, dim3((unsigned)blocks), dim3(DET_THREADS), 0, stream, frames, frame_base, frame_hw,
-                       nframes, tiles, ntiles, th, tw, oh, ow, mean, stdv, out);
+    hipLaunchKernelGGL(prepare_tiles_kernel, prepare_grid(ntiles, oh, ow), dim3(DET_THREADS), 0, stream, frames, frame_base,
+                       frame_hw, nframes, tiles, ntiles, th, tw, oh, ow, mean, stdv, out);
     RR_CHECK_LAUNCH("rr_prepare_tiles");
     return RR_OK;
 }

@@ -10,6 +10,7 @@
 // Latency-bound (one barrier per kept box); algorithmic traffic = n*6*4 B in + kept rows out.
 #include "common.h"
 #include "rrnet_hip.h"
+#include "rowkit.h"
 
 namespace {
 constexpr int NT = 256;
@@ -46,28 +47,19 @@ __global__ __launch_bounds__(NT) void hard_nms_kernel(float *boxes, const int *s
         __syncthreads();
     }
     __syncthreads();
-    // stable compaction of the kept rows to the front of the segment
+    // stable compaction of the kept rows (read from LDS) to the front of the segment
     int run = 0;
-    const int lane = tid & 63, wave = tid >> 6;
     for (int base = 0; base < n; base += NT) {
         const int i = base + tid;
         const bool keep = i < n && !flag[i];
-        const unsigned long long m = __ballot(keep);
-        const int within = __popcll(m & ((1ull << lane) - 1ull));
-        __syncthreads();
-        if (lane == 0) wsum[wave] = __popcll(m);
-        __syncthreads();
-        int before = 0, tot = 0;
-        for (int w = 0; w < NT / 64; ++w) {
-            if (w < wave) before += wsum[w];
-            tot += wsum[w];
-        }
+        int total;
+        const int pos = run + rr_block_rank<NT / 64>(keep, wsum, total);
         if (keep) {
-            float *d = g + (long)(run + before + within) * 6;
-#pragma unroll
-            for (int e = 0; e < 6; ++e) d[e] = bx[i * 6 + e];
+            const float *r = bx + i * 6;
+            rr_store_row6(g + (long)pos * 6, r[0], r[1], r[2], r[3], r[4], r[5]);
         }
-        run += tot;
+        run += total;
+        __syncthreads();
     }
     if (tid == 0) n_out[seg] = run;
 }

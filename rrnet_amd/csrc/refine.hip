@@ -12,6 +12,7 @@
 // HBM traffic is R*(5+4+2)*4 B in and R*6*4 B out per call: latency-bound, not bandwidth-bound.
 #include "common.h"
 #include "rrnet_hip.h"
+#include "rowkit.h"
 
 namespace {
 
@@ -23,45 +24,24 @@ __global__ __launch_bounds__(256) void refine_boxes_kernel(const float *rois, co
                                                            float *out6, int *seg_len)
 {
     __shared__ int wave_cnt[4];
-    __shared__ int run;
     const int s = blockIdx.x;
     const int r0 = seg_off[s], n = seg_off[s + 1] - r0;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) run = 0;
-    __syncthreads();
+    int run = 0;
     for (int base = 0; base < n; base += 256) {
         const int i = base + threadIdx.x;
         bool keep = false;
-        float o0 = 0.f, o1 = 0.f, o2 = 0.f, o3 = 0.f, sc = 0.f, cl = 0.f;
+        float o0 = 0.f, o1 = 0.f, ow = 0.f, oh = 0.f, sc = 0.f, cl = 0.f;
         if (i < n) {
             const long r = r0 + i;
-            const float *q = rois + r * 5;
-            const float *g = reg + r * 4;
-            // generate_bbox: xyxy * scale -> xywh -> w,h += 1 -> centre / size update -> xywh
-            const float x = q[1] * scale, y = q[2] * scale;
-            const float w = (q[3] * scale - x) + 1.0f, h = (q[4] * scale - y) + 1.0f;
-            const float cx = (g[0] * w + x) + w / 2.0f;
-            const float cy = (g[1] * h + y) + h / 2.0f;
-            const float ow = expf(g[2]) * w, oh = expf(g[3]) * h;
-            o0 = cx - ow / 2.0f;
-            o1 = cy - oh / 2.0f;
-            o2 = o0 + ow;           // _ext_nms: x2 = x + w
-            o3 = o1 + oh;
+            rr_generate_bbox(rois + r * 5, reg + r * 4, scale, o0, o1, ow, oh);
             sc = scores[r];
             cl = clses[r] + 1.0f;
             keep = sc > thr;
         }
-        const unsigned long long m = __ballot(keep);
-        if (lane == 0) wave_cnt[wave] = __popcll(m);
-        __syncthreads();
-        int pos = run + __popcll(m & ((1ull << lane) - 1ull));
-        for (int wv = 0; wv < wave; ++wv) pos += wave_cnt[wv];
-        if (keep) {
-            float *o = out6 + (long)(r0 + pos) * 6;
-            o[0] = o0; o[1] = o1; o[2] = o2; o[3] = o3; o[4] = sc; o[5] = cl;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) run += wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+        int total;
+        const int pos = run + rr_block_rank<4>(keep, wave_cnt, total);
+        if (keep) rr_store_row6(out6 + (long)(r0 + pos) * 6, o0, o1, o0 + ow, o1 + oh, sc, cl);   // _ext_nms: x2 = x + w
+        run += total;
         __syncthreads();
     }
     if (threadIdx.x == 0) seg_len[s] = run;
@@ -83,34 +63,19 @@ __global__ __launch_bounds__(256) void finalize_frames_kernel(const float *boxes
     __syncthreads();
     for (int s = s0; s < s0 + segs_per_frame; ++s) {
         const int n = n_out[s], src0 = seg_off[s], dst0 = out_off[s] - o0;
-        for (int i = threadIdx.x; i < n; i += 256) {
-            const unsigned int sc = __float_as_uint(boxes6[(long)(src0 + i) * 6 + 4]);
-            const unsigned int ord = (sc & 0x80000000u) ? ~sc : (sc | 0x80000000u);
-            // high word: score order; low word: ~position in the frame's concatenation (earlier row wins a tie)
-            keys[dst0 + i] = ((unsigned long long)ord << 32) | (unsigned long long)(0xffffffffu - (unsigned int)(dst0 + i));
-        }
+        // position = the row's place in the frame's concatenation
+        for (int i = threadIdx.x; i < n; i += 256)
+            keys[dst0 + i] = rr_score_key(boxes6[(long)(src0 + i) * 6 + 4], (unsigned int)(dst0 + i));
     }
     __syncthreads();
-    for (int k2 = 2; k2 <= KP; k2 <<= 1) {
-        for (int j = k2 >> 1; j > 0; j >>= 1) {
-            for (int t = threadIdx.x; t < KP / 2; t += 256) {
-                const int lo = ((t / j) * 2 * j) + (t % j);
-                const int hi = lo + j;
-                const bool desc = ((lo & k2) == 0);
-                const unsigned long long a = keys[lo], b = keys[hi];
-                if ((a < b) == desc) { keys[lo] = b; keys[hi] = a; }
-            }
-            __syncthreads();
-        }
-    }
+    rr_bitonic_sort<256, true>(keys, KP);
     for (int k = threadIdx.x; k < total; k += 256) {
-        const int pos = (int)(0xffffffffu - (unsigned int)(keys[k] & 0xffffffffull));
+        const int pos = (int)rr_key_pos(keys[k]);
         // segment holding that position: segs_per_frame is small (classes), linear search
         int s = s0;
         while (s + 1 < s0 + segs_per_frame && out_off[s + 1] - o0 <= pos) ++s;
         const float *r = boxes6 + (long)(seg_off[s] + (pos - (out_off[s] - o0))) * 6;
-        float *o = out6 + (long)(o0 + k) * 6;
-        o[0] = r[0]; o[1] = r[1]; o[2] = r[2] - r[0]; o[3] = r[3] - r[1]; o[4] = r[4]; o[5] = r[5];
+        rr_store_row6(out6 + (long)(o0 + k) * 6, r[0], r[1], r[2] - r[0], r[3] - r[1], r[4], r[5]);
     }
 }
 
@@ -121,32 +86,10 @@ __global__ __launch_bounds__(1024) void sort_rows_kernel(const float *rows, int 
 {
     extern __shared__ __align__(16) unsigned char smem[];
     unsigned long long *keys = reinterpret_cast<unsigned long long *>(smem);
-    for (int i = threadIdx.x; i < KP; i += 1024) {
-        unsigned long long key = 0ull;
-        if (i < n) {
-            const unsigned int sc = __float_as_uint(rows[(long)i * 6 + 4]);
-            const unsigned int ord = (sc & 0x80000000u) ? ~sc : (sc | 0x80000000u);
-            key = ((unsigned long long)ord << 32) | (unsigned long long)(0xffffffffu - (unsigned int)i);
-        }
-        keys[i] = key;
-    }
-    __syncthreads();
-    for (int k2 = 2; k2 <= KP; k2 <<= 1) {
-        for (int j = k2 >> 1; j > 0; j >>= 1) {
-            for (int t = threadIdx.x; t < KP / 2; t += 1024) {
-                const int lo = ((t / j) * 2 * j) + (t % j);
-                const int hi = lo + j;
-                const bool desc = ((lo & k2) == 0);
-                const unsigned long long a = keys[lo], b = keys[hi];
-                if ((a < b) == desc) { keys[lo] = b; keys[hi] = a; }
-            }
-            __syncthreads();
-        }
-    }
+    rr_sort_rows6_keys<1024>(rows, n, keys, KP);
     for (int k = threadIdx.x; k < n; k += 1024) {
-        const int pos = (int)(0xffffffffu - (unsigned int)(keys[k] & 0xffffffffull));
-#pragma unroll
-        for (int e = 0; e < 6; ++e) out[(long)k * 6 + e] = rows[(long)pos * 6 + e];
+        const float *r = rows + (long)rr_key_pos(keys[k]) * 6;
+        rr_store_row6(out + (long)k * 6, r[0], r[1], r[2], r[3], r[4], r[5]);
     }
 }
 
@@ -160,7 +103,9 @@ extern "C" int rr_sort_rows_by_score(const float *rows6, int n, float *out6, hip
     while (kp < n) kp <<= 1;
     const size_t lds = (size_t)kp * 8;
     if (lds > 48 * 1024)
-        hipFuncSetAttribute(reinterpret_cast<const void *>(sort_rows_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        RR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(sort_rows_kernel),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
+                     "rr_sort_rows_by_score");
     hipLaunchKernelGGL(sort_rows_kernel, dim3(1), dim3(1024), lds, stream, rows6, n, kp, out6);
     RR_CHECK_LAUNCH("rr_sort_rows_by_score");
     return RR_OK;
@@ -189,8 +134,9 @@ extern "C" int rr_finalize_frames(const float *boxes6, const int *seg_off, const
     while (kp < max_frame_boxes) kp <<= 1;
     const size_t lds = (size_t)kp * 8;
     if (lds > 48 * 1024)
-        hipFuncSetAttribute(reinterpret_cast<const void *>(finalize_frames_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds);
+        RR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(finalize_frames_kernel),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
+                     "rr_finalize_frames");
     hipLaunchKernelGGL(finalize_frames_kernel, dim3(nframes), dim3(256), lds, stream, boxes6, seg_off, n_out, out_off,
                        segs_per_frame, kp, out6);
     RR_CHECK_LAUNCH("rr_finalize_frames");

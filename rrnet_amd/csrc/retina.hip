@@ -7,6 +7,7 @@
 // round like the reference's float32 torch ops.
 #include "common.h"
 #include "rrnet_hip.h"
+#include "rowkit.h"
 
 namespace {
 
@@ -525,15 +526,46 @@ __global__ __launch_bounds__(TPB) void retina_loss_bwd_kernel(const float *__res
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// decode: one workgroup per image, rows appended in anchor order by ballot + prefix
+// decode: one workgroup per image, rows appended in anchor order (rr_block_rank).  The class scan and the box arithmetic
+// are written once, for this kernel and the chunked pair below: all three must round identically.
 // ------------------------------------------------------------------------------------------------------------------
+// The largest class probability of one anchor's C logits and its class: the first maximum, and a NaN is the maximum wherever
+// it stands (torch's max).  `best > thr` is false on a NaN: such a row leaves.
+__device__ __forceinline__ float retina_best_class(const float *q, int C, int &bi)
+{
+    float best = sigmoidf_(q[0]);
+    bi = 0;
+    for (int c = 1; c < C; ++c) {
+        const float p = sigmoidf_(q[c]);
+        if (p > best || p != p) {
+            best = p;
+            bi = c;
+        }
+    }
+    return best;
+}
+
+// anchor (x1, y1, x2, y2) + regression d -> x, y, w, h: centres move by 0.1 * d * size, sizes scale by exp(0.2 * d)
+__device__ __forceinline__ void retina_anchor_decode(const float *anchor, const float *loc, float &o0, float &o1, float &o2,
+                                                     float &o3)
+{
+    const rr_f32x4 bx = *reinterpret_cast<const rr_f32x4 *>(anchor);
+    const rr_f32x4 d = *reinterpret_cast<const rr_f32x4 *>(loc);
+    const float w = bx[2] - bx[0], h = bx[3] - bx[1];
+    const float cx = bx[0] + 0.5f * w, cy = bx[1] + 0.5f * h;
+    const float pcx = cx + (d[0] * 0.1f) * w, pcy = cy + (d[1] * 0.1f) * h;
+    o2 = expf(d[2] * 0.2f) * w;
+    o3 = expf(d[3] * 0.2f) * h;
+    o0 = pcx - 0.5f * o2;
+    o1 = pcy - 0.5f * o3;
+}
+
 __global__ __launch_bounds__(TPB) void retina_decode_kernel(const float *__restrict__ logits, const float *__restrict__ loc,
                                                             const float *__restrict__ anchors, int A, int C, float thr,
                                                             float *__restrict__ rows, int *__restrict__ count)
 {
-    __shared__ int wave_cnt[4];
+    __shared__ int wave_cnt[TPB / 64];
     const int b = blockIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float *dst = rows + (long)b * A * 6;
     int run = 0;
     for (int a0 = 0; a0 < A; a0 += TPB) {
@@ -541,41 +573,16 @@ __global__ __launch_bounds__(TPB) void retina_decode_kernel(const float *__restr
         bool keep = false;
         float o0 = 0.f, o1 = 0.f, o2 = 0.f, o3 = 0.f, sc = 0.f, cl = 0.f;
         if (a < A) {
-            const float *q = logits + ((long)b * A + a) * C;
-            float best = sigmoidf_(q[0]);
-            int bi = 0;
-            for (int c = 1; c < C; ++c) {
-                const float p = sigmoidf_(q[c]);
-                if (p > best || p != p) {                 // first maximum; a NaN is the maximum wherever it stands (torch's max)
-                    best = p;
-                    bi = c;
-                }
-            }
-            keep = best > thr;                            // a row with a NaN leaves
-            if (keep) {
-                const rr_f32x4 bx = *reinterpret_cast<const rr_f32x4 *>(anchors + (long)a * 4);
-                const rr_f32x4 d = *reinterpret_cast<const rr_f32x4 *>(loc + ((long)b * A + a) * 4);
-                const float w = bx[2] - bx[0], h = bx[3] - bx[1];
-                const float cx = bx[0] + 0.5f * w, cy = bx[1] + 0.5f * h;
-                const float pcx = cx + (d[0] * 0.1f) * w, pcy = cy + (d[1] * 0.1f) * h;
-                o2 = expf(d[2] * 0.2f) * w;
-                o3 = expf(d[3] * 0.2f) * h;
-                o0 = pcx - 0.5f * o2;
-                o1 = pcy - 0.5f * o3;
-                sc = best;
-                cl = (float)(bi + 1);
-            }
+            int bi;
+            sc = retina_best_class(logits + ((long)b * A + a) * C, C, bi);
+            cl = (float)(bi + 1);
+            keep = sc > thr;
+            if (keep) retina_anchor_decode(anchors + (long)a * 4, loc + ((long)b * A + a) * 4, o0, o1, o2, o3);
         }
-        const unsigned long long m = __ballot(keep);
-        if (lane == 0) wave_cnt[wave] = __popcll(m);
-        __syncthreads();
-        int pos = run + __popcll(m & ((1ull << lane) - 1ull));
-        for (int wv = 0; wv < wave; ++wv) pos += wave_cnt[wv];
-        if (keep && pos < A) {
-            float *o = dst + (long)pos * 6;
-            o[0] = o0; o[1] = o1; o[2] = o2; o[3] = o3; o[4] = sc; o[5] = cl;
-        }
-        run += wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+        int total;
+        const int pos = run + rr_block_rank<TPB / 64>(keep, wave_cnt, total);
+        if (keep && pos < A) rr_store_row6(dst + (long)pos * 6, o0, o1, o2, o3, sc, cl);
+        run += total;
         __syncthreads();
     }
     if (threadIdx.x == 0) count[b] = run;
@@ -597,42 +604,30 @@ struct ScoreCls { float prob; int cls; };
 __global__ __launch_bounds__(TPB) void retina_score_chunks_kernel(const float *__restrict__ logits, int A, int C, float thr,
                                                                   ScoreCls *__restrict__ sc, int *__restrict__ chunk_cnt)
 {
-    __shared__ int wave_cnt[4];
+    __shared__ int wave_cnt[TPB / 64];
     const int b = blockIdx.y, chunk = blockIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int a = chunk * DCHUNK + threadIdx.x;
     bool keep = false;
     if (a < A) {
-        const float *q = logits + ((long)b * A + a) * C;
-        float best = sigmoidf_(q[0]);
-        int bi = 0;
-        for (int c = 1; c < C; ++c) {
-            const float p = sigmoidf_(q[c]);
-            if (p > best || p != p) {                     // as retina_decode_kernel: first maximum, a NaN is the maximum
-                best = p;
-                bi = c;
-            }
-        }
-        keep = best > thr;
+        int bi;
         ScoreCls r;
-        r.prob = best;
+        r.prob = retina_best_class(logits + ((long)b * A + a) * C, C, bi);
+        keep = r.prob > thr;
         r.cls = keep ? bi + 1 : 0;
         sc[(long)b * A + a] = r;
     }
-    const unsigned long long m = __ballot(keep);
-    if (lane == 0) wave_cnt[wave] = __popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) chunk_cnt[(long)b * gridDim.x + chunk] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+    int total;
+    rr_block_rank<TPB / 64>(keep, wave_cnt, total);
+    if (threadIdx.x == 0) chunk_cnt[(long)b * gridDim.x + chunk] = total;
 }
 
 __global__ __launch_bounds__(TPB) void retina_write_chunks_kernel(const ScoreCls *__restrict__ sc, const int *__restrict__ chunk_cnt,
                                                                   const float *__restrict__ loc, const float *__restrict__ anchors,
                                                                   int A, float *__restrict__ rows, int K, int *__restrict__ count)
 {
-    __shared__ int wave_cnt[4];
-    __shared__ int wave_sum[4];
+    __shared__ int wave_cnt[TPB / 64];
+    __shared__ int wave_sum[TPB / 64];
     const int b = blockIdx.y, chunk = blockIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int *cnt = chunk_cnt + (long)b * gridDim.x;
     int part = 0;
     for (int i = threadIdx.x; i < chunk; i += TPB) part += min(max(cnt[i], 0), DCHUNK);   // a count is at most its chunk
@@ -643,28 +638,17 @@ __global__ __launch_bounds__(TPB) void retina_write_chunks_kernel(const ScoreCls
     r.cls = 0;
     if (a < A) r = sc[(long)b * A + a];
     const bool keep = r.cls > 0;
-    const unsigned long long m = __ballot(keep);
-    if (lane == 0) {
-        wave_sum[wave] = part;
-        wave_cnt[wave] = __popcll(m);
-    }
-    __syncthreads();
+    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = part;            // visible behind rr_block_rank's barrier
+    int total;
+    const int rank = rr_block_rank<TPB / 64>(keep, wave_cnt, total);
     const int base = wave_sum[0] + wave_sum[1] + wave_sum[2] + wave_sum[3];     // base <= chunk * DCHUNK <= A: no overflow
-    int pos = base + __popcll(m & ((1ull << lane) - 1ull));
-    for (int wv = 0; wv < wave; ++wv) pos += wave_cnt[wv];
+    const int pos = base + rank;                                                // the chunks in front, then this one's rows
     if (keep && pos < K) {
-        const rr_f32x4 bx = *reinterpret_cast<const rr_f32x4 *>(anchors + (long)a * 4);
-        const rr_f32x4 d = *reinterpret_cast<const rr_f32x4 *>(loc + ((long)b * A + a) * 4);
-        const float w = bx[2] - bx[0], h = bx[3] - bx[1];
-        const float cx = bx[0] + 0.5f * w, cy = bx[1] + 0.5f * h;
-        const float pcx = cx + (d[0] * 0.1f) * w, pcy = cy + (d[1] * 0.1f) * h;
-        const float o2 = expf(d[2] * 0.2f) * w;
-        const float o3 = expf(d[3] * 0.2f) * h;
-        float *o = rows + ((long)b * K + pos) * 6;
-        o[0] = pcx - 0.5f * o2; o[1] = pcy - 0.5f * o3; o[2] = o2; o[3] = o3; o[4] = r.prob; o[5] = (float)r.cls;
+        float o0, o1, o2, o3;
+        retina_anchor_decode(anchors + (long)a * 4, loc + ((long)b * A + a) * 4, o0, o1, o2, o3);
+        rr_store_row6(rows + ((long)b * K + pos) * 6, o0, o1, o2, o3, r.prob, (float)r.cls);
     }
-    if (chunk == (int)gridDim.x - 1 && threadIdx.x == 0)
-        count[b] = base + wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+    if (chunk == (int)gridDim.x - 1 && threadIdx.x == 0) count[b] = base + total;
 }
 
 inline int blocks_of(long total) { return (int)((total + TPB - 1) / TPB); }

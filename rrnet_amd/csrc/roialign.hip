@@ -9,6 +9,7 @@
 // backward scatters the same taps with float atomics into a zeroed gradient map.
 #include "common.h"
 #include "rrnet_hip.h"
+#include "rowkit.h"        // the bitonic network only: this file is built with the default contraction
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
 namespace {
@@ -354,18 +355,7 @@ __global__ __launch_bounds__(256) void roi_spatial_order_kernel(const float *roi
         keys[i] = key;
     }
     __syncthreads();
-    for (int k2 = 2; k2 <= np; k2 <<= 1) {
-        for (int j = k2 >> 1; j > 0; j >>= 1) {
-            for (int t = threadIdx.x; t < np / 2; t += 256) {
-                const int lo = ((t / j) * 2 * j) + (t % j);
-                const int hi = lo + j;
-                const bool asc = ((lo & k2) == 0);
-                const unsigned long long a = keys[lo], b = keys[hi];
-                if ((a > b) == asc) { keys[lo] = b; keys[hi] = a; }
-            }
-            __syncthreads();
-        }
-    }
+    rr_bitonic_sort<256, false>(keys, np);
     for (int i = threadIdx.x; i < n; i += 256) order[o0 + i] = o0 + (int)(keys[i] & 0xffffffffull);
 }
 }  // namespace

@@ -72,6 +72,40 @@ def _vec3(v, device):
     return torch.tensor([float(x) for x in v], dtype=torch.float32, device=device)
 
 
+def _check_frames(what, frames_u8):
+    """The frame-tensor checks of the detect_frames* entry points; `what` is the caller's name in the messages."""
+    if not torch.is_tensor(frames_u8) or frames_u8.dtype != torch.uint8:
+        raise TypeError("%s: frames must be a uint8 tensor [B,H,W,3], got %s"
+                        % (what, frames_u8.dtype if torch.is_tensor(frames_u8) else type(frames_u8).__name__))
+    if frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
+        raise ValueError("%s: frames must be [B,H,W,3], got %s" % (what, tuple(frames_u8.shape)))
+
+
+def _soft_nms_by_class(merged, count, num_classes):
+    """`_ext_nms` up to the Soft-NMS itself on merged [B,K,6] xywh rows, count int32 [B]: stable score sort into xyxy rows
+    (x2 = x + w as the kernel forms it), stable grouping by class (the padding rows, class -1, are dropped there), per-class
+    gaussian Soft-NMS (sigma 0.5, Nt 0.7, threshold 0.1).  -> (rows [B*K,6], seg_off, n_out, err), all on the device."""
+    ordered = ops.sort_frames_by_score(merged, count, xyxy=True)
+    grouped, seg_off, seg_len = ops.group_by_class(ordered, num_classes, cls_base=1)
+    rows = grouped.view(-1, 6)
+    n_out, err = soft_nms_segments(rows, seg_off, merged.shape[1], sigma=0.5, Nt=0.7, threshold=0.1, method=2,
+                                   seg_len=seg_len, check=False)
+    return rows, seg_off, n_out, err
+
+
+def _hard_nms_tail(rows, count, counts, nms_thresh):
+    """RetinaNet's tail on rows [B,K,6], count int32 [B] (counts: its host copy, not all zero): stable score sort,
+    rr_nms_frames ("+1" IoU, suppression at IoU > nms_thresh), rr_pack_frames.  -> (boxes [n,6], frame_off int32 [B+1]).
+    One host read: the final offsets."""
+    most = int(counts.max())
+    cand_off = ops.seg_prefix(count)
+    ordered = ops.sort_frames_by_score(rows, count, out_off=cand_off)
+    keep, kept = ops.nms_frames(ordered, cand_off, most, nms_thresh)
+    out6, frame_off = ops.pack_frames(ordered, cand_off, keep, kept, most, out_rows=int(counts.sum()))
+    fo = frame_off.cpu()                                            # host read: the final offsets
+    return out6[:int(fo[-1])], frame_off
+
+
 @torch.no_grad()
 def detect_frames(model, frames_u8, scales, mean, std, *, nms, k=1500, score_thr=0.01, scale_factor=4, num_classes=10,
                   timer=None):
@@ -84,11 +118,7 @@ def detect_frames(model, frames_u8, scales, mean, std, *, nms, k=1500, score_thr
     threshold 0.1) and a second stable sort.  Host reads: the model's RoI count per scale and the final counts.
     Raises ValueError when len(scales)*k exceeds the LDS sort's 16384 rows, ZeroDivisionError where soft_nms would.
     timer (optional): called as timer(stage) with 'prepare' / 'model' / 'post' after the launches of each stage."""
-    if not torch.is_tensor(frames_u8) or frames_u8.dtype != torch.uint8:
-        raise TypeError("detect_frames: frames must be a uint8 tensor [B,H,W,3], got %s"
-                        % (frames_u8.dtype if torch.is_tensor(frames_u8) else type(frames_u8).__name__))
-    if frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
-        raise ValueError("detect_frames: frames must be [B,H,W,3], got %s" % (tuple(frames_u8.shape),))
+    _check_frames("detect_frames", frames_u8)
     scales = list(scales)
     rows_per_frame = len(scales) * int(k)
     if rows_per_frame > ops.DETECT_MAX_ROWS or rows_per_frame <= 0:
@@ -126,11 +156,7 @@ def finish_frames(merged, count, nms, num_classes=10):
         out6 = ops.sort_frames_by_score(merged, count, out_off=frame_off)
         fo = frame_off.cpu()                                        # the one sync: final counts
         return out6[:int(fo[-1])], frame_off
-    ordered = ops.sort_frames_by_score(merged, count, xyxy=True)    # padding rows (class -1) are dropped by the grouping
-    grouped, seg_off, seg_len = ops.group_by_class(ordered, num_classes, cls_base=1)
-    rows = grouped.view(-1, 6)
-    n_out, err = soft_nms_segments(rows, seg_off, rows_per_frame, sigma=0.5, Nt=0.7, threshold=0.1, method=2,
-                                   seg_len=seg_len, check=False)
+    rows, seg_off, n_out, err = _soft_nms_by_class(merged, count, num_classes)
     out6, frame_off = ops.finalize_frames(rows, seg_off, n_out, b, num_classes, rows_per_frame)
     frame_off = frame_off.contiguous()
     fo = frame_off.cpu()                                            # the one sync: final counts (+ error flag)
@@ -139,17 +165,16 @@ def finish_frames(merged, count, nms, num_classes=10):
     return out6[:int(fo[-1])], frame_off
 
 
-class Detector:
-    """RRNet from a reference-format checkpoint, ready for `detect`: builds RRNet(cfg) (stage-1 NMS as
-    cfg.Model.nms_type_for_stage1 / nms_per_class_for_stage1 say, bf16 as cfg.Model.bf16 says), loads the state dict
-    (checkpoint=None keeps the initial weights) and sets eval mode."""
+class _LoadedModel:
+    """What the three frame detectors share: model_cls(cfg) with a reference-format state dict (a path or a dict, with or
+    without `module.` prefixes; checkpoint=None keeps the initial weights) on the device, channels-last, in eval mode;
+    mean / std from cfg.Val.transforms."""
 
-    def __init__(self, cfg, checkpoint=None, device=None):
+    def __init__(self, model_cls, cfg, checkpoint, device):
         from rrnet_amd.datasets.augment import chain_params
-        from rrnet_amd.models.rrnet import RRNet
         self.cfg = cfg
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        model = RRNet(cfg)
+        model = model_cls(cfg)
         if checkpoint is not None:
             sd = torch.load(checkpoint, map_location='cpu') if isinstance(checkpoint, (str, os.PathLike)) else checkpoint
             sd = {(key[7:] if key.startswith('module.') else key): v for key, v in sd.items()}
@@ -157,6 +182,16 @@ class Detector:
         self.model = model.to(self.device).to(memory_format=torch.channels_last).eval()
         p = chain_params(cfg.Val.transforms)
         self.mean, self.std = p["mean"], p["std"]
+
+
+class Detector(_LoadedModel):
+    """RRNet from a reference-format checkpoint, ready for `detect`: builds RRNet(cfg) (stage-1 NMS as
+    cfg.Model.nms_type_for_stage1 / nms_per_class_for_stage1 say, bf16 as cfg.Model.bf16 says), loads the state dict
+    (checkpoint=None keeps the initial weights) and sets eval mode."""
+
+    def __init__(self, cfg, checkpoint=None, device=None):
+        from rrnet_amd.models.rrnet import RRNet
+        super().__init__(RRNet, cfg, checkpoint, device)
         self.scale_factor = int(cfg.Train.scale_factor)
         self.num_classes = int(cfg.num_classes)
 
@@ -184,11 +219,7 @@ def detect_frames_centernet(model, frames_u8, scales, mean, std, *, nms, flip=Tr
     Host reads: none per scale; at the end the final counts (with nms also the packed row count and the error flag).
     Raises ValueError when len(scales) * (2 if flip else 1) * k exceeds the LDS sort's 16384 rows, ZeroDivisionError where
     soft_nms would.  timer as in detect_frames."""
-    if not torch.is_tensor(frames_u8) or frames_u8.dtype != torch.uint8:
-        raise TypeError("detect_frames_centernet: frames must be a uint8 tensor [B,H,W,3], got %s"
-                        % (frames_u8.dtype if torch.is_tensor(frames_u8) else type(frames_u8).__name__))
-    if frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
-        raise ValueError("detect_frames_centernet: frames must be [B,H,W,3], got %s" % (tuple(frames_u8.shape),))
+    _check_frames("detect_frames_centernet", frames_u8)
     scales = list(scales)
     halves = 2 if flip else 1
     rows_per_frame = len(scales) * halves * int(k)
@@ -225,12 +256,7 @@ def finish_frames_centernet(merged, count, nms, num_classes=10):
     rows, concatenated — the rows stay xyxy and are not sorted again, as in the reference."""
     if not nms:
         return finish_frames(merged, count, False, num_classes)
-    rows_per_frame = merged.shape[1]
-    ordered = ops.sort_frames_by_score(merged, count, xyxy=True)    # x2 = x + w as the kernel forms it; padding is dropped below
-    grouped, seg_off, seg_len = ops.group_by_class(ordered, num_classes, cls_base=1)
-    rows = grouped.view(-1, 6)
-    n_out, err = soft_nms_segments(rows, seg_off, rows_per_frame, sigma=0.5, Nt=0.7, threshold=0.1, method=2,
-                                   seg_len=seg_len, check=False)
+    rows, seg_off, n_out, err = _soft_nms_by_class(merged, count, num_classes)
     _, _, _, out6, out_off = ops.pack_segments(rows, seg_off, n_out, num_classes, want_rois=False, want_rows=True,
                                                want_offsets=True)   # its host read: the packed row count
     frame_off = out_off[::num_classes].contiguous()
@@ -239,24 +265,14 @@ def finish_frames_centernet(merged, count, nms, num_classes=10):
     return out6, frame_off
 
 
-class CenterNetFrameDetector:
+class CenterNetFrameDetector(_LoadedModel):
     """CenterNet from a reference-format checkpoint, ready for `detect`: the counterpart of Detector.  Builds CenterNet(cfg),
     loads the state dict (with or without `module.` prefixes; checkpoint=None keeps the initial weights), sets eval mode
     and channels-last; mean / std come from cfg.Val.transforms.  fp32 only."""
 
     def __init__(self, cfg, checkpoint=None, device=None):
-        from rrnet_amd.datasets.augment import chain_params
         from rrnet_amd.models.centernet import CenterNet
-        self.cfg = cfg
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        model = CenterNet(cfg)
-        if checkpoint is not None:
-            sd = torch.load(checkpoint, map_location='cpu') if isinstance(checkpoint, (str, os.PathLike)) else checkpoint
-            sd = {(key[7:] if key.startswith('module.') else key): v for key, v in sd.items()}
-            model.load_state_dict(sd)
-        self.model = model.to(self.device).to(memory_format=torch.channels_last).eval()
-        p = chain_params(cfg.Val.transforms)
-        self.mean, self.std = p["mean"], p["std"]
+        super().__init__(CenterNet, cfg, checkpoint, device)
         self.scale_factor = int(cfg.Train.scale_factor)
         self.num_classes = int(cfg.num_classes)
 
@@ -283,11 +299,7 @@ def detect_frames_retinanet(model, frames_u8, mean, std, anchors, *, score_thr=0
     device: per frame the rows RetinaNetOperator.evaluate_images returns.  Host reads: the candidate counts and the final
     offsets.  Raises ValueError when a frame has more than 16384 candidates (evaluate_images' refusal), before the sort.
     timer as in detect_frames."""
-    if not torch.is_tensor(frames_u8) or frames_u8.dtype != torch.uint8:
-        raise TypeError("detect_frames_retinanet: frames must be a uint8 tensor [B,H,W,3], got %s"
-                        % (frames_u8.dtype if torch.is_tensor(frames_u8) else type(frames_u8).__name__))
-    if frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
-        raise ValueError("detect_frames_retinanet: frames must be [B,H,W,3], got %s" % (tuple(frames_u8.shape),))
+    _check_frames("detect_frames_retinanet", frames_u8)
     from rrnet_amd import _C
     _C.require_cuda(frames_u8)
     tick = timer if timer is not None else (lambda stage: None)
@@ -310,17 +322,12 @@ def detect_frames_retinanet(model, frames_u8, mean, std, anchors, *, score_thr=0
         f = int(over[0, 0])
         raise ValueError("detect_frames_retinanet: frame %d has %d candidates above the score threshold; the score sort "
                          "accepts %d per frame" % (f, int(counts[f]), limit))
-    most = int(counts.max())
-    if most == 0:
-        tick('post')
-        return rows.new_zeros((0, 6)), torch.zeros(b + 1, dtype=torch.int32, device=dev)
-    cand_off = ops.seg_prefix(count)
-    ordered = ops.sort_frames_by_score(rows, count, out_off=cand_off)
-    keep, kept = ops.nms_frames(ordered, cand_off, most, nms_thresh)
-    out6, frame_off = ops.pack_frames(ordered, cand_off, keep, kept, most, out_rows=int(counts.sum()))
-    fo = frame_off.cpu()                                            # host read: the final offsets
+    if int(counts.max()) == 0:
+        out = rows.new_zeros((0, 6)), torch.zeros(b + 1, dtype=torch.int32, device=dev)
+    else:
+        out = _hard_nms_tail(rows, count, counts, nms_thresh)
     tick('post')
-    return out6[:int(fo[-1])], frame_off
+    return out
 
 
 def _tile_hw(tile):
@@ -402,15 +409,9 @@ def finish_tiles(rows, count_in, tiles, sizes, tile, in_size, zoom=1.0, margin=0
     ops.merge_tiles(rows, count_in, table, sizes, tile, in_size, np.float32(zoom), margin, merged, count)
     counts = count.cpu()                                            # host read: the frame counts
     refuse_over(counts.tolist())
-    most = int(counts.max())
-    if most == 0:
+    if int(counts.max()) == 0:
         return empty
-    cand_off = ops.seg_prefix(count)
-    ordered = ops.sort_frames_by_score(merged, count, out_off=cand_off)
-    keep, kept = ops.nms_frames(ordered, cand_off, most, nms_thresh)
-    out6, frame_off = ops.pack_frames(ordered, cand_off, keep, kept, most, out_rows=int(counts.sum()))
-    fo = frame_off.cpu()                                            # host read: the final offsets
-    return out6[:int(fo[-1])], frame_off
+    return _hard_nms_tail(merged, count, counts, nms_thresh)
 
 
 def _tiles_of(frames, tile, overlap):
@@ -490,26 +491,16 @@ def detect_tiled_retinanet(model, frames, mean, std, anchors, *, tile, overlap, 
     return out
 
 
-class RetinaNetFrameDetector:
+class RetinaNetFrameDetector(_LoadedModel):
     """RetinaNet from a reference-format checkpoint, ready for `detect`: the counterpart of CenterNetFrameDetector.  Builds
     RetinaNet(cfg), loads the state dict (with or without `module.` prefixes; checkpoint=None keeps the initial weights),
     sets eval mode and channels-last; mean / std come from cfg.Val.transforms; the anchors are Anchors(sizes=(16, 64, 128)),
     cached per frame size on the device.  fp32 only."""
 
     def __init__(self, cfg, checkpoint=None, device=None):
-        from rrnet_amd.datasets.augment import chain_params
         from rrnet_amd.models.retinanet import RetinaNet
         from rrnet_amd.modules.anchor import Anchors
-        self.cfg = cfg
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        model = RetinaNet(cfg)
-        if checkpoint is not None:
-            sd = torch.load(checkpoint, map_location='cpu') if isinstance(checkpoint, (str, os.PathLike)) else checkpoint
-            sd = {(key[7:] if key.startswith('module.') else key): v for key, v in sd.items()}
-            model.load_state_dict(sd)
-        self.model = model.to(self.device).to(memory_format=torch.channels_last).eval()
-        p = chain_params(cfg.Val.transforms)
-        self.mean, self.std = p["mean"], p["std"]
+        super().__init__(RetinaNet, cfg, checkpoint, device)
         self.anchor_maker = Anchors(sizes=(16, 64, 128))
         self._anchors = {}
 
@@ -545,9 +536,16 @@ class RetinaNetFrameDetector:
         x = ops.prepare_tiles(frames, table, (th, tw), zoom, _vec3(self.mean, self.device), _vec3(self.std, self.device))
         best = torch.cat([torch.sigmoid(self.model(x[i:i + tile_batch])[1].float()).amax(dim=2)
                           for i in range(0, len(table), int(tile_batch))])      # [T,A]
-        rows_per_tile = min(int(rows_per_tile), best.shape[1] - 1)
-        thr = float(best.topk(rows_per_tile + 1, dim=1).values[:, -1].max())
-        return thr, int((best > thr).sum(dim=1).max())
+        thr, kept = self._pick_threshold(best, rows_per_tile)
+        return thr, int(kept.max())
+
+    @staticmethod
+    def _pick_threshold(best, rows):
+        """best [N,A] = per image the largest class probability of every anchor -> (the smallest threshold at which
+        `prob > thr` keeps at most `rows` anchors of any image, the number each image keeps at it)."""
+        rows = min(int(rows), best.shape[1] - 1)
+        thr = float(best.topk(rows + 1, dim=1).values[:, -1].max())
+        return thr, (best > thr).sum(dim=1)
 
     @torch.no_grad()
     def threshold_for_rows(self, frames_u8, rows_per_frame):
@@ -557,7 +555,5 @@ class RetinaNetFrameDetector:
         benchmark, not part of the detection path."""
         x = ops.prepare_frames(frames_u8.contiguous(), _vec3(self.mean, self.device), _vec3(self.std, self.device), 1)
         _, cls_pre = self.model(x)
-        best = torch.sigmoid(cls_pre.float()).amax(dim=2)                       # [B,A]
-        rows_per_frame = min(int(rows_per_frame), best.shape[1] - 1)
-        thr = float(best.topk(rows_per_frame + 1, dim=1).values[:, -1].max())   # `prob > thr` keeps at most rows_per_frame
-        return thr, (best > thr).sum(dim=1).tolist()
+        thr, kept = self._pick_threshold(torch.sigmoid(cls_pre.float()).amax(dim=2), rows_per_frame)   # [B,A]
+        return thr, kept.tolist()

@@ -1824,10 +1824,8 @@ def sort_rows_by_score(rows6):
 DETECT_MAX_ROWS = 16384       # RR_DETECT_MAX_ROWS: merged rows of one frame the LDS sort holds
 
 
-def prepare_frames(frames_u8, mean, std, scale_factor):
-    """rr_prepare_frames: frames uint8 [B,H,W,3] (RGB) -> ToTensor -> Normalize -> F.interpolate(scale_factor, bilinear,
-    align_corners=True) -> logical [B,3,floor(H*s),floor(W*s)] float32 in NHWC memory.  mean / std float32 [3] on the
-    device.  Same bits as resize_bilinear_ac on the host-normalised frame."""
+def _prepare_frames(symbol, copies, frames_u8, mean, std, scale_factor):
+    """The body of prepare_frames (copies = 1) and prepare_frames_pair (copies = 2): `copies` output images per frame."""
     import math
     _C.require_cuda(frames_u8, mean, std)
     assert frames_u8.dtype == torch.uint8 and frames_u8.is_contiguous() and frames_u8.dim() == 4 and frames_u8.shape[3] == 3
@@ -1835,10 +1833,16 @@ def prepare_frames(frames_u8, mean, std, scale_factor):
     assert mean.is_contiguous() and std.is_contiguous()
     b, h, w, _ = frames_u8.shape
     oh, ow = int(math.floor(h * scale_factor)), int(math.floor(w * scale_factor))
-    out = empty_nhwc(b, 3, oh, ow, frames_u8.device)
-    _C.check(_C.fn("rr_prepare_frames")(_C.ptr(frames_u8), _C.ptr(mean), _C.ptr(std), _C.ptr(out), b, h, w, oh, ow,
-                                        _C.stream()), "rr_prepare_frames")
+    out = empty_nhwc(copies * b, 3, oh, ow, frames_u8.device)
+    _C.check(_C.fn(symbol)(_C.ptr(frames_u8), _C.ptr(mean), _C.ptr(std), _C.ptr(out), b, h, w, oh, ow, _C.stream()), symbol)
     return out
+
+
+def prepare_frames(frames_u8, mean, std, scale_factor):
+    """rr_prepare_frames: frames uint8 [B,H,W,3] (RGB) -> ToTensor -> Normalize -> F.interpolate(scale_factor, bilinear,
+    align_corners=True) -> logical [B,3,floor(H*s),floor(W*s)] float32 in NHWC memory.  mean / std float32 [3] on the
+    device.  Same bits as resize_bilinear_ac on the host-normalised frame."""
+    return _prepare_frames("rr_prepare_frames", 1, frames_u8, mean, std, scale_factor)
 
 
 def merge_buffers(nframes, k, device):
@@ -1872,17 +1876,7 @@ def merge_scales(rois, reg, scores, clses, frame_off, div, merged, count, scale=
 def prepare_frames_pair(frames_u8, mean, std, scale_factor):
     """rr_prepare_frames_pair: prepare_frames into logical [2B,3,oh,ow] (NHWC memory): images 0..B-1 are prepare_frames'
     output, images B..2B-1 the same pixels mirrored in x (`flip_img` after the resize: the bits of the plain image)."""
-    import math
-    _C.require_cuda(frames_u8, mean, std)
-    assert frames_u8.dtype == torch.uint8 and frames_u8.is_contiguous() and frames_u8.dim() == 4 and frames_u8.shape[3] == 3
-    assert mean.dtype == torch.float32 and std.dtype == torch.float32 and mean.numel() == 3 and std.numel() == 3
-    assert mean.is_contiguous() and std.is_contiguous()
-    b, h, w, _ = frames_u8.shape
-    oh, ow = int(math.floor(h * scale_factor)), int(math.floor(w * scale_factor))
-    out = empty_nhwc(2 * b, 3, oh, ow, frames_u8.device)
-    _C.check(_C.fn("rr_prepare_frames_pair")(_C.ptr(frames_u8), _C.ptr(mean), _C.ptr(std), _C.ptr(out), b, h, w, oh, ow,
-                                             _C.stream()), "rr_prepare_frames_pair")
-    return out
+    return _prepare_frames("rr_prepare_frames_pair", 2, frames_u8, mean, std, scale_factor)
 
 
 def merge_ctnet(rows, nframes, img_w, div, merged, count, pair=True, score_thr=0.01):

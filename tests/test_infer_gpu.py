@@ -93,6 +93,61 @@ def test_refine_kernels_bit_exact_vs_host_composition():
         np.testing.assert_array_equal(got.view(np.uint32), ref.view(np.uint32))
 
 
+def test_refine_boxes_carries_the_count_across_passes():
+    """rr_refine_boxes on segments around and beyond one pass of 256 rows: the rows kept by earlier passes offset the later
+    ones.  seg_len and the kept rows, in order, equal the oracle's generate_bbox -> `score > thr` -> xyxy bit for bit
+    (reg[:, 2:] = 0 keeps exp() out of the picture); a score equal to the threshold and a NaN score both leave."""
+    from oracle import ops as oops
+    from rrnet_amd import ops
+    rng = np.random.default_rng(21)
+    lengths = [0, 1, 63, 64, 65, 256, 257, 513]
+    thr = np.float32(0.01)
+    seg = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)
+    r = int(seg[-1])
+    xy = rng.uniform(0, 40, (r, 2)).astype(np.float32)
+    wh_ = rng.uniform(1, 12, (r, 2)).astype(np.float32)
+    seg_id = np.repeat(np.arange(len(lengths)), lengths).astype(np.float32)       # the oracle selects a segment as a frame
+    rois = np.concatenate([seg_id[:, None], xy, xy + wh_], 1)
+    scores = np.where(np.arange(r) % 2 == 0, rng.uniform(0.02, 1.0, r), rng.uniform(0.0, 0.009, r)).astype(np.float32)
+    scores[seg[7] + 300] = thr                       # in the second pass of the longest segment
+    scores[seg[7] + 302] = np.nan
+    clses = rng.integers(0, 10, r).astype(np.float32)
+    reg = rng.normal(0, 0.1, (r, 4)).astype(np.float32)
+    reg[:, 2:] = 0
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    b6, seg_len = ops.refine_boxes(T(rois), T(reg), T(scores), T(clses), T(seg), 4.0, float(thr))
+    b6, seg_len = b6.cpu().numpy(), seg_len.cpu().numpy()
+    outs = (None, None, None, torch.from_numpy(reg), torch.from_numpy(rois), torch.from_numpy(scores), torch.from_numpy(clses))
+    for s, n in enumerate(lengths):
+        ref = oops.generate_bbox(outs, s, 4)[1].numpy()
+        ref = ref[ref[:, 4] > thr]
+        ref[:, 2:4] = ref[:, 2:4] + ref[:, 0:2]
+        assert seg_len[s] == ref.shape[0], (s, seg_len[s], ref.shape[0])
+        np.testing.assert_array_equal(b6[seg[s]:seg[s] + seg_len[s]].view(np.uint32), ref.view(np.uint32))
+    assert seg_len[7] > 128 and not np.isnan(b6[seg[7]:seg[7] + seg_len[7], 4]).any()     # rows of all three passes stay
+
+
+def test_roi_spatial_order_is_the_stable_sort_by_band_and_column():
+    """rr_roi_spatial_order: per frame the RoIs ordered by (8-pixel row band of the centre, quarter-pixel x of the centre),
+    equal keys in input order; frame sizes around the network's powers of two and its LDS capacity (4096), beyond which a
+    frame keeps its order.  Coordinates are multiples of 0.25 (centres of 0.125): the key is exact in fp32."""
+    from rrnet_amd import ops
+    rng = np.random.default_rng(22)
+    counts = [0, 1, 2, 255, 256, 257, 4096, 4097]
+    fo = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+    r = int(fo[-1])
+    x1 = rng.integers(0, 800, r) * 0.25
+    y1 = rng.integers(0, 1600, r) * 0.25                                           # 50 bands, ~80 RoIs each: many equal keys
+    rois = np.stack([np.repeat(np.arange(len(counts)), counts), x1, y1, x1 + rng.integers(1, 200, r) * 0.25,
+                     y1 + rng.integers(1, 200, r) * 0.25], 1).astype(np.float32)
+    order = ops.roi_spatial_order(torch.from_numpy(rois).cuda(), torch.from_numpy(fo).cuda()).cpu().numpy()
+    cy, cx = 0.5 * (rois[:, 2] + rois[:, 4]), 0.5 * (rois[:, 1] + rois[:, 3])
+    key = (np.clip(cy * 0.125, 0, 65535).astype(np.uint32) << 16) | np.clip(cx * 4, 0, 65535).astype(np.uint32)
+    for f, n in enumerate(counts):
+        exp = np.arange(n) if n > 4096 else np.argsort(key[fo[f]:fo[f + 1]], kind='stable')
+        np.testing.assert_array_equal(order[fo[f]:fo[f + 1]], fo[f] + exp, err_msg="frame of %d RoIs" % n)
+
+
 def test_group_by_class_large_matches_stable_sort():
     from rrnet_amd import ops
     rng = np.random.default_rng(9)

@@ -193,6 +193,41 @@ def test_stage1_hard_nms_kernel_pinned_by_reference_on_integer_boxes(golden_dir)
         np.testing.assert_array_equal(got[:, :5], b[[list(order).index(k) for k in keep]][:, :5])
 
 
+def test_stage1_hard_nms_compacts_a_segment_longer_than_one_pass():
+    """rr_hard_nms_segments on a segment of 600 rows (the compaction runs three passes of 256 and carries the kept count
+    across them), an empty one and a one-row one: n_out and the kept rows, in order, equal a greedy restatement in numpy
+    float32 (plain IoU, `>`), bit for bit.  Integer boxes on a grid, every third a copy of the one before it: 400 stay."""
+    from rrnet_amd import ops
+    n, thr = 600, np.float32(0.7)
+    i = np.arange(n) - (np.arange(n) % 3 == 2)                  # row 3j+2 sits on row 3j+1
+    x1, y1 = 20.0 * (i % 30), 20.0 * (i // 30)
+    big = np.stack([x1, y1, x1 + 10, y1 + 12, np.linspace(0.99, 0.01, n), np.arange(n) % 10], 1).astype(np.float32)
+    one = np.array([[3, 4, 9, 11, 0.5, 2]], np.float32)
+    segs = [big, np.zeros((0, 6), np.float32), one]
+    seg_off = np.concatenate([[0], np.cumsum([s.shape[0] for s in segs])]).astype(np.int32)
+    rows = torch.from_numpy(np.concatenate(segs)).cuda()
+    n_out = ops.hard_nms_segments(rows, torch.from_numpy(seg_off).cuda(), n, float(thr), None).cpu().numpy()
+    rows = rows.cpu().numpy()
+
+    def greedy(b):
+        area = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
+        gone = np.zeros(b.shape[0], bool)
+        for a in range(b.shape[0]):
+            if gone[a]:
+                continue
+            w = np.maximum(np.minimum(b[a, 2], b[a + 1:, 2]) - np.maximum(b[a, 0], b[a + 1:, 0]), np.float32(0))
+            h = np.maximum(np.minimum(b[a, 3], b[a + 1:, 3]) - np.maximum(b[a, 1], b[a + 1:, 1]), np.float32(0))
+            inter = w * h
+            gone[a + 1:] |= inter / (area[a] + area[a + 1:] - inter) > thr
+        return b[~gone]
+
+    assert n_out.tolist() == [400, 0, 1]
+    for s, b in enumerate(segs):
+        ref = greedy(b)
+        assert n_out[s] == ref.shape[0], (s, n_out[s], ref.shape[0])
+        np.testing.assert_array_equal(rows[seg_off[s]:seg_off[s] + n_out[s]].view(np.uint32), ref.view(np.uint32))
+
+
 def test_ext_nms_batch_and_auto_evaluate(tmp_path):
     """utils/metrics: the batched per-file / per-class Soft-NMS equals the oracle's ext_nms file by file, bit for
     bit, and auto_evaluate_results == evaluating those results in memory."""
