@@ -56,10 +56,17 @@ _CTYPE = {"int": c_int, "float": c_float, "double": c_double, "size_t": c_size_t
 _SIGS = None
 
 
+class Signature(tuple):
+    """(restype, [argtypes]) of one entry point, plus `.pointees`: per parameter what a pointer points to ("float",
+    "unsigned short", "void", "float *", ...), "hipStream_t" for the stream, None for a number."""
+    pointees = ()
+
+
 def header_signatures():
     """Parses include/rrnet_hip.h (shipped next to the library as rrnet_amd/rrnet_hip.h when
-    installed, otherwise <repo>/include) -> {name: (restype, [argtypes])}.  The header is the
-    single source of truth for the ABI; pointers map to void*."""
+    installed, otherwise <repo>/include) -> {name: Signature = (restype, [argtypes])}.  The header is the
+    single source of truth for the ABI; pointers map to void* in argtypes, and the signature's `.pointees`
+    keeps what each one points to."""
     import re
     global _SIGS
     if _SIGS is not None:
@@ -71,16 +78,20 @@ def header_signatures():
     for m in re.finditer(r"(?m)^\s*(const\s+char\s*\*|int\s|size_t\s|void\s|double\s)\s*(rr_\w+|_nms)\s*\(([^;{]*?)\)\s*;", text):
         ret, name, args = m.group(1), m.group(2), m.group(3).strip()
         restype = ctypes.c_char_p if "char" in ret else _CTYPE[ret.strip()]
-        argtypes = []
+        argtypes, pointees = [], []
         if args and args != "void":
             for a in args.split(","):
                 a = a.strip()
                 if "*" in a:
                     argtypes.append(c_void_p)
+                    base = " ".join(re.sub(r"\b(const|__restrict__)\b", "", a[:a.index("*")]).split())
+                    pointees.append(base + " *" * (a.count("*") - 1))
                 else:
                     toks = a.replace("const", "").split()
                     argtypes.append(_CTYPE[toks[0]])
-        sigs[name] = (restype, argtypes)
+                    pointees.append("hipStream_t" if toks[0] == "hipStream_t" else None)
+        sigs[name] = Signature((restype, argtypes))
+        sigs[name].pointees = tuple(pointees)
     _SIGS = sigs
     return sigs
 
@@ -98,7 +109,70 @@ def fn(name, argtypes=None, restype=None):
     return f
 
 
+_NO_CPU = "rrnet_amd ops run on the MI355X only: got a %s tensor (no CPU fallback)"
+
+
 def require_cuda(*tensors):
     for t in tensors:
         if t is not None and not t.is_cuda:
-            raise RRNetHipError("rrnet_amd ops run on the MI355X only: got a %s tensor (no CPU fallback)" % t.device)
+            raise RRNetHipError(_NO_CPU % t.device)
+
+
+# What a tensor handed to a pointer parameter may hold, by the header's pointee: the dtypes the wrappers really pass, each of
+# the pointee's element size.  None: anything (a workspace); (): no tensor at all (rr_sum_n's array of pointers).
+POINTEE_DTYPES = {
+    "float": (torch.float32,), "double": (torch.float64,), "void": None, "float *": (),
+    "int": (torch.int32,), "unsigned": (torch.int32,),                    # (unsigned: the maxima's bit patterns)
+    "unsigned short": (torch.bfloat16, torch.float16),                    # bf16 images, the fp16 parts of a split filter
+    "unsigned char": (torch.uint8,), "signed char": (torch.int8,),
+    "long": (torch.int64,), "long long": (torch.int64,), "unsigned long long": (torch.int64,),
+}
+_NUMBER = object()
+_Tensor = torch.Tensor
+_COUNTS = ("_blocks", "_supported", "_supported_dil")       # int-returning entries whose value is a count, not a status
+_PLANS = {}
+
+
+def _plan(name):
+    """name -> (per caller argument the admitted dtypes | None | _NUMBER, stream appended?, host tensors allowed?,
+    the return value is a status?), from the header, built once per entry."""
+    sig = header_signatures().get(name)
+    if sig is None:
+        raise RRNetHipError("%s is not declared in include/rrnet_hip.h" % name)
+    kinds = sig.pointees
+    with_stream = bool(kinds) and kinds[-1] == "hipStream_t"
+    slots = tuple(_NUMBER if k is None else POINTEE_DTYPES[k] for k in (kinds[:-1] if with_stream else kinds))
+    plan = _PLANS[name] = (slots, with_stream, name.endswith("_host"),
+                           sig[0] is c_int and not name.endswith(_COUNTS) and name != "rr_abi_version")
+    return plan
+
+
+def call(name, *args):
+    """Calls entry point `name` of include/rrnet_hip.h: tensors go in as themselves and are checked against the header
+    (a device tensor of a dtype the pointee admits, only in a pointer slot; None is NULL), the current stream is appended
+    where the prototype ends in one, a failing status raises under the entry's own name.  Everything else (numbers,
+    ctypes pointers) passes through.  The tensors are this frame's arguments: they outlive the enqueue."""
+    slots, with_stream, host, status = _PLANS.get(name) or _plan(name)
+    if len(args) != len(slots):
+        raise RRNetHipError("%s takes %d arguments%s (include/rrnet_hip.h), got %d"
+                            % (name, len(slots), " and the stream" if with_stream else "", len(args)))
+    conv = list(args)
+    for i, a in enumerate(args):
+        kind = type(a)               # (numbers and None first: most arguments are, and the test is three pointer compares)
+        if kind is not int and kind is not float and a is not None and isinstance(a, _Tensor):
+            admits = slots[i]
+            if admits is _NUMBER:
+                raise RRNetHipError("%s: argument %d is a tensor, include/rrnet_hip.h declares a number" % (name, i))
+            if not (a.is_cuda or host):
+                raise RRNetHipError(_NO_CPU % a.device)
+            if admits is not None and a.dtype not in admits:
+                raise RRNetHipError("%s: argument %d is a %s tensor, include/rrnet_hip.h declares %s *"
+                                    % (name, i, a.dtype, header_signatures()[name].pointees[i]))
+            conv[i] = c_void_p(a.data_ptr())
+    if with_stream:
+        conv.append(stream())                       # read now, never cached: the weight gradients run on side streams
+    rc = fn(name)(*conv)
+    if not status:
+        return rc
+    if rc != 0:
+        raise RRNetHipError("%s failed (%d): %s" % (name, rc, lib().rr_last_error().decode()))

@@ -11,8 +11,6 @@ import torch
 
 from rrnet_amd import _C
 
-_P = _C.c_void_p
-
 
 def soft_nms_segments(boxes, seg_off, max_seg, sigma=0.5, Nt=0.3, threshold=0.001, method=1, seg_len=None,
                       check=True):
@@ -22,8 +20,7 @@ def soft_nms_segments(boxes, seg_off, max_seg, sigma=0.5, Nt=0.3, threshold=0.00
     the reference's order.  Raises ZeroDivisionError where the reference would (`check=False` skips the
     host read of the flag and returns (n_out, err) for a caller that synchronises later)."""
     _C.require_cuda(boxes, seg_off)
-    assert boxes.dtype == torch.float32 and boxes.is_contiguous() and boxes.dim() == 2
-    assert seg_off.dtype == torch.int32
+    assert boxes.is_contiguous() and boxes.dim() == 2
     nseg = seg_off.numel() - 1
     n_out = torch.zeros(max(nseg, 0), dtype=torch.int32, device=boxes.device)
     if nseg <= 0:
@@ -31,17 +28,15 @@ def soft_nms_segments(boxes, seg_off, max_seg, sigma=0.5, Nt=0.3, threshold=0.00
     if int(method) == 2 and float(np.float32(sigma)) == 0.0:
         raise ZeroDivisionError("float division")
     err = torch.zeros(1, dtype=torch.int32, device=boxes.device)
-    f_ws = _C.fn("rr_soft_nms_workspace_bytes")
-    nbytes = f_ws(boxes.size(0), int(max_seg))
+    nbytes = _C.call("rr_soft_nms_workspace_bytes", boxes.size(0), int(max_seg))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=boxes.device) if nbytes else None
     tail = (int(max_seg), boxes.size(1), float(np.float32(sigma)), float(np.float32(Nt)), float(np.float32(threshold)),
-            int(method), _C.ptr(n_out), _C.ptr(err), _C.ptr(ws), _C.stream())
+            int(method), n_out, err, ws)
     if seg_len is None:
-        _C.check(_C.fn("rr_soft_nms_segments")(_C.ptr(boxes), _C.ptr(seg_off), nseg, *tail), "rr_soft_nms_segments")
+        _C.call("rr_soft_nms_segments", boxes, seg_off, nseg, *tail)
     else:
-        assert seg_len.dtype == torch.int32 and seg_len.numel() == nseg
-        _C.check(_C.fn("rr_soft_nms_ragged")(_C.ptr(boxes), _C.ptr(seg_off), _C.ptr(seg_len), nseg, *tail),
-                 "rr_soft_nms_ragged")
+        assert seg_len.numel() == nseg
+        _C.call("rr_soft_nms_ragged", boxes, seg_off, seg_len, nseg, *tail)
     if not check:
         return n_out, err
     if int(err.item()) != 0:
@@ -78,11 +73,10 @@ def _nms_device(dets, thresh, inclusive):
     order = work[:, 4].argsort()[::-1]                      # the reference's own ordering (gpu_nms.pyx:25-28)
     dev = torch.device("cuda", torch.cuda.current_device())
     d = torch.from_numpy(work[order]).to(dev)
-    ws = torch.empty(_C.fn("rr_nms_workspace_bytes")(n), dtype=torch.uint8, device=dev)
+    ws = torch.empty(_C.call("rr_nms_workspace_bytes", n), dtype=torch.uint8, device=dev)
     keep = torch.empty(n, dtype=torch.int32, device=dev)
     num = torch.zeros(1, dtype=torch.int32, device=dev)
-    _C.check(_C.fn("rr_nms_sorted")(_C.ptr(d), n, 5, float(np.float32(thresh)), int(inclusive), _C.ptr(ws), _C.ptr(keep),
-                                    _C.ptr(num), _C.stream()), "rr_nms_sorted")
+    _C.call("rr_nms_sorted", d, n, 5, float(np.float32(thresh)), int(inclusive), ws, keep, num)
     k = int(num.item())
     return list(order[keep[:k].cpu().numpy()])
 

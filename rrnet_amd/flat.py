@@ -119,13 +119,10 @@ class FlatParams:
             return
         from rrnet_amd import _C
         if self.w16_flat is not None:
-            _C.check(_C.fn("rr_weight_flip_transpose_batch_bf16")(_C.ptr(self.flat), _C.ptr(self.wt_flat), _C.ptr(self.w16_flat),
-                                                                  _C.ptr(self.wt16_flat), _C.ptr(self._wt_table),
-                                                                  self._wt_table.shape[0], _C.stream()),
-                     "rr_weight_flip_transpose_batch_bf16")
+            _C.call("rr_weight_flip_transpose_batch_bf16", self.flat, self.wt_flat, self.w16_flat, self.wt16_flat, self._wt_table,
+                    self._wt_table.shape[0])
         else:
-            _C.check(_C.fn("rr_weight_flip_transpose_batch")(_C.ptr(self.flat), _C.ptr(self.wt_flat), _C.ptr(self._wt_table),
-                                                             self._wt_table.shape[0], _C.stream()), "rr_weight_flip_transpose_batch")
+            _C.call("rr_weight_flip_transpose_batch", self.flat, self.wt_flat, self._wt_table, self._wt_table.shape[0])
         self._wt_version = self.flat._version
         self._wt_pver = {id(p): p._version for p in self.params if p.dim() == 4}
 

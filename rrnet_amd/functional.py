@@ -390,8 +390,7 @@ class _ConvBnSyncMulti(torch.autograd.Function):
         off = 0
         for i, ((y, slab), k) in enumerate(zip(ys, ks)):
             mt = slab.numel() // (2 * k)
-            ops._C.check(ops._C.fn("rr_bn_reduce_slab_count")(ops._C.ptr(slab), mt, k, ops._C.ptr(packed[off:off + 2 * k]), counts[i],
-                                                              ops._C.ptr(packed[tot - L + i:]), ops._C.stream()), "rr_bn_reduce_slab_count")
+            ops._C.call("rr_bn_reduce_slab_count", slab, mt, k, packed[off:off + 2 * k], counts[i], packed[tot - L + i:])
             off += 2 * k
         dptrace.all_reduce(packed, None, "default", "syncbn_fwd x%d" % L)
         cnt_devs = []
@@ -446,10 +445,7 @@ class _ConvBnSyncMulti(torch.autograd.Function):
             if fused is not None:
                 packed[off:off + 2 * k].copy_(fused[:2 * k])
             else:
-                ops._C.check(ops._C.fn("rr_bn_bwd_reduce")(ops._C.ptr(dz), ops._C.ptr(None), ops._C.ptr(y), ops._C.ptr(mean),
-                                                           ops._C.ptr(invstd), ops._C.ptr(msc), ops._C.ptr(msh),
-                                                           ops._C.ptr(packed[off:off + 2 * k]), n * h * w, c, 1, ops._C.stream()),
-                             "rr_bn_bwd_reduce")
+                ops._C.call("rr_bn_bwd_reduce", dz, None, y, mean, invstd, msc, msh, packed[off:off + 2 * k], n * h * w, c, 1)
             # gradients of gamma / beta come from the LOCAL sums (averaged later like any gradient)
             gp, bp = params[3 * i + 1], params[3 * i + 2]
             dg_t, db_t = _grad_target(gp), _grad_target(bp)

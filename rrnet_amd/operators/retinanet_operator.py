@@ -157,11 +157,10 @@ class RetinaNetOperator(BaseOperator):
         xyxy = ordered.clone()
         xyxy[:, 2:4] += xyxy[:, 0:2]                        # :252-253
         dev = rows6.device
-        ws = torch.empty(_C.fn("rr_nms_workspace_bytes")(n), dtype=torch.uint8, device=dev)
+        ws = torch.empty(_C.call("rr_nms_workspace_bytes", n), dtype=torch.uint8, device=dev)
         keep = torch.empty(n, dtype=torch.int32, device=dev)
         num = torch.zeros(1, dtype=torch.int32, device=dev)
-        _C.check(_C.fn("rr_nms_sorted")(_C.ptr(xyxy), n, 6, float(np.float32(NMS_THRESH)), 0, _C.ptr(ws), _C.ptr(keep),
-                                        _C.ptr(num), _C.stream()), "rr_nms_sorted")
+        _C.call("rr_nms_sorted", xyxy, n, 6, float(np.float32(NMS_THRESH)), 0, ws, keep, num)
         return ordered[keep[:int(num.item())].long()]
 
     @staticmethod

@@ -10,7 +10,6 @@ import torch
 
 from rrnet_amd import _C
 
-_P, _I, _F = _C.c_void_p, _C.c_int, _C.c_float
 CL = torch.channels_last
 
 
@@ -84,10 +83,11 @@ TIMER = None
 SYNC_WAIT_S = 0.0      # host time spent blocked in the RoI-count read (bench.py separates it from the enqueue time)
 
 
-def _timed(name, flops, fn, detail=None, nbytes=0.0):
+def _launch(key, flops, entry, args, detail=None, nbytes=0.0):
+    """Entry point `entry` on `args` (_C.call), under the timer key `key` when a timer is on: it is reached inside the timer's fn()."""
     if TIMER is None:
-        return fn()
-    return TIMER.launch(name, flops, fn, detail, nbytes)
+        return _C.call(entry, *args)
+    return TIMER.launch(key, flops, lambda: _C.call(entry, *args), detail, nbytes)
 
 
 _SMALL_TILES = 16
@@ -141,7 +141,7 @@ def f32_of(t):
     img = image_of(t)
     out = torch.empty_like(img, dtype=torch.float32)
     assert out.stride() == img.stride()
-    _C.check(_C.fn("rr_from_bf16")(_C.ptr(img), _C.ptr(out), img.numel(), _C.stream()), "rr_from_bf16")
+    _C.call("rr_from_bf16", img, out, img.numel())
     return out
 
 
@@ -256,7 +256,7 @@ def split_filter(w, amax_word, pixels, flat=None):
         return None
     src = w if flat is None else flat
     out = torch.empty(2 * src.numel(), dtype=torch.float16, device=src.device)
-    _C.check(_C.fn("rr_weight_split_f16")(_C.ptr(src), src.numel(), _C.ptr(amax_word), _C.ptr(out), _C.stream()), "rr_weight_split_f16")
+    _C.call("rr_weight_split_f16", src, src.numel(), amax_word, out)
     return out
 
 
@@ -419,10 +419,10 @@ def bf16_of(t):
     img = b16_side.now(t)
     if img is not None:
         return img
-    assert t.dtype == torch.float32 and t.numel() % 4 == 0
+    assert t.numel() % 4 == 0
     img = torch.empty_like(t, dtype=torch.bfloat16)
     assert img.stride() == t.stride()
-    _C.check(_C.fn("rr_to_bf16")(_C.ptr(t), _C.ptr(img), t.numel(), _C.stream()), "rr_to_bf16")
+    _C.call("rr_to_bf16", t, img, t.numel())
     try:
         b16_side.attach(t, img)
     except AttributeError:
@@ -459,21 +459,26 @@ def wgrad16_takes(x_shape, dy_shape, w_shape, stride):
     """True when conv_wgrad(x, dy, dw, stride, ...) goes to rr_conv16_wgrad (the explicit_out form never does)."""
     k, c, r, s = w_shape
     npix, xn = dy_shape[0] * dy_shape[2] * dy_shape[3], x_shape[0] * x_shape[1] * x_shape[2] * x_shape[3]
-    return bool(_CONV16 and _mode() == MATH_BF16 and npix >= _CONV16_MIN_PIXELS and _C.fn("rr_conv16_wgrad_supported")(c, k, r, s, stride)
+    return bool(_CONV16 and _mode() == MATH_BF16 and npix >= _CONV16_MIN_PIXELS and _C.call("rr_conv16_wgrad_supported", c, k, r, s, stride)
                 and max(xn, npix * k) * 2 < (1 << 31))
 
 
 def conv16_ok(c, k, r, s, stride, pixels, *tensors):
     """-> True when a forward-kernel launch of this shape goes to csrc/conv16.hip (bf16 mode only)."""
     return bool(_CONV16 and _mode() == MATH_BF16 and pixels >= _CONV16_MIN_PIXELS and all(t is None or t.is_cuda for t in tensors)
-                and _C.fn("rr_conv16_supported")(c, k, r, s, stride) and all(t is None or t.numel() * 2 < (1 << 31) for t in tensors))
+                and _C.call("rr_conv16_supported", c, k, r, s, stride) and all(t is None or t.numel() * 2 < (1 << 31) for t in tensors))
+
+
+def _amax_word(device):
+    """A zeroed device word for a maximum's bit pattern: 8 zeroed bytes as int32 [2]; the kernels read and write the first."""
+    return _ZEROS.take(1, device).view(torch.int32)
 
 
 def _absmax_word(t):
-    word = _ZEROS.take(1, t.device)                   # 8 zeroed bytes; the kernels read the first 4
+    word = _amax_word(t.device)
     n = t.numel()
-    assert n % 4 == 0 and t.dtype == torch.float32
-    _C.check(_C.fn("rr_absmax_bits")(_C.ptr(t), n, _C.ptr(word), _C.stream()), "rr_absmax_bits")
+    assert n % 4 == 0
+    _C.call("rr_absmax_bits", t, n, word)
     return word
 
 
@@ -485,7 +490,7 @@ def amax_of(t):
     word = amax_side.now(t)
     if word is not None:
         if _AMAX_CHECK:
-            fresh = int(_absmax_word(t).view(torch.int32)[0].item())
+            fresh = int(_absmax_word(t)[0].item())
             kept = int(word.view(torch.int32)[0].item())
             if fresh != kept:
                 raise RuntimeError("ops.amax_of: stale remembered maximum on a tensor of shape %s: remembered bits 0x%08x, "
@@ -505,14 +510,14 @@ AMAX_CHECKED = [0]       # remembered maxima verified under RR_AMAX_CHECK=1 (the
 
 
 def _math_call(mode, a, b, filter16=None, filter_split=None, takes_filter=False):
-    """-> (entry-point suffix, timer tag, trailing arguments) of a convolution entry point under arithmetic `mode`: fp32 ("", "", stream),
-    bf16 ("_bf16", "+bf16", stream), f16x3 ("_f16x3", "+f16x3", the maxima of the operands a and b, stream).  takes_filter (rr_conv_fprop*,
-    rr_conv_dgrad_s1{,_bnsum}*; not _relubias, _s2, wgrad): in front of the stream the filter's cached bf16 copy / fp16 split, or NULL."""
+    """-> (entry-point suffix, timer tag, trailing arguments) of a convolution entry point under arithmetic `mode`: fp32 ("", "", ()),
+    bf16 ("_bf16", "+bf16", ()), f16x3 ("_f16x3", "+f16x3", the maxima of the operands a and b).  takes_filter (rr_conv_fprop*,
+    rr_conv_dgrad_s1{,_bnsum}*; not _relubias, _s2, wgrad): behind them the filter's cached bf16 copy / fp16 split, or None (NULL)."""
     sfx = ("", "_bf16", "_f16x3")[mode]
-    tail = (_C.ptr(amax_of(a)), _C.ptr(amax_of(b))) if mode == MATH_F16X3 else ()
+    tail = (amax_of(a), amax_of(b)) if mode == MATH_F16X3 else ()
     if takes_filter and mode != MATH_F32:
-        tail += (_C.ptr(filter_split if mode == MATH_F16X3 else filter16),)
-    return sfx, sfx.replace("_", "+"), tail + (_C.stream(),)
+        tail += (filter_split if mode == MATH_F16X3 else filter16,)
+    return sfx, sfx.replace("_", "+"), tail
 
 
 def conv_fprop(x, w, bias=None, stride=1, pad=(0, 0), relu=False, want_stats=False, algo_kg=None, w16=None, w_split=None,
@@ -521,7 +526,6 @@ def conv_fprop(x, w, bias=None, stride=1, pad=(0, 0), relu=False, want_stats=Fal
     and, if want_stats, the per-block BatchNorm partial-sum slab (see rr_conv_fprop).
     algo_kg: the useful reduction length when the operands carry zero padding (timer FLOPs stay algorithmic)."""
     _C.require_cuda(x, w, bias)
-    assert x.dtype == torch.float32 and w.dtype == torch.float32
     n, c, h, wd = x.shape
     k, c2, r, s = w.shape
     assert c == c2
@@ -545,17 +549,14 @@ def conv_fprop(x, w, bias=None, stride=1, pad=(0, 0), relu=False, want_stats=Fal
         if w16 is None:
             w16 = bf16_of(w)
         if want_stats:
-            slab = torch.empty(_C.fn("rr_conv16_stat_slab_bytes")(n, p, q, k) // 8, dtype=torch.float64, device=x.device)
+            slab = torch.empty(_C.call("rr_conv16_stat_slab_bytes", n, p, q, k) // 8, dtype=torch.float64, device=x.device)
         flops = 2.0 * n * p * q * k * (c * r * s if algo_kg is None else algo_kg)
-        _C.check(_timed("conv16_fprop", flops,
-                        lambda: _C.fn("rr_conv16_fprop")(_C.ptr(x16), _C.ptr(w16), _C.ptr(bias), _C.ptr(None if y16 is not None else y),
-                                                         _C.ptr(y16), _C.ptr(slab), n, h, wd, c, k, r, s, stride, pad[0], pad[1],
-                                                         int(relu), _C.stream()),
-                        (n, h, wd, c, k, r, s, stride), 2.0 * (x.numel() + w.numel()) + (2.0 if y16 is not None else 4.0) * y.numel()),
-                 "rr_conv16_fprop")
+        _launch("conv16_fprop", flops, "rr_conv16_fprop",
+                (x16, w16, bias, None if y16 is not None else y, y16, slab, n, h, wd, c, k, r, s, stride, pad[0], pad[1], int(relu)),
+                (n, h, wd, c, k, r, s, stride), 2.0 * (x.numel() + w.numel()) + (2.0 if y16 is not None else 4.0) * y.numel())
         return (y, slab) if want_stats else y
     if want_stats:
-        nbytes = _C.fn("rr_conv_stat_slab_bytes")(n, p, q, k)
+        nbytes = _C.call("rr_conv_stat_slab_bytes", n, p, q, k)
         slab = torch.empty(nbytes // 8, dtype=torch.float64, device=x.device)
     bf = _bf16_ok(c, 4 if _mode() != MATH_F16X3 else k, r, s, x, w, y, pixels=n * p * q)
     flops = 2.0 * n * p * q * k * (c * r * s if algo_kg is None else algo_kg)
@@ -566,11 +567,9 @@ def conv_fprop(x, w, bias=None, stride=1, pad=(0, 0), relu=False, want_stats=Fal
         # data gradients read a filter of zeros / garbage — non-finite gradients, and a step that ran 10 % FASTER
         w_split = split_filter(w, amax_of(w), n * p * q)
     sfx, tag, tail = _math_call(bf, x, w, w16, w_split, takes_filter=True)
-    f = _C.fn("rr_conv_fprop" + sfx)
-    _C.check(_timed(_igemm_name("fprop", k, c % 4 != 0, n * p * q) + tag, flops,
-                    lambda: f(_C.ptr(x), _C.ptr(w), _C.ptr(bias), _C.ptr(y), _C.ptr(slab), n, h, wd, c, k, r, s,
-                              stride, pad[0], pad[1], int(relu), *tail),
-                    (n, h, wd, c, k, r, s, stride), 4.0 * (x.numel() + y.numel() + w.numel())), "rr_conv_fprop")
+    _launch(_igemm_name("fprop", k, c % 4 != 0, n * p * q) + tag, flops, "rr_conv_fprop" + sfx,
+            (x, w, bias, y, slab, n, h, wd, c, k, r, s, stride, pad[0], pad[1], int(relu)) + tail,
+            (n, h, wd, c, k, r, s, stride), 4.0 * (x.numel() + y.numel() + w.numel()))
     return (y, slab) if want_stats else y
 
 
@@ -589,8 +588,7 @@ def conv_fprop_packed(x, w, stride, pad, want_stats=False):
     kp = (kg + 31) // 32 * 32
     p, q = out_hw(h, wd, r, s, stride, pad[0], pad[1])
     xp = empty_nhwc(n, kp, p, q, x.device)
-    _C.check(_C.fn("rr_conv_pack_taps")(_C.ptr(x), _C.ptr(xp), n, h, wd, c, r, s, stride, pad[0], pad[1], kp, _C.stream()),
-             "rr_conv_pack_taps")
+    _C.call("rr_conv_pack_taps", x, xp, n, h, wd, c, r, s, stride, pad[0], pad[1], kp)
     wp = torch.zeros((k, kp), dtype=torch.float32, device=x.device)
     wp[:, :kg] = w.permute(0, 2, 3, 1).reshape(k, kg)                       # OHWI memory = [k][(r,s,c)]
     out = conv_fprop(xp, wp.view(k, kp, 1, 1), None, 1, (0, 0), False,
@@ -689,7 +687,7 @@ def dgrad_route(dy_shape, w_shape, x_shape, stride, pad, link=None, link_b16=Fal
     inside, fits32 = pad[0] < r and pad[1] < s, dx_elems * 4 < (1 << 31)
     # csrc/conv16.hip (bf16 mode): both operands as bf16 tensors below 2 GiB, maps of at least _CONV16_MIN_PIXELS output pixels
     conv16 = _CONV16 and _mode() == MATH_BF16 and device and max(dy_elems, dx_elems) * 2 < (1 << 31)
-    s1_16 = bool(stride == 1 and inside and conv16 and npx >= _CONV16_MIN_PIXELS and _C.fn("rr_conv16_supported")(k, c, r, s, 1))
+    s1_16 = bool(stride == 1 and inside and conv16 and npx >= _CONV16_MIN_PIXELS and _C.call("rr_conv16_supported", k, c, r, s, 1))
 
     def math(kk, pixels):           # the arithmetic of a csrc/conv_bf16.hip launch on a dy of kk channels
         return _bf16_ok(kk, c, r, s, pixels=pixels) if max(dy_elems // k * kk, dx_elems) * 4 < (1 << 31) else 0
@@ -736,10 +734,10 @@ def _flipped_filter(w, wt, wt16, want16):
     unless the caller brought them (FlatParams.wt_view / w16_views)."""
     if wt is None and not (want16 and wt16 is not None):
         wt = torch.empty(w.numel(), dtype=torch.float32, device=w.device)
-        _C.check(_C.fn("rr_weight_flip_transpose")(_C.ptr(w), _C.ptr(wt), *w.shape, _C.stream()), "rr_weight_flip_transpose")
+        _C.call("rr_weight_flip_transpose", w, wt, *w.shape)
     if want16 and wt16 is None:
         wt16 = torch.empty(wt.numel(), dtype=torch.bfloat16, device=w.device)
-        _C.check(_C.fn("rr_to_bf16")(_C.ptr(wt), _C.ptr(wt16), wt.numel(), _C.stream()), "rr_to_bf16")
+        _C.call("rr_to_bf16", wt, wt16, wt.numel())
     return wt, wt16
 
 
@@ -753,13 +751,10 @@ def _dgrad_conv16_s1(dy, w, out, geo, flops, wt, wt16, link=None, z=None):
     dy16 = bf16_of(dy)
     wt16 = _flipped_filter(w, wt, wt16, True)[1]
     if link is None:
-        _C.check(_timed("conv16_dgrad_s1", flops,
-                        lambda: _C.fn("rr_conv16_dgrad_s1")(_C.ptr(dy16), _C.ptr(wt16), _C.ptr(out), None, *geo, _C.stream()), geo[:7] + (1,),
-                        2.0 * (dy.numel() + w.numel()) + 4.0 * out.numel() * (2 if geo[9] else 1)), "rr_conv16_dgrad_s1")
+        _launch("conv16_dgrad_s1", flops, "rr_conv16_dgrad_s1", (dy16, wt16, out, None) + geo, geo[:7] + (1,),
+                2.0 * (dy.numel() + w.numel()) + 4.0 * out.numel() * (2 if geo[9] else 1))
         return
-    _C.check(_timed("conv16_dgrad_s1+relumask", flops,
-                    lambda: _C.fn("rr_conv16_dgrad_s1_relumask")(_C.ptr(dy16), _C.ptr(wt16), _C.ptr(out), *geo, _C.ptr(z), _C.stream()),
-                    geo[:7] + (1,)), "rr_conv16_dgrad_s1_relumask")
+    _launch("conv16_dgrad_s1+relumask", flops, "rr_conv16_dgrad_s1_relumask", (dy16, wt16, out) + geo + (z,), geo[:7] + (1,))
     link.sums, link.dz = _ZEROS.take(2, dy.device), out          # (sums: the "done" marker _ReLU.backward looks for)
 
 
@@ -772,24 +767,21 @@ def _dgrad_relubias(dy, w, out, geo, flops, bf, link, z, wt, head):
     if head:
         want16 = image_wanted(c, n * h * wd, dy.device, 256)
         out16 = torch.empty_like(out, dtype=torch.bfloat16) if want16 else None
-        _C.check(_C.fn("rr_head_dgrad_relubias")(_C.ptr(dy), _C.ptr(w), _C.ptr(out), _C.ptr(out16), _C.ptr(z), _C.ptr(link.sums),
-                                                 n * h * wd, c, k, geo[9], _C.stream()), "rr_head_dgrad_relubias")
+        _C.call("rr_head_dgrad_relubias", dy, w, out, out16, z, link.sums, n * h * wd, c, k, geo[9])
         if want16:
             b16_side.attach(out, out16)
         return
     kp = (k + 3) // 4 * 4
     if kp != k:
         dyp, wp, wt = empty_nhwc(dy.shape[0], kp, dy.shape[2], dy.shape[3], dy.device), zeros_nhwc(kp, c, r, s, dy.device), None
-        _C.check(_C.fn("rr_pad_channels")(_C.ptr(dy), _C.ptr(dyp), dy.shape[0] * dy.shape[2] * dy.shape[3], k, kp, _C.stream()), "rr_pad_channels")
+        _C.call("rr_pad_channels", dy, dyp, dy.shape[0] * dy.shape[2] * dy.shape[3], k, kp)
         wp[:k] = w
         dy, w = dyp, wp
     wt = _flipped_filter(w, wt, None, False)[0]
-    slab = torch.empty(_C.fn("rr_conv_stat_slab_bytes")(n, h, wd, c) // 8, dtype=torch.float64, device=dy.device)
+    slab = torch.empty(_C.call("rr_conv_stat_slab_bytes", n, h, wd, c) // 8, dtype=torch.float64, device=dy.device)
     sfx, tag, tail = _math_call(bf, dy, w)
-    f = _C.fn("rr_conv_dgrad_s1_relubias" + sfx)
-    _C.check(_timed(_igemm_name("fprop", c, False, n * h * wd) + "+relubias" + tag, flops,
-                    lambda: f(_C.ptr(dy), _C.ptr(wt), _C.ptr(out), n, h, wd, c, kp, *geo[5:], _C.ptr(z), _C.ptr(slab), _C.ptr(link.sums), *tail),
-                    geo[:7] + (1,)), "rr_conv_dgrad_s1_relubias")
+    _launch(_igemm_name("fprop", c, False, n * h * wd) + "+relubias" + tag, flops, "rr_conv_dgrad_s1_relubias" + sfx,
+            (dy, wt, out, n, h, wd, c, kp) + geo[5:] + (z, slab, link.sums) + tail, geo[:7] + (1,))
 
 
 def _dgrad_fprop(dy, w, out, geo, flops, bf, wt, wt16, wt_split, link=None, z=None):
@@ -803,13 +795,11 @@ def _dgrad_fprop(dy, w, out, geo, flops, bf, wt, wt16, wt_split, link=None, z=No
     sfx = ("_bnsum" if link is not None else "") + sfx
     name = _igemm_name("fprop", c, False, n * h * wd) + ("+bnsum" if link is not None else "") + tag
     if link is not None:
-        slab = torch.empty(_C.fn("rr_conv_stat_slab_bytes")(n, h, wd, c) // 8, dtype=torch.float64, device=dy.device)
+        slab = torch.empty(_C.call("rr_conv_stat_slab_bytes", n, h, wd, c) // 8, dtype=torch.float64, device=dy.device)
         link.sums, link.dz = _ZEROS.take(2 * c, dy.device), out
-        tail = (_C.ptr(link.y), _C.ptr(z if link.use_z else None), _C.ptr(link.mean), _C.ptr(link.invstd), _C.ptr(link.msc), _C.ptr(link.msh),
-                _C.ptr(slab), _C.ptr(link.sums)) + tail
-    f = _C.fn("rr_conv_dgrad_s1" + sfx)
-    _C.check(_timed(name, flops, lambda: f(_C.ptr(dy), _C.ptr(wt), _C.ptr(out), *geo, *tail), geo[:7] + (1,),
-                    4.0 * (dy.numel() + out.numel() * ((2 if geo[9] else 1) + (link is not None)) + w.numel())), "rr_conv_dgrad_s1" + sfx)
+        tail = (link.y, z if link.use_z else None, link.mean, link.invstd, link.msc, link.msh, slab, link.sums) + tail
+    _launch(name, flops, "rr_conv_dgrad_s1" + sfx, (dy, wt, out) + geo + tail, geo[:7] + (1,),
+            4.0 * (dy.numel() + out.numel() * ((2 if geo[9] else 1) + (link is not None)) + w.numel()))
 
 
 def _dgrad_s2(dy, w, out, geo, flops, bf, conv16):
@@ -817,16 +807,14 @@ def _dgrad_s2(dy, w, out, geo, flops, bf, conv16):
     src = bf16_of(dy) if conv16 else dy
     wsub = torch.empty(w.numel(), dtype=torch.bfloat16 if conv16 else torch.float32, device=dy.device)
     sfx, tag, tail = _math_call(bf, dy, w)             # (bf is never MATH_F32 here, and MATH_BF16 under conv16: dgrad_route)
-    f = _C.fn("rr_conv16_dgrad_s2" if conv16 else "rr_conv_dgrad_s2" + sfx)
-    _C.check(_timed("conv16_dgrad_s2" if conv16 else "conv_dgrad_s2" + tag, flops,
-                    lambda: f(_C.ptr(src), _C.ptr(w), _C.ptr(out), *geo, _C.ptr(wsub), *tail), geo[:7] + (2,)), "rr_conv_dgrad_s2")
+    _launch("conv16_dgrad_s2" if conv16 else "conv_dgrad_s2" + tag, flops, "rr_conv16_dgrad_s2" if conv16 else "rr_conv_dgrad_s2" + sfx,
+            (src, w, out) + geo + (wsub,) + tail, geo[:7] + (2,))
 
 
 def _dgrad_fp32(dy, w, out, geo, flops, stride):
     n, h, wd, c, k = geo[:5]
-    _C.check(_timed(_igemm_name("dgrad", c, (k % 4 != 0) or (c % 4 != 0), n * h * wd, stride), flops,
-                    lambda: _C.fn("rr_conv_dgrad")(_C.ptr(dy), _C.ptr(w), _C.ptr(out), *geo[:7], stride, *geo[7:], _C.stream()),
-                    geo[:7] + (stride,)), "rr_conv_dgrad")
+    _launch(_igemm_name("dgrad", c, (k % 4 != 0) or (c % 4 != 0), n * h * wd, stride), flops, "rr_conv_dgrad",
+            (dy, w, out) + geo[:7] + (stride,) + geo[7:], geo[:7] + (stride,))
 
 
 def conv_dgrad(dy, w, x_shape, stride=1, pad=(0, 0), out=None, accumulate=False, bnsum=None, bnsum_z=None, wt=None, wt16=None,
@@ -878,16 +866,15 @@ def conv_wgrad(x, dy, dw, stride=1, pad=(0, 0), explicit_out=False, algo_c=None)
     flops = 2.0 * dy.shape[0] * dy.shape[2] * dy.shape[3] * k * (c * r * s if algo_c is None else algo_c)
     if wgrad16_takes(x.shape, dy.shape, dw.shape, stride) and not explicit_out:
         x16, dy16 = bf16_of(x), bf16_of(dy)
-        _C.check(_timed("conv16_wgrad", flops, lambda: _C.fn("rr_conv16_wgrad")(_C.ptr(x16), _C.ptr(dy16), _C.ptr(dw), n, h, wd, c, k, r, s, stride,
-                                                                                 pad[0], pad[1], _C.stream()), (n, h, wd, c, k, r, s, stride)), "rr_conv16_wgrad")
+        _launch("conv16_wgrad", flops, "rr_conv16_wgrad", (x16, dy16, dw, n, h, wd, c, k, r, s, stride, pad[0], pad[1]),
+                (n, h, wd, c, k, r, s, stride))
         return dw
     x, dy = f32_of(x), f32_of(dy)            # (bf16-only operands in front of a layer the conv16 weight gradient does not take)
     bf = _bf16_ok(c, k, r, s, x, dy, pixels=dy.shape[0] * dy.shape[2] * dy.shape[3]) if wgrad_16bit_shape(c, k, r, s) else 0
     sfx, tag, wtail = _math_call(bf, x, dy)
-    f = _C.fn("rr_conv_wgrad" + sfx)
-    _C.check(_timed("conv_wgrad<BN=%d>%s" % (128 if c > 32 else 32, tag), flops,
-                    lambda: f(_C.ptr(x), _C.ptr(dy), _C.ptr(dw), n, h, wd, c, k, r, s, stride, pad[0], pad[1],
-                              *((dy.shape[2], dy.shape[3]) if explicit_out else (0, 0)), *wtail), (n, h, wd, c, k, r, s, stride)), "rr_conv_wgrad")
+    _launch("conv_wgrad<BN=%d>%s" % (128 if c > 32 else 32, tag), flops, "rr_conv_wgrad" + sfx,
+            (x, dy, dw, n, h, wd, c, k, r, s, stride, pad[0], pad[1]) + ((dy.shape[2], dy.shape[3]) if explicit_out else (0, 0)) + wtail,
+            (n, h, wd, c, k, r, s, stride))
     return dw
 
 
@@ -934,10 +921,9 @@ def bn_reduce_slab(slab, c, extra=0, count=None):
     mtiles = slab.numel() // (2 * c)
     if count is not None:
         assert extra >= 1
-        _C.check(_C.fn("rr_bn_reduce_slab_count")(_C.ptr(slab), mtiles, c, _C.ptr(sums), float(count), _C.ptr(sums[2 * c:]), _C.stream()),
-                 "rr_bn_reduce_slab_count")
+        _C.call("rr_bn_reduce_slab_count", slab, mtiles, c, sums, float(count), sums[2 * c:])
         return sums
-    _C.check(_C.fn("rr_bn_reduce_slab")(_C.ptr(slab), mtiles, c, _C.ptr(sums), _C.stream()), "rr_bn_reduce_slab")
+    _C.call("rr_bn_reduce_slab", slab, mtiles, c, sums)
     return sums
 
 
@@ -949,19 +935,16 @@ def bn_finalize_sync(sums, count_slot, gamma, beta, running_mean, running_var, m
     buf = _f32(4 * c, gamma.device)
     mean, invstd, scale, shift = buf[0:c], buf[c:2 * c], buf[2 * c:3 * c], buf[3 * c:4 * c]
     cnt = torch.empty(1, dtype=torch.float64, device=gamma.device)
-    assert num_batches_tracked is None or num_batches_tracked.dtype == torch.int64
-    _C.check(_C.fn("rr_bn_finalize_count")(_C.ptr(sums), _C.ptr(count_slot), _C.ptr(gamma), _C.ptr(beta), _C.ptr(running_mean),
-                                           _C.ptr(running_var), float(momentum), float(eps), _C.ptr(mean), _C.ptr(invstd),
-                                           _C.ptr(scale), _C.ptr(shift), c, _C.ptr(num_batches_tracked), _C.ptr(cnt), _C.stream()),
-             "rr_bn_finalize_count")
+    _C.call("rr_bn_finalize_count", sums, count_slot, gamma, beta, running_mean, running_var, float(momentum), float(eps), mean,
+            invstd, scale, shift, c, num_batches_tracked, cnt)
     return mean, invstd, scale, shift, cnt
 
 
 def bn_affine_grad(sums, dgamma, dbeta):
     """dbeta += sums[:c], dgamma += sums[c:2c] (the LOCAL BatchNorm-backward sums, before their SyncBN exchange): one launch."""
     c = dgamma.numel()
-    assert dgamma.is_contiguous() and dbeta.is_contiguous() and dgamma.dtype == torch.float32
-    _C.check(_C.fn("rr_bn_affine_grad")(_C.ptr(sums), _C.ptr(dgamma), _C.ptr(dbeta), c, _C.stream()), "rr_bn_affine_grad")
+    assert dgamma.is_contiguous() and dbeta.is_contiguous()
+    _C.call("rr_bn_affine_grad", sums, dgamma, dbeta, c)
 
 
 def bn_finalize(sums, count, gamma, beta, running_mean, running_var, momentum, eps, count_dev=None,
@@ -970,11 +953,8 @@ def bn_finalize(sums, count, gamma, beta, running_mean, running_var, momentum, e
     dev = gamma.device
     buf = _f32(4 * c, dev)                       # mean | invstd | scale | shift: one allocation
     mean, invstd, scale, shift = buf[0:c], buf[c:2 * c], buf[2 * c:3 * c], buf[3 * c:4 * c]
-    assert num_batches_tracked is None or num_batches_tracked.dtype == torch.int64
-    _C.check(_C.fn("rr_bn_finalize")(_C.ptr(sums), float(count), _C.ptr(count_dev), _C.ptr(gamma), _C.ptr(beta), _C.ptr(running_mean),
-                                     _C.ptr(running_var), float(momentum), float(eps), _C.ptr(mean), _C.ptr(invstd),
-                                     _C.ptr(scale), _C.ptr(shift), c, _C.ptr(num_batches_tracked), _C.stream()),
-             "rr_bn_finalize")
+    _C.call("rr_bn_finalize", sums, float(count), count_dev, gamma, beta, running_mean, running_var, float(momentum), float(eps),
+            mean, invstd, scale, shift, c, num_batches_tracked)
     return mean, invstd, scale, shift
 
 
@@ -984,25 +964,21 @@ def bn_stats_finalize(slab, count, gamma, beta, running_mean, running_var, momen
     buf = _f32(4 * c, gamma.device)
     mean, invstd, scale, shift = buf[0:c], buf[c:2 * c], buf[2 * c:3 * c], buf[3 * c:4 * c]
     mtiles = slab.numel() // (2 * c)
-    assert num_batches_tracked is None or num_batches_tracked.dtype == torch.int64
-    _C.check(_C.fn("rr_bn_stats_finalize")(_C.ptr(slab), mtiles, float(count), _C.ptr(gamma), _C.ptr(beta),
-                                           _C.ptr(running_mean), _C.ptr(running_var), float(momentum), float(eps),
-                                           _C.ptr(mean), _C.ptr(invstd), _C.ptr(scale), _C.ptr(shift), c,
-                                           _C.ptr(num_batches_tracked), _C.stream()), "rr_bn_stats_finalize")
+    _C.call("rr_bn_stats_finalize", slab, mtiles, float(count), gamma, beta, running_mean, running_var, float(momentum), float(eps),
+            mean, invstd, scale, shift, c, num_batches_tracked)
     return mean, invstd, scale, shift
 
 
 def bn_eval_coeffs(gamma, beta, running_mean, running_var, eps):
     c = gamma.numel()
     scale, shift = _f32(c, gamma.device), _f32(c, gamma.device)
-    _C.check(_C.fn("rr_bn_eval_coeffs")(_C.ptr(gamma), _C.ptr(beta), _C.ptr(running_mean), _C.ptr(running_var),
-                                        float(eps), _C.ptr(scale), _C.ptr(shift), c, _C.stream()), "rr_bn_eval_coeffs")
+    _C.call("rr_bn_eval_coeffs", gamma, beta, running_mean, running_var, float(eps), scale, shift, c)
     return scale, shift
 
 
 def _operand(t, phantom):
-    """-> (fp32 pointer, image pointer) of an operand the `_b16` entry points read in either form: one of the two is NULL."""
-    return (_C.ptr(None), _C.ptr(image_of(t))) if phantom else (_C.ptr(t), _C.ptr(None))
+    """-> (fp32 tensor, image) of an operand the `_b16` entry points read in either form: one of the two is None (NULL)."""
+    return (None, image_of(t)) if phantom else (t, None)
 
 
 def _produced(n, c, h, w, device, f32, image):
@@ -1031,16 +1007,15 @@ def bn_apply(y, scale, shift, residual=None, relu=False, res_scale=None, res_shi
     only16 = mixed and bf16_only
     out, out16 = _produced(n, c, h, w, y.device, not only16, only16 or image_wanted(c, n * h * w, y.device))
     if mixed or out16 is not None:
-        _C.check(_C.fn("rr_bn_apply_b16")(*_operand(y, y_ph), _C.ptr(scale), _C.ptr(shift), *_operand(residual, res_ph),
-                                          _C.ptr(res_scale), _C.ptr(res_shift), _C.ptr(out), _C.ptr(out16), y.numel(), c, int(relu),
-                                          _C.stream()), "rr_bn_apply_b16")
+        _C.call("rr_bn_apply_b16", *_operand(y, y_ph), scale, shift, *_operand(residual, res_ph), res_scale, res_shift, out, out16,
+                y.numel(), c, int(relu))
         return _published(out, out16)
-    head = (_C.ptr(y), _C.ptr(scale), _C.ptr(shift), _C.ptr(residual), _C.ptr(res_scale), _C.ptr(res_shift), _C.ptr(out), y.numel(), c, int(relu))
+    head = (y, scale, shift, residual, res_scale, res_shift, out, y.numel(), c, int(relu))
     if amax_wanted(c, n * h * w, y.device):
-        word = _ZEROS.take(1, y.device)
-        _C.check(_C.fn("rr_bn_apply_amax")(*head, _C.ptr(word), _C.stream()), "rr_bn_apply_amax")
+        word = _amax_word(y.device)
+        _C.call("rr_bn_apply_amax", *head, word)
         return _published(out, None, word)
-    _C.check(_C.fn("rr_bn_apply")(*head, _C.stream()), "rr_bn_apply")
+    _C.call("rr_bn_apply", *head)
     return out
 
 
@@ -1049,13 +1024,10 @@ def bn_bwd_reduce(dz, z, y, mean, invstd, extra=0, mask_scale=None, mask_shift=N
     sums = _ZEROS.take(2 * c + extra, y.device)            # pre-zeroed pool slice: no memset launch per layer
     z_ph, y_ph = is_phantom(z), is_phantom(y)
     if z_ph or y_ph:                                        # the layer's output / pre-BN output exist only as bf16 images
-        _C.check(_C.fn("rr_bn_bwd_reduce_b16")(_C.ptr(dz), *_operand(z, z_ph), *_operand(y, y_ph), _C.ptr(mean), _C.ptr(invstd),
-                                               _C.ptr(mask_scale), _C.ptr(mask_shift), _C.ptr(sums), n * h * w, c, _C.stream()),
-                 "rr_bn_bwd_reduce_b16")
+        _C.call("rr_bn_bwd_reduce_b16", dz, *_operand(z, z_ph), *_operand(y, y_ph), mean, invstd, mask_scale, mask_shift, sums,
+                n * h * w, c)
         return sums
-    _C.check(_C.fn("rr_bn_bwd_reduce")(_C.ptr(dz), _C.ptr(z), _C.ptr(y), _C.ptr(mean), _C.ptr(invstd),
-                                       _C.ptr(mask_scale), _C.ptr(mask_shift), _C.ptr(sums),
-                                       n * h * w, c, 1, _C.stream()), "rr_bn_bwd_reduce")
+    _C.call("rr_bn_bwd_reduce", dz, z, y, mean, invstd, mask_scale, mask_shift, sums, n * h * w, c, 1)
     return sums
 
 
@@ -1074,28 +1046,25 @@ def bn_bwd_apply(dz, z, y, mean, invstd, gamma, sums, count, want_g=False, dgamm
     else:
         g = empty_nhwc(n, c, h, w, y.device) if want_g else None
     dx, dx16 = _produced(n, c, h, w, y.device, not only16, only16 or image_wanted(c, n * h * w, y.device))
-    mid = (_C.ptr(mean), _C.ptr(invstd), _C.ptr(gamma), _C.ptr(mask_scale), _C.ptr(mask_shift), _C.ptr(sums), float(count), _C.ptr(count_dev))
+    mid = (mean, invstd, gamma, mask_scale, mask_shift, sums, float(count), count_dev)
     if z_ph or y_ph or dx16 is not None:
-        _C.check(_C.fn("rr_bn_bwd_apply_b16")(_C.ptr(dz), *_operand(z, z_ph), *_operand(y, y_ph), *mid, _C.ptr(dx), _C.ptr(dx16), _C.ptr(g),
-                                              int(g_into is not None), _C.ptr(dgamma), _C.ptr(dbeta), y.numel(), c, _C.stream()),
-                 "rr_bn_bwd_apply_b16")
+        _C.call("rr_bn_bwd_apply_b16", dz, *_operand(z, z_ph), *_operand(y, y_ph), *mid, dx, dx16, g, int(g_into is not None),
+                dgamma, dbeta, y.numel(), c)
         return _published(dx, dx16), g
     if amax_wanted(c, n * h * w, y.device):
         # split-operand convolutions: dx is the operand of the data / weight gradient launched next — its maximum comes out
         # of this pass.  (dx is a fresh tensor that nothing adds into later: the remembered maximum cannot go stale.)
-        word = _ZEROS.take(1, y.device)
-        _C.check(_C.fn("rr_bn_bwd_apply_amax")(_C.ptr(dz), _C.ptr(z), _C.ptr(y), *mid, _C.ptr(dx), _C.ptr(g), int(g_into is not None),
-                                               _C.ptr(dgamma), _C.ptr(dbeta), y.numel(), c, _C.ptr(word), _C.stream()), "rr_bn_bwd_apply_amax")
+        word = _amax_word(y.device)
+        _C.call("rr_bn_bwd_apply_amax", dz, z, y, *mid, dx, g, int(g_into is not None), dgamma, dbeta, y.numel(), c, word)
         return _published(dx, None, word), g
-    _C.check(_C.fn("rr_bn_bwd_apply_gacc" if g_into is not None else "rr_bn_bwd_apply")(
-        _C.ptr(dz), _C.ptr(z), _C.ptr(y), *mid, _C.ptr(dx), _C.ptr(g), _C.ptr(dgamma), _C.ptr(dbeta), y.numel(), c, _C.stream()), "rr_bn_bwd_apply")
+    _C.call("rr_bn_bwd_apply_gacc" if g_into is not None else "rr_bn_bwd_apply", dz, z, y, *mid, dx, g, dgamma, dbeta, y.numel(), c)
     return dx, g
 
 
 def relu_fwd(x):
     out = torch.empty_like(x)
     assert out.stride() == x.stride()
-    _C.check(_C.fn("rr_relu_fwd")(_C.ptr(x), _C.ptr(out), x.numel(), _C.stream()), "rr_relu_fwd")
+    _C.call("rr_relu_fwd", x, out, x.numel())
     return out
 
 
@@ -1108,8 +1077,7 @@ def sum_n(grads, z=None):
     out = torch.empty_like(g0)
     assert out.stride() == g0.stride()
     arr = (ctypes.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
-    _C.check(_C.fn("rr_sum_n")(ctypes.cast(arr, ctypes.c_void_p), len(grads), _C.ptr(z), _C.ptr(out), g0.numel(),
-                               _C.stream()), "rr_sum_n")
+    _C.call("rr_sum_n", ctypes.cast(arr, ctypes.c_void_p), len(grads), z, out, g0.numel())
     return out
 
 
@@ -1118,8 +1086,7 @@ def bias_relu_bwd(dy, z, dbias):
     c = dbias.numel()
     npix = dy.numel() // c
     masked = torch.empty_like(dy) if z is not None else None
-    _C.check(_C.fn("rr_bias_relu_bwd")(_C.ptr(dy), _C.ptr(z), _C.ptr(masked), _C.ptr(dbias), npix, c, _C.stream()),
-             "rr_bias_relu_bwd")
+    _C.call("rr_bias_relu_bwd", dy, z, masked, dbias, npix, c)
     return masked if z is not None else dy
 
 
@@ -1131,21 +1098,18 @@ def upsample_add_fwd(up1, low, bf16_only=False):
     if fast and (bf16_only or is_phantom(up1) or is_phantom(low)):
         u_ph, l_ph = is_phantom(up1), is_phantom(low)
         out, out16 = _produced(n, c, h, w, up1.device, not bf16_only, bf16_only or image_wanted(c, n * h * w, up1.device))
-        _C.check(_C.fn("rr_upsample2x_add_b16")(*_operand(up1, u_ph), *_operand(low, l_ph), _C.ptr(out), _C.ptr(out16), n, h, w, c,
-                                                _C.stream()), "rr_upsample2x_add_b16")
+        _C.call("rr_upsample2x_add_b16", *_operand(up1, u_ph), *_operand(low, l_ph), out, out16, n, h, w, c)
         return _published(out, out16)
     up1, low = f32_of(up1), f32_of(low)
     out = empty_nhwc(n, c, h, w, up1.device)
-    _C.check(_C.fn("rr_upsample_add_fwd")(_C.ptr(up1), _C.ptr(low), _C.ptr(out), n, h, w, low.shape[2], low.shape[3],
-                                          c, _C.stream()), "rr_upsample_add_fwd")
+    _C.call("rr_upsample_add_fwd", up1, low, out, n, h, w, low.shape[2], low.shape[3], c)
     return out
 
 
 def upsample_add_bwd(dout, low_shape):
     n, c, h, w = dout.shape
     dlow = empty_nhwc(n, c, low_shape[2], low_shape[3], dout.device)
-    _C.check(_C.fn("rr_upsample_add_bwd")(_C.ptr(dout), _C.ptr(dlow), n, h, w, low_shape[2], low_shape[3], c,
-                                          _C.stream()), "rr_upsample_add_bwd")
+    _C.call("rr_upsample_add_bwd", dout, dlow, n, h, w, low_shape[2], low_shape[3], c)
     return dlow
 
 
@@ -1156,15 +1120,14 @@ def resize_bilinear_ac(x, scale_factor):
     n, c, h, w = x.shape
     oh, ow = int(math.floor(h * scale_factor)), int(math.floor(w * scale_factor))
     out = empty_nhwc(n, c, oh, ow, x.device)
-    _C.check(_C.fn("rr_resize_bilinear_ac")(_C.ptr(x), _C.ptr(out), n, h, w, oh, ow, c, _C.stream()),
-             "rr_resize_bilinear_ac")
+    _C.call("rr_resize_bilinear_ac", x, out, n, h, w, oh, ow, c)
     return out
 
 
 def avgpool_fwd(x):
     r, c, h, w = x.shape
     out = empty_nhwc(r, c, 1, 1, x.device)
-    _C.check(_C.fn("rr_avgpool_fwd")(_C.ptr(x), _C.ptr(out), r, h * w, c, _C.stream()), "rr_avgpool_fwd")
+    _C.call("rr_avgpool_fwd", x, out, r, h * w, c)
     return out
 
 
@@ -1173,8 +1136,7 @@ def bn_res_relu_avgpool(y, scale, shift, res):
     assert is_nhwc(y) and is_nhwc(res) and y.shape == res.shape
     r, c, h, w = y.shape
     out = empty_nhwc(r, c, 1, 1, y.device)
-    _C.check(_C.fn("rr_bn_res_relu_avgpool")(_C.ptr(y), _C.ptr(scale), _C.ptr(shift), _C.ptr(res), _C.ptr(out), r, h * w, c,
-                                             _C.stream()), "rr_bn_res_relu_avgpool")
+    _C.call("rr_bn_res_relu_avgpool", y, scale, shift, res, out, r, h * w, c)
     return out
 
 
@@ -1186,15 +1148,14 @@ def conv1x1_bn_res_relu_avgpool(h, w, scale, shift, res):
     n = w.shape[0]
     assert tuple(w.shape[1:]) == (k, 1, 1) and tuple(res.shape) == (r, n, ph, pw)
     out = empty_nhwc(r, n, 1, 1, h.device)
-    _C.check(_C.fn("rr_conv1x1_bn_res_relu_avgpool")(_C.ptr(h), _C.ptr(w), _C.ptr(scale), _C.ptr(shift), _C.ptr(res), _C.ptr(out),
-                                                     r, ph * pw, k, n, _C.stream()), "rr_conv1x1_bn_res_relu_avgpool")
+    _C.call("rr_conv1x1_bn_res_relu_avgpool", h, w, scale, shift, res, out, r, ph * pw, k, n)
     return out
 
 
 def avgpool_bwd(dout, shape):
     r, c, h, w = shape
     dx = empty_nhwc(r, c, h, w, dout.device)
-    _C.check(_C.fn("rr_avgpool_bwd")(_C.ptr(dout), _C.ptr(dx), r, h * w, c, _C.stream()), "rr_avgpool_bwd")
+    _C.call("rr_avgpool_bwd", dout, dx, r, h * w, c)
     return dx
 
 
@@ -1202,23 +1163,21 @@ def wh_shift_sum_fwd(t, bias_w, bias_h, k):
     n, c, h, w = t.shape
     assert c >= 2 * k and is_nhwc(t)
     out = empty_nhwc(n, 2, h, w, t.device)
-    _C.check(_C.fn("rr_wh_shift_sum_fwd")(_C.ptr(t), _C.ptr(bias_w), _C.ptr(bias_h), _C.ptr(out), n, h, w, k, c,
-                                          _C.stream()), "rr_wh_shift_sum_fwd")
+    _C.call("rr_wh_shift_sum_fwd", t, bias_w, bias_h, out, n, h, w, k, c)
     return out
 
 
 def wh_shift_sum_bwd(dout, k, ct):
     n, _, h, w = dout.shape
     dt = empty_nhwc(n, ct, h, w, dout.device)
-    _C.check(_C.fn("rr_wh_shift_sum_bwd")(_C.ptr(dout), _C.ptr(dt), n, h, w, k, ct, _C.stream()), "rr_wh_shift_sum_bwd")
+    _C.call("rr_wh_shift_sum_bwd", dout, dt, n, h, w, k, ct)
     return dt
 
 
 def adam_step(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, grad_scale=1.0):
     assert param.numel() % 4 == 0
-    _C.check(_C.fn("rr_adam_step")(_C.ptr(param), _C.ptr(grad), _C.ptr(exp_avg), _C.ptr(exp_avg_sq), param.numel(),
-                                   float(lr), float(beta1), float(beta2), float(eps), int(step), float(grad_scale),
-                                   _C.stream()), "rr_adam_step")
+    _C.call("rr_adam_step", param, grad, exp_avg, exp_avg_sq, param.numel(), float(lr), float(beta1), float(beta2), float(eps),
+            int(step), float(grad_scale))
 
 
 GUARD_CTL_WORDS = 20                # RR_GUARD_CTL_WORDS of include/rrnet_hip.h
@@ -1235,7 +1194,7 @@ def guard_ctl_fresh():
 
 def grad_norm_blocks(n):
     """rr_grad_norm_blocks: the workgroups (= partial sums) of rr_grad_norm over n words; a function of n alone."""
-    return int(_C.fn("rr_grad_norm_blocks")(int(n)))
+    return int(_C.call("rr_grad_norm_blocks", int(n)))
 
 
 def _flat_f32(what, name, t, n=None):
@@ -1260,7 +1219,7 @@ def grad_norm(grad, partial=None, bad=None):
         raise _C.RRNetHipError("grad_norm: partial must be a contiguous float64 [%d] tensor on %s" % (blocks, grad.device))
     if bad.dtype != torch.int32 or not bad.is_contiguous() or bad.numel() != blocks or bad.device != grad.device:
         raise _C.RRNetHipError("grad_norm: bad must be a contiguous int32 [%d] tensor on %s" % (blocks, grad.device))
-    _C.check(_C.fn("rr_grad_norm")(_C.ptr(grad), n, _C.ptr(partial), _C.ptr(bad), _C.stream()), "rr_grad_norm")
+    _C.call("rr_grad_norm", grad, n, partial, bad)
     return partial, bad
 
 
@@ -1273,21 +1232,18 @@ def guard_decide(partial, bad, ctl, grad_scale=1.0, max_norm=float("inf"), skip_
                  beta2=0.999, ema_decay=0.0, ema_warmup=False):
     """rr_guard_decide on the current stream: adds up what grad_norm left, decides skip / clip and advances the control
     record `ctl` (float64 [GUARD_CTL_WORDS] on the device, layout in include/rrnet_hip.h) in place.  Nothing is read back."""
-    _C.require_cuda(partial, bad, ctl)
     if partial.dtype != torch.float64 or not partial.is_contiguous() or bad.dtype != torch.int32 or not bad.is_contiguous() \
             or partial.numel() != bad.numel():
         raise _C.RRNetHipError("guard_decide: partial (float64) and bad (int32) must be contiguous and equally long")
     _check_ctl("guard_decide", ctl, partial.device)
-    _C.check(_C.fn("rr_guard_decide")(_C.ptr(partial), _C.ptr(bad), partial.numel(), float(grad_scale), float(max_norm),
-                                      int(bool(skip_nonfinite)), float(lr), float(beta1), float(beta2), float(ema_decay),
-                                      int(bool(ema_warmup)), _C.ptr(ctl), _C.stream()), "rr_guard_decide")
+    _C.call("rr_guard_decide", partial, bad, partial.numel(), float(grad_scale), float(max_norm), int(bool(skip_nonfinite)),
+            float(lr), float(beta1), float(beta2), float(ema_decay), int(bool(ema_warmup)), ctl)
     return ctl
 
 
 def adam_step_guarded(param, grad, exp_avg, exp_avg_sq, ema, eps, ctl):
     """rr_adam_step_guarded on the current stream: the fused Adam step with its constants read from `ctl`; does nothing when
     ctl says skip; `ema` (None: no averaged weights) is updated in the same pass."""
-    _C.require_cuda(param, grad, exp_avg, exp_avg_sq, ema, ctl)
     _flat_f32("adam_step_guarded", "param", param)
     n = param.numel()
     if n % 4:
@@ -1296,8 +1252,7 @@ def adam_step_guarded(param, grad, exp_avg, exp_avg_sq, ema, eps, ctl):
         if t is not None:
             _flat_f32("adam_step_guarded", name, t, n)
     _check_ctl("adam_step_guarded", ctl, param.device)
-    _C.check(_C.fn("rr_adam_step_guarded")(_C.ptr(param), _C.ptr(grad), _C.ptr(exp_avg), _C.ptr(exp_avg_sq), _C.ptr(ema), n,
-                                           float(eps), _C.ptr(ctl), _C.stream()), "rr_adam_step_guarded")
+    _C.call("rr_adam_step_guarded", param, grad, exp_avg, exp_avg_sq, ema, n, float(eps), ctl)
 
 
 def state_snapshot(src, dst=None, chunk=65536, n=None, out=None):
@@ -1319,8 +1274,7 @@ def state_snapshot(src, dst=None, chunk=65536, n=None, out=None):
             raise _C.RRNetHipError("state_snapshot: out must be a contiguous int64 [%d, 3] tensor on %s" % (nchunks, src.device))
     digest = out if out is not None and nchunks else \
         torch.empty((max(nchunks, 1), 3), dtype=torch.int64, device=src.device)        # never a NULL pointer, also for n == 0
-    _C.check(_C.fn("rr_state_snapshot")(_C.ptr(src), _C.ptr(dst), n, chunk, _C.ptr(digest), _C.stream()),
-             "rr_state_snapshot")
+    _C.call("rr_state_snapshot", src, dst, n, chunk, digest)
     return digest[:nchunks]
 
 
@@ -1329,16 +1283,14 @@ def state_snapshot(src, dst=None, chunk=65536, n=None, out=None):
 # ---------------------------------------------------------------------------------------------
 def focal_fwd(logits, gt):
     sums = torch.empty(3, dtype=torch.float64, device=logits.device)
-    _C.check(_C.fn("rr_focal_loss_fwd")(_C.ptr(logits), _C.ptr(gt), logits.numel(), _C.ptr(sums), _C.stream()),
-             "rr_focal_loss_fwd")
+    _C.call("rr_focal_loss_fwd", logits, gt, logits.numel(), sums)
     return sums
 
 
 def focal_bwd(logits, gt, sums, gout, gscale=1.0):
     d = torch.empty_like(logits)
     assert d.stride() == logits.stride()
-    _C.check(_C.fn("rr_focal_loss_bwd")(_C.ptr(logits), _C.ptr(gt), logits.numel(), _C.ptr(sums), _C.ptr(gout),
-                                        float(gscale), _C.ptr(d), _C.stream()), "rr_focal_loss_bwd")
+    _C.call("rr_focal_loss_bwd", logits, gt, logits.numel(), sums, gout, float(gscale), d)
     return d
 
 
@@ -1346,8 +1298,7 @@ def regl1_fwd(pred, mask, ind, target):
     b, c, h, w = pred.shape
     m = ind.shape[1]
     sums = torch.empty(3, dtype=torch.float64, device=pred.device)
-    _C.check(_C.fn("rr_regl1_fwd")(_C.ptr(pred), _C.ptr(mask), _C.ptr(ind), _C.ptr(target), b, m, c, h * w, _C.ptr(sums),
-                                   _C.stream()), "rr_regl1_fwd")
+    _C.call("rr_regl1_fwd", pred, mask, ind, target, b, m, c, h * w, sums)
     return sums
 
 
@@ -1355,8 +1306,7 @@ def regl1_bwd(pred, mask, ind, target, sums, gout, gscale=1.0):
     b, c, h, w = pred.shape
     m = ind.shape[1]
     d = empty_nhwc(b, c, h, w, pred.device)
-    _C.check(_C.fn("rr_regl1_bwd")(_C.ptr(pred), _C.ptr(mask), _C.ptr(ind), _C.ptr(target), b, m, c, h * w, _C.ptr(sums),
-                                   _C.ptr(gout), float(gscale), _C.ptr(d), _C.stream()), "rr_regl1_bwd")
+    _C.call("rr_regl1_bwd", pred, mask, ind, target, b, m, c, h * w, sums, gout, float(gscale), d)
     return d
 
 
@@ -1372,9 +1322,7 @@ def stage2_loss(rois, reg, gt_xyxy, scale, want_droi=False):
     loss = torch.empty(3, dtype=torch.float64, device=dev)
     dreg = torch.zeros((r, 4), dtype=torch.float32, device=dev)
     droi = torch.zeros((r, 4), dtype=torch.float32, device=dev) if want_droi else None
-    _C.check(_C.fn("rr_stage2_loss")(_C.ptr(rois), _C.ptr(reg), r, _C.ptr(gt_xyxy), b, g, gs, float(scale), _C.ptr(tgt),
-                                     _C.ptr(pos), _C.ptr(npos), _C.ptr(loss), _C.ptr(dreg), _C.ptr(droi), _C.stream()),
-             "rr_stage2_loss")
+    _C.call("rr_stage2_loss", rois, reg, r, gt_xyxy, b, g, gs, float(scale), tgt, pos, npos, loss, dreg, droi)
     return loss, dreg, tgt[:r], pos[:r], npos, droi
 
 
@@ -1391,27 +1339,24 @@ def decode_topk(hm, wh, off, k, is_logits=True, want_pix=False, peak_filter=Fals
     pix = torch.empty((b, k), dtype=torch.int32, device=hm.device) if want_pix else None
     ws, ws_bytes = None, 0
     if spread and h * w * c >= 65536:
-        ws_bytes = _C.fn("rr_decode_workspace_bytes")(b)
+        ws_bytes = _C.call("rr_decode_workspace_bytes", b)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=hm.device)
-    _C.check(_C.fn("rr_decode_topk")(_C.ptr(hm), int(is_logits), int(peak_filter), _C.ptr(wh), _C.ptr(off), b, h, w, c, k,
-                                     int(box_mode), float(scale), _C.ptr(out), _C.ptr(pix), _C.ptr(ws), ws_bytes,
-                                     _C.stream()), "rr_decode_topk")
+    _C.call("rr_decode_topk", hm, int(is_logits), int(peak_filter), wh, off, b, h, w, c, k, int(box_mode), float(scale), out, pix,
+            ws, ws_bytes)
     return (out, pix) if want_pix else out
 
 
 def roi_provenance(rois, scores, clses, decoded, pix):
     r = rois.shape[0]
     roi_pix = torch.full((max(r, 1),), -1, dtype=torch.int32, device=rois.device)
-    _C.check(_C.fn("rr_roi_provenance")(_C.ptr(rois), _C.ptr(scores), _C.ptr(clses), r, _C.ptr(decoded), _C.ptr(pix),
-                                        decoded.shape[1], _C.ptr(roi_pix), _C.stream()), "rr_roi_provenance")
+    _C.call("rr_roi_provenance", rois, scores, clses, r, decoded, pix, decoded.shape[1], roi_pix)
     return roi_pix[:r]
 
 
 def proposal_bwd(droi, rois, roi_pix, wh):
     b, _, h, w = wh.shape
     dwh, doff = empty_nhwc(b, 2, h, w, wh.device), empty_nhwc(b, 2, h, w, wh.device)
-    _C.check(_C.fn("rr_proposal_bwd")(_C.ptr(droi), _C.ptr(rois), _C.ptr(roi_pix), rois.shape[0], _C.ptr(wh), b, h, w,
-                                      _C.ptr(dwh), _C.ptr(doff), _C.stream()), "rr_proposal_bwd")
+    _C.call("rr_proposal_bwd", droi, rois, roi_pix, rois.shape[0], wh, b, h, w, dwh, doff)
     return dwh, doff
 
 
@@ -1419,7 +1364,7 @@ def peak3x3(hm, is_logits=True):
     """`_ctnet_nms` score map: sigmoid(hm) (or hm itself when is_logits=False) where it equals its 3x3 maximum, else 0."""
     b, c, h, w = hm.shape
     out = empty_nhwc(b, c, h, w, hm.device)
-    _C.check(_C.fn("rr_peak3x3")(_C.ptr(hm), int(is_logits), _C.ptr(out), b, h, w, c, _C.stream()), "rr_peak3x3")
+    _C.call("rr_peak3x3", hm, int(is_logits), out, b, h, w, c)
     return out
 
 
@@ -1431,16 +1376,14 @@ def group_by_class(boxes, num_classes, cls_base=0):
     grouped = torch.empty_like(boxes)
     seg_off = torch.empty(b * num_classes + 1, dtype=torch.int32, device=boxes.device)
     seg_len = torch.empty(b * num_classes, dtype=torch.int32, device=boxes.device)
-    _C.check(_C.fn("rr_group_by_class")(_C.ptr(boxes), b, k, num_classes, cls_base, _C.ptr(grouped), _C.ptr(seg_off),
-                                        _C.ptr(seg_len), _C.stream()), "rr_group_by_class")
+    _C.call("rr_group_by_class", boxes, b, k, num_classes, cls_base, grouped, seg_off, seg_len)
     return grouped, seg_off, seg_len
 
 
 def hard_nms_segments(boxes6, seg_off, max_seg, thresh, seg_len=None):
     nseg = seg_off.numel() - 1
     n_out = torch.zeros(nseg, dtype=torch.int32, device=boxes6.device)
-    _C.check(_C.fn("rr_hard_nms_segments")(_C.ptr(boxes6), _C.ptr(seg_off), _C.ptr(seg_len), nseg, int(max_seg),
-                                           float(thresh), _C.ptr(n_out), _C.stream()), "rr_hard_nms_segments")
+    _C.call("rr_hard_nms_segments", boxes6, seg_off, seg_len, nseg, int(max_seg), float(thresh), n_out)
     return n_out
 
 
@@ -1451,7 +1394,7 @@ def wbf_plan(nseg, max_seg):
     """rr_wbf_plan -> list of RR_WBF_PLAN_INTS ints (include/rrnet_hip.h); a bound the kernel refuses raises RRNetHipError."""
     import ctypes
     buf = (ctypes.c_int * 32)()
-    _C.check(_C.fn("rr_wbf_plan")(int(nseg), int(max_seg), buf, 32), "rr_wbf_plan")
+    _C.call("rr_wbf_plan", int(nseg), int(max_seg), buf, 32)
     return list(buf)
 
 
@@ -1476,11 +1419,10 @@ def wbf_segments(rows, seg_off, max_seg, iou_thr, conf_type, weight_sum, seg_len
         raise ValueError("wbf_segments: out must be another contiguous float32 tensor of rows' shape")
     members = torch.zeros(rows.shape[0], dtype=torch.int32, device=dev)
     n_out = torch.zeros(max(nseg, 0), dtype=torch.int32, device=dev)
-    nbytes = _C.fn("rr_wbf_workspace_bytes")(nseg, int(max_seg))
+    nbytes = _C.call("rr_wbf_workspace_bytes", nseg, int(max_seg))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
-    _C.check(_C.fn("rr_wbf_segments")(_C.ptr(rows), _C.ptr(seg_off), _C.ptr(seg_len), nseg, int(max_seg), float(iou_thr),
-                                      int(conf_type), float(weight_sum), _C.ptr(out), _C.ptr(members), _C.ptr(n_out),
-                                      _C.ptr(ws), nbytes, _C.stream()), "rr_wbf_segments")
+    _C.call("rr_wbf_segments", rows, seg_off, seg_len, nseg, int(max_seg), float(iou_thr), int(conf_type), float(weight_sum), out,
+            members, n_out, ws, nbytes)
     return out, members, n_out
 
 
@@ -1504,15 +1446,14 @@ def text_lines(text, file_off):
     if not file_off.is_contiguous():
         raise ValueError("text_lines: file_off must be contiguous")
     n, dev = text.numel(), text.device
-    nblocks = _C.fn("rr_text_line_blocks")(n)
+    nblocks = _C.call("rr_text_line_blocks", n)
     counts = torch.empty(nblocks, dtype=torch.int32, device=dev)
-    _C.check(_C.fn("rr_text_line_counts")(_C.ptr(text), n, _C.ptr(counts), _C.stream()), "rr_text_line_counts")
+    _C.call("rr_text_line_counts", text, n, counts)
     block_off = _exclusive_sum(counts)
     nlines = int(block_off[-1].item())
     line_pos = torch.empty(nlines, dtype=torch.int64, device=dev)
     file_line_off = torch.empty(file_off.numel(), dtype=torch.int64, device=dev)
-    _C.check(_C.fn("rr_text_lines")(_C.ptr(text), n, _C.ptr(file_off), file_off.numel() - 1, _C.ptr(block_off), nlines,
-                                    _C.ptr(line_pos), _C.ptr(file_line_off), _C.stream()), "rr_text_lines")
+    _C.call("rr_text_lines", text, n, file_off, file_off.numel() - 1, block_off, nlines, line_pos, file_line_off)
     return line_pos, file_line_off
 
 
@@ -1524,8 +1465,7 @@ def text_parse(text, line_pos, ncol=8):
     nlines, dev = line_pos.numel(), text.device
     rows = torch.empty((nlines, ncol), dtype=torch.float64, device=dev)
     flags = torch.empty(nlines, dtype=torch.int32, device=dev)
-    _C.check(_C.fn("rr_text_parse")(_C.ptr(text), text.numel(), _C.ptr(line_pos), nlines, int(ncol), _C.ptr(rows),
-                                    _C.ptr(flags), _C.stream()), "rr_text_parse")
+    _C.call("rr_text_parse", text, text.numel(), line_pos, nlines, int(ncol), rows, flags)
     return rows, flags
 
 
@@ -1541,26 +1481,24 @@ def text_format_len(rows6, layout, clamp):
     r, dev = rows6.shape[0], rows6.device
     length = torch.empty(r, dtype=torch.int32, device=dev)
     flag = torch.empty(r, dtype=torch.int32, device=dev)
-    _C.check(_C.fn("rr_text_format_len")(_C.ptr(rows6), r, int(TEXT_LAYOUTS.get(layout, layout)), int(bool(clamp)),
-                                         _C.ptr(length), _C.ptr(flag), _C.stream()), "rr_text_format_len")
+    _C.call("rr_text_format_len", rows6, r, int(TEXT_LAYOUTS.get(layout, layout)), int(bool(clamp)), length, flag)
     return length, flag, _exclusive_sum(length)
 
 
 def text_format(rows6, layout, clamp, byte_off, out):
     """rr_text_format: writes row r to out[byte_off[r] : byte_off[r+1]] (uint8 device buffer) and returns out."""
-    _C.require_cuda(rows6, byte_off, out)
     _check_rows6("text_format", rows6)
     if byte_off.dtype != torch.int64 or byte_off.numel() != rows6.shape[0] + 1 or not byte_off.is_contiguous():
         raise ValueError("text_format: byte_off must be contiguous int64 [R+1]")
     if out.dtype != torch.uint8 or not out.is_contiguous():
         raise ValueError("text_format: out must be a contiguous uint8 buffer")
-    _C.check(_C.fn("rr_text_format")(_C.ptr(rows6), rows6.shape[0], int(TEXT_LAYOUTS.get(layout, layout)), int(bool(clamp)),
-                                     _C.ptr(byte_off), _C.ptr(out), out.numel(), _C.stream()), "rr_text_format")
+    _C.call("rr_text_format", rows6, rows6.shape[0], int(TEXT_LAYOUTS.get(layout, layout)), int(bool(clamp)), byte_off, out,
+            out.numel())
     return out
 
 
 def _np_ptr(a):
-    return _C.c_void_p(a.ctypes.data) if a is not None else _C.c_void_p(0)
+    return _C.c_void_p(a.ctypes.data)
 
 
 def text_parse_host(text, file_off, ncol=8):
@@ -1573,16 +1511,14 @@ def text_parse_host(text, file_off, ncol=8):
     nfiles = file_off.size - 1
     file_line_off = np.zeros(nfiles + 1, np.int64)
     nlines = ctypes.c_long(0)
-    f = _C.fn("rr_text_lines_host")
-    _C.check(f(_np_ptr(text), text.size, _np_ptr(file_off), nfiles, 0, _np_ptr(None), _np_ptr(file_line_off),
-               ctypes.byref(nlines)), "rr_text_lines_host")
+    _C.call("rr_text_lines_host", _np_ptr(text), text.size, _np_ptr(file_off), nfiles, 0, None, _np_ptr(file_line_off), ctypes.byref(nlines))
     line_pos = np.zeros(nlines.value, np.int64)
-    _C.check(f(_np_ptr(text), text.size, _np_ptr(file_off), nfiles, line_pos.size, _np_ptr(line_pos), _np_ptr(file_line_off),
-               ctypes.byref(nlines)), "rr_text_lines_host")
+    _C.call("rr_text_lines_host", _np_ptr(text), text.size, _np_ptr(file_off), nfiles, line_pos.size, _np_ptr(line_pos),
+            _np_ptr(file_line_off), ctypes.byref(nlines))
     rows = np.zeros((line_pos.size, ncol), np.float64)
     flags = np.zeros(line_pos.size, np.int32)
-    _C.check(_C.fn("rr_text_parse_host")(_np_ptr(text), text.size, _np_ptr(line_pos), line_pos.size, int(ncol), _np_ptr(rows),
-                                         _np_ptr(flags)), "rr_text_parse_host")
+    _C.call("rr_text_parse_host", _np_ptr(text), text.size, _np_ptr(line_pos), line_pos.size, int(ncol), _np_ptr(rows),
+            _np_ptr(flags))
     return rows, flags, line_pos, file_line_off
 
 
@@ -1594,14 +1530,12 @@ def text_format_host(rows6, layout, clamp, pad=0, fill=0):
     layout = int(TEXT_LAYOUTS.get(layout, layout))
     r = rows6.shape[0]
     length, flag = np.zeros(r, np.int32), np.zeros(r, np.int32)
-    f = _C.fn("rr_text_format_host")
-    _C.check(f(_np_ptr(rows6), r, layout, int(bool(clamp)), _np_ptr(length), _np_ptr(flag), _np_ptr(None), _np_ptr(None), 0),
-             "rr_text_format_host")
+    _C.call("rr_text_format_host", _np_ptr(rows6), r, layout, int(bool(clamp)), _np_ptr(length), _np_ptr(flag), None, None, 0)
     byte_off = np.zeros(r + 1, np.int64)
     np.cumsum(length, out=byte_off[1:])
     out = np.full(int(byte_off[-1]) + pad, fill, np.uint8)
-    _C.check(f(_np_ptr(rows6), r, layout, int(bool(clamp)), _np_ptr(None), _np_ptr(None), _np_ptr(byte_off), _np_ptr(out),
-               int(byte_off[-1])), "rr_text_format_host")
+    _C.call("rr_text_format_host", _np_ptr(rows6), r, layout, int(bool(clamp)), None, None, _np_ptr(byte_off), _np_ptr(out),
+            int(byte_off[-1]))
     return out, byte_off, flag
 
 
@@ -1609,9 +1543,7 @@ def seg_prefix(n_out):
     """Exclusive prefix of per-segment counts -> int32 [nseg+1] (last entry = total)."""
     nseg = n_out.numel()
     out_off = torch.empty(nseg + 1, dtype=torch.int32, device=n_out.device)
-    nul = _C.c_void_p(0)
-    _C.check(_C.fn("rr_pack_segments")(nul, nul, _C.ptr(n_out), nseg, 1, _C.ptr(out_off), nul, nul, nul, nul, 0,
-                                       _C.stream()), "rr_pack_segments")
+    _C.call("rr_pack_segments", None, None, n_out, nseg, 1, out_off, None, None, None, None, 0)
     return out_off
 
 
@@ -1619,7 +1551,6 @@ def pack_segments(grouped, seg_off, n_out, segs_per_image, want_rois=True, want_
     """-> (rois [R,5], scores [R], clses [R]) and/or rows [R,6]; one host sync to learn R."""
     nseg = n_out.numel()
     dev = grouped.device
-    f = _C.fn("rr_pack_segments")
     out_off = seg_prefix(n_out)
     import time as _time
     t0 = _time.perf_counter()
@@ -1630,8 +1561,7 @@ def pack_segments(grouped, seg_off, n_out, segs_per_image, want_rois=True, want_
     scores = torch.empty(r, dtype=torch.float32, device=dev) if want_rois else None
     clses = torch.empty(r, dtype=torch.float32, device=dev) if want_rois else None
     rows = torch.empty((r, 6), dtype=torch.float32, device=dev) if want_rows else None
-    _C.check(f(_C.ptr(grouped), _C.ptr(seg_off), _C.ptr(n_out), nseg, segs_per_image, _C.ptr(out_off), _C.ptr(rois),
-               _C.ptr(scores), _C.ptr(clses), _C.ptr(rows), 1, _C.stream()), "rr_pack_segments")
+    _C.call("rr_pack_segments", grouped, seg_off, n_out, nseg, segs_per_image, out_off, rois, scores, clses, rows, 1)
     if want_offsets:
         return rois, scores, clses, rows, out_off
     return rois, scores, clses, rows
@@ -1641,7 +1571,7 @@ def ctnet_targets(annos, counts, img_h, img_w, scale_factor=4, num_classes=10):
     """annos [B,M,>=6] cuda float32 (padded), counts [B] cuda int32 -> hm (logical [B,C,Hf,Wf], NHWC memory),
     wh [B,M,2], ind [B,M,1], offset [B,M,2], reg_mask [B,M,1]  (collate_fn_ctnet contract)."""
     _C.require_cuda(annos, counts)
-    assert annos.dtype == torch.float32 and annos.is_contiguous() and counts.dtype == torch.int32
+    assert annos.is_contiguous()
     b, m, st = annos.shape
     hf, wf = img_h // scale_factor, img_w // scale_factor
     dev = annos.device
@@ -1650,24 +1580,21 @@ def ctnet_targets(annos, counts, img_h, img_w, scale_factor=4, num_classes=10):
     ind = torch.empty((b, m, 1), dtype=torch.float32, device=dev)
     off = torch.empty((b, m, 2), dtype=torch.float32, device=dev)
     mask = torch.empty((b, m, 1), dtype=torch.float32, device=dev)
-    _C.check(_C.fn("rr_ctnet_targets")(_C.ptr(annos), _C.ptr(counts), b, m, st, img_h, img_w, scale_factor, num_classes,
-                                       _C.ptr(hm), _C.ptr(wh), _C.ptr(ind), _C.ptr(off), _C.ptr(mask), _C.stream()),
-             "rr_ctnet_targets")
+    _C.call("rr_ctnet_targets", annos, counts, b, m, st, img_h, img_w, scale_factor, num_classes, hm, wh, ind, off, mask)
     return hm, wh, ind, off, mask
 
 
 AUGMENT_PARAMS = 16        # RR_AUGMENT_PARAMS: int32 words of rr_augment_frames' per-image record
 
 
-def _jitter_ptrs(jitter, b):
-    """jitter: None or (factors float32 [B,3], gray_mean int32 [B]) -> the two extra pointers of a _jitter entry."""
+def _jitter_args(jitter, b):
+    """jitter: None or (factors float32 [B,3], gray_mean int32 [B]) -> the two extra arguments of a _jitter entry."""
     if jitter is None:
         return ()
     factors, gray_mean = jitter
-    _C.require_cuda(factors, gray_mean)
-    assert factors.dtype == torch.float32 and factors.is_contiguous() and factors.shape == (b, 3)
-    assert gray_mean.dtype == torch.int32 and gray_mean.is_contiguous() and gray_mean.numel() == b
-    return (_C.ptr(factors), _C.ptr(gray_mean))
+    assert factors.is_contiguous() and factors.shape == (b, 3)
+    assert gray_mean.is_contiguous() and gray_mean.numel() == b
+    return (factors, gray_mean)
 
 
 def augment_frames(src, params, rects, rect_off, taps, mean, std, out_h, out_w, jitter=None):
@@ -1677,20 +1604,18 @@ def augment_frames(src, params, rects, rect_off, taps, mean, std, out_h, out_w, 
     are built (and checked against the window and table sizes) by rrnet_amd.datasets.augment.pack_batch.  `jitter`
     (factors, gray_mean) selects rr_augment_frames_jitter: see augment_frames_jitter."""
     _C.require_cuda(src, params, rects, rect_off, taps, mean, std)
-    assert src.dtype == torch.uint8 and src.is_contiguous() and src.dim() == 1
-    assert params.dtype == torch.int32 and params.is_contiguous() and params.shape[1] == AUGMENT_PARAMS
-    assert rect_off.dtype == torch.int32 and rect_off.numel() == params.shape[0] + 1
-    assert taps.dtype == torch.int32 and taps.is_contiguous() and taps.shape[1] == 3
-    assert mean.dtype == torch.float32 and std.dtype == torch.float32 and mean.numel() == 3 and std.numel() == 3
+    assert src.is_contiguous() and src.dim() == 1
+    assert params.is_contiguous() and params.shape[1] == AUGMENT_PARAMS
+    assert rect_off.numel() == params.shape[0] + 1
+    assert taps.is_contiguous() and taps.shape[1] == 3
+    assert mean.numel() == 3 and std.numel() == 3
     if rects is not None and rects.numel() == 0:
         rects = None
-    assert rects is None or (rects.dtype == torch.int32 and rects.is_contiguous() and rects.shape[1] == 4)
+    assert rects is None or (rects.is_contiguous() and rects.shape[1] == 4)
     b = params.shape[0]
     out = empty_nhwc(b, 3, out_h, out_w, src.device)
-    entry = _C.fn("rr_augment_frames_jitter") if jitter is not None else _C.fn("rr_augment_frames")
-    _C.check(entry(_C.ptr(src), src.numel(), _C.ptr(params), _C.ptr(rects), _C.ptr(rect_off), _C.ptr(taps), taps.shape[0],
-                   _C.ptr(mean), _C.ptr(std), *_jitter_ptrs(jitter, b), _C.ptr(out), b, out_h, out_w, _C.stream()),
-             "rr_augment_frames_jitter" if jitter is not None else "rr_augment_frames")
+    _C.call("rr_augment_frames_jitter" if jitter is not None else "rr_augment_frames", src, src.numel(), params, rects, rect_off,
+            taps, taps.shape[0], mean, std, *_jitter_args(jitter, b), out, b, out_h, out_w)
     return out
 
 
@@ -1714,19 +1639,19 @@ def augment_frames_pasted(src, params, rects, rect_off, taps, pastes, paste_off,
     calls) exist for timing one stage.  `jitter` (factors, gray_mean) selects rr_augment_frames_pasted_jitter: see
     augment_frames_pasted_jitter.  -> [B,3,out_h,out_w] in NHWC memory."""
     _C.require_cuda(src, params, rects, rect_off, taps, pastes, paste_off, mean, std)
-    assert src.dtype == torch.uint8 and src.is_contiguous() and src.dim() == 1
-    assert params.dtype == torch.int32 and params.is_contiguous() and params.shape[1] == AUGMENT_PARAMS
+    assert src.is_contiguous() and src.dim() == 1
+    assert params.is_contiguous() and params.shape[1] == AUGMENT_PARAMS
     b = params.shape[0]
-    assert rect_off.dtype == torch.int32 and rect_off.numel() == b + 1
-    assert paste_off.dtype == torch.int32 and paste_off.numel() == b + 1 and paste_off.is_contiguous()
-    assert taps.dtype == torch.int32 and taps.is_contiguous() and taps.shape[1] == 3
-    assert mean.dtype == torch.float32 and std.dtype == torch.float32 and mean.numel() == 3 and std.numel() == 3
+    assert rect_off.numel() == b + 1
+    assert paste_off.numel() == b + 1 and paste_off.is_contiguous()
+    assert taps.is_contiguous() and taps.shape[1] == 3
+    assert mean.numel() == 3 and std.numel() == 3
     if rects is not None and rects.numel() == 0:
         rects = None
-    assert rects is None or (rects.dtype == torch.int32 and rects.is_contiguous() and rects.shape[1] == 4)
+    assert rects is None or (rects.is_contiguous() and rects.shape[1] == 4)
     if pastes is None or pastes.numel() == 0:
         pastes = torch.zeros((1, PASTE_WORDS), dtype=torch.int32, device=src.device)
-    assert pastes.dtype == torch.int32 and pastes.is_contiguous() and pastes.shape[1] == PASTE_WORDS
+    assert pastes.is_contiguous() and pastes.shape[1] == PASTE_WORDS
     if work is None and canvas_pix is None:
         host = params.cpu()
         canvas_pix = int((host[:, 6].long() * host[:, 7].long()).max())
@@ -1736,13 +1661,11 @@ def augment_frames_pasted(src, params, rects, rect_off, taps, pastes, paste_off,
     canvas, scratch = work if work is not None else paste_workspace(b, canvas_pix, scratch_pix, src.device)
     canvas_pix, scratch_pix = canvas.shape[1], scratch.shape[1]
     assert canvas.shape == (b, canvas_pix, 3) and scratch.shape == (b, scratch_pix, 3) and canvas_pix % 4 == 0
-    assert canvas.dtype == scratch.dtype == torch.float32 and canvas.is_contiguous() and scratch.is_contiguous()
+    assert canvas.is_contiguous() and scratch.is_contiguous()
     out = empty_nhwc(b, 3, out_h, out_w, src.device)
-    entry = _C.fn("rr_augment_frames_pasted_jitter") if jitter is not None else _C.fn("rr_augment_frames_pasted")
-    _C.check(entry(_C.ptr(src), src.numel(), _C.ptr(params), _C.ptr(rects), _C.ptr(rect_off), _C.ptr(taps), taps.shape[0],
-                   _C.ptr(pastes), _C.ptr(paste_off), _C.ptr(mean), _C.ptr(std), *_jitter_ptrs(jitter, b), _C.ptr(canvas),
-                   canvas_pix, _C.ptr(scratch), scratch_pix, _C.ptr(out), b, out_h, out_w, int(stages), _C.stream()),
-             "rr_augment_frames_pasted_jitter" if jitter is not None else "rr_augment_frames_pasted")
+    _C.call("rr_augment_frames_pasted_jitter" if jitter is not None else "rr_augment_frames_pasted", src, src.numel(), params, rects,
+            rect_off, taps, taps.shape[0], pastes, paste_off, mean, std, *_jitter_args(jitter, b), canvas, canvas_pix, scratch,
+            scratch_pix, out, b, out_h, out_w, int(stages))
     return out
 
 
@@ -1758,17 +1681,16 @@ def jitter_gray_mean(src, params, factors, max_pixels=None, work=None):
     read back from the device records (a synchronisation the loader avoids by passing it).  -> (gray_mean int32 [B] =
     int(mean(L) + 0.5) of each brightness-adjusted frame, sums int64 [B] = the integer sums of L)."""
     _C.require_cuda(src, params, factors)
-    assert src.dtype == torch.uint8 and src.is_contiguous() and src.dim() == 1
-    assert params.dtype == torch.int32 and params.is_contiguous() and params.shape[1] == AUGMENT_PARAMS
+    assert src.is_contiguous() and src.dim() == 1
+    assert params.is_contiguous() and params.shape[1] == AUGMENT_PARAMS
     b = params.shape[0]
-    assert factors.dtype == torch.float32 and factors.is_contiguous() and factors.shape == (b, 3)
+    assert factors.is_contiguous() and factors.shape == (b, 3)
     if max_pixels is None:
         host = params.cpu()
         max_pixels = int((host[:, 4].long() * host[:, 5].long()).max())
     sums, gray = work if work is not None else jitter_workspace(b, src.device)
-    assert sums.dtype == torch.int64 and gray.dtype == torch.int32 and sums.numel() == b and gray.numel() == b
-    _C.check(_C.fn("rr_jitter_gray_mean")(_C.ptr(src), src.numel(), _C.ptr(params), _C.ptr(factors), _C.ptr(sums),
-                                          _C.ptr(gray), b, int(max_pixels), _C.stream()), "rr_jitter_gray_mean")
+    assert sums.numel() == b and gray.numel() == b
+    _C.call("rr_jitter_gray_mean", src, src.numel(), params, factors, sums, gray, b, int(max_pixels))
     return gray, sums
 
 
@@ -1795,9 +1717,7 @@ def refine_boxes(rois, reg, scores, clses, seg_off, scale, score_thr):
     nseg = seg_off.numel() - 1
     out6 = torch.empty((r, 6), dtype=torch.float32, device=rois.device)
     seg_len = torch.zeros(max(nseg, 0), dtype=torch.int32, device=rois.device)
-    _C.check(_C.fn("rr_refine_boxes")(_C.ptr(rois), _C.ptr(reg.contiguous()), _C.ptr(scores), _C.ptr(clses),
-                                      _C.ptr(seg_off), nseg, float(scale), float(score_thr), _C.ptr(out6),
-                                      _C.ptr(seg_len), _C.stream()), "rr_refine_boxes")
+    _C.call("rr_refine_boxes", rois, reg.contiguous(), scores, clses, seg_off, nseg, float(scale), float(score_thr), out6, seg_len)
     return out6, seg_len
 
 
@@ -1807,9 +1727,7 @@ def finalize_frames(boxes6, seg_off, n_out, nframes, segs_per_frame, max_frame_b
     [nframes+1] (device)."""
     out_off = seg_prefix(n_out)
     out6 = torch.empty_like(boxes6)
-    _C.check(_C.fn("rr_finalize_frames")(_C.ptr(boxes6), _C.ptr(seg_off), _C.ptr(n_out), _C.ptr(out_off), nframes,
-                                         segs_per_frame, int(max_frame_boxes), _C.ptr(out6), _C.stream()),
-             "rr_finalize_frames")
+    _C.call("rr_finalize_frames", boxes6, seg_off, n_out, out_off, nframes, segs_per_frame, int(max_frame_boxes), out6)
     return out6, out_off[::segs_per_frame]
 
 
@@ -1817,7 +1735,7 @@ def sort_rows_by_score(rows6):
     """[n,6] device rows -> a new tensor ordered by score descending (ties keep their input order)."""
     rows6 = rows6.contiguous()
     out = torch.empty_like(rows6)
-    _C.check(_C.fn("rr_sort_rows_by_score")(_C.ptr(rows6), rows6.shape[0], _C.ptr(out), _C.stream()), "rr_sort_rows_by_score")
+    _C.call("rr_sort_rows_by_score", rows6, rows6.shape[0], out)
     return out
 
 
@@ -1828,13 +1746,13 @@ def _prepare_frames(symbol, copies, frames_u8, mean, std, scale_factor):
     """The body of prepare_frames (copies = 1) and prepare_frames_pair (copies = 2): `copies` output images per frame."""
     import math
     _C.require_cuda(frames_u8, mean, std)
-    assert frames_u8.dtype == torch.uint8 and frames_u8.is_contiguous() and frames_u8.dim() == 4 and frames_u8.shape[3] == 3
-    assert mean.dtype == torch.float32 and std.dtype == torch.float32 and mean.numel() == 3 and std.numel() == 3
+    assert frames_u8.is_contiguous() and frames_u8.dim() == 4 and frames_u8.shape[3] == 3
+    assert mean.numel() == 3 and std.numel() == 3
     assert mean.is_contiguous() and std.is_contiguous()
     b, h, w, _ = frames_u8.shape
     oh, ow = int(math.floor(h * scale_factor)), int(math.floor(w * scale_factor))
     out = empty_nhwc(copies * b, 3, oh, ow, frames_u8.device)
-    _C.check(_C.fn(symbol)(_C.ptr(frames_u8), _C.ptr(mean), _C.ptr(std), _C.ptr(out), b, h, w, oh, ow, _C.stream()), symbol)
+    _C.call(symbol, frames_u8, mean, std, out, b, h, w, oh, ow)
     return out
 
 
@@ -1857,20 +1775,17 @@ def merge_scales(rois, reg, scores, clses, frame_off, div, merged, count, scale=
     """rr_merge_scales: one scale's stage-2 inputs (rois [R,5], reg [R,4], scores / clses [R]; frame_off int32 [B+1] row
     ranges) -> generate_bbox rows (x,y,w,h,score,cls+1), kept when score_thr is None or score > score_thr, x,y,w,h / div
     (IEEE), appended to merged [B,K,6] at count [B] (both updated in place, see merge_buffers)."""
-    _C.require_cuda(rois, reg, scores, clses, frame_off, merged, count)
     r = rois.shape[0]
     b, k, six = merged.shape
-    assert six == 6 and merged.dtype == torch.float32 and merged.is_contiguous() and 0 < k <= DETECT_MAX_ROWS
-    assert count.dtype == torch.int32 and count.numel() == b and count.is_contiguous()
-    assert frame_off.dtype == torch.int32 and frame_off.numel() == b + 1 and frame_off.is_contiguous()
-    assert rois.dtype == torch.float32 and rois.is_contiguous() and tuple(rois.shape) == (r, 5)
-    assert reg.dtype == torch.float32 and tuple(reg.shape) == (r, 4)
-    assert scores.dtype == torch.float32 and scores.is_contiguous() and scores.numel() == r
-    assert clses.dtype == torch.float32 and clses.is_contiguous() and clses.numel() == r
-    _C.check(_C.fn("rr_merge_scales")(_C.ptr(rois), _C.ptr(reg.contiguous()), _C.ptr(scores), _C.ptr(clses),
-                                      _C.ptr(frame_off), b, r, float(scale), float(div), int(score_thr is not None),
-                                      float(score_thr if score_thr is not None else 0.0), _C.ptr(merged), _C.ptr(count), k,
-                                      _C.stream()), "rr_merge_scales")
+    assert six == 6 and merged.is_contiguous() and 0 < k <= DETECT_MAX_ROWS
+    assert count.numel() == b and count.is_contiguous()
+    assert frame_off.numel() == b + 1 and frame_off.is_contiguous()
+    assert rois.is_contiguous() and tuple(rois.shape) == (r, 5)
+    assert tuple(reg.shape) == (r, 4)
+    assert scores.is_contiguous() and scores.numel() == r
+    assert clses.is_contiguous() and clses.numel() == r
+    _C.call("rr_merge_scales", rois, reg.contiguous(), scores, clses, frame_off, b, r, float(scale), float(div),
+            int(score_thr is not None), float(score_thr if score_thr is not None else 0.0), merged, count, k)
 
 
 def prepare_frames_pair(frames_u8, mean, std, scale_factor):
@@ -1883,14 +1798,13 @@ def merge_ctnet(rows, nframes, img_w, div, merged, count, pair=True, score_thr=0
     """rr_merge_ctnet: one scale's CenterNet rows [(2 if pair else 1)*nframes, k_in, 6] (decode_topk, box_mode=1) -> per
     frame the flipped image's rows (image nframes+f, x <- (img_w - x) - w) then the plain image's, kept when score >
     score_thr, x,y,w,h / div (IEEE), appended to merged [nframes,K,6] at count [nframes] (in place, see merge_buffers)."""
-    _C.require_cuda(rows, merged, count)
     b, k, six = merged.shape
-    assert b == nframes and six == 6 and merged.dtype == torch.float32 and merged.is_contiguous() and 0 < k <= DETECT_MAX_ROWS
-    assert count.dtype == torch.int32 and count.numel() == b and count.is_contiguous()
-    assert rows.dtype == torch.float32 and rows.is_contiguous() and rows.dim() == 3 and rows.shape[2] == 6
+    assert b == nframes and six == 6 and merged.is_contiguous() and 0 < k <= DETECT_MAX_ROWS
+    assert count.numel() == b and count.is_contiguous()
+    assert rows.is_contiguous() and rows.dim() == 3 and rows.shape[2] == 6
     assert rows.shape[0] == (2 if pair else 1) * nframes
-    _C.check(_C.fn("rr_merge_ctnet")(_C.ptr(rows), nframes, rows.shape[1], int(bool(pair)), float(img_w), float(div),
-                                     float(score_thr), _C.ptr(merged), _C.ptr(count), k, _C.stream()), "rr_merge_ctnet")
+    _C.call("rr_merge_ctnet", rows, nframes, rows.shape[1], int(bool(pair)), float(img_w), float(div), float(score_thr), merged,
+            count, k)
 
 
 def check_tiles(tiles, sizes, tile):
@@ -1951,8 +1865,7 @@ def prepare_tiles(frames, tiles, tile, zoom, mean, std, out=None):
     else:
         packed = torch.cat([fr.contiguous().view(-1) for fr in frames]) if len(frames) > 1 else frames[0].contiguous()
     _C.require_cuda(packed, mean, std, out)
-    assert packed.dtype == torch.uint8
-    assert mean.dtype == torch.float32 and std.dtype == torch.float32 and mean.numel() == 3 and std.numel() == 3
+    assert mean.numel() == 3 and std.numel() == 3
     assert mean.is_contiguous() and std.is_contiguous()
     oh, ow = int(math.floor(th * zoom)), int(math.floor(tw * zoom))
     if oh <= 0 or ow <= 0:
@@ -1968,9 +1881,7 @@ def prepare_tiles(frames, tiles, tile, zoom, mean, std, out=None):
     frame_base = torch.from_numpy(base).to(dev)
     frame_hw = torch.tensor(sizes, dtype=torch.int32).to(dev)
     tiles_dev = torch.from_numpy(table).to(dev)
-    _C.check(_C.fn("rr_prepare_tiles")(_C.ptr(packed), _C.ptr(frame_base), _C.ptr(frame_hw), len(sizes), _C.ptr(tiles_dev), t,
-                                       th, tw, oh, ow, _C.ptr(mean), _C.ptr(std), _C.ptr(out), _C.stream()),
-             "rr_prepare_tiles")
+    _C.call("rr_prepare_tiles", packed, frame_base, frame_hw, len(sizes), tiles_dev, t, th, tw, oh, ow, mean, std, out)
     return out
 
 
@@ -1988,10 +1899,10 @@ def merge_tiles(rows, count_in, tiles, sizes, tile, in_size, div, margin, merged
     _C.require_cuda(rows, count_in, merged, count)
     f, k, six = merged.shape
     t = table.shape[0]
-    assert f == len(sizes) and six == 6 and merged.dtype == torch.float32 and merged.is_contiguous() and 0 < k <= DETECT_MAX_ROWS
-    assert count.dtype == torch.int32 and count.numel() == f and count.is_contiguous()
-    assert rows.dtype == torch.float32 and rows.is_contiguous() and rows.dim() == 3 and rows.shape[0] == t and rows.shape[2] == 6
-    assert count_in.dtype == torch.int32 and count_in.numel() == t and count_in.is_contiguous()
+    assert f == len(sizes) and six == 6 and merged.is_contiguous() and 0 < k <= DETECT_MAX_ROWS
+    assert count.numel() == f and count.is_contiguous()
+    assert rows.is_contiguous() and rows.dim() == 3 and rows.shape[0] == t and rows.shape[2] == 6
+    assert count_in.numel() == t and count_in.is_contiguous()
     div, margin = float(np.float32(div)), float(np.float32(margin))
     if not div > 0 or not margin >= 0:
         raise ValueError("merge_tiles: zoom %r, margin %r" % (div, margin))
@@ -2003,9 +1914,8 @@ def merge_tiles(rows, count_in, tiles, sizes, tile, in_size, div, margin, merged
     off_dev = torch.from_numpy(tile_off).to(dev)
     hw_dev = torch.tensor([(int(h), int(w)) for h, w in sizes], dtype=torch.int32).to(dev)
     cin = count_in if t else torch.zeros(1, dtype=torch.int32, device=dev)
-    _C.check(_C.fn("rr_merge_tiles")(_C.ptr(rows), _C.ptr(cin), _C.ptr(tiles_dev), _C.ptr(off_dev), _C.ptr(hw_dev), f,
-                                     rows.shape[1], th, tw, int(in_size[0]), int(in_size[1]), div, margin, _C.ptr(merged),
-                                     _C.ptr(count), k, _C.stream()), "rr_merge_tiles")
+    _C.call("rr_merge_tiles", rows, cin, tiles_dev, off_dev, hw_dev, f, rows.shape[1], th, tw, int(in_size[0]), int(in_size[1]),
+            div, margin, merged, count, k)
 
 
 def sort_frames_by_score(rows6, count, out_off=None, xyxy=False):
@@ -2016,12 +1926,11 @@ def sort_frames_by_score(rows6, count, out_off=None, xyxy=False):
     b, k, six = rows6.shape
     if k > DETECT_MAX_ROWS:
         raise ValueError("sort_frames_by_score: %d rows per frame (limit %d)" % (k, DETECT_MAX_ROWS))
-    assert six == 6 and rows6.dtype == torch.float32 and rows6.is_contiguous()
-    assert count.dtype == torch.int32 and count.numel() == b and count.is_contiguous()
-    assert out_off is None or (out_off.dtype == torch.int32 and out_off.numel() == b + 1 and out_off.is_contiguous())
+    assert six == 6 and rows6.is_contiguous()
+    assert count.numel() == b and count.is_contiguous()
+    assert out_off is None or (out_off.numel() == b + 1 and out_off.is_contiguous())
     out = torch.empty((b * k, 6) if out_off is not None else (b, k, 6), dtype=torch.float32, device=rows6.device)
-    _C.check(_C.fn("rr_sort_frames_by_score")(_C.ptr(rows6), _C.ptr(count), _C.ptr(out_off), b, k, int(bool(xyxy)),
-                                              _C.ptr(out), b * k, _C.stream()), "rr_sort_frames_by_score")
+    _C.call("rr_sort_frames_by_score", rows6, count, out_off, b, k, int(bool(xyxy)), out, b * k)
     return out
 
 
@@ -2042,17 +1951,16 @@ def eval_match(dets, det_len, gts, gt_len, thresholds, cls_num=11):
     if not 1 <= t <= EVAL_MAX_THRESHOLDS:
         raise ValueError("eval_match: 1..%d thresholds, got %d" % (EVAL_MAX_THRESHOLDS, t))
     _C.require_cuda(dets, det_len, gts, gt_len, thresholds)
-    assert dets.dtype == torch.float32 and dets.is_contiguous() and gts.dtype == torch.float32 and gts.is_contiguous()
+    assert dets.is_contiguous() and gts.is_contiguous()
     assert gts.shape[0] == f and det_len.numel() == f and gt_len.numel() == f
-    assert det_len.dtype == torch.int32 and gt_len.dtype == torch.int32 and det_len.is_contiguous() and gt_len.is_contiguous()
-    assert thresholds.dtype == torch.float32 and thresholds.is_contiguous()
+    assert det_len.is_contiguous() and gt_len.is_contiguous()
+    assert thresholds.is_contiguous()
     dev = dets.device
     flag_bits = torch.empty((f, dmax), dtype=torch.int32, device=dev)
     counted = torch.empty((f, dmax), dtype=torch.uint8, device=dev)
     target_count = torch.empty((f, cls_num - 1), dtype=torch.int32, device=dev)
-    _C.check(_C.fn("rr_eval_match")(_C.ptr(dets), _C.ptr(det_len), _C.ptr(gts), _C.ptr(gt_len), _C.ptr(thresholds), f,
-                                    dmax, gmax, t, int(cls_num), _C.ptr(flag_bits), _C.ptr(counted),
-                                    _C.ptr(target_count), _C.stream()), "rr_eval_match")
+    _C.call("rr_eval_match", dets, det_len, gts, gt_len, thresholds, f, dmax, gmax, t, int(cls_num), flag_bits, counted,
+            target_count)
     return flag_bits, counted, target_count
 
 
@@ -2062,17 +1970,15 @@ def eval_ap(flag_bits, seg_off, target_count, in_img_count, t):
     -> ap float32 [t], rc float32 [] on the device."""
     _C.require_cuda(flag_bits, seg_off, target_count, in_img_count)
     c = target_count.numel()
-    assert flag_bits.dtype == torch.int32 and flag_bits.is_contiguous() and flag_bits.dim() == 1
-    assert seg_off.dtype == torch.int32 and seg_off.is_contiguous() and seg_off.numel() == c + 1
-    assert target_count.dtype == torch.int32 and in_img_count.dtype == torch.int32 and in_img_count.numel() == c
+    assert flag_bits.is_contiguous() and flag_bits.dim() == 1
+    assert seg_off.is_contiguous() and seg_off.numel() == c + 1
+    assert in_img_count.numel() == c
     assert target_count.is_contiguous() and in_img_count.is_contiguous()
     dev = flag_bits.device
     work = torch.empty(2 * c * int(t), dtype=torch.float32, device=dev)
     ap = torch.empty(int(t), dtype=torch.float32, device=dev)
     rc = torch.empty((), dtype=torch.float32, device=dev)
-    _C.check(_C.fn("rr_eval_ap")(_C.ptr(flag_bits), flag_bits.numel(), _C.ptr(seg_off), _C.ptr(target_count),
-                                 _C.ptr(in_img_count), c, int(t), _C.ptr(work), _C.ptr(ap), _C.ptr(rc), _C.stream()),
-             "rr_eval_ap")
+    _C.call("rr_eval_ap", flag_bits, flag_bits.numel(), seg_off, target_count, in_img_count, c, int(t), work, ap, rc)
     return ap, rc
 
 
@@ -2080,8 +1986,7 @@ def roi_spatial_order(rois, frame_off):
     """Per-frame spatial processing order of the packed RoI list (frame_off int32 [B+1], device) -> int32 [R]."""
     r = rois.shape[0]
     order = torch.empty(max(r, 1), dtype=torch.int32, device=rois.device)
-    _C.check(_C.fn("rr_roi_spatial_order")(_C.ptr(rois), _C.ptr(frame_off), frame_off.numel() - 1, _C.ptr(order),
-                                           _C.stream()), "rr_roi_spatial_order")
+    _C.call("rr_roi_spatial_order", rois, frame_off, frame_off.numel() - 1, order)
     return order[:r]
 
 
@@ -2091,8 +1996,7 @@ def roi_align_fwd(feat, rois, out_size, spatial_scale=1.0, sampling_ratio=-1, or
     r = rois.shape[0]
     ph, pw = out_size
     out = empty_nhwc(r, c, ph, pw, feat.device)
-    _C.check(_C.fn("rr_roi_align_fwd")(_C.ptr(feat), _C.ptr(rois), r, h, w, c, ph, pw, float(spatial_scale),
-                                       int(sampling_ratio), _C.ptr(order), _C.ptr(out), _C.stream()), "rr_roi_align_fwd")
+    _C.call("rr_roi_align_fwd", feat, rois, r, h, w, c, ph, pw, float(spatial_scale), int(sampling_ratio), order, out)
     return out
 
 
@@ -2101,8 +2005,7 @@ def roi_align_bwd(dout, rois, feat_shape, out_size, spatial_scale=1.0, sampling_
     r = rois.shape[0]
     ph, pw = out_size
     dfeat = empty_nhwc(b, c, h, w, dout.device)
-    _C.check(_C.fn("rr_roi_align_bwd")(_C.ptr(dout), _C.ptr(rois), r, b, h, w, c, ph, pw, float(spatial_scale),
-                                       int(sampling_ratio), _C.ptr(dfeat), _C.stream()), "rr_roi_align_bwd")
+    _C.call("rr_roi_align_bwd", dout, rois, r, b, h, w, c, ph, pw, float(spatial_scale), int(sampling_ratio), dfeat)
     return dfeat
 
 
@@ -2120,14 +2023,12 @@ def dcn_fwd(x, offset, mask, w, bias, stride, pad, dilation, dg, bf16=False):
     y = empty_nhwc(n, k, p, q, x.device)
     if bf16 and _DCN_WPACK:
         # weights re-packed to bf16 inside the call (one small kernel): the B operand then reaches LDS by DMA
-        wpack = torch.empty(_C.fn("rr_dcn_wpack_bytes")(c, k, r, s), dtype=torch.uint8, device=x.device)
-        _C.check(_C.fn("rr_dcn_fwd_bf16_packed")(_C.ptr(x), _C.ptr(offset), _C.ptr(mask), _C.ptr(w), _C.ptr(bias), _C.ptr(y),
-                                                 n, h, wd, c, k, r, s, stride, pad[0], pad[1], dilation, dg, _C.ptr(wpack),
-                                                 _C.stream()), "rr_dcn_fwd_bf16_packed")
+        wpack = torch.empty(_C.call("rr_dcn_wpack_bytes", c, k, r, s), dtype=torch.uint8, device=x.device)
+        _C.call("rr_dcn_fwd_bf16_packed", x, offset, mask, w, bias, y, n, h, wd, c, k, r, s, stride, pad[0], pad[1], dilation, dg,
+                wpack)
         return y
     name = "rr_dcn_fwd_bf16" if bf16 else "rr_dcn_fwd"
-    _C.check(_C.fn(name)(_C.ptr(x), _C.ptr(offset), _C.ptr(mask), _C.ptr(w), _C.ptr(bias), _C.ptr(y), n, h, wd,
-                         c, k, r, s, stride, pad[0], pad[1], dilation, dg, _C.stream()), name)
+    _C.call(name, x, offset, mask, w, bias, y, n, h, wd, c, k, r, s, stride, pad[0], pad[1], dilation, dg)
     return y
 
 
@@ -2135,8 +2036,7 @@ def dcn_im2col(x, offset, mask, r, s, stride, pad, dilation, dg):
     n, c, h, wd = x.shape
     m = offset.shape[0] * offset.shape[2] * offset.shape[3]
     col = torch.empty((1, m, 1, r * s * c), dtype=torch.float32, device=x.device).permute(0, 3, 1, 2)
-    _C.check(_C.fn("rr_dcn_im2col")(_C.ptr(x), _C.ptr(offset), _C.ptr(mask), _C.ptr(col), n, h, wd, c, r, s, stride,
-                                    pad[0], pad[1], dilation, dg, _C.stream()), "rr_dcn_im2col")
+    _C.call("rr_dcn_im2col", x, offset, mask, col, n, h, wd, c, r, s, stride, pad[0], pad[1], dilation, dg)
     return col                                           # logical [1, r*s*c, M, 1], memory [M][r*s*c]
 
 
@@ -2146,15 +2046,13 @@ def dcn_col2im(x, offset, mask, dcol, r, s, stride, pad, dilation, dg):
     doff = torch.empty_like(offset)
     dmask = torch.empty_like(mask)
     assert doff.stride() == offset.stride() and dmask.stride() == mask.stride()
-    _C.check(_C.fn("rr_dcn_col2im")(_C.ptr(x), _C.ptr(offset), _C.ptr(mask), _C.ptr(dcol), _C.ptr(dx), _C.ptr(doff),
-                                    _C.ptr(dmask), n, h, wd, c, r, s, stride, pad[0], pad[1], dilation, dg,
-                                    _C.stream()), "rr_dcn_col2im")
+    _C.call("rr_dcn_col2im", x, offset, mask, dcol, dx, doff, dmask, n, h, wd, c, r, s, stride, pad[0], pad[1], dilation, dg)
     return dx, doff, dmask
 
 
 def dcn_fused_bwd_supported(c, k, r, s, stride, dg, dilation=1):
     """Whether rr_dcn_wgrad / rr_dcn_dgrad take a layer of this shape (else: the column path)."""
-    return bool(_C.fn("rr_dcn_fused_bwd_supported_dil")(c, k, r, s, stride, dilation, dg))
+    return bool(_C.call("rr_dcn_fused_bwd_supported_dil", c, k, r, s, stride, dilation, dg))
 
 
 def dcn_wgrad(x, offset, mask, dy, dw, stride, pad, dilation, dg, bf16=False, dy_img=None):
@@ -2165,13 +2063,11 @@ def dcn_wgrad(x, offset, mask, dy, dw, stride, pad, dilation, dg, bf16=False, dy
     n, c, h, wd = x.shape
     k, _, r, s = dw.shape
     if bf16 and dy_img is not None:
-        _C.check(_C.fn("rr_dcn_wgrad_bf16_img")(_C.ptr(x), _C.ptr(offset), _C.ptr(mask), _C.ptr(dy), _C.ptr(dy_img), _C.ptr(dw), n, h,
-                                                wd, c, k, r, s, stride, pad[0], pad[1], dilation, dg, _C.stream()),
-                 "rr_dcn_wgrad_bf16_img")
+        _C.call("rr_dcn_wgrad_bf16_img", x, offset, mask, dy, dy_img, dw, n, h, wd, c, k, r, s, stride, pad[0], pad[1], dilation,
+                dg)
         return dw
     name = "rr_dcn_wgrad_bf16" if bf16 else "rr_dcn_wgrad"
-    _C.check(_C.fn(name)(_C.ptr(x), _C.ptr(offset), _C.ptr(mask), _C.ptr(dy), _C.ptr(dw), n, h, wd, c, k, r, s,
-                         stride, pad[0], pad[1], dilation, dg, _C.stream()), name)
+    _C.call(name, x, offset, mask, dy, dw, n, h, wd, c, k, r, s, stride, pad[0], pad[1], dilation, dg)
     return dw
 
 
@@ -2198,28 +2094,23 @@ def dcn_dgrad(x, offset, mask, w, dy, stride, pad, dilation, dg, bf16=False, out
     if bf16 and _DCN_WPACK:
         # both sweep operands by LDS-DMA: weights packed to bf16 inside the call; dY = its producer's bf16 image when there is
         # one (the heads' 1x1 data gradient), else rounded once into the workspace
-        ws = torch.empty(_C.fn("rr_dcn_dgrad_ws_bytes")(dy.shape[0], dy.shape[2], dy.shape[3], c, k, r, s, int(img is not None)),
+        ws = torch.empty(_C.call("rr_dcn_dgrad_ws_bytes", dy.shape[0], dy.shape[2], dy.shape[3], c, k, r, s, int(img is not None)),
                          dtype=torch.uint8, device=x.device)
-        _C.check(_C.fn("rr_dcn_dgrad_bf16_packed")(_C.ptr(x), _C.ptr(offset), _C.ptr(mask), _C.ptr(w), _C.ptr(dy),
-                                                   _C.ptr(img) if img is not None else None, _C.ptr(dx), _C.ptr(doff), _C.ptr(dmask),
-                                                   n, h, wd, c, k, r, s, stride, pad[0], pad[1], dilation, dg, int(out is not None),
-                                                   _C.ptr(ws), _C.stream()), "rr_dcn_dgrad_bf16_packed")
+        _C.call("rr_dcn_dgrad_bf16_packed", x, offset, mask, w, dy, img, dx, doff, dmask, n, h, wd, c, k, r, s, stride, pad[0], pad[1],
+                dilation, dg, int(out is not None), ws)
         return dx, doff, dmask
     if img is not None:
         # dY's producer already left its bf16 image (the heads' 1x1 data gradient): no conversion pass
-        _C.check(_C.fn("rr_dcn_dgrad_bf16_img")(_C.ptr(x), _C.ptr(offset), _C.ptr(mask), _C.ptr(w), _C.ptr(dy), _C.ptr(img), _C.ptr(dx),
-                                                _C.ptr(doff), _C.ptr(dmask), n, h, wd, c, k, r, s, stride, pad[0], pad[1],
-                                                dilation, dg, _C.stream()), "rr_dcn_dgrad_bf16_img")
+        _C.call("rr_dcn_dgrad_bf16_img", x, offset, mask, w, dy, img, dx, doff, dmask, n, h, wd, c, k, r, s, stride, pad[0], pad[1],
+                dilation, dg)
         return dx, doff, dmask
     if bf16:
         # dY rounded to bf16 once per call (caller scratch): the sweep's eight re-reads of a block's dY tile stay in L2
-        dyb = torch.empty(_C.fn("rr_dcn_dyb_bytes")(dy.shape[0], dy.shape[2], dy.shape[3], k), dtype=torch.uint8, device=x.device)
-        _C.check(_C.fn("rr_dcn_dgrad_bf16_ws")(_C.ptr(x), _C.ptr(offset), _C.ptr(mask), _C.ptr(w), _C.ptr(dy), _C.ptr(dx),
-                                               _C.ptr(doff), _C.ptr(dmask), n, h, wd, c, k, r, s, stride, pad[0], pad[1],
-                                               dilation, dg, _C.ptr(dyb), _C.stream()), "rr_dcn_dgrad_bf16_ws")
+        dyb = torch.empty(_C.call("rr_dcn_dyb_bytes", dy.shape[0], dy.shape[2], dy.shape[3], k), dtype=torch.uint8, device=x.device)
+        _C.call("rr_dcn_dgrad_bf16_ws", x, offset, mask, w, dy, dx, doff, dmask, n, h, wd, c, k, r, s, stride, pad[0], pad[1],
+                dilation, dg, dyb)
         return dx, doff, dmask
-    _C.check(_C.fn("rr_dcn_dgrad")(_C.ptr(x), _C.ptr(offset), _C.ptr(mask), _C.ptr(w), _C.ptr(dy), _C.ptr(dx), _C.ptr(doff),
-                                   _C.ptr(dmask), n, h, wd, c, k, r, s, stride, pad[0], pad[1], dilation, dg, _C.stream()), "rr_dcn_dgrad")
+    _C.call("rr_dcn_dgrad", x, offset, mask, w, dy, dx, doff, dmask, n, h, wd, c, k, r, s, stride, pad[0], pad[1], dilation, dg)
     return dx, doff, dmask
 
 
@@ -2229,15 +2120,14 @@ def dcn_split_fwd(om):
     n, ch, p, q = om.shape
     t = ch // 3
     offset, mask = empty_nhwc(n, 2 * t, p, q, om.device), empty_nhwc(n, t, p, q, om.device)
-    _C.check(_C.fn("rr_dcn_split_fwd")(_C.ptr(om), n * p * q, t, _C.ptr(offset), _C.ptr(mask), _C.stream()), "rr_dcn_split_fwd")
+    _C.call("rr_dcn_split_fwd", om, n * p * q, t, offset, mask)
     return offset, mask
 
 
 def dcn_split_bwd(doffset, dmask, mask):
     n, t, p, q = mask.shape
     dom = empty_nhwc(n, 3 * t, p, q, mask.device)
-    _C.check(_C.fn("rr_dcn_split_bwd")(_C.ptr(doffset), _C.ptr(dmask), _C.ptr(mask), n * p * q, t, _C.ptr(dom), _C.stream()),
-             "rr_dcn_split_bwd")
+    _C.call("rr_dcn_split_bwd", doffset, dmask, mask, n * p * q, t, dom)
     return dom
 
 
@@ -2251,9 +2141,8 @@ def dcn_psroi_fwd(x, rois, trans, no_trans, spatial_scale, output_dim, group_siz
     out = empty_nhwc(n, output_dim, pooled_size, pooled_size, x.device)
     count = empty_nhwc(n, output_dim, pooled_size, pooled_size, x.device)
     tc = 0 if no_trans else trans.shape[1]
-    _C.check(_C.fn("rr_dcn_psroi_fwd")(_C.ptr(x), _C.ptr(rois), _C.ptr(None if no_trans else trans), n, h, w, c, int(no_trans),
-                                       float(spatial_scale), output_dim, group_size, pooled_size, part_size, sample_per_part,
-                                       float(trans_std), tc, _C.ptr(out), _C.ptr(count), _C.stream()), "rr_dcn_psroi_fwd")
+    _C.call("rr_dcn_psroi_fwd", x, rois, None if no_trans else trans, n, h, w, c, int(no_trans), float(spatial_scale), output_dim,
+            group_size, pooled_size, part_size, sample_per_part, float(trans_std), tc, out, count)
     return out, count
 
 
@@ -2265,10 +2154,8 @@ def dcn_psroi_bwd(dout, x, rois, trans, count, no_trans, spatial_scale, output_d
     dx = empty_nhwc(b, c, h, w, x.device)
     dtrans = None if no_trans else torch.empty_like(trans)
     tc = 0 if no_trans else trans.shape[1]
-    _C.check(_C.fn("rr_dcn_psroi_bwd")(_C.ptr(dout), _C.ptr(x), _C.ptr(rois), _C.ptr(None if no_trans else trans), _C.ptr(count),
-                                       n, b, h, w, c, int(no_trans), float(spatial_scale), output_dim, group_size, pooled_size,
-                                       part_size, sample_per_part, float(trans_std), tc, _C.ptr(dx), _C.ptr(dtrans),
-                                       _C.stream()), "rr_dcn_psroi_bwd")
+    _C.call("rr_dcn_psroi_bwd", dout, x, rois, None if no_trans else trans, count, n, b, h, w, c, int(no_trans),
+            float(spatial_scale), output_dim, group_size, pooled_size, part_size, sample_per_part, float(trans_std), tc, dx, dtrans)
     return dx, dtrans
 
 
@@ -2278,42 +2165,40 @@ def dcn_psroi_bwd(dout, x, rois, trans, count, no_trans, spatial_scale, output_d
 def maxpool3x3s2_fwd(x):
     """x NHWC [n,c,h,w] -> (y, idx): MaxPool2d(3, 2, 1) and the winning tap (uint8, 0..8) of every output element."""
     _C.require_cuda(x)
-    assert is_nhwc(x) and x.dtype == torch.float32
+    assert is_nhwc(x)
     n, c, h, w = x.shape
     oh, ow = (h - 1) // 2 + 1, (w - 1) // 2 + 1
     y = empty_nhwc(n, c, oh, ow, x.device)
     idx = empty_nhwc(n, c, oh, ow, x.device, dtype=torch.uint8)
-    _C.check(_C.fn("rr_maxpool3x3s2_fwd")(_C.ptr(x), _C.ptr(y), _C.ptr(idx), n, h, w, c, _C.stream()), "rr_maxpool3x3s2_fwd")
+    _C.call("rr_maxpool3x3s2_fwd", x, y, idx, n, h, w, c)
     return y, idx
 
 
 def maxpool3x3s2_bwd(dy, idx, x_shape):
     n, c, h, w = x_shape
-    assert is_nhwc(dy) and is_nhwc(idx) and dy.shape == idx.shape and dy.dtype == torch.float32
+    assert is_nhwc(dy) and is_nhwc(idx) and dy.shape == idx.shape
     assert tuple(dy.shape) == (n, c, (h - 1) // 2 + 1, (w - 1) // 2 + 1)
     dx = empty_nhwc(n, c, h, w, dy.device)
-    _C.check(_C.fn("rr_maxpool3x3s2_bwd")(_C.ptr(dy), _C.ptr(idx), _C.ptr(dx), n, h, w, c, _C.stream()), "rr_maxpool3x3s2_bwd")
+    _C.call("rr_maxpool3x3s2_bwd", dy, idx, dx, n, h, w, c)
     return dx
 
 
 def bilinear_add_fwd(x, y):
     """y + F.interpolate(x, size(y), mode='bilinear', align_corners=False); both NHWC."""
     _C.require_cuda(x, y)
-    assert is_nhwc(x) and is_nhwc(y) and x.shape[:2] == y.shape[:2] and x.dtype == y.dtype == torch.float32
+    assert is_nhwc(x) and is_nhwc(y) and x.shape[:2] == y.shape[:2]
     n, c, ih, iw = x.shape
     oh, ow = y.shape[2], y.shape[3]
     out = empty_nhwc(n, c, oh, ow, x.device)
-    _C.check(_C.fn("rr_bilinear_add_fwd")(_C.ptr(x), _C.ptr(y), _C.ptr(out), n, ih, iw, oh, ow, c, _C.stream()),
-             "rr_bilinear_add_fwd")
+    _C.call("rr_bilinear_add_fwd", x, y, out, n, ih, iw, oh, ow, c)
     return out
 
 
 def bilinear_add_bwd(dout, x_shape):
     n, c, ih, iw = x_shape
-    assert is_nhwc(dout) and dout.shape[0] == n and dout.shape[1] == c and dout.dtype == torch.float32
+    assert is_nhwc(dout) and dout.shape[0] == n and dout.shape[1] == c
     dx = empty_nhwc(n, c, ih, iw, dout.device)
-    _C.check(_C.fn("rr_bilinear_add_bwd")(_C.ptr(dout), _C.ptr(dx), n, ih, iw, dout.shape[2], dout.shape[3], c, _C.stream()),
-             "rr_bilinear_add_bwd")
+    _C.call("rr_bilinear_add_bwd", dout, dx, n, ih, iw, dout.shape[2], dout.shape[3], c)
     return dx
 
 
@@ -2336,15 +2221,14 @@ def retina_assign(annos, anchors, num_classes):
         "target": torch.empty((b, a, 4), dtype=torch.float32, device=dev),
         "npos": torch.empty((b,), dtype=torch.int32, device=dev),
     }
-    _C.check(_C.fn("rr_retina_assign")(_C.ptr(annos), _C.ptr(anchors), b, m, a, int(num_classes), _C.ptr(out["state"]),
-                                       _C.ptr(out["argmax"]), _C.ptr(out["max_iou"]), _C.ptr(out["cls"]),
-                                       _C.ptr(out["target"]), _C.ptr(out["npos"]), _C.stream()), "rr_retina_assign")
+    _C.call("rr_retina_assign", annos, anchors, b, m, a, int(num_classes), out["state"], out["argmax"], out["max_iou"], out["cls"],
+            out["target"], out["npos"])
     return out
 
 
 def _retina_loss_args(logits, loc, asg):
     assert logits.dim() == 3 and loc.dim() == 3 and loc.shape[2] == 4 and logits.shape[:2] == loc.shape[:2]
-    assert logits.is_contiguous() and loc.is_contiguous() and logits.dtype == loc.dtype == torch.float32
+    assert logits.is_contiguous() and loc.is_contiguous()
     b, a, c = logits.shape
     assert tuple(asg["state"].shape) == (b, a) and tuple(asg["target"].shape) == (b, a, 4)
     return b, a, c
@@ -2354,23 +2238,19 @@ def retina_loss_fwd(logits, loc, asg):
     """-> losses [2] = (classification, regression) of the criterion, bit-identical run to run."""
     _C.require_cuda(logits, loc)
     b, a, c = _retina_loss_args(logits, loc, asg)
-    nblk = _C.fn("rr_retina_loss_blocks")(a, c)
+    nblk = _C.call("rr_retina_loss_blocks", a, c)
     partial = torch.empty((b, nblk, 2), dtype=torch.float64, device=logits.device)
     losses = torch.empty(2, dtype=torch.float32, device=logits.device)
-    _C.check(_C.fn("rr_retina_loss_fwd")(_C.ptr(logits), _C.ptr(loc), _C.ptr(asg["state"]), _C.ptr(asg["cls"]),
-                                         _C.ptr(asg["target"]), _C.ptr(asg["npos"]), b, a, c, _C.ptr(partial), _C.ptr(losses),
-                                         _C.stream()), "rr_retina_loss_fwd")
+    _C.call("rr_retina_loss_fwd", logits, loc, asg["state"], asg["cls"], asg["target"], asg["npos"], b, a, c, partial, losses)
     return losses
 
 
 def retina_loss_bwd(logits, loc, asg, gout):
     """gout [2] (device) -> (d logits [B,A,C], d loc [B,A,4])."""
     b, a, c = _retina_loss_args(logits, loc, asg)
-    assert gout.is_cuda and gout.numel() == 2 and gout.dtype == torch.float32 and gout.is_contiguous()
+    assert gout.numel() == 2 and gout.is_contiguous()
     dlogits, dloc = torch.empty_like(logits), torch.empty_like(loc)
-    _C.check(_C.fn("rr_retina_loss_bwd")(_C.ptr(logits), _C.ptr(loc), _C.ptr(asg["state"]), _C.ptr(asg["cls"]),
-                                         _C.ptr(asg["target"]), _C.ptr(asg["npos"]), _C.ptr(gout), b, a, c, _C.ptr(dlogits),
-                                         _C.ptr(dloc), _C.stream()), "rr_retina_loss_bwd")
+    _C.call("rr_retina_loss_bwd", logits, loc, asg["state"], asg["cls"], asg["target"], asg["npos"], gout, b, a, c, dlogits, dloc)
     return dlogits, dloc
 
 
@@ -2383,8 +2263,7 @@ def retina_decode(logits, loc, anchors, score_thr=0.1):
     rows = torch.zeros((b, a, 6), dtype=torch.float32, device=logits.device)
     count = torch.zeros((b,), dtype=torch.int32, device=logits.device)
     if a > 0:
-        _C.check(_C.fn("rr_retina_decode")(_C.ptr(logits), _C.ptr(loc), _C.ptr(anchors), b, a, c, float(score_thr),
-                                           _C.ptr(rows), _C.ptr(count), _C.stream()), "rr_retina_decode")
+        _C.call("rr_retina_decode", logits, loc, anchors, b, a, c, float(score_thr), rows, count)
     return rows, count
 
 
@@ -2403,13 +2282,11 @@ def retina_decode_frames(logits, loc, anchors, score_thr=0.1, k=None, rows=None)
     k = a if k is None else int(k)
     if rows is None:
         rows = torch.zeros((b, k, 6), dtype=torch.float32, device=logits.device)
-    assert tuple(rows.shape) == (b, k, 6) and rows.dtype == torch.float32 and rows.is_contiguous()
+    assert tuple(rows.shape) == (b, k, 6) and rows.is_contiguous()
     count = torch.zeros((b,), dtype=torch.int32, device=logits.device)
     if a > 0 and b > 0:
-        ws = torch.empty(_C.fn("rr_retina_decode_frames_workspace_bytes")(b, a), dtype=torch.uint8, device=logits.device)
-        _C.check(_C.fn("rr_retina_decode_frames")(_C.ptr(logits), _C.ptr(loc), _C.ptr(anchors), b, a, c, float(score_thr),
-                                                  _C.ptr(rows), k, _C.ptr(count), _C.ptr(ws), _C.stream()),
-                 "rr_retina_decode_frames")
+        ws = torch.empty(_C.call("rr_retina_decode_frames_workspace_bytes", b, a), dtype=torch.uint8, device=logits.device)
+        _C.call("rr_retina_decode_frames", logits, loc, anchors, b, a, c, float(score_thr), rows, k, count, ws)
     return rows, count
 
 
@@ -2419,8 +2296,8 @@ def nms_frames(rows6, frame_off, max_rows, thresh, inclusive=False):
     out_off), frame_off int32 [B+1], max_rows >= the longest frame, R >= B * max_rows.
     -> (keep int32 [R]: keep[frame_off[f] + j] = j-th kept row of frame f, local to the frame; kept int32 [B])."""
     _C.require_cuda(rows6, frame_off)
-    assert rows6.dim() == 2 and rows6.shape[1] == 6 and rows6.dtype == torch.float32 and rows6.is_contiguous()
-    assert frame_off.dtype == torch.int32 and frame_off.dim() == 1 and frame_off.numel() >= 1 and frame_off.is_contiguous()
+    assert rows6.dim() == 2 and rows6.shape[1] == 6 and rows6.is_contiguous()
+    assert frame_off.dim() == 1 and frame_off.numel() >= 1 and frame_off.is_contiguous()
     b, max_rows = frame_off.numel() - 1, int(max_rows)
     if not 0 <= max_rows <= DETECT_MAX_ROWS:
         raise ValueError("nms_frames: %d rows per frame (limit %d)" % (max_rows, DETECT_MAX_ROWS))
@@ -2428,9 +2305,8 @@ def nms_frames(rows6, frame_off, max_rows, thresh, inclusive=False):
     dev = rows6.device
     keep = torch.empty(rows6.shape[0], dtype=torch.int32, device=dev)
     kept = torch.zeros(b, dtype=torch.int32, device=dev)
-    ws = torch.empty(_C.fn("rr_nms_frames_workspace_bytes")(b, max_rows), dtype=torch.uint8, device=dev)
-    _C.check(_C.fn("rr_nms_frames")(_C.ptr(rows6), _C.ptr(frame_off), b, max_rows, float(thresh),
-                                    int(bool(inclusive)), _C.ptr(ws), _C.ptr(keep), _C.ptr(kept), _C.stream()), "rr_nms_frames")
+    ws = torch.empty(_C.call("rr_nms_frames_workspace_bytes", b, max_rows), dtype=torch.uint8, device=dev)
+    _C.call("rr_nms_frames", rows6, frame_off, b, max_rows, float(thresh), int(bool(inclusive)), ws, keep, kept)
     return keep, kept
 
 
@@ -2439,15 +2315,14 @@ def pack_frames(rows6, frame_off, keep, kept, max_rows, out_rows=None):
     int32 [B+1] = exclusive prefix of kept).  out_rows defaults to rows6's row count; the caller slices by out_off[-1]."""
     _C.require_cuda(rows6, frame_off, keep, kept)
     b, max_rows = frame_off.numel() - 1, int(max_rows)
-    assert rows6.dim() == 2 and rows6.shape[1] == 6 and rows6.dtype == torch.float32 and rows6.is_contiguous()
-    assert keep.dtype == torch.int32 and keep.numel() == rows6.shape[0] and keep.is_contiguous()
-    assert kept.dtype == torch.int32 and kept.numel() == b and kept.is_contiguous()
-    assert frame_off.dtype == torch.int32 and frame_off.is_contiguous() and rows6.shape[0] >= b * max_rows
+    assert rows6.dim() == 2 and rows6.shape[1] == 6 and rows6.is_contiguous()
+    assert keep.numel() == rows6.shape[0] and keep.is_contiguous()
+    assert kept.numel() == b and kept.is_contiguous()
+    assert frame_off.is_contiguous() and rows6.shape[0] >= b * max_rows
     out_rows = rows6.shape[0] if out_rows is None else int(out_rows)
     out6 = torch.empty((out_rows, 6), dtype=torch.float32, device=rows6.device)
     out_off = torch.empty(b + 1, dtype=torch.int32, device=rows6.device)
-    _C.check(_C.fn("rr_pack_frames")(_C.ptr(rows6), _C.ptr(frame_off), _C.ptr(keep), _C.ptr(kept), b, max_rows, _C.ptr(out6),
-                                     out_rows, _C.ptr(out_off), _C.stream()), "rr_pack_frames")
+    _C.call("rr_pack_frames", rows6, frame_off, keep, kept, b, max_rows, out6, out_rows, out_off)
     return out6, out_off
 
 
@@ -2487,13 +2362,11 @@ def kmeans_lloyd(X, init, tol=1e-4, max_iter=10000, check_every=16):
     inertia = torch.zeros((r,), dtype=torch.float64, device=dev)
     iters = torch.zeros((r,), dtype=torch.int32, device=dev)
     flags = torch.zeros((r,), dtype=torch.int32, device=dev)
-    ws = torch.empty(_C.fn("rr_kmeans_workspace_bytes")(n, m, k, r), dtype=torch.uint8, device=dev)
-    steps = _C.fn("rr_kmeans_steps")
+    ws = torch.empty(_C.call("rr_kmeans_workspace_bytes", n, m, k, r), dtype=torch.uint8, device=dev)
     left = max_iter
     while left > 0:
         ns = min(check_every, left)
-        _C.check(steps(_C.ptr(X), n, m, k, r, _C.ptr(centres), _C.ptr(labels), _C.ptr(counts), _C.ptr(inertia), _C.ptr(iters),
-                       _C.ptr(flags), float(tol), max_iter, ns, _C.ptr(ws), _C.stream()), "rr_kmeans_steps")
+        _C.call("rr_kmeans_steps", X, n, m, k, r, centres, labels, counts, inertia, iters, flags, float(tol), max_iter, ns, ws)
         left -= ns
         if bool(flags.cpu().numpy().all()):                  # the one host read per `check_every` steps
             break
