@@ -1,4 +1,4 @@
-"""ctypes binding of librrnet_hip.so (include/rrnet_hip.h).
+"""ctypes binding of librrnet_hip.so (include/rrnet_hip.h, and a kernel family's companion header beside it: Family).
 
 The product path has no CPU fallback: if the HIP library is missing or an entry point is
 absent, importing/using an op raises — loudly — instead of computing something else."""
@@ -62,16 +62,10 @@ class Signature(tuple):
     pointees = ()
 
 
-def header_signatures():
-    """Parses include/rrnet_hip.h (shipped next to the library as rrnet_amd/rrnet_hip.h when
-    installed, otherwise <repo>/include) -> {name: Signature = (restype, [argtypes])}.  The header is the
-    single source of truth for the ABI; pointers map to void* in argtypes, and the signature's `.pointees`
-    keeps what each one points to."""
+def _parse_header(fname):
+    """Parses include/<fname> (shipped next to the library as rrnet_amd/<fname> when installed) -> {name: Signature}."""
     import re
-    global _SIGS
-    if _SIGS is not None:
-        return _SIGS
-    cands = [os.path.join(_HERE, "rrnet_hip.h"), os.path.join(os.path.dirname(_HERE), "include", "rrnet_hip.h")]
+    cands = [os.path.join(_HERE, fname), os.path.join(os.path.dirname(_HERE), "include", fname)]
     path = next(p for p in cands if os.path.exists(p))
     text = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
     sigs = {}
@@ -92,19 +86,57 @@ def header_signatures():
                     pointees.append("hipStream_t" if toks[0] == "hipStream_t" else None)
         sigs[name] = Signature((restype, argtypes))
         sigs[name].pointees = tuple(pointees)
-    _SIGS = sigs
     return sigs
 
 
+def header_signatures():
+    """Parses include/rrnet_hip.h (shipped next to the library as rrnet_amd/rrnet_hip.h when
+    installed, otherwise <repo>/include) -> {name: Signature = (restype, [argtypes])}.  The header is the
+    single source of truth for the ABI; pointers map to void* in argtypes, and the signature's `.pointees`
+    keeps what each one points to."""
+    global _SIGS
+    if _SIGS is None:
+        _SIGS = _parse_header(MAIN_HEADER)
+    return _SIGS
+
+
+MAIN_HEADER = "rrnet_hip.h"
+# Companion headers: a kernel family with a header of its own beside rrnet_hip.h (same grammar, same library, same rules).
+# header_signatures() stays the main header's table; a family's entries are reached through its Family object.
+COMPANION_HEADERS = ("rrnet_hip_se.h",)
+_FAMILY_SIGS = {}
+
+
+def family_signatures(header):
+    """{name: Signature} of a companion header (parsed once)."""
+    if header not in COMPANION_HEADERS:
+        raise RRNetHipError("%s is not a header of this library (%s)" % (header, ", ".join((MAIN_HEADER,) + COMPANION_HEADERS)))
+    if header not in _FAMILY_SIGS:
+        _FAMILY_SIGS[header] = _parse_header(header)
+    return _FAMILY_SIGS[header]
+
+
+def declared(name):
+    """-> (Signature, header that declares `name`), or (None, None)."""
+    sig = header_signatures().get(name)
+    if sig is not None:
+        return sig, MAIN_HEADER
+    for header in COMPANION_HEADERS:
+        sig = family_signatures(header).get(name)
+        if sig is not None:
+            return sig, header
+    return None, None
+
+
 def fn(name, argtypes=None, restype=None):
-    """Entry point `name` with the prototype declared in include/rrnet_hip.h."""
+    """Entry point `name` with the prototype declared in include/rrnet_hip.h (or a companion header)."""
     f = getattr(lib(), name, None)
     if f is None:
         raise RRNetHipError("librrnet_hip.so does not export %s (stale build?)" % name)
     if f.argtypes is None:
-        sig = header_signatures().get(name)
+        sig, _ = declared(name)
         if sig is None:
-            raise RRNetHipError("%s is not declared in include/rrnet_hip.h" % name)
+            raise RRNetHipError("%s is not declared in include/%s" % (name, " or include/".join((MAIN_HEADER,) + COMPANION_HEADERS)))
         f.restype, f.argtypes = sig[0], sig[1]
     return f
 
@@ -136,9 +168,9 @@ _PLANS = {}
 def _plan(name):
     """name -> (per caller argument the admitted dtypes | None | _NUMBER, stream appended?, host tensors allowed?,
     the return value is a status?), from the header, built once per entry."""
-    sig = header_signatures().get(name)
+    sig, _ = declared(name)
     if sig is None:
-        raise RRNetHipError("%s is not declared in include/rrnet_hip.h" % name)
+        raise RRNetHipError("%s is not declared in include/%s" % (name, " or include/".join((MAIN_HEADER,) + COMPANION_HEADERS)))
     kinds = sig.pointees
     with_stream = bool(kinds) and kinds[-1] == "hipStream_t"
     slots = tuple(_NUMBER if k is None else POINTEE_DTYPES[k] for k in (kinds[:-1] if with_stream else kinds))
@@ -167,7 +199,7 @@ def call(name, *args):
                 raise RRNetHipError(_NO_CPU % a.device)
             if admits is not None and a.dtype not in admits:
                 raise RRNetHipError("%s: argument %d is a %s tensor, include/rrnet_hip.h declares %s *"
-                                    % (name, i, a.dtype, header_signatures()[name].pointees[i]))
+                                    % (name, i, a.dtype, declared(name)[0].pointees[i]))
             conv[i] = c_void_p(a.data_ptr())
     if with_stream:
         conv.append(stream())                       # read now, never cached: the weight gradients run on side streams
@@ -176,3 +208,19 @@ def call(name, *args):
         return rc
     if rc != 0:
         raise RRNetHipError("%s failed (%d): %s" % (name, rc, lib().rr_last_error().decode()))
+
+
+class Family:
+    """The entry points of one companion header: `Family("rrnet_hip_se.h").call(name, ...)` is call() for a name that header
+    declares, and an error for any other."""
+
+    def __init__(self, header):
+        self.header = header
+
+    def signatures(self):
+        return family_signatures(self.header)
+
+    def call(self, name, *args):
+        if name not in self.signatures():
+            raise RRNetHipError("%s is not declared in include/%s" % (name, self.header))
+        return call(name, *args)

@@ -69,8 +69,7 @@ class ResidualBlock(nn.Module):
         else:
             skip = xb                                   # identity skip: the raw view, its tag names the accumulator
         out = RF.conv_bn_act(xa, self.conv1, self.bn1, relu=True)
-        # relu(bn2(conv2(out)) + skip): BN apply, residual add and ReLU are one kernel
-        return RF.conv_bn_act(out, self.conv2, self.bn2, relu=True, residual=skip)
+        return self.tail(out, skip)
 
 
 class ConvBNRelu(nn.Module):
@@ -90,27 +89,31 @@ class ConvBNRelu(nn.Module):
         return RF.conv_bn_act(x, self.conv, self.bn, relu=self.with_relu)
 
 
-def _blocks(cin, cout, count, first_stride=1, widen_last=False):
+def _blocks(cin, cout, count, first_stride=1, widen_last=False, block=None):
     """`count` ResidualBlocks; the channel change sits on the first block, or on the last one
-    for the up-path (`make_reverse_residual_layer`, hourglass.py:96-102)."""
+    for the up-path (`make_reverse_residual_layer`, hourglass.py:96-102).  `block`: the block class (the SE hourglass' own)."""
+    block = block or ResidualBlock
     if widen_last:
-        mods = [ResidualBlock(cin, cin) for _ in range(count - 1)] + [ResidualBlock(cin, cout)]
+        mods = [block(cin, cin) for _ in range(count - 1)] + [block(cin, cout)]
     else:
-        mods = [ResidualBlock(cin, cout, first_stride)] + [ResidualBlock(cout, cout) for _ in range(count - 1)]
+        mods = [block(cin, cout, first_stride)] + [block(cout, cout) for _ in range(count - 1)]
     return nn.Sequential(*mods)
 
 
 class Hourglass(nn.Module):
+    block = ResidualBlock                                # (backbones/se_hourglass.py: the same module over its own block)
+
     def __init__(self, n, inplanes, layer_nums):
         super().__init__()
         self.n = n
         cur, nxt = inplanes[0], inplanes[1]
         cur_n, nxt_n = layer_nums[0], layer_nums[1]
-        self.up1 = _blocks(cur, cur, cur_n)
+        blk = self.block
+        self.up1 = _blocks(cur, cur, cur_n, block=blk)
         self.max1 = nn.Sequential()                      # the reference pools with the stride-2 block of low1
-        self.low1 = _blocks(cur, nxt, cur_n, first_stride=2)
-        self.low2 = Hourglass(n - 1, inplanes[1:], layer_nums[1:]) if n > 1 else _blocks(nxt, nxt, nxt_n)
-        self.low3 = _blocks(nxt, cur, cur_n, widen_last=True)
+        self.low1 = _blocks(cur, nxt, cur_n, first_stride=2, block=blk)
+        self.low2 = type(self)(n - 1, inplanes[1:], layer_nums[1:]) if n > 1 else _blocks(nxt, nxt, nxt_n, block=blk)
+        self.low3 = _blocks(nxt, cur, cur_n, widen_last=True, block=blk)
         self.up2 = nn.Upsample(scale_factor=2)
 
     # kept for API parity with the reference's static factory methods
@@ -187,6 +190,18 @@ class HourglassNet(nn.Module):
                     pre = RF.conv_bn_act(act, self.conv_[i][0], self.conv_[i][1], relu=True, residual=a)
                     pre = self.residual[i](pre)
         return outs
+
+
+def _load_pretrained(model, pretrained_path, who):
+    """hourglass_net's policy for './hourglass.pth': loaded (strict=False) when it exists, a warning otherwise."""
+    if pretrained_path:
+        if os.path.exists(pretrained_path):
+            model.load_state_dict(torch.load(pretrained_path, map_location='cpu'), strict=False)
+        else:
+            import warnings
+            warnings.warn("%s: %r not found — the backbone keeps its random initialisation (the reference raises "
+                          "FileNotFoundError here)" % (who, pretrained_path), RuntimeWarning, stacklevel=3)
+    return model
 
 
 def hourglass_net(num_stacks=2, pretrained_path='./hourglass.pth'):

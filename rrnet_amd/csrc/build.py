@@ -42,7 +42,7 @@ def _stale(obj, src):
     if not os.path.exists(obj):
         return True
     t = os.path.getmtime(obj)
-    deps = [os.path.join(HERE, src), os.path.join(INC, "rrnet_hip.h")] + \
+    deps = [os.path.join(HERE, src)] + [os.path.join(INC, h) for h in os.listdir(INC) if h.endswith(".h")] + \
            [os.path.join(HERE, h) for h in os.listdir(HERE) if h.endswith(".h")]
     return any(os.path.getmtime(d) > t for d in deps)
 

@@ -691,6 +691,22 @@ def fanout(x, n):
     return outs
 
 
+class _SumN(torch.autograd.Function):
+    """Sum of n same-shape NHWC tensors in one pass (the dense hourglass' skip terms); every term receives the gradient itself."""
+
+    @staticmethod
+    def forward(ctx, *terms):
+        return ops.sum_n([ops.to_nhwc(t) for t in terms])
+
+    @staticmethod
+    def backward(ctx, dout):
+        return tuple(dout if need else None for need in ctx.needs_input_grad)
+
+
+def sum_n(terms):
+    return _SumN.apply(*terms)
+
+
 class GradAcc:
     """Fan-in target shared by the consumers of one fan-out: the first consumer to run its backward publishes its
     input gradient here, the others add into it (inside their dgrad epilogue) and hand autograd `None`, so the
@@ -814,6 +830,92 @@ class _MaxPool3x3S2(torch.autograd.Function):
 
 def max_pool3x3s2(x):
     return _MaxPool3x3S2.apply(x)
+
+
+class _MaxPool2x2(torch.autograd.Function):
+    """nn.MaxPool2d(2) (backbones/se_hourglass.py:164); the backward scatters through the stored taps, one per window."""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = ops.to_nhwc(x)
+        y, idx = ops.maxpool2x2_fwd(x)
+        ctx.save_for_backward(idx)
+        ctx.shape = tuple(x.shape)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (idx,) = ctx.saved_tensors
+        return ops.maxpool2x2_bwd(ops.to_nhwc(dy), idx, ctx.shape)
+
+
+def max_pool2x2(x):
+    return _MaxPool2x2.apply(x)
+
+
+class _SEScaleResRelu(torch.autograd.Function):
+    """relu(u * s + skip), s = sigmoid(W2 relu(W1 mean_hw(u))) per sample and channel: SELayer, the residual add and the ReLU
+    of backbones/se_hourglass.py:12-27,57-60 as one node — squeeze, excite, scale forward; reduce, excite, apply backward."""
+
+    @staticmethod
+    def forward(ctx, u, w1, w2, skip, skip_acc=None):
+        u, skip = ops.to_nhwc(u), ops.to_nhwc(skip)
+        w1c, w2c = w1.contiguous(), w2.contiguous()
+        hw = u.shape[2] * u.shape[3]
+        m, h, s = ops.se_excite_fwd(ops.se_squeeze(u), w1c, w2c, hw)
+        out = ops.se_scale_res_relu_fwd(u, s, skip)
+        ctx.save_for_backward(u, out, m, h, s, w1c, w2c)
+        ctx.params = (w1, w2)
+        ctx.skip_acc = skip_acc
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        u, out, m, h, s, w1c, w2c = ctx.saved_tensors
+        w1, w2 = ctx.params
+        dout = ops.to_nhwc(dout)
+        t1, t2 = _grad_target(w1), _grad_target(w2)
+        flat = t1 is not None and t2 is not None and t1.is_contiguous() and t2.is_contiguous()
+        dw1 = t1 if flat else torch.zeros_like(w1c)
+        dw2 = t2 if flat else torch.zeros_like(w2c)
+        dm = ops.se_excite_bwd(ops.se_bwd_reduce(dout, out, u), s, h, m, w1c, w2c, dw1, dw2)
+        if flat:
+            _mark(w1, w2)
+        acc = ctx.skip_acc
+        want_skip = ctx.needs_input_grad[3]
+        # skip's fan-in buffer already holds another consumer's gradient: the masked gradient is added into it inside the kernel
+        into = acc.buf if (acc is not None and acc.buf is not None and want_skip and _G_INTO) else None
+        if into is not None:
+            ops.amax_drop(into)
+        du, dskip = ops.se_bwd_apply(dout, out, s, dm, dskip_into=into)
+        if acc is not None:
+            acc.pending -= 1
+            if into is None and want_skip:
+                if acc.buf is None:
+                    acc.buf = dskip             # a fresh tensor of ours: it serves as the fan-in target from here on
+                else:                           # (_G_INTO off: the separate add)
+                    acc.buf.add_(dskip)
+                    dskip = None
+        return (du if ctx.needs_input_grad[0] else None, None if flat else dw1, None if flat else dw2,
+                dskip if want_skip else None, None)
+
+
+def se_scale_res_relu(u, fc1_weight, fc2_weight, skip, reduction=16):
+    """u: the block's bn2 output (conv_bn_act(.., relu=False)); fc1_weight [c/reduction, c] / fc2_weight [c, c/reduction]: the two
+    bias-free nn.Linear of SELayer.fc; skip: the block's skip path (may be a raw fan-out view: its GradAcc is joined, so no
+    other contributor takes itself for the last while this node is outstanding).  The gradient handed back for u is a fresh
+    tensor and the output carries no BnLink: bn2's backward takes its ordinary reduction."""
+    c = u.shape[1]
+    if tuple(fc1_weight.shape) != (c // reduction, c) or tuple(fc2_weight.shape) != (c, c // reduction) or c // reduction < 1:
+        raise ValueError("se_scale_res_relu: %d channels at reduction %d need weights [%d, %d] and [%d, %d], got %s and %s"
+                         % (c, reduction, c // reduction, c, c, c // reduction, tuple(fc1_weight.shape), tuple(fc2_weight.shape)))
+    acc = getattr(skip, "_rr_acc", None)               # set only on raw fan-out views (identity skip)
+    if acc is not None:
+        if torch.is_grad_enabled() and skip.requires_grad:
+            acc.pending += 1
+        else:
+            acc = None
+    return _SEScaleResRelu.apply(u, fc1_weight, fc2_weight, skip, acc)
 
 
 class _BilinearAdd(torch.autograd.Function):

@@ -15,7 +15,7 @@ from rrnet_amd import ops
 from rrnet_amd.detectors.centernet_detector import CenterNetDetector, CenterNetWHDetector
 from rrnet_amd.detectors.fasterrcnn_detector import FasterRCNNDetector
 from rrnet_amd.ext.nms.nms_wrapper import soft_nms_segments
-from rrnet_amd.utils.model_tools import get_backbone
+from rrnet_amd.utils.model_tools import get_backbone, refuse_bf16
 
 
 def stage1_proposals(hm, wh, offset, k, num_classes, nms_type='nms', nms_per_class=True, peak_filter=False,
@@ -55,6 +55,7 @@ class RRNet(nn.Module):
         self.num_classes = cfg.num_classes
         self.nms_type = cfg.Model.nms_type_for_stage1
         self.nms_per_class = cfg.Model.nms_per_class_for_stage1
+        refuse_bf16(cfg.Model)
         self.backbone = get_backbone(cfg.Model.backbone, num_stacks=self.num_stacks)
         # builder-defined option (BASELINE configs[3]): the three heads' 3x3 convolutions as ext/dcn DCN layers,
         # optionally with bf16 matrix operands in their forward

@@ -2373,6 +2373,111 @@ def kmeans_lloyd(X, init, tol=1e-4, max_iter=10000, check_every=16):
     return labels, centres, counts, inertia, iters, flags == 1
 
 
+# ---------------------------------------------------------------------------------------------
+# SE hourglass (csrc/se.hip): squeeze-and-excitation tail of the residual block, the stem's 2x2 max-pool
+# ---------------------------------------------------------------------------------------------
+_SE = _C.Family("rrnet_hip_se.h")       # the family's own header beside include/rrnet_hip.h
+SE_MIN_CHUNK_ROWS = 128       # rows of the map one workgroup of the two reductions sums ...
+SE_MAX_CHUNKS = 256           # ... and at most this many chunks per sample (the per-sample kernels finish them one by one)
+
+
+def se_chunk_rows(hw):
+    """Rows per workgroup of rr_se_squeeze / rr_se_bwd_reduce for a map of hw pixels -> (chunk_rows, chunks)."""
+    rows = max(SE_MIN_CHUNK_ROWS, -(-hw // SE_MAX_CHUNKS))
+    return rows, -(-hw // rows)
+
+
+def _se_dims(u):
+    assert is_nhwc(u) and u.dtype == torch.float32
+    n, c, h, w = u.shape
+    return n, c, h * w
+
+
+def se_squeeze(u):
+    """u NHWC [n,c,h,w] -> partial sums over the map, [n, chunks, c] float64."""
+    n, c, hw = _se_dims(u)
+    rows, chunks = se_chunk_rows(hw)
+    part = torch.empty((n, chunks, c), dtype=torch.float64, device=u.device)
+    _SE.call("rr_se_squeeze", u, part, n, hw, c, rows)
+    return part
+
+
+def se_excite_fwd(part, w1, w2, hw):
+    """part of se_squeeze, w1 [c/r, c], w2 [c, c/r] -> (m [n,c] mean, h [n,c/r] = relu(w1 m), s [n,c] = sigmoid(w2 h))."""
+    n, chunks, c = part.shape
+    cr = w1.shape[0]
+    assert tuple(w1.shape) == (cr, c) and tuple(w2.shape) == (c, cr) and w1.is_contiguous() and w2.is_contiguous()
+    m = torch.empty((n, c), dtype=torch.float32, device=part.device)
+    h = torch.empty((n, cr), dtype=torch.float32, device=part.device)
+    s = torch.empty((n, c), dtype=torch.float32, device=part.device)
+    _SE.call("rr_se_excite_fwd", part, w1, w2, m, h, s, n, chunks, c, cr, hw)
+    return m, h, s
+
+
+def se_scale_res_relu_fwd(u, s, skip):
+    """relu(u * s[n, c] + skip), one pass."""
+    n, c, hw = _se_dims(u)
+    assert is_nhwc(skip) and skip.shape == u.shape and tuple(s.shape) == (n, c)
+    out = empty_nhwc(*u.shape, device=u.device)
+    _SE.call("rr_se_scale_res_relu_fwd", u, s, skip, out, n, hw, c)
+    return out
+
+
+def se_bwd_reduce(dout, out, u):
+    """partial sums over the map of dout * (out > 0) * u, [n, chunks, c] float64."""
+    n, c, hw = _se_dims(u)
+    assert is_nhwc(dout) and is_nhwc(out) and dout.shape == u.shape == out.shape
+    rows, chunks = se_chunk_rows(hw)
+    part = torch.empty((n, chunks, c), dtype=torch.float64, device=u.device)
+    _SE.call("rr_se_bwd_reduce", dout, out, u, part, n, hw, c, rows)
+    return part
+
+
+def se_excite_bwd(part, s, h, m, w1, w2, dw1, dw2):
+    """part of se_bwd_reduce -> dm [n,c] (the gradient of the mean); ADDS the weight gradients into dw1 [c/r, c] / dw2 [c, c/r]."""
+    n, chunks, c = part.shape
+    cr = w1.shape[0]
+    assert dw1.shape == w1.shape and dw2.shape == w2.shape and dw1.is_contiguous() and dw2.is_contiguous()
+    dm = torch.empty((n, c), dtype=torch.float32, device=part.device)
+    ws = torch.empty((n, c + cr), dtype=torch.float32, device=part.device)
+    _SE.call("rr_se_excite_bwd", part, s, h, m, w1, w2, dm, dw1, dw2, ws, n, chunks, c, cr)
+    return dm
+
+
+def se_bwd_apply(dout, out, s, dm, dskip_into=None):
+    """-> (du, dskip): du = g * s[n, c] + dm[n, c] / hw, dskip = g = dout * (out > 0).  dskip_into: g is added into that
+    tensor instead (a fan-in buffer that already holds another consumer's gradient) and dskip comes back None."""
+    n, c, hw = _se_dims(out)
+    assert is_nhwc(dout) and dout.shape == out.shape
+    du = empty_nhwc(*out.shape, device=out.device)
+    dskip = None
+    if dskip_into is None:
+        dskip = empty_nhwc(*out.shape, device=out.device)
+    else:
+        assert is_nhwc(dskip_into) and dskip_into.shape == out.shape and dskip_into.dtype == torch.float32
+    _SE.call("rr_se_bwd_apply", dout, out, s, dm, du, dskip, dskip_into, n, hw, c)
+    return du, dskip
+
+
+def maxpool2x2_fwd(x):
+    """x NHWC [n,c,h,w] -> (y, idx): MaxPool2d(2) (floor on odd sizes) and the winning tap (uint8, 0..3) of every output element."""
+    _C.require_cuda(x)
+    assert is_nhwc(x)
+    n, c, h, w = x.shape
+    y = empty_nhwc(n, c, h // 2, w // 2, x.device)
+    idx = empty_nhwc(n, c, h // 2, w // 2, x.device, dtype=torch.uint8)
+    _SE.call("rr_maxpool2x2_fwd", x, y, idx, n, h, w, c)
+    return y, idx
+
+
+def maxpool2x2_bwd(dy, idx, x_shape):
+    n, c, h, w = x_shape
+    assert is_nhwc(dy) and is_nhwc(idx) and dy.shape == idx.shape and tuple(dy.shape) == (n, c, h // 2, w // 2)
+    dx = empty_nhwc(n, c, h, w, dy.device)
+    _SE.call("rr_maxpool2x2_bwd", dy, idx, dx, n, h, w, c)
+    return dx
+
+
 class _OpsModule(types.ModuleType):
     """`ops.BF16` (read / assign) = this thread's arithmetic switch."""
 

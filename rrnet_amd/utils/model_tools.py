@@ -1,20 +1,37 @@
-"""utils/model_tools.py:9-33 of the reference, restricted to the backbones of the models this package carries: the
-hourglass of RRNet / CenterNet (configs/rrnet_config.py:80 -> 'hourglass'; 'hourglass_tiny' is the builder-defined backbone
-of BASELINE.json config 1) and the three ResNets of RetinaNet (configs/retinanet_config.py:72 -> 'resnet50').  The other
-names belong to out-of-scope models."""
+"""utils/model_tools.py:9-33 of the reference, restricted to the backbones this package carries: the hourglass family of
+RRNet / CenterNet — 'hourglass' (configs/rrnet_config.py:80), 'dense_hourglass' (:26-27) and 'se_hourglass' (the reference
+ships backbones/se_hourglass.py without a name in its table; the name is this package's), each with a builder-defined
+'_tiny' sibling ('hourglass_tiny' is the backbone of BASELINE.json config 1) — and the three ResNets of RetinaNet
+(configs/retinanet_config.py:72 -> 'resnet50').  The other names ('hrnet', 'hrnetv2', 'shufflenet', 'trident') load weight
+files nobody has or are commented out in the reference itself."""
+from rrnet_amd.backbones.dense_hourglass import dense_hourglass_net, dense_hourglass_tiny
 from rrnet_amd.backbones.hourglass import hourglass_net, hourglass_tiny
 from rrnet_amd.backbones.resnet import resnet10, resnet50, resnet101
+from rrnet_amd.backbones.se_hourglass import se_hourglass_net, se_hourglass_tiny
 
 _RESNETS = {'resnet10': resnet10, 'resnet50': resnet50, 'resnet101': resnet101}
+_HOURGLASSES = {'hourglass': hourglass_net, 'hourglass_tiny': hourglass_tiny,
+                'dense_hourglass': dense_hourglass_net, 'dense_hourglass_tiny': dense_hourglass_tiny,
+                'se_hourglass': se_hourglass_net, 'se_hourglass_tiny': se_hourglass_tiny}
+FP32_ONLY_BACKBONES = ('dense_hourglass', 'dense_hourglass_tiny', 'se_hourglass', 'se_hourglass_tiny')
 
 
 def get_backbone(backbone, pretrained=False, num_stacks=2):
-    if backbone == 'hourglass':
-        return hourglass_net(num_stacks=num_stacks)
-    if backbone == 'hourglass_tiny':
-        return hourglass_tiny(num_stacks=num_stacks)
+    if backbone in _HOURGLASSES:
+        return _HOURGLASSES[backbone](num_stacks=num_stacks)
     if backbone in _RESNETS:
         return _RESNETS[backbone](pretrained=pretrained)
     raise NotImplementedError(
-        "backbone %r is outside the accelerated path (only 'hourglass' / 'hourglass_tiny' and 'resnet10' / 'resnet50' / "
-        "'resnet101')" % (backbone,))
+        "backbone %r is outside the accelerated path (only 'hourglass' / 'hourglass_tiny', 'dense_hourglass' / "
+        "'dense_hourglass_tiny', 'se_hourglass' / 'se_hourglass_tiny' and 'resnet10' / 'resnet50' / 'resnet101')" % (backbone,))
+
+
+def refuse_bf16(model_cfg):
+    """cfg.Model.bf16 (or conv_math = "bf16") with the dense or the SE hourglass: inside ops.phantom_scope `pre` and the block
+    outputs may exist as bf16 images only, and summing them into a feature that leaves the scope, or reducing them in the
+    squeeze, needs rules nobody has tested.  fp32 and conv_math = "f16x3" (the convolutions only) are supported."""
+    from rrnet_amd import ops
+    if getattr(model_cfg, "backbone", None) in FP32_ONLY_BACKBONES and ops.math_mode(model_cfg) == ops.MATH_BF16:
+        raise NotImplementedError(
+            "cfg.Model.bf16 / conv_math = 'bf16' is not built for backbone %r: its skip sums and its squeeze would read "
+            "bf16-only activations (use fp32 or cfg.Model.conv_math = 'f16x3')" % (model_cfg.backbone,))

@@ -99,7 +99,8 @@ def main(argv=None):
     ap.add_argument("--no-flip", dest="flip", action="store_false", help="CenterNet: the plain image only")
     ap.add_argument("--random-weights", action="store_true")
     ap.add_argument("--workers", type=int, default=8)
-    ap.add_argument("--backbone", help="RetinaNet: override cfg.Model.backbone (resnet10 / resnet50 / resnet101)")
+    ap.add_argument("--backbone", help="override cfg.Model.backbone: resnet10 / resnet50 / resnet101 (RetinaNet), hourglass / "
+                    "dense_hourglass / se_hourglass and their _tiny siblings (RRNet, CenterNet)")
     ap.add_argument("--score-thr", type=float, help="RetinaNet: the candidate threshold (default 0.1)")
     ap.add_argument("--tile", help="RetinaNet: tiled inference on overlapping tiles of this size, N or H,W")
     ap.add_argument("--tile-overlap", type=int, help="pixels two neighbouring tiles share (default: a quarter of the tile)")
@@ -111,8 +112,10 @@ def main(argv=None):
     args = ap.parse_args(argv)
     cfg = load_config(args.config)
     retinanet = args.config.startswith("retinanet")
-    if not retinanet and (args.backbone is not None or args.score_thr is not None):
-        raise SystemExit("--backbone / --score-thr belong to --config retinanet_config")
+    if not retinanet and ((args.backbone or "").startswith("resnet") or args.score_thr is not None):
+        raise SystemExit("--backbone resnet* / --score-thr belong to --config retinanet_config")
+    if not retinanet and args.backbone:
+        cfg.Model.backbone = args.backbone                    # a member of the hourglass family (utils/model_tools)
     tile_options = (args.tile_overlap, args.tile_zoom, args.tile_margin, args.tile_batch)
     if not retinanet and (args.tile is not None or any(v is not None for v in tile_options)):
         raise SystemExit("--tile: tiled inference is built for --config retinanet_config only (RRNet and CenterNet answer "
