@@ -36,31 +36,122 @@ struct DcnArgs {
     int M;
 };
 
+// window kernels: a workgroup owns a WIN_TH x WIN_TW block of output pixels and the input window that block can reach
+constexpr int WIN_TH = rr_plan::DCN_TH, WIN_TW = rr_plan::DCN_TW;
+
+struct DcnWinArgs {
+    DcnArgs a;
+    int RW, WH, WW;        // margin, window height / width in pixels
+    int tiles_y, tiles_x;  // pixel blocks per image
+    // bf16 forward: the weights pre-packed to bf16 [tap][32-channel chunk][filter][32] (rr_dcn_pack_weights_bf16), or null.
+    // With them a K-step's B tile (256 filters x 32 channels = 16 KB, contiguous) goes global -> LDS by
+    // buffer_load ... lds: no staging registers, no converts, no ds_write for the weight operand.
+    const unsigned short *wpk;
+};
+
+// ---- the sampling rule and the tensor addressing, defined ONCE for every kernel below ----------------------------------------
+// The forward and the three gradients have to agree on which corners of a sample at h = -0.5 or h = H - 1 exist: a kernel that
+// decided that for itself would be a wrong gradient at the image border that no shape check catches.
+// offset[m][g][tap] is the (dh, dw) pair at this index, mask[m][g][tap] the value at dcn_mask_at (d offset, d mask likewise);
+// m = (n * P + p) * Q + q.  RS = a.R * a.S is a parameter because the window kernels know it at compile time.
+__device__ __forceinline__ long dcn_offset_at(const DcnArgs &a, int RS, long m, int g, int tap)
+{
+    return m * (2 * a.dg * RS) + g * 2 * RS + 2 * tap;
+}
+__device__ __forceinline__ long dcn_mask_at(const DcnArgs &a, int RS, long m, int g, int tap)
+{
+    return m * (a.dg * RS) + g * RS + tap;
+}
+
+struct DcnPixel { int n, p, q; };
+__device__ __forceinline__ DcnPixel dcn_pixel_of(const DcnArgs &a, long m)
+{
+    const int pq = a.P * a.Q;
+    const int n = (int)(m / pq), rem = (int)(m - (long)n * pq), p = rem / a.Q;
+    return {n, p, rem - p * a.Q};
+}
+
+struct DcnTile {        // pixel block `bid` (x fastest, then y, then the image) of a window kernel
+    int n, y0, x0;      // image, first output pixel
+    int wy0, wx0;       // image coordinates of window pixel (0, 0)
+    long img;           // pixel index of the image's first pixel
+};
+__device__ __forceinline__ DcnTile dcn_tile(const DcnWinArgs &wa, int bid)
+{
+    DcnTile tl;
+    const int txi = bid % wa.tiles_x; bid /= wa.tiles_x;
+    const int tyi = bid % wa.tiles_y;
+    tl.n = bid / wa.tiles_y;
+    tl.y0 = tyi * WIN_TH; tl.x0 = txi * WIN_TW;
+    tl.wy0 = tl.y0 - wa.a.pad_h - wa.RW; tl.wx0 = tl.x0 - wa.a.pad_w - wa.RW;
+    tl.img = (long)tl.n * wa.a.H * wa.a.W;
+    return tl;
+}
+
+// The sample of output pixel (p, q) and tap (ti, tj) with offsets (dh, dw): its position is formed by ONE float32 add per
+// axis; it counts iff -1 < h < H and -1 < w < W; its corner e = (e >> 1, e & 1) is input pixel (h0 + (e >> 1), w0 + (e & 1))
+// and exists (bit e of `valid`) iff the sample counts and that pixel lies in the image.  valid == 0: contributes nothing.
+struct DcnSample { int h0, w0; float lh, lw; int valid; };
+__device__ __forceinline__ DcnSample dcn_sample(const DcnArgs &a, int p, int q, int ti, int tj, int stride, float dh, float dw)
+{
+    const float h = (float)(p * stride - a.pad_h + ti * a.dil) + dh;
+    const float w = (float)(q * stride - a.pad_w + tj * a.dil) + dw;
+    const bool inside = h > -1.f && w > -1.f && h < (float)a.H && w < (float)a.W;
+    const float hf = floorf(h), wf = floorf(w);
+    DcnSample s = {(int)hf, (int)wf, h - hf, w - wf, 0};
+    // (inside gives -1 <= h0 <= H - 1: the upper row can only fall off the top, the lower row off the bottom; columns alike.
+    // Written out per corner: the loop over e compiled to more compares and selects in the L2-gather kernels.)
+    const int h1 = s.h0 + 1, w1 = s.w0 + 1;
+    const bool v0 = inside && s.h0 >= 0 && s.w0 >= 0, v1 = inside && s.h0 >= 0 && w1 <= a.W - 1;
+    const bool v2 = inside && h1 <= a.H - 1 && s.w0 >= 0, v3 = inside && h1 <= a.H - 1 && w1 <= a.W - 1;
+    s.valid = (int)v0 | ((int)v1 << 1) | ((int)v2 << 2) | ((int)v3 << 3);
+    return s;
+}
+
+// bilinear weights of the four corners, and their derivatives in h and w
+__device__ __forceinline__ void dcn_weights(float lh, float lw, float (&wt)[4])
+{
+    const float hh = 1.f - lh, hw = 1.f - lw;
+    wt[0] = hh * hw; wt[1] = hh * lw; wt[2] = lh * hw; wt[3] = lh * lw;
+}
+__device__ __forceinline__ void dcn_dweights(float lh, float lw, float (&dwt_dh)[4], float (&dwt_dw)[4])
+{
+    const float hh = 1.f - lh, hw = 1.f - lw;
+    dwt_dh[0] = -hw; dwt_dh[1] = -lw; dwt_dh[2] = hw; dwt_dh[3] = lw;
+    dwt_dw[0] = -hh; dwt_dw[1] = hh; dwt_dw[2] = -lh; dwt_dw[3] = lh;
+}
+
+// Sample geometry of the windowed gradients, one ds_read_b128 per sample: {lh, lw, mask, window pixel of corner 0 |
+// corner-valid bits << 16 | GEO_SLOW}; all zero for a sample without a valid corner (nothing to add, zero gradients).
+// Fast samples have their whole 2x2 footprint inside the window: corner e is window pixel base + (e >> 1) * WW + (e & 1);
+// the others (GEO_SLOW) recompute their position and go corner by corner.
+constexpr int GEO_SLOW = 1 << 20;
+__device__ __forceinline__ f32x4 dcn_win_geo(const DcnWinArgs &wa, const DcnTile &tl, const DcnSample &s, float mk)
+{
+    if (!s.valid) return f32x4{0.f, 0.f, 0.f, 0.f};
+    const int ly = s.h0 - tl.wy0, lx = s.w0 - tl.wx0;
+    const bool fast = ly >= 0 && ly + 1 < wa.WH && lx >= 0 && lx + 1 < wa.WW;
+    return f32x4{s.lh, s.lw, mk, __int_as_float((s.valid << 16) | (fast ? (ly * wa.WW + lx) : GEO_SLOW))};
+}
+
 struct Tap4 {           // bilinear sample of one (pixel, tap): 4 corner element offsets (pixel base, no channel) + weights
     long o[4];
     float w[4];         // already multiplied by the modulation mask; 0 for corners / samples outside the image
 };
 
-__device__ __forceinline__ Tap4 make_tap(const DcnArgs &a, int n, int p, int q, int i, int j, float dh, float dw, float m)
+__device__ __forceinline__ Tap4 make_tap(const DcnArgs &a, int n, int p, int q, int ti, int tj, float dh, float dw, float m)
 {
     Tap4 t;
-    const float h = (float)(p * a.stride - a.pad_h + i * a.dil) + dh;
-    const float w = (float)(q * a.stride - a.pad_w + j * a.dil) + dw;
-    const bool inside = h > -1.f && w > -1.f && h < (float)a.H && w < (float)a.W;
-    const float hf = floorf(h), wf = floorf(w);
-    const int h0 = (int)hf, w0 = (int)wf, h1 = h0 + 1, w1 = w0 + 1;
-    const float lh = h - hf, lw = w - wf, hh = 1.f - lh, hw = 1.f - lw;
-    const bool v0 = inside && h0 >= 0 && w0 >= 0, v1 = inside && h0 >= 0 && w1 <= a.W - 1;
-    const bool v2 = inside && h1 <= a.H - 1 && w0 >= 0, v3 = inside && h1 <= a.H - 1 && w1 <= a.W - 1;
+    const DcnSample s = dcn_sample(a, p, q, ti, tj, a.stride, dh, dw);
+    float wt[4];
+    dcn_weights(s.lh, s.lw, wt);
     const long base = (long)n * a.H * a.W;
-    t.o[0] = v0 ? (base + (long)h0 * a.W + w0) * a.C : -1;
-    t.o[1] = v1 ? (base + (long)h0 * a.W + w1) * a.C : -1;
-    t.o[2] = v2 ? (base + (long)h1 * a.W + w0) * a.C : -1;
-    t.o[3] = v3 ? (base + (long)h1 * a.W + w1) * a.C : -1;
-    t.w[0] = v0 ? hh * hw * m : 0.f;
-    t.w[1] = v1 ? hh * lw * m : 0.f;
-    t.w[2] = v2 ? lh * hw * m : 0.f;
-    t.w[3] = v3 ? lh * lw * m : 0.f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const bool v = (s.valid >> e) & 1;
+        t.o[e] = v ? (base + (long)(s.h0 + (e >> 1)) * a.W + s.w0 + (e & 1)) * a.C : -1;
+        t.w[e] = v ? wt[e] * m : 0.f;
+    }
     return t;
 }
 
@@ -115,11 +206,8 @@ __global__ __launch_bounds__(256) void dcn_fprop_kernel(const DcnArgs a)
     for (int j = 0; j < AJ; ++j) {
         const int m = m0 + a_row + 32 * j;
         if (m < a.M) {
-            const int pq = a.P * a.Q;
-            rn[j] = m / pq;
-            const int rem = m - rn[j] * pq;
-            rp[j] = rem / a.Q;
-            rq[j] = rem - rp[j] * a.Q;
+            const DcnPixel px = dcn_pixel_of(a, m);
+            rn[j] = px.n; rp[j] = px.p; rq[j] = px.q;
         } else {
             rn[j] = -1; rp[j] = 0; rq[j] = 0;
         }
@@ -134,7 +222,7 @@ __global__ __launch_bounds__(256) void dcn_fprop_kernel(const DcnArgs a)
     int tc_tap = -1, tc_g = -1;
     auto issue = [&](int kc) {
         const int tap = kc / cpt, cch = kc - tap * cpt;
-        const int i = tap / a.S, jx = tap - i * a.S;
+        const int ti = tap / a.S, tj = tap - ti * a.S;
         const int c0 = cch * BK;
         const int g = c0 / cpg;
         const bool c_ok = c0 + a_col < a.C;
@@ -144,9 +232,8 @@ __global__ __launch_bounds__(256) void dcn_fprop_kernel(const DcnArgs a)
             for (int j = 0; j < AJ; ++j) {
                 if (rn[j] >= 0) {
                     const long m = (long)m0 + a_row + 32 * j;
-                    const float *po = a.offset + m * (2 * a.dg * RS) + g * 2 * RS + 2 * tap;
-                    const float mk = a.mask[m * (a.dg * RS) + g * RS + tap];
-                    tc[j] = make_tap(a, rn[j], rp[j], rq[j], i, jx, po[0], po[1], mk);
+                    const float *po = a.offset + dcn_offset_at(a, RS, m, g, tap);
+                    tc[j] = make_tap(a, rn[j], rp[j], rq[j], ti, tj, po[0], po[1], a.mask[dcn_mask_at(a, RS, m, g, tap)]);
                 } else {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) { tc[j].o[e] = -1; tc[j].w[e] = 0.f; }
@@ -265,18 +352,6 @@ __global__ __launch_bounds__(256) void dcn_fprop_kernel(const DcnArgs a)
 // fetched from global memory by the lanes concerned.  The sample geometry (4 corner indices + 4 mask-weighted bilinear
 // weights per pixel and tap) is computed once per workgroup into LDS tables.  K-steps run chunk outer / tap inner.
 // stride 1 only (the window of a strided layer is not compact); other layers take dcn_fprop_kernel.
-constexpr int WIN_TH = rr_plan::DCN_TH, WIN_TW = rr_plan::DCN_TW;
-
-struct DcnWinArgs {
-    DcnArgs a;
-    int RW, WH, WW;        // margin, window height / width in pixels
-    int tiles_y, tiles_x;  // pixel blocks per image
-    // bf16 forward: the weights pre-packed to bf16 [tap][32-channel chunk][filter][32] (rr_dcn_pack_weights_bf16), or null.
-    // With them a K-step's B tile (256 filters x 32 channels = 16 KB, contiguous) goes global -> LDS by
-    // buffer_load ... lds: no staging registers, no converts, no ds_write for the weight operand.
-    const unsigned short *wpk;
-};
-
 // F32: fp32 matrix operands (v_mfma_f32_32x32x2_f32); a K-step is then HALF a window chunk (16 channels of one tap),
 // which keeps the operand images at the bf16 kernel's bytes.
 template <int BN, bool F32>      // 128 or 256 output channels per workgroup: at 256 one gather feeds twice the MFMAs
@@ -300,16 +375,13 @@ __global__ __launch_bounds__(512) void dcn_fprop_win_kernel(const DcnWinArgs wa)
     const int ntiles = (a.K + BN - 1) / BN;
     int bid = blockIdx.x;
     const int n_tile = bid % ntiles; bid /= ntiles;
-    const int txi = bid % wa.tiles_x; bid /= wa.tiles_x;
-    const int tyi = bid % wa.tiles_y;
-    const int n = bid / wa.tiles_y;
-    const int y0 = tyi * WIN_TH, x0 = txi * WIN_TW, n0 = n_tile * BN;
-    const int wy0 = y0 - a.pad_h - wa.RW, wx0 = x0 - a.pad_w - wa.RW;   // image coordinates of window pixel (0, 0)
-    const int cpt = a.C / BK;                                            // channel chunks (C % 32 == 0 on this path)
+    const DcnTile tl = dcn_tile(wa, bid);
+    const int n = tl.n, y0 = tl.y0, x0 = tl.x0, wy0 = tl.wy0, wx0 = tl.wx0, n0 = n_tile * BN;
+    const int cpt = a.C / BK;                                          // channel chunks (C % 32 == 0 on this path)
     const int cpg = a.C / a.dg;
     const int a_col = (t & 7) * 4, a_row = t >> 3;
     const int fa_col = (t & 3) * 4, fa_row = t >> 2;                     // F32 staging: one 16-channel row quarter per thread
-    const long img = (long)n * a.H * a.W;
+    const long img = tl.img;
 
     // ---- geometry tables for deformable group g
     auto build_geo = [&](int g) {
@@ -320,20 +392,16 @@ __global__ __launch_bounds__(512) void dcn_fprop_win_kernel(const DcnWinArgs wa)
             float w4[4] = {0.f, 0.f, 0.f, 0.f};
             if (p < a.P && q < a.Q) {
                 const long m = ((long)n * a.P + p) * a.Q + q;
-                const float *po = a.offset + m * (2 * a.dg * RS) + g * 2 * RS + 2 * tap;
-                const float mk = a.mask[m * (a.dg * RS) + g * RS + tap];
+                const float *po = a.offset + dcn_offset_at(a, RS, m, g, tap);
+                const float mk = a.mask[dcn_mask_at(a, RS, m, g, tap)];
                 const int ti = tap / a.S, tj = tap - ti * a.S;
-                const float h = (float)(p - a.pad_h + ti * a.dil) + po[0];
-                const float w = (float)(q - a.pad_w + tj * a.dil) + po[1];
-                const bool inside = h > -1.f && w > -1.f && h < (float)a.H && w < (float)a.W;
-                const float hf = floorf(h), wf = floorf(w);
-                const int h0 = (int)hf, w0 = (int)wf;
-                const float lh = h - hf, lw = w - wf, hh = 1.f - lh, hw = 1.f - lw;
-                const float cw[4] = {hh * hw, hh * lw, lh * hw, lh * lw};
+                const DcnSample s = dcn_sample(a, p, q, ti, tj, 1, po[0], po[1]);
+                float cw[4];
+                dcn_weights(s.lh, s.lw, cw);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const int hy = h0 + (e >> 1), wx = w0 + (e & 1);
-                    if (inside && hy >= 0 && hy <= a.H - 1 && wx >= 0 && wx <= a.W - 1) {
+                    const int hy = s.h0 + (e >> 1), wx = s.w0 + (e & 1);
+                    if ((s.valid >> e) & 1) {
                         w4[e] = cw[e] * mk;
                         const int ly = hy - wy0, lx = wx - wx0;
                         o[e] = (ly >= 0 && ly < wa.WH && lx >= 0 && lx < wa.WW) ? (unsigned int)(ly * wa.WW + lx)
@@ -619,11 +687,10 @@ __global__ __launch_bounds__(256) void dcn_im2col_kernel(const DcnArgs a, float 
         const long mt = idx / C4;
         const int tap = (int)(mt % RS);
         const long m = mt / RS;
-        const int pq = a.P * a.Q;
-        const int n = (int)(m / pq), rem = (int)(m - (long)n * pq), p = rem / a.Q, q = rem - p * a.Q;
-        const int g = c / cpg, i = tap / a.S, j = tap - i * a.S;
-        const float *po = a.offset + m * (2 * a.dg * RS) + g * 2 * RS + 2 * tap;
-        const Tap4 tp = make_tap(a, n, p, q, i, j, po[0], po[1], a.mask[m * (a.dg * RS) + g * RS + tap]);
+        const DcnPixel px = dcn_pixel_of(a, m);
+        const int g = c / cpg, ti = tap / a.S, tj = tap - ti * a.S;
+        const float *po = a.offset + dcn_offset_at(a, RS, m, g, tap);
+        const Tap4 tp = make_tap(a, px.n, px.p, px.q, ti, tj, po[0], po[1], a.mask[dcn_mask_at(a, RS, m, g, tap)]);
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int e = 0; e < 4; ++e)
@@ -645,25 +712,21 @@ __global__ __launch_bounds__(256) void dcn_col2im_kernel(const DcnArgs a, const 
         const long mt = it / a.dg;
         const int tap = (int)(mt % RS);
         const long m = mt / RS;
-        const int pq = a.P * a.Q;
-        const int n = (int)(m / pq), rem = (int)(m - (long)n * pq), p = rem / a.Q, q = rem - p * a.Q;
-        const int i = tap / a.S, j = tap - i * a.S;
-        const float *po = a.offset + m * (2 * a.dg * RS) + g * 2 * RS + 2 * tap;
-        const float mk = a.mask[m * (a.dg * RS) + g * RS + tap];
-        const float h = (float)(p * a.stride - a.pad_h + i * a.dil) + po[0];
-        const float w = (float)(q * a.stride - a.pad_w + j * a.dil) + po[1];
-        const bool inside = h > -1.f && w > -1.f && h < (float)a.H && w < (float)a.W;
-        const float hf = floorf(h), wf = floorf(w);
-        const int h0 = (int)hf, w0 = (int)wf, h1 = h0 + 1, w1 = w0 + 1;
-        const float lh = h - hf, lw = w - wf, hh = 1.f - lh, hw = 1.f - lw;
-        const bool v[4] = {inside && h0 >= 0 && w0 >= 0, inside && h0 >= 0 && w1 <= a.W - 1,
-                           inside && h1 <= a.H - 1 && w0 >= 0, inside && h1 <= a.H - 1 && w1 <= a.W - 1};
-        const long base = (long)n * a.H * a.W;
-        const long o[4] = {(base + (long)h0 * a.W + w0) * a.C, (base + (long)h0 * a.W + w1) * a.C,
-                           (base + (long)h1 * a.W + w0) * a.C, (base + (long)h1 * a.W + w1) * a.C};
-        const float wt[4] = {hh * hw, hh * lw, lh * hw, lh * lw};
-        const float dh_w[4] = {-hw, -lw, hw, lw};      // d wt / d h
-        const float dw_w[4] = {-hh, hh, -lh, lh};      // d wt / d w
+        const DcnPixel px = dcn_pixel_of(a, m);
+        const int ti = tap / a.S, tj = tap - ti * a.S;
+        const long oi = dcn_offset_at(a, RS, m, g, tap), mi = dcn_mask_at(a, RS, m, g, tap);
+        const float mk = a.mask[mi];
+        const DcnSample s = dcn_sample(a, px.p, px.q, ti, tj, a.stride, a.offset[oi], a.offset[oi + 1]);
+        bool v[4];
+        long o[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            v[e] = (s.valid >> e) & 1;
+            o[e] = (((long)px.n * a.H + s.h0 + (e >> 1)) * a.W + s.w0 + (e & 1)) * a.C;
+        }
+        float wt[4], dh_w[4], dw_w[4];
+        dcn_weights(s.lh, s.lw, wt);
+        dcn_dweights(s.lh, s.lw, dh_w, dw_w);
         float s_mask = 0.f, s_h = 0.f, s_w = 0.f;
         for (int c = g * cpg + lane; c < (g + 1) * cpg; c += 64) {
             const float gcol = dcol[(m * RS + tap) * a.C + c];
@@ -685,9 +748,9 @@ __global__ __launch_bounds__(256) void dcn_col2im_kernel(const DcnArgs a, const 
         }
         s_mask = wave_sum(s_mask); s_h = wave_sum(s_h); s_w = wave_sum(s_w);
         if (lane == 0) {
-            doffset[m * (2 * a.dg * RS) + g * 2 * RS + 2 * tap] = s_h;
-            doffset[m * (2 * a.dg * RS) + g * 2 * RS + 2 * tap + 1] = s_w;
-            dmask[m * (a.dg * RS) + g * RS + tap] = s_mask;
+            doffset[oi] = s_h;
+            doffset[oi + 1] = s_w;
+            dmask[mi] = s_mask;
         }
     }
 }
@@ -746,16 +809,15 @@ __global__ __launch_bounds__(256, 2) void dcn_wgrad_kernel(const DcnBwdArgs b)
     f32x4 ra[4], rv[2][4];
     float rw[2][4];
     float om[4][3];                                   // (dh, dw, mask) of the rows of the K-step after next
-    const int pq = a.P * a.Q;
 
     auto load_om = [&](int kc) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const long m = (long)kc * BK + row + 8 * j;
             if (kc < kc_end && m < a.M) {
-                const float *po = a.offset + m * (2 * a.dg * RS) + g * 2 * RS + 2 * tap;
+                const float *po = a.offset + dcn_offset_at(a, RS, m, g, tap);
                 om[j][0] = po[0]; om[j][1] = po[1];
-                om[j][2] = a.mask[m * (a.dg * RS) + g * RS + tap];
+                om[j][2] = a.mask[dcn_mask_at(a, RS, m, g, tap)];
             } else {
                 om[j][0] = 0.f; om[j][1] = 0.f; om[j][2] = 0.f;
             }
@@ -775,8 +837,8 @@ __global__ __launch_bounds__(256, 2) void dcn_wgrad_kernel(const DcnBwdArgs b)
             const long m = (long)kc * BK + row + 8 * j;
             Tap4 tp;
             if (m < a.M) {
-                const int n = (int)(m / pq), rem = (int)(m - (long)n * pq), p = rem / a.Q, q = rem - p * a.Q;
-                tp = make_tap(a, n, p, q, ti, tj, om[j][0], om[j][1], om[j][2]);
+                const DcnPixel px = dcn_pixel_of(a, m);
+                tp = make_tap(a, px.n, px.p, px.q, ti, tj, om[j][0], om[j][1], om[j][2]);
             } else {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) { tp.o[e] = -1; tp.w[e] = 0.f; }
@@ -892,7 +954,6 @@ __global__ __launch_bounds__(256) void dcn_dgrad_kernel(const DcnBwdArgs b)
     const int nkc = (a.K + BK - 1) / BK;
     const int nct = (a.C + BN - 1) / BN;
     const int cpg = a.C / a.dg;
-    const int pq = a.P * a.Q;
     f32x4 ra[4], rb[4];
 
     for (int tap = 0; tap < RS; ++tap) {
@@ -907,21 +968,16 @@ __global__ __launch_bounds__(256) void dcn_dgrad_kernel(const DcnBwdArgs b)
                     int o[4] = {-1, -1, -1, -1};
                     float w4[4] = {0.f, 0.f, 0.f, 0.f}, flh = 0.f, flw = 0.f, mk = 0.f;
                     if (m < a.M) {
-                        const int n = (int)(m / pq), rem = (int)(m - (long)n * pq), p = rem / a.Q, q = rem - p * a.Q;
-                        const float *po = a.offset + m * (2 * a.dg * RS) + g * 2 * RS + 2 * tap;
-                        mk = a.mask[m * (a.dg * RS) + g * RS + tap];
-                        const float h = (float)(p * a.stride - a.pad_h + ti * a.dil) + po[0];
-                        const float w = (float)(q * a.stride - a.pad_w + tj * a.dil) + po[1];
-                        const bool inside = h > -1.f && w > -1.f && h < (float)a.H && w < (float)a.W;
-                        const float hf = floorf(h), wf = floorf(w);
-                        const int h0 = (int)hf, w0 = (int)wf, h1 = h0 + 1, w1 = w0 + 1;
-                        flh = h - hf; flw = w - wf;
-                        const float hh = 1.f - flh, hw = 1.f - flw;
-                        const int base = n * a.H * a.W;
-                        if (inside && h0 >= 0 && w0 >= 0) { o[0] = base + h0 * a.W + w0; w4[0] = hh * hw; }
-                        if (inside && h0 >= 0 && w1 <= a.W - 1) { o[1] = base + h0 * a.W + w1; w4[1] = hh * flw; }
-                        if (inside && h1 <= a.H - 1 && w0 >= 0) { o[2] = base + h1 * a.W + w0; w4[2] = flh * hw; }
-                        if (inside && h1 <= a.H - 1 && w1 <= a.W - 1) { o[3] = base + h1 * a.W + w1; w4[3] = flh * flw; }
+                        const DcnPixel px = dcn_pixel_of(a, m);
+                        const float *po = a.offset + dcn_offset_at(a, RS, m, g, tap);
+                        mk = a.mask[dcn_mask_at(a, RS, m, g, tap)];
+                        const DcnSample s = dcn_sample(a, px.p, px.q, ti, tj, a.stride, po[0], po[1]);
+                        flh = s.lh; flw = s.lw;
+                        float wt[4];
+                        dcn_weights(flh, flw, wt);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            if ((s.valid >> e) & 1) { o[e] = (px.n * a.H + s.h0 + (e >> 1)) * a.W + s.w0 + (e & 1); w4[e] = wt[e]; }
                     }
 #pragma unroll
                     for (int e = 0; e < 4; ++e) { geo_o[t * 4 + e] = o[e]; geo_w[t * 8 + e] = w4[e]; }
@@ -1013,9 +1069,8 @@ __global__ __launch_bounds__(256) void dcn_dgrad_kernel(const DcnBwdArgs b)
             };
             auto process = [&](int pass, const PassRegs &R) {
                 const int ml = pass * 8 + r8;
-                const float hh = 1.f - R.flh, hw = 1.f - R.flw;
-                const float dhw[4] = {-hw, -R.flw, hw, R.flw};      // d weight / d h of the four corners
-                const float dww[4] = {-hh, hh, -R.flh, R.flh};      // d weight / d w
+                float dhw[4], dww[4];
+                dcn_dweights(R.flh, R.flw, dhw, dww);
                 float s_m = 0.f, s_h = 0.f, s_w = 0.f;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
@@ -1060,9 +1115,9 @@ __global__ __launch_bounds__(256) void dcn_dgrad_kernel(const DcnBwdArgs b)
                 const bool last_of_group = ((c0 + BN) % cpg) == 0 || ct == nct - 1;
                 if (last_of_group) {
                     const long m = (long)m0 + t;
-                    b.dmask[m * (a.dg * RS) + g * RS + tap] = red[t * 3];
-                    b.doffset[m * (2 * a.dg * RS) + g * 2 * RS + 2 * tap] = red[t * 3 + 1];
-                    b.doffset[m * (2 * a.dg * RS) + g * 2 * RS + 2 * tap + 1] = red[t * 3 + 2];
+                    b.dmask[dcn_mask_at(a, RS, m, g, tap)] = red[t * 3];
+                    b.doffset[dcn_offset_at(a, RS, m, g, tap)] = red[t * 3 + 1];
+                    b.doffset[dcn_offset_at(a, RS, m, g, tap) + 1] = red[t * 3 + 2];
                     red[t * 3] = 0.f; red[t * 3 + 1] = 0.f; red[t * 3 + 2] = 0.f;
                 }
             }
@@ -1194,7 +1249,7 @@ __global__ __launch_bounds__(512) void dcn_dgrad_win_kernel(const DcnWinBwdArgs 
     // 32 (w & 3) .. +31 of the block for taps 5 (w >> 2) .. +4 (five accumulator tiles; the ninth..tenth slot idles).
     const DcnWinArgs &wa = wb.w;
     const DcnArgs &a = wa.a;
-    constexpr int CW = 32, WSTR = 33, SST = 36, NT = 512, TG = 5, GEO_SLOW = 1 << 20;
+    constexpr int CW = 32, WSTR = 33, SST = 36, NT = 512, TG = 5;
     constexpr int BKW = F32 ? 16 : 32;                        // filters per K-step
     constexpr int LDF = 20;                                   // fp32 operand rows: 16 + 4 floats (80 B: aligned, conflict-free b128 reads)
     constexpr int A_ELEMS = BM * LDKH;                        // in 2-byte units for both precisions (BM * LDF * 2 == BM * LDKH)
@@ -1202,7 +1257,7 @@ __global__ __launch_bounds__(512) void dcn_dgrad_win_kernel(const DcnWinBwdArgs 
     extern __shared__ __align__(16) unsigned char smem[];
     const int npx = wa.WH * wa.WW;
     int *dxw = reinterpret_cast<int *>(smem);                                       // [npx][33] fixed point (see below)
-    // [BM][RS] x {lh, lw, mask, window pixel of corner 0 | corner-valid bits << 16 | SLOW}: one ds_read_b128 per sample
+    // [BM][RS] x dcn_win_geo
     f32x4 *geo4 = reinterpret_cast<f32x4 *>(dxw + (size_t)((npx * WSTR + 3) & ~3));
     float *red = reinterpret_cast<float *>(geo4 + BM * RS);                         // [BM][RS][3]: d mask, d off h, d off w
     float *xw = red + BM * RS * 3;                                                  // [npx][32]: the input window of this chunk
@@ -1215,19 +1270,15 @@ __global__ __launch_bounds__(512) void dcn_dgrad_win_kernel(const DcnWinBwdArgs 
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int lr = lane & 31, lh_ = lane >> 5;
     const int wpx = wave & 3, wtg = wave >> 2;
-    int bid = dcn_xcd_remap(blockIdx.x, gridDim.x);
-    const int txi = bid % wa.tiles_x; bid /= wa.tiles_x;
-    const int tyi = bid % wa.tiles_y;
-    const int n = bid / wa.tiles_y;
-    const int y0 = tyi * WIN_TH, x0 = txi * WIN_TW;
-    const int wy0 = y0 - a.pad_h - wa.RW, wx0 = x0 - a.pad_w - wa.RW;
+    const DcnTile tl = dcn_tile(wa, dcn_xcd_remap(blockIdx.x, gridDim.x));
+    const int n = tl.n, y0 = tl.y0, x0 = tl.x0, wy0 = tl.wy0, wx0 = tl.wx0;
     const int cpt = a.C / CW, cpg = a.C / a.dg;
     const int nkc = (a.K + BKW - 1) / BKW;
     const int a_col = (t & 7) * 4, a_row = t >> 3;          // a_row 0..63
     const int b_row = a_row & 31, b_tg = a_row >> 5;        // weight rows: ko row b_row, taps 5 b_tg .. +4
     // F32 staging: dY 128 px x 16 ko = one float4 per thread; W 16 ko x 9 taps x 32 ch: ko row (t >> 3) & 15, taps 3 (t >> 7) .. +2
     const int fa_row = t >> 2, fa_col = (t & 3) * 4, fb_row = (t >> 3) & 15, fb_tg = t >> 7;
-    const long img = (long)n * a.H * a.W;
+    const long img = tl.img;
 
     __shared__ int wmaxc[8][32];     // bits of max |dcol| per wave and channel
     __shared__ __align__(16) float fxs[32], fxi[32];   // fixed-point scale of the chunk's channels and its inverse (NaN: non-finite)
@@ -1244,39 +1295,25 @@ __global__ __launch_bounds__(512) void dcn_dgrad_win_kernel(const DcnWinBwdArgs 
         for (int it = t; it < BM * RS; it += NT) {
             const int r = it / RS, tap = it - r * RS;
             const int p = y0 + r / WIN_TW, q = x0 + r % WIN_TW;
-            int packed = 0;                       // no valid corner: nothing to add, zero gradients
-            float flh = 0.f, flw = 0.f, mk = 0.f;
+            DcnSample s{};
+            float mk = 0.f;
             if (p < a.P && q < a.Q) {
                 const long m = ((long)n * a.P + p) * a.Q + q;
-                const float *po = a.offset + m * (2 * a.dg * RS) + g * 2 * RS + 2 * tap;
+                const float *po = a.offset + dcn_offset_at(a, RS, m, g, tap);
                 const int ti = tap / a.S, tj = tap - ti * a.S;
-                const float h = (float)(p - a.pad_h + ti * a.dil) + po[0];
-                const float w = (float)(q - a.pad_w + tj * a.dil) + po[1];
-                if (h > -1.f && w > -1.f && h < (float)a.H && w < (float)a.W) {
-                    const float hf = floorf(h), wf = floorf(w);
-                    const int h0 = (int)hf, w0 = (int)wf;
-                    int valid = 0;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int hy = h0 + (e >> 1), wx = w0 + (e & 1);
-                        if (hy >= 0 && hy <= a.H - 1 && wx >= 0 && wx <= a.W - 1) valid |= 1 << e;
-                    }
-                    // fast samples have their whole 2x2 footprint inside the window: corner e is window pixel
-                    // base + (e >> 1) * WW + (e & 1); the others recompute their position and go corner by corner
-                    const int ly = h0 - wy0, lx = w0 - wx0;
-                    const bool fast = ly >= 0 && ly + 1 < wa.WH && lx >= 0 && lx + 1 < wa.WW;
-                    packed = (valid << 16) | (fast ? (ly * wa.WW + lx) : GEO_SLOW);
-                    flh = h - hf; flw = w - wf;
-                    mk = a.mask[m * (a.dg * RS) + g * RS + tap];
+                s = dcn_sample(a, p, q, ti, tj, 1, po[0], po[1]);
+                if (s.valid) {
+                    mk = a.mask[dcn_mask_at(a, RS, m, g, tap)];
+                    const int ly = s.h0 - wy0, lx = s.w0 - wx0;      // (dcn_win_geo forms the same two: one pair after inlining)
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const int cy = ly + (e >> 1), cx = lx + (e & 1);
-                        if (((valid >> e) & 1) && cy >= 0 && cy < wa.WH && cx >= 0 && cx < wa.WW)
+                        if (((s.valid >> e) & 1) && cy >= 0 && cy < wa.WH && cx >= 0 && cx < wa.WW)
                             atomicAdd(dxw + (cy * wa.WW + cx) * WSTR + CW, 1);
                     }
                 }
             }
-            geo4[it] = f32x4{flh, flw, mk, __int_as_float(packed)};
+            geo4[it] = dcn_win_geo(wa, tl, s, mk);
             atomicMax(&mkmax_bits, (int)(__float_as_uint(mk) & 0x7fffffffu));      // |mask| bound of the block (non-negative floats order as ints)
         }
         __syncthreads();
@@ -1290,9 +1327,9 @@ __global__ __launch_bounds__(512) void dcn_dgrad_win_kernel(const DcnWinBwdArgs 
             const int p = y0 + r / WIN_TW, q = x0 + r % WIN_TW;
             if (p < a.P && q < a.Q) {
                 const long m = ((long)n * a.P + p) * a.Q + q;
-                wb.dmask[m * (a.dg * RS) + g * RS + tap] = red[it * 3];
-                wb.doffset[m * (2 * a.dg * RS) + g * 2 * RS + 2 * tap] = red[it * 3 + 1];
-                wb.doffset[m * (2 * a.dg * RS) + g * 2 * RS + 2 * tap + 1] = red[it * 3 + 2];
+                wb.dmask[dcn_mask_at(a, RS, m, g, tap)] = red[it * 3];
+                wb.doffset[dcn_offset_at(a, RS, m, g, tap)] = red[it * 3 + 1];
+                wb.doffset[dcn_offset_at(a, RS, m, g, tap) + 1] = red[it * 3 + 2];
             }
             red[it * 3] = 0.f; red[it * 3 + 1] = 0.f; red[it * 3 + 2] = 0.f;
         }
@@ -1629,7 +1666,8 @@ __global__ __launch_bounds__(512) void dcn_dgrad_win_kernel(const DcnWinBwdArgs 
                         // Fast samples (the whole 2x2 footprint inside the window; also samples without any valid corner:
                         // gi == 0, mask 0): BRANCH-FREE and, since round 5, MASK-FREE.  A corner outside the image reads a
                         // window pixel that was filled with zeros (its dot product is 0) and adds into a window pixel the
-                        // flush discards — no per-corner validity selects.  Two channels per packed-fp32 instruction.
+                        // flush discards — no per-corner validity selects.  Two channels per packed-fp32 instruction: w01 / w23 are
+                        // dcn_weights, and s_h / s_w below are dcn_dweights with the corner pairs factored out.
                         const float hh = 1.f - flh, hw = 1.f - flw;
                         const f32x2 wcol = {hw, flw};
                         const f32x2 w01 = wcol * hh, w23 = wcol * flh;       // corner weights (top row, bottom row)
@@ -1658,21 +1696,20 @@ __global__ __launch_bounds__(512) void dcn_dgrad_win_kernel(const DcnWinBwdArgs 
                         s_w = mk * (hh * (d[1] - d[0]) + flh * (d[3] - d[2]));
                     } else if ((gi >> 16) & 15) {
                         const int valid = (gi >> 16) & 15;
-                        const float hh = 1.f - flh, hw = 1.f - flw;
-                        const float wt[4] = {hh * hw, hh * flw, flh * hw, flh * flw};
-                        const float dhw[4] = {-hw, -flw, hw, flw};
-                        const float dww[4] = {-hh, hh, -flh, flh};
-                                                const f32x4 gs = gcol * fx4;                           // column gradient in each channel's fixed-point unit
-                        // footprint not inside the window (offset beyond the margin): position again from the offsets
+                        float wt[4], dhw[4], dww[4];
+                        dcn_weights(flh, flw, wt);
+                        dcn_dweights(flh, flw, dhw, dww);
+                        const f32x4 gs = gcol * fx4;                           // column gradient in each channel's fixed-point unit
+                        // footprint not inside the window (offset beyond the margin): position again from the offsets (only
+                        // h0 and w0 of the sample are used: the rest of dcn_sample is dead code here)
                         const int p = y0 + r / WIN_TW, q = x0 + r % WIN_TW;
-                        const float *po = a.offset + (((long)n * a.P + p) * a.Q + q) * (2 * a.dg * RS) + g_cur * 2 * RS + 2 * tap;
+                        const float *po = a.offset + dcn_offset_at(a, RS, ((long)n * a.P + p) * a.Q + q, g_cur, tap);
                         const int ti = tap / a.S, tj = tap - ti * a.S;
-                        const int h0 = (int)floorf((float)(p - a.pad_h + ti * a.dil) + po[0]);
-                        const int w0 = (int)floorf((float)(q - a.pad_w + tj * a.dil) + po[1]);
+                        const DcnSample s = dcn_sample(a, p, q, ti, tj, 1, po[0], po[1]);
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
                             if (!((valid >> e) & 1)) continue;
-                            const int hy = h0 + (e >> 1), wx = w0 + (e & 1);
+                            const int hy = s.h0 + (e >> 1), wx = s.w0 + (e & 1);
                             const int ly = hy - wy0, lx = wx - wx0;
                             const bool inwin = ly >= 0 && ly < wa.WH && lx >= 0 && lx < wa.WW;
                             f32x4 xv;
@@ -1803,14 +1840,14 @@ __global__ __launch_bounds__(512) void dcn_wgrad_win_kernel(const DcnWinWgradArg
     static_assert(!(DYDMA && F32), "the dY ring is bf16 only");
     const DcnWinArgs &wa = wb.w;
     const DcnArgs &a = wa.a;
-    constexpr int CW = 32, NT = 512, GEO_SLOW = 1 << 20, KT = 256;
+    constexpr int CW = 32, NT = 512, KT = 256;
     constexpr int HP = F32 ? 32 : 64;                          // pixels per sub-block
     constexpr int LDP = F32 ? HP + 4 : HP + 8;                 // operand row length in elements (144 B rows either way)
     constexpr int NSUB = BM / HP;
     extern __shared__ __align__(16) unsigned char smem[];
     const int npx = wa.WH * wa.WW;
     float *xw = reinterpret_cast<float *>(smem);                                    // [npx][32]
-    f32x4 *geo4 = reinterpret_cast<f32x4 *>(xw + (size_t)npx * CW);                 // [BM][RS] x {lh, lw, mask, packed corner word}: as in dcn_dgrad_win_kernel
+    f32x4 *geo4 = reinterpret_cast<f32x4 *>(xw + (size_t)npx * CW);                 // [BM][RS] x dcn_win_geo
     unsigned short *dyT = reinterpret_cast<unsigned short *>(geo4 + BM * RS);       // [256 filters][LDP pixels]
     unsigned short *colT = dyT + (DYDMA ? 8 * 6 * 512 : KT * 72);                   // [RS][32 channels][LDP pixels]; DYDMA: dyT = 8 waves x 6 slices x [16 px][32 filters]
     float *dyF = reinterpret_cast<float *>(dyT), *colF = reinterpret_cast<float *>(colT);   // F32 images, same bytes
@@ -1839,17 +1876,14 @@ __global__ __launch_bounds__(512) void dcn_wgrad_win_kernel(const DcnWinWgradArg
     f32x4 rdy[DYDMA ? 1 : PG];
     auto issue_dy = [&](int tile, int sub) {                 // PG pixels x 4 filters, a 1 KB row segment per wave and pixel
         if constexpr (DYDMA) return;
-        int bid = tile;
-        const int txi = bid % wa.tiles_x; bid /= wa.tiles_x;
-        const int tyi = bid % wa.tiles_y;
-        const int n = bid / wa.tiles_y;
+        const DcnTile tl = dcn_tile(wa, tile);
         const int r0 = sub * HP + PG * pg;
-        const int p = tyi * WIN_TH + r0 / WIN_TW, q0 = txi * WIN_TW + r0 % WIN_TW;
+        const int p = tl.y0 + r0 / WIN_TW, q0 = tl.x0 + r0 % WIN_TW;
         const int f = k0 + 4 * fq;
 #pragma unroll
         for (int i = 0; i < (DYDMA ? 1 : PG); ++i)
             rdy[i] = *reinterpret_cast<const f32x4 *>((p < a.P && q0 + i < a.Q && f < a.K)
-                                                          ? wb.dy + (((long)n * a.P + p) * a.Q + q0 + i) * a.K + f : a.zero);
+                                                          ? wb.dy + (((long)tl.n * a.P + p) * a.Q + q0 + i) * a.K + f : a.zero);
     };
     auto commit_dy = [&]() {
         if constexpr (DYDMA) return;
@@ -1882,33 +1916,27 @@ __global__ __launch_bounds__(512) void dcn_wgrad_win_kernel(const DcnWinWgradArg
     const int wv = __builtin_amdgcn_readfirstlane(wave);
     constexpr int GI = (BM * RS + NT - 1) / NT;            // geometry items per thread (3)
     float g_oh[GI], g_ow[GI], g_mk[GI];                    // offsets and mask of the next block's items, loaded under the MFMAs
-    auto prepare_issue = [&](int tl) {
-        int bid = tl;
-        const int txi = bid % wa.tiles_x; bid /= wa.tiles_x;
-        const int tyi = bid % wa.tiles_y;
-        const int n = bid / wa.tiles_y;
-        const int y0 = tyi * WIN_TH, x0 = txi * WIN_TW;
-        const int wy0 = y0 - a.pad_h - wa.RW, wx0 = x0 - a.pad_w - wa.RW;
-        const long img = (long)n * a.H * a.W;
+    auto prepare_issue = [&](int tile) {
+        const DcnTile tl = dcn_tile(wa, tile);
         if (wb.dma_window) {
             for (int piece = wv; piece * 8 < npx; piece += 8) {
                 const int px = piece * 8 + (lane >> 3);
                 if (px < npx) {                                  // lanes past the window's last pixel stay out (exec mask)
                     const int ly = px / wa.WW, lx = px - ly * wa.WW;
-                    const int gy = wy0 + ly, gx = wx0 + lx;
+                    const int gy = tl.wy0 + ly, gx = tl.wx0 + lx;
                     const bool ok = gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
                     dma16(rs_x, __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_void *)(xw + piece * 256)),
-                          ok ? (unsigned)(((img + (long)gy * a.W + gx) * a.C) * 4) + (unsigned)(lane & 7) * 16u : 0x80000000u, (unsigned)(c0 * 4));
+                          ok ? (unsigned)(((tl.img + (long)gy * a.W + gx) * a.C) * 4) + (unsigned)(lane & 7) * 16u : 0x80000000u, (unsigned)(c0 * 4));
                 }
             }
         } else {
             for (int i = t; i < npx * 8; i += NT) {
                 const int px = i >> 3, c4 = (i & 7) * 4;
                 const int ly = px / wa.WW, lx = px - ly * wa.WW;
-                const int gy = wy0 + ly, gx = wx0 + lx;
+                const int gy = tl.wy0 + ly, gx = tl.wx0 + lx;
                 const bool ok = gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
                 *reinterpret_cast<f32x4 *>(xw + (size_t)i * 4) =
-                    *reinterpret_cast<const f32x4 *>(ok ? a.x + (img + (long)gy * a.W + gx) * a.C + c0 + c4 : a.zero);
+                    *reinterpret_cast<const f32x4 *>(ok ? a.x + (tl.img + (long)gy * a.W + gx) * a.C + c0 + c4 : a.zero);
             }
         }
         if constexpr (DYDMA)        // (the other variants read them in prepare_finish, which follows at once: no registers to park them)
@@ -1916,60 +1944,39 @@ __global__ __launch_bounds__(512) void dcn_wgrad_win_kernel(const DcnWinWgradArg
         for (int i = 0; i < GI; ++i) {
             const int it = t + i * NT;
             const int r = it / RS, tap = it - r * RS;
-            const int p = y0 + r / WIN_TW, q = x0 + r % WIN_TW;
+            const int p = tl.y0 + r / WIN_TW, q = tl.x0 + r % WIN_TW;
             g_oh[i] = 0.f; g_ow[i] = 0.f; g_mk[i] = 0.f;
             if (it < BM * RS && p < a.P && q < a.Q) {
-                const long m = ((long)n * a.P + p) * a.Q + q;
-                const float *po = a.offset + m * (2 * a.dg * RS) + g * 2 * RS + 2 * tap;
+                const long m = ((long)tl.n * a.P + p) * a.Q + q;
+                const float *po = a.offset + dcn_offset_at(a, RS, m, g, tap);
                 g_oh[i] = po[0]; g_ow[i] = po[1];
-                g_mk[i] = a.mask[m * (a.dg * RS) + g * RS + tap];
+                g_mk[i] = a.mask[dcn_mask_at(a, RS, m, g, tap)];
             }
         }
     };
-    auto prepare_finish = [&](int tl) {
-        int bid = tl;
-        const int txi = bid % wa.tiles_x; bid /= wa.tiles_x;
-        const int tyi = bid % wa.tiles_y;
-        const int y0 = tyi * WIN_TH, x0 = txi * WIN_TW;
-        const int wy0 = y0 - a.pad_h - wa.RW, wx0 = x0 - a.pad_w - wa.RW;
-        const int n = bid / wa.tiles_y;
+    auto prepare_finish = [&](int tile) {
+        const DcnTile tl = dcn_tile(wa, tile);
 #pragma unroll(DYDMA ? GI : 1)
         for (int i = 0; i < GI; ++i) {
             const int it = t + i * NT;
             if (it >= BM * RS) continue;
             const int r = it / RS, tap = it - r * RS;
-            const int p = y0 + r / WIN_TW, q = x0 + r % WIN_TW;
-            int packed = 0;
-            float flh = 0.f, flw = 0.f, mk = 0.f;
+            const int p = tl.y0 + r / WIN_TW, q = tl.x0 + r % WIN_TW;
+            DcnSample s{};
+            float mk = 0.f;
             if (p < a.P && q < a.Q) {
                 const int ti = tap / a.S, tj = tap - ti * a.S;
-                float oh, ow, omk;
-                if constexpr (DYDMA) { oh = g_oh[i]; ow = g_ow[i]; omk = g_mk[i]; }
+                float oh, ow;
+                if constexpr (DYDMA) { oh = g_oh[i]; ow = g_ow[i]; mk = g_mk[i]; }
                 else {
-                    const long m = ((long)n * a.P + p) * a.Q + q;
-                    const float *po = a.offset + m * (2 * a.dg * RS) + g * 2 * RS + 2 * tap;
+                    const long m = ((long)tl.n * a.P + p) * a.Q + q;
+                    const float *po = a.offset + dcn_offset_at(a, RS, m, g, tap);
                     oh = po[0]; ow = po[1];
-                    omk = a.mask[m * (a.dg * RS) + g * RS + tap];
+                    mk = a.mask[dcn_mask_at(a, RS, m, g, tap)];
                 }
-                const float h = (float)(p - a.pad_h + ti * a.dil) + oh;
-                const float w = (float)(q - a.pad_w + tj * a.dil) + ow;
-                if (h > -1.f && w > -1.f && h < (float)a.H && w < (float)a.W) {
-                    const float hf = floorf(h), wf = floorf(w);
-                    const int h0 = (int)hf, w0 = (int)wf;
-                    int valid = 0;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int hy = h0 + (e >> 1), wx = w0 + (e & 1);
-                        if (hy >= 0 && hy <= a.H - 1 && wx >= 0 && wx <= a.W - 1) valid |= 1 << e;
-                    }
-                    const int ly = h0 - wy0, lx = w0 - wx0;
-                    const bool fast = ly >= 0 && ly + 1 < wa.WH && lx >= 0 && lx + 1 < wa.WW;
-                    packed = (valid << 16) | (fast ? (ly * wa.WW + lx) : GEO_SLOW);
-                    flh = h - hf; flw = w - wf;
-                    mk = omk;
-                }
+                s = dcn_sample(a, p, q, ti, tj, 1, oh, ow);
             }
-            geo4[it] = f32x4{flh, flw, mk, __int_as_float(packed)};
+            geo4[it] = dcn_win_geo(wa, tl, s, mk);
         }
     };
 
@@ -1980,13 +1987,10 @@ __global__ __launch_bounds__(512) void dcn_wgrad_win_kernel(const DcnWinWgradArg
                       __builtin_amdgcn_readfirstlane((int)((long)a.M * a.K * 2)), 0x00020000};
     }();
     unsigned short *const ring = dyT + wv * (6 * 512);
-    auto issue_slice = [&](int tl, int sub, int kk, int slot) {
-        int bid = tl;
-        const int txi = bid % wa.tiles_x; bid /= wa.tiles_x;
-        const int tyi = bid % wa.tiles_y;
-        const int n = bid / wa.tiles_y;
-        const int p = tyi * WIN_TH + sub * (HP / WIN_TW) + kk, q = txi * WIN_TW + (lane >> 2);
-        const unsigned off = (p < a.P && q < a.Q) ? (unsigned)(((((long)n * a.P + p) * a.Q + q) * a.K + (lane & 3) * 8) * 2) : 0x80000000u;
+    auto issue_slice = [&](int tile, int sub, int kk, int slot) {
+        const DcnTile tl = dcn_tile(wa, tile);
+        const int p = tl.y0 + sub * (HP / WIN_TW) + kk, q = tl.x0 + (lane >> 2);
+        const unsigned off = (p < a.P && q < a.Q) ? (unsigned)(((((long)tl.n * a.P + p) * a.Q + q) * a.K + (lane & 3) * 8) * 2) : 0x80000000u;
         dma16(rs_dy, __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_void *)(ring + slot * 512)), off, (unsigned)((k0 + wv * 32) * 2));
     };
     int slot = 0;                                            // ring slot of the current sub-block's first slice
@@ -2000,12 +2004,7 @@ __global__ __launch_bounds__(512) void dcn_wgrad_win_kernel(const DcnWinWgradArg
         }
     }
     for (; tile < ntiles; tile += wb.splits) {
-        int bid = tile;
-        const int txi = bid % wa.tiles_x; bid /= wa.tiles_x;
-        const int tyi = bid % wa.tiles_y;
-        const int n = bid / wa.tiles_y;
-        const int y0 = tyi * WIN_TH, x0 = txi * WIN_TW;
-        const long img = (long)n * a.H * a.W;
+        const DcnTile tl = dcn_tile(wa, tile);
         for (int half = 0; half < NSUB; ++half) {
             if (half == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's window pieces landed
             __syncthreads();                                 // window + geometry visible; dyT / colT free again
@@ -2022,24 +2021,23 @@ __global__ __launch_bounds__(512) void dcn_wgrad_win_kernel(const DcnWinWgradArg
                 f32x4 v = {0.f, 0.f, 0.f, 0.f};
                 if (valid) {
                     const float flh = gq[0], flw = gq[1], mk = gq[2];
-                    const float hh = 1.f - flh, hw = 1.f - flw;
-                    const float wt[4] = {hh * hw * mk, hh * flw * mk, flh * hw * mk, flh * flw * mk};     // as make_tap: the forward's samples exactly
+                    float wt[4];
+                    dcn_weights(flh, flw, wt);          // x mk below, as make_tap: the forward's samples exactly
                     if (!(gi & GEO_SLOW)) {
                         // a corner outside the image reads a window pixel filled with zeros: no validity selects (adding
                         // weight x 0 leaves the forward's sum bit for bit)
                         const float *xb = xw + (size_t)(gi & 0xffff) * CW + a_col;
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) v += *reinterpret_cast<const f32x4 *>(xb + ((e >> 1) * wa.WW + (e & 1)) * CW) * wt[e];
+                        for (int e = 0; e < 4; ++e) v += *reinterpret_cast<const f32x4 *>(xb + ((e >> 1) * wa.WW + (e & 1)) * CW) * (wt[e] * mk);
                     } else {
-                        const int p = y0 + r / WIN_TW, q = x0 + r % WIN_TW;
-                        const float *po = a.offset + (((long)n * a.P + p) * a.Q + q) * (2 * a.dg * RS) + g * 2 * RS + 2 * tap;
+                        const int p = tl.y0 + r / WIN_TW, q = tl.x0 + r % WIN_TW;
+                        const float *po = a.offset + dcn_offset_at(a, RS, ((long)tl.n * a.P + p) * a.Q + q, g, tap);
                         const int ti = tap / a.S, tj = tap - ti * a.S;
-                        const int h0 = (int)floorf((float)(p - a.pad_h + ti * a.dil) + po[0]);
-                        const int w0 = (int)floorf((float)(q - a.pad_w + tj * a.dil) + po[1]);
+                        const DcnSample s = dcn_sample(a, p, q, ti, tj, 1, po[0], po[1]);      // (for h0 and w0 only, as in dcn_dgrad_win_kernel)
 #pragma unroll
                         for (int e = 0; e < 4; ++e)
                             if ((valid >> e) & 1)
-                                v += *reinterpret_cast<const f32x4 *>(a.x + (img + (long)(h0 + (e >> 1)) * a.W + w0 + (e & 1)) * a.C + c0 + a_col) * wt[e];
+                                v += *reinterpret_cast<const f32x4 *>(a.x + (tl.img + (long)(s.h0 + (e >> 1)) * a.W + s.w0 + (e & 1)) * a.C + c0 + a_col) * (wt[e] * mk);
                     }
                 }
                 if constexpr (F32) {
