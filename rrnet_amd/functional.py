@@ -918,6 +918,32 @@ def se_scale_res_relu(u, fc1_weight, fc2_weight, skip, reduction=16):
     return _SEScaleResRelu.apply(u, fc1_weight, fc2_weight, skip, acc)
 
 
+class _WindowAttention(torch.autograd.Function):
+    """softmax over a pixel's dilated window of q . k, weighing v: the unfold chain of modules/self_attention.py:67-91 in
+    three launches (csrc/attn.hip).  The softmax weights are stashed for the backward."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, kernel_size, dilation, padding):
+        q, k, v = ops.to_nhwc(q), ops.to_nhwc(k), ops.to_nhwc(v)
+        out, p = ops.window_attention_fwd(q, k, v, kernel_size, dilation, padding)
+        ctx.save_for_backward(q, k, v, p)
+        ctx.geom = (kernel_size, dilation, padding)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, p = ctx.saved_tensors
+        dq, dk, dv = ops.window_attention_bwd(ops.to_nhwc(dout), q, k, v, p, *ctx.geom)
+        need = ctx.needs_input_grad
+        return (dq if need[0] else None, dk if need[1] else None, dv if need[2] else None, None, None, None)
+
+
+def window_attention(q, k, v, kernel_size, dilation=1, padding=0):
+    """q, k [n, ck, h, w], v [n, cv, h, w] -> context [n, cv, oh, ow] (stride 1; ops.window_attention_geometry), fp32."""
+    kk, d, p, _, _ = ops.window_attention_geometry(q.shape[2], q.shape[3], kernel_size, dilation, padding)
+    return _WindowAttention.apply(q, k, v, kk, d, p)
+
+
 class _BilinearAdd(torch.autograd.Function):
     """F.interpolate(x, size(y), mode='bilinear', align_corners=False) + y  (modules/fpn.py:39-40)."""
 

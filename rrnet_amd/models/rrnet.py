@@ -15,7 +15,7 @@ from rrnet_amd import ops
 from rrnet_amd.detectors.centernet_detector import CenterNetDetector, CenterNetWHDetector
 from rrnet_amd.detectors.fasterrcnn_detector import FasterRCNNDetector
 from rrnet_amd.ext.nms.nms_wrapper import soft_nms_segments
-from rrnet_amd.utils.model_tools import get_backbone, refuse_bf16
+from rrnet_amd.utils.model_tools import build_attention, get_backbone, refuse_bf16
 
 
 def stage1_proposals(hm, wh, offset, k, num_classes, nms_type='nms', nms_per_class=True, peak_filter=False,
@@ -70,6 +70,9 @@ class RRNet(nn.Module):
         # BatchNorm statistics, losses and the optimizer stay fp32
         # cfg.Model.conv_math = "f16x3": split-operand kernels (two fp16 parts per operand, fp32-level accuracy; ops.math_mode)
         self.bf16 = ops.math_mode(cfg.Model)
+        # builder-defined option cfg.Model.attention: a zero-initialised SelfAttentionModule per stack in front of the stage-1
+        # heads; constructed last, so every other parameter draws what it drew without it
+        self.attention = build_attention(cfg.Model, self.num_stacks)
 
     def forward(self, x, k=1500):
         with ops.bf16_scope(self.bf16):
@@ -95,7 +98,7 @@ class RRNet(nn.Module):
 
     def forward_stage1(self, feats):
         from rrnet_amd.models.centernet import run_stage1_heads
-        return run_stage1_heads(feats, (self.hm, self.wh, self.offset_reg), self.num_stacks)
+        return run_stage1_heads(feats, (self.hm, self.wh, self.offset_reg), self.num_stacks, self.attention)
 
     def forward_stage2(self, feats):
         return self.head_detector(feats)

@@ -83,11 +83,12 @@ TIMER = None
 SYNC_WAIT_S = 0.0      # host time spent blocked in the RoI-count read (bench.py separates it from the enqueue time)
 
 
-def _launch(key, flops, entry, args, detail=None, nbytes=0.0):
-    """Entry point `entry` on `args` (_C.call), under the timer key `key` when a timer is on: it is reached inside the timer's fn()."""
+def _launch(key, flops, entry, args, detail=None, nbytes=0.0, call=_C.call):
+    """Entry point `entry` on `args` (_C.call, or a companion header's Family.call), under the timer key `key` when a timer is
+    on: it is reached inside the timer's fn()."""
     if TIMER is None:
-        return _C.call(entry, *args)
-    return TIMER.launch(key, flops, lambda: _C.call(entry, *args), detail, nbytes)
+        return call(entry, *args)
+    return TIMER.launch(key, flops, lambda: call(entry, *args), detail, nbytes)
 
 
 _SMALL_TILES = 16
@@ -2476,6 +2477,71 @@ def maxpool2x2_bwd(dy, idx, x_shape):
     dx = empty_nhwc(n, c, h, w, dy.device)
     _SE.call("rr_maxpool2x2_bwd", dy, idx, dx, n, h, w, c)
     return dx
+
+
+# ---------------------------------------------------------------------------------------------
+# Dilated-window attention (csrc/attn.hip): the unfold / softmax / weighted-sum chain of modules/self_attention.py
+# ---------------------------------------------------------------------------------------------
+_ATTN = _C.Family("rrnet_hip_attn.h")   # the family's own header beside include/rrnet_hip.h
+ATTN_MAX_TAPS = 64
+
+
+def _pair(v):
+    return (int(v[0]), int(v[1])) if isinstance(v, (tuple, list)) else (int(v), int(v))
+
+
+def window_attention_geometry(h, w, kernel_size, dilation, padding):
+    """-> ((kh, kw), (dh, dw), (ph, pw), (oh, ow), (cy, cx)): the output size of the stride-1 window and the offset of an
+    output's query position (modules/self_attention.py:58-60, :84)."""
+    k, d, p = _pair(kernel_size), _pair(dilation), _pair(padding)
+    out = tuple(s + 2 * p[i] - d[i] * (k[i] - 1) for i, s in enumerate((h, w)))
+    centre = tuple(d[i] * (k[i] // 2) - p[i] for i in range(2))
+    return k, d, p, out, centre
+
+
+def _attn_launch(entry, flops, nbytes, *args):
+    return _launch(entry[3:], flops, entry, args, nbytes=nbytes, call=_ATTN.call)
+
+
+def _attn_dims(q, k, v, kernel_size, dilation, padding):
+    assert is_nhwc(q) and is_nhwc(k) and is_nhwc(v) and q.dtype == k.dtype == v.dtype == torch.float32
+    n, ck, h, w = q.shape
+    cv = v.shape[1]
+    assert k.shape == q.shape and tuple(v.shape) == (n, cv, h, w)
+    kk, d, p, out, _ = window_attention_geometry(h, w, kernel_size, dilation, padding)
+    return (n, h, w, ck, cv) + kk + d + p, out, kk[0] * kk[1]
+
+
+def window_attention_fwd(q, k, v, kernel_size, dilation, padding):
+    """q, k NHWC [n,ck,h,w], v NHWC [n,cv,h,w] -> (ctx NHWC [n,cv,oh,ow], p [n,oh,ow,T]): the softmax over a pixel's T window
+    taps of q . k (a padded tap: logit 0, value 0) and the context it weighs out of v."""
+    _C.require_cuda(q, k, v)
+    dims, (oh, ow), taps = _attn_dims(q, k, v, kernel_size, dilation, padding)
+    n, h, w, ck, cv = dims[:5]
+    # (a geometry the entry refuses gets placeholders of one element: the refusal comes from the library, before any launch)
+    ok = oh >= 1 and ow >= 1
+    ctx = empty_nhwc(n, cv, max(oh, 1), max(ow, 1), q.device)
+    p = torch.empty((n, max(oh, 1), max(ow, 1), taps), dtype=torch.float32, device=q.device)
+    px = n * oh * ow if ok else 0
+    _attn_launch("rr_attn_fwd", 2.0 * px * taps * (ck + cv), 4.0 * (n * h * w * (2 * ck + cv) + px * (cv + taps)),
+                 q, k, v, ctx, p, *dims)
+    return ctx, p
+
+
+def window_attention_bwd(dctx, q, k, v, p, kernel_size, dilation, padding):
+    """-> (dq, dk, dv), each written whole (a query position no output reads: 0)."""
+    dims, (oh, ow), taps = _attn_dims(q, k, v, kernel_size, dilation, padding)
+    n, h, w, ck, cv = dims[:5]
+    assert is_nhwc(dctx) and dctx.dtype == torch.float32 and tuple(dctx.shape) == (n, cv, oh, ow)
+    assert tuple(p.shape) == (n, oh, ow, taps) and p.is_contiguous() and p.dtype == torch.float32
+    ds = torch.empty_like(p)
+    dq, dk, dv = empty_nhwc(*q.shape, device=q.device), empty_nhwc(*k.shape, device=q.device), empty_nhwc(*v.shape, device=q.device)
+    px, mp = n * oh * ow, n * h * w
+    _attn_launch("rr_attn_bwd_q", 2.0 * px * taps * (ck + cv), 4.0 * (mp * (2 * ck + cv) + px * (cv + 2 * taps)),
+                 dctx, v, k, p, ds, dq, *dims)
+    _attn_launch("rr_attn_bwd_kv", 2.0 * px * taps * (ck + cv), 4.0 * (mp * (2 * ck + cv) + px * (cv + 2 * taps)),
+                 ds, p, q, dctx, dk, dv, *dims)
+    return dq, dk, dv
 
 
 class _OpsModule(types.ModuleType):

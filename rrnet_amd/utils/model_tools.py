@@ -35,3 +35,37 @@ def refuse_bf16(model_cfg):
         raise NotImplementedError(
             "cfg.Model.bf16 / conv_math = 'bf16' is not built for backbone %r: its skip sums and its squeeze would read "
             "bf16-only activations (use fp32 or cfg.Model.conv_math = 'f16x3')" % (model_cfg.backbone,))
+
+
+def build_attention(model_cfg, num_stacks, in_channels=256):
+    """cfg.Model.attention (builder-defined; absent or None: no attention, None is returned): a dict of SelfAttentionModule
+    keyword arguments -> one module per stack, applied to the feature the stage-1 heads read (models/centernet.run_stage1_heads).
+    `in_channels` defaults to the backbones' 256 features.  Refused together with cfg.Model.bf16 / conv_math = "bf16": the window
+    kernels read fp32 tensors and the block's sum with a bf16-only feature has no tested rule; fp32 and conv_math = "f16x3" (the
+    convolutions only) are supported."""
+    import torch.nn as nn
+
+    from rrnet_amd import ops
+    from rrnet_amd.modules.self_attention import SelfAttentionModule
+    kwargs = getattr(model_cfg, "attention", None)
+    if kwargs is None:
+        return None
+    if ops.math_mode(model_cfg) == ops.MATH_BF16:
+        raise NotImplementedError(
+            "cfg.Model.attention is not built for cfg.Model.bf16 / conv_math = 'bf16': the window-attention kernels are fp32 "
+            "(use fp32 or cfg.Model.conv_math = 'f16x3')")
+    kwargs = dict(kwargs)
+    kwargs.setdefault("in_channels", in_channels)
+    modules = [SelfAttentionModule(**kwargs) for _ in range(num_stacks)]
+    for m in modules:
+        m.check_supported()
+        if m.out_channels != kwargs["in_channels"]:
+            raise ValueError("cfg.Model.attention: out_channels = %d, the residual sum needs the feature's %d"
+                             % (m.out_channels, kwargs["in_channels"]))
+    return nn.ModuleList(modules)
+
+
+def attention_kwargs(kernel_size, dilation, channels=64):
+    """The --attention K DIL of tools/train.py and tools/detect.py -> cfg.Model.attention."""
+    return dict(key_channels=channels, value_channels=channels, kernel_size=int(kernel_size), dilation=int(dilation),
+                padding=int(dilation) * (int(kernel_size) // 2))

@@ -2,13 +2,14 @@
 
   python tools/detect.py --checkpoint ckp-89999.pth --images DIR --out DIR [--config rrnet_config] [--batch 4]
                          [--scales 1,1.1,1.2,1.3,1.4,1.5] [--raw | --nms] [--bf16] [--flip | --no-flip]
-                         [--random-weights]
+                         [--random-weights] [--attention K DIL]
 
 Frames are decoded in threads, grouped by size, uploaded as uint8 and run `--batch` at a time through
 rrnet_amd.inference.detect_frames; every image gets `<out>/<name>.txt` with the lines `x,y,w,h,score,cls,-1,-1` that
 RRNetOperator.save_result writes (utils/metrics reads them).  --raw keeps every box of every scale (the config's
 auto_test=True, for a later threshold sweep); --nms filters by score and runs the per-class Soft-NMS (auto_test=False);
 without either the config decides.  --random-weights runs without a checkpoint (a smoke run: the boxes mean nothing).
+--attention K DIL builds the model with cfg.Model.attention as tools/train.py --attention K DIL trained it (RRNet, CenterNet; fp32).
 
 --config centernet_config runs CenterNet through rrnet_amd.inference.detect_frames_centernet and writes the integer lines
 of CenterNetOperator.save_result.  Every scale is run flipped and plain in one model pass, as the reference's evaluation
@@ -107,6 +108,8 @@ def main(argv=None):
     ap.add_argument("--tile-zoom", type=float, help="resize every tile by this factor in front of the model (default 1)")
     ap.add_argument("--tile-margin", type=float, help="drop boxes within this many input pixels of a cutting tile side (default 0)")
     ap.add_argument("--tile-batch", type=int, help="tiles per model pass (default 8)")
+    ap.add_argument("--attention", type=int, nargs=2, metavar=("K", "DIL"),
+                    help="RRNet, CenterNet: the model carries tools/train.py's --attention K DIL block (cfg.Model.attention)")
     ap.add_argument("--host-text", action="store_true",
                     help="format the result files on the host (write_results) instead of on the device (rrnet_amd/textio.py)")
     args = ap.parse_args(argv)
@@ -123,6 +126,13 @@ def main(argv=None):
     if args.tile is None and any(v is not None for v in tile_options):
         raise SystemExit("--tile-overlap / --tile-zoom / --tile-margin / --tile-batch need --tile")
     args.tile = parse_tile(args)
+    if args.attention is not None:
+        if retinanet:
+            raise SystemExit("--attention: the block sits in front of the stage-1 heads of RRNet and CenterNet")
+        if args.bf16:
+            raise SystemExit("--attention: the window-attention kernels are fp32 (drop --bf16)")
+        from rrnet_amd.utils.model_tools import attention_kwargs
+        cfg.Model.attention = attention_kwargs(*args.attention)
     if retinanet:
         return main_retinanet(args, cfg)
     args.flip = True if args.flip is None else args.flip

@@ -4,7 +4,7 @@
                         [--batch B] [--crop H W] [--backbone NAME] [--bf16] [--full-state] [--resume auto|PATH]
                         [--checkpoint-interval N] [--print-interval N] [--keep-states N] [--color-jitter B C S]
                         [--clip-grad-norm X] [--skip-nonfinite] [--ema DECAY] [--no-ema-warmup] [--warmup ITERS]
-                        [--warmup-factor F]
+                        [--warmup-factor F] [--attention K DIL]
 
 A single process: it sets the config keys and calls the operator's training_process().  Without a dataset under
 --data-root the synthetic loader feeds the loop.  `ckp-{step}.pth` (weights, the reference's format) goes to
@@ -16,7 +16,9 @@ as the reference's): brightness, contrast and saturation factors from [max(1 - x
 --clip-grad-norm X clips the gradient's global norm to X, --skip-nonfinite drops a step whose gradient holds a NaN or an Inf,
 --ema DECAY keeps averaged weights and writes `ckp-ema-{step}.pth` beside each checkpoint (--no-ema-warmup: the full decay
 from the first step); all three are decided on the device inside the optimiser step.  --warmup ITERS puts the
-reference's linear learning-rate warm-up (from --warmup-factor F, default 1/3, of the rate) in front of the milestones."""
+reference's linear learning-rate warm-up (from --warmup-factor F, default 1/3, of the rate) in front of the milestones.
+--attention K DIL (RRNet, CenterNet; fp32) puts a zero-initialised SelfAttentionModule (K x K window at dilation DIL, 64 key
+and value channels, padding DIL * (K // 2)) per stack in front of the stage-1 heads: cfg.Model.attention (DESIGN §22)."""
 import argparse
 import copy
 import importlib
@@ -56,6 +58,7 @@ def parse(argv=None):
     ap.add_argument("--no-ema-warmup", action="store_true")
     ap.add_argument("--warmup", type=int, metavar="ITERS")
     ap.add_argument("--warmup-factor", type=float, metavar="F")
+    ap.add_argument("--attention", type=int, nargs=2, metavar=("K", "DIL"))
     return ap.parse_args(argv)
 
 
@@ -86,6 +89,13 @@ def configure(args):
         cfg.Model.backbone = args.backbone
     if args.bf16:
         cfg.Model.bf16 = True
+    if args.attention is not None:
+        if args.config.startswith("retinanet"):
+            raise SystemExit("--attention: the block sits in front of the stage-1 heads of RRNet and CenterNet")
+        if args.bf16:
+            raise SystemExit("--attention: the window-attention kernels are fp32 (drop --bf16)")
+        from rrnet_amd.utils.model_tools import attention_kwargs
+        cfg.Model.attention = attention_kwargs(*args.attention)
     if args.checkpoint_interval is not None:
         cfg.Train.checkpoint_interval = args.checkpoint_interval
     if args.print_interval is not None:
