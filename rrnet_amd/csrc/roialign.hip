@@ -36,8 +36,9 @@ __device__ __forceinline__ Tap make_tap(float y, float x, int H, int W, long C)
 }
 
 // Sample position start + p * bin + (i + 0.5) * bin / g with every operation rounded on its own, as the reference's
-// CPU definition evaluates it: an FMA-contracted start + p * bin moves samples by an ulp, which the backward's bilinear
-// weights turn into gradient errors of |dout| * ulp(position).
+// CPU definition evaluates it: an FMA-contracted start + p * bin moves samples by an ulp, which the bilinear weights
+// turn into errors of |slope of the map| * ulp(position) forward (2e-5 at 7 bins on an N(0,1) map, where the fp32
+// definition is 4e-7 from fp64) and |dout| * ulp(position) backward.  Every kernel of this file takes its positions here.
 __device__ __forceinline__ float sample_pos(float start, int p, float bin, int i, int g)
 {
 #pragma clang fp contract(off)
@@ -101,13 +102,13 @@ struct AxisW {
     int base[SEP_MAXBINS], n[SEP_MAXBINS];
 };
 
-// weights of one bin along one axis: `start` = roi start + bin * bin_size, g samples, map extent `size`
-__device__ void axis_weights(float start, float bin, int g, int size, float *w, int *base_out, int *n_out)
+// weights of bin p along one axis: `start` = roi start, g samples per bin, map extent `size`
+__device__ void axis_weights(float start, int p, float bin, int g, int size, float *w, int *base_out, int *n_out)
 {
     for (int i = 0; i < SEP_SLOTS; ++i) w[i] = 0.f;
     int base = -1, last = -1;
     for (int i = 0; i < g; ++i) {
-        float y = start + ((float)i + 0.5f) * bin / (float)g;
+        float y = sample_pos(start, p, bin, i, g);
         if (y < -1.0f || y > (float)size) continue;
         if (y <= 0.f) y = 0.f;
         int yl = (int)y, yh;
@@ -140,10 +141,10 @@ __global__ __launch_bounds__(256) void roi_align_sep_kernel(const float *feat, c
     // adaptive sampling, g = ceil(bin size))
     const bool sep = gh <= SEP_MAXG && gw <= SEP_MAXG && bh <= (float)gh && bw <= (float)gw;
     if (sep) {
-        if (lane < PH) axis_weights(y1 + lane * bh, bh, gh, H, ay[wave].w[lane], &ay[wave].base[lane], &ay[wave].n[lane]);
+        if (lane < PH) axis_weights(y1, lane, bh, gh, H, ay[wave].w[lane], &ay[wave].base[lane], &ay[wave].n[lane]);
         else if (lane < PH + PW) {
             const int p = lane - PH;
-            axis_weights(x1 + p * bw, bw, gw, W, ax[wave].w[p], &ax[wave].base[p], &ax[wave].n[p]);
+            axis_weights(x1, p, bw, gw, W, ax[wave].w[p], &ax[wave].base[p], &ax[wave].n[p]);
         }
     }
     __syncthreads();
@@ -156,9 +157,9 @@ __global__ __launch_bounds__(256) void roi_align_sep_kernel(const float *feat, c
                 const int ph = bin / PW, pw = bin % PW;
                 f32x4 acc = {0.f, 0.f, 0.f, 0.f};
                 for (int iy = 0; iy < gh; ++iy) {
-                    const float y = y1 + ph * bh + ((float)iy + 0.5f) * bh / (float)gh;
+                    const float y = sample_pos(y1, ph, bh, iy, gh);
                     for (int ix = 0; ix < gw; ++ix) {
-                        const float x = x1 + pw * bw + ((float)ix + 0.5f) * bw / (float)gw;
+                        const float x = sample_pos(x1, pw, bw, ix, gw);
                         const Tap t = make_tap(y, x, H, W, C);
                         if (!t.ok) continue;
                         const float *f = img + c0;
@@ -231,10 +232,10 @@ __global__ __launch_bounds__(256) void roi_align_3x3_kernel(const float *feat, c
     const int gw = sampling > 0 ? sampling : (int)ceilf(rw / 3.f);
     const bool sep = gh <= SEP_MAXG && gw <= SEP_MAXG && bh <= (float)gh && bw <= (float)gw;
     if (sep) {
-        if (lane < 3) axis_weights(y1 + lane * bh, bh, gh, H, ty[wave].w[lane], &ty[wave].base[lane], &ty[wave].n[lane]);
+        if (lane < 3) axis_weights(y1, lane, bh, gh, H, ty[wave].w[lane], &ty[wave].base[lane], &ty[wave].n[lane]);
         else if (lane < 6) {
             const int p = lane - 3;
-            axis_weights(x1 + p * bw, bw, gw, W, tx[wave].w[p], &tx[wave].base[p], &tx[wave].n[p]);
+            axis_weights(x1, p, bw, gw, W, tx[wave].w[p], &tx[wave].base[p], &tx[wave].n[p]);
         }
     }
     __syncthreads();
@@ -261,9 +262,9 @@ __global__ __launch_bounds__(256) void roi_align_3x3_kernel(const float *feat, c
                 const int ph = bin / 3, pw = bin % 3;
                 f32x4 acc = {0.f, 0.f, 0.f, 0.f};
                 for (int iy = 0; iy < gh; ++iy) {
-                    const float y = y1 + ph * bh + ((float)iy + 0.5f) * bh / (float)gh;
+                    const float y = sample_pos(y1, ph, bh, iy, gh);
                     for (int ix = 0; ix < gw; ++ix) {
-                        const float x = x1 + pw * bw + ((float)ix + 0.5f) * bw / (float)gw;
+                        const float x = sample_pos(x1, pw, bw, ix, gw);
                         const Tap t = make_tap(y, x, H, W, C);
                         if (!t.ok) continue;
                         const float *f = img + c0;

@@ -279,7 +279,7 @@ ROI_DYADIC_BINS_SR2 = (0.625, 1.75, 2.5, 3.5, 5.25, 15.5)
 def roi_dyadic_set(seed, out_size, sampling_ratio, spatial_scale, height, width, n=40, race=500):
     """rois [K,5] float32 (input coordinates: feature units / spatial_scale) on images 0 and 1 of a batch of 3 (image 2
     is never touched): n random dyadic RoIs, partly outside the map, two entirely outside it, and `race` identical RoIs
-    over one ~6x6 patch of image 1 (the backward's atomics race on its pixels)."""
+    over one ~6x6 patch of image 1 (the backward's atomics race on its pixels; race=0: none, any number of bins)."""
     rng = np.random.default_rng(seed)
     ph, pw = out_size
     rows = []
@@ -293,9 +293,10 @@ def roi_dyadic_set(seed, out_size, sampling_ratio, spatial_scale, height, width,
         rows.append([rng.integers(0, 2), x1, y1, x1 + pw * bx, y1 + ph * by])
     rows.append([0, -40.0, -40.0, -40.0 + pw * 1.75, -40.0 + ph * 1.75])           # every sample < -1
     rows.append([1, width + 2.0, 1.0, width + 2.0 + pw * 1.75, 1.0 + ph * 1.75])     # every sample > W
-    ry = max(b for b in (0.875, 1.0, 1.75, 2.0) if ph * b <= 6.25)
-    rx = max(b for b in (0.875, 1.0, 1.75, 2.0) if pw * b <= 6.25)
-    rows += [[1, 5.0, 3.0, 5.0 + pw * rx, 3.0 + ph * ry]] * race
+    if race:                                             # the patch holds at most 7 bins per axis
+        ry = max(b for b in (0.875, 1.0, 1.75, 2.0) if ph * b <= 6.25)
+        rx = max(b for b in (0.875, 1.0, 1.75, 2.0) if pw * b <= 6.25)
+        rows += [[1, 5.0, 3.0, 5.0 + pw * rx, 3.0 + ph * ry]] * race
     rois = np.array(rows, np.float64)
     rois[:, 1:] /= spatial_scale
     return rois.astype(np.float32)
@@ -309,11 +310,11 @@ ROI_DYADIC_CASES = [((3, 3), -1, 1.0, 256), ((3, 3), 2, 1.0, 12), ((3, 3), -1, 0
 ROI_DYADIC_MAP = (3, 30, 36)                          # batch, height, width
 
 
-def roi_dyadic_case(size, sr, scale, ch):
+def roi_dyadic_case(size, sr, scale, ch, race=500):
     """The dyadic RoI set of one ROI_DYADIC_CASES entry."""
     _, h, w = ROI_DYADIC_MAP
     return roi_dyadic_set(seed=100 * size[0] + 10 * size[1] + ch + (sr > 0), out_size=size, sampling_ratio=sr,
-                          spatial_scale=scale, height=h, width=w)
+                          spatial_scale=scale, height=h, width=w, race=race)
 
 
 def roi_sample_grid(roi, out_size, spatial_scale, sampling_ratio, dtype):
@@ -370,6 +371,98 @@ def roi_tap_counts(rois, out_size, spatial_scale, sampling_ratio, batch, height,
                         if w[q] != 0:
                             cnt[base + idx[q]] += k
     return cnt.reshape(batch, height, width)
+
+
+# RoIAlign forward (tests/test_roi_fwd_gpu.py): the dyadic sets above without the race patch (identical RoIs add nothing
+# to a forward), more cases for the routes of rr_roi_align_fwd that the twelve do not reach, and RoIs whose limit
+# samples lie exactly on the inclusive limits -1 and H / W of the inside test.
+ROI_FWD_CASES = ROI_DYADIC_CASES + [
+    ((3, 3), -1, 1.0, 260),                           # 3x3 kernel, second channel pass with one live lane
+    ((7, 7), 2, 0.25, 260),                           # separable kernel, same
+    ((8, 8), -1, 1.0, 4),                             # the most bins the separable kernel takes, one lane
+    ((9, 9), -1, 1.0, 8),                             # generic kernel at a multiple of 4 channels
+    ((1, 9), 2, 0.25, 8),                             # generic, fixed sampling
+    ((3, 3), -1, 1.0, 4)]                             # 3x3, one lane
+ROI_FWD_OUTSIDE = (40, 41)                            # rows of roi_fwd_case entirely outside the map
+
+
+def roi_boundary_set(out_size, spatial_scale, height, width):
+    """rois [8,5] float32 with bins of 1.75 on both axes (2 samples per bin and axis under either sampling mode, 0.875
+    apart, the first 0.4375 inside the RoI): the first sample row exactly -1, the last exactly H, the same in x, and
+    after each its twin moved 1/16 outward, whose limit sample the inside test cuts.  Every coordinate is a multiple
+    of 1/16: positions, weights and their products are exact in float32."""
+    ph, pw = out_size
+    top, left = -1.4375, -1.4375
+    bottom, right = height - 1.75 * ph + 0.4375, width - 1.75 * pw + 0.4375
+    rows = []
+    for k, (x1, y1, dx, dy) in enumerate([(4.0, top, 0, -1), (6.5, bottom, 0, 1), (left, 3.0, -1, 0), (right, 5.5, 1, 0)]):
+        for out in (0.0, 0.0625):
+            x, y = x1 + dx * out, y1 + dy * out
+            rows.append([k % 2, x, y, x + 1.75 * pw, y + 1.75 * ph])
+    rois = np.array(rows, np.float64)
+    rois[:, 1:] /= spatial_scale
+    return rois.astype(np.float32)
+
+
+def roi_fwd_case(size, sr, scale, ch):
+    """The RoIs of one ROI_FWD_CASES entry: the dyadic set of that entry (rows ROI_FWD_OUTSIDE beyond the map), then
+    roi_boundary_set."""
+    _, h, w = ROI_DYADIC_MAP
+    return np.concatenate([roi_dyadic_case(size, sr, scale, ch, race=0), roi_boundary_set(size, scale, h, w)])
+
+
+def roi_forward_route(roi, out_size, spatial_scale, sampling_ratio, channels):
+    """(kernel, branch) that rr_roi_align_fwd (csrc/roialign.hip) takes for one RoI, restated in float32: kernel "3x3",
+    "sep" or "generic"; branch "F" (footprint / separable walk) or "P" (per-sample taps; the generic kernel has no
+    other)."""
+    f = np.float32
+    ph, pw = out_size
+    if channels % 4 == 0 and (ph, pw) == (3, 3):
+        kernel = "3x3"
+    elif channels % 4 == 0 and ph <= 8 and pw <= 8:      # SEP_MAXBINS
+        kernel = "sep"
+    else:
+        return "generic", "P"
+    x1, y1, x2, y2 = (f(f(roi[i]) * f(spatial_scale)) for i in range(1, 5))
+    rw, rh = f(max(f(x2 - x1), f(1))), f(max(f(y2 - y1), f(1)))
+    bh, bw = f(rh / f(ph)), f(rw / f(pw))
+    gh = sampling_ratio if sampling_ratio > 0 else int(np.ceil(bh))
+    gw = sampling_ratio if sampling_ratio > 0 else int(np.ceil(bw))
+    walk = gh <= 16 and gw <= 16 and bh <= f(gh) and bw <= f(gw)      # SEP_MAXG
+    return kernel, "F" if walk else "P"
+
+
+ROI_RANDOM_SIZES = ((3, 3), (7, 7), (2, 5), (9, 9))
+ROI_RANDOM_MAP = (3, 70, 90)                          # batch, height, width
+
+
+def roi_random_set(large=False):
+    """rois [44,5] float32 on images 0 and 1 of a batch of 3: the recipe of
+    test_roi_align_large_and_random_rois_vs_oracle (tests/test_model_gpu.py): random RoIs from 0.3 to 30 pixels, partly
+    outside, four large / border / outside ones.  large=True appends twelve RoIs of 50 to 127 pixels a side, partly
+    beyond the map: sides above 48 take per-sample taps at (3,3) bins under adaptive sampling, sides above 112 at (7,7).
+    For every size of ROI_RANDOM_SIZES and both sampling modes float32 and float64 agree on the sampling grid and on
+    every sample's inside test, and no sample lies within 1e-3 of -1, H or W (tests/test_host_logic.py)."""
+    rng = np.random.default_rng(14)
+    n = 40
+    xy = rng.uniform(-6, 80, (n, 2)).astype(np.float32)
+    wh = np.exp(rng.uniform(np.log(0.3), np.log(30), (n, 2))).astype(np.float32)
+    rois = np.concatenate([rng.integers(0, 2, (n, 1)).astype(np.float32), xy, xy + wh], 1)
+    rois = np.concatenate([rois, np.array([[0, 1.0, 2.0, 88.0, 68.0], [1, -10, -10, 100, 80], [1, 3, 60, 70, 69.5],
+                                           [0, 95, 10, 99, 20]], np.float32)])
+    if large:
+        rois = np.concatenate([rois, np.array([
+            [0, -20.3, -20.6, 100.2, 95.1], [1, 40.3, -61.7, 75.9, 58.8], [0, -33.4, 20.2, 93.1, 49.7],
+            [1, -15.2, 5.3, 110.4, 12.9], [0, 60.7, -25.3, 66.1, 101.2], [1, -40.6, 30.4, 80.3, 75.2],
+            [0, 10.4, -50.2, 22.7, 72.3], [1, 20.6, 10.3, 95.4, 40.7], [0, -12.7, 35.2, 50.6, 78.9],
+            [1, 55.3, -8.4, 70.2, 66.3], [0, 5.8, 15.6, 84.3, 22.1], [1, 30.2, 42.7, 97.6, 93.4]], np.float32)])
+    return rois
+
+
+def measured_tol(err32, ref):
+    """Where only the rounding order differs: 4x the error of the same computation in float32 on the CPU against
+    float64, with a floor of 2u max|ref|."""
+    return max(4.0 * float(err32), 2.0 * U32 * float(np.abs(ref).max(initial=0.0)))
 
 
 def adam_grads(rng, scales, zero_frac=0.05):

@@ -440,6 +440,121 @@ def test_dyadic_roi_set_is_exact_in_fp32():
                         assert [float(np.float32(v / np.float32(cnt))) for v in w] == [v / cnt for v in w64]
 
 
+def test_dyadic_roi_set_without_race_rows_and_unchanged_with_them():
+    """roi_dyadic_set(race=0) adds no race rows and takes any number of bins; the arrays of ROI_DYADIC_CASES (which the
+    backward tests use) are bit for bit what they were before race became optional (CRC-32 over the twelve arrays)."""
+    import zlib
+    import numpy as np
+    from helpers import ROI_DYADIC_CASES, roi_dyadic_case, roi_dyadic_set
+    crc = 0
+    for case in ROI_DYADIC_CASES:
+        rois = roi_dyadic_case(*case)
+        assert rois.shape == (542, 5) and rois.dtype == np.float32
+        crc = zlib.crc32(rois.tobytes(), crc)
+        assert np.array_equal(roi_dyadic_case(*case, race=0), rois[:42])
+        assert np.array_equal(roi_dyadic_case(*case, race=3), rois[:45])
+    assert crc == 0x49ad707
+    assert roi_dyadic_set(5, (9, 9), -1, 1.0, 30, 36, race=0).shape == (42, 5)
+
+
+def _roi_fwd_cells(rois, size, sr, scale, ch):
+    from helpers import roi_forward_route
+    return ["%s-%s" % roi_forward_route(r, size, scale, sr, ch) for r in rois]
+
+
+def test_roi_forward_route_restates_the_dispatch():
+    import numpy as np
+    from helpers import roi_forward_route
+    small, wide, huge = (np.array([0, 2.0, 3.0, 2.0 + s, 3.0 + s], np.float32) for s in (9.0, 48.75, 150.0))
+    assert roi_forward_route(small, (3, 3), 1.0, -1, 256) == ("3x3", "F")
+    assert roi_forward_route(small, (3, 3), 1.0, 2, 256) == ("3x3", "P")           # bins of 3 > 2 samples
+    assert roi_forward_route(small, (3, 3), 0.25, 2, 256) == ("3x3", "F")
+    assert roi_forward_route(small, (3, 3), 1.0, -1, 6) == ("generic", "P")
+    assert roi_forward_route(wide, (3, 3), 1.0, -1, 4) == ("3x3", "P")             # 17 samples per bin
+    assert roi_forward_route(wide[[0, 1, 2, 3, 2]] + [0, 0, 0, 0, 9], (3, 3), 1.0, -1, 4) == ("3x3", "P")   # one axis decides
+    assert roi_forward_route(wide, (7, 7), 1.0, -1, 4) == ("sep", "F")
+    assert roi_forward_route(huge, (7, 7), 1.0, -1, 4) == ("sep", "P")
+    assert roi_forward_route(small, (8, 8), 1.0, -1, 4) == ("sep", "F")
+    assert roi_forward_route(small, (8, 1), 1.0, -1, 4) == ("sep", "F")
+    assert roi_forward_route(small, (9, 1), 1.0, -1, 4) == ("generic", "P")
+    assert roi_forward_route(small, (1, 9), 1.0, -1, 8) == ("generic", "P")
+
+
+def test_roi_forward_cases_reach_every_route_under_both_sampling_modes():
+    """Across ROI_FWD_CASES each of the five (kernel, branch) cells of rr_roi_align_fwd holds at least 5 RoIs under
+    adaptive and at least 5 under fixed sampling; the RoIs entirely outside the map sit at ROI_FWD_OUTSIDE; every RoI
+    names image 0 or 1 of the batch of 3."""
+    import numpy as np
+    from helpers import ROI_DYADIC_MAP, ROI_FWD_CASES, ROI_FWD_OUTSIDE, roi_fwd_case, roi_sample_grid
+    B, H, W = ROI_DYADIC_MAP
+    assert len(ROI_FWD_CASES) == 18
+    cells = {}
+    for size, sr, scale, ch in ROI_FWD_CASES:
+        rois = roi_fwd_case(size, sr, scale, ch)
+        assert rois.shape == (50, 5) and rois.dtype == np.float32
+        assert set(rois[:, 0]) == {0.0, 1.0} and B == 3
+        for cell in _roi_fwd_cells(rois, size, sr, scale, ch):
+            cells[cell, sr > 0] = cells.get((cell, sr > 0), 0) + 1
+        assert all(not ((g >= -1) & (g <= lim)).any() for r, (k, lim) in zip(ROI_FWD_OUTSIDE, ((0, H), (1, W)))
+                   for g in [roi_sample_grid(rois[r], size, scale, sr, np.float64)[k]])
+    print(sorted(cells.items()))
+    assert set(cells) == {(c, m) for c in ("3x3-F", "3x3-P", "sep-F", "sep-P", "generic-P") for m in (False, True)}
+    assert min(cells.values()) >= 5, cells
+
+
+def test_roi_forward_sets_are_exact_in_fp32():
+    """Every sample position of every dyadic and boundary RoI of ROI_FWD_CASES, evaluated as oracle.ops.roi_align does
+    in fp32, equals its fp64 evaluation; the samples per bin are a power of two; and the boundary RoIs put their limit
+    samples exactly on -1, H and W, their twins 1/16 beyond."""
+    import numpy as np
+    from helpers import ROI_DYADIC_MAP, ROI_FWD_CASES, roi_fwd_case, roi_sample_grid
+    _, H, W = ROI_DYADIC_MAP
+    for size, sr, scale, ch in ROI_FWD_CASES:
+        rois = roi_fwd_case(size, sr, scale, ch)
+        for roi in rois:
+            y32, x32, cnt = roi_sample_grid(roi, size, scale, sr, np.float32)
+            y64, x64, cnt64 = roi_sample_grid(roi, size, scale, sr, np.float64)
+            assert cnt == cnt64 and cnt & (cnt - 1) == 0
+            assert np.array_equal(y32.astype(np.float64), y64) and np.array_equal(x32.astype(np.float64), x64)
+            assert np.array_equal(y64 * 256, np.round(y64 * 256)) and np.array_equal(x64 * 256, np.round(x64 * 256))
+        edge = [roi_sample_grid(roi, size, scale, sr, np.float32) for roi in rois[-8:]]
+        assert all(e[2] == 4 for e in edge)
+        assert [edge[0][0].min(), edge[1][0].min()] == [-1.0, -1.0625]
+        assert [edge[2][0].max(), edge[3][0].max()] == [H, H + 0.0625]
+        assert [edge[4][1].min(), edge[5][1].min()] == [-1.0, -1.0625]
+        assert [edge[6][1].max(), edge[7][1].max()] == [W, W + 0.0625]
+        for k, e in enumerate(edge):                  # the other axis stays inside the map
+            other = e[1 if k < 4 else 0]
+            assert other.min() >= 0 and other.max() <= (W if k < 4 else H) - 1
+
+
+def test_roi_random_set_keeps_clear_of_the_inside_limits():
+    """helpers.roi_random_set: its first 44 rows are the backward tests' set; with the large RoIs at least 10 take
+    per-sample taps at (3,3) bins and at least 5 at (7,7) under adaptive sampling; for every size and sampling mode
+    float32 and float64 agree on the sampling grid and on every sample's inside test, no float64 sample lies within
+    1e-3 of -1, H or W, and every RoI names image 0 or 1."""
+    import numpy as np
+    from helpers import ROI_RANDOM_MAP, ROI_RANDOM_SIZES, roi_random_set, roi_sample_grid
+    B, H, W = ROI_RANDOM_MAP
+    rois = roi_random_set(large=True)
+    assert rois.shape == (56, 5) and np.array_equal(rois[:44], roi_random_set()) and roi_random_set().shape == (44, 5)
+    assert set(rois[:, 0]) == {0.0, 1.0} and B == 3
+    assert _roi_fwd_cells(rois, (3, 3), -1, 1.0, 256).count("3x3-P") >= 10
+    assert _roi_fwd_cells(rois, (7, 7), -1, 1.0, 256).count("sep-P") >= 5
+    nearest = np.inf
+    for size in ROI_RANDOM_SIZES:
+        for sr in (-1, 2):
+            for roi in rois:
+                y32, x32, _ = roi_sample_grid(roi, size, 1.0, sr, np.float32)
+                y64, x64, _ = roi_sample_grid(roi, size, 1.0, sr, np.float64)
+                assert y32.shape == y64.shape and x32.shape == x64.shape, (roi, size, sr)
+                for g32, g64, lim in ((y32, y64, H), (x32, x64, W)):
+                    assert np.array_equal((g32 >= -1) & (g32 <= lim), (g64 >= -1) & (g64 <= lim)), (roi, size, sr)
+                    nearest = min(nearest, np.abs(g64 + 1).min(), np.abs(g64 - lim).min())
+    print("nearest sample to a limit: %.3g" % nearest)
+    assert nearest > 1e-3
+
+
 def _syncbn_shards(seed, shapes, c):
     import numpy as np
     import torch

@@ -10,13 +10,11 @@ Tolerances are never read off the kernel:
  - measured (random RoIAlign set, the DCN mask): 4x the error of the same computation in float32 on the CPU against
    float64, with a floor of 2u max|ref|.
 """
-import functools
-
 import numpy as np
 import pytest
 import torch
 
-from helpers import ROI_DYADIC_CASES, ROI_DYADIC_MAP, U32, roi_dyadic_case, roi_tap_counts
+from helpers import ROI_DYADIC_CASES, ROI_DYADIC_MAP, U32, measured_tol, roi_dyadic_case, roi_random_set, roi_tap_counts
 
 pytestmark = pytest.mark.gpu
 CL = torch.channels_last
@@ -24,10 +22,6 @@ CL = torch.channels_last
 
 def _np(t):
     return t.detach().cpu().numpy().astype(np.float64)
-
-
-def measured_tol(err32, ref):
-    return max(4.0 * float(err32), 2.0 * U32 * float(np.abs(ref).max(initial=0.0)))
 
 
 def _oracle_roi_bwd(feat_shape, rois, dout, size, scale, sr, dtype):
@@ -78,18 +72,9 @@ def test_roi_align_bwd_dyadic_set_vs_fp64(size, sr, scale, ch):
     assert np.all(got_out == 0.0)
 
 
-@functools.lru_cache(maxsize=1)
 def _random_set():
-    """The recipe of test_roi_align_large_and_random_rois_vs_oracle (tests/test_model_gpu.py) at 256 channels and a
-    batch of 3: random RoIs from 0.3 to 30 pixels, partly outside, four large / border / outside ones."""
-    rng = np.random.default_rng(14)
-    n = 40
-    xy = rng.uniform(-6, 80, (n, 2)).astype(np.float32)
-    wh = np.exp(rng.uniform(np.log(0.3), np.log(30), (n, 2))).astype(np.float32)
-    rois = np.concatenate([rng.integers(0, 2, (n, 1)).astype(np.float32), xy, xy + wh], 1)
-    rois = np.concatenate([rois, np.array([[0, 1.0, 2.0, 88.0, 68.0], [1, -10, -10, 100, 80], [1, 3, 60, 70, 69.5],
-                                           [0, 95, 10, 99, 20]], np.float32)])
-    return rois, (3, 256, 70, 90)
+    """helpers.roi_random_set (44 RoIs) at 256 channels and a batch of 3."""
+    return roi_random_set(), (3, 256, 70, 90)
 
 
 @pytest.mark.parametrize("sr", [-1, 2])
