@@ -31,6 +31,7 @@ PER_FILE = {
     "kmeans.hip": ["-ffp-contract=off"],
     "wbf.hip": ["-ffp-contract=off"],
     "textio.hip": ["-ffp-contract=off"],
+    "depthwise.hip": ["-ffp-contract=off"],
 }
 
 

@@ -944,6 +944,125 @@ def window_attention(q, k, v, kernel_size, dilation=1, padding=0):
     return _WindowAttention.apply(q, k, v, kk, d, p)
 
 
+class _DwConvBn(torch.autograd.Function):
+    """z = relu?(BN(depthwise3x3(x, w))) (backbones/shufflenet.py:65-66,75-76,89-90), the training statistics out of the
+    convolution's own pass (csrc/depthwise.hip writes rr_conv_fprop's slab), BatchNorm forward and backward on the kernels
+    every other layer uses."""
+
+    @staticmethod
+    def forward(ctx, x, w, gamma, beta, bn, stride, relu):
+        x = ops.to_nhwc(x)
+        c = x.shape[1]
+        if bn.training:
+            y, slab = ops.dwconv3x3_fwd(x, w, None, stride, want_stats=True)
+            count = float(y.numel() // c)
+            mom = bn.momentum if bn.momentum is not None else 0.1
+            if not BN_FUSED_STATS or slab.numel() > 512 * 2 * c:      # (as _ConvBnAct: the fused kernel runs C/32 workgroups only)
+                sums = ops.bn_reduce_slab(slab, c, extra=1)
+                mean, invstd, scale, shift = ops.bn_finalize(sums, count, gamma, beta, bn.running_mean, bn.running_var, mom,
+                                                             bn.eps, None, bn.num_batches_tracked)
+            else:
+                mean, invstd, scale, shift = ops.bn_stats_finalize(slab, count, gamma, beta, bn.running_mean, bn.running_var,
+                                                                   mom, bn.eps, bn.num_batches_tracked)
+            z = ops.bn_apply(y, scale, shift, None, relu)
+            # the ReLU mask is recomputed from y in the backward (no residual here)
+            ctx.save_for_backward(x, w, y, mean, invstd, gamma, scale if relu else None, shift if relu else None)
+            ctx.cfg = (stride, count)
+            ctx.params = (w, gamma, beta)
+            return z
+        # inference: BatchNorm is a per-channel affine map, folded into the filter and the kernel's bias; one launch
+        scale, shift = ops.bn_eval_coeffs(gamma, beta, bn.running_mean, bn.running_var, bn.eps)
+        z = ops.dwconv3x3_fwd(x, w * scale.view(-1, 1, 1, 1), shift, stride)
+        return ops.relu_fwd(z) if relu else z
+
+    @staticmethod
+    def backward(ctx, dz):
+        x, wv, y, mean, invstd, gamma, msc, msh = ctx.saved_tensors
+        stride, count = ctx.cfg
+        w, gamma_p, beta_p = ctx.params
+        dz = ops.to_nhwc(dz)
+        c = y.shape[1]
+        sums = ops.bn_bwd_reduce(dz, None, y, mean, invstd, mask_scale=msc, mask_shift=msh)
+        dg_t, db_t = _grad_target(gamma_p), _grad_target(beta_p)
+        fused_affine = dg_t is not None and db_t is not None
+        ret_dg = ret_db = None
+        if not fused_affine:
+            ret_db, ret_dg = sums[:c].float(), sums[c:2 * c].float()
+        dy, _ = ops.bn_bwd_apply(dz, None, y, mean, invstd, gamma, sums, count, False, dg_t if fused_affine else None,
+                                 db_t if fused_affine else None, None, msc, msh)
+        dx = ops.dwconv3x3_bwd_data(dy, wv, tuple(x.shape), stride) if ctx.needs_input_grad[0] else None
+        w_t = _grad_target(w)
+        ret_dw = None
+        if w_t is not None:
+            ops.dwconv3x3_bwd_weight(x, dy, w_t, stride, accumulate=True)
+            _mark(w)
+        else:
+            ret_dw = ops.dwconv3x3_bwd_weight(x, dy, torch.empty_like(wv), stride, accumulate=False)
+        if fused_affine:
+            _mark(gamma_p, beta_p)
+        return dx, ret_dw, ret_dg, ret_db, None, None, None
+
+
+def dwconv_bn(x, conv, bn, relu=False):
+    """conv: nn.Conv2d(c, c, 3, stride, 1, groups=c, bias=False), bn: nn.BatchNorm2d, used as parameter holders."""
+    c = x.shape[1]
+    if (conv.groups != c or conv.in_channels != c or conv.out_channels != c or tuple(conv.kernel_size) != (3, 3)
+            or tuple(conv.padding) != (1, 1) or tuple(conv.dilation) != (1, 1) or conv.bias is not None
+            or tuple(conv.stride) not in ((1, 1), (2, 2))):
+        raise NotImplementedError("dwconv_bn: only the bias-free depthwise 3x3 convolution with padding 1 and stride 1 or 2 is "
+                                  "built (csrc/depthwise.hip), got %r on %d channels" % (conv, c))
+    if _is_sync(bn):
+        raise NotImplementedError("dwconv_bn: SyncBatchNorm behind a depthwise convolution is not built (one GPU only)")
+    return _DwConvBn.apply(x, conv.weight, bn.weight, bn.bias, bn, conv.stride[0], relu)
+
+
+class _ShuffleCat(torch.autograd.Function):
+    """channel_shuffle(cat(a, b), 2) (backbones/shufflenet.py:31-45,100,110) as one interleaving pass; a and b may be channel
+    slices of NHWC tensors, read in place.  The backward is the de-interleave."""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        return ops.shuffle_interleave(a, b)
+
+    @staticmethod
+    def backward(ctx, g):
+        return ops.shuffle_deinterleave(ops.to_nhwc(g))
+
+
+def _as_rows(t):
+    """t as the kernels can read it in place: an NHWC tensor or a channel slice of one; anything else is laid out NHWC."""
+    try:
+        ops.pixel_rows(t)
+        return t
+    except ValueError:
+        return ops.to_nhwc(t)
+
+
+def shuffle_cat(a, b):
+    return _ShuffleCat.apply(_as_rows(a), _as_rows(b))
+
+
+class _SplitHalves(torch.autograd.Function):
+    """x -> (x[:, :c/2] as a view: the half a stride-1 unit hands through, moved once, by the interleave; x[:, c/2:] copied out
+    into an NHWC tensor of its own for the branch's convolutions).  The backward joins the two gradients in one pass."""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = ops.to_nhwc(x)
+        half = x.shape[1] // 2
+        return x[:, :half], ops.channel_copy(x[:, half:])
+
+    @staticmethod
+    def backward(ctx, dlo, dhi):
+        return ops.channel_join(_as_rows(dlo), _as_rows(dhi))
+
+
+def split_halves(x):
+    if x.shape[1] % 8:
+        raise NotImplementedError("split_halves: %d channels; the halves must be multiples of 4 (a lane moves 16 bytes)" % x.shape[1])
+    return _SplitHalves.apply(x)
+
+
 class _BilinearAdd(torch.autograd.Function):
     """F.interpolate(x, size(y), mode='bilinear', align_corners=False) + y  (modules/fpn.py:39-40)."""
 

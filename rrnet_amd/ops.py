@@ -2544,6 +2544,155 @@ def window_attention_bwd(dctx, q, k, v, p, kernel_size, dilation, padding):
     return dq, dk, dv
 
 
+# ---------------------------------------------------------------------------------------------
+# ShuffleNetV2 (csrc/depthwise.hip): the depthwise 3x3 convolution and the channel shuffle with its split / join copies
+# ---------------------------------------------------------------------------------------------
+_DW = _C.Family("rrnet_hip_dw.h")       # the family's own header beside include/rrnet_hip.h
+DW_SLAB_PIXELS = 64           # RR_DW_SLAB_PIXELS of the header: output pixels per workgroup of the forward = per slab tile
+DW_MIN_TILE_PIXELS = 128      # output pixels one workgroup of the weight gradient's first stage sums ...
+DW_MAX_TILES = 256            # ... and at most this many tiles (the second stage adds them one by one)
+
+
+def _dw_launch(entry, flops, nbytes, *args):
+    return _launch(entry[3:], flops, entry, args, nbytes=nbytes, call=_DW.call)
+
+
+def dw_out_hw(h, w, stride):
+    return (h - 1) // stride + 1, (w - 1) // stride + 1
+
+
+def dw_tile_pixels(pixels):
+    """Output pixels per workgroup of rr_dwconv3x3_bwd_weight's first stage -> (tile_pixels, tiles)."""
+    tile = max(DW_MIN_TILE_PIXELS, -(-pixels // DW_MAX_TILES))
+    return tile, -(-pixels // tile)
+
+
+def _dw_filter(w, c):
+    """The parameter [c, 1, 3, 3] (any of its layouts: one input channel) as the [c, 3, 3] block the kernels read."""
+    assert tuple(w.shape) == (c, 1, 3, 3) and w.dtype == torch.float32, (tuple(w.shape), c)
+    f = w.permute(0, 2, 3, 1)
+    if not f.is_contiguous():
+        f = f.contiguous()
+    return f
+
+
+def dwconv3x3_fwd(x, w, bias=None, stride=1, want_stats=False):
+    """x NHWC [n,c,h,w], w [c,1,3,3] -> y NHWC [n,c,P,Q] (padding 1), or (y, slab) with the BatchNorm partial sums
+    [mtiles,2,c] float64 of y in rr_conv_fprop's layout (bn_stats_finalize / bn_reduce_slab read it)."""
+    _C.require_cuda(x, w, bias)
+    assert is_nhwc(x) and x.dtype == torch.float32
+    n, c, h, wd = x.shape
+    if stride not in (1, 2):
+        raise ValueError("dwconv3x3_fwd: stride %r (1 or 2)" % (stride,))
+    p, q = dw_out_hw(h, wd, stride)
+    y = empty_nhwc(n, c, p, q, x.device)
+    slab = None
+    if want_stats:
+        slab = torch.empty((-(-(n * p * q) // DW_SLAB_PIXELS), 2, c), dtype=torch.float64, device=x.device)
+    _dw_launch("rr_dwconv3x3_fwd", 18.0 * n * p * q * c, 4.0 * c * (n * h * wd + n * p * q), x, _dw_filter(w, c), bias, y, slab,
+               n, h, wd, c, stride)
+    return (y, slab) if want_stats else y
+
+
+def dwconv3x3_bwd_data(dy, w, x_shape, stride=1):
+    """-> dx NHWC of x_shape, written whole."""
+    n, c, h, wd = x_shape
+    p, q = dw_out_hw(h, wd, stride)
+    assert is_nhwc(dy) and dy.dtype == torch.float32 and tuple(dy.shape) == (n, c, p, q)
+    dx = empty_nhwc(n, c, h, wd, dy.device)
+    _dw_launch("rr_dwconv3x3_bwd_data", 18.0 * n * p * q * c, 4.0 * c * (n * h * wd + n * p * q), dy, _dw_filter(w, c), dx,
+               n, h, wd, c, stride)
+    return dx
+
+
+def dwconv3x3_bwd_weight(x, dy, dw, stride=1, accumulate=False):
+    """dw [c,1,3,3] = (accumulate: dw +) the filter gradient; dw is written in place (a parameter's gradient target)."""
+    n, c, h, wd = x.shape
+    p, q = dw_out_hw(h, wd, stride)
+    assert is_nhwc(x) and is_nhwc(dy) and tuple(dy.shape) == (n, c, p, q) and x.dtype == dy.dtype == torch.float32
+    assert tuple(dw.shape) == (c, 1, 3, 3) and dw.permute(0, 2, 3, 1).is_contiguous() and dw.dtype == torch.float32
+    tile, tiles = dw_tile_pixels(n * p * q)
+    partial = torch.empty((tiles, c, 9), dtype=torch.float64, device=x.device)
+    _dw_launch("rr_dwconv3x3_bwd_weight", 18.0 * n * p * q * c, 4.0 * c * (n * h * wd + n * p * q), x, dy, partial, dw,
+               int(bool(accumulate)), n, h, wd, c, stride, tile)
+    return dw
+
+
+def pixel_rows(t):
+    """An NHWC tensor or a channel slice of one -> (pixels, channels, pixel stride in floats).  The pixels must lie one
+    stride apart in n, h, w order; the channels densely."""
+    assert t.dim() == 4 and t.dtype == torch.float32
+    n, c, h, w = t.shape
+    sn, sc, sh, sw = t.stride()
+    stride = step = None
+    ok = sc == 1 or c == 1
+    for size, st in ((w, sw), (h, sh), (n, sn)):          # (a dimension of one element has no stride to speak of)
+        if size == 1:
+            continue
+        if stride is None:
+            stride = st
+        elif st != step:
+            ok = False
+        step = st * size
+    if stride is None:
+        stride = c
+    if not ok or stride < c:
+        raise ValueError("not a channel slice of an NHWC tensor: shape %s strides %s" % (tuple(t.shape), tuple(t.stride())))
+    return n * h * w, c, stride
+
+
+def shuffle_interleave(a, b):
+    """channel_shuffle(cat(a, b), 2): out[:, 2i] = a[:, i], out[:, 2i+1] = b[:, i].  a, b: NHWC tensors or channel slices."""
+    _C.require_cuda(a, b)
+    pa, half, sa = pixel_rows(a)
+    pb, hb, sb = pixel_rows(b)
+    assert a.shape == b.shape
+    n, _, h, w = a.shape
+    out = empty_nhwc(n, 2 * half, h, w, a.device)
+    _dw_launch("rr_shuffle_interleave", 0.0, 16.0 * pa * half, a, sa, b, sb, out, 2 * half, pa, half)
+    return out
+
+
+def shuffle_deinterleave(g, da=None, db=None):
+    """The inverse: -> (da, db) with da[:, i] = g[:, 2i], db[:, i] = g[:, 2i+1]; either may be given (a channel slice to fill)."""
+    pg, c2, sg = pixel_rows(g)
+    n, _, h, w = g.shape
+    half = c2 // 2
+    assert c2 % 2 == 0
+    if da is None:
+        da = empty_nhwc(n, half, h, w, g.device)
+    if db is None:
+        db = empty_nhwc(n, half, h, w, g.device)
+    _, ha, sa = pixel_rows(da)
+    _, hb, sb = pixel_rows(db)
+    assert ha == hb == half and da.shape == db.shape and tuple(da.shape) == (n, half, h, w)
+    _dw_launch("rr_shuffle_deinterleave", 0.0, 16.0 * pg * half, g, sg, da, sa, db, sb, pg, half)
+    return da, db
+
+
+def channel_copy(src, dst=None):
+    """src (a channel slice of an NHWC tensor) -> dst (a fresh NHWC tensor, or the slice given)."""
+    _C.require_cuda(src)
+    ps, ch, ss = pixel_rows(src)
+    if dst is None:
+        dst = empty_nhwc(src.shape[0], ch, src.shape[2], src.shape[3], src.device)
+    _, cd, sd = pixel_rows(dst)
+    assert dst.shape == src.shape
+    _dw_launch("rr_channel_copy", 0.0, 8.0 * ps * ch, src, ss, dst, sd, ps, ch)
+    return dst
+
+
+def channel_join(lo, hi):
+    """cat(lo, hi) along the channels in one launch -> a fresh NHWC tensor."""
+    pl, half, sl = pixel_rows(lo)
+    _, hh, sh = pixel_rows(hi)
+    assert lo.shape == hi.shape
+    n, _, h, w = lo.shape
+    out = empty_nhwc(n, 2 * half, h, w, lo.device)
+    _dw_launch("rr_channel_join", 0.0, 16.0 * pl * half, lo, sl, hi, sh, out, 2 * half, pl, half)
+    return out
+
+
 class _OpsModule(types.ModuleType):
     """`ops.BF16` (read / assign) = this thread's arithmetic switch."""
 

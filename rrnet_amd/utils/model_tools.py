@@ -2,17 +2,21 @@
 RRNet / CenterNet — 'hourglass' (configs/rrnet_config.py:80), 'dense_hourglass' (:26-27) and 'se_hourglass' (the reference
 ships backbones/se_hourglass.py without a name in its table; the name is this package's), each with a builder-defined
 '_tiny' sibling ('hourglass_tiny' is the backbone of BASELINE.json config 1) — and the three ResNets of RetinaNet
-(configs/retinanet_config.py:72 -> 'resnet50').  The other names ('hrnet', 'hrnetv2', 'shufflenet', 'trident') load weight
-files nobody has or are commented out in the reference itself."""
+(configs/retinanet_config.py:72 -> 'resnet50').  ShuffleNetV2 (backbones/shufflenet.py, which the reference ships without a
+name in its table: the names 'shufflenet_v2_x0_5' / '_x1_5' / '_x2_0' and the composition with RetinaNet are this package's)
+is a fourth, light backbone for RetinaNet.  The other names ('hrnet', 'hrnetv2', 'trident') load weight files nobody has or
+are commented out in the reference itself."""
 from rrnet_amd.backbones.dense_hourglass import dense_hourglass_net, dense_hourglass_tiny
 from rrnet_amd.backbones.hourglass import hourglass_net, hourglass_tiny
 from rrnet_amd.backbones.resnet import resnet10, resnet50, resnet101
 from rrnet_amd.backbones.se_hourglass import se_hourglass_net, se_hourglass_tiny
+from rrnet_amd.backbones.shufflenet import shufflenet_v2
 
 _RESNETS = {'resnet10': resnet10, 'resnet50': resnet50, 'resnet101': resnet101}
 _HOURGLASSES = {'hourglass': hourglass_net, 'hourglass_tiny': hourglass_tiny,
                 'dense_hourglass': dense_hourglass_net, 'dense_hourglass_tiny': dense_hourglass_tiny,
                 'se_hourglass': se_hourglass_net, 'se_hourglass_tiny': se_hourglass_tiny}
+_SHUFFLENETS = {'shufflenet_v2_x0_5': 0.5, 'shufflenet_v2_x1_5': 1.5, 'shufflenet_v2_x2_0': 2.0}      # name -> width_mult
 FP32_ONLY_BACKBONES = ('dense_hourglass', 'dense_hourglass_tiny', 'se_hourglass', 'se_hourglass_tiny')
 
 
@@ -21,9 +25,16 @@ def get_backbone(backbone, pretrained=False, num_stacks=2):
         return _HOURGLASSES[backbone](num_stacks=num_stacks)
     if backbone in _RESNETS:
         return _RESNETS[backbone](pretrained=pretrained)
+    if backbone in _SHUFFLENETS:
+        return shufflenet_v2(pretrained=pretrained, width_mult=_SHUFFLENETS[backbone])
+    if backbone == 'shufflenet_v2_x1_0':
+        raise NotImplementedError(
+            "backbone 'shufflenet_v2_x1_0' is not built: at width 1.0 the units' halves have 58 channels, and the BatchNorm "
+            "backward kernels (rr_bn_bwd_reduce) require c % 4 == 0 (use 'shufflenet_v2_x0_5', '_x1_5' or '_x2_0')")
     raise NotImplementedError(
         "backbone %r is outside the accelerated path (only 'hourglass' / 'hourglass_tiny', 'dense_hourglass' / "
-        "'dense_hourglass_tiny', 'se_hourglass' / 'se_hourglass_tiny' and 'resnet10' / 'resnet50' / 'resnet101')" % (backbone,))
+        "'dense_hourglass_tiny', 'se_hourglass' / 'se_hourglass_tiny' and 'resnet10' / 'resnet50' / 'resnet101', "
+        "'shufflenet_v2_x0_5' / 'shufflenet_v2_x1_5' / 'shufflenet_v2_x2_0')" % (backbone,))
 
 
 def refuse_bf16(model_cfg):

@@ -93,7 +93,8 @@ def main(argv=None):
     ap.add_argument("--centernet", action="store_true", help="CenterNet (centernet_config) instead of RRNet; fp32 only")
     ap.add_argument("--retinanet", action="store_true", help="RetinaNet (retinanet_config) instead of RRNet; fp32 only")
     ap.add_argument("--rows", type=int, default=1000, help="--retinanet: candidates per frame the picked threshold leaves")
-    ap.add_argument("--backbone", default=None, help="override cfg.Model.backbone (rehearsals)")
+    ap.add_argument("--backbone", default=None, help="override cfg.Model.backbone (rehearsals; --retinanet: resnet10 / resnet50 / resnet101, "
+                    "shufflenet_v2_x0_5 / _x1_5 / _x2_0)")
     ap.add_argument("--tile", type=int, help="--retinanet: measure tiled inference on NxN tiles over a pool of mixed frame sizes")
     ap.add_argument("--tile-overlap", type=int, default=128)
     ap.add_argument("--tile-zoom", type=float, default=1.0)

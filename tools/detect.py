@@ -18,7 +18,7 @@ does (--no-flip: plain only).  CenterNet is fp32 only: --bf16 is refused with it
 --config retinanet_config runs RetinaNet through rrnet_amd.inference.detect_frames_retinanet (single scale: decode, score
 sort, hard NMS at 0.3) and writes the truncated integer lines of RetinaNetOperator.save_result:
 
-  python tools/detect.py --config retinanet_config --checkpoint ckp.pth --images DIR --out DIR [--backbone resnet50]
+  python tools/detect.py --config retinanet_config --checkpoint ckp.pth --images DIR --out DIR [--backbone resnet50|shufflenet_v2_x0_5|..]
                          [--batch 4] [--score-thr 0.1] [--random-weights]
 
 RetinaNet is fp32 only and its evaluation has one scale, no flip and always the NMS: --bf16, --flip / --no-flip, --scales and
@@ -100,7 +100,8 @@ def main(argv=None):
     ap.add_argument("--no-flip", dest="flip", action="store_false", help="CenterNet: the plain image only")
     ap.add_argument("--random-weights", action="store_true")
     ap.add_argument("--workers", type=int, default=8)
-    ap.add_argument("--backbone", help="override cfg.Model.backbone: resnet10 / resnet50 / resnet101 (RetinaNet), hourglass / "
+    ap.add_argument("--backbone", help="override cfg.Model.backbone: resnet10 / resnet50 / resnet101, shufflenet_v2_x0_5 / "
+                    "_x1_5 / _x2_0 (RetinaNet), hourglass / "
                     "dense_hourglass / se_hourglass and their _tiny siblings (RRNet, CenterNet)")
     ap.add_argument("--score-thr", type=float, help="RetinaNet: the candidate threshold (default 0.1)")
     ap.add_argument("--tile", help="RetinaNet: tiled inference on overlapping tiles of this size, N or H,W")
@@ -115,8 +116,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     cfg = load_config(args.config)
     retinanet = args.config.startswith("retinanet")
-    if not retinanet and ((args.backbone or "").startswith("resnet") or args.score_thr is not None):
-        raise SystemExit("--backbone resnet* / --score-thr belong to --config retinanet_config")
+    if not retinanet and ((args.backbone or "").startswith(("resnet", "shufflenet")) or args.score_thr is not None):
+        raise SystemExit("--backbone resnet* / shufflenet_v2_* / --score-thr belong to --config retinanet_config")
     if not retinanet and args.backbone:
         cfg.Model.backbone = args.backbone                    # a member of the hourglass family (utils/model_tools)
     tile_options = (args.tile_overlap, args.tile_zoom, args.tile_margin, args.tile_batch)

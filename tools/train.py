@@ -17,6 +17,8 @@ as the reference's): brightness, contrast and saturation factors from [max(1 - x
 --ema DECAY keeps averaged weights and writes `ckp-ema-{step}.pth` beside each checkpoint (--no-ema-warmup: the full decay
 from the first step); all three are decided on the device inside the optimiser step.  --warmup ITERS puts the
 reference's linear learning-rate warm-up (from --warmup-factor F, default 1/3, of the rate) in front of the milestones.
+--backbone NAME overrides cfg.Model.backbone (utils/model_tools.get_backbone: the hourglass family for RRNet and CenterNet;
+resnet10 / resnet50 / resnet101 and shufflenet_v2_x0_5 / _x1_5 / _x2_0 for RetinaNet).
 --attention K DIL (RRNet, CenterNet; fp32) puts a zero-initialised SelfAttentionModule (K x K window at dilation DIL, 64 key
 and value channels, padding DIL * (K // 2)) per stack in front of the stage-1 heads: cfg.Model.attention (DESIGN §22)."""
 import argparse
@@ -86,6 +88,8 @@ def configure(args):
         from rrnet_amd.datasets.transforms import ColorJitter
         cfg.Train.transforms.transforms.insert(0, ColorJitter(*args.color_jitter))
     if args.backbone is not None:
+        if args.backbone.startswith("shufflenet") and not args.config.startswith("retinanet"):
+            raise SystemExit("--backbone %s: ShuffleNetV2 is a backbone of RetinaNet (--config retinanet_config)" % args.backbone)
         cfg.Model.backbone = args.backbone
     if args.bf16:
         cfg.Model.bf16 = True
