@@ -69,6 +69,8 @@ struct ConvArgs {
                        // -> Bottleneck.conv2): an M tile = ONE output pixel of 128 consecutive images, so the taps that
                        // fall into the padding are the same for every row of the tile and are skipped, not masked
                        // (a padded 3x3 on a 3x3 map: 49 of 81 (pixel, tap) pairs are real)
+    const int *gate;   // the _unless entry points (plain forward kernel only): the launch returns when *gate <= gate_max — the rows
+    int gate_max;      // route of conv_rows.hip, enqueued next to it with the opposite test, does the work then.  null: no gate
 };
 
 __device__ __forceinline__ int xcd_remap(int bid, int nb)
@@ -92,6 +94,9 @@ template <int BN, int MODE, bool SCALAR, int BKT, int PIPE, bool BNS = false, bo
 __global__ __launch_bounds__(256, PIPE == 2 ? 3 : 1) void conv_igemm_kernel(const ConvArgs a)
 {
     static_assert(BKT == 32 && (PIPE == 0 || PIPE == 2), "conv_igemm_kernel: K-step 32, PIPE 0 or 2");
+    if constexpr (MODE == 0 && !BNS && !POSM) {
+        if (a.gate != nullptr && *a.gate <= a.gate_max) return;      // wave-uniform: two scalar loads, no vector register
+    }
     constexpr int WN = BN / 64 ? BN / 64 : 1;   // waves along N
     constexpr int WM = 4 / WN;                  // waves along M
     constexpr int TM = BM / (WM * 32);
@@ -807,6 +812,8 @@ struct WgradArgs {
     int M;            // N*P*Q
     int chunks_per_split;
     int mt, nt;       // tiles along K and C
+    const int *gate;  // rr_conv_wgrad_unless: the launch returns when *gate <= gate_max (ConvArgs::gate); null: no gate
+    int gate_max;
 };
 
 // BMW x BN output tile (ko x c).  128x128: 2x2 waves of 64x64; 128x32 / 32x128: 4 waves of one 32x32;
@@ -820,6 +827,7 @@ template <int BMW, int BN, bool A_SCALAR, bool B_SCALAR, int PIPE>
 __global__ __launch_bounds__(256, PIPE == 3 ? 3 : 1) void conv_wgrad_kernel(const WgradArgs a)
 {
     static_assert(PIPE == 0 || PIPE == 1 || PIPE == 3, "conv_wgrad_kernel: PIPE 0, 1 or 3");
+    if (a.gate != nullptr && *a.gate <= a.gate_max) return;
     constexpr int TILES = (BMW / 32) * (BN / 32);
     constexpr int KS = TILES == 1 ? 4 : 1;                       // waves splitting K
     constexpr int WN = TILES == 16 ? 2 : (BN / 32 >= 4 ? 4 : 1);
@@ -1278,13 +1286,19 @@ int rr_conv_colstats(const float *y, long M, int C, double *slab, hipStream_t st
 // name: the public entry point that was called.  How the call launches is rr_plan::fprop_plan's decision (conv_plan.h).
 static int fprop_impl(const char *name, const float *x, const float *w, const float *bias, float *y, double *stat_slab,
                       int n, int h, int wd, int c, int k, int r, int s, int stride, int pad_h,
-                      int pad_w, int relu, int accumulate, hipStream_t stream, const BnSumArgs *bs = nullptr)
+                      int pad_w, int relu, int accumulate, hipStream_t stream, const BnSumArgs *bs = nullptr, const int *gate = nullptr,
+                      int gate_max = 0)
 {
     const rr_plan::FpropPlan pl = rr_plan::fprop_plan(rr_plan::MATH_F32, {n, h, wd, c, k, r, s, stride, pad_h, pad_w, 0, 0},
                                                       {bias != nullptr, relu != 0, stat_slab != nullptr, rr_conv_link(bs), accumulate != 0, false});
     RR_CHECK_ARG(pl.refuse == nullptr, "%s: %s", name, pl.refuse);
+    // a gated launch is the plain forward kernel and nothing else: no other kernel family, no producer link, and its split-K zero
+    // fill on the same side of the gate as itself
+    RR_CHECK_ARG(gate == nullptr || (!pl.rows && !pl.pos_major && bs == nullptr && pl.after == rr_plan::AFTER_NONE && !pl.zero_slab),
+                 "%s: this shape does not launch the plain forward kernel alone: no gate", name);
     if (pl.rows) return rr_conv1x1_rows(x, w, bias, y, pl.M, c, k, relu, stream);
     ConvArgs a{};
+    a.gate = gate; a.gate_max = gate_max;
     a.src = x; a.w = w; a.dst = y; a.bias = bias; a.stat_slab = stat_slab;
     a.N = n; a.SH = h; a.SW = wd; a.SC = c;
     a.DH = pl.dh; a.DW = pl.dw; a.DC = k;
@@ -1292,7 +1306,9 @@ static int fprop_impl(const char *name, const float *x, const float *w, const fl
     a.relu = relu; a.accumulate = accumulate; a.ksplit = pl.ks; a.pos_major = pl.pos_major; a.zero = zero_page();
     a.M = (int)pl.M; a.Kg = r * s * c; a.wK = k; a.wC = c;
     if (pl.fused) bs->into(a);
-    if (int rc = rr_conv_before_launch(pl, n, k, y, stat_slab, stream, name)) return rc;
+    if (gate != nullptr && pl.zero_dst) {
+        if (int rc = rr_gated_zero(y, sizeof(float) * (size_t)pl.M * k, gate, gate_max, 0, stream, name)) return rc;
+    } else if (int rc = rr_conv_before_launch(pl, n, k, y, stat_slab, stream, name)) return rc;
     if (int rc = launch_igemm<0>(a, pl.bn, pl.scalar, pl.blocks, 1, pl.ks, stream, name)) return rc;
     return rr_conv_after_launch(pl, bs, k, y, stat_slab, stream, name);
 }
@@ -1389,17 +1405,26 @@ extern "C" int rr_weight_flip_transpose_batch_bf16(const float *flat, float *wt_
 
 // the stride-1 data gradients: rr_dgrad_s1_geom's checks and flip (conv_launch.h), then the forward kernel on (dy, wt)
 static int dgrad_s1(const char *name, bool producer_ok, const float *dy, const float *wt, float *dx, int n, int h, int wd, int c, int k,
-                    int r, int s, int pad_h, int pad_w, int accumulate, hipStream_t stream, const BnSumArgs *bs = nullptr)
+                    int r, int s, int pad_h, int pad_w, int accumulate, hipStream_t stream, const BnSumArgs *bs = nullptr, const int *gate = nullptr,
+                    int gate_max = 0)
 {
     DgradS1Geom g;
     if (int rc = rr_dgrad_s1_geom(name, h, wd, r, s, pad_h, pad_w, producer_ok, &g)) return rc;
-    return fprop_impl(name, dy, wt, nullptr, dx, nullptr, n, g.p, g.q, k, c, r, s, 1, g.pad_h, g.pad_w, 0, accumulate, stream, bs);
+    return fprop_impl(name, dy, wt, nullptr, dx, nullptr, n, g.p, g.q, k, c, r, s, 1, g.pad_h, g.pad_w, 0, accumulate, stream, bs, gate, gate_max);
 }
 
 extern "C" int rr_conv_dgrad_s1(const float *dy, const float *wt, float *dx, int n, int h, int wd, int c, int k,
                                 int r, int s, int pad_h, int pad_w, int accumulate, hipStream_t stream)
 {
     return dgrad_s1("rr_conv_dgrad_s1", true, dy, wt, dx, n, h, wd, c, k, r, s, pad_h, pad_w, accumulate, stream);
+}
+
+// the dense side of the rows route's gate (conv_rows.hip): rr_conv_dgrad_s1, returning at once when *count <= max_rows
+extern "C" int rr_conv_dgrad_s1_unless(const float *dy, const float *wt, float *dx, int n, int h, int wd, int c, int k, int r, int s,
+                                       int pad_h, int pad_w, int accumulate, const int *count, int max_rows, hipStream_t stream)
+{
+    RR_CHECK_ARG(count != nullptr && c % 4 == 0 && k % 4 == 0, "rr_conv_dgrad_s1_unless: a count, C and K multiples of 4");
+    return dgrad_s1("rr_conv_dgrad_s1_unless", true, dy, wt, dx, n, h, wd, c, k, r, s, pad_h, pad_w, accumulate, stream, nullptr, count, max_rows);
 }
 
 // out[m][k], m = (n,p,q), k = (r*S + s)*C + c for k < R*S*C and 0 up to KP: the taps of a small-channel convolution laid
@@ -1484,19 +1509,18 @@ extern "C" int rr_conv_dgrad(const float *dy, const float *w, float *dx, int n, 
     return launch_igemm<1>(a, pl.bn, pl.scalar, pl.blocks, pl.gy, pl.ks, stream, "rr_conv_dgrad");
 }
 
-extern "C" int rr_conv_wgrad(const float *x, const float *dy, float *dw, int n, int h, int wd, int c, int k,
-                             int r, int s, int stride, int pad_h, int pad_w, int out_h, int out_w,
-                             hipStream_t stream)
+static int wgrad_impl(const char *name, const float *x, const float *dy, float *dw, int n, int h, int wd, int c, int k, int r, int s,
+                      int stride, int pad_h, int pad_w, int out_h, int out_w, hipStream_t stream, const int *gate, int gate_max)
 {
     const rr_plan::WgradPlan pl = rr_plan::wgrad_plan(rr_plan::MATH_F32, {n, h, wd, c, k, r, s, stride, pad_h, pad_w, out_h, out_w});
-    if (pl.refuse.why) return rr_refuse("rr_conv_wgrad", pl.refuse);
+    if (pl.refuse.why) return rr_refuse(name, pl.refuse);
     WgradArgs a{};
-    a.x = x; a.dy = dy; a.dw = dw; a.zero = zero_page();
+    a.x = x; a.dy = dy; a.dw = dw; a.zero = zero_page(); a.gate = gate; a.gate_max = gate_max;
     a.N = n; a.H = h; a.W = wd; a.C = c; a.K = k; a.R = r; a.S = s;
     a.P = pl.P; a.Q = pl.Q;
     a.stride = stride; a.pad_h = pad_h; a.pad_w = pad_w;
     a.M = (int)pl.M; a.mt = pl.mt; a.nt = pl.nt; a.chunks_per_split = pl.per_split;
-#define WG(BMv, BNv, ASv, BSv, PIPEv) rr_launch(conv_wgrad_kernel<BMv, BNv, ASv, BSv, PIPEv>, dim3(pl.grid), 256, pl.lds, stream, a, "rr_conv_wgrad")
+#define WG(BMv, BNv, ASv, BSv, PIPEv) rr_launch(conv_wgrad_kernel<BMv, BNv, ASv, BSv, PIPEv>, dim3(pl.grid), 256, pl.lds, stream, a, name)
 #define WG_AB(BMv, BNv) (pl.a_scalar ? (pl.b_scalar ? WG(BMv, BNv, true, true, 0) : WG(BMv, BNv, true, false, 0))         \
                                      : (pl.b_scalar ? WG(BMv, BNv, false, true, 0) : WG(BMv, BNv, false, false, 0)))
     if (pl.pipe == 3) return WG(128, 128, false, false, 3);
@@ -1505,6 +1529,21 @@ extern "C" int rr_conv_wgrad(const float *x, const float *dy, float *dw, int n, 
     return pl.bn == 128 ? WG_AB(32, 128) : WG_AB(32, 32);
 #undef WG
 #undef WG_AB
+}
+
+extern "C" int rr_conv_wgrad(const float *x, const float *dy, float *dw, int n, int h, int wd, int c, int k,
+                             int r, int s, int stride, int pad_h, int pad_w, int out_h, int out_w,
+                             hipStream_t stream)
+{
+    return wgrad_impl("rr_conv_wgrad", x, dy, dw, n, h, wd, c, k, r, s, stride, pad_h, pad_w, out_h, out_w, stream, nullptr, 0);
+}
+
+// the dense side of the rows route's gate: rr_conv_wgrad at stride 1, returning at once when *count <= max_rows
+extern "C" int rr_conv_wgrad_unless(const float *x, const float *dy, float *dw, int n, int h, int wd, int c, int k, int r, int s,
+                                    int pad_h, int pad_w, const int *count, int max_rows, hipStream_t stream)
+{
+    RR_CHECK_ARG(count != nullptr, "rr_conv_wgrad_unless: a count");
+    return wgrad_impl("rr_conv_wgrad_unless", x, dy, dw, n, h, wd, c, k, r, s, 1, pad_h, pad_w, 0, 0, stream, count, max_rows);
 }
 
 // the policy of conv_plan.h as the library was built with it, for tests/test_host_logic.py (C++ linkage, called by mangled name)

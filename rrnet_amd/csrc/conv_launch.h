@@ -4,6 +4,7 @@
 #include "common.h"
 #include "conv_plan.h"
 #include "rrnet_hip.h"
+#include "rrnet_hip_rows.h"
 
 // BatchNorm-backward sums of the producer of the tensor a stride-1 data gradient writes (see csrc/conv.hip ConvArgs::bs_y)
 struct BnSumArgs {
@@ -44,6 +45,9 @@ inline int rr_conv_link(const BnSumArgs *bs) { return bs == nullptr ? rr_plan::L
 
 // column sums / sums of squares of y [M][C] -> slab row 0, rows zeroed by the caller (csrc/conv.hip: colstats_kernel)
 int rr_conv_colstats(const float *y, long M, int C, double *slab, hipStream_t stream, const char *name);
+
+// zero fill on one side of the rows route's gate (csrc/conv_rows.hip): runs iff (*count <= max_rows) == (when_rows != 0)
+int rr_gated_zero(float *p, size_t bytes, const int *count, int max_rows, int when_rows, hipStream_t stream, const char *name);
 
 // in front of the launch: the split-K destination and (filled by rr_conv_colstats afterwards) the statistics slab, one zero-fill launch
 inline int rr_conv_before_launch(const rr_plan::FpropPlan &pl, int n, int k, float *y, double *stat_slab, hipStream_t stream, const char *name)

@@ -363,4 +363,28 @@ inline WgradPlan wgrad_plan(int family, const ConvGeom &g)
     return p;
 }
 
+// ---- the rows route of csrc/conv_rows.hip (rr_conv_dgrad_s1_rows, rr_conv_wgrad_rows): grids sized for max_rows list entries, the
+// workgroups past the count the device finds leave at once
+constexpr int ROWS_DGRAD_BM = 64;          // listed dx pixels of a data-gradient tile (x 128 channels)
+constexpr int ROWS_WGRAD_SLOTS = 1024;     // weight gradient: 256 CUs x 4 resident workgroups (32 KiB of LDS each) ...
+constexpr int ROWS_WGRAD_MIN_CHUNKS = 4;   // ... and never fewer than 4 K-steps of 32 list rows per split (WROWS_MIN_CHUNKS of the kernel)
+struct RowsPlan {
+    int dgrad_x, dgrad_y;     // target tiles; channel tiles
+    int mt, nt, splits, wgrad_grid;
+};
+
+inline RowsPlan rows_plan(int max_rows, int c, int k, int r, int s)
+{
+    RowsPlan p{};
+    p.dgrad_x = cdiv(max_rows, ROWS_DGRAD_BM);
+    p.dgrad_y = cdiv(c, 128);
+    p.mt = cdiv(k, 128); p.nt = cdiv(c, 128);
+    const int tiles = p.mt * p.nt * r * s;
+    p.splits = ROWS_WGRAD_SLOTS / tiles > 1 ? ROWS_WGRAD_SLOTS / tiles : 1;
+    const int most = cdiv(cdiv(max_rows, BK), ROWS_WGRAD_MIN_CHUNKS);
+    if (p.splits > most) p.splits = most;
+    p.wgrad_grid = tiles * p.splits;          // (0 with max_rows == 0: nothing to launch)
+    return p;
+}
+
 }  // namespace rr_plan

@@ -65,6 +65,8 @@ def _head_conv(dcn, bf16):
 
 
 class CenterNetDetector(nn.Module):
+    sparse_grad = False     # set by the model on a head trained through RegL1Loss (the offset head): few pixels carry gradient
+
     def __init__(self, planes, hm=True, num_stacks=2, dcn=False, dcn_bf16=False):
         super().__init__()
         self.hm = hm
@@ -78,7 +80,10 @@ class CenterNetDetector(nn.Module):
 
     def forward(self, input, index):
         head = self.detect_layer[index]
-        return RF.conv_bias(head[0](input), head[1])
+        feat = head[0](input)
+        if self.sparse_grad:
+            RF.expect_sparse_grad(feat)
+        return RF.conv_bias(feat, head[1])
 
 
 class CenterNetWHDetector(nn.Module):
@@ -94,7 +99,7 @@ class CenterNetWHDetector(nn.Module):
                                              for _ in range(num_stacks)])
 
     def forward(self, input, index):
-        conv = self.detect_conv_layer[index][0](input)
+        conv = RF.expect_sparse_grad(self.detect_conv_layer[index][0](input))    # trained through RegL1Loss: few pixels carry gradient
         hc, wc = self.detect_H_layer[index][0].conv, self.detect_W_layer[index][0].conv
         if hc.out_channels == 1 and wc.out_channels == 1 and hc.kernel_size[0] == wc.kernel_size[1]:
             # planes == 1 (the only configuration the reference instantiates): both 17-tap convolutions as

@@ -84,6 +84,8 @@ def _wgrad_async(fn, device, *tensors):
             img = ops.b16_carry(t)
             if img is not None:
                 img.record_stream(side)
+            for aux in ops.rows_side.carry(t) or ():       # the (rows, count) of a listed gradient: read by the rows weight gradient
+                aux.record_stream(side)
     _WG_STATE["pending"] = True
     task = torch._C._current_graph_task_id()       # one join per backward pass (a pass that raised leaves no stale flag)
     if task < 0:                                   # not inside a backward pass (a backward called by hand): join right away
@@ -562,7 +564,9 @@ class _ConvBias(torch.autograd.Function):
             # the consumer's data gradient already masked dy with this layer's ReLU and summed its columns
             if ol.dz is not None and ol.dz.data_ptr() == dy.data_ptr() and ol.dz.shape == dy.shape:
                 fused = ol.sums
-            ol.sums = ol.dz = None
+                if ol.rows is not None:
+                    ops.rows_side.attach(dy, ol.rows)      # ... and listed the pixels where it can be non-zero: both gradients below may take the rows route
+            ol.sums = ol.dz = ol.rows = None
         if b is not None:
             b_t = _grad_target(b)
             tgt = b_t if b_t is not None else torch.zeros_like(b)
@@ -607,6 +611,17 @@ def _conv_bias_apply(x, weight, bias, stride, pad, relu):
     if out_link is not None:
         out._rr_bnlink = out_link
     return out
+
+
+def expect_sparse_grad(t):
+    """`t` is the output of a conv + bias + ReLU layer whose only consumer is a narrow 1x1 layer behind a loss that reads few pixels
+    (RegL1Loss gathers at the objects' centres): that consumer's data gradient then also lists the pixels where the gradient can be
+    non-zero, and this layer's two gradients are computed from the list when the device finds it short (ops.active_rows).  A hint
+    only: a dense gradient takes the dense kernels."""
+    link = getattr(t, "_rr_bnlink", None)
+    if link is not None and link.relu_bias and not link.mask_only:
+        link.want_rows = True
+    return t
 
 
 def conv_bias(x, conv, relu=False):

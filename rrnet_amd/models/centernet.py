@@ -33,6 +33,7 @@ class CenterNet(nn.Module):
         self.hm = CenterNetDetector(planes=self.num_classes, num_stacks=stacks, hm=True)
         self.wh = CenterNetWHDetector(planes=1, num_stacks=stacks)
         self.reg = CenterNetDetector(planes=2, num_stacks=stacks)
+        self.reg.sparse_grad = True             # trained through RegL1Loss: its logits get gradient at the objects' centres only
         # builder-defined option cfg.Model.attention: constructed last, so every other parameter draws what it drew without it
         self.attention = build_attention(cfg.Model, stacks)
 

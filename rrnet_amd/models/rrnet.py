@@ -64,6 +64,7 @@ class RRNet(nn.Module):
         self.hm = CenterNetDetector(planes=self.num_classes, num_stacks=self.num_stacks, hm=True, dcn=dcn, dcn_bf16=dcn_bf16)
         self.wh = CenterNetWHDetector(planes=1, num_stacks=self.num_stacks, dcn=dcn, dcn_bf16=dcn_bf16)
         self.offset_reg = CenterNetDetector(planes=2, num_stacks=self.num_stacks, dcn=dcn, dcn_bf16=dcn_bf16)
+        self.offset_reg.sparse_grad = True      # trained through RegL1Loss: its logits get gradient at the objects' centres only
         self.head_detector = FasterRCNNDetector()
         # builder-defined (BASELINE configs[3] "bf16"; the reference is fp32-only): bf16 matrix operands with fp32
         # accumulation in every convolution of the backbone and the heads (csrc/conv_bf16.hip); activations, weights,

@@ -334,6 +334,8 @@ class _Sidecar:
 
 amax_side, b16_side = _Sidecar("_rr_amax"), _Sidecar("_rr_b16")
 amax_carry, b16_carry = amax_side.carry, b16_side.carry
+# (rows, count) of active_rows(): the pixels where a gradient tensor may be non-zero, made next to it by the launch that wrote it
+rows_side = _Sidecar("_rr_rows")
 
 
 def amax_drop(t):
@@ -360,6 +362,7 @@ def side_restore(carried, x, *image_only):
 def side_publish(t):
     amax_side.publish(t)
     b16_side.publish(t)
+    rows_side.publish(t)
 
 
 def image_wanted(c, pixels, device, multiple=128):
@@ -635,10 +638,14 @@ class BnLink:
     statistics, and the source of its ReLU mask (z for layers with a residual, scale / shift otherwise).  The consumer's
     backward leaves `sums` (and the gradient tensor they were taken of) here; the producer's backward picks them up
     instead of running rr_bn_bwd_reduce when the gradient it receives is that very tensor."""
-    __slots__ = ("y", "use_z", "mean", "invstd", "msc", "msh", "sums", "dz", "consumers", "relu_bias", "mask_only")
+    __slots__ = ("y", "use_z", "mean", "invstd", "msc", "msh", "sums", "dz", "consumers", "relu_bias", "mask_only", "want_rows", "rows")
 
     def __init__(self):
         self.y = self.mean = self.invstd = self.msc = self.msh = self.sums = self.dz = None
+        # want_rows: the producer sits behind a loss that touches few pixels (expect_sparse_grad): the consumer's data gradient
+        # also lists the pixels of its own dy that are not all zero and leaves (rows, count) in `rows`, next to dz
+        self.want_rows = False
+        self.rows = None
         # relu_bias: the producer is conv + bias + ReLU (a head's 3x3 layer): the consumer's data gradient stores the
         # ReLU-masked gradient and sums[:c] is the producer's bias gradient (rr_conv_dgrad_s1_relubias)
         self.relu_bias = False
@@ -765,6 +772,8 @@ def _dgrad_relubias(dy, w, out, geo, flops, bf, link, z, wt, head):
     image of dx comes out of it too.  Else a 10- or 2-channel dy is zero-padded to a multiple of 4 for the vector kernel (25 MB at 8x256x256)."""
     n, h, wd, c, k, r, s = geo[:7]
     link.sums, link.dz = _ZEROS.take(2 * c, dy.device), out
+    if link.want_rows and _CONV_ROWS and r == 1 and s == 1 and _mode() == MATH_F32:
+        link.rows = active_rows(dy)          # a 1x1 layer: dz is zero wherever dy is (the masked gradient and the sums are written as ever)
     if head:
         want16 = image_wanted(c, n * h * wd, dy.device, 256)
         out16 = torch.empty_like(out, dtype=torch.bfloat16) if want16 else None
@@ -818,6 +827,57 @@ def _dgrad_fp32(dy, w, out, geo, flops, stride):
             (dy, w, out) + geo[:7] + (stride,) + geo[7:], geo[:7] + (stride,))
 
 
+# The rows route (csrc/conv_rows.hip).  RR_CONV_ROWS=0: never taken (the A/B switch).
+_ROWS = _C.Family("rrnet_hip_rows.h")       # the family's own header beside include/rrnet_hip.h
+_CONV_ROWS = os.environ.get("RR_CONV_ROWS", "1") != "0"
+# the list length up to which the rows kernels do the work, as a share of the map's pixels: a design constant below the crossover
+# measured with tools/bench_conv.py --rows (profiles/conv_rows_shapes.txt); the choice itself is made on the device
+_ROWS_MAX_SHARE = 8
+_TARGETS_MAX_SHARE = 4      # the same for the data gradient's list of dx pixels (a 3x3 reaches up to nine per listed dy pixel)
+
+
+def active_rows(dy):
+    """dy [N,K,H,W] (NHWC) -> (rows int32[N*H*W], count int32[1], work): the ascending indices of its pixels that hold a non-zero value;
+    work: the scratch with the bit per pixel that active_targets reads."""
+    m, k = dy.shape[0] * dy.shape[2] * dy.shape[3], dy.shape[1]
+    rows = torch.empty(m, dtype=torch.int32, device=dy.device)
+    count = torch.empty(1, dtype=torch.int32, device=dy.device)
+    work = torch.empty(_ROWS.call("rr_active_rows_work_bytes", m) // 4, dtype=torch.int32, device=dy.device)
+    _ROWS.call("rr_active_rows", dy, m, k, rows, count, work)
+    return rows, count, work
+
+
+def active_targets(listed, x_shape, r, s, pad):
+    """active_rows' result for a dy -> (targets int32[N*H*W], count int32[1]): the pixels of dx [x_shape] a listed pixel reaches through a tap."""
+    n, _, h, wd = x_shape
+    dev = listed[0].device
+    targets = torch.empty(n * h * wd, dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    work = torch.empty(_ROWS.call("rr_active_rows_work_bytes", n * h * wd) // 4, dtype=torch.int32, device=dev)
+    _ROWS.call("rr_active_targets", listed[2], n, h, wd, r, s, pad[0], pad[1], targets, count, work)
+    return targets, count
+
+
+def _rows_shape_ok(dy, x_shape, w_shape, stride):
+    """The shapes the pair (rows entry point + _unless entry point) takes: stride 1, a filter with more than one tap on a map of at
+    least 64 pixels (the plain forward kernel is the dense side), C and K multiples of 4, every tensor below 2 GiB."""
+    n, c, h, wd = x_shape
+    k, _, r, s = w_shape
+    return (_CONV_ROWS and stride == 1 and _mode() == MATH_F32 and c % 4 == 0 and k % 4 == 0 and 1 < r * s <= 64 and h * wd >= 64
+            and tuple(dy.shape[2:]) == (h, wd) and max(n * h * wd * max(c, k), k * c * r * s) * 4 < (1 << 31))
+
+
+def _dgrad_rows_pair(dy, w, out, geo, wt, listed):
+    """Both sides of the gate on the same (count, max_rows): the rows kernel on the dx pixels the listed dy pixels reach, the forward kernel on
+    the flipped filter unless that list is short.  Timer keys of their own with no FLOPs: the one that returns at its gate must not enter a
+    roofline figure."""
+    rows, count = active_targets(listed, geo[:1] + (geo[3],) + geo[1:3], geo[5], geo[6], geo[7:9])
+    max_rows = geo[0] * geo[1] * geo[2] // _TARGETS_MAX_SHARE
+    wt = _flipped_filter(w, wt, None, False)[0]
+    _launch("conv_dgrad<rows>", 0.0, "rr_conv_dgrad_s1_rows", (dy, w, out) + geo + (rows, count, max_rows), geo[:7] + (1,), call=_ROWS.call)
+    _launch("conv_dgrad<dense>", 0.0, "rr_conv_dgrad_s1_unless", (dy, wt, out) + geo + (count, max_rows), geo[:7] + (1,), call=_ROWS.call)
+
+
 def conv_dgrad(dy, w, x_shape, stride=1, pad=(0, 0), out=None, accumulate=False, bnsum=None, bnsum_z=None, wt=None, wt16=None,
                wt_split=None):
     """dy [N,K,P,Q], w [K,C,R,S] -> dx [N,C,H,W]; with `out` and accumulate adds into it.  The kernel is dgrad_route's choice.
@@ -843,7 +903,11 @@ def conv_dgrad(dy, w, x_shape, stride=1, pad=(0, 0), out=None, accumulate=False,
         dy = f32_of(dy)               # (relumask included: it rounds the widened copy again — exact, but two passes too many)
     geo = (n, h, wd, c, k, r, s, pad[0], pad[1], int(accumulate))
     flops = 2.0 * dy.shape[0] * dy.shape[2] * dy.shape[3] * k * c * r * s
-    if route in ("conv16_s1", "relumask"):
+    listed = rows_side.now(dy) if route in ("fprop", "fprop_bnsum") and bf == MATH_F32 else None
+    if listed is not None and _rows_shape_ok(dy, x_shape, w.shape, stride):
+        # the pair carries no link: a launch that may return at its gate cannot produce the producer's sums (its own pass runs)
+        _dgrad_rows_pair(dy, w, out, geo, wt, listed)
+    elif route in ("conv16_s1", "relumask"):
         _dgrad_conv16_s1(dy, w, out, geo, flops, wt, wt16, *((bnsum, bnsum_z) if route == "relumask" else ()))
     elif route in ("relubias", "head"):
         _dgrad_relubias(dy, w, out, geo, flops, bf, bnsum, bnsum_z, wt, route == "head")
@@ -869,6 +933,14 @@ def conv_wgrad(x, dy, dw, stride=1, pad=(0, 0), explicit_out=False, algo_c=None)
         x16, dy16 = bf16_of(x), bf16_of(dy)
         _launch("conv16_wgrad", flops, "rr_conv16_wgrad", (x16, dy16, dw, n, h, wd, c, k, r, s, stride, pad[0], pad[1]),
                 (n, h, wd, c, k, r, s, stride))
+        return dw
+    listed = rows_side.now(dy) if not explicit_out and not is_phantom(x) and not is_phantom(dy) else None
+    if listed is not None and _rows_shape_ok(dy, tuple(x.shape), tuple(dw.shape), stride):
+        rows, count = listed[:2]
+        args = (x, dy, dw, n, h, wd, c, k, r, s, pad[0], pad[1])
+        max_rows = n * h * wd // _ROWS_MAX_SHARE
+        _launch("conv_wgrad<rows>", 0.0, "rr_conv_wgrad_rows", args + (rows, count, max_rows), (n, h, wd, c, k, r, s, 1), call=_ROWS.call)
+        _launch("conv_wgrad<dense>", 0.0, "rr_conv_wgrad_unless", args + (count, max_rows), (n, h, wd, c, k, r, s, 1), call=_ROWS.call)
         return dw
     x, dy = f32_of(x), f32_of(dy)            # (bf16-only operands in front of a layer the conv16 weight gradient does not take)
     bf = _bf16_ok(c, k, r, s, x, dy, pixels=dy.shape[0] * dy.shape[2] * dy.shape[3]) if wgrad_16bit_shape(c, k, r, s) else 0

@@ -29,6 +29,53 @@ SHAPES = [  # N, C, H, W, K, R, stride
     (8, 256, 256, 256, 256, 1, 2),
     (8, 3, 1024, 1024, 128, 7, 2),
 ]
+def bench_rows(counts=(800, 8192, 32768)):
+    """--rows: the rows route (csrc/conv_rows.hip) at the headline head shape, 8 x 256 x 256 x 256 -> 256, 3x3: the pair
+    (rows entry point + _unless entry point, as ops launches them) for lists of `counts` active pixels against the dense data
+    and weight gradient, and what each side costs when it returns at the gate."""
+    from rrnet_amd import _C
+    n, c, h, w, k = 8, 256, 256, 256, 256
+    m = n * h * w
+    x = ops.to_nhwc(torch.randn(n, c, h, w, device="cuda"))
+    wt_ = ops.to_nhwc(torch.randn(k, c, 3, 3, device="cuda") * 0.02)
+    flip = torch.empty(wt_.numel(), device="cuda")
+    _C.call("rr_weight_flip_transpose", wt_, flip, k, c, 3, 3)
+    dw = torch.zeros((k, 3, 3, c), device="cuda").permute(0, 3, 1, 2)
+    dx = ops.empty_nhwc(n, c, h, w, "cuda")
+    geo = (n, h, w, c, k, 3, 3, 1, 1)
+    cap = m // ops._ROWS_MAX_SHARE
+    g = torch.Generator(device="cuda").manual_seed(1)
+    for cnt in sorted(set(counts) | {cap, cap + 1}):
+        dy = ops.zeros_nhwc(n, k, h, w, "cuda")
+        sel = torch.randperm(m, device="cuda", generator=g)[:cnt]
+        dy.permute(0, 2, 3, 1).reshape(m, k)[sel] = torch.randn(cnt, k, device="cuda", generator=g)
+        listed = ops.active_rows(dy)
+        rows, count = listed[:2]
+        assert int(count.item()) == cnt
+        tg, tcount = ops.active_targets(listed, (n, c, h, w), 3, 3, (1, 1))      # the data gradient works from the dx pixels the list reaches
+        tcnt, tcap = int(tcount.item()), m // ops._TARGETS_MAX_SHARE
+        t_list = timeit(lambda: ops.active_targets(ops.active_rows(dy), (n, c, h, w), 3, 3, (1, 1)))
+        d_dense = timeit(lambda: _C.call("rr_conv_dgrad_s1", dy, flip, dx, *geo, 0))
+        w_dense = timeit(lambda: _C.call("rr_conv_wgrad", x, dy, dw, n, h, w, c, k, 3, 3, 1, 1, 1, 0, 0))
+        d_rows = timeit(lambda: _C.call("rr_conv_dgrad_s1_rows", dy, wt_, dx, *geo, 0, tg, tcount, m))
+        d_rows_acc = timeit(lambda: _C.call("rr_conv_dgrad_s1_rows", dy, wt_, dx, *geo, 1, tg, tcount, m))
+        w_rows = timeit(lambda: _C.call("rr_conv_wgrad_rows", x, dy, dw, *geo, rows, count, m))
+        d_pair = timeit(lambda: (_C.call("rr_conv_dgrad_s1_rows", dy, wt_, dx, *geo, 0, tg, tcount, tcap),
+                                 _C.call("rr_conv_dgrad_s1_unless", dy, flip, dx, *geo, 0, tcount, tcap)))
+        w_pair = timeit(lambda: (_C.call("rr_conv_wgrad_rows", x, dy, dw, *geo, rows, count, cap),
+                                 _C.call("rr_conv_wgrad_unless", x, dy, dw, *geo, count, cap)))
+        d_exit = timeit(lambda: _C.call("rr_conv_dgrad_s1_unless", dy, flip, dx, *geo, 0, count, m))      # dense launch returning at the gate
+        w_exit = timeit(lambda: _C.call("rr_conv_wgrad_unless", x, dy, dw, *geo, count, m))
+        r_exit = timeit(lambda: (_C.call("rr_conv_dgrad_s1_rows", dy, wt_, dx, *geo, 0, tg, tcount, tcnt - 1),  # rows launches returning at the gate
+                                 _C.call("rr_conv_wgrad_rows", x, dy, dw, *geo, rows, count, cap if cnt > cap else 0)))
+        print("rows %6d -> %6d dx pixels (max_rows %d, %d) | lists %.3f ms | dense dgrad %.3f wgrad %.3f | rows alone dgrad %.3f (accumulating %.3f) wgrad %.3f | "
+              "pair dgrad %.3f wgrad %.3f | at the gate: dense dgrad %.3f wgrad %.3f, rows dgrad+wgrad %.3f ms"
+              % (cnt, tcnt, cap, tcap, t_list, d_dense, w_dense, d_rows, d_rows_acc, w_rows, d_pair, w_pair, d_exit, w_exit, r_exit), flush=True)
+
+
+if "--rows" in sys.argv:
+    bench_rows()
+    sys.exit(0)
 only = [int(a) for a in sys.argv[1:]]
 for i, (n, c, h, w, k, r, st) in enumerate(SHAPES):
     if only and i not in only: continue
