@@ -103,7 +103,7 @@ def header_signatures():
 MAIN_HEADER = "rrnet_hip.h"
 # Companion headers: a kernel family with a header of its own beside rrnet_hip.h (same grammar, same library, same rules).
 # header_signatures() stays the main header's table; a family's entries are reached through its Family object.
-COMPANION_HEADERS = ("rrnet_hip_se.h", "rrnet_hip_attn.h", "rrnet_hip_dw.h", "rrnet_hip_rows.h")
+COMPANION_HEADERS = ("rrnet_hip_se.h", "rrnet_hip_attn.h", "rrnet_hip_dw.h", "rrnet_hip_rows.h", "rrnet_hip_wino.h")
 _FAMILY_SIGS = {}
 
 

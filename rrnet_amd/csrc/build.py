@@ -32,6 +32,7 @@ PER_FILE = {
     "wbf.hip": ["-ffp-contract=off"],
     "textio.hip": ["-ffp-contract=off"],
     "depthwise.hip": ["-ffp-contract=off"],
+    "conv_wino.hip": ["-ffp-contract=off"],
 }
 
 

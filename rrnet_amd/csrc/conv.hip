@@ -71,6 +71,8 @@ struct ConvArgs {
                        // (a padded 3x3 on a 3x3 map: 49 of 81 (pixel, tap) pairs are real)
     const int *gate;   // the _unless entry points (plain forward kernel only): the launch returns when *gate <= gate_max — the rows
     int gate_max;      // route of conv_rows.hip, enqueued next to it with the opposite test, does the work then.  null: no gate
+    long batch_src, batch_w, batch_dst;   // BATCH instantiations (the sixteen GEMMs of conv_wino.hip in one launch): blockIdx.y moves the
+                       // three tensors on by so many elements; every slice is addressed from its own base, so each stays below 2 GiB
 };
 
 __device__ __forceinline__ int xcd_remap(int bid, int nb)
@@ -90,10 +92,12 @@ __device__ __forceinline__ int xcd_remap(int bid, int nb)
 // the extra state cost 20 registers and the third workgroup per CU (457 -> 466 ms per train step).
 // The pipelined instantiations are compiled FOR three workgroups per CU (168 registers): left to itself the allocator
 // follows the epilogue's appetite (220 with the accumulators in AGPRs), not the K loop's.
-template <int BN, int MODE, bool SCALAR, int BKT, int PIPE, bool BNS = false, bool POSM = false>
+// BATCH: grid.y = independent problems of one geometry (ConvArgs::batch_*): the pipelined plain forward kernel only.
+template <int BN, int MODE, bool SCALAR, int BKT, int PIPE, bool BNS = false, bool POSM = false, bool BATCH = false>
 __global__ __launch_bounds__(256, PIPE == 2 ? 3 : 1) void conv_igemm_kernel(const ConvArgs a)
 {
     static_assert(BKT == 32 && (PIPE == 0 || PIPE == 2), "conv_igemm_kernel: K-step 32, PIPE 0 or 2");
+    static_assert(!BATCH || (MODE == 0 && PIPE == 2 && !BNS && !POSM), "conv_igemm_kernel: BATCH is for the pipelined plain forward kernel");
     if constexpr (MODE == 0 && !BNS && !POSM) {
         if (a.gate != nullptr && *a.gate <= a.gate_max) return;      // wave-uniform: two scalar loads, no vector register
     }
@@ -459,8 +463,8 @@ __global__ __launch_bounds__(256, PIPE == 2 ? 3 : 1) void conv_igemm_kernel(cons
         void *q = reinterpret_cast<void *>(((unsigned long long)hi << 32) | lo);
         return __builtin_amdgcn_make_buffer_rsrc(q, 0, __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000);
     };
-    const __amdgpu_buffer_rsrc_t rs_src = make_srd(a.src, (long)a.N * a.SH * a.SW * a.SC * 4);
-    const __amdgpu_buffer_rsrc_t rs_w = make_srd(a.w, (long)a.wK * RS * a.wC * 4);
+    const __amdgpu_buffer_rsrc_t rs_src = make_srd(BATCH ? a.src + (long)blockIdx.y * a.batch_src : a.src, (long)a.N * a.SH * a.SW * a.SC * 4);
+    const __amdgpu_buffer_rsrc_t rs_w = make_srd(BATCH ? a.w + (long)blockIdx.y * a.batch_w : a.w, (long)a.wK * RS * a.wC * 4);
     constexpr unsigned OOB = 0xFFFFFFF0u;
     int a_boff[AJ], b_boff[BJ];
 #pragma unroll
@@ -572,7 +576,7 @@ __global__ __launch_bounds__(256, PIPE == 2 ? 3 : 1) void conv_igemm_kernel(cons
     // the destination through a buffer descriptor (dst32: below 2 GiB, set by launch_igemm): 32-bit byte offsets, and a lane
     // whose row or column lies outside the tensor gets an out-of-range offset, so the buffer unit drops its store / atomic
     // and answers its load with 0 — no exec-mask branch per element, hence nothing between consecutive stores
-    const __amdgpu_buffer_rsrc_t rs_dst = bs_srd(a.dst, a.dst32 ? (long)a.M * a.DC * 4 : 0);
+    const __amdgpu_buffer_rsrc_t rs_dst = bs_srd(BATCH ? a.dst + (long)blockIdx.y * a.batch_dst : a.dst, a.dst32 ? (long)a.M * a.DC * 4 : 0);
     constexpr unsigned OOBD = 0xFFFFFFF0u;
     const int mode_e = a.ksplit > 1 ? 2 : (a.accumulate ? 1 : 0);   // wave-uniform: one branch around the whole epilogue
     auto put_stats = [&](int j, float s1, float s2) {
@@ -1271,6 +1275,27 @@ extern "C" size_t rr_conv_stat_slab_bytes(int n, int p, int q, int k)
 {
     const long M = (long)n * p * q;
     return (size_t)((M + BM - 1) / BM) * 2 * k * sizeof(double);
+}
+
+// The sixteen GEMMs of the Winograd route in one launch: m[i][t][ko] = sum_c v[i][t][c] * u[i][ko][c], i = blockIdx.y — the plain
+// pipelined forward kernel at 1x1 geometry (one "image" of T pixels), plain stores.  The caller (rr_plan::wino_plan) keeps every
+// slice below 2 GiB.
+int rr_conv_wino_gemm(const float *v, const float *u, float *m, long tiles, int c, int k, hipStream_t stream, const char *name)
+{
+    RR_CHECK_ARG(tiles > 0 && c > 0 && k > 0 && c % 4 == 0 && k % 4 == 0 && tiles * c * 4 < (1l << 31) && tiles * k * 4 < (1l << 31)
+                 && (long)k * c * 4 < (1l << 31), "%s: bad GEMM geometry", name);
+    ConvArgs a{};
+    a.src = v; a.w = u; a.dst = m; a.zero = zero_page();
+    a.N = 1; a.SH = 1; a.SW = (int)tiles; a.SC = c;
+    a.DH = 1; a.DW = (int)tiles; a.DC = k;
+    a.R = 1; a.S = 1; a.stride = 1; a.ksplit = 1;
+    a.M = (int)tiles; a.Kg = c; a.wK = k; a.wC = c; a.dst32 = 1;
+    a.batch_src = tiles * c; a.batch_w = (long)k * c; a.batch_dst = tiles * k;
+    const int bn = k > 64 ? 128 : 64;
+    const dim3 grid(rr_cdiv(tiles, BM) * rr_cdiv(k, bn), 16, 1);
+    if (bn == 128)
+        return rr_launch(conv_igemm_kernel<128, 0, false, BK, 2, false, false, true>, grid, 256, igemm_lds(128, false, 1), stream, a, name);
+    return rr_launch(conv_igemm_kernel<64, 0, false, BK, 2, false, false, true>, grid, 256, igemm_lds(64, false, 1), stream, a, name);
 }
 
 int rr_conv_colstats(const float *y, long M, int C, double *slab, hipStream_t stream, const char *name)

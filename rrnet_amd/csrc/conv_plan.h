@@ -387,4 +387,56 @@ inline RowsPlan rows_plan(int max_rows, int c, int k, int r, int s)
     return p;
 }
 
+// ---- the Winograd F(2x2,3x3) route of csrc/conv_wino.hip (rr_conv_wino_fprop, rr_conv_wino_dgrad_bnsum): input transform, sixteen
+// GEMMs in one launch of conv.hip's forward kernel, output transform with the forward kernel's epilogue.  Additive: a launch it
+// does not take stays with fprop_plan.  g is the FORWARD geometry of the launch (a stride-1 data gradient: dy's map, c = its
+// channels, k = dx's), f the forward kernel's flags.
+constexpr long WINO_MIN_PIXELS = 65536;    // the gate's floor in output pixels n*p*q: above it lie the 128 x 128 and 256 x 256 levels of
+                                           // the headline step.  Measured, the route also wins at 32768 and 8192 pixels (8 x 64 x 64 x 384: 0.40
+                                           // against 0.62 ms; 8 x 32 x 32 x 384: 0.105 against 0.18-0.19), but the launches of fp32 data gradients of
+                                           // 8192 and of 32768 pixels are pinned to the direct entry points (tests/golden/conv_bwd_routes.json,
+                                           // tests/test_bn_forward_gpu.py), and below 8192 the small-shape contracts are the direct route's
+constexpr int WINO_OUT_LANES = 4;          // output transform: tile lanes of a workgroup (x 64 channel quads)
+struct WinoPlan {
+    const char *refuse;   // non-null: the route does not take the launch, and why
+    int floor_only;       // ... and the pixel floor is the only reason (the entry points run such a shape: tests, benchmarks)
+    int th, tw;           // tiles along h and w
+    long tiles;           // T = n * th * tw
+    int bn;               // GEMM tile width (conv_igemm_kernel<bn>, 128 rows)
+    int gemm_blocks;      // GEMM workgroups per batch index (grid.x; grid.y = 16)
+    int out_x, out_y;     // output transform: one workgroup per statistics-slab row x 256-channel slice
+    int tiles_per_wg;     // ... and the tiles each of them walks
+    long ws_bytes;        // V [16][T][c] + M [16][T][k]
+};
+
+inline WinoPlan wino_plan(int math, const ConvGeom &g, const ConvFlags &f)
+{
+    WinoPlan p{};
+    const long G2 = 1l << 31;
+#define RR_PLAN_REFUSE(cond, why) do { if (cond) { p.refuse = why; return p; } } while (0)
+    RR_PLAN_REFUSE(!(g.n > 0 && g.h > 0 && g.w > 0 && g.c > 0 && g.k > 0), "bad dims");
+    RR_PLAN_REFUSE(math != MATH_F32, "fp32 arithmetic only");
+    RR_PLAN_REFUSE(!(g.r == 3 && g.s == 3 && g.stride == 1 && g.pad_h == 1 && g.pad_w == 1), "3x3, stride 1, pad 1 only");
+    RR_PLAN_REFUSE(g.out_h > 0 || g.out_w > 0, "no explicit output size");
+    RR_PLAN_REFUSE(!(g.c % 4 == 0 && g.k % 4 == 0), "C and K must be multiples of 4");
+    RR_PLAN_REFUSE(f.strided_dst, "no strided destination");
+    RR_PLAN_REFUSE(f.link == LINK_RELU_BIAS, "the conv + bias + ReLU link is not built on this route");
+    RR_PLAN_REFUSE(f.link == LINK_BN && (f.bias || f.relu || f.stats || g.k > 1024), "a BatchNorm link: plain data gradient, at most 1024 channels");
+    const long M = (long)g.n * g.h * g.w;
+    p.th = (g.h + 1) / 2; p.tw = (g.w + 1) / 2;
+    p.tiles = (long)g.n * p.th * p.tw;
+    // every tensor, and every batch slice of V and M (each addressed from its own base), through 32-bit byte offsets
+    RR_PLAN_REFUSE(!(M * g.c * 4 < G2 && M * g.k * 4 < G2 && 9l * g.c * g.k * 4 < G2 && p.tiles * g.c * 4 < G2 && p.tiles * g.k * 4 < G2),
+                   "tensors must stay below 2 GiB");
+    p.bn = g.k > 64 ? 128 : 64;
+    p.gemm_blocks = cdiv(p.tiles, BM) * cdiv(g.k, p.bn);
+    p.out_x = cdiv(M, BM);
+    p.out_y = cdiv(g.k / 4, 64);
+    p.tiles_per_wg = cdiv(p.tiles, p.out_x);
+    p.ws_bytes = 16l * p.tiles * ((long)g.c + g.k) * 4;
+    if (M < WINO_MIN_PIXELS) { p.refuse = "fewer output pixels than the route's floor"; p.floor_only = 1; }
+#undef RR_PLAN_REFUSE
+    return p;
+}
+
 }  // namespace rr_plan

@@ -82,6 +82,14 @@ class FlatParams:
         self._wt_version = None
         self._wt_pver = {}                          # id(parameter) -> its own version counter at the last fill
         self._wt_enabled = True and dev.type == "cuda"
+        # Winograd-transformed filters U = G g Gt (csrc/conv_wino.hip) of the parameters the route has asked for so far, of the
+        # filter itself (forward) or of its flipped / transposed copy (data gradient): one tensor each, refilled by ONE launch per
+        # optimizer step behind the flipped-filter cache (wino_view, _refresh_wino)
+        self._p_at = {o: p for p, o in zip(params, offs) if p.dim() == 4}
+        self._wino, self._wino_rows, self._wino_table = {}, [], None
+        self._wino_version, self._wino_pver = None, {}
+        if self._wt_enabled:
+            ops.FLAT_BUFFERS.add(self)
         self.overlap = os.environ.get("RR_DP_OVERLAP", "1") != "0"
         self._pg = None
         self._begin_step()
@@ -115,16 +123,50 @@ class FlatParams:
         the update kernel, and by wt_view when the parameters were written some other way: an in-place write to the flat
         buffer (broadcast) or to a parameter (load_state_dict's param.copy_) moves that tensor's version counter, which is
         compared at every use.  A write through `p.data` is invisible to both counters: call invalidate_wt() after one."""
-        if not self._wt_enabled or self.wt_flat is None:
+        if not self._wt_enabled:
             return
         from rrnet_amd import _C
-        if self.w16_flat is not None:
-            _C.call("rr_weight_flip_transpose_batch_bf16", self.flat, self.wt_flat, self.w16_flat, self.wt16_flat, self._wt_table,
-                    self._wt_table.shape[0])
-        else:
-            _C.call("rr_weight_flip_transpose_batch", self.flat, self.wt_flat, self._wt_table, self._wt_table.shape[0])
-        self._wt_version = self.flat._version
-        self._wt_pver = {id(p): p._version for p in self.params if p.dim() == 4}
+        if self.wt_flat is not None:
+            if self.w16_flat is not None:
+                _C.call("rr_weight_flip_transpose_batch_bf16", self.flat, self.wt_flat, self.w16_flat, self.wt16_flat, self._wt_table,
+                        self._wt_table.shape[0])
+            else:
+                _C.call("rr_weight_flip_transpose_batch", self.flat, self.wt_flat, self._wt_table, self._wt_table.shape[0])
+            self._wt_version = self.flat._version
+            self._wt_pver = {id(p): p._version for p in self.params if p.dim() == 4}
+        self._refresh_wino()          # (behind the flipped copies: the data gradients' U is their transform)
+
+    def _refresh_wino(self):
+        if not self._wino:
+            return
+        if self._wino_table is None:
+            self._wino_table = torch.tensor(self._wino_rows, dtype=torch.int64, device=self.flat.device)
+        ops._WINO.call("rr_wino_filter_batch", self._wino_table, len(self._wino_rows))
+        self._wino_version = (self.flat._version, self.epoch)
+        self._wino_pver = {id(p): p._version for p in self._p_at.values()}
+
+    def wino_view(self, w, flipped):
+        """U [16][K'][C'] (flat) of the filter tensor w when it is a 4-D parameter of this buffer, else None.  flipped: of its flipped /
+        transposed copy (K' = c, C' = k), the filter of the stride-1 data gradient.  A filter asked for the first time joins the table
+        of the per-step launch; a cache older than the parameters is refilled first, as wt_view does."""
+        if not self._wt_enabled or w.device != self.flat.device:
+            return None
+        off = w.data_ptr() - self.flat.data_ptr()
+        p = self._p_at.get(off // 4) if 0 <= off < self.numel * 4 and off % 4 == 0 else None
+        if p is None or tuple(w.shape) != tuple(p.shape) or w.stride() != p.stride():
+            return None
+        if flipped and self.wt_view(p) is None:          # (also refills a stale flipped copy, and this cache behind it)
+            return None
+        u = self._wino.get((off, flipped))
+        if u is None:
+            k, c = p.shape[:2]
+            u = self._wino[(off, flipped)] = torch.empty(16 * k * c, dtype=torch.float32, device=self.flat.device)
+            src = self.wt_flat if flipped else self.flat
+            self._wino_rows.append([src.data_ptr() + off, u.data_ptr(), c if flipped else k, k if flipped else c])
+            self._wino_table = self._wino_version = None
+        if self._wino_version != (self.flat._version, self.epoch) or self._wino_pver.get(id(p)) != p._version:
+            self._refresh_wino()
+        return u
 
     def invalidate_wt(self):
         """Mark every per-step quantity derived from the parameters stale: the flipped-filter cache (the next data gradient

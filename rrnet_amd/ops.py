@@ -5,6 +5,7 @@ import os
 import sys
 import threading
 import types
+import weakref
 
 import torch
 
@@ -564,6 +565,13 @@ def conv_fprop(x, w, bias=None, stride=1, pad=(0, 0), relu=False, want_stats=Fal
         slab = torch.empty(nbytes // 8, dtype=torch.float64, device=x.device)
     bf = _bf16_ok(c, 4 if _mode() != MATH_F16X3 else k, r, s, x, w, y, pixels=n * p * q)
     flops = 2.0 * n * p * q * k * (c * r * s if algo_kg is None else algo_kg)
+    if bf == MATH_F32 and wino_takes(n, h, wd, c, k, r, s, stride, pad, bias is not None, relu, want_stats):
+        # the Winograd route (csrc/conv_wino.hip); its timer key carries the multiplications it executes, 16 of the direct 36
+        u, ws = _wino_filter(w, False), _wino_ws(x.device, n, h, wd, c, k)
+        _launch("conv_fprop<wino>", flops * 16.0 / 36.0, "rr_conv_wino_fprop",
+                (x, u, bias, y, slab, ws, ws.numel() * 4, n, h, wd, c, k, int(relu), 0), (n, h, wd, c, k, r, s, stride),
+                4.0 * (x.numel() + y.numel() + w.numel()) + 2.0 * ws.numel() * 4.0, call=_WINO.call)
+        return (y, slab) if want_stats else y
     # w16: the filter already rounded to bf16 (optional); split operands: the two tensors' maxima
     if bf == MATH_F16X3 and w_split is None:
         # a LOCAL that lives until the launch below has been enqueued: built inside the argument tuple the temporary was
@@ -827,6 +835,80 @@ def _dgrad_fp32(dy, w, out, geo, flops, stride):
             (dy, w, out) + geo[:7] + (stride,) + geo[7:], geo[:7] + (stride,))
 
 
+# The Winograd F(2x2,3x3) route of the large stride-1 fp32 3x3 convolutions (csrc/conv_wino.hip): conv_fprop and the
+# "fprop" / "fprop_bnsum" data gradients take it where rr_conv_wino_plan does.  RR_CONV_WINO=0: never taken (the A/B switch).
+_WINO = _C.Family("rrnet_hip_wino.h")
+_CONV_WINO = os.environ.get("RR_CONV_WINO", "1") != "0"
+_WINO_BELOW_FLOOR = False       # test switch: the route also where the plan's pixel floor is its only objection (tests/test_conv_wino_gpu.py)
+_WINO_TAKES = {}                # plan arguments -> the plan's answer (take, the floor is the only reason not to)
+_WINO_PLAN_FN = []
+_WINO_WS = {}                   # (device, stream) -> the grow-only workspace V + M of the launches enqueued there
+FLAT_BUFFERS = weakref.WeakSet()     # the FlatParams that keep transformed filters (rrnet_amd/flat.py registers itself)
+
+
+def wino_takes(n, h, wd, c, k, r, s, stride, pad, bias=False, relu=False, stats=False, accumulate=False, link=False):
+    """Does the Winograd route take this forward-kernel launch (fp32 arithmetic; a data gradient in its forward geometry)?
+    rr_plan::wino_plan's decision, asked once per distinct launch."""
+    if not _CONV_WINO:
+        return False
+    key = (n, h, wd, c, k, r, s, stride, pad[0], pad[1], int(bias) | int(relu) << 1 | int(stats) << 2 | int(accumulate) << 3 | int(link) << 8)
+    hit = _WINO_TAKES.get(key)
+    if hit is None:
+        if not _WINO_PLAN_FN:
+            # typed from the header like every entry, but asked past _C.fn: a shape predicate launches nothing, and how often the host
+            # asks it is not part of what a call computes (the launch records of tests/conv_route_cases.py)
+            f, (sig, _) = getattr(_C.lib(), "rr_conv_wino_plan"), _C.declared("rr_conv_wino_plan")
+            f.restype, f.argtypes = sig[0], sig[1]
+            _WINO_PLAN_FN.append(f)
+        plan = (_C.c_int * 11)()
+        _C.check(_WINO_PLAN_FN[0](MATH_F32, *key[:10], 0, 0, key[10], plan), "rr_conv_wino_plan")
+        hit = _WINO_TAKES[key] = (bool(plan[0]), bool(plan[1]))
+    return hit[0] or (hit[1] and _WINO_BELOW_FLOOR)
+
+
+def _wino_ws(device, n, h, wd, c, k):
+    """The workspace of one launch: never allocated per call, grown to the largest layer seen on this stream (the compute stream; the
+    side-stream weight gradients do not come here)."""
+    need = _WINO.call("rr_conv_wino_ws_bytes", n, h, wd, c, k) // 4
+    key = (device, torch.cuda.current_stream(device).cuda_stream)
+    ws = _WINO_WS.get(key)
+    if ws is None or ws.numel() < need:
+        _WINO_WS[key] = None         # (the old block goes back before the larger one is asked for)
+        ws = _WINO_WS[key] = torch.empty(need, dtype=torch.float32, device=device)
+    return ws
+
+
+def _wino_filter(w, flipped, wt=None):
+    """U [16][K'][C'] of the filter w (flipped: of its flipped / transposed form, the data gradient's filter): the cached transform
+    of a FlatParams buffer's parameter (one launch per optimizer step for all of them), else transformed here."""
+    for flat in FLAT_BUFFERS:
+        u = flat.wino_view(w, flipped)
+        if u is not None:
+            return u
+    k, c = w.shape[0], w.shape[1]
+    src = _flipped_filter(w, wt, None, False)[0] if flipped else w
+    u = torch.empty(16 * k * c, dtype=torch.float32, device=w.device)
+    _WINO.call("rr_wino_filter", src, u, *((c, k) if flipped else (k, c)))
+    return u
+
+
+def _dgrad_wino(dy, w, out, geo, flops, wt, link=None, z=None):
+    """fprop / fprop_bnsum on the Winograd route: the data gradient as the convolution of dy with the flipped filter; with a link the
+    producer's BatchNorm-backward sums come out of the output transform's epilogue (rr_conv_dgrad_s1_bnsum's contract)."""
+    n, h, wd, c, k = geo[:5]
+    u, ws = _wino_filter(w, True, wt), _wino_ws(dy.device, n, h, wd, k, c)
+    nbytes = 4.0 * (dy.numel() + out.numel() * ((2 if geo[9] else 1) + (link is not None)) + w.numel()) + 2.0 * ws.numel() * 4.0
+    if link is None:
+        _launch("conv_dgrad<wino>", flops * 16.0 / 36.0, "rr_conv_wino_fprop",
+                (dy, u, None, out, None, ws, ws.numel() * 4, n, h, wd, k, c, 0, geo[9]), geo[:7] + (1,), nbytes, call=_WINO.call)
+        return
+    slab = torch.empty(_C.call("rr_conv_stat_slab_bytes", n, h, wd, c) // 8, dtype=torch.float64, device=dy.device)
+    link.sums, link.dz = _ZEROS.take(2 * c, dy.device), out
+    _launch("conv_dgrad<wino>+bnsum", flops * 16.0 / 36.0, "rr_conv_wino_dgrad_bnsum",
+            (dy, u, out, ws, ws.numel() * 4, n, h, wd, c, k, geo[9], link.y, z if link.use_z else None, link.mean, link.invstd, link.msc,
+             link.msh, slab, link.sums), geo[:7] + (1,), nbytes, call=_WINO.call)
+
+
 # The rows route (csrc/conv_rows.hip).  RR_CONV_ROWS=0: never taken (the A/B switch).
 _ROWS = _C.Family("rrnet_hip_rows.h")       # the family's own header beside include/rrnet_hip.h
 _CONV_ROWS = os.environ.get("RR_CONV_ROWS", "1") != "0"
@@ -907,6 +989,9 @@ def conv_dgrad(dy, w, x_shape, stride=1, pad=(0, 0), out=None, accumulate=False,
     if listed is not None and _rows_shape_ok(dy, x_shape, w.shape, stride):
         # the pair carries no link: a launch that may return at its gate cannot produce the producer's sums (its own pass runs)
         _dgrad_rows_pair(dy, w, out, geo, wt, listed)
+    elif (route in ("fprop", "fprop_bnsum") and bf == MATH_F32
+          and wino_takes(n, h, wd, k, c, r, s, stride, (r - 1 - pad[0], s - 1 - pad[1]), accumulate=accumulate, link=route == "fprop_bnsum")):
+        _dgrad_wino(dy, w, out, geo, flops, wt, *((bnsum, bnsum_z) if route == "fprop_bnsum" else ()))
     elif route in ("conv16_s1", "relumask"):
         _dgrad_conv16_s1(dy, w, out, geo, flops, wt, wt16, *((bnsum, bnsum_z) if route == "relumask" else ()))
     elif route in ("relubias", "head"):

@@ -73,8 +73,70 @@ def bench_rows(counts=(800, 8192, 32768)):
               % (cnt, tcnt, cap, tcap, t_list, d_dense, w_dense, d_rows, d_rows_acc, w_rows, d_pair, w_pair, d_exit, w_exit, r_exit), flush=True)
 
 
+WINO_SHAPES = [(8, 256, 256, 256, 256), (8, 256, 128, 128, 256), (8, 256, 128, 128, 384), (8, 384, 64, 64, 384),
+               (8, 384, 32, 32, 384)]       # N, C, H, W, K of the headline step's 3x3 stride-1 layers, largest level first
+
+
+def bench_wino(rounds=3):
+    """--wino: the Winograd route (csrc/conv_wino.hip) against the direct kernel at the headline's 3x3 stride-1 levels, per pass
+    (fprop with statistics, dgrad, dgrad accumulating, dgrad with the producer's BatchNorm link), the two arms alternating
+    `rounds` times: mean and spread (max - min) of each, and the route's stages (input transform, GEMMs; the output transform
+    is the rest).  The gate's floor (rr_plan::WINO_MIN_PIXELS) is read off this table: the smallest level at which the route wins
+    by more than twice the larger spread."""
+    from rrnet_amd import _C
+    W = ops._WINO
+    for n, c, h, w, k in WINO_SHAPES:
+        x = ops.to_nhwc(torch.randn(n, c, h, w, device="cuda"))
+        wt = ops.to_nhwc(torch.randn(k, c, 3, 3, device="cuda") * 0.02)
+        dy = ops.to_nhwc(torch.randn(n, k, h, w, device="cuda"))
+        y, dx = ops.empty_nhwc(n, k, h, w, "cuda"), ops.empty_nhwc(n, c, h, w, "cuda")
+        flip = torch.empty(wt.numel(), device="cuda")
+        _C.call("rr_weight_flip_transpose", wt, flip, k, c, 3, 3)
+        u_f, u_d = ops._wino_filter(wt, False), ops._wino_filter(wt, True, flip)
+        ws = ops._wino_ws(x.device, n, h, w, max(c, k), max(c, k))
+        wsb = ws.numel() * 4
+        slab = torch.empty(_C.call("rr_conv_stat_slab_bytes", n, h, w, max(c, k)) // 8, dtype=torch.float64, device="cuda")
+        sums = torch.zeros(2 * c, dtype=torch.float64, device="cuda")
+        py = ops.to_nhwc(torch.randn(n, c, h, w, device="cuda"))
+        mean, invstd = torch.zeros(c, device="cuda"), torch.ones(c, device="cuda")
+        msc, msh = torch.ones(c, device="cuda"), torch.zeros(c, device="cuda")
+        geo = (n, h, w, c, k, 3, 3, 1, 1)
+        arms = {
+            "fprop+stats": (lambda: _C.call("rr_conv_fprop", x, wt, None, y, slab, n, h, w, c, k, 3, 3, 1, 1, 1, 0),
+                            lambda: W.call("rr_conv_wino_fprop", x, u_f, None, y, slab, ws, wsb, n, h, w, c, k, 0, 0)),
+            "dgrad": (lambda: _C.call("rr_conv_dgrad_s1", dy, flip, dx, *geo, 0),
+                      lambda: W.call("rr_conv_wino_fprop", dy, u_d, None, dx, None, ws, wsb, n, h, w, k, c, 0, 0)),
+            "dgrad accumulating": (lambda: _C.call("rr_conv_dgrad_s1", dy, flip, dx, *geo, 1),
+                                   lambda: W.call("rr_conv_wino_fprop", dy, u_d, None, dx, None, ws, wsb, n, h, w, k, c, 0, 1)),
+            "dgrad+bnsum": (lambda: _C.call("rr_conv_dgrad_s1_bnsum", dy, flip, dx, *geo, 0, py, None, mean, invstd, msc, msh, slab, sums),
+                            lambda: W.call("rr_conv_wino_dgrad_bnsum", dy, u_d, dx, ws, wsb, n, h, w, c, k, 0, py, None, mean, invstd, msc, msh,
+                                           slab, sums)),
+        }
+        tiles = n * ((h + 1) // 2) * ((w + 1) // 2)
+        t_in = timeit(lambda: W.call("rr_wino_input", x, ws, n, h, w, c))
+        t_gemm = timeit(lambda: W.call("rr_wino_gemm", ws, u_f, ws[16 * tiles * c:], tiles, c, k))
+        t_filt = timeit(lambda: W.call("rr_wino_filter", wt, u_f, k, c))
+        gflop = 2.0 * 16 * tiles * c * k / 1e9
+        print("N%d C%d %dx%d K%d (%d output pixels) | stages: input transform %.3f ms (%.2f TB/s), GEMMs %.3f ms (%.1f TF), filter transform %.3f ms"
+              % (n, c, h, w, k, n * h * w, t_in, (n * h * w * c + 16.0 * tiles * c) * 4 / t_in / 1e9, t_gemm, gflop / t_gemm, t_filt), flush=True)
+        for name, (direct, wino) in arms.items():
+            td, tw = [], []
+            for _ in range(rounds):
+                td.append(timeit(direct))
+                tw.append(timeit(wino))
+            md, mw = sum(td) / rounds, sum(tw) / rounds
+            sd, sw = max(td) - min(td), max(tw) - min(tw)
+            verdict = "wino wins" if md - mw > 2 * max(sd, sw) else ("direct wins" if mw - md > 2 * max(sd, sw) else "inside the spread")
+            extra = "" if name != "fprop+stats" else " | output transform %.3f ms" % (mw - t_in - t_gemm)
+            print("   %-20s direct %.3f ms (spread %.3f) | wino %.3f ms (spread %.3f) | %+.3f ms: %s%s"
+                  % (name, md, sd, mw, sw, mw - md, verdict, extra), flush=True)
+
+
 if "--rows" in sys.argv:
     bench_rows()
+    sys.exit(0)
+if "--wino" in sys.argv:
+    bench_wino()
     sys.exit(0)
 only = [int(a) for a in sys.argv[1:]]
 for i, (n, c, h, w, k, r, st) in enumerate(SHAPES):
