@@ -49,7 +49,29 @@ typedef struct ihipStream_t *hipStream_t;
  * rr_conv_wino_dgrad_bnsum: rr_conv_dgrad_s1_bnsum's contract on this route: dx [n,h,wd,c] (+)= the data gradient of dy
  *   [n,h,wd,k] (u from wt), and sums [2][c] (zeroed by the caller) receive what rr_bn_bwd_reduce(dx, prod_z, prod_y, ...) returns
  *   (same mask rule rr_bn_affine, same product order); slab: rr_conv_stat_slab_bytes(n, h, wd, c) bytes of scratch.
- * rr_wino_input / rr_wino_gemm: the first two stages alone (benchmarks: per-stage times). */
+ * rr_wino_input / rr_wino_gemm: the first two stages alone (benchmarks: per-stage times).
+ *
+ * ---- The weight gradient of such a layer as F(3x3,2x2): dg = Gt [ sum over tiles (A dy_tile At) . (Bt d B) ] G, A = At^T,
+ * again 16 instead of 36 multiplications per tile and channel pair.  x [n,h,wd,c], dy [n,h,wd,k], dw [k][3][3][c]; C and K
+ * multiples of 4 above 32, every tensor and every slice of V and W below 2 GiB.  Five launches:
+ *   input transform   V[16][T][c] = Bt d B                      (the forward route's kernel)
+ *   dy transform      W[16][T][k] = A dy_tile At                pixels outside dy (ragged last tile row / column) read 0
+ *   zero fill         S[k][16][c] = 0
+ *   sixteen GEMMs     S[ko][i][c] += sum_t W[i][t][ko] * V[i][t][c]   (one launch of the weight-gradient kernel, the tiles split
+ *                                                                     like rr_conv_wgrad splits its pixels: float atomics into S)
+ *   dw transform      dw += Gt S G                              a plain read-modify-write of the running gradient
+ * Results equal rr_conv_wgrad's up to fp32 rounding of a DIFFERENT arithmetic: exact cancellation and the sign of zeros are not
+ * preserved; a non-finite element of dy at filter ko (of x at channel c) stays inside dw[ko] (dw[.][.][.][c]) but may reach all
+ * nine taps there.  Like rr_conv_wgrad's, the sum order of the split partials varies from run to run.
+ *
+ * rr_conv_wino_wgrad_plan: wino_wgrad_plan of csrc/conv_plan.h; arguments as rr_conv_wino_plan, flags: 1 a gated launch
+ *   (rr_conv_wgrad_unless; refused).  plan[RR_WINO_WGRAD_PLAN_INTS] = {take (0: rr_conv_wgrad keeps the launch; never an error), the
+ *   pixel floor is the only reason not to, tiles T (two ints: low 31 bits, high), PIPE of the GEMM kernel (3: T % 32 == 0, else 1),
+ *   splits of T, K-steps per split, GEMM workgroups, workspace bytes (two ints: low 31 bits, high)}.
+ * rr_conv_wino_wgrad_ws_bytes: V + W + S of one launch (16 * T * (c + k) + 16 * k * c floats).
+ * rr_conv_wino_wgrad: dw += the weight gradient; ws: ws_bytes >= rr_conv_wino_wgrad_ws_bytes.  Like the forward entry points it does
+ *   not apply the plan's pixel floor.
+ * rr_wino_dy / rr_wino_wgrad_gemm / rr_wino_dw: the stages alone (benchmarks: per-stage times); rr_wino_wgrad_gemm adds into s. */
 #define RR_WINO_PLAN_INTS 11
 int rr_conv_wino_plan(int math, int n, int h, int wd, int c, int k, int r, int s, int stride, int pad_h, int pad_w, int out_h,
                       int out_w, int flags, int *plan);
@@ -64,6 +86,15 @@ int rr_conv_wino_dgrad_bnsum(const float *dy, const float *u, float *dx, float *
                              double *sums, hipStream_t stream);
 int rr_wino_input(const float *x, float *v, int n, int h, int wd, int c, hipStream_t stream);
 int rr_wino_gemm(const float *v, const float *u, float *m, long tiles, int c, int k, hipStream_t stream);
+#define RR_WINO_WGRAD_PLAN_INTS 10
+int rr_conv_wino_wgrad_plan(int math, int n, int h, int wd, int c, int k, int r, int s, int stride, int pad_h, int pad_w, int out_h,
+                            int out_w, int flags, int *plan);
+size_t rr_conv_wino_wgrad_ws_bytes(int n, int h, int wd, int c, int k);
+int rr_conv_wino_wgrad(const float *x, const float *dy, float *dw, float *ws, size_t ws_bytes, int n, int h, int wd, int c, int k,
+                       hipStream_t stream);
+int rr_wino_dy(const float *dy, float *w, int n, int h, int wd, int k, hipStream_t stream);
+int rr_wino_wgrad_gemm(const float *v, const float *w, float *s, long tiles, int c, int k, hipStream_t stream);
+int rr_wino_dw(const float *s, float *dw, int k, int c, hipStream_t stream);
 
 #ifdef __cplusplus
 }

@@ -818,6 +818,8 @@ struct WgradArgs {
     int mt, nt;       // tiles along K and C
     const int *gate;  // rr_conv_wgrad_unless: the launch returns when *gate <= gate_max (ConvArgs::gate); null: no gate
     int gate_max;
+    long slice_x, slice_dy;   // BATCH instantiations (the sixteen GEMMs of the Winograd weight gradient in one launch): the "tap" moves
+                      // x and dy on by so many elements; every slice is addressed from its own base, so each stays below 2 GiB
 };
 
 // BMW x BN output tile (ko x c).  128x128: 2x2 waves of 64x64; 128x32 / 32x128: 4 waves of one 32x32;
@@ -827,10 +829,14 @@ struct WgradArgs {
 // the tensor offsets go through the buffer instruction's scalar offset, and the per-lane work per load is one add, one
 // compare, one select; ONE LDS image per operand and two barriers inside the last MFMA group (three workgroups per CU,
 // like conv_igemm_kernel<PIPE 2>).
-template <int BMW, int BN, bool A_SCALAR, bool B_SCALAR, int PIPE>
+// BATCH (rr_conv_wino_wgrad_gemm): sixteen independent GEMMs dw[ko][i][c] += sum_t dy_i[t][ko] * x_i[t][c] of one geometry
+// (N = H = P = 1, W = Q = T, no shift, no padding): the "tap" i selects the operand slices (WgradArgs::slice_*) instead of a
+// spatial shift.  The tiles of one (slice, split) are neighbours in the logical id, so that they meet in one XCD's L2.
+template <int BMW, int BN, bool A_SCALAR, bool B_SCALAR, int PIPE, bool BATCH = false>
 __global__ __launch_bounds__(256, PIPE == 3 ? 3 : 1) void conv_wgrad_kernel(const WgradArgs a)
 {
     static_assert(PIPE == 0 || PIPE == 1 || PIPE == 3, "conv_wgrad_kernel: PIPE 0, 1 or 3");
+    static_assert(!BATCH || (PIPE != 0 && BMW == 128 && BN == 128 && !A_SCALAR && !B_SCALAR), "conv_wgrad_kernel: BATCH on the pipelined 128x128 kernels");
     if (a.gate != nullptr && *a.gate <= a.gate_max) return;
     constexpr int TILES = (BMW / 32) * (BN / 32);
     constexpr int KS = TILES == 1 ? 4 : 1;                       // waves splitting K
@@ -849,13 +855,21 @@ __global__ __launch_bounds__(256, PIPE == 3 ? 3 : 1) void conv_wgrad_kernel(cons
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int wk = KS > 1 ? wave : 0;
     const int wm = KS > 1 ? 0 : wave / WN, wn = KS > 1 ? 0 : wave % WN;
-    const int RS = a.R * a.S;
+    const int RS = BATCH ? 16 : a.R * a.S;
     int logical = xcd_remap(blockIdx.x, gridDim.x);
-    const int tap = logical % RS; logical /= RS;
-    const int n_tile = logical % a.nt; logical /= a.nt;
-    const int m_tile = logical % a.mt;
-    const int split = logical / a.mt;
-    const int r = tap / a.S, s = tap - r * a.S;
+    int tap, n_tile, m_tile, split;
+    if constexpr (BATCH) {
+        n_tile = logical % a.nt; logical /= a.nt;
+        m_tile = logical % a.mt; logical /= a.mt;
+        tap = logical % RS;
+        split = logical / RS;
+    } else {
+        tap = logical % RS; logical /= RS;
+        n_tile = logical % a.nt; logical /= a.nt;
+        m_tile = logical % a.mt;
+        split = logical / a.mt;
+    }
+    const int r = BATCH ? 0 : tap / a.S, s = BATCH ? 0 : tap - r * a.S;
     const int ko0 = m_tile * BMW, c0 = n_tile * BN;
     const int total_chunks = (a.M + BK - 1) / BK;
     const int kc_begin = split * a.chunks_per_split;
@@ -1007,14 +1021,14 @@ __global__ __launch_bounds__(256, PIPE == 3 ? 3 : 1) void conv_wgrad_kernel(cons
         void *q = reinterpret_cast<void *>(((unsigned long long)hi << 32) | lo);
         return __builtin_amdgcn_make_buffer_rsrc(q, 0, __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000);
     };
-    const __amdgpu_buffer_rsrc_t rs_dy = make_srd(a.dy, (long)a.M * a.K * 4);
+    const __amdgpu_buffer_rsrc_t rs_dy = make_srd(BATCH ? a.dy + (long)tap * a.slice_dy : a.dy, (long)a.M * a.K * 4);
     // Uniform row walk: the descriptor of x starts pad_w pixels BEFORE the tensor, so that the per-lane
     // offset (lq*stride + s) * C is never negative.  A negative (wrapped) lane offset is out of range for the
     // hardware's bounds check even when the scalar offset brings the address back inside the tensor — the left-most
     // tap column then silently lost the pixel in front of every K-step that does not start a row (Q > 32).  Lanes
     // whose pixel really lies outside the row are masked by the iw test below and never dereference the shifted base.
     const long x_shift = ALIGNED ? (long)a.pad_w * a.C * 4 : 0;
-    const __amdgpu_buffer_rsrc_t rs_x = make_srd(reinterpret_cast<const float *>(reinterpret_cast<const char *>(a.x) - x_shift),
+    const __amdgpu_buffer_rsrc_t rs_x = make_srd(reinterpret_cast<const float *>(reinterpret_cast<const char *>(BATCH ? a.x + (long)tap * a.slice_x : a.x) - x_shift),
                                                  (long)a.N * a.H * a.W * a.C * 4 + x_shift);
     constexpr unsigned OOB = 0xFFFFFFF0u;
     // A rows: byte offset of row j at K-step 0 of this split is a_off[j]; every K-step adds BK*K*4 (scalar)
@@ -1296,6 +1310,23 @@ int rr_conv_wino_gemm(const float *v, const float *u, float *m, long tiles, int 
     if (bn == 128)
         return rr_launch(conv_igemm_kernel<128, 0, false, BK, 2, false, false, true>, grid, 256, igemm_lds(128, false, 1), stream, a, name);
     return rr_launch(conv_igemm_kernel<64, 0, false, BK, 2, false, false, true>, grid, 256, igemm_lds(64, false, 1), stream, a, name);
+}
+
+// The sixteen GEMMs of the Winograd weight gradient in one launch: s[ko][i][c] += sum_t w[i][t][ko] * v[i][t][c] — the pipelined
+// weight-gradient kernel in batch mode, float atomics into s (zeroed by the caller).  rr_plan::wino_wgrad_gemm_plan sizes the launch.
+int rr_conv_wino_wgrad_gemm(const float *v, const float *w, float *s, long tiles, int c, int k, hipStream_t stream, const char *name)
+{
+    RR_CHECK_ARG(tiles > 0 && c > 32 && k > 32 && c % 4 == 0 && k % 4 == 0 && tiles * c * 4 < (1l << 31) && tiles * k * 4 < (1l << 31)
+                 && 16l * k * c * 4 < (1l << 31), "%s: bad GEMM geometry", name);
+    const rr_plan::WinoWgradGemm pl = rr_plan::wino_wgrad_gemm_plan(tiles, c, k);
+    WgradArgs a{};
+    a.x = v; a.dy = w; a.dw = s; a.zero = zero_page();
+    a.N = 1; a.H = 1; a.W = (int)tiles; a.C = c; a.K = k; a.R = 1; a.S = 1;
+    a.P = 1; a.Q = (int)tiles; a.stride = 1;
+    a.M = (int)tiles; a.mt = pl.mt; a.nt = pl.nt; a.chunks_per_split = pl.per_split;
+    a.slice_x = tiles * c; a.slice_dy = tiles * k;
+    if (pl.pipe == 3) return rr_launch(conv_wgrad_kernel<128, 128, false, false, 3, true>, dim3(pl.grid), 256, pl.lds, stream, a, name);
+    return rr_launch(conv_wgrad_kernel<128, 128, false, false, 1, true>, dim3(pl.grid), 256, pl.lds, stream, a, name);
 }
 
 int rr_conv_colstats(const float *y, long M, int C, double *slab, hipStream_t stream, const char *name)

@@ -49,6 +49,9 @@ int rr_conv_colstats(const float *y, long M, int C, double *slab, hipStream_t st
 // the sixteen GEMMs of the Winograd route (csrc/conv_wino.hip) on conv.hip's forward kernel: m[i][t][ko] = sum_c v[i][t][c] * u[i][ko][c]
 int rr_conv_wino_gemm(const float *v, const float *u, float *m, long tiles, int c, int k, hipStream_t stream, const char *name);
 
+// the sixteen GEMMs of its weight gradient on conv.hip's weight-gradient kernel: s[ko][i][c] += sum_t w[i][t][ko] * v[i][t][c]
+int rr_conv_wino_wgrad_gemm(const float *v, const float *w, float *s, long tiles, int c, int k, hipStream_t stream, const char *name);
+
 // zero fill on one side of the rows route's gate (csrc/conv_rows.hip): runs iff (*count <= max_rows) == (when_rows != 0)
 int rr_gated_zero(float *p, size_t bytes, const int *count, int max_rows, int when_rows, hipStream_t stream, const char *name);
 

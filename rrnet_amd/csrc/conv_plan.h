@@ -439,4 +439,57 @@ inline WinoPlan wino_plan(int math, const ConvGeom &g, const ConvFlags &f)
     return p;
 }
 
+// ---- the Winograd F(3x3,2x2) weight gradient of the same layers (rr_conv_wino_wgrad): input transform of x, transform
+// of dy, sixteen GEMMs S[i] = W[i]^T V[i] over the T tiles in one launch of conv.hip's weight-gradient kernel (batch mode), and
+// dw += Gt S G.  Additive: a launch it does not take stays with wgrad_plan.
+constexpr long WINO_WGRAD_MIN_PIXELS = 65536;     // the gate's floor in pixels n*p*q: the 128 x 128 and 256 x 256 levels of the headline step
+
+// the GEMM launch: 128 x 128 tiles of (filters x channels) x 16 slices, the T tiles of the map split like wgrad_plan splits its pixels
+struct WinoWgradGemm { int mt, nt, pipe, splits, per_split, grid, lds; };
+inline WinoWgradGemm wino_wgrad_gemm_plan(long tiles, int c, int k)
+{
+    WinoWgradGemm p{};
+    p.mt = cdiv(k, 128); p.nt = cdiv(c, 128);
+    p.pipe = tiles % BK == 0 ? 3 : 1;           // PIPE 3: every K-step of 32 tiles lies inside the one "row" of T
+    const WgradFill fill = p.pipe == 3 ? WGRAD_F32_PIPE3 : WGRAD_F32;
+    p.splits = pixel_splits(p.mt * p.nt * 16, cdiv(tiles, BK), fill.slots, fill.min_chunks, &p.per_split);
+    p.grid = p.mt * p.nt * 16 * p.splits;
+    p.lds = 4 * (p.pipe == 3 ? 1 : 2) * (BK * 128 + BK * 128);
+    return p;
+}
+
+struct WinoWgradPlan {
+    const char *refuse;   // non-null: the route does not take the launch, and why
+    int floor_only;       // ... and the pixel floor is the only reason (the entry points run such a shape: tests, benchmarks)
+    int th, tw;           // tiles along h and w
+    long tiles;           // T = n * th * tw
+    WinoWgradGemm gemm;
+    long ws_bytes;        // V [16][T][c] + W [16][T][k] + S [k][16][c]
+};
+
+// g: the layer's geometry (x's map, c / k its channels / filters); gated: the launch carries a gate (rr_conv_wgrad_unless)
+inline WinoWgradPlan wino_wgrad_plan(int math, const ConvGeom &g, bool gated)
+{
+    WinoWgradPlan p{};
+    const long G2 = 1l << 31;
+#define RR_PLAN_REFUSE(cond, why) do { if (cond) { p.refuse = why; return p; } } while (0)
+    RR_PLAN_REFUSE(!(g.n > 0 && g.h > 0 && g.w > 0 && g.c > 0 && g.k > 0), "bad dims");
+    RR_PLAN_REFUSE(math != MATH_F32, "fp32 arithmetic only");
+    RR_PLAN_REFUSE(!(g.r == 3 && g.s == 3 && g.stride == 1 && g.pad_h == 1 && g.pad_w == 1), "3x3, stride 1, pad 1 only");
+    RR_PLAN_REFUSE(g.out_h > 0 || g.out_w > 0, "no explicit output size");
+    RR_PLAN_REFUSE(!(g.c % 4 == 0 && g.k % 4 == 0 && g.c > 32 && g.k > 32), "C and K must be multiples of 4 above 32");
+    RR_PLAN_REFUSE(gated, "no gated launch");
+    const long M = (long)g.n * g.h * g.w;
+    p.th = (g.h + 1) / 2; p.tw = (g.w + 1) / 2;
+    p.tiles = (long)g.n * p.th * p.tw;
+    // every tensor, and every slice of V and W (each addressed from its own base), through 32-bit byte offsets
+    RR_PLAN_REFUSE(!(M * g.c * 4 < G2 && M * g.k * 4 < G2 && 16l * g.c * g.k * 4 < G2 && p.tiles * g.c * 4 < G2 && p.tiles * g.k * 4 < G2),
+                   "tensors must stay below 2 GiB");
+    p.gemm = wino_wgrad_gemm_plan(p.tiles, g.c, g.k);
+    p.ws_bytes = (16l * p.tiles * ((long)g.c + g.k) + 16l * g.k * g.c) * 4;
+    if (M < WINO_WGRAD_MIN_PIXELS) { p.refuse = "fewer pixels than the route's floor"; p.floor_only = 1; }
+#undef RR_PLAN_REFUSE
+    return p;
+}
+
 }  // namespace rr_plan

@@ -13,6 +13,9 @@
 // runs once per filter and optimizer step.  A lane owns four channels (16 bytes) of a tile; no atomics, no workgroup waits
 // for another: bit-reproducible.  The file is compiled with -ffp-contract=off (csrc/build.py): the filter cache is a function
 // of the parameters alone and the link's product chains are rounded term by term like the direct kernel's.
+// The weight gradient of the same layers (rr_conv_wino_wgrad): wino_input_kernel, wino_dy_kernel, the sixteen GEMMs over the
+// tiles in one launch of conv.hip's weight-gradient kernel (rr_conv_wino_wgrad_gemm: its split partials meet in float atomics, like
+// the direct weight gradient's), wino_dw_kernel.
 #include "conv_launch.h"
 #include "rrnet_hip_wino.h"
 
@@ -114,6 +117,83 @@ __global__ __launch_bounds__(256) void wino_input_kernel(const float *x, float *
             *reinterpret_cast<f32x4 *>(vp + (4 * a + 1) * bs) = m[a][1] + m[a][2];
             *reinterpret_cast<f32x4 *>(vp + (4 * a + 2) * bs) = m[a][2] - m[a][1];
             *reinterpret_cast<f32x4 *>(vp + (4 * a + 3) * bs) = m[a][1] - m[a][3];
+        }
+    }
+}
+
+// ---- weight gradient: dg = Gt [ sum_tiles (A dy_tile At) . (Bt d B) ] G, A = At^T = rows (1,0), (1,1), (1,-1), (0,-1).
+// dy transform: w[4a + b][t][ko] = (A dy_tile At)[a][b], dy_tile the 2x2 pixels (2 th + i, 2 tw + j) of tile t; those outside the map (the
+// ragged last tile row / column of an odd map) read 0 through an out-of-range buffer offset.  Thread = (tile, filter quad): adds only.
+__global__ __launch_bounds__(256) void wino_dy_kernel(const float *dy, float *w, int H, int W, int K, int TH, int TW, long tiles, long dy_bytes)
+{
+    const __amdgpu_buffer_rsrc_t rs = wino_srd(dy, dy_bytes);
+    const int K4 = K / 4;
+    const long total = tiles * K4;
+    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        const long t = idx / K4;
+        const int k = (int)(idx - t * K4) * 4;
+        const int tw = (int)(t % TW);
+        const long rest = t / TW;
+        const int th = (int)(rest % TH);
+        const int n = (int)(rest / TH);
+        f32x4 d[2][2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int oh = 2 * th + i, ow = 2 * tw + j;
+                const bool in = oh < H && ow < W;
+                const unsigned off = in ? (unsigned)((((n * H + oh) * W + ow) * K + k) * 4) : OOB;
+                d[i][j] = wino_load(rs, off);
+            }
+        f32x4 m[4][2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            m[0][j] = d[0][j];
+            m[1][j] = d[0][j] + d[1][j];
+            m[2][j] = d[0][j] - d[1][j];
+            m[3][j] = -d[1][j];
+        }
+        float *wp = w + t * K + k;
+        const long bs = tiles * K;
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            *reinterpret_cast<f32x4 *>(wp + (4 * a + 0) * bs) = m[a][0];
+            *reinterpret_cast<f32x4 *>(wp + (4 * a + 1) * bs) = m[a][0] + m[a][1];
+            *reinterpret_cast<f32x4 *>(wp + (4 * a + 2) * bs) = m[a][0] - m[a][1];
+            *reinterpret_cast<f32x4 *>(wp + (4 * a + 3) * bs) = -m[a][1];
+        }
+    }
+}
+
+// dw transform: dw[ko][r][s][c] += (Gt S G)[r][s], S[a][b] = s[ko][4a + b][c].  Thread = (filter, channel quad); a plain
+// read-modify-write of the running gradient, ordered behind the GEMM on its stream.
+__global__ __launch_bounds__(256) void wino_dw_kernel(const float *s, float *dw, int K, int C)
+{
+    const int C4 = C / 4;
+    const long total = (long)K * C4;
+    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        const long ko = idx / C4;
+        const int c = (int)(idx - ko * C4) * 4;
+        const float *sp = s + ko * 16 * C + c;
+        f32x4 S[4][4], t[3][4];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) S[i >> 2][i & 3] = *reinterpret_cast<const f32x4 *>(sp + (long)i * C);
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            t[0][b] = S[0][b] + 0.5f * (S[1][b] + S[2][b]);
+            t[1][b] = 0.5f * (S[1][b] - S[2][b]);
+            t[2][b] = 0.5f * (S[1][b] + S[2][b]) + S[3][b];
+        }
+        float *dp = dw + ko * 9 * C + c;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            f32x4 *d0 = reinterpret_cast<f32x4 *>(dp + (long)(3 * r + 0) * C);
+            f32x4 *d1 = reinterpret_cast<f32x4 *>(dp + (long)(3 * r + 1) * C);
+            f32x4 *d2 = reinterpret_cast<f32x4 *>(dp + (long)(3 * r + 2) * C);
+            *d0 += t[r][0] + 0.5f * (t[r][1] + t[r][2]);
+            *d1 += 0.5f * (t[r][1] - t[r][2]);
+            *d2 += 0.5f * (t[r][1] + t[r][2]) + t[r][3];
         }
     }
 }
@@ -276,11 +356,35 @@ int run_filter(const WinoFilterRow *table, const WinoFilterRow &one, int nfilter
     return RR_OK;
 }
 
-int run_input(const float *x, float *v, int n, int h, int wd, int c, const rr_plan::WinoPlan &pl, hipStream_t stream, const char *name)
+int run_input(const float *x, float *v, int n, int h, int wd, int c, int th, int tw, long tiles, hipStream_t stream, const char *name)
 {
-    hipLaunchKernelGGL(wino_input_kernel, dim3(grid_for(pl.tiles * (c / 4))), dim3(256), 0, stream, x, v, h, wd, c, pl.th, pl.tw, pl.tiles,
+    hipLaunchKernelGGL(wino_input_kernel, dim3(grid_for(tiles * (c / 4))), dim3(256), 0, stream, x, v, h, wd, c, th, tw, tiles,
                        (long)n * h * wd * c * 4);
     RR_CHECK_LAUNCH(name);
+    return RR_OK;
+}
+
+int run_dy(const float *dy, float *w, int n, int h, int wd, int k, int th, int tw, long tiles, hipStream_t stream, const char *name)
+{
+    hipLaunchKernelGGL(wino_dy_kernel, dim3(grid_for(tiles * (k / 4))), dim3(256), 0, stream, dy, w, h, wd, k, th, tw, tiles,
+                       (long)n * h * wd * k * 4);
+    RR_CHECK_LAUNCH(name);
+    return RR_OK;
+}
+
+int run_dw(const float *s, float *dw, int k, int c, hipStream_t stream, const char *name)
+{
+    hipLaunchKernelGGL(wino_dw_kernel, dim3(grid_for((long)k * (c / 4))), dim3(256), 0, stream, s, dw, k, c);
+    RR_CHECK_LAUNCH(name);
+    return RR_OK;
+}
+
+// the weight gradient's shape rule as the entry points apply it: wino_wgrad_plan without its pixel floor
+int checked_wgrad_plan(const char *name, int n, int h, int wd, int c, int k, size_t ws_bytes, rr_plan::WinoWgradPlan *pl)
+{
+    *pl = rr_plan::wino_wgrad_plan(rr_plan::MATH_F32, {n, h, wd, c, k, 3, 3, 1, 1, 1, 0, 0}, false);
+    RR_CHECK_ARG(pl->refuse == nullptr || pl->floor_only, "%s: %s", name, pl->refuse);
+    RR_CHECK_ARG(ws_bytes >= (size_t)pl->ws_bytes, "%s: workspace of %ld bytes needed (rr_conv_wino_wgrad_ws_bytes)", name, pl->ws_bytes);
     return RR_OK;
 }
 
@@ -297,7 +401,7 @@ int run_route(const char *name, const float *x, const float *u, float *y, float 
               const rr_plan::WinoPlan &pl, WinoOutArgs &o, bool link, hipStream_t stream)
 {
     float *v = ws, *m = ws + 16 * pl.tiles * c;
-    if (int rc = run_input(x, v, n, h, wd, c, pl, stream, name)) return rc;
+    if (int rc = run_input(x, v, n, h, wd, c, pl.th, pl.tw, pl.tiles, stream, name)) return rc;
     if (int rc = rr_conv_wino_gemm(v, u, m, pl.tiles, c, k, stream, name)) return rc;
     o.m = m; o.y = y; o.y_bytes = (long)n * h * wd * k * 4; o.H = h; o.W = wd; o.K = k; o.TH = pl.th; o.TW = pl.tw; o.tiles = pl.tiles; o.per_wg = pl.tiles_per_wg;
     if (link) hipLaunchKernelGGL(wino_output_kernel<true>, dim3(pl.out_x, pl.out_y), dim3(256), 0, stream, o);
@@ -346,7 +450,7 @@ extern "C" int rr_wino_input(const float *x, float *v, int n, int h, int wd, int
     rr_plan::WinoPlan pl;
     if (int rc = checked_plan("rr_wino_input", n, h, wd, c, c, {}, (size_t)-1, &pl)) return rc;
     RR_CHECK_ARG(x != nullptr && v != nullptr, "rr_wino_input: null argument");
-    return run_input(x, v, n, h, wd, c, pl, stream, "rr_wino_input");
+    return run_input(x, v, n, h, wd, c, pl.th, pl.tw, pl.tiles, stream, "rr_wino_input");
 }
 
 extern "C" int rr_wino_gemm(const float *v, const float *u, float *m, long tiles, int c, int k, hipStream_t stream)
@@ -384,4 +488,56 @@ extern "C" int rr_conv_wino_dgrad_bnsum(const float *dy, const float *u, float *
     o.bs_y = prod_y; o.bs_z = prod_z; o.bs_mean = prod_mean; o.bs_invstd = prod_invstd; o.bs_msc = prod_mask_scale; o.bs_msh = prod_mask_shift;
     if (int rc = run_route(name, dy, u, dx, ws, n, h, wd, k, c, pl, o, true, stream)) return rc;
     return rr_bn_reduce_slab(slab, pl.out_x, c, sums, stream);
+}
+
+extern "C" int rr_conv_wino_wgrad_plan(int math, int n, int h, int wd, int c, int k, int r, int s, int stride, int pad_h, int pad_w, int out_h,
+                                       int out_w, int flags, int *plan)
+{
+    RR_CHECK_ARG(plan != nullptr, "rr_conv_wino_wgrad_plan: bad arguments");
+    const rr_plan::WinoWgradPlan pl = rr_plan::wino_wgrad_plan(math, {n, h, wd, c, k, r, s, stride, pad_h, pad_w, out_h, out_w}, (flags & 1) != 0);
+    const int out[RR_WINO_WGRAD_PLAN_INTS] = {pl.refuse == nullptr, pl.floor_only, (int)(pl.tiles & 0x7fffffff), (int)(pl.tiles >> 31), pl.gemm.pipe,
+                                              pl.gemm.splits, pl.gemm.per_split, pl.gemm.grid, (int)(pl.ws_bytes & 0x7fffffff), (int)(pl.ws_bytes >> 31)};
+    for (int i = 0; i < RR_WINO_WGRAD_PLAN_INTS; ++i) plan[i] = out[i];
+    return RR_OK;
+}
+
+extern "C" size_t rr_conv_wino_wgrad_ws_bytes(int n, int h, int wd, int c, int k)
+{
+    if (n <= 0 || h <= 0 || wd <= 0 || c <= 0 || k <= 0) return 0;
+    return ((size_t)16 * n * ((h + 1) / 2) * ((wd + 1) / 2) * ((size_t)c + k) + (size_t)16 * k * c) * sizeof(float);
+}
+
+extern "C" int rr_wino_dy(const float *dy, float *w, int n, int h, int wd, int k, hipStream_t stream)
+{
+    rr_plan::WinoWgradPlan pl;
+    if (int rc = checked_wgrad_plan("rr_wino_dy", n, h, wd, k, k, (size_t)-1, &pl)) return rc;
+    RR_CHECK_ARG(dy != nullptr && w != nullptr, "rr_wino_dy: null argument");
+    return run_dy(dy, w, n, h, wd, k, pl.th, pl.tw, pl.tiles, stream, "rr_wino_dy");
+}
+
+extern "C" int rr_wino_wgrad_gemm(const float *v, const float *w, float *s, long tiles, int c, int k, hipStream_t stream)
+{
+    RR_CHECK_ARG(v != nullptr && w != nullptr && s != nullptr, "rr_wino_wgrad_gemm: null argument");
+    return rr_conv_wino_wgrad_gemm(v, w, s, tiles, c, k, stream, "rr_wino_wgrad_gemm");
+}
+
+extern "C" int rr_wino_dw(const float *s, float *dw, int k, int c, hipStream_t stream)
+{
+    RR_CHECK_ARG(s != nullptr && dw != nullptr && k > 0 && c > 0 && c % 4 == 0, "rr_wino_dw: bad arguments");
+    return run_dw(s, dw, k, c, stream, "rr_wino_dw");
+}
+
+extern "C" int rr_conv_wino_wgrad(const float *x, const float *dy, float *dw, float *ws, size_t ws_bytes, int n, int h, int wd, int c, int k,
+                                  hipStream_t stream)
+{
+    const char *name = "rr_conv_wino_wgrad";
+    rr_plan::WinoWgradPlan pl;
+    if (int rc = checked_wgrad_plan(name, n, h, wd, c, k, ws_bytes, &pl)) return rc;
+    RR_CHECK_ARG(x != nullptr && dy != nullptr && dw != nullptr && ws != nullptr, "%s: null argument", name);
+    float *v = ws, *w = v + 16 * pl.tiles * c, *s = w + 16 * pl.tiles * k;
+    if (int rc = run_input(x, v, n, h, wd, c, pl.th, pl.tw, pl.tiles, stream, name)) return rc;
+    if (int rc = run_dy(dy, w, n, h, wd, k, pl.th, pl.tw, pl.tiles, stream, name)) return rc;
+    RR_CHECK_HIP(rr_zero2(s, sizeof(float) * 16 * (size_t)k * c, nullptr, 0, stream), name);
+    if (int rc = rr_conv_wino_wgrad_gemm(v, w, s, pl.tiles, c, k, stream, name)) return rc;
+    return run_dw(s, dw, k, c, stream, name);
 }

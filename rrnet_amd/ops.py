@@ -841,7 +841,7 @@ _WINO = _C.Family("rrnet_hip_wino.h")
 _CONV_WINO = os.environ.get("RR_CONV_WINO", "1") != "0"
 _WINO_BELOW_FLOOR = False       # test switch: the route also where the plan's pixel floor is its only objection (tests/test_conv_wino_gpu.py)
 _WINO_TAKES = {}                # plan arguments -> the plan's answer (take, the floor is the only reason not to)
-_WINO_PLAN_FN = []
+_WINO_PLAN_FN = {}              # plan entry -> its typed function
 _WINO_WS = {}                   # (device, stream) -> the grow-only workspace V + M of the launches enqueued there
 FLAT_BUFFERS = weakref.WeakSet()     # the FlatParams that keep transformed filters (rrnet_amd/flat.py registers itself)
 
@@ -854,22 +854,28 @@ def wino_takes(n, h, wd, c, k, r, s, stride, pad, bias=False, relu=False, stats=
     key = (n, h, wd, c, k, r, s, stride, pad[0], pad[1], int(bias) | int(relu) << 1 | int(stats) << 2 | int(accumulate) << 3 | int(link) << 8)
     hit = _WINO_TAKES.get(key)
     if hit is None:
-        if not _WINO_PLAN_FN:
-            # typed from the header like every entry, but asked past _C.fn: a shape predicate launches nothing, and how often the host
-            # asks it is not part of what a call computes (the launch records of tests/conv_route_cases.py)
-            f, (sig, _) = getattr(_C.lib(), "rr_conv_wino_plan"), _C.declared("rr_conv_wino_plan")
-            f.restype, f.argtypes = sig[0], sig[1]
-            _WINO_PLAN_FN.append(f)
         plan = (_C.c_int * 11)()
-        _C.check(_WINO_PLAN_FN[0](MATH_F32, *key[:10], 0, 0, key[10], plan), "rr_conv_wino_plan")
+        _C.check(_wino_plan_fn("rr_conv_wino_plan")(MATH_F32, *key[:10], 0, 0, key[10], plan), "rr_conv_wino_plan")
         hit = _WINO_TAKES[key] = (bool(plan[0]), bool(plan[1]))
     return hit[0] or (hit[1] and _WINO_BELOW_FLOOR)
 
 
-def _wino_ws(device, n, h, wd, c, k):
-    """The workspace of one launch: never allocated per call, grown to the largest layer seen on this stream (the compute stream; the
-    side-stream weight gradients do not come here)."""
-    need = _WINO.call("rr_conv_wino_ws_bytes", n, h, wd, c, k) // 4
+def _wino_plan_fn(entry):
+    # typed from the header like every entry, but asked past _C.fn: a shape predicate launches nothing, and how often the host
+    # asks it is not part of what a call computes (the launch records of tests/conv_route_cases.py)
+    f = _WINO_PLAN_FN.get(entry)
+    if f is None:
+        f, (sig, _) = getattr(_C.lib(), entry), _C.declared(entry)
+        f.restype, f.argtypes = sig[0], sig[1]
+        _WINO_PLAN_FN[entry] = f
+    return f
+
+
+def _wino_ws(device, n, h, wd, c, k, entry="rr_conv_wino_ws_bytes"):
+    """The workspace of one launch: never allocated per call, grown to the largest layer seen on this stream.  The compute stream's
+    block serves the forward and data-gradient launches; the weight gradients of the route (entry: rr_conv_wino_wgrad_ws_bytes) run
+    on functional._wgrad_async's side stream and get a block of their own there."""
+    need = _WINO.call(entry, n, h, wd, c, k) // 4
     key = (device, torch.cuda.current_stream(device).cuda_stream)
     ws = _WINO_WS.get(key)
     if ws is None or ws.numel() < need:
@@ -890,6 +896,26 @@ def _wino_filter(w, flipped, wt=None):
     u = torch.empty(16 * k * c, dtype=torch.float32, device=w.device)
     _WINO.call("rr_wino_filter", src, u, *((c, k) if flipped else (k, c)))
     return u
+
+
+# The weight gradients of the same layers as F(3x3,2x2) (rr_conv_wino_wgrad): conv_wgrad takes the route where
+# rr_conv_wino_wgrad_plan does.  RR_CONV_WINO_WGRAD=0: never taken (an A/B switch of its own: RR_CONV_WINO keeps its meaning).
+_CONV_WINO_WGRAD = os.environ.get("RR_CONV_WINO_WGRAD", "1") != "0"
+_WINO_WGRAD_BELOW_FLOOR = False       # test switch (tests/test_conv_wino_wgrad_gpu.py), as _WINO_BELOW_FLOOR
+_WINO_WGRAD_TAKES = {}
+
+
+def wino_wgrad_takes(n, h, wd, c, k, r, s, stride, pad, explicit_out=False, gated=False):
+    """Does the Winograd route take this fp32 weight-gradient launch?  rr_plan::wino_wgrad_plan's decision, asked once per shape."""
+    if not _CONV_WINO_WGRAD or explicit_out:        # (an explicit output size: the plan refuses it)
+        return False
+    key = (n, h, wd, c, k, r, s, stride, pad[0], pad[1], 0, 0, int(gated))
+    hit = _WINO_WGRAD_TAKES.get(key)
+    if hit is None:
+        plan = (_C.c_int * 10)()
+        _C.check(_wino_plan_fn("rr_conv_wino_wgrad_plan")(MATH_F32, *key, plan), "rr_conv_wino_wgrad_plan")
+        hit = _WINO_WGRAD_TAKES[key] = (bool(plan[0]), bool(plan[1]))
+    return hit[0] or (hit[1] and _WINO_WGRAD_BELOW_FLOOR)
 
 
 def _dgrad_wino(dy, w, out, geo, flops, wt, link=None, z=None):
@@ -1029,6 +1055,14 @@ def conv_wgrad(x, dy, dw, stride=1, pad=(0, 0), explicit_out=False, algo_c=None)
         return dw
     x, dy = f32_of(x), f32_of(dy)            # (bf16-only operands in front of a layer the conv16 weight gradient does not take)
     bf = _bf16_ok(c, k, r, s, x, dy, pixels=dy.shape[0] * dy.shape[2] * dy.shape[3]) if wgrad_16bit_shape(c, k, r, s) else 0
+    if bf == MATH_F32 and wino_wgrad_takes(n, h, wd, c, k, r, s, stride, pad, explicit_out):
+        # the Winograd route; its timer key carries the multiplications it executes, 16 of the direct 36
+        ws = _wino_ws(x.device, n, h, wd, c, k, "rr_conv_wino_wgrad_ws_bytes")
+        tiles = n * ((h + 1) // 2) * ((wd + 1) // 2)
+        used = 4.0 * (16 * tiles * (c + k) + 16 * k * c)        # V + W + S of this launch (the block itself is grow-only), written and read once
+        _launch("conv_wgrad<wino>", flops * 16.0 / 36.0, "rr_conv_wino_wgrad", (x, dy, dw, ws, ws.numel() * 4, n, h, wd, c, k),
+                (n, h, wd, c, k, r, s, stride), 4.0 * (x.numel() + dy.numel() + 2 * dw.numel()) + 2.0 * used, call=_WINO.call)
+        return dw
     sfx, tag, wtail = _math_call(bf, x, dy)
     _launch("conv_wgrad<BN=%d>%s" % (128 if c > 32 else 32, tag), flops, "rr_conv_wgrad" + sfx,
             (x, dy, dw, n, h, wd, c, k, r, s, stride, pad[0], pad[1]) + ((dy.shape[2], dy.shape[3]) if explicit_out else (0, 0)) + wtail,

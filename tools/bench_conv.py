@@ -77,15 +77,49 @@ WINO_SHAPES = [(8, 256, 256, 256, 256), (8, 256, 128, 128, 256), (8, 256, 128, 1
                (8, 384, 32, 32, 384)]       # N, C, H, W, K of the headline step's 3x3 stride-1 layers, largest level first
 
 
-def bench_wino(rounds=3):
+def wino_wgrad_row(n, c, h, w, k, rounds):
+    """One level of --wino: rr_conv_wino_wgrad against rr_conv_wgrad, the arms alternating `rounds` times (mean, spread = max - min), and
+    the route's stages: single measurements taken once before the rounds, not alternated, no spread; the input transform and the zero
+    fill are the remainder."""
+    from rrnet_amd import _C
+    W = ops._WINO
+    tiles = n * ((h + 1) // 2) * ((w + 1) // 2)
+    x = ops.to_nhwc(torch.randn(n, c, h, w, device="cuda"))
+    dy = ops.to_nhwc(torch.randn(n, k, h, w, device="cuda"))
+    dw = ops.zeros_nhwc(k, c, 3, 3, "cuda")
+    wws = ops._wino_ws(x.device, n, h, w, c, k, "rr_conv_wino_wgrad_ws_bytes")
+    v_, w_, s_ = wws, wws[16 * tiles * c:], wws[16 * tiles * (c + k):]
+    W.call("rr_wino_input", x, v_, n, h, w, c)
+    t_dy = timeit(lambda: W.call("rr_wino_dy", dy, w_, n, h, w, k))
+    t_wg = timeit(lambda: W.call("rr_wino_wgrad_gemm", v_, w_, s_, tiles, c, k))
+    t_dw = timeit(lambda: W.call("rr_wino_dw", s_, dw, k, c))
+    td, tw = [], []
+    for _ in range(rounds):
+        td.append(timeit(lambda: _C.call("rr_conv_wgrad", x, dy, dw, n, h, w, c, k, 3, 3, 1, 1, 1, 0, 0)))
+        tw.append(timeit(lambda: W.call("rr_conv_wino_wgrad", x, dy, dw, wws, wws.numel() * 4, n, h, w, c, k)))
+    md, mw = sum(td) / rounds, sum(tw) / rounds
+    sd, sw = max(td) - min(td), max(tw) - min(tw)
+    verdict = "wino wins" if md - mw > 2 * max(sd, sw) else ("direct wins" if mw - md > 2 * max(sd, sw) else "inside the spread")
+    gf = 2.0 * 16 * tiles * c * k / 1e9
+    print("N%d C%d %dx%d K%d (%d pixels) wgrad | direct %.3f ms (spread %.3f, %.1f TF) | wino %.3f ms (spread %.3f) | %+.3f ms: %s | stages: "
+          "dy transform %.3f ms (%.2f TB/s), GEMMs %.3f ms (%.1f TF), dw transform %.3f ms; input transform + zero fill: the rest %.3f ms"
+          % (n, c, h, w, k, n * h * w, md, sd, 2.0 * 9 * n * h * w * c * k / 1e9 / md, mw, sw, mw - md, verdict, t_dy,
+             (n * h * w * k + 16.0 * tiles * k) * 4 / t_dy / 1e9, t_wg, gf / t_wg, t_dw, mw - t_dy - t_wg - t_dw), flush=True)
+
+
+def bench_wino(rounds=3, wgrad_only=False):
     """--wino: the Winograd route (csrc/conv_wino.hip) against the direct kernel at the headline's 3x3 stride-1 levels, per pass
     (fprop with statistics, dgrad, dgrad accumulating, dgrad with the producer's BatchNorm link), the two arms alternating
     `rounds` times: mean and spread (max - min) of each, and the route's stages (input transform, GEMMs; the output transform
     is the rest).  The gate's floor (rr_plan::WINO_MIN_PIXELS) is read off this table: the smallest level at which the route wins
-    by more than twice the larger spread."""
+    by more than twice the larger spread.  The weight-gradient row (rr_conv_wino_wgrad against rr_conv_wgrad) has stages and
+    a floor of its own (rr_plan::WINO_WGRAD_MIN_PIXELS); --wgrad-only prints that row alone."""
     from rrnet_amd import _C
     W = ops._WINO
     for n, c, h, w, k in WINO_SHAPES:
+        wino_wgrad_row(n, c, h, w, k, rounds)
+        if wgrad_only:
+            continue
         x = ops.to_nhwc(torch.randn(n, c, h, w, device="cuda"))
         wt = ops.to_nhwc(torch.randn(k, c, 3, 3, device="cuda") * 0.02)
         dy = ops.to_nhwc(torch.randn(n, k, h, w, device="cuda"))
@@ -136,7 +170,7 @@ if "--rows" in sys.argv:
     bench_rows()
     sys.exit(0)
 if "--wino" in sys.argv:
-    bench_wino()
+    bench_wino(wgrad_only="--wgrad-only" in sys.argv)
     sys.exit(0)
 only = [int(a) for a in sys.argv[1:]]
 for i, (n, c, h, w, k, r, st) in enumerate(SHAPES):
